@@ -13,8 +13,12 @@ Weights, KV cache, logits, arg-max and the token feedback all stay in HBM inside
 Ranks are independent replicas (weak scaling): rank 0 loads the file and the packed weight arena is
 broadcast once over RCCL before the timed region; there is no collective on the data path.
 
-Prints ONE JSON line on rank 0 (see the driver contract); extra keys: roofline, cpu_baseline,
-token_roofline, api_loop, long_context.
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times the
+steps and prints that line (with --dump-outputs DIR it first writes what the last timed step computed
+as DIR/<name>.npy).  --full adds the side measurements after the timed steps, each with runs of its
+own: roofline and per-kernel figures, the other block formats, batched decode, the prompt pass, the
+API loops, the CPU baseline and the PMC passes (extra keys roofline, token_roofline, api_loop*,
+decode_<ftype>, cpu_baseline, ...).
 """
 import argparse
 import json
@@ -91,6 +95,15 @@ def make_prompt(n_vocab, unit):
     import numpy as np
     rng = np.random.default_rng(1000 + unit)
     return [2] + [int(v) for v in rng.integers(4, n_vocab, 3)]   # 4 ids, first is </s> = 2 (biogpt.cpp:859)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy, float32 kept as it is, anything else (ids) as float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def pmc_traffic(model_path):
@@ -235,6 +248,8 @@ def bench_capi(args):
         ids, _ = step(args.warmup + k)
         tokens += sum(len(v) for v in ids)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {("ids" if g == 0 else "ids_device%d" % g): v for g, v in enumerate(ids)})
     out = {
         "metric": "decode tokens/sec BioGPT %s n_ctx=%d" % (args.ftype.upper(), hp.n_positions), "value": round(tokens / elapsed, 2), "unit": "tokens/s", "n_gpus": n,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -279,10 +294,17 @@ def main():
     ap.add_argument("--replicas", default="ranks", choices=["ranks", "capi"],
                     help="N > 1: ranks = one process per GPU under torch.distributed (RCCL), the driver's form; capi = ONE process driving biogpt_hip_replicas_* "
                          "(ncclCommInitAll, a host thread and a stream per device) -- the other form of SURVEY 8(e), for comparison on the same lease")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child passes behind roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements (roofline and per-kernel figures, other formats, batched decode, prompt pass, "
+                         "API loops, CPU baseline, PMC passes); off: the headline steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 --pmc child passes")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the bounded cpu_baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0 / device 0: the sampled ids; prefill: the last token's logits) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` with N > 1 and no launcher (no WORLD_SIZE in the environment): become the launcher.  BIOGPT_BENCH_SELF_LAUNCH=1 takes
     # this branch for N = 1 too (tests on the one-GPU box); =print shows the command and stops.
@@ -408,6 +430,9 @@ def main():
         with open("%s.rank%d" % (dump, rank), "w") as f:
             json.dump({"model": path if rank == 0 else None, "prompt": make_prompt(hp.n_vocab, unit), "ids": [int(v) for v in last_ids]}, f)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": model.read_logits()} if prefill else {"ids": last_ids})
+
     if rank != 0:
         if dist is not None:
             dist.barrier()
@@ -458,8 +483,12 @@ def main():
         t_prompt = elapsed / args.steps
         out["token_roofline"] = {"bytes_per_prompt": int(b), "passes": passes, "GBps": round(b / t_prompt / 1e9, 1), "frac_of_peak": round(b / t_prompt / 1e9 / HBM_PEAK_GBS, 4)}
 
+    # ---- --full: everything below runs after the timed steps, each measurement with runs of its own --------
+    cpu_baseline = args.full and not args.no_cpu_baseline
+    pmc = args.full and not args.no_pmc
+
     # ---- roofline of the dominant kernel + whole-token figure (N = 1 only) ---------------------------
-    if world == 1 and not prefill:
+    if args.full and world == 1 and not prefill:
         try:
             reps = 24 * 20
             quant = args.ftype.startswith("q")
@@ -699,7 +728,7 @@ def main():
     # Four legs on the GPU box's host cores, each a bounded sample of the SAME workload (whole 200-token continuations of 4-token prompts, eval time only as main.cpp:96-103
     # counts it): the block dots as ggml's AVX2 kernels execute them (intrinsics; bo_opts.assoc = 7) on all cores and at the reference CLI's default -t 4 (biogpt.h:111), the
     # scalar fallbacks (assoc = 0, the association the HIP kernels are bit-identical to) on all cores, and the fp32 file (BASELINE configs[0], README.md:24,45) at -t 4 and all cores.
-    if world == 1 and not args.no_cpu_baseline and not prefill:
+    if world == 1 and cpu_baseline and not prefill:
         try:
             from oracle import oracle as O
             cores = usable_cores()
@@ -754,14 +783,14 @@ def main():
 
     # the PMC passes below are child processes on this device: the pipelined launches belong to ONE process per device (engine_xpipe.inc, xpipe_process_lock), and
     # everything that is timed is done -- this process lets go of its context (and with it of the device's lock file) first
-    if world == 1 and not args.no_pmc:
+    if world == 1 and pmc:
         try:
             model.close()
         except Exception:
             pass
     # ---- roofline.traffic: HBM-side bytes per launch of the dominant kernel from the PMC counters, each counter in its OWN rocprofv3 pass over a small child
     #      process (tools/pmc_target.py: 24 single-token launches of the pipelined kernel at 104 keys), after everything that is timed
-    if world == 1 and args.ftype.startswith("q") and not prefill and not args.no_pmc and "roofline" in out and "dec_xpipe" in out["roofline"].get("kernel", ""):
+    if world == 1 and args.ftype.startswith("q") and not prefill and pmc and "roofline" in out and "dec_xpipe" in out["roofline"].get("kernel", ""):
         try:
             t, detail = pmc_traffic(path)
             out["roofline"]["traffic"] = t
@@ -769,7 +798,7 @@ def main():
         except Exception as e:
             out["roofline"]["traffic_detail"] = {"error": str(e)[:300]}
 
-    if world == 1 and not prefill and not args.no_pmc and isinstance(out.get("prompt_chunk_evals"), dict) and "error" not in out["prompt_chunk_evals"]:
+    if world == 1 and not prefill and pmc and isinstance(out.get("prompt_chunk_evals"), dict) and "error" not in out["prompt_chunk_evals"]:
         # fetched / algorithmic bytes of the chunk launch: every XCD streams ALL weights (kernels_xcols.hip.h), so an 8-token eval fetches ~ 8 x the 196 MB a single stream needs
         try:
             tr = pmc_chunk_traffic(path)
@@ -781,7 +810,7 @@ def main():
         except Exception as e:
             out["prompt_chunk_evals"]["traffic"] = {"error": str(e)[:300]}
 
-    if world == 1 and not prefill and not args.no_pmc and isinstance(out.get("prompt_pass"), dict) and "roofline" in out["prompt_pass"]:
+    if world == 1 and not prefill and pmc and isinstance(out.get("prompt_pass"), dict) and "roofline" in out["prompt_pass"]:
         try:
             out["prompt_pass"]["roofline"]["mfma_busy"] = pmc_mfma_busy(path, out["prompt_pass"]["ms_per_pass"] * 1e-3)
         except Exception as e:

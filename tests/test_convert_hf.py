@@ -1,12 +1,9 @@
 """Converter counterpart: HF checkpoint directory -> ggml-model.bin."""
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
-
-REF = "/root/reference"
 
 
 @pytest.fixture(scope="module")
@@ -47,21 +44,33 @@ def test_converted_file_matches_hf_logits(pkg, oracle, hf_dir, tmp_path):
     assert oracle.OracleModel(f16).ftype == 1
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "convert.py")), reason="reference only exists in the build container")
+@pytest.fixture(scope="module")
+def golden_hf_dir(tmp_path_factory, golden_dir):
+    """The HF checkpoint directory that tests/golden/make_golden.py gave the reference's converter (convert.py parse_hparams /
+    parse_vocab / parse_bpe_merges / parse_model), rebuilt from what that converter wrote into tiny_f32.bin: the header, the vocab
+    in id order, the merge lines, and every tensor's name, shape and float32 data in state-dict order."""
+    torch = pytest.importorskip("torch")
+    import modelfile_py
+    hp, vocab, merges, tensors = modelfile_py.read_model(os.path.join(golden_dir, "tiny_f32.bin"))
+    d = tmp_path_factory.mktemp("hf_golden")
+    json.dump(dict(vocab_size=hp["n_vocab"], num_hidden_layers=hp["n_layer"], num_attention_heads=hp["n_head"], max_position_embeddings=hp["n_positions"],
+                   intermediate_size=hp["d_ff"], hidden_size=hp["d_model"]), open(d / "config.json", "w"))
+    json.dump({t.decode("utf-8"): i for i, t in enumerate(vocab)}, open(d / "vocab.json", "w"))
+    # make_golden.py's merge lines carry a third field ("a0 b0 1"); the file keeps the first two, as convert.py does
+    (d / "merges.txt").write_text("".join(m.decode("utf-8") + ("\n" if m.startswith(b"#") else " 1\n") for m in merges), encoding="utf-8")
+    sd = {}
+    for t in tensors:
+        assert t["type"] == 0
+        sd[t["name"]] = torch.from_numpy(np.frombuffer(t["raw"], dtype=np.float32).reshape(t["ne"][::-1]).copy())
+    torch.save(sd, d / "pytorch_model.bin")
+    return str(d)
+
+
 @pytest.mark.parametrize("f16", [False, True])
-def test_bytes_identical_to_reference_converter(pkg, hf_dir, tmp_path, f16):
-    import torch
-    from pathlib import Path
+def test_bytes_identical_to_reference_converter(pkg, golden_hf_dir, golden_dir, tmp_path, f16):
+    """Our converter on the checkpoint the reference's convert.py was given writes the bytes that convert.py wrote (tiny_f32.bin /
+    tiny_f16.bin, committed outputs of the reference's own writer functions)."""
     from biogpt_cpp_amd import convert_hf
-    sys.path.insert(0, REF)
-    import convert as refconv
-    d, _ = hf_dir
-    mine = convert_hf.convert(d, str(tmp_path / "mine.bin"), use_f16=f16)
-    ref = str(tmp_path / "ref.bin")
-    sd = torch.load(os.path.join(d, "pytorch_model.bin"), map_location="cpu")
-    with open(ref, "wb") as out:
-        refconv.parse_hparams(Path(d), out, f16)
-        refconv.parse_vocab(Path(d), out)
-        refconv.parse_bpe_merges(Path(d), out)
-        refconv.parse_model(sd, out, f16)
+    mine = convert_hf.convert(golden_hf_dir, str(tmp_path / "mine.bin"), use_f16=f16)
+    ref = os.path.join(golden_dir, "tiny_f16.bin" if f16 else "tiny_f32.bin")
     assert open(mine, "rb").read() == open(ref, "rb").read()

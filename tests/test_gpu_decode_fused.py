@@ -280,7 +280,8 @@ def test_bench_rccl_replica_path_on_one_gpu(oracle, tmp_path, launcher):
     must be the oracle's."""
     dump = str(tmp_path / "ids.json")
     env = dict(os.environ, BIOGPT_BENCH_DUMP_IDS=dump, BIOGPT_BENCH_DIR=str(tmp_path / "work"))   # bench.py sets HSA_ENABLE_IPC_MODE_LEGACY=0 itself (replicas.py says why)
-    args = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--n-layer", "4", "--n-predict", "40"]
+    args = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--n-layer", "4", "--n-predict", "40",
+            "--dump-outputs", str(tmp_path / "outputs")]
     if launcher == "env":
         env.update(BIOGPT_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29531", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
         cmd = [sys.executable] + args
@@ -310,6 +311,30 @@ def test_bench_rccl_replica_path_on_one_gpu(oracle, tmp_path, launcher):
     rec = json.load(open(dump + ".rank0"))
     ref, _ = oracle.OracleModel(rec["model"], n_threads=16).generate_greedy(rec["prompt"], 40, n_batch=8)
     assert rec["ids"] == [int(v) for v in ref]
+    ids = np.load(str(tmp_path / "outputs" / "ids.npy"))     # --dump-outputs: the same last timed continuation
+    assert ids.dtype == np.float64 and [int(v) for v in ids] == rec["ids"]
+
+
+def test_bench_dump_outputs_prefill(oracle, tmp_path):
+    """`bench.py --workload prefill --dump-outputs DIR`: DIR/logits.npy is the device row of the last timed prompt's last token,
+    equal to the oracle fed the same prompt chunk by chunk (-b 8); a plain run carries none of the --full side figures."""
+    env = dict(os.environ, BIOGPT_BENCH_DIR=str(tmp_path / "work"))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    n_prompt = 40
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--workload", "prefill", "--n-prompt", str(n_prompt), "--steps", "1", "--warmup", "0",
+                        "--n-layer", "4", "--dump-outputs", str(tmp_path / "outputs")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = _last_json_line(r.stdout)
+    assert out["steps"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0 and "roofline" not in out and "cpu_baseline" not in out
+    lg = np.load(str(tmp_path / "outputs" / "logits.npy"))
+    assert lg.dtype == np.float32 and lg.shape == (42384,)
+    rng = np.random.default_rng(7000)                        # bench.py's prompt of the last timed step (unit 0)
+    toks = [2] + [int(v) for v in rng.integers(4, 42384, n_prompt - 1)]
+    o = oracle.OracleModel(str(tmp_path / "work" / "synthetic-L4-q4_0.bin"), n_threads=16)
+    for at in range(0, n_prompt, 8):
+        lo = o.eval(toks[at:at + 8], at)
+    assert float(np.abs(lg - lo).max()) <= ATOL
 
 
 def test_bench_replicas_capi_on_one_gpu(tmp_path):
