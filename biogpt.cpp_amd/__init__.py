@@ -100,6 +100,8 @@ SYMBOLS = [
     ("biogpt_hip_eval_prompt", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     ("biogpt_hip_generate_greedy", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_generate_greedy_batch", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_score", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    ("biogpt_hip_score_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_read_kv", C.c_int, [_P, C.c_int, C.c_size_t, C.c_size_t, _P]),
     ("biogpt_hip_debug_stamps", C.c_int, [_P, C.c_size_t, C.c_size_t, C.POINTER(C.c_ulonglong)]),
     ("biogpt_hip_bench_matvec", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -399,6 +401,51 @@ class BiogptModel:
         if n < 0:
             raise BiogptError(_err())
         return out.reshape(-1)[:len(prompts) * n].reshape(len(prompts), n).copy(), secs.value
+
+    # -- sequence scoring (no reference counterpart): teacher-forced causal log-probabilities --
+    def score(self, tokens, n_past=0, targets=None):
+        """Row i sees tokens[0..i] (after n_past cached positions).  Returns (logprobs float32[n], argmax int32[n], target_logits float32[n]):
+        log P(targets[i] | ...) (natural log; targets=None: the next token, the last row unscored), each row's arg-max, and the target's
+        logit.  Rows with a negative target get 0 in logprobs and target_logits."""
+        toks = np.ascontiguousarray(tokens, dtype=np.int32)
+        tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32)
+        if tg is not None and tg.size != toks.size:
+            raise BiogptError("targets must have one entry per token (%d != %d)" % (tg.size, toks.size))
+        lp = np.zeros(toks.size, dtype=np.float32)
+        am = np.zeros(toks.size, dtype=np.int32)
+        lg = np.zeros(toks.size, dtype=np.float32)
+        if lib().biogpt_hip_score(self._h, toks.ctypes.data, toks.size, int(n_past), None if tg is None else tg.ctypes.data,
+                                  lp.ctypes.data, am.ctypes.data, lg.ctypes.data) != 0:
+            raise BiogptError(_err())
+        return lp, am, lg
+
+    def score_batch(self, seqs, targets=None):
+        """score() of several independent sequences (each from position 0, in its own K / V cache) in common passes.  targets: None, or one
+        entry per sequence -- None (next-token scoring) or that sequence's targets.  Returns a list of (logprobs, argmax, target_logits)."""
+        lens = np.asarray([len(s) for s in seqs], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs]) if len(seqs) else np.zeros(0, np.int32))
+        tg = None
+        if targets is not None:
+            if len(targets) != len(seqs):
+                raise BiogptError("targets must have one entry per sequence")
+            parts = []
+            for s, t in zip(seqs, targets):
+                if t is None:
+                    t = list(s[1:]) + [-1]
+                if len(t) != len(s):
+                    raise BiogptError("targets must have one entry per token")
+                parts.append(np.asarray(t, dtype=np.int32))
+            tg = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, np.int32))
+        n = max(int(flat.size), 1)
+        lp, am, lg = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        if lib().biogpt_hip_score_batch(self._h, flat.ctypes.data, lens.ctypes.data, len(seqs), None if tg is None else tg.ctypes.data,
+                                        lp.ctypes.data, am.ctypes.data, lg.ctypes.data) != 0:
+            raise BiogptError(_err())
+        out, off = [], 0
+        for k in lens:
+            out.append((lp[off:off + k].copy(), am[off:off + k].copy(), lg[off:off + k].copy()))
+            off += int(k)
+        return out
 
     def read_kv(self, which, offset, count):
         out = np.empty(int(count), dtype=np.float32)

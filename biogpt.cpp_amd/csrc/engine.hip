@@ -21,6 +21,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <set>
@@ -39,6 +40,7 @@
 #include "kernels_xcols.hip.h"   // (likewise: xcols_tu.hip)
 #include "kernels_fpipe.hip.h"   // (likewise: fpipe_tu.hip)
 #include "kernels_quant.hip.h"
+#include "kernels_score.hip.h"
 #include "model_file.h"
 #include "quant_host.h"
 
@@ -279,6 +281,10 @@ struct biogpt_hip_ctx {
     bgk::SeqState *seq = nullptr;         // [cap]
     bgk::SeqState *cols = nullptr;        // column states of a multi-sequence prompt pass
     size_t cols_cap = 0;
+    // sequence scoring (biogpt_hip_score*): the call's targets and its three outputs {logprob, arg-max, target logit}, [3][sc_cap] words
+    int32_t *sc_tgt = nullptr;
+    uint32_t *sc_out = nullptr;
+    size_t sc_cap = 0;
     int32_t *seq_gen = nullptr;           // [cap][n_positions]
     int batch_cap = 0;
     std::set<const void *> lds_attr_done;     // kernels whose > 64 KB dynamic-LDS opt-in attribute is set on this device
@@ -1023,9 +1029,12 @@ bool enqueue_xcols(biogpt_hip_ctx *c, int N, int t_max, bool streams = false) {
 
 // batch: one column per sequence (decode step).  cols != null: the columns are prompt tokens of several sequences
 // (column states with seq_id / t_vis), no lm_head -- the caller gets the logits from the following decode step.
-bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool batch = false, const bgk::SeqState *cols = nullptr) {
+// score (with all_rows): the logits of EVERY column into logits_all on the fastest lm_head for the model (biogpt_hip_score*);
+// prompt columns of several sequences (batch + cols) get them too.
+bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool batch = false, const bgk::SeqState *cols = nullptr, bool score = false) {
     t_ctx = c;
     (void)hipGetLastError();   // a failed call of some OTHER context / API leaves its code behind; the checks below are about these launches
+    if (score) all_rows = true;   // every row is needed: none of the launches that keep the activations on chip and compute the last row only
     if (N < 1 || N > c->hp.n_positions) BG_FAIL(false, "internal: a pass of %d columns exceeds the %d-column activation scratch", N, c->hp.n_positions);
     if (N == 1 && !batch && !all_rows && fused_decode_ok(c, t_max)) return enqueue_decode_fused(c, t_max, 1, 0);
     if (N >= 2 && N <= 8 && !batch && !all_rows && xcols_usable(c, N, t_max)) return enqueue_xcols(c, N, t_max);
@@ -1195,8 +1204,14 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
             }
         }
     }
-    if (batch && cols) return true;   // prompt columns: only the KV rows matter
-    if (batch) {  // every sequence needs its logits row: LayerNorm+Q8 once, then the 8-column mat-vec
+    // the final stage, LayerNorm + lm_head: which rows, and on which kernels
+    enum class Final { None, LastRow, AllRows, AllRowsQ8 };
+    const Final fin = (batch && cols && !score) ? Final::None            // prompt columns: only the KV rows matter
+                    : (batch || (score && pchain)) ? Final::AllRowsQ8     // LayerNorm+Q8 once, then the 8-column / matrix-core lm_head
+                    : (all_rows || score) ? Final::AllRows                // every row on the generic kernel (eval_all; scoring of the other models)
+                    : Final::LastRow;
+    if (fin == Final::None) return true;
+    if (fin == Final::AllRowsQ8) {  // every column needs its logits row: LayerNorm+Q8 once, then the 8-column mat-vec (matrix cores from 64 columns)
         const MatSlot &m = c->plan.lm_head;
         const MvShape s = mv_shape(m.type, m.M, m.K, tw, N);
         bgk::MatvecParams p = mv_base(c, m, s);
@@ -1208,11 +1223,12 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
     }
     {  // final LayerNorm + lm_head; only the rows that are returned (F8)
         const MatSlot &m = c->plan.lm_head;
-        const MvShape s = mv_shape(m.type, m.M, m.K, tw, all_rows ? N : 1);
+        const bool rows = fin == Final::AllRows;
+        const MvShape s = mv_shape(m.type, m.M, m.K, tw, rows ? N : 1);
         bgk::MatvecParams p = mv_base(c, m, s);
         p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
         p.ldx = D; p.ldo = V;
-        if (all_rows) {
+        if (rows) {
             p.x = c->x; p.N = N; p.out = c->logits_all;
         } else {
             p.x = c->x + (size_t)(N - 1) * D; p.N = 1; p.out = c->logits;
@@ -1221,7 +1237,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
         }
         int lm_grid = 0;
         HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(p, s, st, &lm_grid)));
-        if (!all_rows) c->lm_blocks = lm_grid;
+        if (!rows) c->lm_blocks = lm_grid;
     }
     return true;
 }
@@ -1450,7 +1466,7 @@ void destroy(biogpt_hip_ctx *c) {
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2185,6 +2201,66 @@ int biogpt_hip_generate_greedy(biogpt_hip_ctx *ctx, const int32_t *prompt, int32
 
 static int hp_cols(const biogpt_hip_ctx *c) { return c->hp.n_positions; }   // scratch is sized [n_positions] columns
 
+// per-sequence F32 K / V caches + state of n_seqs independent sequences (192 MiB per BioGPT-base sequence); new buffers drop the captured batched-decode graphs
+static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
+    if (n_seqs <= ctx->batch_cap) return true;
+    const size_t seq_stride = (size_t)ctx->hp.n_layer * ctx->hp.n_positions * ctx->hp.d_model;
+    for (void *p : {(void *)ctx->bk, (void *)ctx->bv, (void *)ctx->seq, (void *)ctx->seq_gen}) if (p) (void)hipFree(p);
+    ctx->bk = ctx->bv = nullptr; ctx->seq = nullptr; ctx->seq_gen = nullptr; ctx->batch_cap = 0;
+    HIP_TRY(false, hipMalloc(&ctx->bk, seq_stride * 4 * n_seqs));
+    HIP_TRY(false, hipMalloc(&ctx->bv, seq_stride * 4 * n_seqs));
+    HIP_TRY(false, hipMalloc(&ctx->seq, sizeof(bgk::SeqState) * n_seqs));
+    HIP_TRY(false, hipMalloc(&ctx->seq_gen, (size_t)n_seqs * ctx->hp.n_positions * 4));
+    ctx->batch_cap = n_seqs;
+    for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    return true;
+}
+
+// Prompt columns of several sequences in common passes (generate_greedy_batch's prompt ingestion, score_batch): every token is a
+// column that knows its sequence, its position and the end of its own n_batch-chunk (SeqState::seq_id / n_past / t_vis); whole
+// chunks are packed into passes of up to BIOGPT_HIP_PROMPT_COLS columns (at most n_positions: the activation scratch).  The columns
+// follow the flat order of `seqs`.  Per pass the column states go to ctx->cols, then pass(n_cols, t_max, flat0) enqueues the pass
+// (flat0 = flat index of its first token).
+static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int n_seqs, int n_batch,
+                               const std::function<bool(int, int, size_t)> &pass) {
+    const int max_cols = std::min(std::max(std::max(1, ctx->opt.prompt_cols), n_batch), hp_cols(ctx));   // the activation scratch holds n_positions columns
+    std::vector<bgk::SeqState> cols;
+    int pass_tmax = 0;
+    size_t flat0 = 0;
+    auto flush = [&]() -> bool {
+        if (cols.empty()) return true;
+        if (cols.size() > ctx->cols_cap) {
+            if (ctx->cols) (void)hipFree(ctx->cols);
+            ctx->cols = nullptr; ctx->cols_cap = 0;
+            HIP_TRY(false, hipMalloc(&ctx->cols, sizeof(bgk::SeqState) * cols.size()));
+            ctx->cols_cap = cols.size();
+        }
+        HIP_TRY(false, hipMemcpyAsync(ctx->cols, cols.data(), sizeof(bgk::SeqState) * cols.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(false, hipStreamSynchronize(ctx->stream));   // the host vector is reused for the next pass
+        if (!pass((int)cols.size(), pass_tmax, flat0)) return false;
+        flat0 += cols.size();
+        cols.clear();
+        pass_tmax = 0;
+        return true;
+    };
+    size_t off = 0;
+    for (int s = 0; s < n_seqs; s++) {
+        const int len = lens[s];
+        for (int at = 0; at < len; at += n_batch) {
+            const int m = std::min(n_batch, len - at);
+            if (!cols.empty() && (int)cols.size() + m > max_cols && !flush()) return false;
+            for (int i = 0; i < m; i++) {
+                bgk::SeqState cst{};
+                cst.n_past = at + i; cst.token = seqs[off + (size_t)(at + i)]; cst.seq_id = s; cst.t_vis = at + m;
+                cols.push_back(cst);
+            }
+            pass_tmax = std::max(pass_tmax, at + m);
+        }
+        off += (size_t)len;
+    }
+    return flush();
+}
+
 static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_seqs,
                                       int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out) {
     XpCallScope xp_scope(ctx);
@@ -2196,7 +2272,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_seqs (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
     if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
     const auto &hp = ctx->hp;
-    const int P = hp.n_positions, D = hp.d_model, V = hp.n_vocab;
+    const int P = hp.n_positions, V = hp.n_vocab;
     int max_len = 0;
     {
         size_t off = 0;
@@ -2211,17 +2287,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     if (n_predict <= 0) return 0;
     HIP_TRY(-2, hipSetDevice(ctx->device));
     if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    const size_t seq_stride = (size_t)hp.n_layer * P * D;
-    if (n_seqs > ctx->batch_cap) {  // per-sequence F32 KV caches + state (192 MiB per BioGPT-base sequence)
-        for (void *p : {(void *)ctx->bk, (void *)ctx->bv, (void *)ctx->seq, (void *)ctx->seq_gen}) if (p) (void)hipFree(p);
-        ctx->bk = ctx->bv = nullptr; ctx->seq = nullptr; ctx->seq_gen = nullptr; ctx->batch_cap = 0;
-        HIP_TRY(-2, hipMalloc(&ctx->bk, seq_stride * 4 * n_seqs));
-        HIP_TRY(-2, hipMalloc(&ctx->bv, seq_stride * 4 * n_seqs));
-        HIP_TRY(-2, hipMalloc(&ctx->seq, sizeof(bgk::SeqState) * n_seqs));
-        HIP_TRY(-2, hipMalloc(&ctx->seq_gen, (size_t)n_seqs * P * 4));
-        ctx->batch_cap = n_seqs;
-        for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    }
+    if (!ensure_seq_caches(ctx, n_seqs)) return -2;
     {   // matrix-core chain: decode steps have n_seqs columns, the prompt pass all prompt tokens; build the tiled weights before any graph capture
         long total = 0;
         for (int s = 0; s < n_seqs; s++) total += prompt_lens[s];
@@ -2277,47 +2343,12 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
 
     const auto t0 = std::chrono::steady_clock::now();
-    // Prompt ingestion for ALL sequences together (main.cpp:129-137 per sequence): every prompt token is a column that
-    // knows its sequence, its position and the end of its own n_batch-chunk (SeqState::seq_id / n_past / t_vis); whole
-    // chunks are packed into passes of up to BIOGPT_HIP_PROMPT_COLS columns.  The pass only has to fill the KV caches:
-    // the first decode step below re-evaluates each sequence's LAST prompt token (same K/V row, same visible keys as
-    // its chunk gave it) and its arg-max is the first sampled token.
-    {
-        const int max_cols = std::min(std::max(std::max(1, ctx->opt.prompt_cols), n_batch), hp_cols(ctx));   // the activation scratch holds n_positions columns
-        std::vector<bgk::SeqState> cols;
-        int pass_tmax = 0;
-        auto flush = [&]() -> bool {
-            if (cols.empty()) return true;
-            if (cols.size() > ctx->cols_cap) {
-                if (ctx->cols) (void)hipFree(ctx->cols);
-                ctx->cols = nullptr; ctx->cols_cap = 0;
-                HIP_TRY(false, hipMalloc(&ctx->cols, sizeof(bgk::SeqState) * cols.size()));
-                ctx->cols_cap = cols.size();
-            }
-            HIP_TRY(false, hipMemcpyAsync(ctx->cols, cols.data(), sizeof(bgk::SeqState) * cols.size(), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(false, hipStreamSynchronize(ctx->stream));   // the host vector is reused for the next pass
-            if (!enqueue_forward(ctx, (int)cols.size(), false, pass_tmax, true, ctx->cols)) return false;
-            cols.clear();
-            pass_tmax = 0;
-            return true;
-        };
-        size_t off = 0;
-        for (int s = 0; s < n_seqs; s++) {
-            const int len = prompt_lens[s];
-            for (int at = 0; at < len; at += n_batch) {
-                const int m = std::min(n_batch, len - at);
-                if (!cols.empty() && (int)cols.size() + m > max_cols && !flush()) return -2;
-                for (int i = 0; i < m; i++) {
-                    bgk::SeqState cst{};
-                    cst.n_past = at + i; cst.token = prompts[off + (size_t)(at + i)]; cst.seq_id = s; cst.t_vis = at + m;
-                    cols.push_back(cst);
-                }
-                pass_tmax = std::max(pass_tmax, at + m);
-            }
-            off += (size_t)len;
-        }
-        if (!flush()) return -2;
-    }
+    // Prompt ingestion for ALL sequences together (main.cpp:129-137 per sequence), packed into common passes (pack_column_passes).
+    // The pass only has to fill the KV caches: the first decode step below re-evaluates each sequence's LAST prompt token (same K/V
+    // row, same visible keys as its chunk gave it) and its arg-max is the first sampled token.
+    if (!pack_column_passes(ctx, prompts, prompt_lens, n_seqs, n_batch,
+                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }))
+        return -2;
     if (!batch_step(max_len)) return -2;   // last prompt token of every sequence -> first sampled token, n_past = prompt length
     for (int k = 1; k < n_predict; k++) {  // batched decode: one column per sequence
         const int t_max = max_len + k;
@@ -2337,6 +2368,146 @@ int biogpt_hip_generate_greedy_batch(biogpt_hip_ctx *ctx, const int32_t *prompts
                                      int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out) {
     int rc = generate_greedy_batch_once(ctx, prompts, prompt_lens, n_seqs, n_batch, n_predict, out_ids, seconds_out);
     if (rc < 0 && xpipe_retry(ctx, 0)) rc = generate_greedy_batch_once(ctx, prompts, prompt_lens, n_seqs, n_batch, n_predict, out_ids, seconds_out);
+    return rc;
+}
+
+// ---- sequence scoring: teacher-forced causal passes, the log-softmax of every row on the device (kernels_score.hip.h) ----------------
+// Row i of a scored sequence sees keys [0, n_past + i]: the prompt pass of biogpt_hip_eval_prompt with n_batch = 1 (DevState::chunk = 1;
+// one column per sequence token, SeqState::t_vis = position + 1, for score_batch), whatever BIOGPT_HIP_CAUSAL says.  The lm_head runs over
+// every column of a pass into logits_all (at most one pass of rows), logprob_rows_kernel reduces each row to {log-probability of the
+// target, arg-max, target logit}; the call's targets go up once, its outputs come back in one copy.
+static bool check_targets(const biogpt_hip_ctx *c, const int32_t *targets, int n, int seq) {
+    if (!targets) return true;
+    for (int i = 0; i < n; i++)
+        if (targets[i] >= c->hp.n_vocab) BG_FAIL(false, "target id %d (sequence %d, row %d) out of range: must be < %d (negative: row not scored)", targets[i], seq, i, c->hp.n_vocab);
+    return true;
+}
+
+// logits_all holds at least `rows` rows; a new buffer drops the captured batched-decode graphs (they hold the old pointer)
+static bool ensure_logits_rows(biogpt_hip_ctx *c, size_t rows) {
+    if (rows <= c->logits_all_rows) return true;
+    if (c->logits_all) (void)hipFree(c->logits_all);
+    c->logits_all = nullptr; c->logits_all_rows = 0;
+    HIP_TRY(false, hipMalloc(&c->logits_all, rows * c->hp.n_vocab * 4));
+    c->logits_all_rows = rows;
+    for (auto &g : c->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    c->graph_batch_n = 0;
+    return true;
+}
+
+// the targets of all `total` rows of the call (NULL: the next token of the same sequence, -1 for its last row) -> sc_tgt;
+// sc_out laid out [3][total] for this call: log-probabilities, arg-max ids, target logits
+static bool score_setup(biogpt_hip_ctx *c, const int32_t *seqs, const int32_t *lens, int n_seqs, const int32_t *targets, size_t total) {
+    if (total > c->sc_cap) {
+        for (void *p : {(void *)c->sc_tgt, (void *)c->sc_out}) if (p) (void)hipFree(p);
+        c->sc_tgt = nullptr; c->sc_out = nullptr; c->sc_cap = 0;
+        HIP_TRY(false, hipMalloc(&c->sc_tgt, total * 4));
+        HIP_TRY(false, hipMalloc(&c->sc_out, 3 * total * 4));
+        c->sc_cap = total;
+    }
+    std::vector<int32_t> tg(total);
+    size_t off = 0;
+    for (int s = 0; s < n_seqs; s++) {
+        for (int i = 0; i < lens[s]; i++) tg[off + i] = targets ? targets[off + i] : (i + 1 < lens[s] ? seqs[off + i + 1] : -1);
+        off += (size_t)lens[s];
+    }
+    HIP_TRY(false, hipMemcpy(c->sc_tgt, tg.data(), total * 4, hipMemcpyHostToDevice));
+    return true;
+}
+
+// the log-softmax of the m rows logits_all holds for flat rows [flat0, flat0 + m) of the call
+static bool enqueue_logprob(biogpt_hip_ctx *c, int m, size_t flat0, size_t total) {
+    const int V = c->hp.n_vocab;
+    float *const lp = reinterpret_cast<float *>(c->sc_out) + flat0;
+    int32_t *const am = reinterpret_cast<int32_t *>(c->sc_out + total) + flat0;
+    float *const lg = reinterpret_cast<float *>(c->sc_out + 2 * total) + flat0;
+    hipLaunchKernelGGL(bgk::logprob_rows_kernel, dim3(m), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->sc_tgt + flat0, lp, am, lg);
+    HIP_TRY(false, hipGetLastError());
+    return true;
+}
+
+// one copy of the outputs back, then into the caller's arrays (argmax_out / logit_out may be NULL)
+static int score_finish(biogpt_hip_ctx *c, size_t total, float *logprob_out, int32_t *argmax_out, float *logit_out) {
+    std::vector<uint32_t> h(3 * total);
+    HIP_TRY(-2, hipMemcpyAsync(h.data(), c->sc_out, 3 * total * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(-2, hipStreamSynchronize(c->stream));
+    c->mbox_synced = c->mbox_sent;
+    if (!xpipe_check(c)) return -2;
+    std::memcpy(logprob_out, h.data(), total * 4);
+    if (argmax_out) std::memcpy(argmax_out, h.data() + total, total * 4);
+    if (logit_out) std::memcpy(logit_out, h.data() + 2 * total, total * 4);
+    return 0;
+}
+
+static int score_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, const int32_t *targets,
+                      float *logprob_out, int32_t *argmax_out, float *logit_out) {
+    XpCallScope xp_scope(ctx);
+    clear_error();
+    if (!check_eval_args(ctx, tokens, n, n_past)) return -1;
+    if (!logprob_out) BG_FAIL(-1, "null logprob buffer");
+    if (!check_targets(ctx, targets, n, 0)) return -1;
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
+    // the passes of biogpt_hip_eval_prompt(tokens, n_past, n_batch = 1): same borders, same K / V rows
+    const int max_cols = std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
+    const int first = std::min(max_cols, (int)n);
+    if (first >= ctx->opt.mfma_min(64) && is_quantized(ftype_to_type(ctx->hp.ftype)) && !ensure_tile_images(ctx)) return -2;
+    if (!ensure_logits_rows(ctx, (size_t)first) || !score_setup(ctx, tokens, &n, 1, targets, (size_t)n)) return -2;
+    const int V = ctx->hp.n_vocab;
+    for (int at = 0; at < n;) {
+        const int m = std::min(max_cols, n - at);
+        if (!upload_state(ctx, tokens + at, m, n_past + at, m > 1 ? 1 : 0)) return -2;
+        if (!enqueue_forward(ctx, m, true, n_past + at + m, false, nullptr, true)) return -2;
+        if (!enqueue_logprob(ctx, m, (size_t)at, (size_t)n)) return -2;
+        at += m;
+        if (at == n)   // the last row is what biogpt_hip_read_logits / biogpt_hip_logits_device return afterwards
+            HIP_TRY(-2, hipMemcpyAsync(ctx->logits, ctx->logits_all + (size_t)(m - 1) * V, (size_t)V * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    return score_finish(ctx, (size_t)n, logprob_out, argmax_out, logit_out);
+}
+
+static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
+                            float *logprob_out, int32_t *argmax_out, float *logit_out) {
+    XpCallScope xp_scope(ctx);
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!seqs || !lens || !logprob_out) BG_FAIL(-1, "null argument");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");   // each sequence owns a full F32 KV cache
+    const auto &hp = ctx->hp;
+    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64 && !ctx->opt.no_fast && !ctx->opt.no_chain))
+        BG_FAIL(-1, "batched scoring needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    size_t total = 0;
+    for (int s = 0; s < n_seqs; s++) {
+        if (lens[s] < 1) BG_FAIL(-1, "empty sequence (sequence %d)", s);
+        if (!check_eval_args(ctx, seqs + total, lens[s], 0)) return -1;
+        if (!check_targets(ctx, targets ? targets + total : nullptr, lens[s], s)) return -1;
+        total += (size_t)lens[s];
+    }
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
+    // every sequence from position 0 in its own K / V cache (bk / bv): the context's own cache and position stay as they are
+    const size_t max_cols = (size_t)std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
+    if (!ensure_seq_caches(ctx, n_seqs)) return -2;
+    if ((long)std::min(max_cols, total) >= ctx->opt.mfma_min(64) && !ensure_tile_images(ctx)) return -2;
+    if (!ensure_logits_rows(ctx, std::min(max_cols, total)) || !score_setup(ctx, seqs, lens, n_seqs, targets, total)) return -2;
+    if (!pack_column_passes(ctx, seqs, lens, n_seqs, 1, [&](int n_cols, int t_max, size_t flat0) {
+            return enqueue_forward(ctx, n_cols, true, t_max, true, ctx->cols, true) && enqueue_logprob(ctx, n_cols, flat0, total);
+        }))
+        return -2;
+    return score_finish(ctx, total, logprob_out, argmax_out, logit_out);
+}
+
+int biogpt_hip_score(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, const int32_t *targets,
+                     float *logprob_out, int32_t *argmax_out, float *logit_out) {
+    int rc = score_once(ctx, tokens, n_tokens, n_past, targets, logprob_out, argmax_out, logit_out);
+    if (rc < 0 && xpipe_retry(ctx, n_past)) rc = score_once(ctx, tokens, n_tokens, n_past, targets, logprob_out, argmax_out, logit_out);
+    return rc;
+}
+int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
+                           float *logprob_out, int32_t *argmax_out, float *logit_out) {
+    int rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
+    if (rc < 0 && xpipe_retry(ctx, 0)) rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
     return rc;
 }
 

@@ -225,6 +225,29 @@ int biogpt_hip_generate_greedy_batch(biogpt_hip_ctx *ctx, const int32_t *prompts
                                      int32_t n_seqs, int32_t n_batch, int32_t n_predict, int32_t *out_ids,
                                      double *seconds_out);
 
+/* ---- sequence scoring (no counterpart in the reference) ---------------------------------------
+ * biogpt_hip_score: teacher-forced, causal log-probabilities of a sequence.  Row i sees the keys [0, n_past + i] -- what
+ * biogpt_hip_eval_prompt(..., n_batch = 1) and a loop of single-token biogpt_hip_eval calls compute; NOT the unmasked chunk of
+ * biogpt_hip_eval_all (F1), and independent of BIOGPT_HIP_CAUSAL.  For every row i with targets[i] >= 0, with l = the row's logits,
+ * m = max(l), t = targets[i]:  logprob_out[i] = (l[t] - m) - log(sum_v exp(l[v] - m))  (natural log),  logit_out[i] = l[t]  (bit-identical
+ * to the row eval_prompt(tokens[0..i], n_past, 1) returns); rows with targets[i] < 0 get 0 in both.  argmax_out[i] = the arg-max of row i
+ * (lowest id on ties) for every row.  targets == NULL: next-token scoring, targets[i] = tokens[i + 1] and -1 for the last row.
+ * argmax_out and logit_out may be NULL.  Arguments as for biogpt_hip_eval, plus targets[i] < n_vocab.  Afterwards the K / V rows
+ * [n_past, n_past + n_tokens) and the device row (biogpt_hip_read_logits) are those biogpt_hip_eval_prompt(..., 1) leaves: a following
+ * biogpt_hip_eval at n_past + n_tokens continues the sequence.  Passes of up to BIOGPT_HIP_PROMPT_COLS (512) columns; the log-softmax
+ * runs on the device, n_tokens x 12 bytes cross PCIe.  Returns 0 or < 0. */
+int biogpt_hip_score(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, const int32_t *targets,
+                     float *logprob_out, int32_t *argmax_out, float *logit_out);
+
+/* The same for n_seqs independent sequences, each scored from position 0 in its own K / V cache (the context's own cache and position
+ * are left alone): seqs = the sequences concatenated, lens[n_seqs] their lengths (the layout of biogpt_hip_generate_greedy_batch);
+ * targets (may be NULL: next-token scoring per sequence) and the outputs use the same flat layout as seqs.  The columns of all sequences
+ * travel through common passes of up to BIOGPT_HIP_PROMPT_COLS columns; every sequence's results are bit-identical to
+ * biogpt_hip_score(seq, n_past = 0).  Needs the BioGPT-base fast chain (block-quantized weights) and n_seqs <= 512, like
+ * biogpt_hip_generate_greedy_batch; anything else fails with -1.  Returns 0 or < 0. */
+int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
+                           float *logprob_out, int32_t *argmax_out, float *logit_out);
+
 /* ---- introspection for tests / profiling ---------------------------------------------------
  * Copy `count` floats of the F32 KV cache (which: 0 = K, 1 = V) starting at element `offset` of
  * the flat [n_layer][n_positions][d_model] array (biogpt.cpp:331-335) to host memory. */
