@@ -177,34 +177,16 @@ int env_int(const char *name, int dflt) {
 // Tuning / debugging switches.  Read from the environment ONCE, when a context is created (and again only on
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
-    int mv_waves, max_wgs, lm_steps, fast_steps, no_fast, no_chain, mfma_min_cols, attn_group_min,
-        split_min, attn_slim_min, dbg, target_wgs, prompt_cols, no_graph, causal, no_fused_decode, fc1_blocks, fc2_waves, oproj_waves, attn_tile, eval_graph_split, qkv_waves, fc1_waves, attn_waves, xpipe, xpipe_fault, xpipe_tables, xpipe_lm, xpipe_multi, xpipe_long, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols, resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, eval_sync, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault;
+    int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
-        mv_waves = get("BIOGPT_HIP_MV_WAVES", 4);
-        max_wgs = get("BIOGPT_HIP_MAX_WGS", 1024);
-        lm_steps = get("BIOGPT_HIP_LM_STEPS", 8);
-        fast_steps = get("BIOGPT_HIP_FAST_STEPS", 1);
-        no_fast = get("BIOGPT_HIP_NO_FAST", 0);
-        no_chain = get("BIOGPT_HIP_NO_CHAIN", 0);
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
-        mfma_min_cols = get("BIOGPT_HIP_MFMA_MIN_COLS", -1);      // -1: measured cross-overs (48 decode columns / 64 prompt columns)
-        attn_group_min = get("BIOGPT_HIP_ATTN_GROUP_MIN", 80);
-        split_min = get("BIOGPT_HIP_SPLIT_MIN", 256);
-        attn_slim_min = get("BIOGPT_HIP_ATTN_SLIM_MIN", 48);
         dbg = get("BIOGPT_HIP_DBG", 0);
-        target_wgs = get("BIOGPT_HIP_TARGET_WGS", 256);
         prompt_cols = get("BIOGPT_HIP_PROMPT_COLS", 512);
         no_graph = get("BIOGPT_HIP_NO_GRAPH", 0);
         causal = get("BIOGPT_HIP_CAUSAL", 0);
         no_fused_decode = get("BIOGPT_HIP_NO_FUSED_DECODE", 0);
-        fc1_blocks = get("BIOGPT_HIP_FC1_BLOCKS", 1);
-        fc2_waves = get("BIOGPT_HIP_FC2_WAVES", 8);      // same-process sweeps (profiles/decode_shapes_r2.txt): 8 waves beat 16 and 4
-        oproj_waves = get("BIOGPT_HIP_OPROJ_WAVES", 8);
-        qkv_waves = get("BIOGPT_HIP_QKV_WAVES", 8);
-        fc1_waves = get("BIOGPT_HIP_FC1_WAVES", 8);
-        attn_waves = get("BIOGPT_HIP_ATTN_WAVES", 8);
-        xpipe_tables = get("BIOGPT_HIP_XPIPE_TABLES", 3);   // bit 0: the MLP halves keep the GELU table's non-trivial slices in LDS (70 KB); bit 1: the attention workgroups the exp table's (39 KB)
         resident = get("BIOGPT_HIP_RESIDENT", 1);           // biogpt_hip_eval with one token: the pipelined launch stays on the device and takes the next call's token from a pinned mailbox
         res_dbg = get("BIOGPT_HIP_RES_DBG", 0);              // measurement only (kernels_xpipe.hip.h XpParams::res_dbg)
         lm_stream = get("BIOGPT_HIP_LM_STREAM", 1);          // the stand-alone lm_head as lm_stream_kernel (0: matvec_fast_kernel<PRO_LN, EPI_LOGITS>)
@@ -212,7 +194,6 @@ struct EngineOptions {
         resident_us = get("BIOGPT_HIP_RESIDENT_US", 1000);   // ... for at most this long without a new token (the device is not shared meanwhile)
         hop_place = get("BIOGPT_HIP_HOP_PLACE", 1);        // the cross-XCD hand-off regions: 1 placed by a calibration launch (xpipe_place_hops), 0 first candidate, 2 the slower one (A/B)
         verbose = get("BIOGPT_HIP_VERBOSE", 0);
-        eval_sync = get("BIOGPT_HIP_EVAL_SYNC", 0);
         topk_blocks = get("BIOGPT_HIP_TOPK_BLOCKS", 1);    // biogpt_hip_eval_topk behind a resident launch: select from the blocks whose maximum can hold a candidate (0: scan the whole row)
         xpipe_dual = get("BIOGPT_HIP_XPIPE_DUAL", 1);       // contexts of 257 .. 512 keys (multi-token launches, graph replays, resident launches): dec_xpipe_kernel with two workgroups per head (0: kernels_xlong.hip.h, as in round 3)
         fpipe_lead = get("BIOGPT_HIP_FPIPE_LEAD", -1);       // the persistent float launch: 64-clock units a polling wave lets pass between its own workgroup's publication and its first sweep (-1: 26 for F32 files, 16 for F16 -- the measured optima, profiles/fpipe_lead_scan_r6.txt)
@@ -220,19 +201,14 @@ struct EngineOptions {
         fpipe_stamps = get("BIOGPT_HIP_FPIPE_STAMPS", 0);   // diagnostics: the persistent launch records stage-border times of three workgroups (biogpt_hip_fpipe_stamps)
         fpipe = get("BIOGPT_HIP_FPIPE", 1);                 // single-token steps of F32 / F16 files as ONE persistent launch for all layers (kernels_fpipe.hip.h); 0: five launches per layer
         xcols = get("BIOGPT_HIP_XCOLS", 1);                 // evals of 2 .. 8 tokens (the reference's prompt chunks) as ONE persistent launch, one column per XCD (kernels_xcols.hip.h); 0: the launch chain of kernels_fast.hip.h
-        xpipe_long = get("BIOGPT_HIP_XPIPE_LONG", 1);       // contexts of 257 .. 1024 keys on the pipeline too (kernels_xlong.hip.h: attention spread over the chip)
         xpipe_multi = get("BIOGPT_HIP_XPIPE_MULTI", 1);     // biogpt_hip_generate_greedy: all tokens of a context bucket in one pipelined launch
-        xpipe_lm = get("BIOGPT_HIP_XPIPE_LM", 1);           // final LayerNorm + lm_head inside the pipelined launch
         xpipe_fault = get("BIOGPT_HIP_XPIPE_FAULT", 0);   // test hook: the first pipelined launch finds a 33rd workgroup on XCD 0 and drains
         xpipe = get("BIOGPT_HIP_XPIPE", 1);             // the XCD-pipelined single-launch decode step (kernels_xpipe.hip.h)
-        attn_tile = get("BIOGPT_HIP_ATTN_TILE", 1);
         graph_contended = get("BIOGPT_HIP_GRAPH_CONTENDED", 0);   // test switch: replay the five-launch eval graph even while ANOTHER context holds the pipeline slot (the arrangement of profiles/two_contexts_r4.txt)
         fault_stale = get("BIOGPT_HIP_FAULT_STALE", 0);           // test switch: every k-th replayed eval starts from the PREVIOUS mailbox slot (the stale-row symptom, injected)
         proc_lock = get("BIOGPT_HIP_PROC_LOCK", 1);               // one process per device drives the pipelined launches (engine_xpipe.inc, xpipe_process_lock)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
-        eval_graph_split = get("BIOGPT_HIP_EVAL_GRAPH_SPLIT", 0);   // 0: per entry point (eval_topk: one graph, eval: two segments)
     }
-    int mfma_min(int dflt) const { return mfma_min_cols >= 0 ? mfma_min_cols : dflt; }
 };
 
 namespace {
@@ -378,12 +354,11 @@ bgk::DevMatrix dev_matrix(const biogpt_hip_ctx *c, const MatSlot &m) {
 const float *dev_vec(const biogpt_hip_ctx *c, size_t off) { return reinterpret_cast<const float *>(c->arena + off); }
 
 struct MvShape { int upr, lpr_log2, nit, rpw, nwaves, grid; };
-// the context whose launches the calling thread is enqueueing (set at every entry point that launches): the launch
-// helpers below read its cached options and per-device state -- one host thread drives one device at a time
-thread_local biogpt_hip_ctx *t_ctx = nullptr;
-const EngineOptions &opt() { return t_ctx->opt; }
 
-MvShape mv_shape(int32_t type, int64_t M, int64_t K, int target_wgs, int N = 1) {
+// shape of the generic mat-vec launch (matvec_kernel): up to MATVEC_WAVES waves per workgroup while that keeps >= MATVEC_MIN_GRID
+// workgroups, then row steps per wave until the grid is at most MATVEC_MAX_GRID workgroups (the sweep: tools/archive/sweep_matvec.py)
+constexpr int MATVEC_WAVES = 4, MATVEC_MIN_GRID = 256, MATVEC_MAX_GRID = 1024;
+MvShape mv_shape(int32_t type, int64_t M, int64_t K) {
     MvShape s;
     const int elems = (type == T_F32) ? 4 : (type == T_F16) ? 8 : 32;
     s.upr = (int)(K / elems);
@@ -391,14 +366,10 @@ MvShape mv_shape(int32_t type, int64_t M, int64_t K, int target_wgs, int N = 1) 
     s.lpr_log2 = ilog2(lpr);
     s.nit = (s.upr + lpr - 1) / lpr;
     const int rps = 64 / lpr;
-    // waves per workgroup: as many as possible (up to 4) while keeping >= target_wgs workgroups
-    int nw = opt().mv_waves;
-    while (nw > 1 && (M + (int64_t)nw * rps - 1) / ((int64_t)nw * rps) < target_wgs) nw >>= 1;
+    int nw = MATVEC_WAVES;
+    while (nw > 1 && (M + (int64_t)nw * rps - 1) / ((int64_t)nw * rps) < MATVEC_MIN_GRID) nw >>= 1;
     int steps = 1;
-    const int max_wgs = opt().max_wgs;
-    // one finisher lane per (row, column) of a wave: rows_per_wave * columns <= 64
-    (void)N;
-    while ( (M + (int64_t)nw * rps * steps - 1) / ((int64_t)nw * rps * steps) > max_wgs) steps++;
+    while ( (M + (int64_t)nw * rps * steps - 1) / ((int64_t)nw * rps * steps) > MATVEC_MAX_GRID) steps++;
     s.nwaves = nw;
     s.rpw = rps * steps;
     s.grid = (int)((M + (int64_t)nw * s.rpw - 1) / ((int64_t)nw * s.rpw));
@@ -432,28 +403,41 @@ hipError_t launch_mv_nc(const bgk::MatvecParams &p, const MvShape &s, hipStream_
 }
 
 // ---- shape-specialised single-token path (kernels_fast.hip.h) --------------------------------------
+// row steps per wave of the single-token lm_head: LM_ROW_STEPS, halved while the grid would have fewer than 128 workgroups (keep the chip covered);
+// every other site takes one row step per wave.  rps: rows per wave step
+constexpr int LM_ROW_STEPS = 8;
+int lm_fast_steps(int M, int rps) {
+    int steps = LM_ROW_STEPS;
+    while (steps > 1 && (M + 4 * rps * steps - 1) / (4 * rps * steps) < 128) steps >>= 1;
+    return steps;
+}
+
 template <int WT, int PRO, int EPI, int K>
-hipError_t launch_fast_k(bgk::MatvecParams p, hipStream_t st) {
+hipError_t launch_fast_k(bgk::MatvecParams p, hipStream_t st, int *grid_out) {
     constexpr int BPR = K / 32, LPR = BPR < 64 ? BPR : 64, RPS = 64 / LPR;
-    const int M = p.W.M;
-    int steps = (EPI == bgk::EPI_LOGITS) ? opt().lm_steps : opt().fast_steps;
-    while (steps > 1 && (M + 4 * RPS * steps - 1) / (4 * RPS * steps) < 128) steps >>= 1;  // keep the chip covered
+    const int steps = EPI == bgk::EPI_LOGITS ? lm_fast_steps(p.W.M, RPS) : 1;
     p.rpw = RPS * steps;
-    const int grid = (M + 4 * p.rpw - 1) / (4 * p.rpw);
+    const int grid = (p.W.M + 4 * p.rpw - 1) / (4 * p.rpw);
+    if (grid_out) *grid_out = grid;
     const size_t sm = bgk::matvec_fast_smem_bytes(K, p.rpw);
-    if (steps > 1) hipLaunchKernelGGL((bgk::matvec_fast_kernel<WT, PRO, EPI, K, 4>), dim3(grid), dim3(256), sm, st, p);
-    else hipLaunchKernelGGL((bgk::matvec_fast_kernel<WT, PRO, EPI, K, 1>), dim3(grid), dim3(256), sm, st, p);
+    if constexpr (EPI == bgk::EPI_LOGITS) {
+        if (steps > 1) {
+            hipLaunchKernelGGL((bgk::matvec_fast_kernel<WT, PRO, EPI, K, 4>), dim3(grid), dim3(256), sm, st, p);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((bgk::matvec_fast_kernel<WT, PRO, EPI, K, 1>), dim3(grid), dim3(256), sm, st, p);
     return hipGetLastError();
 }
 
 template <int WT, int PRO, int EPI>
-bool try_launch_fast(const bgk::MatvecParams &p, hipStream_t st, hipError_t &err, int *grid_out) {
-    if (p.N != 1 || opt().no_fast) return false;
+bool try_launch_fast(const EngineOptions &o, const bgk::MatvecParams &p, hipStream_t st, hipError_t &err, int *grid_out) {
+    if (p.N != 1) return false;
     const int K = p.W.K;
     if (EPI == bgk::EPI_QKV && p.D != K) return false;
     if constexpr (EPI == bgk::EPI_LOGITS && PRO == bgk::PRO_LN) {
         // the single-token lm_head as one pass with all loads up front (kernels_lmhead.hip.h), when the partials are the 64-row blocks its consumers expect
-        if (K == 1024 && opt().lm_stream && opt().lm_steps == 8 && p.W.M >= 64 * 128 && (p.dbg & 0xff & ~32) == 0) {
+        if (K == 1024 && o.lm_stream && p.W.M >= 64 * 128 && (p.dbg & 0xff & ~32) == 0) {
             constexpr int NB = 3;      // 64-row blocks per workgroup of 8 waves (2 x 8 and 3 / 4 x 16 waves measured: 8.9 / 6.8 / 8.4 us)
             const int blocks = (p.W.M + 63) / 64;
             hipLaunchKernelGGL((bgk::lm_stream_kernel<WT>), dim3((blocks + NB - 1) / NB), dim3(512), bgk::lm_stream_smem_bytes(bgk::TypeInfo<WT>::q81), st, p);
@@ -463,18 +447,12 @@ bool try_launch_fast(const bgk::MatvecParams &p, hipStream_t st, hipError_t &err
         }
     }
     if (K == 1024) {
-        err = launch_fast_k<WT, PRO, EPI, 1024>(p, st);
+        err = launch_fast_k<WT, PRO, EPI, 1024>(p, st, grid_out);
     } else if (K == 4096) {
-        if constexpr (PRO == bgk::PRO_PLAIN) err = launch_fast_k<WT, PRO, EPI, 4096>(p, st);
+        if constexpr (PRO == bgk::PRO_PLAIN) err = launch_fast_k<WT, PRO, EPI, 4096>(p, st, grid_out);
         else return false;
     } else {
         return false;
-    }
-    if (grid_out) {
-        const int BPR = K / 32, LPR = BPR < 64 ? BPR : 64, RPS = 64 / LPR;
-        int steps = (EPI == bgk::EPI_LOGITS) ? opt().lm_steps : opt().fast_steps;
-        while (steps > 1 && (p.W.M + 4 * RPS * steps - 1) / (4 * RPS * steps) < 128) steps >>= 1;
-        *grid_out = (p.W.M + 4 * RPS * steps - 1) / (4 * RPS * steps);
     }
     return true;
 }
@@ -549,11 +527,11 @@ hipError_t launch_lnq(const biogpt_hip_ctx *c, const float *x, int N, size_t ln_
 
 // ---- float weights, one column, BioGPT-base shapes (kernels_fdecode.hip.h): the whole matrix requested at t = 0 --------------------
 template <int WT, int PRO, int EPI>
-bool try_launch_fdec(const bgk::MatvecParams &p, hipStream_t st, hipError_t &err) {
+bool try_launch_fdec(const EngineOptions &o, const bgk::MatvecParams &p, hipStream_t st, hipError_t &err) {
     if constexpr (EPI == bgk::EPI_LOGITS || EPI == bgk::EPI_GELU_Q8 || PRO == bgk::PRO_Q8IN) {
         return false;
     } else {
-        if (p.N != 1 || opt().no_fast || opt().no_fdec || p.seq != nullptr || (p.dbg & 0xff) != 0) return false;
+        if (p.N != 1 || o.no_fdec || p.seq != nullptr || (p.dbg & 0xff) != 0) return false;
         const int K = p.W.K, M = p.W.M;
         if (EPI == bgk::EPI_QKV && (p.D != K || p.dk <= 0)) return false;
         if (K == 1024 && M == 3072 && PRO == bgk::PRO_LN && EPI == bgk::EPI_QKV) hipLaunchKernelGGL((bgk::fdec_kernel<WT, PRO, EPI, 1024, 3>), dim3(256), dim3(256), 0, st, p);
@@ -568,28 +546,29 @@ bool try_launch_fdec(const bgk::MatvecParams &p, hipStream_t st, hipError_t &err
 }
 
 template <int WT, int PRO, int EPI>
-hipError_t launch_mv_typed(const bgk::MatvecParams &p, const MvShape &s, hipStream_t st, int *grid_out) {
+hipError_t launch_mv_typed(const EngineOptions &o, const bgk::MatvecParams &p, const MvShape &s, hipStream_t st, int *grid_out) {
     if (grid_out) *grid_out = s.grid;
     if constexpr (bgk::TypeInfo<WT>::quant) {
         hipError_t err = hipSuccess;
-        if (try_launch_fast<WT, PRO, EPI>(p, st, err, grid_out)) return err;
+        if (try_launch_fast<WT, PRO, EPI>(o, p, st, err, grid_out)) return err;
     } else {
         hipError_t err = hipSuccess;
-        if (try_launch_fdec<WT, PRO, EPI>(p, st, err)) return err;
+        if (try_launch_fdec<WT, PRO, EPI>(o, p, st, err)) return err;
     }
     return launch_mv_nc<WT, PRO, EPI>(p, s, st);
 }
 
+// o: the options of the context whose launch this is (LM_STREAM, NO_FDEC)
 template <int PRO, int EPI>
-hipError_t launch_mv(const bgk::MatvecParams &p, const MvShape &s, hipStream_t st, int *grid_out = nullptr) {
+hipError_t launch_mv(const EngineOptions &o, const bgk::MatvecParams &p, const MvShape &s, hipStream_t st, int *grid_out = nullptr) {
     switch (p.W.type) {
-        case T_F32: return launch_mv_typed<bgk::W_F32, PRO, EPI>(p, s, st, grid_out);
-        case T_F16: return launch_mv_typed<bgk::W_F16, PRO, EPI>(p, s, st, grid_out);
-        case T_Q4_0: return launch_mv_typed<bgk::W_Q4_0, PRO, EPI>(p, s, st, grid_out);
-        case T_Q4_1: return launch_mv_typed<bgk::W_Q4_1, PRO, EPI>(p, s, st, grid_out);
-        case T_Q5_0: return launch_mv_typed<bgk::W_Q5_0, PRO, EPI>(p, s, st, grid_out);
-        case T_Q5_1: return launch_mv_typed<bgk::W_Q5_1, PRO, EPI>(p, s, st, grid_out);
-        case T_Q8_0: return launch_mv_typed<bgk::W_Q8_0, PRO, EPI>(p, s, st, grid_out);
+        case T_F32: return launch_mv_typed<bgk::W_F32, PRO, EPI>(o, p, s, st, grid_out);
+        case T_F16: return launch_mv_typed<bgk::W_F16, PRO, EPI>(o, p, s, st, grid_out);
+        case T_Q4_0: return launch_mv_typed<bgk::W_Q4_0, PRO, EPI>(o, p, s, st, grid_out);
+        case T_Q4_1: return launch_mv_typed<bgk::W_Q4_1, PRO, EPI>(o, p, s, st, grid_out);
+        case T_Q5_0: return launch_mv_typed<bgk::W_Q5_0, PRO, EPI>(o, p, s, st, grid_out);
+        case T_Q5_1: return launch_mv_typed<bgk::W_Q5_1, PRO, EPI>(o, p, s, st, grid_out);
+        case T_Q8_0: return launch_mv_typed<bgk::W_Q8_0, PRO, EPI>(o, p, s, st, grid_out);
         default: return hipErrorInvalidValue;
     }
 }
@@ -611,8 +590,6 @@ bgk::MatvecParams mv_base(const biogpt_hip_ctx *c, const MatSlot &m, const MvSha
     p.k_pow2 = (m.K & (m.K - 1)) == 0;
     return p;
 }
-
-int target_wgs() { return opt().target_wgs; }
 
 hipError_t launch_lnq(const biogpt_hip_ctx *c, const float *x, int N, size_t ln_w, size_t ln_b, int q81, hipStream_t st) {
     const double inv_k = 1.0 / 1024.0;
@@ -680,19 +657,17 @@ bool ensure_tile_images(biogpt_hip_ctx *c) {
 bool fused_decode_ok(const biogpt_hip_ctx *c, int t_max) {
     const auto &hp = c->hp;
     return is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.n_head == 16 && t_max <= 1024 &&
-           hp.n_positions >= 64 && !c->opt.no_fast && !c->opt.no_chain && !c->opt.no_fused_decode;
+           hp.n_positions >= 64 && !c->opt.no_fused_decode;
 }
 
 // only: -1 = the five kernels of the layer in order; 0..4 = just that kernel (biogpt_hip_bench_matvec)
+// Workgroup shapes: 8 waves each (same-process sweeps, profiles/decode_shapes_r2.txt: 8 waves beat 16 and 4); the attention takes
+// 8 waves up to 128 keys and 16 beyond
 template <int WT>
 hipError_t launch_decode_layer(biogpt_hip_ctx *c, const bgk::DecQkvParams &a, const bgk::DecAttnParams &at, const bgk::DecOprojParams &op,
                                const bgk::DecFc1Params &f1, const bgk::DecFc2Params &f2, int only = -1) {
     hipStream_t st = c->stream;
-    if (only < 0 || only == 0) {
-        if (c->opt.qkv_waves == 8) hipLaunchKernelGGL((bgk::dec_qkv_kernel<WT, 8>), dim3(192), dim3(512), bgk::dec_qkv_smem_bytes(), st, a);
-        else if (c->opt.qkv_waves == 4) hipLaunchKernelGGL((bgk::dec_qkv_kernel<WT, 4>), dim3(384), dim3(256), bgk::dec_qkv_smem_bytes(), st, a);
-        else hipLaunchKernelGGL((bgk::dec_qkv_kernel<WT, 16>), dim3(96), dim3(1024), bgk::dec_qkv_smem_bytes(), st, a);
-    }
+    if (only < 0 || only == 0) hipLaunchKernelGGL((bgk::dec_qkv_kernel<WT, 8>), dim3(192), dim3(512), bgk::dec_qkv_smem_bytes(), st, a);
     if ((only < 0 || only == 1) && at.t_cap > 256) {
         // beyond 256 keys one workgroup per head would pull up to 512 KB of K / V through one compute unit: the keys of a head
         // are spread over H x T/64 workgroups in three dependent launches (attn_split_*_kernel, kernels_fast.hip.h)
@@ -707,36 +682,19 @@ hipError_t launch_decode_layer(biogpt_hip_ctx *c, const bgk::DecQkvParams &a, co
         hipLaunchKernelGGL(bgk::attn_split_pv_kernel, dim3(16, sa.n_split), dim3(256), 0, st, sa);
         hipLaunchKernelGGL(bgk::attn_split_combine_kernel, dim3(16), dim3(64), 0, st, sa);
     } else if (only < 0 || only == 1) {
-        if (c->opt.attn_waves == 8 && at.t_cap <= 64) hipLaunchKernelGGL((bgk::dec_attn_kernel<8, 8>), dim3(16), dim3(512), 0, st, at);
-        else if (c->opt.attn_waves == 8 && at.t_cap <= 128) hipLaunchKernelGGL((bgk::dec_attn_kernel<4, 8>), dim3(16), dim3(512), 0, st, at);
-        else if (at.t_cap <= 64) hipLaunchKernelGGL((bgk::dec_attn_kernel<16, 16>), dim3(16), dim3(1024), 0, st, at);
-        else if (at.t_cap <= 128) hipLaunchKernelGGL((bgk::dec_attn_kernel<8, 16>), dim3(16), dim3(1024), 0, st, at);
+        if (at.t_cap <= 64) hipLaunchKernelGGL((bgk::dec_attn_kernel<8, 8>), dim3(16), dim3(512), 0, st, at);
+        else if (at.t_cap <= 128) hipLaunchKernelGGL((bgk::dec_attn_kernel<4, 8>), dim3(16), dim3(512), 0, st, at);
         else hipLaunchKernelGGL((bgk::dec_attn_kernel<4, 16>), dim3(16), dim3(1024), 0, st, at);
     }
-    if (only < 0 || only == 2) {
-        if (c->opt.oproj_waves == 4) hipLaunchKernelGGL((bgk::dec_oproj_kernel<WT, 4>), dim3(128), dim3(256), bgk::dec_oproj_smem_bytes(4), st, op);
-        else if (c->opt.oproj_waves == 8) hipLaunchKernelGGL((bgk::dec_oproj_kernel<WT, 8>), dim3(64), dim3(512), bgk::dec_oproj_smem_bytes(8), st, op);
-        else hipLaunchKernelGGL((bgk::dec_oproj_kernel<WT, 16>), dim3(32), dim3(1024), bgk::dec_oproj_smem_bytes(16), st, op);
-    }
-    if (only < 0 || only == 3) {
-        if (c->opt.fc1_blocks == 2) hipLaunchKernelGGL((bgk::dec_fc1_kernel<WT, 2, 16>), dim3(64), dim3(1024), bgk::dec_fc1_smem_bytes<2>(), st, f1);
-        else if (c->opt.fc1_waves == 8) hipLaunchKernelGGL((bgk::dec_fc1_kernel<WT, 1, 8>), dim3(128), dim3(512), bgk::dec_fc1_smem_bytes<1>(), st, f1);
-        else if (c->opt.fc1_waves == 4) hipLaunchKernelGGL((bgk::dec_fc1_kernel<WT, 1, 4>), dim3(128), dim3(256), bgk::dec_fc1_smem_bytes<1>(), st, f1);
-        else hipLaunchKernelGGL((bgk::dec_fc1_kernel<WT, 1, 16>), dim3(128), dim3(1024), bgk::dec_fc1_smem_bytes<1>(), st, f1);
-    }
-    if (only < 0 || only == 4) {
-        if (c->opt.fc2_waves == 4) hipLaunchKernelGGL((bgk::dec_fc2_kernel<WT, 4>), dim3(256), dim3(256), bgk::dec_fc2_smem_bytes(4), st, f2);
-        else if (c->opt.fc2_waves == 8) hipLaunchKernelGGL((bgk::dec_fc2_kernel<WT, 8>), dim3(128), dim3(512), bgk::dec_fc2_smem_bytes(8), st, f2);
-        else hipLaunchKernelGGL((bgk::dec_fc2_kernel<WT, 16>), dim3(64), dim3(1024), bgk::dec_fc2_smem_bytes(16), st, f2);
-    }
+    if (only < 0 || only == 2) hipLaunchKernelGGL((bgk::dec_oproj_kernel<WT, 8>), dim3(64), dim3(512), bgk::dec_oproj_smem_bytes(8), st, op);
+    if (only < 0 || only == 3) hipLaunchKernelGGL((bgk::dec_fc1_kernel<WT, 1, 8>), dim3(128), dim3(512), bgk::dec_fc1_smem_bytes<1>(), st, f1);
+    if (only < 0 || only == 4) hipLaunchKernelGGL((bgk::dec_fc2_kernel<WT, 8>), dim3(128), dim3(512), bgk::dec_fc2_smem_bytes(8), st, f2);
     return hipGetLastError();
 }
 
 // grid of the single-token lm_head launch (launch_fast_k, K = 1024: 2 rows per wave step, 4 waves)
 int fast_lm_grid(const biogpt_hip_ctx *c) {
-    const int M = c->hp.n_vocab;
-    int steps = c->opt.lm_steps;
-    while (steps > 1 && (M + 8 * steps - 1) / (8 * steps) < 128) steps >>= 1;
+    const int M = c->hp.n_vocab, steps = lm_fast_steps(M, 2);
     return (M + 8 * steps - 1) / (8 * steps);
 }
 
@@ -747,7 +705,6 @@ int fast_lm_grid(const biogpt_hip_ctx *c) {
 struct ResidentArgs { int32_t tok0, n_past0; uint32_t seq0; int32_t spec0; };
 bool enqueue_decode_fused(biogpt_hip_ctx *c, int t_max, int tok_src, int advance, int l0 = 0, int l1 = -1, int only = -1, int n_tok = 1, float *host_row = nullptr,
                           bool *host_row_done = nullptr, int pl = -1, const ResidentArgs *ra = nullptr) {
-    t_ctx = c;
     (void)hipGetLastError();
     const auto &hp = c->hp;
     const int D = hp.d_model, V = hp.n_vocab, P = hp.n_positions;
@@ -852,7 +809,7 @@ bool enqueue_decode_fused(biogpt_hip_ctx *c, int t_max, int tok_src, int advance
     if (only >= 0 || only == -2 || l1 < hp.n_layer) return true;   // one kernel (bench) or a leading segment of the step: no lm_head
     {  // final LayerNorm + lm_head (last row only, F8) + per-workgroup arg-max partials; block 0 advances the position
         const MatSlot &m = c->plan.lm_head;
-        const MvShape s = mv_shape(m.type, m.M, m.K, target_wgs(), 1);
+        const MvShape s = mv_shape(m.type, m.M, m.K);
         bgk::MatvecParams p = mv_base(c, m, s);
         p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
         p.ldx = D; p.ldo = V; p.x = c->x; p.N = 1; p.out = c->logits;
@@ -860,7 +817,7 @@ bool enqueue_decode_fused(biogpt_hip_ctx *c, int t_max, int tok_src, int advance
         p.st_adv = c->state; p.adv = advance;
         p.lineage = c->seq_dev;
         int lm_grid = 0;
-        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(p, s, c->stream, &lm_grid)));
+        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, c->stream, &lm_grid)));
         if (lm_grid != lm_parts) BG_FAIL(false, "internal: lm_head grid %d != expected %d", lm_grid, lm_parts);
         c->lm_blocks = lm_grid;
     }
@@ -874,7 +831,7 @@ bool fpipe_prepare(biogpt_hip_ctx *c) {
     if (c->fp_state != 0) return c->fp_state == 1;
     c->fp_state = -1;
     const auto &hp = c->hp;
-    if (!c->opt.fpipe || c->opt.no_fast || hp.d_model != 1024 || hp.d_ff != 4096 || hp.n_head != 16 || hp.n_layer < 1 || c->device < 0 || c->device >= 64) return false;
+    if (!c->opt.fpipe || hp.d_model != 1024 || hp.d_ff != 4096 || hp.n_head != 16 || hp.n_layer < 1 || c->device < 0 || c->device >= 64) return false;
     int32_t wt = -1;
     for (const auto &L : c->plan.layers) {
         for (const MatSlot *m : {&L.qkv, &L.o, &L.fc1, &L.fc2}) {
@@ -984,7 +941,6 @@ bool xcols_usable(biogpt_hip_ctx *c, int N, int t_max) {
 
 // the N columns of the device state (upload_state) through all layers in one launch, then the ordinary final LayerNorm + lm_head launch on the LAST column (F8)
 bool enqueue_xcols(biogpt_hip_ctx *c, int N, int t_max, bool streams = false) {
-    t_ctx = c;
     (void)hipGetLastError();
     const auto &hp = c->hp;
     const int D = hp.d_model, V = hp.n_vocab, P = hp.n_positions;
@@ -1013,7 +969,7 @@ bool enqueue_xcols(biogpt_hip_ctx *c, int N, int t_max, bool streams = false) {
     if (streams) return true;      // every sequence's row: the caller's 8-column lm_head chain on c->x
     {  // final LayerNorm + lm_head of the last column + per-workgroup arg-max partials
         const MatSlot &m = c->plan.lm_head;
-        const MvShape s = mv_shape(m.type, m.M, m.K, target_wgs(), 1);
+        const MvShape s = mv_shape(m.type, m.M, m.K);
         bgk::MatvecParams p = mv_base(c, m, s);
         p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
         p.ldx = D; p.ldo = V;
@@ -1021,18 +977,22 @@ bool enqueue_xcols(biogpt_hip_ctx *c, int N, int t_max, bool streams = false) {
         if (s.grid > c->pmax_cap) BG_FAIL(false, "internal: arg-max partial buffer too small (%d > %d)", s.grid, c->pmax_cap);
         p.pmax_val = c->pmax_val; p.pmax_idx = c->pmax_idx;
         int lm_grid = 0;
-        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(p, s, c->stream, &lm_grid)));
+        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, c->stream, &lm_grid)));
         c->lm_blocks = lm_grid;
     }
     return true;
 }
+
+// Measured cross-overs of the many-column paths (HISTORY.md §4.7 / §4.8): the chain runs on the int8 matrix cores from 48 columns in the decode
+// steps of many sequences and from 64 in passes (below, the 8-column VALU kernels are faster); a pass takes the grouped-query attention from
+// 80 columns, a decode step of many sequences the slim attention kernel from 48; one query beyond 256 keys spreads its head over the chip
+constexpr int MFMA_MIN_DECODE_COLS = 48, MFMA_MIN_PASS_COLS = 64, GROUPED_ATTN_MIN_COLS = 80, SLIM_ATTN_MIN_COLS = 48, SPLIT_ATTN_ABOVE_KEYS = 256;
 
 // batch: one column per sequence (decode step).  cols != null: the columns are prompt tokens of several sequences
 // (column states with seq_id / t_vis), no lm_head -- the caller gets the logits from the following decode step.
 // score (with all_rows): the logits of EVERY column into logits_all on the fastest lm_head for the model (biogpt_hip_score*);
 // prompt columns of several sequences (batch + cols) get them too.
 bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool batch = false, const bgk::SeqState *cols = nullptr, bool score = false) {
-    t_ctx = c;
     (void)hipGetLastError();   // a failed call of some OTHER context / API leaves its code behind; the checks below are about these launches
     if (score) all_rows = true;   // every row is needed: none of the launches that keep the activations on chip and compute the last row only
     if (N < 1 || N > c->hp.n_positions) BG_FAIL(false, "internal: a pass of %d columns exceeds the %d-column activation scratch", N, c->hp.n_positions);
@@ -1042,7 +1002,6 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
     const int D = hp.d_model, F = hp.d_ff, V = hp.n_vocab, H = hp.n_head, P = hp.n_positions;
     const int dk = D / H;
     hipStream_t st = c->stream;
-    const int tw = target_wgs();
     // attention workgroup size: a thread owns up to ATTN_MAXK whole keys, so T <= 4 * threads
     int attn_threads = 256;
     while (attn_threads < 1024 && t_max > attn_threads) attn_threads <<= 1;  // ~1 key per thread when possible
@@ -1051,12 +1010,10 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
 
     // single-token fast chain: BioGPT-base shapes, block-quantized weights -> producer-side Q8 hand-offs
     const int32_t wt = ftype_to_type(hp.ftype);
-    const bool chain = is_quantized(wt) && D == 1024 && F == 4096 && dk == 64 && t_max <= 1024 &&
-                       !opt().no_fast && !opt().no_chain;
+    const bool chain = is_quantized(wt) && D == 1024 && F == 4096 && dk == 64 && t_max <= 1024;
     const bool pchain = chain && (N > 1 || batch);   // several columns: LayerNorm+Q8 once per site (lnq_kernel), 8 columns per workgroup
     // enough columns to fill 16-wide MFMA tiles: the chain runs on the int8 matrix cores from the row-tiled weight image
-    // (measured cross-overs: decode steps of S sequences 48; prompt passes 64 columns)
-    const bool mfma = pchain && N >= opt().mfma_min((batch && !cols) ? 48 : 64) && c->tile_img != nullptr;
+    const bool mfma = pchain && N >= ((batch && !cols) ? MFMA_MIN_DECODE_COLS : MFMA_MIN_PASS_COLS) && c->tile_img != nullptr;
     bgk::DevMatrix img;
     auto tile = [&](const MatSlot &m) -> const bgk::DevMatrix * { if (!mfma) return nullptr; img = tile_matrix(c, m); return &img; };
     if (batch && !chain) BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
@@ -1080,7 +1037,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
     for (int l = 0; l < hp.n_layer && !xc_streams && !fp_one; l++) {
         const LayerSlots &L = c->plan.layers[(size_t)l];
         {  // LN0 + fused q/k/v projection + bias + Q scale + KV append
-            const MvShape s = mv_shape(L.qkv.type, L.qkv.M, L.qkv.K, tw, N);
+            const MvShape s = mv_shape(L.qkv.type, L.qkv.M, L.qkv.K);
             bgk::MatvecParams p = mv_base(c, L.qkv, s);
             p.x = c->x; p.ldx = D; p.N = N;
             p.ln_w = dev_vec(c, L.ln0_w); p.ln_b = dev_vec(c, L.ln0_b);
@@ -1095,7 +1052,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
                 p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
                 HIP_TRY(false, launch_chain(CHAIN_QKV_Q8, p, st, tile(L.qkv)));
             } else {
-                HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_QKV>(p, s, st)));
+                HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_QKV>(c->opt, p, s, st)));
             }
         }
         {  // attention
@@ -1108,16 +1065,15 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
             a.dbg = c->opt.dbg; a.tstamp = c->tstamp;
             a.q81 = q81;
             if (chain) { a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; }
-            if (!batch && dk == 64 && t_max <= 1024 && N >= opt().attn_group_min && !opt().no_fast) {
+            if (!batch && dk == 64 && t_max <= 1024 && N >= GROUPED_ATTN_MIN_COLS) {
                 // a pass of many query columns: register-tiled kernel, 16 queries per workgroup share every K / V row they load
-                // (BIOGPT_HIP_ATTN_TILE=0: the first grouped kernel, 8 queries per workgroup, kept as the A/B arm of the equivalence test)
                 a.t_cap = std::min(P, t_max);
                 // (the tile kernel addresses a thread's four consecutive key rows from ONE base clamped to P - 4: that is only their own rows when 4 | P and P >= 4;
-                //  any other table size takes the grouped kernel, which clamps row by row)
-                if (opt().attn_tile && (P & 3) == 0 && P >= 4) {
+                //  any other table size takes the grouped kernel, 8 queries per workgroup, which clamps row by row)
+                if ((P & 3) == 0 && P >= 4) {
                     // up to 640 keys the K / V rows of the two MAC loops travel through a ring in LDS, two steps ahead (global_load_lds); beyond, the ring has no room
                     // beside the scores in a 2-workgroups-per-compute-unit footprint: loads at the top of each step
-                    const bool dma = bgk::attn_tile_dma_ok(a.t_cap) && opt().attn_tile != 2;      // (BIOGPT_HIP_ATTN_TILE=2: the A/B arm without the ring)
+                    const bool dma = bgk::attn_tile_dma_ok(a.t_cap);
                     const size_t smb = bgk::attn_tile_smem_bytes<16>(a.t_cap);
                     const void *fn = dma ? reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, true>) : reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, false>);
                     if (smb > 64 * 1024 && !c->lds_attr_done.count(fn)) {
@@ -1129,12 +1085,11 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
                 } else {
                     hipLaunchKernelGGL((bgk::attn_group_kernel<8>), dim3(H, (N + 7) / 8), dim3(512), bgk::attn_group_smem_bytes(a.t_cap), st, a);
                 }
-            } else if (dk == 64 && t_max <= 1024 && !opt().no_fast) {
+            } else if (dk == 64 && t_max <= 1024) {
                 // loads are bounded by t_cap (= P when the table is not a multiple of 64; the workgroup stays whole
                 // waves); 4 lanes per key, 16 prefetched V rows per lane
                 a.t_cap = std::min(P, (t_max + 63) & ~63);
-                const int split_min = opt().split_min;
-                if (N == 1 && !batch && a.t_cap > split_min) {
+                if (N == 1 && !batch && a.t_cap > SPLIT_ATTN_ABOVE_KEYS) {
                     // long context, one query: spread the head's keys over the chip (three dependent launches)
                     a.sp_scores = c->sp_scores; a.sp_max = c->sp_max; a.sp_pv = c->sp_pv;
                     a.n_split = (a.t_cap + bgk::SPLIT_KEYS - 1) / bgk::SPLIT_KEYS;
@@ -1142,7 +1097,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
                     hipLaunchKernelGGL(bgk::attn_split_scores_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
                     hipLaunchKernelGGL(bgk::attn_split_pv_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
                     hipLaunchKernelGGL(bgk::attn_split_combine_kernel, dim3(H), dim3(64), 0, st, a);
-                } else if (batch && N >= opt().attn_slim_min) {
+                } else if (batch && N >= SLIM_ATTN_MIN_COLS) {
                     // many (sequence, head) workgroups: throughput over latency -- one lane quad per 4 keys (4 key passes), a
                     // quarter of the threads, four times as many workgroups resident per compute unit
                     const int t64 = (a.t_cap + 63) & ~63;
@@ -1159,7 +1114,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
             }
         }
         {  // out_proj + bias + residual
-            const MvShape s = mv_shape(L.o.type, L.o.M, L.o.K, tw, N);
+            const MvShape s = mv_shape(L.o.type, L.o.M, L.o.K);
             bgk::MatvecParams p = mv_base(c, L.o, s);
             p.x = c->att; p.ldx = D; p.N = N;
             p.bias = dev_vec(c, L.o_b);
@@ -1168,11 +1123,11 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
                 p.aq_q = c->aq_q[0]; p.aq_d = c->aq_d[0]; p.aq_s = c->aq_s[0];
                 HIP_TRY(false, launch_chain(CHAIN_OPROJ, p, st, tile(L.o)));
             } else {
-                HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(p, s, st)));
+                HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
             }
         }
         {  // LN1 + fc1 + bias + GELU
-            const MvShape s = mv_shape(L.fc1.type, L.fc1.M, L.fc1.K, tw, N);
+            const MvShape s = mv_shape(L.fc1.type, L.fc1.M, L.fc1.K);
             bgk::MatvecParams p = mv_base(c, L.fc1, s);
             p.x = c->x1; p.ldx = D; p.N = N;
             p.ln_w = dev_vec(c, L.ln1_w); p.ln_b = dev_vec(c, L.ln1_b);
@@ -1187,11 +1142,11 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
                 p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
                 HIP_TRY(false, launch_chain(CHAIN_FC1, p, st));
             } else {
-                HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_GELU>(p, s, st)));
+                HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_GELU>(c->opt, p, s, st)));
             }
         }
         {  // fc2 + bias + residual
-            const MvShape s = mv_shape(L.fc2.type, L.fc2.M, L.fc2.K, tw, N);
+            const MvShape s = mv_shape(L.fc2.type, L.fc2.M, L.fc2.K);
             bgk::MatvecParams p = mv_base(c, L.fc2, s);
             p.x = c->h; p.ldx = F; p.N = N;
             p.bias = dev_vec(c, L.fc2_b);
@@ -1200,7 +1155,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
                 p.aq_q = c->aq_q[1]; p.aq_d = c->aq_d[1]; p.aq_s = c->aq_s[1];
                 HIP_TRY(false, launch_chain(CHAIN_FC2, p, st, tile(L.fc2)));
             } else {
-                HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(p, s, st)));
+                HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
             }
         }
     }
@@ -1213,7 +1168,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
     if (fin == Final::None) return true;
     if (fin == Final::AllRowsQ8) {  // every column needs its logits row: LayerNorm+Q8 once, then the 8-column mat-vec (matrix cores from 64 columns)
         const MatSlot &m = c->plan.lm_head;
-        const MvShape s = mv_shape(m.type, m.M, m.K, tw, N);
+        const MvShape s = mv_shape(m.type, m.M, m.K);
         bgk::MatvecParams p = mv_base(c, m, s);
         HIP_TRY(false, launch_lnq(c, c->x, N, c->plan.ln_w, c->plan.ln_b, q81, st));
         p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
@@ -1224,7 +1179,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
     {  // final LayerNorm + lm_head; only the rows that are returned (F8)
         const MatSlot &m = c->plan.lm_head;
         const bool rows = fin == Final::AllRows;
-        const MvShape s = mv_shape(m.type, m.M, m.K, tw, rows ? N : 1);
+        const MvShape s = mv_shape(m.type, m.M, m.K);
         bgk::MatvecParams p = mv_base(c, m, s);
         p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
         p.ldx = D; p.ldo = V;
@@ -1236,7 +1191,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
             p.pmax_val = c->pmax_val; p.pmax_idx = c->pmax_idx;
         }
         int lm_grid = 0;
-        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(p, s, st, &lm_grid)));
+        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, st, &lm_grid)));
         if (!rows) c->lm_blocks = lm_grid;
     }
     return true;
@@ -1687,12 +1642,8 @@ int biogpt_hip_merge(const biogpt_hip_ctx *ctx, int32_t rank, const char **bytes
 
 #include "engine_resident.inc"
 
-// low-latency wait for everything enqueued on the context's stream (the caller is blocked on this token anyway).  BIOGPT_HIP_EVAL_SYNC=1: hipStreamSynchronize instead
-// (diagnostic)
+// low-latency wait for everything enqueued on the context's stream (the caller is blocked on this token anyway)
 static bool poll_stream(biogpt_hip_ctx *ctx) {
-    if (ctx->opt.eval_sync == 1) { HIP_TRY(false, hipStreamSynchronize(ctx->stream)); return true; }
-    if (ctx->opt.eval_sync == 2) { HIP_TRY(false, hipDeviceSynchronize()); return true; }
-    if (ctx->opt.eval_sync == 3) { HIP_TRY(false, hipEventRecord(ctx->ev1, ctx->stream)); HIP_TRY(false, hipEventSynchronize(ctx->ev1)); return true; }
     for (;;) {
         const hipError_t q = hipStreamQuery(ctx->stream);
         if (q == hipSuccess) return true;
@@ -2028,7 +1979,7 @@ int biogpt_hip_eval_all(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, i
 bool enqueue_prompt(biogpt_hip_ctx *c, const int32_t *tokens, int n, int n_past, int n_batch, int *last_cols = nullptr) {
     const int max_cols = std::max(1, c->opt.prompt_cols);   // measured (Q4_0, -b 8, 512-token prompt): 16 -> 17.9k, 64 -> 36k, 128 -> 66k, 256 -> 87k, 512 -> 97k prompt tok/s
     const int group = n_batch >= max_cols ? n_batch : (max_cols / n_batch) * n_batch;   // whole chunks per pass
-    if (std::min(group, n) >= c->opt.mfma_min(64) && is_quantized(ftype_to_type(c->hp.ftype)) && !ensure_tile_images(c)) return false;
+    if (std::min(group, n) >= MFMA_MIN_PASS_COLS && is_quantized(ftype_to_type(c->hp.ftype)) && !ensure_tile_images(c)) return false;
     for (int at = 0; at < n;) {
         const int m = std::min(group, n - at);
         if (!upload_state(c, tokens + at, m, n_past + at, m > n_batch ? n_batch : 0)) return false;
@@ -2291,7 +2242,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     {   // matrix-core chain: decode steps have n_seqs columns, the prompt pass all prompt tokens; build the tiled weights before any graph capture
         long total = 0;
         for (int s = 0; s < n_seqs; s++) total += prompt_lens[s];
-        if (std::max<long>(n_seqs, total) >= ctx->opt.mfma_min(48) && !ensure_tile_images(ctx)) return -2;
+        if (std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return -2;
     }
     if ((size_t)n_seqs > ctx->logits_all_rows) {
         if (ctx->logits_all) (void)hipFree(ctx->logits_all);
@@ -2451,7 +2402,7 @@ static int score_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int
     // the passes of biogpt_hip_eval_prompt(tokens, n_past, n_batch = 1): same borders, same K / V rows
     const int max_cols = std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
     const int first = std::min(max_cols, (int)n);
-    if (first >= ctx->opt.mfma_min(64) && is_quantized(ftype_to_type(ctx->hp.ftype)) && !ensure_tile_images(ctx)) return -2;
+    if (first >= MFMA_MIN_PASS_COLS && is_quantized(ftype_to_type(ctx->hp.ftype)) && !ensure_tile_images(ctx)) return -2;
     if (!ensure_logits_rows(ctx, (size_t)first) || !score_setup(ctx, tokens, &n, 1, targets, (size_t)n)) return -2;
     const int V = ctx->hp.n_vocab;
     for (int at = 0; at < n;) {
@@ -2475,7 +2426,7 @@ static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");   // each sequence owns a full F32 KV cache
     const auto &hp = ctx->hp;
-    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64 && !ctx->opt.no_fast && !ctx->opt.no_chain))
+    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
         BG_FAIL(-1, "batched scoring needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
     size_t total = 0;
     for (int s = 0; s < n_seqs; s++) {
@@ -2489,7 +2440,7 @@ static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     // every sequence from position 0 in its own K / V cache (bk / bv): the context's own cache and position stay as they are
     const size_t max_cols = (size_t)std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
     if (!ensure_seq_caches(ctx, n_seqs)) return -2;
-    if ((long)std::min(max_cols, total) >= ctx->opt.mfma_min(64) && !ensure_tile_images(ctx)) return -2;
+    if ((long)std::min(max_cols, total) >= MFMA_MIN_PASS_COLS && !ensure_tile_images(ctx)) return -2;
     if (!ensure_logits_rows(ctx, std::min(max_cols, total)) || !score_setup(ctx, seqs, lens, n_seqs, targets, total)) return -2;
     if (!pack_column_passes(ctx, seqs, lens, n_seqs, 1, [&](int n_cols, int t_max, size_t flat0) {
             return enqueue_forward(ctx, n_cols, true, t_max, true, ctx->cols, true) && enqueue_logprob(ctx, n_cols, flat0, total);

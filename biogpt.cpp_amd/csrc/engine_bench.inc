@@ -9,15 +9,12 @@ int biogpt_hip_bench_matvec(biogpt_hip_ctx *ctx, int which, int layer, int reps,
     if (which >= 6 && which < 12 && !fused_decode_ok(ctx, 104)) BG_FAIL(-1, "the five-launch decode layer needs BioGPT-base shapes and block-quantized weights");
     HIP_TRY(-2, hipSetDevice(ctx->device));
     if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    t_ctx = ctx;
     const auto &hp = ctx->hp;
     const int D = hp.d_model, F = hp.d_ff, V = hp.n_vocab, P = hp.n_positions;
-    const int tw = target_wgs();
     // cycling through the layers defeats L2 residency of one matrix (SURVEY 8d); the whole model still
     // fits the 256 MiB Infinity Cache -- stated in DESIGN.md
     const int32_t wt0 = ftype_to_type(hp.ftype);
-    const bool chain = is_quantized(wt0) && D == 1024 && F == 4096 && D / hp.n_head == 64 && P <= 1024 &&
-                       !opt().no_fast && !opt().no_chain;
+    const bool chain = is_quantized(wt0) && D == 1024 && F == 4096 && D / hp.n_head == 64 && P <= 1024;
     // which == 12: the stand-alone lm_head with its weights NOT resident in the Infinity Cache: 14 copies of the matrix (Q4_0: 14 x 24.6 MB = 344 MB > 256 MB + the L2s),
     // a different one every launch -- the figure `north_star`'s "HBM roofline" means; which == 4 reads the one copy the model owns, which stays cache-resident between launches
     struct ColdCopies {
@@ -67,37 +64,37 @@ int biogpt_hip_bench_matvec(biogpt_hip_ctx *ctx, int which, int layer, int reps,
         }
         const LayerSlots &L = ctx->plan.layers[(size_t)(hp.n_layer ? l % hp.n_layer : 0)];
         if (which == 0) {
-            const MvShape s = mv_shape(L.fc1.type, L.fc1.M, L.fc1.K, tw);
+            const MvShape s = mv_shape(L.fc1.type, L.fc1.M, L.fc1.K);
             bgk::MatvecParams p = mv_base(ctx, L.fc1, s);
             p.x = ctx->x1; p.ldx = D; p.N = 1; p.ln_w = dev_vec(ctx, L.ln1_w); p.ln_b = dev_vec(ctx, L.ln1_b);
             p.bias = dev_vec(ctx, L.fc1_b); p.out = ctx->h; p.ldo = F;
             if (chain) { p.oq_q = ctx->aq_q[1]; p.oq_d = ctx->aq_d[1]; p.oq_s = ctx->aq_s[1]; HIP_TRY(false, launch_chain(CHAIN_FC1, p, ctx->stream)); }
-            else HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_GELU>(p, s, ctx->stream)));
+            else HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_GELU>(ctx->opt, p, s, ctx->stream)));
         } else if (which == 1) {
-            const MvShape s = mv_shape(L.fc2.type, L.fc2.M, L.fc2.K, tw);
+            const MvShape s = mv_shape(L.fc2.type, L.fc2.M, L.fc2.K);
             bgk::MatvecParams p = mv_base(ctx, L.fc2, s);
             p.x = ctx->h; p.ldx = F; p.N = 1; p.bias = dev_vec(ctx, L.fc2_b);
             p.resid = ctx->x1; p.ldr = D; p.out = ctx->x; p.ldo = D;
             if (chain) { p.aq_q = ctx->aq_q[1]; p.aq_d = ctx->aq_d[1]; p.aq_s = ctx->aq_s[1]; HIP_TRY(false, launch_chain(CHAIN_FC2, p, ctx->stream)); }
-            else HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(p, s, ctx->stream)));
+            else HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(ctx->opt, p, s, ctx->stream)));
         } else if (which == 2) {
-            const MvShape s = mv_shape(L.qkv.type, L.qkv.M, L.qkv.K, tw);
+            const MvShape s = mv_shape(L.qkv.type, L.qkv.M, L.qkv.K);
             bgk::MatvecParams p = mv_base(ctx, L.qkv, s);
             p.x = ctx->x; p.ldx = D; p.N = 1; p.ln_w = dev_vec(ctx, L.ln0_w); p.ln_b = dev_vec(ctx, L.ln0_b);
             p.bias = dev_vec(ctx, L.qkv_b); p.q_out = ctx->q;
             p.kcache = ctx->memory_k + (size_t)(l % hp.n_layer) * P * D; p.vcache = ctx->memory_v + (size_t)(l % hp.n_layer) * P * D;
             p.q_scale = 0.125f;
-            HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_QKV>(p, s, ctx->stream)));
+            HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_QKV>(ctx->opt, p, s, ctx->stream)));
         } else if (which == 3) {
-            const MvShape s = mv_shape(L.o.type, L.o.M, L.o.K, tw);
+            const MvShape s = mv_shape(L.o.type, L.o.M, L.o.K);
             bgk::MatvecParams p = mv_base(ctx, L.o, s);
             p.x = ctx->att; p.ldx = D; p.N = 1; p.bias = dev_vec(ctx, L.o_b);
             p.resid = ctx->x; p.ldr = D; p.out = ctx->x1; p.ldo = D;
             if (chain) { p.aq_q = ctx->aq_q[0]; p.aq_d = ctx->aq_d[0]; p.aq_s = ctx->aq_s[0]; HIP_TRY(false, launch_chain(CHAIN_OPROJ, p, ctx->stream)); }
-            else HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(p, s, ctx->stream)));
+            else HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(ctx->opt, p, s, ctx->stream)));
         } else {
             const MatSlot &m = ctx->plan.lm_head;
-            const MvShape s = mv_shape(m.type, m.M, m.K, tw);
+            const MvShape s = mv_shape(m.type, m.M, m.K);
             bgk::MatvecParams p = mv_base(ctx, m, s);
             p.x = ctx->x; p.ldx = D; p.N = 1; p.ln_w = dev_vec(ctx, ctx->plan.ln_w); p.ln_b = dev_vec(ctx, ctx->plan.ln_b);
             p.out = ctx->logits; p.ldo = V; p.pmax_val = ctx->pmax_val; p.pmax_idx = ctx->pmax_idx;
@@ -105,7 +102,7 @@ int biogpt_hip_bench_matvec(biogpt_hip_ctx *ctx, int which, int layer, int reps,
                 const uint8_t *q = cold.v[(size_t)l % cold.v.size()];
                 p.W.qs = q; p.W.sc = q + cold_sc_off; p.W.qh = reinterpret_cast<const uint32_t *>(q + cold_qh_off);
             }
-            HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(p, s, ctx->stream)));
+            HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(ctx->opt, p, s, ctx->stream)));
         }
         return true;
     };
@@ -151,8 +148,8 @@ int biogpt_hip_bench_matvec(biogpt_hip_ctx *ctx, int which, int layer, int reps,
     if (stamps) {  // timeline of the last two launches (A then B), shader-clock cycles
         const MatSlot *mm = which == 0 ? &ctx->plan.layers[0].fc1 : which == 1 ? &ctx->plan.layers[0].fc2
                           : which == 2 ? &ctx->plan.layers[0].qkv : which == 3 ? &ctx->plan.layers[0].o : &ctx->plan.lm_head;
-        int grid = mv_shape(mm->type, mm->M, mm->K, tw).grid;
-        if (which == 4 && ctx->opt.lm_stream && ctx->opt.lm_steps == 8 && mm->K == 1024 && is_quantized(mm->type) && !ctx->opt.no_fast) grid = ((mm->M + 63) / 64 + 2) / 3;      // lm_stream_kernel's
+        int grid = mv_shape(mm->type, mm->M, mm->K).grid;
+        if (which == 4 && ctx->opt.lm_stream && mm->K == 1024 && is_quantized(mm->type)) grid = ((mm->M + 63) / 64 + 2) / 3;      // lm_stream_kernel's
         std::vector<unsigned long long> h(2 * (size_t)grid * 8);
         HIP_TRY(-2, hipMemcpy(h.data(), ctx->tstamp, h.size() * 8, hipMemcpyDeviceToHost));
         const int pb = ctx->launch_parity, pa = pb ^ 1;  // B = last launch, A = the one before
@@ -179,7 +176,7 @@ int biogpt_hip_bench_matvec(biogpt_hip_ctx *ctx, int which, int layer, int reps,
             for (const auto &L : ctx->plan.layers)
                 for (const MatSlot *m : {&L.qkv, &L.o, &L.fc1, &L.fc2}) b += (double)file_row_bytes(m->type, m->K) * (double)m->M;
             b += hp.n_layer * (2.0 * 104 * D * 4 + 2.0 * D * 4) + 8.0 * D;
-            if (which == 11 && ctx->opt.xpipe_lm) b += (double)file_row_bytes(ctx->plan.lm_head.type, ctx->plan.lm_head.K) * (double)ctx->plan.lm_head.M + 4.0 * V;   // + the output projection and the logits row
+            if (which == 11) b += (double)file_row_bytes(ctx->plan.lm_head.type, ctx->plan.lm_head.K) * (double)ctx->plan.lm_head.M + 4.0 * V;   // + the output projection and the logits row
             *bytes_out = b;
             return 0;
         }
@@ -368,7 +365,6 @@ int biogpt_hip_bench_stream(biogpt_hip_ctx *ctx, int32_t rows, int reps, int ste
     if (ctx->hp.d_model != 1024 || rows < 1024 || rows % 1024 || reps < 1 || steps < 2) BG_FAIL(-1, "bad argument");
     HIP_TRY(-2, hipSetDevice(ctx->device));
     if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    t_ctx = ctx;
     const size_t nblk = (size_t)rows * 32;
     uint8_t *qs = nullptr, *sc = nullptr;
     float *out = nullptr;
@@ -499,8 +495,7 @@ int biogpt_hip_bench_decode(biogpt_hip_ctx *ctx, int32_t n_past, int reps, doubl
         const int nk = 5 * ctx->hp.n_layer;
         std::vector<unsigned long long> w((size_t)nk * 2048);
         HIP_TRY(-2, hipMemcpy(w.data(), ctx->tstamp + 128, w.size() * 8, hipMemcpyDeviceToHost));
-        const int grids[5] = {ctx->opt.qkv_waves == 8 ? 192 : ctx->opt.qkv_waves == 4 ? 384 : 96, 16, ctx->opt.oproj_waves == 4 ? 128 : ctx->opt.oproj_waves == 8 ? 64 : 32, ctx->opt.fc1_blocks == 2 ? 64 : 128,
-                              ctx->opt.fc2_waves == 4 ? 256 : ctx->opt.fc2_waves == 8 ? 128 : 64};
+        const int grids[5] = {192, 16, 64, 128, 128};      // launch_decode_layer's workgroups
         const char *kn[5] = {"dec_qkv  ", "dec_attn ", "dec_oproj", "dec_fc1  ", "dec_fc2  "};
         double acc[5][5] = {};
         unsigned long long prev_exit = 0;

@@ -207,7 +207,7 @@ void xpipe_prepare(biogpt_hip_ctx *c) {
         xpipe_release(c);
         return;
     }
-    if (hp.n_positions > 256 && c->opt.xpipe_long) {   // contexts beyond 256 keys: the key-range helpers' granules (393 KB per layer); without them those contexts keep the five-launch layer
+    if (hp.n_positions > 256) {   // contexts beyond 256 keys: the key-range helpers' granules (393 KB per layer); without them those contexts keep the five-launch layer
         const size_t lbytes = (size_t)hp.n_layer * bgk::XL_G_LAYER * 8;
         if (hipMalloc(&c->xp_gran_l, lbytes) != hipSuccess || hipMemset(c->xp_gran_l, 0, lbytes) != hipSuccess) {
             (void)hipGetLastError();
@@ -223,7 +223,7 @@ void xpipe_prepare(biogpt_hip_ctx *c) {
     }
     {
         // the GELU table, rebuilt exactly as upload_weights builds it: identity from some positive argument up to +inf, one constant from some negative
-        // argument down to the most negative finite value
+        // argument down to the most negative finite value; the MLP halves keep its non-trivial slices in LDS (70 KB)
         std::vector<uint16_t> tg(65536);
         for (uint32_t i = 0; i < 65536; i++) tg[i] = f32_to_f16(gelu_tanh_f32(f16_to_f32((uint16_t)i)));
         int P = 0x7C01;
@@ -233,11 +233,9 @@ void xpipe_prepare(biogpt_hip_ctx *c) {
         while (N > 0 && tg[0x8000 + (size_t)N - 1] == Z) N--;
         P = (P + 7) & ~7; N = (N + 7) & ~7;
         const size_t lds_max = 160 * 1024;
-        if (c->opt.xpipe_tables & 1) {
-            if (P <= 0x7C00 && N <= 0x7C00 && bgk::xpipe_smem_bytes(P + N) <= lds_max) { c->xp_gelu_p = P; c->xp_gelu_n = N; c->xp_gelu_z = Z; }
-        }
+        if (P <= 0x7C00 && N <= 0x7C00 && bgk::xpipe_smem_bytes(P + N) <= lds_max) { c->xp_gelu_p = P; c->xp_gelu_n = N; c->xp_gelu_z = Z; }
     }
-    if ((c->opt.xpipe_tables & 2) && c->xp_gelu_p + c->xp_gelu_n > 0) {
+    if (c->xp_gelu_p + c->xp_gelu_n > 0) {
         // ggml_soft_max's table, rebuilt exactly as upload_weights builds it: arguments are <= 0; entry [0] must be 1.0 and the entries 0 from some negative argument
         // down to the most negative finite value; the slice in between shares the LDS region of the GELU slices (which only the MLP halves use)
         std::vector<uint16_t> te(0x7C00);
@@ -254,7 +252,7 @@ void xpipe_prepare(biogpt_hip_ctx *c) {
 
 // may a step of context bucket t_max go through the pipeline at all (model, device, options, bucket) ?
 bool xpipe_bucket_ok(const biogpt_hip_ctx *c, int t_max) {
-    return c->opt.xpipe && c->xp_state == 1 && (t_max <= 256 || (t_max <= 1024 && c->xp_gran_l != nullptr && c->opt.xpipe_long)) && c->device >= 0 && c->device < 64;
+    return c->opt.xpipe && c->xp_state == 1 && (t_max <= 256 || (t_max <= 1024 && c->xp_gran_l != nullptr)) && c->device >= 0 && c->device < 64;
 }
 // ... and does this context hold the device's pipeline slot ?  Taken here if it is free -- or if its holder is outside every API call that took it and
 // has nothing in flight (a resident launch that left after its idle time keeps the slot until its context is called again: such a holder is relieved here;
@@ -356,7 +354,7 @@ bool xpipe_lm_folds(const biogpt_hip_ctx *c) {
     const MatSlot &m = c->plan.lm_head;
     // workgroups that take rows: the pipelined launch up to 256 keys (kernels_xpipe.hip.h, xp_lm_rank) and the long-context one (kernels_xlong.hip.h: every XCD but XCD 0 and the last unit's)
     const int lm_parts = fast_lm_grid(c), last_xcd = xpipe_last_xcd(c), lm_wgs = std::min(bgk::xp_lm_capacity(2 * hp.n_layer), 32 * (8 - 1 - (last_xcd != 0 ? 1 : 0)));
-    return c->opt.xpipe_lm && m.type == ftype_to_type(hp.ftype) && m.K == 1024 && m.M == hp.n_vocab && lm_parts == (hp.n_vocab + 63) / 64 && lm_parts <= 4 * lm_wgs && lm_parts <= 1024;
+    return m.type == ftype_to_type(hp.ftype) && m.K == 1024 && m.M == hp.n_vocab && lm_parts == (hp.n_vocab + 63) / 64 && lm_parts <= 4 * lm_wgs && lm_parts <= 1024;
 }
 int xpipe_multi_tokens(biogpt_hip_ctx *c, int T) {
     if (!c->opt.xpipe_multi || !xpipe_lm_folds(c)) return 0;

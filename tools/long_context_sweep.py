@@ -1,5 +1,5 @@
 """Decode time per token vs context length (captured graph replay at fixed n_past), BioGPT-base Q4_0.
-    python tools/long_context_sweep.py [n_past ...]   # BIOGPT_HIP_SPLIT_MIN=100000 disables the key-split attention
+    python tools/long_context_sweep.py [n_past ...]
 """
 import os
 import sys
@@ -18,7 +18,6 @@ if not os.path.exists(q):
 m = pkg.BiogptModel.load(q, verbosity=0)
 m.generate_greedy([2, 5, 6, 7], 8)
 hp = m.hparams if hasattr(m, "hparams") else None
-print("split_min =", os.environ.get("BIOGPT_HIP_SPLIT_MIN", "default"))
 points = [int(a) for a in sys.argv[1:]] or [63, 103, 255, 256, 300, 383, 511, 512, 700, 1023]
 for n_past in points:
     t = m.bench_decode(n_past, reps=200)

@@ -1,5 +1,5 @@
 """Time to ingest a prompt of n tokens (-b 8 semantics, biogpt_hip_eval_prompt), BioGPT-base Q4_0:
-    python tools/prompt_sweep.py [n ...]      (BIOGPT_HIP_MFMA_MIN_COLS / BIOGPT_HIP_ATTN_GROUP_MIN select the kernels)"""
+    python tools/prompt_sweep.py [n ...]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
