@@ -100,6 +100,8 @@ SYMBOLS = [
     ("biogpt_hip_eval_prompt", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     ("biogpt_hip_generate_greedy", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_generate_greedy_batch", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_generate_beam", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P,
+                                          C.POINTER(C.c_double)]),
     ("biogpt_hip_score", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_score_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_read_kv", C.c_int, [_P, C.c_int, C.c_size_t, C.c_size_t, _P]),
@@ -401,6 +403,26 @@ class BiogptModel:
         if n < 0:
             raise BiogptError(_err())
         return out.reshape(-1)[:len(prompts) * n].reshape(len(prompts), n).copy(), secs.value
+
+    def generate_beam(self, prompt, n_predict, n_beams=5, eos_id=2, length_penalty=1.0, early_stopping=True, n_batch=8):
+        """Beam search (transformers' num_beams with do_sample=False).  Returns ([(ids int32[len], score), ...] best first,
+        seconds): each hypothesis's generated ids (an EOS that ended it included) and its normalized score."""
+        pr = np.ascontiguousarray(prompt, dtype=np.int32)
+        w = max(int(n_predict), 1)
+        out = np.zeros((max(int(n_beams), 1), w), dtype=np.int32)
+        lens = np.zeros(max(int(n_beams), 1), dtype=np.int32)
+        scores = np.zeros(max(int(n_beams), 1), dtype=np.float32)
+        secs = C.c_double(0.0)
+        n = lib().biogpt_hip_generate_beam(self._h, pr.ctypes.data, pr.size, int(n_batch), int(n_beams), int(n_predict), int(eos_id),
+                                           float(length_penalty), 1 if early_stopping else 0, out.ctypes.data, lens.ctypes.data,
+                                           scores.ctypes.data, C.byref(secs))
+        if n < 0:
+            raise BiogptError(_err())
+        if n == 0:
+            return [], secs.value
+        stride = min(int(n_predict), self.hparams.n_positions - pr.size)   # rows are [n_beams][n_predict as clamped]
+        flat = out.reshape(-1)
+        return [(flat[r * stride:r * stride + int(lens[r])].copy(), float(scores[r])) for r in range(n)], secs.value
 
     # -- sequence scoring (no reference counterpart): teacher-forced causal log-probabilities --
     def score(self, tokens, n_past=0, targets=None):

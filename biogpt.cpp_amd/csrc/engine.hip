@@ -41,6 +41,7 @@
 #include "kernels_fpipe.hip.h"   // (likewise: fpipe_tu.hip)
 #include "kernels_quant.hip.h"
 #include "kernels_score.hip.h"
+#include "kernels_beam.hip.h"
 #include "model_file.h"
 #include "quant_host.h"
 
@@ -268,6 +269,14 @@ struct biogpt_hip_ctx {
     int launch_parity = 0;
     hipGraphExec_t graph_batch[12] = {};  // [6 * (steps as column-per-XCD launches) + context bucket], captured for graph_batch_n sequences
     int graph_batch_n = 0;
+    // beam search (biogpt_hip_generate_beam, kernels_beam.hip.h): its captured steps (layout of graph_batch, for graph_beam_n beams), the device
+    // state + pool ids (BeamCtl, then [BEAM_MAX][n_positions] words), the candidates, and the pinned done words of two groups of steps
+    hipGraphExec_t graph_beam[12] = {};
+    int graph_beam_n = 0;
+    bgk::BeamCtl *beam_ctl = nullptr;
+    bgk::BeamCand *beam_cand = nullptr;
+    int32_t *beam_done_host = nullptr;
+    hipEvent_t beam_ev[2] = {};
 
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1415,13 +1424,16 @@ void destroy(biogpt_hip_ctx *c) {
     for (auto &pl : c->graph_step) for (auto &row : pl) for (auto &g : row) if (g) (void)hipGraphExecDestroy(g);
     for (auto &pl : c->graph_eval) for (auto &f : pl) for (auto &row : f) for (auto &g : row) if (g) (void)hipGraphExecDestroy(g);
     for (auto &g : c->graph_batch) if (g) (void)hipGraphExecDestroy(g);
+    for (auto &g : c->graph_beam) if (g) (void)hipGraphExecDestroy(g);
+    for (auto &e : c->beam_ev) if (e) (void)hipEventDestroy(e);
+    if (c->beam_done_host) (void)hipHostFree(c->beam_done_host);
     xpipe_release(c);
     if (c->topk_host) (void)hipHostFree(c->topk_host);
     if (c->mbox_host) (void)hipHostFree(c->mbox_host);
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->beam_ctl, (void *)c->beam_cand}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1597,6 +1609,8 @@ int biogpt_hip_refresh_options(biogpt_hip_ctx *ctx) {
     for (auto &pl : ctx->graph_eval) for (auto &f : pl) for (auto &row : f) for (auto &g : row) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     ctx->graph_batch_n = 0;
+    for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    ctx->graph_beam_n = 0;
     // the pipelined path is rebuilt from the new options (GELU slice, fault hook, long-context buffers) -- which also re-arms a context that had abandoned the
     // path after a disturbed launch: an explicit call, not an automatic cool-down
     HIP_TRY(-2, hipSetDevice(ctx->device));
@@ -1962,6 +1976,8 @@ int biogpt_hip_eval_all(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, i
         // the captured batched-decode graphs hold the old logits_all pointer
         for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         ctx->graph_batch_n = 0;
+        for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        ctx->graph_beam_n = 0;
     }
     if (!upload_state(ctx, tokens, n, n_past)) return -2;
     if (!enqueue_forward(ctx, n, true, n_past + n)) return -2;
@@ -2164,6 +2180,7 @@ static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
     HIP_TRY(false, hipMalloc(&ctx->seq_gen, (size_t)n_seqs * ctx->hp.n_positions * 4));
     ctx->batch_cap = n_seqs;
     for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     return true;
 }
 
@@ -2250,6 +2267,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
         HIP_TRY(-2, hipMalloc(&ctx->logits_all, (size_t)n_seqs * V * 4));
         ctx->logits_all_rows = (size_t)n_seqs;
         for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     }
     if (ctx->graph_batch_n != n_seqs) {
         for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
@@ -2343,6 +2361,8 @@ static bool ensure_logits_rows(biogpt_hip_ctx *c, size_t rows) {
     c->logits_all_rows = rows;
     for (auto &g : c->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     c->graph_batch_n = 0;
+    for (auto &g : c->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    c->graph_beam_n = 0;
     return true;
 }
 
@@ -2459,6 +2479,149 @@ int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32
                            float *logprob_out, int32_t *argmax_out, float *logit_out) {
     int rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
     if (rc < 0 && xpipe_retry(ctx, 0)) rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
+    return rc;
+}
+
+// ---- beam search: B columns of the batched decode step + selection and K / V forks on the device (kernels_beam.hip.h) ---------------------
+// The prompt goes into slot 0 (pack_column_passes, chunks of n_batch); step 1 re-evaluates its last token as ONE column (eager) and fans the
+// prompt rows out to every slot; steps 2 .. n_predict are forward(B columns) + beam_rows + beam_select + kv_fork, captured per context bucket
+// (graph_beam, laid out like graph_batch).  The host enqueues steps in groups of 8 and reads the done word of the group before through pinned
+// memory; steps after it change nothing.  The context's own K / V cache and position are left alone.
+static bool enqueue_beam_select(biogpt_hip_ctx *c, int B, int n_rows) {
+    const auto &hp = c->hp;
+    const int V = hp.n_vocab, P = hp.n_positions, K = 2 * B;
+    if (K <= 8) hipLaunchKernelGGL(bgk::beam_rows_kernel<8>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
+    else if (K <= 16) hipLaunchKernelGGL(bgk::beam_rows_kernel<16>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
+    else hipLaunchKernelGGL(bgk::beam_rows_kernel<32>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
+    HIP_TRY(false, hipGetLastError());
+    int32_t *const pool_ids = reinterpret_cast<int32_t *>(c->beam_ctl + 1);
+    hipLaunchKernelGGL(bgk::beam_select_kernel, dim3(1), dim3(bgk::BEAM_SELECT_THREADS), 0, c->stream, c->beam_cand, n_rows, c->beam_ctl, c->seq, c->seq_gen, P, pool_ids);
+    HIP_TRY(false, hipGetLastError());
+    const int dk = hp.d_model / hp.n_head;
+    hipLaunchKernelGGL(bgk::kv_fork_kernel, dim3(hp.n_layer * hp.n_head, std::max(1, B - 1), 2), dim3(256), 0, c->stream, c->beam_ctl, c->bk, c->bv,
+                       (int64_t)hp.n_layer * P * hp.d_model, P, dk, c->seq_gen, P);
+    HIP_TRY(false, hipGetLastError());
+    return true;
+}
+
+static int generate_beam_once(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
+                              int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
+                              double *seconds_out) {
+    XpCallScope xp_scope(ctx);
+    struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } } xc_scope{ctx};
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!prompt || !out_ids || !out_lens || !out_scores) BG_FAIL(-1, "null argument");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
+    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
+    if (n_prompt < 1) BG_FAIL(-1, "empty prompt");
+    const auto &hp = ctx->hp;
+    const int P = hp.n_positions, B = n_beams;
+    if (eos_id < -1 || eos_id >= hp.n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, hp.n_vocab);
+    if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
+    if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
+    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
+        BG_FAIL(-1, "beam search needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (hp.n_vocab < 2 * B) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", hp.n_vocab);
+    if (!check_eval_args(ctx, prompt, n_prompt, 0)) return -1;
+    n_predict = std::min(n_predict, P - n_prompt);  // main.cpp:82
+    if (n_predict <= 0) return 0;
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
+    if (!ensure_seq_caches(ctx, B)) return -2;
+    if (std::max(B, n_prompt) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return -2;   // (as generate_greedy_batch: before any capture)
+    if (!ensure_logits_rows(ctx, (size_t)B)) return -2;
+    if (!ctx->beam_ctl) {
+        HIP_TRY(-2, hipMalloc(&ctx->beam_ctl, sizeof(bgk::BeamCtl) + (size_t)bgk::BEAM_MAX * P * 4));
+        HIP_TRY(-2, hipMalloc(&ctx->beam_cand, sizeof(bgk::BeamCand) * bgk::BEAM_MAX * 2 * bgk::BEAM_MAX));
+        HIP_TRY(-2, hipHostMalloc(&ctx->beam_done_host, 2 * sizeof(int32_t)));
+        for (auto &e : ctx->beam_ev) HIP_TRY(-2, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (ctx->graph_beam_n != B) {
+        for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        ctx->graph_beam_n = B;
+    }
+    {   // the call's parameters and the search's initial state; every column starts as the prompt's last token (only column 0 runs step 1)
+        bgk::BeamCtl h{};
+        h.n_beams = B; h.n_prompt = n_prompt; h.n_predict = n_predict; h.eos_id = eos_id;
+        h.length_penalty = length_penalty; h.early_stopping = early_stopping; h.ids_stride = P;
+        h.heur_unsat = 1;
+        HIP_TRY(-2, hipMemcpy(ctx->beam_ctl, &h, sizeof(h), hipMemcpyHostToDevice));
+        std::vector<bgk::SeqState> hs((size_t)B);
+        for (auto &st : hs) { st = bgk::SeqState{}; st.n_past = n_prompt - 1; st.token = prompt[n_prompt - 1]; }
+        HIP_TRY(-2, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * B, hipMemcpyHostToDevice));
+    }
+
+    // 2 .. 8 beams: the steps as column-per-XCD launches while this call holds the device's pipeline slot (decided ONCE, before any capture)
+    ctx->xc_batch = (B >= 2 && B <= 8 && n_prompt + 1 <= 256 && xcols_prepare(ctx, B, std::min(256, n_prompt + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
+    const int pl = ctx->xc_batch;
+    auto beam_step = [&](int t_max) -> bool { return enqueue_forward(ctx, B, false, t_max, true) && enqueue_beam_select(ctx, B, B); };
+    const bool use_graph = ctx->opt.no_graph == 0 && (pl != 0 || plain_graph_begin(ctx));      // (a captured five-launch step is not replayed beside another context's persistent launch)
+    if (use_graph && n_predict > 1) {
+        for (int b = graph_bucket(n_prompt + 1); b <= graph_bucket(n_prompt + n_predict - 1); b++) {
+            if (ctx->graph_beam[6 * pl + b]) continue;
+            hipGraph_t g = nullptr;
+            HIP_TRY(-2, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+            const bool ok = beam_step(bucket_tmax(ctx, b));
+            hipError_t e = hipStreamEndCapture(ctx->stream, &g);
+            if (!ok) { if (g) (void)hipGraphDestroy(g); return -2; }
+            HIP_TRY(-2, e);
+            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_beam[6 * pl + b], g, nullptr, nullptr, 0));
+            (void)hipGraphDestroy(g);
+        }
+    }
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+
+    const auto t0 = std::chrono::steady_clock::now();
+    const int32_t lens[1] = {n_prompt};
+    if (!pack_column_passes(ctx, prompt, lens, 1, n_batch,
+                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }))
+        return -2;
+    // step 1: the last prompt token as one column (n_past = n_prompt - 1); its row alone expands (the other beams start at -1e9)
+    if (!enqueue_forward(ctx, 1, false, n_prompt, true) || !enqueue_beam_select(ctx, B, 1)) return -2;
+    for (int k = 2, grp = 0; k <= n_predict; grp++) {
+        for (const int end = std::min(n_predict, k + 7); k <= end; k++) {
+            const int t_max = n_prompt + k - 1;      // keys visible to the token at position n_prompt + k - 2
+            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_beam[6 * pl + graph_bucket(t_max)], ctx->stream));
+            else if (!beam_step(t_max)) return -2;
+        }
+        HIP_TRY(-2, hipMemcpyAsync(ctx->beam_done_host + (grp & 1), &ctx->beam_ctl->done, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(-2, hipEventRecord(ctx->beam_ev[grp & 1], ctx->stream));
+        if (grp > 0) {   // the group before this one has finished: stop enqueueing once it says so (one group stays in flight)
+            HIP_TRY(-2, hipEventSynchronize(ctx->beam_ev[(grp - 1) & 1]));
+            if (ctx->beam_done_host[(grp - 1) & 1]) break;
+        }
+    }
+    std::vector<uint8_t> h(sizeof(bgk::BeamCtl) + (size_t)B * P * 4);
+    HIP_TRY(-2, hipMemcpyAsync(h.data(), ctx->beam_ctl, h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    bgk::BeamCtl st;
+    std::memcpy(&st, h.data(), sizeof(st));
+    if (!st.done || st.pool_n < 1 || st.pool_n > B) BG_FAIL(-2, "internal: beam search ended with %d hypotheses (done word %d)", st.pool_n, st.done);
+    const int32_t *ids = reinterpret_cast<const int32_t *>(h.data() + sizeof(bgk::BeamCtl));
+    for (int r = 0; r < B; r++) {
+        int32_t *o = out_ids + (size_t)r * n_predict;
+        std::fill(o, o + n_predict, -1);
+        out_lens[r] = 0; out_scores[r] = 0.0f;
+        if (r >= st.pool_n) continue;
+        const int slot = st.pool_order[r];
+        out_lens[r] = std::min(st.pool_len[slot], n_predict);
+        out_scores[r] = st.pool_score[slot];
+        std::memcpy(o, ids + (size_t)slot * P, (size_t)out_lens[r] * 4);
+    }
+    return st.pool_n;
+}
+
+int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
+                             int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
+                             double *seconds_out) {
+    int rc = generate_beam_once(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores, seconds_out);
+    if (rc < 0 && xpipe_retry(ctx, 0))
+        rc = generate_beam_once(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores, seconds_out);
     return rc;
 }
 

@@ -1,0 +1,307 @@
+// Beam search (biogpt_hip_generate_beam): the selection of a beam step on the device, inside the captured step.
+// A step is the batched decode of the B running beams (one column and one K / V cache slot per beam), then:
+//
+//   beam_rows_kernel    one workgroup per beam row of logits_all: the passes of logprob_rows_kernel (row maximum m, S = sum exp(l - m))
+//                       and the row's top K = 2B (logit, id), equal logits: lower id first.  Writes K candidates
+//                       {s_b + lp, column, id} with lp = (l - m) - log(S) (double arithmetic, rounded once), s_b + lp in f32.
+//   beam_select_kernel  one workgroup: the top 2B of all candidates (score descending, parent rank ascending, id ascending), the next
+//                       running beams, the finished pool and the stopping rules of transformers' _beam_search, the
+//                       new column states and a fork list.  Children are assigned to columns so that the column -> cache mapping
+//                       stays the identity: the first child of a parent keeps the parent's column, further children take the columns
+//                       of parents without children.  Fork sources and destinations are then disjoint sets.
+//   kv_fork_kernel      for each fork: K and V rows [lo, hi) of every layer and head from the source slot to the destination slot
+//                       (head-major cache: one contiguous run per (layer, head)), plus the token history.  Fixed grid (capturable).
+//
+// Nothing here leaves the device; the host only reads the done word between groups of steps and the pool at the end.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernels.hip.h"
+#include "kernels_score.hip.h"
+
+namespace bgk {
+
+constexpr int BEAM_MAX = 16;                   // beams per call; 2 * BEAM_MAX candidates per row
+constexpr int BEAM_SELECT_THREADS = BEAM_MAX * 2 * BEAM_MAX;   // one thread per candidate of a full step
+
+struct BeamCand {
+    float score;    // accumulated log-probability, f32
+    int32_t col;    // parent's column
+    int32_t id;     // token
+    int32_t pad;
+};
+
+// Device state of one beam search call.  The first block is uploaded by the host per call; the rest is the kernels' own.
+struct BeamCtl {
+    int32_t n_beams, n_prompt, n_predict, eos_id;   // eos_id < 0: none
+    float length_penalty;
+    int32_t early_stopping;
+    int32_t ids_stride;                             // words between two pool rows of pool_ids
+    int32_t pad0;
+    // running state
+    int32_t done;          // set once the search has stopped: later steps change nothing
+    int32_t step;          // tokens generated so far
+    int32_t pool_n;        // finished hypotheses held (<= n_beams)
+    int32_t heur_unsat;    // transformers' is_early_stop_heuristic_unsatisfied
+    float run_score[BEAM_MAX];     // per column: accumulated score of the beam in it
+    int32_t col_rank[BEAM_MAX];    // per column: that beam's rank among the running beams
+    int32_t pool_order[BEAM_MAX];  // pool slots, best first
+    int32_t pool_len[BEAM_MAX];    // per slot: generated tokens (EOS included)
+    float pool_score[BEAM_MAX];    // per slot: normalized score
+    int32_t fork_n, fork_lo, fork_hi, fork_gen;     // forks of the last step; rows [lo, hi) of K / V, fork_gen tokens of history
+    int32_t fork_src[BEAM_MAX], fork_dst[BEAM_MAX];
+};
+
+__device__ __forceinline__ bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// insert (v, i) into the descending list (tv, ti): compile-time indices only, the list stays in registers
+template <int KM>
+__device__ __forceinline__ void beam_insert(float v, int i, float (&tv)[KM], int (&ti)[KM]) {
+    if (!beam_better(v, i, tv[KM - 1], ti[KM - 1])) return;
+#pragma unroll
+    for (int j = 0; j < KM; j++) {
+        const bool b = beam_better(v, i, tv[j], ti[j]);
+        const float of = tv[j];
+        const int oi = ti[j];
+        tv[j] = b ? v : of; ti[j] = b ? i : oi;
+        v = b ? of : v; i = b ? oi : i;
+    }
+}
+
+// logits: [n_rows][ldl] (row r = column r); K = 2 * n_beams <= KM; cand: [n_rows][K]
+template <int KM>
+__global__ __launch_bounds__(LP_THREADS) void beam_rows_kernel(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
+    __shared__ float w_v[LP_THREADS / 64][KM];
+    __shared__ int w_i[LP_THREADS / 64][KM];
+    __shared__ double s_ls;
+    __shared__ float t_v[LP_THREADS];
+    __shared__ int t_i[LP_THREADS];
+    __shared__ float s_thr_v;
+    __shared__ int s_thr_i;
+    const int col = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float *row = logits + (size_t)col * ldl;
+    float m;
+    int bi;
+    double S;
+    lp_row_stats(row, n_vocab, m, bi, S);
+    if (tid == 0) s_ls = log(S);
+
+    // this thread's top KM over its elements (same split as the passes: scalar head, float4 body, scalar tail)
+    float tv[KM];
+    int ti[KM];
+#pragma unroll
+    for (int j = 0; j < KM; j++) { tv[j] = -INFINITY; ti[j] = 0x7fffffff; }
+    const int head = min(n_vocab, (int)(((16u - ((uint32_t)(uintptr_t)row & 15u)) & 15u) >> 2));
+    const int nvec = (n_vocab - head) >> 2;
+    const int tail0 = head + 4 * nvec;
+    const float4 *body = reinterpret_cast<const float4 *>(row + head);
+    // a threshold first: the K-th best of the threads' own maxima.  K threads hold an element at least that good, so nothing worse
+    // can be in the row's top K; the insertions below see only the few elements at or above it (else every wave would run the
+    // insertion network for nearly every element: with ~166 elements per lane, some lane of 64 almost always has a new entry)
+    float mv = -INFINITY;
+    int mi = 0x7fffffff;
+    if (tid < head) lp_better(row[tid], tid, mv, mi);
+    for (int i = tid; i < nvec; i += LP_THREADS) {
+        const float4 a = body[i];
+        const int ia = head + 4 * i;
+        lp_better(a.x, ia, mv, mi); lp_better(a.y, ia + 1, mv, mi); lp_better(a.z, ia + 2, mv, mi); lp_better(a.w, ia + 3, mv, mi);
+    }
+    if (tail0 + tid < n_vocab) lp_better(row[tail0 + tid], tail0 + tid, mv, mi);
+    t_v[tid] = mv; t_i[tid] = mi;
+    if (tid == 0) { s_thr_v = -INFINITY; s_thr_i = 0x7fffffff; }   // (a tiny vocabulary: fewer than K threads hold elements, all pass)
+    __syncthreads();
+    {
+        int rank = 0;
+        for (int j = 0; j < LP_THREADS; j++) rank += beam_better(t_v[j], t_i[j], mv, mi) ? 1 : 0;
+        if (rank == K - 1) { s_thr_v = mv; s_thr_i = mi; }     // (the pairs are distinct: exactly one thread has rank K - 1)
+    }
+    __syncthreads();
+    const float thr_v = s_thr_v;
+    const int thr_i = s_thr_i;
+    auto consider = [&](float v, int i) { if (!beam_better(thr_v, thr_i, v, i)) beam_insert<KM>(v, i, tv, ti); };
+    if (tid < head) consider(row[tid], tid);
+    for (int i = tid; i < nvec; i += LP_THREADS) {
+        const float4 a = body[i];
+        const int ia = head + 4 * i;
+        consider(a.x, ia); consider(a.y, ia + 1); consider(a.z, ia + 2); consider(a.w, ia + 3);
+    }
+    if (tail0 + tid < n_vocab) consider(row[tail0 + tid], tail0 + tid);
+
+    // per wave: K rounds of a wave arg-max over the lanes' list heads; the winner pops its head (ids are unique)
+    for (int r = 0; r < K; r++) {
+        float bv = tv[0];
+        int bidx = ti[0];
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(bv, off, 64);
+            const int oi = __shfl_xor(bidx, off, 64);
+            if (beam_better(ov, oi, bv, bidx)) { bv = ov; bidx = oi; }
+        }
+        if (bidx != 0x7fffffff && ti[0] == bidx) {
+#pragma unroll
+            for (int j = 0; j + 1 < KM; j++) { tv[j] = tv[j + 1]; ti[j] = ti[j + 1]; }
+            tv[KM - 1] = -INFINITY; ti[KM - 1] = 0x7fffffff;
+        }
+        if (lane == 0) { w_v[wv][r] = bv; w_i[wv][r] = bidx; }
+    }
+    __syncthreads();
+    // the four wave lists -> the row's top K: each entry finds its rank among all of them
+    const int n_ent = (LP_THREADS / 64) * K;
+    if (tid < n_ent) {
+        const int ew = tid / K, er = tid - ew * K;
+        const float v = w_v[ew][er];
+        const int id = w_i[ew][er];
+        if (id != 0x7fffffff) {
+            int rank = 0;
+            for (int w = 0; w < LP_THREADS / 64; w++)
+                for (int r = 0; r < K; r++) rank += beam_better(w_v[w][r], w_i[w][r], v, id) ? 1 : 0;
+            if (rank < K) {
+                const float lp = (float)(((double)v - (double)m) - s_ls);
+                BeamCand c;
+                c.score = ctl->run_score[col] + lp;
+                c.col = col; c.id = id; c.pad = 0;
+                cand[(size_t)col * K + rank] = c;
+            }
+        }
+    }
+}
+
+// candidate order of a step: score descending, then the parent's rank, then the token id
+__device__ __forceinline__ bool cand_before(const BeamCand &a, int ra, const BeamCand &b, int rb) {
+    if (a.score != b.score) return a.score > b.score;
+    if (ra != rb) return ra < rb;
+    return a.id < b.id;
+}
+
+__device__ __forceinline__ float beam_norm(float s, int gen_len, float lp) { return (float)((double)s / pow((double)gen_len, (double)lp)); }
+
+// n_rows beam rows (1 at the first step, n_beams after) of K = 2 * n_beams candidates each.  seq: the n_beams column states;
+// seq_gen: [column][gen_stride] token histories; pool_ids: [slot][ctl->ids_stride].
+__global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const BeamCand *cand, int n_rows, BeamCtl *ctl, SeqState *seq,
+                                                                          int32_t *seq_gen, int gen_stride, int32_t *pool_ids) {
+    __shared__ BeamCand s_c[2 * BEAM_MAX];
+    __shared__ int s_pend[BEAM_MAX];     // per pool slot: the candidate whose ids it takes in this step, -1 none
+    __shared__ int s_run[BEAM_MAX], s_dest[BEAM_MAX], s_taken[BEAM_MAX];   // thread 0's lists (LDS: no scratch)
+    __shared__ int s_k;
+    const int tid = threadIdx.x;
+    if (ctl->done) return;
+    const int B = ctl->n_beams, K = 2 * B, n = n_rows * K;
+    if (tid < n) {   // rank of this candidate among all of them (a total order: (column, id) pairs are unique)
+        const BeamCand c = cand[tid];
+        const int rc = ctl->col_rank[c.col];
+        int rank = 0;
+        for (int j = 0; j < n; j++) {
+            const BeamCand o = cand[j];
+            rank += cand_before(o, ctl->col_rank[o.col], c, rc) ? 1 : 0;
+        }
+        if (rank < K) s_c[rank] = c;
+    }
+    if (tid < BEAM_MAX) s_pend[tid] = -1;
+    __syncthreads();
+    if (tid == 0) {
+        const int k = ctl->step + 1;             // generated tokens, this step's included
+        const float lpen = ctl->length_penalty;
+        const int eos = ctl->eos_id;
+        auto hit = [&](int i) { return (eos >= 0 && s_c[i].id == eos) || k >= ctl->n_predict; };
+        // the next running beams: the first B candidates that do not stop
+        int *const run = s_run;
+        int nr = 0;
+        for (int i = 0; i < K && nr < B; i++)
+            if (!hit(i)) run[nr++] = i;
+        // the finished pool (_update_finished_beams): candidates among the first B that stop, unless the pool is full under
+        // early_stopping or the heuristic has tripped; best B by normalized score, earlier entries first on ties
+        int pool_n = ctl->pool_n;
+        if (!(pool_n == B && ctl->early_stopping) && ctl->heur_unsat) {
+            for (int i = 0; i < B; i++) {
+                if (!hit(i)) continue;
+                const float sc = beam_norm(s_c[i].score, k, lpen);
+                int pos = 0;
+                while (pos < pool_n && ctl->pool_score[ctl->pool_order[pos]] >= sc) pos++;
+                if (pos >= B) continue;
+                int slot;
+                if (pool_n < B) {
+                    slot = pool_n;
+                    for (int j = pool_n; j > pos; j--) ctl->pool_order[j] = ctl->pool_order[j - 1];
+                    pool_n++;
+                } else {
+                    slot = ctl->pool_order[B - 1];   // the worst entry leaves
+                    for (int j = B - 1; j > pos; j--) ctl->pool_order[j] = ctl->pool_order[j - 1];
+                }
+                ctl->pool_order[pos] = slot;
+                ctl->pool_score[slot] = sc;
+                ctl->pool_len[slot] = k;
+                s_pend[slot] = i;
+            }
+            ctl->pool_n = pool_n;
+        }
+        // _check_early_stop_heuristic: only a full pool can trip it
+        if (ctl->heur_unsat && pool_n == B && nr > 0)
+            ctl->heur_unsat = beam_norm(s_c[run[0]].score, k, lpen) > ctl->pool_score[ctl->pool_order[B - 1]] ? 1 : 0;
+        const int done = (!ctl->heur_unsat || (pool_n == B && ctl->early_stopping) || nr < B || k >= ctl->n_predict) ? 1 : 0;
+        // columns: the first child of a parent stays in its column, further children take the columns of parents without children
+        int *const taken = s_taken, *const dest = s_dest;
+        for (int c = 0; c < BEAM_MAX; c++) taken[c] = 0;
+        for (int r = 0; r < nr; r++) {
+            const int p = s_c[run[r]].col;
+            dest[r] = taken[p] ? -1 : p;
+            taken[p] = 1;
+        }
+        int nf = 0, free_c = 0;
+        for (int r = 0; r < nr; r++) {
+            if (dest[r] >= 0) continue;
+            while (taken[free_c]) free_c++;
+            taken[free_c] = 1;
+            dest[r] = free_c;
+            ctl->fork_src[nf] = s_c[run[r]].col; ctl->fork_dst[nf] = free_c; nf++;
+        }
+        const int n_past = ctl->n_prompt - 1 + k;    // the position of the token each beam evaluates next
+        for (int r = 0; r < nr; r++) {
+            const int c = dest[r];
+            ctl->run_score[c] = s_c[run[r]].score;
+            ctl->col_rank[c] = r;
+            SeqState &s = seq[c];
+            s.token = s_c[run[r]].id;
+            s.n_past = n_past;
+            s.n_gen = k;
+            seq_gen[(size_t)c * gen_stride + (k - 1)] = s_c[run[r]].id;
+        }
+        // the first step fans the prompt rows of slot 0 out to every slot; later forks copy the generated rows only
+        ctl->fork_n = nf;
+        ctl->fork_lo = k == 1 ? 0 : ctl->n_prompt;
+        ctl->fork_hi = n_past;
+        ctl->fork_gen = k - 1;
+        ctl->step = k;
+        ctl->done = done;
+        s_k = k;
+    }
+    __syncthreads();
+    // ids of the hypotheses that entered the pool: the parent's history, then the candidate's token
+    const int k = s_k;
+    for (int slot = 0; slot < B; slot++) {
+        const int i = s_pend[slot];
+        if (i < 0) continue;
+        const int32_t *src = seq_gen + (size_t)s_c[i].col * gen_stride;
+        int32_t *dst = pool_ids + (size_t)slot * ctl->ids_stride;
+        for (int j = tid; j < k; j += blockDim.x) dst[j] = j + 1 < k ? src[j] : s_c[i].id;
+    }
+}
+
+// grid (n_layer * n_head, max(1, n_beams - 1), 2 [K, V]); seq_stride floats between two slots, P * dk between two heads
+__global__ __launch_bounds__(256) void kv_fork_kernel(const BeamCtl *ctl, float *kroot, float *vroot, int64_t seq_stride, int P, int dk,
+                                                      int32_t *seq_gen, int gen_stride) {
+    const int f = blockIdx.y;
+    if (ctl->done || f >= ctl->fork_n) return;
+    const int src = ctl->fork_src[f], dst = ctl->fork_dst[f];
+    const int lo = ctl->fork_lo, hi = ctl->fork_hi;
+    const size_t run0 = (size_t)blockIdx.x * P * dk;    // (layer, head) run; layers are n_head runs apart
+    float *root = blockIdx.z == 0 ? kroot : vroot;
+    const float4 *s4 = reinterpret_cast<const float4 *>(root + (size_t)src * seq_stride + run0 + (size_t)lo * dk);
+    float4 *d4 = reinterpret_cast<float4 *>(root + (size_t)dst * seq_stride + run0 + (size_t)lo * dk);
+    const int n4 = hi > lo ? (hi - lo) * dk / 4 : 0;
+    for (int i = threadIdx.x; i < n4; i += blockDim.x) d4[i] = s4[i];
+    if (blockIdx.x == 0 && blockIdx.z == 0)
+        for (int j = threadIdx.x; j < ctl->fork_gen; j += blockDim.x) seq_gen[(size_t)dst * gen_stride + j] = seq_gen[(size_t)src * gen_stride + j];
+}
+
+}  // namespace bgk

@@ -24,15 +24,13 @@ __device__ __forceinline__ void lp_better(float v, int i, float &bv, int &bi) {
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
 }
 
-// logits: [N][ldl] floats (N = gridDim.x); targets / lp_out / am_out / lg_out: [N], already offset to the pass's first column.
-// targets[c] < 0: lp_out = lg_out = 0 (am_out is written for every column).
-__global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(const float *logits, int ldl, int n_vocab, const int32_t *targets,
-                                                                 float *lp_out, int32_t *am_out, float *lg_out) {
+// The two passes over one logits row by a workgroup of LP_THREADS threads (shared with beam_rows_kernel, kernels_beam.hip.h).
+// Every thread returns the row maximum m and its lowest arg-max bi; thread 0 also the exponential sum S = sum_v exp(l[v] - m).
+__device__ __forceinline__ void lp_row_stats(const float *row, int n_vocab, float &m, int &bi, double &S) {
     __shared__ float s_max[LP_THREADS / 64];
     __shared__ int s_idx[LP_THREADS / 64];
     __shared__ double s_sum[LP_THREADS / 64];
-    const int col = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float *row = logits + (size_t)col * ldl;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // elements in front of the first 16-byte boundary, then whole float4s, then the tail
     const int head = min(n_vocab, (int)(((16u - ((uint32_t)(uintptr_t)row & 15u)) & 15u) >> 2));
     const int nvec = (n_vocab - head) >> 2;
@@ -41,7 +39,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(const float *l
 
     // ---- pass 1: maximum + lowest arg-max ----
     float bv = -INFINITY;
-    int bi = 0x7fffffff;
+    bi = 0x7fffffff;
     if (tid < head) lp_better(row[tid], tid, bv, bi);
     for (int i = tid; i < nvec; i += 2 * LP_THREADS) {      // two 16-byte loads in flight per lane
         const int j = i + LP_THREADS;
@@ -60,7 +58,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(const float *l
     if (lane == 0) { s_max[wv] = bv; s_idx[wv] = bi; }
     __syncthreads();
     for (int w = 0; w < LP_THREADS / 64; w++) lp_better(s_max[w], s_idx[w], bv, bi);   // every thread: the same order, the same result
-    const float m = bv;
+    m = bv;
 
     // ---- pass 2: sum of exp(l - m) ----
     float s = 0.0f;
@@ -76,9 +74,22 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(const float *l
     const double ws = wave_sum_f64((double)s);
     if (lane == 0) s_sum[wv] = ws;
     __syncthreads();
-    if (tid == 0) {
-        double S = 0.0;
+    S = 0.0;
+    if (tid == 0)
         for (int w = 0; w < LP_THREADS / 64; w++) S += s_sum[w];
+}
+
+// logits: [N][ldl] floats (N = gridDim.x); targets / lp_out / am_out / lg_out: [N], already offset to the pass's first column.
+// targets[c] < 0: lp_out = lg_out = 0 (am_out is written for every column).
+__global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(const float *logits, int ldl, int n_vocab, const int32_t *targets,
+                                                                 float *lp_out, int32_t *am_out, float *lg_out) {
+    const int col = blockIdx.x;
+    const float *row = logits + (size_t)col * ldl;
+    float m;
+    int bi;
+    double S;
+    lp_row_stats(row, n_vocab, m, bi, S);
+    if (threadIdx.x == 0) {
         const int t = targets[col];
         float lp = 0.0f, lt = 0.0f;
         if (t >= 0 && t < n_vocab) {

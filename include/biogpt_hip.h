@@ -225,6 +225,22 @@ int biogpt_hip_generate_greedy_batch(biogpt_hip_ctx *ctx, const int32_t *prompts
                                      int32_t n_seqs, int32_t n_batch, int32_t n_predict, int32_t *out_ids,
                                      double *seconds_out);
 
+/* Beam search for one prompt: transformers' GenerationMixin._beam_search with do_sample = False, one EOS id (eos_id = -1: none), no logits
+ * processors, early_stopping 0 / 1 and any length_penalty ("Beam search").  The n_beams running beams decode together as the
+ * columns of biogpt_hip_generate_greedy_batch, each in its own K / V cache; the log-softmax and top-2B of every beam row, the selection, the
+ * pool of finished hypotheses and the K / V copies of forked beams run on the device inside the captured step (csrc/kernels_beam.hip.h).
+ * The prompt is ingested in chunks of n_batch, as biogpt_hip_generate_greedy does; n_beams = 1 with eos_id = -1 returns its ids.
+ * n_predict is clamped to n_positions - n_prompt (main.cpp:82).  Writes the finished hypotheses best first: out_ids [n_beams][n_predict]
+ * (entries past a hypothesis's length are -1; an EOS that ended it is included), out_lens[n_beams] generated tokens, out_scores[n_beams]
+ * normalized scores (sum of log-probabilities / length^length_penalty).  The context's own K / V cache and position are left alone.  Needs
+ * the BioGPT-base fast chain (block-quantized weights), like biogpt_hip_generate_greedy_batch; anything else fails with -1.  Returns n_beams
+ * (hypotheses written), 0 if n_predict clamps to 0, < 0 on error (argument errors, -1, come before any HIP call). */
+int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch,
+                             int32_t n_beams /* 1..16 */, int32_t n_predict, int32_t eos_id /* -1: none */,
+                             float length_penalty, int32_t early_stopping /* 0/1 */,
+                             int32_t *out_ids /* [n_beams][n_predict] */, int32_t *out_lens, float *out_scores,
+                             double *seconds_out);
+
 /* ---- sequence scoring (no counterpart in the reference) ---------------------------------------
  * biogpt_hip_score: teacher-forced, causal log-probabilities of a sequence.  Row i sees the keys [0, n_past + i] -- what
  * biogpt_hip_eval_prompt(..., n_batch = 1) and a loop of single-token biogpt_hip_eval calls compute; NOT the unmasked chunk of
