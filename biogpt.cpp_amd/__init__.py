@@ -102,6 +102,11 @@ SYMBOLS = [
     ("biogpt_hip_generate_greedy_batch", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_generate_beam", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P,
                                           C.POINTER(C.c_double)]),
+    ("biogpt_hip_generate_sample", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32, _P, _P,
+                                            C.POINTER(C.c_double)]),
+    ("biogpt_hip_mt19937_seed", C.c_int, [C.c_uint32, _P]),
+    ("biogpt_hip_sample_candidates_host", C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, _P, _P]),
+    ("biogpt_hip_sample_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P]),
     ("biogpt_hip_score", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_score_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_read_kv", C.c_int, [_P, C.c_int, C.c_size_t, C.c_size_t, _P]),
@@ -423,6 +428,34 @@ class BiogptModel:
         stride = min(int(n_predict), self.hparams.n_positions - pr.size)   # rows are [n_beams][n_predict as clamped]
         flat = out.reshape(-1)
         return [(flat[r * stride:r * stride + int(lens[r])].copy(), float(scores[r])) for r in range(n)], secs.value
+
+    def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8):
+        """n_samples sampled continuations of every prompt (list of id lists, or one flat id list), drawn on the device by the reference's top-k / top-p
+        sampler (INTEGRATION.md, "Sampled generation").  Sequence p * n_samples + j is sample j of prompt p with std::mt19937(seeds[...]); seeds=None:
+        seed + sequence index.  Returns ([ids int32[len], ...] in sequence order, seconds); an EOS that ended a sequence is included."""
+        if len(prompts) and np.isscalar(prompts[0]):
+            prompts = [prompts]
+        lens = np.asarray([len(p) for p in prompts], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]) if len(prompts) else np.zeros(0, np.int32))
+        n = len(prompts) * int(n_samples)
+        if seeds is None:
+            seeds = [(int(seed) + r) & 0xFFFFFFFF for r in range(max(n, 0))]
+        sd = np.ascontiguousarray(seeds, dtype=np.uint32)
+        if sd.size != max(n, 0):
+            raise BiogptError("seeds must have one entry per sequence (%d != %d)" % (sd.size, n))
+        w = max(int(n_predict), 1)
+        out = np.zeros((max(n, 1), w), dtype=np.int32)
+        ol = np.zeros(max(n, 1), dtype=np.int32)
+        secs = C.c_double(0.0)
+        got = lib().biogpt_hip_generate_sample(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples), int(n_batch), int(n_predict),
+                                               int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id), out.ctypes.data, ol.ctypes.data,
+                                               C.byref(secs))
+        if got < 0:
+            raise BiogptError(_err())
+        if got == 0:
+            return [], secs.value
+        rows = out.reshape(-1)      # rows are [n][n_predict as clamped]
+        return [rows[r * got:r * got + int(ol[r])].copy() for r in range(n)], secs.value
 
     # -- sequence scoring (no reference counterpart): teacher-forced causal log-probabilities --
     def score(self, tokens, n_past=0, targets=None):

@@ -42,6 +42,7 @@
 #include "kernels_quant.hip.h"
 #include "kernels_score.hip.h"
 #include "kernels_beam.hip.h"
+#include "kernels_sample.hip.h"
 #include "model_file.h"
 #include "quant_host.h"
 
@@ -277,6 +278,14 @@ struct biogpt_hip_ctx {
     bgk::BeamCand *beam_cand = nullptr;
     int32_t *beam_done_host = nullptr;
     hipEvent_t beam_ev[2] = {};
+    // sampled generation (biogpt_hip_generate_sample, kernels_sample.hip.h): its captured steps (layout of graph_batch, for graph_sample_n sequences), the call's
+    // parameters + one generator state per sequence (SampleCtl, then sample_cap SampleSeq), and the pinned live counts of two groups of steps
+    hipGraphExec_t graph_sample[12] = {};
+    int graph_sample_n = 0;
+    bgk::SampleCtl *sample_ctl = nullptr;
+    int sample_cap = 0;
+    int32_t *sample_live_host = nullptr;
+    hipEvent_t sample_ev[2] = {};
 
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1427,13 +1436,16 @@ void destroy(biogpt_hip_ctx *c) {
     for (auto &g : c->graph_beam) if (g) (void)hipGraphExecDestroy(g);
     for (auto &e : c->beam_ev) if (e) (void)hipEventDestroy(e);
     if (c->beam_done_host) (void)hipHostFree(c->beam_done_host);
+    for (auto &g : c->graph_sample) if (g) (void)hipGraphExecDestroy(g);
+    for (auto &e : c->sample_ev) if (e) (void)hipEventDestroy(e);
+    if (c->sample_live_host) (void)hipHostFree(c->sample_live_host);
     xpipe_release(c);
     if (c->topk_host) (void)hipHostFree(c->topk_host);
     if (c->mbox_host) (void)hipHostFree(c->mbox_host);
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->beam_ctl, (void *)c->beam_cand}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->beam_ctl, (void *)c->beam_cand, (void *)c->sample_ctl}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1611,6 +1623,8 @@ int biogpt_hip_refresh_options(biogpt_hip_ctx *ctx) {
     ctx->graph_batch_n = 0;
     for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     ctx->graph_beam_n = 0;
+    for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    ctx->graph_sample_n = 0;
     // the pipelined path is rebuilt from the new options (GELU slice, fault hook, long-context buffers) -- which also re-arms a context that had abandoned the
     // path after a disturbed launch: an explicit call, not an automatic cool-down
     HIP_TRY(-2, hipSetDevice(ctx->device));
@@ -1978,6 +1992,8 @@ int biogpt_hip_eval_all(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, i
         ctx->graph_batch_n = 0;
         for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         ctx->graph_beam_n = 0;
+        for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        ctx->graph_sample_n = 0;
     }
     if (!upload_state(ctx, tokens, n, n_past)) return -2;
     if (!enqueue_forward(ctx, n, true, n_past + n)) return -2;
@@ -2181,6 +2197,7 @@ static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
     ctx->batch_cap = n_seqs;
     for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     return true;
 }
 
@@ -2188,9 +2205,9 @@ static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
 // column that knows its sequence, its position and the end of its own n_batch-chunk (SeqState::seq_id / n_past / t_vis); whole
 // chunks are packed into passes of up to BIOGPT_HIP_PROMPT_COLS columns (at most n_positions: the activation scratch).  The columns
 // follow the flat order of `seqs`.  Per pass the column states go to ctx->cols, then pass(n_cols, t_max, flat0) enqueues the pass
-// (flat0 = flat index of its first token).
+// (flat0 = flat index of its first token).  Sequence s fills the K / V cache slot s * slot_stride.
 static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int n_seqs, int n_batch,
-                               const std::function<bool(int, int, size_t)> &pass) {
+                               const std::function<bool(int, int, size_t)> &pass, int slot_stride = 1) {
     const int max_cols = std::min(std::max(std::max(1, ctx->opt.prompt_cols), n_batch), hp_cols(ctx));   // the activation scratch holds n_positions columns
     std::vector<bgk::SeqState> cols;
     int pass_tmax = 0;
@@ -2219,7 +2236,7 @@ static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const i
             if (!cols.empty() && (int)cols.size() + m > max_cols && !flush()) return false;
             for (int i = 0; i < m; i++) {
                 bgk::SeqState cst{};
-                cst.n_past = at + i; cst.token = seqs[off + (size_t)(at + i)]; cst.seq_id = s; cst.t_vis = at + m;
+                cst.n_past = at + i; cst.token = seqs[off + (size_t)(at + i)]; cst.seq_id = s * slot_stride; cst.t_vis = at + m;
                 cols.push_back(cst);
             }
             pass_tmax = std::max(pass_tmax, at + m);
@@ -2268,6 +2285,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
         ctx->logits_all_rows = (size_t)n_seqs;
         for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     }
     if (ctx->graph_batch_n != n_seqs) {
         for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
@@ -2363,6 +2381,8 @@ static bool ensure_logits_rows(biogpt_hip_ctx *c, size_t rows) {
     c->graph_batch_n = 0;
     for (auto &g : c->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     c->graph_beam_n = 0;
+    for (auto &g : c->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    c->graph_sample_n = 0;
     return true;
 }
 
@@ -2623,6 +2643,221 @@ int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t
     if (rc < 0 && xpipe_retry(ctx, 0))
         rc = generate_beam_once(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores, seconds_out);
     return rc;
+}
+
+// ---- sampled generation: n_prompts x n_samples columns of the batched decode step + the reference's sampler on the device (kernels_sample.hip.h) ----
+// Built like generate_greedy_batch_once with sample_rows_kernel in the place of argmax_rows_kernel (graph_sample, laid out like graph_batch).  A prompt with
+// several samples is evaluated once, into the slot of its first sample; kv_share_kernel copies its rows to the other slots before the first step.  With an
+// EOS id the host enqueues steps in groups of 8 and reads the count of unfinished sequences of the group before through pinned memory, as beam search reads
+// its done word.  The context's own K / V cache, position and logits row are left alone.
+static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
+                                int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
+                                int32_t *out_ids, int32_t *out_lens, double *seconds_out) {
+    XpCallScope xp_scope(ctx);
+    struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } } xc_scope{ctx};
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!prompts || !prompt_lens || !seeds || !out_ids || !out_lens) BG_FAIL(-1, "null argument");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (n_prompts < 1 || n_samples < 1 || (int64_t)n_prompts * n_samples > 512) BG_FAIL(-1, "n_prompts x n_samples must be in [1, 512]");   // each sequence owns a full F32 KV cache
+    const int n_seqs = n_prompts * n_samples;
+    if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_prompts x n_samples (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
+    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
+    const auto &hp = ctx->hp;
+    const int P = hp.n_positions, V = hp.n_vocab;
+    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > V) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
+    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
+    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
+    if (eos_id < -1 || eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
+    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
+        BG_FAIL(-1, "sampled generation needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    int max_len = 0;
+    long total = 0;
+    for (int p = 0; p < n_prompts; p++) {
+        if (prompt_lens[p] < 1) BG_FAIL(-1, "empty prompt (prompt %d)", p);
+        if (!check_eval_args(ctx, prompts + total, prompt_lens[p], 0)) return -1;
+        max_len = std::max(max_len, prompt_lens[p]);
+        total += prompt_lens[p];
+    }
+    n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
+    if (n_predict <= 0) return 0;
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
+    if (!ensure_seq_caches(ctx, n_seqs)) return -2;
+    if (std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return -2;   // (as generate_greedy_batch: before any capture)
+    if (!ensure_logits_rows(ctx, (size_t)n_seqs)) return -2;
+    if (n_seqs > ctx->sample_cap) {
+        if (ctx->sample_ctl) (void)hipFree(ctx->sample_ctl);
+        ctx->sample_ctl = nullptr; ctx->sample_cap = 0;
+        for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        HIP_TRY(-2, hipMalloc(&ctx->sample_ctl, sizeof(bgk::SampleCtl) + sizeof(bgk::SampleSeq) * (size_t)n_seqs));
+        ctx->sample_cap = n_seqs;
+    }
+    if (!ctx->sample_live_host) {
+        HIP_TRY(-2, hipHostMalloc(&ctx->sample_live_host, 2 * sizeof(int32_t)));
+        for (auto &e : ctx->sample_ev) HIP_TRY(-2, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (ctx->graph_sample_n != n_seqs) {
+        for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        ctx->graph_sample_n = n_seqs;
+    }
+    bgk::SampleSeq *const sample_seq = reinterpret_cast<bgk::SampleSeq *>(ctx->sample_ctl + 1);
+    {   // the call's parameters, the generators (std::mt19937(seeds[r]), their first block of outputs made here) and the column states: every
+        // sequence starts at its prompt's LAST token (the prompt pass below leaves it to the first step)
+        std::vector<uint8_t> h(sizeof(bgk::SampleCtl) + sizeof(bgk::SampleSeq) * (size_t)n_seqs, 0);
+        bgk::SampleCtl hc{};
+        hc.top_k = top_k; hc.eos_id = eos_id; hc.n_live = n_seqs; hc.top_p = top_p; hc.temp = temp;
+        std::memcpy(h.data(), &hc, sizeof(hc));
+        bgk::SampleSeq *hq = reinterpret_cast<bgk::SampleSeq *>(h.data() + sizeof(bgk::SampleCtl));
+        for (int r = 0; r < n_seqs; r++) { bgk::mt_seed(seeds[r], hq[r].mt); bgk::mt_regenerate(hq[r].mt); }
+        HIP_TRY(-2, hipMemcpy(ctx->sample_ctl, h.data(), h.size(), hipMemcpyHostToDevice));
+        std::vector<bgk::SeqState> hs((size_t)n_seqs);
+        size_t o = 0;
+        for (int p = 0; p < n_prompts; p++) {
+            o += (size_t)prompt_lens[p];
+            for (int j = 0; j < n_samples; j++) {
+                bgk::SeqState &st = hs[(size_t)p * n_samples + j];
+                st = bgk::SeqState{};
+                st.n_past = prompt_lens[p] - 1; st.token = prompts[o - 1]; st.seq_id = p * n_samples + j;
+            }
+        }
+        HIP_TRY(-2, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * n_seqs, hipMemcpyHostToDevice));
+    }
+
+    // 2 .. 8 sequences: the steps as column-per-XCD launches while this call holds the device's pipeline slot (decided ONCE, before any capture)
+    ctx->xc_batch = (n_seqs >= 2 && n_seqs <= 8 && max_len + 1 <= 256 && xcols_prepare(ctx, n_seqs, std::min(256, max_len + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
+    const int pl = ctx->xc_batch;
+    auto sample_step = [&](int t_max) -> bool {
+        if (!enqueue_forward(ctx, n_seqs, false, t_max, true)) return false;
+        hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->sample_ctl, sample_seq,
+                           ctx->seq, ctx->seq_gen, P);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    const bool use_graph = ctx->opt.no_graph == 0 && (pl != 0 || plain_graph_begin(ctx));      // (a captured step is not replayed beside another context's persistent launch)
+    if (use_graph) {
+        for (int b = graph_bucket(max_len + 1); b <= graph_bucket(std::max(1, max_len + n_predict - 1)); b++) {
+            if (ctx->graph_sample[6 * pl + b]) continue;
+            hipGraph_t g = nullptr;
+            HIP_TRY(-2, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+            const bool ok = sample_step(bucket_tmax(ctx, b));
+            hipError_t e = hipStreamEndCapture(ctx->stream, &g);
+            if (!ok) { if (g) (void)hipGraphDestroy(g); return -2; }
+            HIP_TRY(-2, e);
+            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_sample[6 * pl + b], g, nullptr, nullptr, 0));
+            (void)hipGraphDestroy(g);
+        }
+    }
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!pack_column_passes(ctx, prompts, prompt_lens, n_prompts, n_batch,
+                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }, n_samples))
+        return -2;
+    if (n_samples > 1) {
+        hipLaunchKernelGGL(bgk::kv_share_kernel, dim3(hp.n_layer * hp.n_head, n_seqs, 2), dim3(256), 0, ctx->stream, ctx->seq, n_samples, ctx->bk, ctx->bv,
+                           (int64_t)hp.n_layer * P * hp.d_model, P, hp.d_model / hp.n_head);
+        HIP_TRY(-2, hipGetLastError());
+    }
+    if (!sample_step(max_len)) return -2;   // last prompt token of every sequence -> first sampled token
+    for (int k = 1, grp = 0; k < n_predict; grp++) {
+        for (const int end = std::min(n_predict - 1, k + 7); k <= end; k++) {
+            const int t_max = max_len + k;
+            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_sample[6 * pl + graph_bucket(t_max)], ctx->stream));
+            else if (!sample_step(t_max)) return -2;
+        }
+        if (eos_id < 0) continue;
+        HIP_TRY(-2, hipMemcpyAsync(ctx->sample_live_host + (grp & 1), &ctx->sample_ctl->n_live, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(-2, hipEventRecord(ctx->sample_ev[grp & 1], ctx->stream));
+        if (grp > 0) {   // the group before this one has finished: stop enqueueing once every sequence has (one group stays in flight)
+            HIP_TRY(-2, hipEventSynchronize(ctx->sample_ev[(grp - 1) & 1]));
+            if (ctx->sample_live_host[(grp - 1) & 1] <= 0) break;
+        }
+    }
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    std::vector<int32_t> gen((size_t)n_seqs * P);
+    std::vector<bgk::SeqState> hs((size_t)n_seqs);
+    HIP_TRY(-2, hipMemcpy(gen.data(), ctx->seq_gen, gen.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(hs.data(), ctx->seq, sizeof(bgk::SeqState) * n_seqs, hipMemcpyDeviceToHost));
+    for (int r = 0; r < n_seqs; r++) {
+        const int len = std::max(0, std::min(hs[(size_t)r].n_gen, n_predict));
+        int32_t *o = out_ids + (size_t)r * n_predict;
+        std::fill(o, o + n_predict, -1);
+        std::memcpy(o, gen.data() + (size_t)r * P, (size_t)len * 4);
+        out_lens[r] = len;
+    }
+    return n_predict;
+}
+
+int biogpt_hip_generate_sample(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
+                               int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
+                               int32_t *out_ids, int32_t *out_lens, double *seconds_out) {
+    int rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out);
+    if (rc < 0 && xpipe_retry(ctx, 0))
+        rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out);
+    return rc;
+}
+
+// the sampler's tail and its generator on the host: no device, no context
+int biogpt_hip_mt19937_seed(uint32_t seed, uint32_t *state625) {
+    clear_error();
+    if (!state625) BG_FAIL(-1, "null argument");
+    bgk::mt_seed(seed, state625);
+    return 0;
+}
+int biogpt_hip_sample_candidates_host(const float *vals, const int32_t *ids, int32_t k, double top_p, double temp, uint32_t *mt_state625, int32_t *id_out) {
+    clear_error();
+    if (!vals || !ids || !mt_state625 || !id_out) BG_FAIL(-1, "null argument");
+    if (k < 1 || k > (1 << 20)) BG_FAIL(-1, "k must be in [1, %d]", 1 << 20);
+    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
+    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
+    if (mt_state625[bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index %u out of range", mt_state625[bgk::MT_N]);
+    bgk::SampleWork w;
+    std::vector<double> p((size_t)k);
+    *id_out = ids[bgk::sample_tail(vals, k, top_p, temp, mt_state625, p.data(), w, 0, 1, bgk::SampleNoSync())];
+    return 0;
+}
+
+// sample_rows_kernel over rows held in host memory (tests: ties, any row width and alignment, the selection's round form, a generator block running
+// out): row r draws from mt_states[r] (625 words, advanced in place; the words of a block regenerated on the device are those of the host's form)
+int biogpt_hip_sample_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, int32_t top_k, double top_p, double temp,
+                                  uint32_t *mt_states, int32_t *ids_out) {
+    clear_error();
+    if (!logits || !mt_states || !ids_out) BG_FAIL(-1, "null argument");
+    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
+    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > n_vocab) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
+    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
+    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
+    for (int r = 0; r < n_rows; r++)
+        if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sizeof(bgk::SampleCtl) + sizeof(bgk::SampleSeq) * (size_t)n_rows;
+    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = (size_t)n_rows * 4;
+    std::vector<uint8_t> h(sq_b, 0);
+    bgk::SampleCtl hc{};
+    hc.top_k = top_k; hc.eos_id = -1; hc.n_live = n_rows; hc.top_p = top_p; hc.temp = temp;
+    std::memcpy(h.data(), &hc, sizeof(hc));
+    bgk::SampleSeq *hq = reinterpret_cast<bgk::SampleSeq *>(h.data() + sizeof(bgk::SampleCtl));
+    for (int r = 0; r < n_rows; r++) std::memcpy(hq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
+    uint8_t *d = nullptr;      // [logits | ctl + states | column states | ids], each part 16-byte aligned
+    const size_t o_sq = (lg_b + 15) & ~(size_t)15, o_st = (o_sq + sq_b + 15) & ~(size_t)15, o_id = (o_st + st_b + 15) & ~(size_t)15;
+    HIP_TRY(-2, hipMalloc(&d, o_id + id_b));
+    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+    HIP_TRY(-2, hipMemcpy(d, logits, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d + o_sq, h.data(), sq_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d + o_st, 0, o_id + id_b - o_st));
+    hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, reinterpret_cast<const float *>(d), n_vocab, n_vocab,
+                       reinterpret_cast<bgk::SampleCtl *>(d + o_sq), reinterpret_cast<bgk::SampleSeq *>(d + o_sq + sizeof(bgk::SampleCtl)),
+                       reinterpret_cast<bgk::SeqState *>(d + o_st), reinterpret_cast<int32_t *>(d + o_id), 1);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(h.data(), d + o_sq, sq_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(ids_out, d + o_id, id_b, hipMemcpyDeviceToHost));
+    for (int r = 0; r < n_rows; r++) std::memcpy(mt_states + (size_t)r * 625, hq[r].mt, 625 * 4);
+    return 0;
 }
 
 // profiling builds (BIOGPT_HIP_PROFILE_HOOKS + BIOGPT_HIP_DBG=128): the raw 100 MHz stage stamps the pipelined launches left (kernels_xpipe.hip.h XP_WALL / XP_TAIL)

@@ -1,0 +1,314 @@
+// Sampled generation (biogpt_hip_generate_sample): biogpt_sample_top_k_top_p (biogpt.cpp:908-980) on the device, inside the captured step.
+// A step is the batched decode of the running sequences (one column and one K / V cache slot per sequence), then:
+//
+//   sample_rows_kernel   one workgroup per sequence row of logits_all:
+//                          selection  the row's top k (value descending, equal values: lower id first -- the order of topk_kernel / host_topk).
+//                                     Pass 1: every thread's own maximum; the k-th best of the 256 maxima is a lower bound of the row's k-th
+//                                     value (k threads hold an element at least that good).  Pass 2 (the row is on chip by now): the few
+//                                     elements at or above the bound go to a list in LDS; each finds its rank among them by counting.
+//                                     A row with more than SAMPLE_CAND_CAP such elements (many of the best in few threads) takes k rounds
+//                                     of a workgroup-wide arg-max instead: slow, and not what a model's logits look like.
+//                          tail       sample_tail() below: scale, exp, normalise, top-p cut, renormalise, libstdc++'s discrete_distribution
+//                                     (ONE generate_canonical<double, 53> = two mt19937 outputs, none with fewer than two candidates), all in
+//                                     double.  The per-candidate operations run one per thread, the sums in candidate order on thread 0.
+//                          append     the id to the sequence's history, its next token and position; an EOS sets the sequence's finished
+//                                     flag instead: a finished column keeps its token and position (it recomputes the K / V row it has).
+//   kv_share_kernel      before the first step of a call with several samples per prompt: the prompt's K / V rows from the slot of the
+//                        prompt's first sample to the slots of the others (head-major cache: one contiguous run per (layer, head)).
+//
+// The random state is std::mt19937's: 624 words + the index, one per sequence in device memory, seeded on the host.  sample_tail and the
+// generator are __host__ __device__: biogpt_hip_sample_candidates_host runs the same text on the CPU.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "kernels.hip.h"
+#include "kernels_score.hip.h"
+
+namespace bgk {
+
+constexpr int SAMPLE_MAX_K = 64;          // top_k of a call (the limit of biogpt_hip_eval_topk)
+constexpr int SAMPLE_THREADS = 256;       // 4 waves per row, as logprob_rows_kernel
+constexpr int SAMPLE_CAND_CAP = 1024;     // candidates the LDS list holds
+constexpr int MT_N = 624, MT_M = 397;
+
+// the call's parameters and the count of unfinished sequences (the host polls it when an EOS id is given)
+struct SampleCtl {
+    int32_t top_k, eos_id;     // eos_id < 0: none
+    int32_t n_live, pad;
+    double top_p, temp;
+};
+
+struct SampleSeq {
+    uint32_t mt[MT_N + 1];     // std::mt19937: the state words, then the index of the next output (624: regenerate first)
+    int32_t finished;
+    int32_t pad[2];
+};
+
+// ---- std::mt19937 ([rand.eng.mers]) ----------------------------------------------------------------------------------------------------
+__host__ __device__ inline uint32_t mt_mix(uint32_t cur, uint32_t nxt, uint32_t far) {
+    const uint32_t y = (cur & 0x80000000u) | (nxt & 0x7fffffffu);
+    return far ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+}
+__host__ __device__ inline void mt_seed(uint32_t seed, uint32_t *mt) {
+    mt[0] = seed;
+    for (int i = 1; i < MT_N; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+    mt[MT_N] = MT_N;
+}
+__host__ __device__ inline void mt_regenerate(uint32_t *mt) {
+    for (int i = 0; i < MT_N - MT_M; i++) mt[i] = mt_mix(mt[i], mt[i + 1], mt[i + MT_M]);
+    for (int i = MT_N - MT_M; i < MT_N - 1; i++) mt[i] = mt_mix(mt[i], mt[i + 1], mt[i + MT_M - MT_N]);
+    mt[MT_N - 1] = mt_mix(mt[MT_N - 1], mt[0], mt[MT_M - 1]);
+    mt[MT_N] = 0;
+}
+__host__ __device__ inline uint32_t mt_next(uint32_t *mt) {
+    if (mt[MT_N] >= (uint32_t)MT_N) mt_regenerate(mt);
+    uint32_t y = mt[mt[MT_N]];
+    mt[MT_N] += 1;
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    y ^= y >> 18;
+    return y;
+}
+
+// ---- the tail: k candidates in selection order -> the sampled candidate's index ----------------------------------------------------------
+struct SampleWork {
+    double total;
+    int32_t n, pick;
+};
+
+struct SampleNoSync { __host__ __device__ void operator()() const {} };
+
+// biogpt.cpp:938-980 over vals[0 .. k) (f32 logits, best first); p: k doubles of workspace.  `nl` callers with lane = 0 .. nl - 1 run it together, sync() making w
+// visible between the steps; the host runs it with nl = 1.  Returns the index of the chosen candidate (every caller the same).
+template <class Sync>
+__host__ __device__ inline int sample_tail(const float *vals, int k, double top_p, double temp, uint32_t *mt, double *p, SampleWork &w, int lane, int nl, Sync sync) {
+    const double scale = 1.0 / temp;
+    double maxl = -INFINITY;
+    for (int i = 0; i < k; i++) {
+        const double v = (double)vals[i] * scale;
+        maxl = v > maxl ? v : maxl;
+    }
+    for (int i = lane; i < k; i += nl) p[i] = exp((double)vals[i] * scale - maxl);
+    sync();
+    if (lane == 0) {
+        double total = 0.0;
+        for (int i = 0; i < k; i++) total += p[i];
+        w.total = total;
+    }
+    sync();
+    for (int i = lane; i < k; i += nl) p[i] = p[i] / w.total;
+    sync();
+    if (lane == 0) {      // the top-p cut at the first cumsum >= top_p; w.total: the renormalisation factor
+        int n = k;
+        double inv = 1.0;
+        if (top_p < 1.0) {
+            double cumsum = 0.0;
+            for (int i = 0; i < k; i++) {
+                cumsum += p[i];
+                if (cumsum >= top_p) { n = i + 1; break; }
+            }
+            inv = 1.0 / cumsum;
+        }
+        w.n = n;
+        w.total = inv;
+    }
+    sync();
+    const int n = w.n;
+    if (top_p < 1.0)
+        for (int i = lane; i < n; i += nl) p[i] = p[i] * w.total;
+    sync();
+    // std::discrete_distribution (libstdc++): fewer than two probabilities -> 0 and no draw
+    if (n < 2) return 0;
+    if (lane == 0) {
+        double total = 0.0;
+        for (int i = 0; i < n; i++) total += p[i];
+        w.total = total;
+    }
+    sync();
+    for (int i = lane; i < n; i += nl) p[i] = p[i] / w.total;
+    sync();
+    if (lane == 0) {
+        double run = 0.0;
+        for (int i = 0; i < n; i++) { run += p[i]; p[i] = run; }
+        p[n - 1] = 1.0;
+        const double a = (double)mt_next(mt);      // generate_canonical<double, 53>: (a + b * 2^32) / 2^64
+        const double b = (double)mt_next(mt);
+        double u = (a + b * 4294967296.0) / 18446744073709551616.0;
+        if (u >= 1.0) u = 0x1.fffffffffffffp-1;    // nextafter(1, 0)
+        int lo = 0, hi = n;                        // std::lower_bound: the first partial sum >= u
+        while (lo < hi) {
+            const int mid = (lo + hi) / 2;
+            if (p[mid] < u) lo = mid + 1; else hi = mid;
+        }
+        w.pick = lo;
+    }
+    sync();
+    return w.pick;
+}
+
+struct SampleBlockSync { __device__ void operator()() const { __syncthreads(); } };
+
+// f(value, index) over every element of the row: a scalar head up to the first 16-byte boundary, float4s (two in flight), a scalar tail
+template <class F>
+__device__ __forceinline__ void sample_scan_row(const float *row, int n_vocab, F f) {
+    const int tid = threadIdx.x;
+    const int head = min(n_vocab, (int)(((16u - ((uint32_t)(uintptr_t)row & 15u)) & 15u) >> 2));
+    const int nvec = (n_vocab - head) >> 2;
+    const int tail0 = head + 4 * nvec;
+    const float4 *body = reinterpret_cast<const float4 *>(row + head);
+    if (tid < head) f(row[tid], tid);
+    for (int i = tid; i < nvec; i += 2 * SAMPLE_THREADS) {
+        const int j = i + SAMPLE_THREADS;
+        const float4 a = body[i];
+        const float4 b = j < nvec ? body[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const int ia = head + 4 * i, ib = head + 4 * j;
+        f(a.x, ia); f(a.y, ia + 1); f(a.z, ia + 2); f(a.w, ia + 3);
+        if (j < nvec) { f(b.x, ib); f(b.y, ib + 1); f(b.z, ib + 2); f(b.w, ib + 3); }
+    }
+    if (tail0 + tid < n_vocab) f(row[tail0 + tid], tail0 + tid);
+}
+
+// (av, ai) comes before (bv, bi) in selection order
+__device__ __forceinline__ bool sample_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+
+// logits: [rows][ldl] (row r = column r = sequence r); seq / sq: the rows' states; seq_gen: [row][gen_stride] token histories
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float *logits, int ldl, int n_vocab, SampleCtl *ctl, SampleSeq *sq,
+                                                                     SeqState *seq, int32_t *seq_gen, int gen_stride) {
+    __shared__ float t_v[SAMPLE_THREADS];
+    __shared__ int t_i[SAMPLE_THREADS];
+    __shared__ float c_v[SAMPLE_CAND_CAP];
+    __shared__ int c_i[SAMPLE_CAND_CAP];
+    __shared__ float top_v[SAMPLE_MAX_K];
+    __shared__ int top_i[SAMPLE_MAX_K];
+    __shared__ uint32_t mt_old[MT_N], mt_new[MT_N];
+    __shared__ SampleWork work;
+    __shared__ double work_p[SAMPLE_MAX_K];
+    __shared__ float s_thr_v;
+    __shared__ int s_thr_i, s_n;
+    __shared__ float r_v[SAMPLE_THREADS / 64];
+    __shared__ int r_i[SAMPLE_THREADS / 64];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    SampleSeq *const me = sq + r;
+    if (me->finished) return;
+    const float *row = logits + (size_t)r * ldl;
+    const int K = min(min(ctl->top_k, SAMPLE_MAX_K), n_vocab);
+
+    // ---- the generator: an exhausted block of outputs is regenerated by the whole workgroup (the words of [0, 227), [227, 454), [454, 623)
+    //      and 623 depend on the old block and on the ranges before them only) ----
+    if (me->mt[MT_N] == (uint32_t)MT_N) {
+        constexpr int D = MT_N - MT_M;
+        for (int i = tid; i < MT_N; i += SAMPLE_THREADS) mt_old[i] = me->mt[i];
+        __syncthreads();
+        if (tid < D) mt_new[tid] = mt_mix(mt_old[tid], mt_old[tid + 1], mt_old[tid + MT_M]);
+        __syncthreads();
+        if (tid < D) mt_new[tid + D] = mt_mix(mt_old[tid + D], mt_old[tid + D + 1], mt_new[tid]);
+        __syncthreads();
+        if (tid + 2 * D < MT_N - 1) mt_new[tid + 2 * D] = mt_mix(mt_old[tid + 2 * D], mt_old[tid + 2 * D + 1], mt_new[tid + D]);
+        __syncthreads();
+        if (tid == 0) mt_new[MT_N - 1] = mt_mix(mt_old[MT_N - 1], mt_new[0], mt_new[MT_M - 1]);
+        __syncthreads();
+        for (int i = tid; i < MT_N; i += SAMPLE_THREADS) me->mt[i] = mt_new[i];
+        if (tid == 0) me->mt[MT_N] = 0;
+        __syncthreads();
+    }
+
+    // ---- pass 1: the bound ----
+    float mv = -INFINITY;
+    int mi = 0x7fffffff;
+    sample_scan_row(row, n_vocab, [&](float v, int i) { lp_better(v, i, mv, mi); });
+    t_v[tid] = mv; t_i[tid] = mi;
+    if (tid == 0) { s_thr_v = -INFINITY; s_thr_i = 0x7fffffff; s_n = 0; }      // (fewer than K threads with an element: everything passes)
+    __syncthreads();
+    {
+        int rank = 0;
+        for (int j = 0; j < SAMPLE_THREADS; j++) rank += sample_before(t_v[j], t_i[j], mv, mi) ? 1 : 0;
+        if (rank == K - 1 && mi != 0x7fffffff) { s_thr_v = mv; s_thr_i = mi; }   // (pairs with an element are distinct: one thread at most)
+    }
+    __syncthreads();
+    const float thr_v = s_thr_v;
+    const int thr_i = s_thr_i;
+
+    // ---- pass 2: the elements at or above the bound (NaNs never are, as in host_topk) ----
+    sample_scan_row(row, n_vocab, [&](float v, int i) {
+        if (v == v && !sample_before(thr_v, thr_i, v, i)) {
+            const int slot = atomicAdd(&s_n, 1);
+            if (slot < SAMPLE_CAND_CAP) { c_v[slot] = v; c_i[slot] = i; }
+        }
+    });
+    __syncthreads();
+    const int n_c = s_n;
+    int k_eff;
+    if (n_c <= SAMPLE_CAND_CAP) {
+        k_eff = min(K, n_c);
+        for (int c = tid; c < n_c; c += SAMPLE_THREADS) {
+            const float v = c_v[c];
+            const int id = c_i[c];
+            int rank = 0;
+            for (int j = 0; j < n_c; j++) rank += sample_before(c_v[j], c_i[j], v, id) ? 1 : 0;
+            if (rank < K) { top_v[rank] = v; top_i[rank] = id; }
+        }
+        __syncthreads();
+    } else {      // K rounds: the best element after the one picked before
+        float pv = INFINITY;
+        int pi = -1;
+        k_eff = 0;
+        for (int rd = 0; rd < K; rd++) {
+            float bv = -INFINITY;
+            int bi = 0x7fffffff;
+            sample_scan_row(row, n_vocab, [&](float v, int i) {
+                if (v == v && sample_before(pv, pi, v, i)) lp_better(v, i, bv, bi);
+            });
+            for (int off = 32; off > 0; off >>= 1) {
+                const float ov = __shfl_xor(bv, off, 64);
+                const int oi = __shfl_xor(bi, off, 64);
+                lp_better(ov, oi, bv, bi);
+            }
+            if (lane == 0) { r_v[wv] = bv; r_i[wv] = bi; }
+            __syncthreads();
+            for (int w = 0; w < SAMPLE_THREADS / 64; w++) lp_better(r_v[w], r_i[w], bv, bi);
+            __syncthreads();
+            if (bi == 0x7fffffff) break;      // (uniform: every thread holds the same pair)
+            if (tid == 0) { top_v[rd] = bv; top_i[rd] = bi; }
+            pv = bv; pi = bi;
+            k_eff = rd + 1;
+        }
+        __syncthreads();
+    }
+
+    // ---- the draw ----
+    int id = 0;
+    if (k_eff > 0) id = top_i[sample_tail(top_v, k_eff, ctl->top_p, ctl->temp, me->mt, work_p, work, tid, SAMPLE_THREADS, SampleBlockSync())];
+    if (tid == 0) {
+        SeqState *s = seq + r;
+        const int g = s->n_gen;
+        if (g < gen_stride) seq_gen[(size_t)r * gen_stride + g] = id;
+        s->n_gen = g + 1;
+        if (ctl->eos_id >= 0 && id == ctl->eos_id) {
+            me->finished = 1;
+            atomicSub(&ctl->n_live, 1);
+        } else {
+            s->token = id;
+            s->n_past += 1;
+        }
+    }
+}
+
+// grid (n_layer * n_head, n_seqs, 2 [K, V]); seq_stride floats between two slots, P * dk between two heads.  Sequence r with r % n_samples != 0
+// takes the rows [0, its position) -- the prompt without its last token -- from the slot of its prompt's first sample.
+__global__ __launch_bounds__(256) void kv_share_kernel(const SeqState *seq, int n_samples, float *kroot, float *vroot, int64_t seq_stride, int P, int dk) {
+    const int r = blockIdx.y, j = r % n_samples;
+    if (j == 0) return;
+    const int rows = min(seq[r].n_past, P);
+    const size_t run0 = (size_t)blockIdx.x * P * dk;
+    float *root = blockIdx.z == 0 ? kroot : vroot;
+    const float4 *s4 = reinterpret_cast<const float4 *>(root + (size_t)(r - j) * seq_stride + run0);
+    float4 *d4 = reinterpret_cast<float4 *>(root + (size_t)r * seq_stride + run0);
+    const int n4 = rows > 0 ? rows * dk / 4 : 0;
+    for (int i = threadIdx.x; i < n4; i += blockDim.x) d4[i] = s4[i];
+}
+
+}  // namespace bgk

@@ -241,6 +241,36 @@ int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t
                              int32_t *out_ids /* [n_beams][n_predict] */, int32_t *out_lens, float *out_scores,
                              double *seconds_out);
 
+/* Sampled generation, batched: n_samples continuations of each of n_prompts prompts, drawn by the reference's sampler (biogpt_sample_top_k_top_p,
+ * biogpt.cpp:908-980) on the device inside the captured decode step (csrc/kernels_sample.hip.h).  Sequence r = p * n_samples + j is sample j of
+ * prompt p and is what main.cpp:91-151 produces for that prompt with --seed seeds[r] --top_k --top_p --temp -b n_batch (its own std::mt19937(seeds[r])),
+ * stopped after the first eos_id if one is given ("Sampled generation": scale = 1 / temp and all probability arithmetic in double;
+ * candidates by value descending, lower id first on equal values; top-p cut at the first cumsum >= top_p, then the renormalisation; libstdc++'s
+ * discrete_distribution with one generate_canonical<double, 53>; no draw when fewer than two candidates are left).  The device's exp() is not glibc's:
+ * the ids equal the reference loop's unless a draw lies within a few ulp of a partial-sum border or a cumulative sum within a few ulp of top_p.
+ * prompts = the prompts concatenated, prompt_lens[n_prompts] their lengths (a prompt is evaluated once, its K / V rows copied to its other samples);
+ * n_predict is clamped to n_positions - max(prompt_lens).  out_ids is [n_prompts * n_samples][returned n_predict] with -1 after a sequence's end,
+ * out_lens its generated tokens (an EOS that ended it included).  n_prompts * n_samples in [1, 512]; top_k in [1, 64]; temp finite and > 0; top_p
+ * finite (>= 1: no cut); eos_id in [-1, n_vocab).  The context's own K / V cache, position and logits row are left alone.  Needs the BioGPT-base fast
+ * chain (block-quantized weights), like biogpt_hip_generate_greedy_batch; anything else fails with -1.  Returns the clamped n_predict, 0 if that is
+ * <= 0, < 0 on error (argument errors, -1, come before any HIP call). */
+int biogpt_hip_generate_sample(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts,
+                               int32_t n_samples, int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp,
+                               const uint32_t *seeds /* [n_prompts * n_samples] */, int32_t eos_id /* -1: none */,
+                               int32_t *out_ids, int32_t *out_lens, double *seconds_out);
+
+/* The sampler's tail on the host (no device, no context; the function the kernel runs): state625 = the 624 words of std::mt19937(seed) + the index of
+ * the next output (624 after seeding).  biogpt_hip_sample_candidates_host draws from k candidates already in selection order (vals: their f32
+ * logits, best first; ids: their token ids), advancing the state in place.  Both return 0 or -1. */
+int biogpt_hip_mt19937_seed(uint32_t seed, uint32_t *state625);
+int biogpt_hip_sample_candidates_host(const float *vals, const int32_t *ids, int32_t k, double top_p, double temp,
+                                      uint32_t *mt_state625, int32_t *id_out);
+
+/* sample_rows_kernel over n_rows <= 4096 logits rows of n_vocab floats held in host memory: row r is drawn from with the state mt_states[r * 625 ..]
+ * (advanced in place; a block of outputs regenerated on the device holds the words the host's form would).  For tests of the kernel itself. */
+int biogpt_hip_sample_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, int32_t top_k, double top_p, double temp,
+                                  uint32_t *mt_states, int32_t *ids_out);
+
 /* ---- sequence scoring (no counterpart in the reference) ---------------------------------------
  * biogpt_hip_score: teacher-forced, causal log-probabilities of a sequence.  Row i sees the keys [0, n_past + i] -- what
  * biogpt_hip_eval_prompt(..., n_batch = 1) and a loop of single-token biogpt_hip_eval calls compute; NOT the unmasked chunk of
