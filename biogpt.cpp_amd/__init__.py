@@ -35,6 +35,36 @@ class HParams(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class GenRules(C.Structure):
+    """biogpt_hip_gen_rules (include/biogpt_hip.h): generation rules of generate_beam / generate_sample."""
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32), ("min_new_tokens", C.c_int32),
+                ("n_suppress", C.c_int32), ("suppress", C.POINTER(C.c_int32))]
+
+
+def gen_rules(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):
+    """(GenRules, the array its `suppress` points into -- keep it alive for the call)."""
+    ids = np.ascontiguousarray(list(suppress_tokens), dtype=np.int32)
+    r = GenRules(float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens), int(ids.size),
+                 ids.ctypes.data_as(C.POINTER(C.c_int32)) if ids.size else None)
+    return r, ids
+
+
+def rules_rows(rows, histories, prompt_lens=None, mode=0, eos_id=-1, device=0, **rules):
+    """rules_rows_kernel on rows held in host memory (biogpt_hip_rules_rows_device): rows float32 [n][n_vocab], histories a list of id lists (row r's
+    prompt + generated tokens, the first prompt_lens[r] its prompt; None: all of it).  mode 0: logits; 1: log-probabilities first.  Returns the rows."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv = a.shape
+    hl = np.asarray([len(h) for h in histories], dtype=np.int32)
+    pl = hl.copy() if prompt_lens is None else np.ascontiguousarray(prompt_lens, dtype=np.int32)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(h, dtype=np.int32) for h in histories] + [np.zeros(1, np.int32)]))
+    r, keep = gen_rules(**rules)
+    out = np.empty_like(a)
+    if lib().biogpt_hip_rules_rows_device(int(device), int(mode), a.ctypes.data, n, nv, flat.ctypes.data, hl.ctypes.data, pl.ctypes.data, int(eos_id),
+                                          C.byref(r), out.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return out
+
+
 BIOGPT_BASE = dict(n_vocab=42384, n_layer=24, n_head=16, n_positions=1024, d_ff=4096, d_model=1024,
                    ftype=0, n_merges=40000)
 
@@ -104,6 +134,11 @@ SYMBOLS = [
                                           C.POINTER(C.c_double)]),
     ("biogpt_hip_generate_sample", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32, _P, _P,
                                             C.POINTER(C.c_double)]),
+    ("biogpt_hip_generate_beam_rules", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P,
+                                                C.POINTER(C.c_double), C.POINTER(GenRules)]),
+    ("biogpt_hip_generate_sample_rules", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32, _P, _P,
+                                                  C.POINTER(C.c_double), C.POINTER(GenRules)]),
+    ("biogpt_hip_rules_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(GenRules), _P]),
     ("biogpt_hip_mt19937_seed", C.c_int, [C.c_uint32, _P]),
     ("biogpt_hip_sample_candidates_host", C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, _P, _P]),
     ("biogpt_hip_sample_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P]),
@@ -409,18 +444,21 @@ class BiogptModel:
             raise BiogptError(_err())
         return out.reshape(-1)[:len(prompts) * n].reshape(len(prompts), n).copy(), secs.value
 
-    def generate_beam(self, prompt, n_predict, n_beams=5, eos_id=2, length_penalty=1.0, early_stopping=True, n_batch=8):
+    def generate_beam(self, prompt, n_predict, n_beams=5, eos_id=2, length_penalty=1.0, early_stopping=True, n_batch=8,
+                      repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):
         """Beam search (transformers' num_beams with do_sample=False).  Returns ([(ids int32[len], score), ...] best first,
-        seconds): each hypothesis's generated ids (an EOS that ended it included) and its normalized score."""
+        seconds): each hypothesis's generated ids (an EOS that ended it included) and its normalized score.  The last four arguments are
+        transformers' logits processors of the same names, applied to each beam row's log-probabilities ("Generation rules")."""
+        rules, keep = gen_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
         pr = np.ascontiguousarray(prompt, dtype=np.int32)
         w = max(int(n_predict), 1)
         out = np.zeros((max(int(n_beams), 1), w), dtype=np.int32)
         lens = np.zeros(max(int(n_beams), 1), dtype=np.int32)
         scores = np.zeros(max(int(n_beams), 1), dtype=np.float32)
         secs = C.c_double(0.0)
-        n = lib().biogpt_hip_generate_beam(self._h, pr.ctypes.data, pr.size, int(n_batch), int(n_beams), int(n_predict), int(eos_id),
-                                           float(length_penalty), 1 if early_stopping else 0, out.ctypes.data, lens.ctypes.data,
-                                           scores.ctypes.data, C.byref(secs))
+        n = lib().biogpt_hip_generate_beam_rules(self._h, pr.ctypes.data, pr.size, int(n_batch), int(n_beams), int(n_predict), int(eos_id),
+                                                 float(length_penalty), 1 if early_stopping else 0, out.ctypes.data, lens.ctypes.data,
+                                                 scores.ctypes.data, C.byref(secs), C.byref(rules))
         if n < 0:
             raise BiogptError(_err())
         if n == 0:
@@ -429,10 +467,14 @@ class BiogptModel:
         flat = out.reshape(-1)
         return [(flat[r * stride:r * stride + int(lens[r])].copy(), float(scores[r])) for r in range(n)], secs.value
 
-    def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8):
+    def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
+                        repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):
         """n_samples sampled continuations of every prompt (list of id lists, or one flat id list), drawn on the device by the reference's top-k / top-p
         sampler (INTEGRATION.md, "Sampled generation").  Sequence p * n_samples + j is sample j of prompt p with std::mt19937(seeds[...]); seeds=None:
-        seed + sequence index.  Returns ([ids int32[len], ...] in sequence order, seconds); an EOS that ended a sequence is included."""
+        seed + sequence index.  Returns ([ids int32[len], ...] in sequence order, seconds); an EOS that ended a sequence is included.  The last four arguments
+        are transformers' logits processors of the same names, applied to the raw logits row in front of the sampler ("Generation
+        rules"); top_k=1 never draws: greedy decoding with rules and an EOS."""
+        rules, keep = gen_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
         if len(prompts) and np.isscalar(prompts[0]):
             prompts = [prompts]
         lens = np.asarray([len(p) for p in prompts], dtype=np.int32)
@@ -447,9 +489,9 @@ class BiogptModel:
         out = np.zeros((max(n, 1), w), dtype=np.int32)
         ol = np.zeros(max(n, 1), dtype=np.int32)
         secs = C.c_double(0.0)
-        got = lib().biogpt_hip_generate_sample(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples), int(n_batch), int(n_predict),
-                                               int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id), out.ctypes.data, ol.ctypes.data,
-                                               C.byref(secs))
+        got = lib().biogpt_hip_generate_sample_rules(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples), int(n_batch), int(n_predict),
+                                                     int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id), out.ctypes.data, ol.ctypes.data,
+                                                     C.byref(secs), C.byref(rules))
         if got < 0:
             raise BiogptError(_err())
         if got == 0:

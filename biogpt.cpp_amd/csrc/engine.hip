@@ -43,6 +43,7 @@
 #include "kernels_score.hip.h"
 #include "kernels_beam.hip.h"
 #include "kernels_sample.hip.h"
+#include "kernels_rules.hip.h"
 #include "model_file.h"
 #include "quant_host.h"
 
@@ -271,8 +272,9 @@ struct biogpt_hip_ctx {
     hipGraphExec_t graph_batch[12] = {};  // [6 * (steps as column-per-XCD launches) + context bucket], captured for graph_batch_n sequences
     int graph_batch_n = 0;
     // beam search (biogpt_hip_generate_beam, kernels_beam.hip.h): its captured steps (layout of graph_batch, for graph_beam_n beams), the device
-    // state + pool ids (BeamCtl, then [BEAM_MAX][n_positions] words), the candidates, and the pinned done words of two groups of steps
-    hipGraphExec_t graph_beam[12] = {};
+    // state + pool ids (BeamCtl, then [BEAM_MAX][n_positions] words), the candidates, and the pinned done words of two groups of steps.
+    // Steps with generation rules are graphs of their own: [12 * (rules active) + 6 * (column-per-XCD) + bucket]
+    hipGraphExec_t graph_beam[24] = {};
     int graph_beam_n = 0;
     bgk::BeamCtl *beam_ctl = nullptr;
     bgk::BeamCand *beam_cand = nullptr;
@@ -280,12 +282,16 @@ struct biogpt_hip_ctx {
     hipEvent_t beam_ev[2] = {};
     // sampled generation (biogpt_hip_generate_sample, kernels_sample.hip.h): its captured steps (layout of graph_batch, for graph_sample_n sequences), the call's
     // parameters + one generator state per sequence (SampleCtl, then sample_cap SampleSeq), and the pinned live counts of two groups of steps
-    hipGraphExec_t graph_sample[12] = {};
+    // (graphs indexed as graph_beam)
+    hipGraphExec_t graph_sample[24] = {};
     int graph_sample_n = 0;
     bgk::SampleCtl *sample_ctl = nullptr;
     int sample_cap = 0;
     int32_t *sample_live_host = nullptr;
     hipEvent_t sample_ev[2] = {};
+    // generation rules (kernels_rules.hip.h): RulesCtl, RULES_ROWS RulesRow, then the call's prompts (one copy per prompt); allocated once, at its
+    // largest, so that captured steps keep their pointers
+    uint8_t *rules_buf = nullptr;
 
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1445,7 +1451,7 @@ void destroy(biogpt_hip_ctx *c) {
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->beam_ctl, (void *)c->beam_cand, (void *)c->sample_ctl}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->beam_ctl, (void *)c->beam_cand, (void *)c->sample_ctl, (void *)c->rules_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2502,15 +2508,88 @@ int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32
     return rc;
 }
 
+// ---- generation rules: transformers' logits processors on the device, between the forward pass and the selection (kernels_rules.hip.h) --------
+// One check for the three entry points, before any HIP call.  n_positions < 0: no model (the kernel-alone entry).
+constexpr int RULES_ROWS = 512;     // rows of a call: sequences of biogpt_hip_generate_sample (beams: BEAM_MAX)
+
+static bool check_rules(const biogpt_hip_gen_rules *r, int n_vocab, int n_positions) {
+    if (!r) return true;
+    if (!std::isfinite(r->repetition_penalty) || !(r->repetition_penalty > 0.0f)) BG_FAIL(false, "repetition_penalty must be finite and > 0 (1.0: off)");
+    if (r->no_repeat_ngram_size < 0) BG_FAIL(false, "no_repeat_ngram_size must be >= 0 (0: off)");
+    if (n_positions >= 0 && r->no_repeat_ngram_size > n_positions)
+        BG_FAIL(false, "no_repeat_ngram_size %d exceeds the model's %d positions", r->no_repeat_ngram_size, n_positions);
+    if (r->min_new_tokens < 0) BG_FAIL(false, "min_new_tokens must be >= 0 (0: off)");
+    if (r->n_suppress < 0 || r->n_suppress > bgk::RULES_MAX_SUPPRESS) BG_FAIL(false, "n_suppress must be in [0, %d]", bgk::RULES_MAX_SUPPRESS);
+    if (r->n_suppress > 0 && !r->suppress) BG_FAIL(false, "suppress is NULL with n_suppress = %d", r->n_suppress);
+    for (int i = 0; i < r->n_suppress; i++)
+        if (r->suppress[i] < 0 || r->suppress[i] >= n_vocab) BG_FAIL(false, "suppress[%d] = %d out of range: must be in [0, %d)", i, r->suppress[i], n_vocab);
+    if (n_vocab > bgk::RULES_MAX_VOCAB) BG_FAIL(false, "generation rules hold one bit per token in LDS: n_vocab must be at most %d", bgk::RULES_MAX_VOCAB);
+    return true;
+}
+
+// a rule that writes -inf is active (min_new_tokens only with an EOS id, as transformers adds its processor)
+static bool rules_ban(const biogpt_hip_gen_rules *r, int eos_id) {
+    return r && (r->no_repeat_ngram_size > 0 || (r->min_new_tokens > 0 && eos_id >= 0) || r->n_suppress > 0);
+}
+static bool rules_active(const biogpt_hip_gen_rules *r, int eos_id) { return r && (r->repetition_penalty != 1.0f || rules_ban(r, eos_id)); }
+
+static bgk::RulesCtl rules_ctl_of(const biogpt_hip_gen_rules *r, int mode, int eos_id) {
+    bgk::RulesCtl h{};
+    h.penalty = r->repetition_penalty; h.ngram = r->no_repeat_ngram_size; h.min_new = eos_id >= 0 ? r->min_new_tokens : 0;
+    h.n_suppress = r->n_suppress; h.eos_id = eos_id; h.mode = mode;
+    for (int i = 0; i < r->n_suppress; i++) h.suppress[i] = r->suppress[i];
+    return h;
+}
+
+static size_t rules_rows_off() { return sizeof(bgk::RulesCtl); }
+static size_t rules_toks_off() { return sizeof(bgk::RulesCtl) + sizeof(bgk::RulesRow) * RULES_ROWS; }
+
+// the call's rules, its rows (row p * rows_per_prompt + j reads prompt p) and its prompts -> the device, once per call
+static bool rules_upload(biogpt_hip_ctx *c, const biogpt_hip_gen_rules *r, int mode, int eos_id, const int32_t *prompts, const int32_t *prompt_lens,
+                         int n_prompts, int rows_per_prompt) {
+    const size_t P = (size_t)c->hp.n_positions;
+    if (!c->rules_buf) HIP_TRY(false, hipMalloc(&c->rules_buf, rules_toks_off() + (size_t)RULES_ROWS * P * 4));
+    size_t total = 0;
+    for (int p = 0; p < n_prompts; p++) total += (size_t)prompt_lens[p];
+    std::vector<uint8_t> h(rules_toks_off() + total * 4, 0);
+    const bgk::RulesCtl hc = rules_ctl_of(r, mode, eos_id);
+    std::memcpy(h.data(), &hc, sizeof(hc));
+    bgk::RulesRow *rows = reinterpret_cast<bgk::RulesRow *>(h.data() + rules_rows_off());
+    size_t o = 0;
+    for (int p = 0; p < n_prompts; p++) {
+        for (int j = 0; j < rows_per_prompt; j++) rows[(size_t)p * rows_per_prompt + j] = bgk::RulesRow{(int32_t)o, prompt_lens[p]};
+        o += (size_t)prompt_lens[p];
+    }
+    std::memcpy(h.data() + rules_toks_off(), prompts, total * 4);
+    HIP_TRY(false, hipMemcpy(c->rules_buf, h.data(), h.size(), hipMemcpyHostToDevice));
+    return true;
+}
+
+// skip: a device word per row (skip_stride words apart) that, set, leaves the row alone
+static bool enqueue_rules(biogpt_hip_ctx *c, int n_rows, const int32_t *skip, int skip_stride) {
+    const int V = c->hp.n_vocab;
+    hipLaunchKernelGGL(bgk::rules_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((V + 31) / 32) * 4, c->stream, c->logits_all, V, V,
+                       reinterpret_cast<const bgk::RulesCtl *>(c->rules_buf), reinterpret_cast<const bgk::RulesRow *>(c->rules_buf + rules_rows_off()),
+                       reinterpret_cast<const int32_t *>(c->rules_buf + rules_toks_off()), c->seq, c->seq_gen, c->hp.n_positions, skip, skip_stride);
+    HIP_TRY(false, hipGetLastError());
+    return true;
+}
+
 // ---- beam search: B columns of the batched decode step + selection and K / V forks on the device (kernels_beam.hip.h) ---------------------
 // The prompt goes into slot 0 (pack_column_passes, chunks of n_batch); step 1 re-evaluates its last token as ONE column (eager) and fans the
 // prompt rows out to every slot; steps 2 .. n_predict are forward(B columns) + beam_rows + beam_select + kv_fork, captured per context bucket
 // (graph_beam, laid out like graph_batch).  The host enqueues steps in groups of 8 and reads the done word of the group before through pinned
 // memory; steps after it change nothing.  The context's own K / V cache and position are left alone.
-static bool enqueue_beam_select(biogpt_hip_ctx *c, int B, int n_rows) {
+// `rules`: the rows become processed log-probabilities first (rules_rows_kernel, mode 1) and the top-2B takes them as they are.
+static bool enqueue_beam_select(biogpt_hip_ctx *c, int B, int n_rows, bool rules = false) {
     const auto &hp = c->hp;
     const int V = hp.n_vocab, P = hp.n_positions, K = 2 * B;
-    if (K <= 8) hipLaunchKernelGGL(bgk::beam_rows_kernel<8>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
+    if (rules) {
+        if (!enqueue_rules(c, n_rows, &c->beam_ctl->done, 0)) return false;
+        if (K <= 8) hipLaunchKernelGGL(bgk::beam_given_rows_kernel<8>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
+        else if (K <= 16) hipLaunchKernelGGL(bgk::beam_given_rows_kernel<16>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
+        else hipLaunchKernelGGL(bgk::beam_given_rows_kernel<32>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
+    } else if (K <= 8) hipLaunchKernelGGL(bgk::beam_rows_kernel<8>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
     else if (K <= 16) hipLaunchKernelGGL(bgk::beam_rows_kernel<16>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
     else hipLaunchKernelGGL(bgk::beam_rows_kernel<32>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
     HIP_TRY(false, hipGetLastError());
@@ -2526,7 +2605,7 @@ static bool enqueue_beam_select(biogpt_hip_ctx *c, int B, int n_rows) {
 
 static int generate_beam_once(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
                               int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
-                              double *seconds_out) {
+                              double *seconds_out, const biogpt_hip_gen_rules *rules) {
     XpCallScope xp_scope(ctx);
     struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } } xc_scope{ctx};
     clear_error();
@@ -2544,6 +2623,10 @@ static int generate_beam_once(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_
     if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
         BG_FAIL(-1, "beam search needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
     if (hp.n_vocab < 2 * B) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", hp.n_vocab);
+    if (!check_rules(rules, hp.n_vocab, P)) return -1;
+    if (rules_ban(rules, eos_id) && hp.n_vocab - rules->n_suppress - 1 - P < 2 * B)
+        BG_FAIL(-1, "the rules could leave a row fewer than 2 x n_beams candidates: n_vocab - n_suppress - 1 - n_positions = %d < %d", hp.n_vocab - rules->n_suppress - 1 - P, 2 * B);
+    const bool ru = rules_active(rules, eos_id);
     if (!check_eval_args(ctx, prompt, n_prompt, 0)) return -1;
     n_predict = std::min(n_predict, P - n_prompt);  // main.cpp:82
     if (n_predict <= 0) return 0;
@@ -2571,23 +2654,24 @@ static int generate_beam_once(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_
         std::vector<bgk::SeqState> hs((size_t)B);
         for (auto &st : hs) { st = bgk::SeqState{}; st.n_past = n_prompt - 1; st.token = prompt[n_prompt - 1]; }
         HIP_TRY(-2, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * B, hipMemcpyHostToDevice));
+        if (ru && !rules_upload(ctx, rules, 1, eos_id, prompt, &n_prompt, 1, B)) return -2;
     }
 
     // 2 .. 8 beams: the steps as column-per-XCD launches while this call holds the device's pipeline slot (decided ONCE, before any capture)
     ctx->xc_batch = (B >= 2 && B <= 8 && n_prompt + 1 <= 256 && xcols_prepare(ctx, B, std::min(256, n_prompt + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
-    const int pl = ctx->xc_batch;
-    auto beam_step = [&](int t_max) -> bool { return enqueue_forward(ctx, B, false, t_max, true) && enqueue_beam_select(ctx, B, B); };
+    const int pl = ctx->xc_batch, gset = 6 * pl + (ru ? 12 : 0);      // gset: which set of captured steps
+    auto beam_step = [&](int t_max) -> bool { return enqueue_forward(ctx, B, false, t_max, true) && enqueue_beam_select(ctx, B, B, ru); };
     const bool use_graph = ctx->opt.no_graph == 0 && (pl != 0 || plain_graph_begin(ctx));      // (a captured five-launch step is not replayed beside another context's persistent launch)
     if (use_graph && n_predict > 1) {
         for (int b = graph_bucket(n_prompt + 1); b <= graph_bucket(n_prompt + n_predict - 1); b++) {
-            if (ctx->graph_beam[6 * pl + b]) continue;
+            if (ctx->graph_beam[gset + b]) continue;
             hipGraph_t g = nullptr;
             HIP_TRY(-2, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
             const bool ok = beam_step(bucket_tmax(ctx, b));
             hipError_t e = hipStreamEndCapture(ctx->stream, &g);
             if (!ok) { if (g) (void)hipGraphDestroy(g); return -2; }
             HIP_TRY(-2, e);
-            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_beam[6 * pl + b], g, nullptr, nullptr, 0));
+            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_beam[gset + b], g, nullptr, nullptr, 0));
             (void)hipGraphDestroy(g);
         }
     }
@@ -2599,11 +2683,11 @@ static int generate_beam_once(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_
                             [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }))
         return -2;
     // step 1: the last prompt token as one column (n_past = n_prompt - 1); its row alone expands (the other beams start at -1e9)
-    if (!enqueue_forward(ctx, 1, false, n_prompt, true) || !enqueue_beam_select(ctx, B, 1)) return -2;
+    if (!enqueue_forward(ctx, 1, false, n_prompt, true) || !enqueue_beam_select(ctx, B, 1, ru)) return -2;
     for (int k = 2, grp = 0; k <= n_predict; grp++) {
         for (const int end = std::min(n_predict, k + 7); k <= end; k++) {
             const int t_max = n_prompt + k - 1;      // keys visible to the token at position n_prompt + k - 2
-            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_beam[6 * pl + graph_bucket(t_max)], ctx->stream));
+            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_beam[gset + graph_bucket(t_max)], ctx->stream));
             else if (!beam_step(t_max)) return -2;
         }
         HIP_TRY(-2, hipMemcpyAsync(ctx->beam_done_host + (grp & 1), &ctx->beam_ctl->done, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2639,9 +2723,16 @@ static int generate_beam_once(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_
 int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
                              int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
                              double *seconds_out) {
-    int rc = generate_beam_once(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores, seconds_out);
+    return biogpt_hip_generate_beam_rules(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores,
+                                          seconds_out, nullptr);
+}
+
+int biogpt_hip_generate_beam_rules(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
+                                   int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
+                                   double *seconds_out, const biogpt_hip_gen_rules *rules) {
+    int rc = generate_beam_once(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores, seconds_out, rules);
     if (rc < 0 && xpipe_retry(ctx, 0))
-        rc = generate_beam_once(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores, seconds_out);
+        rc = generate_beam_once(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores, seconds_out, rules);
     return rc;
 }
 
@@ -2652,7 +2743,7 @@ int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t
 // its done word.  The context's own K / V cache, position and logits row are left alone.
 static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
                                 int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
-                                int32_t *out_ids, int32_t *out_lens, double *seconds_out) {
+                                int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules) {
     XpCallScope xp_scope(ctx);
     struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } } xc_scope{ctx};
     clear_error();
@@ -2671,6 +2762,8 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     if (eos_id < -1 || eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
     if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
         BG_FAIL(-1, "sampled generation needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (!check_rules(rules, V, P)) return -1;
+    const bool ru = rules_active(rules, eos_id);
     int max_len = 0;
     long total = 0;
     for (int p = 0; p < n_prompts; p++) {
@@ -2722,13 +2815,15 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
             }
         }
         HIP_TRY(-2, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * n_seqs, hipMemcpyHostToDevice));
+        if (ru && !rules_upload(ctx, rules, 0, eos_id, prompts, prompt_lens, n_prompts, n_samples)) return -2;
     }
 
     // 2 .. 8 sequences: the steps as column-per-XCD launches while this call holds the device's pipeline slot (decided ONCE, before any capture)
     ctx->xc_batch = (n_seqs >= 2 && n_seqs <= 8 && max_len + 1 <= 256 && xcols_prepare(ctx, n_seqs, std::min(256, max_len + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
-    const int pl = ctx->xc_batch;
+    const int pl = ctx->xc_batch, gset = 6 * pl + (ru ? 12 : 0);      // gset: which set of captured steps
     auto sample_step = [&](int t_max) -> bool {
         if (!enqueue_forward(ctx, n_seqs, false, t_max, true)) return false;
+        if (ru && !enqueue_rules(ctx, n_seqs, &sample_seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
         hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->sample_ctl, sample_seq,
                            ctx->seq, ctx->seq_gen, P);
         HIP_TRY(false, hipGetLastError());
@@ -2737,14 +2832,14 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     const bool use_graph = ctx->opt.no_graph == 0 && (pl != 0 || plain_graph_begin(ctx));      // (a captured step is not replayed beside another context's persistent launch)
     if (use_graph) {
         for (int b = graph_bucket(max_len + 1); b <= graph_bucket(std::max(1, max_len + n_predict - 1)); b++) {
-            if (ctx->graph_sample[6 * pl + b]) continue;
+            if (ctx->graph_sample[gset + b]) continue;
             hipGraph_t g = nullptr;
             HIP_TRY(-2, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
             const bool ok = sample_step(bucket_tmax(ctx, b));
             hipError_t e = hipStreamEndCapture(ctx->stream, &g);
             if (!ok) { if (g) (void)hipGraphDestroy(g); return -2; }
             HIP_TRY(-2, e);
-            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_sample[6 * pl + b], g, nullptr, nullptr, 0));
+            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_sample[gset + b], g, nullptr, nullptr, 0));
             (void)hipGraphDestroy(g);
         }
     }
@@ -2763,7 +2858,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     for (int k = 1, grp = 0; k < n_predict; grp++) {
         for (const int end = std::min(n_predict - 1, k + 7); k <= end; k++) {
             const int t_max = max_len + k;
-            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_sample[6 * pl + graph_bucket(t_max)], ctx->stream));
+            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_sample[gset + graph_bucket(t_max)], ctx->stream));
             else if (!sample_step(t_max)) return -2;
         }
         if (eos_id < 0) continue;
@@ -2795,10 +2890,72 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
 int biogpt_hip_generate_sample(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
                                int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
                                int32_t *out_ids, int32_t *out_lens, double *seconds_out) {
-    int rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out);
+    return biogpt_hip_generate_sample_rules(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens,
+                                            seconds_out, nullptr);
+}
+
+int biogpt_hip_generate_sample_rules(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
+                                     int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
+                                     int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules) {
+    int rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, rules);
     if (rc < 0 && xpipe_retry(ctx, 0))
-        rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out);
+        rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, rules);
     return rc;
+}
+
+// rules_rows_kernel over rows held in host memory (tests of the kernel itself): row r's history is hist_lens[r] tokens of `hist` (the histories
+// concatenated), the first prompt_lens[r] of them its prompt -- laid out for the kernel as a call lays them out (prompt words, generated words)
+int biogpt_hip_rules_rows_device(int device, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist, const int32_t *hist_lens,
+                                 const int32_t *prompt_lens, int32_t eos_id, const biogpt_hip_gen_rules *rules, float *rows_out) {
+    clear_error();
+    if (!rows || !hist || !hist_lens || !prompt_lens || !rules || !rows_out) BG_FAIL(-1, "null argument");
+    if (mode != 0 && mode != 1) BG_FAIL(-1, "mode must be 0 (logits) or 1 (log-probabilities)");
+    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
+    if (eos_id < -1 || eos_id >= n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, n_vocab);
+    if (!check_rules(rules, n_vocab, -1)) return -1;
+    size_t total = 0, n_pr = 0;
+    int gs = 1;
+    for (int r = 0; r < n_rows; r++) {
+        if (hist_lens[r] < 0 || hist_lens[r] > (1 << 20) || prompt_lens[r] < 0 || prompt_lens[r] > hist_lens[r])
+            BG_FAIL(-1, "hist_lens / prompt_lens of row %d: need 0 <= prompt_lens <= hist_lens <= %d", r, 1 << 20);
+        for (int i = 0; i < hist_lens[r]; i++)
+            if (hist[total + i] < 0 || hist[total + i] >= n_vocab) BG_FAIL(-1, "hist: token %d of row %d out of range", i, r);
+        total += (size_t)hist_lens[r]; n_pr += (size_t)prompt_lens[r];
+        gs = std::max(gs, hist_lens[r] - prompt_lens[r]);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4;
+    const size_t o_rr = sizeof(bgk::RulesCtl), o_tk = o_rr + sizeof(bgk::RulesRow) * (size_t)n_rows, o_st = (o_tk + n_pr * 4 + 15) & ~(size_t)15;
+    const size_t o_gn = o_st + sizeof(bgk::SeqState) * (size_t)n_rows, side_b = o_gn + (size_t)n_rows * gs * 4;
+    std::vector<uint8_t> h(side_b, 0);      // [ctl | rows | prompt words | column states | generated words]
+    const bgk::RulesCtl hc = rules_ctl_of(rules, mode, eos_id);
+    std::memcpy(h.data(), &hc, sizeof(hc));
+    bgk::RulesRow *rr = reinterpret_cast<bgk::RulesRow *>(h.data() + o_rr);
+    int32_t *tk = reinterpret_cast<int32_t *>(h.data() + o_tk), *gn = reinterpret_cast<int32_t *>(h.data() + o_gn);
+    bgk::SeqState *st = reinterpret_cast<bgk::SeqState *>(h.data() + o_st);
+    size_t at = 0, po = 0;
+    for (int r = 0; r < n_rows; r++) {
+        const int np = prompt_lens[r], ng = hist_lens[r] - np;
+        rr[r] = bgk::RulesRow{(int32_t)po, np};
+        std::memcpy(tk + po, hist + at, (size_t)np * 4);
+        std::memcpy(gn + (size_t)r * gs, hist + at + np, (size_t)ng * 4);
+        st[r].n_gen = ng;
+        at += (size_t)hist_lens[r]; po += (size_t)np;
+    }
+    uint8_t *d = nullptr;
+    const size_t o_side = (lg_b + 15) & ~(size_t)15;
+    HIP_TRY(-2, hipMalloc(&d, o_side + side_b));
+    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+    HIP_TRY(-2, hipMemcpy(d, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d + o_side, h.data(), side_b, hipMemcpyHostToDevice));
+    uint8_t *const sd = d + o_side;
+    hipLaunchKernelGGL(bgk::rules_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((n_vocab + 31) / 32) * 4, 0, reinterpret_cast<float *>(d), n_vocab, n_vocab,
+                       reinterpret_cast<const bgk::RulesCtl *>(sd), reinterpret_cast<const bgk::RulesRow *>(sd + o_rr), reinterpret_cast<const int32_t *>(sd + o_tk),
+                       reinterpret_cast<const bgk::SeqState *>(sd + o_st), reinterpret_cast<const int32_t *>(sd + o_gn), gs, nullptr, 0);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(rows_out, d, lg_b, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // the sampler's tail and its generator on the host: no device, no context

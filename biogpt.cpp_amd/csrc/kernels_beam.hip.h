@@ -70,9 +70,11 @@ __device__ __forceinline__ void beam_insert(float v, int i, float (&tv)[KM], int
     }
 }
 
-// logits: [n_rows][ldl] (row r = column r); K = 2 * n_beams <= KM; cand: [n_rows][K]
-template <int KM>
-__global__ __launch_bounds__(LP_THREADS) void beam_rows_kernel(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
+// The body of beam_rows_kernel.  GIVEN = false: the row holds logits (the log-softmax is taken here).  GIVEN = true: it holds log-probabilities
+// already, processed by rules_rows_kernel (kernels_rules.hip.h), and its values are taken as they are (an entry at -inf becomes a candidate only
+// where fewer than K finite ones are left, which the argument check of the rules excludes).
+template <int KM, bool GIVEN>
+__device__ __forceinline__ void beam_rows_body(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
     __shared__ float w_v[LP_THREADS / 64][KM];
     __shared__ int w_i[LP_THREADS / 64][KM];
     __shared__ double s_ls;
@@ -82,11 +84,13 @@ __global__ __launch_bounds__(LP_THREADS) void beam_rows_kernel(const float *logi
     __shared__ int s_thr_i;
     const int col = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float *row = logits + (size_t)col * ldl;
-    float m;
-    int bi;
-    double S;
-    lp_row_stats(row, n_vocab, m, bi, S);
-    if (tid == 0) s_ls = log(S);
+    float m = 0.0f;
+    if constexpr (!GIVEN) {
+        int bi;
+        double S;
+        lp_row_stats(row, n_vocab, m, bi, S);
+        if (tid == 0) s_ls = log(S);
+    }
 
     // this thread's top KM over its elements (same split as the passes: scalar head, float4 body, scalar tail)
     float tv[KM];
@@ -157,7 +161,8 @@ __global__ __launch_bounds__(LP_THREADS) void beam_rows_kernel(const float *logi
             for (int w = 0; w < LP_THREADS / 64; w++)
                 for (int r = 0; r < K; r++) rank += beam_better(w_v[w][r], w_i[w][r], v, id) ? 1 : 0;
             if (rank < K) {
-                const float lp = (float)(((double)v - (double)m) - s_ls);
+                float lp = v;
+                if constexpr (!GIVEN) lp = (float)(((double)v - (double)m) - s_ls);
                 BeamCand c;
                 c.score = ctl->run_score[col] + lp;
                 c.col = col; c.id = id; c.pad = 0;
@@ -165,6 +170,18 @@ __global__ __launch_bounds__(LP_THREADS) void beam_rows_kernel(const float *logi
             }
         }
     }
+}
+
+// logits: [n_rows][ldl] (row r = column r); K = 2 * n_beams <= KM; cand: [n_rows][K]
+template <int KM>
+__global__ __launch_bounds__(LP_THREADS) void beam_rows_kernel(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
+    beam_rows_body<KM, false>(logits, ldl, n_vocab, ctl, K, cand);
+}
+
+// the same over rows of processed log-probabilities (a step with generation rules)
+template <int KM>
+__global__ __launch_bounds__(LP_THREADS) void beam_given_rows_kernel(const float *logp, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
+    beam_rows_body<KM, true>(logp, ldl, n_vocab, ctl, K, cand);
 }
 
 // candidate order of a step: score descending, then the parent's rank, then the token id

@@ -226,7 +226,7 @@ int biogpt_hip_generate_greedy_batch(biogpt_hip_ctx *ctx, const int32_t *prompts
                                      double *seconds_out);
 
 /* Beam search for one prompt: transformers' GenerationMixin._beam_search with do_sample = False, one EOS id (eos_id = -1: none), no logits
- * processors, early_stopping 0 / 1 and any length_penalty ("Beam search").  The n_beams running beams decode together as the
+ * processors (biogpt_hip_generate_beam_rules below adds them), early_stopping 0 / 1 and any length_penalty ("Beam search").  The n_beams running beams decode together as the
  * columns of biogpt_hip_generate_greedy_batch, each in its own K / V cache; the log-softmax and top-2B of every beam row, the selection, the
  * pool of finished hypotheses and the K / V copies of forked beams run on the device inside the captured step (csrc/kernels_beam.hip.h).
  * The prompt is ingested in chunks of n_batch, as biogpt_hip_generate_greedy does; n_beams = 1 with eos_id = -1 returns its ids.
@@ -270,6 +270,45 @@ int biogpt_hip_sample_candidates_host(const float *vals, const int32_t *ids, int
  * (advanced in place; a block of outputs regenerated on the device holds the words the host's form would).  For tests of the kernel itself. */
 int biogpt_hip_sample_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, int32_t top_k, double top_p, double temp,
                                   uint32_t *mt_states, int32_t *ids_out);
+
+/* ---- generation rules: transformers' logits processors of the same names, on the device inside the captured step (csrc/kernels_rules.hip.h;
+ * INTEGRATION.md, "Generation rules").  For a row whose sequence so far is h = prompt + generated tokens, L = len(h), values s:
+ *   repetition_penalty p    every DISTINCT token t of h, once: s[t] = s[t] < 0 ? s[t] * p : s[t] / p (f32, IEEE division)
+ *   no_repeat_ngram_size n  if L + 1 >= n: every i in [0, L - n] with h[i .. i+n-2] == h[L-n+1 .. L-1] bans h[i+n-1] (s = -inf); n = 1 bans every token seen
+ *   min_new_tokens m        with an EOS id and fewer than m tokens generated: s[eos] = -inf (ignored without an EOS id)
+ *   suppress                s[t] = -inf for each listed id, every step
+ * The history includes the prompt.  The penalty is applied first.  biogpt_hip_generate_sample_rules applies the rules to the raw logits row, in
+ * front of the reference's sampler (top_k = 1 never draws: greedy decoding with rules and an EOS); biogpt_hip_generate_beam_rules applies them to
+ * the row's log-probabilities, after the log-softmax and before the top-2B, as transformers' _beam_search does (banned tokens stay in the
+ * normalising sum; the penalty multiplies negative log-probabilities). */
+typedef struct biogpt_hip_gen_rules {
+    float repetition_penalty;      /* 1.0 off; finite, > 0 */
+    int32_t no_repeat_ngram_size;  /* 0 off; <= n_positions */
+    int32_t min_new_tokens;        /* 0 off */
+    int32_t n_suppress;            /* 0 .. 256 */
+    const int32_t *suppress;       /* ids in [0, n_vocab) */
+} biogpt_hip_gen_rules;
+
+/* biogpt_hip_generate_beam / biogpt_hip_generate_sample with rules.  rules == NULL, or a struct with every rule off: the result of the function
+ * without rules, bit for bit, through the same launches and captured steps (a step with rules is a captured graph of its own; the values of the
+ * rules live in device memory, not in the graph).  Argument errors (-1, the message names the field) come before any HIP call.  For beam search a
+ * rule set that could leave a row with fewer than 2 x n_beams finite candidates (a banning rule active and
+ * n_vocab - n_suppress - 1 - n_positions < 2 * n_beams) is an argument error. */
+int biogpt_hip_generate_beam_rules(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch,
+                                   int32_t n_beams, int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping,
+                                   int32_t *out_ids, int32_t *out_lens, float *out_scores, double *seconds_out,
+                                   const biogpt_hip_gen_rules *rules);
+int biogpt_hip_generate_sample_rules(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts,
+                                     int32_t n_samples, int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp,
+                                     const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, double *seconds_out,
+                                     const biogpt_hip_gen_rules *rules);
+
+/* rules_rows_kernel over n_rows <= 4096 rows of n_vocab floats held in host memory.  mode 0: the rows are logits; mode 1: each row becomes its
+ * log-probabilities first, (float)(((double)l - max) - log(sum exp(l - max))).  Row r's history is hist_lens[r] tokens of hist (the histories
+ * concatenated), the first prompt_lens[r] of them its prompt.  rows_out: [n_rows][n_vocab].  For tests of the kernel itself. */
+int biogpt_hip_rules_rows_device(int device, int32_t mode /* 0 logits, 1 log-probabilities */, const float *rows, int32_t n_rows, int32_t n_vocab,
+                                 const int32_t *hist /* concatenated */, const int32_t *hist_lens, const int32_t *prompt_lens, int32_t eos_id,
+                                 const biogpt_hip_gen_rules *rules, float *rows_out);
 
 /* ---- sequence scoring (no counterpart in the reference) ---------------------------------------
  * biogpt_hip_score: teacher-forced, causal log-probabilities of a sequence.  Row i sees the keys [0, n_past + i] -- what
