@@ -41,6 +41,38 @@ class GenRules(C.Structure):
                 ("n_suppress", C.c_int32), ("suppress", C.POINTER(C.c_int32))]
 
 
+class EmbedOpts(C.Structure):
+    """biogpt_hip_embed_opts (include/biogpt_hip.h): what embed_batch returns per sequence."""
+    _fields_ = [("layer", C.c_int32), ("pooling", C.c_int32), ("normalize", C.c_int32), ("n_out", C.c_int32),
+                ("w", C.POINTER(C.c_float)), ("b", C.POINTER(C.c_float))]
+
+
+POOLING = {"none": 0, "last": 1, "mean": 2}
+
+
+def embed_opts(layer=-1, pooling="last", normalize=False, head=None):
+    """(EmbedOpts, the arrays its `w` / `b` point into -- keep them alive for the call).  head: W [n_out, d_model] or (W, b)."""
+    if pooling not in POOLING:
+        raise BiogptError("pooling must be one of 'none', 'last', 'mean' (got %r)" % (pooling,))
+    w = b = None
+    if head is not None:
+        if isinstance(head, (tuple, list)) and len(head) == 2 and np.ndim(head[0]) == 2:
+            w, b = head
+        else:
+            w = head
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        if w.ndim != 2:
+            raise BiogptError("head: W must be a [n_out, d_model] matrix")
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+            if b.size != w.shape[0]:
+                raise BiogptError("head: b must have one entry per row of W (%d != %d)" % (b.size, w.shape[0]))
+    fp = C.POINTER(C.c_float)
+    o = EmbedOpts(int(layer), POOLING[pooling], 1 if normalize else 0, 0 if w is None else int(w.shape[0]),
+                  None if w is None else w.ctypes.data_as(fp), None if b is None else b.ctypes.data_as(fp))
+    return o, (w, b)
+
+
 def gen_rules(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):
     """(GenRules, the array its `suppress` points into -- keep it alive for the call)."""
     ids = np.ascontiguousarray(list(suppress_tokens), dtype=np.int32)
@@ -144,6 +176,8 @@ SYMBOLS = [
     ("biogpt_hip_sample_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P]),
     ("biogpt_hip_score", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_score_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("biogpt_hip_hidden", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    ("biogpt_hip_embed_batch", C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(EmbedOpts), _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_read_kv", C.c_int, [_P, C.c_int, C.c_size_t, C.c_size_t, _P]),
     ("biogpt_hip_debug_stamps", C.c_int, [_P, C.c_size_t, C.c_size_t, C.POINTER(C.c_ulonglong)]),
     ("biogpt_hip_bench_matvec", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -543,6 +577,41 @@ class BiogptModel:
             out.append((lp[off:off + k].copy(), am[off:off + k].copy(), lg[off:off + k].copy()))
             off += int(k)
         return out
+
+    # -- hidden states, pooled embeddings, classification heads (no reference counterpart) --
+    def hidden(self, tokens, n_past=0):
+        """The final hidden state (after the last LayerNorm) of every token, float32 [n, d_model]; row i sees tokens[0..i] (after n_past
+        cached positions).  Leaves the K / V rows of eval_prompt(tokens, n_past, 1); the context's logits row is undefined afterwards."""
+        toks = np.ascontiguousarray(tokens, dtype=np.int32)
+        out = np.zeros((toks.size, self.hparams.d_model), dtype=np.float32)
+        if lib().biogpt_hip_hidden(self._h, toks.ctypes.data, toks.size, int(n_past), out.ctypes.data) != 0:
+            raise BiogptError(_err())
+        return out
+
+    def embed_batch(self, seqs, layer=-1, pooling="last", normalize=False, head=None):
+        """Embeddings of several independent sequences (list of id lists, each from position 0 in its own K / V cache) in common causal passes.
+        layer: transformers' hidden_states index (0 embeddings ... n_layer = -1 after the final LayerNorm); pooling "last" / "mean": one row per
+        sequence, float32 [n_seqs, width]; "none": a list of per-sequence arrays [len, width].  normalize: L2-normalised rows.  head: W
+        [n_out, d_model] or (W, b), applied on the device to the pooled rows (or to every token's row): width = n_out, else d_model."""
+        o, keep = embed_opts(layer, pooling, normalize, head)
+        if keep[0] is not None and keep[0].shape[1] != self.hparams.d_model:
+            raise BiogptError("head: W must have d_model = %d columns (got %d)" % (self.hparams.d_model, keep[0].shape[1]))
+        lens = np.asarray([len(s) for s in seqs], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs]) if len(seqs) else np.zeros(0, np.int32))
+        width = int(o.n_out) if o.n_out > 0 else self.hparams.d_model
+        rows = len(seqs) if o.pooling else int(flat.size)
+        out = np.zeros((max(rows, 1), max(width, 1)), dtype=np.float32)
+        secs = C.c_double(0.0)
+        if lib().biogpt_hip_embed_batch(self._h, flat.ctypes.data, lens.ctypes.data, len(seqs), C.byref(o), out.ctypes.data, C.byref(secs)) != 0:
+            raise BiogptError(_err())
+        self.embed_seconds = secs.value
+        if o.pooling:
+            return out[:rows]
+        res, off = [], 0
+        for k in lens:
+            res.append(out[off:off + k].copy())
+            off += int(k)
+        return res
 
     def read_kv(self, which, offset, count):
         out = np.empty(int(count), dtype=np.float32)

@@ -41,6 +41,7 @@
 #include "kernels_fpipe.hip.h"   // (likewise: fpipe_tu.hip)
 #include "kernels_quant.hip.h"
 #include "kernels_score.hip.h"
+#include "kernels_embed.hip.h"
 #include "kernels_beam.hip.h"
 #include "kernels_sample.hip.h"
 #include "kernels_rules.hip.h"
@@ -264,6 +265,9 @@ struct biogpt_hip_ctx {
     int32_t *sc_tgt = nullptr;
     uint32_t *sc_out = nullptr;
     size_t sc_cap = 0;
+    // hidden states / embeddings (biogpt_hip_hidden, biogpt_hip_embed_batch): one block that holds the call's output rows and what the call needs beside them
+    uint8_t *emb_buf = nullptr;
+    size_t emb_cap = 0;
     int32_t *seq_gen = nullptr;           // [cap][n_positions]
     int batch_cap = 0;
     std::set<const void *> lds_attr_done;     // kernels whose > 64 KB dynamic-LDS opt-in attribute is set on this device
@@ -1016,9 +1020,13 @@ constexpr int MFMA_MIN_DECODE_COLS = 48, MFMA_MIN_PASS_COLS = 64, GROUPED_ATTN_M
 // (column states with seq_id / t_vis), no lm_head -- the caller gets the logits from the following decode step.
 // score (with all_rows): the logits of EVERY column into logits_all on the fastest lm_head for the model (biogpt_hip_score*);
 // prompt columns of several sequences (batch + cols) get them too.
-bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool batch = false, const bgk::SeqState *cols = nullptr, bool score = false) {
+// hid: no logits at all (biogpt_hip_hidden / biogpt_hip_embed_batch) -- the first hid->layers layers only, then the final LayerNorm of every column
+// as f32 rows into hid->ln_out; ln_out == null: no LayerNorm either, the rows are the residual stream c->x itself.
+struct HiddenStage { int layers; float *ln_out; };
+bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool batch = false, const bgk::SeqState *cols = nullptr, bool score = false,
+                     const HiddenStage *hid = nullptr) {
     (void)hipGetLastError();   // a failed call of some OTHER context / API leaves its code behind; the checks below are about these launches
-    if (score) all_rows = true;   // every row is needed: none of the launches that keep the activations on chip and compute the last row only
+    if (score || hid) all_rows = true;   // every row is needed: none of the launches that keep the activations on chip and compute the last row only
     if (N < 1 || N > c->hp.n_positions) BG_FAIL(false, "internal: a pass of %d columns exceeds the %d-column activation scratch", N, c->hp.n_positions);
     if (N == 1 && !batch && !all_rows && fused_decode_ok(c, t_max)) return enqueue_decode_fused(c, t_max, 1, 0);
     if (N >= 2 && N <= 8 && !batch && !all_rows && xcols_usable(c, N, t_max)) return enqueue_xcols(c, N, t_max);
@@ -1058,7 +1066,8 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
     const bool fp_one = N == 1 && !batch && !all_rows && !chain &&
                         (c->fp_force >= 0 ? (c->fp_force == 1 && c->fp_state == 1 && t_max <= bgk::FP_TMAX) : fpipe_usable(c, t_max));
     if (fp_one && !enqueue_fpipe(c)) return false;
-    for (int l = 0; l < hp.n_layer && !xc_streams && !fp_one; l++) {
+    const int n_run = hid ? hid->layers : hp.n_layer;
+    for (int l = 0; l < n_run && !xc_streams && !fp_one; l++) {
         const LayerSlots &L = c->plan.layers[(size_t)l];
         {  // LN0 + fused q/k/v projection + bias + Q scale + KV append
             const MvShape s = mv_shape(L.qkv.type, L.qkv.M, L.qkv.K);
@@ -1184,12 +1193,21 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
         }
     }
     // the final stage, LayerNorm + lm_head: which rows, and on which kernels
-    enum class Final { None, LastRow, AllRows, AllRowsQ8 };
-    const Final fin = (batch && cols && !score) ? Final::None            // prompt columns: only the KV rows matter
+    enum class Final { None, LastRow, AllRows, AllRowsQ8, Hidden };
+    const Final fin = hid ? Final::Hidden                                 // f32 rows in front of the lm_head (kernels_embed.hip.h)
+                    : (batch && cols && !score) ? Final::None            // prompt columns: only the KV rows matter
                     : (batch || (score && pchain)) ? Final::AllRowsQ8     // LayerNorm+Q8 once, then the 8-column / matrix-core lm_head
                     : (all_rows || score) ? Final::AllRows                // every row on the generic kernel (eval_all; scoring of the other models)
                     : Final::LastRow;
     if (fin == Final::None) return true;
+    if (fin == Final::Hidden) {
+        if (!hid->ln_out) return true;
+        const float *lw = dev_vec(c, c->plan.ln_w), *lb = dev_vec(c, c->plan.ln_b);
+        if (D == 1024) hipLaunchKernelGGL((bgk::ln_rows_kernel<1024>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / 1024.0, hid->ln_out);
+        else hipLaunchKernelGGL((bgk::ln_rows_kernel<0>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / (double)D, hid->ln_out);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    }
     if (fin == Final::AllRowsQ8) {  // every column needs its logits row: LayerNorm+Q8 once, then the 8-column mat-vec (matrix cores from 64 columns)
         const MatSlot &m = c->plan.lm_head;
         const MvShape s = mv_shape(m.type, m.M, m.K);
@@ -1451,7 +1469,7 @@ void destroy(biogpt_hip_ctx *c) {
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->beam_ctl, (void *)c->beam_cand, (void *)c->sample_ctl, (void *)c->rules_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->beam_ctl, (void *)c->beam_cand, (void *)c->sample_ctl, (void *)c->rules_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2505,6 +2523,189 @@ int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32
                            float *logprob_out, int32_t *argmax_out, float *logit_out) {
     int rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
     if (rc < 0 && xpipe_retry(ctx, 0)) rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
+    return rc;
+}
+
+// ---- hidden states, pooled embeddings, classification heads: the same causal passes without the lm_head (kernels_embed.hip.h) ------------
+// The passes are those of scoring (one column per token, row i sees keys [0, position of i]); their final stage is Final::Hidden: the final
+// LayerNorm of every column as f32 rows -- or, for a layer index k < n_layer, the residual stream after k layers as it lies in c->x.  Pooling
+// and the caller's linear head run on the device per pass; the call's rows come back in one copy.
+struct EmbedPlan {      // byte offsets into emb_buf (each a multiple of 16)
+    size_t out = 0, pooled = 0, acc = 0, hid = 0, w = 0, b = 0, lens = 0, bytes = 0;
+};
+static bool ensure_embed_buf(biogpt_hip_ctx *c, size_t bytes) {
+    if (bytes <= c->emb_cap) return true;
+    if (c->emb_buf) (void)hipFree(c->emb_buf);
+    c->emb_buf = nullptr; c->emb_cap = 0;
+    if (hipMalloc(&c->emb_buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->emb_buf = nullptr;
+        BG_FAIL(false, "out of device memory: the %zu-byte buffer of this call's output rows could not be allocated", bytes);
+    }
+    c->emb_cap = bytes;
+    return true;
+}
+
+// the argument errors of biogpt_hip_embed_batch that need no model: before the context is looked at, before any HIP call
+static bool check_embed_args(const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const biogpt_hip_embed_opts &o, const float *out) {
+    if (!seqs || !lens || !out) BG_FAIL(false, "null argument (seqs, lens and out must be given)");
+    if (n_seqs < 1 || n_seqs > 512) BG_FAIL(false, "n_seqs must be in [1, 512]");   // each sequence owns a full F32 KV cache
+    if (o.layer < -1) BG_FAIL(false, "layer (%d) must be in [-1, n_layer]", o.layer);
+    if (o.pooling < 0 || o.pooling > 2) BG_FAIL(false, "unknown pooling (%d): 0 none, 1 last token, 2 mean", o.pooling);
+    if (o.normalize != 0 && o.normalize != 1) BG_FAIL(false, "normalize (%d) must be 0 or 1", o.normalize);
+    if (o.n_out < 0 || o.n_out > 256) BG_FAIL(false, "n_out (%d) must be in [0, 256]", o.n_out);
+    if (o.n_out > 0 && !o.w) BG_FAIL(false, "w is NULL with n_out = %d", o.n_out);
+    if (o.n_out == 0 && o.w) BG_FAIL(false, "w given with n_out = 0");
+    if (o.n_out == 0 && o.b) BG_FAIL(false, "b given with n_out = 0");
+    if (o.normalize && o.n_out > 0) BG_FAIL(false, "normalize cannot be combined with a head (n_out = %d)", o.n_out);
+    for (int i = 0; o.b && i < o.n_out; i++)
+        if (!std::isfinite(o.b[i])) BG_FAIL(false, "b[%d] is not finite", i);
+    size_t off = 0;
+    for (int s = 0; s < n_seqs; s++) {
+        if (lens[s] < 1) BG_FAIL(false, "empty sequence (sequence %d)", s);
+        for (int i = 0; i < lens[s]; i++)
+            if (seqs[off + i] < 0) BG_FAIL(false, "token id %d out of range (sequence %d, token %d)", seqs[off + i], s, i);
+        off += (size_t)lens[s];
+    }
+    return true;
+}
+// w [n_out][d_model] holds finite values only (its extent needs the model's width: after the model checks, still before any HIP call)
+static bool check_head_values(const biogpt_hip_embed_opts &o, int D) {
+    for (size_t i = 0; i < (size_t)o.n_out * D; i++)
+        if (!std::isfinite(o.w[i])) BG_FAIL(false, "w[%zu][%zu] is not finite", i / D, i % D);
+    return true;
+}
+
+static bool enqueue_head(biogpt_hip_ctx *c, const float *rows, int n_rows, const float *w, const float *b, int n_out, float *out) {
+    const int D = c->hp.d_model;
+    hipLaunchKernelGGL(bgk::head_rows_kernel, dim3((n_rows + bgk::HEAD_ROWS - 1) / bgk::HEAD_ROWS), dim3(256), (size_t)bgk::HEAD_ROWS * D * 4, c->stream,
+                       rows, n_rows, D, w, b, n_out, out);
+    HIP_TRY(false, hipGetLastError());
+    return true;
+}
+
+static int hidden_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, float *hidden_out) {
+    XpCallScope xp_scope(ctx);
+    clear_error();
+    if (!hidden_out) BG_FAIL(-1, "null hidden_out buffer");
+    if (!check_eval_args(ctx, tokens, n, n_past)) return -1;
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
+    // the passes of biogpt_hip_score: same borders, same K / V rows as biogpt_hip_eval_prompt(tokens, n_past, n_batch = 1)
+    const int max_cols = std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
+    const int first = std::min(max_cols, (int)n);
+    const size_t D = (size_t)ctx->hp.d_model;
+    if (first >= MFMA_MIN_PASS_COLS && is_quantized(ftype_to_type(ctx->hp.ftype)) && !ensure_tile_images(ctx)) return -2;
+    if (!ensure_embed_buf(ctx, (size_t)n * D * 4)) return -2;
+    float *const out = reinterpret_cast<float *>(ctx->emb_buf);
+    for (int at = 0; at < n;) {
+        const int m = std::min(max_cols, n - at);
+        const HiddenStage hs{ctx->hp.n_layer, out + (size_t)at * D};
+        if (!upload_state(ctx, tokens + at, m, n_past + at, m > 1 ? 1 : 0)) return -2;
+        if (!enqueue_forward(ctx, m, true, n_past + at + m, false, nullptr, false, &hs)) return -2;
+        at += m;
+    }
+    HIP_TRY(-2, hipMemcpyAsync(hidden_out, out, (size_t)n * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    ctx->mbox_synced = ctx->mbox_sent;
+    if (!xpipe_check(ctx)) return -2;
+    return 0;
+}
+
+static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const biogpt_hip_embed_opts *opts,
+                            float *out_host, double *seconds_out) {
+    XpCallScope xp_scope(ctx);
+    clear_error();
+    biogpt_hip_embed_opts o{-1, 1, 0, 0, nullptr, nullptr};
+    if (opts) o = *opts;
+    if (!check_embed_args(seqs, lens, n_seqs, o, out_host)) return -1;
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    const auto &hp = ctx->hp;
+    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
+        BG_FAIL(-1, "batched embedding needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (o.layer > hp.n_layer) BG_FAIL(-1, "layer (%d) must be in [-1, n_layer = %d]", o.layer, hp.n_layer);
+    size_t total = 0;
+    for (int s = 0; s < n_seqs; s++) {
+        if (!check_eval_args(ctx, seqs + total, lens[s], 0)) return -1;
+        total += (size_t)lens[s];
+    }
+    if (o.n_out > 0 && !check_head_values(o, hp.d_model)) return -1;
+    const int k = o.layer < 0 ? hp.n_layer : o.layer;
+    const size_t D = (size_t)hp.d_model, W = o.n_out > 0 ? (size_t)o.n_out : D;
+    const size_t n_rows = o.pooling != bgk::POOL_NONE ? (size_t)n_seqs : total;
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
+    // every sequence from position 0 in its own K / V cache (bk / bv): the context's own cache, position and logits row stay as they are
+    const size_t max_cols = (size_t)std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
+    if (!ensure_seq_caches(ctx, n_seqs)) return -2;
+    if ((long)std::min(max_cols, total) >= MFMA_MIN_PASS_COLS && !ensure_tile_images(ctx)) return -2;
+    const bool direct = o.pooling == bgk::POOL_NONE && o.n_out == 0;      // the rows of a pass are output rows as they are
+    EmbedPlan pl;
+    auto take = [&](size_t bytes) { const size_t at = pl.bytes; pl.bytes += (bytes + 15) & ~(size_t)15; return at; };
+    pl.out = take(n_rows * W * 4);
+    if (o.pooling != bgk::POOL_NONE && o.n_out > 0) pl.pooled = take((size_t)n_seqs * D * 4);
+    if (o.pooling == bgk::POOL_MEAN) pl.acc = take((size_t)n_seqs * D * 8);
+    if (!direct && k == hp.n_layer) pl.hid = take(std::min(max_cols, total) * D * 4);
+    if (o.n_out > 0) { pl.w = take((size_t)o.n_out * D * 4); pl.b = take((size_t)o.n_out * 4); }
+    pl.lens = take((size_t)n_seqs * 4);
+    if (!ensure_embed_buf(ctx, pl.bytes)) return -2;
+    uint8_t *const base = ctx->emb_buf;
+    float *const d_out = reinterpret_cast<float *>(base + pl.out);
+    float *const d_pool = o.pooling == bgk::POOL_NONE ? nullptr : (o.n_out > 0 ? reinterpret_cast<float *>(base + pl.pooled) : d_out);
+    double *const d_acc = o.pooling == bgk::POOL_MEAN ? reinterpret_cast<double *>(base + pl.acc) : nullptr;
+    float *const d_hid = reinterpret_cast<float *>(base + pl.hid);
+    const float *const d_w = reinterpret_cast<const float *>(base + pl.w);
+    const float *const d_b = o.b ? reinterpret_cast<const float *>(base + pl.b) : nullptr;
+    const int32_t *const d_lens = reinterpret_cast<const int32_t *>(base + pl.lens);
+    hipStream_t st = ctx->stream;
+    // the call's inputs go up once (blocking copies: the host arrays are the caller's)
+    HIP_TRY(-2, hipMemcpy(base + pl.lens, lens, (size_t)n_seqs * 4, hipMemcpyHostToDevice));
+    if (o.n_out > 0) {
+        HIP_TRY(-2, hipMemcpy(base + pl.w, o.w, (size_t)o.n_out * D * 4, hipMemcpyHostToDevice));
+        if (o.b) HIP_TRY(-2, hipMemcpy(base + pl.b, o.b, (size_t)o.n_out * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(-2, hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (d_acc) HIP_TRY(-2, hipMemsetAsync(d_acc, 0, (size_t)n_seqs * D * 8, st));
+    if (!pack_column_passes(ctx, seqs, lens, n_seqs, 1, [&](int n_cols, int t_max, size_t flat0) {
+            const HiddenStage hs{k, k < hp.n_layer ? nullptr : (direct ? d_out + flat0 * D : d_hid)};
+            if (!enqueue_forward(ctx, n_cols, true, t_max, true, ctx->cols, false, &hs)) return false;
+            const float *rows = hs.ln_out ? hs.ln_out : ctx->x;
+            if (o.pooling == bgk::POOL_NONE) {
+                if (o.n_out > 0) return enqueue_head(ctx, rows, n_cols, d_w, d_b, o.n_out, d_out + flat0 * W);
+                if (!hs.ln_out) HIP_TRY(false, hipMemcpyAsync(d_out + flat0 * D, ctx->x, (size_t)n_cols * D * 4, hipMemcpyDeviceToDevice, st));
+                return true;
+            }
+            hipLaunchKernelGGL(bgk::pool_rows_kernel, dim3((unsigned)((D + 63) / 64), n_cols), dim3(256), 0, st, rows, n_cols, (int)D, ctx->cols, d_lens, o.pooling,
+                               d_pool, d_acc);
+            HIP_TRY(false, hipGetLastError());
+            return true;
+        }))
+        return -2;
+    if (d_acc || o.normalize) {      // the mean of every accumulator row; the L2 normalisation of every output row
+        hipLaunchKernelGGL(bgk::pool_finish_kernel, dim3((unsigned)n_rows), dim3(256), 0, st, d_pool ? d_pool : d_out, (int)D, d_acc, d_lens, o.normalize);
+        HIP_TRY(-2, hipGetLastError());
+    }
+    if (d_pool && o.n_out > 0 && !enqueue_head(ctx, d_pool, n_seqs, d_w, d_b, o.n_out, d_out)) return -2;
+    HIP_TRY(-2, hipMemcpyAsync(out_host, d_out, n_rows * W * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(-2, hipStreamSynchronize(st));
+    const auto t1 = std::chrono::steady_clock::now();
+    ctx->mbox_synced = ctx->mbox_sent;
+    if (!xpipe_check(ctx)) return -2;
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    return 0;
+}
+
+int biogpt_hip_hidden(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, float *hidden_out) {
+    int rc = hidden_once(ctx, tokens, n_tokens, n_past, hidden_out);
+    if (rc < 0 && xpipe_retry(ctx, n_past)) rc = hidden_once(ctx, tokens, n_tokens, n_past, hidden_out);
+    return rc;
+}
+int biogpt_hip_embed_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const biogpt_hip_embed_opts *opts,
+                           float *out, double *seconds_out) {
+    int rc = embed_batch_once(ctx, seqs, lens, n_seqs, opts, out, seconds_out);
+    if (rc < 0 && xpipe_retry(ctx, 0)) rc = embed_batch_once(ctx, seqs, lens, n_seqs, opts, out, seconds_out);
     return rc;
 }
 

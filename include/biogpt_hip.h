@@ -333,6 +333,43 @@ int biogpt_hip_score(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_token
 int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
                            float *logprob_out, int32_t *argmax_out, float *logit_out);
 
+/* ---- hidden states, pooled embeddings, classification heads (no counterpart in the reference) ----
+ * The activations in front of the lm_head, from the causal passes of biogpt_hip_score without the lm_head and the log-softmax.
+ *
+ * biogpt_hip_hidden: the final hidden state (after the last LayerNorm; transformers' last_hidden_state) of every token, f32
+ * [n_tokens][d_model].  Causal whatever BIOGPT_HIP_CAUSAL says: row i sees the keys [0, n_past + i].  Serves every model
+ * biogpt_hip_score serves (all seven file types, any shape).  Arguments as for biogpt_hip_eval.  Afterwards the K / V rows
+ * [n_past, n_past + n_tokens) and the context's position are those biogpt_hip_eval_prompt(tokens, n_past, 1) leaves: a following
+ * biogpt_hip_eval at n_past + n_tokens continues the sequence.  The context's logits row (biogpt_hip_read_logits /
+ * biogpt_hip_logits_device) is UNDEFINED after the call: no logits are computed.  Returns 0 or < 0. */
+/* final hidden state (after the last LayerNorm) of every token: [n_tokens][d_model]; causal: row i sees keys [0, n_past + i] */
+int biogpt_hip_hidden(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, float *hidden_out);
+
+typedef struct biogpt_hip_embed_opts {
+    int32_t layer;      /* transformers' hidden_states index: 0 = embeddings ... k = input of layer k ... n_layer = after the final LayerNorm; -1 = n_layer */
+    int32_t pooling;    /* 0 none (one row per token, flat order of seqs), 1 last token, 2 mean over the sequence's tokens */
+    int32_t normalize;  /* 1: L2-normalise each output row; only without a head */
+    int32_t n_out;      /* head: 0 = none, else rows of w, in [1, 256] */
+    const float *w;     /* [n_out][d_model] f32, host memory */
+    const float *b;     /* [n_out] or NULL */
+} biogpt_hip_embed_opts;
+
+/* Embeddings of n_seqs independent sequences (seqs / lens: the layout of biogpt_hip_score_batch), each from position 0 in a K / V
+ * cache of its own; the context's own cache, position and logits row are left alone.  Without pooling and with layer = n_layer every
+ * sequence's rows are bit-identical to biogpt_hip_hidden(seq, 0).  layer = k < n_layer stops after k layers (no final LayerNorm:
+ * the residual stream, transformers' hidden_states[k]) and costs k / n_layer of the passes.  Pooling runs on the device: the row of the
+ * last token, or the mean over the sequence's rows (double sums, rounded once); normalize divides each output row by its L2 norm
+ * (a zero row stays zero).  A head is applied on the device to the pooled rows (sequence classification, BioGptForSequenceClassification.score)
+ * or, without pooling, to every token's row (token classification): out[r][o] = (float)(b[o] + sum_d (double)w[o][d] * (double)x[r][d]).
+ * Needs the BioGPT-base fast chain (block-quantized weights) and n_seqs in [1, 512], like biogpt_hip_score_batch; other files fail with
+ * -1 (biogpt_hip_hidden serves them).  Argument errors (null pointers, an empty sequence, bad token ids, layer outside [-1, n_layer],
+ * unknown pooling, normalize with a head, n_out outside [0, 256], n_out > 0 without w, w or b with n_out = 0, a non-finite value in
+ * w or b) return -1 before any HIP call and name the field; a failed allocation returns -2 and names the size.  seconds_out (may be
+ * NULL): the passes, pooling, head and the copy back.  Returns 0 or < 0. */
+/* out: [rows][width]; rows = n_seqs with pooling, sum(lens) without; width = n_out with a head, else d_model */
+int biogpt_hip_embed_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs,
+                           const biogpt_hip_embed_opts *opts /* NULL: {-1, 1, 0, 0, NULL, NULL} */, float *out, double *seconds_out);
+
 /* ---- introspection for tests / profiling ---------------------------------------------------
  * Copy `count` floats of the F32 KV cache (which: 0 = K, 1 = V) starting at element `offset` of
  * the flat [n_layer][n_positions][d_model] array (biogpt.cpp:331-335) to host memory. */
