@@ -170,6 +170,8 @@ SYMBOLS = [
                                                 C.POINTER(C.c_double), C.POINTER(GenRules)]),
     ("biogpt_hip_generate_sample_rules", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32, _P, _P,
                                                   C.POINTER(C.c_double), C.POINTER(GenRules)]),
+    ("biogpt_hip_generate_beam_batch", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.POINTER(GenRules),
+                                                _P, _P, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_rules_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(GenRules), _P]),
     ("biogpt_hip_mt19937_seed", C.c_int, [C.c_uint32, _P]),
     ("biogpt_hip_sample_candidates_host", C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, _P, _P]),
@@ -500,6 +502,34 @@ class BiogptModel:
         stride = min(int(n_predict), self.hparams.n_positions - pr.size)   # rows are [n_beams][n_predict as clamped]
         flat = out.reshape(-1)
         return [(flat[r * stride:r * stride + int(lens[r])].copy(), float(scores[r])) for r in range(n)], secs.value
+
+    def generate_beam_batch(self, prompts, n_predict, n_beams=5, eos_id=2, length_penalty=1.0, early_stopping=True, n_batch=8,
+                            repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):
+        """Beam search over a batch of prompts (list of id lists, or one flat id list) in one call: every prompt is a search of its own, all of them
+        columns of the same decode steps ("Beam search over a batch").  Returns ([[(ids int32[len], score), ...] best first, one list
+        per prompt], seconds); prompt p's list is generate_beam(prompts[p], n_predict as clamped for the longest prompt, ...), bit for bit."""
+        rules, keep = gen_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
+        if len(prompts) and np.isscalar(prompts[0]):
+            prompts = [prompts]
+        G, B = len(prompts), max(int(n_beams), 1)
+        lens = np.asarray([len(p) for p in prompts], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]) if G else np.zeros(0, np.int32))
+        w = max(int(n_predict), 1)
+        out = np.zeros((max(G, 1) * B, w), dtype=np.int32)
+        ol = np.zeros(max(G, 1) * B, dtype=np.int32)
+        scores = np.zeros(max(G, 1) * B, dtype=np.float32)
+        counts = np.zeros(max(G, 1), dtype=np.int32)
+        secs = C.c_double(0.0)
+        got = lib().biogpt_hip_generate_beam_batch(self._h, flat.ctypes.data, lens.ctypes.data, G, int(n_batch), int(n_beams), int(n_predict), int(eos_id),
+                                                   float(length_penalty), 1 if early_stopping else 0, C.byref(rules), out.ctypes.data, ol.ctypes.data,
+                                                   scores.ctypes.data, counts.ctypes.data, C.byref(secs))
+        if got < 0:
+            raise BiogptError(_err())
+        if got == 0:
+            return [[] for _ in range(G)], secs.value
+        rows = out.reshape(-1)      # rows are [G][n_beams][n_predict as clamped]
+        return [[(rows[(p * B + r) * got:(p * B + r) * got + int(ol[p * B + r])].copy(), float(scores[p * B + r])) for r in range(int(counts[p]))]
+                for p in range(G)], secs.value
 
     def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
                         repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):

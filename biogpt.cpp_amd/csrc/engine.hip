@@ -293,6 +293,14 @@ struct biogpt_hip_ctx {
     int sample_cap = 0;
     int32_t *sample_live_host = nullptr;
     hipEvent_t sample_ev[2] = {};
+    // beam search over a batch of prompts (biogpt_hip_generate_beam_batch): its captured steps (indexed as graph_beam, for graph_bbatch_g groups of
+    // graph_bbatch_b beams), one block of device state allocated once at its largest (bbatch_* offsets below: captured steps keep their pointers),
+    // and the pinned counts of unfinished groups of two groups of steps
+    hipGraphExec_t graph_bbatch[24] = {};
+    int graph_bbatch_g = 0, graph_bbatch_b = 0;
+    uint8_t *bbatch_buf = nullptr;
+    int32_t *bbatch_live_host = nullptr;
+    hipEvent_t bbatch_ev[2] = {};
     // generation rules (kernels_rules.hip.h): RulesCtl, RULES_ROWS RulesRow, then the call's prompts (one copy per prompt); allocated once, at its
     // largest, so that captured steps keep their pointers
     uint8_t *rules_buf = nullptr;
@@ -1463,13 +1471,16 @@ void destroy(biogpt_hip_ctx *c) {
     for (auto &g : c->graph_sample) if (g) (void)hipGraphExecDestroy(g);
     for (auto &e : c->sample_ev) if (e) (void)hipEventDestroy(e);
     if (c->sample_live_host) (void)hipHostFree(c->sample_live_host);
+    for (auto &g : c->graph_bbatch) if (g) (void)hipGraphExecDestroy(g);
+    for (auto &e : c->bbatch_ev) if (e) (void)hipEventDestroy(e);
+    if (c->bbatch_live_host) (void)hipHostFree(c->bbatch_live_host);
     xpipe_release(c);
     if (c->topk_host) (void)hipHostFree(c->topk_host);
     if (c->mbox_host) (void)hipHostFree(c->mbox_host);
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->beam_ctl, (void *)c->beam_cand, (void *)c->sample_ctl, (void *)c->rules_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->beam_ctl, (void *)c->beam_cand, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->bbatch_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1649,6 +1660,7 @@ int biogpt_hip_refresh_options(biogpt_hip_ctx *ctx) {
     ctx->graph_beam_n = 0;
     for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     ctx->graph_sample_n = 0;
+    for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     // the pipelined path is rebuilt from the new options (GELU slice, fault hook, long-context buffers) -- which also re-arms a context that had abandoned the
     // path after a disturbed launch: an explicit call, not an automatic cool-down
     HIP_TRY(-2, hipSetDevice(ctx->device));
@@ -2018,6 +2030,7 @@ int biogpt_hip_eval_all(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, i
         ctx->graph_beam_n = 0;
         for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         ctx->graph_sample_n = 0;
+        for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     }
     if (!upload_state(ctx, tokens, n, n_past)) return -2;
     if (!enqueue_forward(ctx, n, true, n_past + n)) return -2;
@@ -2222,6 +2235,7 @@ static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
     for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     return true;
 }
 
@@ -2310,6 +2324,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
         for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     }
     if (ctx->graph_batch_n != n_seqs) {
         for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
@@ -2407,6 +2422,7 @@ static bool ensure_logits_rows(biogpt_hip_ctx *c, size_t rows) {
     c->graph_beam_n = 0;
     for (auto &g : c->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     c->graph_sample_n = 0;
+    for (auto &g : c->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     return true;
 }
 
@@ -3101,6 +3117,218 @@ int biogpt_hip_generate_sample_rules(biogpt_hip_ctx *ctx, const int32_t *prompts
     int rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, rules);
     if (rc < 0 && xpipe_retry(ctx, 0))
         rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, rules);
+    return rc;
+}
+
+// ---- beam search over a batch of prompts: G groups of B columns of the batched decode step, every group a search of its own (kernels_beam.hip.h) ----
+// Built like generate_sample_once: every prompt is evaluated once, into the slot of its group's first column (pack_column_passes, slot stride B), and
+// kv_share_kernel copies its rows to the group's other slots.  Every step, the first included, is forward(G * B columns) + beam_group_rows +
+// beam_group_select + kv_group_fork (graph_bbatch, laid out like graph_beam): at a group's first step the device expands its first row alone, which is the
+// single call's one-column step.  The host enqueues steps in groups of 8 and reads the count of unfinished groups of the group before through pinned
+// memory.  The context's own K / V cache, position and logits row are left alone.
+constexpr int BBATCH_COLS = 512;    // columns of a call, at most
+static size_t bbatch_forks_off() { return sizeof(bgk::BeamBatchHdr); }
+static size_t bbatch_skip_off() { return bbatch_forks_off() + sizeof(bgk::BeamFork) * BBATCH_COLS; }
+static size_t bbatch_ctl_off() { return bbatch_skip_off() + 4 * (size_t)BBATCH_COLS; }
+static size_t bbatch_cand_off() { return bbatch_ctl_off() + sizeof(bgk::BeamCtl) * BBATCH_COLS; }
+static size_t bbatch_ids_off() { return bbatch_cand_off() + sizeof(bgk::BeamCand) * BBATCH_COLS * 2 * bgk::BEAM_MAX; }
+
+static void launch_beam_group_rows(biogpt_hip_ctx *c, int G, int B, bool given) {
+    const int V = c->hp.n_vocab, K = 2 * B;
+    const bgk::BeamCtl *ctl = reinterpret_cast<const bgk::BeamCtl *>(c->bbatch_buf + bbatch_ctl_off());
+    bgk::BeamBatchHdr *hdr = reinterpret_cast<bgk::BeamBatchHdr *>(c->bbatch_buf);
+    bgk::BeamCand *cand = reinterpret_cast<bgk::BeamCand *>(c->bbatch_buf + bbatch_cand_off());
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(G * B), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, ctl, B, hdr, cand); };
+    if (given) {
+        if (K <= 8) go(bgk::beam_group_rows_kernel<8, true>);
+        else if (K <= 16) go(bgk::beam_group_rows_kernel<16, true>);
+        else go(bgk::beam_group_rows_kernel<32, true>);
+    } else if (K <= 8) go(bgk::beam_group_rows_kernel<8, false>);
+    else if (K <= 16) go(bgk::beam_group_rows_kernel<16, false>);
+    else go(bgk::beam_group_rows_kernel<32, false>);
+}
+
+static bool enqueue_beam_group_select(biogpt_hip_ctx *c, int G, int B, bool rules) {
+    const auto &hp = c->hp;
+    const int P = hp.n_positions;
+    bgk::BeamBatchHdr *hdr = reinterpret_cast<bgk::BeamBatchHdr *>(c->bbatch_buf);
+    bgk::BeamFork *forks = reinterpret_cast<bgk::BeamFork *>(c->bbatch_buf + bbatch_forks_off());
+    int32_t *col_skip = reinterpret_cast<int32_t *>(c->bbatch_buf + bbatch_skip_off());
+    if (rules) {
+        if (!enqueue_rules(c, G * B, col_skip, 1)) return false;
+        launch_beam_group_rows(c, G, B, true);
+    } else launch_beam_group_rows(c, G, B, false);
+    HIP_TRY(false, hipGetLastError());
+    hipLaunchKernelGGL(bgk::beam_group_select_kernel, dim3(G), dim3(bgk::BEAM_SELECT_THREADS), 0, c->stream,
+                       reinterpret_cast<const bgk::BeamCand *>(c->bbatch_buf + bbatch_cand_off()), reinterpret_cast<bgk::BeamCtl *>(c->bbatch_buf + bbatch_ctl_off()), B,
+                       c->seq, c->seq_gen, P, reinterpret_cast<int32_t *>(c->bbatch_buf + bbatch_ids_off()), hdr, forks, col_skip);
+    HIP_TRY(false, hipGetLastError());
+    if (B > 1) {
+        hipLaunchKernelGGL(bgk::kv_group_fork_kernel, dim3(hp.n_layer * hp.n_head, bgk::BEAM_FORK_WGS, 2), dim3(256), 0, c->stream, hdr, forks, c->bk, c->bv,
+                           (int64_t)hp.n_layer * P * hp.d_model, P, hp.d_model / hp.n_head, c->seq_gen, P);
+        HIP_TRY(false, hipGetLastError());
+    }
+    return true;
+}
+
+static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_batch, int32_t n_beams,
+                                    int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping, const biogpt_hip_gen_rules *rules,
+                                    int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts, double *seconds_out) {
+    XpCallScope xp_scope(ctx);
+    struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } } xc_scope{ctx};
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!prompts || !prompt_lens || !out_ids || !out_lens || !out_scores || !out_counts) BG_FAIL(-1, "null argument");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (n_prompts < 1) BG_FAIL(-1, "n_prompts must be >= 1");
+    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
+    if ((int64_t)n_prompts * n_beams > BBATCH_COLS) BG_FAIL(-1, "n_prompts x n_beams must be at most %d", BBATCH_COLS);   // each column owns a full F32 KV cache
+    const int G = n_prompts, B = n_beams, n_seqs = G * B;
+    if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_prompts x n_beams (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
+    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
+    const auto &hp = ctx->hp;
+    const int P = hp.n_positions;
+    if (eos_id < -1 || eos_id >= hp.n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, hp.n_vocab);
+    if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
+    if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
+    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
+        BG_FAIL(-1, "beam search needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (hp.n_vocab < 2 * B) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", hp.n_vocab);
+    if (!check_rules(rules, hp.n_vocab, P)) return -1;
+    if (rules_ban(rules, eos_id) && hp.n_vocab - rules->n_suppress - 1 - P < 2 * B)
+        BG_FAIL(-1, "the rules could leave a row fewer than 2 x n_beams candidates: n_vocab - n_suppress - 1 - n_positions = %d < %d", hp.n_vocab - rules->n_suppress - 1 - P, 2 * B);
+    const bool ru = rules_active(rules, eos_id);
+    int max_len = 0;
+    long total = 0;
+    for (int p = 0; p < G; p++) {
+        if (prompt_lens[p] < 1) BG_FAIL(-1, "empty prompt (prompt %d)", p);
+        if (!check_eval_args(ctx, prompts + total, prompt_lens[p], 0)) return -1;
+        max_len = std::max(max_len, prompt_lens[p]);
+        total += prompt_lens[p];
+    }
+    n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
+    if (n_predict <= 0) return 0;
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
+    if (!ensure_seq_caches(ctx, n_seqs)) return -2;
+    if (std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return -2;   // (as generate_greedy_batch: before any capture)
+    if (!ensure_logits_rows(ctx, (size_t)n_seqs)) return -2;
+    if (!ctx->bbatch_buf) {
+        HIP_TRY(-2, hipMalloc(&ctx->bbatch_buf, bbatch_ids_off() + (size_t)BBATCH_COLS * P * 4));
+        HIP_TRY(-2, hipHostMalloc(&ctx->bbatch_live_host, 2 * sizeof(int32_t)));
+        for (auto &e : ctx->bbatch_ev) HIP_TRY(-2, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (ctx->graph_bbatch_g != G || ctx->graph_bbatch_b != B) {
+        for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        ctx->graph_bbatch_g = G; ctx->graph_bbatch_b = B;
+    }
+    bgk::BeamBatchHdr *const hdr = reinterpret_cast<bgk::BeamBatchHdr *>(ctx->bbatch_buf);
+    {   // the call's parameters and every group's initial state; every column starts as its prompt's last token (the prompt pass below leaves it to
+        // the first step).  The rules kernel skips the columns whose row the first step does not expand.
+        std::vector<uint8_t> h(bbatch_ctl_off() + sizeof(bgk::BeamCtl) * (size_t)G, 0);
+        bgk::BeamBatchHdr hh{};
+        hh.n_live = G;
+        std::memcpy(h.data(), &hh, sizeof(hh));
+        int32_t *skip = reinterpret_cast<int32_t *>(h.data() + bbatch_skip_off());
+        bgk::BeamCtl *hc = reinterpret_cast<bgk::BeamCtl *>(h.data() + bbatch_ctl_off());
+        std::vector<bgk::SeqState> hs((size_t)n_seqs);
+        size_t o = 0;
+        for (int p = 0; p < G; p++) {
+            o += (size_t)prompt_lens[p];
+            bgk::BeamCtl &c = hc[p];
+            c.n_beams = B; c.n_prompt = prompt_lens[p]; c.n_predict = n_predict; c.eos_id = eos_id;
+            c.length_penalty = length_penalty; c.early_stopping = early_stopping; c.ids_stride = P;
+            c.heur_unsat = 1;
+            for (int j = 0; j < B; j++) {
+                bgk::SeqState &st = hs[(size_t)p * B + j];
+                st = bgk::SeqState{};
+                st.n_past = prompt_lens[p] - 1; st.token = prompts[o - 1]; st.seq_id = p * B + j;
+                skip[p * B + j] = j > 0 ? 1 : 0;
+            }
+        }
+        HIP_TRY(-2, hipMemcpy(ctx->bbatch_buf, h.data(), h.size(), hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * n_seqs, hipMemcpyHostToDevice));
+        if (ru && !rules_upload(ctx, rules, 1, eos_id, prompts, prompt_lens, G, B)) return -2;
+    }
+
+    // 2 .. 8 columns: the steps as column-per-XCD launches while this call holds the device's pipeline slot (decided ONCE, before any capture)
+    ctx->xc_batch = (n_seqs >= 2 && n_seqs <= 8 && max_len + 1 <= 256 && xcols_prepare(ctx, n_seqs, std::min(256, max_len + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
+    const int pl = ctx->xc_batch, gset = 6 * pl + (ru ? 12 : 0);      // gset: which set of captured steps
+    auto group_step = [&](int t_max) -> bool { return enqueue_forward(ctx, n_seqs, false, t_max, true) && enqueue_beam_group_select(ctx, G, B, ru); };
+    const bool use_graph = ctx->opt.no_graph == 0 && (pl != 0 || plain_graph_begin(ctx));      // (a captured step is not replayed beside another context's persistent launch)
+    if (use_graph && n_predict > 1) {
+        for (int b = graph_bucket(max_len + 1); b <= graph_bucket(max_len + n_predict - 1); b++) {
+            if (ctx->graph_bbatch[gset + b]) continue;
+            hipGraph_t g = nullptr;
+            HIP_TRY(-2, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+            const bool ok = group_step(bucket_tmax(ctx, b));
+            hipError_t e = hipStreamEndCapture(ctx->stream, &g);
+            if (!ok) { if (g) (void)hipGraphDestroy(g); return -2; }
+            HIP_TRY(-2, e);
+            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_bbatch[gset + b], g, nullptr, nullptr, 0));
+            (void)hipGraphDestroy(g);
+        }
+    }
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!pack_column_passes(ctx, prompts, prompt_lens, G, n_batch,
+                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }, B))
+        return -2;
+    if (B > 1) {
+        hipLaunchKernelGGL(bgk::kv_share_kernel, dim3(hp.n_layer * hp.n_head, n_seqs, 2), dim3(256), 0, ctx->stream, ctx->seq, B, ctx->bk, ctx->bv,
+                           (int64_t)hp.n_layer * P * hp.d_model, P, hp.d_model / hp.n_head);
+        HIP_TRY(-2, hipGetLastError());
+    }
+    if (!group_step(max_len)) return -2;    // step 1: the last prompt token of every group; its first row alone expands
+    for (int k = 2, grp = 0; k <= n_predict; grp++) {
+        for (const int end = std::min(n_predict, k + 7); k <= end; k++) {
+            const int t_max = max_len + k - 1;      // keys visible to the token at position max_len + k - 2
+            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_bbatch[gset + graph_bucket(t_max)], ctx->stream));
+            else if (!group_step(t_max)) return -2;
+        }
+        HIP_TRY(-2, hipMemcpyAsync(ctx->bbatch_live_host + (grp & 1), &hdr->n_live, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(-2, hipEventRecord(ctx->bbatch_ev[grp & 1], ctx->stream));
+        if (grp > 0) {   // the group of steps before this one has finished: stop enqueueing once every search has (one group stays in flight)
+            HIP_TRY(-2, hipEventSynchronize(ctx->bbatch_ev[(grp - 1) & 1]));
+            if (ctx->bbatch_live_host[(grp - 1) & 1] <= 0) break;
+        }
+    }
+    std::vector<bgk::BeamCtl> hc((size_t)G);
+    std::vector<int32_t> ids((size_t)n_seqs * P);
+    HIP_TRY(-2, hipMemcpyAsync(hc.data(), ctx->bbatch_buf + bbatch_ctl_off(), sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(-2, hipMemcpyAsync(ids.data(), ctx->bbatch_buf + bbatch_ids_off(), ids.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    for (int p = 0; p < G; p++) {
+        const bgk::BeamCtl &st = hc[(size_t)p];
+        if (!st.done || st.pool_n < 1 || st.pool_n > B) BG_FAIL(-2, "internal: beam search of prompt %d ended with %d hypotheses (done word %d)", p, st.pool_n, st.done);
+        out_counts[p] = st.pool_n;
+        for (int r = 0; r < B; r++) {
+            const size_t row = (size_t)p * B + r;
+            int32_t *o = out_ids + row * n_predict;
+            std::fill(o, o + n_predict, -1);
+            out_lens[row] = 0; out_scores[row] = 0.0f;
+            if (r >= st.pool_n) continue;
+            const int slot = st.pool_order[r];
+            out_lens[row] = std::min(st.pool_len[slot], n_predict);
+            out_scores[row] = st.pool_score[slot];
+            std::memcpy(o, ids.data() + ((size_t)p * B + slot) * P, (size_t)out_lens[row] * 4);
+        }
+    }
+    return n_predict;
+}
+
+int biogpt_hip_generate_beam_batch(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_batch, int32_t n_beams,
+                                   int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping, const biogpt_hip_gen_rules *rules,
+                                   int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts, double *seconds_out) {
+    int rc = generate_beam_batch_once(ctx, prompts, prompt_lens, n_prompts, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, rules, out_ids, out_lens,
+                                      out_scores, out_counts, seconds_out);
+    if (rc < 0 && xpipe_retry(ctx, 0))
+        rc = generate_beam_batch_once(ctx, prompts, prompt_lens, n_prompts, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, rules, out_ids, out_lens,
+                                      out_scores, out_counts, seconds_out);
     return rc;
 }
 

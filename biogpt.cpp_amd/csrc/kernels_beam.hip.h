@@ -13,6 +13,19 @@
 //                       (head-major cache: one contiguous run per (layer, head)), plus the token history.  Fixed grid (capturable).
 //
 // Nothing here leaves the device; the host only reads the done word between groups of steps and the pool at the end.
+//
+// Beam search over a batch of prompts (biogpt_hip_generate_beam_batch): G independent searches of B beams in one step of G * B columns.
+// Group g owns the columns and cache slots [g * B, (g + 1) * B) and one BeamCtl of an array of G; everything a group's kernels touch is the
+// single search's state shifted by the group's base, so the bodies above serve both:
+//
+//   beam_group_rows_kernel    one workgroup per column: beam_rows_body with the running score of the column's group.  A finished group's rows
+//                             and, at a group's first step, every row but its first return at once.
+//   beam_group_select_kernel  one workgroup per group: beam_select_body on the group's slices, then the group's forks (column base added) appended
+//                             to ONE compacted list, the per-column skip words of the rules kernel, and the count of unfinished groups.
+//   kv_group_fork_kernel      grid (n_layer * n_head, BEAM_FORK_WGS, 2): the workgroups of a (layer, head, K | V) stride over the compacted list.
+//                             The grid is fixed (capturable) and does not grow with G * (B - 1).
+//
+// A finished group leaves everything alone: its columns keep token and position and recompute a K / V row they already hold.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -73,8 +86,10 @@ __device__ __forceinline__ void beam_insert(float v, int i, float (&tv)[KM], int
 // The body of beam_rows_kernel.  GIVEN = false: the row holds logits (the log-softmax is taken here).  GIVEN = true: it holds log-probabilities
 // already, processed by rules_rows_kernel (kernels_rules.hip.h), and its values are taken as they are (an entry at -inf becomes a candidate only
 // where fewer than K finite ones are left, which the argument check of the rules excludes).
+// row: the row's n_vocab values; run_score: the accumulated score of the beam in this row; col: the column the candidates name as their parent;
+// cand: the row's K candidates.
 template <int KM, bool GIVEN>
-__device__ __forceinline__ void beam_rows_body(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
+__device__ __forceinline__ void beam_rows_body(const float *row, int n_vocab, const float *run_score, int col, int K, BeamCand *cand) {
     __shared__ float w_v[LP_THREADS / 64][KM];
     __shared__ int w_i[LP_THREADS / 64][KM];
     __shared__ double s_ls;
@@ -82,8 +97,7 @@ __device__ __forceinline__ void beam_rows_body(const float *logits, int ldl, int
     __shared__ int t_i[LP_THREADS];
     __shared__ float s_thr_v;
     __shared__ int s_thr_i;
-    const int col = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float *row = logits + (size_t)col * ldl;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     float m = 0.0f;
     if constexpr (!GIVEN) {
         int bi;
@@ -164,9 +178,9 @@ __device__ __forceinline__ void beam_rows_body(const float *logits, int ldl, int
                 float lp = v;
                 if constexpr (!GIVEN) lp = (float)(((double)v - (double)m) - s_ls);
                 BeamCand c;
-                c.score = ctl->run_score[col] + lp;
+                c.score = *run_score + lp;
                 c.col = col; c.id = id; c.pad = 0;
-                cand[(size_t)col * K + rank] = c;
+                cand[rank] = c;
             }
         }
     }
@@ -175,13 +189,15 @@ __device__ __forceinline__ void beam_rows_body(const float *logits, int ldl, int
 // logits: [n_rows][ldl] (row r = column r); K = 2 * n_beams <= KM; cand: [n_rows][K]
 template <int KM>
 __global__ __launch_bounds__(LP_THREADS) void beam_rows_kernel(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
-    beam_rows_body<KM, false>(logits, ldl, n_vocab, ctl, K, cand);
+    const int col = blockIdx.x;
+    beam_rows_body<KM, false>(logits + (size_t)col * ldl, n_vocab, &ctl->run_score[col], col, K, cand + (size_t)col * K);
 }
 
 // the same over rows of processed log-probabilities (a step with generation rules)
 template <int KM>
 __global__ __launch_bounds__(LP_THREADS) void beam_given_rows_kernel(const float *logp, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
-    beam_rows_body<KM, true>(logp, ldl, n_vocab, ctl, K, cand);
+    const int col = blockIdx.x;
+    beam_rows_body<KM, true>(logp + (size_t)col * ldl, n_vocab, &ctl->run_score[col], col, K, cand + (size_t)col * K);
 }
 
 // candidate order of a step: score descending, then the parent's rank, then the token id
@@ -195,14 +211,15 @@ __device__ __forceinline__ float beam_norm(float s, int gen_len, float lp) { ret
 
 // n_rows beam rows (1 at the first step, n_beams after) of K = 2 * n_beams candidates each.  seq: the n_beams column states;
 // seq_gen: [column][gen_stride] token histories; pool_ids: [slot][ctl->ids_stride].
-__global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const BeamCand *cand, int n_rows, BeamCtl *ctl, SeqState *seq,
-                                                                          int32_t *seq_gen, int gen_stride, int32_t *pool_ids) {
+// The body of beam_select_kernel; false: the search had stopped before this step and nothing was touched (uniform over the workgroup).
+__device__ __forceinline__ bool beam_select_body(const BeamCand *cand, int n_rows, BeamCtl *ctl, SeqState *seq, int32_t *seq_gen, int gen_stride,
+                                                 int32_t *pool_ids) {
     __shared__ BeamCand s_c[2 * BEAM_MAX];
     __shared__ int s_pend[BEAM_MAX];     // per pool slot: the candidate whose ids it takes in this step, -1 none
     __shared__ int s_run[BEAM_MAX], s_dest[BEAM_MAX], s_taken[BEAM_MAX];   // thread 0's lists (LDS: no scratch)
     __shared__ int s_k;
     const int tid = threadIdx.x;
-    if (ctl->done) return;
+    if (ctl->done) return false;
     const int B = ctl->n_beams, K = 2 * B, n = n_rows * K;
     if (tid < n) {   // rank of this candidate among all of them (a total order: (column, id) pairs are unique)
         const BeamCand c = cand[tid];
@@ -302,6 +319,12 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const 
         int32_t *dst = pool_ids + (size_t)slot * ctl->ids_stride;
         for (int j = tid; j < k; j += blockDim.x) dst[j] = j + 1 < k ? src[j] : s_c[i].id;
     }
+    return true;
+}
+
+__global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const BeamCand *cand, int n_rows, BeamCtl *ctl, SeqState *seq,
+                                                                          int32_t *seq_gen, int gen_stride, int32_t *pool_ids) {
+    (void)beam_select_body(cand, n_rows, ctl, seq, seq_gen, gen_stride, pool_ids);
 }
 
 // grid (n_layer * n_head, max(1, n_beams - 1), 2 [K, V]); seq_stride floats between two slots, P * dk between two heads
@@ -319,6 +342,79 @@ __global__ __launch_bounds__(256) void kv_fork_kernel(const BeamCtl *ctl, float 
     for (int i = threadIdx.x; i < n4; i += blockDim.x) d4[i] = s4[i];
     if (blockIdx.x == 0 && blockIdx.z == 0)
         for (int j = threadIdx.x; j < ctl->fork_gen; j += blockDim.x) seq_gen[(size_t)dst * gen_stride + j] = seq_gen[(size_t)src * gen_stride + j];
+}
+
+// ---- beam search over a batch of prompts -------------------------------------------------------------------------------------------------
+
+constexpr int BEAM_FORK_WGS = 8;               // copy workgroups per (layer, head, K | V), striding over the step's fork list
+
+struct BeamBatchHdr {
+    int32_t n_live;        // groups still searching
+    int32_t fork_n;        // entries of the fork list of this step (reset by the row kernel of the next)
+    int32_t pad[2];
+};
+
+struct BeamFork {
+    int32_t src, dst;      // cache slots (= columns)
+    int32_t lo, hi;        // K / V rows [lo, hi)
+    int32_t gen;           // tokens of history
+    int32_t pad[3];
+};
+
+// logits: [G * B][ldl] (row r = column r); ctl: [G]; cand: [G * B][2 * B].  KM >= 2 * B.
+template <int KM, bool GIVEN>
+__global__ __launch_bounds__(LP_THREADS) void beam_group_rows_kernel(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int B, BeamBatchHdr *hdr,
+                                                                     BeamCand *cand) {
+    const int col = blockIdx.x, g = col / B, j = col - g * B;
+    if (col == 0 && threadIdx.x == 0) hdr->fork_n = 0;      // the copies of the step before are done (stream order)
+    const BeamCtl *c = ctl + g;
+    if (c->done || (c->step == 0 && j > 0)) return;         // (a group's first step expands its first row alone)
+    beam_rows_body<KM, GIVEN>(logits + (size_t)col * ldl, n_vocab, &c->run_score[j], j, 2 * B, cand + (size_t)col * 2 * B);
+}
+
+// grid: G.  seq, seq_gen, col_skip: all G * B columns; pool_ids: [G * B][ctl->ids_stride]; forks: room for G * (B - 1) entries.
+__global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_group_select_kernel(const BeamCand *cand, BeamCtl *ctl, int B, SeqState *seq, int32_t *seq_gen,
+                                                                                int gen_stride, int32_t *pool_ids, BeamBatchHdr *hdr, BeamFork *forks,
+                                                                                int32_t *col_skip) {
+    const int g = blockIdx.x, base = g * B;
+    BeamCtl *c = ctl + g;
+    const int n_rows = c->step == 0 ? 1 : B;
+    if (!beam_select_body(cand + (size_t)base * 2 * B, n_rows, c, seq + base, seq_gen + (size_t)base * gen_stride, gen_stride,
+                          pool_ids + (size_t)base * c->ids_stride))
+        return;
+    if (threadIdx.x != 0) return;
+    const int done = c->done;
+    if (done) atomicSub(&hdr->n_live, 1);
+    // every slot of the group holds the prompt's rows already (kv_share_kernel before the first step, then the step's own row): a fork
+    // copies the generated rows only
+    const int lo = c->n_prompt, hi = c->fork_hi, gen = c->fork_gen, nf = c->fork_n;
+    if (!done && nf > 0 && (hi > lo || gen > 0)) {
+        const int at = atomicAdd(&hdr->fork_n, nf);
+        for (int f = 0; f < nf; f++) {
+            BeamFork k;
+            k.src = base + c->fork_src[f]; k.dst = base + c->fork_dst[f]; k.lo = lo; k.hi = hi; k.gen = gen;
+            k.pad[0] = k.pad[1] = k.pad[2] = 0;
+            forks[at + f] = k;
+        }
+    }
+    for (int j = 0; j < B; j++) col_skip[base + j] = done;
+}
+
+// grid (n_layer * n_head, BEAM_FORK_WGS, 2 [K, V]); seq_stride floats between two slots, P * dk between two heads
+__global__ __launch_bounds__(256) void kv_group_fork_kernel(const BeamBatchHdr *hdr, const BeamFork *forks, float *kroot, float *vroot, int64_t seq_stride,
+                                                            int P, int dk, int32_t *seq_gen, int gen_stride) {
+    const int n = hdr->fork_n;
+    const size_t run0 = (size_t)blockIdx.x * P * dk;    // (layer, head) run; layers are n_head runs apart
+    float *root = blockIdx.z == 0 ? kroot : vroot;
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const BeamFork k = forks[f];
+        const float4 *s4 = reinterpret_cast<const float4 *>(root + (size_t)k.src * seq_stride + run0 + (size_t)k.lo * dk);
+        float4 *d4 = reinterpret_cast<float4 *>(root + (size_t)k.dst * seq_stride + run0 + (size_t)k.lo * dk);
+        const int n4 = k.hi > k.lo ? (k.hi - k.lo) * dk / 4 : 0;
+        for (int i = threadIdx.x; i < n4; i += blockDim.x) d4[i] = s4[i];
+        if (blockIdx.x == 0 && blockIdx.z == 0)
+            for (int j = threadIdx.x; j < k.gen; j += blockDim.x) seq_gen[(size_t)k.dst * gen_stride + j] = seq_gen[(size_t)k.src * gen_stride + j];
+    }
 }
 
 }  // namespace bgk

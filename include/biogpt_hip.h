@@ -303,6 +303,25 @@ int biogpt_hip_generate_sample_rules(biogpt_hip_ctx *ctx, const int32_t *prompts
                                      const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, double *seconds_out,
                                      const biogpt_hip_gen_rules *rules);
 
+/* Beam search over a batch of prompts in one call: n_prompts independent searches of n_beams beams each, as the n_prompts * n_beams columns of one
+ * batched decode step (group g owns the columns and K / V cache slots [g * n_beams, (g + 1) * n_beams)).  The selection, the pool of finished
+ * hypotheses, the stopping rules, the slot assignment and the K / V copies of forked beams run per group on the device inside the captured step
+ * (csrc/kernels_beam.hip.h); a finished group leaves its state alone while the others go on.  prompts = the prompts concatenated,
+ * prompt_lens[n_prompts] their lengths (a prompt is evaluated once, its K / V rows copied to its group's other slots); n_predict is clamped to
+ * n' = n_positions - max(prompt_lens).  For prompt p the result is what
+ *   biogpt_hip_generate_beam_rules(prompt p, n_batch, n_beams, n', eos_id, length_penalty, early_stopping, rules)
+ * returns, hypothesis for hypothesis, ids and f32 scores bit for bit (n_prompts = 1 is biogpt_hip_generate_beam).  rules == NULL: none.
+ * out_ids is [n_prompts][n_beams][returned n_predict] (-1 past a hypothesis's length and in rows past a prompt's count), out_lens and out_scores
+ * [n_prompts][n_beams], out_counts[n_prompts] the hypotheses written per prompt.  n_beams in [1, 16]; n_prompts * n_beams in [1, 512] (each column
+ * owns a full F32 KV cache); the other arguments as biogpt_hip_generate_beam_rules checks them.  The context's own K / V cache, position and logits
+ * row are left alone.  Needs the BioGPT-base fast chain (block-quantized weights); anything else fails with -1.  Returns the clamped n_predict, 0 if
+ * that is <= 0, < 0 on error (argument errors, -1, the message names the field, come before any HIP call). */
+int biogpt_hip_generate_beam_batch(biogpt_hip_ctx *ctx, const int32_t *prompts /* concatenated */, const int32_t *prompt_lens, int32_t n_prompts,
+                                   int32_t n_batch, int32_t n_beams, int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping,
+                                   const biogpt_hip_gen_rules *rules /* NULL: none */,
+                                   int32_t *out_ids /* [n_prompts][n_beams][returned n_predict], -1 filled */, int32_t *out_lens /* [n_prompts][n_beams] */,
+                                   float *out_scores /* [n_prompts][n_beams] */, int32_t *out_counts /* [n_prompts]: hypotheses returned */, double *seconds_out);
+
 /* rules_rows_kernel over n_rows <= 4096 rows of n_vocab floats held in host memory.  mode 0: the rows are logits; mode 1: each row becomes its
  * log-probabilities first, (float)(((double)l - max) - log(sum exp(l - max))).  Row r's history is hist_lens[r] tokens of hist (the histories
  * concatenated), the first prompt_lens[r] of them its prompt.  rows_out: [n_rows][n_vocab].  For tests of the kernel itself. */
