@@ -178,6 +178,7 @@ SYMBOLS = [
     ("biogpt_hip_sample_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P]),
     ("biogpt_hip_score", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_score_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("biogpt_hip_score_continuations", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_hidden", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     ("biogpt_hip_embed_batch", C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(EmbedOpts), _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_read_kv", C.c_int, [_P, C.c_int, C.c_size_t, C.c_size_t, _P]),
@@ -607,6 +608,34 @@ class BiogptModel:
             out.append((lp[off:off + k].copy(), am[off:off + k].copy(), lg[off:off + k].copy()))
             off += int(k)
         return out
+
+    def score_continuations(self, prefix, continuations):
+        """Many continuations of ONE prefix (lists of ids): the prefix is evaluated once and read in place by every continuation.  Returns one
+        (logprobs, argmax, logits) triple per continuation, each array of the continuation's length: entry i is log P(cont[i] | prefix,
+        cont[:i]), the arg-max of that row and cont[i]'s logit -- rows len(prefix) - 1 + i of score(prefix + cont), bit for bit."""
+        pre = np.ascontiguousarray(prefix, dtype=np.int32).reshape(-1)
+        lens = np.asarray([len(c) for c in continuations], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int32).reshape(-1) for c in continuations])
+                                    if len(continuations) else np.zeros(0, np.int32))
+        n = max(int(flat.size), 1)
+        lp, am, lg = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        secs = C.c_double(0.0)
+        if lib().biogpt_hip_score_continuations(self._h, pre.ctypes.data, int(pre.size), flat.ctypes.data, lens.ctypes.data, len(continuations),
+                                                lp.ctypes.data, am.ctypes.data, lg.ctypes.data, C.byref(secs)) != 0:
+            raise BiogptError(_err())
+        self.score_seconds = secs.value
+        out, off = [], 0
+        for k in lens:
+            out.append((lp[off:off + k].copy(), am[off:off + k].copy(), lg[off:off + k].copy()))
+            off += int(k)
+        return out
+
+    def rank_continuations(self, prefix, continuations, normalize=False):
+        """(order, sums): the indices of `continuations` from the most to the least likely after `prefix`, and every continuation's summed
+        log-probability (float64 sums on the host; normalize: divided by the continuation's length).  Ties keep the order given."""
+        rows = self.score_continuations(prefix, continuations)
+        sums = np.asarray([lp.astype(np.float64).sum() / (len(lp) if normalize else 1) for lp, _, _ in rows], dtype=np.float64)
+        return np.argsort(-sums, kind="stable"), sums
 
     # -- hidden states, pooled embeddings, classification heads (no reference counterpart) --
     def hidden(self, tokens, n_past=0):

@@ -1031,8 +1031,11 @@ constexpr int MFMA_MIN_DECODE_COLS = 48, MFMA_MIN_PASS_COLS = 64, GROUPED_ATTN_M
 // hid: no logits at all (biogpt_hip_hidden / biogpt_hip_embed_batch) -- the first hid->layers layers only, then the final LayerNorm of every column
 // as f32 rows into hid->ln_out; ln_out == null: no LayerNorm either, the rows are the residual stream c->x itself.
 struct HiddenStage { int layers; float *ln_out; };
+// shared (with batch + cols): the columns read their first SeqState::pad[0] K / V rows from the slot SeqState::pad[1] (attn_fast_kernel<.., SHARED>;
+// biogpt_hip_score_continuations); with score, only the columns from head_from on get logits (rows 0 .. N - head_from of logits_all): the
+// columns in front of them are prefix columns whose K / V rows alone matter.  head_from == N: no lm_head at all.
 bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool batch = false, const bgk::SeqState *cols = nullptr, bool score = false,
-                     const HiddenStage *hid = nullptr) {
+                     const HiddenStage *hid = nullptr, bool shared = false, int head_from = 0) {
     (void)hipGetLastError();   // a failed call of some OTHER context / API leaves its code behind; the checks below are about these launches
     if (score || hid) all_rows = true;   // every row is needed: none of the launches that keep the activations on chip and compute the last row only
     if (N < 1 || N > c->hp.n_positions) BG_FAIL(false, "internal: a pass of %d columns exceeds the %d-column activation scratch", N, c->hp.n_positions);
@@ -1057,6 +1060,8 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
     bgk::DevMatrix img;
     auto tile = [&](const MatSlot &m) -> const bgk::DevMatrix * { if (!mfma) return nullptr; img = tile_matrix(c, m); return &img; };
     if (batch && !chain) BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (shared && !(batch && cols)) BG_FAIL(false, "internal: shared-prefix attention needs column states");
+    if (head_from < 0 || head_from > N || (head_from > 0 && !(shared && score))) BG_FAIL(false, "internal: head_from (%d) of a pass of %d columns", head_from, N);
     const int64_t seq_stride = (int64_t)hp.n_layer * P * D;
     float *const kroot = batch ? c->bk : c->memory_k;
     float *const vroot = batch ? c->bv : c->memory_v;
@@ -1138,6 +1143,13 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
                     hipLaunchKernelGGL(bgk::attn_split_scores_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
                     hipLaunchKernelGGL(bgk::attn_split_pv_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
                     hipLaunchKernelGGL(bgk::attn_split_combine_kernel, dim3(H), dim3(64), 0, st, a);
+                } else if (shared) {
+                    // the table below, on the instantiations that take a column's first rows from the shared slot
+                    const int t64 = (a.t_cap + 63) & ~63;
+                    if (N >= SLIM_ATTN_MIN_COLS) hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, true>), dim3(H, N), dim3(std::max(256, t64)), 0, st, a);
+                    else if (a.t_cap <= 256) hipLaunchKernelGGL((bgk::attn_fast_kernel<1, true, true>), dim3(H, N), dim3(4 * t64), 0, st, a);
+                    else if (a.t_cap <= 512) hipLaunchKernelGGL((bgk::attn_fast_kernel<2, false, true>), dim3(H, N), dim3(1024), 0, st, a);
+                    else hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, true>), dim3(H, N), dim3(1024), 0, st, a);
                 } else if (batch && N >= SLIM_ATTN_MIN_COLS) {
                     // many (sequence, head) workgroups: throughput over latency -- one lane quad per 4 keys (4 key passes), a
                     // quarter of the threads, four times as many workgroups resident per compute unit
@@ -1203,7 +1215,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
     // the final stage, LayerNorm + lm_head: which rows, and on which kernels
     enum class Final { None, LastRow, AllRows, AllRowsQ8, Hidden };
     const Final fin = hid ? Final::Hidden                                 // f32 rows in front of the lm_head (kernels_embed.hip.h)
-                    : (batch && cols && !score) ? Final::None            // prompt columns: only the KV rows matter
+                    : (batch && cols && (!score || head_from == N)) ? Final::None   // prompt columns: only the KV rows matter
                     : (batch || (score && pchain)) ? Final::AllRowsQ8     // LayerNorm+Q8 once, then the 8-column / matrix-core lm_head
                     : (all_rows || score) ? Final::AllRows                // every row on the generic kernel (eval_all; scoring of the other models)
                     : Final::LastRow;
@@ -1220,10 +1232,15 @@ bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool ba
         const MatSlot &m = c->plan.lm_head;
         const MvShape s = mv_shape(m.type, m.M, m.K);
         bgk::MatvecParams p = mv_base(c, m, s);
-        HIP_TRY(false, launch_lnq(c, c->x, N, c->plan.ln_w, c->plan.ln_b, q81, st));
+        // head_from > 0: the kernel a pass of n_rows columns alone would take.  Below 64 rows that is the 8-column VALU kernel, where score_batch of
+        // the concatenation (64 columns or more) takes the matrix cores: the bit-for-bit promise of biogpt_hip_score_continuations rests on the two
+        // lm_head kernels giving IDENTICAL f32 rows (exact int32 block sums, the same f32 scaling and block order in both) -- as score_batch ==
+        // score already does across pass sizes.  A change to either kernel's arithmetic breaks that equality (tests/test_gpu_prefix.py, test_gpu_score.py).
+        const int n_rows = N - head_from;
+        HIP_TRY(false, launch_lnq(c, c->x + (size_t)head_from * D, n_rows, c->plan.ln_w, c->plan.ln_b, q81, st));
         p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
-        p.N = N; p.out = c->logits_all; p.ldo = V;
-        HIP_TRY(false, launch_chain(CHAIN_LMHEAD_Q8, p, st, tile(c->plan.lm_head)));
+        p.N = n_rows; p.out = c->logits_all; p.ldo = V;
+        HIP_TRY(false, launch_chain(CHAIN_LMHEAD_Q8, p, st, (head_from > 0 && n_rows < MFMA_MIN_PASS_COLS) ? nullptr : tile(c->plan.lm_head)));
         return true;
     }
     {  // final LayerNorm + lm_head; only the rows that are returned (F8)
@@ -2239,6 +2256,26 @@ static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
     return true;
 }
 
+// One pass of packed columns (pack_column_passes, pack_continuation_passes): the column states go up to ctx->cols (grown to the pass), then
+// pass(n_cols, t_max, flat0) enqueues the pass; afterwards the host vector is empty and flat0 / pass_tmax stand at the next pass.
+static bool flush_columns(biogpt_hip_ctx *ctx, std::vector<bgk::SeqState> &cols, int &pass_tmax, size_t &flat0,
+                          const std::function<bool(int, int, size_t)> &pass) {
+    if (cols.empty()) return true;
+    if (cols.size() > ctx->cols_cap) {
+        if (ctx->cols) (void)hipFree(ctx->cols);
+        ctx->cols = nullptr; ctx->cols_cap = 0;
+        HIP_TRY(false, hipMalloc(&ctx->cols, sizeof(bgk::SeqState) * cols.size()));
+        ctx->cols_cap = cols.size();
+    }
+    HIP_TRY(false, hipMemcpyAsync(ctx->cols, cols.data(), sizeof(bgk::SeqState) * cols.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(false, hipStreamSynchronize(ctx->stream));   // the host vector is reused for the next pass
+    if (!pass((int)cols.size(), pass_tmax, flat0)) return false;
+    flat0 += cols.size();
+    cols.clear();
+    pass_tmax = 0;
+    return true;
+}
+
 // Prompt columns of several sequences in common passes (generate_greedy_batch's prompt ingestion, score_batch): every token is a
 // column that knows its sequence, its position and the end of its own n_batch-chunk (SeqState::seq_id / n_past / t_vis); whole
 // chunks are packed into passes of up to BIOGPT_HIP_PROMPT_COLS columns (at most n_positions: the activation scratch).  The columns
@@ -2250,22 +2287,7 @@ static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const i
     std::vector<bgk::SeqState> cols;
     int pass_tmax = 0;
     size_t flat0 = 0;
-    auto flush = [&]() -> bool {
-        if (cols.empty()) return true;
-        if (cols.size() > ctx->cols_cap) {
-            if (ctx->cols) (void)hipFree(ctx->cols);
-            ctx->cols = nullptr; ctx->cols_cap = 0;
-            HIP_TRY(false, hipMalloc(&ctx->cols, sizeof(bgk::SeqState) * cols.size()));
-            ctx->cols_cap = cols.size();
-        }
-        HIP_TRY(false, hipMemcpyAsync(ctx->cols, cols.data(), sizeof(bgk::SeqState) * cols.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(false, hipStreamSynchronize(ctx->stream));   // the host vector is reused for the next pass
-        if (!pass((int)cols.size(), pass_tmax, flat0)) return false;
-        flat0 += cols.size();
-        cols.clear();
-        pass_tmax = 0;
-        return true;
-    };
+    auto flush = [&]() -> bool { return flush_columns(ctx, cols, pass_tmax, flat0, pass); };
     size_t off = 0;
     for (int s = 0; s < n_seqs; s++) {
         const int len = lens[s];
@@ -2539,6 +2561,114 @@ int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32
                            float *logprob_out, int32_t *argmax_out, float *logit_out) {
     int rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
     if (rc < 0 && xpipe_retry(ctx, 0)) rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
+    return rc;
+}
+
+// ---- many continuations of one prefix: the prefix once, read in place by every continuation's columns ------------------------------------
+// The prefix rows [0, n_prefix - 1) go into slot 0 of the per-sequence caches as the prompt columns of generate_greedy_batch do (t_vis = position + 1,
+// no lm_head: none of their logits are wanted).  Continuation c owns slot 1 + c; its columns are the LAST prefix token at position n_prefix - 1
+// (every continuation re-evaluates it, as the samples of generate_sample do: one target per row) and then its own tokens but the last.  A
+// column's attention reads rows [0, n_prefix - 1) from slot 0 and the rest from its own slot (attn_fast_kernel<.., SHARED>): no K / V row is
+// copied.  Prefix columns and continuation columns travel in ONE stream of passes of up to BIOGPT_HIP_PROMPT_COLS columns, the prefix first: a
+// short call is one pass, and a continuation column may share a pass with the prefix columns it reads (the q/k/v launch of a layer has written
+// every column's row before its attention launch starts, as for the columns of one sequence).  pass(n_cols, t_max, flat0, n_pre): the first n_pre
+// columns of the pass are prefix columns; the others follow the flat order of `conts`, so their flat row (from flat0) is the flat index of their TARGET.
+static bool pack_continuation_passes(biogpt_hip_ctx *ctx, const int32_t *prefix, int n_prefix, const int32_t *conts, const int32_t *cont_lens, int n_conts,
+                                     const std::function<bool(int, int, size_t, int)> &pass) {
+    const size_t max_cols = (size_t)std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
+    std::vector<bgk::SeqState> cols;
+    int pass_tmax = 0, n_pre = 0;
+    size_t flat0 = 0;
+    auto flush = [&]() -> bool {
+        size_t at = flat0;
+        const int pre = n_pre;
+        if (!flush_columns(ctx, cols, pass_tmax, at, [&](int n_cols, int t_max, size_t f) { return pass(n_cols, t_max, f, pre); })) return false;
+        flat0 = at - (size_t)pre;      // prefix columns have no flat row
+        n_pre = 0;
+        return true;
+    };
+    for (int i = 0; i + 1 < n_prefix; i++) {
+        if (cols.size() == max_cols && !flush()) return false;
+        bgk::SeqState cst{};
+        cst.n_past = i; cst.token = prefix[i]; cst.seq_id = 0; cst.t_vis = i + 1;      // pad[0] = 0: every row its own
+        cols.push_back(cst);
+        n_pre++;
+        pass_tmax = std::max(pass_tmax, i + 1);
+    }
+    size_t off = 0;
+    for (int c = 0; c < n_conts; c++) {
+        for (int i = 0; i < cont_lens[c]; i++) {
+            if (cols.size() == max_cols && !flush()) return false;
+            bgk::SeqState cst{};
+            cst.n_past = n_prefix - 1 + i; cst.token = i == 0 ? prefix[n_prefix - 1] : conts[off + (size_t)(i - 1)]; cst.seq_id = 1 + c; cst.t_vis = n_prefix + i;
+            cst.pad[0] = n_prefix - 1; cst.pad[1] = 0;      // rows [0, n_prefix - 1) lie in slot 0
+            cols.push_back(cst);
+            pass_tmax = std::max(pass_tmax, n_prefix + i);
+        }
+        off += (size_t)cont_lens[c];
+    }
+    return flush();
+}
+
+static int score_continuations_once(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *conts, const int32_t *cont_lens,
+                                    int32_t n_conts, float *logprob_out, int32_t *argmax_out, float *logit_out, double *seconds_out) {
+    XpCallScope xp_scope(ctx);
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!prefix) BG_FAIL(-1, "null argument: prefix");
+    if (!conts) BG_FAIL(-1, "null argument: conts");
+    if (!cont_lens) BG_FAIL(-1, "null argument: cont_lens");
+    if (!logprob_out) BG_FAIL(-1, "null argument: logprob_out");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (n_prefix < 1) BG_FAIL(-1, "n_prefix must be >= 1 (got %d)", n_prefix);
+    if (n_conts < 1 || n_conts > 511) BG_FAIL(-1, "n_conts must be in [1, 511] (got %d)", n_conts);   // slot 0 is the prefix; each continuation owns a full F32 KV cache
+    const auto &hp = ctx->hp;
+    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
+        BG_FAIL(-1, "shared-prefix scoring needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (n_prefix > hp.n_positions) BG_FAIL(-1, "n_prefix (%d) exceeds n_positions (%d)", n_prefix, hp.n_positions);
+    for (int i = 0; i < n_prefix; i++)
+        if (prefix[i] < 0 || prefix[i] >= hp.n_vocab) BG_FAIL(-1, "token id %d (prefix, position %d) out of range [0, %d)", prefix[i], i, hp.n_vocab);
+    size_t total = 0;
+    for (int c = 0; c < n_conts; c++) {
+        const int len = cont_lens[c];
+        if (len < 1) BG_FAIL(-1, "empty continuation (continuation %d)", c);
+        if (len > hp.n_positions - n_prefix)
+            BG_FAIL(-1, "n_prefix (%d) + cont_lens[%d] (%d) exceeds n_positions (%d)", n_prefix, c, len, hp.n_positions);
+        for (int i = 0; i < len; i++) {
+            const int32_t t = conts[total + (size_t)i];
+            if (t < 0 || t >= hp.n_vocab) BG_FAIL(-1, "token id %d (continuation %d, position %d) out of range [0, %d)", t, c, i, hp.n_vocab);
+        }
+        total += (size_t)len;
+    }
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
+    // the prefix and every continuation in the per-sequence caches (bk / bv): the context's own cache, position and logits row stay as they are
+    const size_t max_cols = (size_t)std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
+    const int n_shared = n_prefix - 1;
+    if (!ensure_seq_caches(ctx, n_conts + 1)) {
+        (void)hipGetLastError();
+        BG_FAIL(-2, "out of device memory: the %zu-byte K / V caches of %d continuations and their prefix could not be allocated",
+                (size_t)2 * 4 * hp.n_layer * hp.n_positions * hp.d_model * (size_t)(n_conts + 1), n_conts);
+    }
+    if ((long)std::min(max_cols, total + (size_t)n_shared) >= MFMA_MIN_PASS_COLS && !ensure_tile_images(ctx)) return -2;
+    if (!ensure_logits_rows(ctx, std::min(max_cols, total)) || !score_setup(ctx, conts, cont_lens, n_conts, conts, total)) return -2;
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!pack_continuation_passes(ctx, prefix, n_prefix, conts, cont_lens, n_conts, [&](int n_cols, int t_max, size_t flat0, int n_pre) {
+            return enqueue_forward(ctx, n_cols, true, t_max, true, ctx->cols, true, nullptr, true, n_pre) &&
+                   (n_pre == n_cols || enqueue_logprob(ctx, n_cols - n_pre, flat0, total));
+        }))
+        return -2;
+    const int rc = score_finish(ctx, total, logprob_out, argmax_out, logit_out);
+    if (rc == 0 && seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int biogpt_hip_score_continuations(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *conts, const int32_t *cont_lens,
+                                   int32_t n_conts, float *logprob_out, int32_t *argmax_out, float *logit_out, double *seconds_out) {
+    int rc = score_continuations_once(ctx, prefix, n_prefix, conts, cont_lens, n_conts, logprob_out, argmax_out, logit_out, seconds_out);
+    if (rc < 0 && xpipe_retry(ctx, 0))
+        rc = score_continuations_once(ctx, prefix, n_prefix, conts, cont_lens, n_conts, logprob_out, argmax_out, logit_out, seconds_out);
     return rc;
 }
 

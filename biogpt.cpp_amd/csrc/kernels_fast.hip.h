@@ -421,7 +421,13 @@ __device__ __forceinline__ void store_head_output(const AttnParams &p, int i, in
     }
 }
 
-template <int KP, bool VPRE>
+// SHARED (columns of biogpt_hip_score_continuations): key / value row j of a column lies in ANOTHER slot when j < n_shared -- the prefix
+// that all continuations of a call have in common, evaluated once and read where it lies -- and in the column's own slot otherwise.
+// n_shared and the shared slot travel per column (SeqState::pad[0] / pad[1]; 0 rows: none).  Only the row ADDRESSES differ: each load
+// picks one of two bases (a select on the pointer, no branch around the load); the rows of either slot are one contiguous run of the
+// head-major cache.  Scores, mask, table exponent, sums and PV slices are the code below for both, so a column's result is bit for bit
+// what the plain instantiation computes from the same t_vis rows in one slot.
+template <int KP, bool VPRE, bool SHARED = false>
 __global__ __launch_bounds__(1024) void attn_fast_kernel(const AttnParams p) {
     constexpr int DK = 64;
     __shared__ float S[KP * 256];
@@ -456,6 +462,11 @@ __global__ __launch_bounds__(1024) void attn_fast_kernel(const AttnParams p) {
     const float4 *kbase = reinterpret_cast<const float4 *>(p.kcache + seq_off + (size_t)h * p.P * DK) + ksub;   // [H][P][dk]
     const float *__restrict__ vbase = p.vcache + seq_off + (size_t)h * p.P * DK + d;
     const float4 *qp = reinterpret_cast<const float4 *>(p.q + (size_t)i * D + (size_t)h * DK) + ksub;
+    // SHARED: the same two bases in the shared slot, and the first row that is the column's own
+    const int n_shared = SHARED ? p.seq[i].pad[0] : 0;
+    const size_t shr_off = SHARED ? (size_t)p.seq[i].pad[1] * p.kv_seq_stride : 0;
+    const float4 *kshr = SHARED ? reinterpret_cast<const float4 *>(p.kcache + shr_off + (size_t)h * p.P * DK) + ksub : kbase;
+    const float *__restrict__ vshr = SHARED ? p.vcache + shr_off + (size_t)h * p.P * DK + d : vbase;
 
     // ---- entry: all loads ----
     const int n_past = p.seq ? p.seq[i].n_past : p.st->n_past;
@@ -465,7 +476,7 @@ __global__ __launch_bounds__(1024) void attn_fast_kernel(const AttnParams p) {
         const int j = ps * kpp + kidx;
         if (j < t_cap && !AT_DBG(1)) {
 #pragma unroll
-            for (int m = 0; m < 4; m++) kr[ps][m] = kbase[(size_t)j * (DK / 4) + 4 * m];
+            for (int m = 0; m < 4; m++) kr[ps][m] = ((SHARED && j < n_shared) ? kshr : kbase)[(size_t)j * (DK / 4) + 4 * m];
         }
     }
     float4 qv[4];
@@ -476,7 +487,7 @@ __global__ __launch_bounds__(1024) void attn_fast_kernel(const AttnParams p) {
 #pragma unroll
         for (int k = 0; k < 16; k++) {
             const int j = sl + nsl * k;
-            if (j < t_cap && !AT_DBG(2)) vr[k] = vbase[(size_t)j * DK];
+            if (j < t_cap && !AT_DBG(2)) vr[k] = ((SHARED && j < n_shared) ? vshr : vbase)[(size_t)j * DK];
         }
     }
     AT_STAMP(1);
@@ -542,7 +553,8 @@ __global__ __launch_bounds__(1024) void attn_fast_kernel(const AttnParams p) {
         for (int j = sl; j < T; j += nsl * 8) {
             float v8[8];
 #pragma unroll
-            for (int k = 0; k < 8; k++) v8[k] = (j + nsl * k < t_cap) ? vbase[(size_t)(j + nsl * k) * DK] : 0.0f;
+            for (int k = 0; k < 8; k++)
+                v8[k] = (j + nsl * k < t_cap) ? ((SHARED && j + nsl * k < n_shared) ? vshr : vbase)[(size_t)(j + nsl * k) * DK] : 0.0f;
 #pragma unroll
             for (int k = 0; k < 8; k += 2) {
                 if (j + nsl * k < T) a0 += (double)__fmul_rn(v8[k], __fmul_rn(S[j + nsl * k], inv));

@@ -352,6 +352,22 @@ int biogpt_hip_score(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_token
 int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
                            float *logprob_out, int32_t *argmax_out, float *logit_out);
 
+/* Many continuations of ONE prefix (multiple choice, label ranking, reranking hypotheses of one prompt): conts = the n_conts continuations
+ * concatenated, cont_lens[n_conts] their lengths; the outputs use the flat layout of conts.  For continuation c and i in [0, cont_lens[c]):
+ * logprob_out = log P(cont_c[i] | prefix, cont_c[0..i)), logit_out = that token's logit, argmax_out = the row's arg-max -- rows
+ * n_prefix - 1 + i of biogpt_hip_score(prefix + cont_c, 0), bit for bit.  The prefix rows [0, n_prefix - 1) are evaluated ONCE, without an
+ * lm_head, into a K / V cache slot that every continuation's attention reads in place; no K / V row is copied.  Every continuation
+ * re-evaluates the last prefix token in a slot of its own and its last token is never a column: n_prefix - 1 + sum(cont_lens) columns
+ * instead of the sum(n_prefix + cont_lens[c]) of biogpt_hip_score_batch on the concatenations.  The context's own cache, position and
+ * logits row are left alone.  Needs the BioGPT-base fast chain (block-quantized weights), like biogpt_hip_score_batch.  Argument errors
+ * (null pointers, n_prefix < 1, n_conts outside [1, 511], an empty continuation, a token id out of range, n_prefix + cont_lens[c] >
+ * n_positions, a model without the fast chain) return -1 before any HIP call and name the field; a failed allocation returns -2 and names
+ * the size.  argmax_out and logit_out may be NULL.  seconds_out (may be NULL): the passes and the copy back.  Returns 0 or < 0. */
+int biogpt_hip_score_continuations(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix,
+                                   const int32_t *conts /* concatenated */, const int32_t *cont_lens, int32_t n_conts,
+                                   float *logprob_out, int32_t *argmax_out /* may be NULL */, float *logit_out /* may be NULL */,
+                                   double *seconds_out /* may be NULL */);
+
 /* ---- hidden states, pooled embeddings, classification heads (no counterpart in the reference) ----
  * The activations in front of the lm_head, from the causal passes of biogpt_hip_score without the lm_head and the log-softmax.
  *
