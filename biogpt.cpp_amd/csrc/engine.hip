@@ -218,6 +218,13 @@ struct EngineOptions {
 namespace {
 }  // namespace
 
+// The captured steps of one mode of column generation: [12 * (rules active) + 6 * (steps as column-per-XCD launches) + context bucket], valid for
+// the call shape (key_a, key_b) they were captured for -- sequences, or groups and beams
+struct ColumnGraphs {
+    hipGraphExec_t exec[24] = {};
+    int key_a = 0, key_b = 0;
+};
+
 // ---- context ----------------------------------------------------------------------------------------
 struct biogpt_hip_ctx {
     EngineOptions opt{};
@@ -273,34 +280,18 @@ struct biogpt_hip_ctx {
     std::set<const void *> lds_attr_done;     // kernels whose > 64 KB dynamic-LDS opt-in attribute is set on this device
     unsigned long long *tstamp = nullptr;     // profiling only (opt.dbg & 32)
     int launch_parity = 0;
-    hipGraphExec_t graph_batch[12] = {};  // [6 * (steps as column-per-XCD launches) + context bucket], captured for graph_batch_n sequences
-    int graph_batch_n = 0;
-    // beam search (biogpt_hip_generate_beam, kernels_beam.hip.h): its captured steps (layout of graph_batch, for graph_beam_n beams), the device
-    // state + pool ids (BeamCtl, then [BEAM_MAX][n_positions] words), the candidates, and the pinned done words of two groups of steps.
-    // Steps with generation rules are graphs of their own: [12 * (rules active) + 6 * (column-per-XCD) + bucket]
-    hipGraphExec_t graph_beam[24] = {};
-    int graph_beam_n = 0;
-    bgk::BeamCtl *beam_ctl = nullptr;
-    bgk::BeamCand *beam_cand = nullptr;
-    int32_t *beam_done_host = nullptr;
-    hipEvent_t beam_ev[2] = {};
-    // sampled generation (biogpt_hip_generate_sample, kernels_sample.hip.h): its captured steps (layout of graph_batch, for graph_sample_n sequences), the call's
-    // parameters + one generator state per sequence (SampleCtl, then sample_cap SampleSeq), and the pinned live counts of two groups of steps
-    // (graphs indexed as graph_beam)
-    hipGraphExec_t graph_sample[24] = {};
-    int graph_sample_n = 0;
+    // column generation (greedy batch, sampling, beam search; the driver stands before generate_greedy_batch_once): the captured steps of each mode,
+    // and the pinned word pair + event pair through which the host reads a mode's count of unfinished sequences / searches between groups of steps
+    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam;
+    int32_t *live_host = nullptr;
+    hipEvent_t live_ev[2] = {};
+    // sampled generation (biogpt_hip_generate_sample, kernels_sample.hip.h): the call's parameters + one generator state per sequence (SampleCtl, then
+    // sample_cap SampleSeq)
     bgk::SampleCtl *sample_ctl = nullptr;
     int sample_cap = 0;
-    int32_t *sample_live_host = nullptr;
-    hipEvent_t sample_ev[2] = {};
-    // beam search over a batch of prompts (biogpt_hip_generate_beam_batch): its captured steps (indexed as graph_beam, for graph_bbatch_g groups of
-    // graph_bbatch_b beams), one block of device state allocated once at its largest (bbatch_* offsets below: captured steps keep their pointers),
-    // and the pinned counts of unfinished groups of two groups of steps
-    hipGraphExec_t graph_bbatch[24] = {};
-    int graph_bbatch_g = 0, graph_bbatch_b = 0;
+    // beam search (biogpt_hip_generate_beam_batch, kernels_beam.hip.h): one block of device state allocated once at its largest (bbatch_* offsets below:
+    // captured steps keep their pointers)
     uint8_t *bbatch_buf = nullptr;
-    int32_t *bbatch_live_host = nullptr;
-    hipEvent_t bbatch_ev[2] = {};
     // generation rules (kernels_rules.hip.h): RulesCtl, RULES_ROWS RulesRow, then the call's prompts (one copy per prompt); allocated once, at its
     // largest, so that captured steps keep their pointers
     uint8_t *rules_buf = nullptr;
@@ -325,7 +316,7 @@ struct biogpt_hip_ctx {
     int state_n_past = 0, state_chunk = 0; // what the last upload_state put into the device state
     int64_t xc_launches = 0;               // evals that went through the chunk launch (biogpt_hip_chunk_launches)
     int32_t gen_launch_tokens[16] = {0}; int gen_launches = 0;   // the last biogpt_hip_generate_greedy: tokens of each multi-token pipelined launch (biogpt_hip_generate_launches)
-    int xc_batch = 0;                      // biogpt_hip_generate_greedy_batch with 2 .. 8 sequences holds the device's pipeline slot: its decode steps run as column-per-XCD launches (streams mode)
+    int xc_batch = 0;                      // a column generation call with 2 .. 8 columns holds the device's pipeline slot (choose_column_path): its decode steps run as column-per-XCD launches (streams mode)
     uint32_t *xp_ctl = nullptr;
     bgk::xp_u64 *xp_samp = nullptr;        // arg-max partials handed from token t to token t + 1 inside a multi-token launch
     uint32_t *xp_err_host = nullptr;
@@ -374,6 +365,14 @@ static bool resident_stop(biogpt_hip_ctx *c);   // ends a resident single-token 
 // An entry point that enqueues work of its own (generate_*, eval_all, eval_prompt, the bench calls) makes the row of an EARLIER replayed single-token eval history: its lineage
 // watch must not fire on a later biogpt_hip_read_logits (it would re-evaluate the old token at the old position over this call's K / V rows).  ADVICE r5.
 static inline void disarm_lineage(biogpt_hip_ctx *c) { c->dev_stamp_expect = 0; c->stamp_expect = 0; }
+
+static void drop_graphs(ColumnGraphs &gs) {
+    for (auto &g : gs.exec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+}
+// Captured column steps hold the pointers of seq / bk / bv / logits_all and launch shapes chosen from the options: whatever replaces one of those drops them all
+static void drop_column_graphs(biogpt_hip_ctx *c) {
+    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam}) drop_graphs(*gs);
+}
 
 namespace {
 
@@ -1340,6 +1339,8 @@ bool alloc_runtime(biogpt_hip_ctx *c) {
     HIP_TRY(false, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIP_TRY(false, hipEventCreate(&c->ev0));
     HIP_TRY(false, hipEventCreate(&c->ev1));
+    HIP_TRY(false, hipHostMalloc(&c->live_host, 2 * sizeof(int32_t)));
+    for (auto &e : c->live_ev) HIP_TRY(false, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return true;
 }
 
@@ -1481,23 +1482,16 @@ void destroy(biogpt_hip_ctx *c) {
         fprintf(stderr, "resident evals: %ld calls, %.2f us waiting for the completion words, %.2f us between a return and the next post\n", c->res_calls, c->res_t_wait / c->res_calls * 1e6, c->res_t_call / c->res_calls * 1e6);
     for (auto &pl : c->graph_step) for (auto &row : pl) for (auto &g : row) if (g) (void)hipGraphExecDestroy(g);
     for (auto &pl : c->graph_eval) for (auto &f : pl) for (auto &row : f) for (auto &g : row) if (g) (void)hipGraphExecDestroy(g);
-    for (auto &g : c->graph_batch) if (g) (void)hipGraphExecDestroy(g);
-    for (auto &g : c->graph_beam) if (g) (void)hipGraphExecDestroy(g);
-    for (auto &e : c->beam_ev) if (e) (void)hipEventDestroy(e);
-    if (c->beam_done_host) (void)hipHostFree(c->beam_done_host);
-    for (auto &g : c->graph_sample) if (g) (void)hipGraphExecDestroy(g);
-    for (auto &e : c->sample_ev) if (e) (void)hipEventDestroy(e);
-    if (c->sample_live_host) (void)hipHostFree(c->sample_live_host);
-    for (auto &g : c->graph_bbatch) if (g) (void)hipGraphExecDestroy(g);
-    for (auto &e : c->bbatch_ev) if (e) (void)hipEventDestroy(e);
-    if (c->bbatch_live_host) (void)hipHostFree(c->bbatch_live_host);
+    drop_column_graphs(c);
+    for (auto &e : c->live_ev) if (e) (void)hipEventDestroy(e);
+    if (c->live_host) (void)hipHostFree(c->live_host);
     xpipe_release(c);
     if (c->topk_host) (void)hipHostFree(c->topk_host);
     if (c->mbox_host) (void)hipHostFree(c->mbox_host);
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->beam_ctl, (void *)c->beam_cand, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->bbatch_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->bbatch_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1671,13 +1665,7 @@ int biogpt_hip_refresh_options(biogpt_hip_ctx *ctx) {
     // captured graphs bake launch shapes chosen from the options
     for (auto &pl : ctx->graph_step) for (auto &row : pl) for (auto &g : row) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     for (auto &pl : ctx->graph_eval) for (auto &f : pl) for (auto &row : f) for (auto &g : row) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    ctx->graph_batch_n = 0;
-    for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    ctx->graph_beam_n = 0;
-    for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    ctx->graph_sample_n = 0;
-    for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    drop_column_graphs(ctx);
     // the pipelined path is rebuilt from the new options (GELU slice, fault hook, long-context buffers) -- which also re-arms a context that had abandoned the
     // path after a disturbed launch: an explicit call, not an automatic cool-down
     HIP_TRY(-2, hipSetDevice(ctx->device));
@@ -2040,14 +2028,7 @@ int biogpt_hip_eval_all(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, i
         ctx->logits_all = nullptr;
         HIP_TRY(-2, hipMalloc(&ctx->logits_all, (size_t)n * ctx->hp.n_vocab * 4));
         ctx->logits_all_rows = (size_t)n;
-        // the captured batched-decode graphs hold the old logits_all pointer
-        for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        ctx->graph_batch_n = 0;
-        for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        ctx->graph_beam_n = 0;
-        for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        ctx->graph_sample_n = 0;
-        for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        drop_column_graphs(ctx);
     }
     if (!upload_state(ctx, tokens, n, n_past)) return -2;
     if (!enqueue_forward(ctx, n, true, n_past + n)) return -2;
@@ -2187,6 +2168,12 @@ static bool xpipe_retry(biogpt_hip_ctx *ctx, int n_past) {
     }
     return true;
 }
+// once(): the call; a negative result after a tripped pipeline is repeated once
+static int with_xpipe_retry(biogpt_hip_ctx *ctx, int n_past, const std::function<int()> &once) {
+    int rc = once();
+    if (rc < 0 && xpipe_retry(ctx, n_past)) rc = once();
+    return rc;
+}
 int biogpt_hip_eval_inplace(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, const float **row_out) {
     if (!row_out) BG_FAIL(-1, "null row pointer");
     int rc = eval_once(ctx, tokens, n, n_past, nullptr);
@@ -2225,15 +2212,11 @@ int biogpt_hip_eval(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32
     return rc;
 }
 int biogpt_hip_eval_topk(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, int32_t k, float *vals_out, int32_t *ids_out) {
-    int rc = eval_topk_once(ctx, tokens, n, n_past, k, vals_out, ids_out);
-    if (rc < 0 && xpipe_retry(ctx, n_past)) rc = eval_topk_once(ctx, tokens, n, n_past, k, vals_out, ids_out);
-    return rc;
+    return with_xpipe_retry(ctx, n_past, [&] { return eval_topk_once(ctx, tokens, n, n_past, k, vals_out, ids_out); });
 }
 int biogpt_hip_generate_greedy(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_predict, int32_t *out_ids,
                                double *seconds_out) {
-    int rc = generate_greedy_once(ctx, prompt, n_prompt, n_batch, n_predict, out_ids, seconds_out);
-    if (rc < 0 && xpipe_retry(ctx, 0)) rc = generate_greedy_once(ctx, prompt, n_prompt, n_batch, n_predict, out_ids, seconds_out);
-    return rc;
+    return with_xpipe_retry(ctx, 0, [&] { return generate_greedy_once(ctx, prompt, n_prompt, n_batch, n_predict, out_ids, seconds_out); });
 }
 
 static int hp_cols(const biogpt_hip_ctx *c) { return c->hp.n_positions; }   // scratch is sized [n_positions] columns
@@ -2249,10 +2232,18 @@ static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
     HIP_TRY(false, hipMalloc(&ctx->seq, sizeof(bgk::SeqState) * n_seqs));
     HIP_TRY(false, hipMalloc(&ctx->seq_gen, (size_t)n_seqs * ctx->hp.n_positions * 4));
     ctx->batch_cap = n_seqs;
-    for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    drop_column_graphs(ctx);
+    return true;
+}
+
+// logits_all holds at least `rows` rows; a new buffer drops the captured column steps (they hold the old pointer)
+static bool ensure_logits_rows(biogpt_hip_ctx *c, size_t rows) {
+    if (rows <= c->logits_all_rows) return true;
+    if (c->logits_all) (void)hipFree(c->logits_all);
+    c->logits_all = nullptr; c->logits_all_rows = 0;
+    HIP_TRY(false, hipMalloc(&c->logits_all, rows * c->hp.n_vocab * 4));
+    c->logits_all_rows = rows;
+    drop_column_graphs(c);
     return true;
 }
 
@@ -2306,103 +2297,168 @@ static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const i
     return flush();
 }
 
+// ---- column generation: the host side that greedy batch, sampling and beam search share ----------------------------------------------
+// Such a call generates with one column (and one K / V cache slot) per sequence.  It reads: checks, the mode's device state, a `step` lambda, then
+// capture_column_steps, [t0] ingest_column_prompts, run_column_steps [t1], read-back.  step(t_max) enqueues one step of the mode: the forward pass of all
+// columns with t_max visible keys, then the mode's selection kernels, which leave every column's next token and position in ctx->seq.
+using ColumnStep = std::function<bool(int)>;
+
+// ends the call's hold on the column-per-XCD launches (choose_column_path) when the call returns
+struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } };
+
+// n prompts, concatenated: none empty, every token valid; the longest and the sum of their lengths
+static bool check_prompts(const biogpt_hip_ctx *c, const int32_t *prompts, const int32_t *lens, int n, const char *unit, int *max_len, long *total) {
+    *max_len = 0; *total = 0;
+    for (int p = 0; p < n; p++) {
+        if (lens[p] < 1) BG_FAIL(false, "empty prompt (%s %d)", unit, p);
+        if (!check_eval_args(c, prompts + *total, lens[p], 0)) return false;
+        *max_len = std::max(*max_len, lens[p]);
+        *total += lens[p];
+    }
+    return true;
+}
+
+static bool check_fast_chain(const biogpt_hip_ctx *c, const char *what) {
+    const auto &hp = c->hp;
+    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
+        BG_FAIL(false, "%s needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)", what);
+    return true;
+}
+
+// the device, the caches and the logits rows of n_seqs columns; `total` prompt tokens go through the prompt pass
+static bool begin_column_call(biogpt_hip_ctx *ctx, int n_seqs, long total) {
+    HIP_TRY(false, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return false;
+    disarm_lineage(ctx);
+    if (!ensure_seq_caches(ctx, n_seqs)) return false;
+    // matrix-core chain: decode steps have n_seqs columns, the prompt pass all prompt tokens; build the tiled weights before any graph capture
+    if (std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return false;
+    return ensure_logits_rows(ctx, (size_t)n_seqs);
+}
+
+// the captured steps serve calls of one shape: another shape drops them
+static void column_graphs_for(ColumnGraphs &gs, int a, int b) {
+    if (gs.key_a == a && gs.key_b == b) return;
+    drop_graphs(gs);
+    gs.key_a = a; gs.key_b = b;
+}
+
+// Column p * per_prompt + j starts at prompt p's LAST token (the prompt pass leaves it to the first step), in the cache slot of its own index
+static bool upload_column_starts(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *lens, int n_prompts, int per_prompt) {
+    std::vector<bgk::SeqState> hs((size_t)n_prompts * per_prompt);
+    size_t o = 0;
+    for (int p = 0; p < n_prompts; p++) {
+        o += (size_t)lens[p];
+        for (int j = 0; j < per_prompt; j++) {
+            bgk::SeqState &st = hs[(size_t)p * per_prompt + j];
+            st = bgk::SeqState{};
+            st.n_past = lens[p] - 1; st.token = prompts[o - 1]; st.seq_id = p * per_prompt + j;
+        }
+    }
+    HIP_TRY(false, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * hs.size(), hipMemcpyHostToDevice));
+    return true;
+}
+
+// 2 .. 8 columns: the steps as column-per-XCD launches while this call holds the device's pipeline slot.  Decided ONCE per call, before any capture: a
+// graph is replayed only in the state it was captured for.  Returns the choice (0 | 1), which is also ctx->xc_batch until the call's XcBatchScope ends.
+static int choose_column_path(biogpt_hip_ctx *ctx, int n_seqs, int max_len) {
+    ctx->xc_batch = (n_seqs >= 2 && n_seqs <= 8 && max_len + 1 <= 256 && xcols_prepare(ctx, n_seqs, std::min(256, max_len + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
+    return ctx->xc_batch;
+}
+
+// Captures `step` for the context buckets of steps 2 .. n_predict (t_max = max_len + 1 .. max_len + n_predict - 1: the ones run_column_steps replays) into
+// graphs.exec[gset + bucket], where they are not there yet.  *use_graph: whether the steps are replayed at all.
+static bool capture_column_steps(biogpt_hip_ctx *ctx, ColumnGraphs &graphs, int gset, int max_len, int n_predict, const ColumnStep &step, bool *use_graph) {
+    *use_graph = ctx->opt.no_graph == 0 && (ctx->xc_batch != 0 || plain_graph_begin(ctx));      // (a captured five-launch step is not replayed beside another context's persistent launch)
+    if (*use_graph && n_predict > 1) {
+        for (int b = graph_bucket(max_len + 1); b <= graph_bucket(max_len + n_predict - 1); b++) {
+            if (graphs.exec[gset + b]) continue;
+            hipGraph_t g = nullptr;
+            HIP_TRY(false, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+            const bool ok = step(bucket_tmax(ctx, b));
+            hipError_t e = hipStreamEndCapture(ctx->stream, &g);
+            if (!ok) { if (g) (void)hipGraphDestroy(g); return false; }
+            HIP_TRY(false, e);
+            HIP_TRY(false, hipGraphInstantiate(&graphs.exec[gset + b], g, nullptr, nullptr, 0));
+            (void)hipGraphDestroy(g);
+        }
+    }
+    HIP_TRY(false, hipStreamSynchronize(ctx->stream));
+    return true;
+}
+
+// Prompt ingestion for ALL prompts together (main.cpp:129-137 per prompt), packed into common passes (pack_column_passes): prompt p fills the cache slot of
+// its first column, kv_share_kernel copies its rows to its other per_prompt - 1 slots.  The pass only has to fill the K / V caches: the first step
+// re-evaluates each prompt's LAST token (same K / V row, same visible keys as its chunk gave it).
+static bool ingest_column_prompts(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *lens, int n_prompts, int n_batch, int per_prompt) {
+    const auto &hp = ctx->hp;
+    if (!pack_column_passes(ctx, prompts, lens, n_prompts, n_batch,
+                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }, per_prompt))
+        return false;
+    if (per_prompt > 1) {
+        hipLaunchKernelGGL(bgk::kv_share_kernel, dim3(hp.n_layer * hp.n_head, n_prompts * per_prompt, 2), dim3(256), 0, ctx->stream, ctx->seq, per_prompt, ctx->bk, ctx->bv,
+                           (int64_t)hp.n_layer * hp.n_positions * hp.d_model, hp.n_positions, hp.d_model / hp.n_head);
+        HIP_TRY(false, hipGetLastError());
+    }
+    return true;
+}
+
+// Step 1 eagerly (the last prompt token of every column, t_max = max_len), then steps 2 .. n_predict (t_max = max_len + 1 ..) replayed or eager, enqueued in
+// groups of 8.  live_dev (or null): a device word that holds how many sequences / searches still run.  It is copied to one of two pinned words after each
+// group, and once the group BEFORE the one just enqueued reports none, nothing more is enqueued (one group stays in flight; steps after the end change nothing).
+static bool run_column_steps(biogpt_hip_ctx *ctx, const ColumnGraphs &graphs, int gset, bool use_graph, int max_len, int n_predict, const ColumnStep &step,
+                             const int32_t *live_dev) {
+    if (!step(max_len)) return false;
+    for (int k = 1, grp = 0; k < n_predict; grp++) {
+        for (const int end = std::min(n_predict - 1, k + 7); k <= end; k++) {
+            const int t_max = max_len + k;
+            if (use_graph) HIP_TRY(false, hipGraphLaunch(graphs.exec[gset + graph_bucket(t_max)], ctx->stream));
+            else if (!step(t_max)) return false;
+        }
+        if (!live_dev) continue;
+        HIP_TRY(false, hipMemcpyAsync(ctx->live_host + (grp & 1), live_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(false, hipEventRecord(ctx->live_ev[grp & 1], ctx->stream));
+        if (grp > 0) {
+            HIP_TRY(false, hipEventSynchronize(ctx->live_ev[(grp - 1) & 1]));
+            if (ctx->live_host[(grp - 1) & 1] <= 0) break;
+        }
+    }
+    return true;
+}
+
 static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_seqs,
                                       int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out) {
     XpCallScope xp_scope(ctx);
-    struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } } xc_scope{ctx};
+    XcBatchScope xc_scope{ctx};
     clear_error();
     if (!ctx || !prompts || !prompt_lens || !out_ids) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");   // activation buffers hold n_positions >= 512 columns; each sequence owns a full F32 KV cache
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_seqs (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
     if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
-    const auto &hp = ctx->hp;
-    const int P = hp.n_positions, V = hp.n_vocab;
-    int max_len = 0;
-    {
-        size_t off = 0;
-        for (int s = 0; s < n_seqs; s++) {
-            if (prompt_lens[s] < 1) BG_FAIL(-1, "empty prompt (sequence %d)", s);
-            if (!check_eval_args(ctx, prompts + off, prompt_lens[s], 0)) return -1;
-            max_len = std::max(max_len, prompt_lens[s]);
-            off += (size_t)prompt_lens[s];
-        }
-    }
+    const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
+    int max_len;
+    long total;
+    if (!check_prompts(ctx, prompts, prompt_lens, n_seqs, "sequence", &max_len, &total)) return -1;
     n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
     if (n_predict <= 0) return 0;
-    HIP_TRY(-2, hipSetDevice(ctx->device));
-    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    if (!ensure_seq_caches(ctx, n_seqs)) return -2;
-    {   // matrix-core chain: decode steps have n_seqs columns, the prompt pass all prompt tokens; build the tiled weights before any graph capture
-        long total = 0;
-        for (int s = 0; s < n_seqs; s++) total += prompt_lens[s];
-        if (std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return -2;
-    }
-    if ((size_t)n_seqs > ctx->logits_all_rows) {
-        if (ctx->logits_all) (void)hipFree(ctx->logits_all);
-        ctx->logits_all = nullptr;
-        HIP_TRY(-2, hipMalloc(&ctx->logits_all, (size_t)n_seqs * V * 4));
-        ctx->logits_all_rows = (size_t)n_seqs;
-        for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    }
-    if (ctx->graph_batch_n != n_seqs) {
-        for (auto &g : ctx->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        ctx->graph_batch_n = n_seqs;
-    }
-    std::vector<bgk::SeqState> hs((size_t)n_seqs);
-    for (int s = 0; s < n_seqs; s++) {   // the prompt pass below leaves the LAST prompt token to the first decode step
-        hs[(size_t)s] = bgk::SeqState{};
-        hs[(size_t)s].n_past = prompt_lens[s] - 1;
-        hs[(size_t)s].seq_id = s;
-    }
-    {
-        size_t o = 0;
-        for (int s = 0; s < n_seqs; s++) { o += (size_t)prompt_lens[s]; hs[(size_t)s].token = prompts[o - 1]; }
-    }
-    HIP_TRY(-2, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * n_seqs, hipMemcpyHostToDevice));
+    if (!begin_column_call(ctx, n_seqs, total)) return -2;
+    column_graphs_for(ctx->graphs_greedy, n_seqs, 0);
+    if (!upload_column_starts(ctx, prompts, prompt_lens, n_seqs, 1)) return -2;
 
-    // 2 .. 8 sequences: the decode steps as column-per-XCD launches while this call holds the device's pipeline slot (decided ONCE, before any capture: a graph is
-    // replayed only in the state it was captured for -- graph_batch[6 * pl + bucket])
-    ctx->xc_batch = (n_seqs >= 2 && n_seqs <= 8 && max_len + 1 <= 256 && xcols_prepare(ctx, n_seqs, std::min(256, max_len + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
-    const int pl = ctx->xc_batch;
-    auto batch_step = [&](int t_max) -> bool {
+    const ColumnStep step = [&](int t_max) -> bool {
         if (!enqueue_forward(ctx, n_seqs, false, t_max, true)) return false;
         hipLaunchKernelGGL(bgk::argmax_rows_kernel, dim3(n_seqs), dim3(1024), 0, ctx->stream, ctx->logits_all, V, V, ctx->seq, 0, ctx->seq_gen, P, 1);
         HIP_TRY(false, hipGetLastError());
         return true;
     };
-    const bool use_graph = ctx->opt.no_graph == 0 && (pl != 0 || plain_graph_begin(ctx));      // (a captured five-launch step is not replayed beside another context's persistent launch)
-    if (use_graph) {
-        for (int b = graph_bucket(max_len + 1); b <= graph_bucket(std::max(1, max_len + n_predict - 1)); b++) {
-            if (ctx->graph_batch[6 * pl + b]) continue;
-            hipGraph_t g = nullptr;
-            HIP_TRY(-2, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-            const bool ok = batch_step(bucket_tmax(ctx, b));
-            hipError_t e = hipStreamEndCapture(ctx->stream, &g);
-            if (!ok) { if (g) (void)hipGraphDestroy(g); return -2; }
-            HIP_TRY(-2, e);
-            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_batch[6 * pl + b], g, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(g);
-        }
-    }
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const int gset = 6 * choose_column_path(ctx, n_seqs, max_len);
+    bool use_graph;
+    if (!capture_column_steps(ctx, ctx->graphs_greedy, gset, max_len, n_predict, step, &use_graph)) return -2;
 
     const auto t0 = std::chrono::steady_clock::now();
-    // Prompt ingestion for ALL sequences together (main.cpp:129-137 per sequence), packed into common passes (pack_column_passes).
-    // The pass only has to fill the KV caches: the first decode step below re-evaluates each sequence's LAST prompt token (same K/V
-    // row, same visible keys as its chunk gave it) and its arg-max is the first sampled token.
-    if (!pack_column_passes(ctx, prompts, prompt_lens, n_seqs, n_batch,
-                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }))
-        return -2;
-    if (!batch_step(max_len)) return -2;   // last prompt token of every sequence -> first sampled token, n_past = prompt length
-    for (int k = 1; k < n_predict; k++) {  // batched decode: one column per sequence
-        const int t_max = max_len + k;
-        if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_batch[6 * pl + graph_bucket(t_max)], ctx->stream));
-        else if (!batch_step(t_max)) return -2;
-    }
+    if (!ingest_column_prompts(ctx, prompts, prompt_lens, n_seqs, n_batch, 1)) return -2;
+    if (!run_column_steps(ctx, ctx->graphs_greedy, gset, use_graph, max_len, n_predict, step, nullptr)) return -2;   // every step's arg-max is the next token
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
     const auto t1 = std::chrono::steady_clock::now();
     if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
@@ -2414,9 +2470,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
 }
 int biogpt_hip_generate_greedy_batch(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_seqs,
                                      int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out) {
-    int rc = generate_greedy_batch_once(ctx, prompts, prompt_lens, n_seqs, n_batch, n_predict, out_ids, seconds_out);
-    if (rc < 0 && xpipe_retry(ctx, 0)) rc = generate_greedy_batch_once(ctx, prompts, prompt_lens, n_seqs, n_batch, n_predict, out_ids, seconds_out);
-    return rc;
+    return with_xpipe_retry(ctx, 0, [&] { return generate_greedy_batch_once(ctx, prompts, prompt_lens, n_seqs, n_batch, n_predict, out_ids, seconds_out); });
 }
 
 // ---- sequence scoring: teacher-forced causal passes, the log-softmax of every row on the device (kernels_score.hip.h) ----------------
@@ -2428,23 +2482,6 @@ static bool check_targets(const biogpt_hip_ctx *c, const int32_t *targets, int n
     if (!targets) return true;
     for (int i = 0; i < n; i++)
         if (targets[i] >= c->hp.n_vocab) BG_FAIL(false, "target id %d (sequence %d, row %d) out of range: must be < %d (negative: row not scored)", targets[i], seq, i, c->hp.n_vocab);
-    return true;
-}
-
-// logits_all holds at least `rows` rows; a new buffer drops the captured batched-decode graphs (they hold the old pointer)
-static bool ensure_logits_rows(biogpt_hip_ctx *c, size_t rows) {
-    if (rows <= c->logits_all_rows) return true;
-    if (c->logits_all) (void)hipFree(c->logits_all);
-    c->logits_all = nullptr; c->logits_all_rows = 0;
-    HIP_TRY(false, hipMalloc(&c->logits_all, rows * c->hp.n_vocab * 4));
-    c->logits_all_rows = rows;
-    for (auto &g : c->graph_batch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    c->graph_batch_n = 0;
-    for (auto &g : c->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    c->graph_beam_n = 0;
-    for (auto &g : c->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    c->graph_sample_n = 0;
-    for (auto &g : c->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
     return true;
 }
 
@@ -2553,15 +2590,11 @@ static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
 
 int biogpt_hip_score(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, const int32_t *targets,
                      float *logprob_out, int32_t *argmax_out, float *logit_out) {
-    int rc = score_once(ctx, tokens, n_tokens, n_past, targets, logprob_out, argmax_out, logit_out);
-    if (rc < 0 && xpipe_retry(ctx, n_past)) rc = score_once(ctx, tokens, n_tokens, n_past, targets, logprob_out, argmax_out, logit_out);
-    return rc;
+    return with_xpipe_retry(ctx, n_past, [&] { return score_once(ctx, tokens, n_tokens, n_past, targets, logprob_out, argmax_out, logit_out); });
 }
 int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
                            float *logprob_out, int32_t *argmax_out, float *logit_out) {
-    int rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
-    if (rc < 0 && xpipe_retry(ctx, 0)) rc = score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out);
-    return rc;
+    return with_xpipe_retry(ctx, 0, [&] { return score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out); });
 }
 
 // ---- many continuations of one prefix: the prefix once, read in place by every continuation's columns ------------------------------------
@@ -2666,10 +2699,9 @@ static int score_continuations_once(biogpt_hip_ctx *ctx, const int32_t *prefix, 
 
 int biogpt_hip_score_continuations(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *conts, const int32_t *cont_lens,
                                    int32_t n_conts, float *logprob_out, int32_t *argmax_out, float *logit_out, double *seconds_out) {
-    int rc = score_continuations_once(ctx, prefix, n_prefix, conts, cont_lens, n_conts, logprob_out, argmax_out, logit_out, seconds_out);
-    if (rc < 0 && xpipe_retry(ctx, 0))
-        rc = score_continuations_once(ctx, prefix, n_prefix, conts, cont_lens, n_conts, logprob_out, argmax_out, logit_out, seconds_out);
-    return rc;
+    return with_xpipe_retry(ctx, 0, [&] {
+        return score_continuations_once(ctx, prefix, n_prefix, conts, cont_lens, n_conts, logprob_out, argmax_out, logit_out, seconds_out);
+    });
 }
 
 // ---- hidden states, pooled embeddings, classification heads: the same causal passes without the lm_head (kernels_embed.hip.h) ------------
@@ -2844,15 +2876,11 @@ static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
 }
 
 int biogpt_hip_hidden(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, float *hidden_out) {
-    int rc = hidden_once(ctx, tokens, n_tokens, n_past, hidden_out);
-    if (rc < 0 && xpipe_retry(ctx, n_past)) rc = hidden_once(ctx, tokens, n_tokens, n_past, hidden_out);
-    return rc;
+    return with_xpipe_retry(ctx, n_past, [&] { return hidden_once(ctx, tokens, n_tokens, n_past, hidden_out); });
 }
 int biogpt_hip_embed_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const biogpt_hip_embed_opts *opts,
                            float *out, double *seconds_out) {
-    int rc = embed_batch_once(ctx, seqs, lens, n_seqs, opts, out, seconds_out);
-    if (rc < 0 && xpipe_retry(ctx, 0)) rc = embed_batch_once(ctx, seqs, lens, n_seqs, opts, out, seconds_out);
-    return rc;
+    return with_xpipe_retry(ctx, 0, [&] { return embed_batch_once(ctx, seqs, lens, n_seqs, opts, out, seconds_out); });
 }
 
 // ---- generation rules: transformers' logits processors on the device, between the forward pass and the selection (kernels_rules.hip.h) --------
@@ -2922,177 +2950,15 @@ static bool enqueue_rules(biogpt_hip_ctx *c, int n_rows, const int32_t *skip, in
     return true;
 }
 
-// ---- beam search: B columns of the batched decode step + selection and K / V forks on the device (kernels_beam.hip.h) ---------------------
-// The prompt goes into slot 0 (pack_column_passes, chunks of n_batch); step 1 re-evaluates its last token as ONE column (eager) and fans the
-// prompt rows out to every slot; steps 2 .. n_predict are forward(B columns) + beam_rows + beam_select + kv_fork, captured per context bucket
-// (graph_beam, laid out like graph_batch).  The host enqueues steps in groups of 8 and reads the done word of the group before through pinned
-// memory; steps after it change nothing.  The context's own K / V cache and position are left alone.
-// `rules`: the rows become processed log-probabilities first (rules_rows_kernel, mode 1) and the top-2B takes them as they are.
-static bool enqueue_beam_select(biogpt_hip_ctx *c, int B, int n_rows, bool rules = false) {
-    const auto &hp = c->hp;
-    const int V = hp.n_vocab, P = hp.n_positions, K = 2 * B;
-    if (rules) {
-        if (!enqueue_rules(c, n_rows, &c->beam_ctl->done, 0)) return false;
-        if (K <= 8) hipLaunchKernelGGL(bgk::beam_given_rows_kernel<8>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
-        else if (K <= 16) hipLaunchKernelGGL(bgk::beam_given_rows_kernel<16>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
-        else hipLaunchKernelGGL(bgk::beam_given_rows_kernel<32>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
-    } else if (K <= 8) hipLaunchKernelGGL(bgk::beam_rows_kernel<8>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
-    else if (K <= 16) hipLaunchKernelGGL(bgk::beam_rows_kernel<16>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
-    else hipLaunchKernelGGL(bgk::beam_rows_kernel<32>, dim3(n_rows), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->beam_ctl, K, c->beam_cand);
-    HIP_TRY(false, hipGetLastError());
-    int32_t *const pool_ids = reinterpret_cast<int32_t *>(c->beam_ctl + 1);
-    hipLaunchKernelGGL(bgk::beam_select_kernel, dim3(1), dim3(bgk::BEAM_SELECT_THREADS), 0, c->stream, c->beam_cand, n_rows, c->beam_ctl, c->seq, c->seq_gen, P, pool_ids);
-    HIP_TRY(false, hipGetLastError());
-    const int dk = hp.d_model / hp.n_head;
-    hipLaunchKernelGGL(bgk::kv_fork_kernel, dim3(hp.n_layer * hp.n_head, std::max(1, B - 1), 2), dim3(256), 0, c->stream, c->beam_ctl, c->bk, c->bv,
-                       (int64_t)hp.n_layer * P * hp.d_model, P, dk, c->seq_gen, P);
-    HIP_TRY(false, hipGetLastError());
-    return true;
-}
-
-static int generate_beam_once(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
-                              int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
-                              double *seconds_out, const biogpt_hip_gen_rules *rules) {
-    XpCallScope xp_scope(ctx);
-    struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } } xc_scope{ctx};
-    clear_error();
-    if (!ctx) BG_FAIL(-1, "null context");
-    if (!prompt || !out_ids || !out_lens || !out_scores) BG_FAIL(-1, "null argument");
-    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
-    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
-    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
-    if (n_prompt < 1) BG_FAIL(-1, "empty prompt");
-    const auto &hp = ctx->hp;
-    const int P = hp.n_positions, B = n_beams;
-    if (eos_id < -1 || eos_id >= hp.n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, hp.n_vocab);
-    if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
-    if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
-    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
-        BG_FAIL(-1, "beam search needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
-    if (hp.n_vocab < 2 * B) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", hp.n_vocab);
-    if (!check_rules(rules, hp.n_vocab, P)) return -1;
-    if (rules_ban(rules, eos_id) && hp.n_vocab - rules->n_suppress - 1 - P < 2 * B)
-        BG_FAIL(-1, "the rules could leave a row fewer than 2 x n_beams candidates: n_vocab - n_suppress - 1 - n_positions = %d < %d", hp.n_vocab - rules->n_suppress - 1 - P, 2 * B);
-    const bool ru = rules_active(rules, eos_id);
-    if (!check_eval_args(ctx, prompt, n_prompt, 0)) return -1;
-    n_predict = std::min(n_predict, P - n_prompt);  // main.cpp:82
-    if (n_predict <= 0) return 0;
-    HIP_TRY(-2, hipSetDevice(ctx->device));
-    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    if (!ensure_seq_caches(ctx, B)) return -2;
-    if (std::max(B, n_prompt) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return -2;   // (as generate_greedy_batch: before any capture)
-    if (!ensure_logits_rows(ctx, (size_t)B)) return -2;
-    if (!ctx->beam_ctl) {
-        HIP_TRY(-2, hipMalloc(&ctx->beam_ctl, sizeof(bgk::BeamCtl) + (size_t)bgk::BEAM_MAX * P * 4));
-        HIP_TRY(-2, hipMalloc(&ctx->beam_cand, sizeof(bgk::BeamCand) * bgk::BEAM_MAX * 2 * bgk::BEAM_MAX));
-        HIP_TRY(-2, hipHostMalloc(&ctx->beam_done_host, 2 * sizeof(int32_t)));
-        for (auto &e : ctx->beam_ev) HIP_TRY(-2, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    if (ctx->graph_beam_n != B) {
-        for (auto &g : ctx->graph_beam) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        ctx->graph_beam_n = B;
-    }
-    {   // the call's parameters and the search's initial state; every column starts as the prompt's last token (only column 0 runs step 1)
-        bgk::BeamCtl h{};
-        h.n_beams = B; h.n_prompt = n_prompt; h.n_predict = n_predict; h.eos_id = eos_id;
-        h.length_penalty = length_penalty; h.early_stopping = early_stopping; h.ids_stride = P;
-        h.heur_unsat = 1;
-        HIP_TRY(-2, hipMemcpy(ctx->beam_ctl, &h, sizeof(h), hipMemcpyHostToDevice));
-        std::vector<bgk::SeqState> hs((size_t)B);
-        for (auto &st : hs) { st = bgk::SeqState{}; st.n_past = n_prompt - 1; st.token = prompt[n_prompt - 1]; }
-        HIP_TRY(-2, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * B, hipMemcpyHostToDevice));
-        if (ru && !rules_upload(ctx, rules, 1, eos_id, prompt, &n_prompt, 1, B)) return -2;
-    }
-
-    // 2 .. 8 beams: the steps as column-per-XCD launches while this call holds the device's pipeline slot (decided ONCE, before any capture)
-    ctx->xc_batch = (B >= 2 && B <= 8 && n_prompt + 1 <= 256 && xcols_prepare(ctx, B, std::min(256, n_prompt + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
-    const int pl = ctx->xc_batch, gset = 6 * pl + (ru ? 12 : 0);      // gset: which set of captured steps
-    auto beam_step = [&](int t_max) -> bool { return enqueue_forward(ctx, B, false, t_max, true) && enqueue_beam_select(ctx, B, B, ru); };
-    const bool use_graph = ctx->opt.no_graph == 0 && (pl != 0 || plain_graph_begin(ctx));      // (a captured five-launch step is not replayed beside another context's persistent launch)
-    if (use_graph && n_predict > 1) {
-        for (int b = graph_bucket(n_prompt + 1); b <= graph_bucket(n_prompt + n_predict - 1); b++) {
-            if (ctx->graph_beam[gset + b]) continue;
-            hipGraph_t g = nullptr;
-            HIP_TRY(-2, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-            const bool ok = beam_step(bucket_tmax(ctx, b));
-            hipError_t e = hipStreamEndCapture(ctx->stream, &g);
-            if (!ok) { if (g) (void)hipGraphDestroy(g); return -2; }
-            HIP_TRY(-2, e);
-            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_beam[gset + b], g, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(g);
-        }
-    }
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-
-    const auto t0 = std::chrono::steady_clock::now();
-    const int32_t lens[1] = {n_prompt};
-    if (!pack_column_passes(ctx, prompt, lens, 1, n_batch,
-                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }))
-        return -2;
-    // step 1: the last prompt token as one column (n_past = n_prompt - 1); its row alone expands (the other beams start at -1e9)
-    if (!enqueue_forward(ctx, 1, false, n_prompt, true) || !enqueue_beam_select(ctx, B, 1, ru)) return -2;
-    for (int k = 2, grp = 0; k <= n_predict; grp++) {
-        for (const int end = std::min(n_predict, k + 7); k <= end; k++) {
-            const int t_max = n_prompt + k - 1;      // keys visible to the token at position n_prompt + k - 2
-            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_beam[gset + graph_bucket(t_max)], ctx->stream));
-            else if (!beam_step(t_max)) return -2;
-        }
-        HIP_TRY(-2, hipMemcpyAsync(ctx->beam_done_host + (grp & 1), &ctx->beam_ctl->done, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(-2, hipEventRecord(ctx->beam_ev[grp & 1], ctx->stream));
-        if (grp > 0) {   // the group before this one has finished: stop enqueueing once it says so (one group stays in flight)
-            HIP_TRY(-2, hipEventSynchronize(ctx->beam_ev[(grp - 1) & 1]));
-            if (ctx->beam_done_host[(grp - 1) & 1]) break;
-        }
-    }
-    std::vector<uint8_t> h(sizeof(bgk::BeamCtl) + (size_t)B * P * 4);
-    HIP_TRY(-2, hipMemcpyAsync(h.data(), ctx->beam_ctl, h.size(), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
-    bgk::BeamCtl st;
-    std::memcpy(&st, h.data(), sizeof(st));
-    if (!st.done || st.pool_n < 1 || st.pool_n > B) BG_FAIL(-2, "internal: beam search ended with %d hypotheses (done word %d)", st.pool_n, st.done);
-    const int32_t *ids = reinterpret_cast<const int32_t *>(h.data() + sizeof(bgk::BeamCtl));
-    for (int r = 0; r < B; r++) {
-        int32_t *o = out_ids + (size_t)r * n_predict;
-        std::fill(o, o + n_predict, -1);
-        out_lens[r] = 0; out_scores[r] = 0.0f;
-        if (r >= st.pool_n) continue;
-        const int slot = st.pool_order[r];
-        out_lens[r] = std::min(st.pool_len[slot], n_predict);
-        out_scores[r] = st.pool_score[slot];
-        std::memcpy(o, ids + (size_t)slot * P, (size_t)out_lens[r] * 4);
-    }
-    return st.pool_n;
-}
-
-int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
-                             int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
-                             double *seconds_out) {
-    return biogpt_hip_generate_beam_rules(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores,
-                                          seconds_out, nullptr);
-}
-
-int biogpt_hip_generate_beam_rules(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
-                                   int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
-                                   double *seconds_out, const biogpt_hip_gen_rules *rules) {
-    int rc = generate_beam_once(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores, seconds_out, rules);
-    if (rc < 0 && xpipe_retry(ctx, 0))
-        rc = generate_beam_once(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores, seconds_out, rules);
-    return rc;
-}
-
 // ---- sampled generation: n_prompts x n_samples columns of the batched decode step + the reference's sampler on the device (kernels_sample.hip.h) ----
-// Built like generate_greedy_batch_once with sample_rows_kernel in the place of argmax_rows_kernel (graph_sample, laid out like graph_batch).  A prompt with
-// several samples is evaluated once, into the slot of its first sample; kv_share_kernel copies its rows to the other slots before the first step.  With an
-// EOS id the host enqueues steps in groups of 8 and reads the count of unfinished sequences of the group before through pinned memory, as beam search reads
-// its done word.  The context's own K / V cache, position and logits row are left alone.
+// The column generation above with sample_rows_kernel as the selection.  A prompt with several samples is evaluated once, into the slot of its first
+// sample.  With an EOS id the steps stop once every sequence has finished (SampleCtl::n_live).  The context's own K / V cache, position and logits row
+// are left alone.
 static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
                                 int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
                                 int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules) {
     XpCallScope xp_scope(ctx);
-    struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } } xc_scope{ctx};
+    XcBatchScope xc_scope{ctx};
     clear_error();
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompts || !prompt_lens || !seeds || !out_ids || !out_lens) BG_FAIL(-1, "null argument");
@@ -3101,49 +2967,30 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     const int n_seqs = n_prompts * n_samples;
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_prompts x n_samples (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
     if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
-    const auto &hp = ctx->hp;
-    const int P = hp.n_positions, V = hp.n_vocab;
+    const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
     if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > V) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
     if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
     if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
     if (eos_id < -1 || eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
-    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
-        BG_FAIL(-1, "sampled generation needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (!check_fast_chain(ctx, "sampled generation")) return -1;
     if (!check_rules(rules, V, P)) return -1;
     const bool ru = rules_active(rules, eos_id);
-    int max_len = 0;
-    long total = 0;
-    for (int p = 0; p < n_prompts; p++) {
-        if (prompt_lens[p] < 1) BG_FAIL(-1, "empty prompt (prompt %d)", p);
-        if (!check_eval_args(ctx, prompts + total, prompt_lens[p], 0)) return -1;
-        max_len = std::max(max_len, prompt_lens[p]);
-        total += prompt_lens[p];
-    }
+    int max_len;
+    long total;
+    if (!check_prompts(ctx, prompts, prompt_lens, n_prompts, "prompt", &max_len, &total)) return -1;
     n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
     if (n_predict <= 0) return 0;
-    HIP_TRY(-2, hipSetDevice(ctx->device));
-    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    if (!ensure_seq_caches(ctx, n_seqs)) return -2;
-    if (std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return -2;   // (as generate_greedy_batch: before any capture)
-    if (!ensure_logits_rows(ctx, (size_t)n_seqs)) return -2;
+    if (!begin_column_call(ctx, n_seqs, total)) return -2;
     if (n_seqs > ctx->sample_cap) {
         if (ctx->sample_ctl) (void)hipFree(ctx->sample_ctl);
         ctx->sample_ctl = nullptr; ctx->sample_cap = 0;
-        for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        drop_graphs(ctx->graphs_sample);
         HIP_TRY(-2, hipMalloc(&ctx->sample_ctl, sizeof(bgk::SampleCtl) + sizeof(bgk::SampleSeq) * (size_t)n_seqs));
         ctx->sample_cap = n_seqs;
     }
-    if (!ctx->sample_live_host) {
-        HIP_TRY(-2, hipHostMalloc(&ctx->sample_live_host, 2 * sizeof(int32_t)));
-        for (auto &e : ctx->sample_ev) HIP_TRY(-2, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    if (ctx->graph_sample_n != n_seqs) {
-        for (auto &g : ctx->graph_sample) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        ctx->graph_sample_n = n_seqs;
-    }
+    column_graphs_for(ctx->graphs_sample, n_seqs, 0);
     bgk::SampleSeq *const sample_seq = reinterpret_cast<bgk::SampleSeq *>(ctx->sample_ctl + 1);
-    {   // the call's parameters, the generators (std::mt19937(seeds[r]), their first block of outputs made here) and the column states: every
-        // sequence starts at its prompt's LAST token (the prompt pass below leaves it to the first step)
+    {   // the call's parameters and the generators (std::mt19937(seeds[r]), their first block of outputs made here)
         std::vector<uint8_t> h(sizeof(bgk::SampleCtl) + sizeof(bgk::SampleSeq) * (size_t)n_seqs, 0);
         bgk::SampleCtl hc{};
         hc.top_k = top_k; hc.eos_id = eos_id; hc.n_live = n_seqs; hc.top_p = top_p; hc.temp = temp;
@@ -3151,24 +2998,11 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
         bgk::SampleSeq *hq = reinterpret_cast<bgk::SampleSeq *>(h.data() + sizeof(bgk::SampleCtl));
         for (int r = 0; r < n_seqs; r++) { bgk::mt_seed(seeds[r], hq[r].mt); bgk::mt_regenerate(hq[r].mt); }
         HIP_TRY(-2, hipMemcpy(ctx->sample_ctl, h.data(), h.size(), hipMemcpyHostToDevice));
-        std::vector<bgk::SeqState> hs((size_t)n_seqs);
-        size_t o = 0;
-        for (int p = 0; p < n_prompts; p++) {
-            o += (size_t)prompt_lens[p];
-            for (int j = 0; j < n_samples; j++) {
-                bgk::SeqState &st = hs[(size_t)p * n_samples + j];
-                st = bgk::SeqState{};
-                st.n_past = prompt_lens[p] - 1; st.token = prompts[o - 1]; st.seq_id = p * n_samples + j;
-            }
-        }
-        HIP_TRY(-2, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * n_seqs, hipMemcpyHostToDevice));
-        if (ru && !rules_upload(ctx, rules, 0, eos_id, prompts, prompt_lens, n_prompts, n_samples)) return -2;
     }
+    if (!upload_column_starts(ctx, prompts, prompt_lens, n_prompts, n_samples)) return -2;
+    if (ru && !rules_upload(ctx, rules, 0, eos_id, prompts, prompt_lens, n_prompts, n_samples)) return -2;
 
-    // 2 .. 8 sequences: the steps as column-per-XCD launches while this call holds the device's pipeline slot (decided ONCE, before any capture)
-    ctx->xc_batch = (n_seqs >= 2 && n_seqs <= 8 && max_len + 1 <= 256 && xcols_prepare(ctx, n_seqs, std::min(256, max_len + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
-    const int pl = ctx->xc_batch, gset = 6 * pl + (ru ? 12 : 0);      // gset: which set of captured steps
-    auto sample_step = [&](int t_max) -> bool {
+    const ColumnStep step = [&](int t_max) -> bool {
         if (!enqueue_forward(ctx, n_seqs, false, t_max, true)) return false;
         if (ru && !enqueue_rules(ctx, n_seqs, &sample_seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
         hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->sample_ctl, sample_seq,
@@ -3176,46 +3010,13 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
         HIP_TRY(false, hipGetLastError());
         return true;
     };
-    const bool use_graph = ctx->opt.no_graph == 0 && (pl != 0 || plain_graph_begin(ctx));      // (a captured step is not replayed beside another context's persistent launch)
-    if (use_graph) {
-        for (int b = graph_bucket(max_len + 1); b <= graph_bucket(std::max(1, max_len + n_predict - 1)); b++) {
-            if (ctx->graph_sample[gset + b]) continue;
-            hipGraph_t g = nullptr;
-            HIP_TRY(-2, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-            const bool ok = sample_step(bucket_tmax(ctx, b));
-            hipError_t e = hipStreamEndCapture(ctx->stream, &g);
-            if (!ok) { if (g) (void)hipGraphDestroy(g); return -2; }
-            HIP_TRY(-2, e);
-            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_sample[gset + b], g, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(g);
-        }
-    }
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const int gset = 6 * choose_column_path(ctx, n_seqs, max_len) + (ru ? 12 : 0);
+    bool use_graph;
+    if (!capture_column_steps(ctx, ctx->graphs_sample, gset, max_len, n_predict, step, &use_graph)) return -2;
 
     const auto t0 = std::chrono::steady_clock::now();
-    if (!pack_column_passes(ctx, prompts, prompt_lens, n_prompts, n_batch,
-                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }, n_samples))
-        return -2;
-    if (n_samples > 1) {
-        hipLaunchKernelGGL(bgk::kv_share_kernel, dim3(hp.n_layer * hp.n_head, n_seqs, 2), dim3(256), 0, ctx->stream, ctx->seq, n_samples, ctx->bk, ctx->bv,
-                           (int64_t)hp.n_layer * P * hp.d_model, P, hp.d_model / hp.n_head);
-        HIP_TRY(-2, hipGetLastError());
-    }
-    if (!sample_step(max_len)) return -2;   // last prompt token of every sequence -> first sampled token
-    for (int k = 1, grp = 0; k < n_predict; grp++) {
-        for (const int end = std::min(n_predict - 1, k + 7); k <= end; k++) {
-            const int t_max = max_len + k;
-            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_sample[gset + graph_bucket(t_max)], ctx->stream));
-            else if (!sample_step(t_max)) return -2;
-        }
-        if (eos_id < 0) continue;
-        HIP_TRY(-2, hipMemcpyAsync(ctx->sample_live_host + (grp & 1), &ctx->sample_ctl->n_live, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(-2, hipEventRecord(ctx->sample_ev[grp & 1], ctx->stream));
-        if (grp > 0) {   // the group before this one has finished: stop enqueueing once every sequence has (one group stays in flight)
-            HIP_TRY(-2, hipEventSynchronize(ctx->sample_ev[(grp - 1) & 1]));
-            if (ctx->sample_live_host[(grp - 1) & 1] <= 0) break;
-        }
-    }
+    if (!ingest_column_prompts(ctx, prompts, prompt_lens, n_prompts, n_batch, n_samples)) return -2;
+    if (!run_column_steps(ctx, ctx->graphs_sample, gset, use_graph, max_len, n_predict, step, eos_id >= 0 ? &ctx->sample_ctl->n_live : nullptr)) return -2;
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
     const auto t1 = std::chrono::steady_clock::now();
     if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
@@ -3244,18 +3045,16 @@ int biogpt_hip_generate_sample(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
 int biogpt_hip_generate_sample_rules(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
                                      int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
                                      int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules) {
-    int rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, rules);
-    if (rc < 0 && xpipe_retry(ctx, 0))
-        rc = generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, rules);
-    return rc;
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, rules);
+    });
 }
 
-// ---- beam search over a batch of prompts: G groups of B columns of the batched decode step, every group a search of its own (kernels_beam.hip.h) ----
-// Built like generate_sample_once: every prompt is evaluated once, into the slot of its group's first column (pack_column_passes, slot stride B), and
-// kv_share_kernel copies its rows to the group's other slots.  Every step, the first included, is forward(G * B columns) + beam_group_rows +
-// beam_group_select + kv_group_fork (graph_bbatch, laid out like graph_beam): at a group's first step the device expands its first row alone, which is the
-// single call's one-column step.  The host enqueues steps in groups of 8 and reads the count of unfinished groups of the group before through pinned
-// memory.  The context's own K / V cache, position and logits row are left alone.
+// ---- beam search: G prompts x B beams as columns of the batched decode step, every prompt a search of its own (kernels_beam.hip.h) ----
+// The column generation above with the three beam kernels as the selection: forward(G * B columns) + beam_group_rows + beam_group_select + kv_group_fork.
+// Every prompt is evaluated once, into the slot of its group's first column; at a group's first step the device expands its first row alone (the other
+// beams have no score yet).  The steps stop once every search has finished (BeamBatchHdr::n_live).  biogpt_hip_generate_beam is the call with G = 1.  The
+// context's own K / V cache, position and logits row are left alone.
 constexpr int BBATCH_COLS = 512;    // columns of a call, at most
 static size_t bbatch_forks_off() { return sizeof(bgk::BeamBatchHdr); }
 static size_t bbatch_skip_off() { return bbatch_forks_off() + sizeof(bgk::BeamFork) * BBATCH_COLS; }
@@ -3305,7 +3104,7 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
                                     int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping, const biogpt_hip_gen_rules *rules,
                                     int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts, double *seconds_out) {
     XpCallScope xp_scope(ctx);
-    struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } } xc_scope{ctx};
+    XcBatchScope xc_scope{ctx};
     clear_error();
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompts || !prompt_lens || !out_ids || !out_lens || !out_scores || !out_counts) BG_FAIL(-1, "null argument");
@@ -3321,109 +3120,48 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     if (eos_id < -1 || eos_id >= hp.n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, hp.n_vocab);
     if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
     if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
-    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
-        BG_FAIL(-1, "beam search needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (!check_fast_chain(ctx, "beam search")) return -1;
     if (hp.n_vocab < 2 * B) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", hp.n_vocab);
     if (!check_rules(rules, hp.n_vocab, P)) return -1;
     if (rules_ban(rules, eos_id) && hp.n_vocab - rules->n_suppress - 1 - P < 2 * B)
         BG_FAIL(-1, "the rules could leave a row fewer than 2 x n_beams candidates: n_vocab - n_suppress - 1 - n_positions = %d < %d", hp.n_vocab - rules->n_suppress - 1 - P, 2 * B);
     const bool ru = rules_active(rules, eos_id);
-    int max_len = 0;
-    long total = 0;
-    for (int p = 0; p < G; p++) {
-        if (prompt_lens[p] < 1) BG_FAIL(-1, "empty prompt (prompt %d)", p);
-        if (!check_eval_args(ctx, prompts + total, prompt_lens[p], 0)) return -1;
-        max_len = std::max(max_len, prompt_lens[p]);
-        total += prompt_lens[p];
-    }
+    int max_len;
+    long total;
+    if (!check_prompts(ctx, prompts, prompt_lens, G, "prompt", &max_len, &total)) return -1;
     n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
     if (n_predict <= 0) return 0;
-    HIP_TRY(-2, hipSetDevice(ctx->device));
-    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    if (!ensure_seq_caches(ctx, n_seqs)) return -2;
-    if (std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return -2;   // (as generate_greedy_batch: before any capture)
-    if (!ensure_logits_rows(ctx, (size_t)n_seqs)) return -2;
-    if (!ctx->bbatch_buf) {
-        HIP_TRY(-2, hipMalloc(&ctx->bbatch_buf, bbatch_ids_off() + (size_t)BBATCH_COLS * P * 4));
-        HIP_TRY(-2, hipHostMalloc(&ctx->bbatch_live_host, 2 * sizeof(int32_t)));
-        for (auto &e : ctx->bbatch_ev) HIP_TRY(-2, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    if (ctx->graph_bbatch_g != G || ctx->graph_bbatch_b != B) {
-        for (auto &g : ctx->graph_bbatch) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        ctx->graph_bbatch_g = G; ctx->graph_bbatch_b = B;
-    }
+    if (!begin_column_call(ctx, n_seqs, total)) return -2;
+    if (!ctx->bbatch_buf) HIP_TRY(-2, hipMalloc(&ctx->bbatch_buf, bbatch_ids_off() + (size_t)BBATCH_COLS * P * 4));
+    column_graphs_for(ctx->graphs_beam, G, B);
     bgk::BeamBatchHdr *const hdr = reinterpret_cast<bgk::BeamBatchHdr *>(ctx->bbatch_buf);
-    {   // the call's parameters and every group's initial state; every column starts as its prompt's last token (the prompt pass below leaves it to
-        // the first step).  The rules kernel skips the columns whose row the first step does not expand.
+    {   // the call's parameters and every group's initial state.  The rules kernel skips the columns whose row the first step does not expand.
         std::vector<uint8_t> h(bbatch_ctl_off() + sizeof(bgk::BeamCtl) * (size_t)G, 0);
         bgk::BeamBatchHdr hh{};
         hh.n_live = G;
         std::memcpy(h.data(), &hh, sizeof(hh));
         int32_t *skip = reinterpret_cast<int32_t *>(h.data() + bbatch_skip_off());
         bgk::BeamCtl *hc = reinterpret_cast<bgk::BeamCtl *>(h.data() + bbatch_ctl_off());
-        std::vector<bgk::SeqState> hs((size_t)n_seqs);
-        size_t o = 0;
         for (int p = 0; p < G; p++) {
-            o += (size_t)prompt_lens[p];
             bgk::BeamCtl &c = hc[p];
             c.n_beams = B; c.n_prompt = prompt_lens[p]; c.n_predict = n_predict; c.eos_id = eos_id;
             c.length_penalty = length_penalty; c.early_stopping = early_stopping; c.ids_stride = P;
             c.heur_unsat = 1;
-            for (int j = 0; j < B; j++) {
-                bgk::SeqState &st = hs[(size_t)p * B + j];
-                st = bgk::SeqState{};
-                st.n_past = prompt_lens[p] - 1; st.token = prompts[o - 1]; st.seq_id = p * B + j;
-                skip[p * B + j] = j > 0 ? 1 : 0;
-            }
+            for (int j = 1; j < B; j++) skip[p * B + j] = 1;
         }
         HIP_TRY(-2, hipMemcpy(ctx->bbatch_buf, h.data(), h.size(), hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * n_seqs, hipMemcpyHostToDevice));
-        if (ru && !rules_upload(ctx, rules, 1, eos_id, prompts, prompt_lens, G, B)) return -2;
     }
+    if (!upload_column_starts(ctx, prompts, prompt_lens, G, B)) return -2;
+    if (ru && !rules_upload(ctx, rules, 1, eos_id, prompts, prompt_lens, G, B)) return -2;
 
-    // 2 .. 8 columns: the steps as column-per-XCD launches while this call holds the device's pipeline slot (decided ONCE, before any capture)
-    ctx->xc_batch = (n_seqs >= 2 && n_seqs <= 8 && max_len + 1 <= 256 && xcols_prepare(ctx, n_seqs, std::min(256, max_len + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
-    const int pl = ctx->xc_batch, gset = 6 * pl + (ru ? 12 : 0);      // gset: which set of captured steps
-    auto group_step = [&](int t_max) -> bool { return enqueue_forward(ctx, n_seqs, false, t_max, true) && enqueue_beam_group_select(ctx, G, B, ru); };
-    const bool use_graph = ctx->opt.no_graph == 0 && (pl != 0 || plain_graph_begin(ctx));      // (a captured step is not replayed beside another context's persistent launch)
-    if (use_graph && n_predict > 1) {
-        for (int b = graph_bucket(max_len + 1); b <= graph_bucket(max_len + n_predict - 1); b++) {
-            if (ctx->graph_bbatch[gset + b]) continue;
-            hipGraph_t g = nullptr;
-            HIP_TRY(-2, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-            const bool ok = group_step(bucket_tmax(ctx, b));
-            hipError_t e = hipStreamEndCapture(ctx->stream, &g);
-            if (!ok) { if (g) (void)hipGraphDestroy(g); return -2; }
-            HIP_TRY(-2, e);
-            HIP_TRY(-2, hipGraphInstantiate(&ctx->graph_bbatch[gset + b], g, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(g);
-        }
-    }
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const ColumnStep step = [&](int t_max) -> bool { return enqueue_forward(ctx, n_seqs, false, t_max, true) && enqueue_beam_group_select(ctx, G, B, ru); };
+    const int gset = 6 * choose_column_path(ctx, n_seqs, max_len) + (ru ? 12 : 0);
+    bool use_graph;
+    if (!capture_column_steps(ctx, ctx->graphs_beam, gset, max_len, n_predict, step, &use_graph)) return -2;
 
     const auto t0 = std::chrono::steady_clock::now();
-    if (!pack_column_passes(ctx, prompts, prompt_lens, G, n_batch,
-                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }, B))
-        return -2;
-    if (B > 1) {
-        hipLaunchKernelGGL(bgk::kv_share_kernel, dim3(hp.n_layer * hp.n_head, n_seqs, 2), dim3(256), 0, ctx->stream, ctx->seq, B, ctx->bk, ctx->bv,
-                           (int64_t)hp.n_layer * P * hp.d_model, P, hp.d_model / hp.n_head);
-        HIP_TRY(-2, hipGetLastError());
-    }
-    if (!group_step(max_len)) return -2;    // step 1: the last prompt token of every group; its first row alone expands
-    for (int k = 2, grp = 0; k <= n_predict; grp++) {
-        for (const int end = std::min(n_predict, k + 7); k <= end; k++) {
-            const int t_max = max_len + k - 1;      // keys visible to the token at position max_len + k - 2
-            if (use_graph) HIP_TRY(-2, hipGraphLaunch(ctx->graph_bbatch[gset + graph_bucket(t_max)], ctx->stream));
-            else if (!group_step(t_max)) return -2;
-        }
-        HIP_TRY(-2, hipMemcpyAsync(ctx->bbatch_live_host + (grp & 1), &hdr->n_live, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(-2, hipEventRecord(ctx->bbatch_ev[grp & 1], ctx->stream));
-        if (grp > 0) {   // the group of steps before this one has finished: stop enqueueing once every search has (one group stays in flight)
-            HIP_TRY(-2, hipEventSynchronize(ctx->bbatch_ev[(grp - 1) & 1]));
-            if (ctx->bbatch_live_host[(grp - 1) & 1] <= 0) break;
-        }
-    }
+    if (!ingest_column_prompts(ctx, prompts, prompt_lens, G, n_batch, B)) return -2;
+    if (!run_column_steps(ctx, ctx->graphs_beam, gset, use_graph, max_len, n_predict, step, &hdr->n_live)) return -2;
     std::vector<bgk::BeamCtl> hc((size_t)G);
     std::vector<int32_t> ids((size_t)n_seqs * P);
     HIP_TRY(-2, hipMemcpyAsync(hc.data(), ctx->bbatch_buf + bbatch_ctl_off(), sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyDeviceToHost, ctx->stream));
@@ -3454,12 +3192,34 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
 int biogpt_hip_generate_beam_batch(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_batch, int32_t n_beams,
                                    int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping, const biogpt_hip_gen_rules *rules,
                                    int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts, double *seconds_out) {
-    int rc = generate_beam_batch_once(ctx, prompts, prompt_lens, n_prompts, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, rules, out_ids, out_lens,
-                                      out_scores, out_counts, seconds_out);
-    if (rc < 0 && xpipe_retry(ctx, 0))
-        rc = generate_beam_batch_once(ctx, prompts, prompt_lens, n_prompts, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, rules, out_ids, out_lens,
-                                      out_scores, out_counts, seconds_out);
-    return rc;
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_beam_batch_once(ctx, prompts, prompt_lens, n_prompts, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, rules, out_ids, out_lens,
+                                        out_scores, out_counts, seconds_out);
+    });
+}
+
+// one prompt: the call above with a group of one; returns the number of hypotheses
+int biogpt_hip_generate_beam_rules(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
+                                   int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
+                                   double *seconds_out, const biogpt_hip_gen_rules *rules) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!prompt || !out_ids || !out_lens || !out_scores) BG_FAIL(-1, "null argument");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
+    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
+    if (n_prompt < 1) BG_FAIL(-1, "empty prompt");      // (in this order: a call with several bad arguments reports the first of them)
+    int32_t count[1] = {0};
+    const int rc = biogpt_hip_generate_beam_batch(ctx, prompt, &n_prompt, 1, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, rules, out_ids, out_lens,
+                                                  out_scores, count, seconds_out);
+    return rc > 0 ? count[0] : rc;
+}
+
+int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_batch, int32_t n_beams, int32_t n_predict,
+                             int32_t eos_id, float length_penalty, int32_t early_stopping, int32_t *out_ids, int32_t *out_lens, float *out_scores,
+                             double *seconds_out) {
+    return biogpt_hip_generate_beam_rules(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores,
+                                          seconds_out, nullptr);
 }
 
 // rules_rows_kernel over rows held in host memory (tests of the kernel itself): row r's history is hist_lens[r] tokens of `hist` (the histories

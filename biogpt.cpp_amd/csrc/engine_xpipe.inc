@@ -283,7 +283,7 @@ bool pipeline_slot_take(biogpt_hip_ctx *c) {
     if (owner == c) c->xp_in_call = true;      // until the API call that asked returns (XpCallScope)
     return owner == c;
 }
-// A captured five-launch step (a "plain" graph: graph_eval / graph_step / graph_batch with pl == 0) must not be replayed beside ANOTHER context's persistent launch: on
+// A captured five-launch step (a "plain" graph: graph_eval / graph_step / a column step captured without the column-per-XCD launch) must not be replayed beside ANOTHER context's persistent launch: on
 // this runtime its last nodes were observed to see the previous replay's activations (profiles/two_contexts_r4.txt; cause not found, profiles/stale_row_r5.txt).  The
 // decision and its record are one step under g_xp_mu (ADVICE r4: a check followed by a launch let the slot change hands in between):
 //   plain_graph_begin(c)  false: another context holds the slot -- the caller takes eager launches.  true: c is entered in the device's list of contexts with such

@@ -1,31 +1,28 @@
-// Beam search (biogpt_hip_generate_beam): the selection of a beam step on the device, inside the captured step.
-// A step is the batched decode of the B running beams (one column and one K / V cache slot per beam), then:
+// Beam search (biogpt_hip_generate_beam_batch; biogpt_hip_generate_beam is the call with one prompt): the selection of a beam step on the
+// device, inside the captured step.  G independent searches of B beams run as one batched decode of G * B columns (one column and one K / V
+// cache slot per beam).  Group g owns the columns and cache slots [g * B, (g + 1) * B) and one BeamCtl of an array of G; what a group's
+// kernels touch is its own slice of every array, so the bodies below are written for one search and take the slice.  After the forward pass:
 //
-//   beam_rows_kernel    one workgroup per beam row of logits_all: the passes of logprob_rows_kernel (row maximum m, S = sum exp(l - m))
-//                       and the row's top K = 2B (logit, id), equal logits: lower id first.  Writes K candidates
-//                       {s_b + lp, column, id} with lp = (l - m) - log(S) (double arithmetic, rounded once), s_b + lp in f32.
-//   beam_select_kernel  one workgroup: the top 2B of all candidates (score descending, parent rank ascending, id ascending), the next
-//                       running beams, the finished pool and the stopping rules of transformers' _beam_search, the
-//                       new column states and a fork list.  Children are assigned to columns so that the column -> cache mapping
-//                       stays the identity: the first child of a parent keeps the parent's column, further children take the columns
-//                       of parents without children.  Fork sources and destinations are then disjoint sets.
-//   kv_fork_kernel      for each fork: K and V rows [lo, hi) of every layer and head from the source slot to the destination slot
-//                       (head-major cache: one contiguous run per (layer, head)), plus the token history.  Fixed grid (capturable).
+//   beam_group_rows_kernel    one workgroup per column (row of logits_all): the passes of logprob_rows_kernel (row maximum m,
+//                             S = sum exp(l - m)) and the row's top K = 2B (logit, id), equal logits: lower id first.  Writes K candidates
+//                             {s_b + lp, column within the group, id} with lp = (l - m) - log(S) (double arithmetic, rounded once), s_b + lp
+//                             in f32.  A finished group's rows and, at a group's first step, every row but its first return at once (the
+//                             other beams have no score yet).  GIVEN: the row holds processed log-probabilities (generation rules).
+//   beam_group_select_kernel  one workgroup per group: the top 2B of all candidates (score descending, parent rank ascending, id ascending),
+//                             the next running beams, the finished pool and the stopping rules of transformers' _beam_search
+//                             (INTEGRATION.md), the new column states and the group's forks.  Children are assigned to columns so that the
+//                             column -> cache mapping stays the identity: the first child of a parent keeps the parent's column, further
+//                             children take the columns of parents without children.  Fork sources and destinations are then disjoint
+//                             sets.  The forks (column base added) are appended to ONE compacted list; the kernel also writes the
+//                             per-column skip words of the rules kernel and counts the unfinished groups down.
+//   kv_group_fork_kernel      grid (n_layer * n_head, BEAM_FORK_WGS, 2): for each fork, K and V rows [lo, hi) of every layer and head from
+//                             the source slot to the destination slot (head-major cache: one contiguous run per (layer, head)), plus the
+//                             token history.  The workgroups of a (layer, head, K | V) stride over the compacted list: the grid is fixed
+//                             (capturable) and does not grow with G * (B - 1).
 //
-// Nothing here leaves the device; the host only reads the done word between groups of steps and the pool at the end.
-//
-// Beam search over a batch of prompts (biogpt_hip_generate_beam_batch): G independent searches of B beams in one step of G * B columns.
-// Group g owns the columns and cache slots [g * B, (g + 1) * B) and one BeamCtl of an array of G; everything a group's kernels touch is the
-// single search's state shifted by the group's base, so the bodies above serve both:
-//
-//   beam_group_rows_kernel    one workgroup per column: beam_rows_body with the running score of the column's group.  A finished group's rows
-//                             and, at a group's first step, every row but its first return at once.
-//   beam_group_select_kernel  one workgroup per group: beam_select_body on the group's slices, then the group's forks (column base added) appended
-//                             to ONE compacted list, the per-column skip words of the rules kernel, and the count of unfinished groups.
-//   kv_group_fork_kernel      grid (n_layer * n_head, BEAM_FORK_WGS, 2): the workgroups of a (layer, head, K | V) stride over the compacted list.
-//                             The grid is fixed (capturable) and does not grow with G * (B - 1).
-//
-// A finished group leaves everything alone: its columns keep token and position and recompute a K / V row they already hold.
+// Every slot of a group holds its prompt's rows before the first step (kv_share_kernel), so a fork copies generated rows only.  A finished
+// group leaves everything alone: its columns keep token and position and recompute a K / V row they already hold.  Nothing here leaves the
+// device; the host only reads the count of unfinished groups between groups of steps and the pools at the end.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -38,6 +35,7 @@ namespace bgk {
 
 constexpr int BEAM_MAX = 16;                   // beams per call; 2 * BEAM_MAX candidates per row
 constexpr int BEAM_SELECT_THREADS = BEAM_MAX * 2 * BEAM_MAX;   // one thread per candidate of a full step
+constexpr int BEAM_FORK_WGS = 8;               // copy workgroups per (layer, head, K | V), striding over the step's fork list
 
 struct BeamCand {
     float score;    // accumulated log-probability, f32
@@ -46,7 +44,7 @@ struct BeamCand {
     int32_t pad;
 };
 
-// Device state of one beam search call.  The first block is uploaded by the host per call; the rest is the kernels' own.
+// Device state of one search (group).  The first block is uploaded by the host per call; the rest is the kernels' own.
 struct BeamCtl {
     int32_t n_beams, n_prompt, n_predict, eos_id;   // eos_id < 0: none
     float length_penalty;
@@ -63,8 +61,22 @@ struct BeamCtl {
     int32_t pool_order[BEAM_MAX];  // pool slots, best first
     int32_t pool_len[BEAM_MAX];    // per slot: generated tokens (EOS included)
     float pool_score[BEAM_MAX];    // per slot: normalized score
-    int32_t fork_n, fork_lo, fork_hi, fork_gen;     // forks of the last step; rows [lo, hi) of K / V, fork_gen tokens of history
+    int32_t fork_n, fork_hi, fork_gen;              // forks of the last step; rows [n_prompt, fork_hi) of K / V, fork_gen tokens of history
     int32_t fork_src[BEAM_MAX], fork_dst[BEAM_MAX];
+};
+
+// what the groups of a call share
+struct BeamBatchHdr {
+    int32_t n_live;        // groups still searching
+    int32_t fork_n;        // entries of the fork list of this step (reset by the row kernel of the next)
+    int32_t pad[2];
+};
+
+struct BeamFork {
+    int32_t src, dst;      // cache slots (= columns)
+    int32_t lo, hi;        // K / V rows [lo, hi)
+    int32_t gen;           // tokens of history
+    int32_t pad[3];
 };
 
 __device__ __forceinline__ bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
@@ -83,7 +95,7 @@ __device__ __forceinline__ void beam_insert(float v, int i, float (&tv)[KM], int
     }
 }
 
-// The body of beam_rows_kernel.  GIVEN = false: the row holds logits (the log-softmax is taken here).  GIVEN = true: it holds log-probabilities
+// The body of beam_group_rows_kernel.  GIVEN = false: the row holds logits (the log-softmax is taken here).  GIVEN = true: it holds log-probabilities
 // already, processed by rules_rows_kernel (kernels_rules.hip.h), and its values are taken as they are (an entry at -inf becomes a candidate only
 // where fewer than K finite ones are left, which the argument check of the rules excludes).
 // row: the row's n_vocab values; run_score: the accumulated score of the beam in this row; col: the column the candidates name as their parent;
@@ -186,18 +198,15 @@ __device__ __forceinline__ void beam_rows_body(const float *row, int n_vocab, co
     }
 }
 
-// logits: [n_rows][ldl] (row r = column r); K = 2 * n_beams <= KM; cand: [n_rows][K]
-template <int KM>
-__global__ __launch_bounds__(LP_THREADS) void beam_rows_kernel(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
-    const int col = blockIdx.x;
-    beam_rows_body<KM, false>(logits + (size_t)col * ldl, n_vocab, &ctl->run_score[col], col, K, cand + (size_t)col * K);
-}
-
-// the same over rows of processed log-probabilities (a step with generation rules)
-template <int KM>
-__global__ __launch_bounds__(LP_THREADS) void beam_given_rows_kernel(const float *logp, int ldl, int n_vocab, const BeamCtl *ctl, int K, BeamCand *cand) {
-    const int col = blockIdx.x;
-    beam_rows_body<KM, true>(logp + (size_t)col * ldl, n_vocab, &ctl->run_score[col], col, K, cand + (size_t)col * K);
+// logits: [G * B][ldl] (row r = column r); ctl: [G]; cand: [G * B][2 * B].  KM >= 2 * B.
+template <int KM, bool GIVEN>
+__global__ __launch_bounds__(LP_THREADS) void beam_group_rows_kernel(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int B, BeamBatchHdr *hdr,
+                                                                     BeamCand *cand) {
+    const int col = blockIdx.x, g = col / B, j = col - g * B;
+    if (col == 0 && threadIdx.x == 0) hdr->fork_n = 0;      // the copies of the step before are done (stream order)
+    const BeamCtl *c = ctl + g;
+    if (c->done || (c->step == 0 && j > 0)) return;         // (a group's first step expands its first row alone)
+    beam_rows_body<KM, GIVEN>(logits + (size_t)col * ldl, n_vocab, &c->run_score[j], j, 2 * B, cand + (size_t)col * 2 * B);
 }
 
 // candidate order of a step: score descending, then the parent's rank, then the token id
@@ -211,7 +220,7 @@ __device__ __forceinline__ float beam_norm(float s, int gen_len, float lp) { ret
 
 // n_rows beam rows (1 at the first step, n_beams after) of K = 2 * n_beams candidates each.  seq: the n_beams column states;
 // seq_gen: [column][gen_stride] token histories; pool_ids: [slot][ctl->ids_stride].
-// The body of beam_select_kernel; false: the search had stopped before this step and nothing was touched (uniform over the workgroup).
+// The search's part of beam_group_select_kernel; false: the search had stopped before this step and nothing was touched (uniform over the workgroup).
 __device__ __forceinline__ bool beam_select_body(const BeamCand *cand, int n_rows, BeamCtl *ctl, SeqState *seq, int32_t *seq_gen, int gen_stride,
                                                  int32_t *pool_ids) {
     __shared__ BeamCand s_c[2 * BEAM_MAX];
@@ -300,9 +309,7 @@ __device__ __forceinline__ bool beam_select_body(const BeamCand *cand, int n_row
             s.n_gen = k;
             seq_gen[(size_t)c * gen_stride + (k - 1)] = s_c[run[r]].id;
         }
-        // the first step fans the prompt rows of slot 0 out to every slot; later forks copy the generated rows only
         ctl->fork_n = nf;
-        ctl->fork_lo = k == 1 ? 0 : ctl->n_prompt;
         ctl->fork_hi = n_past;
         ctl->fork_gen = k - 1;
         ctl->step = k;
@@ -320,56 +327,6 @@ __device__ __forceinline__ bool beam_select_body(const BeamCand *cand, int n_row
         for (int j = tid; j < k; j += blockDim.x) dst[j] = j + 1 < k ? src[j] : s_c[i].id;
     }
     return true;
-}
-
-__global__ __launch_bounds__(BEAM_SELECT_THREADS) void beam_select_kernel(const BeamCand *cand, int n_rows, BeamCtl *ctl, SeqState *seq,
-                                                                          int32_t *seq_gen, int gen_stride, int32_t *pool_ids) {
-    (void)beam_select_body(cand, n_rows, ctl, seq, seq_gen, gen_stride, pool_ids);
-}
-
-// grid (n_layer * n_head, max(1, n_beams - 1), 2 [K, V]); seq_stride floats between two slots, P * dk between two heads
-__global__ __launch_bounds__(256) void kv_fork_kernel(const BeamCtl *ctl, float *kroot, float *vroot, int64_t seq_stride, int P, int dk,
-                                                      int32_t *seq_gen, int gen_stride) {
-    const int f = blockIdx.y;
-    if (ctl->done || f >= ctl->fork_n) return;
-    const int src = ctl->fork_src[f], dst = ctl->fork_dst[f];
-    const int lo = ctl->fork_lo, hi = ctl->fork_hi;
-    const size_t run0 = (size_t)blockIdx.x * P * dk;    // (layer, head) run; layers are n_head runs apart
-    float *root = blockIdx.z == 0 ? kroot : vroot;
-    const float4 *s4 = reinterpret_cast<const float4 *>(root + (size_t)src * seq_stride + run0 + (size_t)lo * dk);
-    float4 *d4 = reinterpret_cast<float4 *>(root + (size_t)dst * seq_stride + run0 + (size_t)lo * dk);
-    const int n4 = hi > lo ? (hi - lo) * dk / 4 : 0;
-    for (int i = threadIdx.x; i < n4; i += blockDim.x) d4[i] = s4[i];
-    if (blockIdx.x == 0 && blockIdx.z == 0)
-        for (int j = threadIdx.x; j < ctl->fork_gen; j += blockDim.x) seq_gen[(size_t)dst * gen_stride + j] = seq_gen[(size_t)src * gen_stride + j];
-}
-
-// ---- beam search over a batch of prompts -------------------------------------------------------------------------------------------------
-
-constexpr int BEAM_FORK_WGS = 8;               // copy workgroups per (layer, head, K | V), striding over the step's fork list
-
-struct BeamBatchHdr {
-    int32_t n_live;        // groups still searching
-    int32_t fork_n;        // entries of the fork list of this step (reset by the row kernel of the next)
-    int32_t pad[2];
-};
-
-struct BeamFork {
-    int32_t src, dst;      // cache slots (= columns)
-    int32_t lo, hi;        // K / V rows [lo, hi)
-    int32_t gen;           // tokens of history
-    int32_t pad[3];
-};
-
-// logits: [G * B][ldl] (row r = column r); ctl: [G]; cand: [G * B][2 * B].  KM >= 2 * B.
-template <int KM, bool GIVEN>
-__global__ __launch_bounds__(LP_THREADS) void beam_group_rows_kernel(const float *logits, int ldl, int n_vocab, const BeamCtl *ctl, int B, BeamBatchHdr *hdr,
-                                                                     BeamCand *cand) {
-    const int col = blockIdx.x, g = col / B, j = col - g * B;
-    if (col == 0 && threadIdx.x == 0) hdr->fork_n = 0;      // the copies of the step before are done (stream order)
-    const BeamCtl *c = ctl + g;
-    if (c->done || (c->step == 0 && j > 0)) return;         // (a group's first step expands its first row alone)
-    beam_rows_body<KM, GIVEN>(logits + (size_t)col * ldl, n_vocab, &c->run_score[j], j, 2 * B, cand + (size_t)col * 2 * B);
 }
 
 // grid: G.  seq, seq_gen, col_skip: all G * B columns; pool_ids: [G * B][ctl->ids_stride]; forks: room for G * (B - 1) entries.

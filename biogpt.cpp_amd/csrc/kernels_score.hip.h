@@ -24,7 +24,7 @@ __device__ __forceinline__ void lp_better(float v, int i, float &bv, int &bi) {
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
 }
 
-// The two passes over one logits row by a workgroup of LP_THREADS threads (shared with beam_rows_kernel, kernels_beam.hip.h).
+// The two passes over one logits row by a workgroup of LP_THREADS threads (shared with beam_group_rows_kernel, kernels_beam.hip.h).
 // Every thread returns the row maximum m and its lowest arg-max bi; thread 0 also the exponential sum S = sum_v exp(l[v] - m).
 __device__ __forceinline__ void lp_row_stats(const float *row, int n_vocab, float &m, int &bi, double &S) {
     __shared__ float s_max[LP_THREADS / 64];

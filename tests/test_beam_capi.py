@@ -36,8 +36,8 @@ def test_beam_null_context_fails_without_a_device(pkg):
 
 
 def test_beam_kernels_use_no_scratch(pkg, tmp_path):
-    """beam_rows_kernel (every instantiation), beam_select_kernel and kv_fork_kernel: the kernel descriptors in obj/engine.o, read as
-    test_score_capi.py reads logprob_rows_kernel's."""
+    """beam_group_rows_kernel (every instantiation), beam_group_select_kernel and kv_group_fork_kernel: the kernel descriptors in obj/engine.o,
+    read as test_score_capi.py reads logprob_rows_kernel's."""
     llvm = "/opt/rocm/lib/llvm/bin"
     if not (os.path.exists(llvm + "/clang-offload-bundler") and shutil.which("objcopy")):
         pytest.skip("no clang-offload-bundler / objcopy in this image")
@@ -54,7 +54,7 @@ def test_beam_kernels_use_no_scratch(pkg, tmp_path):
         if m:
             name = m.group(1)
         m = re.match(r"\s+\.private_segment_fixed_size:\s+(\d+)", line)
-        if m and name and re.search(r"beam_rows_kernel|beam_select_kernel|kv_fork_kernel", name):
+        if m and name and re.search(r"beam_group_rows_kernel|beam_group_select_kernel|kv_group_fork_kernel", name):
             assert int(m.group(1)) == 0, "%s uses %s bytes of scratch per lane" % (name, m.group(1))
             seen.add(name)
-    assert len(seen) == 5, seen      # beam_rows_kernel<8 / 16 / 32>, beam_select_kernel, kv_fork_kernel
+    assert len(seen) == 8, seen      # beam_group_rows_kernel<8 / 16 / 32, false / true>, beam_group_select_kernel, kv_group_fork_kernel

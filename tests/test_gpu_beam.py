@@ -1,4 +1,4 @@
-"""Beam search (biogpt_hip_generate_beam, kernels_beam.hip.h) on the GPU: one beam is greedy decoding; the search equals beam_ref (the
+"""Beam search (biogpt_hip_generate_beam: the batched search with one prompt, kernels_beam.hip.h) on the GPU: one beam is greedy decoding; the search equals beam_ref (the
 restatement pinned to transformers by test_beam_restatement.py) driven by the oracle; its scores are the engine's own scoring of the
 hypotheses; the captured, eager and column-per-XCD paths agree; the context's own K / V cache is left alone."""
 import numpy as np
@@ -85,11 +85,7 @@ def oracle_rows(oracle, files):
     return get, eos_of
 
 
-@pytest.mark.parametrize("es", [True, False])
-@pytest.mark.parametrize("nb", [1, 8])
-@pytest.mark.parametrize("B", [2, 4, 5, 8])
-@pytest.mark.parametrize("name", ["q4_0", "q5_1", "q8_0"])
-def test_beam_against_restatement(pkg, files, oracle_rows, name, B, nb, es):
+def check_against_restatement(pkg, files, oracle_rows, name, B, nb, es):
     get, eos_of = oracle_rows
     eos = eos_of(name)
     want, margins = beam_ref.beam_search(get(name, nb), B, N_PREDICT, eos, 1.0, es)
@@ -103,6 +99,21 @@ def test_beam_against_restatement(pkg, files, oracle_rows, name, B, nb, es):
         assert list(ids_g) == list(ids_w), (r, list(ids_g), list(ids_w))
         assert abs(float(s_g) - float(s_w)) <= 1e-4, (r, float(s_g), float(s_w))
     print("%s B=%d n_batch=%d early_stopping=%s eos=%d: %d steps, lengths %s" % (name, B, nb, es, eos, len(margins), [len(h[0]) for h in got]))
+
+
+@pytest.mark.parametrize("es", [True, False])
+@pytest.mark.parametrize("nb", [1, 8])
+@pytest.mark.parametrize("B", [2, 4, 5, 8])
+@pytest.mark.parametrize("name", ["q4_0", "q5_1", "q8_0"])
+def test_beam_against_restatement(pkg, files, oracle_rows, name, B, nb, es):
+    check_against_restatement(pkg, files, oracle_rows, name, B, nb, es)
+
+
+@pytest.mark.parametrize("es", [True, False])
+def test_twelve_beams_against_restatement(pkg, files, oracle_rows, es):
+    """24 candidates per row (the 32-entry instantiation of the row kernel) and up to 11 forks in a step, more than the 8 copy workgroups a
+    (layer, head) has: they stride over the fork list."""
+    check_against_restatement(pkg, files, oracle_rows, "q4_0", 12, 8, es)
 
 
 def test_eos_fires_in_the_restatement_cases(oracle_rows):

@@ -1,8 +1,9 @@
-"""Beam search over a batch of prompts (biogpt_hip_generate_beam_batch, kernels_beam.hip.h) on the GPU.  The definition: for every prompt the
-batched call returns what biogpt_hip_generate_beam_rules returns for that prompt alone (n_predict clamped for the longest prompt), hypothesis
-for hypothesis, ids and f32 scores bit for bit -- whatever the number of columns (chunk kernel, 8-column chain, matrix cores), with groups that
-finish at different steps, with rules, captured or eager.  One batch is also held to beam_ref (the restatement pinned to transformers) driven by
-the oracle.  The context's own K / V cache and position are left alone."""
+"""Beam search over a batch of prompts (biogpt_hip_generate_beam_batch, kernels_beam.hip.h) on the GPU.  The searches of a call are independent:
+for every prompt the batched call returns what the call with that prompt alone returns (biogpt_hip_generate_beam_rules, a group of one; n_predict
+clamped for the longest prompt), hypothesis for hypothesis, ids and f32 scores bit for bit -- whatever the number of columns (chunk kernel,
+8-column chain, matrix cores), with groups that finish at different steps, with rules, captured or eager.  What a search computes is held to
+beam_ref (the restatement pinned to transformers) driven by the oracle, here for one batch per weight type and in test_gpu_beam.py for single
+calls.  The context's own K / V cache and position are left alone."""
 import ctypes
 
 import numpy as np
@@ -161,11 +162,12 @@ def test_groups_finish_at_different_steps(models):
 
 # ---- 3. the restatement, driven by the oracle ----
 
-def test_batch_against_restatement(models, oracle, files):
-    g = models["q4_0"]
+@pytest.mark.parametrize("name", ["q4_0", "q5_1", "q8_0"])
+def test_batch_against_restatement(models, oracle, files, name):
+    g = models[name]
     B, nb, n_predict = 4, 8, 10
     prompts = [prompt_of(13, 3), prompt_of(9, 71), prompt_of(17, 72)]
-    rows = [beam_ref.OracleLogprobs(oracle.OracleModel(files["q4_0"], n_threads=16), p, nb) for p in prompts]
+    rows = [beam_ref.OracleLogprobs(oracle.OracleModel(files[name], n_threads=16), p, nb) for p in prompts]
     eos = int(beam_ref.beam_search(rows[0], B, n_predict, -1, 1.0, True)[0][0][0][2])
     want = []
     for p, r in enumerate(rows):

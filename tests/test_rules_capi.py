@@ -114,7 +114,7 @@ def test_rules_struct_errors_the_python_helper_cannot_build(pkg):
 
 
 def test_rules_kernels_use_no_scratch(pkg, tmp_path):
-    """rules_rows_kernel and beam_given_rows_kernel (every instantiation): the kernel descriptors in obj/engine.o, read as test_beam_capi.py reads
+    """rules_rows_kernel and beam_group_rows_kernel over processed log-probabilities (<8 / 16 / 32, true>): the kernel descriptors in obj/engine.o, read as test_beam_capi.py reads
     the beam kernels'."""
     llvm = "/opt/rocm/lib/llvm/bin"
     if not (os.path.exists(llvm + "/clang-offload-bundler") and shutil.which("objcopy")):
@@ -132,7 +132,7 @@ def test_rules_kernels_use_no_scratch(pkg, tmp_path):
         if m:
             name = m.group(1)
         m = re.match(r"\s+\.private_segment_fixed_size:\s+(\d+)", line)
-        if m and name and re.search(r"rules_rows_kernel|beam_given_rows_kernel", name):
+        if m and name and re.search(r"rules_rows_kernel|beam_group_rows_kernelILi\d+ELb1E", name):
             assert int(m.group(1)) == 0, "%s uses %s bytes of scratch per lane" % (name, m.group(1))
             seen.add(name)
-    assert len(seen) == 4, seen      # rules_rows_kernel, beam_given_rows_kernel<8 / 16 / 32>
+    assert len(seen) == 4, seen      # rules_rows_kernel, beam_group_rows_kernel<8 / 16 / 32, true>
