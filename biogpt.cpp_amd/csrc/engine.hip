@@ -1023,244 +1023,322 @@ bool enqueue_xcols(biogpt_hip_ctx *c, int N, int t_max, bool streams = false) {
 // 80 columns, a decode step of many sequences the slim attention kernel from 48; one query beyond 256 keys spreads its head over the chip
 constexpr int MFMA_MIN_DECODE_COLS = 48, MFMA_MIN_PASS_COLS = 64, GROUPED_ATTN_MIN_COLS = 80, SLIM_ATTN_MIN_COLS = 48, SPLIT_ATTN_ABOVE_KEYS = 256;
 
-// batch: one column per sequence (decode step).  cols != null: the columns are prompt tokens of several sequences
-// (column states with seq_id / t_vis), no lm_head -- the caller gets the logits from the following decode step.
-// score (with all_rows): the logits of EVERY column into logits_all on the fastest lm_head for the model (biogpt_hip_score*);
-// prompt columns of several sequences (batch + cols) get them too.
-// hid: no logits at all (biogpt_hip_hidden / biogpt_hip_embed_batch) -- the first hid->layers layers only, then the final LayerNorm of every column
-// as f32 rows into hid->ln_out; ln_out == null: no LayerNorm either, the rows are the residual stream c->x itself.
+// ---- a forward pass, by name --------------------------------------------------------------------------------------------------------------
+// Hidden rows (biogpt_hip_hidden / biogpt_hip_embed_batch): the first `layers` layers only, then the final LayerNorm of every column as f32 rows
+// into ln_out; ln_out == null: no LayerNorm either, the rows are the residual stream c->x itself.
 struct HiddenStage { int layers; float *ln_out; };
-// shared (with batch + cols): the columns read their first SeqState::pad[0] K / V rows from the slot SeqState::pad[1] (attn_fast_kernel<.., SHARED>;
-// biogpt_hip_score_continuations); with score, only the columns from head_from on get logits (rows 0 .. N - head_from of logits_all): the
-// columns in front of them are prefix columns whose K / V rows alone matter.  head_from == N: no lm_head at all.
-bool enqueue_forward(biogpt_hip_ctx *c, int N, bool all_rows, int t_max, bool batch = false, const bgk::SeqState *cols = nullptr, bool score = false,
-                     const HiddenStage *hid = nullptr, bool shared = false, int head_from = 0) {
-    (void)hipGetLastError();   // a failed call of some OTHER context / API leaves its code behind; the checks below are about these launches
-    if (score || hid) all_rows = true;   // every row is needed: none of the launches that keep the activations on chip and compute the last row only
-    if (N < 1 || N > c->hp.n_positions) BG_FAIL(false, "internal: a pass of %d columns exceeds the %d-column activation scratch", N, c->hp.n_positions);
-    if (N == 1 && !batch && !all_rows && fused_decode_ok(c, t_max)) return enqueue_decode_fused(c, t_max, 1, 0);
-    if (N >= 2 && N <= 8 && !batch && !all_rows && xcols_usable(c, N, t_max)) return enqueue_xcols(c, N, t_max);
-    const auto &hp = c->hp;
-    const int D = hp.d_model, F = hp.d_ff, V = hp.n_vocab, H = hp.n_head, P = hp.n_positions;
-    const int dk = D / H;
-    hipStream_t st = c->stream;
-    // attention workgroup size: a thread owns up to ATTN_MAXK whole keys, so T <= 4 * threads
-    int attn_threads = 256;
-    while (attn_threads < 1024 && t_max > attn_threads) attn_threads <<= 1;  // ~1 key per thread when possible
-    if (attn_threads % dk != 0 || t_max > bgk::ATTN_MAXK * attn_threads)
-        BG_FAIL(false, "context of %d tokens / head size %d not supported by the attention kernel", t_max, dk);
 
-    // single-token fast chain: BioGPT-base shapes, block-quantized weights -> producer-side Q8 hand-offs
-    const int32_t wt = ftype_to_type(hp.ftype);
-    const bool chain = is_quantized(wt) && D == 1024 && F == 4096 && dk == 64 && t_max <= 1024;
-    const bool pchain = chain && (N > 1 || batch);   // several columns: LayerNorm+Q8 once per site (lnq_kernel), 8 columns per workgroup
-    // enough columns to fill 16-wide MFMA tiles: the chain runs on the int8 matrix cores from the row-tiled weight image
-    const bool mfma = pchain && N >= ((batch && !cols) ? MFMA_MIN_DECODE_COLS : MFMA_MIN_PASS_COLS) && c->tile_img != nullptr;
+// What enqueue_forward runs.  Only the named constructors build one, so a combination they do not name -- shared-prefix attention without column
+// states, "logits from column k on" outside scoring -- cannot reach the launch code.
+struct ForwardPass {
+    enum class Cols {       // where the columns come from, and whose K / V cache they use
+        Context,            // the context's own: c->state, memory_k / memory_v
+        PerSequence,        // one column per sequence (a decode step of many sequences): c->seq, bk / bv
+        Packed,             // packed column states (tokens of several sequences, each with its seq_id / t_vis): c->cols, bk / bv
+    };
+    enum class Rows {       // which rows are wanted at the end
+        Last,               // the last column's logits into c->logits, with the arg-max partials
+        AllGeneric,         // every column's logits into logits_all on the generic kernel (biogpt_hip_eval_all)
+        All,                // every column's logits into logits_all on the fastest lm_head for the model: LayerNorm+Q8 once, then the 8-column / matrix-core
+                            // lm_head where the many-column chain applies, the generic kernel otherwise (biogpt_hip_score*, the decode steps of many sequences)
+        None,               // none: only the K / V rows matter (the caller gets the logits from the following decode step)
+        Hidden,             // no logits at all: `hid`
+    };
+    int n_cols, t_max;
+    Cols cols;
+    Rows rows;
+    HiddenStage hid;        // Rows::Hidden
+    // Packed + All only (biogpt_hip_score_continuations): the columns read their first SeqState::pad[0] K / V rows from the slot SeqState::pad[1]
+    // (attn_fast_kernel<.., SHARED>), and only the columns from head_from on get logits (rows 0 .. n_cols - head_from of logits_all): the columns in
+    // front of them are prefix columns whose K / V rows alone matter
+    bool shared_prefix;
+    int head_from;
+
+    // the context's own columns
+    static ForwardPass last_row(int n, int t_max) { return {n, t_max, Cols::Context, Rows::Last}; }
+    static ForwardPass every_row(int n, int t_max) { return {n, t_max, Cols::Context, Rows::AllGeneric}; }
+    static ForwardPass scored(int n, int t_max) { return {n, t_max, Cols::Context, Rows::All}; }
+    static ForwardPass hidden(int n, int t_max, HiddenStage hs) { return {n, t_max, Cols::Context, Rows::Hidden, hs}; }
+    // one decode step of n_seqs sequences, every sequence's row
+    static ForwardPass decode_step(int n_seqs, int t_max) { return {n_seqs, t_max, Cols::PerSequence, Rows::All}; }
+    // packed columns (c->cols)
+    static ForwardPass packed_prompts(int n, int t_max) { return {n, t_max, Cols::Packed, Rows::None}; }
+    static ForwardPass packed_scored(int n, int t_max) { return {n, t_max, Cols::Packed, Rows::All}; }
+    static ForwardPass packed_hidden(int n, int t_max, HiddenStage hs) { return {n, t_max, Cols::Packed, Rows::Hidden, hs}; }
+    // the first n_prefix columns are prefix columns (all of them: no lm_head at all), the others read the prefix in place
+    static ForwardPass packed_continuations(int n, int t_max, int n_prefix) {
+        return {n, t_max, Cols::Packed, n_prefix < n ? Rows::All : Rows::None, HiddenStage{0, nullptr}, true, n_prefix < n ? n_prefix : 0};
+    }
+
+private:
+    ForwardPass(int n, int t, Cols c, Rows r, HiddenStage h = HiddenStage{0, nullptr}, bool shared = false, int from = 0)
+        : n_cols(n), t_max(t), cols(c), rows(r), hid(h), shared_prefix(shared), head_from(from) {}
+};
+
+// what the launches of one pass share: derived once from the pass and the model (enqueue_forward)
+struct PassLaunch {
+    biogpt_hip_ctx *c;
+    const ForwardPass &pass;
+    hipStream_t st;
+    int N, D, F, V, H, P, dk;
+    int attn_threads;               // attention workgroup size of the generic kernel
+    bool chain, pchain, mfma;       // the single-token fast chain; its many-column form; on the int8 matrix cores
+    int q81;
+    const bgk::SeqState *seq;       // column states of a pass over the per-sequence caches (null: the context's own columns)
+    int col_mode;                   // 1: packed columns
+    int64_t seq_stride;
+    float *kroot, *vroot;
     bgk::DevMatrix img;
-    auto tile = [&](const MatSlot &m) -> const bgk::DevMatrix * { if (!mfma) return nullptr; img = tile_matrix(c, m); return &img; };
-    if (batch && !chain) BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
-    if (shared && !(batch && cols)) BG_FAIL(false, "internal: shared-prefix attention needs column states");
-    if (head_from < 0 || head_from > N || (head_from > 0 && !(shared && score))) BG_FAIL(false, "internal: head_from (%d) of a pass of %d columns", head_from, N);
-    const int64_t seq_stride = (int64_t)hp.n_layer * P * D;
-    float *const kroot = batch ? c->bk : c->memory_k;
-    float *const vroot = batch ? c->bv : c->memory_v;
-    const int q81 = (wt == T_Q4_1 || wt == T_Q5_1) ? 1 : 0;
+    const bgk::DevMatrix *tile(const MatSlot &m) { if (!mfma) return nullptr; img = tile_matrix(c, m); return &img; }
+};
 
-    // a decode step of 2 .. 8 sequences while the caller (biogpt_hip_generate_greedy_batch) holds the device's pipeline slot: embedding + all layers as ONE launch,
-    // one sequence per XCD (kernels_xcols.hip.h, streams mode); the rows below on its output
-    const bool xc_streams = batch && !cols && c->xc_batch != 0 && t_max <= 256 && xcols_prepare(c, N, t_max);
-    if (xc_streams) { if (!enqueue_xcols(c, N, t_max, true)) return false; }
-    else
-    hipLaunchKernelGGL(bgk::embed_kernel, dim3((D + 255) / 256, N), dim3(256), 0, st,
-                       dev_matrix(c, c->plan.embed_tokens), dev_matrix(c, c->plan.embed_pos), c->state,
-                       sqrtf((float)D), c->x, D, batch ? (cols ? cols : c->seq) : nullptr);
-    // a single token of a float-weight file: all layers as ONE persistent launch (kernels_fpipe.hip.h) on the embedding the launch above left in c->x
-    const bool fp_one = N == 1 && !batch && !all_rows && !chain &&
-                        (c->fp_force >= 0 ? (c->fp_force == 1 && c->fp_state == 1 && t_max <= bgk::FP_TMAX) : fpipe_usable(c, t_max));
-    if (fp_one && !enqueue_fpipe(c)) return false;
-    const int n_run = hid ? hid->layers : hp.n_layer;
-    for (int l = 0; l < n_run && !xc_streams && !fp_one; l++) {
-        const LayerSlots &L = c->plan.layers[(size_t)l];
-        {  // LN0 + fused q/k/v projection + bias + Q scale + KV append
-            const MvShape s = mv_shape(L.qkv.type, L.qkv.M, L.qkv.K);
-            bgk::MatvecParams p = mv_base(c, L.qkv, s);
-            p.x = c->x; p.ldx = D; p.N = N;
-            p.ln_w = dev_vec(c, L.ln0_w); p.ln_b = dev_vec(c, L.ln0_b);
-            p.bias = dev_vec(c, L.qkv_b);
-            p.q_out = c->q;
-            p.kcache = kroot + (size_t)l * P * D;
-            p.vcache = vroot + (size_t)l * P * D;
-            if (batch) { p.seq = cols ? cols : c->seq; p.col_mode = cols ? 1 : 0; p.kv_seq_stride = seq_stride; }
-            p.q_scale = 1.0f / sqrtf((float)dk);
-            if (pchain) {
-                HIP_TRY(false, launch_lnq(c, c->x, N, L.ln0_w, L.ln0_b, q81, st));
-                p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
-                HIP_TRY(false, launch_chain(CHAIN_QKV_Q8, p, st, tile(L.qkv)));
-            } else {
-                HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_QKV>(c->opt, p, s, st)));
+// attn_fast_kernel's launch table: 4 lanes per key, 16 prefetched V rows per lane; SHARED: the instantiations that take a column's first rows from the shared slot
+template <bool SHARED>
+void launch_attn_fast(const bgk::AttnParams &a, bool slim, int H, int N, hipStream_t st) {
+    const int t64 = (a.t_cap + 63) & ~63;
+    // slim: many (sequence, head) workgroups: throughput over latency -- one lane quad per 4 keys (4 key passes), a
+    // quarter of the threads, four times as many workgroups resident per compute unit
+    if (slim) hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, SHARED>), dim3(H, N), dim3(std::max(256, t64)), 0, st, a);
+    else if (a.t_cap <= 256) hipLaunchKernelGGL((bgk::attn_fast_kernel<1, true, SHARED>), dim3(H, N), dim3(4 * t64), 0, st, a);
+    else if (a.t_cap <= 512) hipLaunchKernelGGL((bgk::attn_fast_kernel<2, false, SHARED>), dim3(H, N), dim3(1024), 0, st, a);
+    else hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, SHARED>), dim3(H, N), dim3(1024), 0, st, a);
+}
+
+// the attention launch(es) of layer l
+bool enqueue_attention(PassLaunch &k, int l) {
+    biogpt_hip_ctx *c = k.c;
+    const int N = k.N, D = k.D, H = k.H, P = k.P, dk = k.dk, t_max = k.pass.t_max;
+    const bool batch = k.seq != nullptr;
+    hipStream_t st = k.st;
+    bgk::AttnParams a{};
+    a.q = c->q; a.kcache = k.kroot + (size_t)l * P * D; a.vcache = k.vroot + (size_t)l * P * D;
+    if (batch) { a.seq = k.seq; a.col_mode = k.col_mode; a.kv_seq_stride = k.seq_stride; }
+    a.out = c->att; a.st = c->state;
+    a.exp_tab = reinterpret_cast<const uint16_t *>(c->arena + c->plan.exp_tab);
+    a.N = N; a.D = D; a.dk = dk; a.P = P;
+    a.dbg = c->opt.dbg; a.tstamp = c->tstamp;
+    a.q81 = k.q81;
+    if (k.chain) { a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; }
+    if (!(dk == 64 && t_max <= 1024)) {
+        hipLaunchKernelGGL(bgk::attn_kernel, dim3(H, N), dim3(k.attn_threads), bgk::attn_smem_bytes(P, dk, k.attn_threads), st, a);
+        return true;
+    }
+    if (!batch && N >= GROUPED_ATTN_MIN_COLS) {
+        // a pass of many query columns: register-tiled kernel, 16 queries per workgroup share every K / V row they load
+        a.t_cap = std::min(P, t_max);
+        // (the tile kernel addresses a thread's four consecutive key rows from ONE base clamped to P - 4: that is only their own rows when 4 | P and P >= 4;
+        //  any other table size takes the grouped kernel, 8 queries per workgroup, which clamps row by row)
+        if ((P & 3) == 0 && P >= 4) {
+            // up to 640 keys the K / V rows of the two MAC loops travel through a ring in LDS, two steps ahead (global_load_lds); beyond, the ring has no room
+            // beside the scores in a 2-workgroups-per-compute-unit footprint: loads at the top of each step
+            const bool dma = bgk::attn_tile_dma_ok(a.t_cap);
+            const size_t smb = bgk::attn_tile_smem_bytes<16>(a.t_cap);
+            const void *fn = dma ? reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, true>) : reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, false>);
+            if (smb > 64 * 1024 && !c->lds_attr_done.count(fn)) {
+                HIP_TRY(false, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bgk::attn_tile_smem_bytes<16>(P)));
+                c->lds_attr_done.insert(fn);
             }
+            if (dma) hipLaunchKernelGGL((bgk::attn_tile_kernel<16, true>), dim3(H, (N + 15) / 16), dim3(512), smb, st, a);
+            else hipLaunchKernelGGL((bgk::attn_tile_kernel<16, false>), dim3(H, (N + 15) / 16), dim3(512), smb, st, a);
+        } else {
+            hipLaunchKernelGGL((bgk::attn_group_kernel<8>), dim3(H, (N + 7) / 8), dim3(512), bgk::attn_group_smem_bytes(a.t_cap), st, a);
         }
-        {  // attention
-            bgk::AttnParams a{};
-            a.q = c->q; a.kcache = kroot + (size_t)l * P * D; a.vcache = vroot + (size_t)l * P * D;
-            if (batch) { a.seq = cols ? cols : c->seq; a.col_mode = cols ? 1 : 0; a.kv_seq_stride = seq_stride; }
-            a.out = c->att; a.st = c->state;
-            a.exp_tab = reinterpret_cast<const uint16_t *>(c->arena + c->plan.exp_tab);
-            a.N = N; a.D = D; a.dk = dk; a.P = P;
-            a.dbg = c->opt.dbg; a.tstamp = c->tstamp;
-            a.q81 = q81;
-            if (chain) { a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; }
-            if (!batch && dk == 64 && t_max <= 1024 && N >= GROUPED_ATTN_MIN_COLS) {
-                // a pass of many query columns: register-tiled kernel, 16 queries per workgroup share every K / V row they load
-                a.t_cap = std::min(P, t_max);
-                // (the tile kernel addresses a thread's four consecutive key rows from ONE base clamped to P - 4: that is only their own rows when 4 | P and P >= 4;
-                //  any other table size takes the grouped kernel, 8 queries per workgroup, which clamps row by row)
-                if ((P & 3) == 0 && P >= 4) {
-                    // up to 640 keys the K / V rows of the two MAC loops travel through a ring in LDS, two steps ahead (global_load_lds); beyond, the ring has no room
-                    // beside the scores in a 2-workgroups-per-compute-unit footprint: loads at the top of each step
-                    const bool dma = bgk::attn_tile_dma_ok(a.t_cap);
-                    const size_t smb = bgk::attn_tile_smem_bytes<16>(a.t_cap);
-                    const void *fn = dma ? reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, true>) : reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, false>);
-                    if (smb > 64 * 1024 && !c->lds_attr_done.count(fn)) {
-                        HIP_TRY(false, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bgk::attn_tile_smem_bytes<16>(P)));
-                        c->lds_attr_done.insert(fn);
-                    }
-                    if (dma) hipLaunchKernelGGL((bgk::attn_tile_kernel<16, true>), dim3(H, (N + 15) / 16), dim3(512), smb, st, a);
-                    else hipLaunchKernelGGL((bgk::attn_tile_kernel<16, false>), dim3(H, (N + 15) / 16), dim3(512), smb, st, a);
-                } else {
-                    hipLaunchKernelGGL((bgk::attn_group_kernel<8>), dim3(H, (N + 7) / 8), dim3(512), bgk::attn_group_smem_bytes(a.t_cap), st, a);
-                }
-            } else if (dk == 64 && t_max <= 1024) {
-                // loads are bounded by t_cap (= P when the table is not a multiple of 64; the workgroup stays whole
-                // waves); 4 lanes per key, 16 prefetched V rows per lane
-                a.t_cap = std::min(P, (t_max + 63) & ~63);
-                if (N == 1 && !batch && a.t_cap > SPLIT_ATTN_ABOVE_KEYS) {
-                    // long context, one query: spread the head's keys over the chip (three dependent launches)
-                    a.sp_scores = c->sp_scores; a.sp_max = c->sp_max; a.sp_pv = c->sp_pv;
-                    a.n_split = (a.t_cap + bgk::SPLIT_KEYS - 1) / bgk::SPLIT_KEYS;
-                    if (a.n_split > bgk::SPLIT_MAX) BG_FAIL(false, "internal: %d key ranges exceed the %d the split attention kernels hold", a.n_split, bgk::SPLIT_MAX);
-                    hipLaunchKernelGGL(bgk::attn_split_scores_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
-                    hipLaunchKernelGGL(bgk::attn_split_pv_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
-                    hipLaunchKernelGGL(bgk::attn_split_combine_kernel, dim3(H), dim3(64), 0, st, a);
-                } else if (shared) {
-                    // the table below, on the instantiations that take a column's first rows from the shared slot
-                    const int t64 = (a.t_cap + 63) & ~63;
-                    if (N >= SLIM_ATTN_MIN_COLS) hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, true>), dim3(H, N), dim3(std::max(256, t64)), 0, st, a);
-                    else if (a.t_cap <= 256) hipLaunchKernelGGL((bgk::attn_fast_kernel<1, true, true>), dim3(H, N), dim3(4 * t64), 0, st, a);
-                    else if (a.t_cap <= 512) hipLaunchKernelGGL((bgk::attn_fast_kernel<2, false, true>), dim3(H, N), dim3(1024), 0, st, a);
-                    else hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, true>), dim3(H, N), dim3(1024), 0, st, a);
-                } else if (batch && N >= SLIM_ATTN_MIN_COLS) {
-                    // many (sequence, head) workgroups: throughput over latency -- one lane quad per 4 keys (4 key passes), a
-                    // quarter of the threads, four times as many workgroups resident per compute unit
-                    const int t64 = (a.t_cap + 63) & ~63;
-                    hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false>), dim3(H, N), dim3(std::max(256, t64)), 0, st, a);
-                } else if (a.t_cap <= 256) {
-                    hipLaunchKernelGGL((bgk::attn_fast_kernel<1, true>), dim3(H, N), dim3(4 * ((a.t_cap + 63) & ~63)), 0, st, a);
-                } else if (a.t_cap <= 512) {
-                    hipLaunchKernelGGL((bgk::attn_fast_kernel<2, false>), dim3(H, N), dim3(1024), 0, st, a);
-                } else {
-                    hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false>), dim3(H, N), dim3(1024), 0, st, a);
-                }
-            } else {
-                hipLaunchKernelGGL(bgk::attn_kernel, dim3(H, N), dim3(attn_threads), bgk::attn_smem_bytes(P, dk, attn_threads), st, a);
-            }
-        }
-        {  // out_proj + bias + residual
-            const MvShape s = mv_shape(L.o.type, L.o.M, L.o.K);
-            bgk::MatvecParams p = mv_base(c, L.o, s);
-            p.x = c->att; p.ldx = D; p.N = N;
-            p.bias = dev_vec(c, L.o_b);
-            p.resid = c->x; p.ldr = D; p.out = c->x1; p.ldo = D;
-            if (chain) {
-                p.aq_q = c->aq_q[0]; p.aq_d = c->aq_d[0]; p.aq_s = c->aq_s[0];
-                HIP_TRY(false, launch_chain(CHAIN_OPROJ, p, st, tile(L.o)));
-            } else {
-                HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
-            }
-        }
-        {  // LN1 + fc1 + bias + GELU
-            const MvShape s = mv_shape(L.fc1.type, L.fc1.M, L.fc1.K);
-            bgk::MatvecParams p = mv_base(c, L.fc1, s);
-            p.x = c->x1; p.ldx = D; p.N = N;
-            p.ln_w = dev_vec(c, L.ln1_w); p.ln_b = dev_vec(c, L.ln1_b);
-            p.bias = dev_vec(c, L.fc1_b);
-            p.out = c->h; p.ldo = F;
-            if (pchain) {
-                HIP_TRY(false, launch_lnq(c, c->x1, N, L.ln1_w, L.ln1_b, q81, st));
-                p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
-                p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
-                HIP_TRY(false, launch_chain(CHAIN_FC1_Q8, p, st, tile(L.fc1)));
-            } else if (chain) {
-                p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
-                HIP_TRY(false, launch_chain(CHAIN_FC1, p, st));
-            } else {
-                HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_GELU>(c->opt, p, s, st)));
-            }
-        }
-        {  // fc2 + bias + residual
-            const MvShape s = mv_shape(L.fc2.type, L.fc2.M, L.fc2.K);
-            bgk::MatvecParams p = mv_base(c, L.fc2, s);
-            p.x = c->h; p.ldx = F; p.N = N;
-            p.bias = dev_vec(c, L.fc2_b);
-            p.resid = c->x1; p.ldr = D; p.out = c->x; p.ldo = D;
-            if (chain) {
-                p.aq_q = c->aq_q[1]; p.aq_d = c->aq_d[1]; p.aq_s = c->aq_s[1];
-                HIP_TRY(false, launch_chain(CHAIN_FC2, p, st, tile(L.fc2)));
-            } else {
-                HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
-            }
+        return true;
+    }
+    // loads are bounded by t_cap (= P when the table is not a multiple of 64; the workgroup stays whole waves)
+    a.t_cap = std::min(P, (t_max + 63) & ~63);
+    if (N == 1 && !batch && a.t_cap > SPLIT_ATTN_ABOVE_KEYS) {
+        // long context, one query: spread the head's keys over the chip (three dependent launches)
+        a.sp_scores = c->sp_scores; a.sp_max = c->sp_max; a.sp_pv = c->sp_pv;
+        a.n_split = (a.t_cap + bgk::SPLIT_KEYS - 1) / bgk::SPLIT_KEYS;
+        if (a.n_split > bgk::SPLIT_MAX) BG_FAIL(false, "internal: %d key ranges exceed the %d the split attention kernels hold", a.n_split, bgk::SPLIT_MAX);
+        hipLaunchKernelGGL(bgk::attn_split_scores_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(bgk::attn_split_pv_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(bgk::attn_split_combine_kernel, dim3(H), dim3(64), 0, st, a);
+        return true;
+    }
+    const bool slim = batch && N >= SLIM_ATTN_MIN_COLS;
+    if (k.pass.shared_prefix) launch_attn_fast<true>(a, slim, H, N, st);
+    else launch_attn_fast<false>(a, slim, H, N, st);
+    return true;
+}
+
+// layer l on the chain of launches: q/k/v, attention, out_proj, fc1, fc2
+bool enqueue_layer(PassLaunch &k, int l) {
+    biogpt_hip_ctx *c = k.c;
+    const int N = k.N, D = k.D, F = k.F, P = k.P;
+    hipStream_t st = k.st;
+    const LayerSlots &L = c->plan.layers[(size_t)l];
+    {  // LN0 + fused q/k/v projection + bias + Q scale + KV append
+        const MvShape s = mv_shape(L.qkv.type, L.qkv.M, L.qkv.K);
+        bgk::MatvecParams p = mv_base(c, L.qkv, s);
+        p.x = c->x; p.ldx = D; p.N = N;
+        p.ln_w = dev_vec(c, L.ln0_w); p.ln_b = dev_vec(c, L.ln0_b);
+        p.bias = dev_vec(c, L.qkv_b);
+        p.q_out = c->q;
+        p.kcache = k.kroot + (size_t)l * P * D;
+        p.vcache = k.vroot + (size_t)l * P * D;
+        if (k.seq) { p.seq = k.seq; p.col_mode = k.col_mode; p.kv_seq_stride = k.seq_stride; }
+        p.q_scale = 1.0f / sqrtf((float)k.dk);
+        if (k.pchain) {
+            HIP_TRY(false, launch_lnq(c, c->x, N, L.ln0_w, L.ln0_b, k.q81, st));
+            p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
+            HIP_TRY(false, launch_chain(CHAIN_QKV_Q8, p, st, k.tile(L.qkv)));
+        } else {
+            HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_QKV>(c->opt, p, s, st)));
         }
     }
-    // the final stage, LayerNorm + lm_head: which rows, and on which kernels
-    enum class Final { None, LastRow, AllRows, AllRowsQ8, Hidden };
-    const Final fin = hid ? Final::Hidden                                 // f32 rows in front of the lm_head (kernels_embed.hip.h)
-                    : (batch && cols && (!score || head_from == N)) ? Final::None   // prompt columns: only the KV rows matter
-                    : (batch || (score && pchain)) ? Final::AllRowsQ8     // LayerNorm+Q8 once, then the 8-column / matrix-core lm_head
-                    : (all_rows || score) ? Final::AllRows                // every row on the generic kernel (eval_all; scoring of the other models)
-                    : Final::LastRow;
-    if (fin == Final::None) return true;
-    if (fin == Final::Hidden) {
-        if (!hid->ln_out) return true;
+    if (!enqueue_attention(k, l)) return false;
+    {  // out_proj + bias + residual
+        const MvShape s = mv_shape(L.o.type, L.o.M, L.o.K);
+        bgk::MatvecParams p = mv_base(c, L.o, s);
+        p.x = c->att; p.ldx = D; p.N = N;
+        p.bias = dev_vec(c, L.o_b);
+        p.resid = c->x; p.ldr = D; p.out = c->x1; p.ldo = D;
+        if (k.chain) {
+            p.aq_q = c->aq_q[0]; p.aq_d = c->aq_d[0]; p.aq_s = c->aq_s[0];
+            HIP_TRY(false, launch_chain(CHAIN_OPROJ, p, st, k.tile(L.o)));
+        } else {
+            HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
+        }
+    }
+    {  // LN1 + fc1 + bias + GELU
+        const MvShape s = mv_shape(L.fc1.type, L.fc1.M, L.fc1.K);
+        bgk::MatvecParams p = mv_base(c, L.fc1, s);
+        p.x = c->x1; p.ldx = D; p.N = N;
+        p.ln_w = dev_vec(c, L.ln1_w); p.ln_b = dev_vec(c, L.ln1_b);
+        p.bias = dev_vec(c, L.fc1_b);
+        p.out = c->h; p.ldo = F;
+        if (k.pchain) {
+            HIP_TRY(false, launch_lnq(c, c->x1, N, L.ln1_w, L.ln1_b, k.q81, st));
+            p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
+            p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
+            HIP_TRY(false, launch_chain(CHAIN_FC1_Q8, p, st, k.tile(L.fc1)));
+        } else if (k.chain) {
+            p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
+            HIP_TRY(false, launch_chain(CHAIN_FC1, p, st));
+        } else {
+            HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_GELU>(c->opt, p, s, st)));
+        }
+    }
+    {  // fc2 + bias + residual
+        const MvShape s = mv_shape(L.fc2.type, L.fc2.M, L.fc2.K);
+        bgk::MatvecParams p = mv_base(c, L.fc2, s);
+        p.x = c->h; p.ldx = F; p.N = N;
+        p.bias = dev_vec(c, L.fc2_b);
+        p.resid = c->x1; p.ldr = D; p.out = c->x; p.ldo = D;
+        if (k.chain) {
+            p.aq_q = c->aq_q[1]; p.aq_d = c->aq_d[1]; p.aq_s = c->aq_s[1];
+            HIP_TRY(false, launch_chain(CHAIN_FC2, p, st, k.tile(L.fc2)));
+        } else {
+            HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
+        }
+    }
+    return true;
+}
+
+// the final stage of a pass on the residual stream c->x: the rows the pass names, LayerNorm + lm_head (or the hidden rows in front of it)
+bool enqueue_final(PassLaunch &k) {
+    using Rows = ForwardPass::Rows;
+    biogpt_hip_ctx *c = k.c;
+    const int N = k.N, D = k.D, V = k.V;
+    hipStream_t st = k.st;
+    const Rows rows = k.pass.rows;
+    if (rows == Rows::None) return true;   // prompt columns: only the KV rows matter
+    if (rows == Rows::Hidden) {            // f32 rows in front of the lm_head (kernels_embed.hip.h)
+        float *const ln_out = k.pass.hid.ln_out;
+        if (!ln_out) return true;
         const float *lw = dev_vec(c, c->plan.ln_w), *lb = dev_vec(c, c->plan.ln_b);
-        if (D == 1024) hipLaunchKernelGGL((bgk::ln_rows_kernel<1024>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / 1024.0, hid->ln_out);
-        else hipLaunchKernelGGL((bgk::ln_rows_kernel<0>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / (double)D, hid->ln_out);
+        if (D == 1024) hipLaunchKernelGGL((bgk::ln_rows_kernel<1024>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / 1024.0, ln_out);
+        else hipLaunchKernelGGL((bgk::ln_rows_kernel<0>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / (double)D, ln_out);
         HIP_TRY(false, hipGetLastError());
         return true;
     }
-    if (fin == Final::AllRowsQ8) {  // every column needs its logits row: LayerNorm+Q8 once, then the 8-column mat-vec (matrix cores from 64 columns)
-        const MatSlot &m = c->plan.lm_head;
-        const MvShape s = mv_shape(m.type, m.M, m.K);
-        bgk::MatvecParams p = mv_base(c, m, s);
+    const MatSlot &m = c->plan.lm_head;
+    const MvShape s = mv_shape(m.type, m.M, m.K);
+    bgk::MatvecParams p = mv_base(c, m, s);
+    if (rows == Rows::All && k.pchain) {  // every column needs its logits row: LayerNorm+Q8 once, then the 8-column mat-vec (matrix cores from 64 columns)
         // head_from > 0: the kernel a pass of n_rows columns alone would take.  Below 64 rows that is the 8-column VALU kernel, where score_batch of
         // the concatenation (64 columns or more) takes the matrix cores: the bit-for-bit promise of biogpt_hip_score_continuations rests on the two
         // lm_head kernels giving IDENTICAL f32 rows (exact int32 block sums, the same f32 scaling and block order in both) -- as score_batch ==
         // score already does across pass sizes.  A change to either kernel's arithmetic breaks that equality (tests/test_gpu_prefix.py, test_gpu_score.py).
-        const int n_rows = N - head_from;
-        HIP_TRY(false, launch_lnq(c, c->x + (size_t)head_from * D, n_rows, c->plan.ln_w, c->plan.ln_b, q81, st));
+        const int head_from = k.pass.head_from, n_rows = N - head_from;
+        HIP_TRY(false, launch_lnq(c, c->x + (size_t)head_from * D, n_rows, c->plan.ln_w, c->plan.ln_b, k.q81, st));
         p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
         p.N = n_rows; p.out = c->logits_all; p.ldo = V;
-        HIP_TRY(false, launch_chain(CHAIN_LMHEAD_Q8, p, st, (head_from > 0 && n_rows < MFMA_MIN_PASS_COLS) ? nullptr : tile(c->plan.lm_head)));
+        HIP_TRY(false, launch_chain(CHAIN_LMHEAD_Q8, p, st, (head_from > 0 && n_rows < MFMA_MIN_PASS_COLS) ? nullptr : k.tile(c->plan.lm_head)));
         return true;
     }
-    {  // final LayerNorm + lm_head; only the rows that are returned (F8)
-        const MatSlot &m = c->plan.lm_head;
-        const bool rows = fin == Final::AllRows;
-        const MvShape s = mv_shape(m.type, m.M, m.K);
-        bgk::MatvecParams p = mv_base(c, m, s);
-        p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
-        p.ldx = D; p.ldo = V;
-        if (rows) {
-            p.x = c->x; p.N = N; p.out = c->logits_all;
-        } else {
-            p.x = c->x + (size_t)(N - 1) * D; p.N = 1; p.out = c->logits;
-            if (s.grid > c->pmax_cap) BG_FAIL(false, "internal: arg-max partial buffer too small (%d > %d)", s.grid, c->pmax_cap);
-            p.pmax_val = c->pmax_val; p.pmax_idx = c->pmax_idx;
-        }
-        int lm_grid = 0;
-        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, st, &lm_grid)));
-        if (!rows) c->lm_blocks = lm_grid;
+    // final LayerNorm + lm_head on the generic kernel; only the rows that are returned (F8)
+    p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
+    p.ldx = D; p.ldo = V;
+    if (rows != Rows::Last) {   // eval_all; scoring of the other models
+        p.x = c->x; p.N = N; p.out = c->logits_all;
+    } else {
+        p.x = c->x + (size_t)(N - 1) * D; p.N = 1; p.out = c->logits;
+        if (s.grid > c->pmax_cap) BG_FAIL(false, "internal: arg-max partial buffer too small (%d > %d)", s.grid, c->pmax_cap);
+        p.pmax_val = c->pmax_val; p.pmax_idx = c->pmax_idx;
     }
+    int lm_grid = 0;
+    HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, st, &lm_grid)));
+    if (rows == Rows::Last) c->lm_blocks = lm_grid;
     return true;
+}
+
+// One forward pass: the embedding, the layers, the final stage -- on the launch that fits the pass (the fused single-token launch and the 2 .. 8-column
+// chunk launch for the context's own columns with the last row wanted; the column-per-XCD launch for a decode step of 2 .. 8 sequences; the persistent
+// float launch for one token of a float file), otherwise five launches per layer.
+bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
+    using Cols = ForwardPass::Cols;
+    using Rows = ForwardPass::Rows;
+    (void)hipGetLastError();   // a failed call of some OTHER context / API leaves its code behind; the checks below are about these launches
+    const int N = pass.n_cols, t_max = pass.t_max;
+    // every row but the last is needed elsewhere: none of the launches that keep the activations on chip and compute the last row only
+    const bool last_own = pass.cols == Cols::Context && pass.rows == Rows::Last;
+    if (N < 1 || N > c->hp.n_positions) BG_FAIL(false, "internal: a pass of %d columns exceeds the %d-column activation scratch", N, c->hp.n_positions);
+    if (N == 1 && last_own && fused_decode_ok(c, t_max)) return enqueue_decode_fused(c, t_max, 1, 0);
+    if (N >= 2 && N <= 8 && last_own && xcols_usable(c, N, t_max)) return enqueue_xcols(c, N, t_max);
+    const auto &hp = c->hp;
+    const bool batch = pass.cols != Cols::Context;
+    PassLaunch k{c, pass, c->stream};
+    k.N = N; k.D = hp.d_model; k.F = hp.d_ff; k.V = hp.n_vocab; k.H = hp.n_head; k.P = hp.n_positions;
+    k.dk = k.D / k.H;
+    // attention workgroup size: a thread owns up to ATTN_MAXK whole keys, so T <= 4 * threads
+    k.attn_threads = 256;
+    while (k.attn_threads < 1024 && t_max > k.attn_threads) k.attn_threads <<= 1;  // ~1 key per thread when possible
+    if (k.attn_threads % k.dk != 0 || t_max > bgk::ATTN_MAXK * k.attn_threads)
+        BG_FAIL(false, "context of %d tokens / head size %d not supported by the attention kernel", t_max, k.dk);
+
+    // single-token fast chain: BioGPT-base shapes, block-quantized weights -> producer-side Q8 hand-offs
+    const int32_t wt = ftype_to_type(hp.ftype);
+    k.chain = is_quantized(wt) && k.D == 1024 && k.F == 4096 && k.dk == 64 && t_max <= 1024;
+    k.pchain = k.chain && (N > 1 || batch);   // several columns: LayerNorm+Q8 once per site (lnq_kernel), 8 columns per workgroup
+    // enough columns to fill 16-wide MFMA tiles: the chain runs on the int8 matrix cores from the row-tiled weight image
+    k.mfma = k.pchain && N >= (pass.cols == Cols::PerSequence ? MFMA_MIN_DECODE_COLS : MFMA_MIN_PASS_COLS) && c->tile_img != nullptr;
+    if (batch && !k.chain) BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    k.seq = pass.cols == Cols::Packed ? c->cols : (batch ? c->seq : nullptr);
+    k.col_mode = pass.cols == Cols::Packed ? 1 : 0;
+    k.seq_stride = (int64_t)hp.n_layer * k.P * k.D;
+    k.kroot = batch ? c->bk : c->memory_k;
+    k.vroot = batch ? c->bv : c->memory_v;
+    k.q81 = (wt == T_Q4_1 || wt == T_Q5_1) ? 1 : 0;
+
+    // a decode step of 2 .. 8 sequences while the caller (biogpt_hip_generate_greedy_batch) holds the device's pipeline slot: embedding + all layers as ONE launch,
+    // one sequence per XCD (kernels_xcols.hip.h, streams mode); the rows below on its output
+    const bool xc_streams = pass.cols == Cols::PerSequence && c->xc_batch != 0 && t_max <= 256 && xcols_prepare(c, N, t_max);
+    if (xc_streams) { if (!enqueue_xcols(c, N, t_max, true)) return false; }
+    else
+    hipLaunchKernelGGL(bgk::embed_kernel, dim3((k.D + 255) / 256, N), dim3(256), 0, k.st,
+                       dev_matrix(c, c->plan.embed_tokens), dev_matrix(c, c->plan.embed_pos), c->state,
+                       sqrtf((float)k.D), c->x, k.D, k.seq);
+    // a single token of a float-weight file: all layers as ONE persistent launch (kernels_fpipe.hip.h) on the embedding the launch above left in c->x
+    const bool fp_one = N == 1 && last_own && !k.chain &&
+                        (c->fp_force >= 0 ? (c->fp_force == 1 && c->fp_state == 1 && t_max <= bgk::FP_TMAX) : fpipe_usable(c, t_max));
+    if (fp_one && !enqueue_fpipe(c)) return false;
+    const int n_run = pass.rows == Rows::Hidden ? pass.hid.layers : hp.n_layer;
+    for (int l = 0; l < n_run && !xc_streams && !fp_one; l++)
+        if (!enqueue_layer(k, l)) return false;
+    return enqueue_final(k);
 }
 
 bool enqueue_argmax(biogpt_hip_ctx *c, int n_eval) {
@@ -1590,7 +1668,7 @@ bool ensure_graph(biogpt_hip_ctx *c, int advance, int bucket, int pl) {
     const int tmax = bucket_tmax(c, bucket);
     c->fp_force = pl;
     bool ok = fused_decode_ok(c, tmax) ? enqueue_decode_fused(c, tmax, 2, advance, 0, -1, -1, 1, nullptr, nullptr, pl)
-                                       : (enqueue_forward(c, 1, false, tmax) && enqueue_argmax(c, advance));
+                                       : (enqueue_forward(c, ForwardPass::last_row(1, tmax)) && enqueue_argmax(c, advance));
     c->fp_force = -1;
     hipError_t e = hipStreamEndCapture(c->stream, &g);
     if (!ok) { if (g) (void)hipGraphDestroy(g); return false; }
@@ -1709,40 +1787,54 @@ int biogpt_hip_merge(const biogpt_hip_ctx *ctx, int32_t rank, const char **bytes
     return 0;
 }
 
-#include "engine_resident.inc"
-
-// low-latency wait for everything enqueued on the context's stream (the caller is blocked on this token anyway)
-static bool poll_stream(biogpt_hip_ctx *ctx) {
+// how a call waits for its stream: asleep in the runtime, or polling -- the low-latency wait of a caller that is blocked on this token anyway
+enum class Wait { Sleep, Poll };
+static bool drain_stream(biogpt_hip_ctx *ctx, Wait how) {
+    if (how == Wait::Sleep) { HIP_TRY(false, hipStreamSynchronize(ctx->stream)); return true; }
     for (;;) {
         const hipError_t q = hipStreamQuery(ctx->stream);
         if (q == hipSuccess) return true;
         if (q != hipErrorNotReady) HIP_TRY(false, q);
     }
 }
+// The end of a call that waits for its results: the stream has drained, so every mailbox slot sent has been read, and the pipeline says whether one of
+// its launches was disturbed (false: the call's outputs are garbage, last_error says why -- the entry points return -2)
+static bool wait_stream(biogpt_hip_ctx *ctx, Wait how = Wait::Sleep) {
+    if (!drain_stream(ctx, how)) return false;
+    ctx->mbox_synced = ctx->mbox_sent;
+    return xpipe_check(ctx);
+}
 
-// the k largest values of a row, descending, equal values: lower index first (topk_kernel's order) -- ONE pass: a block of 16 values is only looked at when its
-// maximum beats the current k-th value.  Returns how many were found (< k only when the row holds NaNs)
-static int host_topk(const float *row, int n, int k, float *vals, int32_t *ids) {
+#include "engine_resident.inc"
+
+// the k largest of the values offered so far, descending, equal values: lower index first when they are offered in index order (topk_kernel's order); NaNs are never taken
+struct TopkInsert {
+    float *vals; int32_t *ids; int k;
     int have = 0;
-    float thr = -INFINITY;
-    auto offer = [&](float v, int i) {
+    float thr = -INFINITY;      // the k-th value once k are held
+    void offer(float v, int i) {
         if ((have == k && !(v > thr)) || v != v) return;
         int pos = have < k ? have : k - 1;
         while (pos > 0 && vals[pos - 1] < v) { vals[pos] = vals[pos - 1]; ids[pos] = ids[pos - 1]; pos--; }
         vals[pos] = v; ids[pos] = i;
         if (have < k) have++;
         if (have == k) thr = vals[k - 1];
-    };
+    }
+};
+// the k largest values of a row -- ONE pass: a block of 16 values is only looked at when its maximum beats the current k-th value.  Returns how many were
+// found (< k only when the row holds NaNs)
+static int host_topk(const float *row, int n, int k, float *vals, int32_t *ids) {
+    TopkInsert top{vals, ids, k};
     int i = 0;
-    for (; i < n && have < k; i++) offer(row[i], i);
+    for (; i < n && top.have < k; i++) top.offer(row[i], i);
     for (; i + 16 <= n; i += 16) {
         float m = -INFINITY;      // (not row[i]: a NaN there would hide the block -- every comparison with it is false)
         for (int j = 0; j < 16; j++) m = row[i + j] > m ? row[i + j] : m;
-        if (m > thr)
-            for (int j = 0; j < 16; j++) offer(row[i + j], i + j);
+        if (m > top.thr)
+            for (int j = 0; j < 16; j++) top.offer(row[i + j], i + j);
     }
-    for (; i < n; i++) offer(row[i], i);
-    return have;
+    for (; i < n; i++) top.offer(row[i], i);
+    return top.have;
 }
 
 // The same selection when the launch has left the maxima of the row's 64-row blocks behind it (a resident launch): the k-th largest block maximum t0 is a lower
@@ -1762,22 +1854,31 @@ static int host_topk_blocks(const float *row, int n, int k, const float *bmax, i
         if (have_b < k) have_b++;
     }
     const float t0 = top[k - 1];
-    int have = 0;
-    float thr = -INFINITY;
+    TopkInsert sel{vals, ids, k};
     for (int b = 0; b < nblocks; b++) {
         if (!(bmax[b] >= t0)) continue;
         const int i0 = b * 64, i1 = std::min(n, i0 + 64);
-        for (int i = i0; i < i1; i++) {
-            const float v = row[i];
-            if ((have == k && !(v > thr)) || v != v) continue;
-            int pos = have < k ? have : k - 1;
-            while (pos > 0 && vals[pos - 1] < v) { vals[pos] = vals[pos - 1]; ids[pos] = ids[pos - 1]; pos--; }
-            vals[pos] = v; ids[pos] = i;
-            if (have < k) have++;
-            if (have == k) thr = vals[k - 1];
-        }
+        for (int i = i0; i < i1; i++) sel.offer(row[i], i);
     }
-    return have;
+    return sel.have;
+}
+
+// A replayed five-launch eval carries the sequence number its FIRST node fetched, forwarded by the last layer and the lm_head as they started: any other
+// number means that the result is not this call's (profiles/two_contexts_r4.txt, profiles/stale_row_r5.txt).  Repair: the device's replay counter is put
+// right and the call is repeated on eager launches (same tokens, same position: the K / V rows are written again with the same values); refetch() then
+// enqueues the fetch of the result again.  on_device: the row in question is the device's (biogpt_hip_eval_device), not the one returned to the caller.
+extern "C++" template <class Refetch>
+int repair_stale_row(biogpt_hip_ctx *ctx, const int32_t *tokens, int n, int n_past, uint32_t got, uint32_t want, bool on_device, Wait how, Refetch refetch) {
+    ctx->stale_rows++;
+    if (ctx->opt.verbose)
+        fprintf(stderr, "biogpt_hip[%p]: the replayed eval at position %d %s the row of call %u instead of %u%s: repeated on eager launches\n", (void *)ctx, n_past,
+                on_device ? "left" : "returned", got, want, on_device ? " on the device" : "");
+    uint32_t *const fix = reinterpret_cast<uint32_t *>(ctx->mbox_host + 64 * 8);
+    *fix = ctx->mbox_sent;
+    HIP_TRY(-2, hipMemcpyAsync(ctx->mbox_ctr, fix, 4, hipMemcpyHostToDevice, ctx->stream));
+    if (!upload_state(ctx, tokens, n, n_past) || !enqueue_forward(ctx, ForwardPass::last_row(n, n_past + n)) || !refetch()) return -2;
+    // (not wait_stream: every mailbox slot was already read when the stale row was found, and the eager launches sent none)
+    return (drain_stream(ctx, how) && xpipe_check(ctx)) ? 0 : -2;
 }
 
 static int eval_topk_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, int32_t k, float *vals_out, int32_t *ids_out) {
@@ -1808,30 +1909,22 @@ static int eval_topk_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n,
     // the kernel writes its <= 64 pairs straight into pinned host memory: no copy command behind it
     float *out_val = reinterpret_cast<float *>(ctx->topk_host);
     int32_t *out_idx = reinterpret_cast<int32_t *>(ctx->topk_host + 64 * 4);
-    hipLaunchKernelGGL(bgk::topk_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->logits, ctx->hp.n_vocab, k, ctx->pmax_val, ctx->lm_blocks,
-                       out_val, out_idx, out_idx + 64);
-    HIP_TRY(-2, hipGetLastError());
+    auto select = [&]() -> bool {
+        hipLaunchKernelGGL(bgk::topk_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->logits, ctx->hp.n_vocab, k, ctx->pmax_val, ctx->lm_blocks,
+                           out_val, out_idx, out_idx + 64);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    if (!select()) return -2;
     uint32_t *const got = (ctx->dev_stamp_expect != 0 && ctx->mbox_host) ? reinterpret_cast<uint32_t *>(ctx->mbox_host + 64 * 8) + 1 : nullptr;
     if (got) HIP_TRY(-2, hipMemcpyAsync(got, ctx->seq_dev + bgk::SEQ_LM_HEAD, 4, hipMemcpyDeviceToHost, ctx->stream));   // the device row's lineage (a replayed five-launch step)
-    // low-latency wait: poll the stream instead of sleeping on it (the caller is blocked on this token anyway)
-    if (!poll_stream(ctx)) return -2;
-    ctx->mbox_synced = ctx->mbox_sent;
-    if (!xpipe_check(ctx)) return -2;
+    if (!wait_stream(ctx, Wait::Poll)) return -2;
     if (got) {
         const uint32_t want = ctx->dev_stamp_expect;
         ctx->dev_stamp_expect = 0;
         if (*got != want) {      // the row is another call's: the call again on eager launches, the selection again
-            ctx->stale_rows++;
-            if (ctx->opt.verbose) fprintf(stderr, "biogpt_hip[%p]: the replayed eval at position %d left the row of call %u instead of %u on the device: repeated on eager launches\n", (void *)ctx, n_past, *got, want);
-            uint32_t *const fix = reinterpret_cast<uint32_t *>(ctx->mbox_host + 64 * 8);
-            *fix = ctx->mbox_sent;
-            HIP_TRY(-2, hipMemcpyAsync(ctx->mbox_ctr, fix, 4, hipMemcpyHostToDevice, ctx->stream));
-            if (!upload_state(ctx, tokens, n, n_past) || !enqueue_forward(ctx, n, false, n_past + n)) return -2;
-            hipLaunchKernelGGL(bgk::topk_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->logits, ctx->hp.n_vocab, k, ctx->pmax_val, ctx->lm_blocks,
-                               out_val, out_idx, out_idx + 64);
-            HIP_TRY(-2, hipGetLastError());
-            if (!poll_stream(ctx)) return -2;
-            if (!xpipe_check(ctx)) return -2;
+            const int fixed = repair_stale_row(ctx, tokens, n, n_past, *got, want, true, Wait::Poll, select);
+            if (fixed != 0) return fixed;
         }
     }
     const float *hv = reinterpret_cast<const float *>(ctx->topk_host);
@@ -1852,65 +1945,6 @@ static int eval_topk_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n,
     return k;
 }
 
-// arg-max with the lowest index winning ties (what std::max_element returns), eight independent running maxima so that the compiler can keep them in
-// one vector register: ~4 us for 42 k logits against ~20 us for the scalar loop
-static int32_t argmax_first(const float *v, size_t n) {
-    float best[8]; int32_t at[8];
-    for (int j = 0; j < 8; j++) { best[j] = -INFINITY; at[j] = 0x7fffffff; }
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8)
-        for (int j = 0; j < 8; j++)
-            if (v[i + j] > best[j]) { best[j] = v[i + j]; at[j] = (int32_t)(i + j); }
-    for (; i < n; i++)
-        if (v[i] > best[i & 7] ) { best[i & 7] = v[i]; at[i & 7] = (int32_t)i; }
-    float b = -INFINITY; int32_t a = 0x7fffffff;
-    for (int j = 0; j < 8; j++)
-        if (at[j] != 0x7fffffff && (best[j] > b || (best[j] == b && at[j] < a))) { b = best[j]; a = at[j]; }
-    return a == 0x7fffffff ? 0 : a;
-}
-
-// The reference's host loop (main.cpp:91-151, greedy) as a C++ caller would run it on this library -- one eval call per
-// token, the sampler on the host -- timed without any scripting-language overhead: mode 0 = biogpt_hip_eval (the whole
-// logits row crosses PCIe, host arg-max), mode 1 = biogpt_hip_eval_topk with k = 40 (the CLI's top_k; 512 bytes cross).
-int biogpt_hip_bench_api_loop(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_predict, int32_t mode, int32_t *out_ids,
-                              double *seconds_out) {
-    clear_error();
-    if (!ctx || !prompt || n_prompt < 1 || n_predict < 1 || mode < 0 || mode > 4) BG_FAIL(-1, "bad argument");
-    if (!check_eval_args(ctx, prompt, n_prompt, 0)) return -1;
-    n_predict = std::min(n_predict, ctx->hp.n_positions - n_prompt);
-    const size_t V = (size_t)ctx->hp.n_vocab;
-    std::vector<float> logits(mode == 0 ? V : 64);
-    int32_t ids[64];
-    const auto t0 = std::chrono::steady_clock::now();
-    int32_t tok = 0;
-    int n_past = 0;
-    for (int k = 0; k < n_predict; k++) {
-        const int32_t *in = (k == 0) ? prompt : &tok;
-        const int n_in = (k == 0) ? n_prompt : 1;
-        if (mode == 0) {
-            if (biogpt_hip_eval(ctx, in, n_in, n_past, logits.data()) != 0) return -2;
-            tok = (int32_t)(std::max_element(logits.begin(), logits.end()) - logits.begin());
-        } else if (mode == 3 || mode == 4) {   // the row read in place (pinned host memory the launch wrote), arg-max over 8 interleaved lanes; mode 4 (diagnostic): no arg-max, token fixed
-            const float *row = nullptr;
-            if (biogpt_hip_eval_inplace(ctx, in, n_in, n_past, &row) != 0) return -2;
-            tok = mode == 3 ? argmax_first(row, V) : 2;
-        } else if (mode == 1) {
-            if (biogpt_hip_eval_topk(ctx, in, n_in, n_past, 40, logits.data(), ids) < 0) return -2;
-            tok = ids[0];
-        } else {   // mode 2 (diagnostic): the eval and a stream synchronise only -- no output leaves the device; token fixed
-            if (biogpt_hip_eval_device(ctx, in, n_in, n_past) != 0) return -2;
-            HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-            ctx->mbox_synced = ctx->mbox_sent;
-    if (!xpipe_check(ctx)) return -2;
-            tok = 2;
-        }
-        n_past += n_in;
-        if (out_ids) out_ids[k] = tok;
-    }
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return n_predict;
-}
-
 const float *biogpt_hip_logits_device(const biogpt_hip_ctx *ctx) {
     if (!ctx) return nullptr;
     // a resident launch may hold the last accepted row in its alternate buffer (odd sequence numbers) and may be running one position ahead: it is stopped here -- its
@@ -1927,25 +1961,17 @@ int biogpt_hip_read_logits(biogpt_hip_ctx *ctx, float *out) {
     HIP_TRY(-2, hipMemcpyAsync(out, ctx->logits, (size_t)ctx->hp.n_vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
     uint32_t *const got = ctx->mbox_host ? reinterpret_cast<uint32_t *>(ctx->mbox_host + 64 * 8) + 1 : nullptr;
     if (ctx->dev_stamp_expect != 0 && got) HIP_TRY(-2, hipMemcpyAsync(got, ctx->seq_dev + bgk::SEQ_LM_HEAD, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    ctx->mbox_synced = ctx->mbox_sent;
-    if (!xpipe_check(ctx)) return -2;
+    if (!wait_stream(ctx)) return -2;
     if (ctx->dev_stamp_expect != 0 && got) {
         // the device row of a replayed five-launch eval (biogpt_hip_eval_device): the same lineage check as eval_once's, the same repair
         const uint32_t want = ctx->dev_stamp_expect;
         ctx->dev_stamp_expect = 0;
-        if (*got != want) {
-            ctx->stale_rows++;
-            if (ctx->opt.verbose) fprintf(stderr, "biogpt_hip[%p]: the replayed eval at position %d left the row of call %u instead of %u on the device: repeated on eager launches\n", (void *)ctx, ctx->dev_stamp_n_past, *got, want);
-            uint32_t *const fix = reinterpret_cast<uint32_t *>(ctx->mbox_host + 64 * 8);
-            *fix = ctx->mbox_sent;
-            HIP_TRY(-2, hipMemcpyAsync(ctx->mbox_ctr, fix, 4, hipMemcpyHostToDevice, ctx->stream));
-            const int32_t tok = ctx->dev_stamp_tok;
-            if (!upload_state(ctx, &tok, 1, ctx->dev_stamp_n_past) || !enqueue_forward(ctx, 1, false, ctx->dev_stamp_n_past + 1)) return -2;
-            HIP_TRY(-2, hipMemcpyAsync(out, ctx->logits, (size_t)ctx->hp.n_vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-            if (!xpipe_check(ctx)) return -2;
-        }
+        const int32_t tok = ctx->dev_stamp_tok;
+        if (*got != want)
+            return repair_stale_row(ctx, &tok, 1, ctx->dev_stamp_n_past, *got, want, true, Wait::Sleep, [&]() -> bool {
+                HIP_TRY(false, hipMemcpyAsync(out, ctx->logits, (size_t)ctx->hp.n_vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
+                return true;
+            });
     }
     return 0;
 }
@@ -1990,31 +2016,33 @@ static int eval_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int3
         if (!ctx->logits_host) HIP_TRY(-2, hipHostMalloc(reinterpret_cast<void **>(&ctx->logits_host), host_row_bytes(ctx), hipHostMallocDefault));
         HIP_TRY(-2, hipMemcpyAsync(ctx->logits_host, ctx->logits, bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (!poll_stream(ctx)) return -2;   // poll: the caller is blocked on this token anyway
-    ctx->mbox_synced = ctx->mbox_sent;
-    if (!xpipe_check(ctx)) return -2;
-    if (in_graph && ctx->stamp_expect != 0) {
-        // the row of a replayed five-launch graph carries the sequence number its FIRST node fetched, forwarded by the last layer and the lm_head as they started: any
-        // other number means that the row is not this call's (profiles/two_contexts_r4.txt, profiles/stale_row_r5.txt).  Repair: the device's replay counter is put
-        // right and the call is repeated on eager launches (same token, same position: the K / V row is written again with the same values).
+    if (!wait_stream(ctx, Wait::Poll)) return -2;
+    if (in_graph && ctx->stamp_expect != 0) {      // the pinned row of a replayed five-launch graph: its lineage lies behind it
         const uint32_t got = reinterpret_cast<const uint32_t *>(ctx->logits_host)[host_stamp_index(ctx)];
         const uint32_t want = ctx->stamp_expect;
         ctx->stamp_expect = 0;
         if (got != want) {
-            ctx->stale_rows++;
-            if (ctx->opt.verbose) fprintf(stderr, "biogpt_hip[%p]: the replayed eval at position %d returned the row of call %u instead of %u: repeated on eager launches\n", (void *)ctx, n_past, got, want);
-            uint32_t *const fix = reinterpret_cast<uint32_t *>(ctx->mbox_host + 64 * 8);
-            *fix = ctx->mbox_sent;
-            HIP_TRY(-2, hipMemcpyAsync(ctx->mbox_ctr, fix, 4, hipMemcpyHostToDevice, ctx->stream));
-            if (!upload_state(ctx, tokens, n, n_past) || !enqueue_forward(ctx, n, false, n_past + n)) return -2;
-            HIP_TRY(-2, hipMemcpyAsync(ctx->logits_host, ctx->logits, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            if (!poll_stream(ctx)) return -2;
-            if (!xpipe_check(ctx)) return -2;
+            const int fixed = repair_stale_row(ctx, tokens, n, n_past, got, want, false, Wait::Poll, [&]() -> bool {
+                HIP_TRY(false, hipMemcpyAsync(ctx->logits_host, ctx->logits, bytes, hipMemcpyDeviceToHost, ctx->stream));
+                return true;
+            });
+            if (fixed != 0) return fixed;
         }
     }
     ctx->row_cur = ctx->logits_host;
     if (logits_out) std::memcpy(logits_out, ctx->logits_host, bytes);
     return 0;
+}
+
+// logits_all holds at least `rows` rows; a new buffer drops the captured column steps (they hold the old pointer)
+static bool ensure_logits_rows(biogpt_hip_ctx *c, size_t rows) {
+    if (rows <= c->logits_all_rows) return true;
+    if (c->logits_all) (void)hipFree(c->logits_all);
+    c->logits_all = nullptr; c->logits_all_rows = 0;
+    HIP_TRY(false, hipMalloc(&c->logits_all, rows * c->hp.n_vocab * 4));
+    c->logits_all_rows = rows;
+    drop_column_graphs(c);
+    return true;
 }
 
 int biogpt_hip_eval_all(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, float *logits_out) {
@@ -2023,15 +2051,9 @@ int biogpt_hip_eval_all(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, i
     if (!check_eval_args(ctx, tokens, n, n_past)) return -1;
     HIP_TRY(-2, hipSetDevice(ctx->device));
     if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    if ((size_t)n > ctx->logits_all_rows) {
-        if (ctx->logits_all) (void)hipFree(ctx->logits_all);
-        ctx->logits_all = nullptr;
-        HIP_TRY(-2, hipMalloc(&ctx->logits_all, (size_t)n * ctx->hp.n_vocab * 4));
-        ctx->logits_all_rows = (size_t)n;
-        drop_column_graphs(ctx);
-    }
+    if (!ensure_logits_rows(ctx, (size_t)n)) return -2;
     if (!upload_state(ctx, tokens, n, n_past)) return -2;
-    if (!enqueue_forward(ctx, n, true, n_past + n)) return -2;
+    if (!enqueue_forward(ctx, ForwardPass::every_row(n, n_past + n))) return -2;
     HIP_TRY(-2, hipMemcpyAsync(logits_out, ctx->logits_all, (size_t)n * ctx->hp.n_vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
     return 0;
@@ -2050,7 +2072,7 @@ bool enqueue_prompt(biogpt_hip_ctx *c, const int32_t *tokens, int n, int n_past,
     for (int at = 0; at < n;) {
         const int m = std::min(group, n - at);
         if (!upload_state(c, tokens + at, m, n_past + at, m > n_batch ? n_batch : 0)) return false;
-        if (!enqueue_forward(c, m, false, n_past + at + m)) return false;
+        if (!enqueue_forward(c, ForwardPass::last_row(m, n_past + at + m))) return false;
         if (last_cols) *last_cols = m;   // the device state now describes this pass (its n_past, its m tokens)
         at += m;
     }
@@ -2067,9 +2089,7 @@ static int eval_prompt_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t 
     if (!enqueue_prompt(ctx, tokens, n_tokens, n_past, n_batch)) return -2;
     if (logits_out) {
         HIP_TRY(-2, hipMemcpyAsync(logits_out, ctx->logits, (size_t)ctx->hp.n_vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-        ctx->mbox_synced = ctx->mbox_sent;
-        if (!xpipe_check(ctx)) return -2;      // a prompt of up to 8 tokens is a pipelined launch (kernels_xcols.hip.h; one token: kernels_xpipe.hip.h)
+        if (!wait_stream(ctx)) return -2;      // a prompt of up to 8 tokens is a pipelined launch (kernels_xcols.hip.h; one token: kernels_xpipe.hip.h)
     }
     return 0;
 }
@@ -2137,7 +2157,7 @@ static int generate_greedy_once(biogpt_hip_ctx *ctx, const int32_t *prompt, int3
         } else if (use_graph) {
             HIP_TRY(-2, hipGraphLaunch(ctx->graph_step[pl_of(graph_bucket(T))][1][graph_bucket(T)], ctx->stream));
         } else {
-            if (!enqueue_forward(ctx, 1, false, T) || !enqueue_argmax(ctx, 1)) return -2;
+            if (!enqueue_forward(ctx, ForwardPass::last_row(1, T)) || !enqueue_argmax(ctx, 1)) return -2;
         }
     }
     if (pending && !enqueue_argmax(ctx, 0)) return -2;   // the last token's sampler
@@ -2169,15 +2189,15 @@ static bool xpipe_retry(biogpt_hip_ctx *ctx, int n_past) {
     return true;
 }
 // once(): the call; a negative result after a tripped pipeline is repeated once
-static int with_xpipe_retry(biogpt_hip_ctx *ctx, int n_past, const std::function<int()> &once) {
+extern "C++" template <class Once>
+int with_xpipe_retry(biogpt_hip_ctx *ctx, int n_past, Once once) {
     int rc = once();
     if (rc < 0 && xpipe_retry(ctx, n_past)) rc = once();
     return rc;
 }
 int biogpt_hip_eval_inplace(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, const float **row_out) {
     if (!row_out) BG_FAIL(-1, "null row pointer");
-    int rc = eval_once(ctx, tokens, n, n_past, nullptr);
-    if (rc != 0 && xpipe_retry(ctx, n_past)) rc = eval_once(ctx, tokens, n, n_past, nullptr);
+    const int rc = with_xpipe_retry(ctx, n_past, [&] { return eval_once(ctx, tokens, n, n_past, nullptr); });
     *row_out = rc == 0 ? ctx->row_cur : nullptr;
     return rc;
 }
@@ -2201,15 +2221,11 @@ int biogpt_hip_resident_stats(const biogpt_hip_ctx *ctx, int64_t *out4) {
     return 0;
 }
 int biogpt_hip_eval_prompt(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, int32_t n_batch, float *logits_out) {
-    int rc = eval_prompt_once(ctx, tokens, n_tokens, n_past, n_batch, logits_out);
-    if (rc != 0 && xpipe_retry(ctx, n_past)) rc = eval_prompt_once(ctx, tokens, n_tokens, n_past, n_batch, logits_out);
-    return rc;
+    return with_xpipe_retry(ctx, n_past, [&] { return eval_prompt_once(ctx, tokens, n_tokens, n_past, n_batch, logits_out); });
 }
 int biogpt_hip_eval(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, float *logits_out) {
     if (!logits_out) BG_FAIL(-1, "null logits buffer");
-    int rc = eval_once(ctx, tokens, n, n_past, logits_out);
-    if (rc != 0 && xpipe_retry(ctx, n_past)) rc = eval_once(ctx, tokens, n, n_past, logits_out);
-    return rc;
+    return with_xpipe_retry(ctx, n_past, [&] { return eval_once(ctx, tokens, n, n_past, logits_out); });
 }
 int biogpt_hip_eval_topk(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, int32_t k, float *vals_out, int32_t *ids_out) {
     return with_xpipe_retry(ctx, n_past, [&] { return eval_topk_once(ctx, tokens, n, n_past, k, vals_out, ids_out); });
@@ -2233,17 +2249,6 @@ static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
     HIP_TRY(false, hipMalloc(&ctx->seq_gen, (size_t)n_seqs * ctx->hp.n_positions * 4));
     ctx->batch_cap = n_seqs;
     drop_column_graphs(ctx);
-    return true;
-}
-
-// logits_all holds at least `rows` rows; a new buffer drops the captured column steps (they hold the old pointer)
-static bool ensure_logits_rows(biogpt_hip_ctx *c, size_t rows) {
-    if (rows <= c->logits_all_rows) return true;
-    if (c->logits_all) (void)hipFree(c->logits_all);
-    c->logits_all = nullptr; c->logits_all_rows = 0;
-    HIP_TRY(false, hipMalloc(&c->logits_all, rows * c->hp.n_vocab * 4));
-    c->logits_all_rows = rows;
-    drop_column_graphs(c);
     return true;
 }
 
@@ -2393,7 +2398,7 @@ static bool capture_column_steps(biogpt_hip_ctx *ctx, ColumnGraphs &graphs, int 
 static bool ingest_column_prompts(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *lens, int n_prompts, int n_batch, int per_prompt) {
     const auto &hp = ctx->hp;
     if (!pack_column_passes(ctx, prompts, lens, n_prompts, n_batch,
-                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, n_cols, false, t_max, true, ctx->cols); }, per_prompt))
+                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); }, per_prompt))
         return false;
     if (per_prompt > 1) {
         hipLaunchKernelGGL(bgk::kv_share_kernel, dim3(hp.n_layer * hp.n_head, n_prompts * per_prompt, 2), dim3(256), 0, ctx->stream, ctx->seq, per_prompt, ctx->bk, ctx->bv,
@@ -2447,7 +2452,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     if (!upload_column_starts(ctx, prompts, prompt_lens, n_seqs, 1)) return -2;
 
     const ColumnStep step = [&](int t_max) -> bool {
-        if (!enqueue_forward(ctx, n_seqs, false, t_max, true)) return false;
+        if (!enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max))) return false;
         hipLaunchKernelGGL(bgk::argmax_rows_kernel, dim3(n_seqs), dim3(1024), 0, ctx->stream, ctx->logits_all, V, V, ctx->seq, 0, ctx->seq_gen, P, 1);
         HIP_TRY(false, hipGetLastError());
         return true;
@@ -2520,13 +2525,29 @@ static bool enqueue_logprob(biogpt_hip_ctx *c, int m, size_t flat0, size_t total
 static int score_finish(biogpt_hip_ctx *c, size_t total, float *logprob_out, int32_t *argmax_out, float *logit_out) {
     std::vector<uint32_t> h(3 * total);
     HIP_TRY(-2, hipMemcpyAsync(h.data(), c->sc_out, 3 * total * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(-2, hipStreamSynchronize(c->stream));
-    c->mbox_synced = c->mbox_sent;
-    if (!xpipe_check(c)) return -2;
+    if (!wait_stream(c)) return -2;
     std::memcpy(logprob_out, h.data(), total * 4);
     if (argmax_out) std::memcpy(argmax_out, h.data() + total, total * 4);
     if (logit_out) std::memcpy(logit_out, h.data() + 2 * total, total * 4);
     return 0;
+}
+
+// The causal passes of ONE sequence in the context's own cache (biogpt_hip_score, biogpt_hip_hidden): the passes of biogpt_hip_eval_prompt(tokens, n_past,
+// n_batch = 1) -- same borders, same K / V rows.  causal_pass_cols: the columns of a pass at most (0: failure), with the tiled weights built if the first
+// pass takes the matrix cores; causal_passes: per pass the state upload (a pass of several columns: chunks of one), then pass(at, m) for tokens [at, at + m).
+static int causal_pass_cols(biogpt_hip_ctx *ctx, int n) {
+    const int max_cols = std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
+    if (std::min(max_cols, n) >= MFMA_MIN_PASS_COLS && is_quantized(ftype_to_type(ctx->hp.ftype)) && !ensure_tile_images(ctx)) return 0;
+    return max_cols;
+}
+extern "C++" template <class Pass>
+bool causal_passes(biogpt_hip_ctx *ctx, const int32_t *tokens, int n, int n_past, int max_cols, Pass pass) {
+    for (int at = 0; at < n;) {
+        const int m = std::min(max_cols, n - at);
+        if (!upload_state(ctx, tokens + at, m, n_past + at, m > 1 ? 1 : 0) || !pass(at, m)) return false;
+        at += m;
+    }
+    return true;
 }
 
 static int score_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, const int32_t *targets,
@@ -2538,21 +2559,17 @@ static int score_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int
     if (!check_targets(ctx, targets, n, 0)) return -1;
     HIP_TRY(-2, hipSetDevice(ctx->device));
     if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    // the passes of biogpt_hip_eval_prompt(tokens, n_past, n_batch = 1): same borders, same K / V rows
-    const int max_cols = std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
-    const int first = std::min(max_cols, (int)n);
-    if (first >= MFMA_MIN_PASS_COLS && is_quantized(ftype_to_type(ctx->hp.ftype)) && !ensure_tile_images(ctx)) return -2;
-    if (!ensure_logits_rows(ctx, (size_t)first) || !score_setup(ctx, tokens, &n, 1, targets, (size_t)n)) return -2;
-    const int V = ctx->hp.n_vocab;
-    for (int at = 0; at < n;) {
-        const int m = std::min(max_cols, n - at);
-        if (!upload_state(ctx, tokens + at, m, n_past + at, m > 1 ? 1 : 0)) return -2;
-        if (!enqueue_forward(ctx, m, true, n_past + at + m, false, nullptr, true)) return -2;
-        if (!enqueue_logprob(ctx, m, (size_t)at, (size_t)n)) return -2;
-        at += m;
-        if (at == n)   // the last row is what biogpt_hip_read_logits / biogpt_hip_logits_device return afterwards
-            HIP_TRY(-2, hipMemcpyAsync(ctx->logits, ctx->logits_all + (size_t)(m - 1) * V, (size_t)V * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    }
+    const int max_cols = causal_pass_cols(ctx, n);
+    if (!max_cols) return -2;
+    if (!ensure_logits_rows(ctx, (size_t)std::min(max_cols, (int)n)) || !score_setup(ctx, tokens, &n, 1, targets, (size_t)n)) return -2;
+    const size_t V = (size_t)ctx->hp.n_vocab;
+    const bool ok = causal_passes(ctx, tokens, n, n_past, max_cols, [&](int at, int m) -> bool {
+        if (!enqueue_forward(ctx, ForwardPass::scored(m, n_past + at + m)) || !enqueue_logprob(ctx, m, (size_t)at, (size_t)n)) return false;
+        if (at + m == n)   // the last row is what biogpt_hip_read_logits / biogpt_hip_logits_device return afterwards
+            HIP_TRY(false, hipMemcpyAsync(ctx->logits, ctx->logits_all + (size_t)(m - 1) * V, V * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        return true;
+    });
+    if (!ok) return -2;
     return score_finish(ctx, (size_t)n, logprob_out, argmax_out, logit_out);
 }
 
@@ -2564,9 +2581,7 @@ static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (!seqs || !lens || !logprob_out) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");   // each sequence owns a full F32 KV cache
-    const auto &hp = ctx->hp;
-    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
-        BG_FAIL(-1, "batched scoring needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (!check_fast_chain(ctx, "batched scoring")) return -1;
     size_t total = 0;
     for (int s = 0; s < n_seqs; s++) {
         if (lens[s] < 1) BG_FAIL(-1, "empty sequence (sequence %d)", s);
@@ -2582,7 +2597,7 @@ static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if ((long)std::min(max_cols, total) >= MFMA_MIN_PASS_COLS && !ensure_tile_images(ctx)) return -2;
     if (!ensure_logits_rows(ctx, std::min(max_cols, total)) || !score_setup(ctx, seqs, lens, n_seqs, targets, total)) return -2;
     if (!pack_column_passes(ctx, seqs, lens, n_seqs, 1, [&](int n_cols, int t_max, size_t flat0) {
-            return enqueue_forward(ctx, n_cols, true, t_max, true, ctx->cols, true) && enqueue_logprob(ctx, n_cols, flat0, total);
+            return enqueue_forward(ctx, ForwardPass::packed_scored(n_cols, t_max)) && enqueue_logprob(ctx, n_cols, flat0, total);
         }))
         return -2;
     return score_finish(ctx, total, logprob_out, argmax_out, logit_out);
@@ -2656,8 +2671,7 @@ static int score_continuations_once(biogpt_hip_ctx *ctx, const int32_t *prefix, 
     if (n_prefix < 1) BG_FAIL(-1, "n_prefix must be >= 1 (got %d)", n_prefix);
     if (n_conts < 1 || n_conts > 511) BG_FAIL(-1, "n_conts must be in [1, 511] (got %d)", n_conts);   // slot 0 is the prefix; each continuation owns a full F32 KV cache
     const auto &hp = ctx->hp;
-    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
-        BG_FAIL(-1, "shared-prefix scoring needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (!check_fast_chain(ctx, "shared-prefix scoring")) return -1;
     if (n_prefix > hp.n_positions) BG_FAIL(-1, "n_prefix (%d) exceeds n_positions (%d)", n_prefix, hp.n_positions);
     for (int i = 0; i < n_prefix; i++)
         if (prefix[i] < 0 || prefix[i] >= hp.n_vocab) BG_FAIL(-1, "token id %d (prefix, position %d) out of range [0, %d)", prefix[i], i, hp.n_vocab);
@@ -2688,7 +2702,7 @@ static int score_continuations_once(biogpt_hip_ctx *ctx, const int32_t *prefix, 
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
     const auto t0 = std::chrono::steady_clock::now();
     if (!pack_continuation_passes(ctx, prefix, n_prefix, conts, cont_lens, n_conts, [&](int n_cols, int t_max, size_t flat0, int n_pre) {
-            return enqueue_forward(ctx, n_cols, true, t_max, true, ctx->cols, true, nullptr, true, n_pre) &&
+            return enqueue_forward(ctx, ForwardPass::packed_continuations(n_cols, t_max, n_pre)) &&
                    (n_pre == n_cols || enqueue_logprob(ctx, n_cols - n_pre, flat0, total));
         }))
         return -2;
@@ -2705,7 +2719,7 @@ int biogpt_hip_score_continuations(biogpt_hip_ctx *ctx, const int32_t *prefix, i
 }
 
 // ---- hidden states, pooled embeddings, classification heads: the same causal passes without the lm_head (kernels_embed.hip.h) ------------
-// The passes are those of scoring (one column per token, row i sees keys [0, position of i]); their final stage is Final::Hidden: the final
+// The passes are those of scoring (one column per token, row i sees keys [0, position of i]); their final stage is Rows::Hidden: the final
 // LayerNorm of every column as f32 rows -- or, for a layer index k < n_layer, the residual stream after k layers as it lies in c->x.  Pooling
 // and the caller's linear head run on the device per pass; the call's rows come back in one copy.
 struct EmbedPlan {      // byte offsets into emb_buf (each a multiple of 16)
@@ -2769,25 +2783,17 @@ static int hidden_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, in
     if (!check_eval_args(ctx, tokens, n, n_past)) return -1;
     HIP_TRY(-2, hipSetDevice(ctx->device));
     if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
-    // the passes of biogpt_hip_score: same borders, same K / V rows as biogpt_hip_eval_prompt(tokens, n_past, n_batch = 1)
-    const int max_cols = std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
-    const int first = std::min(max_cols, (int)n);
     const size_t D = (size_t)ctx->hp.d_model;
-    if (first >= MFMA_MIN_PASS_COLS && is_quantized(ftype_to_type(ctx->hp.ftype)) && !ensure_tile_images(ctx)) return -2;
+    const int max_cols = causal_pass_cols(ctx, n);      // the passes of biogpt_hip_score
+    if (!max_cols) return -2;
     if (!ensure_embed_buf(ctx, (size_t)n * D * 4)) return -2;
     float *const out = reinterpret_cast<float *>(ctx->emb_buf);
-    for (int at = 0; at < n;) {
-        const int m = std::min(max_cols, n - at);
-        const HiddenStage hs{ctx->hp.n_layer, out + (size_t)at * D};
-        if (!upload_state(ctx, tokens + at, m, n_past + at, m > 1 ? 1 : 0)) return -2;
-        if (!enqueue_forward(ctx, m, true, n_past + at + m, false, nullptr, false, &hs)) return -2;
-        at += m;
-    }
+    if (!causal_passes(ctx, tokens, n, n_past, max_cols, [&](int at, int m) {
+            return enqueue_forward(ctx, ForwardPass::hidden(m, n_past + at + m, HiddenStage{ctx->hp.n_layer, out + (size_t)at * D}));
+        }))
+        return -2;
     HIP_TRY(-2, hipMemcpyAsync(hidden_out, out, (size_t)n * D * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    ctx->mbox_synced = ctx->mbox_sent;
-    if (!xpipe_check(ctx)) return -2;
-    return 0;
+    return wait_stream(ctx) ? 0 : -2;
 }
 
 static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const biogpt_hip_embed_opts *opts,
@@ -2800,8 +2806,7 @@ static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (!ctx) BG_FAIL(-1, "null context");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     const auto &hp = ctx->hp;
-    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
-        BG_FAIL(-1, "batched embedding needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    if (!check_fast_chain(ctx, "batched embedding")) return -1;
     if (o.layer > hp.n_layer) BG_FAIL(-1, "layer (%d) must be in [-1, n_layer = %d]", o.layer, hp.n_layer);
     size_t total = 0;
     for (int s = 0; s < n_seqs; s++) {
@@ -2848,7 +2853,7 @@ static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (d_acc) HIP_TRY(-2, hipMemsetAsync(d_acc, 0, (size_t)n_seqs * D * 8, st));
     if (!pack_column_passes(ctx, seqs, lens, n_seqs, 1, [&](int n_cols, int t_max, size_t flat0) {
             const HiddenStage hs{k, k < hp.n_layer ? nullptr : (direct ? d_out + flat0 * D : d_hid)};
-            if (!enqueue_forward(ctx, n_cols, true, t_max, true, ctx->cols, false, &hs)) return false;
+            if (!enqueue_forward(ctx, ForwardPass::packed_hidden(n_cols, t_max, hs))) return false;
             const float *rows = hs.ln_out ? hs.ln_out : ctx->x;
             if (o.pooling == bgk::POOL_NONE) {
                 if (o.n_out > 0) return enqueue_head(ctx, rows, n_cols, d_w, d_b, o.n_out, d_out + flat0 * W);
@@ -2867,10 +2872,8 @@ static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     }
     if (d_pool && o.n_out > 0 && !enqueue_head(ctx, d_pool, n_seqs, d_w, d_b, o.n_out, d_out)) return -2;
     HIP_TRY(-2, hipMemcpyAsync(out_host, d_out, n_rows * W * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(-2, hipStreamSynchronize(st));
+    if (!wait_stream(ctx)) return -2;
     const auto t1 = std::chrono::steady_clock::now();
-    ctx->mbox_synced = ctx->mbox_sent;
-    if (!xpipe_check(ctx)) return -2;
     if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
     return 0;
 }
@@ -3003,7 +3006,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     if (ru && !rules_upload(ctx, rules, 0, eos_id, prompts, prompt_lens, n_prompts, n_samples)) return -2;
 
     const ColumnStep step = [&](int t_max) -> bool {
-        if (!enqueue_forward(ctx, n_seqs, false, t_max, true)) return false;
+        if (!enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max))) return false;
         if (ru && !enqueue_rules(ctx, n_seqs, &sample_seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
         hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->sample_ctl, sample_seq,
                            ctx->seq, ctx->seq_gen, P);
@@ -3154,7 +3157,7 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     if (!upload_column_starts(ctx, prompts, prompt_lens, G, B)) return -2;
     if (ru && !rules_upload(ctx, rules, 1, eos_id, prompts, prompt_lens, G, B)) return -2;
 
-    const ColumnStep step = [&](int t_max) -> bool { return enqueue_forward(ctx, n_seqs, false, t_max, true) && enqueue_beam_group_select(ctx, G, B, ru); };
+    const ColumnStep step = [&](int t_max) -> bool { return enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max)) && enqueue_beam_group_select(ctx, G, B, ru); };
     const int gset = 6 * choose_column_path(ctx, n_seqs, max_len) + (ru ? 12 : 0);
     bool use_graph;
     if (!capture_column_steps(ctx, ctx->graphs_beam, gset, max_len, n_predict, step, &use_graph)) return -2;

@@ -1,4 +1,4 @@
-// Part of engine.hip (textually included there: same translation unit, same anonymous namespace / extern "C" block): measurement entry points of the C-ABI (biogpt_hip_bench_matvec / _stream / _decode): HIP-event timed launches on the context's stream, profiling-build stage timelines.
+// Part of engine.hip (textually included there: same translation unit, same anonymous namespace / extern "C" block): measurement entry points of the C-ABI (biogpt_hip_bench_matvec / _stream / _decode / _api_loop): HIP-event timed launches on the context's stream, profiling-build stage timelines.
 
 int biogpt_hip_bench_matvec(biogpt_hip_ctx *ctx, int which, int layer, int reps, double *seconds_out, double *bytes_out) {
     XpCallScope xp_scope(ctx);
@@ -555,3 +555,59 @@ int biogpt_hip_bench_decode(biogpt_hip_ctx *ctx, int32_t n_past, int reps, doubl
     return 0;
 }
 
+// arg-max with the lowest index winning ties (what std::max_element returns), eight independent running maxima so that the compiler can keep them in
+// one vector register: ~4 us for 42 k logits against ~20 us for the scalar loop
+static int32_t argmax_first(const float *v, size_t n) {
+    float best[8]; int32_t at[8];
+    for (int j = 0; j < 8; j++) { best[j] = -INFINITY; at[j] = 0x7fffffff; }
+    size_t i = 0;
+    for (; i + 8 <= n; i += 8)
+        for (int j = 0; j < 8; j++)
+            if (v[i + j] > best[j]) { best[j] = v[i + j]; at[j] = (int32_t)(i + j); }
+    for (; i < n; i++)
+        if (v[i] > best[i & 7] ) { best[i & 7] = v[i]; at[i & 7] = (int32_t)i; }
+    float b = -INFINITY; int32_t a = 0x7fffffff;
+    for (int j = 0; j < 8; j++)
+        if (at[j] != 0x7fffffff && (best[j] > b || (best[j] == b && at[j] < a))) { b = best[j]; a = at[j]; }
+    return a == 0x7fffffff ? 0 : a;
+}
+
+// The reference's host loop (main.cpp:91-151, greedy) as a C++ caller would run it on this library -- one eval call per
+// token, the sampler on the host -- timed without any scripting-language overhead: mode 0 = biogpt_hip_eval (the whole
+// logits row crosses PCIe, host arg-max), mode 1 = biogpt_hip_eval_topk with k = 40 (the CLI's top_k; 512 bytes cross).
+int biogpt_hip_bench_api_loop(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t n_prompt, int32_t n_predict, int32_t mode, int32_t *out_ids,
+                              double *seconds_out) {
+    clear_error();
+    if (!ctx || !prompt || n_prompt < 1 || n_predict < 1 || mode < 0 || mode > 4) BG_FAIL(-1, "bad argument");
+    if (!check_eval_args(ctx, prompt, n_prompt, 0)) return -1;
+    n_predict = std::min(n_predict, ctx->hp.n_positions - n_prompt);
+    const size_t V = (size_t)ctx->hp.n_vocab;
+    std::vector<float> logits(mode == 0 ? V : 64);
+    int32_t ids[64];
+    const auto t0 = std::chrono::steady_clock::now();
+    int32_t tok = 0;
+    int n_past = 0;
+    for (int k = 0; k < n_predict; k++) {
+        const int32_t *in = (k == 0) ? prompt : &tok;
+        const int n_in = (k == 0) ? n_prompt : 1;
+        if (mode == 0) {
+            if (biogpt_hip_eval(ctx, in, n_in, n_past, logits.data()) != 0) return -2;
+            tok = (int32_t)(std::max_element(logits.begin(), logits.end()) - logits.begin());
+        } else if (mode == 3 || mode == 4) {   // the row read in place (pinned host memory the launch wrote), arg-max over 8 interleaved lanes; mode 4 (diagnostic): no arg-max, token fixed
+            const float *row = nullptr;
+            if (biogpt_hip_eval_inplace(ctx, in, n_in, n_past, &row) != 0) return -2;
+            tok = mode == 3 ? argmax_first(row, V) : 2;
+        } else if (mode == 1) {
+            if (biogpt_hip_eval_topk(ctx, in, n_in, n_past, 40, logits.data(), ids) < 0) return -2;
+            tok = ids[0];
+        } else {   // mode 2 (diagnostic): the eval and a stream synchronise only -- no output leaves the device; token fixed
+            if (biogpt_hip_eval_device(ctx, in, n_in, n_past) != 0) return -2;
+            if (!wait_stream(ctx)) return -2;
+            tok = 2;
+        }
+        n_past += n_in;
+        if (out_ids) out_ids[k] = tok;
+    }
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return n_predict;
+}

@@ -168,9 +168,7 @@ static int eval_device_impl(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t 
     // token and the position from a pinned mailbox slot -- instead of a copy command and 121 launches one by one
     if (n == 1 && !ctx->opt.no_graph && fused_decode_ok(ctx, bucket_tmax(ctx, graph_bucket(n_past + 1)))) {   // the captured step runs at the BUCKET's context bound
         if (ctx->mbox_host && ctx->mbox_sent - ctx->mbox_synced >= 64) {   // never overwrite a slot a queued replay has not read yet
-            HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-            ctx->mbox_synced = ctx->mbox_sent;
-            if (!xpipe_check(ctx)) return -2;
+            if (!wait_stream(ctx)) return -2;
         }
         const int b = graph_bucket(n_past + 1);
         const int pl = xpipe_usable(ctx, bucket_tmax(ctx, b)) ? 1 : 0;   // holds the slot until the stream is next synchronised (xpipe_check)
@@ -237,7 +235,7 @@ static int eval_device_impl(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t 
     }
 eager:
     if (!upload_state(ctx, tokens, n, n_past)) return -2;
-    if (!enqueue_forward(ctx, n, false, n_past + n)) return -2;
+    if (!enqueue_forward(ctx, ForwardPass::last_row(n, n_past + n))) return -2;
     return 0;
 }
 
