@@ -97,6 +97,24 @@ def rules_rows(rows, histories, prompt_lens=None, mode=0, eos_id=-1, device=0, *
     return out
 
 
+def contrast_rank(cand, ctx_rows, probs, alpha, device=0):
+    """The penalty and selection kernels of contrastive search on rows held in host memory (biogpt_hip_contrast_rank_device): cand float32 [k][d],
+    ctx_rows float32 [T][d], probs float32 [k].  Returns (pen float32[k], score float32[k], winner)."""
+    c = np.ascontiguousarray(cand, dtype=np.float32)
+    h = np.ascontiguousarray(ctx_rows, dtype=np.float32)
+    p = np.ascontiguousarray(probs, dtype=np.float32).reshape(-1)
+    if c.ndim != 2 or h.ndim != 2 or c.shape[1] != h.shape[1] or p.size != c.shape[0]:
+        raise BiogptError("contrast_rank: cand [k][d], ctx_rows [T][d] and probs [k] do not fit together")
+    k, d = c.shape
+    pen = np.zeros(k, dtype=np.float32)
+    score = np.zeros(k, dtype=np.float32)
+    win = C.c_int32(-1)
+    if lib().biogpt_hip_contrast_rank_device(int(device), c.ctypes.data, h.ctypes.data, k, h.shape[0], d, p.ctypes.data, float(alpha), pen.ctypes.data,
+                                             score.ctypes.data, C.addressof(win)) != 0:
+        raise BiogptError(_err())
+    return pen, score, int(win.value)
+
+
 BIOGPT_BASE = dict(n_vocab=42384, n_layer=24, n_head=16, n_positions=1024, d_ff=4096, d_model=1024,
                    ftype=0, n_merges=40000)
 
@@ -172,6 +190,8 @@ SYMBOLS = [
                                                   C.POINTER(C.c_double), C.POINTER(GenRules)]),
     ("biogpt_hip_generate_beam_batch", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.POINTER(GenRules),
                                                 _P, _P, _P, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_generate_contrastive", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_contrast_rank_device", C.c_int, [C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P]),
     ("biogpt_hip_rules_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(GenRules), _P]),
     ("biogpt_hip_mt19937_seed", C.c_int, [C.c_uint32, _P]),
     ("biogpt_hip_sample_candidates_host", C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, _P, _P]),
@@ -531,6 +551,29 @@ class BiogptModel:
         rows = out.reshape(-1)      # rows are [G][n_beams][n_predict as clamped]
         return [[(rows[(p * B + r) * got:(p * B + r) * got + int(ol[p * B + r])].copy(), float(scores[p * B + r])) for r in range(int(counts[p]))]
                 for p in range(G)], secs.value
+
+    def generate_contrastive(self, prompts, n_predict, top_k=4, penalty_alpha=0.6, eos_id=-1, n_batch=8):
+        """Contrastive search (transformers' generate(penalty_alpha, top_k)) over a batch of prompts (list of id lists, or one flat id list), the
+        degeneration penalty and the selection on the device ("Contrastive search").  Returns ([ids int32[len], ...] one per prompt,
+        [scores float32[len], ...] the winning score of every token); an EOS that ended a prompt's search is included."""
+        if len(prompts) and np.isscalar(prompts[0]):
+            prompts = [prompts]
+        G = len(prompts)
+        lens = np.asarray([len(p) for p in prompts], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]) if G else np.zeros(0, np.int32))
+        w = max(int(n_predict), 1)
+        out = np.zeros((max(G, 1), w), dtype=np.int32)
+        sc = np.zeros((max(G, 1), w), dtype=np.float32)
+        ol = np.zeros(max(G, 1), dtype=np.int32)
+        secs = C.c_double(0.0)
+        got = lib().biogpt_hip_generate_contrastive(self._h, flat.ctypes.data, lens.ctypes.data, G, int(n_batch), int(top_k), float(penalty_alpha), int(n_predict),
+                                                    int(eos_id), out.ctypes.data, ol.ctypes.data, sc.ctypes.data, C.byref(secs))
+        if got < 0:
+            raise BiogptError(_err())
+        if got == 0:
+            return [np.zeros(0, np.int32) for _ in range(G)], [np.zeros(0, np.float32) for _ in range(G)]
+        rows, srows = out.reshape(-1), sc.reshape(-1)      # rows are [G][n_predict as clamped]
+        return ([rows[p * got:p * got + int(ol[p])].copy() for p in range(G)], [srows[p * got:p * got + int(ol[p])].copy() for p in range(G)])
 
     def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
                         repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):

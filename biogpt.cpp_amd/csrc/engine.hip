@@ -45,6 +45,7 @@
 #include "kernels_beam.hip.h"
 #include "kernels_sample.hip.h"
 #include "kernels_rules.hip.h"
+#include "kernels_contrast.hip.h"
 #include "model_file.h"
 #include "quant_host.h"
 
@@ -282,7 +283,7 @@ struct biogpt_hip_ctx {
     int launch_parity = 0;
     // column generation (greedy batch, sampling, beam search; the driver stands before generate_greedy_batch_once): the captured steps of each mode,
     // and the pinned word pair + event pair through which the host reads a mode's count of unfinished sequences / searches between groups of steps
-    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam;
+    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam, graphs_contrast;
     int32_t *live_host = nullptr;
     hipEvent_t live_ev[2] = {};
     // sampled generation (biogpt_hip_generate_sample, kernels_sample.hip.h): the call's parameters + one generator state per sequence (SampleCtl, then
@@ -295,6 +296,11 @@ struct biogpt_hip_ctx {
     // generation rules (kernels_rules.hip.h): RulesCtl, RULES_ROWS RulesRow, then the call's prompts (one copy per prompt); allocated once, at its
     // largest, so that captured steps keep their pointers
     uint8_t *rules_buf = nullptr;
+    // contrastive search (biogpt_hip_generate_contrastive, kernels_contrast.hip.h): the step's device state at its largest (contrast_* offsets below), allocated
+    // at the first such call; the context store of contrast_groups groups -- [groups][n_positions][d_model] f32 rows, then their squared norms as doubles
+    uint8_t *contrast_buf = nullptr;
+    float *contrast_h = nullptr;
+    int contrast_groups = 0;
 
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -371,7 +377,7 @@ static void drop_graphs(ColumnGraphs &gs) {
 }
 // Captured column steps hold the pointers of seq / bk / bv / logits_all and launch shapes chosen from the options: whatever replaces one of those drops them all
 static void drop_column_graphs(biogpt_hip_ctx *c) {
-    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam}) drop_graphs(*gs);
+    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam, &c->graphs_contrast}) drop_graphs(*gs);
 }
 
 namespace {
@@ -1026,7 +1032,8 @@ constexpr int MFMA_MIN_DECODE_COLS = 48, MFMA_MIN_PASS_COLS = 64, GROUPED_ATTN_M
 // ---- a forward pass, by name --------------------------------------------------------------------------------------------------------------
 // Hidden rows (biogpt_hip_hidden / biogpt_hip_embed_batch): the first `layers` layers only, then the final LayerNorm of every column as f32 rows
 // into ln_out; ln_out == null: no LayerNorm either, the rows are the residual stream c->x itself.
-struct HiddenStage { int layers; float *ln_out; };
+// scatter_div > 0 (packed columns): column i's row goes to row (seq_id / scatter_div) * n_positions + n_past of ln_out -- the context store of contrastive search.
+struct HiddenStage { int layers; float *ln_out; int scatter_div = 0; };
 
 // What enqueue_forward runs.  Only the named constructors build one, so a combination they do not name -- shared-prefix attention without column
 // states, "logits from column k on" outside scoring -- cannot reach the launch code.
@@ -1047,7 +1054,7 @@ struct ForwardPass {
     int n_cols, t_max;
     Cols cols;
     Rows rows;
-    HiddenStage hid;        // Rows::Hidden
+    HiddenStage hid;        // Rows::Hidden; with other rows and ln_out != null: the final-LayerNorm f32 rows of every column BESIDE those rows (contrastive search)
     // Packed + All only (biogpt_hip_score_continuations): the columns read their first SeqState::pad[0] K / V rows from the slot SeqState::pad[1]
     // (attn_fast_kernel<.., SHARED>), and only the columns from head_from on get logits (rows 0 .. n_cols - head_from of logits_all): the columns in
     // front of them are prefix columns whose K / V rows alone matter
@@ -1061,8 +1068,14 @@ struct ForwardPass {
     static ForwardPass hidden(int n, int t_max, HiddenStage hs) { return {n, t_max, Cols::Context, Rows::Hidden, hs}; }
     // one decode step of n_seqs sequences, every sequence's row
     static ForwardPass decode_step(int n_seqs, int t_max) { return {n_seqs, t_max, Cols::PerSequence, Rows::All}; }
+    // the same, and every sequence's hidden row into ln_out [n_seqs][d_model]
+    static ForwardPass decode_step_hidden(int n_seqs, int t_max, float *ln_out) { return {n_seqs, t_max, Cols::PerSequence, Rows::All, HiddenStage{0, ln_out}}; }
     // packed columns (c->cols)
     static ForwardPass packed_prompts(int n, int t_max) { return {n, t_max, Cols::Packed, Rows::None}; }
+    // the same, and every column's hidden row scattered into store[(seq_id / per_prompt) * n_positions + n_past]; store == null: packed_prompts
+    static ForwardPass packed_prompts_hidden(int n, int t_max, float *store, int per_prompt) {
+        return {n, t_max, Cols::Packed, Rows::None, HiddenStage{0, store, per_prompt}};
+    }
     static ForwardPass packed_scored(int n, int t_max) { return {n, t_max, Cols::Packed, Rows::All}; }
     static ForwardPass packed_hidden(int n, int t_max, HiddenStage hs) { return {n, t_max, Cols::Packed, Rows::Hidden, hs}; }
     // the first n_prefix columns are prefix columns (all of them: no lm_head at all), the others read the prefix in place
@@ -1244,16 +1257,15 @@ bool enqueue_final(PassLaunch &k) {
     const int N = k.N, D = k.D, V = k.V;
     hipStream_t st = k.st;
     const Rows rows = k.pass.rows;
-    if (rows == Rows::None) return true;   // prompt columns: only the KV rows matter
-    if (rows == Rows::Hidden) {            // f32 rows in front of the lm_head (kernels_embed.hip.h)
-        float *const ln_out = k.pass.hid.ln_out;
-        if (!ln_out) return true;
+    if (float *const ln_out = k.pass.hid.ln_out) {      // f32 rows in front of the lm_head (kernels_embed.hip.h)
         const float *lw = dev_vec(c, c->plan.ln_w), *lb = dev_vec(c, c->plan.ln_b);
-        if (D == 1024) hipLaunchKernelGGL((bgk::ln_rows_kernel<1024>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / 1024.0, ln_out);
-        else hipLaunchKernelGGL((bgk::ln_rows_kernel<0>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / (double)D, ln_out);
+        const int div = k.pass.hid.scatter_div;
+        const bgk::SeqState *sc = div > 0 ? k.seq : nullptr;
+        if (D == 1024) hipLaunchKernelGGL((bgk::ln_rows_kernel<1024>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / 1024.0, ln_out, sc, div, k.P);
+        else hipLaunchKernelGGL((bgk::ln_rows_kernel<0>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / (double)D, ln_out, sc, div, k.P);
         HIP_TRY(false, hipGetLastError());
-        return true;
     }
+    if (rows == Rows::None || rows == Rows::Hidden) return true;   // prompt columns: only the KV rows matter; hidden rows: no lm_head
     const MatSlot &m = c->plan.lm_head;
     const MvShape s = mv_shape(m.type, m.M, m.K);
     bgk::MatvecParams p = mv_base(c, m, s);
@@ -1569,7 +1581,7 @@ void destroy(biogpt_hip_ctx *c) {
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->bbatch_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2395,10 +2407,12 @@ static bool capture_column_steps(biogpt_hip_ctx *ctx, ColumnGraphs &graphs, int 
 // Prompt ingestion for ALL prompts together (main.cpp:129-137 per prompt), packed into common passes (pack_column_passes): prompt p fills the cache slot of
 // its first column, kv_share_kernel copies its rows to its other per_prompt - 1 slots.  The pass only has to fill the K / V caches: the first step
 // re-evaluates each prompt's LAST token (same K / V row, same visible keys as its chunk gave it).
-static bool ingest_column_prompts(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *lens, int n_prompts, int n_batch, int per_prompt) {
+static bool ingest_column_prompts(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *lens, int n_prompts, int n_batch, int per_prompt,
+                                  float *hidden_store = nullptr) {
     const auto &hp = ctx->hp;
     if (!pack_column_passes(ctx, prompts, lens, n_prompts, n_batch,
-                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); }, per_prompt))
+                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts_hidden(n_cols, t_max, hidden_store, per_prompt)); },
+                            per_prompt))
         return false;
     if (per_prompt > 1) {
         hipLaunchKernelGGL(bgk::kv_share_kernel, dim3(hp.n_layer * hp.n_head, n_prompts * per_prompt, 2), dim3(256), 0, ctx->stream, ctx->seq, per_prompt, ctx->bk, ctx->bv,
@@ -3223,6 +3237,194 @@ int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t
                              double *seconds_out) {
     return biogpt_hip_generate_beam_rules(ctx, prompt, n_prompt, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, out_ids, out_lens, out_scores,
                                           seconds_out, nullptr);
+}
+
+// ---- contrastive search: G prompts x k candidates as columns of the batched decode step (kernels_contrast.hip.h) ----
+// The column generation above with contrast_rank + contrast_select + contrast_kv_row as the selection, and the hidden rows of the step's columns as a
+// second epilogue of its forward pass.  Every prompt is evaluated once, into the slot of its group's first column, and the same pass leaves the hidden rows
+// of its tokens in the group's context store; a group's first step carries the prompt's last token in all k columns (ContrastGroup::first), so
+// n_predict tokens take n_predict + 1 steps of one captured form.  The steps stop once every group has finished (ContrastCtl::n_live).  The context's own
+// K / V cache, position and logits row are left alone.
+constexpr int CONTRAST_COLS = 512;    // columns of a call, at most (and so groups: top_k = 1)
+static int contrast_slabs(const biogpt_hip_ctx *c) { return (c->hp.n_positions + bgk::CT_SLAB - 1) / bgk::CT_SLAB; }
+static size_t contrast_grp_off() { return sizeof(bgk::ContrastCtl); }
+static size_t contrast_cand_off() { return (contrast_grp_off() + sizeof(bgk::ContrastGroup) * CONTRAST_COLS + 15) & ~(size_t)15; }
+static size_t contrast_slab_off(const biogpt_hip_ctx *c) { return contrast_cand_off() + (size_t)CONTRAST_COLS * c->hp.d_model * 4; }
+static size_t contrast_score_off(const biogpt_hip_ctx *c) { return contrast_slab_off(c) + (size_t)CONTRAST_COLS * contrast_slabs(c) * bgk::CT_MAX_K * 4; }
+static size_t contrast_buf_bytes(const biogpt_hip_ctx *c) { return contrast_score_off(c) + (size_t)CONTRAST_COLS * c->hp.n_positions * 4; }
+
+// the rank kernel's dynamic LDS: the candidate rows, at least the room of its closing exchange; above 64 KB it has to be asked for
+static bool contrast_rank_lds(std::set<const void *> *done, int k, int d, size_t *bytes) {
+    *bytes = std::max((size_t)k * d * 4, (size_t)4 * bgk::CT_MAX_K * 4);
+    const void *fn = reinterpret_cast<const void *>(bgk::contrast_rank_kernel);
+    if (*bytes >= 64 * 1024 && !(done && done->count(fn))) {
+        HIP_TRY(false, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bgk::CT_MAX_K * bgk::CT_MAX_D * 4));
+        if (done) done->insert(fn);
+    }
+    return true;
+}
+
+static int generate_contrastive_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_batch, int32_t top_k,
+                                     float penalty_alpha, int32_t n_predict, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, float *out_scores,
+                                     double *seconds_out) {
+    clear_error();
+    // (what can be judged without the model comes first: these fail the same way with no context and no device)
+    if (!prompts) BG_FAIL(-1, "null argument: prompts");
+    if (!prompt_lens) BG_FAIL(-1, "null argument: prompt_lens");
+    if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
+    if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
+    if (n_prompts < 1) BG_FAIL(-1, "n_prompts must be >= 1");
+    if (top_k < 1 || top_k > bgk::CT_MAX_K) BG_FAIL(-1, "top_k must be in [1, %d]", bgk::CT_MAX_K);
+    if ((int64_t)n_prompts * top_k > CONTRAST_COLS) BG_FAIL(-1, "n_prompts x top_k must be at most %d", CONTRAST_COLS);   // each column owns a full F32 KV cache
+    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
+    if (!(penalty_alpha >= 0.0f && penalty_alpha <= 1.0f)) BG_FAIL(-1, "penalty_alpha must be in [0, 1]");
+    if (eos_id < -1) BG_FAIL(-1, "eos_id %d out of range: must be a token id, or -1 for none", eos_id);
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    const int G = n_prompts, K = top_k, n_seqs = G * K;
+    if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_prompts x top_k (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
+    const auto &hp = ctx->hp;
+    const int P = hp.n_positions, V = hp.n_vocab, D = hp.d_model;
+    if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
+    if (!check_fast_chain(ctx, "contrastive search")) return -1;
+    if (V < K) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than top_k candidates", V);
+    int max_len;
+    long total;
+    if (!check_prompts(ctx, prompts, prompt_lens, G, "prompt", &max_len, &total)) return -1;
+    n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
+    if (n_predict <= 0) return 0;
+    // every argument has been judged: from here on the call may take (and must give back) the device's pipeline slot and the column-per-XCD hold
+    XpCallScope xp_scope(ctx);
+    XcBatchScope xc_scope{ctx};
+    if (!begin_column_call(ctx, n_seqs, total)) return -2;
+    if (!ctx->contrast_buf) HIP_TRY(-2, hipMalloc(&ctx->contrast_buf, contrast_buf_bytes(ctx)));
+    if (G > ctx->contrast_groups) {      // the context store: new pointers, so the captured steps go
+        if (ctx->contrast_h) (void)hipFree(ctx->contrast_h);
+        ctx->contrast_h = nullptr; ctx->contrast_groups = 0;
+        drop_graphs(ctx->graphs_contrast);
+        const size_t bytes = (size_t)G * P * ((size_t)D * 4 + 8);
+        if (hipMalloc(&ctx->contrast_h, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            BG_FAIL(-2, "contrastive search: no room for the context store of %d prompts (%zu bytes: n_prompts x n_positions x (d_model f32 + one double))", G, bytes);
+        }
+        ctx->contrast_groups = G;
+    }
+    column_graphs_for(ctx->graphs_contrast, G, K);
+    bgk::ContrastCtl *const ctl = reinterpret_cast<bgk::ContrastCtl *>(ctx->contrast_buf);
+    bgk::ContrastGroup *const grp = reinterpret_cast<bgk::ContrastGroup *>(ctx->contrast_buf + contrast_grp_off());
+    float *const cand = reinterpret_cast<float *>(ctx->contrast_buf + contrast_cand_off());
+    float *const slab_max = reinterpret_cast<float *>(ctx->contrast_buf + contrast_slab_off(ctx));
+    float *const scores = reinterpret_cast<float *>(ctx->contrast_buf + contrast_score_off(ctx));
+    float *const H = ctx->contrast_h;
+    double *const Hn = reinterpret_cast<double *>(H + (size_t)ctx->contrast_groups * P * D);
+    const int n_slabs = contrast_slabs(ctx);
+    {   // the call's parameters and every group's initial state: the prompt without its last token is the context, the first step appends that token's row
+        std::vector<uint8_t> h(contrast_grp_off() + sizeof(bgk::ContrastGroup) * (size_t)G, 0);
+        bgk::ContrastCtl hc{};
+        hc.top_k = K; hc.eos_id = eos_id; hc.n_live = G; hc.alpha = penalty_alpha;
+        std::memcpy(h.data(), &hc, sizeof(hc));
+        bgk::ContrastGroup *hg = reinterpret_cast<bgk::ContrastGroup *>(h.data() + contrast_grp_off());
+        for (int p = 0; p < G; p++) { hg[p].len = prompt_lens[p] - 1; hg[p].first = 1; hg[p].copy_pos = -1; }
+        HIP_TRY(-2, hipMemcpy(ctx->contrast_buf, h.data(), h.size(), hipMemcpyHostToDevice));
+    }
+    if (!upload_column_starts(ctx, prompts, prompt_lens, G, K)) return -2;
+    size_t rank_lds;
+    if (!contrast_rank_lds(&ctx->lds_attr_done, K, D, &rank_lds)) return -2;
+
+    const int64_t seq_stride = (int64_t)hp.n_layer * P * D;
+    const ColumnStep step = [&](int t_max) -> bool {
+        if (!enqueue_forward(ctx, ForwardPass::decode_step_hidden(n_seqs, t_max, cand))) return false;
+        hipLaunchKernelGGL(bgk::contrast_rank_kernel, dim3(n_slabs, G), dim3(bgk::CT_THREADS), rank_lds, ctx->stream, cand, H, Hn, grp, K, D, P, slab_max);
+        hipLaunchKernelGGL(bgk::contrast_select_kernel, dim3(G), dim3(bgk::CT_THREADS), 0, ctx->stream, cand, ctx->logits_all, V, V, ctl, grp, slab_max, n_slabs, H, Hn, D, P,
+                           ctx->seq, ctx->seq_gen, P, scores);
+        if (K > 1)
+            hipLaunchKernelGGL(bgk::contrast_kv_row_kernel, dim3(hp.n_layer * hp.n_head, G), dim3(256), 0, ctx->stream, grp, K, ctx->bk, ctx->bv, seq_stride, P, D / hp.n_head);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    const int n_steps = n_predict + 1;      // the prompt's last token, then one step per generated token
+    const int gset = 6 * choose_column_path(ctx, n_seqs, max_len);
+    bool use_graph;
+    if (!capture_column_steps(ctx, ctx->graphs_contrast, gset, max_len, n_steps, step, &use_graph)) return -2;
+
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!ingest_column_prompts(ctx, prompts, prompt_lens, G, n_batch, K, H)) return -2;
+    hipLaunchKernelGGL(bgk::contrast_norms_kernel, dim3(n_slabs, G), dim3(bgk::CT_THREADS), 0, ctx->stream, H, Hn, grp, D, P);
+    HIP_TRY(-2, hipGetLastError());
+    if (!run_column_steps(ctx, ctx->graphs_contrast, gset, use_graph, max_len, n_steps, step, eos_id >= 0 ? &ctl->n_live : nullptr)) return -2;
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    std::vector<int32_t> gen((size_t)n_seqs * P);
+    std::vector<float> sc((size_t)G * P);
+    std::vector<bgk::SeqState> hs((size_t)n_seqs);
+    HIP_TRY(-2, hipMemcpy(gen.data(), ctx->seq_gen, gen.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(sc.data(), scores, sc.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(hs.data(), ctx->seq, sizeof(bgk::SeqState) * n_seqs, hipMemcpyDeviceToHost));
+    for (int p = 0; p < G; p++) {      // a group's output is the history of its first column
+        const int len = std::max(0, std::min(hs[(size_t)p * K].n_gen, n_predict));
+        int32_t *o = out_ids + (size_t)p * n_predict;
+        std::fill(o, o + n_predict, -1);
+        std::memcpy(o, gen.data() + (size_t)p * K * P, (size_t)len * 4);
+        out_lens[p] = len;
+        if (out_scores) {
+            std::fill(out_scores + (size_t)p * n_predict, out_scores + (size_t)(p + 1) * n_predict, 0.0f);
+            std::memcpy(out_scores + (size_t)p * n_predict, sc.data() + (size_t)p * P, (size_t)len * 4);
+        }
+    }
+    return n_predict;
+}
+
+int biogpt_hip_generate_contrastive(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_batch, int32_t top_k,
+                                    float penalty_alpha, int32_t n_predict, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, float *out_scores,
+                                    double *seconds_out) {
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_contrastive_once(ctx, prompts, prompt_lens, n_prompts, n_batch, top_k, penalty_alpha, n_predict, eos_id, out_ids, out_lens, out_scores, seconds_out);
+    });
+}
+
+// contrast_rank_kernel + contrast_pick over rows held in host memory (tests of the kernels themselves): k candidate rows against T context rows, no model
+int biogpt_hip_contrast_rank_device(int device, const float *cand, const float *ctx_rows, int32_t k, int32_t T, int32_t d, const float *probs, float alpha,
+                                    float *pen_out, float *score_out, int32_t *winner_out) {
+    clear_error();
+    if (!cand || !ctx_rows || !probs || !pen_out || !score_out || !winner_out) BG_FAIL(-1, "null argument");
+    if (k < 1 || k > bgk::CT_MAX_K) BG_FAIL(-1, "k must be in [1, %d]", bgk::CT_MAX_K);
+    if (T < 1 || T > (1 << 20)) BG_FAIL(-1, "T must be in [1, %d]", 1 << 20);
+    if (d < 4 || d > bgk::CT_MAX_D || d % 4) BG_FAIL(-1, "d must be a multiple of 4 in [4, %d]", bgk::CT_MAX_D);
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) BG_FAIL(-1, "alpha must be in [0, 1]");
+    HIP_TRY(-2, hipSetDevice(device));
+    const int n_slabs = (T + bgk::CT_SLAB - 1) / bgk::CT_SLAB;
+    // [context rows | candidate rows | norms | slab maxima | probabilities | group | out]
+    const size_t o_c = (size_t)T * d * 4, o_n = o_c + (size_t)k * d * 4, o_s = o_n + (size_t)T * 8, o_p = o_s + (size_t)n_slabs * bgk::CT_MAX_K * 4;
+    const size_t o_g = o_p + bgk::CT_MAX_K * 4, o_o = o_g + sizeof(bgk::ContrastGroup), bytes = o_o + (2 * bgk::CT_MAX_K + 1) * 4;
+    uint8_t *dv = nullptr;
+    HIP_TRY(-2, hipMalloc(&dv, bytes));
+    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{dv};
+    bgk::ContrastGroup hg{};
+    hg.len = T;
+    HIP_TRY(-2, hipMemcpy(dv, ctx_rows, o_c, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(dv + o_c, cand, (size_t)k * d * 4, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(dv + o_p, probs, (size_t)k * 4, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(dv + o_g, &hg, sizeof(hg), hipMemcpyHostToDevice));
+    const float *H = reinterpret_cast<const float *>(dv);
+    double *Hn = reinterpret_cast<double *>(dv + o_n);
+    float *slab_max = reinterpret_cast<float *>(dv + o_s);
+    const bgk::ContrastGroup *grp = reinterpret_cast<const bgk::ContrastGroup *>(dv + o_g);
+    size_t rank_lds;
+    if (!contrast_rank_lds(nullptr, k, d, &rank_lds)) return -2;
+    hipLaunchKernelGGL(bgk::contrast_norms_kernel, dim3(n_slabs, 1), dim3(bgk::CT_THREADS), 0, 0, H, Hn, grp, d, T);
+    hipLaunchKernelGGL(bgk::contrast_rank_kernel, dim3(n_slabs, 1), dim3(bgk::CT_THREADS), rank_lds, 0, reinterpret_cast<const float *>(dv + o_c), H, Hn, grp, k, d, T, slab_max);
+    hipLaunchKernelGGL(bgk::contrast_pick_kernel, dim3(1), dim3(bgk::CT_THREADS), 0, 0, slab_max, grp, k, reinterpret_cast<const float *>(dv + o_p), alpha,
+                       reinterpret_cast<float *>(dv + o_o));
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    float out[2 * bgk::CT_MAX_K + 1];
+    HIP_TRY(-2, hipMemcpy(out, dv + o_o, (size_t)(2 * k + 1) * 4, hipMemcpyDeviceToHost));
+    std::memcpy(pen_out, out, (size_t)k * 4);
+    std::memcpy(score_out, out + k, (size_t)k * 4);
+    std::memcpy(winner_out, out + 2 * k, 4);
+    return 0;
 }
 
 // rules_rows_kernel over rows held in host memory (tests of the kernel itself): row r's history is hist_lens[r] tokens of `hist` (the histories

@@ -25,11 +25,13 @@ namespace bgk {
 
 enum PoolMode : int { POOL_NONE = 0, POOL_LAST = 1, POOL_MEAN = 2 };
 
-// x: [N][ldx] floats (N = gridDim.x), out: [N][k] floats; inv_k = 1.0 / k
+// x: [N][ldx] floats (N = gridDim.x), out: [N][k] floats; inv_k = 1.0 / k.  cols != null: column i's row is row (cols[i].seq_id / slot_div) * P + cols[i].n_past
+// of out (the context store of contrastive search: one run of P rows per group of slot_div cache slots)
 template <int K>
 __global__ __launch_bounds__(256) void ln_rows_kernel(const float *x, int ldx, int k, const float *ln_w, const float *ln_b, float eps, double inv_k,
-                                                      float *out) {
+                                                      float *out, const SeqState *cols, int slot_div, int P) {
     const int col = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t orow = cols ? (size_t)(cols[col].seq_id / slot_div) * P + cols[col].n_past : (size_t)col;
     const float4 *xcol = reinterpret_cast<const float4 *>(x + (size_t)col * ldx);
     if constexpr (K == 1024) {
         constexpr int NJJ = K / 4 / 64, NSHARE = NJJ / 4;
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const float *x, int ldx, i
             v.y = __fadd_rn(__fmul_rn(lw4[i].y, __fmul_rn(__fsub_rn(v.y, mean), scale)), lb4[i].y);
             v.z = __fadd_rn(__fmul_rn(lw4[i].z, __fmul_rn(__fsub_rn(v.z, mean), scale)), lb4[i].z);
             v.w = __fadd_rn(__fmul_rn(lw4[i].w, __fmul_rn(__fsub_rn(v.w, mean), scale)), lb4[i].w);
-            reinterpret_cast<float4 *>(out + (size_t)col * K)[ch] = v;
+            reinterpret_cast<float4 *>(out + orow * K)[ch] = v;
         }
     } else {
         const int nch = k >> 2;
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const float *x, int ldx, i
             v.y = __fadd_rn(__fmul_rn(w.y, __fmul_rn(__fsub_rn(v.y, mean), scale)), b.y);
             v.z = __fadd_rn(__fmul_rn(w.z, __fmul_rn(__fsub_rn(v.z, mean), scale)), b.z);
             v.w = __fadd_rn(__fmul_rn(w.w, __fmul_rn(__fsub_rn(v.w, mean), scale)), b.w);
-            reinterpret_cast<float4 *>(out + (size_t)col * k)[ch] = v;
+            reinterpret_cast<float4 *>(out + orow * k)[ch] = v;
         }
     }
 }

@@ -175,47 +175,19 @@ __device__ __forceinline__ void sample_scan_row(const float *row, int n_vocab, F
 // (av, ai) comes before (bv, bi) in selection order
 __device__ __forceinline__ bool sample_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
 
-// logits: [rows][ldl] (row r = column r = sequence r); seq / sq: the rows' states; seq_gen: [row][gen_stride] token histories
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float *logits, int ldl, int n_vocab, SampleCtl *ctl, SampleSeq *sq,
-                                                                     SeqState *seq, int32_t *seq_gen, int gen_stride) {
+// The selection of sample_rows_kernel (and of contrast_select_kernel, kernels_contrast.hip.h): the row's best K <= SAMPLE_MAX_K elements into top_v / top_i
+// (LDS of the caller), value descending, equal values lower id first; NaNs never.  Called by all SAMPLE_THREADS threads; returns how many there are
+// (uniform), visible to every thread on return.
+__device__ __forceinline__ int sample_topk(const float *row, int n_vocab, int K, float *top_v, int *top_i) {
     __shared__ float t_v[SAMPLE_THREADS];
     __shared__ int t_i[SAMPLE_THREADS];
     __shared__ float c_v[SAMPLE_CAND_CAP];
     __shared__ int c_i[SAMPLE_CAND_CAP];
-    __shared__ float top_v[SAMPLE_MAX_K];
-    __shared__ int top_i[SAMPLE_MAX_K];
-    __shared__ uint32_t mt_old[MT_N], mt_new[MT_N];
-    __shared__ SampleWork work;
-    __shared__ double work_p[SAMPLE_MAX_K];
     __shared__ float s_thr_v;
     __shared__ int s_thr_i, s_n;
     __shared__ float r_v[SAMPLE_THREADS / 64];
     __shared__ int r_i[SAMPLE_THREADS / 64];
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    SampleSeq *const me = sq + r;
-    if (me->finished) return;
-    const float *row = logits + (size_t)r * ldl;
-    const int K = min(min(ctl->top_k, SAMPLE_MAX_K), n_vocab);
-
-    // ---- the generator: an exhausted block of outputs is regenerated by the whole workgroup (the words of [0, 227), [227, 454), [454, 623)
-    //      and 623 depend on the old block and on the ranges before them only) ----
-    if (me->mt[MT_N] == (uint32_t)MT_N) {
-        constexpr int D = MT_N - MT_M;
-        for (int i = tid; i < MT_N; i += SAMPLE_THREADS) mt_old[i] = me->mt[i];
-        __syncthreads();
-        if (tid < D) mt_new[tid] = mt_mix(mt_old[tid], mt_old[tid + 1], mt_old[tid + MT_M]);
-        __syncthreads();
-        if (tid < D) mt_new[tid + D] = mt_mix(mt_old[tid + D], mt_old[tid + D + 1], mt_new[tid]);
-        __syncthreads();
-        if (tid + 2 * D < MT_N - 1) mt_new[tid + 2 * D] = mt_mix(mt_old[tid + 2 * D], mt_old[tid + 2 * D + 1], mt_new[tid + D]);
-        __syncthreads();
-        if (tid == 0) mt_new[MT_N - 1] = mt_mix(mt_old[MT_N - 1], mt_new[0], mt_new[MT_M - 1]);
-        __syncthreads();
-        for (int i = tid; i < MT_N; i += SAMPLE_THREADS) me->mt[i] = mt_new[i];
-        if (tid == 0) me->mt[MT_N] = 0;
-        __syncthreads();
-    }
-
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // ---- pass 1: the bound ----
     float mv = -INFINITY;
     int mi = 0x7fffffff;
@@ -278,6 +250,44 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float
         }
         __syncthreads();
     }
+
+    return k_eff;
+}
+
+// logits: [rows][ldl] (row r = column r = sequence r); seq / sq: the rows' states; seq_gen: [row][gen_stride] token histories
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float *logits, int ldl, int n_vocab, SampleCtl *ctl, SampleSeq *sq,
+                                                                     SeqState *seq, int32_t *seq_gen, int gen_stride) {
+    __shared__ float top_v[SAMPLE_MAX_K];
+    __shared__ int top_i[SAMPLE_MAX_K];
+    __shared__ uint32_t mt_old[MT_N], mt_new[MT_N];
+    __shared__ SampleWork work;
+    __shared__ double work_p[SAMPLE_MAX_K];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    SampleSeq *const me = sq + r;
+    if (me->finished) return;
+    const float *row = logits + (size_t)r * ldl;
+    const int K = min(min(ctl->top_k, SAMPLE_MAX_K), n_vocab);
+
+    // ---- the generator: an exhausted block of outputs is regenerated by the whole workgroup (the words of [0, 227), [227, 454), [454, 623)
+    //      and 623 depend on the old block and on the ranges before them only) ----
+    if (me->mt[MT_N] == (uint32_t)MT_N) {
+        constexpr int D = MT_N - MT_M;
+        for (int i = tid; i < MT_N; i += SAMPLE_THREADS) mt_old[i] = me->mt[i];
+        __syncthreads();
+        if (tid < D) mt_new[tid] = mt_mix(mt_old[tid], mt_old[tid + 1], mt_old[tid + MT_M]);
+        __syncthreads();
+        if (tid < D) mt_new[tid + D] = mt_mix(mt_old[tid + D], mt_old[tid + D + 1], mt_new[tid]);
+        __syncthreads();
+        if (tid + 2 * D < MT_N - 1) mt_new[tid + 2 * D] = mt_mix(mt_old[tid + 2 * D], mt_old[tid + 2 * D + 1], mt_new[tid + D]);
+        __syncthreads();
+        if (tid == 0) mt_new[MT_N - 1] = mt_mix(mt_old[MT_N - 1], mt_new[0], mt_new[MT_M - 1]);
+        __syncthreads();
+        for (int i = tid; i < MT_N; i += SAMPLE_THREADS) me->mt[i] = mt_new[i];
+        if (tid == 0) me->mt[MT_N] = 0;
+        __syncthreads();
+    }
+
+    const int k_eff = sample_topk(row, n_vocab, K, top_v, top_i);
 
     // ---- the draw ----
     int id = 0;

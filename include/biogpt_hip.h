@@ -329,6 +329,33 @@ int biogpt_hip_rules_rows_device(int device, int32_t mode /* 0 logits, 1 log-pro
                                  const int32_t *hist /* concatenated */, const int32_t *hist_lens, const int32_t *prompt_lens, int32_t eos_id,
                                  const biogpt_hip_gen_rules *rules, float *rows_out);
 
+/* Contrastive search (Su et al. 2022; transformers' generate(penalty_alpha, top_k)): n_prompts deterministic searches in one call.  Group g owns the
+ * top_k columns and K / V cache slots [g * top_k, (g + 1) * top_k) and a context store H_g: one f32 hidden row (biogpt_hip_hidden's row, after the
+ * final LayerNorm) per context token and its squared norm as a double.  The prompt pass (chunks of n_batch) leaves the rows of prompt tokens
+ * 0 .. L - 2 in H_g; the first step evaluates the last prompt token, appends its row, and its logits row l gives the first candidates: the top_k
+ * largest values (value descending, lower id first on ties), p_j = (float)(exp((double)l_j - (double)m) / S) with the row maximum m and exponential
+ * sum S of biogpt_hip_score's log-softmax.  Every later step feeds candidate j to column j at position len(H_g), which gives its hidden row h_j
+ * and logits row; pen_j = max_i sim(h_j, H_g[i]), sim(a, b) = (float)(dot / sqrt(na * nb)) from double sums of exact f32 products (0 if a norm is 0);
+ * score_j = (float)((1 - (double)alpha) * (double)p_j - (double)alpha * (double)pen_j); the winner is the highest score, the lowest j on ties.
+ * Its id is the next token, its row joins H_g, its logits row gives the next candidates, its K / V row of that position is copied to the group's
+ * other slots.  A winner equal to eos_id ends the group (the EOS is part of the output).  n generated tokens take n + 1 steps; n_predict is
+ * clamped to n' = n_positions - max(prompt_lens).  A prompt's result does not depend on what else is in the call; top_k = 1 or penalty_alpha = 0
+ * give the ids of biogpt_hip_generate_greedy_batch.  No rules or warpers.  out_ids is [n_prompts][returned n_predict] (-1 past a prompt's length),
+ * out_lens [n_prompts], out_scores (may be NULL) [n_prompts][returned n_predict] the winning score of every token (0 past the length).
+ * top_k in [1, 16], penalty_alpha in [0, 1], n_prompts * top_k in [1, 512] (each column owns a full F32 KV cache), eos_id in [-1, n_vocab).  The
+ * context's own K / V cache, position and logits row are left alone.  Needs the BioGPT-base fast chain (block-quantized weights); anything else
+ * fails with -1.  Returns the clamped n_predict, 0 if that is <= 0, < 0 on error (argument errors, -1, the message names the field, come before
+ * any HIP call; -2 names the size of a context store that did not fit). */
+int biogpt_hip_generate_contrastive(biogpt_hip_ctx *ctx, const int32_t *prompts /* concatenated */, const int32_t *prompt_lens, int32_t n_prompts,
+                                    int32_t n_batch, int32_t top_k, float penalty_alpha, int32_t n_predict, int32_t eos_id /* -1: none */,
+                                    int32_t *out_ids /* [n_prompts][returned n_predict], -1 filled */, int32_t *out_lens /* [n_prompts] */,
+                                    float *out_scores /* [n_prompts][returned n_predict], may be NULL */, double *seconds_out);
+
+/* The penalty and selection kernels of contrastive search over rows held in host memory, no model: k <= 16 candidate rows and T context rows of d
+ * floats (4 | d, d <= 1024), probs[k] and alpha as above.  pen_out[k], score_out[k], *winner_out.  For tests of the kernels themselves. */
+int biogpt_hip_contrast_rank_device(int device, const float *cand /* [k][d] */, const float *ctx_rows /* [T][d] */, int32_t k, int32_t T, int32_t d,
+                                    const float *probs /* [k] */, float alpha, float *pen_out, float *score_out, int32_t *winner_out);
+
 /* ---- sequence scoring (no counterpart in the reference) ---------------------------------------
  * biogpt_hip_score: teacher-forced, causal log-probabilities of a sequence.  Row i sees the keys [0, n_past + i] -- what
  * biogpt_hip_eval_prompt(..., n_batch = 1) and a loop of single-token biogpt_hip_eval calls compute; NOT the unmasked chunk of
