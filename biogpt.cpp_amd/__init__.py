@@ -97,6 +97,69 @@ def rules_rows(rows, histories, prompt_lens=None, mode=0, eos_id=-1, device=0, *
     return out
 
 
+def logprob_rows(rows, targets, device=0):
+    """logprob_rows_kernel on rows held in host memory (biogpt_hip_logprob_rows_device): rows float32 [n][n_vocab], targets [n] (-1: none).
+    Returns (lp float32[n], argmax int32[n], logit float32[n])."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv = a.shape
+    t = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+    if t.size != n:
+        raise BiogptError("logprob_rows: one target per row (%d != %d)" % (t.size, n))
+    lp, am, lg = np.empty(n, np.float32), np.empty(n, np.int32), np.empty(n, np.float32)
+    if lib().biogpt_hip_logprob_rows_device(int(device), a.ctypes.data, n, nv, t.ctypes.data, lp.ctypes.data, am.ctypes.data, lg.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return lp, am, lg
+
+
+def beam_rows(rows, n_beams, run_score, given=False, first_step=False, device=0):
+    """beam_group_rows_kernel on rows held in host memory (biogpt_hip_beam_rows_device): rows float32 [G * n_beams][n_vocab], run_score [G * n_beams].
+    Returns (score float32, col int32, id int32), each [G * n_beams][2 * n_beams]; rows the kernel left alone hold (NaN, -1, -1)."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv = a.shape
+    rs = np.ascontiguousarray(run_score, dtype=np.float32).reshape(-1)
+    if rs.size != n:
+        raise BiogptError("beam_rows: one run_score per row (%d != %d)" % (rs.size, n))
+    K = 2 * int(n_beams)
+    sc, col, ids = np.empty((n, K), np.float32), np.empty((n, K), np.int32), np.empty((n, K), np.int32)
+    if lib().biogpt_hip_beam_rows_device(int(device), a.ctypes.data, n, nv, 1 if given else 0, int(n_beams), rs.ctypes.data, 1 if first_step else 0,
+                                         sc.ctypes.data, col.ctypes.data, ids.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return sc, col, ids
+
+
+def beam_table(table, start_tokens, prompt_lens, n_beams, n_predict, eos_id=-1, length_penalty=1.0, early_stopping=True, given=True, max_steps=None,
+               device=0):
+    """A beam search over the beam kernels with a table for a model (biogpt_hip_beam_table_device): table float32 [R][n_vocab], one start token and
+    prompt length per group.  Returns (results, state): results = per group [(ids, score), ...] best first, or None if max_steps ended the run first;
+    state = dict of token, n_gen, run_score, rank [G][B], hist [G][B][n_predict], done, step [G], k, v [G][B][2][P][4]."""
+    a = np.ascontiguousarray(table, dtype=np.float32)
+    R, nv = a.shape
+    st = np.ascontiguousarray(start_tokens, dtype=np.int32).reshape(-1)
+    pl = np.ascontiguousarray(prompt_lens, dtype=np.int32).reshape(-1)
+    if st.size != pl.size or st.size < 1:
+        raise BiogptError("beam_table: one start token and one prompt length per group")
+    G, B, n = int(st.size), int(n_beams), int(n_predict)
+    P = int(pl.max()) + n
+    ids = np.empty((G, max(B, 0), max(n, 0)), np.int32)
+    lens, scores, counts = np.empty((G, max(B, 0)), np.int32), np.empty((G, max(B, 0)), np.float32), np.empty(G, np.int32)
+    shape = (G, max(B, 0))
+    tok, ngen, rank, rs = np.empty(shape, np.int32), np.empty(shape, np.int32), np.empty(shape, np.int32), np.empty(shape, np.float32)
+    hist = np.empty(shape + (max(n, 0),), np.int32)
+    done, step = np.empty(G, np.int32), np.empty(G, np.int32)
+    kv = np.empty((2,) + shape + (2, max(P, 1), 4), np.float32)
+    rc = lib().biogpt_hip_beam_table_device(int(device), a.ctypes.data, R, nv, 1 if given else 0, st.ctypes.data, pl.ctypes.data, G, B, n, int(eos_id),
+                                            float(length_penalty), 1 if early_stopping else 0, n if max_steps is None else int(max_steps), ids.ctypes.data,
+                                            lens.ctypes.data, scores.ctypes.data, counts.ctypes.data, tok.ctypes.data, ngen.ctypes.data, hist.ctypes.data,
+                                            rs.ctypes.data, rank.ctypes.data, done.ctypes.data, step.ctypes.data, kv.ctypes.data)
+    if rc < 0:
+        raise BiogptError(_err())
+    state = dict(token=tok, n_gen=ngen, run_score=rs, rank=rank, hist=hist, done=done, step=step, k=kv[0], v=kv[1])
+    if rc == 0:
+        return None, state
+    results = [[([int(t) for t in ids[g, r, :lens[g, r]]], np.float32(scores[g, r])) for r in range(int(counts[g]))] for g in range(G)]
+    return results, state
+
+
 def contrast_rank(cand, ctx_rows, probs, alpha, device=0):
     """The penalty and selection kernels of contrastive search on rows held in host memory (biogpt_hip_contrast_rank_device): cand float32 [k][d],
     ctx_rows float32 [T][d], probs float32 [k].  Returns (pen float32[k], score float32[k], winner)."""
@@ -193,6 +256,10 @@ SYMBOLS = [
     ("biogpt_hip_generate_contrastive", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_contrast_rank_device", C.c_int, [C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P]),
     ("biogpt_hip_rules_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(GenRules), _P]),
+    ("biogpt_hip_logprob_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    ("biogpt_hip_beam_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    ("biogpt_hip_beam_table_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                              C.c_int32, C.c_int32] + [_P] * 12),
     ("biogpt_hip_mt19937_seed", C.c_int, [C.c_uint32, _P]),
     ("biogpt_hip_sample_candidates_host", C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, _P, _P]),
     ("biogpt_hip_sample_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P]),

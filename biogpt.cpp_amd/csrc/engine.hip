@@ -3079,12 +3079,46 @@ static size_t bbatch_ctl_off() { return bbatch_skip_off() + 4 * (size_t)BBATCH_C
 static size_t bbatch_cand_off() { return bbatch_ctl_off() + sizeof(bgk::BeamCtl) * BBATCH_COLS; }
 static size_t bbatch_ids_off() { return bbatch_cand_off() + sizeof(bgk::BeamCand) * BBATCH_COLS * 2 * bgk::BEAM_MAX; }
 
-static void launch_beam_group_rows(biogpt_hip_ctx *c, int G, int B, bool given) {
-    const int V = c->hp.n_vocab, K = 2 * B;
-    const bgk::BeamCtl *ctl = reinterpret_cast<const bgk::BeamCtl *>(c->bbatch_buf + bbatch_ctl_off());
-    bgk::BeamBatchHdr *hdr = reinterpret_cast<bgk::BeamBatchHdr *>(c->bbatch_buf);
-    bgk::BeamCand *cand = reinterpret_cast<bgk::BeamCand *>(c->bbatch_buf + bbatch_cand_off());
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(G * B), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, ctl, B, hdr, cand); };
+// The buffers a beam step works on: the context's (beam_bufs_of) or a test entry's own (biogpt_hip_beam_rows_device, biogpt_hip_beam_table_device).
+struct BeamBufs {
+    hipStream_t stream;
+    const float *logits;        // [G * B][n_vocab]
+    int n_vocab;
+    bgk::BeamBatchHdr *hdr;
+    bgk::BeamFork *forks;       // room for G * (B - 1)
+    int32_t *col_skip;          // [G * B]
+    bgk::BeamCtl *ctl;          // [G]
+    bgk::BeamCand *cand;        // [G * B][2 * B]
+    int32_t *pool_ids;          // [G * B][ctl->ids_stride]
+    bgk::SeqState *seq;         // [G * B]
+    int32_t *seq_gen;           // [G * B][gen_stride]
+    int gen_stride;
+    float *bk, *bv;             // [G * B] cache slots of seq_stride floats: kv_runs (layer, head) runs of P * dk
+    int64_t seq_stride;
+    int kv_runs, P, dk;
+};
+
+static BeamBufs beam_bufs_of(biogpt_hip_ctx *c) {
+    const auto &hp = c->hp;
+    const int P = hp.n_positions;
+    BeamBufs b{};
+    b.stream = c->stream;
+    b.logits = c->logits_all; b.n_vocab = hp.n_vocab;
+    b.hdr = reinterpret_cast<bgk::BeamBatchHdr *>(c->bbatch_buf);
+    b.forks = reinterpret_cast<bgk::BeamFork *>(c->bbatch_buf + bbatch_forks_off());
+    b.col_skip = reinterpret_cast<int32_t *>(c->bbatch_buf + bbatch_skip_off());
+    b.ctl = reinterpret_cast<bgk::BeamCtl *>(c->bbatch_buf + bbatch_ctl_off());
+    b.cand = reinterpret_cast<bgk::BeamCand *>(c->bbatch_buf + bbatch_cand_off());
+    b.pool_ids = reinterpret_cast<int32_t *>(c->bbatch_buf + bbatch_ids_off());
+    b.seq = c->seq; b.seq_gen = c->seq_gen; b.gen_stride = P;
+    b.bk = c->bk; b.bv = c->bv;
+    b.seq_stride = (int64_t)hp.n_layer * P * hp.d_model; b.kv_runs = hp.n_layer * hp.n_head; b.P = P; b.dk = hp.d_model / hp.n_head;
+    return b;
+}
+
+static void launch_beam_group_rows(const BeamBufs &b, int G, int B, bool given) {
+    const int V = b.n_vocab, K = 2 * B;
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(G * B), dim3(bgk::LP_THREADS), 0, b.stream, b.logits, V, V, b.ctl, B, b.hdr, b.cand); };
     if (given) {
         if (K <= 8) go(bgk::beam_group_rows_kernel<8, true>);
         else if (K <= 16) go(bgk::beam_group_rows_kernel<16, true>);
@@ -3094,25 +3128,39 @@ static void launch_beam_group_rows(biogpt_hip_ctx *c, int G, int B, bool given) 
     else go(bgk::beam_group_rows_kernel<32, false>);
 }
 
-static bool enqueue_beam_group_select(biogpt_hip_ctx *c, int G, int B, bool rules) {
-    const auto &hp = c->hp;
-    const int P = hp.n_positions;
-    bgk::BeamBatchHdr *hdr = reinterpret_cast<bgk::BeamBatchHdr *>(c->bbatch_buf);
-    bgk::BeamFork *forks = reinterpret_cast<bgk::BeamFork *>(c->bbatch_buf + bbatch_forks_off());
-    int32_t *col_skip = reinterpret_cast<int32_t *>(c->bbatch_buf + bbatch_skip_off());
-    if (rules) {
-        if (!enqueue_rules(c, G * B, col_skip, 1)) return false;
-        launch_beam_group_rows(c, G, B, true);
-    } else launch_beam_group_rows(c, G, B, false);
+// rows -> select -> fork.  given: the rows hold log-probabilities already (the rules kernel has run over them)
+static bool enqueue_beam_group_select(const BeamBufs &b, int G, int B, bool given) {
+    launch_beam_group_rows(b, G, B, given);
     HIP_TRY(false, hipGetLastError());
-    hipLaunchKernelGGL(bgk::beam_group_select_kernel, dim3(G), dim3(bgk::BEAM_SELECT_THREADS), 0, c->stream,
-                       reinterpret_cast<const bgk::BeamCand *>(c->bbatch_buf + bbatch_cand_off()), reinterpret_cast<bgk::BeamCtl *>(c->bbatch_buf + bbatch_ctl_off()), B,
-                       c->seq, c->seq_gen, P, reinterpret_cast<int32_t *>(c->bbatch_buf + bbatch_ids_off()), hdr, forks, col_skip);
+    hipLaunchKernelGGL(bgk::beam_group_select_kernel, dim3(G), dim3(bgk::BEAM_SELECT_THREADS), 0, b.stream, b.cand, b.ctl, B, b.seq, b.seq_gen, b.gen_stride, b.pool_ids,
+                       b.hdr, b.forks, b.col_skip);
     HIP_TRY(false, hipGetLastError());
     if (B > 1) {
-        hipLaunchKernelGGL(bgk::kv_group_fork_kernel, dim3(hp.n_layer * hp.n_head, bgk::BEAM_FORK_WGS, 2), dim3(256), 0, c->stream, hdr, forks, c->bk, c->bv,
-                           (int64_t)hp.n_layer * P * hp.d_model, P, hp.d_model / hp.n_head, c->seq_gen, P);
+        hipLaunchKernelGGL(bgk::kv_group_fork_kernel, dim3(b.kv_runs, bgk::BEAM_FORK_WGS, 2), dim3(256), 0, b.stream, b.hdr, b.forks, b.bk, b.bv, b.seq_stride, b.P, b.dk,
+                           b.seq_gen, b.gen_stride);
         HIP_TRY(false, hipGetLastError());
+    }
+    return true;
+}
+
+// the pools of G finished searches (ctl: host copies; pool_ids: [G * B][ids_stride]) -> the output rows of biogpt_hip_generate_beam_batch
+static bool beam_read_pools(const bgk::BeamCtl *ctl, const int32_t *pool_ids, size_t ids_stride, int G, int B, int n_predict, int32_t *out_ids, int32_t *out_lens,
+                            float *out_scores, int32_t *out_counts) {
+    for (int p = 0; p < G; p++) {
+        const bgk::BeamCtl &st = ctl[p];
+        if (!st.done || st.pool_n < 1 || st.pool_n > B) BG_FAIL(false, "internal: beam search of prompt %d ended with %d hypotheses (done word %d)", p, st.pool_n, st.done);
+        out_counts[p] = st.pool_n;
+        for (int r = 0; r < B; r++) {
+            const size_t row = (size_t)p * B + r;
+            int32_t *o = out_ids + row * n_predict;
+            std::fill(o, o + n_predict, -1);
+            out_lens[row] = 0; out_scores[row] = 0.0f;
+            if (r >= st.pool_n) continue;
+            const int slot = st.pool_order[r];
+            out_lens[row] = std::min(st.pool_len[slot], n_predict);
+            out_scores[row] = st.pool_score[slot];
+            std::memcpy(o, pool_ids + ((size_t)p * B + slot) * ids_stride, (size_t)out_lens[row] * 4);
+        }
     }
     return true;
 }
@@ -3171,7 +3219,10 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     if (!upload_column_starts(ctx, prompts, prompt_lens, G, B)) return -2;
     if (ru && !rules_upload(ctx, rules, 1, eos_id, prompts, prompt_lens, G, B)) return -2;
 
-    const ColumnStep step = [&](int t_max) -> bool { return enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max)) && enqueue_beam_group_select(ctx, G, B, ru); };
+    const BeamBufs bufs = beam_bufs_of(ctx);
+    const ColumnStep step = [&](int t_max) -> bool {
+        return enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max)) && (!ru || enqueue_rules(ctx, n_seqs, bufs.col_skip, 1)) && enqueue_beam_group_select(bufs, G, B, ru);
+    };
     const int gset = 6 * choose_column_path(ctx, n_seqs, max_len) + (ru ? 12 : 0);
     bool use_graph;
     if (!capture_column_steps(ctx, ctx->graphs_beam, gset, max_len, n_predict, step, &use_graph)) return -2;
@@ -3187,22 +3238,7 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     const auto t1 = std::chrono::steady_clock::now();
     if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
     if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
-    for (int p = 0; p < G; p++) {
-        const bgk::BeamCtl &st = hc[(size_t)p];
-        if (!st.done || st.pool_n < 1 || st.pool_n > B) BG_FAIL(-2, "internal: beam search of prompt %d ended with %d hypotheses (done word %d)", p, st.pool_n, st.done);
-        out_counts[p] = st.pool_n;
-        for (int r = 0; r < B; r++) {
-            const size_t row = (size_t)p * B + r;
-            int32_t *o = out_ids + row * n_predict;
-            std::fill(o, o + n_predict, -1);
-            out_lens[row] = 0; out_scores[row] = 0.0f;
-            if (r >= st.pool_n) continue;
-            const int slot = st.pool_order[r];
-            out_lens[row] = std::min(st.pool_len[slot], n_predict);
-            out_scores[row] = st.pool_score[slot];
-            std::memcpy(o, ids.data() + ((size_t)p * B + slot) * P, (size_t)out_lens[row] * 4);
-        }
-    }
+    if (!beam_read_pools(hc.data(), ids.data(), (size_t)P, G, B, n_predict, out_ids, out_lens, out_scores, out_counts)) return -2;
     return n_predict;
 }
 
@@ -3480,6 +3516,223 @@ int biogpt_hip_rules_rows_device(int device, int32_t mode, const float *rows, in
     HIP_TRY(-2, hipDeviceSynchronize());
     HIP_TRY(-2, hipMemcpy(rows_out, d, lg_b, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// logprob_rows_kernel over rows held in host memory (tests of the kernel itself): ldl = n_vocab, so an odd n_vocab puts rows 1, 2, 3 on the other
+// 16-byte alignments
+int biogpt_hip_logprob_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *targets, float *lp_out, int32_t *argmax_out,
+                                   float *logit_out) {
+    clear_error();
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!targets) BG_FAIL(-1, "targets is NULL");
+    if (!lp_out || !argmax_out || !logit_out) BG_FAIL(-1, "lp_out, argmax_out or logit_out is NULL");
+    if (n_rows < 1 || n_rows > 4096) BG_FAIL(-1, "n_rows must be in [1, 4096]");
+    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
+    for (int r = 0; r < n_rows; r++)
+        if (targets[r] < -1 || targets[r] >= n_vocab) BG_FAIL(-1, "targets[%d] = %d out of range: must be in [0, %d), or -1 for none", r, targets[r], n_vocab);
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, n_b = (size_t)n_rows * 4;
+    const size_t o_tg = (lg_b + 15) & ~(size_t)15, o_lp = o_tg + n_b, o_am = o_lp + n_b, o_lg = o_am + n_b;      // [rows | targets | lp | arg-max | logit]
+    uint8_t *d = nullptr;
+    HIP_TRY(-2, hipMalloc(&d, o_lg + n_b));
+    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+    HIP_TRY(-2, hipMemcpy(d, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d + o_tg, targets, n_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d + o_lp, 0xff, 3 * n_b));
+    hipLaunchKernelGGL(bgk::logprob_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, reinterpret_cast<const float *>(d), n_vocab, n_vocab,
+                       reinterpret_cast<const int32_t *>(d + o_tg), reinterpret_cast<float *>(d + o_lp), reinterpret_cast<int32_t *>(d + o_am),
+                       reinterpret_cast<float *>(d + o_lg));
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(lp_out, d + o_lp, n_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(argmax_out, d + o_am, n_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(logit_out, d + o_lg, n_b, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// what the beam entries below check of a row read as log-probabilities: the row kernel's precondition (the rules' argument check in a call)
+static bool beam_given_rows_ok(const float *rows, size_t n_rows, int n_vocab, int K, const char *what) {
+    for (size_t r = 0; r < n_rows; r++) {
+        int finite = 0;
+        for (int v = 0; v < n_vocab && finite < K; v++) finite += std::isfinite(rows[r * n_vocab + v]) ? 1 : 0;
+        if (finite < K) BG_FAIL(false, "%s: row %zu holds fewer than 2 x n_beams = %d finite log-probabilities", what, r, K);
+    }
+    return true;
+}
+
+// beam_group_rows_kernel over rows held in host memory (tests of the kernel itself), through the dispatch of a call: row r is column r % n_beams of group
+// r / n_beams, run_score[r] the score of the beam in it.  Every candidate is a sentinel (score NaN, col = id = -1) before the launch; with first_step a
+// group's row 0 alone may write.
+int biogpt_hip_beam_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t given, int32_t n_beams, const float *run_score,
+                                int32_t first_step, float *cand_score, int32_t *cand_col, int32_t *cand_id) {
+    clear_error();
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!run_score) BG_FAIL(-1, "run_score is NULL");
+    if (!cand_score || !cand_col || !cand_id) BG_FAIL(-1, "cand_score, cand_col or cand_id is NULL");
+    if (given != 0 && given != 1) BG_FAIL(-1, "given must be 0 (logits) or 1 (log-probabilities)");
+    if (first_step != 0 && first_step != 1) BG_FAIL(-1, "first_step must be 0 or 1");
+    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
+    if (n_rows < 1 || n_rows > BBATCH_COLS || n_rows % n_beams) BG_FAIL(-1, "n_rows must be a multiple of n_beams in [1, %d]", BBATCH_COLS);
+    if (n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be at most %d", 1 << 20);
+    if (n_vocab < 2 * n_beams) BG_FAIL(-1, "n_vocab: a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", n_vocab);
+    const int B = n_beams, G = n_rows / B, K = 2 * B;
+    if (given && !beam_given_rows_ok(rows, (size_t)n_rows, n_vocab, K, "rows")) return -1;
+    HIP_TRY(-2, hipSetDevice(device));
+    std::vector<bgk::BeamCtl> hc((size_t)G);
+    for (int g = 0; g < G; g++) {
+        bgk::BeamCtl &c = hc[(size_t)g];
+        c = bgk::BeamCtl{};
+        c.n_beams = B; c.step = first_step ? 0 : 1; c.heur_unsat = 1;
+        for (int j = 0; j < B; j++) { c.run_score[j] = run_score[g * B + j]; c.col_rank[j] = j; }
+    }
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, ctl_b = sizeof(bgk::BeamCtl) * (size_t)G, cd_b = sizeof(bgk::BeamCand) * (size_t)n_rows * K;
+    const size_t o_hd = (lg_b + 15) & ~(size_t)15, o_ct = o_hd + sizeof(bgk::BeamBatchHdr), o_cd = (o_ct + ctl_b + 15) & ~(size_t)15;     // [rows | hdr | ctl | cand]
+    uint8_t *d = nullptr;
+    HIP_TRY(-2, hipMalloc(&d, o_cd + cd_b));
+    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+    HIP_TRY(-2, hipMemcpy(d, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d + o_hd, 0, sizeof(bgk::BeamBatchHdr)));
+    HIP_TRY(-2, hipMemcpy(d + o_ct, hc.data(), ctl_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d + o_cd, 0xff, cd_b));
+    BeamBufs b{};
+    b.stream = 0;
+    b.logits = reinterpret_cast<const float *>(d); b.n_vocab = n_vocab;
+    b.hdr = reinterpret_cast<bgk::BeamBatchHdr *>(d + o_hd);
+    b.ctl = reinterpret_cast<bgk::BeamCtl *>(d + o_ct);
+    b.cand = reinterpret_cast<bgk::BeamCand *>(d + o_cd);
+    launch_beam_group_rows(b, G, B, given != 0);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    std::vector<bgk::BeamCand> out((size_t)n_rows * K);
+    HIP_TRY(-2, hipMemcpy(out.data(), d + o_cd, cd_b, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < out.size(); i++) { cand_score[i] = out[i].score; cand_col[i] = out[i].col; cand_id[i] = out[i].id; }
+    return 0;
+}
+
+// A whole beam search over the three beam kernels with the model replaced by a lookup (beam_table_feed_kernel, kernels_beam.hip.h), through the step
+// and the read-out of biogpt_hip_generate_beam_batch: at most max_steps steps of feed + rows + select + fork, the live-group word read after each.
+// Not capturable (it synchronizes every step).
+int biogpt_hip_beam_table_device(int device, const float *table, int32_t n_table_rows, int32_t n_vocab, int32_t given, const int32_t *start_tokens,
+                                 const int32_t *prompt_lens, int32_t n_groups, int32_t n_beams, int32_t n_predict, int32_t eos_id, float length_penalty,
+                                 int32_t early_stopping, int32_t max_steps, int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts,
+                                 int32_t *col_token, int32_t *col_n_gen, int32_t *col_hist, float *col_run_score, int32_t *col_rank, int32_t *grp_done,
+                                 int32_t *grp_step, float *kv_out) {
+    clear_error();
+    if (!table) BG_FAIL(-1, "table is NULL");
+    if (!start_tokens || !prompt_lens) BG_FAIL(-1, "start_tokens or prompt_lens is NULL");
+    if (!out_ids || !out_lens || !out_scores || !out_counts) BG_FAIL(-1, "out_ids, out_lens, out_scores or out_counts is NULL");
+    if (!col_token || !col_n_gen || !col_hist || !col_run_score || !col_rank || !grp_done || !grp_step || !kv_out) BG_FAIL(-1, "a state output (col_*, grp_*, kv_out) is NULL");
+    if (given != 0 && given != 1) BG_FAIL(-1, "given must be 0 (logits) or 1 (log-probabilities)");
+    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
+    if (n_groups < 1 || (int64_t)n_groups * n_beams > BBATCH_COLS) BG_FAIL(-1, "n_groups x n_beams must be in [1, %d]", BBATCH_COLS);
+    if (n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be at most %d", 1 << 20);
+    if (n_vocab < 2 * n_beams) BG_FAIL(-1, "n_vocab: a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", n_vocab);
+    if (n_table_rows < 1 || n_table_rows > (1 << 16)) BG_FAIL(-1, "n_table_rows must be in [1, %d]", 1 << 16);
+    if (n_predict < 1 || n_predict > 1024) BG_FAIL(-1, "n_predict must be in [1, 1024]");
+    if (max_steps < 1) BG_FAIL(-1, "max_steps must be >= 1");
+    if (eos_id < -1 || eos_id >= n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, n_vocab);
+    if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
+    if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
+    const int G = n_groups, B = n_beams, n_cols = G * B;
+    int max_len = 0;
+    for (int g = 0; g < G; g++) {
+        if (prompt_lens[g] < 1 || prompt_lens[g] > 1024) BG_FAIL(-1, "prompt_lens[%d] must be in [1, 1024]", g);
+        if (start_tokens[g] < 0 || start_tokens[g] >= n_vocab) BG_FAIL(-1, "start_tokens[%d] = %d out of range: must be in [0, %d)", g, start_tokens[g], n_vocab);
+        max_len = std::max(max_len, prompt_lens[g]);
+    }
+    if (given && !beam_given_rows_ok(table, (size_t)n_table_rows, n_vocab, 2 * B, "table")) return -1;
+    HIP_TRY(-2, hipSetDevice(device));
+    const int P = max_len + n_predict;
+    constexpr int H = bgk::TABLE_HEADS, DK = bgk::TABLE_DK;
+    // [table | logits | K | V | hdr | forks | skip | ctl | cand | pool ids | column states | histories], each part 16-byte aligned
+    size_t at = 0;
+    auto part = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
+    const size_t kv_b = (size_t)n_cols * H * P * DK * 4;
+    const size_t o_tb = part((size_t)n_table_rows * n_vocab * 4), o_lg = part((size_t)n_cols * n_vocab * 4), o_k = part(kv_b), o_v = part(kv_b);
+    const size_t o_hd = part(sizeof(bgk::BeamBatchHdr)), o_fk = part(sizeof(bgk::BeamFork) * (size_t)n_cols), o_sk = part((size_t)n_cols * 4);
+    const size_t o_ct = part(sizeof(bgk::BeamCtl) * (size_t)G), o_cd = part(sizeof(bgk::BeamCand) * (size_t)n_cols * 2 * B), o_id = part((size_t)n_cols * P * 4);
+    const size_t o_sq = part(sizeof(bgk::SeqState) * (size_t)n_cols), o_gn = part((size_t)n_cols * P * 4);
+    uint8_t *d = nullptr;
+    HIP_TRY(-2, hipMalloc(&d, at));
+    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+    std::vector<bgk::BeamCtl> hc((size_t)G);
+    std::vector<bgk::SeqState> hs((size_t)n_cols);
+    std::vector<int32_t> skip((size_t)n_cols, 0);
+    for (int g = 0; g < G; g++) {       // the initial state of a call (generate_beam_batch_once, upload_column_starts)
+        bgk::BeamCtl &c = hc[(size_t)g];
+        c = bgk::BeamCtl{};
+        c.n_beams = B; c.n_prompt = prompt_lens[g]; c.n_predict = n_predict; c.eos_id = eos_id;
+        c.length_penalty = length_penalty; c.early_stopping = early_stopping; c.ids_stride = P;
+        c.heur_unsat = 1;
+        for (int j = 0; j < B; j++) {
+            bgk::SeqState &st = hs[(size_t)g * B + j];
+            st = bgk::SeqState{};
+            st.n_past = prompt_lens[g] - 1; st.token = start_tokens[g]; st.seq_id = g * B + j;
+            if (j > 0) skip[(size_t)g * B + j] = 1;
+        }
+    }
+    bgk::BeamBatchHdr hh{};
+    hh.n_live = G;
+    std::vector<float> kv_fill(2 * kv_b / 4, -1.0f);       // a row no step has written reads -1
+    HIP_TRY(-2, hipMemcpy(d + o_tb, table, (size_t)n_table_rows * n_vocab * 4, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d + o_lg, 0, (size_t)n_cols * n_vocab * 4));
+    HIP_TRY(-2, hipMemcpy(d + o_k, kv_fill.data(), kv_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d + o_v, kv_fill.data(), kv_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d + o_hd, &hh, sizeof(hh), hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d + o_fk, 0, sizeof(bgk::BeamFork) * (size_t)n_cols));
+    HIP_TRY(-2, hipMemcpy(d + o_sk, skip.data(), (size_t)n_cols * 4, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d + o_ct, hc.data(), sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d + o_cd, 0xff, sizeof(bgk::BeamCand) * (size_t)n_cols * 2 * B));
+    HIP_TRY(-2, hipMemset(d + o_id, 0xff, (size_t)n_cols * P * 4));
+    HIP_TRY(-2, hipMemcpy(d + o_sq, hs.data(), sizeof(bgk::SeqState) * (size_t)n_cols, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d + o_gn, 0xff, (size_t)n_cols * P * 4));
+    BeamBufs b{};
+    b.stream = 0;
+    b.logits = reinterpret_cast<const float *>(d + o_lg); b.n_vocab = n_vocab;
+    b.hdr = reinterpret_cast<bgk::BeamBatchHdr *>(d + o_hd);
+    b.forks = reinterpret_cast<bgk::BeamFork *>(d + o_fk);
+    b.col_skip = reinterpret_cast<int32_t *>(d + o_sk);
+    b.ctl = reinterpret_cast<bgk::BeamCtl *>(d + o_ct);
+    b.cand = reinterpret_cast<bgk::BeamCand *>(d + o_cd);
+    b.pool_ids = reinterpret_cast<int32_t *>(d + o_id);
+    b.seq = reinterpret_cast<bgk::SeqState *>(d + o_sq);
+    b.seq_gen = reinterpret_cast<int32_t *>(d + o_gn); b.gen_stride = P;
+    b.bk = reinterpret_cast<float *>(d + o_k); b.bv = reinterpret_cast<float *>(d + o_v);
+    b.seq_stride = (int64_t)H * P * DK; b.kv_runs = H; b.P = P; b.dk = DK;
+    int n_live = G;
+    for (int s = 0; s < std::min(max_steps, n_predict) && n_live > 0; s++) {
+        hipLaunchKernelGGL(bgk::beam_table_feed_kernel, dim3(n_cols), dim3(256), 0, 0, b.seq, reinterpret_cast<const float *>(d + o_tb), n_table_rows, n_vocab,
+                           reinterpret_cast<float *>(d + o_lg), b.bk, b.bv, P);
+        HIP_TRY(-2, hipGetLastError());
+        if (!enqueue_beam_group_select(b, G, B, given != 0)) return -2;
+        HIP_TRY(-2, hipMemcpy(&hh, d + o_hd, sizeof(hh), hipMemcpyDeviceToHost));      // (synchronizes)
+        n_live = hh.n_live;
+    }
+    std::vector<int32_t> ids((size_t)n_cols * P), gen((size_t)n_cols * P);
+    HIP_TRY(-2, hipMemcpy(hc.data(), d + o_ct, sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(hs.data(), d + o_sq, sizeof(bgk::SeqState) * (size_t)n_cols, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(ids.data(), d + o_id, ids.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(gen.data(), d + o_gn, gen.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(kv_out, d + o_k, kv_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(kv_out + kv_b / 4, d + o_v, kv_b, hipMemcpyDeviceToHost));
+    for (int g = 0; g < G; g++) {
+        grp_done[g] = hc[(size_t)g].done; grp_step[g] = hc[(size_t)g].step;
+        for (int j = 0; j < B; j++) {
+            const size_t c = (size_t)g * B + j;
+            col_token[c] = hs[c].token; col_n_gen[c] = hs[c].n_gen;
+            col_run_score[c] = hc[(size_t)g].run_score[j]; col_rank[c] = hc[(size_t)g].col_rank[j];
+            std::memcpy(col_hist + c * n_predict, gen.data() + c * P, (size_t)n_predict * 4);
+        }
+    }
+    if (n_live > 0) {       // stopped by max_steps: no result yet
+        std::fill(out_ids, out_ids + (size_t)n_cols * n_predict, -1);
+        std::fill(out_lens, out_lens + n_cols, 0);
+        std::fill(out_scores, out_scores + n_cols, 0.0f);
+        std::fill(out_counts, out_counts + G, 0);
+        return 0;
+    }
+    if (!beam_read_pools(hc.data(), ids.data(), (size_t)P, G, B, n_predict, out_ids, out_lens, out_scores, out_counts)) return -2;
+    return n_predict;
 }
 
 // the sampler's tail and its generator on the host: no device, no context

@@ -374,4 +374,29 @@ __global__ __launch_bounds__(256) void kv_group_fork_kernel(const BeamBatchHdr *
     }
 }
 
+// ---- the model of biogpt_hip_beam_table_device (tests of the three kernels above without a forward pass) ----
+// What a decode step leaves for column c with token t at position p: its logits row, here row t % n_table_rows of a table, and its K / V row of
+// position p in its own cache slot, here a stamp that names (token, position, head, K | V) in exact floats.  1 layer, TABLE_HEADS heads of TABLE_DK.
+constexpr int TABLE_HEADS = 2, TABLE_DK = 4;
+
+__device__ __forceinline__ float4 beam_table_stamp(int token, int pos, int head, int kv) {
+    return make_float4((float)token, (float)pos, (float)(2 * head + kv), (float)((token + 7 * pos + 3 * head + kv) & 0xffff));
+}
+
+// grid: the columns.  table: [n_table_rows][n_vocab]; logits: [columns][n_vocab]; kroot / vroot: [columns][TABLE_HEADS][P][TABLE_DK].
+__global__ __launch_bounds__(256) void beam_table_feed_kernel(const SeqState *seq, const float *table, int n_table_rows, int n_vocab, float *logits, float *kroot,
+                                                              float *vroot, int P) {
+    const int col = blockIdx.x;
+    const SeqState s = seq[col];
+    if (s.token < 0 || s.n_past < 0 || s.n_past >= P) return;      // (never: the select kernel's positions end at n_prompt - 1 + n_predict < P)
+    const float *src = table + (size_t)(s.token % n_table_rows) * n_vocab;
+    float *dst = logits + (size_t)col * n_vocab;
+    for (int i = threadIdx.x; i < n_vocab; i += blockDim.x) dst[i] = src[i];
+    if (threadIdx.x < 2 * TABLE_HEADS) {
+        const int head = threadIdx.x >> 1, kv = threadIdx.x & 1;
+        float *root = kv ? vroot : kroot;
+        *reinterpret_cast<float4 *>(root + (((size_t)col * TABLE_HEADS + head) * P + s.n_past) * TABLE_DK) = beam_table_stamp(s.token, s.n_past, head, kv);
+    }
+}
+
 }  // namespace bgk

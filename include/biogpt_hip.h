@@ -329,6 +329,38 @@ int biogpt_hip_rules_rows_device(int device, int32_t mode /* 0 logits, 1 log-pro
                                  const int32_t *hist /* concatenated */, const int32_t *hist_lens, const int32_t *prompt_lens, int32_t eos_id,
                                  const biogpt_hip_gen_rules *rules, float *rows_out);
 
+/* logprob_rows_kernel (the log-softmax of biogpt_hip_score and of every beam score) over n_rows <= 4096 rows of n_vocab floats held in host memory,
+ * row stride n_vocab: an odd n_vocab puts consecutive rows on the four 16-byte alignments.  targets[r] in [-1, n_vocab); for row r the outputs are
+ * what biogpt_hip_score documents for a row: lp_out, argmax_out (lowest id on ties), logit_out; target -1 gives lp = logit = 0.  For tests of the
+ * kernel itself. */
+int biogpt_hip_logprob_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *targets, float *lp_out,
+                                   int32_t *argmax_out, float *logit_out);
+
+/* beam_group_rows_kernel over n_rows <= 512 rows of n_vocab >= 2 * n_beams floats held in host memory, launched by the dispatch a call uses
+ * (the 8 / 16 / 32-entry instantiation by n_beams; given = 1: the rows hold log-probabilities and are taken as they are, each with at least
+ * 2 * n_beams finite values).  Row r is column r % n_beams of group r / n_beams and run_score[r] the score of the beam in it; n_rows is a multiple of
+ * n_beams.  Outputs are [n_rows][2 * n_beams], best candidate first: cand_score = (float)(run_score + lp), cand_col = the column within the group,
+ * cand_id the token.  Every entry is a sentinel (score NaN, col = id = -1) before the launch: with first_step = 1 only a group's row 0 is expanded
+ * and the other rows keep it.  For tests of the kernel itself. */
+int biogpt_hip_beam_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t given, int32_t n_beams, const float *run_score,
+                                int32_t first_step, float *cand_score, int32_t *cand_col, int32_t *cand_id);
+
+/* A whole beam search over the beam kernels with the model replaced by a lookup: the row of a column whose token is t is table[t % n_table_rows]
+ * (table: [n_table_rows][n_vocab], logits, or log-probabilities with given = 1), and the K / V row it leaves at its position p in its cache slot
+ * (1 layer, 2 heads of 4 floats, P = max(prompt_lens) + n_predict positions) is the stamp {t, p, 2 * head + (0 K | 1 V),
+ * (t + 7 p + 3 head + (0 | 1)) & 0xffff}.  Group g starts as a call with a prompt of prompt_lens[g] tokens ending in start_tokens[g] does.  Runs at
+ * most max_steps steps (row, select and fork kernels through the step code of biogpt_hip_generate_beam_batch), fewer if every group finishes.
+ * out_ids [n_groups][n_beams][n_predict], out_lens, out_scores, out_counts: as biogpt_hip_generate_beam_batch writes them, by the same read-out,
+ * if every group has finished (returns n_predict); else they are emptied and the call returns 0.  The state after the last step, always:
+ * col_token, col_n_gen, col_run_score, col_rank [n_groups * n_beams], col_hist [n_groups * n_beams][n_predict] (-1 where nothing was written),
+ * grp_done, grp_step [n_groups], kv_out [2 K | V][n_groups * n_beams][2][P][4] (-1 where no step has written).  < 0 on error (argument errors, -1,
+ * the message names the argument, come before any HIP call).  For tests of the kernels themselves. */
+int biogpt_hip_beam_table_device(int device, const float *table, int32_t n_table_rows, int32_t n_vocab, int32_t given, const int32_t *start_tokens,
+                                 const int32_t *prompt_lens, int32_t n_groups, int32_t n_beams, int32_t n_predict, int32_t eos_id, float length_penalty,
+                                 int32_t early_stopping, int32_t max_steps, int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts,
+                                 int32_t *col_token, int32_t *col_n_gen, int32_t *col_hist, float *col_run_score, int32_t *col_rank, int32_t *grp_done,
+                                 int32_t *grp_step, float *kv_out);
+
 /* Contrastive search (Su et al. 2022; transformers' generate(penalty_alpha, top_k)): n_prompts deterministic searches in one call.  Group g owns the
  * top_k columns and K / V cache slots [g * top_k, (g + 1) * top_k) and a context store H_g: one f32 hidden row (biogpt_hip_hidden's row, after the
  * final LayerNorm) per context token and its squared norm as a double.  The prompt pass (chunks of n_batch) leaves the rows of prompt tokens

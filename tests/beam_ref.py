@@ -26,6 +26,32 @@ def beam_search(logprobs, n_beams, n_predict, eos_id=-1, length_penalty=1.0, ear
     """Returns (hyps, margins): hyps = [(ids list, normalized score float32), ...] best first; margins = per step the smallest gap of
     the step's decisions (float, inf where a step decides nothing): between the n_beams-th running beam kept and the best candidate
     rejected, at the border of the finished pool, and at the early-stop comparison."""
+    hyps, margins, _ = _search(logprobs, n_beams, n_predict, eos_id, length_penalty, early_stopping, None, None)
+    return hyps, margins
+
+
+def running_beams(logprobs, n_beams, n_predict, max_steps, eos_id=-1, length_penalty=1.0, early_stopping=True, trace=None):
+    """The running beams after max_steps steps of beam_search (fewer if the search stops first), in rank order: [(ids list, float32 score), ...].
+    trace: a list that receives one dict per step -- cand (the 2 * n_beams candidates (score, parent rank, id) in order), parents (the parent
+    rank of each new running beam), evicted (hypotheses pushed out of a full pool), done."""
+    return _search(logprobs, n_beams, n_predict, eos_id, length_penalty, early_stopping, max_steps, trace)[2]
+
+
+def _leading(sc, n):
+    """Flat indices into sc [rows][V] that hold every row's first n entries by (value descending, id ascending), and possibly more: all a step looks
+    at (its 2B candidates and the first candidate left out are within the first 2B + 1 of the global order, so within these of their rows).  Sorting
+    these instead of all rows x V values changes no result."""
+    V = sc.shape[1]
+    if V <= n:
+        return np.arange(sc.size)
+    keep = []
+    for b in range(sc.shape[0]):
+        nth = np.partition(sc[b], V - n)[V - n]      # the n-th largest value: ties with it stay in
+        keep.append(b * V + np.nonzero(sc[b] >= nth)[0])
+    return np.concatenate(keep)
+
+
+def _search(logprobs, n_beams, n_predict, eos_id, length_penalty, early_stopping, max_steps, trace):
     B = int(n_beams)
     running = [([], np.float32(0.0))]      # step 1 expands beam 0 alone (the others start at -1e9)
     pool = []                              # [(normalized score, ids)], best first, earlier entries first on ties
@@ -35,22 +61,22 @@ def beam_search(logprobs, n_beams, n_predict, eos_id=-1, length_penalty=1.0, ear
         rows = np.asarray(logprobs([r[0] for r in running]), dtype=np.float32)
         V = rows.shape[1]
         sc = np.stack([(np.float32(s) + rows[b]).astype(np.float32) for b, (_, s) in enumerate(running)])
-        par = np.repeat(np.arange(len(running)), V)
-        ids = np.tile(np.arange(V), len(running))
         flat = sc.reshape(-1)
-        order = np.lexsort((ids, par, -flat.astype(np.float64)))     # score descending, parent rank, token id
-        cand = [(flat[i], int(par[i]), int(ids[i])) for i in order[:2 * B]]
+        lead = _leading(sc, 2 * B + 1)
+        order = lead[np.lexsort((lead % V, lead // V, -flat[lead].astype(np.float64)))]     # score descending, parent rank, token id
+        cand = [(flat[i], int(i // V), int(i % V)) for i in order[:2 * B]]
 
         def hit(c):
             return (eos_id >= 0 and c[2] == eos_id) or k >= n_predict
 
         gaps = []
+        evicted = 0
         nonhit = [c for c in cand if not hit(c)]
         new_running = nonhit[:B]
         if len(nonhit) >= B:     # the B-th running beam against the best non-stopping candidate left out (over all B x V)
             kept = set((c[1], c[2]) for c in new_running)
             for i in order:
-                c = (flat[i], int(par[i]), int(ids[i]))
+                c = (flat[i], int(i // V), int(i % V))
                 if (c[1], c[2]) not in kept and not hit(c):
                     gaps.append(float(new_running[-1][0]) - float(c[0]))
                     break
@@ -68,6 +94,7 @@ def beam_search(logprobs, n_beams, n_predict, eos_id=-1, length_penalty=1.0, ear
                     gaps.append(abs(float(ns) - float(pool[-1][0])))
                 if pos < B:
                     pool.insert(pos, (ns, hyp))
+                    evicted += len(pool[B:])
                     del pool[B:]
         # _check_early_stop_heuristic: a full pool only
         if heur_unsat and len(pool) == B and new_running:
@@ -77,9 +104,11 @@ def beam_search(logprobs, n_beams, n_predict, eos_id=-1, length_penalty=1.0, ear
         margins.append(min(gaps) if gaps else float("inf"))
         done = (not heur_unsat) or (len(pool) == B and early_stopping) or len(nonhit) < B or k >= n_predict
         running = [(list(running[c[1]][0]) + [c[2]], c[0]) for c in new_running]
-        if done:
+        if trace is not None:
+            trace.append(dict(cand=cand, parents=[c[1] for c in new_running], evicted=evicted, done=done))
+        if done or (max_steps is not None and k >= max_steps):
             break
-    return [(ids, s) for s, ids in pool], margins
+    return [(ids, s) for s, ids in pool], margins, running
 
 
 class OracleLogprobs:
