@@ -2314,14 +2314,69 @@ static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const i
     return flush();
 }
 
-// ---- column generation: the host side that greedy batch, sampling and beam search share ----------------------------------------------
-// Such a call generates with one column (and one K / V cache slot) per sequence.  It reads: checks, the mode's device state, a `step` lambda, then
-// capture_column_steps, [t0] ingest_column_prompts, run_column_steps [t1], read-back.  step(t_max) enqueues one step of the mode: the forward pass of all
-// columns with t_max visible keys, then the mode's selection kernels, which leave every column's next token and position in ctx->seq.
+// ---- byte buffers in parts --------------------------------------------------------------------------------------------------------------
+// The parts of one buffer, one after another, each at a multiple of 16 bytes.  A layout function lays its parts out at a base pointer -- the device buffer, or a
+// host image of its head -- and with no base gives the size alone, so a size cannot disagree with its offsets.
+extern "C++" {
+struct ByteLayout {
+    size_t at = 0;
+    size_t part(size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; }
+    size_t bytes() const { return at; }
+    template <class T> T *take(uint8_t *base, size_t n) { const size_t o = part(n * sizeof(T)); return base ? reinterpret_cast<T *>(base + o) : nullptr; }
+};
+// A zeroed host image of the head [first, end) of a device buffer laid out in parts: at(part) is the image's copy of the part; upload() puts it in place
+struct HeadImage {
+    uint8_t *d0;
+    std::vector<uint8_t> h;
+    HeadImage(void *first, void *end) : d0(static_cast<uint8_t *>(first)), h((size_t)(static_cast<uint8_t *>(end) - static_cast<uint8_t *>(first)), 0) {}
+    template <class T> T *at(T *part) { return reinterpret_cast<T *>(h.data() + (reinterpret_cast<uint8_t *>(part) - d0)); }
+    bool upload() { HIP_TRY(false, hipMemcpy(d0, h.data(), h.size(), hipMemcpyHostToDevice)); return true; }
+};
+// scratch device memory of one call
+struct DeviceBytes {
+    uint8_t *p = nullptr;
+    DeviceBytes() = default;
+    DeviceBytes(const DeviceBytes &) = delete;
+    bool alloc(size_t bytes) { HIP_TRY(false, hipMalloc(&p, bytes)); return true; }
+    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(p + off); }
+    ~DeviceBytes() { if (p) (void)hipFree(p); }
+};
+}  // extern "C++"
+
+// ---- column generation: the host side that greedy batch, sampling, beam search and contrastive search share ------------------------------
+// Such a call generates with one column (and one K / V cache slot) per sequence: column p * per_prompt + j belongs to prompt p.  A mode checks its arguments,
+// describes itself as a ColumnCall, hands it to run_column_call and reads its results back.
 using ColumnStep = std::function<bool(int)>;
 
 // ends the call's hold on the column-per-XCD launches (choose_column_path) when the call returns
 struct XcBatchScope { biogpt_hip_ctx *c; ~XcBatchScope() { if (c) c->xc_batch = 0; } };
+
+struct ColumnCall {
+    // The call's hold on the device's pipeline slot and on the column-per-XCD launches ends with the description, when the mode returns.  A mode builds it after
+    // its argument checks: XpCallScope's constructor does nothing and xc_batch is set by choose_column_path alone, so where the scopes begin cannot be observed.
+    XpCallScope xp_scope;
+    XcBatchScope xc_scope;
+    explicit ColumnCall(biogpt_hip_ctx *c) : xp_scope(c), xc_scope{c} {}
+    const int32_t *prompts = nullptr, *prompt_lens = nullptr;      // concatenated; `unit` names one in a message
+    const char *unit = "prompt";
+    int n_prompts = 0, per_prompt = 1, n_batch = 1;
+    ColumnGraphs *graphs = nullptr;     // the mode's captured steps, valid for the call shape (key_a, key_b)
+    int key_a = 0, key_b = 0;
+    int extra_steps = 0;                // steps beyond one per token (contrastive: 1, the prompt's last token has a step of its own)
+    int gset_extra = 0;                 // 12 with rules: another form of the step, so other graphs
+    // set by run_column_call before any callable runs: the tokens to generate as clamped, the longest prompt, all prompt tokens
+    int n_predict = 0, max_len = 0;
+    long total = 0;
+    // prepare() may set these two: they lie in buffers it grows
+    const int32_t *live_dev = nullptr;  // device word that counts what still runs (null: every step is enqueued)
+    float *hidden_store = nullptr;      // where the prompt pass leaves the hidden rows of its columns (null: nowhere)
+    std::function<bool()> prepare;      // grows the mode's buffers, dropping its graphs where a pointer moves; runs before the graphs' key is looked at
+    std::function<bool()> upload;       // the call's parameters, initial state and rules -> the device
+    ColumnStep step;                    // step(t_max): the forward pass of all columns with t_max visible keys + the mode's selection, which leaves every column's
+                                        // next token and position in ctx->seq
+    std::function<bool()> after_ingest; // enqueued between the prompt pass and the first step
+    std::function<bool()> before_sync;  // enqueued behind the last step, in front of the call's one synchronize (inside the timed span)
+};
 
 // n prompts, concatenated: none empty, every token valid; the longest and the sum of their lengths
 static bool check_prompts(const biogpt_hip_ctx *c, const int32_t *prompts, const int32_t *lens, int n, const char *unit, int *max_len, long *total) {
@@ -2361,16 +2416,19 @@ static void column_graphs_for(ColumnGraphs &gs, int a, int b) {
 }
 
 // Column p * per_prompt + j starts at prompt p's LAST token (the prompt pass leaves it to the first step), in the cache slot of its own index
+static void fill_column_starts(bgk::SeqState *hs, int p, int per_prompt, int n_prompt, int32_t last_token) {
+    for (int j = 0; j < per_prompt; j++) {
+        bgk::SeqState &st = hs[(size_t)p * per_prompt + j];
+        st = bgk::SeqState{};
+        st.n_past = n_prompt - 1; st.token = last_token; st.seq_id = p * per_prompt + j;
+    }
+}
 static bool upload_column_starts(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *lens, int n_prompts, int per_prompt) {
     std::vector<bgk::SeqState> hs((size_t)n_prompts * per_prompt);
     size_t o = 0;
     for (int p = 0; p < n_prompts; p++) {
         o += (size_t)lens[p];
-        for (int j = 0; j < per_prompt; j++) {
-            bgk::SeqState &st = hs[(size_t)p * per_prompt + j];
-            st = bgk::SeqState{};
-            st.n_past = lens[p] - 1; st.token = prompts[o - 1]; st.seq_id = p * per_prompt + j;
-        }
+        fill_column_starts(hs.data(), p, per_prompt, lens[p], prompts[o - 1]);
     }
     HIP_TRY(false, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * hs.size(), hipMemcpyHostToDevice));
     return true;
@@ -2445,10 +2503,36 @@ static bool run_column_steps(biogpt_hip_ctx *ctx, const ColumnGraphs &graphs, in
     return true;
 }
 
+// The one order of a column call.  Returns the tokens to generate as clamped (> 0) once every step has run and the stream has drained; 0: the longest prompt
+// leaves no room (nothing was touched); -1: a bad prompt; -2: a failure.
+static int run_column_call(biogpt_hip_ctx *ctx, ColumnCall &cc, int n_predict, double *seconds_out) {
+    if (!check_prompts(ctx, cc.prompts, cc.prompt_lens, cc.n_prompts, cc.unit, &cc.max_len, &cc.total)) return -1;
+    cc.n_predict = std::min(n_predict, ctx->hp.n_positions - cc.max_len);  // main.cpp:82, for the longest prompt
+    if (cc.n_predict <= 0) return 0;
+    const int n_seqs = cc.n_prompts * cc.per_prompt, n_steps = cc.n_predict + cc.extra_steps;
+    if (!begin_column_call(ctx, n_seqs, cc.total)) return -2;
+    if (cc.prepare && !cc.prepare()) return -2;      // buffers grow and graphs drop BEFORE the key is looked at: a captured step never holds a freed pointer
+    column_graphs_for(*cc.graphs, cc.key_a, cc.key_b);
+    if (!upload_column_starts(ctx, cc.prompts, cc.prompt_lens, cc.n_prompts, cc.per_prompt)) return -2;
+    if (cc.upload && !cc.upload()) return -2;
+    const int gset = 6 * choose_column_path(ctx, n_seqs, cc.max_len) + cc.gset_extra;
+    bool use_graph;
+    if (!capture_column_steps(ctx, *cc.graphs, gset, cc.max_len, n_steps, cc.step, &use_graph)) return -2;
+
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!ingest_column_prompts(ctx, cc.prompts, cc.prompt_lens, cc.n_prompts, cc.n_batch, cc.per_prompt, cc.hidden_store)) return -2;
+    if (cc.after_ingest && !cc.after_ingest()) return -2;
+    if (!run_column_steps(ctx, *cc.graphs, gset, use_graph, cc.max_len, n_steps, cc.step, cc.live_dev)) return -2;
+    if (cc.before_sync && !cc.before_sync()) return -2;
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the mode's caller repeats it on the launch chain)
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    return cc.n_predict;
+}
+
 static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_seqs,
                                       int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out) {
-    XpCallScope xp_scope(ctx);
-    XcBatchScope xc_scope{ctx};
     clear_error();
     if (!ctx || !prompts || !prompt_lens || !out_ids) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
@@ -2456,32 +2540,18 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_seqs (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
     if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
     const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
-    int max_len;
-    long total;
-    if (!check_prompts(ctx, prompts, prompt_lens, n_seqs, "sequence", &max_len, &total)) return -1;
-    n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
-    if (n_predict <= 0) return 0;
-    if (!begin_column_call(ctx, n_seqs, total)) return -2;
-    column_graphs_for(ctx->graphs_greedy, n_seqs, 0);
-    if (!upload_column_starts(ctx, prompts, prompt_lens, n_seqs, 1)) return -2;
-
-    const ColumnStep step = [&](int t_max) -> bool {
+    ColumnCall cc(ctx);
+    cc.prompts = prompts; cc.prompt_lens = prompt_lens; cc.unit = "sequence";
+    cc.n_prompts = n_seqs; cc.n_batch = n_batch;
+    cc.graphs = &ctx->graphs_greedy; cc.key_a = n_seqs;
+    cc.step = [&](int t_max) -> bool {      // every step's arg-max is the next token
         if (!enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max))) return false;
         hipLaunchKernelGGL(bgk::argmax_rows_kernel, dim3(n_seqs), dim3(1024), 0, ctx->stream, ctx->logits_all, V, V, ctx->seq, 0, ctx->seq_gen, P, 1);
         HIP_TRY(false, hipGetLastError());
         return true;
     };
-    const int gset = 6 * choose_column_path(ctx, n_seqs, max_len);
-    bool use_graph;
-    if (!capture_column_steps(ctx, ctx->graphs_greedy, gset, max_len, n_predict, step, &use_graph)) return -2;
-
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ingest_column_prompts(ctx, prompts, prompt_lens, n_seqs, n_batch, 1)) return -2;
-    if (!run_column_steps(ctx, ctx->graphs_greedy, gset, use_graph, max_len, n_predict, step, nullptr)) return -2;   // every step's arg-max is the next token
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    n_predict = run_column_call(ctx, cc, n_predict, seconds_out);
+    if (n_predict <= 0) return n_predict;
     std::vector<int32_t> gen((size_t)n_seqs * P);
     HIP_TRY(-2, hipMemcpy(gen.data(), ctx->seq_gen, gen.size() * 4, hipMemcpyDeviceToHost));
     for (int s = 0; s < n_seqs; s++) std::memcpy(out_ids + (size_t)s * n_predict, gen.data() + (size_t)s * P, (size_t)n_predict * 4);
@@ -2933,26 +3003,36 @@ static bgk::RulesCtl rules_ctl_of(const biogpt_hip_gen_rules *r, int mode, int e
     return h;
 }
 
-static size_t rules_rows_off() { return sizeof(bgk::RulesCtl); }
-static size_t rules_toks_off() { return sizeof(bgk::RulesCtl) + sizeof(bgk::RulesRow) * RULES_ROWS; }
+// The rules buffer: allocated once, at its largest (RULES_ROWS prompts of n_positions tokens), so that captured steps keep their pointers
+struct RulesBufs {
+    bgk::RulesCtl *ctl;
+    bgk::RulesRow *rows;    // [RULES_ROWS]
+    int32_t *toks;          // the call's prompts, one copy per prompt
+    size_t bytes;
+};
+static RulesBufs rules_bufs_at(uint8_t *base, size_t n_toks) {
+    ByteLayout l;
+    RulesBufs b{};
+    b.ctl = l.take<bgk::RulesCtl>(base, 1); b.rows = l.take<bgk::RulesRow>(base, RULES_ROWS); b.toks = l.take<int32_t>(base, n_toks);
+    b.bytes = l.bytes();
+    return b;
+}
 
 // the call's rules, its rows (row p * rows_per_prompt + j reads prompt p) and its prompts -> the device, once per call
 static bool rules_upload(biogpt_hip_ctx *c, const biogpt_hip_gen_rules *r, int mode, int eos_id, const int32_t *prompts, const int32_t *prompt_lens,
                          int n_prompts, int rows_per_prompt) {
-    const size_t P = (size_t)c->hp.n_positions;
-    if (!c->rules_buf) HIP_TRY(false, hipMalloc(&c->rules_buf, rules_toks_off() + (size_t)RULES_ROWS * P * 4));
+    if (!c->rules_buf) HIP_TRY(false, hipMalloc(&c->rules_buf, rules_bufs_at(nullptr, (size_t)RULES_ROWS * c->hp.n_positions).bytes));
     size_t total = 0;
     for (int p = 0; p < n_prompts; p++) total += (size_t)prompt_lens[p];
-    std::vector<uint8_t> h(rules_toks_off() + total * 4, 0);
-    const bgk::RulesCtl hc = rules_ctl_of(r, mode, eos_id);
-    std::memcpy(h.data(), &hc, sizeof(hc));
-    bgk::RulesRow *rows = reinterpret_cast<bgk::RulesRow *>(h.data() + rules_rows_off());
+    std::vector<uint8_t> h(rules_bufs_at(nullptr, total).bytes, 0);
+    const RulesBufs hb = rules_bufs_at(h.data(), total);
+    *hb.ctl = rules_ctl_of(r, mode, eos_id);
     size_t o = 0;
     for (int p = 0; p < n_prompts; p++) {
-        for (int j = 0; j < rows_per_prompt; j++) rows[(size_t)p * rows_per_prompt + j] = bgk::RulesRow{(int32_t)o, prompt_lens[p]};
+        for (int j = 0; j < rows_per_prompt; j++) hb.rows[(size_t)p * rows_per_prompt + j] = bgk::RulesRow{(int32_t)o, prompt_lens[p]};
         o += (size_t)prompt_lens[p];
     }
-    std::memcpy(h.data() + rules_toks_off(), prompts, total * 4);
+    std::memcpy(hb.toks, prompts, total * 4);
     HIP_TRY(false, hipMemcpy(c->rules_buf, h.data(), h.size(), hipMemcpyHostToDevice));
     return true;
 }
@@ -2960,9 +3040,9 @@ static bool rules_upload(biogpt_hip_ctx *c, const biogpt_hip_gen_rules *r, int m
 // skip: a device word per row (skip_stride words apart) that, set, leaves the row alone
 static bool enqueue_rules(biogpt_hip_ctx *c, int n_rows, const int32_t *skip, int skip_stride) {
     const int V = c->hp.n_vocab;
-    hipLaunchKernelGGL(bgk::rules_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((V + 31) / 32) * 4, c->stream, c->logits_all, V, V,
-                       reinterpret_cast<const bgk::RulesCtl *>(c->rules_buf), reinterpret_cast<const bgk::RulesRow *>(c->rules_buf + rules_rows_off()),
-                       reinterpret_cast<const int32_t *>(c->rules_buf + rules_toks_off()), c->seq, c->seq_gen, c->hp.n_positions, skip, skip_stride);
+    const RulesBufs b = rules_bufs_at(c->rules_buf, 0);
+    hipLaunchKernelGGL(bgk::rules_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((V + 31) / 32) * 4, c->stream, c->logits_all, V, V, b.ctl, b.rows, b.toks, c->seq,
+                       c->seq_gen, c->hp.n_positions, skip, skip_stride);
     HIP_TRY(false, hipGetLastError());
     return true;
 }
@@ -2971,11 +3051,28 @@ static bool enqueue_rules(biogpt_hip_ctx *c, int n_rows, const int32_t *skip, in
 // The column generation above with sample_rows_kernel as the selection.  A prompt with several samples is evaluated once, into the slot of its first
 // sample.  With an EOS id the steps stop once every sequence has finished (SampleCtl::n_live).  The context's own K / V cache, position and logits row
 // are left alone.
+struct SampleBufs {
+    bgk::SampleCtl *ctl;
+    bgk::SampleSeq *seq;    // [n_seqs]
+    size_t bytes;
+};
+static SampleBufs sample_bufs_at(uint8_t *base, size_t n_seqs) {
+    ByteLayout l;
+    SampleBufs b{};
+    b.ctl = l.take<bgk::SampleCtl>(base, 1); b.seq = l.take<bgk::SampleSeq>(base, n_seqs);
+    b.bytes = l.bytes();
+    return b;
+}
+// the parameters of a call as it starts: all n_seqs sequences run
+static bgk::SampleCtl sample_ctl_of(int top_k, int eos_id, int n_seqs, double top_p, double temp) {
+    bgk::SampleCtl hc{};
+    hc.top_k = top_k; hc.eos_id = eos_id; hc.n_live = n_seqs; hc.top_p = top_p; hc.temp = temp;
+    return hc;
+}
+
 static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
                                 int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
                                 int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules) {
-    XpCallScope xp_scope(ctx);
-    XcBatchScope xc_scope{ctx};
     clear_error();
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompts || !prompt_lens || !seeds || !out_ids || !out_lens) BG_FAIL(-1, "null argument");
@@ -2992,52 +3089,41 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     if (!check_fast_chain(ctx, "sampled generation")) return -1;
     if (!check_rules(rules, V, P)) return -1;
     const bool ru = rules_active(rules, eos_id);
-    int max_len;
-    long total;
-    if (!check_prompts(ctx, prompts, prompt_lens, n_prompts, "prompt", &max_len, &total)) return -1;
-    n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
-    if (n_predict <= 0) return 0;
-    if (!begin_column_call(ctx, n_seqs, total)) return -2;
-    if (n_seqs > ctx->sample_cap) {
-        if (ctx->sample_ctl) (void)hipFree(ctx->sample_ctl);
-        ctx->sample_ctl = nullptr; ctx->sample_cap = 0;
-        drop_graphs(ctx->graphs_sample);
-        HIP_TRY(-2, hipMalloc(&ctx->sample_ctl, sizeof(bgk::SampleCtl) + sizeof(bgk::SampleSeq) * (size_t)n_seqs));
-        ctx->sample_cap = n_seqs;
-    }
-    column_graphs_for(ctx->graphs_sample, n_seqs, 0);
-    bgk::SampleSeq *const sample_seq = reinterpret_cast<bgk::SampleSeq *>(ctx->sample_ctl + 1);
-    {   // the call's parameters and the generators (std::mt19937(seeds[r]), their first block of outputs made here)
-        std::vector<uint8_t> h(sizeof(bgk::SampleCtl) + sizeof(bgk::SampleSeq) * (size_t)n_seqs, 0);
-        bgk::SampleCtl hc{};
-        hc.top_k = top_k; hc.eos_id = eos_id; hc.n_live = n_seqs; hc.top_p = top_p; hc.temp = temp;
-        std::memcpy(h.data(), &hc, sizeof(hc));
-        bgk::SampleSeq *hq = reinterpret_cast<bgk::SampleSeq *>(h.data() + sizeof(bgk::SampleCtl));
-        for (int r = 0; r < n_seqs; r++) { bgk::mt_seed(seeds[r], hq[r].mt); bgk::mt_regenerate(hq[r].mt); }
-        HIP_TRY(-2, hipMemcpy(ctx->sample_ctl, h.data(), h.size(), hipMemcpyHostToDevice));
-    }
-    if (!upload_column_starts(ctx, prompts, prompt_lens, n_prompts, n_samples)) return -2;
-    if (ru && !rules_upload(ctx, rules, 0, eos_id, prompts, prompt_lens, n_prompts, n_samples)) return -2;
-
-    const ColumnStep step = [&](int t_max) -> bool {
+    SampleBufs sb{};
+    ColumnCall cc(ctx);
+    cc.prompts = prompts; cc.prompt_lens = prompt_lens;
+    cc.n_prompts = n_prompts; cc.per_prompt = n_samples; cc.n_batch = n_batch;
+    cc.graphs = &ctx->graphs_sample; cc.key_a = n_seqs;
+    cc.gset_extra = ru ? 12 : 0;
+    cc.prepare = [&]() -> bool {
+        if (n_seqs > ctx->sample_cap) {
+            if (ctx->sample_ctl) (void)hipFree(ctx->sample_ctl);
+            ctx->sample_ctl = nullptr; ctx->sample_cap = 0;
+            drop_graphs(ctx->graphs_sample);
+            HIP_TRY(false, hipMalloc(&ctx->sample_ctl, sample_bufs_at(nullptr, (size_t)n_seqs).bytes));
+            ctx->sample_cap = n_seqs;
+        }
+        sb = sample_bufs_at(reinterpret_cast<uint8_t *>(ctx->sample_ctl), (size_t)n_seqs);
+        if (eos_id >= 0) cc.live_dev = &sb.ctl->n_live;
+        return true;
+    };
+    cc.upload = [&]() -> bool {      // the call's parameters and the generators (std::mt19937(seeds[r]), their first block of outputs made here)
+        std::vector<uint8_t> h(sb.bytes, 0);
+        const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_seqs);
+        *hb.ctl = sample_ctl_of(top_k, eos_id, n_seqs, top_p, temp);
+        for (int r = 0; r < n_seqs; r++) { bgk::mt_seed(seeds[r], hb.seq[r].mt); bgk::mt_regenerate(hb.seq[r].mt); }
+        HIP_TRY(false, hipMemcpy(sb.ctl, h.data(), h.size(), hipMemcpyHostToDevice));
+        return !ru || rules_upload(ctx, rules, 0, eos_id, prompts, prompt_lens, n_prompts, n_samples);
+    };
+    cc.step = [&](int t_max) -> bool {
         if (!enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max))) return false;
-        if (ru && !enqueue_rules(ctx, n_seqs, &sample_seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
-        hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->sample_ctl, sample_seq,
-                           ctx->seq, ctx->seq_gen, P);
+        if (ru && !enqueue_rules(ctx, n_seqs, &sb.seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
+        hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, sb.ctl, sb.seq, ctx->seq, ctx->seq_gen, P);
         HIP_TRY(false, hipGetLastError());
         return true;
     };
-    const int gset = 6 * choose_column_path(ctx, n_seqs, max_len) + (ru ? 12 : 0);
-    bool use_graph;
-    if (!capture_column_steps(ctx, ctx->graphs_sample, gset, max_len, n_predict, step, &use_graph)) return -2;
-
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ingest_column_prompts(ctx, prompts, prompt_lens, n_prompts, n_batch, n_samples)) return -2;
-    if (!run_column_steps(ctx, ctx->graphs_sample, gset, use_graph, max_len, n_predict, step, eos_id >= 0 ? &ctx->sample_ctl->n_live : nullptr)) return -2;
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    n_predict = run_column_call(ctx, cc, n_predict, seconds_out);
+    if (n_predict <= 0) return n_predict;
     std::vector<int32_t> gen((size_t)n_seqs * P);
     std::vector<bgk::SeqState> hs((size_t)n_seqs);
     HIP_TRY(-2, hipMemcpy(gen.data(), ctx->seq_gen, gen.size() * 4, hipMemcpyDeviceToHost));
@@ -3073,12 +3159,6 @@ int biogpt_hip_generate_sample_rules(biogpt_hip_ctx *ctx, const int32_t *prompts
 // beams have no score yet).  The steps stop once every search has finished (BeamBatchHdr::n_live).  biogpt_hip_generate_beam is the call with G = 1.  The
 // context's own K / V cache, position and logits row are left alone.
 constexpr int BBATCH_COLS = 512;    // columns of a call, at most
-static size_t bbatch_forks_off() { return sizeof(bgk::BeamBatchHdr); }
-static size_t bbatch_skip_off() { return bbatch_forks_off() + sizeof(bgk::BeamFork) * BBATCH_COLS; }
-static size_t bbatch_ctl_off() { return bbatch_skip_off() + 4 * (size_t)BBATCH_COLS; }
-static size_t bbatch_cand_off() { return bbatch_ctl_off() + sizeof(bgk::BeamCtl) * BBATCH_COLS; }
-static size_t bbatch_ids_off() { return bbatch_cand_off() + sizeof(bgk::BeamCand) * BBATCH_COLS * 2 * bgk::BEAM_MAX; }
-
 // The buffers a beam step works on: the context's (beam_bufs_of) or a test entry's own (biogpt_hip_beam_rows_device, biogpt_hip_beam_table_device).
 struct BeamBufs {
     hipStream_t stream;
@@ -3098,22 +3178,52 @@ struct BeamBufs {
     int kv_runs, P, dk;
 };
 
-static BeamBufs beam_bufs_of(biogpt_hip_ctx *c) {
+// The state block of a beam step -- [hdr | forks | skip | ctl | cand | pool ids] -- for `cols` columns in `groups` groups, laid out at l's position in the buffer at
+// base
+static void beam_state_parts(ByteLayout &l, uint8_t *base, size_t cols, size_t groups, size_t cand_per_col, size_t ids_stride, BeamBufs *b) {
+    b->hdr = l.take<bgk::BeamBatchHdr>(base, 1);
+    b->forks = l.take<bgk::BeamFork>(base, cols);
+    b->col_skip = l.take<int32_t>(base, cols);
+    b->ctl = l.take<bgk::BeamCtl>(base, groups);
+    b->cand = l.take<bgk::BeamCand>(base, cols * cand_per_col);
+    b->pool_ids = l.take<int32_t>(base, cols * ids_stride);
+}
+
+// the context's: one block allocated once at its largest (captured steps keep their pointers); bbatch_buf null: the block's size alone
+static BeamBufs beam_bufs_of(biogpt_hip_ctx *c, size_t *bytes = nullptr) {
     const auto &hp = c->hp;
     const int P = hp.n_positions;
     BeamBufs b{};
+    ByteLayout l;
+    beam_state_parts(l, c->bbatch_buf, BBATCH_COLS, BBATCH_COLS, 2 * bgk::BEAM_MAX, (size_t)P, &b);
+    if (bytes) *bytes = l.bytes();
     b.stream = c->stream;
     b.logits = c->logits_all; b.n_vocab = hp.n_vocab;
-    b.hdr = reinterpret_cast<bgk::BeamBatchHdr *>(c->bbatch_buf);
-    b.forks = reinterpret_cast<bgk::BeamFork *>(c->bbatch_buf + bbatch_forks_off());
-    b.col_skip = reinterpret_cast<int32_t *>(c->bbatch_buf + bbatch_skip_off());
-    b.ctl = reinterpret_cast<bgk::BeamCtl *>(c->bbatch_buf + bbatch_ctl_off());
-    b.cand = reinterpret_cast<bgk::BeamCand *>(c->bbatch_buf + bbatch_cand_off());
-    b.pool_ids = reinterpret_cast<int32_t *>(c->bbatch_buf + bbatch_ids_off());
     b.seq = c->seq; b.seq_gen = c->seq_gen; b.gen_stride = P;
     b.bk = c->bk; b.bv = c->bv;
     b.seq_stride = (int64_t)hp.n_layer * P * hp.d_model; b.kv_runs = hp.n_layer * hp.n_head; b.P = P; b.dk = hp.d_model / hp.n_head;
     return b;
+}
+
+// a group's search as a call starts it
+static bgk::BeamCtl beam_ctl_of(int n_beams, int n_prompt, int n_predict, int eos_id, float length_penalty, int early_stopping, int ids_stride) {
+    bgk::BeamCtl c{};
+    c.n_beams = n_beams; c.n_prompt = n_prompt; c.n_predict = n_predict; c.eos_id = eos_id;
+    c.length_penalty = length_penalty; c.early_stopping = early_stopping; c.ids_stride = ids_stride;
+    c.heur_unsat = 1;
+    return c;
+}
+
+// The head of a state block (hdr .. ctl of G groups) as a call starts it: all G searches run, no forks, and the rules kernel skips the columns whose row the first
+// step does not expand.  ids_stride = b.P.
+static bool upload_beam_start(const BeamBufs &b, int G, int B, const int32_t *prompt_lens, int n_predict, int eos_id, float length_penalty, int early_stopping) {
+    HeadImage im(b.hdr, b.ctl + G);
+    im.at(b.hdr)->n_live = G;
+    for (int p = 0; p < G; p++) {
+        im.at(b.ctl)[p] = beam_ctl_of(B, prompt_lens[p], n_predict, eos_id, length_penalty, early_stopping, b.P);
+        for (int j = 1; j < B; j++) im.at(b.col_skip)[p * B + j] = 1;
+    }
+    return im.upload();
 }
 
 static void launch_beam_group_rows(const BeamBufs &b, int G, int B, bool given) {
@@ -3168,8 +3278,6 @@ static bool beam_read_pools(const bgk::BeamCtl *ctl, const int32_t *pool_ids, si
 static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_batch, int32_t n_beams,
                                     int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping, const biogpt_hip_gen_rules *rules,
                                     int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts, double *seconds_out) {
-    XpCallScope xp_scope(ctx);
-    XcBatchScope xc_scope{ctx};
     clear_error();
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompts || !prompt_lens || !out_ids || !out_lens || !out_scores || !out_counts) BG_FAIL(-1, "null argument");
@@ -3191,53 +3299,39 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     if (rules_ban(rules, eos_id) && hp.n_vocab - rules->n_suppress - 1 - P < 2 * B)
         BG_FAIL(-1, "the rules could leave a row fewer than 2 x n_beams candidates: n_vocab - n_suppress - 1 - n_positions = %d < %d", hp.n_vocab - rules->n_suppress - 1 - P, 2 * B);
     const bool ru = rules_active(rules, eos_id);
-    int max_len;
-    long total;
-    if (!check_prompts(ctx, prompts, prompt_lens, G, "prompt", &max_len, &total)) return -1;
-    n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
-    if (n_predict <= 0) return 0;
-    if (!begin_column_call(ctx, n_seqs, total)) return -2;
-    if (!ctx->bbatch_buf) HIP_TRY(-2, hipMalloc(&ctx->bbatch_buf, bbatch_ids_off() + (size_t)BBATCH_COLS * P * 4));
-    column_graphs_for(ctx->graphs_beam, G, B);
-    bgk::BeamBatchHdr *const hdr = reinterpret_cast<bgk::BeamBatchHdr *>(ctx->bbatch_buf);
-    {   // the call's parameters and every group's initial state.  The rules kernel skips the columns whose row the first step does not expand.
-        std::vector<uint8_t> h(bbatch_ctl_off() + sizeof(bgk::BeamCtl) * (size_t)G, 0);
-        bgk::BeamBatchHdr hh{};
-        hh.n_live = G;
-        std::memcpy(h.data(), &hh, sizeof(hh));
-        int32_t *skip = reinterpret_cast<int32_t *>(h.data() + bbatch_skip_off());
-        bgk::BeamCtl *hc = reinterpret_cast<bgk::BeamCtl *>(h.data() + bbatch_ctl_off());
-        for (int p = 0; p < G; p++) {
-            bgk::BeamCtl &c = hc[p];
-            c.n_beams = B; c.n_prompt = prompt_lens[p]; c.n_predict = n_predict; c.eos_id = eos_id;
-            c.length_penalty = length_penalty; c.early_stopping = early_stopping; c.ids_stride = P;
-            c.heur_unsat = 1;
-            for (int j = 1; j < B; j++) skip[p * B + j] = 1;
+    BeamBufs bufs{};
+    std::vector<bgk::BeamCtl> hc;
+    std::vector<int32_t> ids;
+    ColumnCall cc(ctx);
+    cc.prompts = prompts; cc.prompt_lens = prompt_lens;
+    cc.n_prompts = G; cc.per_prompt = B; cc.n_batch = n_batch;
+    cc.graphs = &ctx->graphs_beam; cc.key_a = G; cc.key_b = B;
+    cc.gset_extra = ru ? 12 : 0;
+    cc.prepare = [&]() -> bool {
+        if (!ctx->bbatch_buf) {
+            size_t bytes;
+            beam_bufs_of(ctx, &bytes);
+            HIP_TRY(false, hipMalloc(&ctx->bbatch_buf, bytes));
         }
-        HIP_TRY(-2, hipMemcpy(ctx->bbatch_buf, h.data(), h.size(), hipMemcpyHostToDevice));
-    }
-    if (!upload_column_starts(ctx, prompts, prompt_lens, G, B)) return -2;
-    if (ru && !rules_upload(ctx, rules, 1, eos_id, prompts, prompt_lens, G, B)) return -2;
-
-    const BeamBufs bufs = beam_bufs_of(ctx);
-    const ColumnStep step = [&](int t_max) -> bool {
+        bufs = beam_bufs_of(ctx);
+        cc.live_dev = &bufs.hdr->n_live;
+        return true;
+    };
+    cc.upload = [&]() -> bool {
+        return upload_beam_start(bufs, G, B, prompt_lens, cc.n_predict, eos_id, length_penalty, early_stopping) &&
+               (!ru || rules_upload(ctx, rules, 1, eos_id, prompts, prompt_lens, G, B));
+    };
+    cc.step = [&](int t_max) -> bool {
         return enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max)) && (!ru || enqueue_rules(ctx, n_seqs, bufs.col_skip, 1)) && enqueue_beam_group_select(bufs, G, B, ru);
     };
-    const int gset = 6 * choose_column_path(ctx, n_seqs, max_len) + (ru ? 12 : 0);
-    bool use_graph;
-    if (!capture_column_steps(ctx, ctx->graphs_beam, gset, max_len, n_predict, step, &use_graph)) return -2;
-
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ingest_column_prompts(ctx, prompts, prompt_lens, G, n_batch, B)) return -2;
-    if (!run_column_steps(ctx, ctx->graphs_beam, gset, use_graph, max_len, n_predict, step, &hdr->n_live)) return -2;
-    std::vector<bgk::BeamCtl> hc((size_t)G);
-    std::vector<int32_t> ids((size_t)n_seqs * P);
-    HIP_TRY(-2, hipMemcpyAsync(hc.data(), ctx->bbatch_buf + bbatch_ctl_off(), sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(-2, hipMemcpyAsync(ids.data(), ctx->bbatch_buf + bbatch_ids_off(), ids.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    cc.before_sync = [&]() -> bool {      // every group's pool comes back behind the last step
+        hc.resize((size_t)G); ids.resize((size_t)n_seqs * P);
+        HIP_TRY(false, hipMemcpyAsync(hc.data(), bufs.ctl, sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(false, hipMemcpyAsync(ids.data(), bufs.pool_ids, ids.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        return true;
+    };
+    n_predict = run_column_call(ctx, cc, n_predict, seconds_out);
+    if (n_predict <= 0) return n_predict;
     if (!beam_read_pools(hc.data(), ids.data(), (size_t)P, G, B, n_predict, out_ids, out_lens, out_scores, out_counts)) return -2;
     return n_predict;
 }
@@ -3283,11 +3377,26 @@ int biogpt_hip_generate_beam(biogpt_hip_ctx *ctx, const int32_t *prompt, int32_t
 // K / V cache, position and logits row are left alone.
 constexpr int CONTRAST_COLS = 512;    // columns of a call, at most (and so groups: top_k = 1)
 static int contrast_slabs(const biogpt_hip_ctx *c) { return (c->hp.n_positions + bgk::CT_SLAB - 1) / bgk::CT_SLAB; }
-static size_t contrast_grp_off() { return sizeof(bgk::ContrastCtl); }
-static size_t contrast_cand_off() { return (contrast_grp_off() + sizeof(bgk::ContrastGroup) * CONTRAST_COLS + 15) & ~(size_t)15; }
-static size_t contrast_slab_off(const biogpt_hip_ctx *c) { return contrast_cand_off() + (size_t)CONTRAST_COLS * c->hp.d_model * 4; }
-static size_t contrast_score_off(const biogpt_hip_ctx *c) { return contrast_slab_off(c) + (size_t)CONTRAST_COLS * contrast_slabs(c) * bgk::CT_MAX_K * 4; }
-static size_t contrast_buf_bytes(const biogpt_hip_ctx *c) { return contrast_score_off(c) + (size_t)CONTRAST_COLS * c->hp.n_positions * 4; }
+// The step's device state, one block allocated at the first call at its largest (captured steps keep their pointers); contrast_buf null: the block's size alone
+struct ContrastBufs {
+    bgk::ContrastCtl *ctl;
+    bgk::ContrastGroup *grp;    // [CONTRAST_COLS]
+    float *cand;                // [CONTRAST_COLS][d_model]: the hidden rows of the step's columns
+    float *slab_max;            // [CONTRAST_COLS][slabs][CT_MAX_K]
+    float *scores;              // [CONTRAST_COLS][n_positions]: the winning score of every token
+    size_t bytes;
+};
+static ContrastBufs contrast_bufs_at(uint8_t *base, const biogpt_hip_ctx *c) {
+    ByteLayout l;
+    ContrastBufs b{};
+    b.ctl = l.take<bgk::ContrastCtl>(base, 1);
+    b.grp = l.take<bgk::ContrastGroup>(base, CONTRAST_COLS);
+    b.cand = l.take<float>(base, (size_t)CONTRAST_COLS * c->hp.d_model);
+    b.slab_max = l.take<float>(base, (size_t)CONTRAST_COLS * contrast_slabs(c) * bgk::CT_MAX_K);
+    b.scores = l.take<float>(base, (size_t)CONTRAST_COLS * c->hp.n_positions);
+    b.bytes = l.bytes();
+    return b;
+}
 
 // the rank kernel's dynamic LDS: the candidate rows, at least the room of its closing exchange; above 64 KB it has to be asked for
 static bool contrast_rank_lds(std::set<const void *> *done, int k, int d, size_t *bytes) {
@@ -3324,79 +3433,67 @@ static int generate_contrastive_once(biogpt_hip_ctx *ctx, const int32_t *prompts
     if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
     if (!check_fast_chain(ctx, "contrastive search")) return -1;
     if (V < K) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than top_k candidates", V);
-    int max_len;
-    long total;
-    if (!check_prompts(ctx, prompts, prompt_lens, G, "prompt", &max_len, &total)) return -1;
-    n_predict = std::min(n_predict, P - max_len);  // main.cpp:82, for the longest prompt
-    if (n_predict <= 0) return 0;
-    // every argument has been judged: from here on the call may take (and must give back) the device's pipeline slot and the column-per-XCD hold
-    XpCallScope xp_scope(ctx);
-    XcBatchScope xc_scope{ctx};
-    if (!begin_column_call(ctx, n_seqs, total)) return -2;
-    if (!ctx->contrast_buf) HIP_TRY(-2, hipMalloc(&ctx->contrast_buf, contrast_buf_bytes(ctx)));
-    if (G > ctx->contrast_groups) {      // the context store: new pointers, so the captured steps go
-        if (ctx->contrast_h) (void)hipFree(ctx->contrast_h);
-        ctx->contrast_h = nullptr; ctx->contrast_groups = 0;
-        drop_graphs(ctx->graphs_contrast);
-        const size_t bytes = (size_t)G * P * ((size_t)D * 4 + 8);
-        if (hipMalloc(&ctx->contrast_h, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            BG_FAIL(-2, "contrastive search: no room for the context store of %d prompts (%zu bytes: n_prompts x n_positions x (d_model f32 + one double))", G, bytes);
-        }
-        ctx->contrast_groups = G;
-    }
-    column_graphs_for(ctx->graphs_contrast, G, K);
-    bgk::ContrastCtl *const ctl = reinterpret_cast<bgk::ContrastCtl *>(ctx->contrast_buf);
-    bgk::ContrastGroup *const grp = reinterpret_cast<bgk::ContrastGroup *>(ctx->contrast_buf + contrast_grp_off());
-    float *const cand = reinterpret_cast<float *>(ctx->contrast_buf + contrast_cand_off());
-    float *const slab_max = reinterpret_cast<float *>(ctx->contrast_buf + contrast_slab_off(ctx));
-    float *const scores = reinterpret_cast<float *>(ctx->contrast_buf + contrast_score_off(ctx));
-    float *const H = ctx->contrast_h;
-    double *const Hn = reinterpret_cast<double *>(H + (size_t)ctx->contrast_groups * P * D);
+    ContrastBufs cb{};
+    float *H = nullptr;         // the context store: [groups][n_positions][d_model] f32 rows, then their squared norms
+    double *Hn = nullptr;
+    size_t rank_lds = 0;
     const int n_slabs = contrast_slabs(ctx);
-    {   // the call's parameters and every group's initial state: the prompt without its last token is the context, the first step appends that token's row
-        std::vector<uint8_t> h(contrast_grp_off() + sizeof(bgk::ContrastGroup) * (size_t)G, 0);
-        bgk::ContrastCtl hc{};
-        hc.top_k = K; hc.eos_id = eos_id; hc.n_live = G; hc.alpha = penalty_alpha;
-        std::memcpy(h.data(), &hc, sizeof(hc));
-        bgk::ContrastGroup *hg = reinterpret_cast<bgk::ContrastGroup *>(h.data() + contrast_grp_off());
-        for (int p = 0; p < G; p++) { hg[p].len = prompt_lens[p] - 1; hg[p].first = 1; hg[p].copy_pos = -1; }
-        HIP_TRY(-2, hipMemcpy(ctx->contrast_buf, h.data(), h.size(), hipMemcpyHostToDevice));
-    }
-    if (!upload_column_starts(ctx, prompts, prompt_lens, G, K)) return -2;
-    size_t rank_lds;
-    if (!contrast_rank_lds(&ctx->lds_attr_done, K, D, &rank_lds)) return -2;
-
     const int64_t seq_stride = (int64_t)hp.n_layer * P * D;
-    const ColumnStep step = [&](int t_max) -> bool {
-        if (!enqueue_forward(ctx, ForwardPass::decode_step_hidden(n_seqs, t_max, cand))) return false;
-        hipLaunchKernelGGL(bgk::contrast_rank_kernel, dim3(n_slabs, G), dim3(bgk::CT_THREADS), rank_lds, ctx->stream, cand, H, Hn, grp, K, D, P, slab_max);
-        hipLaunchKernelGGL(bgk::contrast_select_kernel, dim3(G), dim3(bgk::CT_THREADS), 0, ctx->stream, cand, ctx->logits_all, V, V, ctl, grp, slab_max, n_slabs, H, Hn, D, P,
-                           ctx->seq, ctx->seq_gen, P, scores);
+    ColumnCall cc(ctx);
+    cc.prompts = prompts; cc.prompt_lens = prompt_lens;
+    cc.n_prompts = G; cc.per_prompt = K; cc.n_batch = n_batch;
+    cc.graphs = &ctx->graphs_contrast; cc.key_a = G; cc.key_b = K;
+    cc.extra_steps = 1;      // the prompt's last token, then one step per generated token
+    cc.prepare = [&]() -> bool {
+        if (!ctx->contrast_buf) HIP_TRY(false, hipMalloc(&ctx->contrast_buf, contrast_bufs_at(nullptr, ctx).bytes));
+        if (G > ctx->contrast_groups) {      // the context store: new pointers, so the captured steps go
+            if (ctx->contrast_h) (void)hipFree(ctx->contrast_h);
+            ctx->contrast_h = nullptr; ctx->contrast_groups = 0;
+            drop_graphs(ctx->graphs_contrast);
+            const size_t bytes = (size_t)G * P * ((size_t)D * 4 + 8);
+            if (hipMalloc(&ctx->contrast_h, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                BG_FAIL(false, "contrastive search: no room for the context store of %d prompts (%zu bytes: n_prompts x n_positions x (d_model f32 + one double))", G, bytes);
+            }
+            ctx->contrast_groups = G;
+        }
+        cb = contrast_bufs_at(ctx->contrast_buf, ctx);
+        H = ctx->contrast_h;
+        Hn = reinterpret_cast<double *>(H + (size_t)ctx->contrast_groups * P * D);
+        cc.hidden_store = H;
+        if (eos_id >= 0) cc.live_dev = &cb.ctl->n_live;
+        return contrast_rank_lds(&ctx->lds_attr_done, K, D, &rank_lds);
+    };
+    cc.upload = [&]() -> bool {      // the call's parameters and every group's initial state: the prompt without its last token is the context, the first step appends that token's row
+        HeadImage im(cb.ctl, cb.grp + G);
+        bgk::ContrastCtl *hc = im.at(cb.ctl);
+        hc->top_k = K; hc->eos_id = eos_id; hc->n_live = G; hc->alpha = penalty_alpha;
+        bgk::ContrastGroup *hg = im.at(cb.grp);
+        for (int p = 0; p < G; p++) { hg[p].len = prompt_lens[p] - 1; hg[p].first = 1; hg[p].copy_pos = -1; }
+        return im.upload();
+    };
+    cc.step = [&](int t_max) -> bool {
+        if (!enqueue_forward(ctx, ForwardPass::decode_step_hidden(n_seqs, t_max, cb.cand))) return false;
+        hipLaunchKernelGGL(bgk::contrast_rank_kernel, dim3(n_slabs, G), dim3(bgk::CT_THREADS), rank_lds, ctx->stream, cb.cand, H, Hn, cb.grp, K, D, P, cb.slab_max);
+        hipLaunchKernelGGL(bgk::contrast_select_kernel, dim3(G), dim3(bgk::CT_THREADS), 0, ctx->stream, cb.cand, ctx->logits_all, V, V, cb.ctl, cb.grp, cb.slab_max, n_slabs, H, Hn, D, P,
+                           ctx->seq, ctx->seq_gen, P, cb.scores);
         if (K > 1)
-            hipLaunchKernelGGL(bgk::contrast_kv_row_kernel, dim3(hp.n_layer * hp.n_head, G), dim3(256), 0, ctx->stream, grp, K, ctx->bk, ctx->bv, seq_stride, P, D / hp.n_head);
+            hipLaunchKernelGGL(bgk::contrast_kv_row_kernel, dim3(hp.n_layer * hp.n_head, G), dim3(256), 0, ctx->stream, cb.grp, K, ctx->bk, ctx->bv, seq_stride, P, D / hp.n_head);
         HIP_TRY(false, hipGetLastError());
         return true;
     };
-    const int n_steps = n_predict + 1;      // the prompt's last token, then one step per generated token
-    const int gset = 6 * choose_column_path(ctx, n_seqs, max_len);
-    bool use_graph;
-    if (!capture_column_steps(ctx, ctx->graphs_contrast, gset, max_len, n_steps, step, &use_graph)) return -2;
-
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ingest_column_prompts(ctx, prompts, prompt_lens, G, n_batch, K, H)) return -2;
-    hipLaunchKernelGGL(bgk::contrast_norms_kernel, dim3(n_slabs, G), dim3(bgk::CT_THREADS), 0, ctx->stream, H, Hn, grp, D, P);
-    HIP_TRY(-2, hipGetLastError());
-    if (!run_column_steps(ctx, ctx->graphs_contrast, gset, use_graph, max_len, n_steps, step, eos_id >= 0 ? &ctl->n_live : nullptr)) return -2;
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the caller below repeats it on the launch chain)
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    cc.after_ingest = [&]() -> bool {      // the squared norms of the rows the prompt pass left in the store
+        hipLaunchKernelGGL(bgk::contrast_norms_kernel, dim3(n_slabs, G), dim3(bgk::CT_THREADS), 0, ctx->stream, H, Hn, cb.grp, D, P);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    n_predict = run_column_call(ctx, cc, n_predict, seconds_out);
+    if (n_predict <= 0) return n_predict;
     std::vector<int32_t> gen((size_t)n_seqs * P);
     std::vector<float> sc((size_t)G * P);
     std::vector<bgk::SeqState> hs((size_t)n_seqs);
     HIP_TRY(-2, hipMemcpy(gen.data(), ctx->seq_gen, gen.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(sc.data(), scores, sc.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(sc.data(), cb.scores, sc.size() * 4, hipMemcpyDeviceToHost));
     HIP_TRY(-2, hipMemcpy(hs.data(), ctx->seq, sizeof(bgk::SeqState) * n_seqs, hipMemcpyDeviceToHost));
     for (int p = 0; p < G; p++) {      // a group's output is the history of its first column
         const int len = std::max(0, std::min(hs[(size_t)p * K].n_gen, n_predict));
@@ -3418,380 +3515,6 @@ int biogpt_hip_generate_contrastive(biogpt_hip_ctx *ctx, const int32_t *prompts,
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_contrastive_once(ctx, prompts, prompt_lens, n_prompts, n_batch, top_k, penalty_alpha, n_predict, eos_id, out_ids, out_lens, out_scores, seconds_out);
     });
-}
-
-// contrast_rank_kernel + contrast_pick over rows held in host memory (tests of the kernels themselves): k candidate rows against T context rows, no model
-int biogpt_hip_contrast_rank_device(int device, const float *cand, const float *ctx_rows, int32_t k, int32_t T, int32_t d, const float *probs, float alpha,
-                                    float *pen_out, float *score_out, int32_t *winner_out) {
-    clear_error();
-    if (!cand || !ctx_rows || !probs || !pen_out || !score_out || !winner_out) BG_FAIL(-1, "null argument");
-    if (k < 1 || k > bgk::CT_MAX_K) BG_FAIL(-1, "k must be in [1, %d]", bgk::CT_MAX_K);
-    if (T < 1 || T > (1 << 20)) BG_FAIL(-1, "T must be in [1, %d]", 1 << 20);
-    if (d < 4 || d > bgk::CT_MAX_D || d % 4) BG_FAIL(-1, "d must be a multiple of 4 in [4, %d]", bgk::CT_MAX_D);
-    if (!(alpha >= 0.0f && alpha <= 1.0f)) BG_FAIL(-1, "alpha must be in [0, 1]");
-    HIP_TRY(-2, hipSetDevice(device));
-    const int n_slabs = (T + bgk::CT_SLAB - 1) / bgk::CT_SLAB;
-    // [context rows | candidate rows | norms | slab maxima | probabilities | group | out]
-    const size_t o_c = (size_t)T * d * 4, o_n = o_c + (size_t)k * d * 4, o_s = o_n + (size_t)T * 8, o_p = o_s + (size_t)n_slabs * bgk::CT_MAX_K * 4;
-    const size_t o_g = o_p + bgk::CT_MAX_K * 4, o_o = o_g + sizeof(bgk::ContrastGroup), bytes = o_o + (2 * bgk::CT_MAX_K + 1) * 4;
-    uint8_t *dv = nullptr;
-    HIP_TRY(-2, hipMalloc(&dv, bytes));
-    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{dv};
-    bgk::ContrastGroup hg{};
-    hg.len = T;
-    HIP_TRY(-2, hipMemcpy(dv, ctx_rows, o_c, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(dv + o_c, cand, (size_t)k * d * 4, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(dv + o_p, probs, (size_t)k * 4, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(dv + o_g, &hg, sizeof(hg), hipMemcpyHostToDevice));
-    const float *H = reinterpret_cast<const float *>(dv);
-    double *Hn = reinterpret_cast<double *>(dv + o_n);
-    float *slab_max = reinterpret_cast<float *>(dv + o_s);
-    const bgk::ContrastGroup *grp = reinterpret_cast<const bgk::ContrastGroup *>(dv + o_g);
-    size_t rank_lds;
-    if (!contrast_rank_lds(nullptr, k, d, &rank_lds)) return -2;
-    hipLaunchKernelGGL(bgk::contrast_norms_kernel, dim3(n_slabs, 1), dim3(bgk::CT_THREADS), 0, 0, H, Hn, grp, d, T);
-    hipLaunchKernelGGL(bgk::contrast_rank_kernel, dim3(n_slabs, 1), dim3(bgk::CT_THREADS), rank_lds, 0, reinterpret_cast<const float *>(dv + o_c), H, Hn, grp, k, d, T, slab_max);
-    hipLaunchKernelGGL(bgk::contrast_pick_kernel, dim3(1), dim3(bgk::CT_THREADS), 0, 0, slab_max, grp, k, reinterpret_cast<const float *>(dv + o_p), alpha,
-                       reinterpret_cast<float *>(dv + o_o));
-    HIP_TRY(-2, hipGetLastError());
-    HIP_TRY(-2, hipDeviceSynchronize());
-    float out[2 * bgk::CT_MAX_K + 1];
-    HIP_TRY(-2, hipMemcpy(out, dv + o_o, (size_t)(2 * k + 1) * 4, hipMemcpyDeviceToHost));
-    std::memcpy(pen_out, out, (size_t)k * 4);
-    std::memcpy(score_out, out + k, (size_t)k * 4);
-    std::memcpy(winner_out, out + 2 * k, 4);
-    return 0;
-}
-
-// rules_rows_kernel over rows held in host memory (tests of the kernel itself): row r's history is hist_lens[r] tokens of `hist` (the histories
-// concatenated), the first prompt_lens[r] of them its prompt -- laid out for the kernel as a call lays them out (prompt words, generated words)
-int biogpt_hip_rules_rows_device(int device, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist, const int32_t *hist_lens,
-                                 const int32_t *prompt_lens, int32_t eos_id, const biogpt_hip_gen_rules *rules, float *rows_out) {
-    clear_error();
-    if (!rows || !hist || !hist_lens || !prompt_lens || !rules || !rows_out) BG_FAIL(-1, "null argument");
-    if (mode != 0 && mode != 1) BG_FAIL(-1, "mode must be 0 (logits) or 1 (log-probabilities)");
-    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
-    if (eos_id < -1 || eos_id >= n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, n_vocab);
-    if (!check_rules(rules, n_vocab, -1)) return -1;
-    size_t total = 0, n_pr = 0;
-    int gs = 1;
-    for (int r = 0; r < n_rows; r++) {
-        if (hist_lens[r] < 0 || hist_lens[r] > (1 << 20) || prompt_lens[r] < 0 || prompt_lens[r] > hist_lens[r])
-            BG_FAIL(-1, "hist_lens / prompt_lens of row %d: need 0 <= prompt_lens <= hist_lens <= %d", r, 1 << 20);
-        for (int i = 0; i < hist_lens[r]; i++)
-            if (hist[total + i] < 0 || hist[total + i] >= n_vocab) BG_FAIL(-1, "hist: token %d of row %d out of range", i, r);
-        total += (size_t)hist_lens[r]; n_pr += (size_t)prompt_lens[r];
-        gs = std::max(gs, hist_lens[r] - prompt_lens[r]);
-    }
-    HIP_TRY(-2, hipSetDevice(device));
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4;
-    const size_t o_rr = sizeof(bgk::RulesCtl), o_tk = o_rr + sizeof(bgk::RulesRow) * (size_t)n_rows, o_st = (o_tk + n_pr * 4 + 15) & ~(size_t)15;
-    const size_t o_gn = o_st + sizeof(bgk::SeqState) * (size_t)n_rows, side_b = o_gn + (size_t)n_rows * gs * 4;
-    std::vector<uint8_t> h(side_b, 0);      // [ctl | rows | prompt words | column states | generated words]
-    const bgk::RulesCtl hc = rules_ctl_of(rules, mode, eos_id);
-    std::memcpy(h.data(), &hc, sizeof(hc));
-    bgk::RulesRow *rr = reinterpret_cast<bgk::RulesRow *>(h.data() + o_rr);
-    int32_t *tk = reinterpret_cast<int32_t *>(h.data() + o_tk), *gn = reinterpret_cast<int32_t *>(h.data() + o_gn);
-    bgk::SeqState *st = reinterpret_cast<bgk::SeqState *>(h.data() + o_st);
-    size_t at = 0, po = 0;
-    for (int r = 0; r < n_rows; r++) {
-        const int np = prompt_lens[r], ng = hist_lens[r] - np;
-        rr[r] = bgk::RulesRow{(int32_t)po, np};
-        std::memcpy(tk + po, hist + at, (size_t)np * 4);
-        std::memcpy(gn + (size_t)r * gs, hist + at + np, (size_t)ng * 4);
-        st[r].n_gen = ng;
-        at += (size_t)hist_lens[r]; po += (size_t)np;
-    }
-    uint8_t *d = nullptr;
-    const size_t o_side = (lg_b + 15) & ~(size_t)15;
-    HIP_TRY(-2, hipMalloc(&d, o_side + side_b));
-    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
-    HIP_TRY(-2, hipMemcpy(d, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d + o_side, h.data(), side_b, hipMemcpyHostToDevice));
-    uint8_t *const sd = d + o_side;
-    hipLaunchKernelGGL(bgk::rules_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((n_vocab + 31) / 32) * 4, 0, reinterpret_cast<float *>(d), n_vocab, n_vocab,
-                       reinterpret_cast<const bgk::RulesCtl *>(sd), reinterpret_cast<const bgk::RulesRow *>(sd + o_rr), reinterpret_cast<const int32_t *>(sd + o_tk),
-                       reinterpret_cast<const bgk::SeqState *>(sd + o_st), reinterpret_cast<const int32_t *>(sd + o_gn), gs, nullptr, 0);
-    HIP_TRY(-2, hipGetLastError());
-    HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(rows_out, d, lg_b, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// logprob_rows_kernel over rows held in host memory (tests of the kernel itself): ldl = n_vocab, so an odd n_vocab puts rows 1, 2, 3 on the other
-// 16-byte alignments
-int biogpt_hip_logprob_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *targets, float *lp_out, int32_t *argmax_out,
-                                   float *logit_out) {
-    clear_error();
-    if (!rows) BG_FAIL(-1, "rows is NULL");
-    if (!targets) BG_FAIL(-1, "targets is NULL");
-    if (!lp_out || !argmax_out || !logit_out) BG_FAIL(-1, "lp_out, argmax_out or logit_out is NULL");
-    if (n_rows < 1 || n_rows > 4096) BG_FAIL(-1, "n_rows must be in [1, 4096]");
-    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
-    for (int r = 0; r < n_rows; r++)
-        if (targets[r] < -1 || targets[r] >= n_vocab) BG_FAIL(-1, "targets[%d] = %d out of range: must be in [0, %d), or -1 for none", r, targets[r], n_vocab);
-    HIP_TRY(-2, hipSetDevice(device));
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, n_b = (size_t)n_rows * 4;
-    const size_t o_tg = (lg_b + 15) & ~(size_t)15, o_lp = o_tg + n_b, o_am = o_lp + n_b, o_lg = o_am + n_b;      // [rows | targets | lp | arg-max | logit]
-    uint8_t *d = nullptr;
-    HIP_TRY(-2, hipMalloc(&d, o_lg + n_b));
-    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
-    HIP_TRY(-2, hipMemcpy(d, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d + o_tg, targets, n_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d + o_lp, 0xff, 3 * n_b));
-    hipLaunchKernelGGL(bgk::logprob_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, reinterpret_cast<const float *>(d), n_vocab, n_vocab,
-                       reinterpret_cast<const int32_t *>(d + o_tg), reinterpret_cast<float *>(d + o_lp), reinterpret_cast<int32_t *>(d + o_am),
-                       reinterpret_cast<float *>(d + o_lg));
-    HIP_TRY(-2, hipGetLastError());
-    HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(lp_out, d + o_lp, n_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(argmax_out, d + o_am, n_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(logit_out, d + o_lg, n_b, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// what the beam entries below check of a row read as log-probabilities: the row kernel's precondition (the rules' argument check in a call)
-static bool beam_given_rows_ok(const float *rows, size_t n_rows, int n_vocab, int K, const char *what) {
-    for (size_t r = 0; r < n_rows; r++) {
-        int finite = 0;
-        for (int v = 0; v < n_vocab && finite < K; v++) finite += std::isfinite(rows[r * n_vocab + v]) ? 1 : 0;
-        if (finite < K) BG_FAIL(false, "%s: row %zu holds fewer than 2 x n_beams = %d finite log-probabilities", what, r, K);
-    }
-    return true;
-}
-
-// beam_group_rows_kernel over rows held in host memory (tests of the kernel itself), through the dispatch of a call: row r is column r % n_beams of group
-// r / n_beams, run_score[r] the score of the beam in it.  Every candidate is a sentinel (score NaN, col = id = -1) before the launch; with first_step a
-// group's row 0 alone may write.
-int biogpt_hip_beam_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t given, int32_t n_beams, const float *run_score,
-                                int32_t first_step, float *cand_score, int32_t *cand_col, int32_t *cand_id) {
-    clear_error();
-    if (!rows) BG_FAIL(-1, "rows is NULL");
-    if (!run_score) BG_FAIL(-1, "run_score is NULL");
-    if (!cand_score || !cand_col || !cand_id) BG_FAIL(-1, "cand_score, cand_col or cand_id is NULL");
-    if (given != 0 && given != 1) BG_FAIL(-1, "given must be 0 (logits) or 1 (log-probabilities)");
-    if (first_step != 0 && first_step != 1) BG_FAIL(-1, "first_step must be 0 or 1");
-    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
-    if (n_rows < 1 || n_rows > BBATCH_COLS || n_rows % n_beams) BG_FAIL(-1, "n_rows must be a multiple of n_beams in [1, %d]", BBATCH_COLS);
-    if (n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be at most %d", 1 << 20);
-    if (n_vocab < 2 * n_beams) BG_FAIL(-1, "n_vocab: a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", n_vocab);
-    const int B = n_beams, G = n_rows / B, K = 2 * B;
-    if (given && !beam_given_rows_ok(rows, (size_t)n_rows, n_vocab, K, "rows")) return -1;
-    HIP_TRY(-2, hipSetDevice(device));
-    std::vector<bgk::BeamCtl> hc((size_t)G);
-    for (int g = 0; g < G; g++) {
-        bgk::BeamCtl &c = hc[(size_t)g];
-        c = bgk::BeamCtl{};
-        c.n_beams = B; c.step = first_step ? 0 : 1; c.heur_unsat = 1;
-        for (int j = 0; j < B; j++) { c.run_score[j] = run_score[g * B + j]; c.col_rank[j] = j; }
-    }
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, ctl_b = sizeof(bgk::BeamCtl) * (size_t)G, cd_b = sizeof(bgk::BeamCand) * (size_t)n_rows * K;
-    const size_t o_hd = (lg_b + 15) & ~(size_t)15, o_ct = o_hd + sizeof(bgk::BeamBatchHdr), o_cd = (o_ct + ctl_b + 15) & ~(size_t)15;     // [rows | hdr | ctl | cand]
-    uint8_t *d = nullptr;
-    HIP_TRY(-2, hipMalloc(&d, o_cd + cd_b));
-    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
-    HIP_TRY(-2, hipMemcpy(d, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d + o_hd, 0, sizeof(bgk::BeamBatchHdr)));
-    HIP_TRY(-2, hipMemcpy(d + o_ct, hc.data(), ctl_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d + o_cd, 0xff, cd_b));
-    BeamBufs b{};
-    b.stream = 0;
-    b.logits = reinterpret_cast<const float *>(d); b.n_vocab = n_vocab;
-    b.hdr = reinterpret_cast<bgk::BeamBatchHdr *>(d + o_hd);
-    b.ctl = reinterpret_cast<bgk::BeamCtl *>(d + o_ct);
-    b.cand = reinterpret_cast<bgk::BeamCand *>(d + o_cd);
-    launch_beam_group_rows(b, G, B, given != 0);
-    HIP_TRY(-2, hipGetLastError());
-    HIP_TRY(-2, hipDeviceSynchronize());
-    std::vector<bgk::BeamCand> out((size_t)n_rows * K);
-    HIP_TRY(-2, hipMemcpy(out.data(), d + o_cd, cd_b, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < out.size(); i++) { cand_score[i] = out[i].score; cand_col[i] = out[i].col; cand_id[i] = out[i].id; }
-    return 0;
-}
-
-// A whole beam search over the three beam kernels with the model replaced by a lookup (beam_table_feed_kernel, kernels_beam.hip.h), through the step
-// and the read-out of biogpt_hip_generate_beam_batch: at most max_steps steps of feed + rows + select + fork, the live-group word read after each.
-// Not capturable (it synchronizes every step).
-int biogpt_hip_beam_table_device(int device, const float *table, int32_t n_table_rows, int32_t n_vocab, int32_t given, const int32_t *start_tokens,
-                                 const int32_t *prompt_lens, int32_t n_groups, int32_t n_beams, int32_t n_predict, int32_t eos_id, float length_penalty,
-                                 int32_t early_stopping, int32_t max_steps, int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts,
-                                 int32_t *col_token, int32_t *col_n_gen, int32_t *col_hist, float *col_run_score, int32_t *col_rank, int32_t *grp_done,
-                                 int32_t *grp_step, float *kv_out) {
-    clear_error();
-    if (!table) BG_FAIL(-1, "table is NULL");
-    if (!start_tokens || !prompt_lens) BG_FAIL(-1, "start_tokens or prompt_lens is NULL");
-    if (!out_ids || !out_lens || !out_scores || !out_counts) BG_FAIL(-1, "out_ids, out_lens, out_scores or out_counts is NULL");
-    if (!col_token || !col_n_gen || !col_hist || !col_run_score || !col_rank || !grp_done || !grp_step || !kv_out) BG_FAIL(-1, "a state output (col_*, grp_*, kv_out) is NULL");
-    if (given != 0 && given != 1) BG_FAIL(-1, "given must be 0 (logits) or 1 (log-probabilities)");
-    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
-    if (n_groups < 1 || (int64_t)n_groups * n_beams > BBATCH_COLS) BG_FAIL(-1, "n_groups x n_beams must be in [1, %d]", BBATCH_COLS);
-    if (n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be at most %d", 1 << 20);
-    if (n_vocab < 2 * n_beams) BG_FAIL(-1, "n_vocab: a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", n_vocab);
-    if (n_table_rows < 1 || n_table_rows > (1 << 16)) BG_FAIL(-1, "n_table_rows must be in [1, %d]", 1 << 16);
-    if (n_predict < 1 || n_predict > 1024) BG_FAIL(-1, "n_predict must be in [1, 1024]");
-    if (max_steps < 1) BG_FAIL(-1, "max_steps must be >= 1");
-    if (eos_id < -1 || eos_id >= n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, n_vocab);
-    if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
-    if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
-    const int G = n_groups, B = n_beams, n_cols = G * B;
-    int max_len = 0;
-    for (int g = 0; g < G; g++) {
-        if (prompt_lens[g] < 1 || prompt_lens[g] > 1024) BG_FAIL(-1, "prompt_lens[%d] must be in [1, 1024]", g);
-        if (start_tokens[g] < 0 || start_tokens[g] >= n_vocab) BG_FAIL(-1, "start_tokens[%d] = %d out of range: must be in [0, %d)", g, start_tokens[g], n_vocab);
-        max_len = std::max(max_len, prompt_lens[g]);
-    }
-    if (given && !beam_given_rows_ok(table, (size_t)n_table_rows, n_vocab, 2 * B, "table")) return -1;
-    HIP_TRY(-2, hipSetDevice(device));
-    const int P = max_len + n_predict;
-    constexpr int H = bgk::TABLE_HEADS, DK = bgk::TABLE_DK;
-    // [table | logits | K | V | hdr | forks | skip | ctl | cand | pool ids | column states | histories], each part 16-byte aligned
-    size_t at = 0;
-    auto part = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
-    const size_t kv_b = (size_t)n_cols * H * P * DK * 4;
-    const size_t o_tb = part((size_t)n_table_rows * n_vocab * 4), o_lg = part((size_t)n_cols * n_vocab * 4), o_k = part(kv_b), o_v = part(kv_b);
-    const size_t o_hd = part(sizeof(bgk::BeamBatchHdr)), o_fk = part(sizeof(bgk::BeamFork) * (size_t)n_cols), o_sk = part((size_t)n_cols * 4);
-    const size_t o_ct = part(sizeof(bgk::BeamCtl) * (size_t)G), o_cd = part(sizeof(bgk::BeamCand) * (size_t)n_cols * 2 * B), o_id = part((size_t)n_cols * P * 4);
-    const size_t o_sq = part(sizeof(bgk::SeqState) * (size_t)n_cols), o_gn = part((size_t)n_cols * P * 4);
-    uint8_t *d = nullptr;
-    HIP_TRY(-2, hipMalloc(&d, at));
-    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
-    std::vector<bgk::BeamCtl> hc((size_t)G);
-    std::vector<bgk::SeqState> hs((size_t)n_cols);
-    std::vector<int32_t> skip((size_t)n_cols, 0);
-    for (int g = 0; g < G; g++) {       // the initial state of a call (generate_beam_batch_once, upload_column_starts)
-        bgk::BeamCtl &c = hc[(size_t)g];
-        c = bgk::BeamCtl{};
-        c.n_beams = B; c.n_prompt = prompt_lens[g]; c.n_predict = n_predict; c.eos_id = eos_id;
-        c.length_penalty = length_penalty; c.early_stopping = early_stopping; c.ids_stride = P;
-        c.heur_unsat = 1;
-        for (int j = 0; j < B; j++) {
-            bgk::SeqState &st = hs[(size_t)g * B + j];
-            st = bgk::SeqState{};
-            st.n_past = prompt_lens[g] - 1; st.token = start_tokens[g]; st.seq_id = g * B + j;
-            if (j > 0) skip[(size_t)g * B + j] = 1;
-        }
-    }
-    bgk::BeamBatchHdr hh{};
-    hh.n_live = G;
-    std::vector<float> kv_fill(2 * kv_b / 4, -1.0f);       // a row no step has written reads -1
-    HIP_TRY(-2, hipMemcpy(d + o_tb, table, (size_t)n_table_rows * n_vocab * 4, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d + o_lg, 0, (size_t)n_cols * n_vocab * 4));
-    HIP_TRY(-2, hipMemcpy(d + o_k, kv_fill.data(), kv_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d + o_v, kv_fill.data(), kv_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d + o_hd, &hh, sizeof(hh), hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d + o_fk, 0, sizeof(bgk::BeamFork) * (size_t)n_cols));
-    HIP_TRY(-2, hipMemcpy(d + o_sk, skip.data(), (size_t)n_cols * 4, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d + o_ct, hc.data(), sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d + o_cd, 0xff, sizeof(bgk::BeamCand) * (size_t)n_cols * 2 * B));
-    HIP_TRY(-2, hipMemset(d + o_id, 0xff, (size_t)n_cols * P * 4));
-    HIP_TRY(-2, hipMemcpy(d + o_sq, hs.data(), sizeof(bgk::SeqState) * (size_t)n_cols, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d + o_gn, 0xff, (size_t)n_cols * P * 4));
-    BeamBufs b{};
-    b.stream = 0;
-    b.logits = reinterpret_cast<const float *>(d + o_lg); b.n_vocab = n_vocab;
-    b.hdr = reinterpret_cast<bgk::BeamBatchHdr *>(d + o_hd);
-    b.forks = reinterpret_cast<bgk::BeamFork *>(d + o_fk);
-    b.col_skip = reinterpret_cast<int32_t *>(d + o_sk);
-    b.ctl = reinterpret_cast<bgk::BeamCtl *>(d + o_ct);
-    b.cand = reinterpret_cast<bgk::BeamCand *>(d + o_cd);
-    b.pool_ids = reinterpret_cast<int32_t *>(d + o_id);
-    b.seq = reinterpret_cast<bgk::SeqState *>(d + o_sq);
-    b.seq_gen = reinterpret_cast<int32_t *>(d + o_gn); b.gen_stride = P;
-    b.bk = reinterpret_cast<float *>(d + o_k); b.bv = reinterpret_cast<float *>(d + o_v);
-    b.seq_stride = (int64_t)H * P * DK; b.kv_runs = H; b.P = P; b.dk = DK;
-    int n_live = G;
-    for (int s = 0; s < std::min(max_steps, n_predict) && n_live > 0; s++) {
-        hipLaunchKernelGGL(bgk::beam_table_feed_kernel, dim3(n_cols), dim3(256), 0, 0, b.seq, reinterpret_cast<const float *>(d + o_tb), n_table_rows, n_vocab,
-                           reinterpret_cast<float *>(d + o_lg), b.bk, b.bv, P);
-        HIP_TRY(-2, hipGetLastError());
-        if (!enqueue_beam_group_select(b, G, B, given != 0)) return -2;
-        HIP_TRY(-2, hipMemcpy(&hh, d + o_hd, sizeof(hh), hipMemcpyDeviceToHost));      // (synchronizes)
-        n_live = hh.n_live;
-    }
-    std::vector<int32_t> ids((size_t)n_cols * P), gen((size_t)n_cols * P);
-    HIP_TRY(-2, hipMemcpy(hc.data(), d + o_ct, sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(hs.data(), d + o_sq, sizeof(bgk::SeqState) * (size_t)n_cols, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(ids.data(), d + o_id, ids.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(gen.data(), d + o_gn, gen.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(kv_out, d + o_k, kv_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(kv_out + kv_b / 4, d + o_v, kv_b, hipMemcpyDeviceToHost));
-    for (int g = 0; g < G; g++) {
-        grp_done[g] = hc[(size_t)g].done; grp_step[g] = hc[(size_t)g].step;
-        for (int j = 0; j < B; j++) {
-            const size_t c = (size_t)g * B + j;
-            col_token[c] = hs[c].token; col_n_gen[c] = hs[c].n_gen;
-            col_run_score[c] = hc[(size_t)g].run_score[j]; col_rank[c] = hc[(size_t)g].col_rank[j];
-            std::memcpy(col_hist + c * n_predict, gen.data() + c * P, (size_t)n_predict * 4);
-        }
-    }
-    if (n_live > 0) {       // stopped by max_steps: no result yet
-        std::fill(out_ids, out_ids + (size_t)n_cols * n_predict, -1);
-        std::fill(out_lens, out_lens + n_cols, 0);
-        std::fill(out_scores, out_scores + n_cols, 0.0f);
-        std::fill(out_counts, out_counts + G, 0);
-        return 0;
-    }
-    if (!beam_read_pools(hc.data(), ids.data(), (size_t)P, G, B, n_predict, out_ids, out_lens, out_scores, out_counts)) return -2;
-    return n_predict;
-}
-
-// the sampler's tail and its generator on the host: no device, no context
-int biogpt_hip_mt19937_seed(uint32_t seed, uint32_t *state625) {
-    clear_error();
-    if (!state625) BG_FAIL(-1, "null argument");
-    bgk::mt_seed(seed, state625);
-    return 0;
-}
-int biogpt_hip_sample_candidates_host(const float *vals, const int32_t *ids, int32_t k, double top_p, double temp, uint32_t *mt_state625, int32_t *id_out) {
-    clear_error();
-    if (!vals || !ids || !mt_state625 || !id_out) BG_FAIL(-1, "null argument");
-    if (k < 1 || k > (1 << 20)) BG_FAIL(-1, "k must be in [1, %d]", 1 << 20);
-    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
-    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
-    if (mt_state625[bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index %u out of range", mt_state625[bgk::MT_N]);
-    bgk::SampleWork w;
-    std::vector<double> p((size_t)k);
-    *id_out = ids[bgk::sample_tail(vals, k, top_p, temp, mt_state625, p.data(), w, 0, 1, bgk::SampleNoSync())];
-    return 0;
-}
-
-// sample_rows_kernel over rows held in host memory (tests: ties, any row width and alignment, the selection's round form, a generator block running
-// out): row r draws from mt_states[r] (625 words, advanced in place; the words of a block regenerated on the device are those of the host's form)
-int biogpt_hip_sample_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, int32_t top_k, double top_p, double temp,
-                                  uint32_t *mt_states, int32_t *ids_out) {
-    clear_error();
-    if (!logits || !mt_states || !ids_out) BG_FAIL(-1, "null argument");
-    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
-    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > n_vocab) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
-    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
-    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
-    for (int r = 0; r < n_rows; r++)
-        if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
-    HIP_TRY(-2, hipSetDevice(device));
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sizeof(bgk::SampleCtl) + sizeof(bgk::SampleSeq) * (size_t)n_rows;
-    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = (size_t)n_rows * 4;
-    std::vector<uint8_t> h(sq_b, 0);
-    bgk::SampleCtl hc{};
-    hc.top_k = top_k; hc.eos_id = -1; hc.n_live = n_rows; hc.top_p = top_p; hc.temp = temp;
-    std::memcpy(h.data(), &hc, sizeof(hc));
-    bgk::SampleSeq *hq = reinterpret_cast<bgk::SampleSeq *>(h.data() + sizeof(bgk::SampleCtl));
-    for (int r = 0; r < n_rows; r++) std::memcpy(hq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
-    uint8_t *d = nullptr;      // [logits | ctl + states | column states | ids], each part 16-byte aligned
-    const size_t o_sq = (lg_b + 15) & ~(size_t)15, o_st = (o_sq + sq_b + 15) & ~(size_t)15, o_id = (o_st + st_b + 15) & ~(size_t)15;
-    HIP_TRY(-2, hipMalloc(&d, o_id + id_b));
-    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } guard{d};
-    HIP_TRY(-2, hipMemcpy(d, logits, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d + o_sq, h.data(), sq_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d + o_st, 0, o_id + id_b - o_st));
-    hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, reinterpret_cast<const float *>(d), n_vocab, n_vocab,
-                       reinterpret_cast<bgk::SampleCtl *>(d + o_sq), reinterpret_cast<bgk::SampleSeq *>(d + o_sq + sizeof(bgk::SampleCtl)),
-                       reinterpret_cast<bgk::SeqState *>(d + o_st), reinterpret_cast<int32_t *>(d + o_id), 1);
-    HIP_TRY(-2, hipGetLastError());
-    HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(h.data(), d + o_sq, sq_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(ids_out, d + o_id, id_b, hipMemcpyDeviceToHost));
-    for (int r = 0; r < n_rows; r++) std::memcpy(mt_states + (size_t)r * 625, hq[r].mt, 625 * 4);
-    return 0;
 }
 
 // profiling builds (BIOGPT_HIP_PROFILE_HOOKS + BIOGPT_HIP_DBG=128): the raw 100 MHz stage stamps the pipelined launches left (kernels_xpipe.hip.h XP_WALL / XP_TAIL)
@@ -3817,45 +3540,19 @@ int biogpt_hip_read_kv(biogpt_hip_ctx *ctx, int which, size_t offset, size_t cou
     if (!resident_stop(ctx)) return -2;
     // the device cache is head-major [layer][head][pos][dk]; the caller sees the reference's flat [layer][pos][d_model]
     // view (biogpt.cpp:331-335).  Only the requested range is gathered on the device and copied.
-    float *stage = nullptr;
-    HIP_TRY(-2, hipMalloc(&stage, count * 4));
+    DeviceBytes stage;
+    if (!stage.alloc(count * 4)) return -2;
     const float *cache = which ? ctx->memory_v : ctx->memory_k;
-    hipLaunchKernelGGL(bgk::kv_gather_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, cache, stage, (unsigned long long)offset,
+    hipLaunchKernelGGL(bgk::kv_gather_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, cache, stage.at<float>(0), (unsigned long long)offset,
                        (unsigned long long)count, (int)P, (int)D, (int)H, (int)dk);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, stage, count * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(stage);
-    HIP_TRY(-2, e);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipMemcpyAsync(out, stage.p, count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
 #include "engine_bench.inc"
-// SURVEY 8 f1 on the device: `nrows` rows of `k` f32 values (host memory) -> the file's block format of `type`, byte-identical to
-// the host quantizer (biogpt_hip_quantize_file uses the host one: it has to work without a GPU)
-int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, int64_t nrows, int64_t k, uint8_t *dst) {
-    clear_error();
-    if (!src || !dst || nrows < 1 || k < QK || k % QK) BG_FAIL(-1, "bad argument (row length must be a multiple of %d)", QK);
-    if (!is_quantized(type)) BG_FAIL(-1, "type %d is not a block-quantized format", type);
-    if (!select_device(device)) return -1;
-    const long long nblocks = (long long)nrows * (k / QK);
-    const size_t in_bytes = (size_t)nrows * (size_t)k * 4, out_bytes = (size_t)nblocks * file_block_bytes(type);
-    float *d_src = nullptr;
-    uint8_t *d_dst = nullptr;
-    HIP_TRY(-2, hipMalloc(&d_src, in_bytes));
-    if (hipMalloc(&d_dst, out_bytes) != hipSuccess) { (void)hipFree(d_src); BG_FAIL(-2, "hipMalloc of %zu bytes failed", out_bytes); }
-    hipError_t e = hipMemcpy(d_src, src, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(bgk::quantize_blocks_kernel, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, 0, d_src, d_dst, nblocks, (int)type,
-                           (int)file_block_bytes(type));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(dst, d_dst, out_bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d_src); (void)hipFree(d_dst);
-    HIP_TRY(-2, e);
-    return 0;
-}
-
+#include "engine_probe.inc"
 int biogpt_hip_quantize_file(const char *fname_in, const char *fname_out, int32_t ftype) {
     clear_error();
     if (!fname_in || !fname_out) BG_FAIL(-1, "null file name");

@@ -1,0 +1,365 @@
+// Kernels reached without a model (tests of the kernels themselves, tools): rows held in host memory go to scratch device memory, the kernel runs as a call
+// launches it, the results come back.  Part of engine.hip's translation unit.  Each entry reads: checks, layout, upload, launch, read back.
+
+// contrast_rank_kernel + contrast_pick over rows held in host memory (tests of the kernels themselves): k candidate rows against T context rows, no model
+int biogpt_hip_contrast_rank_device(int device, const float *cand, const float *ctx_rows, int32_t k, int32_t T, int32_t d, const float *probs, float alpha,
+                                    float *pen_out, float *score_out, int32_t *winner_out) {
+    clear_error();
+    if (!cand || !ctx_rows || !probs || !pen_out || !score_out || !winner_out) BG_FAIL(-1, "null argument");
+    if (k < 1 || k > bgk::CT_MAX_K) BG_FAIL(-1, "k must be in [1, %d]", bgk::CT_MAX_K);
+    if (T < 1 || T > (1 << 20)) BG_FAIL(-1, "T must be in [1, %d]", 1 << 20);
+    if (d < 4 || d > bgk::CT_MAX_D || d % 4) BG_FAIL(-1, "d must be a multiple of 4 in [4, %d]", bgk::CT_MAX_D);
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) BG_FAIL(-1, "alpha must be in [0, 1]");
+    HIP_TRY(-2, hipSetDevice(device));
+    const int n_slabs = (T + bgk::CT_SLAB - 1) / bgk::CT_SLAB;
+    ByteLayout l;      // [context rows | candidate rows | norms | slab maxima | probabilities | group | out]
+    const size_t o_h = l.part((size_t)T * d * 4), o_c = l.part((size_t)k * d * 4), o_n = l.part((size_t)T * 8), o_s = l.part((size_t)n_slabs * bgk::CT_MAX_K * 4);
+    const size_t o_p = l.part(bgk::CT_MAX_K * 4), o_g = l.part(sizeof(bgk::ContrastGroup)), o_o = l.part((2 * bgk::CT_MAX_K + 1) * 4);
+    DeviceBytes dv;
+    if (!dv.alloc(l.bytes())) return -2;
+    bgk::ContrastGroup hg{};
+    hg.len = T;
+    HIP_TRY(-2, hipMemcpy(dv.p + o_h, ctx_rows, (size_t)T * d * 4, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(dv.p + o_c, cand, (size_t)k * d * 4, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(dv.p + o_p, probs, (size_t)k * 4, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(dv.p + o_g, &hg, sizeof(hg), hipMemcpyHostToDevice));
+    const float *H = dv.at<float>(o_h);
+    double *Hn = dv.at<double>(o_n);
+    float *slab_max = dv.at<float>(o_s);
+    const bgk::ContrastGroup *grp = dv.at<bgk::ContrastGroup>(o_g);
+    size_t rank_lds;
+    if (!contrast_rank_lds(nullptr, k, d, &rank_lds)) return -2;
+    hipLaunchKernelGGL(bgk::contrast_norms_kernel, dim3(n_slabs, 1), dim3(bgk::CT_THREADS), 0, 0, H, Hn, grp, d, T);
+    hipLaunchKernelGGL(bgk::contrast_rank_kernel, dim3(n_slabs, 1), dim3(bgk::CT_THREADS), rank_lds, 0, dv.at<const float>(o_c), H, Hn, grp, k, d, T, slab_max);
+    hipLaunchKernelGGL(bgk::contrast_pick_kernel, dim3(1), dim3(bgk::CT_THREADS), 0, 0, slab_max, grp, k, dv.at<const float>(o_p), alpha, dv.at<float>(o_o));
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    float out[2 * bgk::CT_MAX_K + 1];
+    HIP_TRY(-2, hipMemcpy(out, dv.p + o_o, (size_t)(2 * k + 1) * 4, hipMemcpyDeviceToHost));
+    std::memcpy(pen_out, out, (size_t)k * 4);
+    std::memcpy(score_out, out + k, (size_t)k * 4);
+    std::memcpy(winner_out, out + 2 * k, 4);
+    return 0;
+}
+
+// rules_rows_kernel over rows held in host memory (tests of the kernel itself): row r's history is hist_lens[r] tokens of `hist` (the histories
+// concatenated), the first prompt_lens[r] of them its prompt -- laid out for the kernel as a call lays them out (prompt words, generated words)
+int biogpt_hip_rules_rows_device(int device, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist, const int32_t *hist_lens,
+                                 const int32_t *prompt_lens, int32_t eos_id, const biogpt_hip_gen_rules *rules, float *rows_out) {
+    clear_error();
+    if (!rows || !hist || !hist_lens || !prompt_lens || !rules || !rows_out) BG_FAIL(-1, "null argument");
+    if (mode != 0 && mode != 1) BG_FAIL(-1, "mode must be 0 (logits) or 1 (log-probabilities)");
+    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
+    if (eos_id < -1 || eos_id >= n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, n_vocab);
+    if (!check_rules(rules, n_vocab, -1)) return -1;
+    size_t total = 0, n_pr = 0;
+    int gs = 1;
+    for (int r = 0; r < n_rows; r++) {
+        if (hist_lens[r] < 0 || hist_lens[r] > (1 << 20) || prompt_lens[r] < 0 || prompt_lens[r] > hist_lens[r])
+            BG_FAIL(-1, "hist_lens / prompt_lens of row %d: need 0 <= prompt_lens <= hist_lens <= %d", r, 1 << 20);
+        for (int i = 0; i < hist_lens[r]; i++)
+            if (hist[total + i] < 0 || hist[total + i] >= n_vocab) BG_FAIL(-1, "hist: token %d of row %d out of range", i, r);
+        total += (size_t)hist_lens[r]; n_pr += (size_t)prompt_lens[r];
+        gs = std::max(gs, hist_lens[r] - prompt_lens[r]);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4;
+    ByteLayout sl;      // the side image: [ctl | rows | prompt words | column states | generated words]
+    const size_t o_ct = sl.part(sizeof(bgk::RulesCtl)), o_rr = sl.part(sizeof(bgk::RulesRow) * (size_t)n_rows), o_tk = sl.part(n_pr * 4);
+    const size_t o_st = sl.part(sizeof(bgk::SeqState) * (size_t)n_rows), o_gn = sl.part((size_t)n_rows * gs * 4);
+    std::vector<uint8_t> h(sl.bytes(), 0);
+    *reinterpret_cast<bgk::RulesCtl *>(h.data() + o_ct) = rules_ctl_of(rules, mode, eos_id);
+    bgk::RulesRow *rr = reinterpret_cast<bgk::RulesRow *>(h.data() + o_rr);
+    int32_t *tk = reinterpret_cast<int32_t *>(h.data() + o_tk), *gn = reinterpret_cast<int32_t *>(h.data() + o_gn);
+    bgk::SeqState *st = reinterpret_cast<bgk::SeqState *>(h.data() + o_st);
+    size_t at = 0, po = 0;
+    for (int r = 0; r < n_rows; r++) {
+        const int np = prompt_lens[r], ng = hist_lens[r] - np;
+        rr[r] = bgk::RulesRow{(int32_t)po, np};
+        std::memcpy(tk + po, hist + at, (size_t)np * 4);
+        std::memcpy(gn + (size_t)r * gs, hist + at + np, (size_t)ng * 4);
+        st[r].n_gen = ng;
+        at += (size_t)hist_lens[r]; po += (size_t)np;
+    }
+    ByteLayout l;       // [rows | side image]
+    const size_t o_lg = l.part(lg_b), o_side = l.part(h.size());
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_side, h.data(), h.size(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(bgk::rules_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((n_vocab + 31) / 32) * 4, 0, d.at<float>(o_lg), n_vocab, n_vocab,
+                       d.at<const bgk::RulesCtl>(o_side + o_ct), d.at<const bgk::RulesRow>(o_side + o_rr), d.at<const int32_t>(o_side + o_tk),
+                       d.at<const bgk::SeqState>(o_side + o_st), d.at<const int32_t>(o_side + o_gn), gs, nullptr, 0);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(rows_out, d.p + o_lg, lg_b, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// logprob_rows_kernel over rows held in host memory (tests of the kernel itself): ldl = n_vocab, so an odd n_vocab puts rows 1, 2, 3 on the other
+// 16-byte alignments
+int biogpt_hip_logprob_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *targets, float *lp_out, int32_t *argmax_out,
+                                   float *logit_out) {
+    clear_error();
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!targets) BG_FAIL(-1, "targets is NULL");
+    if (!lp_out || !argmax_out || !logit_out) BG_FAIL(-1, "lp_out, argmax_out or logit_out is NULL");
+    if (n_rows < 1 || n_rows > 4096) BG_FAIL(-1, "n_rows must be in [1, 4096]");
+    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
+    for (int r = 0; r < n_rows; r++)
+        if (targets[r] < -1 || targets[r] >= n_vocab) BG_FAIL(-1, "targets[%d] = %d out of range: must be in [0, %d), or -1 for none", r, targets[r], n_vocab);
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, n_b = (size_t)n_rows * 4;
+    ByteLayout l;      // [rows | targets | lp, arg-max, logit: three arrays of n_rows words, one after another]
+    const size_t o_lg = l.part(lg_b), o_tg = l.part(n_b), o_lp = l.part(3 * n_b), o_am = o_lp + n_b, o_tl = o_am + n_b;
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_tg, targets, n_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_lp, 0xff, 3 * n_b));
+    hipLaunchKernelGGL(bgk::logprob_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, d.at<const int32_t>(o_tg),
+                       d.at<float>(o_lp), d.at<int32_t>(o_am), d.at<float>(o_tl));
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(lp_out, d.p + o_lp, n_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(argmax_out, d.p + o_am, n_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(logit_out, d.p + o_tl, n_b, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// what the beam entries below check of a row read as log-probabilities: the row kernel's precondition (the rules' argument check in a call)
+static bool beam_given_rows_ok(const float *rows, size_t n_rows, int n_vocab, int K, const char *what) {
+    for (size_t r = 0; r < n_rows; r++) {
+        int finite = 0;
+        for (int v = 0; v < n_vocab && finite < K; v++) finite += std::isfinite(rows[r * n_vocab + v]) ? 1 : 0;
+        if (finite < K) BG_FAIL(false, "%s: row %zu holds fewer than 2 x n_beams = %d finite log-probabilities", what, r, K);
+    }
+    return true;
+}
+
+// beam_group_rows_kernel over rows held in host memory (tests of the kernel itself), through the dispatch of a call: row r is column r % n_beams of group
+// r / n_beams, run_score[r] the score of the beam in it.  Every candidate is a sentinel (score NaN, col = id = -1) before the launch; with first_step a
+// group's row 0 alone may write.
+int biogpt_hip_beam_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t given, int32_t n_beams, const float *run_score,
+                                int32_t first_step, float *cand_score, int32_t *cand_col, int32_t *cand_id) {
+    clear_error();
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!run_score) BG_FAIL(-1, "run_score is NULL");
+    if (!cand_score || !cand_col || !cand_id) BG_FAIL(-1, "cand_score, cand_col or cand_id is NULL");
+    if (given != 0 && given != 1) BG_FAIL(-1, "given must be 0 (logits) or 1 (log-probabilities)");
+    if (first_step != 0 && first_step != 1) BG_FAIL(-1, "first_step must be 0 or 1");
+    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
+    if (n_rows < 1 || n_rows > BBATCH_COLS || n_rows % n_beams) BG_FAIL(-1, "n_rows must be a multiple of n_beams in [1, %d]", BBATCH_COLS);
+    if (n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be at most %d", 1 << 20);
+    if (n_vocab < 2 * n_beams) BG_FAIL(-1, "n_vocab: a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", n_vocab);
+    const int B = n_beams, G = n_rows / B, K = 2 * B;
+    if (given && !beam_given_rows_ok(rows, (size_t)n_rows, n_vocab, K, "rows")) return -1;
+    HIP_TRY(-2, hipSetDevice(device));
+    std::vector<bgk::BeamCtl> hc((size_t)G);
+    for (int g = 0; g < G; g++) {
+        bgk::BeamCtl &c = hc[(size_t)g];
+        c = bgk::BeamCtl{};
+        c.n_beams = B; c.step = first_step ? 0 : 1; c.heur_unsat = 1;
+        for (int j = 0; j < B; j++) { c.run_score[j] = run_score[g * B + j]; c.col_rank[j] = j; }
+    }
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, ctl_b = sizeof(bgk::BeamCtl) * (size_t)G, cd_b = sizeof(bgk::BeamCand) * (size_t)n_rows * K;
+    ByteLayout l;      // [rows | hdr | ctl | cand]
+    const size_t o_lg = l.part(lg_b), o_hd = l.part(sizeof(bgk::BeamBatchHdr)), o_ct = l.part(ctl_b), o_cd = l.part(cd_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_hd, 0, sizeof(bgk::BeamBatchHdr)));
+    HIP_TRY(-2, hipMemcpy(d.p + o_ct, hc.data(), ctl_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_cd, 0xff, cd_b));
+    BeamBufs b{};
+    b.stream = 0;
+    b.logits = d.at<const float>(o_lg); b.n_vocab = n_vocab;
+    b.hdr = d.at<bgk::BeamBatchHdr>(o_hd); b.ctl = d.at<bgk::BeamCtl>(o_ct); b.cand = d.at<bgk::BeamCand>(o_cd);
+    launch_beam_group_rows(b, G, B, given != 0);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    std::vector<bgk::BeamCand> out((size_t)n_rows * K);
+    HIP_TRY(-2, hipMemcpy(out.data(), d.p + o_cd, cd_b, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < out.size(); i++) { cand_score[i] = out[i].score; cand_col[i] = out[i].col; cand_id[i] = out[i].id; }
+    return 0;
+}
+
+// A whole beam search over the three beam kernels with the model replaced by a lookup (beam_table_feed_kernel, kernels_beam.hip.h), through the step
+// and the read-out of biogpt_hip_generate_beam_batch: at most max_steps steps of feed + rows + select + fork, the live-group word read after each.
+// Not capturable (it synchronizes every step).
+int biogpt_hip_beam_table_device(int device, const float *table, int32_t n_table_rows, int32_t n_vocab, int32_t given, const int32_t *start_tokens,
+                                 const int32_t *prompt_lens, int32_t n_groups, int32_t n_beams, int32_t n_predict, int32_t eos_id, float length_penalty,
+                                 int32_t early_stopping, int32_t max_steps, int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts,
+                                 int32_t *col_token, int32_t *col_n_gen, int32_t *col_hist, float *col_run_score, int32_t *col_rank, int32_t *grp_done,
+                                 int32_t *grp_step, float *kv_out) {
+    clear_error();
+    if (!table) BG_FAIL(-1, "table is NULL");
+    if (!start_tokens || !prompt_lens) BG_FAIL(-1, "start_tokens or prompt_lens is NULL");
+    if (!out_ids || !out_lens || !out_scores || !out_counts) BG_FAIL(-1, "out_ids, out_lens, out_scores or out_counts is NULL");
+    if (!col_token || !col_n_gen || !col_hist || !col_run_score || !col_rank || !grp_done || !grp_step || !kv_out) BG_FAIL(-1, "a state output (col_*, grp_*, kv_out) is NULL");
+    if (given != 0 && given != 1) BG_FAIL(-1, "given must be 0 (logits) or 1 (log-probabilities)");
+    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
+    if (n_groups < 1 || (int64_t)n_groups * n_beams > BBATCH_COLS) BG_FAIL(-1, "n_groups x n_beams must be in [1, %d]", BBATCH_COLS);
+    if (n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be at most %d", 1 << 20);
+    if (n_vocab < 2 * n_beams) BG_FAIL(-1, "n_vocab: a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", n_vocab);
+    if (n_table_rows < 1 || n_table_rows > (1 << 16)) BG_FAIL(-1, "n_table_rows must be in [1, %d]", 1 << 16);
+    if (n_predict < 1 || n_predict > 1024) BG_FAIL(-1, "n_predict must be in [1, 1024]");
+    if (max_steps < 1) BG_FAIL(-1, "max_steps must be >= 1");
+    if (eos_id < -1 || eos_id >= n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, n_vocab);
+    if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
+    if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
+    const int G = n_groups, B = n_beams, n_cols = G * B;
+    int max_len = 0;
+    for (int g = 0; g < G; g++) {
+        if (prompt_lens[g] < 1 || prompt_lens[g] > 1024) BG_FAIL(-1, "prompt_lens[%d] must be in [1, 1024]", g);
+        if (start_tokens[g] < 0 || start_tokens[g] >= n_vocab) BG_FAIL(-1, "start_tokens[%d] = %d out of range: must be in [0, %d)", g, start_tokens[g], n_vocab);
+        max_len = std::max(max_len, prompt_lens[g]);
+    }
+    if (given && !beam_given_rows_ok(table, (size_t)n_table_rows, n_vocab, 2 * B, "table")) return -1;
+    HIP_TRY(-2, hipSetDevice(device));
+    const int P = max_len + n_predict;
+    constexpr int H = bgk::TABLE_HEADS, DK = bgk::TABLE_DK;
+    DeviceBytes d;
+    float *table_d = nullptr, *logits_d = nullptr;
+    const size_t tb_b = (size_t)n_table_rows * n_vocab * 4, lg_b = (size_t)n_cols * n_vocab * 4, kv_b = (size_t)n_cols * H * P * DK * 4, gen_b = (size_t)n_cols * P * 4;
+    BeamBufs b{};
+    auto lay = [&](uint8_t *base) {      // [table | logits | K | V | the state block of a call | column states | histories]; no base: the size alone
+        ByteLayout l;
+        table_d = l.take<float>(base, tb_b / 4); logits_d = l.take<float>(base, lg_b / 4);
+        b.bk = l.take<float>(base, kv_b / 4); b.bv = l.take<float>(base, kv_b / 4);
+        beam_state_parts(l, base, (size_t)n_cols, (size_t)G, (size_t)2 * B, (size_t)P, &b);
+        b.seq = l.take<bgk::SeqState>(base, (size_t)n_cols); b.seq_gen = l.take<int32_t>(base, gen_b / 4);
+        return l.bytes();
+    };
+    if (!d.alloc(lay(nullptr))) return -2;
+    lay(d.p);
+    b.stream = 0;
+    b.logits = logits_d; b.n_vocab = n_vocab; b.gen_stride = P;
+    b.seq_stride = (int64_t)H * P * DK; b.kv_runs = H; b.P = P; b.dk = DK;
+    std::vector<bgk::BeamCtl> hc((size_t)G);
+    std::vector<bgk::SeqState> hs((size_t)n_cols);
+    for (int g = 0; g < G; g++) fill_column_starts(hs.data(), g, B, prompt_lens[g], start_tokens[g]);
+    std::vector<float> kv_fill(kv_b / 4, -1.0f);       // a row no step has written reads -1
+    HIP_TRY(-2, hipMemcpy(table_d, table, tb_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(logits_d, 0, lg_b));
+    HIP_TRY(-2, hipMemcpy(b.bk, kv_fill.data(), kv_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(b.bv, kv_fill.data(), kv_b, hipMemcpyHostToDevice));
+    if (!upload_beam_start(b, G, B, prompt_lens, n_predict, eos_id, length_penalty, early_stopping)) return -2;      // the initial state of a call
+    HIP_TRY(-2, hipMemset(b.cand, 0xff, sizeof(bgk::BeamCand) * (size_t)n_cols * 2 * B));
+    HIP_TRY(-2, hipMemset(b.pool_ids, 0xff, gen_b));
+    HIP_TRY(-2, hipMemcpy(b.seq, hs.data(), sizeof(bgk::SeqState) * (size_t)n_cols, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(b.seq_gen, 0xff, gen_b));
+    bgk::BeamBatchHdr hh{};
+    int n_live = G;
+    for (int s = 0; s < std::min(max_steps, n_predict) && n_live > 0; s++) {
+        hipLaunchKernelGGL(bgk::beam_table_feed_kernel, dim3(n_cols), dim3(256), 0, 0, b.seq, table_d, n_table_rows, n_vocab, logits_d, b.bk, b.bv, P);
+        HIP_TRY(-2, hipGetLastError());
+        if (!enqueue_beam_group_select(b, G, B, given != 0)) return -2;
+        HIP_TRY(-2, hipMemcpy(&hh, b.hdr, sizeof(hh), hipMemcpyDeviceToHost));      // (synchronizes)
+        n_live = hh.n_live;
+    }
+    std::vector<int32_t> ids((size_t)n_cols * P), gen((size_t)n_cols * P);
+    HIP_TRY(-2, hipMemcpy(hc.data(), b.ctl, sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(hs.data(), b.seq, sizeof(bgk::SeqState) * (size_t)n_cols, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(ids.data(), b.pool_ids, ids.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(gen.data(), b.seq_gen, gen.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(kv_out, b.bk, kv_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(kv_out + kv_b / 4, b.bv, kv_b, hipMemcpyDeviceToHost));
+    for (int g = 0; g < G; g++) {
+        grp_done[g] = hc[(size_t)g].done; grp_step[g] = hc[(size_t)g].step;
+        for (int j = 0; j < B; j++) {
+            const size_t c = (size_t)g * B + j;
+            col_token[c] = hs[c].token; col_n_gen[c] = hs[c].n_gen;
+            col_run_score[c] = hc[(size_t)g].run_score[j]; col_rank[c] = hc[(size_t)g].col_rank[j];
+            std::memcpy(col_hist + c * n_predict, gen.data() + c * P, (size_t)n_predict * 4);
+        }
+    }
+    if (n_live > 0) {       // stopped by max_steps: no result yet
+        std::fill(out_ids, out_ids + (size_t)n_cols * n_predict, -1);
+        std::fill(out_lens, out_lens + n_cols, 0);
+        std::fill(out_scores, out_scores + n_cols, 0.0f);
+        std::fill(out_counts, out_counts + G, 0);
+        return 0;
+    }
+    if (!beam_read_pools(hc.data(), ids.data(), (size_t)P, G, B, n_predict, out_ids, out_lens, out_scores, out_counts)) return -2;
+    return n_predict;
+}
+
+// the sampler's tail and its generator on the host: no device, no context
+int biogpt_hip_mt19937_seed(uint32_t seed, uint32_t *state625) {
+    clear_error();
+    if (!state625) BG_FAIL(-1, "null argument");
+    bgk::mt_seed(seed, state625);
+    return 0;
+}
+int biogpt_hip_sample_candidates_host(const float *vals, const int32_t *ids, int32_t k, double top_p, double temp, uint32_t *mt_state625, int32_t *id_out) {
+    clear_error();
+    if (!vals || !ids || !mt_state625 || !id_out) BG_FAIL(-1, "null argument");
+    if (k < 1 || k > (1 << 20)) BG_FAIL(-1, "k must be in [1, %d]", 1 << 20);
+    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
+    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
+    if (mt_state625[bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index %u out of range", mt_state625[bgk::MT_N]);
+    bgk::SampleWork w;
+    std::vector<double> p((size_t)k);
+    *id_out = ids[bgk::sample_tail(vals, k, top_p, temp, mt_state625, p.data(), w, 0, 1, bgk::SampleNoSync())];
+    return 0;
+}
+
+// sample_rows_kernel over rows held in host memory (tests: ties, any row width and alignment, the selection's round form, a generator block running
+// out): row r draws from mt_states[r] (625 words, advanced in place; the words of a block regenerated on the device are those of the host's form)
+int biogpt_hip_sample_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, int32_t top_k, double top_p, double temp,
+                                  uint32_t *mt_states, int32_t *ids_out) {
+    clear_error();
+    if (!logits || !mt_states || !ids_out) BG_FAIL(-1, "null argument");
+    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
+    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > n_vocab) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
+    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
+    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
+    for (int r = 0; r < n_rows; r++)
+        if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sample_bufs_at(nullptr, (size_t)n_rows).bytes;
+    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = (size_t)n_rows * 4;
+    std::vector<uint8_t> h(sq_b, 0);
+    const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_rows);
+    *hb.ctl = sample_ctl_of(top_k, -1, n_rows, top_p, temp);
+    bgk::SampleSeq *const hq = hb.seq;
+    for (int r = 0; r < n_rows; r++) std::memcpy(hq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
+    ByteLayout l;      // [logits | ctl + states | column states | ids]
+    const size_t o_lg = l.part(lg_b), o_sq = l.part(sq_b), o_st = l.part(st_b), o_id = l.part(id_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    const SampleBufs sb = sample_bufs_at(d.p + o_sq, (size_t)n_rows);
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, logits, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(sb.ctl, h.data(), sq_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_st, 0, l.bytes() - o_st));
+    hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, sb.ctl, sb.seq,
+                       d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), 1);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(h.data(), sb.ctl, sq_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
+    for (int r = 0; r < n_rows; r++) std::memcpy(mt_states + (size_t)r * 625, hq[r].mt, 625 * 4);
+    return 0;
+}
+
+// SURVEY 8 f1 on the device: `nrows` rows of `k` f32 values (host memory) -> the file's block format of `type`, byte-identical to
+// the host quantizer (biogpt_hip_quantize_file uses the host one: it has to work without a GPU)
+int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, int64_t nrows, int64_t k, uint8_t *dst) {
+    clear_error();
+    if (!src || !dst || nrows < 1 || k < QK || k % QK) BG_FAIL(-1, "bad argument (row length must be a multiple of %d)", QK);
+    if (!is_quantized(type)) BG_FAIL(-1, "type %d is not a block-quantized format", type);
+    if (!select_device(device)) return -1;
+    const long long nblocks = (long long)nrows * (k / QK);
+    const size_t in_bytes = (size_t)nrows * (size_t)k * 4, out_bytes = (size_t)nblocks * file_block_bytes(type);
+    DeviceBytes d_src, d_dst;
+    if (!d_src.alloc(in_bytes)) return -2;
+    if (!d_dst.alloc(out_bytes)) BG_FAIL(-2, "hipMalloc of %zu bytes failed", out_bytes);
+    HIP_TRY(-2, hipMemcpy(d_src.p, src, in_bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(bgk::quantize_blocks_kernel, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, 0, d_src.at<float>(0), d_dst.p, nblocks, (int)type,
+                       (int)file_block_bytes(type));
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipMemcpy(dst, d_dst.p, out_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
