@@ -111,6 +111,60 @@ def logprob_rows(rows, targets, device=0):
     return lp, am, lg
 
 
+def lookup_draft(texts, n_gen, n_past, n_predict, max_draft=7, max_ngram=3, finished=None, device=0):
+    """lookup_draft_kernel on texts held in host memory (biogpt_hip_lookup_draft_device): texts a list of id lists (corpus + prompt + generated tokens), n_gen[s]
+    how many of text s were generated, n_past[s] the position of its last token.  Returns (drafts: list of id lists, d int32[n], cols int32[n][1 + max_draft][4]:
+    token, n_past, seq_id, t_vis of every packed column state)."""
+    n = len(texts)
+    lens = np.asarray([len(t) for t in texts], dtype=np.int32)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.int32) for t in texts] + [np.zeros(1, np.int32)]))
+    ng = np.ascontiguousarray(n_gen, dtype=np.int32).reshape(-1)
+    npast = np.ascontiguousarray(n_past, dtype=np.int32).reshape(-1)
+    if ng.size != n or npast.size != n:
+        raise BiogptError("lookup_draft: one n_gen and one n_past per text")
+    fin = None if finished is None else np.ascontiguousarray(finished, dtype=np.int32).reshape(-1)
+    dr = np.zeros((max(n, 1), 16), np.int32)
+    d = np.zeros(max(n, 1), np.int32)
+    cols = np.zeros((max(n, 1), 1 + max(int(max_draft), 0), 4), np.int32)
+    if lib().biogpt_hip_lookup_draft_device(int(device), flat.ctypes.data, lens.ctypes.data, n, ng.ctypes.data, npast.ctypes.data,
+                                            None if fin is None else fin.ctypes.data, int(n_predict), int(max_draft), int(max_ngram), dr.ctypes.data,
+                                            d.ctypes.data, cols.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return [dr[s, :int(d[s])].tolist() for s in range(n)], d[:n].copy(), cols[:n].copy()
+
+
+def lookup_accept(rows, drafts, n_gen, n_past, n_predict, max_draft, eos_id=-1, finished=None, device=0):
+    """lookup_accept_kernel on logits rows held in host memory (biogpt_hip_lookup_accept_device): rows float32 [n * (1 + max_draft)][n_vocab], drafts a list of
+    id lists (at most max_draft each).  Returns (emitted: list of id lists, state int32[n][4]: token, n_past, n_gen, finished; stats int32[n][3]: passes, drafted,
+    accepted; (live count, furthest position))."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n = len(drafts)
+    S = 1 + int(max_draft)
+    if a.ndim != 2 or a.shape[0] != n * S:
+        raise BiogptError("lookup_accept: rows must be [n * (1 + max_draft)][n_vocab]")
+    dr = np.full((max(n, 1), 16), -1, np.int32)
+    d = np.zeros(max(n, 1), np.int32)
+    for s, t in enumerate(drafts):
+        if len(t) > 15:
+            raise BiogptError("lookup_accept: a draft holds at most 15 tokens")
+        d[s] = len(t)
+        dr[s, :len(t)] = np.asarray(t, dtype=np.int32)
+    ng = np.ascontiguousarray(n_gen, dtype=np.int32).reshape(-1)
+    npast = np.ascontiguousarray(n_past, dtype=np.int32).reshape(-1)
+    if ng.size != n or npast.size != n:
+        raise BiogptError("lookup_accept: one n_gen and one n_past per sequence")
+    fin = None if finished is None else np.ascontiguousarray(finished, dtype=np.int32).reshape(-1)
+    emit = np.zeros((max(n, 1), 16), np.int32)
+    state = np.zeros((max(n, 1), 4), np.int32)
+    stats = np.zeros((max(n, 1), 3), np.int32)
+    live = np.zeros(2, np.int32)
+    if lib().biogpt_hip_lookup_accept_device(int(device), a.ctypes.data, n, a.shape[1], int(max_draft), dr.ctypes.data, d.ctypes.data, ng.ctypes.data,
+                                             npast.ctypes.data, None if fin is None else fin.ctypes.data, int(n_predict), int(eos_id), emit.ctypes.data,
+                                             state.ctypes.data, stats.ctypes.data, live.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return [[int(v) for v in emit[s] if v >= 0] for s in range(n)], state[:n].copy(), stats[:n].copy(), (int(live[0]), int(live[1]))
+
+
 def beam_rows(rows, n_beams, run_score, given=False, first_step=False, device=0):
     """beam_group_rows_kernel on rows held in host memory (biogpt_hip_beam_rows_device): rows float32 [G * n_beams][n_vocab], run_score [G * n_beams].
     Returns (score float32, col int32, id int32), each [G * n_beams][2 * n_beams]; rows the kernel left alone hold (NaN, -1, -1)."""
@@ -255,6 +309,9 @@ SYMBOLS = [
                                                 _P, _P, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_generate_contrastive", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_contrast_rank_device", C.c_int, [C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P]),
+    ("biogpt_hip_generate_lookup", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_lookup_draft_device", C.c_int, [C.c_int, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("biogpt_hip_lookup_accept_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_rules_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(GenRules), _P]),
     ("biogpt_hip_logprob_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_beam_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
@@ -641,6 +698,40 @@ class BiogptModel:
             return [np.zeros(0, np.int32) for _ in range(G)], [np.zeros(0, np.float32) for _ in range(G)]
         rows, srows = out.reshape(-1), sc.reshape(-1)      # rows are [G][n_predict as clamped]
         return ([rows[p * got:p * got + int(ol[p])].copy() for p in range(G)], [srows[p * got:p * got + int(ol[p])].copy() for p in range(G)])
+
+    def generate_lookup(self, prompts, n_predict, max_draft=7, max_ngram=3, corpus=None, eos_id=-1, n_batch=8):
+        """Prompt-lookup speculative decoding (transformers' generate(prompt_lookup_num_tokens=max_draft, max_matching_ngram_size=max_ngram)) over a batch
+        of prompts (list of id lists, or one flat id list): the ids of generate_greedy_batch, in fewer passes where the output copies from the prompt,
+        from what was generated so far or from corpus[p] (an id list per prompt of material likely to be copied; INTEGRATION.md, "Prompt-lookup decoding").
+        Returns ([ids int32[len], ...] one per prompt, [{"passes", "drafted", "accepted"}, ...], seconds); an EOS that ended a prompt is included."""
+        if len(prompts) and np.isscalar(prompts[0]):
+            prompts = [prompts]
+            if corpus is not None and (len(corpus) == 0 or np.isscalar(corpus[0])):
+                corpus = [corpus]
+        G = len(prompts)
+        lens = np.asarray([len(p) for p in prompts], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]) if G else np.zeros(0, np.int32))
+        cflat = clens = None
+        if corpus is not None:
+            if len(corpus) != G:
+                raise BiogptError("generate_lookup: one corpus per prompt (%d != %d)" % (len(corpus), G))
+            clens = np.asarray([len(c) for c in corpus], dtype=np.int32)
+            cflat = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int32) for c in corpus] + [np.zeros(1, np.int32)]))
+        w = max(int(n_predict), 1)
+        out = np.zeros((max(G, 1), w), dtype=np.int32)
+        ol = np.zeros(max(G, 1), dtype=np.int32)
+        st = np.zeros((max(G, 1), 3), dtype=np.int32)
+        secs = C.c_double(0.0)
+        got = lib().biogpt_hip_generate_lookup(self._h, flat.ctypes.data, lens.ctypes.data, G, None if cflat is None else cflat.ctypes.data,
+                                               None if clens is None else clens.ctypes.data, int(n_batch), int(n_predict), int(max_draft), int(max_ngram),
+                                               int(eos_id), out.ctypes.data, ol.ctypes.data, st.ctypes.data, C.byref(secs))
+        if got < 0:
+            raise BiogptError(_err())
+        if got == 0:
+            return [np.zeros(0, np.int32) for _ in range(G)], [dict(passes=0, drafted=0, accepted=0) for _ in range(G)], secs.value
+        rows = out.reshape(-1)      # rows are [G][n_predict as clamped]
+        return ([rows[p * got:p * got + int(ol[p])].copy() for p in range(G)],
+                [dict(passes=int(st[p, 0]), drafted=int(st[p, 1]), accepted=int(st[p, 2])) for p in range(G)], secs.value)
 
     def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
                         repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):

@@ -46,6 +46,7 @@
 #include "kernels_sample.hip.h"
 #include "kernels_rules.hip.h"
 #include "kernels_contrast.hip.h"
+#include "kernels_lookup.hip.h"
 #include "model_file.h"
 #include "quant_host.h"
 
@@ -283,7 +284,7 @@ struct biogpt_hip_ctx {
     int launch_parity = 0;
     // column generation (greedy batch, sampling, beam search; the driver stands before generate_greedy_batch_once): the captured steps of each mode,
     // and the pinned word pair + event pair through which the host reads a mode's count of unfinished sequences / searches between groups of steps
-    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam, graphs_contrast;
+    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam, graphs_contrast, graphs_lookup;
     int32_t *live_host = nullptr;
     hipEvent_t live_ev[2] = {};
     // sampled generation (biogpt_hip_generate_sample, kernels_sample.hip.h): the call's parameters + one generator state per sequence (SampleCtl, then
@@ -301,6 +302,9 @@ struct biogpt_hip_ctx {
     uint8_t *contrast_buf = nullptr;
     float *contrast_h = nullptr;
     int contrast_groups = 0;
+    // prompt-lookup decoding (biogpt_hip_generate_lookup, kernels_lookup.hip.h): the step's device state at its largest (lookup_bufs_at), allocated at the
+    // first such call -- captured steps keep their pointers
+    uint8_t *lookup_buf = nullptr;
 
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -377,7 +381,7 @@ static void drop_graphs(ColumnGraphs &gs) {
 }
 // Captured column steps hold the pointers of seq / bk / bv / logits_all and launch shapes chosen from the options: whatever replaces one of those drops them all
 static void drop_column_graphs(biogpt_hip_ctx *c) {
-    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam, &c->graphs_contrast}) drop_graphs(*gs);
+    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam, &c->graphs_contrast, &c->graphs_lookup}) drop_graphs(*gs);
 }
 
 namespace {
@@ -1060,6 +1064,7 @@ struct ForwardPass {
     // front of them are prefix columns whose K / V rows alone matter
     bool shared_prefix;
     int head_from;
+    const bgk::SeqState *col_states = nullptr;      // Packed: the column states where they are not c->cols (packed_verify)
 
     // the context's own columns
     static ForwardPass last_row(int n, int t_max) { return {n, t_max, Cols::Context, Rows::Last}; }
@@ -1077,6 +1082,13 @@ struct ForwardPass {
         return {n, t_max, Cols::Packed, Rows::None, HiddenStage{0, store, per_prompt}};
     }
     static ForwardPass packed_scored(int n, int t_max) { return {n, t_max, Cols::Packed, Rows::All}; }
+    // the same over column states a kernel of the captured step has written (prompt-lookup decoding: a sequence's current token and its drafted tokens at
+    // consecutive positions, t_vis = position + 1); `cols` keeps its address for as long as a graph holds the pass
+    static ForwardPass packed_verify(int n, int t_max, const bgk::SeqState *cols) {
+        ForwardPass p{n, t_max, Cols::Packed, Rows::All};
+        p.col_states = cols;
+        return p;
+    }
     static ForwardPass packed_hidden(int n, int t_max, HiddenStage hs) { return {n, t_max, Cols::Packed, Rows::Hidden, hs}; }
     // the first n_prefix columns are prefix columns (all of them: no lm_head at all), the others read the prefix in place
     static ForwardPass packed_continuations(int n, int t_max, int n_prefix) {
@@ -1328,7 +1340,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     // enough columns to fill 16-wide MFMA tiles: the chain runs on the int8 matrix cores from the row-tiled weight image
     k.mfma = k.pchain && N >= (pass.cols == Cols::PerSequence ? MFMA_MIN_DECODE_COLS : MFMA_MIN_PASS_COLS) && c->tile_img != nullptr;
     if (batch && !k.chain) BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
-    k.seq = pass.cols == Cols::Packed ? c->cols : (batch ? c->seq : nullptr);
+    k.seq = pass.cols == Cols::Packed ? (pass.col_states ? pass.col_states : c->cols) : (batch ? c->seq : nullptr);
     k.col_mode = pass.cols == Cols::Packed ? 1 : 0;
     k.seq_stride = (int64_t)hp.n_layer * k.P * k.D;
     k.kroot = batch ? c->bk : c->memory_k;
@@ -1429,7 +1441,7 @@ bool alloc_runtime(biogpt_hip_ctx *c) {
     HIP_TRY(false, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIP_TRY(false, hipEventCreate(&c->ev0));
     HIP_TRY(false, hipEventCreate(&c->ev1));
-    HIP_TRY(false, hipHostMalloc(&c->live_host, 2 * sizeof(int32_t)));
+    HIP_TRY(false, hipHostMalloc(&c->live_host, 4 * sizeof(int32_t)));
     for (auto &e : c->live_ev) HIP_TRY(false, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return true;
 }
@@ -1581,7 +1593,7 @@ void destroy(biogpt_hip_ctx *c) {
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2364,6 +2376,9 @@ struct ColumnCall {
     int key_a = 0, key_b = 0;
     int extra_steps = 0;                // steps beyond one per token (contrastive: 1, the prompt's last token has a step of its own)
     int gset_extra = 0;                 // 12 with rules: another form of the step, so other graphs
+    int key_stride = 1;                 // positions a column can move on in one step, at most (prompt-lookup decoding: 1 + max_draft); > 1: the word behind
+                                        // live_dev holds the furthest position of any column
+    bool plain_steps = false;           // the step is no decode step of one column per sequence: never the column-per-XCD launches
     // set by run_column_call before any callable runs: the tokens to generate as clamped, the longest prompt, all prompt tokens
     int n_predict = 0, max_len = 0;
     long total = 0;
@@ -2441,12 +2456,24 @@ static int choose_column_path(biogpt_hip_ctx *ctx, int n_seqs, int max_len) {
     return ctx->xc_batch;
 }
 
-// Captures `step` for the context buckets of steps 2 .. n_predict (t_max = max_len + 1 .. max_len + n_predict - 1: the ones run_column_steps replays) into
+// The keys a step can see at most.  Step k (0: the prompt's last token) of a call whose columns move on by at most `stride` positions per step has columns up to
+// position max_len - 1 + (k + 1) * stride - 1; with stride 1 that is the one key per step of every mode but prompt-lookup decoding.
+struct ColumnKeys {
+    int max_len, stride, P;
+    // steps enqueued between two reads of the live word.  One group stays in flight behind the word the host waits for, so up to two groups run after the end:
+    // little beside one step per token, half a call where a step is 8 tokens -- a stride > 1 polls every second step (a step of several columns per sequence
+    // is long beside a graph launch)
+    int group() const { return stride > 1 ? 2 : 8; }
+    int worst(int k) const { return (int)std::min<long>(P, (long)max_len + (long)(k + 1) * stride - 1); }
+    int first_replayed() const { return std::min(P, max_len + 1); }      // no replayed step is bounded lower
+};
+
+// Captures `step` for the context buckets of steps 2 .. n_steps (t_max = max_len + 1 .. keys.worst(n_steps - 1): the ones run_column_steps replays) into
 // graphs.exec[gset + bucket], where they are not there yet.  *use_graph: whether the steps are replayed at all.
-static bool capture_column_steps(biogpt_hip_ctx *ctx, ColumnGraphs &graphs, int gset, int max_len, int n_predict, const ColumnStep &step, bool *use_graph) {
+static bool capture_column_steps(biogpt_hip_ctx *ctx, ColumnGraphs &graphs, int gset, const ColumnKeys &keys, int n_steps, const ColumnStep &step, bool *use_graph) {
     *use_graph = ctx->opt.no_graph == 0 && (ctx->xc_batch != 0 || plain_graph_begin(ctx));      // (a captured five-launch step is not replayed beside another context's persistent launch)
-    if (*use_graph && n_predict > 1) {
-        for (int b = graph_bucket(max_len + 1); b <= graph_bucket(max_len + n_predict - 1); b++) {
+    if (*use_graph && n_steps > 1) {
+        for (int b = graph_bucket(keys.first_replayed()); b <= graph_bucket(keys.worst(n_steps - 1)); b++) {
             if (graphs.exec[gset + b]) continue;
             hipGraph_t g = nullptr;
             HIP_TRY(false, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
@@ -2480,24 +2507,32 @@ static bool ingest_column_prompts(biogpt_hip_ctx *ctx, const int32_t *prompts, c
     return true;
 }
 
-// Step 1 eagerly (the last prompt token of every column, t_max = max_len), then steps 2 .. n_predict (t_max = max_len + 1 ..) replayed or eager, enqueued in
-// groups of 8.  live_dev (or null): a device word that holds how many sequences / searches still run.  It is copied to one of two pinned words after each
+// Step 1 eagerly (the last prompt token of every column, t_max = keys.worst(0)), then steps 2 .. n_steps replayed or eager, enqueued in groups of keys.group().
+// live_dev (or null): a device word that holds how many sequences / searches still run.  It is copied to one of two pinned slots after each
 // group, and once the group BEFORE the one just enqueued reports none, nothing more is enqueued (one group stays in flight; steps after the end change nothing).
-static bool run_column_steps(biogpt_hip_ctx *ctx, const ColumnGraphs &graphs, int gset, bool use_graph, int max_len, int n_predict, const ColumnStep &step,
+// keys.stride > 1: the word behind live_dev (the furthest position of any column) travels with it, and a step k behind the last step e whose word has come back
+// is bounded by that position + (k - e) * stride instead of keys.worst(k): attention follows the context the columns really have.
+static bool run_column_steps(biogpt_hip_ctx *ctx, const ColumnGraphs &graphs, int gset, bool use_graph, const ColumnKeys &keys, int n_steps, const ColumnStep &step,
                              const int32_t *live_dev) {
-    if (!step(max_len)) return false;
-    for (int k = 1, grp = 0; k < n_predict; grp++) {
-        for (const int end = std::min(n_predict - 1, k + 7); k <= end; k++) {
-            const int t_max = max_len + k;
+    if (!step(keys.worst(0))) return false;
+    const bool with_pos = live_dev && keys.stride > 1;
+    int seen_step = -1, seen_pos = 0, grp_last[2] = {0, 0};
+    for (int k = 1, grp = 0; k < n_steps; grp++) {
+        for (const int end = std::min(n_steps - 1, k + keys.group() - 1); k <= end; k++) {
+            int t_max = keys.worst(k);
+            if (seen_step >= 0) t_max = std::min<long>(t_max, std::max<long>(keys.first_replayed(), (long)seen_pos + (long)(k - seen_step) * keys.stride));
             if (use_graph) HIP_TRY(false, hipGraphLaunch(graphs.exec[gset + graph_bucket(t_max)], ctx->stream));
             else if (!step(t_max)) return false;
         }
         if (!live_dev) continue;
-        HIP_TRY(false, hipMemcpyAsync(ctx->live_host + (grp & 1), live_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(false, hipMemcpyAsync(ctx->live_host + 2 * (grp & 1), live_dev, with_pos ? 8 : 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(false, hipEventRecord(ctx->live_ev[grp & 1], ctx->stream));
+        grp_last[grp & 1] = k - 1;
         if (grp > 0) {
-            HIP_TRY(false, hipEventSynchronize(ctx->live_ev[(grp - 1) & 1]));
-            if (ctx->live_host[(grp - 1) & 1] <= 0) break;
+            const int o = (grp - 1) & 1;
+            HIP_TRY(false, hipEventSynchronize(ctx->live_ev[o]));
+            if (ctx->live_host[2 * o] <= 0) break;
+            if (with_pos) { seen_step = grp_last[o]; seen_pos = ctx->live_host[2 * o + 1]; }
         }
     }
     return true;
@@ -2515,14 +2550,15 @@ static int run_column_call(biogpt_hip_ctx *ctx, ColumnCall &cc, int n_predict, d
     column_graphs_for(*cc.graphs, cc.key_a, cc.key_b);
     if (!upload_column_starts(ctx, cc.prompts, cc.prompt_lens, cc.n_prompts, cc.per_prompt)) return -2;
     if (cc.upload && !cc.upload()) return -2;
-    const int gset = 6 * choose_column_path(ctx, n_seqs, cc.max_len) + cc.gset_extra;
+    const int gset = (cc.plain_steps ? 0 : 6 * choose_column_path(ctx, n_seqs, cc.max_len)) + cc.gset_extra;
+    const ColumnKeys keys{cc.max_len, cc.key_stride, ctx->hp.n_positions};
     bool use_graph;
-    if (!capture_column_steps(ctx, *cc.graphs, gset, cc.max_len, n_steps, cc.step, &use_graph)) return -2;
+    if (!capture_column_steps(ctx, *cc.graphs, gset, keys, n_steps, cc.step, &use_graph)) return -2;
 
     const auto t0 = std::chrono::steady_clock::now();
     if (!ingest_column_prompts(ctx, cc.prompts, cc.prompt_lens, cc.n_prompts, cc.n_batch, cc.per_prompt, cc.hidden_store)) return -2;
     if (cc.after_ingest && !cc.after_ingest()) return -2;
-    if (!run_column_steps(ctx, *cc.graphs, gset, use_graph, cc.max_len, n_steps, cc.step, cc.live_dev)) return -2;
+    if (!run_column_steps(ctx, *cc.graphs, gset, use_graph, keys, n_steps, cc.step, cc.live_dev)) return -2;
     if (cc.before_sync && !cc.before_sync()) return -2;
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
     const auto t1 = std::chrono::steady_clock::now();
@@ -3514,6 +3550,158 @@ int biogpt_hip_generate_contrastive(biogpt_hip_ctx *ctx, const int32_t *prompts,
                                     double *seconds_out) {
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_contrastive_once(ctx, prompts, prompt_lens, n_prompts, n_batch, top_k, penalty_alpha, n_predict, eos_id, out_ids, out_lens, out_scores, seconds_out);
+    });
+}
+
+// ---- prompt-lookup speculative decoding (kernels_lookup.hip.h) ------------------------------------------------------------------------------------
+// One sequence and K / V cache slot per prompt (per_prompt = 1); a step is a packed pass of 1 + max_draft columns per sequence: the sequence's current token and
+// the tokens lookup_draft_kernel copied from its text behind the earliest match of its longest matching tail n-gram, at consecutive positions with
+// t_vis = position + 1 -- exactly what single-token steps would have shown each of them.  lookup_accept_kernel keeps the arg-max of every row up to the first
+// draft that is not its row's arg-max, so the ids are those of biogpt_hip_generate_greedy_batch whatever was drafted.  A sequence moves on by 1 .. 1 + max_draft
+// positions per step, a number only the device knows: the driver's key stride is 1 + max_draft and the steps' attention bound follows the furthest position the
+// device reports (run_column_steps).  The steps stop through LookupCtl::n_live; the worst case is n_predict steps.
+constexpr int LOOKUP_COLS = 512;                // columns of a step, at most (and so sequences: max_draft = 0)
+constexpr size_t LOOKUP_TEXT_WORDS = (size_t)1 << 21;      // the texts of a call: every sequence has corpus_len + n_positions words
+struct LookupBufs {
+    bgk::LookupCtl *ctl;
+    bgk::LookupSeq *seq;        // [LOOKUP_COLS]
+    bgk::SeqState *cols;        // [LOOKUP_COLS]: the packed column states of the step
+    int32_t *text;              // [LOOKUP_TEXT_WORDS]
+    size_t bytes;
+};
+static LookupBufs lookup_bufs_at(uint8_t *base, size_t n_seqs = LOOKUP_COLS, size_t n_cols = LOOKUP_COLS, size_t text_words = LOOKUP_TEXT_WORDS) {
+    ByteLayout l;
+    LookupBufs b{};
+    b.ctl = l.take<bgk::LookupCtl>(base, 1);
+    b.seq = l.take<bgk::LookupSeq>(base, n_seqs);
+    b.cols = l.take<bgk::SeqState>(base, n_cols);
+    b.text = l.take<int32_t>(base, text_words);
+    b.bytes = l.bytes();
+    return b;
+}
+
+// what can be judged of a lookup call without the model
+static bool check_lookup_shape(int64_t n_seqs, int max_draft, int max_ngram) {
+    if (max_draft < 0 || max_draft > bgk::LK_MAX_DRAFT) BG_FAIL(false, "max_draft must be in [0, %d]", bgk::LK_MAX_DRAFT);
+    if (max_ngram < 1 || max_ngram > bgk::LK_MAX_NGRAM) BG_FAIL(false, "max_ngram must be in [1, %d]", bgk::LK_MAX_NGRAM);
+    if (n_seqs * (1 + max_draft) > LOOKUP_COLS) BG_FAIL(false, "n_prompts x (1 + max_draft) must be at most %d", LOOKUP_COLS);
+    return true;
+}
+
+static int generate_lookup_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, const int32_t *corpus,
+                                const int32_t *corpus_lens, int32_t n_batch, int32_t n_predict, int32_t max_draft, int32_t max_ngram, int32_t eos_id,
+                                int32_t *out_ids, int32_t *out_lens, int32_t *out_stats, double *seconds_out) {
+    clear_error();
+    // (what can be judged without the model comes first: these fail the same way with no context and no device)
+    if (!prompts) BG_FAIL(-1, "null argument: prompts");
+    if (!prompt_lens) BG_FAIL(-1, "null argument: prompt_lens");
+    if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
+    if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
+    if ((corpus == nullptr) != (corpus_lens == nullptr)) BG_FAIL(-1, "corpus and corpus_lens must both be given, or both be NULL");
+    if (n_prompts < 1) BG_FAIL(-1, "n_prompts must be >= 1");
+    if (!check_lookup_shape(n_prompts, max_draft, max_ngram)) return -1;
+    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
+    if (eos_id < -1) BG_FAIL(-1, "eos_id %d out of range: must be a token id, or -1 for none", eos_id);
+    size_t corpus_total = 0;
+    for (int p = 0; corpus_lens && p < n_prompts; p++) {
+        if (corpus_lens[p] < 0) BG_FAIL(-1, "corpus_lens[%d] = %d is negative", p, corpus_lens[p]);
+        corpus_total += (size_t)corpus_lens[p];
+    }
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    const int G = n_prompts, S = 1 + max_draft, n_cols = G * S;
+    if (n_cols > hp_cols(ctx)) BG_FAIL(-1, "n_prompts x (1 + max_draft) (%d) exceeds the %d activation columns of this model", n_cols, hp_cols(ctx));
+    const auto &hp = ctx->hp;
+    const int P = hp.n_positions, V = hp.n_vocab;
+    if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
+    for (size_t i = 0; i < corpus_total; i++)
+        if (corpus[i] < 0 || corpus[i] >= V) BG_FAIL(-1, "corpus id %d out of range [0, %d)", corpus[i], V);
+    if (corpus_total + (size_t)G * P > LOOKUP_TEXT_WORDS)
+        BG_FAIL(-1, "corpus tokens (%zu) + n_prompts x n_positions (%d x %d) exceed the %zu words of the text buffer", corpus_total, G, P, LOOKUP_TEXT_WORDS);
+    if (!check_fast_chain(ctx, "prompt-lookup decoding")) return -1;
+
+    if (max_draft == 0) {      // nothing to draft: the batched greedy call itself, its ids cut behind the first EOS
+        std::vector<int32_t> ids((size_t)G * std::max(n_predict, 1));
+        const int n = generate_greedy_batch_once(ctx, prompts, prompt_lens, G, n_batch, n_predict, ids.data(), seconds_out);
+        if (n <= 0) return n;
+        for (int p = 0; p < G; p++) {
+            const int32_t *row = ids.data() + (size_t)p * n;
+            int len = n;
+            for (int i = 0; i < n && eos_id >= 0; i++) if (row[i] == eos_id) { len = i + 1; break; }
+            std::fill(out_ids + (size_t)p * n, out_ids + (size_t)(p + 1) * n, -1);
+            std::memcpy(out_ids + (size_t)p * n, row, (size_t)len * 4);
+            out_lens[p] = len;
+            if (out_stats) { out_stats[3 * p] = len; out_stats[3 * p + 1] = 0; out_stats[3 * p + 2] = 0; }
+        }
+        return n;
+    }
+
+    LookupBufs lb{};
+    ColumnCall cc(ctx);
+    cc.prompts = prompts; cc.prompt_lens = prompt_lens;
+    cc.n_prompts = G; cc.n_batch = n_batch;
+    cc.graphs = &ctx->graphs_lookup; cc.key_a = G; cc.key_b = max_draft;
+    cc.key_stride = S; cc.plain_steps = true;
+    cc.prepare = [&]() -> bool {
+        if (!ctx->lookup_buf) HIP_TRY(false, hipMalloc(&ctx->lookup_buf, lookup_bufs_at(nullptr).bytes));
+        lb = lookup_bufs_at(ctx->lookup_buf);
+        cc.live_dev = &lb.ctl->n_live;
+        if (n_cols >= MFMA_MIN_PASS_COLS && !ensure_tile_images(ctx)) return false;
+        return ensure_logits_rows(ctx, (size_t)n_cols);      // (a new buffer drops this mode's captured steps with the others')
+    };
+    cc.upload = [&]() -> bool {      // the call's parameters, every sequence's counters and its text: corpus ++ prompt, the generated tokens follow on the device
+        HeadImage im(lb.ctl, lb.seq + G);
+        bgk::LookupCtl *hc = im.at(lb.ctl);
+        hc->max_draft = max_draft; hc->max_ngram = max_ngram; hc->eos_id = eos_id; hc->n_predict = cc.n_predict;
+        hc->n_live = G; hc->max_pos = cc.max_len - 1;
+        bgk::LookupSeq *hq = im.at(lb.seq);
+        std::vector<int32_t> text(corpus_total + (size_t)G * P, 0);
+        size_t at = 0, co = 0, po = 0;
+        for (int p = 0; p < G; p++) {
+            const int cl = corpus_lens ? corpus_lens[p] : 0;
+            hq[p].text_off = (int32_t)at; hq[p].base_len = cl + prompt_lens[p];
+            if (cl) std::memcpy(text.data() + at, corpus + co, (size_t)cl * 4);
+            std::memcpy(text.data() + at + cl, prompts + po, (size_t)prompt_lens[p] * 4);
+            at += (size_t)cl + P; co += (size_t)cl; po += (size_t)prompt_lens[p];
+        }
+        HIP_TRY(false, hipMemcpy(lb.text, text.data(), text.size() * 4, hipMemcpyHostToDevice));
+        return im.upload();
+    };
+    cc.step = [&](int t_max) -> bool {
+        hipLaunchKernelGGL(bgk::lookup_draft_kernel, dim3(G), dim3(bgk::LK_DRAFT_THREADS), 0, ctx->stream, lb.ctl, lb.seq, lb.text, ctx->seq, lb.cols);
+        HIP_TRY(false, hipGetLastError());
+        if (!enqueue_forward(ctx, ForwardPass::packed_verify(n_cols, t_max, lb.cols))) return false;
+        hipLaunchKernelGGL(bgk::lookup_accept_kernel, dim3(G), dim3(bgk::LK_ACCEPT_THREADS), 0, ctx->stream, lb.ctl, lb.seq, lb.text, ctx->logits_all, V, V, ctx->seq,
+                           ctx->seq_gen, P);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    n_predict = run_column_call(ctx, cc, n_predict, seconds_out);
+    if (n_predict <= 0) return n_predict;
+    std::vector<int32_t> gen((size_t)G * P);
+    std::vector<bgk::SeqState> hs((size_t)G);
+    std::vector<bgk::LookupSeq> hq((size_t)G);
+    HIP_TRY(-2, hipMemcpy(gen.data(), ctx->seq_gen, gen.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(hs.data(), ctx->seq, sizeof(bgk::SeqState) * G, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(hq.data(), lb.seq, sizeof(bgk::LookupSeq) * G, hipMemcpyDeviceToHost));
+    for (int p = 0; p < G; p++) {
+        if (!hq[(size_t)p].finished) BG_FAIL(-2, "internal: prompt-lookup decoding left prompt %d unfinished after %d steps (%d of %d tokens)", p, n_predict, hs[(size_t)p].n_gen, n_predict);
+        const int len = std::max(0, std::min(hs[(size_t)p].n_gen, n_predict));
+        int32_t *o = out_ids + (size_t)p * n_predict;
+        std::fill(o, o + n_predict, -1);
+        std::memcpy(o, gen.data() + (size_t)p * P, (size_t)len * 4);
+        out_lens[p] = len;
+        if (out_stats) { out_stats[3 * p] = hq[(size_t)p].passes; out_stats[3 * p + 1] = hq[(size_t)p].drafted; out_stats[3 * p + 2] = hq[(size_t)p].accepted; }
+    }
+    return n_predict;
+}
+
+int biogpt_hip_generate_lookup(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, const int32_t *corpus,
+                               const int32_t *corpus_lens, int32_t n_batch, int32_t n_predict, int32_t max_draft, int32_t max_ngram, int32_t eos_id,
+                               int32_t *out_ids, int32_t *out_lens, int32_t *out_stats, double *seconds_out) {
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_lookup_once(ctx, prompts, prompt_lens, n_prompts, corpus, corpus_lens, n_batch, n_predict, max_draft, max_ngram, eos_id, out_ids, out_lens,
+                                    out_stats, seconds_out);
     });
 }
 

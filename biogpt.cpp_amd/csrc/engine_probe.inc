@@ -363,3 +363,133 @@ int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, 
     return 0;
 }
 
+
+// lookup_draft_kernel over texts held in host memory (tests of the kernel itself): sequence s has the text texts[..] of text_lens[s] tokens (corpus ++ prompt ++
+// its n_gen[s] generated tokens, the last one its current token at position n_past[s]).  draft_out [n_seqs][16] (-1 behind the draft), d_out [n_seqs],
+// cols_out [n_seqs][1 + max_draft][4]: token, n_past, seq_id, t_vis of every packed column state, the padding columns included.
+int biogpt_hip_lookup_draft_device(int device, const int32_t *texts, const int32_t *text_lens, int32_t n_seqs, const int32_t *n_gen, const int32_t *n_past,
+                                   const int32_t *finished, int32_t n_predict, int32_t max_draft, int32_t max_ngram, int32_t *draft_out, int32_t *d_out,
+                                   int32_t *cols_out) {
+    clear_error();
+    if (!texts || !text_lens) BG_FAIL(-1, "texts or text_lens is NULL");
+    if (!n_gen || !n_past) BG_FAIL(-1, "n_gen or n_past is NULL");
+    if (!draft_out || !d_out || !cols_out) BG_FAIL(-1, "draft_out, d_out or cols_out is NULL");
+    if (n_seqs < 1) BG_FAIL(-1, "n_seqs must be >= 1");
+    if (!check_lookup_shape(n_seqs, max_draft, max_ngram)) return -1;
+    if (n_predict < 1 || n_predict > (1 << 16)) BG_FAIL(-1, "n_predict must be in [1, %d]", 1 << 16);
+    size_t total = 0;
+    for (int s = 0; s < n_seqs; s++) {
+        if (text_lens[s] < 1) BG_FAIL(-1, "text_lens[%d] must be >= 1", s);
+        if (n_gen[s] < 0 || n_gen[s] >= text_lens[s]) BG_FAIL(-1, "n_gen[%d] = %d must be in [0, text_lens[%d])", s, n_gen[s], s);
+        if (n_past[s] < 0) BG_FAIL(-1, "n_past[%d] is negative", s);
+        total += (size_t)text_lens[s];
+    }
+    if (total > LOOKUP_TEXT_WORDS) BG_FAIL(-1, "the texts (%zu tokens) exceed the %zu words of the text buffer", total, LOOKUP_TEXT_WORDS);
+    HIP_TRY(-2, hipSetDevice(device));
+    const int S = 1 + max_draft;
+    const size_t sz = lookup_bufs_at(nullptr, (size_t)n_seqs, (size_t)n_seqs * S, total).bytes;
+    std::vector<uint8_t> h(sz, 0);
+    const LookupBufs hb = lookup_bufs_at(h.data(), (size_t)n_seqs, (size_t)n_seqs * S, total);
+    hb.ctl->max_draft = max_draft; hb.ctl->max_ngram = max_ngram; hb.ctl->eos_id = -1; hb.ctl->n_predict = n_predict; hb.ctl->n_live = n_seqs;
+    std::memcpy(hb.text, texts, total * 4);
+    std::vector<bgk::SeqState> hs((size_t)n_seqs);
+    size_t at = 0;
+    for (int s = 0; s < n_seqs; s++) {
+        hb.seq[s].text_off = (int32_t)at; hb.seq[s].base_len = text_lens[s] - n_gen[s]; hb.seq[s].finished = finished && finished[s] ? 1 : 0;
+        at += (size_t)text_lens[s];
+        hs[(size_t)s] = bgk::SeqState{};
+        hs[(size_t)s].n_past = n_past[s]; hs[(size_t)s].token = texts[at - 1]; hs[(size_t)s].n_gen = n_gen[s]; hs[(size_t)s].seq_id = s;
+    }
+    ByteLayout l;      // [the step's state, with the column states as 0xff | sequence states]
+    const size_t o_lb = l.part(sz), o_st = l.part(sizeof(bgk::SeqState) * (size_t)n_seqs);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    const LookupBufs lb = lookup_bufs_at(d.p + o_lb, (size_t)n_seqs, (size_t)n_seqs * S, total);
+    std::memset(hb.cols, 0xff, sizeof(bgk::SeqState) * (size_t)n_seqs * S);
+    HIP_TRY(-2, hipMemcpy(d.p + o_lb, h.data(), sz, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_st, hs.data(), sizeof(bgk::SeqState) * (size_t)n_seqs, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(bgk::lookup_draft_kernel, dim3(n_seqs), dim3(bgk::LK_DRAFT_THREADS), 0, 0, lb.ctl, lb.seq, lb.text, d.at<const bgk::SeqState>(o_st), lb.cols);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_lb, sz, hipMemcpyDeviceToHost));
+    for (int s = 0; s < n_seqs; s++) {
+        std::memcpy(draft_out + (size_t)s * (bgk::LK_MAX_DRAFT + 1), hb.seq[s].draft, sizeof(hb.seq[s].draft));
+        d_out[s] = hb.seq[s].d;
+        for (int j = 0; j < S; j++) {
+            const bgk::SeqState &c = hb.cols[(size_t)s * S + j];
+            int32_t *o = cols_out + ((size_t)s * S + j) * 4;
+            o[0] = c.token; o[1] = c.n_past; o[2] = c.seq_id; o[3] = c.t_vis;
+        }
+    }
+    return 0;
+}
+
+// lookup_accept_kernel over logits rows held in host memory: rows [n_seqs * (1 + max_draft)][n_vocab], sequence s at n_gen[s] tokens and position n_past[s] with
+// the draft drafts[s][0 .. d[s]) (stride 16).  emit_out [n_seqs][16] the ids appended (-1 behind them), state_out [n_seqs][4] the column's token (-1: none appended),
+// n_past, n_gen, finished; stats_out [n_seqs][3] passes, drafted, accepted (from zero); live_out [2] the live word (from the unfinished sequences) and the
+// furthest position.
+int biogpt_hip_lookup_accept_device(int device, const float *rows, int32_t n_seqs, int32_t n_vocab, int32_t max_draft, const int32_t *drafts, const int32_t *d_in,
+                                    const int32_t *n_gen, const int32_t *n_past, const int32_t *finished, int32_t n_predict, int32_t eos_id, int32_t *emit_out,
+                                    int32_t *state_out, int32_t *stats_out, int32_t *live_out) {
+    clear_error();
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!drafts || !d_in) BG_FAIL(-1, "drafts or d is NULL");
+    if (!n_gen || !n_past) BG_FAIL(-1, "n_gen or n_past is NULL");
+    if (!emit_out || !state_out || !stats_out || !live_out) BG_FAIL(-1, "emit_out, state_out, stats_out or live_out is NULL");
+    if (n_seqs < 1) BG_FAIL(-1, "n_seqs must be >= 1");
+    if (!check_lookup_shape(n_seqs, max_draft, 1)) return -1;
+    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
+    if (n_predict < 1 || n_predict > (1 << 16)) BG_FAIL(-1, "n_predict must be in [1, %d]", 1 << 16);
+    if (eos_id < -1 || eos_id >= n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, n_vocab);
+    int live = 0, far = 0;
+    for (int s = 0; s < n_seqs; s++) {
+        if (d_in[s] < 0 || d_in[s] > max_draft) BG_FAIL(-1, "d[%d] = %d must be in [0, max_draft]", s, d_in[s]);
+        if (n_gen[s] < 0 || n_gen[s] > n_predict) BG_FAIL(-1, "n_gen[%d] = %d must be in [0, n_predict]", s, n_gen[s]);
+        if (n_past[s] < 0) BG_FAIL(-1, "n_past[%d] is negative", s);
+        live += finished && finished[s] ? 0 : 1;
+        far = std::max(far, n_past[s]);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    const int S = 1 + max_draft;
+    const size_t words = (size_t)n_seqs * n_predict;      // a sequence's text here is its generated tokens alone
+    const size_t sz = lookup_bufs_at(nullptr, (size_t)n_seqs, 0, words).bytes;
+    std::vector<uint8_t> h(sz, 0);
+    const LookupBufs hb = lookup_bufs_at(h.data(), (size_t)n_seqs, 0, words);
+    hb.ctl->max_draft = max_draft; hb.ctl->max_ngram = 1; hb.ctl->eos_id = eos_id; hb.ctl->n_predict = n_predict; hb.ctl->n_live = live; hb.ctl->max_pos = far;
+    std::vector<bgk::SeqState> hs((size_t)n_seqs);
+    for (int s = 0; s < n_seqs; s++) {
+        bgk::LookupSeq &q = hb.seq[s];
+        q.text_off = (int32_t)((size_t)s * n_predict); q.base_len = 0; q.finished = finished && finished[s] ? 1 : 0; q.d = d_in[s];
+        std::memcpy(q.draft, drafts + (size_t)s * (bgk::LK_MAX_DRAFT + 1), sizeof(q.draft));
+        hs[(size_t)s] = bgk::SeqState{};
+        hs[(size_t)s].n_past = n_past[s]; hs[(size_t)s].token = -1; hs[(size_t)s].n_gen = n_gen[s]; hs[(size_t)s].seq_id = s;
+    }
+    const size_t lg_b = (size_t)n_seqs * S * n_vocab * 4, st_b = sizeof(bgk::SeqState) * (size_t)n_seqs, gen_b = words * 4;
+    ByteLayout l;      // [rows | the step's state | sequence states | generated ids, 0xff]
+    const size_t o_lg = l.part(lg_b), o_lb = l.part(sz), o_st = l.part(st_b), o_gen = l.part(gen_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    const LookupBufs lb = lookup_bufs_at(d.p + o_lb, (size_t)n_seqs, 0, words);
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_lb, h.data(), sz, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_st, hs.data(), st_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_gen, 0xff, gen_b));
+    hipLaunchKernelGGL(bgk::lookup_accept_kernel, dim3(n_seqs), dim3(bgk::LK_ACCEPT_THREADS), 0, 0, lb.ctl, lb.seq, lb.text, d.at<const float>(o_lg), n_vocab, n_vocab,
+                       d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_gen), n_predict);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    std::vector<int32_t> gen(words);
+    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_lb, sz, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(hs.data(), d.p + o_st, st_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(gen.data(), d.p + o_gen, gen_b, hipMemcpyDeviceToHost));
+    for (int s = 0; s < n_seqs; s++) {
+        int32_t *e = emit_out + (size_t)s * (bgk::LK_MAX_DRAFT + 1);
+        std::fill(e, e + bgk::LK_MAX_DRAFT + 1, -1);
+        for (int i = n_gen[s]; i < hs[(size_t)s].n_gen && i - n_gen[s] <= bgk::LK_MAX_DRAFT && i < n_predict; i++) e[i - n_gen[s]] = gen[(size_t)s * n_predict + i];
+        int32_t *o = state_out + (size_t)s * 4;
+        o[0] = hs[(size_t)s].token; o[1] = hs[(size_t)s].n_past; o[2] = hs[(size_t)s].n_gen; o[3] = hb.seq[s].finished;
+        stats_out[3 * s] = hb.seq[s].passes; stats_out[3 * s + 1] = hb.seq[s].drafted; stats_out[3 * s + 2] = hb.seq[s].accepted;
+    }
+    live_out[0] = hb.ctl->n_live; live_out[1] = hb.ctl->max_pos;
+    return 0;
+}

@@ -388,6 +388,43 @@ int biogpt_hip_generate_contrastive(biogpt_hip_ctx *ctx, const int32_t *prompts 
 int biogpt_hip_contrast_rank_device(int device, const float *cand /* [k][d] */, const float *ctx_rows /* [T][d] */, int32_t k, int32_t T, int32_t d,
                                     const float *probs /* [k] */, float alpha, float *pen_out, float *score_out, int32_t *winner_out);
 
+/* Prompt-lookup speculative decoding (transformers' generate(prompt_lookup_num_tokens = max_draft, max_matching_ngram_size = max_ngram); llama.cpp's
+ * lookup): greedy decoding of n_prompts prompts whose ids are those of biogpt_hip_generate_greedy_batch, bit for bit, in fewer forward passes where the
+ * output copies from text the sequence already holds.  Sequence p's text T is corpus_p ++ prompt_p ++ its generated tokens, of length L; corpus_p
+ * (corpus_lens[p] ids of the concatenated `corpus`; both NULL: none) is material likely to be copied and is never evaluated.  Before every pass, for
+ * n = max_ngram down to 1: the i in [0, L - n - 1] with T[i .. i + n) == T[L - n .. L); the largest n with a match wins, among its matches the smallest
+ * i.  The draft is T[i + n .. i + n + d), d = min(max_draft, L - (i + n), n_predict - n_gen - 1); no match: d = 0.  The pass evaluates the current
+ * token and the d drafted tokens at consecutive positions (each sees the keys up to its own position), a_j is the arg-max of row j (lowest id on
+ * ties); the longest m with draft[j] == a_j for all j < m is accepted and a_0 .. a_m are appended, cut at n_predict and behind the first eos_id.
+ * out_ids is [n_prompts][returned n_predict] (-1 past a prompt's length), out_lens [n_prompts], out_stats (may be NULL) [n_prompts][3]: passes,
+ * drafted tokens, drafted tokens that reached the output (so a prompt's length is passes + accepted).  A prompt's ids and stats do not depend on what
+ * else is in the call.  max_draft in [0, 15] (0: biogpt_hip_generate_greedy_batch itself), max_ngram in [1, 8], n_prompts * (1 + max_draft) in
+ * [1, 512] and at most n_positions, eos_id in [-1, n_vocab), corpus ids in [0, n_vocab), sum(corpus_lens) + n_prompts * n_positions <= 2^21.  The
+ * context's own K / V cache, position and logits row are left alone.  Needs the BioGPT-base fast chain (block-quantized weights); anything else
+ * fails with -1.  Returns n_predict as clamped to n_positions - max(prompt_lens), 0 if that is <= 0, < 0 on error (argument errors, -1, the
+ * message names the field, come before any HIP call). */
+int biogpt_hip_generate_lookup(biogpt_hip_ctx *ctx, const int32_t *prompts /* concatenated */, const int32_t *prompt_lens, int32_t n_prompts,
+                               const int32_t *corpus /* concatenated, may be NULL */, const int32_t *corpus_lens /* may be NULL */, int32_t n_batch,
+                               int32_t n_predict, int32_t max_draft, int32_t max_ngram, int32_t eos_id /* -1: none */,
+                               int32_t *out_ids /* [n_prompts][returned n_predict], -1 filled */, int32_t *out_lens /* [n_prompts] */,
+                               int32_t *out_stats /* [n_prompts][3], may be NULL */, double *seconds_out);
+
+/* The draft kernel of prompt-lookup decoding over texts held in host memory, no model: sequence s has text_lens[s] tokens of the concatenated `texts`
+ * (the last n_gen[s] of them generated, the last one its current token at position n_past[s]); finished (may be NULL): sequences that draft nothing.
+ * draft_out [n_seqs][16] (-1 behind the draft), d_out [n_seqs], cols_out [n_seqs][1 + max_draft][4]: token, n_past, seq_id, t_vis of every packed
+ * column state (the columns beyond 1 + d repeat column 0).  For tests of the kernel itself. */
+int biogpt_hip_lookup_draft_device(int device, const int32_t *texts, const int32_t *text_lens, int32_t n_seqs, const int32_t *n_gen, const int32_t *n_past,
+                                   const int32_t *finished, int32_t n_predict, int32_t max_draft, int32_t max_ngram, int32_t *draft_out, int32_t *d_out,
+                                   int32_t *cols_out);
+
+/* The accept kernel over logits rows held in host memory: rows [n_seqs * (1 + max_draft)][n_vocab], sequence s with n_gen[s] tokens at position
+ * n_past[s] and the draft drafts[s][0 .. d[s]) (stride 16).  emit_out [n_seqs][16] the ids appended (-1 behind them), state_out [n_seqs][4]: the
+ * column's token (-1: nothing appended), n_past, n_gen, finished; stats_out [n_seqs][3]: passes, drafted, accepted; live_out [2]: the count of
+ * unfinished sequences and the furthest position.  For tests of the kernel itself. */
+int biogpt_hip_lookup_accept_device(int device, const float *rows, int32_t n_seqs, int32_t n_vocab, int32_t max_draft, const int32_t *drafts, const int32_t *d,
+                                    const int32_t *n_gen, const int32_t *n_past, const int32_t *finished, int32_t n_predict, int32_t eos_id, int32_t *emit_out,
+                                    int32_t *state_out, int32_t *stats_out, int32_t *live_out);
+
 /* ---- sequence scoring (no counterpart in the reference) ---------------------------------------
  * biogpt_hip_score: teacher-forced, causal log-probabilities of a sequence.  Row i sees the keys [0, n_past + i] -- what
  * biogpt_hip_eval_prompt(..., n_batch = 1) and a loop of single-token biogpt_hip_eval calls compute; NOT the unmasked chunk of
