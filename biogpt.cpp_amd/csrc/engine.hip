@@ -2582,7 +2582,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     cc.graphs = &ctx->graphs_greedy; cc.key_a = n_seqs;
     cc.step = [&](int t_max) -> bool {      // every step's arg-max is the next token
         if (!enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max))) return false;
-        hipLaunchKernelGGL(bgk::argmax_rows_kernel, dim3(n_seqs), dim3(1024), 0, ctx->stream, ctx->logits_all, V, V, ctx->seq, 0, ctx->seq_gen, P, 1);
+        hipLaunchKernelGGL(bgk::argmax_rows_kernel, dim3(n_seqs), dim3(bgk::ARGMAX_ROWS_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->seq, 0, ctx->seq_gen, P, 1);
         HIP_TRY(false, hipGetLastError());
         return true;
     };

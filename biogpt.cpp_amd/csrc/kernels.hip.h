@@ -894,37 +894,4 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float *pmax_val, cons
     }
 }
 
-
-// Batched decode sampler: one workgroup per sequence row of logits[rows][ld]; arg-max (lowest id wins ties),
-// appended to the sequence's id list, becomes its next input token; advance = 1 moves its position on.
-__global__ __launch_bounds__(1024) void argmax_rows_kernel(const float *logits, int ld, int n_vocab, SeqState *seq, int seq0,
-                                                           int32_t *gen_ids, int gen_stride, int advance) {
-    __shared__ float sv[16];
-    __shared__ int si[16];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
-    const float *lg = logits + (size_t)row * ld;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int k = tid; k < n_vocab; k += blockDim.x) {
-        const float v = lg[k];
-        if (v > bv) { bv = v; bi = k; }   // ascending k: the first maximum is kept
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(bv, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { sv[wv] = bv; si[wv] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < nw; w++)
-            if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
-        SeqState *s = seq + seq0 + row;
-        gen_ids[(size_t)(seq0 + row) * gen_stride + s->n_gen] = bi;
-        s->n_gen += 1;
-        s->token = bi;
-        s->n_past += advance;
-    }
-}
-
 }  // namespace bgk

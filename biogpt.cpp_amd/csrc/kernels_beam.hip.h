@@ -4,7 +4,8 @@
 // kernels touch is its own slice of every array, so the bodies below are written for one search and take the slice.  After the forward pass:
 //
 //   beam_group_rows_kernel    one workgroup per column (row of logits_all): the passes of logprob_rows_kernel (row maximum m,
-//                             S = sum exp(l - m)) and the row's top K = 2B (logit, id), equal logits: lower id first.  Writes K candidates
+//                             S = sum exp(l - m)) and the row's top K = 2B (logit, id), equal logits: lower id first (the order, the walk and the
+//                             bound: kernels_rows.hip.h, DESIGN.md "Row kernels").  Writes K candidates
 //                             {s_b + lp, column within the group, id} with lp = (l - m) - log(S) (double arithmetic, rounded once), s_b + lp
 //                             in f32.  A finished group's rows and, at a group's first step, every row but its first return at once (the
 //                             other beams have no score yet).  GIVEN: the row holds processed log-probabilities (generation rules).
@@ -79,15 +80,13 @@ struct BeamFork {
     int32_t pad[3];
 };
 
-__device__ __forceinline__ bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
 // insert (v, i) into the descending list (tv, ti): compile-time indices only, the list stays in registers
 template <int KM>
 __device__ __forceinline__ void beam_insert(float v, int i, float (&tv)[KM], int (&ti)[KM]) {
-    if (!beam_better(v, i, tv[KM - 1], ti[KM - 1])) return;
+    if (!row_before(v, i, tv[KM - 1], ti[KM - 1])) return;
 #pragma unroll
     for (int j = 0; j < KM; j++) {
-        const bool b = beam_better(v, i, tv[j], ti[j]);
+        const bool b = row_before(v, i, tv[j], ti[j]);
         const float of = tv[j];
         const int oi = ti[j];
         tv[j] = b ? v : of; ti[j] = b ? i : oi;
@@ -105,10 +104,6 @@ __device__ __forceinline__ void beam_rows_body(const float *row, int n_vocab, co
     __shared__ float w_v[LP_THREADS / 64][KM];
     __shared__ int w_i[LP_THREADS / 64][KM];
     __shared__ double s_ls;
-    __shared__ float t_v[LP_THREADS];
-    __shared__ int t_i[LP_THREADS];
-    __shared__ float s_thr_v;
-    __shared__ int s_thr_i;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     float m = 0.0f;
     if constexpr (!GIVEN) {
@@ -118,46 +113,17 @@ __device__ __forceinline__ void beam_rows_body(const float *row, int n_vocab, co
         if (tid == 0) s_ls = log(S);
     }
 
-    // this thread's top KM over its elements (same split as the passes: scalar head, float4 body, scalar tail)
+    // this thread's top KM over its elements: the bound first (row_kth_bound, kernels_rows.hip.h), then the insertions of the few elements at or above it
     float tv[KM];
     int ti[KM];
 #pragma unroll
-    for (int j = 0; j < KM; j++) { tv[j] = -INFINITY; ti[j] = 0x7fffffff; }
-    const int head = min(n_vocab, (int)(((16u - ((uint32_t)(uintptr_t)row & 15u)) & 15u) >> 2));
-    const int nvec = (n_vocab - head) >> 2;
-    const int tail0 = head + 4 * nvec;
-    const float4 *body = reinterpret_cast<const float4 *>(row + head);
-    // a threshold first: the K-th best of the threads' own maxima.  K threads hold an element at least that good, so nothing worse
-    // can be in the row's top K; the insertions below see only the few elements at or above it (else every wave would run the
-    // insertion network for nearly every element: with ~166 elements per lane, some lane of 64 almost always has a new entry)
-    float mv = -INFINITY;
-    int mi = 0x7fffffff;
-    if (tid < head) lp_better(row[tid], tid, mv, mi);
-    for (int i = tid; i < nvec; i += LP_THREADS) {
-        const float4 a = body[i];
-        const int ia = head + 4 * i;
-        lp_better(a.x, ia, mv, mi); lp_better(a.y, ia + 1, mv, mi); lp_better(a.z, ia + 2, mv, mi); lp_better(a.w, ia + 3, mv, mi);
-    }
-    if (tail0 + tid < n_vocab) lp_better(row[tail0 + tid], tail0 + tid, mv, mi);
-    t_v[tid] = mv; t_i[tid] = mi;
-    if (tid == 0) { s_thr_v = -INFINITY; s_thr_i = 0x7fffffff; }   // (a tiny vocabulary: fewer than K threads hold elements, all pass)
-    __syncthreads();
-    {
-        int rank = 0;
-        for (int j = 0; j < LP_THREADS; j++) rank += beam_better(t_v[j], t_i[j], mv, mi) ? 1 : 0;
-        if (rank == K - 1) { s_thr_v = mv; s_thr_i = mi; }     // (the pairs are distinct: exactly one thread has rank K - 1)
-    }
-    __syncthreads();
-    const float thr_v = s_thr_v;
-    const int thr_i = s_thr_i;
-    auto consider = [&](float v, int i) { if (!beam_better(thr_v, thr_i, v, i)) beam_insert<KM>(v, i, tv, ti); };
-    if (tid < head) consider(row[tid], tid);
-    for (int i = tid; i < nvec; i += LP_THREADS) {
-        const float4 a = body[i];
-        const int ia = head + 4 * i;
-        consider(a.x, ia); consider(a.y, ia + 1); consider(a.z, ia + 2); consider(a.w, ia + 3);
-    }
-    if (tail0 + tid < n_vocab) consider(row[tail0 + tid], tail0 + tid);
+    for (int j = 0; j < KM; j++) { tv[j] = ROW_NONE_V; ti[j] = ROW_NONE_I; }
+    float mv = ROW_NONE_V, thr_v;
+    int mi = ROW_NONE_I, thr_i;
+    constexpr int DEPTH = 2;      // measured beside the KM-entry register lists (profiles/rows_kernels_ab.txt): <32, true> 80.6 us with two loads in flight, 88.5 with one
+    row_scan<LP_THREADS, DEPTH>(row, n_vocab, [&](float v, int i) { row_keep(v, i, mv, mi); });
+    row_kth_bound<LP_THREADS>(mv, mi, K, thr_v, thr_i);
+    row_scan<LP_THREADS, DEPTH>(row, n_vocab, [&](float v, int i) { if (!row_before(thr_v, thr_i, v, i)) beam_insert<KM>(v, i, tv, ti); });
 
     // per wave: K rounds of a wave arg-max over the lanes' list heads; the winner pops its head (ids are unique)
     for (int r = 0; r < K; r++) {
@@ -166,12 +132,12 @@ __device__ __forceinline__ void beam_rows_body(const float *row, int n_vocab, co
         for (int off = 32; off > 0; off >>= 1) {
             const float ov = __shfl_xor(bv, off, 64);
             const int oi = __shfl_xor(bidx, off, 64);
-            if (beam_better(ov, oi, bv, bidx)) { bv = ov; bidx = oi; }
+            row_keep(ov, oi, bv, bidx);
         }
-        if (bidx != 0x7fffffff && ti[0] == bidx) {
+        if (bidx != ROW_NONE_I && ti[0] == bidx) {
 #pragma unroll
             for (int j = 0; j + 1 < KM; j++) { tv[j] = tv[j + 1]; ti[j] = ti[j + 1]; }
-            tv[KM - 1] = -INFINITY; ti[KM - 1] = 0x7fffffff;
+            tv[KM - 1] = ROW_NONE_V; ti[KM - 1] = ROW_NONE_I;
         }
         if (lane == 0) { w_v[wv][r] = bv; w_i[wv][r] = bidx; }
     }
@@ -182,10 +148,10 @@ __device__ __forceinline__ void beam_rows_body(const float *row, int n_vocab, co
         const int ew = tid / K, er = tid - ew * K;
         const float v = w_v[ew][er];
         const int id = w_i[ew][er];
-        if (id != 0x7fffffff) {
+        if (id != ROW_NONE_I) {
             int rank = 0;
             for (int w = 0; w < LP_THREADS / 64; w++)
-                for (int r = 0; r < K; r++) rank += beam_better(w_v[w][r], w_i[w][r], v, id) ? 1 : 0;
+                for (int r = 0; r < K; r++) rank += row_before(w_v[w][r], w_i[w][r], v, id) ? 1 : 0;
             if (rank < K) {
                 float lp = v;
                 if constexpr (!GIVEN) lp = (float)(((double)v - (double)m) - s_ls);

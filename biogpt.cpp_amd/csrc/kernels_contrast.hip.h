@@ -10,7 +10,8 @@
 //                           k dots in double, sim = (float)(dot / sqrt(na * nb)), the running maximum of candidate j in lane j.  Writes k partial
 //                           maxima per slab; slabs at or beyond the group's length, and finished groups, exit at once.
 //   contrast_select_kernel  one workgroup per group: the slab maxima -> pen_j, score_j = (float)((1 - a) * p_j - a * pen_j), the winner (highest score,
-//                           lowest j on ties); its id to seq_gen, its hidden row and norm appended to H[g]; lp_row_stats + sample_topk of the winner's
+//                           lowest j on ties); its id to seq_gen, its hidden row and norm appended to H[g]; lp_row_stats + sample_topk (both on the row kernels'
+//                           shared pieces, kernels_rows.hip.h, DESIGN.md "Row kernels") of the winner's
 //                           logits row -> the next k candidates and their probabilities; the k column states advance; an EOS finishes the group.
 //                           A group's FIRST step is the same step: its k columns all carry the prompt's last token, so "candidate 0" wins by decree,
 //                           nothing is written to seq_gen, and the row appended to H[g] is that token's.

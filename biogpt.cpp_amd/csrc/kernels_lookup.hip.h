@@ -12,7 +12,7 @@
 //                           copies of column 0 (the grid of the pass is fixed: they write the same K / V row with the same values).  A finished sequence
 //                           drafts nothing.
 //   (the packed pass with every row's logits: ForwardPass::packed_verify)
-//   lookup_accept_kernel    one workgroup per sequence.  a_j = arg-max of row j (lowest id on ties, as argmax_rows_kernel), for j = 0, 1, ... while
+//   lookup_accept_kernel    one workgroup per sequence.  a_j = arg-max of row j (row_argmax, kernels_rows.hip.h, as argmax_rows_kernel), for j = 0, 1, ... while
 //                           j <= d and every draft before matched (the rows behind the first mismatch are never read).  a_0 .. a_m are appended to seq_gen
 //                           and to T, cut at n_predict and behind the first eos_id; the column moves on by the number of tokens appended.  Counters:
 //                           passes + 1, drafted + d, accepted + (tokens appended - 1: the drafted tokens that reached the output), so a sequence's
@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "kernels.hip.h"
+#include "kernels_rows.hip.h"
 
 namespace bgk {
 
@@ -103,39 +104,20 @@ __global__ __launch_bounds__(LK_DRAFT_THREADS) void lookup_draft_kernel(const Lo
 
 __global__ __launch_bounds__(LK_ACCEPT_THREADS) void lookup_accept_kernel(LookupCtl *ctl, LookupSeq *ls, int32_t *text, const float *logits, int ld, int n_vocab,
                                                                           SeqState *seq, int32_t *gen_ids, int gen_stride) {
-    __shared__ float sv[LK_ACCEPT_THREADS / 64];
-    __shared__ int si[LK_ACCEPT_THREADS / 64];
     __shared__ int32_t am[LK_MAX_DRAFT + 1];
-    __shared__ int go_on;
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    constexpr int NW = LK_ACCEPT_THREADS / 64;
+    const int s = blockIdx.x, tid = threadIdx.x;
     LookupSeq *q = ls + s;
     if (q->finished) return;
     const int md = ctl->max_draft, d = q->d;
     int m = 0;      // drafts accepted so far; rows 0 .. m get their arg-max
     for (int j = 0; j <= d; j++) {
-        const float *lg = logits + ((size_t)s * (md + 1) + j) * ld;
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int k = tid; k < n_vocab; k += LK_ACCEPT_THREADS) {
-            const float v = lg[k];
-            if (v > bv) { bv = v; bi = k; }   // ascending k: the first maximum is kept
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(bv, off, 64);
-            const int oi = __shfl_xor(bi, off, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { sv[wv] = bv; si[wv] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < NW; w++)
-                if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
-            am[j] = bi;
-            go_on = j < d && q->draft[j] == bi;
-        }
-        __syncthreads();
-        if (!go_on) break;      // (the same word in every thread; the next write to it lies behind the next barrier pair)
+        float bv;
+        int bi;
+        row_argmax<LK_ACCEPT_THREADS>(logits + ((size_t)s * (md + 1) + j) * ld, n_vocab, bv, bi);
+        const int id = bi == ROW_NONE_I ? 0 : bi;      // (a row of NaNs only)
+        if (tid == 0) am[j] = id;
+        __syncthreads();      // row_argmax's words are written again by the next row
+        if (!(j < d && q->draft[j] == id)) break;      // (the same pair in every thread)
         m = j + 1;
     }
     if (tid == 0) {

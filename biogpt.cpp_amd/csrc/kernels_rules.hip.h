@@ -4,7 +4,7 @@
 //   rules_rows_kernel    one workgroup per row (column) of logits_all, in place.  The row's history h is its prompt (one copy per prompt in the
 //                        rules buffer, shared by the prompt's samples and by all beams) followed by its generated tokens (seq_gen), L = len(h):
 //                          mode 1 only    the row becomes its log-probabilities first: (float)(((double)l - m) - log S), the formula of
-//                                         beam_group_rows_kernel through the same lp_row_stats; its GIVEN form then takes the values as they are
+//                                         beam_group_rows_kernel through the same lp_row_stats (on the row kernels' shared pieces, kernels_rows.hip.h); its GIVEN form then takes the values as they are
 //                          penalty        every DISTINCT token of h once: s < 0 ? s * p : s / p (f32, IEEE division).  A bitmap of n_vocab bits in
 //                                         LDS, set with atomicOr: the thread that finds the bit clear applies the penalty
 //                          n-gram         every position i in [0, L - n] whose n - 1 tokens equal the last n - 1 of h bans h[i + n - 1]

@@ -3,8 +3,8 @@
 //
 //   sample_rows_kernel   one workgroup per sequence row of logits_all:
 //                          selection  the row's top k (value descending, equal values: lower id first -- the order of topk_kernel / host_topk).
-//                                     Pass 1: every thread's own maximum; the k-th best of the 256 maxima is a lower bound of the row's k-th
-//                                     value (k threads hold an element at least that good).  Pass 2 (the row is on chip by now): the few
+//                                     Pass 1: the bound (row_kth_bound; the walk, the order and the arg-max are the row kernels' shared pieces,
+//                                     kernels_rows.hip.h, DESIGN.md "Row kernels").  Pass 2 (the row is on chip by now): the few
 //                                     elements at or above the bound go to a list in LDS; each finds its rank among them by counting.
 //                                     A row with more than SAMPLE_CAND_CAP such elements (many of the best in few threads) takes k rounds
 //                                     of a workgroup-wide arg-max instead: slow, and not what a model's logits look like.
@@ -152,61 +152,24 @@ __host__ __device__ inline int sample_tail(const float *vals, int k, double top_
 
 struct SampleBlockSync { __device__ void operator()() const { __syncthreads(); } };
 
-// f(value, index) over every element of the row: a scalar head up to the first 16-byte boundary, float4s (two in flight), a scalar tail
-template <class F>
-__device__ __forceinline__ void sample_scan_row(const float *row, int n_vocab, F f) {
-    const int tid = threadIdx.x;
-    const int head = min(n_vocab, (int)(((16u - ((uint32_t)(uintptr_t)row & 15u)) & 15u) >> 2));
-    const int nvec = (n_vocab - head) >> 2;
-    const int tail0 = head + 4 * nvec;
-    const float4 *body = reinterpret_cast<const float4 *>(row + head);
-    if (tid < head) f(row[tid], tid);
-    for (int i = tid; i < nvec; i += 2 * SAMPLE_THREADS) {
-        const int j = i + SAMPLE_THREADS;
-        const float4 a = body[i];
-        const float4 b = j < nvec ? body[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        const int ia = head + 4 * i, ib = head + 4 * j;
-        f(a.x, ia); f(a.y, ia + 1); f(a.z, ia + 2); f(a.w, ia + 3);
-        if (j < nvec) { f(b.x, ib); f(b.y, ib + 1); f(b.z, ib + 2); f(b.w, ib + 3); }
-    }
-    if (tail0 + tid < n_vocab) f(row[tail0 + tid], tail0 + tid);
-}
-
-// (av, ai) comes before (bv, bi) in selection order
-__device__ __forceinline__ bool sample_before(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
 // The selection of sample_rows_kernel (and of contrast_select_kernel, kernels_contrast.hip.h): the row's best K <= SAMPLE_MAX_K elements into top_v / top_i
 // (LDS of the caller), value descending, equal values lower id first; NaNs never.  Called by all SAMPLE_THREADS threads; returns how many there are
 // (uniform), visible to every thread on return.
 __device__ __forceinline__ int sample_topk(const float *row, int n_vocab, int K, float *top_v, int *top_i) {
-    __shared__ float t_v[SAMPLE_THREADS];
-    __shared__ int t_i[SAMPLE_THREADS];
     __shared__ float c_v[SAMPLE_CAND_CAP];
     __shared__ int c_i[SAMPLE_CAND_CAP];
-    __shared__ float s_thr_v;
-    __shared__ int s_thr_i, s_n;
-    __shared__ float r_v[SAMPLE_THREADS / 64];
-    __shared__ int r_i[SAMPLE_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // ---- pass 1: the bound ----
-    float mv = -INFINITY;
-    int mi = 0x7fffffff;
-    sample_scan_row(row, n_vocab, [&](float v, int i) { lp_better(v, i, mv, mi); });
-    t_v[tid] = mv; t_i[tid] = mi;
-    if (tid == 0) { s_thr_v = -INFINITY; s_thr_i = 0x7fffffff; s_n = 0; }      // (fewer than K threads with an element: everything passes)
-    __syncthreads();
-    {
-        int rank = 0;
-        for (int j = 0; j < SAMPLE_THREADS; j++) rank += sample_before(t_v[j], t_i[j], mv, mi) ? 1 : 0;
-        if (rank == K - 1 && mi != 0x7fffffff) { s_thr_v = mv; s_thr_i = mi; }   // (pairs with an element are distinct: one thread at most)
-    }
-    __syncthreads();
-    const float thr_v = s_thr_v;
-    const int thr_i = s_thr_i;
+    __shared__ int s_n;
+    const int tid = threadIdx.x;
+    // ---- pass 1: the bound (row_kth_bound, kernels_rows.hip.h; its first barrier publishes s_n) ----
+    float mv = ROW_NONE_V, thr_v;
+    int mi = ROW_NONE_I, thr_i;
+    row_scan<SAMPLE_THREADS>(row, n_vocab, [&](float v, int i) { row_keep(v, i, mv, mi); });
+    if (tid == 0) s_n = 0;
+    row_kth_bound<SAMPLE_THREADS>(mv, mi, K, thr_v, thr_i);
 
     // ---- pass 2: the elements at or above the bound (NaNs never are, as in host_topk) ----
-    sample_scan_row(row, n_vocab, [&](float v, int i) {
-        if (v == v && !sample_before(thr_v, thr_i, v, i)) {
+    row_scan<SAMPLE_THREADS>(row, n_vocab, [&](float v, int i) {
+        if (v == v && !row_before(thr_v, thr_i, v, i)) {
             const int slot = atomicAdd(&s_n, 1);
             if (slot < SAMPLE_CAND_CAP) { c_v[slot] = v; c_i[slot] = i; }
         }
@@ -220,7 +183,7 @@ __device__ __forceinline__ int sample_topk(const float *row, int n_vocab, int K,
             const float v = c_v[c];
             const int id = c_i[c];
             int rank = 0;
-            for (int j = 0; j < n_c; j++) rank += sample_before(c_v[j], c_i[j], v, id) ? 1 : 0;
+            for (int j = 0; j < n_c; j++) rank += row_before(c_v[j], c_i[j], v, id) ? 1 : 0;
             if (rank < K) { top_v[rank] = v; top_i[rank] = id; }
         }
         __syncthreads();
@@ -229,21 +192,14 @@ __device__ __forceinline__ int sample_topk(const float *row, int n_vocab, int K,
         int pi = -1;
         k_eff = 0;
         for (int rd = 0; rd < K; rd++) {
-            float bv = -INFINITY;
-            int bi = 0x7fffffff;
-            sample_scan_row(row, n_vocab, [&](float v, int i) {
-                if (v == v && sample_before(pv, pi, v, i)) lp_better(v, i, bv, bi);
+            float bv = ROW_NONE_V;
+            int bi = ROW_NONE_I;
+            row_scan<SAMPLE_THREADS>(row, n_vocab, [&](float v, int i) {
+                if (v == v && row_before(pv, pi, v, i)) row_keep(v, i, bv, bi);
             });
-            for (int off = 32; off > 0; off >>= 1) {
-                const float ov = __shfl_xor(bv, off, 64);
-                const int oi = __shfl_xor(bi, off, 64);
-                lp_better(ov, oi, bv, bi);
-            }
-            if (lane == 0) { r_v[wv] = bv; r_i[wv] = bi; }
-            __syncthreads();
-            for (int w = 0; w < SAMPLE_THREADS / 64; w++) lp_better(r_v[w], r_i[w], bv, bi);
-            __syncthreads();
-            if (bi == 0x7fffffff) break;      // (uniform: every thread holds the same pair)
+            block_best<SAMPLE_THREADS>(bv, bi);
+            __syncthreads();      // block_best's words are written again by the next round
+            if (bi == ROW_NONE_I) break;      // (uniform: every thread holds the same pair)
             if (tid == 0) { top_v[rd] = bv; top_i[rd] = bi; }
             pv = bv; pi = bi;
             k_eff = rd + 1;

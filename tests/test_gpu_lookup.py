@@ -113,7 +113,7 @@ def rows_with(rng, n_vocab, am):
     return rows
 
 
-@pytest.mark.parametrize("n_vocab", [320, 42384])
+@pytest.mark.parametrize("n_vocab", [320, 1021, 42383, 42384])      # (odd widths: the stacked rows start on all four 16-byte alignments)
 def test_accept_kernel_alone(pkg, n_vocab):
     rng = np.random.default_rng(n_vocab)
     md, n_predict, eos = 7, 20, 77
@@ -121,19 +121,26 @@ def test_accept_kernel_alone(pkg, n_vocab):
     cases = [      # (draft, arg-max of rows 0 .. (-1: random), n_gen)
         ([4, 5, 6, 7, 8, 9, 10], [4, 5, 6, 7, 8, 9, 10, hi], 2),       # all drafts right
         ([4, 5, 6], [9, 5, 6, 7, -1, -1, -1, -1], 2),                  # first draft wrong
-        ([4, 5, 6, 8, 9], [4, 5, hi, 8, 9, 3, -1, -1], 0),             # wrong in the middle
+        ([4, 0, 6, 8, 9], [4, 0, hi, 8, 9, 3, -1, -1], 0),             # wrong in the middle; row 1 (row 17 of the stack: with an odd width 1 or 3 floats off
+        #                                                                a 16-byte boundary) has its maximum at id 0, in the scalar head, row 2 in the tail
         ([], [11, -1, -1, -1, -1, -1, -1, -1], 5),                     # d = 0
         ([4, 5, 6], [4, 5, 6, 7, -1, -1, -1, -1], 1),                  # row 1 holds an exact tie (below): the lower id wins
         ([4, eos, 6, 7], [4, eos, 6, 7, 8, -1, -1, -1], 3),            # EOS inside the accepted run
         ([4, 5, 6, 7], [4, 5, 6, 7, 8, -1, -1, -1], 17),               # n_predict reached inside the run
         ([4, 5], [4, 5, 6, -1, -1, -1, -1, -1], 17),                   # ... exactly at its end
         ([4, 5], [4, 5, 6, -1, -1, -1, -1, -1], 20),                   # finished before: untouched
+        ([], [-1, -1, -1, -1, -1, -1, -1, -1], 4),                     # d = 0, row 0 all -inf (below): id 0
+        ([], [-1, -1, -1, -1, -1, -1, -1, -1], 6),                     # d = 0, row 0 all NaN (below): id 0
     ]
     n = len(cases) if n_vocab == 320 else 5      # (the wide rows: the first five cases)
     cases = cases[:n]
     rows = np.concatenate([rows_with(rng, n_vocab, am) for _, am, _ in cases])
     rows[4 * (md + 1) + 1, [5, 200]] = 9.0      # case 4, row 1: ids 5 and 200 tie; 5 is drafted and wins
     rows[4 * (md + 1) + 2, [6, 3]] = 9.0        # ... row 2: ids 3 and 6 tie; 6 is drafted and loses
+    if n_vocab == 320:
+        rows[9 * (md + 1)] = -np.inf
+        rows[10 * (md + 1)] = np.nan
+        assert lookup_ref.argmax_low(rows[9 * (md + 1)]) == 0 and lookup_ref.argmax_low(rows[10 * (md + 1)]) == 0
     n_gen = [c[2] for c in cases]
     n_past = [30 + 3 * s + g for s, g in enumerate(n_gen)]
     finished = [1 if g >= n_predict else 0 for g in n_gen]
@@ -151,9 +158,10 @@ def test_accept_kernel_alone(pkg, n_vocab):
         want_live -= int(fin)
         want_far = max(want_far, npast)
     assert (live, far) == (want_live, want_far)
-    assert emitted[0] == [4, 5, 6, 7, 8, 9, 10, hi] and emitted[1] == [9] and emitted[2] == [4, 5, hi] and emitted[3] == [11] and emitted[4] == [4, 5, 3]
+    assert emitted[0] == [4, 5, 6, 7, 8, 9, 10, hi] and emitted[1] == [9] and emitted[2] == [4, 0, hi] and emitted[3] == [11] and emitted[4] == [4, 5, 3]
     if n_vocab == 320:
         assert emitted[5] == [4, eos] and emitted[6] == [4, 5, 6] and emitted[7] == [4, 5, 6] and state[5][3] == 1 and state[6][3] == 1 and state[7][3] == 1
+        assert emitted[9] == [0] and emitted[10] == [0] and state[9][0] == 0 and state[10][0] == 0      # (never the empty pair's id 0x7fffffff)
 
 
 # ---- 3. identity with greedy decoding ----
