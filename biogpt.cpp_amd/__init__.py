@@ -97,6 +97,88 @@ def rules_rows(rows, histories, prompt_lens=None, mode=0, eos_id=-1, device=0, *
     return out
 
 
+class Trie:
+    """A closed set of token sequences for constrained decoding (biogpt_hip_trie; INTEGRATION.md, "Constrained decoding"): pass it as trie= to
+    generate_beam / generate_beam_batch / generate_sample.  Built on the host; the device copy is made at the first use on a device and freed by
+    close()."""
+
+    def __init__(self, handle, n_vocab):
+        self._h = handle
+        self.n_vocab = int(n_vocab)
+
+    @classmethod
+    def build(cls, seqs, n_vocab):
+        """seqs: a list of id lists, each of at least one token in [0, n_vocab).  Duplicates merge; an entry may be a prefix of another."""
+        seqs = [np.asarray(q, dtype=np.int32).reshape(-1) for q in seqs]
+        lens = np.asarray([q.size for q in seqs], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(seqs + [np.zeros(1, np.int32)]))
+        h = lib().biogpt_hip_trie_build(flat.ctypes.data, lens.ctypes.data, len(seqs), int(n_vocab))
+        if not h:
+            raise BiogptError(_err())
+        return cls(h, n_vocab)
+
+    def info(self):
+        """dict(entries (after merging), nodes, edges, max_depth, max_fanout)."""
+        out = (C.c_int64 * 5)()
+        if lib().biogpt_hip_trie_info(self._h, out) != 0:
+            raise BiogptError(_err())
+        return dict(zip(("entries", "nodes", "edges", "max_depth", "max_fanout"), (int(v) for v in out)))
+
+    def allowed(self, gen, eos_id):
+        """The ids allowed after the generated tokens `gen`, ascending (biogpt_hip_trie_allowed_host: the definition of the mask)."""
+        g = np.ascontiguousarray(gen, dtype=np.int32).reshape(-1)
+        n = lib().biogpt_hip_trie_allowed_host(self._h, g.ctypes.data if g.size else None, g.size, int(eos_id), None, 0)
+        if n < 0:
+            raise BiogptError(_err())
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        if lib().biogpt_hip_trie_allowed_host(self._h, g.ctypes.data if g.size else None, g.size, int(eos_id), out.ctypes.data, n) != n:
+            raise BiogptError(_err())
+        return out[:n].copy()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().biogpt_hip_trie_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _trie_handle(trie):
+    if not isinstance(trie, Trie) or not trie._h:
+        raise BiogptError("trie must be an open Trie (Trie.build(seqs, n_vocab))")
+    return trie._h
+
+
+def trie_rows(rows, trie, histories, mode=0, eos_id=2, device=0, reps=0):
+    """trie_rows_kernel on rows held in host memory (biogpt_hip_trie_rows_device): rows float32 [n][n_vocab], histories a list of id lists (row r's
+    generated tokens; the prompt is no part of the walk).  mode 0: logits; 1: the allowed entries become log-probabilities.  Returns the rows; with
+    reps > 0 (biogpt_hip_trie_rows_bench) also the microseconds of reps further launches, by device events."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv = a.shape
+    hl = np.asarray([len(h) for h in histories], dtype=np.int32)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(h, dtype=np.int32) for h in histories] + [np.zeros(1, np.int32)]))
+    out = np.empty_like(a)
+    if reps:
+        us = np.zeros(int(reps), dtype=np.float32)
+        if lib().biogpt_hip_trie_rows_bench(int(device), _trie_handle(trie), int(mode), a.ctypes.data, n, nv, flat.ctypes.data, hl.ctypes.data, int(eos_id),
+                                            out.ctypes.data, int(reps), us.ctypes.data) != 0:
+            raise BiogptError(_err())
+        return out, us
+    if lib().biogpt_hip_trie_rows_device(int(device), _trie_handle(trie), int(mode), a.ctypes.data, n, nv, flat.ctypes.data, hl.ctypes.data, int(eos_id),
+                                         out.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return out
+
+
+def _no_rules_with_trie(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens):
+    if float(repetition_penalty) != 1.0 or int(no_repeat_ngram_size) or int(min_new_tokens) or len(tuple(suppress_tokens)):
+        raise BiogptError("generation rules together with a trie are not supported")
+
+
 def logprob_rows(rows, targets, device=0):
     """logprob_rows_kernel on rows held in host memory (biogpt_hip_logprob_rows_device): rows float32 [n][n_vocab], targets [n] (-1: none).
     Returns (lp float32[n], argmax int32[n], logit float32[n])."""
@@ -165,9 +247,10 @@ def lookup_accept(rows, drafts, n_gen, n_past, n_predict, max_draft, eos_id=-1, 
     return [[int(v) for v in emit[s] if v >= 0] for s in range(n)], state[:n].copy(), stats[:n].copy(), (int(live[0]), int(live[1]))
 
 
-def beam_rows(rows, n_beams, run_score, given=False, first_step=False, device=0):
+def beam_rows(rows, n_beams, run_score, given=False, first_step=False, device=0, masked=False):
     """beam_group_rows_kernel on rows held in host memory (biogpt_hip_beam_rows_device): rows float32 [G * n_beams][n_vocab], run_score [G * n_beams].
-    Returns (score float32, col int32, id int32), each [G * n_beams][2 * n_beams]; rows the kernel left alone hold (NaN, -1, -1)."""
+    Returns (score float32, col int32, id int32), each [G * n_beams][2 * n_beams]; rows the kernel left alone hold (NaN, -1, -1).  masked (with given):
+    the rows may hold fewer than 2 * n_beams finite values, as a trie step leaves them (biogpt_hip_beam_rows_masked_device)."""
     a = np.ascontiguousarray(rows, dtype=np.float32)
     n, nv = a.shape
     rs = np.ascontiguousarray(run_score, dtype=np.float32).reshape(-1)
@@ -175,6 +258,13 @@ def beam_rows(rows, n_beams, run_score, given=False, first_step=False, device=0)
         raise BiogptError("beam_rows: one run_score per row (%d != %d)" % (rs.size, n))
     K = 2 * int(n_beams)
     sc, col, ids = np.empty((n, K), np.float32), np.empty((n, K), np.int32), np.empty((n, K), np.int32)
+    if masked:
+        if not given:
+            raise BiogptError("beam_rows: masked rows are log-probabilities (given=True)")
+        if lib().biogpt_hip_beam_rows_masked_device(int(device), a.ctypes.data, n, nv, int(n_beams), rs.ctypes.data, 1 if first_step else 0, sc.ctypes.data,
+                                                    col.ctypes.data, ids.ctypes.data) != 0:
+            raise BiogptError(_err())
+        return sc, col, ids
     if lib().biogpt_hip_beam_rows_device(int(device), a.ctypes.data, n, nv, 1 if given else 0, int(n_beams), rs.ctypes.data, 1 if first_step else 0,
                                          sc.ctypes.data, col.ctypes.data, ids.ctypes.data) != 0:
         raise BiogptError(_err())
@@ -313,6 +403,17 @@ SYMBOLS = [
     ("biogpt_hip_lookup_draft_device", C.c_int, [C.c_int, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("biogpt_hip_lookup_accept_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_rules_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(GenRules), _P]),
+    ("biogpt_hip_trie_build", _P, [_P, _P, C.c_int32, C.c_int32]),
+    ("biogpt_hip_trie_free", None, [_P]),
+    ("biogpt_hip_trie_info", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("biogpt_hip_trie_allowed_host", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    ("biogpt_hip_generate_beam_trie", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P, _P, _P,
+                                               C.POINTER(C.c_double)]),
+    ("biogpt_hip_generate_sample_trie", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32, _P, _P, _P,
+                                                 C.POINTER(C.c_double)]),
+    ("biogpt_hip_trie_rows_device", C.c_int, [C.c_int, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P]),
+    ("biogpt_hip_trie_rows_bench", C.c_int, [C.c_int, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P]),
+    ("biogpt_hip_beam_rows_masked_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     ("biogpt_hip_logprob_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_beam_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     ("biogpt_hip_beam_table_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
@@ -626,10 +727,15 @@ class BiogptModel:
         return out.reshape(-1)[:len(prompts) * n].reshape(len(prompts), n).copy(), secs.value
 
     def generate_beam(self, prompt, n_predict, n_beams=5, eos_id=2, length_penalty=1.0, early_stopping=True, n_batch=8,
-                      repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):
+                      repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None):
         """Beam search (transformers' num_beams with do_sample=False).  Returns ([(ids int32[len], score), ...] best first,
-        seconds): each hypothesis's generated ids (an EOS that ended it included) and its normalized score.  The last four arguments are
-        transformers' logits processors of the same names, applied to each beam row's log-probabilities ("Generation rules")."""
+        seconds): each hypothesis's generated ids (an EOS that ended it included) and its normalized score.  The four rule arguments are
+        transformers' logits processors of the same names, applied to each beam row's log-probabilities ("Generation rules").
+        trie: a Trie -- the output is restricted to its entries ("Constrained decoding": keep the hypotheses with a finite score)."""
+        if trie is not None:
+            hyps, secs = self.generate_beam_batch([list(prompt)], n_predict, n_beams, eos_id, length_penalty, early_stopping, n_batch, repetition_penalty,
+                                                  no_repeat_ngram_size, min_new_tokens, suppress_tokens, trie=trie)
+            return hyps[0], secs
         rules, keep = gen_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
         pr = np.ascontiguousarray(prompt, dtype=np.int32)
         w = max(int(n_predict), 1)
@@ -649,10 +755,11 @@ class BiogptModel:
         return [(flat[r * stride:r * stride + int(lens[r])].copy(), float(scores[r])) for r in range(n)], secs.value
 
     def generate_beam_batch(self, prompts, n_predict, n_beams=5, eos_id=2, length_penalty=1.0, early_stopping=True, n_batch=8,
-                            repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):
+                            repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None):
         """Beam search over a batch of prompts (list of id lists, or one flat id list) in one call: every prompt is a search of its own, all of them
         columns of the same decode steps ("Beam search over a batch").  Returns ([[(ids int32[len], score), ...] best first, one list
-        per prompt], seconds); prompt p's list is generate_beam(prompts[p], n_predict as clamped for the longest prompt, ...), bit for bit."""
+        per prompt], seconds); prompt p's list is generate_beam(prompts[p], n_predict as clamped for the longest prompt, ...), bit for bit.  trie: a Trie
+        shared by all prompts -- every search is restricted to its entries (biogpt_hip_generate_beam_trie)."""
         rules, keep = gen_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
         if len(prompts) and np.isscalar(prompts[0]):
             prompts = [prompts]
@@ -665,9 +772,15 @@ class BiogptModel:
         scores = np.zeros(max(G, 1) * B, dtype=np.float32)
         counts = np.zeros(max(G, 1), dtype=np.int32)
         secs = C.c_double(0.0)
-        got = lib().biogpt_hip_generate_beam_batch(self._h, flat.ctypes.data, lens.ctypes.data, G, int(n_batch), int(n_beams), int(n_predict), int(eos_id),
-                                                   float(length_penalty), 1 if early_stopping else 0, C.byref(rules), out.ctypes.data, ol.ctypes.data,
-                                                   scores.ctypes.data, counts.ctypes.data, C.byref(secs))
+        if trie is not None:
+            _no_rules_with_trie(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
+            got = lib().biogpt_hip_generate_beam_trie(self._h, flat.ctypes.data, lens.ctypes.data, G, int(n_batch), int(n_beams), int(n_predict), int(eos_id),
+                                                      float(length_penalty), 1 if early_stopping else 0, _trie_handle(trie), out.ctypes.data, ol.ctypes.data,
+                                                      scores.ctypes.data, counts.ctypes.data, C.byref(secs))
+        else:
+            got = lib().biogpt_hip_generate_beam_batch(self._h, flat.ctypes.data, lens.ctypes.data, G, int(n_batch), int(n_beams), int(n_predict), int(eos_id),
+                                                       float(length_penalty), 1 if early_stopping else 0, C.byref(rules), out.ctypes.data, ol.ctypes.data,
+                                                       scores.ctypes.data, counts.ctypes.data, C.byref(secs))
         if got < 0:
             raise BiogptError(_err())
         if got == 0:
@@ -734,12 +847,13 @@ class BiogptModel:
                 [dict(passes=int(st[p, 0]), drafted=int(st[p, 1]), accepted=int(st[p, 2])) for p in range(G)], secs.value)
 
     def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
-                        repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=()):
+                        repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None):
         """n_samples sampled continuations of every prompt (list of id lists, or one flat id list), drawn on the device by the reference's top-k / top-p
         sampler (INTEGRATION.md, "Sampled generation").  Sequence p * n_samples + j is sample j of prompt p with std::mt19937(seeds[...]); seeds=None:
         seed + sequence index.  Returns ([ids int32[len], ...] in sequence order, seconds); an EOS that ended a sequence is included.  The last four arguments
         are transformers' logits processors of the same names, applied to the raw logits row in front of the sampler ("Generation
-        rules"); top_k=1 never draws: greedy decoding with rules and an EOS."""
+        rules"); top_k=1 never draws: greedy decoding with rules and an EOS.  trie: a Trie -- every row is masked to the tokens that continue an entry
+        (or EOS where one ends) in front of the sampler (biogpt_hip_generate_sample_trie; needs eos_id >= 0); top_k=1: constrained greedy decoding."""
         rules, keep = gen_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
         if len(prompts) and np.isscalar(prompts[0]):
             prompts = [prompts]
@@ -755,9 +869,15 @@ class BiogptModel:
         out = np.zeros((max(n, 1), w), dtype=np.int32)
         ol = np.zeros(max(n, 1), dtype=np.int32)
         secs = C.c_double(0.0)
-        got = lib().biogpt_hip_generate_sample_rules(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples), int(n_batch), int(n_predict),
-                                                     int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id), out.ctypes.data, ol.ctypes.data,
-                                                     C.byref(secs), C.byref(rules))
+        if trie is not None:
+            _no_rules_with_trie(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
+            got = lib().biogpt_hip_generate_sample_trie(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples), int(n_batch), int(n_predict),
+                                                        int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id), _trie_handle(trie), out.ctypes.data,
+                                                        ol.ctypes.data, C.byref(secs))
+        else:
+            got = lib().biogpt_hip_generate_sample_rules(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples), int(n_batch), int(n_predict),
+                                                         int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id), out.ctypes.data, ol.ctypes.data,
+                                                         C.byref(secs), C.byref(rules))
         if got < 0:
             raise BiogptError(_err())
         if got == 0:

@@ -45,10 +45,12 @@
 #include "kernels_beam.hip.h"
 #include "kernels_sample.hip.h"
 #include "kernels_rules.hip.h"
+#include "kernels_trie.hip.h"
 #include "kernels_contrast.hip.h"
 #include "kernels_lookup.hip.h"
 #include "model_file.h"
 #include "quant_host.h"
+#include "trie_host.h"
 
 using namespace bg;
 
@@ -220,10 +222,10 @@ struct EngineOptions {
 namespace {
 }  // namespace
 
-// The captured steps of one mode of column generation: [12 * (rules active) + 6 * (steps as column-per-XCD launches) + context bucket], valid for
-// the call shape (key_a, key_b) they were captured for -- sequences, or groups and beams
+// The captured steps of one mode of column generation: [12 * (form of the step: 0 plain, 1 with rules, 2 with a trie) + 6 * (steps as column-per-XCD
+// launches) + context bucket], valid for the call shape (key_a, key_b) they were captured for -- sequences, or groups and beams
 struct ColumnGraphs {
-    hipGraphExec_t exec[24] = {};
+    hipGraphExec_t exec[36] = {};
     int key_a = 0, key_b = 0;
 };
 
@@ -297,6 +299,8 @@ struct biogpt_hip_ctx {
     // generation rules (kernels_rules.hip.h): RulesCtl, RULES_ROWS RulesRow, then the call's prompts (one copy per prompt); allocated once, at its
     // largest, so that captured steps keep their pointers
     uint8_t *rules_buf = nullptr;
+    // trie-constrained generation (kernels_trie.hip.h): the call's TrieCtl; allocated once (captured steps keep the pointer, the trie's arrays are named in it)
+    bgk::TrieCtl *trie_ctl = nullptr;
     // contrastive search (biogpt_hip_generate_contrastive, kernels_contrast.hip.h): the step's device state at its largest (contrast_* offsets below), allocated
     // at the first such call; the context store of contrast_groups groups -- [groups][n_positions][d_model] f32 rows, then their squared norms as doubles
     uint8_t *contrast_buf = nullptr;
@@ -1593,7 +1597,7 @@ void destroy(biogpt_hip_ctx *c) {
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2375,7 +2379,7 @@ struct ColumnCall {
     ColumnGraphs *graphs = nullptr;     // the mode's captured steps, valid for the call shape (key_a, key_b)
     int key_a = 0, key_b = 0;
     int extra_steps = 0;                // steps beyond one per token (contrastive: 1, the prompt's last token has a step of its own)
-    int gset_extra = 0;                 // 12 with rules: another form of the step, so other graphs
+    int gset_extra = 0;                 // 12 with rules, 24 with a trie: another form of the step, so other graphs
     int key_stride = 1;                 // positions a column can move on in one step, at most (prompt-lookup decoding: 1 + max_draft); > 1: the word behind
                                         // live_dev holds the furthest position of any column
     bool plain_steps = false;           // the step is no decode step of one column per sequence: never the column-per-XCD launches
@@ -3083,6 +3087,67 @@ static bool enqueue_rules(biogpt_hip_ctx *c, int n_rows, const int32_t *skip, in
     return true;
 }
 
+// ---- trie-constrained generation: PrefixConstrainedLogitsProcessor over a closed set of sequences, between the forward pass and the selection (kernels_trie.hip.h) ----
+// What can be judged without a model, before any HIP call: the two generation entries and the kernel-alone entry
+static bool check_trie(const biogpt_hip_trie *trie, int eos_id) {
+    if (!trie) BG_FAIL(false, "trie is NULL (the functions without a trie generate unconstrained)");
+    if (eos_id < 0) BG_FAIL(false, "eos_id must be >= 0 with a trie: EOS is how an entry ends");
+    if (eos_id >= trie->n_vocab) BG_FAIL(false, "eos_id %d out of range: must be in [0, %d)", eos_id, trie->n_vocab);
+    if (trie->uses(eos_id)) BG_FAIL(false, "eos_id %d occurs in an entry of the trie", eos_id);
+    if (trie->n_vocab > bgk::RULES_MAX_VOCAB) BG_FAIL(false, "a trie step holds one bit per token in LDS: n_vocab must be at most %d", bgk::RULES_MAX_VOCAB);
+    return true;
+}
+static bool check_trie_vocab(const biogpt_hip_trie *trie, int n_vocab) {
+    if (trie->n_vocab != n_vocab) BG_FAIL(false, "trie: built for n_vocab = %d, the model has %d", trie->n_vocab, n_vocab);
+    return true;
+}
+
+// The trie's arrays on `device` -- [first | tok | child | term] in one block, uploaded at the first use there and freed with the handle -- as a TrieCtl
+static bool trie_device(biogpt_hip_trie *trie, int device, bgk::TrieCtl *out) {
+    ByteLayout l;
+    const size_t o_f = l.part(trie->first.size() * 4), o_t = l.part(trie->tok.size() * 4), o_c = l.part(trie->child.size() * 4), o_m = l.part(trie->term.size());
+    uint8_t *block = nullptr;
+    for (const auto &c : trie->copies) if (c.device == device) block = static_cast<uint8_t *>(c.block);
+    if (!block) {
+        std::vector<uint8_t> h(l.bytes(), 0);
+        std::memcpy(h.data() + o_f, trie->first.data(), trie->first.size() * 4);
+        std::memcpy(h.data() + o_t, trie->tok.data(), trie->tok.size() * 4);
+        std::memcpy(h.data() + o_c, trie->child.data(), trie->child.size() * 4);
+        std::memcpy(h.data() + o_m, trie->term.data(), trie->term.size());
+        HIP_TRY(false, hipMalloc(&block, h.size()));
+        if (hipMemcpy(block, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(block);
+            BG_FAIL(false, "the trie's upload failed: %s", hipGetErrorString(hipGetLastError()));
+        }
+        trie->copies.push_back({device, block});
+        trie->free_copy = [](int, void *b) { (void)hipFree(b); };
+    }
+    *out = bgk::TrieCtl{};
+    out->first = reinterpret_cast<const int32_t *>(block + o_f); out->tok = reinterpret_cast<const int32_t *>(block + o_t);
+    out->child = reinterpret_cast<const int32_t *>(block + o_c); out->term = block + o_m;
+    out->n_nodes = (int32_t)trie->n_nodes();
+    return true;
+}
+
+// the call's trie, EOS id and mode -> the context's TrieCtl, once per call
+static bool trie_upload(biogpt_hip_ctx *c, biogpt_hip_trie *trie, int mode, int eos_id) {
+    bgk::TrieCtl h;
+    if (!trie_device(trie, c->device, &h)) return false;
+    h.eos_id = eos_id; h.mode = mode;
+    if (!c->trie_ctl) HIP_TRY(false, hipMalloc(&c->trie_ctl, sizeof(bgk::TrieCtl)));
+    HIP_TRY(false, hipMemcpy(c->trie_ctl, &h, sizeof(h), hipMemcpyHostToDevice));
+    return true;
+}
+
+// skip: as enqueue_rules
+static bool enqueue_trie(biogpt_hip_ctx *c, int n_rows, const int32_t *skip, int skip_stride) {
+    const int V = c->hp.n_vocab;
+    hipLaunchKernelGGL(bgk::trie_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((V + 31) / 32) * 4, c->stream, c->logits_all, V, V, c->trie_ctl, c->seq, c->seq_gen,
+                       c->hp.n_positions, skip, skip_stride);
+    HIP_TRY(false, hipGetLastError());
+    return true;
+}
+
 // ---- sampled generation: n_prompts x n_samples columns of the batched decode step + the reference's sampler on the device (kernels_sample.hip.h) ----
 // The column generation above with sample_rows_kernel as the selection.  A prompt with several samples is evaluated once, into the slot of its first
 // sample.  With an EOS id the steps stop once every sequence has finished (SampleCtl::n_live).  The context's own K / V cache, position and logits row
@@ -3108,7 +3173,7 @@ static bgk::SampleCtl sample_ctl_of(int top_k, int eos_id, int n_seqs, double to
 
 static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
                                 int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
-                                int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules) {
+                                int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules, biogpt_hip_trie *trie = nullptr) {
     clear_error();
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompts || !prompt_lens || !seeds || !out_ids || !out_lens) BG_FAIL(-1, "null argument");
@@ -3124,13 +3189,14 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     if (eos_id < -1 || eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
     if (!check_fast_chain(ctx, "sampled generation")) return -1;
     if (!check_rules(rules, V, P)) return -1;
+    if (trie && !check_trie_vocab(trie, V)) return -1;
     const bool ru = rules_active(rules, eos_id);
     SampleBufs sb{};
     ColumnCall cc(ctx);
     cc.prompts = prompts; cc.prompt_lens = prompt_lens;
     cc.n_prompts = n_prompts; cc.per_prompt = n_samples; cc.n_batch = n_batch;
     cc.graphs = &ctx->graphs_sample; cc.key_a = n_seqs;
-    cc.gset_extra = ru ? 12 : 0;
+    cc.gset_extra = trie ? 24 : ru ? 12 : 0;
     cc.prepare = [&]() -> bool {
         if (n_seqs > ctx->sample_cap) {
             if (ctx->sample_ctl) (void)hipFree(ctx->sample_ctl);
@@ -3149,11 +3215,13 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
         *hb.ctl = sample_ctl_of(top_k, eos_id, n_seqs, top_p, temp);
         for (int r = 0; r < n_seqs; r++) { bgk::mt_seed(seeds[r], hb.seq[r].mt); bgk::mt_regenerate(hb.seq[r].mt); }
         HIP_TRY(false, hipMemcpy(sb.ctl, h.data(), h.size(), hipMemcpyHostToDevice));
+        if (trie && !trie_upload(ctx, trie, 0, eos_id)) return false;
         return !ru || rules_upload(ctx, rules, 0, eos_id, prompts, prompt_lens, n_prompts, n_samples);
     };
     cc.step = [&](int t_max) -> bool {
         if (!enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max))) return false;
         if (ru && !enqueue_rules(ctx, n_seqs, &sb.seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
+        if (trie && !enqueue_trie(ctx, n_seqs, &sb.seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
         hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, sb.ctl, sb.seq, ctx->seq, ctx->seq_gen, P);
         HIP_TRY(false, hipGetLastError());
         return true;
@@ -3186,6 +3254,18 @@ int biogpt_hip_generate_sample_rules(biogpt_hip_ctx *ctx, const int32_t *prompts
                                      int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules) {
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, rules);
+    });
+}
+
+// biogpt_hip_generate_sample with trie_rows_kernel (mode 0) in front of the sampler; no rules
+int biogpt_hip_generate_sample_trie(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
+                                    int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
+                                    biogpt_hip_trie *trie, int32_t *out_ids, int32_t *out_lens, double *seconds_out) {
+    clear_error();
+    if (!check_trie(trie, eos_id)) return -1;
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, nullptr,
+                                    trie);
     });
 }
 
@@ -3313,7 +3393,7 @@ static bool beam_read_pools(const bgk::BeamCtl *ctl, const int32_t *pool_ids, si
 
 static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_batch, int32_t n_beams,
                                     int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping, const biogpt_hip_gen_rules *rules,
-                                    int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts, double *seconds_out) {
+                                    int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts, double *seconds_out, biogpt_hip_trie *trie = nullptr) {
     clear_error();
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompts || !prompt_lens || !out_ids || !out_lens || !out_scores || !out_counts) BG_FAIL(-1, "null argument");
@@ -3334,7 +3414,9 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     if (!check_rules(rules, hp.n_vocab, P)) return -1;
     if (rules_ban(rules, eos_id) && hp.n_vocab - rules->n_suppress - 1 - P < 2 * B)
         BG_FAIL(-1, "the rules could leave a row fewer than 2 x n_beams candidates: n_vocab - n_suppress - 1 - n_positions = %d < %d", hp.n_vocab - rules->n_suppress - 1 - P, 2 * B);
+    if (trie && !check_trie_vocab(trie, hp.n_vocab)) return -1;
     const bool ru = rules_active(rules, eos_id);
+    const bool given = ru || trie;      // the row kernel takes processed log-probabilities as they are
     BeamBufs bufs{};
     std::vector<bgk::BeamCtl> hc;
     std::vector<int32_t> ids;
@@ -3342,7 +3424,7 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     cc.prompts = prompts; cc.prompt_lens = prompt_lens;
     cc.n_prompts = G; cc.per_prompt = B; cc.n_batch = n_batch;
     cc.graphs = &ctx->graphs_beam; cc.key_a = G; cc.key_b = B;
-    cc.gset_extra = ru ? 12 : 0;
+    cc.gset_extra = trie ? 24 : ru ? 12 : 0;
     cc.prepare = [&]() -> bool {
         if (!ctx->bbatch_buf) {
             size_t bytes;
@@ -3355,10 +3437,11 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     };
     cc.upload = [&]() -> bool {
         return upload_beam_start(bufs, G, B, prompt_lens, cc.n_predict, eos_id, length_penalty, early_stopping) &&
-               (!ru || rules_upload(ctx, rules, 1, eos_id, prompts, prompt_lens, G, B));
+               (!ru || rules_upload(ctx, rules, 1, eos_id, prompts, prompt_lens, G, B)) && (!trie || trie_upload(ctx, trie, 1, eos_id));
     };
     cc.step = [&](int t_max) -> bool {
-        return enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max)) && (!ru || enqueue_rules(ctx, n_seqs, bufs.col_skip, 1)) && enqueue_beam_group_select(bufs, G, B, ru);
+        return enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max)) && (!ru || enqueue_rules(ctx, n_seqs, bufs.col_skip, 1)) &&
+               (!trie || enqueue_trie(ctx, n_seqs, bufs.col_skip, 1)) && enqueue_beam_group_select(bufs, G, B, given);
     };
     cc.before_sync = [&]() -> bool {      // every group's pool comes back behind the last step
         hc.resize((size_t)G); ids.resize((size_t)n_seqs * P);
@@ -3378,6 +3461,19 @@ int biogpt_hip_generate_beam_batch(biogpt_hip_ctx *ctx, const int32_t *prompts, 
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_beam_batch_once(ctx, prompts, prompt_lens, n_prompts, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, rules, out_ids, out_lens,
                                         out_scores, out_counts, seconds_out);
+    });
+}
+
+// biogpt_hip_generate_beam_batch with trie_rows_kernel (mode 1) in front of the selection over given rows; no rules.  Candidates at -inf are legal here: a
+// row holds as few finite values as the trie allows, and the search is beam_ref's over the masked rows ("Constrained decoding")
+int biogpt_hip_generate_beam_trie(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_batch, int32_t n_beams,
+                                  int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping, biogpt_hip_trie *trie, int32_t *out_ids,
+                                  int32_t *out_lens, float *out_scores, int32_t *out_counts, double *seconds_out) {
+    clear_error();
+    if (!check_trie(trie, eos_id)) return -1;
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_beam_batch_once(ctx, prompts, prompt_lens, n_prompts, n_batch, n_beams, n_predict, eos_id, length_penalty, early_stopping, nullptr, out_ids, out_lens,
+                                        out_scores, out_counts, seconds_out, trie);
     });
 }
 

@@ -96,6 +96,90 @@ int biogpt_hip_rules_rows_device(int device, int32_t mode, const float *rows, in
     return 0;
 }
 
+// trie_rows_kernel over rows held in host memory (tests of the kernel itself, tools): row r's generated tokens are hist_lens[r] tokens of `hist` (the
+// histories concatenated), laid out for the kernel as a call lays them out.  reps > 0 (biogpt_hip_trie_rows_bench): the launch is then repeated on the
+// same rows, restored by a device copy in front of each, and us_out[i] is the time between two events around launch i alone
+static int trie_rows_device(int device, biogpt_hip_trie *trie, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist,
+                            const int32_t *hist_lens, int32_t eos_id, float *rows_out, int32_t reps, float *us_out) {
+    clear_error();
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!hist || !hist_lens) BG_FAIL(-1, "hist or hist_lens is NULL");
+    if (!rows_out) BG_FAIL(-1, "rows_out is NULL");
+    if (mode != 0 && mode != 1) BG_FAIL(-1, "mode must be 0 (logits) or 1 (log-probabilities)");
+    if (n_rows < 1 || n_rows > 4096) BG_FAIL(-1, "n_rows must be in [1, 4096]");
+    if (reps < 0 || reps > 10000 || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, 10000], with us_out");
+    if (!check_trie(trie, eos_id)) return -1;
+    if (n_vocab != trie->n_vocab) BG_FAIL(-1, "n_vocab = %d, the trie was built for %d", n_vocab, trie->n_vocab);
+    size_t total = 0;
+    int gs = 1;
+    for (int r = 0; r < n_rows; r++) {
+        if (hist_lens[r] < 0 || hist_lens[r] > (1 << 20)) BG_FAIL(-1, "hist_lens[%d] = %d: must be in [0, %d]", r, hist_lens[r], 1 << 20);
+        for (int i = 0; i < hist_lens[r]; i++)
+            if (hist[total + i] < 0 || hist[total + i] >= n_vocab) BG_FAIL(-1, "hist: token %d of row %d out of range", i, r);
+        total += (size_t)hist_lens[r];
+        gs = std::max(gs, hist_lens[r]);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4;
+    ByteLayout l;      // [rows | ctl | column states | generated words | the rows again, with reps]
+    const size_t o_lg = l.part(lg_b), o_ct = l.part(sizeof(bgk::TrieCtl)), o_st = l.part(sizeof(bgk::SeqState) * (size_t)n_rows), o_gn = l.part((size_t)n_rows * gs * 4);
+    const size_t side_b = l.bytes() - o_ct, o_keep = l.part(reps > 0 ? lg_b : 0);
+    std::vector<uint8_t> h(side_b, 0);      // the image of ctl .. generated words
+    bgk::TrieCtl *hc = reinterpret_cast<bgk::TrieCtl *>(h.data());
+    if (!trie_device(trie, device, hc)) return -2;
+    hc->eos_id = eos_id; hc->mode = mode;
+    bgk::SeqState *st = reinterpret_cast<bgk::SeqState *>(h.data() + (o_st - o_ct));
+    int32_t *gn = reinterpret_cast<int32_t *>(h.data() + (o_gn - o_ct));
+    size_t at = 0;
+    for (int r = 0; r < n_rows; r++) {
+        std::memcpy(gn + (size_t)r * gs, hist + at, (size_t)hist_lens[r] * 4);
+        st[r].n_gen = hist_lens[r];
+        at += (size_t)hist_lens[r];
+    }
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_ct, h.data(), h.size(), hipMemcpyHostToDevice));
+    auto launch = [&] {
+        hipLaunchKernelGGL(bgk::trie_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((n_vocab + 31) / 32) * 4, 0, d.at<float>(o_lg), n_vocab, n_vocab,
+                           d.at<const bgk::TrieCtl>(o_ct), d.at<const bgk::SeqState>(o_st), d.at<const int32_t>(o_gn), gs, nullptr, 0);
+    };
+    launch();
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(rows_out, d.p + o_lg, lg_b, hipMemcpyDeviceToHost));
+    if (reps > 0) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIP_TRY(-2, hipMemcpy(d.p + o_keep, rows, lg_b, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipEventCreate(&e0));
+        HIP_TRY(-2, hipEventCreate(&e1));
+        hipError_t err = hipSuccess;
+        for (int i = 0; i < reps && err == hipSuccess; i++) {
+            float ms = 0.0f;
+            err = hipMemcpyAsync(d.p + o_lg, d.p + o_keep, lg_b, hipMemcpyDeviceToDevice, 0);
+            if (err == hipSuccess) err = hipEventRecord(e0, 0);
+            if (err == hipSuccess) { launch(); err = hipGetLastError(); }
+            if (err == hipSuccess) err = hipEventRecord(e1, 0);
+            if (err == hipSuccess) err = hipEventSynchronize(e1);
+            if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+            us_out[i] = ms * 1e3f;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        HIP_TRY(-2, err);
+    }
+    return 0;
+}
+int biogpt_hip_trie_rows_device(int device, biogpt_hip_trie *trie, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist,
+                                const int32_t *hist_lens, int32_t eos_id, float *rows_out) {
+    return trie_rows_device(device, trie, mode, rows, n_rows, n_vocab, hist, hist_lens, eos_id, rows_out, 0, nullptr);
+}
+int biogpt_hip_trie_rows_bench(int device, biogpt_hip_trie *trie, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist,
+                               const int32_t *hist_lens, int32_t eos_id, float *rows_out, int32_t reps, float *us_out) {
+    if (reps < 1) { clear_error(); BG_FAIL(-1, "reps must be in [1, 10000]"); }
+    return trie_rows_device(device, trie, mode, rows, n_rows, n_vocab, hist, hist_lens, eos_id, rows_out, reps, us_out);
+}
+
 // logprob_rows_kernel over rows held in host memory (tests of the kernel itself): ldl = n_vocab, so an odd n_vocab puts rows 1, 2, 3 on the other
 // 16-byte alignments
 int biogpt_hip_logprob_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *targets, float *lp_out, int32_t *argmax_out,
@@ -139,9 +223,9 @@ static bool beam_given_rows_ok(const float *rows, size_t n_rows, int n_vocab, in
 
 // beam_group_rows_kernel over rows held in host memory (tests of the kernel itself), through the dispatch of a call: row r is column r % n_beams of group
 // r / n_beams, run_score[r] the score of the beam in it.  Every candidate is a sentinel (score NaN, col = id = -1) before the launch; with first_step a
-// group's row 0 alone may write.
-int biogpt_hip_beam_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t given, int32_t n_beams, const float *run_score,
-                                int32_t first_step, float *cand_score, int32_t *cand_col, int32_t *cand_id) {
+// group's row 0 alone may write.  masked: given rows may hold fewer than 2 x n_beams finite values, as the rows of a trie step do.
+static int beam_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t given, int32_t n_beams, const float *run_score,
+                            int32_t first_step, float *cand_score, int32_t *cand_col, int32_t *cand_id, bool masked) {
     clear_error();
     if (!rows) BG_FAIL(-1, "rows is NULL");
     if (!run_score) BG_FAIL(-1, "run_score is NULL");
@@ -153,7 +237,7 @@ int biogpt_hip_beam_rows_device(int device, const float *rows, int32_t n_rows, i
     if (n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be at most %d", 1 << 20);
     if (n_vocab < 2 * n_beams) BG_FAIL(-1, "n_vocab: a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", n_vocab);
     const int B = n_beams, G = n_rows / B, K = 2 * B;
-    if (given && !beam_given_rows_ok(rows, (size_t)n_rows, n_vocab, K, "rows")) return -1;
+    if (given && !masked && !beam_given_rows_ok(rows, (size_t)n_rows, n_vocab, K, "rows")) return -1;
     HIP_TRY(-2, hipSetDevice(device));
     std::vector<bgk::BeamCtl> hc((size_t)G);
     for (int g = 0; g < G; g++) {
@@ -182,6 +266,16 @@ int biogpt_hip_beam_rows_device(int device, const float *rows, int32_t n_rows, i
     HIP_TRY(-2, hipMemcpy(out.data(), d.p + o_cd, cd_b, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < out.size(); i++) { cand_score[i] = out[i].score; cand_col[i] = out[i].col; cand_id[i] = out[i].id; }
     return 0;
+}
+
+int biogpt_hip_beam_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t given, int32_t n_beams, const float *run_score,
+                                int32_t first_step, float *cand_score, int32_t *cand_col, int32_t *cand_id) {
+    return beam_rows_device(device, rows, n_rows, n_vocab, given, n_beams, run_score, first_step, cand_score, cand_col, cand_id, false);
+}
+// the rows of a trie step: log-probabilities of which any number may be -inf
+int biogpt_hip_beam_rows_masked_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_beams, const float *run_score, int32_t first_step,
+                                       float *cand_score, int32_t *cand_col, int32_t *cand_id) {
+    return beam_rows_device(device, rows, n_rows, n_vocab, 1, n_beams, run_score, first_step, cand_score, cand_col, cand_id, true);
 }
 
 // A whole beam search over the three beam kernels with the model replaced by a lookup (beam_table_feed_kernel, kernels_beam.hip.h), through the step

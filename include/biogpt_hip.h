@@ -329,6 +329,57 @@ int biogpt_hip_rules_rows_device(int device, int32_t mode /* 0 logits, 1 log-pro
                                  const int32_t *hist /* concatenated */, const int32_t *hist_lens, const int32_t *prompt_lens, int32_t eos_id,
                                  const biogpt_hip_gen_rules *rules, float *rows_out);
 
+/* ---- trie-constrained generation: output restricted to a closed set of token sequences (entity names, labels of a schema), transformers'
+ * prefix_allowed_tokens_fn / PrefixConstrainedLogitsProcessor over a trie, on the device inside the captured step (csrc/trie_host.cpp,
+ * csrc/kernels_trie.hip.h; INTEGRATION.md, "Constrained decoding").
+ *
+ * The definition.  Let g be the tokens generated so far (the prompt excluded).  Walk g from the root:
+ *   the walk ends at node u       A = {tokens of u's edges} + {eos_id if an entry ends at u}
+ *   the walk leaves the trie      A = {eos_id}      (only a beam that took a candidate at -inf gets there)
+ * A is never empty.  The masked row is s[t] for t in A and -inf elsewhere.
+ *
+ * biogpt_hip_trie_build: n_seqs >= 1 entries, concatenated in seqs, entry i of lens[i] >= 1 tokens in [0, n_vocab).  Duplicates merge; an entry may
+ * be a prefix of another.  NULL (biogpt_hip_last_error() names the argument) for zero entries, an empty entry or an id out of range.  Host only: no
+ * HIP call.  The layout is CSR: node u's edges are [first[u], first[u + 1]) of tok (ascending) and child, a terminal flag per node, and a bitmap of
+ * the tokens that occur anywhere.  The device copy is made at the first use on a device and freed with the handle: free it after the contexts that
+ * used it are idle.  A handle may serve any number of calls and contexts, one call at a time. */
+typedef struct biogpt_hip_trie biogpt_hip_trie;
+biogpt_hip_trie *biogpt_hip_trie_build(const int32_t *seqs /* concatenated */, const int32_t *lens, int32_t n_seqs, int32_t n_vocab);
+void biogpt_hip_trie_free(biogpt_hip_trie *trie);
+/* out: entries after merging, nodes, edges, the longest entry (max depth), the largest number of edges of a node (max fan-out) */
+int biogpt_hip_trie_info(const biogpt_hip_trie *trie, int64_t out[5]);
+/* The allowed set A after the generated tokens gen[0 .. n_gen), ascending, into out_ids (the first cap of them); returns its size, -1 on an argument
+ * error.  eos_id in [0, n_vocab).  This function is the definition the kernel restates. */
+int biogpt_hip_trie_allowed_host(const biogpt_hip_trie *trie, const int32_t *gen, int32_t n_gen, int32_t eos_id, int32_t *out_ids, int32_t cap);
+
+/* biogpt_hip_generate_beam_batch with every beam row masked by the trie: the row becomes its log-probabilities (the normalising sum over the
+ * UNMASKED row, as in transformers' _beam_search) and -inf outside A, then the selection runs.  Candidates at -inf are legal: they are ordered by the
+ * existing rule (score, parent rank, token id), can become running beams or pool entries, and hypotheses with score -inf are returned as they are --
+ * keep the ones with a finite score, and choose n_predict >= max depth + 1 so that entries can finish.  Every finite hypothesis that ends in eos_id is
+ * an entry of the trie.  eos_id >= 0 is required and must occur in no entry; the trie's n_vocab must be the model's; trie == NULL is an argument
+ * error (the functions without a trie exist); everything else as biogpt_hip_generate_beam_batch checks it.  No rules parameter: rules together with
+ * a trie are not supported.  A step with a trie is a captured graph of its own that serves any trie (its arrays are named in device memory). */
+int biogpt_hip_generate_beam_trie(biogpt_hip_ctx *ctx, const int32_t *prompts /* concatenated */, const int32_t *prompt_lens, int32_t n_prompts,
+                                  int32_t n_batch, int32_t n_beams, int32_t n_predict, int32_t eos_id, float length_penalty, int32_t early_stopping,
+                                  biogpt_hip_trie *trie, int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts, double *seconds_out);
+/* biogpt_hip_generate_sample with every unfinished sequence's logits row masked by the trie in front of the sampler; top_k = 1 is constrained greedy
+ * decoding.  Candidates at -inf carry weight 0.  Arguments as above and as biogpt_hip_generate_sample checks them. */
+int biogpt_hip_generate_sample_trie(biogpt_hip_ctx *ctx, const int32_t *prompts /* concatenated */, const int32_t *prompt_lens, int32_t n_prompts,
+                                    int32_t n_samples, int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp,
+                                    const uint32_t *seeds, int32_t eos_id, biogpt_hip_trie *trie, int32_t *out_ids, int32_t *out_lens, double *seconds_out);
+/* trie_rows_kernel over n_rows <= 4096 rows of n_vocab floats held in host memory.  mode 0: logits; mode 1: the members of A become log-probabilities.
+ * Row r's generated tokens are hist_lens[r] tokens of hist.  rows_out: [n_rows][n_vocab].  For tests of the kernel itself and tools. */
+int biogpt_hip_trie_rows_device(int device, biogpt_hip_trie *trie, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab,
+                                const int32_t *hist /* generated tokens, concatenated */, const int32_t *hist_lens, int32_t eos_id, float *rows_out);
+/* biogpt_hip_trie_rows_device, then reps in [1, 10000] further launches over the same rows (restored on the device in front of each launch);
+ * us_out[i]: microseconds between two device events around launch i alone.  For tools/trie_bench.py. */
+int biogpt_hip_trie_rows_bench(int device, biogpt_hip_trie *trie, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist,
+                               const int32_t *hist_lens, int32_t eos_id, float *rows_out, int32_t reps, float *us_out /* [reps] */);
+/* biogpt_hip_beam_rows_device with given = 1 over rows of which any number of values may be -inf, as a trie step leaves them (entries at -inf become
+ * candidates, lower id first, where fewer than 2 * n_beams finite ones are left).  For tests of the kernel itself. */
+int biogpt_hip_beam_rows_masked_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_beams, const float *run_score,
+                                       int32_t first_step, float *cand_score, int32_t *cand_col, int32_t *cand_id);
+
 /* logprob_rows_kernel (the log-softmax of biogpt_hip_score and of every beam score) over n_rows <= 4096 rows of n_vocab floats held in host memory,
  * row stride n_vocab: an odd n_vocab puts consecutive rows on the four 16-byte alignments.  targets[r] in [-1, n_vocab); for row r the outputs are
  * what biogpt_hip_score documents for a row: lp_out, argmax_out (lowest id on ties), logit_out; target -1 gives lp = logit = 0.  For tests of the
