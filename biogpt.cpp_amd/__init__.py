@@ -424,6 +424,12 @@ SYMBOLS = [
     ("biogpt_hip_score", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_score_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_score_continuations", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_generate_greedy_prefix", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_generate_sample_prefix", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
+                                                    C.c_int32, _P, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_prefix_stats", C.c_int, [_P, _P]),
+    ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    ("biogpt_hip_attn_prefix_bench", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     ("biogpt_hip_hidden", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     ("biogpt_hip_embed_batch", C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(EmbedOpts), _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_read_kv", C.c_int, [_P, C.c_int, C.c_size_t, C.c_size_t, _P]),
@@ -465,6 +471,13 @@ def lib():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+def _flat_ids(seqs):
+    """The id lists concatenated, int32; never a zero-sized buffer (its address would be null for a call that names no token at all)."""
+    parts = [np.asarray(s, dtype=np.int32).reshape(-1) for s in seqs]
+    flat = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+    return np.ascontiguousarray(flat if flat.size else np.zeros(1, np.int32))
 
 
 def _err():
@@ -714,17 +727,37 @@ class BiogptModel:
             raise BiogptError(_err())
         return out[:n].copy(), secs.value
 
-    def generate_greedy_batch(self, prompts, n_predict, n_batch=8):
-        """Batched decode of several independent prompts (list of id lists) on this device."""
+    def generate_greedy_batch(self, prompts, n_predict, n_batch=8, prefix=None):
+        """Batched decode of several independent prompts (list of id lists) on this device.  prefix: a list of ids that stands in front of every
+        prompt -- sequence s is prefix + prompts[s], and a prompt may then be empty.  The ids are those of the call on the concatenations; the
+        prefix is evaluated once ("Generation behind a shared prefix"; prefix_stats())."""
         lens = np.asarray([len(p) for p in prompts], dtype=np.int32)
+        secs = C.c_double(0.0)
+        if prefix is not None:
+            out = np.zeros((max(len(prompts), 1), max(int(n_predict), 1)), dtype=np.int32)
+            n_pre, pre = len(prefix), _flat_ids([prefix])
+            flat = _flat_ids(prompts)
+            n = lib().biogpt_hip_generate_greedy_prefix(self._h, pre.ctypes.data, n_pre, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_batch),
+                                                        int(n_predict), out.ctypes.data, C.byref(secs))
+            if n < 0:
+                raise BiogptError(_err())
+            return out.reshape(-1)[:len(prompts) * n].reshape(len(prompts), n).copy(), secs.value
         flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]))
         out = np.zeros((len(prompts), max(int(n_predict), 1)), dtype=np.int32)
-        secs = C.c_double(0.0)
         n = lib().biogpt_hip_generate_greedy_batch(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_batch),
                                                    int(n_predict), out.ctypes.data, C.byref(secs))
         if n < 0:
             raise BiogptError(_err())
         return out.reshape(-1)[:len(prompts) * n].reshape(len(prompts), n).copy(), secs.value
+
+    def prefix_stats(self):
+        """Of the last generate_greedy_batch / generate_sample with prefix= on this model: n_shared (prefix rows evaluated once), prompt_columns (all
+        prompt columns evaluated), path (the route of the decode steps -- 0: the launch chain, shared rows read in place; 1: column-per-XCD launches, shared
+        rows copied into every column's slot, also reported when n_shared is 0 and nothing was copied), columns."""
+        out = np.zeros(4, dtype=np.int32)
+        if lib().biogpt_hip_prefix_stats(self._h, out.ctypes.data) != 0:
+            raise BiogptError(_err())
+        return dict(n_shared=int(out[0]), prompt_columns=int(out[1]), path=int(out[2]), columns=int(out[3]))
 
     def generate_beam(self, prompt, n_predict, n_beams=5, eos_id=2, length_penalty=1.0, early_stopping=True, n_batch=8,
                       repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None):
@@ -847,18 +880,29 @@ class BiogptModel:
                 [dict(passes=int(st[p, 0]), drafted=int(st[p, 1]), accepted=int(st[p, 2])) for p in range(G)], secs.value)
 
     def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
-                        repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None):
+                        repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None, prefix=None):
         """n_samples sampled continuations of every prompt (list of id lists, or one flat id list), drawn on the device by the reference's top-k / top-p
         sampler (INTEGRATION.md, "Sampled generation").  Sequence p * n_samples + j is sample j of prompt p with std::mt19937(seeds[...]); seeds=None:
         seed + sequence index.  Returns ([ids int32[len], ...] in sequence order, seconds); an EOS that ended a sequence is included.  The last four arguments
         are transformers' logits processors of the same names, applied to the raw logits row in front of the sampler ("Generation
         rules"); top_k=1 never draws: greedy decoding with rules and an EOS.  trie: a Trie -- every row is masked to the tokens that continue an entry
-        (or EOS where one ends) in front of the sampler (biogpt_hip_generate_sample_trie; needs eos_id >= 0); top_k=1: constrained greedy decoding."""
+        (or EOS where one ends) in front of the sampler (biogpt_hip_generate_sample_trie; needs eos_id >= 0); top_k=1: constrained greedy decoding.
+        prefix: a list of ids in front of every prompt -- sequence p is prefix + prompts[p], a prompt may then be empty ([[]]: n_samples of the prefix
+        alone), the ids are those of the call on the concatenations and the prefix is evaluated once ("Generation behind a shared
+        prefix").  Not with rules or a trie: ValueError."""
+        if prefix is not None:
+            if trie is not None:
+                raise ValueError("prefix= cannot be combined with trie=")
+            if float(repetition_penalty) != 1.0 or int(no_repeat_ngram_size) != 0 or int(min_new_tokens) != 0 or len(suppress_tokens):
+                raise ValueError("prefix= cannot be combined with generation rules")
         rules, keep = gen_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
         if len(prompts) and np.isscalar(prompts[0]):
             prompts = [prompts]
         lens = np.asarray([len(p) for p in prompts], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]) if len(prompts) else np.zeros(0, np.int32))
+        if prefix is not None:
+            flat = _flat_ids(prompts)
+        else:
+            flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]) if len(prompts) else np.zeros(0, np.int32))
         n = len(prompts) * int(n_samples)
         if seeds is None:
             seeds = [(int(seed) + r) & 0xFFFFFFFF for r in range(max(n, 0))]
@@ -869,7 +913,12 @@ class BiogptModel:
         out = np.zeros((max(n, 1), w), dtype=np.int32)
         ol = np.zeros(max(n, 1), dtype=np.int32)
         secs = C.c_double(0.0)
-        if trie is not None:
+        if prefix is not None:
+            pre = _flat_ids([prefix])
+            got = lib().biogpt_hip_generate_sample_prefix(self._h, pre.ctypes.data, len(prefix), flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples),
+                                                          int(n_batch), int(n_predict), int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id),
+                                                          out.ctypes.data, ol.ctypes.data, C.byref(secs))
+        elif trie is not None:
             _no_rules_with_trie(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
             got = lib().biogpt_hip_generate_sample_trie(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples), int(n_batch), int(n_predict),
                                                         int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id), _trie_handle(trie), out.ctypes.data,

@@ -186,7 +186,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -215,6 +215,7 @@ struct EngineOptions {
         graph_contended = get("BIOGPT_HIP_GRAPH_CONTENDED", 0);   // test switch: replay the five-launch eval graph even while ANOTHER context holds the pipeline slot (the arrangement of profiles/two_contexts_r4.txt)
         fault_stale = get("BIOGPT_HIP_FAULT_STALE", 0);           // test switch: every k-th replayed eval starts from the PREVIOUS mailbox slot (the stale-row symptom, injected)
         proc_lock = get("BIOGPT_HIP_PROC_LOCK", 1);               // one process per device drives the pipelined launches (engine_xpipe.inc, xpipe_process_lock)
+        prefix_attn = get("BIOGPT_HIP_PREFIX_ATTN", -1);          // decode steps behind a shared prefix: -1 attn_prefix_kernel where it was measured faster (PREFIX_ATTN_MIN_*), 0 never, 1 always (A/B arms)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
     }
 };
@@ -222,10 +223,11 @@ struct EngineOptions {
 namespace {
 }  // namespace
 
-// The captured steps of one mode of column generation: [12 * (form of the step: 0 plain, 1 with rules, 2 with a trie) + 6 * (steps as column-per-XCD
-// launches) + context bucket], valid for the call shape (key_a, key_b) they were captured for -- sequences, or groups and beams
+// The captured steps of one mode of column generation: [12 * (form of the step: 0 plain, 1 with rules, 2 with a trie, 3 behind a shared prefix read in
+// place) + 6 * (steps as column-per-XCD launches) + context bucket], valid for the call shape (key_a, key_b) they were captured for -- sequences, or
+// groups and beams
 struct ColumnGraphs {
-    hipGraphExec_t exec[36] = {};
+    hipGraphExec_t exec[48] = {};
     int key_a = 0, key_b = 0;
 };
 
@@ -330,6 +332,7 @@ struct biogpt_hip_ctx {
     int state_n_past = 0, state_chunk = 0; // what the last upload_state put into the device state
     int64_t xc_launches = 0;               // evals that went through the chunk launch (biogpt_hip_chunk_launches)
     int32_t gen_launch_tokens[16] = {0}; int gen_launches = 0;   // the last biogpt_hip_generate_greedy: tokens of each multi-token pipelined launch (biogpt_hip_generate_launches)
+    int32_t prefix_stats[4] = {0, 0, 0, 0};   // of the last biogpt_hip_generate_*_prefix call that generated tokens: shared rows, prompt columns evaluated, path (0 in place, 1 copied), columns
     int xc_batch = 0;                      // a column generation call with 2 .. 8 columns holds the device's pipeline slot (choose_column_path): its decode steps run as column-per-XCD launches (streams mode)
     uint32_t *xp_ctl = nullptr;
     bgk::xp_u64 *xp_samp = nullptr;        // arg-max partials handed from token t to token t + 1 inside a multi-token launch
@@ -1035,6 +1038,13 @@ bool enqueue_xcols(biogpt_hip_ctx *c, int N, int t_max, bool streams = false) {
 // Measured cross-overs of the many-column paths (HISTORY.md §4.7 / §4.8): the chain runs on the int8 matrix cores from 48 columns in the decode
 // steps of many sequences and from 64 in passes (below, the 8-column VALU kernels are faster); a pass takes the grouped-query attention from
 // 80 columns, a decode step of many sequences the slim attention kernel from 48; one query beyond 256 keys spreads its head over the chip
+// attn_prefix_kernel<8> instead of attn_fast_kernel<.., SHARED> for a decode step behind a shared prefix: from this many columns and shared rows on.
+// (2026-10-19, tools/prefix_gen_bench.py --ab: the in-place call, 24 layers, 16-token suffixes + 64 tokens, the kernel never / always taken, grouped / existing.
+// 128 / 256 columns: 0.91 / 0.91 x behind 376 shared rows, 0.74 / 0.72 x behind 888, but 1.14 / 1.23 x behind 56.  16 / 48 / 64 columns: 1.70 / 1.42 / 1.36 x (56),
+// 1.77 / 1.29 / 1.20 x (376), 1.87 / 1.20 / 1.05 x (888): it loses everywhere below 128 columns.  Between 56 and 376 shared rows and between 64 and 128 columns the
+// call was not measured: the thresholds are the smallest measured wins.  Repeated stand-alone launches (--kernel, K / V in cache) flatter the kernel: there it
+// already wins at 64 columns with 8 own rows.  DESIGN.md 4.7 has the tables.)
+constexpr int PREFIX_ATTN_MIN_COLS = 128, PREFIX_ATTN_MIN_SHARED = 376;
 constexpr int MFMA_MIN_DECODE_COLS = 48, MFMA_MIN_PASS_COLS = 64, GROUPED_ATTN_MIN_COLS = 80, SLIM_ATTN_MIN_COLS = 48, SPLIT_ATTN_ABOVE_KEYS = 256;
 
 // ---- a forward pass, by name --------------------------------------------------------------------------------------------------------------
@@ -1063,11 +1073,13 @@ struct ForwardPass {
     Cols cols;
     Rows rows;
     HiddenStage hid;        // Rows::Hidden; with other rows and ln_out != null: the final-LayerNorm f32 rows of every column BESIDE those rows (contrastive search)
-    // Packed + All only (biogpt_hip_score_continuations): the columns read their first SeqState::pad[0] K / V rows from the slot SeqState::pad[1]
-    // (attn_fast_kernel<.., SHARED>), and only the columns from head_from on get logits (rows 0 .. n_cols - head_from of logits_all): the columns in
+    // Packed columns (biogpt_hip_score_continuations, the prompts of biogpt_hip_generate_*_prefix) and the decode steps behind a shared prefix
+    // (decode_step_shared): the columns read their first SeqState::pad[0] K / V rows from the slot SeqState::pad[1]
+    // (attn_fast_kernel<.., SHARED>); packed columns with logits: only the columns from head_from on get logits (rows 0 .. n_cols - head_from of logits_all): the columns in
     // front of them are prefix columns whose K / V rows alone matter
     bool shared_prefix;
     int head_from;
+    int shared_rows = 0;    // decode_step_shared
     const bgk::SeqState *col_states = nullptr;      // Packed: the column states where they are not c->cols (packed_verify)
 
     // the context's own columns
@@ -1077,6 +1089,14 @@ struct ForwardPass {
     static ForwardPass hidden(int n, int t_max, HiddenStage hs) { return {n, t_max, Cols::Context, Rows::Hidden, hs}; }
     // one decode step of n_seqs sequences, every sequence's row
     static ForwardPass decode_step(int n_seqs, int t_max) { return {n_seqs, t_max, Cols::PerSequence, Rows::All}; }
+    // the same behind a shared prefix: every sequence reads its first SeqState::pad[0] K / V rows in the slot SeqState::pad[1], where they were evaluated once
+    // shared_rows: how many, for the choice of the attention kernel alone -- the kernels read the number from the column states, so a captured step stays
+    // right (if not the fastest choice) for a call whose prefix has another length
+    static ForwardPass decode_step_shared(int n_seqs, int t_max, int shared_rows) {
+        ForwardPass p{n_seqs, t_max, Cols::PerSequence, Rows::All, HiddenStage{0, nullptr}, true};
+        p.shared_rows = shared_rows;
+        return p;
+    }
     // the same, and every sequence's hidden row into ln_out [n_seqs][d_model]
     static ForwardPass decode_step_hidden(int n_seqs, int t_max, float *ln_out) { return {n_seqs, t_max, Cols::PerSequence, Rows::All, HiddenStage{0, ln_out}}; }
     // packed columns (c->cols)
@@ -1187,7 +1207,11 @@ bool enqueue_attention(PassLaunch &k, int l) {
         return true;
     }
     const bool slim = batch && N >= SLIM_ATTN_MIN_COLS;
-    if (k.pass.shared_prefix) launch_attn_fast<true>(a, slim, H, N, st);
+    // a decode step behind ONE shared prefix: eight columns per workgroup load a shared row once
+    const bool grouped = k.pass.shared_prefix && k.pass.cols == ForwardPass::Cols::PerSequence && a.t_cap <= bgk::PFX_MAX_KEYS &&
+                         (c->opt.prefix_attn < 0 ? N >= PREFIX_ATTN_MIN_COLS && k.pass.shared_rows >= PREFIX_ATTN_MIN_SHARED : c->opt.prefix_attn == 1);
+    if (grouped) hipLaunchKernelGGL((bgk::attn_prefix_kernel<8>), dim3(H, (N + 7) / 8), dim3(512), 0, st, a);
+    else if (k.pass.shared_prefix) launch_attn_fast<true>(a, slim, H, N, st);
     else launch_attn_fast<false>(a, slim, H, N, st);
     return true;
 }
@@ -2304,9 +2328,12 @@ static bool flush_columns(biogpt_hip_ctx *ctx, std::vector<bgk::SeqState> &cols,
 // column that knows its sequence, its position and the end of its own n_batch-chunk (SeqState::seq_id / n_past / t_vis); whole
 // chunks are packed into passes of up to BIOGPT_HIP_PROMPT_COLS columns (at most n_positions: the activation scratch).  The columns
 // follow the flat order of `seqs`.  Per pass the column states go to ctx->cols, then pass(n_cols, t_max, flat0) enqueues the pass
-// (flat0 = flat index of its first token).  Sequence s fills the K / V cache slot s * slot_stride.
+// (flat0 = flat index of its first token).  Sequence s fills the K / V cache slot slot0 + s * slot_stride.  shared.n > 0: every sequence stands behind
+// shared.n rows that lie in slot shared.slot (a multiple of n_batch, so the chunks are those of the whole sequence): its first token has position shared.n
+// and its columns read those rows in place (SeqState::pad[0] / pad[1]; the pass is ForwardPass::packed_continuations).
+struct SharedRows { int n = 0, slot = 0; };
 static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int n_seqs, int n_batch,
-                               const std::function<bool(int, int, size_t)> &pass, int slot_stride = 1) {
+                               const std::function<bool(int, int, size_t)> &pass, int slot_stride = 1, int slot0 = 0, SharedRows shared = SharedRows{}) {
     const int max_cols = std::min(std::max(std::max(1, ctx->opt.prompt_cols), n_batch), hp_cols(ctx));   // the activation scratch holds n_positions columns
     std::vector<bgk::SeqState> cols;
     int pass_tmax = 0;
@@ -2320,10 +2347,11 @@ static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const i
             if (!cols.empty() && (int)cols.size() + m > max_cols && !flush()) return false;
             for (int i = 0; i < m; i++) {
                 bgk::SeqState cst{};
-                cst.n_past = at + i; cst.token = seqs[off + (size_t)(at + i)]; cst.seq_id = s * slot_stride; cst.t_vis = at + m;
+                cst.n_past = shared.n + at + i; cst.token = seqs[off + (size_t)(at + i)]; cst.seq_id = slot0 + s * slot_stride; cst.t_vis = shared.n + at + m;
+                cst.pad[0] = shared.n; cst.pad[1] = shared.slot;
                 cols.push_back(cst);
             }
-            pass_tmax = std::max(pass_tmax, at + m);
+            pass_tmax = std::max(pass_tmax, shared.n + at + m);
         }
         off += (size_t)len;
     }
@@ -2383,6 +2411,13 @@ struct ColumnCall {
     int key_stride = 1;                 // positions a column can move on in one step, at most (prompt-lookup decoding: 1 + max_draft); > 1: the word behind
                                         // live_dev holds the furthest position of any column
     bool plain_steps = false;           // the step is no decode step of one column per sequence: never the column-per-XCD launches
+    // A shared prefix (biogpt_hip_generate_*_prefix): sequence p is prefix ++ prompt p, and a prompt may be empty.  The first n_shared prefix rows are evaluated
+    // once, into the slot behind the columns' (index n_prompts * per_prompt).  in_place: the steps read them there (the step is
+    // ForwardPass::decode_step_shared); otherwise -- steps as column-per-XCD launches -- they are copied into every column's slot before the first step.
+    const int32_t *prefix = nullptr;
+    int n_prefix = 0;
+    int n_shared = 0;                   // set by run_column_call, as in_place: the largest multiple of n_batch <= n_prefix - 1
+    bool in_place = false;
     // set by run_column_call before any callable runs: the tokens to generate as clamped, the longest prompt, all prompt tokens
     int n_predict = 0, max_len = 0;
     long total = 0;
@@ -2417,11 +2452,12 @@ static bool check_fast_chain(const biogpt_hip_ctx *c, const char *what) {
 }
 
 // the device, the caches and the logits rows of n_seqs columns; `total` prompt tokens go through the prompt pass
-static bool begin_column_call(biogpt_hip_ctx *ctx, int n_seqs, long total) {
+// (n_slots: n_seqs, and one more for a shared prefix)
+static bool begin_column_call(biogpt_hip_ctx *ctx, int n_slots, int n_seqs, long total) {
     HIP_TRY(false, hipSetDevice(ctx->device));
     if (!resident_stop(ctx)) return false;
     disarm_lineage(ctx);
-    if (!ensure_seq_caches(ctx, n_seqs)) return false;
+    if (!ensure_seq_caches(ctx, n_slots)) return false;
     // matrix-core chain: decode steps have n_seqs columns, the prompt pass all prompt tokens; build the tiled weights before any graph capture
     if (std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return false;
     return ensure_logits_rows(ctx, (size_t)n_seqs);
@@ -2442,13 +2478,16 @@ static void fill_column_starts(bgk::SeqState *hs, int p, int per_prompt, int n_p
         st.n_past = n_prompt - 1; st.token = last_token; st.seq_id = p * per_prompt + j;
     }
 }
-static bool upload_column_starts(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *lens, int n_prompts, int per_prompt) {
+// pos0: the position of every prompt's first token (rows in front of it: a shared prefix); shared: the rows the steps read in another slot (none: {})
+static bool upload_column_starts(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *lens, int n_prompts, int per_prompt, int pos0 = 0,
+                                 SharedRows shared = SharedRows{}) {
     std::vector<bgk::SeqState> hs((size_t)n_prompts * per_prompt);
     size_t o = 0;
     for (int p = 0; p < n_prompts; p++) {
         o += (size_t)lens[p];
-        fill_column_starts(hs.data(), p, per_prompt, lens[p], prompts[o - 1]);
+        fill_column_starts(hs.data(), p, per_prompt, pos0 + lens[p], prompts[o - 1]);
     }
+    for (bgk::SeqState &st : hs) { st.pad[0] = shared.n; st.pad[1] = shared.n > 0 ? shared.slot : 0; }
     HIP_TRY(false, hipMemcpy(ctx->seq, hs.data(), sizeof(bgk::SeqState) * hs.size(), hipMemcpyHostToDevice));
     return true;
 }
@@ -2496,18 +2535,71 @@ static bool capture_column_steps(biogpt_hip_ctx *ctx, ColumnGraphs &graphs, int 
 // Prompt ingestion for ALL prompts together (main.cpp:129-137 per prompt), packed into common passes (pack_column_passes): prompt p fills the cache slot of
 // its first column, kv_share_kernel copies its rows to its other per_prompt - 1 slots.  The pass only has to fill the K / V caches: the first step
 // re-evaluates each prompt's LAST token (same K / V row, same visible keys as its chunk gave it).
-static bool ingest_column_prompts(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *lens, int n_prompts, int n_batch, int per_prompt,
-                                  float *hidden_store = nullptr) {
+// A shared prefix (shared.n > 0 rows of `prefix`): those rows go once into slot shared.slot, as the prompt columns of one sequence; `prompts` are then the
+// sequences' tokens from position shared.n on, packed columns that read the shared rows where they lie.  Steps that know one slot per column (!cc.in_place):
+// kv_prefix_copy_kernel then copies the shared rows into every column's slot.  kv_share_kernel copies a prompt's own rows only, on either path.
+// prompts / lens: the call's prompts, or behind a prefix what follows the shared rows.
+static bool ingest_column_prompts(biogpt_hip_ctx *ctx, const ColumnCall &cc, const int32_t *prompts, const int32_t *lens, SharedRows shared) {
     const auto &hp = ctx->hp;
+    const int n_prompts = cc.n_prompts, n_batch = cc.n_batch, per_prompt = cc.per_prompt;
+    float *const hidden_store = cc.hidden_store;
+    const int32_t *const prefix = cc.prefix;
+    const bool copy_shared = !cc.in_place;
+    const int64_t seq_stride = (int64_t)hp.n_layer * hp.n_positions * hp.d_model;
+    if (shared.n > 0) {
+        const int32_t n = shared.n;
+        if (!pack_column_passes(ctx, prefix, &n, 1, n_batch, [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); },
+                                1, shared.slot))
+            return false;
+    }
     if (!pack_column_passes(ctx, prompts, lens, n_prompts, n_batch,
-                            [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts_hidden(n_cols, t_max, hidden_store, per_prompt)); },
-                            per_prompt))
+                            [&](int n_cols, int t_max, size_t) {
+                                return enqueue_forward(ctx, shared.n > 0 ? ForwardPass::packed_continuations(n_cols, t_max, n_cols)
+                                                                         : ForwardPass::packed_prompts_hidden(n_cols, t_max, hidden_store, per_prompt));
+                            },
+                            per_prompt, 0, shared))
         return false;
     if (per_prompt > 1) {
-        hipLaunchKernelGGL(bgk::kv_share_kernel, dim3(hp.n_layer * hp.n_head, n_prompts * per_prompt, 2), dim3(256), 0, ctx->stream, ctx->seq, per_prompt, ctx->bk, ctx->bv,
-                           (int64_t)hp.n_layer * hp.n_positions * hp.d_model, hp.n_positions, hp.d_model / hp.n_head);
+        hipLaunchKernelGGL(bgk::kv_share_kernel, dim3(hp.n_layer * hp.n_head, n_prompts * per_prompt, 2), dim3(256), 0, ctx->stream, ctx->seq, per_prompt, shared.n, ctx->bk, ctx->bv,
+                           seq_stride, hp.n_positions, hp.d_model / hp.n_head);
         HIP_TRY(false, hipGetLastError());
     }
+    if (shared.n > 0 && copy_shared) {
+        hipLaunchKernelGGL(bgk::kv_prefix_copy_kernel, dim3(hp.n_layer * hp.n_head, n_prompts * per_prompt, 2), dim3(256), 0, ctx->stream, shared.n, shared.slot, ctx->bk, ctx->bv,
+                           seq_stride, hp.n_positions, hp.d_model / hp.n_head);
+        HIP_TRY(false, hipGetLastError());
+    }
+    return true;
+}
+
+// The prompts of a call behind a shared prefix, checked: the prefix is not empty, a suffix may be, every token is valid and every sequence fits the position
+// table.  eff / eff_lens: every sequence's tokens from position n_shared on (prefix[n_shared:] ++ suffix, never empty).
+static bool prefix_prompts(const biogpt_hip_ctx *c, ColumnCall &cc, std::vector<int32_t> &eff, std::vector<int32_t> &eff_lens) {
+    const int P = c->hp.n_positions, V = c->hp.n_vocab;
+    if (cc.n_prefix < 1) BG_FAIL(false, "n_prefix must be >= 1 (got %d)", cc.n_prefix);
+    if (cc.n_prefix > P) BG_FAIL(false, "n_prefix (%d) exceeds n_positions (%d)", cc.n_prefix, P);
+    for (int i = 0; i < cc.n_prefix; i++)
+        if (cc.prefix[i] < 0 || cc.prefix[i] >= V) BG_FAIL(false, "token id %d (prefix, position %d) out of range [0, %d)", cc.prefix[i], i, V);
+    cc.n_shared = (cc.n_prefix - 1) / cc.n_batch * cc.n_batch;
+    const int own = cc.n_prefix - cc.n_shared;
+    size_t off = 0;
+    int max_suffix = 0;
+    for (int p = 0; p < cc.n_prompts; p++) {
+        const int len = cc.prompt_lens[p];
+        if (len < 0) BG_FAIL(false, "suffix_lens[%d] (%d) is negative", p, len);
+        if (len > P - cc.n_prefix) BG_FAIL(false, "n_prefix (%d) + suffix_lens[%d] (%d) exceeds n_positions (%d)", cc.n_prefix, p, len, P);
+        for (int i = 0; i < len; i++) {
+            const int32_t t = cc.prompts[off + (size_t)i];
+            if (t < 0 || t >= V) BG_FAIL(false, "token id %d (%s %d, position %d) out of range [0, %d)", t, cc.unit, p, i, V);
+        }
+        eff.insert(eff.end(), cc.prefix + cc.n_shared, cc.prefix + cc.n_prefix);
+        eff.insert(eff.end(), cc.prompts + off, cc.prompts + off + (size_t)len);
+        eff_lens.push_back(own + len);
+        max_suffix = std::max(max_suffix, len);
+        off += (size_t)len;
+    }
+    cc.max_len = cc.n_prefix + max_suffix;
+    cc.total = (long)cc.n_shared + (long)eff.size();
     return true;
 }
 
@@ -2545,22 +2637,33 @@ static bool run_column_steps(biogpt_hip_ctx *ctx, const ColumnGraphs &graphs, in
 // The one order of a column call.  Returns the tokens to generate as clamped (> 0) once every step has run and the stream has drained; 0: the longest prompt
 // leaves no room (nothing was touched); -1: a bad prompt; -2: a failure.
 static int run_column_call(biogpt_hip_ctx *ctx, ColumnCall &cc, int n_predict, double *seconds_out) {
-    if (!check_prompts(ctx, cc.prompts, cc.prompt_lens, cc.n_prompts, cc.unit, &cc.max_len, &cc.total)) return -1;
+    // behind a prefix the call's prompts are what follows the shared rows; max_len stays the longest whole sequence
+    std::vector<int32_t> eff, eff_lens;
+    const int32_t *prompts = cc.prompts, *lens = cc.prompt_lens;
+    if (cc.prefix) {
+        if (!prefix_prompts(ctx, cc, eff, eff_lens)) return -1;
+        prompts = eff.data(); lens = eff_lens.data();
+    } else if (!check_prompts(ctx, cc.prompts, cc.prompt_lens, cc.n_prompts, cc.unit, &cc.max_len, &cc.total)) {
+        return -1;
+    }
     cc.n_predict = std::min(n_predict, ctx->hp.n_positions - cc.max_len);  // main.cpp:82, for the longest prompt
     if (cc.n_predict <= 0) return 0;
     const int n_seqs = cc.n_prompts * cc.per_prompt, n_steps = cc.n_predict + cc.extra_steps;
-    if (!begin_column_call(ctx, n_seqs, cc.total)) return -2;
+    const SharedRows shared{cc.n_shared, n_seqs};       // (n_shared == 0: nothing is shared and every launch is that of the call without a prefix)
+    if (!begin_column_call(ctx, n_seqs + (cc.prefix ? 1 : 0), n_seqs, cc.total)) return -2;
     if (cc.prepare && !cc.prepare()) return -2;      // buffers grow and graphs drop BEFORE the key is looked at: a captured step never holds a freed pointer
     column_graphs_for(*cc.graphs, cc.key_a, cc.key_b);
-    if (!upload_column_starts(ctx, cc.prompts, cc.prompt_lens, cc.n_prompts, cc.per_prompt)) return -2;
+    const int xc = cc.plain_steps ? 0 : choose_column_path(ctx, n_seqs, cc.max_len);
+    cc.in_place = cc.n_shared > 0 && xc == 0;
+    if (!upload_column_starts(ctx, prompts, lens, cc.n_prompts, cc.per_prompt, cc.n_shared, cc.in_place ? shared : SharedRows{})) return -2;
     if (cc.upload && !cc.upload()) return -2;
-    const int gset = (cc.plain_steps ? 0 : 6 * choose_column_path(ctx, n_seqs, cc.max_len)) + cc.gset_extra;
+    const int gset = 6 * xc + (cc.in_place ? 36 : cc.gset_extra);
     const ColumnKeys keys{cc.max_len, cc.key_stride, ctx->hp.n_positions};
     bool use_graph;
     if (!capture_column_steps(ctx, *cc.graphs, gset, keys, n_steps, cc.step, &use_graph)) return -2;
 
     const auto t0 = std::chrono::steady_clock::now();
-    if (!ingest_column_prompts(ctx, cc.prompts, cc.prompt_lens, cc.n_prompts, cc.n_batch, cc.per_prompt, cc.hidden_store)) return -2;
+    if (!ingest_column_prompts(ctx, cc, prompts, lens, shared)) return -2;
     if (cc.after_ingest && !cc.after_ingest()) return -2;
     if (!run_column_steps(ctx, *cc.graphs, gset, use_graph, keys, n_steps, cc.step, cc.live_dev)) return -2;
     if (cc.before_sync && !cc.before_sync()) return -2;
@@ -2568,14 +2671,19 @@ static int run_column_call(biogpt_hip_ctx *ctx, ColumnCall &cc, int n_predict, d
     const auto t1 = std::chrono::steady_clock::now();
     if (!xpipe_check(ctx)) return -2;      // (steps as column-per-XCD launches: a disturbed one spoils the run -- the mode's caller repeats it on the launch chain)
     if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    // (a call that failed, or whose n_predict clamped to 0, leaves the stats of the last call that generated)
+    if (cc.prefix) { ctx->prefix_stats[0] = cc.n_shared; ctx->prefix_stats[1] = (int32_t)cc.total; ctx->prefix_stats[2] = xc; ctx->prefix_stats[3] = n_seqs; }
     return cc.n_predict;
 }
 
+// prefix != null (biogpt_hip_generate_greedy_prefix): sequence s is prefix ++ prompt s, the prompts are suffixes and may be empty
 static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_seqs,
-                                      int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out) {
+                                      int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out, const int32_t *prefix = nullptr, int32_t n_prefix = 0) {
     clear_error();
     if (!ctx || !prompts || !prompt_lens || !out_ids) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (prefix && (n_seqs < 1 || n_seqs > 511)) BG_FAIL(-1, "n_seqs must be in [1, 511] behind a prefix (got %d)", n_seqs);   // one slot holds the prefix
+    if (prefix && !check_fast_chain(ctx, "generation behind a shared prefix")) return -1;
     if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");   // activation buffers hold n_positions >= 512 columns; each sequence owns a full F32 KV cache
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_seqs (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
     if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
@@ -2584,8 +2692,9 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     cc.prompts = prompts; cc.prompt_lens = prompt_lens; cc.unit = "sequence";
     cc.n_prompts = n_seqs; cc.n_batch = n_batch;
     cc.graphs = &ctx->graphs_greedy; cc.key_a = n_seqs;
+    cc.prefix = prefix; cc.n_prefix = n_prefix;
     cc.step = [&](int t_max) -> bool {      // every step's arg-max is the next token
-        if (!enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max))) return false;
+        if (!enqueue_forward(ctx, cc.in_place ? ForwardPass::decode_step_shared(n_seqs, t_max, cc.n_shared) : ForwardPass::decode_step(n_seqs, t_max))) return false;
         hipLaunchKernelGGL(bgk::argmax_rows_kernel, dim3(n_seqs), dim3(bgk::ARGMAX_ROWS_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->seq, 0, ctx->seq_gen, P, 1);
         HIP_TRY(false, hipGetLastError());
         return true;
@@ -2600,6 +2709,31 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
 int biogpt_hip_generate_greedy_batch(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_seqs,
                                      int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out) {
     return with_xpipe_retry(ctx, 0, [&] { return generate_greedy_batch_once(ctx, prompts, prompt_lens, n_seqs, n_batch, n_predict, out_ids, seconds_out); });
+}
+
+// ---- generation behind a shared prefix: the prefix's first n_shared rows evaluated once, read in place by every sequence (or copied, 2 .. 8 columns) ----
+static bool check_prefix_pointers(const biogpt_hip_ctx *ctx, const int32_t *prefix, const int32_t *suffixes, const int32_t *suffix_lens) {
+    clear_error();
+    if (!ctx) BG_FAIL(false, "null context");
+    if (!prefix) BG_FAIL(false, "null argument: prefix");
+    if (!suffixes) BG_FAIL(false, "null argument: suffixes");
+    if (!suffix_lens) BG_FAIL(false, "null argument: suffix_lens");
+    return true;
+}
+int biogpt_hip_generate_greedy_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes, const int32_t *suffix_lens, int32_t n_seqs,
+                                      int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out) {
+    if (!check_prefix_pointers(ctx, prefix, suffixes, suffix_lens)) return -1;
+    if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_greedy_batch_once(ctx, suffixes, suffix_lens, n_seqs, n_batch, n_predict, out_ids, seconds_out, prefix, n_prefix);
+    });
+}
+int biogpt_hip_prefix_stats(const biogpt_hip_ctx *ctx, int32_t out[4]) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!out) BG_FAIL(-1, "null argument: out");
+    std::memcpy(out, ctx->prefix_stats, sizeof(ctx->prefix_stats));
+    return 0;
 }
 
 // ---- sequence scoring: teacher-forced causal passes, the log-softmax of every row on the device (kernels_score.hip.h) ----------------
@@ -3173,11 +3307,14 @@ static bgk::SampleCtl sample_ctl_of(int top_k, int eos_id, int n_seqs, double to
 
 static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
                                 int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
-                                int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules, biogpt_hip_trie *trie = nullptr) {
+                                int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules, biogpt_hip_trie *trie = nullptr,
+                                const int32_t *prefix = nullptr, int32_t n_prefix = 0) {
     clear_error();
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompts || !prompt_lens || !seeds || !out_ids || !out_lens) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (prefix && (n_prompts < 1 || n_samples < 1 || (int64_t)n_prompts * n_samples > 511))
+        BG_FAIL(-1, "n_prompts x n_samples must be in [1, 511] behind a prefix");   // one slot holds the prefix
     if (n_prompts < 1 || n_samples < 1 || (int64_t)n_prompts * n_samples > 512) BG_FAIL(-1, "n_prompts x n_samples must be in [1, 512]");   // each sequence owns a full F32 KV cache
     const int n_seqs = n_prompts * n_samples;
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_prompts x n_samples (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
@@ -3197,6 +3334,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     cc.n_prompts = n_prompts; cc.per_prompt = n_samples; cc.n_batch = n_batch;
     cc.graphs = &ctx->graphs_sample; cc.key_a = n_seqs;
     cc.gset_extra = trie ? 24 : ru ? 12 : 0;
+    cc.prefix = prefix; cc.n_prefix = n_prefix;     // (prefix != null, biogpt_hip_generate_sample_prefix: the prompts are suffixes and may be empty; no rules, no trie)
     cc.prepare = [&]() -> bool {
         if (n_seqs > ctx->sample_cap) {
             if (ctx->sample_ctl) (void)hipFree(ctx->sample_ctl);
@@ -3219,7 +3357,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
         return !ru || rules_upload(ctx, rules, 0, eos_id, prompts, prompt_lens, n_prompts, n_samples);
     };
     cc.step = [&](int t_max) -> bool {
-        if (!enqueue_forward(ctx, ForwardPass::decode_step(n_seqs, t_max))) return false;
+        if (!enqueue_forward(ctx, cc.in_place ? ForwardPass::decode_step_shared(n_seqs, t_max, cc.n_shared) : ForwardPass::decode_step(n_seqs, t_max))) return false;
         if (ru && !enqueue_rules(ctx, n_seqs, &sb.seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
         if (trie && !enqueue_trie(ctx, n_seqs, &sb.seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
         hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, sb.ctl, sb.seq, ctx->seq, ctx->seq_gen, P);
@@ -3254,6 +3392,17 @@ int biogpt_hip_generate_sample_rules(biogpt_hip_ctx *ctx, const int32_t *prompts
                                      int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules) {
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, rules);
+    });
+}
+
+// biogpt_hip_generate_sample of the sequences prefix ++ suffix_p behind the shared prefix rows; no rules, no trie
+int biogpt_hip_generate_sample_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes, const int32_t *suffix_lens, int32_t n_prompts,
+                                      int32_t n_samples, int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
+                                      int32_t *out_ids, int32_t *out_lens, double *seconds_out) {
+    if (!check_prefix_pointers(ctx, prefix, suffixes, suffix_lens)) return -1;
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_sample_once(ctx, suffixes, suffix_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, nullptr,
+                                    nullptr, prefix, n_prefix);
     });
 }
 

@@ -180,6 +180,94 @@ int biogpt_hip_trie_rows_bench(int device, biogpt_hip_trie *trie, int32_t mode, 
     return trie_rows_device(device, trie, mode, rows, n_rows, n_vocab, hist, hist_lens, eos_id, rows_out, reps, us_out);
 }
 
+// One decode attention launch over caller-supplied inputs: N columns behind a shared prefix, head size 64, one layer.  q [N][H * 64]; k_slots / v_slots
+// [N + 1][H][P][64]: slot i is column i's own, slot N the prefix's; seq_states [N] SeqState (n_past, pad[0] = shared rows, pad[1] = their slot; column i = slot i).
+// which 0: attn_fast_kernel<4, false, true> as a slim launch; 1: attn_prefix_kernel<8> (then pad[0] / pad[1] must be the same for every column).  q8 0: f32 rows
+// only; 1 / 2: also the Q8_0 / Q8_1 blocks of the rows (out_q [N][H * 64], out_d / out_s [N][H * 2]).  reps > 0: the launch repeated, us_out[i] microseconds
+// between two events around launch i alone -- a repeated stand-alone launch finds its K / V rows in cache.
+static int attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
+                              const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps, float *us_out) {
+    clear_error();
+    if (!q || !k_slots || !v_slots || !seq_states || !out) BG_FAIL(-1, "q, k_slots, v_slots, seq_states or out is NULL");
+    if (H < 1 || H > 64) BG_FAIL(-1, "H must be in [1, 64]");
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (P < 1 || P > bgk::PFX_MAX_KEYS) BG_FAIL(-1, "P must be in [1, %d]", bgk::PFX_MAX_KEYS);
+    if (t_cap < 1 || t_cap > P) BG_FAIL(-1, "t_cap must be in [1, P]");
+    if (which != 0 && which != 1) BG_FAIL(-1, "which must be 0 (attn_fast_kernel<4, false, true>) or 1 (attn_prefix_kernel<8>)");
+    if (q8 < 0 || q8 > 2 || (q8 > 0 && (!out_q || !out_d || !out_s))) BG_FAIL(-1, "q8 must be 0, 1 or 2, with out_q, out_d and out_s");
+    if (reps < 0 || reps > 10000 || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, 10000], with us_out");
+    static_assert(sizeof(bgk::SeqState) == 32, "eight words per column state");
+    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
+    for (int i = 0; i < N; i++) {
+        if (hs[i].n_past < 0 || hs[i].n_past >= t_cap) BG_FAIL(-1, "column %d: n_past %d outside [0, t_cap)", i, hs[i].n_past);
+        if (hs[i].pad[0] < 0 || hs[i].pad[0] > hs[i].n_past) BG_FAIL(-1, "column %d: %d shared rows outside [0, n_past]", i, hs[i].pad[0]);
+        if (hs[i].pad[1] < 0 || hs[i].pad[1] > N) BG_FAIL(-1, "column %d: shared slot %d outside [0, N]", i, hs[i].pad[1]);
+        if (which == 1 && (hs[i].pad[0] != hs[0].pad[0] || hs[i].pad[1] != hs[0].pad[1])) BG_FAIL(-1, "column %d: attn_prefix_kernel needs one shared range for all columns", i);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    const int D = H * 64;
+    const size_t slot = (size_t)H * P * 64, kv_b = slot * 4 * (size_t)(N + 1), row_b = (size_t)N * D * 4, blk = (size_t)N * (D / 32);
+    ByteLayout l;
+    const size_t o_k = l.part(kv_b), o_v = l.part(kv_b), o_q = l.part(row_b), o_st = l.part(sizeof(bgk::SeqState) * (size_t)N), o_tab = l.part(65536 * 2), o_out = l.part(row_b),
+                 o_oq = l.part((size_t)N * D), o_od = l.part(blk * 4), o_os = l.part(blk * 4);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    std::vector<uint16_t> te(65536);
+    for (uint32_t i = 0; i < 65536; i++) te[i] = f32_to_f16(expf(f16_to_f32((uint16_t)i)));      // the table of the model loader
+    HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_q, q, row_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_tab, te.data(), 65536 * 2, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));
+    bgk::AttnParams a{};
+    a.q = d.at<const float>(o_q); a.kcache = d.at<const float>(o_k); a.vcache = d.at<const float>(o_v); a.out = d.at<float>(o_out);
+    a.exp_tab = d.at<const uint16_t>(o_tab);
+    a.N = N; a.D = D; a.dk = 64; a.P = P; a.t_cap = t_cap;
+    a.seq = d.at<const bgk::SeqState>(o_st); a.col_mode = 0; a.kv_seq_stride = (int64_t)slot;
+    a.q81 = q8 == 2 ? 1 : 0;
+    if (q8 > 0) { a.oq_q = d.at<int8_t>(o_oq); a.oq_d = d.at<float>(o_od); a.oq_s = d.at<uint32_t>(o_os); }
+    auto launch = [&] {
+        if (which == 1) hipLaunchKernelGGL((bgk::attn_prefix_kernel<8>), dim3(H, (N + 7) / 8), dim3(512), 0, 0, a);
+        else hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, true>), dim3(H, N), dim3(std::max(256, (t_cap + 63) & ~63)), 0, 0, a);
+    };
+    launch();
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, row_b, hipMemcpyDeviceToHost));
+    if (q8 > 0) {
+        HIP_TRY(-2, hipMemcpy(out_q, d.p + o_oq, (size_t)N * D, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(out_d, d.p + o_od, blk * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(out_s, d.p + o_os, blk * 4, hipMemcpyDeviceToHost));
+    }
+    if (reps > 0) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIP_TRY(-2, hipEventCreate(&e0));
+        HIP_TRY(-2, hipEventCreate(&e1));
+        bool ok = true;
+        for (int i = 0; i < reps && ok; i++) {
+            ok = hipEventRecord(e0, 0) == hipSuccess;
+            launch();
+            ok = ok && hipEventRecord(e1, 0) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
+            float ms = 0.0f;
+            ok = ok && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+            us_out[i] = ms * 1000.0f;
+        }
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        if (!ok) BG_FAIL(-2, "a timed attention launch failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+}
+int biogpt_hip_attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
+                                  const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s) {
+    return attn_prefix_device(device, H, N, P, t_cap, q, k_slots, v_slots, seq_states, which, q8, out, out_q, out_d, out_s, 0, nullptr);
+}
+int biogpt_hip_attn_prefix_bench(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
+                                 const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps, float *us_out) {
+    if (reps < 1) { clear_error(); BG_FAIL(-1, "reps must be in [1, 10000]"); }
+    return attn_prefix_device(device, H, N, P, t_cap, q, k_slots, v_slots, seq_states, which, q8, out, out_q, out_d, out_s, reps, us_out);
+}
+
 // logprob_rows_kernel over rows held in host memory (tests of the kernel itself): ldl = n_vocab, so an odd n_vocab puts rows 1, 2, 3 on the other
 // 16-byte alignments
 int biogpt_hip_logprob_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *targets, float *lp_out, int32_t *argmax_out,

@@ -576,6 +576,155 @@ __global__ __launch_bounds__(1024) void attn_fast_kernel(const AttnParams p) {
 #undef AT_DBG
 }
 
+// ---- decode attention of columns behind ONE shared prefix, eight columns per workgroup -------------------
+// A decode step behind a shared prefix (ForwardPass::decode_step_shared): every column reads the same rows [0, n_shared) of the prefix slot and a few rows
+// of its own.  One workgroup per (head, column) requests each shared K / V row once per column; here a workgroup serves G = 8 columns of one head and
+// loads a shared row ONCE for all of them.  Grid (H, ceil(N / G)), 512 threads = 8 waves; column c0 + q is query q, at its own position.
+//   scores, shared   4 lanes per key, 128 keys per sweep: a K row is loaded once and scored against the 8 queries (LDS), attn_fast_kernel's arithmetic
+//                    per (key, query): __fmul_rn products, four double accumulators, quad DPP reduce
+//   scores, own      wave q: query q's rows [n_shared, T_q) from its own slot, 16 keys per sweep
+//   softmax          wave q: query q -- maximum, fp16-table exponent, double row sum (a sum of fp16 values: exact in any order), p = fl(e * inv_sum_f32(sum))
+//   PV               thread (slice s of 8, dim d): a shared V row is loaded once and goes into 8 double accumulators; own rows per query; the 8 slices are
+//                    combined through LDS (the area of the scores) by wave q, which stores query q through store_head_output
+// n_shared and the prefix slot are read from the group's first column (SeqState::pad[0] / pad[1]: the same for every column of such a step, never a launch
+// parameter).  Every load is bounded by min(t_cap, P, PFX_MAX_KEYS) through T_q and n_shared; columns beyond N are masked (wave-uniform).  The per-element
+// arithmetic is attn_fast_kernel's; only the association of the double PV sums differs (8 slices here).
+constexpr int PFX_MAX_KEYS = 1024;      // scores [keys][G] floats in LDS: 32 KB
+
+template <int G>
+__global__ __launch_bounds__(512) void attn_prefix_kernel(const AttnParams p) {
+    static_assert(G == 8, "eight columns, one per wave");
+    constexpr int DK = 64;
+    __shared__ __attribute__((aligned(16))) float S[PFX_MAX_KEYS * G];      // scores, then probabilities [key][query]; afterwards the PV partials [slice][query][dim] doubles
+    __shared__ __attribute__((aligned(16))) float Q[G * DK];
+    __shared__ int Tq[G];
+    static_assert(sizeof(float) * PFX_MAX_KEYS * G >= sizeof(double) * 8 * G * DK, "the PV partials fit the score area");
+    const int h = blockIdx.x, c0 = blockIdx.y * G;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int cap = min(min(p.t_cap, p.P), PFX_MAX_KEYS);
+    const size_t head = (size_t)h * p.P * DK;
+    const int n_shared = max(0, min(p.seq[c0].pad[0], cap));
+    const size_t shr_off = (size_t)p.seq[c0].pad[1] * p.kv_seq_stride;
+
+    // ---- queries and their visible keys into LDS (a column beyond N: no keys) ----
+    {
+        const int c = c0 + wv;
+        Q[wv * DK + lane] = c < p.N ? p.q[(size_t)c * p.D + (size_t)h * DK + lane] : 0.0f;
+        if (lane == 0) Tq[wv] = c < p.N ? max(0, min(p.col_mode ? p.seq[c].t_vis : p.seq[c].n_past + 1, cap)) : 0;
+    }
+    __syncthreads();
+
+    const int ksub = tid & 3;
+    // ---- scores over the shared rows: lane ksub of a quad owns float4 #(4m + ksub) of the key row ----
+    {
+        const float4 *kshr = reinterpret_cast<const float4 *>(p.kcache + shr_off + head) + ksub;
+        for (int j = tid >> 2; j < n_shared; j += 128) {
+            float4 kr[4];
+#pragma unroll
+            for (int m = 0; m < 4; m++) kr[m] = kshr[(size_t)j * (DK / 4) + 4 * m];
+#pragma unroll
+            for (int q = 0; q < G; q++) {
+                const float4 *qp = reinterpret_cast<const float4 *>(Q + q * DK) + ksub;
+                double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+                for (int m = 0; m < 4; m++) {
+                    const float4 qv = qp[4 * m];
+                    a0 += (double)__fmul_rn(kr[m].x, qv.x); a1 += (double)__fmul_rn(kr[m].y, qv.y);
+                    a2 += (double)__fmul_rn(kr[m].z, qv.z); a3 += (double)__fmul_rn(kr[m].w, qv.w);
+                }
+                double acc = (a0 + a1) + (a2 + a3);
+                acc += dpp_d<DPP_QUAD_XOR1>(acc);
+                acc += dpp_d<DPP_QUAD_XOR2>(acc);
+                if (ksub == 0) S[j * G + q] = (float)acc;
+            }
+        }
+    }
+    // ---- scores over a query's own rows: wave q, 16 keys per sweep ----
+    {
+        const int T = Tq[wv];
+        const size_t own_off = (size_t)(p.col_mode ? p.seq[min(c0 + wv, p.N - 1)].seq_id : min(c0 + wv, p.N - 1)) * p.kv_seq_stride;
+        const float4 *kown = reinterpret_cast<const float4 *>(p.kcache + own_off + head) + ksub;
+        const float4 *qp = reinterpret_cast<const float4 *>(Q + wv * DK) + ksub;
+        for (int j = n_shared + (lane >> 2); j < T; j += 16) {
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                const float4 kr = kown[(size_t)j * (DK / 4) + 4 * m], qv = qp[4 * m];
+                a0 += (double)__fmul_rn(kr.x, qv.x); a1 += (double)__fmul_rn(kr.y, qv.y);
+                a2 += (double)__fmul_rn(kr.z, qv.z); a3 += (double)__fmul_rn(kr.w, qv.w);
+            }
+            double acc = (a0 + a1) + (a2 + a3);
+            acc += dpp_d<DPP_QUAD_XOR1>(acc);
+            acc += dpp_d<DPP_QUAD_XOR2>(acc);
+            if (ksub == 0) S[j * G + wv] = (float)acc;
+        }
+    }
+    __syncthreads();
+
+    // ---- softmax of query wv over its T keys (ggml_soft_max: fp16-table exp, double sum, scale by (float)(1/sum)) ----
+    {
+        const int T = Tq[wv];
+        float mx = -INFINITY;
+        for (int j = lane; j < T; j += 64) mx = fmaxf(mx, S[j * G + wv]);
+        mx = wave_max_f32(mx);
+        double sum = 0.0;
+        for (int j = lane; j < T; j += 64) {
+            const float val = h2f(p.exp_tab[f2h(__fsub_rn(S[j * G + wv], mx))]);
+            S[j * G + wv] = val;
+            sum += (double)val;
+        }
+        sum = wave_sum_f64(sum);
+        const float inv = inv_sum_f32(sum);
+        for (int j = lane; j < T; j += 64) S[j * G + wv] = __fmul_rn(S[j * G + wv], inv);
+    }
+    __syncthreads();
+
+    // ---- PV: slice wv of 8, dim lane ----
+    double acc[G];
+#pragma unroll
+    for (int q = 0; q < G; q++) acc[q] = 0.0;
+    {
+        const float *__restrict__ vshr = p.vcache + shr_off + head + lane;
+        int tq[G];
+#pragma unroll
+        for (int q = 0; q < G; q++) tq[q] = Tq[q];
+        for (int j = wv; j < n_shared; j += 32) {
+            float v4[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) v4[k] = (j + 8 * k < n_shared) ? vshr[(size_t)(j + 8 * k) * DK] : 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int jj = j + 8 * k;
+                if (jj < n_shared) {
+                    const float4 p0 = *reinterpret_cast<const float4 *>(S + jj * G), p1 = *reinterpret_cast<const float4 *>(S + jj * G + 4);
+                    const float pr[G] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+#pragma unroll
+                    for (int q = 0; q < G; q++)
+                        if (jj < tq[q]) acc[q] += (double)__fmul_rn(v4[k], pr[q]);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < G; q++) {
+            const int c = min(c0 + q, p.N - 1);
+            const size_t own_off = (size_t)(p.col_mode ? p.seq[c].seq_id : c) * p.kv_seq_stride;
+            const float *__restrict__ vown = p.vcache + own_off + head + lane;
+            for (int j = n_shared + wv; j < tq[q]; j += 8) acc[q] += (double)__fmul_rn(vown[(size_t)j * DK], S[j * G + q]);
+        }
+    }
+    __syncthreads();      // every probability has been read: the area becomes the partials
+    double *part = reinterpret_cast<double *>(S);
+#pragma unroll
+    for (int q = 0; q < G; q++) part[(wv * G + q) * DK + lane] = acc[q];
+    __syncthreads();
+    if (c0 + wv < p.N) {
+        double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+        for (int s2 = 0; s2 < 8; s2 += 2) { t0 += part[(s2 * G + wv) * DK + lane]; t1 += part[((s2 + 1) * G + wv) * DK + lane]; }
+        store_head_output(p, c0 + wv, h, lane, (float)(t0 + t1), p.oq_q != nullptr);
+    }
+}
+
 // ---- single-token attention over a long context, split over the keys -----------------------------------
 // attn_fast_kernel puts a head on ONE compute unit: at 1024 keys that is 512 KB of K/V through one CU per
 // layer (21 us measured) while 240 CUs idle.  Here a head's keys are cut into ranges of 64 and spread over

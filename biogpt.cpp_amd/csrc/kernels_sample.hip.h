@@ -15,6 +15,8 @@
 //                                     flag instead: a finished column keeps its token and position (it recomputes the K / V row it has).
 //   kv_share_kernel      before the first step of a call with several samples per prompt: the prompt's K / V rows from the slot of the
 //                        prompt's first sample to the slots of the others (head-major cache: one contiguous run per (layer, head)).
+//   kv_prefix_copy_kernel  a call behind a shared prefix whose steps know one slot per sequence: the prefix's shared rows from the slot they were
+//                        evaluated into to the slot of every sequence.
 //
 // The random state is std::mt19937's: 624 words + the index, one per sequence in device memory, seeded on the host.  sample_tail and the
 // generator are __host__ __device__: biogpt_hip_sample_candidates_host runs the same text on the CPU.
@@ -264,16 +266,32 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float
 }
 
 // grid (n_layer * n_head, n_seqs, 2 [K, V]); seq_stride floats between two slots, P * dk between two heads.  Sequence r with r % n_samples != 0
-// takes the rows [0, its position) -- the prompt without its last token -- from the slot of its prompt's first sample.
-__global__ __launch_bounds__(256) void kv_share_kernel(const SeqState *seq, int n_samples, float *kroot, float *vroot, int64_t seq_stride, int P, int dk) {
+// takes the rows [first_row, its position) -- the prompt without its last token -- from the slot of its prompt's first sample.  first_row > 0: the rows in
+// front are those of a shared prefix (SeqState::pad[0] where the steps read them in the prefix's slot; kv_prefix_copy_kernel brings them where they do not):
+// that range of the first sample's slot was never written and is not read here.
+__global__ __launch_bounds__(256) void kv_share_kernel(const SeqState *seq, int n_samples, int first_row, float *kroot, float *vroot, int64_t seq_stride, int P, int dk) {
     const int r = blockIdx.y, j = r % n_samples;
     if (j == 0) return;
     const int rows = min(seq[r].n_past, P);
+    const int first = min(max(first_row, 0), max(rows, 0));
     const size_t run0 = (size_t)blockIdx.x * P * dk;
     float *root = blockIdx.z == 0 ? kroot : vroot;
     const float4 *s4 = reinterpret_cast<const float4 *>(root + (size_t)(r - j) * seq_stride + run0);
     float4 *d4 = reinterpret_cast<float4 *>(root + (size_t)r * seq_stride + run0);
     const int n4 = rows > 0 ? rows * dk / 4 : 0;
+    for (int i = first * dk / 4 + threadIdx.x; i < n4; i += blockDim.x) d4[i] = s4[i];
+}
+
+// grid (n_layer * n_head, n_seqs, 2 [K, V]), as kv_share_kernel: the rows [0, n_shared) of slot `slot` -- a shared prefix, evaluated once -- into the slot
+// of every sequence r, for decode steps that know one slot per sequence (the column-per-XCD launches of 2 .. 8 sequences).
+__global__ __launch_bounds__(256) void kv_prefix_copy_kernel(int n_shared, int slot, float *kroot, float *vroot, int64_t seq_stride, int P, int dk) {
+    const int r = blockIdx.y;
+    if (r == slot) return;
+    const size_t run0 = (size_t)blockIdx.x * P * dk;
+    float *root = blockIdx.z == 0 ? kroot : vroot;
+    const float4 *s4 = reinterpret_cast<const float4 *>(root + (size_t)slot * seq_stride + run0);
+    float4 *d4 = reinterpret_cast<float4 *>(root + (size_t)r * seq_stride + run0);
+    const int n4 = min(n_shared, P) > 0 ? min(n_shared, P) * dk / 4 : 0;
     for (int i = threadIdx.x; i < n4; i += blockDim.x) d4[i] = s4[i];
 }
 

@@ -375,6 +375,18 @@ int biogpt_hip_trie_rows_device(int device, biogpt_hip_trie *trie, int32_t mode,
  * us_out[i]: microseconds between two device events around launch i alone.  For tools/trie_bench.py. */
 int biogpt_hip_trie_rows_bench(int device, biogpt_hip_trie *trie, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist,
                                const int32_t *hist_lens, int32_t eos_id, float *rows_out, int32_t reps, float *us_out /* [reps] */);
+/* One decode attention launch of N columns behind a shared prefix over caller-supplied inputs (head size 64, one layer): q [N][H * 64]; k_slots / v_slots
+ * [N + 1][H][P][64], slot i column i's own and slot N the prefix's; seq_states [N][8] words as the engine's column states (n_past, ..., pad[0] = shared rows,
+ * pad[1] = their slot).  which 0: the existing attn_fast_kernel<4, false, true>; 1: attn_prefix_kernel<8>, eight columns per workgroup (one shared range for
+ * all columns).  out [N][H * 64]; q8 1 / 2: also the rows' Q8_0 / Q8_1 blocks (out_q [N][H * 64], out_d / out_s [N][H * 2]), 0: none (the three may be NULL).
+ * For tests of the kernel itself and tools. */
+int biogpt_hip_attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
+                                  const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s);
+/* biogpt_hip_attn_prefix_device, then reps in [1, 10000] further launches on the same inputs; us_out[i]: microseconds between two device events around
+ * launch i alone (the K / V rows are in cache from the launch before).  For tools/prefix_gen_bench.py. */
+int biogpt_hip_attn_prefix_bench(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
+                                 const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps,
+                                 float *us_out /* [reps] */);
 /* biogpt_hip_beam_rows_device with given = 1 over rows of which any number of values may be -inf, as a trie step leaves them (entries at -inf become
  * candidates, lower id first, where fewer than 2 * n_beams finite ones are left).  For tests of the kernel itself. */
 int biogpt_hip_beam_rows_masked_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_beams, const float *run_score,
@@ -514,6 +526,30 @@ int biogpt_hip_score_continuations(biogpt_hip_ctx *ctx, const int32_t *prefix, i
                                    const int32_t *conts /* concatenated */, const int32_t *cont_lens, int32_t n_conts,
                                    float *logprob_out, int32_t *argmax_out /* may be NULL */, float *logit_out /* may be NULL */,
                                    double *seconds_out /* may be NULL */);
+
+/* ---- generation behind a shared prefix: one long few-shot or instruction block in front of many short inputs, or N samples of one long prompt ----
+ * Sequence s is prefix ++ suffix_s (suffixes = the suffixes concatenated, suffix_lens their lengths; a suffix may be empty).  The ids -- for sampling
+ * also the lengths -- are those of biogpt_hip_generate_greedy_batch / biogpt_hip_generate_sample on the concatenations with the same n_batch, seeds
+ * and n_predict, bit for bit; n_predict is clamped to n_positions - (n_prefix + the longest suffix).  The prefix's first n_shared rows -- the largest
+ * multiple of n_batch <= n_prefix - 1, so every n_batch chunk of a concatenation is either shared or a sequence's own -- are evaluated ONCE, without
+ * an lm_head, into a K / V slot of their own; every sequence then evaluates prefix[n_shared:] ++ suffix_s only.  The decode steps read the shared
+ * rows in place (path 0); where the steps of the plain call run as column-per-XCD launches (2 .. 8 columns, at most 255 prompt tokens) the shared rows
+ * are copied into every column's slot instead and the steps are exactly those of the plain call (path 1).  n_shared == 0: the plain call.
+ * Columns (n_seqs, n_prompts * n_samples) in [1, 511]: one slot holds the prefix.  Argument errors (null pointers, n_prefix < 1, a token id out of
+ * range, n_prefix + suffix_lens[s] > n_positions, a model without the BioGPT-base fast chain, and those of the plain calls) return -1 before any HIP
+ * call.  There is no form with generation rules or a trie.  The context's own K / V cache, position and logits row are left alone.  Returns as the
+ * plain calls: the clamped n_predict, 0 if that is <= 0, < 0 on error. */
+int biogpt_hip_generate_greedy_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes /* concatenated */,
+                                      const int32_t *suffix_lens, int32_t n_seqs, int32_t n_batch, int32_t n_predict, int32_t *out_ids,
+                                      double *seconds_out /* may be NULL */);
+int biogpt_hip_generate_sample_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes /* concatenated */,
+                                      const int32_t *suffix_lens, int32_t n_prompts, int32_t n_samples, int32_t n_batch, int32_t n_predict,
+                                      int32_t top_k, double top_p, double temp, const uint32_t *seeds /* [n_prompts * n_samples] */,
+                                      int32_t eos_id /* -1: none */, int32_t *out_ids, int32_t *out_lens, double *seconds_out /* may be NULL */);
+/* Of the last of the two calls above that generated tokens on this context (a failed call, or one whose n_predict clamps to 0, changes nothing): {n_shared, prompt columns evaluated (n_shared + the sum over the prompts of
+ * n_prefix - n_shared + suffix_lens[s]), path, columns}.  path names the route of the decode steps: 1 where they are column-per-XCD launches and shared
+ * rows reach the columns' slots by a copy (also with n_shared == 0, when there was nothing to copy), 0 where they run on the launch chain and read shared rows in place.  Returns 0, or -1 for a null argument. */
+int biogpt_hip_prefix_stats(const biogpt_hip_ctx *ctx, int32_t out[4]);
 
 /* ---- hidden states, pooled embeddings, classification heads (no counterpart in the reference) ----
  * The activations in front of the lm_head, from the causal passes of biogpt_hip_score without the lm_head and the log-softmax.
