@@ -428,6 +428,7 @@ SYMBOLS = [
     ("biogpt_hip_generate_sample_prefix", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
                                                     C.c_int32, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_prefix_stats", C.c_int, [_P, _P]),
+    ("biogpt_hip_attn_device", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_attn_prefix_bench", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     ("biogpt_hip_hidden", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),

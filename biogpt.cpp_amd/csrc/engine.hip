@@ -1141,16 +1141,96 @@ struct PassLaunch {
     const bgk::DevMatrix *tile(const MatSlot &m) { if (!mfma) return nullptr; img = tile_matrix(c, m); return &img; }
 };
 
-// attn_fast_kernel's launch table: 4 lanes per key, 16 prefetched V rows per lane; SHARED: the instantiations that take a column's first rows from the shared slot
+// ---- the stand-alone attention launches ---------------------------------------------------------------------------------------------------
+// Which kernel a launch is, and its geometry: what the launch helpers below report.  enqueue_attention and the probe of single kernels
+// (biogpt_hip_attn_device, engine_probe.inc) launch through the same helpers, so the probe's launch is the engine's.
+enum AttnKernel : int {
+    AK_FAST_1 = 0, AK_FAST_2 = 1, AK_FAST_4 = 2, AK_FAST_SLIM = 3,      // attn_fast_kernel<1, true>, <2, false>, <4, false> at 1024 threads, <4, false> as the slim launch
+    AK_FAST_SHARED = 4,                                                  // + the four above: their SHARED instantiations
+    AK_PREFIX = 8, AK_SPLIT = 9, AK_GROUP = 10, AK_TILE_DMA = 11, AK_TILE = 12, AK_GENERIC = 13,
+};
+struct AttnLaunch { int kernel, threads, grid_x, grid_y; size_t lds; };
+
+// the load bound t_cap of a launch: a pass of many query columns takes its keys as they are; the per-column kernels whole waves (= P when the table is not a multiple of 64)
+inline int attn_pass_t_cap(int P, int t_max) { return std::min(P, t_max); }
+inline int attn_decode_t_cap(int P, int t_max) { return std::min(P, (t_max + 63) & ~63); }
+// the tile kernel addresses a thread's four consecutive key rows from ONE base clamped to P - 4: that is only their own rows when 4 | P and P >= 4;
+// any other table size takes the grouped kernel, 8 queries per workgroup, which clamps row by row
+inline bool attn_tile_table_ok(int P) { return (P & 3) == 0 && P >= 4; }
+// workgroup size of the generic kernel: a thread owns up to ATTN_MAXK whole keys, so T <= 4 * threads; ~1 key per thread when possible
+inline int attn_generic_threads(int t_max) {
+    int nt = 256;
+    while (nt < 1024 && t_max > nt) nt <<= 1;
+    return nt;
+}
+inline bool attn_generic_ok(int threads, int dk, int t_max) { return threads % dk == 0 && t_max <= bgk::ATTN_MAXK * threads; }
+
+// attn_fast_kernel's launch table: 4 lanes per key, 16 prefetched V rows per lane
+// slim: many (sequence, head) workgroups: throughput over latency -- one lane quad per 4 keys (4 key passes), a
+// quarter of the threads, four times as many workgroups resident per compute unit
+inline AttnLaunch attn_fast_geometry(int t_cap, bool slim, bool shared, int H, int N) {
+    const int t64 = (t_cap + 63) & ~63, sh = shared ? AK_FAST_SHARED : 0;
+    if (slim) return {AK_FAST_SLIM + sh, std::max(256, t64), H, N, 0};
+    if (t_cap <= 256) return {AK_FAST_1 + sh, 4 * t64, H, N, 0};
+    if (t_cap <= 512) return {AK_FAST_2 + sh, 1024, H, N, 0};
+    return {AK_FAST_4 + sh, 1024, H, N, 0};
+}
+// SHARED: the instantiations that take a column's first rows from the shared slot
 template <bool SHARED>
-void launch_attn_fast(const bgk::AttnParams &a, bool slim, int H, int N, hipStream_t st) {
-    const int t64 = (a.t_cap + 63) & ~63;
-    // slim: many (sequence, head) workgroups: throughput over latency -- one lane quad per 4 keys (4 key passes), a
-    // quarter of the threads, four times as many workgroups resident per compute unit
-    if (slim) hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, SHARED>), dim3(H, N), dim3(std::max(256, t64)), 0, st, a);
-    else if (a.t_cap <= 256) hipLaunchKernelGGL((bgk::attn_fast_kernel<1, true, SHARED>), dim3(H, N), dim3(4 * t64), 0, st, a);
-    else if (a.t_cap <= 512) hipLaunchKernelGGL((bgk::attn_fast_kernel<2, false, SHARED>), dim3(H, N), dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, SHARED>), dim3(H, N), dim3(1024), 0, st, a);
+AttnLaunch launch_attn_fast(const bgk::AttnParams &a, bool slim, int H, int N, hipStream_t st) {
+    const AttnLaunch g = attn_fast_geometry(a.t_cap, slim, SHARED, H, N);
+    const dim3 grid(g.grid_x, g.grid_y), block(g.threads);
+    switch (g.kernel & 3) {
+    case AK_FAST_SLIM: hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, SHARED>), grid, block, 0, st, a); break;
+    case AK_FAST_1: hipLaunchKernelGGL((bgk::attn_fast_kernel<1, true, SHARED>), grid, block, 0, st, a); break;
+    case AK_FAST_2: hipLaunchKernelGGL((bgk::attn_fast_kernel<2, false, SHARED>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, SHARED>), grid, block, 0, st, a); break;
+    }
+    return g;
+}
+// a decode step behind ONE shared prefix: eight columns per workgroup load a shared row once
+inline AttnLaunch launch_attn_prefix(const bgk::AttnParams &a, int H, int N, hipStream_t st) {
+    const AttnLaunch g{AK_PREFIX, 512, H, (N + 7) / 8, 0};
+    hipLaunchKernelGGL((bgk::attn_prefix_kernel<8>), dim3(g.grid_x, g.grid_y), dim3(g.threads), 0, st, a);
+    return g;
+}
+// a pass of many query columns: register-tiled kernel, 16 queries per workgroup share every K / V row they load (tables with attn_tile_table_ok)
+// lds_done: the kernels whose > 64 KB dynamic-LDS opt-in attribute is set on this device
+inline bool launch_attn_tile(const bgk::AttnParams &a, int H, int N, hipStream_t st, std::set<const void *> &lds_done, AttnLaunch *out) {
+    // up to 640 keys the K / V rows of the two MAC loops travel through a ring in LDS, two steps ahead (global_load_lds); beyond, the ring has no room
+    // beside the scores in a 2-workgroups-per-compute-unit footprint: loads at the top of each step
+    const bool dma = bgk::attn_tile_dma_ok(a.t_cap);
+    const size_t smb = bgk::attn_tile_smem_bytes<16>(a.t_cap);
+    const void *fn = dma ? reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, true>) : reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, false>);
+    if (smb > 64 * 1024 && !lds_done.count(fn)) {
+        HIP_TRY(false, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bgk::attn_tile_smem_bytes<16>(a.P)));
+        lds_done.insert(fn);
+    }
+    const AttnLaunch g{dma ? AK_TILE_DMA : AK_TILE, 512, H, (N + 15) / 16, smb};
+    if (dma) hipLaunchKernelGGL((bgk::attn_tile_kernel<16, true>), dim3(g.grid_x, g.grid_y), dim3(g.threads), smb, st, a);
+    else hipLaunchKernelGGL((bgk::attn_tile_kernel<16, false>), dim3(g.grid_x, g.grid_y), dim3(g.threads), smb, st, a);
+    if (out) *out = g;
+    return true;
+}
+inline AttnLaunch launch_attn_group(const bgk::AttnParams &a, int H, int N, hipStream_t st) {
+    const AttnLaunch g{AK_GROUP, 512, H, (N + 7) / 8, bgk::attn_group_smem_bytes(a.t_cap)};
+    hipLaunchKernelGGL((bgk::attn_group_kernel<8>), dim3(g.grid_x, g.grid_y), dim3(g.threads), g.lds, st, a);
+    return g;
+}
+// long context, one query: spread the head's keys over the chip (three dependent launches); a.sp_* are the caller's scratch, a.n_split is set here
+inline bool launch_attn_split(bgk::AttnParams &a, int H, hipStream_t st, AttnLaunch *out) {
+    a.n_split = (a.t_cap + bgk::SPLIT_KEYS - 1) / bgk::SPLIT_KEYS;
+    if (a.n_split > bgk::SPLIT_MAX) BG_FAIL(false, "internal: %d key ranges exceed the %d the split attention kernels hold", a.n_split, bgk::SPLIT_MAX);
+    hipLaunchKernelGGL(bgk::attn_split_scores_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(bgk::attn_split_pv_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(bgk::attn_split_combine_kernel, dim3(H), dim3(64), 0, st, a);
+    if (out) *out = {AK_SPLIT, 256, H, a.n_split, 0};
+    return true;
+}
+inline AttnLaunch launch_attn_generic(const bgk::AttnParams &a, int H, int N, int threads, hipStream_t st) {
+    const AttnLaunch g{AK_GENERIC, threads, H, N, bgk::attn_smem_bytes(a.P, a.dk, threads)};
+    hipLaunchKernelGGL(bgk::attn_kernel, dim3(g.grid_x, g.grid_y), dim3(g.threads), g.lds, st, a);
+    return g;
 }
 
 // the attention launch(es) of layer l
@@ -1169,48 +1249,25 @@ bool enqueue_attention(PassLaunch &k, int l) {
     a.q81 = k.q81;
     if (k.chain) { a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; }
     if (!(dk == 64 && t_max <= 1024)) {
-        hipLaunchKernelGGL(bgk::attn_kernel, dim3(H, N), dim3(k.attn_threads), bgk::attn_smem_bytes(P, dk, k.attn_threads), st, a);
+        launch_attn_generic(a, H, N, k.attn_threads, st);
         return true;
     }
     if (!batch && N >= GROUPED_ATTN_MIN_COLS) {
-        // a pass of many query columns: register-tiled kernel, 16 queries per workgroup share every K / V row they load
-        a.t_cap = std::min(P, t_max);
-        // (the tile kernel addresses a thread's four consecutive key rows from ONE base clamped to P - 4: that is only their own rows when 4 | P and P >= 4;
-        //  any other table size takes the grouped kernel, 8 queries per workgroup, which clamps row by row)
-        if ((P & 3) == 0 && P >= 4) {
-            // up to 640 keys the K / V rows of the two MAC loops travel through a ring in LDS, two steps ahead (global_load_lds); beyond, the ring has no room
-            // beside the scores in a 2-workgroups-per-compute-unit footprint: loads at the top of each step
-            const bool dma = bgk::attn_tile_dma_ok(a.t_cap);
-            const size_t smb = bgk::attn_tile_smem_bytes<16>(a.t_cap);
-            const void *fn = dma ? reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, true>) : reinterpret_cast<const void *>(bgk::attn_tile_kernel<16, false>);
-            if (smb > 64 * 1024 && !c->lds_attr_done.count(fn)) {
-                HIP_TRY(false, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bgk::attn_tile_smem_bytes<16>(P)));
-                c->lds_attr_done.insert(fn);
-            }
-            if (dma) hipLaunchKernelGGL((bgk::attn_tile_kernel<16, true>), dim3(H, (N + 15) / 16), dim3(512), smb, st, a);
-            else hipLaunchKernelGGL((bgk::attn_tile_kernel<16, false>), dim3(H, (N + 15) / 16), dim3(512), smb, st, a);
-        } else {
-            hipLaunchKernelGGL((bgk::attn_group_kernel<8>), dim3(H, (N + 7) / 8), dim3(512), bgk::attn_group_smem_bytes(a.t_cap), st, a);
-        }
+        a.t_cap = attn_pass_t_cap(P, t_max);
+        if (attn_tile_table_ok(P)) return launch_attn_tile(a, H, N, st, c->lds_attr_done, nullptr);
+        launch_attn_group(a, H, N, st);
         return true;
     }
-    // loads are bounded by t_cap (= P when the table is not a multiple of 64; the workgroup stays whole waves)
-    a.t_cap = std::min(P, (t_max + 63) & ~63);
+    // loads are bounded by t_cap
+    a.t_cap = attn_decode_t_cap(P, t_max);
     if (N == 1 && !batch && a.t_cap > SPLIT_ATTN_ABOVE_KEYS) {
-        // long context, one query: spread the head's keys over the chip (three dependent launches)
         a.sp_scores = c->sp_scores; a.sp_max = c->sp_max; a.sp_pv = c->sp_pv;
-        a.n_split = (a.t_cap + bgk::SPLIT_KEYS - 1) / bgk::SPLIT_KEYS;
-        if (a.n_split > bgk::SPLIT_MAX) BG_FAIL(false, "internal: %d key ranges exceed the %d the split attention kernels hold", a.n_split, bgk::SPLIT_MAX);
-        hipLaunchKernelGGL(bgk::attn_split_scores_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(bgk::attn_split_pv_kernel, dim3(H, a.n_split), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(bgk::attn_split_combine_kernel, dim3(H), dim3(64), 0, st, a);
-        return true;
+        return launch_attn_split(a, H, st, nullptr);
     }
     const bool slim = batch && N >= SLIM_ATTN_MIN_COLS;
-    // a decode step behind ONE shared prefix: eight columns per workgroup load a shared row once
     const bool grouped = k.pass.shared_prefix && k.pass.cols == ForwardPass::Cols::PerSequence && a.t_cap <= bgk::PFX_MAX_KEYS &&
                          (c->opt.prefix_attn < 0 ? N >= PREFIX_ATTN_MIN_COLS && k.pass.shared_rows >= PREFIX_ATTN_MIN_SHARED : c->opt.prefix_attn == 1);
-    if (grouped) hipLaunchKernelGGL((bgk::attn_prefix_kernel<8>), dim3(H, (N + 7) / 8), dim3(512), 0, st, a);
+    if (grouped) launch_attn_prefix(a, H, N, st);
     else if (k.pass.shared_prefix) launch_attn_fast<true>(a, slim, H, N, st);
     else launch_attn_fast<false>(a, slim, H, N, st);
     return true;
@@ -1355,10 +1412,8 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     PassLaunch k{c, pass, c->stream};
     k.N = N; k.D = hp.d_model; k.F = hp.d_ff; k.V = hp.n_vocab; k.H = hp.n_head; k.P = hp.n_positions;
     k.dk = k.D / k.H;
-    // attention workgroup size: a thread owns up to ATTN_MAXK whole keys, so T <= 4 * threads
-    k.attn_threads = 256;
-    while (k.attn_threads < 1024 && t_max > k.attn_threads) k.attn_threads <<= 1;  // ~1 key per thread when possible
-    if (k.attn_threads % k.dk != 0 || t_max > bgk::ATTN_MAXK * k.attn_threads)
+    k.attn_threads = attn_generic_threads(t_max);
+    if (!attn_generic_ok(k.attn_threads, k.dk, t_max))
         BG_FAIL(false, "context of %d tokens / head size %d not supported by the attention kernel", t_max, k.dk);
 
     // single-token fast chain: BioGPT-base shapes, block-quantized weights -> producer-side Q8 hand-offs

@@ -180,63 +180,144 @@ int biogpt_hip_trie_rows_bench(int device, biogpt_hip_trie *trie, int32_t mode, 
     return trie_rows_device(device, trie, mode, rows, n_rows, n_vocab, hist, hist_lens, eos_id, rows_out, reps, us_out);
 }
 
-// One decode attention launch over caller-supplied inputs: N columns behind a shared prefix, head size 64, one layer.  q [N][H * 64]; k_slots / v_slots
-// [N + 1][H][P][64]: slot i is column i's own, slot N the prefix's; seq_states [N] SeqState (n_past, pad[0] = shared rows, pad[1] = their slot; column i = slot i).
-// which 0: attn_fast_kernel<4, false, true> as a slim launch; 1: attn_prefix_kernel<8> (then pad[0] / pad[1] must be the same for every column).  q8 0: f32 rows
-// only; 1 / 2: also the Q8_0 / Q8_1 blocks of the rows (out_q [N][H * 64], out_d / out_s [N][H * 2]).  reps > 0: the launch repeated, us_out[i] microseconds
-// between two events around launch i alone -- a repeated stand-alone launch finds its K / V rows in cache.
-static int attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
-                              const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps, float *us_out) {
-    clear_error();
-    if (!q || !k_slots || !v_slots || !seq_states || !out) BG_FAIL(-1, "q, k_slots, v_slots, seq_states or out is NULL");
+// One stand-alone attention launch over caller-supplied inputs, through the launch helpers of enqueue_attention (one layer).  route: the AttnKernel the
+// caller expects; a combination for which the engine would launch another kernel, or none, is refused before anything is allocated.  H heads of dk values
+// (dk = 64 for every kernel but the generic one); q [N][H * dk]; k_slots / v_slots [n_slots][H][P][dk].  Column states: dev_state {n_past, n_gen, causal, chunk}
+// (the context's own columns: one slot, visible_keys per column) or seq_states [N] SeqState words (col_mode 0: column i = slot i, T = n_past + 1; 1: slot
+// seq_id, T = t_vis; the SHARED kernels and attn_prefix_kernel: the first pad[0] rows in slot pad[1]).  t_max: the pass's furthest visible key count, from
+// which t_cap follows as in the engine.  q8 0: f32 rows only; 1 / 2: also their Q8_0 / Q8_1 blocks.  The outputs are returned WHOLE as they were allocated:
+// rows = N rounded up to 16, plus one guard row, preset to 0xff -- out [rows][H * dk], out_q [rows][H * dk], out_d / out_s [rows][H * dk / 32] -- so a store
+// beyond column N shows.  launched [8]: kernel, threads, grid x, grid y, dynamic LDS bytes, t_cap, key ranges (split), 0.
+// reps > 0: the launch repeated, us_out[i] microseconds between two events around launch i alone -- a repeated stand-alone launch finds its K / V rows in cache.
+static int host_visible_keys(const int32_t *ds, int i, int N) {      // visible_keys (kernels.hip.h) on the host
+    if (ds[2]) return ds[0] + i + 1;
+    if (ds[3] <= 0) return ds[0] + N;
+    const int end = (i / ds[3] + 1) * ds[3];
+    return ds[0] + std::min(end, N);
+}
+static int attn_device(int device, int32_t route, int32_t H, int32_t dk, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots,
+                       const float *v_slots, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t q8, float *out, int8_t *out_q, float *out_d,
+                       uint32_t *out_s, int32_t *launched, int32_t reps, float *us_out) {
+    if (!q || !k_slots || !v_slots || !out) BG_FAIL(-1, "q, k_slots, v_slots or out is NULL");
+    const bool fast = route >= AK_FAST_1 && route < AK_PREFIX, shared = fast && route >= AK_FAST_SHARED;
+    if (!fast && (route < AK_PREFIX || route > AK_GENERIC)) BG_FAIL(-1, "route %d is no attention kernel", route);
     if (H < 1 || H > 64) BG_FAIL(-1, "H must be in [1, 64]");
     if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
-    if (P < 1 || P > bgk::PFX_MAX_KEYS) BG_FAIL(-1, "P must be in [1, %d]", bgk::PFX_MAX_KEYS);
-    if (t_cap < 1 || t_cap > P) BG_FAIL(-1, "t_cap must be in [1, P]");
-    if (which != 0 && which != 1) BG_FAIL(-1, "which must be 0 (attn_fast_kernel<4, false, true>) or 1 (attn_prefix_kernel<8>)");
+    if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+    if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
+    if (t_max < 1 || t_max > P) BG_FAIL(-1, "t_max must be in [1, P]: t_cap never exceeds the table");
     if (q8 < 0 || q8 > 2 || (q8 > 0 && (!out_q || !out_d || !out_s))) BG_FAIL(-1, "q8 must be 0, 1 or 2, with out_q, out_d and out_s");
     if (reps < 0 || reps > 10000 || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, 10000], with us_out");
+    if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
+    if ((dev_state != nullptr) == (seq_states != nullptr)) BG_FAIL(-1, "exactly one of dev_state and seq_states names the column states");
     static_assert(sizeof(bgk::SeqState) == 32, "eight words per column state");
+    static_assert(sizeof(bgk::DevState) == 16, "four words of context state");
+    const bool batch = seq_states != nullptr;
+    // ---- what the engine would launch for this pass, and with which bounds ----
+    int threads = 0;
+    if (route == AK_GENERIC) {
+        if (dk < 4 || dk > 256 || (dk & 3)) BG_FAIL(-1, "dk must be a multiple of 4 in [4, 256]");
+        if (dk == 64 && t_max <= 1024) BG_FAIL(-1, "head size 64 up to 1024 keys never takes the generic kernel");
+        if (batch) BG_FAIL(-1, "the generic kernel serves the context's own columns only (dev_state)");
+        if (q8) BG_FAIL(-1, "the generic kernel writes no Q8 blocks");
+        threads = attn_generic_threads(t_max);
+        if (!attn_generic_ok(threads, dk, t_max)) BG_FAIL(-1, "context of %d tokens / head size %d not supported by the attention kernel (%d threads)", t_max, dk, threads);
+        if (bgk::attn_smem_bytes(P, dk, threads) > 64 * 1024) BG_FAIL(-1, "a table of %d rows exceeds the generic kernel's LDS", P);
+    } else {
+        if (dk != 64) BG_FAIL(-1, "dk must be 64 for every kernel but the generic one");
+        if (t_max > 1024) BG_FAIL(-1, "t_cap: beyond 1024 keys a pass takes the generic kernel (the reach of every other one)");
+        if (P > 2048) BG_FAIL(-1, "P must be at most 2048 for every kernel but the generic one");
+    }
+    const bool pass_kernel = route == AK_GROUP || route == AK_TILE || route == AK_TILE_DMA;
+    const int t_cap = route == AK_GENERIC ? P : pass_kernel ? attn_pass_t_cap(P, t_max) : attn_decode_t_cap(P, t_max);
+    if (pass_kernel || route == AK_SPLIT) {
+        if (batch) BG_FAIL(-1, "this kernel serves the context's own columns only (dev_state)");
+        if (pass_kernel && (route == AK_GROUP) == attn_tile_table_ok(P)) BG_FAIL(-1, "a table of P = %d rows takes %s", P, attn_tile_table_ok(P) ? "the tile kernel (4 | P)" : "the grouped kernel (P not a multiple of 4)");
+        if ((route == AK_TILE || route == AK_TILE_DMA) && (route == AK_TILE_DMA) != bgk::attn_tile_dma_ok(t_cap)) BG_FAIL(-1, "t_cap %d takes the %s form of the tile kernel", t_cap, bgk::attn_tile_dma_ok(t_cap) ? "DMA" : "plain");
+    }
+    if (route == AK_SPLIT) {
+        if (N != 1) BG_FAIL(-1, "the split kernels serve N = 1 only");
+        if (t_cap <= SPLIT_ATTN_ABOVE_KEYS) BG_FAIL(-1, "t_cap %d: the split kernels run above %d keys only", t_cap, SPLIT_ATTN_ABOVE_KEYS);
+        if ((t_cap + bgk::SPLIT_KEYS - 1) / bgk::SPLIT_KEYS > bgk::SPLIT_MAX) BG_FAIL(-1, "t_cap %d: more than %d key ranges", t_cap, bgk::SPLIT_MAX);
+    }
+    if (route == AK_PREFIX) {
+        if (!batch || col_mode != 0) BG_FAIL(-1, "attn_prefix_kernel serves decode steps only (seq_states, col_mode 0)");
+        if (t_cap > bgk::PFX_MAX_KEYS || P > bgk::PFX_MAX_KEYS) BG_FAIL(-1, "P must be in [1, %d] for attn_prefix_kernel", bgk::PFX_MAX_KEYS);
+    }
+    if (fast) {
+        if (shared && !batch) BG_FAIL(-1, "the SHARED kernels need seq_states");
+        const bool slim = (route & 3) == AK_FAST_SLIM;
+        if (slim && !batch) BG_FAIL(-1, "the slim launch serves decode steps of many sequences (seq_states)");
+        const AttnLaunch g = attn_fast_geometry(t_cap, slim, shared, H, N);
+        if (g.kernel != route) BG_FAIL(-1, "t_cap %d is outside the reach of route %d: the engine launches kernel %d there", t_cap, route, g.kernel);
+    }
+    // ---- every column's visible keys lie inside [1, t_cap], every slot inside the arrays ----
     const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
     for (int i = 0; i < N; i++) {
-        if (hs[i].n_past < 0 || hs[i].n_past >= t_cap) BG_FAIL(-1, "column %d: n_past %d outside [0, t_cap)", i, hs[i].n_past);
-        if (hs[i].pad[0] < 0 || hs[i].pad[0] > hs[i].n_past) BG_FAIL(-1, "column %d: %d shared rows outside [0, n_past]", i, hs[i].pad[0]);
-        if (hs[i].pad[1] < 0 || hs[i].pad[1] > N) BG_FAIL(-1, "column %d: shared slot %d outside [0, N]", i, hs[i].pad[1]);
-        if (which == 1 && (hs[i].pad[0] != hs[0].pad[0] || hs[i].pad[1] != hs[0].pad[1])) BG_FAIL(-1, "column %d: attn_prefix_kernel needs one shared range for all columns", i);
+        const int T = !batch ? host_visible_keys(dev_state, i, N) : col_mode ? hs[i].t_vis : hs[i].n_past + 1;
+        if (!batch && dev_state[0] < 0) BG_FAIL(-1, "n_past %d is negative", dev_state[0]);
+        if (batch && !col_mode && (hs[i].n_past < 0 || hs[i].n_past >= t_cap)) BG_FAIL(-1, "column %d: n_past %d outside [0, t_cap)", i, hs[i].n_past);
+        if (T < 1 || T > t_cap || T > t_max) BG_FAIL(-1, "column %d: %d visible keys outside [1, t_cap = %d] (t_max %d)", i, T, t_cap, t_max);
+        if (!batch) continue;
+        const int slot = col_mode ? hs[i].seq_id : i;
+        if (slot < 0 || slot >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, slot);
+        if (shared || route == AK_PREFIX) {
+            if (hs[i].pad[0] < 0 || hs[i].pad[0] > (col_mode ? T : hs[i].n_past)) BG_FAIL(-1, "column %d: %d shared rows outside [0, n_past]", i, hs[i].pad[0]);
+            if (hs[i].pad[1] < 0 || hs[i].pad[1] >= n_slots) BG_FAIL(-1, "column %d: shared slot %d outside [0, n_slots)", i, hs[i].pad[1]);
+            if (route == AK_PREFIX && (hs[i].pad[0] != hs[0].pad[0] || hs[i].pad[1] != hs[0].pad[1])) BG_FAIL(-1, "column %d: attn_prefix_kernel needs one shared range for all columns", i);
+        }
     }
+    if (!batch && n_slots != 1) BG_FAIL(-1, "the context's own columns have one slot");
     HIP_TRY(-2, hipSetDevice(device));
-    const int D = H * 64;
-    const size_t slot = (size_t)H * P * 64, kv_b = slot * 4 * (size_t)(N + 1), row_b = (size_t)N * D * 4, blk = (size_t)N * (D / 32);
+    const int D = H * dk, rows = ((N + 15) & ~15) + 1;
+    const size_t slot = (size_t)H * P * dk, kv_b = slot * 4 * (size_t)n_slots, q_b = (size_t)N * D * 4, row_b = (size_t)rows * D * 4, blk = (size_t)rows * (D / 32);
     ByteLayout l;
-    const size_t o_k = l.part(kv_b), o_v = l.part(kv_b), o_q = l.part(row_b), o_st = l.part(sizeof(bgk::SeqState) * (size_t)N), o_tab = l.part(65536 * 2), o_out = l.part(row_b),
-                 o_oq = l.part((size_t)N * D), o_od = l.part(blk * 4), o_os = l.part(blk * 4);
+    const size_t o_k = l.part(kv_b), o_v = l.part(kv_b), o_q = l.part(q_b), o_st = l.part(sizeof(bgk::SeqState) * (size_t)N), o_ds = l.part(sizeof(bgk::DevState)),
+                 o_tab = l.part(65536 * 2), o_out = l.part(row_b), o_oq = l.part((size_t)rows * D), o_od = l.part(blk * 4), o_os = l.part(blk * 4),
+                 o_sps = l.part((size_t)H * P * 4), o_spm = l.part((size_t)H * bgk::SPLIT_MAX * 4), o_spv = l.part((size_t)H * bgk::SPLIT_MAX * 64 * 8);
     DeviceBytes d;
     if (!d.alloc(l.bytes())) return -2;
     std::vector<uint16_t> te(65536);
     for (uint32_t i = 0; i < 65536; i++) te[i] = f32_to_f16(expf(f16_to_f32((uint16_t)i)));      // the table of the model loader
+    const int32_t no_state[4] = {0, 0, 0, 0};
     HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
     HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_q, q, row_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_q, q, q_b, hipMemcpyHostToDevice));
+    if (batch) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_ds, batch ? no_state : dev_state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
     HIP_TRY(-2, hipMemcpy(d.p + o_tab, te.data(), 65536 * 2, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));
+    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));      // the outputs with their guard rows, and the split scratch (a range past the context reads as NaN)
     bgk::AttnParams a{};
     a.q = d.at<const float>(o_q); a.kcache = d.at<const float>(o_k); a.vcache = d.at<const float>(o_v); a.out = d.at<float>(o_out);
+    a.st = d.at<const bgk::DevState>(o_ds);
     a.exp_tab = d.at<const uint16_t>(o_tab);
-    a.N = N; a.D = D; a.dk = 64; a.P = P; a.t_cap = t_cap;
-    a.seq = d.at<const bgk::SeqState>(o_st); a.col_mode = 0; a.kv_seq_stride = (int64_t)slot;
+    a.N = N; a.D = D; a.dk = dk; a.P = P; a.t_cap = t_cap;
+    if (batch) { a.seq = d.at<const bgk::SeqState>(o_st); a.col_mode = col_mode; a.kv_seq_stride = (int64_t)slot; }
     a.q81 = q8 == 2 ? 1 : 0;
     if (q8 > 0) { a.oq_q = d.at<int8_t>(o_oq); a.oq_d = d.at<float>(o_od); a.oq_s = d.at<uint32_t>(o_os); }
-    auto launch = [&] {
-        if (which == 1) hipLaunchKernelGGL((bgk::attn_prefix_kernel<8>), dim3(H, (N + 7) / 8), dim3(512), 0, 0, a);
-        else hipLaunchKernelGGL((bgk::attn_fast_kernel<4, false, true>), dim3(H, N), dim3(std::max(256, (t_cap + 63) & ~63)), 0, 0, a);
+    if (route == AK_SPLIT) { a.sp_scores = d.at<float>(o_sps); a.sp_max = d.at<float>(o_spm); a.sp_pv = d.at<double>(o_spv); }
+    std::set<const void *> lds_done;
+    AttnLaunch g{};
+    auto launch = [&]() -> bool {
+        if (route == AK_GENERIC) g = launch_attn_generic(a, H, N, threads, 0);
+        else if (route == AK_GROUP) g = launch_attn_group(a, H, N, 0);
+        else if (route == AK_TILE || route == AK_TILE_DMA) return launch_attn_tile(a, H, N, 0, lds_done, &g);
+        else if (route == AK_SPLIT) return launch_attn_split(a, H, 0, &g);
+        else if (route == AK_PREFIX) g = launch_attn_prefix(a, H, N, 0);
+        else if (shared) g = launch_attn_fast<true>(a, (route & 3) == AK_FAST_SLIM, H, N, 0);
+        else g = launch_attn_fast<false>(a, (route & 3) == AK_FAST_SLIM, H, N, 0);
+        return true;
     };
-    launch();
+    if (!launch()) return -2;
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
+    if (launched) {
+        const int32_t rep[8] = {g.kernel, g.threads, g.grid_x, g.grid_y, (int32_t)g.lds, t_cap, a.n_split, 0};
+        std::memcpy(launched, rep, sizeof(rep));
+    }
     HIP_TRY(-2, hipMemcpy(out, d.p + o_out, row_b, hipMemcpyDeviceToHost));
     if (q8 > 0) {
-        HIP_TRY(-2, hipMemcpy(out_q, d.p + o_oq, (size_t)N * D, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(out_q, d.p + o_oq, (size_t)rows * D, hipMemcpyDeviceToHost));
         HIP_TRY(-2, hipMemcpy(out_d, d.p + o_od, blk * 4, hipMemcpyDeviceToHost));
         HIP_TRY(-2, hipMemcpy(out_s, d.p + o_os, blk * 4, hipMemcpyDeviceToHost));
     }
@@ -247,7 +328,7 @@ static int attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32
         bool ok = true;
         for (int i = 0; i < reps && ok; i++) {
             ok = hipEventRecord(e0, 0) == hipSuccess;
-            launch();
+            ok = launch() && ok;
             ok = ok && hipEventRecord(e1, 0) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
             float ms = 0.0f;
             ok = ok && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
@@ -258,13 +339,47 @@ static int attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32
     }
     return 0;
 }
+int biogpt_hip_attn_device(int device, int32_t route, int32_t H, int32_t dk, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots,
+                           const float *v_slots, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t q8, float *out, int8_t *out_q, float *out_d,
+                           uint32_t *out_s, int32_t *launched) {
+    clear_error();
+    return attn_device(device, route, H, dk, N, P, t_max, n_slots, q, k_slots, v_slots, dev_state, seq_states, col_mode, q8, out, out_q, out_d, out_s, launched, 0, nullptr);
+}
+
+// One decode attention launch of N columns behind a shared prefix (head size 64): k_slots / v_slots [N + 1][H][P][64], slot i column i's own, slot N the prefix's.
+// which 0: attn_fast_kernel<4, false, true> as a slim launch; 1: attn_prefix_kernel<8>.  A caller of attn_device with the outputs cut to their N rows.
+static int attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
+                              const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps, float *us_out) {
+    clear_error();
+    if (!q || !k_slots || !v_slots || !seq_states || !out) BG_FAIL(-1, "q, k_slots, v_slots, seq_states or out is NULL");
+    if (H < 1 || H > 64) BG_FAIL(-1, "H must be in [1, 64]");
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (P < 1 || P > bgk::PFX_MAX_KEYS) BG_FAIL(-1, "P must be in [1, %d]", bgk::PFX_MAX_KEYS);
+    if (t_cap < 1 || t_cap > P || attn_decode_t_cap(P, t_cap) != t_cap) BG_FAIL(-1, "t_cap must be in [1, P], and a multiple of 64 or P");
+    if (which != 0 && which != 1) BG_FAIL(-1, "which must be 0 (attn_fast_kernel<4, false, true>) or 1 (attn_prefix_kernel<8>)");
+    if (q8 < 0 || q8 > 2 || (q8 > 0 && (!out_q || !out_d || !out_s))) BG_FAIL(-1, "q8 must be 0, 1 or 2, with out_q, out_d and out_s");
+    const int D = H * 64, rows = ((N + 15) & ~15) + 1;
+    std::vector<float> o((size_t)rows * D), od((size_t)rows * (D / 32));
+    std::vector<int8_t> oq((size_t)rows * D);
+    std::vector<uint32_t> os((size_t)rows * (D / 32));
+    const int rc = attn_device(device, which == 1 ? AK_PREFIX : AK_FAST_SLIM + AK_FAST_SHARED, H, 64, N, P, t_cap, N + 1, q, k_slots, v_slots, nullptr, seq_states, 0, q8, o.data(),
+                               oq.data(), od.data(), os.data(), nullptr, reps, us_out);
+    if (rc != 0) return rc;
+    std::memcpy(out, o.data(), (size_t)N * D * 4);
+    if (q8 > 0) {
+        std::memcpy(out_q, oq.data(), (size_t)N * D);
+        std::memcpy(out_d, od.data(), (size_t)N * (D / 32) * 4);
+        std::memcpy(out_s, os.data(), (size_t)N * (D / 32) * 4);
+    }
+    return 0;
+}
 int biogpt_hip_attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
                                   const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s) {
     return attn_prefix_device(device, H, N, P, t_cap, q, k_slots, v_slots, seq_states, which, q8, out, out_q, out_d, out_s, 0, nullptr);
 }
 int biogpt_hip_attn_prefix_bench(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
                                  const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps, float *us_out) {
-    if (reps < 1) { clear_error(); BG_FAIL(-1, "reps must be in [1, 10000]"); }
+    if (reps < 1 || reps > 10000 || !us_out) { clear_error(); BG_FAIL(-1, "reps must be in [1, 10000], with us_out"); }
     return attn_prefix_device(device, H, N, P, t_cap, q, k_slots, v_slots, seq_states, which, q8, out, out_q, out_d, out_s, reps, us_out);
 }
 

@@ -375,10 +375,22 @@ int biogpt_hip_trie_rows_device(int device, biogpt_hip_trie *trie, int32_t mode,
  * us_out[i]: microseconds between two device events around launch i alone.  For tools/trie_bench.py. */
 int biogpt_hip_trie_rows_bench(int device, biogpt_hip_trie *trie, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist,
                                const int32_t *hist_lens, int32_t eos_id, float *rows_out, int32_t reps, float *us_out /* [reps] */);
+/* One stand-alone attention launch over caller-supplied inputs, through the launch code of the engine's own passes (one layer).  route names the kernel the caller
+ * expects: 0 .. 3 attn_fast_kernel<1, true>, <2, false>, <4, false> at 1024 threads and <4, false> as the slim launch, 4 .. 7 their SHARED instantiations,
+ * 8 attn_prefix_kernel<8>, 9 the three attn_split_* launches, 10 attn_group_kernel<8>, 11 / 12 attn_tile_kernel<16, true> / <16, false>, 13 attn_kernel.  A
+ * combination for which the engine would launch another kernel, or none, returns -1.  q [N][H * dk] (dk = 64 but for route 13); k_slots / v_slots
+ * [n_slots][H][P][dk].  Exactly one of dev_state (4 words: n_past, n_gen, causal, chunk; one slot) and seq_states ([N][8] words as the engine's column states;
+ * col_mode 0: column i reads slot i and n_past + 1 keys, 1: slot seq_id and t_vis keys; routes 4 .. 8: the first pad[0] rows from slot pad[1]).  t_max: the
+ * furthest column's visible keys, from which the launch's load bound follows as in a pass.  The outputs come back whole, as allocated and preset to 0xff bytes:
+ * rows = N rounded up to 16, plus 1 -- out [rows][H * dk]; q8 1 / 2: also the rows' Q8_0 / Q8_1 blocks, out_q [rows][H * dk], out_d / out_s [rows][H * dk / 32].
+ * launched [8] (may be NULL): kernel (as route), threads, grid x, grid y, dynamic LDS bytes, t_cap, key ranges (route 9), 0.  For tests of the kernels themselves. */
+int biogpt_hip_attn_device(int device, int32_t route, int32_t H, int32_t dk, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q,
+                           const float *k_slots, const float *v_slots, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t q8, float *out,
+                           int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched);
 /* One decode attention launch of N columns behind a shared prefix over caller-supplied inputs (head size 64, one layer): q [N][H * 64]; k_slots / v_slots
  * [N + 1][H][P][64], slot i column i's own and slot N the prefix's; seq_states [N][8] words as the engine's column states (n_past, ..., pad[0] = shared rows,
  * pad[1] = their slot).  which 0: the existing attn_fast_kernel<4, false, true>; 1: attn_prefix_kernel<8>, eight columns per workgroup (one shared range for
- * all columns).  out [N][H * 64]; q8 1 / 2: also the rows' Q8_0 / Q8_1 blocks (out_q [N][H * 64], out_d / out_s [N][H * 2]), 0: none (the three may be NULL).
+ * all columns); t_cap a multiple of 64, or P.  out [N][H * 64]; q8 1 / 2: also the rows' Q8_0 / Q8_1 blocks (out_q [N][H * 64], out_d / out_s [N][H * 2]), 0: none (the three may be NULL).
  * For tests of the kernel itself and tools. */
 int biogpt_hip_attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
                                   const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s);

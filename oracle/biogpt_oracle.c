@@ -1037,6 +1037,51 @@ static inline float gelu_erf_f32(float x) { return (float)(0.5 * (double)x * (1.
 /* ------------------------------------------------------------------------------------------
  * forward pass: biogpt_graph (biogpt.cpp:624-810) + row selection of biogpt_eval (:840-844)
  * ---------------------------------------------------------------------------------------- */
+/* One (head, query) of the attention of bo_eval (biogpt.cpp:729-764): the query's dk values qv against T visible keys; key / value row j of the head lies at
+ * K + j * stride / V + j * stride.  KQ = mul_mat(K, Q), ggml_soft_max, ggml_vec_scale_f32, KQV = mul_mat(V_trans, attn_weights) into out[dk]. */
+int bo_attn_head(const float *qv, const float *K, const float *V, int dk, int64_t stride, int T, int exp_f32, int assoc, float *out) {
+    if (!qv || !K || !V || !out || dk < 1 || T < 1) return -1;
+    init_tables();
+    const int Tlim = T;
+    float *S = (float *)malloc(sizeof(float) * (size_t)T);
+    for (int j = 0; j < Tlim; j++) /* KQ = mul_mat(K, Q) */
+        S[j] = (assoc & 1) ? vec_dot_f32_simd_x(assoc & 4, dk, K + (size_t)j * stride, qv) : vec_dot_f32(dk, K + (size_t)j * stride, qv);
+    /* ggml_soft_max */
+    float mx = -INFINITY;
+    for (int j = 0; j < Tlim; j++)
+        if (S[j] > mx) mx = S[j];
+    double sum = 0.0;
+    for (int j = 0; j < Tlim; j++) {
+        float val;
+        if (exp_f32) {
+            val = expf(S[j] - mx);
+        } else {
+            val = F16(g_table_exp[bo_fp32_to_fp16(S[j] - mx)]);
+        }
+        sum += (double)val;
+        S[j] = val;
+    }
+    sum              = 1.0 / sum;
+    const float fsum = (float)sum;
+    for (int j = 0; j < Tlim; j++) S[j] *= fsum; /* ggml_vec_scale_f32 */
+    /* KQV = mul_mat(V_trans, attn_weights): dot over T for each of the dk dims */
+    if (assoc & 1) { /* V_trans row (contiguous over the keys) . probabilities, SIMD-shaped */
+        float *vt_row = (float *)malloc(sizeof(float) * (size_t)Tlim);
+        for (int d = 0; d < dk; d++) {
+            for (int j = 0; j < Tlim; j++) vt_row[j] = V[(size_t)j * stride + d];
+            out[d] = vec_dot_f32_simd_x(assoc & 4, Tlim, vt_row, S);
+        }
+        free(vt_row);
+    } else
+    for (int d = 0; d < dk; d++) {
+        double acc = 0.0;
+        for (int j = 0; j < Tlim; j++) acc += (double)(V[(size_t)j * stride + d] * S[j]);
+        out[d] = (float)acc;
+    }
+    free(S);
+    return 0;
+}
+
 int bo_eval(bo_model *m, const int32_t *tokens, int N, int n_past, float *logits_last, float *logits_all) {
     if (!m || !m->layers || N < 1) return -1;
     const int D = m->d_model, F = m->d_ff, V = m->n_vocab, H = m->n_head, P = m->n_positions, L = m->n_layer;
@@ -1105,45 +1150,10 @@ int bo_eval(bo_model *m, const int32_t *tokens, int N, int n_past, float *logits
 #pragma omp parallel for schedule(static) num_threads(threads)
         for (int hi = 0; hi < H * N; hi++) {
             const int h = hi / N, i = hi % N;
-            float *S  = (float *)malloc(sizeof(float) * (size_t)T);
-            const float *qv = q + (size_t)i * D + (size_t)h * dk;
             int Tlim = T;
             if (m->opts.causal) Tlim = n_past + i + 1;
-            for (int j = 0; j < Tlim; j++) /* KQ = mul_mat(K, Q) */
-                S[j] = (m->opts.assoc & 1) ? vec_dot_f32_simd_x(m->opts.assoc & 4, dk, Kl + (size_t)j * D + (size_t)h * dk, qv) : vec_dot_f32(dk, Kl + (size_t)j * D + (size_t)h * dk, qv);
-            /* ggml_soft_max */
-            float mx = -INFINITY;
-            for (int j = 0; j < Tlim; j++)
-                if (S[j] > mx) mx = S[j];
-            double sum = 0.0;
-            for (int j = 0; j < Tlim; j++) {
-                float val;
-                if (m->opts.exp_f32) {
-                    val = expf(S[j] - mx);
-                } else {
-                    val = F16(g_table_exp[bo_fp32_to_fp16(S[j] - mx)]);
-                }
-                sum += (double)val;
-                S[j] = val;
-            }
-            sum              = 1.0 / sum;
-            const float fsum = (float)sum;
-            for (int j = 0; j < Tlim; j++) S[j] *= fsum; /* ggml_vec_scale_f32 */
-            /* KQV = mul_mat(V_trans, attn_weights): dot over T for each of the dk dims */
-            if (m->opts.assoc & 1) { /* V_trans row (contiguous over the keys) . probabilities, SIMD-shaped */
-                float *vt_row = (float *)malloc(sizeof(float) * (size_t)Tlim);
-                for (int d = 0; d < dk; d++) {
-                    for (int j = 0; j < Tlim; j++) vt_row[j] = Vl[(size_t)j * D + (size_t)h * dk + d];
-                    att[(size_t)i * D + (size_t)h * dk + d] = vec_dot_f32_simd_x(m->opts.assoc & 4, Tlim, vt_row, S);
-                }
-                free(vt_row);
-            } else
-            for (int d = 0; d < dk; d++) {
-                double acc = 0.0;
-                for (int j = 0; j < Tlim; j++) acc += (double)(Vl[(size_t)j * D + (size_t)h * dk + d] * S[j]);
-                att[(size_t)i * D + (size_t)h * dk + d] = (float)acc;
-            }
-            free(S);
+            bo_attn_head(q + (size_t)i * D + (size_t)h * dk, Kl + (size_t)h * dk, Vl + (size_t)h * dk, dk, D, Tlim, m->opts.exp_f32, m->opts.assoc,
+                         att + (size_t)i * D + (size_t)h * dk);
         }
 
         /* out projection + bias + residual (biogpt.cpp:767-772) */

@@ -92,6 +92,10 @@ int       bo_n_tensors(const bo_model *m);
  * returns 0 on success */
 int bo_eval(bo_model *m, const int32_t *tokens, int n, int n_past, float *logits_last, float *logits_all);
 
+/* the attention of one (head, query) inside bo_eval, callable alone: qv [dk] (already scaled), key / value row j of the head at K + j * stride / V + j * stride,
+ * T visible keys; exp_f32 and assoc as in bo_opts; out [dk].  returns 0 on success */
+int bo_attn_head(const float *qv, const float *K, const float *V, int dk, int64_t stride, int T, int exp_f32, int assoc, float *out);
+
 /* debugging taps: copy of the hidden state after layer `layer` (or -1: after embedding,
  * n_layer: after the final LayerNorm) for the most recent eval; out is [n][d_model] */
 int bo_tap(const bo_model *m, int layer, float *out);

@@ -78,6 +78,8 @@ def lib():
     L.bo_n_tensors.argtypes = [C.c_void_p]
     L.bo_eval.restype = C.c_int
     L.bo_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.bo_attn_head.restype = C.c_int
+    L.bo_attn_head.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.bo_tap.restype = C.c_int
     L.bo_tap.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.bo_kv.restype = C.POINTER(C.c_float)
@@ -212,3 +214,18 @@ def have_avx2():
 def vec_dot_q(wtype, k, wrow_bytes, yblocks_bytes):
     """The reference's scalar vec_dot of one weight row (file-format bytes) against an activation row already quantized to Q8_0 / Q8_1 blocks."""
     return float(lib().bo_vec_dot_q(int(wtype), int(k), C.c_char_p(bytes(wrow_bytes)), C.c_char_p(bytes(yblocks_bytes))))
+
+
+def attn_head(q, K, V, T, exp_f32=0, assoc=0):
+    """The attention of one (head, query) as bo_eval computes it (bo_attn_head): q [dk] float32 (already scaled), K / V float32 [rows >= T][dk] with any row
+    stride (the last axis contiguous), T visible keys.  Returns the head's dk outputs."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    dk = q.size
+    for a in (K, V):
+        assert a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == dk and a.shape[0] >= T and a.strides[1] == 4 and a.strides[0] % 4 == 0
+    assert K.strides[0] == V.strides[0]
+    out = np.zeros(dk, dtype=np.float32)
+    rc = lib().bo_attn_head(q.ctypes.data, K.ctypes.data, V.ctypes.data, dk, K.strides[0] // 4, int(T), int(exp_f32), int(assoc), out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("oracle attn_head failed rc=%d" % rc)
+    return out

@@ -1,6 +1,7 @@
 """attn_prefix_kernel<8> (decode attention of eight columns behind one shared prefix per workgroup) through biogpt_hip_attn_prefix_device: bit for bit the
-f32 rows and the Q8 blocks of the existing attn_fast_kernel<4, false, true> on the same inputs.  The existing kernel is the reference; it is held to the
-oracle by the tests of the calls that run it.  A mismatch here is a finding to report with its rows, not a tolerance to add."""
+f32 rows and the Q8 blocks of the existing attn_fast_kernel<4, false, true> on the same inputs.  The existing kernel is the reference here; both kernels are
+held to the oracle's attention, alone and bit for bit, by tests/test_gpu_attn_kernels.py.  A mismatch here is a finding to report with its rows, not a
+tolerance to add."""
 import numpy as np
 import pytest
 
