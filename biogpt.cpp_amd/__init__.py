@@ -10,6 +10,7 @@ Names mirror the reference: biogpt_model_load() -> BiogptModel, biogpt_eval() ->
 biogpt_model_quantize_internal()/quantize CLI -> quantize_file().
 """
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -39,6 +40,32 @@ class GenRules(C.Structure):
     """biogpt_hip_gen_rules (include/biogpt_hip.h): generation rules of generate_beam / generate_sample."""
     _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32), ("min_new_tokens", C.c_int32),
                 ("n_suppress", C.c_int32), ("suppress", C.POINTER(C.c_int32))]
+
+
+class GenLogprobs(C.Structure):
+    """biogpt_hip_gen_logprobs (include/biogpt_hip.h)."""
+    _fields_ = [("n_top", C.c_int32), ("lp", C.c_void_p), ("top_ids", C.c_void_p), ("top_lp", C.c_void_p)]
+
+
+class _LogprobArrays:
+    """The arrays of a logprobs=K request for n sequences of w entries, and the struct that names them."""
+
+    def __init__(self, k, n, w):
+        self.k = int(k)
+        if not 0 <= self.k <= 8:
+            raise ValueError("logprobs must be None or an integer in [0, 8] (got %r)" % (k,))
+        self.lp = np.zeros((max(n, 1), w), dtype=np.float32)
+        self.ids = np.full((max(n, 1), w, max(self.k, 1)), -1, dtype=np.int32)
+        self.top = np.zeros((max(n, 1), w, max(self.k, 1)), dtype=np.float32)
+        self.req = GenLogprobs(self.k, self.lp.ctypes.data, self.ids.ctypes.data, self.top.ctypes.data)
+
+    def info(self, n, got, lens):
+        """[(logprobs float32[len], top_ids int32[len, K], top_logprobs float32[len, K]), ...]: the call wrote rows of `got` entries."""
+        k = self.k
+        lp = self.lp.reshape(-1)[:n * got].reshape(n, got)
+        ids = self.ids.reshape(-1)[:n * got * k].reshape(n, got, k)
+        top = self.top.reshape(-1)[:n * got * k].reshape(n, got, k)
+        return [(lp[r, :lens[r]].copy(), ids[r, :lens[r]].copy(), top[r, :lens[r]].copy()) for r in range(n)]
 
 
 class EmbedOpts(C.Structure):
@@ -191,6 +218,23 @@ def logprob_rows(rows, targets, device=0):
     if lib().biogpt_hip_logprob_rows_device(int(device), a.ctypes.data, n, nv, t.ctypes.data, lp.ctypes.data, am.ctypes.data, lg.ctypes.data) != 0:
         raise BiogptError(_err())
     return lp, am, lg
+
+
+def genlp_rows(rows, n_top, mode=0, top_k=40, top_p=0.9, temp=0.9, states=None, device=0):
+    """The selection kernels of generation with log-probabilities on rows held in host memory (biogpt_hip_genlp_rows_device): mode 0
+    genlp_greedy_rows_kernel, mode 1 sample_lp_rows_kernel drawing from states (uint32 [n][625], advanced in place).  Returns (ids int32[n],
+    logprobs float32[n], top_ids int32[n, n_top], top_logprobs float32[n, n_top])."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv, k = int(a.shape[0]), int(a.shape[1]), int(n_top)
+    ids, lp = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float32)
+    tid, tlp = np.zeros((n, max(k, 1)), dtype=np.int32), np.zeros((n, max(k, 1)), dtype=np.float32)
+    if states is not None and not (states.dtype == np.uint32 and states.flags["C_CONTIGUOUS"] and states.shape == (n, 625)):
+        raise BiogptError("states must be a contiguous uint32 array [n][625]")
+    if lib().biogpt_hip_genlp_rows_device(int(device), int(mode), a.ctypes.data, n, nv, k, int(top_k), float(top_p), float(temp),
+                                          None if states is None else states.ctypes.data, ids.ctypes.data, lp.ctypes.data,
+                                          tid.ctypes.data if k > 0 else None, tlp.ctypes.data if k > 0 else None) != 0:
+        raise BiogptError(_err())
+    return ids, lp, tid[:, :k], tlp[:, :k]
 
 
 def lookup_draft(texts, n_gen, n_past, n_predict, max_draft=7, max_ngram=3, finished=None, device=0):
@@ -428,6 +472,10 @@ SYMBOLS = [
     ("biogpt_hip_generate_sample_prefix", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
                                                     C.c_int32, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_prefix_stats", C.c_int, [_P, _P]),
+    ("biogpt_hip_generate_greedy_batch_lp", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(GenLogprobs)]),
+    ("biogpt_hip_generate_sample_lp", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
+                                                C.c_int32, _P, _P, C.POINTER(C.c_double), C.POINTER(GenLogprobs)]),
+    ("biogpt_hip_genlp_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
     ("biogpt_hip_attn_device", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_attn_prefix_bench", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
@@ -629,6 +677,18 @@ def arena_bytes_for(hp):
     return int(lib().biogpt_hip_arena_bytes_for(C.byref(hp)))
 
 
+def _logprobs_keyword(plain):
+    """Adds the keyword-only logprobs=None to the generation method `plain`, whose own parameters, defaults and return value stay what they are (functools.wraps:
+    introspection reports the plain method; logprobs is the one keyword more the call accepts, behind all of them).  None: the method itself.  K: the method
+    of the same name with a leading underscore, given the same arguments and logprobs=K, which returns (ids, info, seconds)."""
+    @functools.wraps(plain)
+    def call(self, *args, logprobs=None, **kw):
+        if logprobs is None:
+            return plain(self, *args, **kw)
+        return getattr(BiogptModel, "_" + plain.__name__)(self, *args, logprobs=logprobs, **kw)
+    return call
+
+
 class BiogptModel:
     """biogpt_model + biogpt_vocab handle (biogpt.h:78-107, :37-48) living on one HIP device."""
 
@@ -728,12 +788,31 @@ class BiogptModel:
             raise BiogptError(_err())
         return out[:n].copy(), secs.value
 
+    @_logprobs_keyword
     def generate_greedy_batch(self, prompts, n_predict, n_batch=8, prefix=None):
         """Batched decode of several independent prompts (list of id lists) on this device.  prefix: a list of ids that stands in front of every
         prompt -- sequence s is prefix + prompts[s], and a prompt may then be empty.  The ids are those of the call on the concatenations; the
-        prefix is evaluated once ("Generation behind a shared prefix"; prefix_stats())."""
+        prefix is evaluated once ("Generation behind a shared prefix"; prefix_stats()).  logprobs (keyword only): None, or K in [0, 8] -- the
+        call then returns (ids, info, seconds) with info[s] = (logprobs float32[n], top_ids int32[n, K], top_logprobs float32[n, K]), n the
+        n_predict as clamped: the model's log-probability of every generated token, as score_batch gives it, and every row's K best entries
+        ("Log-probabilities of generated tokens"); the ids are those of the call without it."""
+        return BiogptModel._generate_greedy_batch(self, prompts, n_predict, n_batch, prefix)
+
+    def _generate_greedy_batch(self, prompts, n_predict, n_batch=8, prefix=None, logprobs=None):
+        """generate_greedy_batch, and with logprobs=K its form that returns (ids, info, seconds)."""
         lens = np.asarray([len(p) for p in prompts], dtype=np.int32)
         secs = C.c_double(0.0)
+        if logprobs is not None:
+            n_seqs = len(prompts)
+            out = np.zeros((max(n_seqs, 1), max(int(n_predict), 1)), dtype=np.int32)
+            arr = _LogprobArrays(logprobs, n_seqs, out.shape[1])
+            pre = None if prefix is None else _flat_ids([prefix])
+            flat = _flat_ids(prompts)
+            n = lib().biogpt_hip_generate_greedy_batch_lp(self._h, None if pre is None else pre.ctypes.data, 0 if prefix is None else len(prefix), flat.ctypes.data,
+                                                          lens.ctypes.data, n_seqs, int(n_batch), int(n_predict), out.ctypes.data, C.byref(secs), C.byref(arr.req))
+            if n < 0:
+                raise BiogptError(_err())
+            return out.reshape(-1)[:n_seqs * n].reshape(n_seqs, n).copy(), arr.info(n_seqs, n, [n] * n_seqs), secs.value
         if prefix is not None:
             out = np.zeros((max(len(prompts), 1), max(int(n_predict), 1)), dtype=np.int32)
             n_pre, pre = len(prefix), _flat_ids([prefix])
@@ -880,6 +959,7 @@ class BiogptModel:
         return ([rows[p * got:p * got + int(ol[p])].copy() for p in range(G)],
                 [dict(passes=int(st[p, 0]), drafted=int(st[p, 1]), accepted=int(st[p, 2])) for p in range(G)], secs.value)
 
+    @_logprobs_keyword
     def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
                         repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None, prefix=None):
         """n_samples sampled continuations of every prompt (list of id lists, or one flat id list), drawn on the device by the reference's top-k / top-p
@@ -890,7 +970,22 @@ class BiogptModel:
         (or EOS where one ends) in front of the sampler (biogpt_hip_generate_sample_trie; needs eos_id >= 0); top_k=1: constrained greedy decoding.
         prefix: a list of ids in front of every prompt -- sequence p is prefix + prompts[p], a prompt may then be empty ([[]]: n_samples of the prefix
         alone), the ids are those of the call on the concatenations and the prefix is evaluated once ("Generation behind a shared
-        prefix").  Not with rules or a trie: ValueError."""
+        prefix").  Not with rules or a trie: ValueError.
+        logprobs (keyword only): None, or K in [0, 8] -- the call then returns (ids, info, seconds) with info[r] = (logprobs float32[len], top_ids int32[len, K],
+        top_logprobs float32[len, K]): the model's log-probability of every generated token under the RAW row (temperature 1, no top_k / top_p cut: the
+        number score_batch gives, not the probability under the truncated sampling distribution) and every row's K best entries (INTEGRATION.md,
+        "Log-probabilities of generated tokens").  The ids are those of the call without it.  Not with rules or a trie: ValueError."""
+        return BiogptModel._generate_sample(self, prompts, n_predict, n_samples, top_k, top_p, temp, seed, seeds, eos_id, n_batch, repetition_penalty, no_repeat_ngram_size,
+                                            min_new_tokens, suppress_tokens, trie, prefix)
+
+    def _generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
+                         repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None, prefix=None, logprobs=None):
+        """generate_sample, and with logprobs=K its form that returns (ids, info, seconds)."""
+        if logprobs is not None:
+            if trie is not None:
+                raise ValueError("logprobs= cannot be combined with trie=")
+            if float(repetition_penalty) != 1.0 or int(no_repeat_ngram_size) != 0 or int(min_new_tokens) != 0 or len(suppress_tokens):
+                raise ValueError("logprobs= cannot be combined with generation rules")
         if prefix is not None:
             if trie is not None:
                 raise ValueError("prefix= cannot be combined with trie=")
@@ -914,6 +1009,19 @@ class BiogptModel:
         out = np.zeros((max(n, 1), w), dtype=np.int32)
         ol = np.zeros(max(n, 1), dtype=np.int32)
         secs = C.c_double(0.0)
+        if logprobs is not None:
+            arr = _LogprobArrays(logprobs, n, w)
+            pre = None if prefix is None else _flat_ids([prefix])
+            flat = _flat_ids(prompts)
+            got = lib().biogpt_hip_generate_sample_lp(self._h, None if pre is None else pre.ctypes.data, 0 if prefix is None else len(prefix), flat.ctypes.data,
+                                                      lens.ctypes.data, len(prompts), int(n_samples), int(n_batch), int(n_predict), int(top_k), float(top_p), float(temp),
+                                                      sd.ctypes.data, int(eos_id), out.ctypes.data, ol.ctypes.data, C.byref(secs), C.byref(arr.req))
+            if got < 0:
+                raise BiogptError(_err())
+            if got == 0:
+                return [], [], secs.value
+            rows = out.reshape(-1)
+            return [rows[r * got:r * got + int(ol[r])].copy() for r in range(n)], arr.info(n, got, [int(v) for v in ol[:n]]), secs.value
         if prefix is not None:
             pre = _flat_ids([prefix])
             got = lib().biogpt_hip_generate_sample_prefix(self._h, pre.ctypes.data, len(prefix), flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples),

@@ -44,6 +44,7 @@
 #include "kernels_embed.hip.h"
 #include "kernels_beam.hip.h"
 #include "kernels_sample.hip.h"
+#include "kernels_genlp.hip.h"
 #include "kernels_rules.hip.h"
 #include "kernels_trie.hip.h"
 #include "kernels_contrast.hip.h"
@@ -224,10 +225,10 @@ namespace {
 }  // namespace
 
 // The captured steps of one mode of column generation: [12 * (form of the step: 0 plain, 1 with rules, 2 with a trie, 3 behind a shared prefix read in
-// place) + 6 * (steps as column-per-XCD launches) + context bucket], valid for the call shape (key_a, key_b) they were captured for -- sequences, or
-// groups and beams
+// place, 4 with log-probabilities, 5 with log-probabilities behind a shared prefix read in place) + 6 * (steps as column-per-XCD launches) + context
+// bucket], valid for the call shape (key_a, key_b) they were captured for -- sequences, or groups and beams
 struct ColumnGraphs {
-    hipGraphExec_t exec[48] = {};
+    hipGraphExec_t exec[72] = {};
     int key_a = 0, key_b = 0;
 };
 
@@ -311,6 +312,9 @@ struct biogpt_hip_ctx {
     // prompt-lookup decoding (biogpt_hip_generate_lookup, kernels_lookup.hip.h): the step's device state at its largest (lookup_bufs_at), allocated at the
     // first such call -- captured steps keep their pointers
     uint8_t *lookup_buf = nullptr;
+    // log-probabilities of generated tokens (biogpt_hip_generate_*_lp, kernels_genlp.hip.h): GenLpCtl and the three result arrays at their largest
+    // (genlp_bufs_at), allocated at the first such call -- captured steps keep their pointers; a context that is never asked has none
+    uint8_t *genlp_buf = nullptr;
 
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1676,7 +1680,7 @@ void destroy(biogpt_hip_ctx *c) {
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf, (void *)c->genlp_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2463,6 +2467,7 @@ struct ColumnCall {
     int key_a = 0, key_b = 0;
     int extra_steps = 0;                // steps beyond one per token (contrastive: 1, the prompt's last token has a step of its own)
     int gset_extra = 0;                 // 12 with rules, 24 with a trie: another form of the step, so other graphs
+    bool with_lp = false;               // the selection also writes log-probabilities (kernels_genlp.hip.h; never with rules or a trie): graph sets of its own
     int key_stride = 1;                 // positions a column can move on in one step, at most (prompt-lookup decoding: 1 + max_draft); > 1: the word behind
                                         // live_dev holds the furthest position of any column
     bool plain_steps = false;           // the step is no decode step of one column per sequence: never the column-per-XCD launches
@@ -2712,7 +2717,7 @@ static int run_column_call(biogpt_hip_ctx *ctx, ColumnCall &cc, int n_predict, d
     cc.in_place = cc.n_shared > 0 && xc == 0;
     if (!upload_column_starts(ctx, prompts, lens, cc.n_prompts, cc.per_prompt, cc.n_shared, cc.in_place ? shared : SharedRows{})) return -2;
     if (cc.upload && !cc.upload()) return -2;
-    const int gset = 6 * xc + (cc.in_place ? 36 : cc.gset_extra);
+    const int gset = 6 * xc + (cc.with_lp ? (cc.in_place ? 60 : 48) : cc.in_place ? 36 : cc.gset_extra);
     const ColumnKeys keys{cc.max_len, cc.key_stride, ctx->hp.n_positions};
     bool use_graph;
     if (!capture_column_steps(ctx, *cc.graphs, gset, keys, n_steps, cc.step, &use_graph)) return -2;
@@ -2731,11 +2736,78 @@ static int run_column_call(biogpt_hip_ctx *ctx, ColumnCall &cc, int n_predict, d
     return cc.n_predict;
 }
 
-// prefix != null (biogpt_hip_generate_greedy_prefix): sequence s is prefix ++ prompt s, the prompts are suffixes and may be empty
+// ---- log-probabilities of generated tokens: what greedy batch and sampled generation add when asked (kernels_genlp.hip.h) ----------------------
+// The selection kernel of the step writes entry n_gen of every sequence into the context's block: GenLpCtl {n_top, stride = the call's n_predict as
+// clamped}, then lp [seqs][stride], top_ids and top_lp [seqs][stride][n_top] -- the layout of the caller's arrays, so the read-out is one copy each.
+// The block is allocated once, for GENLP_COLS sequences of n_positions entries with GENLP_MAX_TOP alternatives: a captured step keeps its pointers and,
+// n_top and stride being device words, serves every K.
+constexpr int GENLP_COLS = 512;     // columns of a call, at most
+struct GenLpBufs {
+    bgk::GenLpCtl *ctl;
+    float *lp;
+    int32_t *top_ids;
+    float *top_lp;
+    size_t bytes;
+    bgk::GenLpOut out() const { return bgk::GenLpOut{ctl, lp, top_ids, top_lp}; }
+};
+static GenLpBufs genlp_bufs_at(uint8_t *base, size_t entries, size_t n_top = bgk::GENLP_MAX_TOP) {
+    ByteLayout l;
+    GenLpBufs b{};
+    b.ctl = l.take<bgk::GenLpCtl>(base, 1); b.lp = l.take<float>(base, entries);
+    b.top_ids = l.take<int32_t>(base, entries * n_top); b.top_lp = l.take<float>(base, entries * n_top);
+    b.bytes = l.bytes();
+    return b;
+}
+// the request of a call, before any HIP call; n_vocab < 0: not known yet
+static bool check_gen_logprobs(const biogpt_hip_gen_logprobs *lp, int n_vocab) {
+    if (!lp) BG_FAIL(false, "null argument: logprobs");
+    if (!lp->lp) BG_FAIL(false, "null argument: logprobs.lp");
+    if (lp->n_top < 0 || lp->n_top > bgk::GENLP_MAX_TOP) BG_FAIL(false, "logprobs.n_top must be in [0, %d] (got %d)", bgk::GENLP_MAX_TOP, lp->n_top);
+    if (lp->n_top > 0 && !lp->top_ids) BG_FAIL(false, "null argument: logprobs.top_ids (n_top is %d)", lp->n_top);
+    if (lp->n_top > 0 && !lp->top_lp) BG_FAIL(false, "null argument: logprobs.top_lp (n_top is %d)", lp->n_top);
+    if (n_vocab >= 0 && lp->n_top > n_vocab) BG_FAIL(false, "logprobs.n_top (%d) exceeds n_vocab (%d)", lp->n_top, n_vocab);
+    return true;
+}
+static bool genlp_prepare(biogpt_hip_ctx *ctx, GenLpBufs *b) {
+    const size_t entries = (size_t)GENLP_COLS * ctx->hp.n_positions;
+    if (!ctx->genlp_buf) HIP_TRY(false, hipMalloc(&ctx->genlp_buf, genlp_bufs_at(nullptr, entries).bytes));
+    *b = genlp_bufs_at(ctx->genlp_buf, entries);
+    return true;
+}
+static bool genlp_upload(const GenLpBufs &b, int n_top, int stride) {
+    bgk::GenLpCtl h{};
+    h.n_top = n_top; h.stride = stride;
+    HIP_TRY(false, hipMemcpy(b.ctl, &h, sizeof(h), hipMemcpyHostToDevice));
+    return true;
+}
+// The call's results -> the caller's arrays: [n_seqs][n_predict] and [n_seqs][n_predict][n_top].  lens (or null: every sequence has n_predict entries):
+// entries at or past a sequence's length read 0 (lp, top_lp) and -1 (top_ids).
+static bool genlp_read(const GenLpBufs &b, const biogpt_hip_gen_logprobs *lp, int n_seqs, int n_predict, const int32_t *lens) {
+    const size_t n = (size_t)n_seqs * n_predict, K = (size_t)lp->n_top;
+    HIP_TRY(false, hipMemcpy(lp->lp, b.lp, n * 4, hipMemcpyDeviceToHost));
+    if (K > 0) {
+        HIP_TRY(false, hipMemcpy(lp->top_ids, b.top_ids, n * K * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(false, hipMemcpy(lp->top_lp, b.top_lp, n * K * 4, hipMemcpyDeviceToHost));
+    }
+    for (int r = 0; lens && r < n_seqs; r++) {
+        const size_t at = (size_t)r * n_predict + (size_t)lens[r], end = (size_t)(r + 1) * n_predict;
+        std::fill(lp->lp + at, lp->lp + end, 0.0f);
+        if (K > 0) {
+            std::fill(lp->top_ids + at * K, lp->top_ids + end * K, -1);
+            std::fill(lp->top_lp + at * K, lp->top_lp + end * K, 0.0f);
+        }
+    }
+    return true;
+}
+
+// prefix != null (biogpt_hip_generate_greedy_prefix): sequence s is prefix ++ prompt s, the prompts are suffixes and may be empty;
+// lp != null (biogpt_hip_generate_greedy_batch_lp): genlp_greedy_rows_kernel is the selection, and lp's arrays take the log-probabilities
 static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_seqs,
-                                      int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out, const int32_t *prefix = nullptr, int32_t n_prefix = 0) {
+                                      int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out, const int32_t *prefix = nullptr, int32_t n_prefix = 0,
+                                      const biogpt_hip_gen_logprobs *lp = nullptr) {
     clear_error();
     if (!ctx || !prompts || !prompt_lens || !out_ids) BG_FAIL(-1, "null argument");
+    if (lp && !check_gen_logprobs(lp, ctx->hp.n_vocab)) return -1;
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     if (prefix && (n_seqs < 1 || n_seqs > 511)) BG_FAIL(-1, "n_seqs must be in [1, 511] behind a prefix (got %d)", n_seqs);   // one slot holds the prefix
     if (prefix && !check_fast_chain(ctx, "generation behind a shared prefix")) return -1;
@@ -2748,9 +2820,18 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     cc.n_prompts = n_seqs; cc.n_batch = n_batch;
     cc.graphs = &ctx->graphs_greedy; cc.key_a = n_seqs;
     cc.prefix = prefix; cc.n_prefix = n_prefix;
+    GenLpBufs lb{};
+    if (lp) {
+        cc.with_lp = true;
+        cc.prepare = [&]() -> bool { return genlp_prepare(ctx, &lb); };
+        cc.upload = [&]() -> bool { return genlp_upload(lb, lp->n_top, cc.n_predict); };
+    }
     cc.step = [&](int t_max) -> bool {      // every step's arg-max is the next token
         if (!enqueue_forward(ctx, cc.in_place ? ForwardPass::decode_step_shared(n_seqs, t_max, cc.n_shared) : ForwardPass::decode_step(n_seqs, t_max))) return false;
-        hipLaunchKernelGGL(bgk::argmax_rows_kernel, dim3(n_seqs), dim3(bgk::ARGMAX_ROWS_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->seq, 0, ctx->seq_gen, P, 1);
+        if (lp)
+            hipLaunchKernelGGL(bgk::genlp_greedy_rows_kernel, dim3(n_seqs), dim3(bgk::LP_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->seq, ctx->seq_gen, P, 1, lb.out());
+        else
+            hipLaunchKernelGGL(bgk::argmax_rows_kernel, dim3(n_seqs), dim3(bgk::ARGMAX_ROWS_THREADS), 0, ctx->stream, ctx->logits_all, V, V, ctx->seq, 0, ctx->seq_gen, P, 1);
         HIP_TRY(false, hipGetLastError());
         return true;
     };
@@ -2759,6 +2840,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     std::vector<int32_t> gen((size_t)n_seqs * P);
     HIP_TRY(-2, hipMemcpy(gen.data(), ctx->seq_gen, gen.size() * 4, hipMemcpyDeviceToHost));
     for (int s = 0; s < n_seqs; s++) std::memcpy(out_ids + (size_t)s * n_predict, gen.data() + (size_t)s * P, (size_t)n_predict * 4);
+    if (lp && !genlp_read(lb, lp, n_seqs, n_predict, nullptr)) return -2;
     return n_predict;
 }
 int biogpt_hip_generate_greedy_batch(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_seqs,
@@ -2781,6 +2863,25 @@ int biogpt_hip_generate_greedy_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix
     if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_greedy_batch_once(ctx, suffixes, suffix_lens, n_seqs, n_batch, n_predict, out_ids, seconds_out, prefix, n_prefix);
+    });
+}
+// the pointers of a *_lp call: the request first (a caller's mistake there is named whatever else is wrong), then those of the form it takes
+static bool check_lp_pointers(const biogpt_hip_ctx *ctx, const biogpt_hip_gen_logprobs *lp, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes,
+                              const int32_t *suffix_lens) {
+    clear_error();
+    if (!check_gen_logprobs(lp, -1)) return false;
+    if (!prefix && n_prefix != 0) BG_FAIL(false, "n_prefix must be 0 without a prefix (got %d)", n_prefix);
+    if (prefix) return check_prefix_pointers(ctx, prefix, suffixes, suffix_lens);
+    if (!ctx) BG_FAIL(false, "null context");
+    return true;
+}
+// biogpt_hip_generate_greedy_batch (prefix == null) or biogpt_hip_generate_greedy_prefix with the log-probabilities of the generated tokens
+int biogpt_hip_generate_greedy_batch_lp(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes, const int32_t *suffix_lens, int32_t n_seqs,
+                                        int32_t n_batch, int32_t n_predict, int32_t *out_ids, double *seconds_out, const biogpt_hip_gen_logprobs *logprobs) {
+    if (!check_lp_pointers(ctx, logprobs, prefix, n_prefix, suffixes, suffix_lens)) return -1;
+    if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_greedy_batch_once(ctx, suffixes, suffix_lens, n_seqs, n_batch, n_predict, out_ids, seconds_out, prefix, prefix ? n_prefix : 0, logprobs);
     });
 }
 int biogpt_hip_prefix_stats(const biogpt_hip_ctx *ctx, int32_t out[4]) {
@@ -3363,10 +3464,12 @@ static bgk::SampleCtl sample_ctl_of(int top_k, int eos_id, int n_seqs, double to
 static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
                                 int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
                                 int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules, biogpt_hip_trie *trie = nullptr,
-                                const int32_t *prefix = nullptr, int32_t n_prefix = 0) {
+                                const int32_t *prefix = nullptr, int32_t n_prefix = 0, const biogpt_hip_gen_logprobs *lp = nullptr) {
     clear_error();
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompts || !prompt_lens || !seeds || !out_ids || !out_lens) BG_FAIL(-1, "null argument");
+    if (lp && !check_gen_logprobs(lp, ctx->hp.n_vocab)) return -1;
+    if (lp && (rules || trie)) BG_FAIL(-1, "log-probabilities cannot be combined with generation rules or a trie");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     if (prefix && (n_prompts < 1 || n_samples < 1 || (int64_t)n_prompts * n_samples > 511))
         BG_FAIL(-1, "n_prompts x n_samples must be in [1, 511] behind a prefix");   // one slot holds the prefix
@@ -3384,13 +3487,16 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     if (trie && !check_trie_vocab(trie, V)) return -1;
     const bool ru = rules_active(rules, eos_id);
     SampleBufs sb{};
+    GenLpBufs lb{};
     ColumnCall cc(ctx);
     cc.prompts = prompts; cc.prompt_lens = prompt_lens;
     cc.n_prompts = n_prompts; cc.per_prompt = n_samples; cc.n_batch = n_batch;
     cc.graphs = &ctx->graphs_sample; cc.key_a = n_seqs;
     cc.gset_extra = trie ? 24 : ru ? 12 : 0;
     cc.prefix = prefix; cc.n_prefix = n_prefix;     // (prefix != null, biogpt_hip_generate_sample_prefix: the prompts are suffixes and may be empty; no rules, no trie)
+    cc.with_lp = lp != nullptr;                     // (biogpt_hip_generate_sample_lp: sample_lp_rows_kernel is the selection; no rules, no trie)
     cc.prepare = [&]() -> bool {
+        if (lp && !genlp_prepare(ctx, &lb)) return false;
         if (n_seqs > ctx->sample_cap) {
             if (ctx->sample_ctl) (void)hipFree(ctx->sample_ctl);
             ctx->sample_ctl = nullptr; ctx->sample_cap = 0;
@@ -3408,6 +3514,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
         *hb.ctl = sample_ctl_of(top_k, eos_id, n_seqs, top_p, temp);
         for (int r = 0; r < n_seqs; r++) { bgk::mt_seed(seeds[r], hb.seq[r].mt); bgk::mt_regenerate(hb.seq[r].mt); }
         HIP_TRY(false, hipMemcpy(sb.ctl, h.data(), h.size(), hipMemcpyHostToDevice));
+        if (lp && !genlp_upload(lb, lp->n_top, cc.n_predict)) return false;
         if (trie && !trie_upload(ctx, trie, 0, eos_id)) return false;
         return !ru || rules_upload(ctx, rules, 0, eos_id, prompts, prompt_lens, n_prompts, n_samples);
     };
@@ -3415,7 +3522,11 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
         if (!enqueue_forward(ctx, cc.in_place ? ForwardPass::decode_step_shared(n_seqs, t_max, cc.n_shared) : ForwardPass::decode_step(n_seqs, t_max))) return false;
         if (ru && !enqueue_rules(ctx, n_seqs, &sb.seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
         if (trie && !enqueue_trie(ctx, n_seqs, &sb.seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
-        hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, sb.ctl, sb.seq, ctx->seq, ctx->seq_gen, P);
+        if (lp)
+            hipLaunchKernelGGL(bgk::sample_lp_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, sb.ctl, sb.seq, ctx->seq, ctx->seq_gen, P,
+                               lb.out());
+        else
+            hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, sb.ctl, sb.seq, ctx->seq, ctx->seq_gen, P);
         HIP_TRY(false, hipGetLastError());
         return true;
     };
@@ -3432,6 +3543,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
         std::memcpy(o, gen.data() + (size_t)r * P, (size_t)len * 4);
         out_lens[r] = len;
     }
+    if (lp && !genlp_read(lb, lp, n_seqs, n_predict, out_lens)) return -2;
     return n_predict;
 }
 
@@ -3458,6 +3570,17 @@ int biogpt_hip_generate_sample_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_sample_once(ctx, suffixes, suffix_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, nullptr,
                                     nullptr, prefix, n_prefix);
+    });
+}
+
+// biogpt_hip_generate_sample (prefix == null) or biogpt_hip_generate_sample_prefix with the log-probabilities of the generated tokens; no rules, no trie
+int biogpt_hip_generate_sample_lp(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes, const int32_t *suffix_lens, int32_t n_prompts,
+                                  int32_t n_samples, int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
+                                  int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_logprobs *logprobs) {
+    if (!check_lp_pointers(ctx, logprobs, prefix, n_prefix, suffixes, suffix_lens)) return -1;
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_sample_once(ctx, suffixes, suffix_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, nullptr,
+                                    nullptr, prefix, prefix ? n_prefix : 0, logprobs);
     });
 }
 

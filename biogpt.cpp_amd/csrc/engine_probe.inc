@@ -640,6 +640,63 @@ int biogpt_hip_sample_rows_device(int device, const float *logits, int32_t n_row
     return 0;
 }
 
+// genlp_greedy_rows_kernel (mode 0) or sample_lp_rows_kernel (mode 1) over rows held in host memory (tests of the kernels themselves), one entry per row
+// (stride 1): ids_out [n_rows] the chosen ids, lp_out [n_rows] their log-probabilities, top_ids_out / top_lp_out [n_rows][n_top] the rows' best entries
+// (null with n_top 0).  Mode 1 draws as biogpt_hip_sample_rows_device does (top_k, top_p, temp, mt_states: 625 words per row, advanced in place); mode 0
+// ignores those four.  The outputs are filled with 0xff bytes before the launch.
+int biogpt_hip_genlp_rows_device(int device, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t top_k, double top_p, double temp,
+                                 uint32_t *mt_states, int32_t *ids_out, float *lp_out, int32_t *top_ids_out, float *top_lp_out) {
+    clear_error();
+    if (mode != 0 && mode != 1) BG_FAIL(-1, "mode must be 0 (greedy) or 1 (sampled)");
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!ids_out) BG_FAIL(-1, "ids_out is NULL");
+    if (n_rows < 1 || n_rows > 4096) BG_FAIL(-1, "n_rows must be in [1, 4096]");
+    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
+    const biogpt_hip_gen_logprobs req{n_top, lp_out, top_ids_out, top_lp_out};
+    if (!check_gen_logprobs(&req, n_vocab)) return -1;
+    if (mode == 1) {
+        if (!mt_states) BG_FAIL(-1, "mt_states is NULL");
+        if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > n_vocab) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
+        if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
+        if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
+        for (int r = 0; r < n_rows; r++)
+            if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sample_bufs_at(nullptr, (size_t)n_rows).bytes, lp_b = genlp_bufs_at(nullptr, (size_t)n_rows, (size_t)n_top).bytes;
+    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = (size_t)n_rows * 4;
+    std::vector<uint8_t> h(sq_b, 0);
+    const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_rows);
+    *hb.ctl = sample_ctl_of(mode == 1 ? top_k : 1, -1, n_rows, top_p, temp);
+    for (int r = 0; mode == 1 && r < n_rows; r++) std::memcpy(hb.seq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
+    ByteLayout l;      // [logits | ctl + states | column states | ids | the log-probability block]
+    const size_t o_lg = l.part(lg_b), o_sq = l.part(sq_b), o_st = l.part(st_b), o_id = l.part(id_b), o_lp = l.part(lp_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    const SampleBufs sb = sample_bufs_at(d.p + o_sq, (size_t)n_rows);
+    const GenLpBufs lb = genlp_bufs_at(d.p + o_lp, (size_t)n_rows, (size_t)n_top);
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(sb.ctl, h.data(), sq_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_st, 0, st_b));
+    HIP_TRY(-2, hipMemset(d.p + o_id, 0xff, l.bytes() - o_id));
+    if (!genlp_upload(lb, n_top, 1)) return -2;
+    if (mode == 0)
+        hipLaunchKernelGGL(bgk::genlp_greedy_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, d.at<bgk::SeqState>(o_st),
+                           d.at<int32_t>(o_id), 1, 1, lb.out());
+    else
+        hipLaunchKernelGGL(bgk::sample_lp_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, sb.ctl, sb.seq,
+                           d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), 1, lb.out());
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
+    if (!genlp_read(lb, &req, n_rows, 1, nullptr)) return -2;
+    if (mode == 1) {
+        HIP_TRY(-2, hipMemcpy(h.data(), sb.ctl, sq_b, hipMemcpyDeviceToHost));
+        for (int r = 0; r < n_rows; r++) std::memcpy(mt_states + (size_t)r * 625, hb.seq[r].mt, 625 * 4);
+    }
+    return 0;
+}
+
 // SURVEY 8 f1 on the device: `nrows` rows of `k` f32 values (host memory) -> the file's block format of `type`, byte-identical to
 // the host quantizer (biogpt_hip_quantize_file uses the host one: it has to work without a GPU)
 int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, int64_t nrows, int64_t k, uint8_t *dst) {

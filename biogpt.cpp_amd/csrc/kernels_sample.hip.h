@@ -13,6 +13,8 @@
 //                                     double.  The per-candidate operations run one per thread, the sums in candidate order on thread 0.
 //                          append     the id to the sequence's history, its next token and position; an EOS sets the sequence's finished
 //                                     flag instead: a finished column keeps its token and position (it recomputes the K / V row it has).
+//                        The step is sample_rows_step<Extra>; sample_rows_kernel instantiates it with SamplePlain (nothing added), sample_lp_rows_kernel
+//                        (kernels_genlp.hip.h) with the log-probabilities of the drawn token and of the row's best entries.
 //   kv_share_kernel      before the first step of a call with several samples per prompt: the prompt's K / V rows from the slot of the
 //                        prompt's first sample to the slots of the others (head-major cache: one contiguous run per (layer, head)).
 //   kv_prefix_copy_kernel  a call behind a shared prefix whose steps know one slot per sequence: the prefix's shared rows from the slot they were
@@ -212,9 +214,21 @@ __device__ __forceinline__ int sample_topk(const float *row, int n_vocab, int K,
     return k_eff;
 }
 
+// What a kernel may add to the step of sample_rows_kernel without touching its draw (sample_lp_rows_kernel, kernels_genlp.hip.h: the log-probabilities of
+// the drawn token and of the row's best): also_select() more candidates wanted than top_k (they follow the top_k in the same order, so the draw sees the
+// candidates it would have seen); row_stats() by every thread behind the selection (k_all candidates in top_v, visible); emit() by thread 0 with the
+// sequence's entry g and the drawn candidate's index.  This one adds nothing.
+struct SamplePlain {
+    __device__ __forceinline__ int also_select() const { return 0; }
+    __device__ __forceinline__ void row_stats(const float *, int, const float *, int) {}
+    __device__ __forceinline__ void emit(int, int, int, const float *, const int *, int) {}
+};
+
+// The step of one row, by the SAMPLE_THREADS threads of its workgroup.
 // logits: [rows][ldl] (row r = column r = sequence r); seq / sq: the rows' states; seq_gen: [row][gen_stride] token histories
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float *logits, int ldl, int n_vocab, SampleCtl *ctl, SampleSeq *sq,
-                                                                     SeqState *seq, int32_t *seq_gen, int gen_stride) {
+template <class Extra>
+__device__ __forceinline__ void sample_rows_step(const float *logits, int ldl, int n_vocab, SampleCtl *ctl, SampleSeq *sq, SeqState *seq, int32_t *seq_gen,
+                                                 int gen_stride, Extra extra) {
     __shared__ float top_v[SAMPLE_MAX_K];
     __shared__ int top_i[SAMPLE_MAX_K];
     __shared__ uint32_t mt_old[MT_N], mt_new[MT_N];
@@ -245,15 +259,21 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float
         __syncthreads();
     }
 
-    const int k_eff = sample_topk(row, n_vocab, K, top_v, top_i);
+    const int k_all = sample_topk(row, n_vocab, max(K, min(min(extra.also_select(), SAMPLE_MAX_K), n_vocab)), top_v, top_i);
+    const int k_eff = min(k_all, K);
+    extra.row_stats(row, n_vocab, top_v, k_all);
 
     // ---- the draw ----
-    int id = 0;
-    if (k_eff > 0) id = top_i[sample_tail(top_v, k_eff, ctl->top_p, ctl->temp, me->mt, work_p, work, tid, SAMPLE_THREADS, SampleBlockSync())];
+    int pick = 0, id = 0;
+    if (k_eff > 0) {
+        pick = sample_tail(top_v, k_eff, ctl->top_p, ctl->temp, me->mt, work_p, work, tid, SAMPLE_THREADS, SampleBlockSync());
+        id = top_i[pick];
+    }
     if (tid == 0) {
         SeqState *s = seq + r;
         const int g = s->n_gen;
         if (g < gen_stride) seq_gen[(size_t)r * gen_stride + g] = id;
+        extra.emit(r, g, pick, top_v, top_i, k_all);
         s->n_gen = g + 1;
         if (ctl->eos_id >= 0 && id == ctl->eos_id) {
             me->finished = 1;
@@ -263,6 +283,11 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float
             s->n_past += 1;
         }
     }
+}
+
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float *logits, int ldl, int n_vocab, SampleCtl *ctl, SampleSeq *sq,
+                                                                     SeqState *seq, int32_t *seq_gen, int gen_stride) {
+    sample_rows_step(logits, ldl, n_vocab, ctl, sq, seq, seq_gen, gen_stride, SamplePlain());
 }
 
 // grid (n_layer * n_head, n_seqs, 2 [K, V]); seq_stride floats between two slots, P * dk between two heads.  Sequence r with r % n_samples != 0

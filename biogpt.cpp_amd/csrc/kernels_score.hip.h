@@ -20,12 +20,11 @@ namespace bgk {
 
 constexpr int LP_THREADS = 256;   // 4 waves per column; 42384 logits = 41 float4 per lane
 
-// The two passes over one logits row by a workgroup of LP_THREADS threads (shared with beam_group_rows_kernel, kernels_beam.hip.h).
-// Every thread returns the row maximum m and its lowest arg-max bi; thread 0 also the exponential sum S = sum_v exp(l[v] - m).
-__device__ __forceinline__ void lp_row_stats(const float *row, int n_vocab, float &m, int &bi, double &S) {
+// The second pass alone, for a caller that holds the row maximum m already (every thread the same; sample_lp_rows_kernel, kernels_genlp.hip.h, has it from its
+// selection): thread 0 returns S = sum_v exp(l[v] - m).  One barrier; whatever shares LP_THREADS with it and came before has passed a barrier of its own.
+__device__ __forceinline__ void lp_row_sum(const float *row, int n_vocab, float m, double &S) {
     __shared__ double s_sum[LP_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    row_argmax<LP_THREADS>(row, n_vocab, m, bi);
     // sum of exp(l - m): head, then the quads, then the tail; each quad as (x + y) + (z + w)
     float s = 0.0f;
     row_scan<LP_THREADS>(
@@ -37,6 +36,13 @@ __device__ __forceinline__ void lp_row_stats(const float *row, int n_vocab, floa
     S = 0.0;
     if (tid == 0)
         for (int w = 0; w < LP_THREADS / 64; w++) S += s_sum[w];
+}
+
+// The two passes over one logits row by a workgroup of LP_THREADS threads (shared with beam_group_rows_kernel, kernels_beam.hip.h, and the selection kernels
+// of kernels_genlp.hip.h).  Every thread returns the row maximum m and its lowest arg-max bi; thread 0 also the exponential sum S = sum_v exp(l[v] - m).
+__device__ __forceinline__ void lp_row_stats(const float *row, int n_vocab, float &m, int &bi, double &S) {
+    row_argmax<LP_THREADS>(row, n_vocab, m, bi);
+    lp_row_sum(row, n_vocab, m, S);
 }
 
 // logits: [N][ldl] floats (N = gridDim.x); targets / lp_out / am_out / lg_out: [N], already offset to the pass's first column.

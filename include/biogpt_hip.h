@@ -563,6 +563,48 @@ int biogpt_hip_generate_sample_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix
  * rows reach the columns' slots by a copy (also with n_shared == 0, when there was nothing to copy), 0 where they run on the launch chain and read shared rows in place.  Returns 0, or -1 for a null argument. */
 int biogpt_hip_prefix_stats(const biogpt_hip_ctx *ctx, int32_t out[4]);
 
+/* ---- log-probabilities of generated tokens: the model's confidence in what it generated, without a second pass (transformers' output_scores /
+ * compute_transition_scores, the logprobs = k of OpenAI-style interfaces) ----
+ * For sequence r and its generated token t < out_lens[r] (greedy: every t < the clamped n_predict), with l the f32 logits row the token was chosen
+ * from -- the raw row: temperature 1, neither top_k nor top_p applied -- m = max l and S = sum_v exp(l[v] - m):
+ *   lp[r][t] = (l[id] - m) - log(S), the arithmetic of biogpt_hip_score (f32 lane sums combined in double, rounded once): the model's log-probability
+ *   of the emitted token, bit for bit what biogpt_hip_score_batch returns for the concatenation prompt_r ++ ids_r with n_batch = 1 -- NOT the
+ *   probability under the truncated sampling distribution;
+ *   top_ids[r][t][0 .. n_top) / top_lp[r][t][0 .. n_top): the row's first n_top entries, value descending and equal values lower id first, with their
+ *   log-probabilities by the same formula.  top_ids[r][t][0] is the row's arg-max: in greedy generation the emitted id.
+ * lp is [n][w] and top_ids / top_lp are [n][w][n_top], n the call's sequences and w the n_predict the call returns (as out_ids is [n][w]).  Entries at
+ * or past a sequence's length are 0 (lp, top_lp) and -1 (top_ids); an EOS that ended a sampled sequence counts as generated and has its entry.
+ * n_top in [0, 8]; with 0 top_ids and top_lp are not touched and may be NULL.  The selection kernel of the captured step writes the numbers
+ * (csrc/kernels_genlp.hip.h), n_top travels in device memory: one set of captured steps serves every n_top. */
+typedef struct biogpt_hip_gen_logprobs {
+    int32_t  n_top;
+    float   *lp;
+    int32_t *top_ids;
+    float   *top_lp;
+} biogpt_hip_gen_logprobs;
+/* biogpt_hip_generate_greedy_batch / biogpt_hip_generate_sample with log-probabilities.  The arguments are those of the _prefix forms: prefix == NULL
+ * with n_prefix == 0 is the plain call on the prompts `suffixes` (none empty then), otherwise the call behind the shared prefix, on either of its
+ * paths.  The ids, the lengths, the generator's stream and the return value are those of the call without log-probabilities, bit for bit.  Argument
+ * errors return -1 before any HIP call, the message naming the field: logprobs NULL, logprobs.lp NULL, logprobs.n_top outside [0, 8], n_top > 0 with
+ * logprobs.top_ids or logprobs.top_lp NULL, n_top > n_vocab, n_prefix != 0 without a prefix, and those of the calls without log-probabilities.  There
+ * is no form with generation rules or a trie, and none for beam search, contrastive search, prompt-lookup decoding or biogpt_hip_generate_greedy. */
+int biogpt_hip_generate_greedy_batch_lp(biogpt_hip_ctx *ctx, const int32_t *prefix /* or NULL */, int32_t n_prefix, const int32_t *suffixes /* concatenated */,
+                                        const int32_t *suffix_lens, int32_t n_seqs, int32_t n_batch, int32_t n_predict, int32_t *out_ids,
+                                        double *seconds_out /* may be NULL */, const biogpt_hip_gen_logprobs *logprobs);
+int biogpt_hip_generate_sample_lp(biogpt_hip_ctx *ctx, const int32_t *prefix /* or NULL */, int32_t n_prefix, const int32_t *suffixes /* concatenated */,
+                                  const int32_t *suffix_lens, int32_t n_prompts, int32_t n_samples, int32_t n_batch, int32_t n_predict,
+                                  int32_t top_k, double top_p, double temp, const uint32_t *seeds /* [n_prompts * n_samples] */,
+                                  int32_t eos_id /* -1: none */, int32_t *out_ids, int32_t *out_lens, double *seconds_out /* may be NULL */,
+                                  const biogpt_hip_gen_logprobs *logprobs);
+/* Test hook: the two selection kernels alone over rows held in host memory ([n_rows][n_vocab] f32, any width and alignment), one entry per row.  mode 0:
+ * genlp_greedy_rows_kernel; mode 1: sample_lp_rows_kernel, drawing as biogpt_hip_sample_rows_device does (top_k, top_p, temp; mt_states: 625 words per
+ * row, advanced in place) -- mode 0 ignores those four.  ids_out [n_rows]: the chosen ids; lp_out [n_rows]; top_ids_out / top_lp_out [n_rows][n_top]
+ * (NULL with n_top 0).  Argument errors (those of logprobs above with n_vocab the argument, mode, NULL pointers, n_rows outside [1, 4096], and in mode 1
+ * those of biogpt_hip_sample_rows_device) return -1 before any HIP call.  Returns 0, < 0 on error. */
+int biogpt_hip_genlp_rows_device(int device, int32_t mode /* 0 greedy, 1 sampled */, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top,
+                                 int32_t top_k, double top_p, double temp, uint32_t *mt_states, int32_t *ids_out, float *lp_out, int32_t *top_ids_out,
+                                 float *top_lp_out);
+
 /* ---- hidden states, pooled embeddings, classification heads (no counterpart in the reference) ----
  * The activations in front of the lm_head, from the causal passes of biogpt_hip_score without the lm_head and the log-softmax.
  *
