@@ -68,6 +68,15 @@ class _LogprobArrays:
         return [(lp[r, :lens[r]].copy(), ids[r, :lens[r]].copy(), top[r, :lens[r]].copy()) for r in range(n)]
 
 
+class QueueStats(C.Structure):
+    """biogpt_hip_queue_stats"""
+    _fields_ = [("columns", C.c_int32), ("steps", C.c_int32), ("groups", C.c_int32), ("admissions", C.c_int32), ("prompt_columns", C.c_int32),
+                ("busy_column_steps", C.c_int64), ("column_steps", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class EmbedOpts(C.Structure):
     """biogpt_hip_embed_opts (include/biogpt_hip.h): what embed_batch returns per sequence."""
     _fields_ = [("layer", C.c_int32), ("pooling", C.c_int32), ("normalize", C.c_int32), ("n_out", C.c_int32),
@@ -291,6 +300,20 @@ def lookup_accept(rows, drafts, n_gen, n_past, n_predict, max_draft, eos_id=-1, 
     return [[int(v) for v in emit[s] if v >= 0] for s in range(n)], state[:n].copy(), stats[:n].copy(), (int(live[0]), int(live[1]))
 
 
+def queue_plan(gen_lens, max_columns, group):
+    """The schedule of BiogptModel.generate_queue from the generated lengths alone (biogpt_hip_queue_plan: the host struct the call itself drives, no device):
+    ({"stats": {...}, "admit_step": [...], "column": [...]}); a request of length 0 never takes a column (-1 in both lists); prompt_columns stays 0."""
+    gl = np.ascontiguousarray(gen_lens, dtype=np.int32).reshape(-1)
+    n = int(gl.size)
+    if n == 0:
+        gl = np.zeros(1, np.int32)
+    adm, col = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+    st = QueueStats()
+    if lib().biogpt_hip_queue_plan(gl.ctypes.data, n, int(max_columns), int(group), adm.ctypes.data, col.ctypes.data, C.byref(st)) != 0:
+        raise BiogptError(_err())
+    return {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:n]], "column": [int(v) for v in col[:n]]}
+
+
 def beam_rows(rows, n_beams, run_score, given=False, first_step=False, device=0, masked=False):
     """beam_group_rows_kernel on rows held in host memory (biogpt_hip_beam_rows_device): rows float32 [G * n_beams][n_vocab], run_score [G * n_beams].
     Returns (score float32, col int32, id int32), each [G * n_beams][2 * n_beams]; rows the kernel left alone hold (NaN, -1, -1).  masked (with given):
@@ -444,6 +467,9 @@ SYMBOLS = [
     ("biogpt_hip_generate_contrastive", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_contrast_rank_device", C.c_int, [C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P]),
     ("biogpt_hip_generate_lookup", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_generate_queue", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32,
+                                           _P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(QueueStats)]),
+    ("biogpt_hip_queue_plan", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(QueueStats)]),
     ("biogpt_hip_lookup_draft_device", C.c_int, [C.c_int, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("biogpt_hip_lookup_accept_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_rules_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(GenRules), _P]),
@@ -958,6 +984,44 @@ class BiogptModel:
         rows = out.reshape(-1)      # rows are [G][n_predict as clamped]
         return ([rows[p * got:p * got + int(ol[p])].copy() for p in range(G)],
                 [dict(passes=int(st[p, 0]), drafted=int(st[p, 1]), accepted=int(st[p, 2])) for p in range(G)], secs.value)
+
+    def generate_queue(self, prompts, n_predict, max_columns=64, group=4, top_k=1, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8, n_predicts=None):
+        """Generation over a queue of requests (continuous batching; INTEGRATION.md, "Generation over a queue"): prompts is a list of id lists of any length,
+        at most max_columns of them run at a time, and a request that finishes -- by eos_id, or after its own n_predicts[r] (None: n_predict) tokens as
+        clamped to ITS prompt -- hands its column to the next one.  Request r's ids are those of generate_sample([prompts[r]], n_r, top_k, top_p, temp,
+        seeds=[seeds[r]], eos_id, n_batch) alone, whatever else is in the queue; seeds=None: seed + r.  top_k=1 (the default) never draws: greedy decoding
+        with an EOS.  group: steps between two looks at the columns.  Returns ([ids int32[len], ...] in request order, {"stats": {...}, "admit_step":
+        [...], "column": [...]}, seconds); a request without room for a token gets no ids and -1 in both lists."""
+        if len(prompts) and np.isscalar(prompts[0]):
+            prompts = [prompts]
+        R = len(prompts)
+        lens = np.asarray([len(p) for p in prompts] or [0], dtype=np.int32)
+        flat = _flat_ids(prompts)
+        if seeds is None:
+            seeds = [(int(seed) + r) & 0xFFFFFFFF for r in range(R)]
+        sd = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        if sd.size != R:
+            raise BiogptError("seeds must have one entry per request (%d != %d)" % (sd.size, R))
+        np_arr = None
+        if n_predicts is not None:
+            np_arr = np.ascontiguousarray(n_predicts, dtype=np.int32).reshape(-1)
+            if np_arr.size != R:
+                raise BiogptError("n_predicts must have one entry per request (%d != %d)" % (np_arr.size, R))
+        if sd.size == 0:
+            sd = np.zeros(1, np.uint32)
+        w = max(int(n_predict), 0)
+        out = np.zeros((max(R, 1), max(w, 1)), dtype=np.int32)
+        ol, adm, col = (np.zeros(max(R, 1), dtype=np.int32) for _ in range(3))
+        st = QueueStats()
+        secs = C.c_double(0.0)
+        rc = lib().biogpt_hip_generate_queue(self._h, flat.ctypes.data, lens.ctypes.data, R, None if np_arr is None or R == 0 else np_arr.ctypes.data, int(n_predict),
+                                             int(max_columns), int(group), int(n_batch), int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id),
+                                             out.ctypes.data, ol.ctypes.data, adm.ctypes.data, col.ctypes.data, C.byref(secs), C.byref(st))
+        if rc < 0:
+            raise BiogptError(_err())
+        rows = out.reshape(-1)      # rows are [R][n_predict as given]
+        ids = [rows[r * w:r * w + int(ol[r])].copy() for r in range(R)]
+        return ids, {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:R]], "column": [int(v) for v in col[:R]]}, secs.value
 
     @_logprobs_keyword
     def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,

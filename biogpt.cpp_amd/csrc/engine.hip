@@ -49,6 +49,7 @@
 #include "kernels_trie.hip.h"
 #include "kernels_contrast.hip.h"
 #include "kernels_lookup.hip.h"
+#include "kernels_queue.hip.h"
 #include "model_file.h"
 #include "quant_host.h"
 #include "trie_host.h"
@@ -289,7 +290,7 @@ struct biogpt_hip_ctx {
     int launch_parity = 0;
     // column generation (greedy batch, sampling, beam search; the driver stands before generate_greedy_batch_once): the captured steps of each mode,
     // and the pinned word pair + event pair through which the host reads a mode's count of unfinished sequences / searches between groups of steps
-    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam, graphs_contrast, graphs_lookup;
+    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam, graphs_contrast, graphs_lookup, graphs_queue;
     int32_t *live_host = nullptr;
     hipEvent_t live_ev[2] = {};
     // sampled generation (biogpt_hip_generate_sample, kernels_sample.hip.h): the call's parameters + one generator state per sequence (SampleCtl, then
@@ -315,6 +316,10 @@ struct biogpt_hip_ctx {
     // log-probabilities of generated tokens (biogpt_hip_generate_*_lp, kernels_genlp.hip.h): GenLpCtl and the three result arrays at their largest
     // (genlp_bufs_at), allocated at the first such call -- captured steps keep their pointers; a context that is never asked has none
     uint8_t *genlp_buf = nullptr;
+    // generation over a queue (biogpt_hip_generate_queue, kernels_queue.hip.h): the step's device state at its largest (queue_bufs_at), allocated at the
+    // first such call -- captured steps keep their pointers -- and its pinned twin: the header the host reads behind a group, the admit list it uploads
+    uint8_t *queue_buf = nullptr;
+    uint8_t *queue_host = nullptr;
 
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -392,7 +397,7 @@ static void drop_graphs(ColumnGraphs &gs) {
 }
 // Captured column steps hold the pointers of seq / bk / bv / logits_all and launch shapes chosen from the options: whatever replaces one of those drops them all
 static void drop_column_graphs(biogpt_hip_ctx *c) {
-    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam, &c->graphs_contrast, &c->graphs_lookup}) drop_graphs(*gs);
+    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam, &c->graphs_contrast, &c->graphs_lookup, &c->graphs_queue}) drop_graphs(*gs);
 }
 
 namespace {
@@ -1674,13 +1679,14 @@ void destroy(biogpt_hip_ctx *c) {
     drop_column_graphs(c);
     for (auto &e : c->live_ev) if (e) (void)hipEventDestroy(e);
     if (c->live_host) (void)hipHostFree(c->live_host);
+    if (c->queue_host) (void)hipHostFree(c->queue_host);
     xpipe_release(c);
     if (c->topk_host) (void)hipHostFree(c->topk_host);
     if (c->mbox_host) (void)hipHostFree(c->mbox_host);
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf, (void *)c->genlp_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf, (void *)c->genlp_buf, (void *)c->queue_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2390,9 +2396,11 @@ static bool flush_columns(biogpt_hip_ctx *ctx, std::vector<bgk::SeqState> &cols,
 // (flat0 = flat index of its first token).  Sequence s fills the K / V cache slot slot0 + s * slot_stride.  shared.n > 0: every sequence stands behind
 // shared.n rows that lie in slot shared.slot (a multiple of n_batch, so the chunks are those of the whole sequence): its first token has position shared.n
 // and its columns read those rows in place (SeqState::pad[0] / pad[1]; the pass is ForwardPass::packed_continuations).
+// slots (or null): sequence s fills slot slots[s] instead (biogpt_hip_generate_queue refills the columns that have finished).
 struct SharedRows { int n = 0, slot = 0; };
 static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int n_seqs, int n_batch,
-                               const std::function<bool(int, int, size_t)> &pass, int slot_stride = 1, int slot0 = 0, SharedRows shared = SharedRows{}) {
+                               const std::function<bool(int, int, size_t)> &pass, int slot_stride = 1, int slot0 = 0, SharedRows shared = SharedRows{},
+                               const int32_t *slots = nullptr) {
     const int max_cols = std::min(std::max(std::max(1, ctx->opt.prompt_cols), n_batch), hp_cols(ctx));   // the activation scratch holds n_positions columns
     std::vector<bgk::SeqState> cols;
     int pass_tmax = 0;
@@ -2406,7 +2414,7 @@ static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const i
             if (!cols.empty() && (int)cols.size() + m > max_cols && !flush()) return false;
             for (int i = 0; i < m; i++) {
                 bgk::SeqState cst{};
-                cst.n_past = shared.n + at + i; cst.token = seqs[off + (size_t)(at + i)]; cst.seq_id = slot0 + s * slot_stride; cst.t_vis = shared.n + at + m;
+                cst.n_past = shared.n + at + i; cst.token = seqs[off + (size_t)(at + i)]; cst.seq_id = slots ? slots[s] : slot0 + s * slot_stride; cst.t_vis = shared.n + at + m;
                 cst.pad[0] = shared.n; cst.pad[1] = shared.slot;
                 cols.push_back(cst);
             }
@@ -4125,6 +4133,269 @@ int biogpt_hip_generate_lookup(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_lookup_once(ctx, prompts, prompt_lens, n_prompts, corpus, corpus_lens, n_batch, n_predict, max_draft, max_ngram, eos_id, out_ids, out_lens,
                                     out_stats, seconds_out);
+    });
+}
+
+// ---- generation over a queue: finished columns are refilled from a queue of requests (kernels_queue.hip.h) -----------------------------------------
+// C = min(max_columns, eligible requests) columns and K / V slots serve any number of requests: a request takes a column when one is free, generates there
+// at its own positions, under its own limit and with its own generator, and leaves the column to the next request when it finishes (EOS or limit).  The
+// schedule counts steps, never time (QueueSchedule; biogpt_hip_queue_plan is the same struct with given lengths):
+//   1. eligible requests (those that may generate a token) are admitted in index order, the first C into columns 0 .. C - 1;
+//   2. steps are enqueued in groups of min(group, the most tokens any running column may still generate);
+//   3. behind each group the header (QueueHdr: finished flags, generated lengths) travels to pinned memory and the host waits for it;
+//   4. every column found finished has its ids copied from its seq_gen row to the caller's row, in stream order, before the column is reused;
+//   5. finished columns are refilled in ascending column order with the pending requests in ascending request order: their prompts go through packed
+//      prompt passes into exactly those slots, one admit launch sets their state, they take part from the next group's first step;
+//   6. the call ends when a header shows no running column and nothing is pending.
+// The host bounds every step's keys itself: a column in use -- running, or finished and not refilled yet (it still attends at its frozen position) -- stands
+// at position len - 1 + min(steps since admission, its limit) at most.  A refilled slot keeps its old rows beyond the new prompt: no decode-step attention
+// kernel lets a column see a key at or beyond its own n_past + 1.  The steps are always the launch chain (plain_steps).
+extern "C++" {
+struct QueueSchedule {
+    const int32_t *cap;                     // tokens request r may generate at most; 0: it never takes a column
+    int R, C = 0, group, next = 0, pending = 0, running = 0;
+    std::vector<int32_t> req, since;        // per column: its request (-1: none yet), steps since its admission
+    std::vector<uint8_t> live;              // per column: its request still runs
+    biogpt_hip_queue_stats st{};
+    QueueSchedule(const int32_t *cap_, int R_, int max_columns, int group_) : cap(cap_), R(R_), group(group_) {
+        for (int r = 0; r < R; r++) pending += cap[r] > 0 ? 1 : 0;
+        C = std::min(max_columns, pending);
+        req.assign((size_t)C, -1); since.assign((size_t)C, 0); live.assign((size_t)C, 0);
+        st.columns = C;
+    }
+    bool done() const { return running == 0 && pending == 0; }
+    // free columns, ascending <- pending requests, ascending: admit(col, r) for each; the number admitted
+    template <class Admit> int refill(Admit admit) {
+        int n = 0;
+        for (int col = 0; col < C && pending > 0; col++) {
+            if (live[(size_t)col]) continue;
+            while (cap[next] <= 0) next++;
+            req[(size_t)col] = next; since[(size_t)col] = 0; live[(size_t)col] = 1;
+            admit(col, next);
+            next++; pending--; running++; n++;
+        }
+        st.admissions += n > 0 ? 1 : 0;
+        return n;
+    }
+    int group_steps() const {
+        int most = 0;
+        for (int col = 0; col < C; col++) if (live[(size_t)col]) most = std::max(most, cap[req[(size_t)col]] - since[(size_t)col]);
+        return std::min(group, most);
+    }
+    // the position of column col's token at its next step, at most (len: its prompt's length); -1: the column was never used
+    int position(int col, int len) const { return req[(size_t)col] < 0 ? -1 : len - 1 + std::min(since[(size_t)col], cap[req[(size_t)col]]); }
+    void step() { for (int col = 0; col < C; col++) if (req[(size_t)col] >= 0) since[(size_t)col]++; st.steps++; st.column_steps += C; }
+    void end_group() { st.groups++; }
+    void retire(int col, int len) { live[(size_t)col] = 0; running--; st.busy_column_steps += len; }
+};
+}  // extern "C++"
+
+int biogpt_hip_queue_plan(const int32_t *gen_lens, int32_t n_requests, int32_t max_columns, int32_t group, int32_t *admit_step, int32_t *column,
+                          biogpt_hip_queue_stats *stats) {
+    clear_error();
+    if (!gen_lens) BG_FAIL(-1, "null argument: gen_lens");
+    if (!admit_step) BG_FAIL(-1, "null argument: admit_step");
+    if (!column) BG_FAIL(-1, "null argument: column");
+    if (n_requests < 1) BG_FAIL(-1, "n_requests must be >= 1");
+    if (max_columns < 1 || max_columns > bgk::QUEUE_COLS) BG_FAIL(-1, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
+    if (group < 1 || group > 64) BG_FAIL(-1, "group must be in [1, 64]");
+    for (int r = 0; r < n_requests; r++) if (gen_lens[r] < 0) BG_FAIL(-1, "gen_lens[%d] (%d) is negative", r, gen_lens[r]);
+    std::fill(admit_step, admit_step + n_requests, -1);
+    std::fill(column, column + n_requests, -1);
+    QueueSchedule q(gen_lens, n_requests, max_columns, group);
+    while (!q.done()) {
+        q.refill([&](int col, int r) { admit_step[r] = q.st.steps; column[r] = col; });
+        for (int g = q.group_steps(); g > 0; g--) q.step();
+        q.end_group();
+        for (int col = 0; col < q.C; col++)
+            if (q.live[(size_t)col] && q.since[(size_t)col] >= gen_lens[q.req[(size_t)col]]) q.retire(col, gen_lens[q.req[(size_t)col]]);
+    }
+    if (stats) *stats = q.st;
+    return 0;
+}
+
+struct QueueBufs {
+    bgk::SampleCtl *ctl;
+    bgk::SampleSeq *seq;        // [QUEUE_COLS]
+    int32_t *limit;             // [QUEUE_COLS]
+    bgk::QueueHdr *hdr;
+    bgk::QueueAdmit *admit;     // [QUEUE_COLS]
+    size_t bytes;
+};
+static QueueBufs queue_bufs_at(uint8_t *base) {
+    ByteLayout l;
+    QueueBufs b{};
+    b.ctl = l.take<bgk::SampleCtl>(base, 1); b.seq = l.take<bgk::SampleSeq>(base, bgk::QUEUE_COLS); b.limit = l.take<int32_t>(base, bgk::QUEUE_COLS);
+    b.hdr = l.take<bgk::QueueHdr>(base, 1); b.admit = l.take<bgk::QueueAdmit>(base, bgk::QUEUE_COLS);
+    b.bytes = l.bytes();
+    return b;
+}
+// the pinned twin: the header as the host reads it, the admit list as the host writes it
+struct QueueHost { bgk::QueueHdr hdr; bgk::QueueAdmit admit[bgk::QUEUE_COLS]; };
+
+static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,
+                               int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch, int32_t top_k, double top_p, double temp,
+                               const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, int32_t *out_admit_step, int32_t *out_column,
+                               double *seconds_out, biogpt_hip_queue_stats *stats) {
+    clear_error();
+    // (what can be judged without the model comes first: these fail the same way with no context and no device)
+    if (!prompts) BG_FAIL(-1, "null argument: prompts");
+    if (!prompt_lens) BG_FAIL(-1, "null argument: prompt_lens");
+    if (!seeds) BG_FAIL(-1, "null argument: seeds");
+    if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
+    if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
+    if (n_requests < 1) BG_FAIL(-1, "n_requests must be >= 1");
+    if (max_columns < 1 || max_columns > bgk::QUEUE_COLS) BG_FAIL(-1, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
+    if (group < 1 || group > 64) BG_FAIL(-1, "group must be in [1, 64]");
+    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
+    if (n_predict < 0) BG_FAIL(-1, "n_predict must be >= 0");
+    for (int r = 0; n_predicts && r < n_requests; r++)
+        if (n_predicts[r] < 0 || n_predicts[r] > n_predict) BG_FAIL(-1, "n_predicts[%d] (%d) must be in [0, n_predict = %d]", r, n_predicts[r], n_predict);
+    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
+    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
+    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
+    if (eos_id < -1) BG_FAIL(-1, "eos_id %d out of range: must be a token id, or -1 for none", eos_id);
+    std::vector<size_t> off((size_t)n_requests + 1, 0);
+    for (int r = 0; r < n_requests; r++) {
+        if (prompt_lens[r] < 1) BG_FAIL(-1, "empty prompt (request %d)", r);
+        off[(size_t)r + 1] = off[(size_t)r] + (size_t)prompt_lens[r];
+    }
+    for (int r = 0; r < n_requests; r++)
+        for (int i = 0; i < prompt_lens[r]; i++)
+            if (prompts[off[(size_t)r] + (size_t)i] < 0) BG_FAIL(-1, "token id %d (request %d, position %d) out of range", prompts[off[(size_t)r] + (size_t)i], r, i);
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
+    if (top_k > V) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
+    if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
+    for (int r = 0; r < n_requests; r++) {
+        if (prompt_lens[r] > P) BG_FAIL(-1, "prompt_lens[%d] (%d) exceeds n_positions (%d)", r, prompt_lens[r], P);
+        for (int i = 0; i < prompt_lens[r]; i++)
+            if (prompts[off[(size_t)r] + (size_t)i] >= V) BG_FAIL(-1, "token id %d (request %d, position %d) out of range [0, %d)", prompts[off[(size_t)r] + (size_t)i], r, i, V);
+    }
+    if (!check_fast_chain(ctx, "generation over a queue")) return -1;
+
+    // every request's own clamp (main.cpp:82 per request); the buckets the steps can need
+    std::vector<int32_t> cap((size_t)n_requests);
+    int min_len = P, max_keys = 0;
+    long total = 0;
+    for (int r = 0; r < n_requests; r++) {
+        cap[(size_t)r] = std::min(n_predicts ? n_predicts[r] : n_predict, P - prompt_lens[r]);
+        if (cap[(size_t)r] <= 0) continue;
+        min_len = std::min(min_len, prompt_lens[r]); max_keys = std::max(max_keys, prompt_lens[r] + cap[(size_t)r]);
+        total += prompt_lens[r];
+    }
+    std::fill(out_ids, out_ids + (size_t)n_requests * (size_t)n_predict, -1);
+    std::fill(out_lens, out_lens + n_requests, 0);
+    if (out_admit_step) std::fill(out_admit_step, out_admit_step + n_requests, -1);
+    if (out_column) std::fill(out_column, out_column + n_requests, -1);
+    if (seconds_out) *seconds_out = 0.0;
+    QueueSchedule q(cap.data(), n_requests, max_columns, group);
+    const int C = q.C;
+    if (stats) *stats = q.st;
+    if (C == 0) return 0;      // nobody has room for a token: nothing was touched
+    if (C > hp_cols(ctx)) BG_FAIL(-1, "max_columns (%d) exceeds the %d activation columns of this model", C, hp_cols(ctx));
+
+    XpCallScope xp_scope(ctx);
+    XcBatchScope xc_scope{ctx};
+    if (!begin_column_call(ctx, C, C, std::min<long>(total, P))) return -2;
+    ctx->xc_batch = 0;
+    if (!ctx->queue_buf) HIP_TRY(-2, hipMalloc(&ctx->queue_buf, queue_bufs_at(nullptr).bytes));
+    if (!ctx->queue_host) HIP_TRY(-2, hipHostMalloc(&ctx->queue_host, sizeof(QueueHost)));
+    const QueueBufs qb = queue_bufs_at(ctx->queue_buf);
+    QueueHost *const qh = reinterpret_cast<QueueHost *>(ctx->queue_host);
+    column_graphs_for(ctx->graphs_queue, C, 0);
+    {      // the call's parameters; nobody runs yet
+        const bgk::SampleCtl hc = sample_ctl_of(top_k, eos_id, 0, top_p, temp);
+        HIP_TRY(-2, hipMemcpy(qb.ctl, &hc, sizeof(hc), hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemset(qb.hdr, 0, sizeof(bgk::QueueHdr)));
+    }
+    const ColumnStep step = [&](int t_max) -> bool {
+        if (!enqueue_forward(ctx, ForwardPass::decode_step(C, t_max))) return false;
+        hipLaunchKernelGGL(bgk::queue_rows_kernel, dim3(C), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, qb.ctl, qb.seq, ctx->seq, ctx->seq_gen, P,
+                           qb.limit, qb.hdr);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    // (ColumnKeys of a call whose first replayed step sees min_len keys and whose last one max_keys: every bucket a step here can be bounded by)
+    bool use_graph;
+    if (!capture_column_steps(ctx, ctx->graphs_queue, 0, ColumnKeys{min_len - 1, 1, P}, max_keys - min_len + 2, step, &use_graph)) return -2;
+
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> flat, lens, slots;
+    while (!q.done()) {
+        // ---- refill: the prompts of the admitted requests into exactly their columns' slots, then one admit launch ----
+        flat.clear(); lens.clear(); slots.clear();
+        const int n_admit = q.refill([&](int col, int r) {
+            const int32_t *p = prompts + off[(size_t)r];
+            const int len = prompt_lens[r];
+            bgk::QueueAdmit &a = qh->admit[slots.size()];
+            a = bgk::QueueAdmit{};
+            a.col = col; a.last_token = p[len - 1]; a.len = len; a.limit = cap[(size_t)r]; a.seed = seeds[r];
+            flat.insert(flat.end(), p, p + len); lens.push_back(len); slots.push_back(col);
+            if (out_admit_step) out_admit_step[r] = q.st.steps;
+            if (out_column) out_column[r] = col;
+            q.st.prompt_columns += len;
+        });
+        if (n_admit > 0) {
+            if (!pack_column_passes(ctx, flat.data(), lens.data(), n_admit, n_batch,
+                                    [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); }, 1, 0, SharedRows{},
+                                    slots.data()))
+                return -2;
+            HIP_TRY(-2, hipMemcpyAsync(qb.admit, qh->admit, sizeof(bgk::QueueAdmit) * (size_t)n_admit, hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(bgk::queue_admit_kernel, dim3(n_admit), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, qb.seq, ctx->seq, qb.limit, qb.hdr);
+            HIP_TRY(-2, hipGetLastError());
+        }
+        // ---- one group of steps ----
+        for (int g = q.group_steps(); g > 0; g--) {
+            int t_max = 1;
+            for (int col = 0; col < C; col++)
+                if (q.req[(size_t)col] >= 0) t_max = std::max(t_max, q.position(col, prompt_lens[q.req[(size_t)col]]) + 1);
+            t_max = std::min(t_max, P);
+            if (use_graph) {
+                hipGraphExec_t ge = ctx->graphs_queue.exec[graph_bucket(t_max)];
+                if (!ge) BG_FAIL(-2, "internal: no captured queue step for %d keys", t_max);
+                HIP_TRY(-2, hipGraphLaunch(ge, ctx->stream));
+            } else if (!step(t_max)) {
+                return -2;
+            }
+            q.step();
+        }
+        q.end_group();
+        // ---- the look at the columns: the header behind the group (lag 0) ----
+        HIP_TRY(-2, hipMemcpyAsync(&qh->hdr, qb.hdr, sizeof(bgk::QueueHdr), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(-2, hipEventRecord(ctx->live_ev[0], ctx->stream));
+        HIP_TRY(-2, hipEventSynchronize(ctx->live_ev[0]));
+        for (int col = 0; col < C; col++) {
+            if (!q.live[(size_t)col]) continue;
+            const int r = q.req[(size_t)col];
+            if (!qh->hdr.fin[col]) {
+                if (q.since[(size_t)col] >= cap[(size_t)r])
+                    BG_FAIL(-2, "internal: request %d (column %d) is unfinished after %d steps, its limit is %d", r, col, q.since[(size_t)col], cap[(size_t)r]);
+                continue;
+            }
+            const int len = std::max(0, std::min(qh->hdr.len[col], cap[(size_t)r]));
+            if (len > 0)
+                HIP_TRY(-2, hipMemcpyAsync(out_ids + (size_t)r * (size_t)n_predict, ctx->seq_gen + (size_t)col * P, (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
+            out_lens[r] = len;
+            q.retire(col, len);
+        }
+    }
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (!xpipe_check(ctx)) return -2;
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    if (stats) *stats = q.st;
+    return 0;
+}
+
+int biogpt_hip_generate_queue(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,
+                              int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch, int32_t top_k, double top_p, double temp,
+                              const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, int32_t *out_admit_step, int32_t *out_column,
+                              double *seconds_out, biogpt_hip_queue_stats *stats) {
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_queue_once(ctx, prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch, top_k, top_p, temp, seeds, eos_id,
+                                   out_ids, out_lens, out_admit_step, out_column, seconds_out, stats);
     });
 }
 

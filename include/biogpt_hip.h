@@ -484,6 +484,43 @@ int biogpt_hip_generate_lookup(biogpt_hip_ctx *ctx, const int32_t *prompts /* co
                                int32_t *out_ids /* [n_prompts][returned n_predict], -1 filled */, int32_t *out_lens /* [n_prompts] */,
                                int32_t *out_stats /* [n_prompts][3], may be NULL */, double *seconds_out);
 
+/* ---- generation over a queue (continuous batching): finished columns are refilled from a queue of requests ----
+ * n_requests requests (prompts concatenated, prompt_lens their lengths) share C = min(max_columns, eligible requests) columns and K / V cache slots: a
+ * request takes a column when one is free and leaves it when it finishes, by EOS or at its own limit.  Request r's ids and length are those of
+ * biogpt_hip_generate_sample(its prompt alone, n_samples 1, n_r, the same top_k / top_p / temp / eos_id / n_batch, seeds[r]), bit for bit, with
+ * n_r = min(n_predicts[r], n_positions - prompt_lens[r]): the clamp is per request.  What else is in the queue, max_columns and group change nothing but the
+ * time.  top_k = 1 never draws: greedy decoding with an EOS.  A request with n_r == 0 gets length 0 and never takes a column.  n_predicts == NULL: n_predict
+ * for every request.  out_ids is [n_requests][n_predict] (n_predict is the row stride as GIVEN, not clamped) with -1 behind a request's length; out_lens
+ * the generated tokens (an EOS that ended a request included).  out_admit_step[r] (may be NULL): the steps run before r's first step; out_column[r] (may be
+ * NULL): its column; both -1 for a request that never ran.  The schedule is deterministic in steps (biogpt_hip_queue_plan computes it from the lengths
+ * alone): requests are admitted in index order, steps run in groups of `group`, behind each group the host looks at the columns and refills the
+ * finished ones, lowest column first.  stats (may be NULL): columns = C; steps; groups; admissions = refill rounds, the first included; prompt_columns =
+ * prompt tokens evaluated; busy_column_steps = the sum of out_lens; column_steps = C * steps.  n_requests is limited by host memory alone: prompts stay on
+ * the host until admitted.  max_columns in [1, 512], group in [1, 64], n_predicts[r] in [0, n_predict], top_k in [1, 64], temp finite and > 0, top_p finite,
+ * eos_id in [-1, n_vocab), no empty prompt, prompt_lens[r] <= n_positions.  The context's own K / V cache, position and logits row are left alone.  Needs
+ * the BioGPT-base fast chain (block-quantized weights); anything else fails with -1.  No rules, trie, prefix, log-probabilities or several samples per
+ * request; the steps always run as the launch chain.  Returns 0, or < 0 on error (argument errors, -1, the message names the field, come before any HIP
+ * call). */
+typedef struct biogpt_hip_queue_stats {
+    int32_t columns, steps, groups, admissions, prompt_columns;
+    int64_t busy_column_steps, column_steps;
+} biogpt_hip_queue_stats;
+
+int biogpt_hip_generate_queue(biogpt_hip_ctx *ctx, const int32_t *prompts /* concatenated */, const int32_t *prompt_lens, int32_t n_requests,
+                              const int32_t *n_predicts /* [n_requests], or NULL: n_predict for all */,
+                              int32_t n_predict /* row stride of out_ids; every n_predicts[r] <= n_predict */, int32_t max_columns /* 1 .. 512 */,
+                              int32_t group /* steps between two looks at the columns, 1 .. 64 */, int32_t n_batch, int32_t top_k, double top_p, double temp,
+                              const uint32_t *seeds /* [n_requests] */, int32_t eos_id /* -1: none */,
+                              int32_t *out_ids /* [n_requests][n_predict], -1 behind a request's length */, int32_t *out_lens,
+                              int32_t *out_admit_step /* may be NULL */, int32_t *out_column /* may be NULL */, double *seconds_out,
+                              biogpt_hip_queue_stats *stats /* may be NULL */);
+
+/* The scheduler of biogpt_hip_generate_queue alone, on the host: no context, no HIP call.  gen_lens[r] = the tokens request r generates (0: it never takes a
+ * column) -- the schedule of a call whose requests all run to their limits, and of a call with an EOS wherever no group was cut short by limits that
+ * an EOS undercut.  admit_step / column [n_requests] and stats as above; prompt_columns stays 0 (the plan knows no prompts).  Returns 0 or -1. */
+int biogpt_hip_queue_plan(const int32_t *gen_lens, int32_t n_requests, int32_t max_columns, int32_t group, int32_t *admit_step, int32_t *column,
+                          biogpt_hip_queue_stats *stats /* may be NULL */);
+
 /* The draft kernel of prompt-lookup decoding over texts held in host memory, no model: sequence s has text_lens[s] tokens of the concatenated `texts`
  * (the last n_gen[s] of them generated, the last one its current token at position n_past[s]); finished (may be NULL): sequences that draft nothing.
  * draft_out [n_seqs][16] (-1 behind the draft), d_out [n_seqs], cols_out [n_seqs][1 + max_draft][4]: token, n_past, seq_id, t_vis of every packed
