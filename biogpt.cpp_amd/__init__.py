@@ -300,16 +300,28 @@ def lookup_accept(rows, drafts, n_gen, n_past, n_predict, max_draft, eos_id=-1, 
     return [[int(v) for v in emit[s] if v >= 0] for s in range(n)], state[:n].copy(), stats[:n].copy(), (int(live[0]), int(live[1]))
 
 
-def queue_plan(gen_lens, max_columns, group):
+def queue_plan(gen_lens, max_columns, group, limits=None):
     """The schedule of BiogptModel.generate_queue from the generated lengths alone (biogpt_hip_queue_plan: the host struct the call itself drives, no device):
-    ({"stats": {...}, "admit_step": [...], "column": [...]}); a request of length 0 never takes a column (-1 in both lists); prompt_columns stays 0."""
+    ({"stats": {...}, "admit_step": [...], "column": [...]}); a request of length 0 never takes a column (-1 in both lists); prompt_columns stays 0.
+    limits (biogpt_hip_queue_plan_limits): what every request may generate at most, as clamped -- the schedule of a run whose requests end before their
+    limits (an EOS, a beam search that stops), where a group is sized from the limits; for generate_beam_queue gen_lens are info["steps"] and max_columns
+    the number of slots."""
     gl = np.ascontiguousarray(gen_lens, dtype=np.int32).reshape(-1)
     n = int(gl.size)
     if n == 0:
         gl = np.zeros(1, np.int32)
     adm, col = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
     st = QueueStats()
-    if lib().biogpt_hip_queue_plan(gl.ctypes.data, n, int(max_columns), int(group), adm.ctypes.data, col.ctypes.data, C.byref(st)) != 0:
+    if limits is not None:
+        lm = np.ascontiguousarray(limits, dtype=np.int32).reshape(-1)
+        if lm.size != n:
+            raise BiogptError("limits must have one entry per request (%d != %d)" % (lm.size, n))
+        if n == 0:
+            lm = np.zeros(1, np.int32)
+        rc = lib().biogpt_hip_queue_plan_limits(gl.ctypes.data, lm.ctypes.data, n, int(max_columns), int(group), adm.ctypes.data, col.ctypes.data, C.byref(st))
+    else:
+        rc = lib().biogpt_hip_queue_plan(gl.ctypes.data, n, int(max_columns), int(group), adm.ctypes.data, col.ctypes.data, C.byref(st))
+    if rc != 0:
         raise BiogptError(_err())
     return {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:n]], "column": [int(v) for v in col[:n]]}
 
@@ -470,6 +482,10 @@ SYMBOLS = [
     ("biogpt_hip_generate_queue", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32,
                                            _P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(QueueStats)]),
     ("biogpt_hip_queue_plan", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(QueueStats)]),
+    ("biogpt_hip_queue_plan_limits", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(QueueStats)]),
+    ("biogpt_hip_read_column_state", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    ("biogpt_hip_generate_beam_queue", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P,
+                                                _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(QueueStats)]),
     ("biogpt_hip_lookup_draft_device", C.c_int, [C.c_int, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("biogpt_hip_lookup_accept_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_rules_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(GenRules), _P]),
@@ -1022,6 +1038,56 @@ class BiogptModel:
         rows = out.reshape(-1)      # rows are [R][n_predict as given]
         ids = [rows[r * w:r * w + int(ol[r])].copy() for r in range(R)]
         return ids, {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:R]], "column": [int(v) for v in col[:R]]}, secs.value
+
+    def read_column_state(self, column, pos, which=0, n_ids=0):
+        """Tests of slot reuse (biogpt_hip_read_column_state): (the K (which 0) or V (1) row of position pos in every layer of column `column`'s own cache slot,
+        float32 [n_layer, d_model]; the first n_ids ids of the column's beam pool row) as the last column call left them."""
+        hp = self.hparams
+        kv = np.zeros((hp.n_layer, hp.d_model), dtype=np.float32)
+        ids = np.zeros(max(int(n_ids), 1), dtype=np.int32)
+        if lib().biogpt_hip_read_column_state(self._h, int(column), int(which), int(pos), kv.ctypes.data, int(n_ids), ids.ctypes.data if n_ids else None) != 0:
+            raise BiogptError(_err())
+        return kv, ids[:int(n_ids)].copy()
+
+    def generate_beam_queue(self, prompts, n_predict, n_beams=5, max_columns=510, group=4, eos_id=2, length_penalty=1.0, early_stopping=True, n_batch=8,
+                            n_predicts=None, trie=None):
+        """Beam search over a queue of requests (continuous batching; INTEGRATION.md, "Beam search over a queue"): prompts is a list of id lists of any
+        length, max_columns // n_beams searches run at a time, and a search that stops -- by transformers' stopping rules, or after its own n_predicts[r]
+        (None: n_predict) steps as clamped to ITS prompt -- hands its n_beams columns to the next request.  Request r's list is generate_beam(prompts[r],
+        n_r, n_beams, eos_id, length_penalty, early_stopping, n_batch, trie=trie) alone, whatever else is in the queue.  group: steps between two looks at
+        the slots; max_columns=510 is the fastest setting measured and 510 K / V caches, 96 GiB at BioGPT-base, where they are all used: 160 was
+        1.26 x slower on a workload without an EOS.  The caches stay allocated to this model after the call, until close().  No generation rules, prefix= or
+        logprobs=.  Returns ([[(ids int32[len], score), ...] best first, one list per request], {"stats":
+        {...} counted in slots, "admit_step": [...], "slot": [...], "steps": [...]}, seconds) -- queue_plan(steps, slots, group, limits=[n_r, ...]) computes the last
+        three from the first; a request without room for a token gets an empty list, -1 in
+        admit_step and slot, and 0 steps."""
+        if len(prompts) and np.isscalar(prompts[0]):
+            prompts = [prompts]
+        R, B = len(prompts), max(int(n_beams), 1)
+        lens = np.asarray([len(p) for p in prompts] or [0], dtype=np.int32)
+        flat = _flat_ids(prompts)
+        np_arr = None
+        if n_predicts is not None:
+            np_arr = np.ascontiguousarray(n_predicts, dtype=np.int32).reshape(-1)
+            if np_arr.size != R:
+                raise BiogptError("n_predicts must have one entry per request (%d != %d)" % (np_arr.size, R))
+        w = max(int(n_predict), 0)
+        out = np.zeros((max(R, 1) * B, max(w, 1)), dtype=np.int32)
+        ol = np.zeros(max(R, 1) * B, dtype=np.int32)
+        scores = np.zeros(max(R, 1) * B, dtype=np.float32)
+        counts, steps, adm, slot = (np.zeros(max(R, 1), dtype=np.int32) for _ in range(4))
+        st = QueueStats()
+        secs = C.c_double(0.0)
+        rc = lib().biogpt_hip_generate_beam_queue(self._h, flat.ctypes.data, lens.ctypes.data, R, None if np_arr is None or R == 0 else np_arr.ctypes.data,
+                                                  int(n_predict), int(n_beams), int(max_columns), int(group), int(n_batch), int(eos_id), float(length_penalty),
+                                                  1 if early_stopping else 0, None if trie is None else _trie_handle(trie), out.ctypes.data, ol.ctypes.data,
+                                                  scores.ctypes.data, counts.ctypes.data, steps.ctypes.data, adm.ctypes.data, slot.ctypes.data, C.byref(secs),
+                                                  C.byref(st))
+        if rc < 0:
+            raise BiogptError(_err())
+        rows = out.reshape(-1)      # rows are [R][n_beams][n_predict as given]
+        hyps = [[(rows[(r * B + i) * w:(r * B + i) * w + int(ol[r * B + i])].copy(), float(scores[r * B + i])) for i in range(int(counts[r]))] for r in range(R)]
+        return hyps, {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:R]], "slot": [int(v) for v in slot[:R]], "steps": [int(v) for v in steps[:R]]}, secs.value
 
     @_logprobs_keyword
     def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,

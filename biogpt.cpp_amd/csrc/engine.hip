@@ -50,6 +50,7 @@
 #include "kernels_contrast.hip.h"
 #include "kernels_lookup.hip.h"
 #include "kernels_queue.hip.h"
+#include "kernels_beam_queue.hip.h"
 #include "model_file.h"
 #include "quant_host.h"
 #include "trie_host.h"
@@ -290,7 +291,7 @@ struct biogpt_hip_ctx {
     int launch_parity = 0;
     // column generation (greedy batch, sampling, beam search; the driver stands before generate_greedy_batch_once): the captured steps of each mode,
     // and the pinned word pair + event pair through which the host reads a mode's count of unfinished sequences / searches between groups of steps
-    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam, graphs_contrast, graphs_lookup, graphs_queue;
+    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam, graphs_contrast, graphs_lookup, graphs_queue, graphs_bqueue;
     int32_t *live_host = nullptr;
     hipEvent_t live_ev[2] = {};
     // sampled generation (biogpt_hip_generate_sample, kernels_sample.hip.h): the call's parameters + one generator state per sequence (SampleCtl, then
@@ -320,6 +321,11 @@ struct biogpt_hip_ctx {
     // first such call -- captured steps keep their pointers -- and its pinned twin: the header the host reads behind a group, the admit list it uploads
     uint8_t *queue_buf = nullptr;
     uint8_t *queue_host = nullptr;
+    // beam search over a queue (biogpt_hip_generate_beam_queue, kernels_beam_queue.hip.h): the searches' state is bbatch_buf; this block holds what the queue adds
+    // (bqueue_bufs_at: the report header and the admit list), allocated at the first such call, and its pinned twin (BeamQueueHost, then the pool rows of
+    // every slot as they come back)
+    uint8_t *bqueue_buf = nullptr;
+    uint8_t *bqueue_host = nullptr;
 
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -397,7 +403,7 @@ static void drop_graphs(ColumnGraphs &gs) {
 }
 // Captured column steps hold the pointers of seq / bk / bv / logits_all and launch shapes chosen from the options: whatever replaces one of those drops them all
 static void drop_column_graphs(biogpt_hip_ctx *c) {
-    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam, &c->graphs_contrast, &c->graphs_lookup, &c->graphs_queue}) drop_graphs(*gs);
+    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam, &c->graphs_contrast, &c->graphs_lookup, &c->graphs_queue, &c->graphs_bqueue}) drop_graphs(*gs);
 }
 
 namespace {
@@ -1680,13 +1686,14 @@ void destroy(biogpt_hip_ctx *c) {
     for (auto &e : c->live_ev) if (e) (void)hipEventDestroy(e);
     if (c->live_host) (void)hipHostFree(c->live_host);
     if (c->queue_host) (void)hipHostFree(c->queue_host);
+    if (c->bqueue_host) (void)hipHostFree(c->bqueue_host);
     xpipe_release(c);
     if (c->topk_host) (void)hipHostFree(c->topk_host);
     if (c->mbox_host) (void)hipHostFree(c->mbox_host);
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf, (void *)c->genlp_buf, (void *)c->queue_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf, (void *)c->genlp_buf, (void *)c->queue_buf, (void *)c->bqueue_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -3705,11 +3712,12 @@ static bool enqueue_beam_group_select(const BeamBufs &b, int G, int B, bool give
 }
 
 // the pools of G finished searches (ctl: host copies; pool_ids: [G * B][ids_stride]) -> the output rows of biogpt_hip_generate_beam_batch
+// unit, index0: what a failure names -- group p is `unit` index0 + p
 static bool beam_read_pools(const bgk::BeamCtl *ctl, const int32_t *pool_ids, size_t ids_stride, int G, int B, int n_predict, int32_t *out_ids, int32_t *out_lens,
-                            float *out_scores, int32_t *out_counts) {
+                            float *out_scores, int32_t *out_counts, const char *unit = "prompt", int index0 = 0) {
     for (int p = 0; p < G; p++) {
         const bgk::BeamCtl &st = ctl[p];
-        if (!st.done || st.pool_n < 1 || st.pool_n > B) BG_FAIL(false, "internal: beam search of prompt %d ended with %d hypotheses (done word %d)", p, st.pool_n, st.done);
+        if (!st.done || st.pool_n < 1 || st.pool_n > B) BG_FAIL(false, "internal: beam search of %s %d ended with %d hypotheses (done word %d)", unit, index0 + p, st.pool_n, st.done);
         out_counts[p] = st.pool_n;
         for (int r = 0; r < B; r++) {
             const size_t row = (size_t)p * B + r;
@@ -4190,19 +4198,26 @@ struct QueueSchedule {
 };
 }  // extern "C++"
 
-int biogpt_hip_queue_plan(const int32_t *gen_lens, int32_t n_requests, int32_t max_columns, int32_t group, int32_t *admit_step, int32_t *column,
-                          biogpt_hip_queue_stats *stats) {
+// limits == gen_lens: biogpt_hip_queue_plan.  The host of a run sizes a group from the limits (it does not know where a request will end) and a look finds
+// finished whoever has generated all its gen_lens[r] tokens.
+static int queue_plan_of(const int32_t *gen_lens, const int32_t *limits, int32_t n_requests, int32_t max_columns, int32_t group, int32_t *admit_step, int32_t *column,
+                         biogpt_hip_queue_stats *stats) {
     clear_error();
     if (!gen_lens) BG_FAIL(-1, "null argument: gen_lens");
+    if (!limits) BG_FAIL(-1, "null argument: limits");
     if (!admit_step) BG_FAIL(-1, "null argument: admit_step");
     if (!column) BG_FAIL(-1, "null argument: column");
     if (n_requests < 1) BG_FAIL(-1, "n_requests must be >= 1");
     if (max_columns < 1 || max_columns > bgk::QUEUE_COLS) BG_FAIL(-1, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
     if (group < 1 || group > 64) BG_FAIL(-1, "group must be in [1, 64]");
     for (int r = 0; r < n_requests; r++) if (gen_lens[r] < 0) BG_FAIL(-1, "gen_lens[%d] (%d) is negative", r, gen_lens[r]);
+    for (int r = 0; r < n_requests; r++) {
+        if (limits[r] < gen_lens[r]) BG_FAIL(-1, "limits[%d] (%d) is below gen_lens[%d] (%d)", r, limits[r], r, gen_lens[r]);
+        if (limits[r] > 0 && gen_lens[r] < 1) BG_FAIL(-1, "gen_lens[%d] is 0 under a limit of %d: a request that takes a column generates a token", r, limits[r]);
+    }
     std::fill(admit_step, admit_step + n_requests, -1);
     std::fill(column, column + n_requests, -1);
-    QueueSchedule q(gen_lens, n_requests, max_columns, group);
+    QueueSchedule q(limits, n_requests, max_columns, group);
     while (!q.done()) {
         q.refill([&](int col, int r) { admit_step[r] = q.st.steps; column[r] = col; });
         for (int g = q.group_steps(); g > 0; g--) q.step();
@@ -4212,6 +4227,16 @@ int biogpt_hip_queue_plan(const int32_t *gen_lens, int32_t n_requests, int32_t m
     }
     if (stats) *stats = q.st;
     return 0;
+}
+
+int biogpt_hip_queue_plan(const int32_t *gen_lens, int32_t n_requests, int32_t max_columns, int32_t group, int32_t *admit_step, int32_t *column,
+                          biogpt_hip_queue_stats *stats) {
+    return queue_plan_of(gen_lens, gen_lens, n_requests, max_columns, group, admit_step, column, stats);
+}
+
+int biogpt_hip_queue_plan_limits(const int32_t *gen_lens, const int32_t *limits, int32_t n_requests, int32_t max_columns, int32_t group, int32_t *admit_step,
+                                 int32_t *column, biogpt_hip_queue_stats *stats) {
+    return queue_plan_of(gen_lens, limits, n_requests, max_columns, group, admit_step, column, stats);
 }
 
 struct QueueBufs {
@@ -4399,6 +4424,253 @@ int biogpt_hip_generate_queue(biogpt_hip_ctx *ctx, const int32_t *prompts, const
     });
 }
 
+// ---- beam search over a queue: finished searches hand their B columns on (kernels_beam_queue.hip.h) ------------------------------------------------
+// S = min(max_columns / n_beams, eligible requests) group slots of B columns and K / V slots each serve any number of requests: a request's search runs in one
+// slot -- group `slot` of biogpt_hip_generate_beam_batch's state, columns [slot * B, (slot + 1) * B) -- under its own clamp, and when it stops, by
+// transformers' stopping rules or after its own n_predict steps, its pool is copied out and the slot goes to the next request.  The schedule is
+// generate_queue's, the same QueueSchedule with "columns" = slots: admission in index order, groups of min(group, the most steps any running search may
+// still take), the report header (BeamQueueHdr) read behind each group, refill in ascending slot / request order.  A refill is a packed prompt pass into the
+// first slot of each admitted group, kv_share_slots_kernel to the group's other slots, and one admit launch.  The host bounds a step's keys as
+// generate_queue does.  A refilled slot keeps its old K / V rows beyond the new prompt and its old pool rows: no decode-step attention kernel lets a column
+// see a key at or beyond its own n_past + 1, and pool_n = 0 hides the pool.
+// The searches' state block is the context's bbatch_buf, the one biogpt_hip_generate_beam_batch uses (allocated once at its largest: the captured steps of
+// both keep their pointers, and a closed call uploads its whole start state, so neither sees the other's leftovers); what the queue adds -- report header and
+// admit list -- is a block of its own.  The steps are captured per bucket into graphs_bqueue, keyed by (S, B), trie or not, and always run the launch chain.
+struct BeamQueueBufs {
+    bgk::BeamQueueHdr *hdr;
+    bgk::BeamQueueAdmit *admit;     // [BEAM_QUEUE_SLOTS]
+    size_t bytes;
+};
+static BeamQueueBufs bqueue_bufs_at(uint8_t *base) {
+    ByteLayout l;
+    BeamQueueBufs b{};
+    b.hdr = l.take<bgk::BeamQueueHdr>(base, 1); b.admit = l.take<bgk::BeamQueueAdmit>(base, bgk::BEAM_QUEUE_SLOTS);
+    b.bytes = l.bytes();
+    return b;
+}
+// the pinned twin: the header as the host reads it, the admit list as the host writes it, every slot's BeamCtl as it comes back; the slots' pool rows
+// ([BBATCH_COLS][n_positions] words) lie behind it
+struct BeamQueueHost {
+    bgk::BeamQueueHdr hdr;
+    bgk::BeamQueueAdmit admit[bgk::BEAM_QUEUE_SLOTS];
+    bgk::BeamCtl ctl[bgk::BEAM_QUEUE_SLOTS];
+};
+
+static int generate_beam_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,
+                                    int32_t n_predict, int32_t n_beams, int32_t max_columns, int32_t group, int32_t n_batch, int32_t eos_id, float length_penalty,
+                                    int32_t early_stopping, biogpt_hip_trie *trie, int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts,
+                                    int32_t *out_steps, int32_t *out_admit_step, int32_t *out_slot, double *seconds_out, biogpt_hip_queue_stats *stats) {
+    clear_error();
+    // (what can be judged without the model comes first: these fail the same way with no context and no device)
+    if (!prompts) BG_FAIL(-1, "null argument: prompts");
+    if (!prompt_lens) BG_FAIL(-1, "null argument: prompt_lens");
+    if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
+    if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
+    if (!out_scores) BG_FAIL(-1, "null argument: out_scores");
+    if (!out_counts) BG_FAIL(-1, "null argument: out_counts");
+    if (n_requests < 1) BG_FAIL(-1, "n_requests must be >= 1");
+    if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
+    if (max_columns < n_beams || max_columns > BBATCH_COLS) BG_FAIL(-1, "max_columns must be in [n_beams = %d, %d]", n_beams, BBATCH_COLS);
+    if (group < 1 || group > 64) BG_FAIL(-1, "group must be in [1, 64]");
+    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
+    if (n_predict < 0) BG_FAIL(-1, "n_predict must be >= 0");
+    for (int r = 0; n_predicts && r < n_requests; r++)
+        if (n_predicts[r] < 0 || n_predicts[r] > n_predict) BG_FAIL(-1, "n_predicts[%d] (%d) must be in [0, n_predict = %d]", r, n_predicts[r], n_predict);
+    if (eos_id < -1) BG_FAIL(-1, "eos_id %d out of range: must be a token id, or -1 for none", eos_id);
+    if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
+    if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
+    if (trie && !check_trie(trie, eos_id)) return -1;
+    std::vector<size_t> off((size_t)n_requests + 1, 0);
+    for (int r = 0; r < n_requests; r++) {
+        if (prompt_lens[r] < 1) BG_FAIL(-1, "empty prompt (request %d)", r);
+        off[(size_t)r + 1] = off[(size_t)r] + (size_t)prompt_lens[r];
+    }
+    for (int r = 0; r < n_requests; r++)
+        for (int i = 0; i < prompt_lens[r]; i++)
+            if (prompts[off[(size_t)r] + (size_t)i] < 0) BG_FAIL(-1, "token id %d (request %d, position %d) out of range", prompts[off[(size_t)r] + (size_t)i], r, i);
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab, B = n_beams;
+    if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
+    for (int r = 0; r < n_requests; r++) {
+        if (prompt_lens[r] > P) BG_FAIL(-1, "prompt_lens[%d] (%d) exceeds n_positions (%d)", r, prompt_lens[r], P);
+        for (int i = 0; i < prompt_lens[r]; i++)
+            if (prompts[off[(size_t)r] + (size_t)i] >= V) BG_FAIL(-1, "token id %d (request %d, position %d) out of range [0, %d)", prompts[off[(size_t)r] + (size_t)i], r, i, V);
+    }
+    if (!check_fast_chain(ctx, "beam search over a queue")) return -1;
+    if (V < 2 * B) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", V);
+    if (trie && !check_trie_vocab(trie, V)) return -1;
+
+    // every request's own clamp (main.cpp:82 per request: what biogpt_hip_generate_beam applies to the prompt alone); the buckets the steps can need
+    std::vector<int32_t> cap((size_t)n_requests);
+    int min_len = P, max_keys = 0;
+    long total = 0;
+    for (int r = 0; r < n_requests; r++) {
+        cap[(size_t)r] = std::min(n_predicts ? n_predicts[r] : n_predict, P - prompt_lens[r]);
+        if (cap[(size_t)r] <= 0) continue;
+        min_len = std::min(min_len, prompt_lens[r]); max_keys = std::max(max_keys, prompt_lens[r] + cap[(size_t)r]);
+        total += prompt_lens[r];
+    }
+    const size_t row = (size_t)n_predict, rows = (size_t)n_requests * (size_t)B;
+    std::fill(out_ids, out_ids + rows * row, -1);
+    std::fill(out_lens, out_lens + rows, 0);
+    std::fill(out_scores, out_scores + rows, 0.0f);
+    std::fill(out_counts, out_counts + n_requests, 0);
+    if (out_steps) std::fill(out_steps, out_steps + n_requests, 0);
+    if (out_admit_step) std::fill(out_admit_step, out_admit_step + n_requests, -1);
+    if (out_slot) std::fill(out_slot, out_slot + n_requests, -1);
+    if (seconds_out) *seconds_out = 0.0;
+    QueueSchedule q(cap.data(), n_requests, max_columns / B, group);
+    const int S = q.C, C = S * B;
+    if (stats) *stats = q.st;
+    if (S == 0) return 0;      // nobody has room for a token: nothing was touched
+    if (C > hp_cols(ctx)) BG_FAIL(-1, "max_columns (%d) exceeds the %d activation columns of this model", C, hp_cols(ctx));
+
+    XpCallScope xp_scope(ctx);
+    XcBatchScope xc_scope{ctx};
+    if (!begin_column_call(ctx, C, C, std::min<long>(total, P))) return -2;
+    ctx->xc_batch = 0;
+    if (!ctx->bbatch_buf) {
+        size_t bytes;
+        beam_bufs_of(ctx, &bytes);
+        HIP_TRY(-2, hipMalloc(&ctx->bbatch_buf, bytes));
+    }
+    const size_t pool_words = (size_t)BBATCH_COLS * (size_t)P;
+    if (!ctx->bqueue_buf) HIP_TRY(-2, hipMalloc(&ctx->bqueue_buf, bqueue_bufs_at(nullptr).bytes));
+    if (!ctx->bqueue_host) HIP_TRY(-2, hipHostMalloc(&ctx->bqueue_host, sizeof(BeamQueueHost) + pool_words * 4));
+    const BeamBufs bufs = beam_bufs_of(ctx);
+    const BeamQueueBufs qb = bqueue_bufs_at(ctx->bqueue_buf);
+    BeamQueueHost *const qh = reinterpret_cast<BeamQueueHost *>(ctx->bqueue_host);
+    int32_t *const pool_host = reinterpret_cast<int32_t *>(ctx->bqueue_host + sizeof(BeamQueueHost));
+    column_graphs_for(ctx->graphs_bqueue, S, B);
+    const int gset = trie ? 6 : 0;
+    const bool given = trie != nullptr;
+    bgk::BeamQueueCall call{};
+    call.n_beams = B; call.eos_id = eos_id; call.length_penalty = length_penalty; call.early_stopping = early_stopping; call.ids_stride = P; call.n_slots = S;
+    {      // nobody runs yet: every slot's search reads as stopped and reported, no forks
+        HeadImage im(bufs.hdr, bufs.ctl + S);
+        for (int s = 0; s < S; s++) {
+            im.at(bufs.ctl)[s] = beam_ctl_of(B, 1, 0, eos_id, length_penalty, early_stopping, P);
+            im.at(bufs.ctl)[s].done = 1;
+        }
+        for (int c = 0; c < C; c++) im.at(bufs.col_skip)[c] = 1;
+        if (!im.upload()) return -2;
+        qh->hdr = bgk::BeamQueueHdr{};
+        for (int s = 0; s < S; s++) qh->hdr.fin[s] = 1;
+        HIP_TRY(-2, hipMemcpy(qb.hdr, &qh->hdr, sizeof(bgk::BeamQueueHdr), hipMemcpyHostToDevice));
+        if (trie && !trie_upload(ctx, trie, 1, eos_id)) return -2;
+    }
+    const ColumnStep step = [&](int t_max) -> bool {
+        if (!enqueue_forward(ctx, ForwardPass::decode_step(C, t_max))) return false;
+        if (trie && !enqueue_trie(ctx, C, bufs.col_skip, 1)) return false;
+        if (!enqueue_beam_group_select(bufs, S, B, given)) return false;
+        hipLaunchKernelGGL(bgk::beam_slot_report_kernel, dim3((S + bgk::BEAM_QUEUE_REPORT_THREADS - 1) / bgk::BEAM_QUEUE_REPORT_THREADS),
+                           dim3(bgk::BEAM_QUEUE_REPORT_THREADS), 0, ctx->stream, bufs.ctl, S, qb.hdr);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    // (ColumnKeys of a call whose first replayed step sees min_len keys and whose last one max_keys: every bucket a step here can be bounded by)
+    bool use_graph;
+    if (!capture_column_steps(ctx, ctx->graphs_bqueue, gset, ColumnKeys{min_len - 1, 1, P}, max_keys - min_len + 2, step, &use_graph)) return -2;
+
+    const auto &hp = ctx->hp;
+    const int64_t seq_stride = (int64_t)hp.n_layer * P * hp.d_model;
+    std::vector<std::pair<int, int>> landing;              // (slot, request): copies enqueued, not yet known to have arrived
+    // the pool of a search whose copies have arrived -> request r's rows
+    auto decode = [&](int slot, int r) -> bool {
+        const size_t o = (size_t)r * (size_t)B;
+        return beam_read_pools(&qh->ctl[slot], pool_host + (size_t)slot * B * P, (size_t)P, 1, B, n_predict, out_ids + o * row, out_lens + o, out_scores + o, out_counts + r,
+                               "request", r);
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> flat, lens, slots;
+    while (!q.done()) {
+        // ---- refill: the prompts of the admitted requests into the first slot of their groups, shared with the groups' other slots, then one admit launch ----
+        flat.clear(); lens.clear(); slots.clear();
+        const int n_admit = q.refill([&](int slot, int r) {
+            const int32_t *p = prompts + off[(size_t)r];
+            const int len = prompt_lens[r];
+            qh->admit[slots.size()] = bgk::BeamQueueAdmit{slot, p[len - 1], len, cap[(size_t)r]};
+            flat.insert(flat.end(), p, p + len); lens.push_back(len); slots.push_back(slot * B);
+            if (out_admit_step) out_admit_step[r] = q.st.steps;
+            if (out_slot) out_slot[r] = slot;
+            q.st.prompt_columns += len;
+        });
+        if (n_admit > 0) {
+            if (!pack_column_passes(ctx, flat.data(), lens.data(), n_admit, n_batch,
+                                    [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); }, 1, 0, SharedRows{},
+                                    slots.data()))
+                return -2;
+            HIP_TRY(-2, hipMemcpyAsync(qb.admit, qh->admit, sizeof(bgk::BeamQueueAdmit) * (size_t)n_admit, hipMemcpyHostToDevice, ctx->stream));
+            if (B > 1) {
+                hipLaunchKernelGGL(bgk::kv_share_slots_kernel, dim3(hp.n_layer * hp.n_head, n_admit * (B - 1), 2), dim3(256), 0, ctx->stream, qb.admit, B, S, ctx->bk, ctx->bv,
+                                   seq_stride, P, hp.d_model / hp.n_head);
+                HIP_TRY(-2, hipGetLastError());
+            }
+            hipLaunchKernelGGL(bgk::beam_slot_admit_kernel, dim3(n_admit), dim3(bgk::BEAM_QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, call, bufs.ctl, ctx->seq, bufs.col_skip,
+                               bufs.hdr, qb.hdr);
+            HIP_TRY(-2, hipGetLastError());
+        }
+        // ---- one group of steps ----
+        for (int g = q.group_steps(); g > 0; g--) {
+            int t_max = 1;
+            for (int slot = 0; slot < S; slot++)
+                if (q.req[(size_t)slot] >= 0) t_max = std::max(t_max, q.position(slot, prompt_lens[q.req[(size_t)slot]]) + 1);
+            t_max = std::min(t_max, P);
+            if (use_graph) {
+                hipGraphExec_t ge = ctx->graphs_bqueue.exec[gset + graph_bucket(t_max)];
+                if (!ge) BG_FAIL(-2, "internal: no captured beam queue step for %d keys", t_max);
+                HIP_TRY(-2, hipGraphLaunch(ge, ctx->stream));
+            } else if (!step(t_max)) {
+                return -2;
+            }
+            q.step();
+        }
+        q.end_group();
+        // ---- the look at the slots: the header behind the group (lag 0) ----
+        HIP_TRY(-2, hipMemcpyAsync(&qh->hdr, qb.hdr, sizeof(bgk::BeamQueueHdr), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(-2, hipEventRecord(ctx->live_ev[0], ctx->stream));
+        HIP_TRY(-2, hipEventSynchronize(ctx->live_ev[0]));
+        // (the copies of the look before stand in front of this header in the stream: they have arrived, and their slots' twins are free again)
+        for (const auto &sr : landing) if (!decode(sr.first, sr.second)) return -2;
+        landing.clear();
+        for (int slot = 0; slot < S; slot++) {
+            if (!q.live[(size_t)slot]) continue;
+            const int r = q.req[(size_t)slot];
+            if (!qh->hdr.fin[slot]) {
+                if (q.since[(size_t)slot] >= cap[(size_t)r])
+                    BG_FAIL(-2, "internal: request %d (slot %d) is unfinished after %d steps, its limit is %d", r, slot, q.since[(size_t)slot], cap[(size_t)r]);
+                continue;
+            }
+            // the search's state and its B pool rows (whole rows up to the last one's limit), in stream order before the slot is reused
+            const int n_steps = std::max(0, std::min(qh->hdr.steps[slot], cap[(size_t)r]));
+            HIP_TRY(-2, hipMemcpyAsync(&qh->ctl[slot], bufs.ctl + slot, sizeof(bgk::BeamCtl), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(-2, hipMemcpyAsync(pool_host + (size_t)slot * B * P, bufs.pool_ids + (size_t)slot * B * P, ((size_t)(B - 1) * P + (size_t)cap[(size_t)r]) * 4,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+            landing.emplace_back(slot, r);
+            if (out_steps) out_steps[r] = n_steps;
+            q.retire(slot, n_steps);
+        }
+    }
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    for (const auto &sr : landing) if (!decode(sr.first, sr.second)) return -2;
+    if (!xpipe_check(ctx)) return -2;
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    if (stats) *stats = q.st;
+    return 0;
+}
+
+int biogpt_hip_generate_beam_queue(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,
+                                   int32_t n_predict, int32_t n_beams, int32_t max_columns, int32_t group, int32_t n_batch, int32_t eos_id, float length_penalty,
+                                   int32_t early_stopping, biogpt_hip_trie *trie, int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts,
+                                   int32_t *out_steps, int32_t *out_admit_step, int32_t *out_slot, double *seconds_out, biogpt_hip_queue_stats *stats) {
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_beam_queue_once(ctx, prompts, prompt_lens, n_requests, n_predicts, n_predict, n_beams, max_columns, group, n_batch, eos_id, length_penalty,
+                                        early_stopping, trie, out_ids, out_lens, out_scores, out_counts, out_steps, out_admit_step, out_slot, seconds_out, stats);
+    });
+}
+
 // profiling builds (BIOGPT_HIP_PROFILE_HOOKS + BIOGPT_HIP_DBG=128): the raw 100 MHz stage stamps the pipelined launches left (kernels_xpipe.hip.h XP_WALL / XP_TAIL)
 int biogpt_hip_debug_stamps(biogpt_hip_ctx *ctx, size_t offset, size_t count, unsigned long long *out) {
     clear_error();
@@ -4430,6 +4702,27 @@ int biogpt_hip_read_kv(biogpt_hip_ctx *ctx, int which, size_t offset, size_t cou
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipMemcpyAsync(out, stage.p, count * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// What the last column call left in a column's K / V cache slot and beam pool row (tests of slot reuse): the K (which 0) or V (1) row of position pos in every
+// layer, [n_layer][d_model] in the reference's channel order, and the first n_ids words of pool row `column` (either output may be NULL)
+int biogpt_hip_read_column_state(biogpt_hip_ctx *ctx, int32_t column, int32_t which, int32_t pos, float *kv_out, int32_t n_ids, int32_t *pool_out) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    const int L = ctx->hp.n_layer, P = ctx->hp.n_positions, D = ctx->hp.d_model, H = ctx->hp.n_head, dk = D / H;
+    if (column < 0 || column >= ctx->batch_cap) BG_FAIL(-1, "column %d out of range: this context holds %d column caches", column, ctx->batch_cap);
+    if (kv_out && (pos < 0 || pos >= P)) BG_FAIL(-1, "pos %d out of range [0, %d)", pos, P);
+    if (pool_out && (n_ids < 0 || n_ids > P || column >= BBATCH_COLS || !ctx->bbatch_buf)) BG_FAIL(-1, "no pool row %d of %d words (no beam search has run?)", column, n_ids);
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    if (kv_out) {      // head-major [column][layer][head][pos][dk]
+        const float *root = (which ? ctx->bv : ctx->bk) + (size_t)column * L * P * D;
+        for (int l = 0; l < L; l++)
+            for (int h = 0; h < H; h++)
+                HIP_TRY(-2, hipMemcpy(kv_out + (size_t)l * D + (size_t)h * dk, root + (((size_t)l * H + h) * P + pos) * dk, (size_t)dk * 4, hipMemcpyDeviceToHost));
+    }
+    if (pool_out && n_ids > 0) HIP_TRY(-2, hipMemcpy(pool_out, beam_bufs_of(ctx).pool_ids + (size_t)column * P, (size_t)n_ids * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -520,6 +520,40 @@ int biogpt_hip_generate_queue(biogpt_hip_ctx *ctx, const int32_t *prompts /* con
  * an EOS undercut.  admit_step / column [n_requests] and stats as above; prompt_columns stays 0 (the plan knows no prompts).  Returns 0 or -1. */
 int biogpt_hip_queue_plan(const int32_t *gen_lens, int32_t n_requests, int32_t max_columns, int32_t group, int32_t *admit_step, int32_t *column,
                           biogpt_hip_queue_stats *stats /* may be NULL */);
+/* The same scheduler for requests that may end before their limits, as a run drives it: limits[r] = the tokens request r may generate at most (n_r above; 0: it
+ * never takes a column), gen_lens[r] <= limits[r] the tokens it generates (>= 1 where limits[r] > 0).  A group is min(group, the most tokens any running request
+ * may STILL generate under its limit) -- the host of a run does not know where a request will end -- and a look finds finished whoever has generated its
+ * gen_lens[r] tokens.  This is the schedule of every run of biogpt_hip_generate_queue and biogpt_hip_generate_beam_queue (there: steps and slots), with or
+ * without an EOS; with limits == gen_lens it is biogpt_hip_queue_plan.  Returns 0 or -1. */
+int biogpt_hip_queue_plan_limits(const int32_t *gen_lens, const int32_t *limits, int32_t n_requests, int32_t max_columns, int32_t group, int32_t *admit_step,
+                                 int32_t *column, biogpt_hip_queue_stats *stats /* may be NULL */);
+
+/* ---- beam search over a queue: finished searches hand their n_beams columns to the next request ----
+ * n_requests requests share S = min(max_columns / n_beams, eligible requests) group slots of n_beams columns and K / V cache slots each: a request's search
+ * takes a slot when one is free and leaves it when it stops, by transformers' stopping rules or after its own limit.  Request r's hypotheses, lengths, count
+ * and scores are those of biogpt_hip_generate_beam(its prompt alone, n_r, the same n_beams / eos_id / length_penalty / early_stopping / n_batch) -- with a trie,
+ * of biogpt_hip_generate_beam_trie of that prompt alone -- bit for bit, with n_r = min(n_predicts[r], n_positions - prompt_lens[r]): the clamp is per
+ * request.  What else is in the queue, max_columns and group change nothing but the time.  A request with n_r == 0 gets count 0 and never takes a slot.
+ * n_predicts == NULL: n_predict for every request.  out_ids is [n_requests][n_beams][n_predict] (n_predict is the row stride as GIVEN, not clamped), best
+ * hypothesis first, -1 behind a hypothesis's length; out_lens / out_scores [n_requests][n_beams]; out_counts [n_requests] the hypotheses held (rows beyond:
+ * length 0, score 0).  out_steps[r] (may be NULL): the steps r's search took; out_admit_step[r] (may be NULL): the steps run before its first one;
+ * out_slot[r] (may be NULL): its slot; the last two -1 for a request that never ran.  The schedule is biogpt_hip_generate_queue's with slots for columns:
+ * biogpt_hip_queue_plan_limits(out_steps, the limits n_r, n_requests, S, group) computes it for every run.  biogpt_hip_queue_plan(out_steps, ...) is the same
+ * schedule only where no group was cut short by a limit that an early stop undercut -- always at group = 1 or when every search ran to its limit; after an early
+ * stop with group > 1 a run may take more steps than that plan.  stats (may be NULL) count in slots: columns = S; steps; groups;
+ * admissions; prompt_columns = prompt tokens evaluated (once per request); busy_column_steps = the sum of out_steps; column_steps = S * steps.
+ * Needs 1 <= n_beams <= 16, n_beams <= max_columns <= 512, group in [1, 64], the BioGPT-base fast chain (block-quantized weights) and, with a trie, what
+ * biogpt_hip_generate_beam_trie needs.  No generation rules (their history is built per call from the call's prompts), prefix or log-probabilities; the
+ * steps always run as the launch chain.  The context's own K / V cache, position and logits row are left alone.  Returns 0, or < 0 on error (argument
+ * errors, -1, the message names the field, come before any HIP call). */
+int biogpt_hip_generate_beam_queue(biogpt_hip_ctx *ctx, const int32_t *prompts /* concatenated */, const int32_t *prompt_lens, int32_t n_requests,
+                                   const int32_t *n_predicts /* [n_requests], or NULL: n_predict for all */,
+                                   int32_t n_predict /* row stride of out_ids; every n_predicts[r] <= n_predict */, int32_t n_beams,
+                                   int32_t max_columns /* n_beams .. 512 */, int32_t group /* steps between two looks at the slots, 1 .. 64 */, int32_t n_batch,
+                                   int32_t eos_id /* -1: none */, float length_penalty, int32_t early_stopping, biogpt_hip_trie *trie /* may be NULL */,
+                                   int32_t *out_ids /* [n_requests][n_beams][n_predict] */, int32_t *out_lens, float *out_scores, int32_t *out_counts,
+                                   int32_t *out_steps /* may be NULL */, int32_t *out_admit_step /* may be NULL */, int32_t *out_slot /* may be NULL */,
+                                   double *seconds_out, biogpt_hip_queue_stats *stats /* may be NULL */);
 
 /* The draft kernel of prompt-lookup decoding over texts held in host memory, no model: sequence s has text_lens[s] tokens of the concatenated `texts`
  * (the last n_gen[s] of them generated, the last one its current token at position n_past[s]); finished (may be NULL): sequences that draft nothing.
@@ -683,6 +717,10 @@ int biogpt_hip_embed_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32
  * Copy `count` floats of the F32 KV cache (which: 0 = K, 1 = V) starting at element `offset` of
  * the flat [n_layer][n_positions][d_model] array (biogpt.cpp:331-335) to host memory. */
 int biogpt_hip_read_kv(biogpt_hip_ctx *ctx, int which, size_t offset, size_t count, float *out);
+/* Tests of slot reuse: what the last column call (batched generation, beam search, a queue) left in column `column`'s own K / V cache slot and beam pool row.
+ * kv_out (may be NULL): the K (which 0) or V (1) row of position pos in every layer, [n_layer][d_model]; pool_out (may be NULL): the first n_ids words of the
+ * column's pool row.  Nothing is cleared between calls, so rows no call has written hold what the allocation held.  Returns 0, -1 (arguments) or -2. */
+int biogpt_hip_read_column_state(biogpt_hip_ctx *ctx, int32_t column, int32_t which, int32_t pos, float *kv_out, int32_t n_ids, int32_t *pool_out);
 
 /* Profiling builds only (-DBIOGPT_HIP_PROFILE_HOOKS, BIOGPT_HIP_DBG=128; no reference counterpart): the raw wall-clock stamps (100 MHz ticks) the
  * pipelined decode launches left in the context's stamp buffer, `count` words from word `offset` (tools/tail_timeline.py). */
