@@ -47,6 +47,53 @@ class GenLogprobs(C.Structure):
     _fields_ = [("n_top", C.c_int32), ("lp", C.c_void_p), ("top_ids", C.c_void_p), ("top_lp", C.c_void_p)]
 
 
+class Sampler(C.Structure):
+    """biogpt_hip_sampler (include/biogpt_hip.h): a sampler of any width, made by sampler()."""
+    _fields_ = [("top_k", C.c_int32), ("pad", C.c_int32), ("top_p", C.c_double), ("min_p", C.c_double), ("temp", C.c_double)]
+
+    def __repr__(self):
+        return "sampler(top_k=%d, top_p=%r, min_p=%r, temp=%r)" % (self.top_k, self.top_p, self.min_p, self.temp)
+
+
+def sampler(top_k=0, top_p=1.0, min_p=0.0, temp=1.0):
+    """A sampler for generate_sample(sampler=) and sample_wide_rows: top_k 0 is the whole vocabulary, top_p >= 1 no cut, min_p 0 off -- the defaults draw from
+    the model's own distribution ("Sampled generation").  The ranges are checked by the call that uses it."""
+    return Sampler(int(top_k), 0, float(top_p), float(min_p), float(temp))
+
+
+def _as_sampler(s):
+    return s if isinstance(s, Sampler) else sampler(*s)
+
+
+def sample_wide_rows(rows, sampler, states, device=0):
+    """sample_wide_rows_kernel on rows held in host memory (biogpt_hip_sample_wide_rows_device): rows float32 [n][n_vocab]; states uint32 [n][625], the
+    generators, advanced in place.  Returns (ids int32[n], n_cand int32[n]): the drawn ids and the candidates left after all cuts."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv = int(a.shape[0]), int(a.shape[1])
+    if not (isinstance(states, np.ndarray) and states.dtype == np.uint32 and states.flags["C_CONTIGUOUS"] and states.shape == (n, 625)):
+        raise BiogptError("states must be a contiguous uint32 array [n][625]")
+    sp = _as_sampler(sampler)
+    ids, nc = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    if lib().biogpt_hip_sample_wide_rows_device(int(device), a.ctypes.data, n, nv, C.byref(sp), states.ctypes.data, ids.ctypes.data, nc.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return ids, nc
+
+
+def sample_wide_rows_bench(rows, sampler, states, which=0, reps=20, device=0):
+    """One kernel alone on such rows (biogpt_hip_sample_wide_rows_bench): which 0 sample_wide_rows_kernel, 1 sample_rows_kernel.  Returns the seconds of
+    reps launches, each from the states as given (they are not advanced), by device events."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv = int(a.shape[0]), int(a.shape[1])
+    st = np.ascontiguousarray(states, dtype=np.uint32)
+    if st.shape != (n, 625):
+        raise BiogptError("states must be a uint32 array [n][625]")
+    sp = _as_sampler(sampler)
+    secs = np.zeros(max(int(reps), 1), dtype=np.float64)
+    if lib().biogpt_hip_sample_wide_rows_bench(int(device), a.ctypes.data, n, nv, C.byref(sp), st.ctypes.data, int(which), int(reps), secs.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return secs
+
+
 class _LogprobArrays:
     """The arrays of a logprobs=K request for n sequences of w entries, and the struct that names them."""
 
@@ -514,6 +561,11 @@ SYMBOLS = [
     ("biogpt_hip_generate_sample_prefix", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
                                                     C.c_int32, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_prefix_stats", C.c_int, [_P, _P]),
+    ("biogpt_hip_generate_sample_wide", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_generate_sample_wide_prefix", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P,
+                                                         C.POINTER(C.c_double)]),
+    ("biogpt_hip_sample_wide_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    ("biogpt_hip_sample_wide_rows_bench", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
     ("biogpt_hip_generate_greedy_batch_lp", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(GenLogprobs)]),
     ("biogpt_hip_generate_sample_lp", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
                                                 C.c_int32, _P, _P, C.POINTER(C.c_double), C.POINTER(GenLogprobs)]),
@@ -728,6 +780,17 @@ def _logprobs_keyword(plain):
         if logprobs is None:
             return plain(self, *args, **kw)
         return getattr(BiogptModel, "_" + plain.__name__)(self, *args, logprobs=logprobs, **kw)
+    return call
+
+
+def _sampler_keyword(plain):
+    """Adds the keyword-only sampler=None to generate_sample, as _logprobs_keyword adds logprobs: the method's own parameters stay what they are.  None: the
+    method itself.  A sampler: _generate_sample with the same arguments and sampler=."""
+    @functools.wraps(plain)
+    def call(self, *args, sampler=None, **kw):
+        if sampler is None:
+            return plain(self, *args, **kw)
+        return BiogptModel._generate_sample(self, *args, sampler=sampler, **kw)
     return call
 
 
@@ -1090,6 +1153,7 @@ class BiogptModel:
         return hyps, {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:R]], "slot": [int(v) for v in slot[:R]], "steps": [int(v) for v in steps[:R]]}, secs.value
 
     @_logprobs_keyword
+    @_sampler_keyword
     def generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
                         repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None, prefix=None):
         """n_samples sampled continuations of every prompt (list of id lists, or one flat id list), drawn on the device by the reference's top-k / top-p
@@ -1104,13 +1168,27 @@ class BiogptModel:
         logprobs (keyword only): None, or K in [0, 8] -- the call then returns (ids, info, seconds) with info[r] = (logprobs float32[len], top_ids int32[len, K],
         top_logprobs float32[len, K]): the model's log-probability of every generated token under the RAW row (temperature 1, no top_k / top_p cut: the
         number score_batch gives, not the probability under the truncated sampling distribution) and every row's K best entries (INTEGRATION.md,
-        "Log-probabilities of generated tokens").  The ids are those of the call without it.  Not with rules or a trie: ValueError."""
+        "Log-probabilities of generated tokens").  The ids are those of the call without it.  Not with rules or a trie: ValueError.
+        sampler (keyword only): None, or a sampler(top_k, top_p, min_p, temp) of any width -- top_k 0 or up to n_vocab, with min-p -- drawn by
+        sample_wide_rows_kernel ("Sampled generation"); top_k, top_p and temp must then be left at their defaults (BiogptError), everything
+        else works as without it.  With top_k in [1, 64] and min_p 0 the call is the plain one with the sampler's values.  Not with logprobs, rules or a
+        trie: ValueError."""
         return BiogptModel._generate_sample(self, prompts, n_predict, n_samples, top_k, top_p, temp, seed, seeds, eos_id, n_batch, repetition_penalty, no_repeat_ngram_size,
                                             min_new_tokens, suppress_tokens, trie, prefix)
 
     def _generate_sample(self, prompts, n_predict, n_samples=1, top_k=40, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8,
-                         repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None, prefix=None, logprobs=None):
-        """generate_sample, and with logprobs=K its form that returns (ids, info, seconds)."""
+                         repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), trie=None, prefix=None, logprobs=None, sampler=None):
+        """generate_sample, with logprobs=K its form that returns (ids, info, seconds), with sampler= the wide sampler's."""
+        if sampler is not None:
+            if logprobs is not None:
+                raise ValueError("sampler= cannot be combined with logprobs=")
+            if trie is not None:
+                raise ValueError("sampler= cannot be combined with trie=")
+            if float(repetition_penalty) != 1.0 or int(no_repeat_ngram_size) != 0 or int(min_new_tokens) != 0 or len(suppress_tokens):
+                raise ValueError("sampler= cannot be combined with generation rules")
+            if (top_k, top_p, temp) != (40, 0.9, 0.9):
+                raise BiogptError("sampler= carries top_k, top_p and temp: leave the call's own at their defaults")
+            sampler = _as_sampler(sampler)
         if logprobs is not None:
             if trie is not None:
                 raise ValueError("logprobs= cannot be combined with trie=")
@@ -1152,7 +1230,15 @@ class BiogptModel:
                 return [], [], secs.value
             rows = out.reshape(-1)
             return [rows[r * got:r * got + int(ol[r])].copy() for r in range(n)], arr.info(n, got, [int(v) for v in ol[:n]]), secs.value
-        if prefix is not None:
+        if sampler is not None and prefix is not None:
+            pre = _flat_ids([prefix])
+            got = lib().biogpt_hip_generate_sample_wide_prefix(self._h, pre.ctypes.data, len(prefix), flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples),
+                                                               int(n_batch), int(n_predict), C.byref(sampler), sd.ctypes.data, int(eos_id), out.ctypes.data,
+                                                               ol.ctypes.data, C.byref(secs))
+        elif sampler is not None:
+            got = lib().biogpt_hip_generate_sample_wide(self._h, flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples), int(n_batch), int(n_predict),
+                                                        C.byref(sampler), sd.ctypes.data, int(eos_id), out.ctypes.data, ol.ctypes.data, C.byref(secs))
+        elif prefix is not None:
             pre = _flat_ids([prefix])
             got = lib().biogpt_hip_generate_sample_prefix(self._h, pre.ctypes.data, len(prefix), flat.ctypes.data, lens.ctypes.data, len(prompts), int(n_samples),
                                                           int(n_batch), int(n_predict), int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id),

@@ -44,6 +44,7 @@
 #include "kernels_embed.hip.h"
 #include "kernels_beam.hip.h"
 #include "kernels_sample.hip.h"
+#include "kernels_wide_sample.hip.h"
 #include "kernels_genlp.hip.h"
 #include "kernels_rules.hip.h"
 #include "kernels_trie.hip.h"
@@ -230,7 +231,7 @@ namespace {
 // place, 4 with log-probabilities, 5 with log-probabilities behind a shared prefix read in place) + 6 * (steps as column-per-XCD launches) + context
 // bucket], valid for the call shape (key_a, key_b) they were captured for -- sequences, or groups and beams
 struct ColumnGraphs {
-    hipGraphExec_t exec[72] = {};
+    hipGraphExec_t exec[96] = {};
     int key_a = 0, key_b = 0;
 };
 
@@ -2481,7 +2482,8 @@ struct ColumnCall {
     ColumnGraphs *graphs = nullptr;     // the mode's captured steps, valid for the call shape (key_a, key_b)
     int key_a = 0, key_b = 0;
     int extra_steps = 0;                // steps beyond one per token (contrastive: 1, the prompt's last token has a step of its own)
-    int gset_extra = 0;                 // 12 with rules, 24 with a trie: another form of the step, so other graphs
+    int gset_extra = 0;                 // 12 with rules, 24 with a trie, 72 with the wide sampler (84 behind shared rows read in place): another form of the
+                                        // step, so other graphs
     bool with_lp = false;               // the selection also writes log-probabilities (kernels_genlp.hip.h; never with rules or a trie): graph sets of its own
     int key_stride = 1;                 // positions a column can move on in one step, at most (prompt-lookup decoding: 1 + max_draft); > 1: the word behind
                                         // live_dev holds the furthest position of any column
@@ -2732,7 +2734,7 @@ static int run_column_call(biogpt_hip_ctx *ctx, ColumnCall &cc, int n_predict, d
     cc.in_place = cc.n_shared > 0 && xc == 0;
     if (!upload_column_starts(ctx, prompts, lens, cc.n_prompts, cc.per_prompt, cc.n_shared, cc.in_place ? shared : SharedRows{})) return -2;
     if (cc.upload && !cc.upload()) return -2;
-    const int gset = 6 * xc + (cc.with_lp ? (cc.in_place ? 60 : 48) : cc.in_place ? 36 : cc.gset_extra);
+    const int gset = 6 * xc + (cc.with_lp ? (cc.in_place ? 60 : 48) : cc.in_place ? (cc.gset_extra == 72 ? 84 : 36) : cc.gset_extra);
     const ColumnKeys keys{cc.max_len, cc.key_stride, ctx->hp.n_positions};
     bool use_graph;
     if (!capture_column_steps(ctx, *cc.graphs, gset, keys, n_steps, cc.step, &use_graph)) return -2;
@@ -3460,12 +3462,13 @@ static bool enqueue_trie(biogpt_hip_ctx *c, int n_rows, const int32_t *skip, int
 struct SampleBufs {
     bgk::SampleCtl *ctl;
     bgk::SampleSeq *seq;    // [n_seqs]
+    bgk::SampleWide *wide;  // the sampler of a wide call (kernels_wide_sample.hip.h), behind everything the plain step knows
     size_t bytes;
 };
 static SampleBufs sample_bufs_at(uint8_t *base, size_t n_seqs) {
     ByteLayout l;
     SampleBufs b{};
-    b.ctl = l.take<bgk::SampleCtl>(base, 1); b.seq = l.take<bgk::SampleSeq>(base, n_seqs);
+    b.ctl = l.take<bgk::SampleCtl>(base, 1); b.seq = l.take<bgk::SampleSeq>(base, n_seqs); b.wide = l.take<bgk::SampleWide>(base, 1);
     b.bytes = l.bytes();
     return b;
 }
@@ -3476,12 +3479,36 @@ static bgk::SampleCtl sample_ctl_of(int top_k, int eos_id, int n_seqs, double to
     return hc;
 }
 
+static_assert(sizeof(bgk::SampleWide) == sizeof(biogpt_hip_sampler), "the sampler goes to the device as it is");
+// the ranges of a sampler's values, for rows of V entries (V < 0: the width is not known yet)
+static bool check_sampler(const biogpt_hip_sampler *sp, int V) {
+    if (!sp) BG_FAIL(false, "null sampler");
+    if (sp->top_k < 0) BG_FAIL(false, "sampler: top_k must be 0 (the whole vocabulary) or in [1, n_vocab] (got %d)", sp->top_k);
+    if (V >= 0 && sp->top_k > V) BG_FAIL(false, "sampler: top_k must be 0 (the whole vocabulary) or in [1, n_vocab = %d] (got %d)", V, sp->top_k);
+    if (!std::isfinite(sp->temp) || !(sp->temp > 0.0)) BG_FAIL(false, "sampler: temp must be finite and > 0");
+    if (!std::isfinite(sp->top_p)) BG_FAIL(false, "sampler: top_p must be finite (>= 1: no cut)");
+    if (!std::isfinite(sp->min_p) || !(sp->min_p >= 0.0 && sp->min_p < 1.0)) BG_FAIL(false, "sampler: min_p must be finite and in [0, 1) (0: off)");
+    return true;
+}
+static bgk::SampleWide sample_wide_of(const biogpt_hip_sampler &sp) {
+    bgk::SampleWide w{};
+    w.top_k = sp.top_k; w.top_p = sp.top_p; w.min_p = sp.min_p; w.temp = sp.temp;
+    return w;
+}
+// a sampler that sample_rows_kernel serves: the call is then the plain one
+static bool sampler_is_plain(const biogpt_hip_sampler &sp) { return sp.top_k >= 1 && sp.top_k <= bgk::SAMPLE_MAX_K && sp.min_p == 0.0; }
+
 static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
                                 int32_t n_batch, int32_t n_predict, int32_t top_k, double top_p, double temp, const uint32_t *seeds, int32_t eos_id,
                                 int32_t *out_ids, int32_t *out_lens, double *seconds_out, const biogpt_hip_gen_rules *rules, biogpt_hip_trie *trie = nullptr,
-                                const int32_t *prefix = nullptr, int32_t n_prefix = 0, const biogpt_hip_gen_logprobs *lp = nullptr) {
+                                const int32_t *prefix = nullptr, int32_t n_prefix = 0, const biogpt_hip_gen_logprobs *lp = nullptr,
+                                const biogpt_hip_sampler *wide = nullptr) {
     clear_error();
     if (!ctx) BG_FAIL(-1, "null context");
+    // (wide != null, biogpt_hip_generate_sample_wide / _prefix: sample_wide_rows_kernel is the selection and top_k, top_p, temp are not looked at; no rules, no
+    // trie, no log-probabilities)
+    if (wide && (rules || trie || lp)) BG_FAIL(-1, "the wide sampler cannot be combined with generation rules, a trie or log-probabilities");
+    if (wide && !check_sampler(wide, ctx->hp.n_vocab)) return -1;
     if (!prompts || !prompt_lens || !seeds || !out_ids || !out_lens) BG_FAIL(-1, "null argument");
     if (lp && !check_gen_logprobs(lp, ctx->hp.n_vocab)) return -1;
     if (lp && (rules || trie)) BG_FAIL(-1, "log-probabilities cannot be combined with generation rules or a trie");
@@ -3507,7 +3534,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     cc.prompts = prompts; cc.prompt_lens = prompt_lens;
     cc.n_prompts = n_prompts; cc.per_prompt = n_samples; cc.n_batch = n_batch;
     cc.graphs = &ctx->graphs_sample; cc.key_a = n_seqs;
-    cc.gset_extra = trie ? 24 : ru ? 12 : 0;
+    cc.gset_extra = wide ? 72 : trie ? 24 : ru ? 12 : 0;
     cc.prefix = prefix; cc.n_prefix = n_prefix;     // (prefix != null, biogpt_hip_generate_sample_prefix: the prompts are suffixes and may be empty; no rules, no trie)
     cc.with_lp = lp != nullptr;                     // (biogpt_hip_generate_sample_lp: sample_lp_rows_kernel is the selection; no rules, no trie)
     cc.prepare = [&]() -> bool {
@@ -3527,6 +3554,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
         std::vector<uint8_t> h(sb.bytes, 0);
         const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_seqs);
         *hb.ctl = sample_ctl_of(top_k, eos_id, n_seqs, top_p, temp);
+        if (wide) *hb.wide = sample_wide_of(*wide);
         for (int r = 0; r < n_seqs; r++) { bgk::mt_seed(seeds[r], hb.seq[r].mt); bgk::mt_regenerate(hb.seq[r].mt); }
         HIP_TRY(false, hipMemcpy(sb.ctl, h.data(), h.size(), hipMemcpyHostToDevice));
         if (lp && !genlp_upload(lb, lp->n_top, cc.n_predict)) return false;
@@ -3537,7 +3565,10 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
         if (!enqueue_forward(ctx, cc.in_place ? ForwardPass::decode_step_shared(n_seqs, t_max, cc.n_shared) : ForwardPass::decode_step(n_seqs, t_max))) return false;
         if (ru && !enqueue_rules(ctx, n_seqs, &sb.seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
         if (trie && !enqueue_trie(ctx, n_seqs, &sb.seq->finished, (int)(sizeof(bgk::SampleSeq) / 4))) return false;
-        if (lp)
+        if (wide)
+            hipLaunchKernelGGL(bgk::sample_wide_rows_kernel, dim3(n_seqs), dim3(bgk::WIDE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, sb.wide, sb.ctl, sb.seq, ctx->seq,
+                               ctx->seq_gen, P, (int32_t *)nullptr);
+        else if (lp)
             hipLaunchKernelGGL(bgk::sample_lp_rows_kernel, dim3(n_seqs), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, sb.ctl, sb.seq, ctx->seq, ctx->seq_gen, P,
                                lb.out());
         else
@@ -3586,6 +3617,32 @@ int biogpt_hip_generate_sample_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix
         return generate_sample_once(ctx, suffixes, suffix_lens, n_prompts, n_samples, n_batch, n_predict, top_k, top_p, temp, seeds, eos_id, out_ids, out_lens, seconds_out, nullptr,
                                     nullptr, prefix, n_prefix);
     });
+}
+
+// biogpt_hip_generate_sample (prefix == null) or biogpt_hip_generate_sample_prefix with a sampler of any width.  One that sample_rows_kernel serves is handed
+// to the plain call as its three values: the same launches, the same graphs
+static int generate_sample_wide(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts,
+                                int32_t n_samples, int32_t n_batch, int32_t n_predict, const biogpt_hip_sampler *sampler, const uint32_t *seeds, int32_t eos_id,
+                                int32_t *out_ids, int32_t *out_lens, double *seconds_out) {
+    clear_error();
+    if (!check_sampler(sampler, ctx ? ctx->hp.n_vocab : -1)) return -1;
+    const bool plain = sampler_is_plain(*sampler);
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_sample_once(ctx, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, plain ? sampler->top_k : 1, plain ? sampler->top_p : 1.0,
+                                    plain ? sampler->temp : 1.0, seeds, eos_id, out_ids, out_lens, seconds_out, nullptr, nullptr, prefix, prefix ? n_prefix : 0, nullptr,
+                                    plain ? nullptr : sampler);
+    });
+}
+int biogpt_hip_generate_sample_wide(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples, int32_t n_batch,
+                                    int32_t n_predict, const biogpt_hip_sampler *sampler, const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens,
+                                    double *seconds_out) {
+    return generate_sample_wide(ctx, nullptr, 0, prompts, prompt_lens, n_prompts, n_samples, n_batch, n_predict, sampler, seeds, eos_id, out_ids, out_lens, seconds_out);
+}
+int biogpt_hip_generate_sample_wide_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes, const int32_t *suffix_lens,
+                                           int32_t n_prompts, int32_t n_samples, int32_t n_batch, int32_t n_predict, const biogpt_hip_sampler *sampler,
+                                           const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, double *seconds_out) {
+    if (!check_prefix_pointers(ctx, prefix, suffixes, suffix_lens)) return -1;
+    return generate_sample_wide(ctx, prefix, n_prefix, suffixes, suffix_lens, n_prompts, n_samples, n_batch, n_predict, sampler, seeds, eos_id, out_ids, out_lens, seconds_out);
 }
 
 // biogpt_hip_generate_sample (prefix == null) or biogpt_hip_generate_sample_prefix with the log-probabilities of the generated tokens; no rules, no trie

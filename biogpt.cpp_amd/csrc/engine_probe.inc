@@ -640,6 +640,90 @@ int biogpt_hip_sample_rows_device(int device, const float *logits, int32_t n_row
     return 0;
 }
 
+// sample_wide_rows_kernel (which 0) or sample_rows_kernel (which 1) over rows held in host memory, as biogpt_hip_sample_rows_device.  mt_out (or null): the
+// states after one launch; n_cand_out (or null): which 0 only.  reps > 0 (biogpt_hip_sample_wide_rows_bench): the launch is then repeated from the states it
+// began with, restored by a device copy in front of each, and seconds_out[i] is the time between two events around launch i alone
+static int sample_wide_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, const biogpt_hip_sampler *sampler, const uint32_t *mt_in,
+                                   uint32_t *mt_out, int32_t *ids_out, int32_t *n_cand_out, int32_t which, int32_t reps, double *seconds_out) {
+    if (!logits || !mt_in) BG_FAIL(-1, "null argument");
+    if (!check_sampler(sampler, n_vocab < 1 ? -1 : n_vocab)) return -1;
+    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
+    if (which != 0 && which != 1) BG_FAIL(-1, "which must be 0 (sample_wide_rows_kernel) or 1 (sample_rows_kernel)");
+    if (which == 1 && !sampler_is_plain(*sampler)) BG_FAIL(-1, "sample_rows_kernel serves top_k in [1, %d] with min_p 0", bgk::SAMPLE_MAX_K);
+    if (reps < 0 || reps > 10000 || (reps > 0 && !seconds_out)) BG_FAIL(-1, "reps must be in [0, 10000], with seconds_out");
+    for (int r = 0; r < n_rows; r++)
+        if (mt_in[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sample_bufs_at(nullptr, (size_t)n_rows).bytes;
+    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = (size_t)n_rows * 4;
+    std::vector<uint8_t> h(sq_b, 0);
+    const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_rows);
+    *hb.ctl = sample_ctl_of(which == 1 ? sampler->top_k : 1, -1, n_rows, which == 1 ? sampler->top_p : 1.0, which == 1 ? sampler->temp : 1.0);
+    *hb.wide = sample_wide_of(*sampler);
+    for (int r = 0; r < n_rows; r++) std::memcpy(hb.seq[r].mt, mt_in + (size_t)r * 625, 625 * 4);
+    ByteLayout l;      // [logits | ctl + states + sampler | column states | ids | candidate counts | ctl + states + sampler again, with reps]
+    const size_t o_lg = l.part(lg_b), o_sq = l.part(sq_b), o_st = l.part(st_b), o_id = l.part(id_b), o_nc = l.part(id_b), o_keep = l.part(reps > 0 ? sq_b : 0);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    const SampleBufs sb = sample_bufs_at(d.p + o_sq, (size_t)n_rows);
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, logits, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(sb.ctl, h.data(), sq_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_st, 0, o_keep - o_st));
+    auto launch = [&] {
+        if (which == 0)
+            hipLaunchKernelGGL(bgk::sample_wide_rows_kernel, dim3(n_rows), dim3(bgk::WIDE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, sb.wide, sb.ctl, sb.seq,
+                               d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), 1, d.at<int32_t>(o_nc));
+        else
+            hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, sb.ctl, sb.seq,
+                               d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), 1);
+    };
+    launch();
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    if (mt_out) {
+        std::vector<uint8_t> back(sq_b);
+        HIP_TRY(-2, hipMemcpy(back.data(), sb.ctl, sq_b, hipMemcpyDeviceToHost));
+        const SampleBufs bb = sample_bufs_at(back.data(), (size_t)n_rows);
+        for (int r = 0; r < n_rows; r++) std::memcpy(mt_out + (size_t)r * 625, bb.seq[r].mt, 625 * 4);
+    }
+    if (ids_out) HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
+    if (n_cand_out) HIP_TRY(-2, hipMemcpy(n_cand_out, d.p + o_nc, id_b, hipMemcpyDeviceToHost));
+    if (reps > 0) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIP_TRY(-2, hipMemcpy(d.p + o_keep, h.data(), sq_b, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipEventCreate(&e0));
+        HIP_TRY(-2, hipEventCreate(&e1));
+        hipError_t err = hipSuccess;
+        for (int i = 0; i < reps && err == hipSuccess; i++) {
+            float ms = 0.0f;
+            err = hipMemcpyAsync(sb.ctl, d.p + o_keep, sq_b, hipMemcpyDeviceToDevice, 0);
+            if (err == hipSuccess) err = hipMemsetAsync(d.p + o_st, 0, st_b, 0);
+            if (err == hipSuccess) err = hipEventRecord(e0, 0);
+            if (err == hipSuccess) { launch(); err = hipGetLastError(); }
+            if (err == hipSuccess) err = hipEventRecord(e1, 0);
+            if (err == hipSuccess) err = hipEventSynchronize(e1);
+            if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+            seconds_out[i] = (double)ms * 1e-3;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        HIP_TRY(-2, err);
+    }
+    return 0;
+}
+int biogpt_hip_sample_wide_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, const biogpt_hip_sampler *sampler, uint32_t *mt_states,
+                                       int32_t *ids_out, int32_t *n_cand_out) {
+    clear_error();
+    if (!ids_out) BG_FAIL(-1, "null argument");
+    return sample_wide_rows_device(device, logits, n_rows, n_vocab, sampler, mt_states, mt_states, ids_out, n_cand_out, 0, 0, nullptr);
+}
+int biogpt_hip_sample_wide_rows_bench(int device, const float *logits, int32_t n_rows, int32_t n_vocab, const biogpt_hip_sampler *sampler, const uint32_t *mt_states,
+                                      int32_t which, int32_t reps, double *seconds_out) {
+    clear_error();
+    if (reps < 1) BG_FAIL(-1, "reps must be in [1, 10000]");
+    return sample_wide_rows_device(device, logits, n_rows, n_vocab, sampler, mt_states, nullptr, nullptr, nullptr, which, reps, seconds_out);
+}
+
 // genlp_greedy_rows_kernel (mode 0) or sample_lp_rows_kernel (mode 1) over rows held in host memory (tests of the kernels themselves), one entry per row
 // (stride 1): ids_out [n_rows] the chosen ids, lp_out [n_rows] their log-probabilities, top_ids_out / top_lp_out [n_rows][n_top] the rows' best entries
 // (null with n_top 0).  Mode 1 draws as biogpt_hip_sample_rows_device does (top_k, top_p, temp, mt_states: 625 words per row, advanced in place); mode 0

@@ -14,7 +14,9 @@
 //                          append     the id to the sequence's history, its next token and position; an EOS sets the sequence's finished
 //                                     flag instead: a finished column keeps its token and position (it recomputes the K / V row it has).
 //                        The step is sample_rows_step<Extra>; sample_rows_kernel instantiates it with SamplePlain (nothing added), sample_lp_rows_kernel
-//                        (kernels_genlp.hip.h) with the log-probabilities of the drawn token and of the row's best entries.
+//                        (kernels_genlp.hip.h) with the log-probabilities of the drawn token and of the row's best entries.  The generator's block and the
+//                        append are functions of their own (sample_mt_refill, sample_append): sample_wide_rows_kernel (kernels_wide_sample.hip.h), the
+//                        selection for any top_k with min-p, runs the same.
 //   kv_share_kernel      before the first step of a call with several samples per prompt: the prompt's K / V rows from the slot of the
 //                        prompt's first sample to the slots of the others (head-major cache: one contiguous run per (layer, head)).
 //   kv_prefix_copy_kernel  a call behind a shared prefix whose steps know one slot per sequence: the prefix's shared rows from the slot they were
@@ -214,6 +216,49 @@ __device__ __forceinline__ int sample_topk(const float *row, int n_vocab, int K,
     return k_eff;
 }
 
+// ---- what a sampling step shares with the wide sampler (kernels_wide_sample.hip.h): the generator's block and the step's epilogue ----
+// An exhausted block of outputs is regenerated by the whole workgroup of THREADS >= 227 threads (the words of [0, 227), [227, 454), [454, 623) and 623
+// depend on the old block and on the ranges before them only).  mt_old / mt_new: MT_N words of LDS each.  Called by every thread.
+template <int THREADS>
+__device__ __forceinline__ void sample_mt_refill(SampleSeq *me, uint32_t *mt_old, uint32_t *mt_new) {
+    static_assert(THREADS >= MT_N - MT_M, "one thread per word of a range");
+    const int tid = threadIdx.x;
+    if (me->mt[MT_N] == (uint32_t)MT_N) {
+        constexpr int D = MT_N - MT_M;
+        for (int i = tid; i < MT_N; i += THREADS) mt_old[i] = me->mt[i];
+        __syncthreads();
+        if (tid < D) mt_new[tid] = mt_mix(mt_old[tid], mt_old[tid + 1], mt_old[tid + MT_M]);
+        __syncthreads();
+        if (tid < D) mt_new[tid + D] = mt_mix(mt_old[tid + D], mt_old[tid + D + 1], mt_new[tid]);
+        __syncthreads();
+        if (tid < D && tid + 2 * D < MT_N - 1) mt_new[tid + 2 * D] = mt_mix(mt_old[tid + 2 * D], mt_old[tid + 2 * D + 1], mt_new[tid + D]);
+        __syncthreads();
+        if (tid == 0) mt_new[MT_N - 1] = mt_mix(mt_old[MT_N - 1], mt_new[0], mt_new[MT_M - 1]);
+        __syncthreads();
+        for (int i = tid; i < MT_N; i += THREADS) me->mt[i] = mt_new[i];
+        if (tid == 0) me->mt[MT_N] = 0;
+        __syncthreads();
+    }
+}
+
+// The epilogue of row r's step, by one thread: the id to the sequence's history, its next token and position; an EOS sets the sequence's finished flag
+// instead and takes it off the count of the unfinished.  emit(g): what the caller adds for entry g of the history.
+template <class Emit>
+__device__ __forceinline__ void sample_append(int r, int id, int eos_id, int32_t *n_live, SampleSeq *me, SeqState *seq, int32_t *seq_gen, int gen_stride, Emit emit) {
+    SeqState *s = seq + r;
+    const int g = s->n_gen;
+    if (g < gen_stride) seq_gen[(size_t)r * gen_stride + g] = id;
+    emit(g);
+    s->n_gen = g + 1;
+    if (eos_id >= 0 && id == eos_id) {
+        me->finished = 1;
+        atomicSub(n_live, 1);
+    } else {
+        s->token = id;
+        s->n_past += 1;
+    }
+}
+
 // What a kernel may add to the step of sample_rows_kernel without touching its draw (sample_lp_rows_kernel, kernels_genlp.hip.h: the log-probabilities of
 // the drawn token and of the row's best): also_select() more candidates wanted than top_k (they follow the top_k in the same order, so the draw sees the
 // candidates it would have seen); row_stats() by every thread behind the selection (k_all candidates in top_v, visible); emit() by thread 0 with the
@@ -240,24 +285,7 @@ __device__ __forceinline__ void sample_rows_step(const float *logits, int ldl, i
     const float *row = logits + (size_t)r * ldl;
     const int K = min(min(ctl->top_k, SAMPLE_MAX_K), n_vocab);
 
-    // ---- the generator: an exhausted block of outputs is regenerated by the whole workgroup (the words of [0, 227), [227, 454), [454, 623)
-    //      and 623 depend on the old block and on the ranges before them only) ----
-    if (me->mt[MT_N] == (uint32_t)MT_N) {
-        constexpr int D = MT_N - MT_M;
-        for (int i = tid; i < MT_N; i += SAMPLE_THREADS) mt_old[i] = me->mt[i];
-        __syncthreads();
-        if (tid < D) mt_new[tid] = mt_mix(mt_old[tid], mt_old[tid + 1], mt_old[tid + MT_M]);
-        __syncthreads();
-        if (tid < D) mt_new[tid + D] = mt_mix(mt_old[tid + D], mt_old[tid + D + 1], mt_new[tid]);
-        __syncthreads();
-        if (tid + 2 * D < MT_N - 1) mt_new[tid + 2 * D] = mt_mix(mt_old[tid + 2 * D], mt_old[tid + 2 * D + 1], mt_new[tid + D]);
-        __syncthreads();
-        if (tid == 0) mt_new[MT_N - 1] = mt_mix(mt_old[MT_N - 1], mt_new[0], mt_new[MT_M - 1]);
-        __syncthreads();
-        for (int i = tid; i < MT_N; i += SAMPLE_THREADS) me->mt[i] = mt_new[i];
-        if (tid == 0) me->mt[MT_N] = 0;
-        __syncthreads();
-    }
+    sample_mt_refill<SAMPLE_THREADS>(me, mt_old, mt_new);
 
     const int k_all = sample_topk(row, n_vocab, max(K, min(min(extra.also_select(), SAMPLE_MAX_K), n_vocab)), top_v, top_i);
     const int k_eff = min(k_all, K);
@@ -269,20 +297,7 @@ __device__ __forceinline__ void sample_rows_step(const float *logits, int ldl, i
         pick = sample_tail(top_v, k_eff, ctl->top_p, ctl->temp, me->mt, work_p, work, tid, SAMPLE_THREADS, SampleBlockSync());
         id = top_i[pick];
     }
-    if (tid == 0) {
-        SeqState *s = seq + r;
-        const int g = s->n_gen;
-        if (g < gen_stride) seq_gen[(size_t)r * gen_stride + g] = id;
-        extra.emit(r, g, pick, top_v, top_i, k_all);
-        s->n_gen = g + 1;
-        if (ctl->eos_id >= 0 && id == ctl->eos_id) {
-            me->finished = 1;
-            atomicSub(&ctl->n_live, 1);
-        } else {
-            s->token = id;
-            s->n_past += 1;
-        }
-    }
+    if (tid == 0) sample_append(r, id, ctl->eos_id, &ctl->n_live, me, seq, seq_gen, gen_stride, [&](int g) { extra.emit(r, g, pick, top_v, top_i, k_all); });
 }
 
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(const float *logits, int ldl, int n_vocab, SampleCtl *ctl, SampleSeq *sq,

@@ -634,6 +634,41 @@ int biogpt_hip_generate_sample_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix
  * rows reach the columns' slots by a copy (also with n_shared == 0, when there was nothing to copy), 0 where they run on the launch chain and read shared rows in place.  Returns 0, or -1 for a null argument. */
 int biogpt_hip_prefix_stats(const biogpt_hip_ctx *ctx, int32_t out[4]);
 
+/* ---- whole-vocabulary sampling: any top_k up to n_vocab, top_p and min_p, drawn on the device inside the captured step (csrc/kernels_wide_sample.hip.h;
+ * INTEGRATION.md, "Sampled generation") ----
+ * A sampler is (top_k, top_p, min_p, temp).  top_k 0: the whole vocabulary (k = n_vocab), else k = top_k in [1, n_vocab]; temp finite and > 0; top_p
+ * finite (>= 1: no cut); min_p finite and in [0, 1) (0: off).  A row's result is biogpt_sample_top_k_top_p's (biogpt.cpp:908-980) with that k, as
+ * biogpt_hip_generate_sample states it, with one stage added between the top-p cut and the draw: of the n candidates left, the longest prefix with
+ * probs[i] >= min_p * probs[0] stays (candidate 0 always; the draw normalises).  top_k = 0, top_p = 1, temp = 1 draws from the model's own distribution.
+ * A row whose best value is -inf, or that holds NaNs only, gives id 0 and takes no generator output; rows hold no +inf.  The device sums integers
+ * (weights rounded to 2^-62 of the best candidate's), in any order: the same row, sampler and generator state give the same id whatever else is in
+ * the call, and the ids are the reference's wherever no decision -- a compared cumulative sum against top_p, u against a partial sum of the draw,
+ * probs[i] / probs[0] against min_p -- lies within 1e-9 of its border (the sums differ from the reference's sequential ones by < 5e-12).
+ * With top_k in [1, 64] and min_p = 0 the generate calls below ARE biogpt_hip_generate_sample / _prefix with the sampler's values, bit for bit; otherwise
+ * the step's selection is sample_wide_rows_kernel, one launch as before, captured once for any sampler (the values live in device memory).  Everything else --
+ * sequences, seeds, n_batch, EOS, outputs, limits, return values -- is as for biogpt_hip_generate_sample / biogpt_hip_generate_sample_prefix.  There is
+ * no form with log-probabilities, generation rules, a trie or a queue.  Argument errors return -1 before any HIP call. */
+typedef struct biogpt_hip_sampler {
+    int32_t top_k, pad;
+    double top_p, min_p, temp;
+} biogpt_hip_sampler;
+int biogpt_hip_generate_sample_wide(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_prompts, int32_t n_samples,
+                                    int32_t n_batch, int32_t n_predict, const biogpt_hip_sampler *sampler, const uint32_t *seeds, int32_t eos_id,
+                                    int32_t *out_ids, int32_t *out_lens, double *seconds_out /* may be NULL */);
+int biogpt_hip_generate_sample_wide_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes /* concatenated */,
+                                           const int32_t *suffix_lens, int32_t n_prompts, int32_t n_samples, int32_t n_batch, int32_t n_predict,
+                                           const biogpt_hip_sampler *sampler, const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens,
+                                           double *seconds_out /* may be NULL */);
+/* sample_wide_rows_kernel -- always, also for k <= 64 -- over n_rows <= 4096 logits rows of n_vocab floats held in host memory: row r is drawn from with
+ * the state mt_states[r * 625 ..] (advanced in place); n_cand_out[r] (may be NULL): the candidates left after all cuts, 0 for a row without a finite
+ * value.  For tests of the kernel itself. */
+int biogpt_hip_sample_wide_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, const biogpt_hip_sampler *sampler,
+                                       uint32_t *mt_states, int32_t *ids_out, int32_t *n_cand_out);
+/* One kernel alone on such rows, for measurement: which 0 sample_wide_rows_kernel, 1 sample_rows_kernel (then top_k in [1, 64], min_p 0).  After one
+ * launch that is not timed, reps in [1, 10000] launches from the same generator states; seconds_out[i]: the time between two events around launch i. */
+int biogpt_hip_sample_wide_rows_bench(int device, const float *logits, int32_t n_rows, int32_t n_vocab, const biogpt_hip_sampler *sampler,
+                                      const uint32_t *mt_states, int32_t which, int32_t reps, double *seconds_out);
+
 /* ---- log-probabilities of generated tokens: the model's confidence in what it generated, without a second pass (transformers' output_scores /
  * compute_transition_scores, the logprobs = k of OpenAI-style interfaces) ----
  * For sequence r and its generated token t < out_lens[r] (greedy: every t < the clamped n_predict), with l the f32 logits row the token was chosen
