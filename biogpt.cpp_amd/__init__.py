@@ -497,6 +497,7 @@ SYMBOLS = [
     ("biogpt_hip_eval_inplace", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(C.POINTER(C.c_float))]),
     ("biogpt_hip_resident_stats", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("biogpt_hip_chunk_launches", C.c_int64, [_P]),
+    ("biogpt_hip_mfma_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_stamps", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     ("biogpt_hip_generate_launches", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
@@ -571,6 +572,7 @@ SYMBOLS = [
                                                 C.c_int32, _P, _P, C.POINTER(C.c_double), C.POINTER(GenLogprobs)]),
     ("biogpt_hip_genlp_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
     ("biogpt_hip_attn_device", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    ("biogpt_hip_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32] + [_P] * 7 + [C.c_int32] * 3 + [_P] * 7),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_attn_prefix_bench", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     ("biogpt_hip_hidden", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
@@ -643,6 +645,53 @@ def quantize_rows_device(rows, type_id, device=0):
     if lib().biogpt_hip_quantize_rows_device(int(device), int(type_id), a.ctypes.data, nrows, k, out.ctypes.data) != 0:
         raise BiogptError(_err())
     return out
+
+
+CHAIN_OPS = {"LNQ": 0, "QKV": 1, "OPROJ": 2, "FC1_LN": 3, "FC1_Q8": 4, "FC2": 5, "LMHEAD": 6}
+CHAIN_ROUTES = {"VALU_1": 0, "VALU_8": 1, "MFMA_1": 2, "MFMA_2": 3}
+CHAIN_SHAPES = {"QKV": (3072, 1024), "OPROJ": (1024, 1024), "FC1_LN": (4096, 1024), "FC1_Q8": (4096, 1024), "FC2": (1024, 4096)}      # LMHEAD: (any, 1024)
+
+
+def chain_device(op, route=None, wtype=0, M=0, N=1, w_rows=None, x=None, ln_w=None, ln_b=None, q81=0, aq_q=None, aq_d=None, aq_s=None, bias=None, resid=None,
+                 dev_state=None, seq_states=None, col_mode=0, P=0, k_slots=None, v_slots=None, device=0):
+    """One stand-alone launch of a linear stage of the many-column chain (biogpt_hip_chain_device; include/biogpt_hip.h has the inputs of each op).  op and route by
+    name (CHAIN_OPS, CHAIN_ROUTES; LNQ has no route).  Returns a dict of the outputs WHOLE as the probe allocated them, guard columns and rows included and preset to
+    0xff bytes: "out" float32 [cols, ldo] ([cols, 1024] for QKV), "out_q" int8 / "out_d" float32 / "out_s" uint32 for the ops that write Q8 blocks, "k" / "v" (copies
+    of k_slots / v_slots after the launch, QKV), "launched" (kernel, threads, grid x, grid y, dynamic LDS bytes, cols, ldo, 0).  Raises BiogptError on a refusal."""
+    opn = CHAIN_OPS[op]
+    rt = -1 if op == "LNQ" else CHAIN_ROUTES[route]
+    cols, ldo = ((N + 15) & ~15) + 1, (0 if op == "LNQ" else ((M + 127) & ~127) + 16)
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    res = {}
+    q8_out = op in ("LNQ", "FC1_LN", "FC1_Q8")
+    if q8_out:
+        mq = 1024 if op == "LNQ" else M
+        res["out_q"], res["out_d"], res["out_s"] = np.zeros((cols, mq), np.int8), np.zeros((cols, mq // 32), np.float32), np.zeros((cols, mq // 32), np.uint32)
+    else:
+        res["out"] = np.zeros((cols, 1024 if op == "QKV" else ldo), np.float32)
+    n_slots = 0
+    if op == "QKV":
+        res["k"], res["v"] = np.array(k_slots, dtype=np.float32, order="C"), np.array(v_slots, dtype=np.float32, order="C")
+        n_slots = res["k"].shape[0]
+        assert res["k"].shape == res["v"].shape == (n_slots, 16, P, 64)
+    launched = np.zeros(8, np.int32)
+    o = lambda name: res[name].ctypes.data if name in res else None
+    rc = lib().biogpt_hip_chain_device(int(device), opn, rt, int(wtype), int(M), int(N), ptr(w_rows, np.uint8), ptr(x, np.float32), ptr(ln_w, np.float32),
+                                       ptr(ln_b, np.float32), int(q81), ptr(aq_q, np.int8), ptr(aq_d, np.float32), ptr(aq_s, np.uint32), ptr(bias, np.float32),
+                                       ptr(resid, np.float32), ptr(dev_state, np.int32), ptr(seq_states, np.int32), int(col_mode), int(P), n_slots, o("k"), o("v"),
+                                       o("out"), o("out_q"), o("out_d"), o("out_s"), launched.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    res["launched"] = launched
+    return res
 
 
 def write_synthetic(path, seed=0x42494F47, **hparams):
@@ -1418,6 +1467,10 @@ class BiogptModel:
         buf = (C.c_uint64 * 3072)()
         n = int(lib().biogpt_hip_fpipe_stamps(self._h, buf, 3072))
         return None if n != 3072 else np.frombuffer(buf, dtype=np.uint64).reshape(3, 32, 32).copy()
+
+    def mfma_launches(self):
+        """Launches of the many-column chain that went to the matrix-core kernels (biogpt_hip_mfma_launches)."""
+        return int(lib().biogpt_hip_mfma_launches(self._h))
 
     def chunk_launches(self):
         """Evals of 2 .. 8 tokens that went through the column-per-XCD launch (biogpt_hip_chunk_launches)."""

@@ -176,6 +176,13 @@ inline float gelu_tanh_f32(float x) {  // ggml_gelu_f32 [SURVEY A.5]
     return 0.5f * x * (1.0f + tanhf(SQRT_2_OVER_PI * x * (1.0f + GELU_COEF_A * x * x)));
 }
 
+// the fp16 GELU table, built the way ggml_init builds it [SURVEY A.5]: the loader's, and the probe's of single kernels (engine_probe.inc)
+std::vector<uint16_t> gelu_table_f16() {
+    std::vector<uint16_t> tg(65536);
+    for (uint32_t i = 0; i < 65536; i++) tg[i] = f32_to_f16(gelu_tanh_f32(f16_to_f32((uint16_t)i)));
+    return tg;
+}
+
 int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 int ilog2(int v) { int l = 0; while ((1 << l) < v) l++; return l; }
 
@@ -347,6 +354,7 @@ struct biogpt_hip_ctx {
     int xc_lds = 0;                        // 0 not tried, 1 the kernels' LDS attribute is set, -1 it could not be set (such evals keep the launch chain)
     int state_n_past = 0, state_chunk = 0; // what the last upload_state put into the device state
     int64_t xc_launches = 0;               // evals that went through the chunk launch (biogpt_hip_chunk_launches)
+    int64_t mfma_launches = 0;             // launches of the many-column chain that went to the matrix-core kernels (biogpt_hip_mfma_launches)
     int32_t gen_launch_tokens[16] = {0}; int gen_launches = 0;   // the last biogpt_hip_generate_greedy: tokens of each multi-token pipelined launch (biogpt_hip_generate_launches)
     int32_t prefix_stats[4] = {0, 0, 0, 0};   // of the last biogpt_hip_generate_*_prefix call that generated tokens: shared rows, prompt columns evaluated, path (0 in place, 1 copied), columns
     int xc_batch = 0;                      // a column generation call with 2 .. 8 columns holds the device's pipeline slot (choose_column_path): its decode steps run as column-per-XCD launches (streams mode)
@@ -527,40 +535,48 @@ bool try_launch_fast(const EngineOptions &o, const bgk::MatvecParams &p, hipStre
 
 // fast-chain launches with producer-quantized activations (attention -> out_proj, fc1 -> fc2; for
 // prefill chunks also lnq_kernel -> q/k/v and -> fc1), NC = 1 (decode) or 8 columns per workgroup
+// Which kernel a launch of the many-column linear chain is, and its geometry: what launch_chain and bg_mfma_launch report when asked.  The engine and the probe
+// of single kernels (biogpt_hip_chain_device, engine_probe.inc) launch through the same helpers, so the probe's launch is the engine's.
+using bgk::CK_VALU_1; using bgk::CK_VALU_8; using bgk::CK_MFMA_1; using bgk::CK_MFMA_2;      // (kernels.hip.h: mfma_tu.hip reports with the same enumerators)
+struct ChainLaunch { int32_t kernel, threads, grid_x, grid_y, lds; };
+static_assert(sizeof(ChainLaunch) == 5 * sizeof(int32_t), "crosses to mfma_tu.hip as five words");
+
 template <int WT, int PRO, int EPI, int K, int PF, int NC>
-hipError_t launch_fast_explicit(bgk::MatvecParams p, int steps, hipStream_t st) {
+hipError_t launch_fast_explicit(bgk::MatvecParams p, int steps, hipStream_t st, ChainLaunch *rep = nullptr) {
     constexpr int BPR = K / 32, LPR = BPR < 64 ? BPR : 64, RPS = 64 / LPR;
     p.rpw = RPS * steps;
     const int grid = (p.W.M + 4 * p.rpw - 1) / (4 * p.rpw);
     const int gy = (p.N + NC - 1) / NC;
-    hipLaunchKernelGGL((bgk::matvec_fast_kernel<WT, PRO, EPI, K, PF, NC>), dim3(grid, gy), dim3(256),
-                       bgk::matvec_fast_smem_bytes(K, p.rpw, NC, EPI == bgk::EPI_GELU_Q8), st, p);
+    const size_t sm = bgk::matvec_fast_smem_bytes(K, p.rpw, NC, EPI == bgk::EPI_GELU_Q8);
+    if (rep) *rep = ChainLaunch{NC == 1 ? CK_VALU_1 : CK_VALU_8, 256, grid, gy, (int32_t)sm};
+    hipLaunchKernelGGL((bgk::matvec_fast_kernel<WT, PRO, EPI, K, PF, NC>), dim3(grid, gy), dim3(256), sm, st, p);
     return hipGetLastError();
 }
 
 enum ChainOp { CHAIN_QKV_Q8, CHAIN_OPROJ, CHAIN_FC1, CHAIN_FC1_Q8, CHAIN_FC2, CHAIN_LMHEAD_Q8 };
 template <int WT, int NC>
-hipError_t launch_chain_nc(ChainOp op, const bgk::MatvecParams &p, hipStream_t st) {
+hipError_t launch_chain_nc(ChainOp op, const bgk::MatvecParams &p, hipStream_t st, ChainLaunch *rep) {
     switch (op) {
-        case CHAIN_QKV_Q8: return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_QKV, 1024, 1, NC>(p, 1, st);
-        case CHAIN_OPROJ: return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_RESID, 1024, 1, NC>(p, 1, st);
+        case CHAIN_QKV_Q8: return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_QKV, 1024, 1, NC>(p, 1, st, rep);
+        case CHAIN_OPROJ: return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_RESID, 1024, 1, NC>(p, 1, st, rep);
         case CHAIN_FC1:   // decode: LayerNorm fused; 32 rows / workgroup = one Q8 block of fc2's input
-            if constexpr (NC == 1) return launch_fast_explicit<WT, bgk::PRO_LN, bgk::EPI_GELU_Q8, 1024, 4, 1>(p, 4, st);
+            if constexpr (NC == 1) return launch_fast_explicit<WT, bgk::PRO_LN, bgk::EPI_GELU_Q8, 1024, 4, 1>(p, 4, st, rep);
             else return hipErrorInvalidValue;
-        case CHAIN_FC1_Q8: return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_GELU_Q8, 1024, 4, NC>(p, 4, st);
-        case CHAIN_FC2: return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_RESID, 4096, 1, NC>(p, 1, st);
+        case CHAIN_FC1_Q8: return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_GELU_Q8, 1024, 4, NC>(p, 4, st, rep);
+        case CHAIN_FC2: return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_RESID, 4096, 1, NC>(p, 1, st, rep);
         case CHAIN_LMHEAD_Q8:  // rows_per_wave * columns <= 64 finisher lanes: 4 row steps with 8 columns
-            if constexpr (NC == 8) return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_LOGITS, 1024, 4, 8>(p, 4, st);
+            if constexpr (NC == 8) return launch_fast_explicit<WT, bgk::PRO_Q8IN, bgk::EPI_LOGITS, 1024, 4, 8>(p, 4, st, rep);
             else return hipErrorInvalidValue;
     }
     return hipErrorInvalidValue;
 }
 // many columns (prompt passes, batched sequences): the same chain on the int8 matrix cores, reading the row-tiled
 // weight image (kernels_mfma.hip.h; the 25 kernels live in their own translation unit, mfma_tu.hip)
-extern "C" int bg_mfma_launch(int wt, int op, const void *params, size_t params_bytes, const void *img, size_t img_bytes, hipStream_t st);
+// report: null, or five words (a ChainLaunch) that the launch fills in
+extern "C" int bg_mfma_launch(int wt, int op, const void *params, size_t params_bytes, const void *img, size_t img_bytes, hipStream_t st, int32_t *report);
 extern "C" int bg_mfma_retile(int wt, const void *src, size_t src_bytes, uint8_t *dq, uint8_t *ds, hipStream_t st);
 template <int WT>
-hipError_t launch_chain_mfma(ChainOp op, const bgk::MatvecParams &p, const bgk::DevMatrix &img, hipStream_t st) {
+hipError_t launch_chain_mfma(ChainOp op, const bgk::MatvecParams &p, const bgk::DevMatrix &img, hipStream_t st, ChainLaunch *rep) {
     int site = -1;
     switch (op) {
         case CHAIN_QKV_Q8: site = 0; break;
@@ -570,26 +586,36 @@ hipError_t launch_chain_mfma(ChainOp op, const bgk::MatvecParams &p, const bgk::
         case CHAIN_LMHEAD_Q8: site = 4; break;
         default: return hipErrorInvalidValue;
     }
-    return (hipError_t)bg_mfma_launch(WT, site, &p, sizeof(p), &img, sizeof(img), st);
+    return (hipError_t)bg_mfma_launch(WT, site, &p, sizeof(p), &img, sizeof(img), st, reinterpret_cast<int32_t *>(rep));
 }
+// the 1-column form: one column of the context's own, at the sites that have one (q/k/v, fc1 after lnq_kernel and the all-rows lm_head are 8-column kernels at any N)
+inline bool chain_one_column(ChainOp op, int N, bool col_states) { return N == 1 && !col_states && op != CHAIN_LMHEAD_Q8 && op != CHAIN_QKV_Q8 && op != CHAIN_FC1_Q8; }
 template <int WT>
-hipError_t launch_chain_typed(ChainOp op, const bgk::MatvecParams &p, hipStream_t st, const bgk::DevMatrix *img) {
+hipError_t launch_chain_typed(ChainOp op, const bgk::MatvecParams &p, hipStream_t st, const bgk::DevMatrix *img, ChainLaunch *rep) {
     if constexpr (bgk::TypeInfo<WT>::quant) {
-        if (img != nullptr && op != CHAIN_FC1) return launch_chain_mfma<WT>(op, p, *img, st);
-        if (p.N == 1 && p.seq == nullptr && op != CHAIN_LMHEAD_Q8 && op != CHAIN_QKV_Q8 && op != CHAIN_FC1_Q8) return launch_chain_nc<WT, 1>(op, p, st);
-        return launch_chain_nc<WT, 8>(op, p, st);
+        if (img != nullptr && op != CHAIN_FC1) return launch_chain_mfma<WT>(op, p, *img, st, rep);
+        if (chain_one_column(op, p.N, p.seq != nullptr)) return launch_chain_nc<WT, 1>(op, p, st, rep);
+        return launch_chain_nc<WT, 8>(op, p, st, rep);
     }
     return hipErrorInvalidValue;
 }
-hipError_t launch_chain(ChainOp op, const bgk::MatvecParams &p, hipStream_t st, const bgk::DevMatrix *img = nullptr) {
+// rep: null, or what was launched
+hipError_t launch_chain(ChainOp op, const bgk::MatvecParams &p, hipStream_t st, const bgk::DevMatrix *img = nullptr, ChainLaunch *rep = nullptr) {
     switch (p.W.type) {
-        case T_Q4_0: return launch_chain_typed<bgk::W_Q4_0>(op, p, st, img);
-        case T_Q4_1: return launch_chain_typed<bgk::W_Q4_1>(op, p, st, img);
-        case T_Q5_0: return launch_chain_typed<bgk::W_Q5_0>(op, p, st, img);
-        case T_Q5_1: return launch_chain_typed<bgk::W_Q5_1>(op, p, st, img);
-        case T_Q8_0: return launch_chain_typed<bgk::W_Q8_0>(op, p, st, img);
+        case T_Q4_0: return launch_chain_typed<bgk::W_Q4_0>(op, p, st, img, rep);
+        case T_Q4_1: return launch_chain_typed<bgk::W_Q4_1>(op, p, st, img, rep);
+        case T_Q5_0: return launch_chain_typed<bgk::W_Q5_0>(op, p, st, img, rep);
+        case T_Q5_1: return launch_chain_typed<bgk::W_Q5_1>(op, p, st, img, rep);
+        case T_Q8_0: return launch_chain_typed<bgk::W_Q8_0>(op, p, st, img, rep);
         default: return hipErrorInvalidValue;
     }
+}
+// LayerNorm + Q8 of N columns of 1024 values (lnq_kernel): a helper over pointers, for the engine's sites (below) and the probe
+inline hipError_t launch_lnq(const float *x, int N, const float *ln_w, const float *ln_b, int q81, int8_t *oq_q, float *oq_d, uint32_t *oq_s, hipStream_t st) {
+    const double inv_k = 1.0 / 1024.0;
+    if (q81) hipLaunchKernelGGL((bgk::lnq_kernel<1024, true>), dim3(N), dim3(256), 0, st, x, 1024, ln_w, ln_b, 1e-5f, inv_k, oq_q, oq_d, oq_s);
+    else hipLaunchKernelGGL((bgk::lnq_kernel<1024, false>), dim3(N), dim3(256), 0, st, x, 1024, ln_w, ln_b, 1e-5f, inv_k, oq_q, oq_d, oq_s);
+    return hipGetLastError();
 }
 hipError_t launch_lnq(const biogpt_hip_ctx *c, const float *x, int N, size_t ln_w, size_t ln_b, int q81, hipStream_t st);
 
@@ -660,10 +686,7 @@ bgk::MatvecParams mv_base(const biogpt_hip_ctx *c, const MatSlot &m, const MvSha
 }
 
 hipError_t launch_lnq(const biogpt_hip_ctx *c, const float *x, int N, size_t ln_w, size_t ln_b, int q81, hipStream_t st) {
-    const double inv_k = 1.0 / 1024.0;
-    if (q81) hipLaunchKernelGGL((bgk::lnq_kernel<1024, true>), dim3(N), dim3(256), 0, st, x, 1024, dev_vec(c, ln_w), dev_vec(c, ln_b), 1e-5f, inv_k, c->aq_q[2], c->aq_d[2], c->aq_s[2]);
-    else hipLaunchKernelGGL((bgk::lnq_kernel<1024, false>), dim3(N), dim3(256), 0, st, x, 1024, dev_vec(c, ln_w), dev_vec(c, ln_b), 1e-5f, inv_k, c->aq_q[2], c->aq_d[2], c->aq_s[2]);
-    return hipGetLastError();
+    return launch_lnq(x, N, dev_vec(c, ln_w), dev_vec(c, ln_b), q81, c->aq_q[2], c->aq_d[2], c->aq_s[2], st);
 }
 
 // The fixed launch sequence for N tokens at the device-resident n_past (biogpt_graph's op order).
@@ -679,15 +702,22 @@ bgk::DevMatrix tile_matrix(const biogpt_hip_ctx *c, const MatSlot &m) {
     d.type = m.type; d.M = (int32_t)m.M; d.K = (int32_t)m.K;
     return d;
 }
+// The image is addressed by whole 16-row tiles (retile_kernel, matmul_mfma_kernel): a matrix has one only when its rows are whole tiles.  Every layer matrix of the
+// chain's shapes is; an lm_head of a vocabulary that is no multiple of 16 is not, and stays on the 8-column kernel (PassLaunch::tile).
+inline bool tile_image_ok(const MatSlot &m) { return is_quantized(m.type) && m.M % 16 == 0; }
+// where a matrix's image lies: the 32-byte expanded blocks, then the f32 scales ({d, m} for Q4_1 / Q5_1), each part starting on 256 bytes; off: the running offset
+inline void tile_image_place(int32_t type, int64_t M, int64_t K, size_t &off, size_t &xq, size_t &xs) {
+    const size_t nblk = (size_t)M * (size_t)(K / QK);
+    const bool q81 = type == T_Q4_1 || type == T_Q5_1;
+    xq = off; off = (off + nblk * 32 + 255) & ~(size_t)255;
+    xs = off; off = (off + nblk * (q81 ? 8 : 4) + 255) & ~(size_t)255;
+}
 bool ensure_tile_images(biogpt_hip_ctx *c) {
     if (c->tile_img || c->tile_img_failed) return true;
     size_t off = 0;
     auto place = [&](MatSlot &m) {
-        if (!is_quantized(m.type)) return;
-        const size_t nblk = (size_t)m.M * (size_t)(m.K / QK);
-        const bool q81 = m.type == T_Q4_1 || m.type == T_Q5_1;
-        m.xq = off; off = (off + nblk * 32 + 255) & ~(size_t)255;
-        m.xs = off; off = (off + nblk * (q81 ? 8 : 4) + 255) & ~(size_t)255;
+        if (!tile_image_ok(m)) return;
+        tile_image_place(m.type, m.M, m.K, off, m.xq, m.xs);
     };
     for (auto &L : c->plan.layers) { place(L.qkv); place(L.o); place(L.fc1); place(L.fc2); }
     place(c->plan.lm_head);
@@ -700,7 +730,7 @@ bool ensure_tile_images(biogpt_hip_ctx *c) {
     }
     bool retile_ok = true;
     auto one = [&](const MatSlot &m) {
-        if (!is_quantized(m.type)) return;
+        if (!tile_image_ok(m)) return;
         const bgk::DevMatrix src = dev_matrix(c, m);
         if (bg_mfma_retile(m.type, &src, sizeof(src), c->tile_img + m.xq, c->tile_img + m.xs, c->stream) != (int)hipSuccess) retile_ok = false;
     };
@@ -1154,7 +1184,15 @@ struct PassLaunch {
     int64_t seq_stride;
     float *kroot, *vroot;
     bgk::DevMatrix img;
-    const bgk::DevMatrix *tile(const MatSlot &m) { if (!mfma) return nullptr; img = tile_matrix(c, m); return &img; }
+    // a matrix whose rows are no whole 16-row tiles (an lm_head of a vocabulary that is no multiple of 16) has no image: it stays on the 8-column kernel
+    const bgk::DevMatrix *tile(const MatSlot &m) { if (!mfma || !tile_image_ok(m)) return nullptr; img = tile_matrix(c, m); return &img; }
+    // one launch of the chain; counts the ones that went to the matrix cores
+    hipError_t chain_launch(ChainOp op, const bgk::MatvecParams &p, const bgk::DevMatrix *image = nullptr) {
+        ChainLaunch rep{};
+        const hipError_t e = launch_chain(op, p, st, image, &rep);
+        if (e == hipSuccess && rep.kernel >= CK_MFMA_1) c->mfma_launches++;
+        return e;
+    }
 };
 
 // ---- the stand-alone attention launches ---------------------------------------------------------------------------------------------------
@@ -1309,7 +1347,7 @@ bool enqueue_layer(PassLaunch &k, int l) {
         if (k.pchain) {
             HIP_TRY(false, launch_lnq(c, c->x, N, L.ln0_w, L.ln0_b, k.q81, st));
             p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
-            HIP_TRY(false, launch_chain(CHAIN_QKV_Q8, p, st, k.tile(L.qkv)));
+            HIP_TRY(false, k.chain_launch(CHAIN_QKV_Q8, p, k.tile(L.qkv)));
         } else {
             HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_QKV>(c->opt, p, s, st)));
         }
@@ -1323,7 +1361,7 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.resid = c->x; p.ldr = D; p.out = c->x1; p.ldo = D;
         if (k.chain) {
             p.aq_q = c->aq_q[0]; p.aq_d = c->aq_d[0]; p.aq_s = c->aq_s[0];
-            HIP_TRY(false, launch_chain(CHAIN_OPROJ, p, st, k.tile(L.o)));
+            HIP_TRY(false, k.chain_launch(CHAIN_OPROJ, p, k.tile(L.o)));
         } else {
             HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
         }
@@ -1339,10 +1377,10 @@ bool enqueue_layer(PassLaunch &k, int l) {
             HIP_TRY(false, launch_lnq(c, c->x1, N, L.ln1_w, L.ln1_b, k.q81, st));
             p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
             p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
-            HIP_TRY(false, launch_chain(CHAIN_FC1_Q8, p, st, k.tile(L.fc1)));
+            HIP_TRY(false, k.chain_launch(CHAIN_FC1_Q8, p, k.tile(L.fc1)));
         } else if (k.chain) {
             p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
-            HIP_TRY(false, launch_chain(CHAIN_FC1, p, st));
+            HIP_TRY(false, k.chain_launch(CHAIN_FC1, p));
         } else {
             HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_GELU>(c->opt, p, s, st)));
         }
@@ -1355,7 +1393,7 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.resid = c->x1; p.ldr = D; p.out = c->x; p.ldo = D;
         if (k.chain) {
             p.aq_q = c->aq_q[1]; p.aq_d = c->aq_d[1]; p.aq_s = c->aq_s[1];
-            HIP_TRY(false, launch_chain(CHAIN_FC2, p, st, k.tile(L.fc2)));
+            HIP_TRY(false, k.chain_launch(CHAIN_FC2, p, k.tile(L.fc2)));
         } else {
             HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
         }
@@ -1391,7 +1429,7 @@ bool enqueue_final(PassLaunch &k) {
         HIP_TRY(false, launch_lnq(c, c->x + (size_t)head_from * D, n_rows, c->plan.ln_w, c->plan.ln_b, k.q81, st));
         p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
         p.N = n_rows; p.out = c->logits_all; p.ldo = V;
-        HIP_TRY(false, launch_chain(CHAIN_LMHEAD_Q8, p, st, (head_from > 0 && n_rows < MFMA_MIN_PASS_COLS) ? nullptr : k.tile(c->plan.lm_head)));
+        HIP_TRY(false, k.chain_launch(CHAIN_LMHEAD_Q8, p, (head_from > 0 && n_rows < MFMA_MIN_PASS_COLS) ? nullptr : k.tile(c->plan.lm_head)));
         return true;
     }
     // final LayerNorm + lm_head on the generic kernel; only the rows that are returned (F8)
@@ -1627,12 +1665,9 @@ bool upload_weights(biogpt_hip_ctx *c, const ModelFile &mf) {
     if (!put_matrix("output_projection.weight", pl.lm_head, 0, hp.n_vocab, D)) return false;
 
     // fp16 tables, built the way ggml_init builds them [SURVEY A.5]
-    std::vector<uint16_t> tg(65536), te(65536);
-    for (uint32_t i = 0; i < 65536; i++) {
-        const float f = f16_to_f32((uint16_t)i);
-        tg[i] = f32_to_f16(gelu_tanh_f32(f));
-        te[i] = f32_to_f16(expf(f));
-    }
+    const std::vector<uint16_t> tg = gelu_table_f16();
+    std::vector<uint16_t> te(65536);
+    for (uint32_t i = 0; i < 65536; i++) te[i] = f32_to_f16(expf(f16_to_f32((uint16_t)i)));
     HIP_TRY(false, hipMemcpy(c->arena + pl.gelu_tab, tg.data(), 65536 * 2, hipMemcpyHostToDevice));
     HIP_TRY(false, hipMemcpy(c->arena + pl.exp_tab, te.data(), 65536 * 2, hipMemcpyHostToDevice));
     return true;
@@ -2327,6 +2362,7 @@ int biogpt_hip_eval_inplace(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t 
     return rc;
 }
 int64_t biogpt_hip_chunk_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->xc_launches : -1; }
+int64_t biogpt_hip_mfma_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->mfma_launches : -1; }
 int biogpt_hip_fpipe_stamps(biogpt_hip_ctx *ctx, uint64_t *out, int n) {
     if (!ctx || !out || n < 0 || ctx->fp_state != 1 || !ctx->opt.fpipe_stamps) return -1;
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;

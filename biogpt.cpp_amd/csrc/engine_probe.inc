@@ -931,3 +931,183 @@ int biogpt_hip_lookup_accept_device(int device, const float *rows, int32_t n_seq
     live_out[0] = hb.ctl->n_live; live_out[1] = hb.ctl->max_pos;
     return 0;
 }
+
+// One stand-alone launch of a linear stage of the many-column chain over caller-supplied inputs, through launch_lnq / launch_chain -- the helpers of enqueue_layer and
+// enqueue_final -- so the probe's launch is the engine's.  op: 0 LNQ (lnq_kernel), 1 QKV, 2 OPROJ, 3 FC1_LN (the 1-column form with LayerNorm fused), 4 FC1_Q8, 5 FC2,
+// 6 LMHEAD.  route: the ChainKernel the caller expects (0 the 1-column VALU kernel, 1 the 8-column one, 2 / 3 matmul_mfma_kernel with one / two row tiles per wave); a
+// route the engine would not take for (op, type, M, N, column states) is refused before anything is allocated, as is a shape that is not the site's own.  Only QKV carries
+// column states, so only there can the probe tell a pass (matrix cores from 64 columns) from a decode step of many sequences (from 48); for the other ops a matrix-core
+// route is accepted from 48 columns on -- what the engine launches in a decode step, though never in a pass of 48 .. 63 columns.  w_rows: M rows
+// in the file's block format, repacked by repack_rows; for a matrix-core route the row-tiled image is laid out by tile_image_place and built by bg_mfma_retile.
+// Outputs come back WHOLE as allocated and preset to 0xff: cols = N rounded up to 16, plus one guard column; ldo = M rounded up to 128, plus 16 guard rows.
+//   LNQ            x [N][1024], ln_w, ln_b; q81 picks the Q8_1 form              -> out_q [cols][1024], out_d / out_s [cols][32]
+//   QKV            aq_*, bias [3072]; dev_state, or seq_states [N][8] + col_mode -> out [cols][1024] (q), k_slots / v_slots [n_slots][16][P][64] updated in place
+//   OPROJ, FC2     aq_*, bias [1024], resid [N][1024]                            -> out [cols][ldo]
+//   FC1_LN         x [1][1024], ln_w, ln_b, bias [4096]                          -> out_q [cols][4096], out_d / out_s [cols][128]
+//   FC1_Q8         aq_*, bias [4096]                                             -> the same
+//   LMHEAD         aq_*                                                          -> out [cols][ldo]
+// aq_q [N][K] int8, aq_d [N][K / 32] f32, aq_s [N][K / 32] words, as a producer leaves them (Q8_0: d rounded through f16, the integer block sum; Q8_1: d, the bits of d * sum).
+// launched [8]: kernel, threads, grid x, grid y, dynamic LDS bytes, cols, ldo, 0.
+enum ChainProbeOp : int { CP_LNQ = 0, CP_QKV = 1, CP_OPROJ = 2, CP_FC1_LN = 3, CP_FC1_Q8 = 4, CP_FC2 = 5, CP_LMHEAD = 6 };
+extern "C" int bg_mfma_tiles(int wt, int op, int M, int N);
+int biogpt_hip_chain_device(int device, int32_t op, int32_t route, int32_t wtype, int32_t M, int32_t N, const void *w_rows, const float *x, const float *ln_w,
+                            const float *ln_b, int32_t q81, const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid,
+                            const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t P, int32_t n_slots, float *k_slots, float *v_slots,
+                            float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched) {
+    clear_error();
+    static_assert(sizeof(bgk::SeqState) == 32 && sizeof(bgk::DevState) == 16, "eight words per column state, four of context state");
+    if (op < CP_LNQ || op > CP_LMHEAD) BG_FAIL(-1, "op %d is no stage of the chain", op);
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    const bool lnq = op == CP_LNQ, ln_in = lnq || op == CP_FC1_LN, q8_out = lnq || op == CP_FC1_LN || op == CP_FC1_Q8, f32_out = !q8_out;
+    const int K = op == CP_FC2 ? 4096 : 1024;
+    // ---- the site's own shape ----
+    if (lnq) {
+        if (q81 != 0 && q81 != 1) BG_FAIL(-1, "q81 must be 0 (Q8_0 blocks) or 1 (Q8_1)");
+        if (route != -1) BG_FAIL(-1, "LNQ has one kernel: route must be -1");
+    } else {
+        if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+        if (!w_rows) BG_FAIL(-1, "w_rows is NULL");
+        const int want = op == CP_QKV ? 3072 : (op == CP_FC1_LN || op == CP_FC1_Q8) ? 4096 : 1024;
+        if (op != CP_LMHEAD && M != want) BG_FAIL(-1, "M = %d is not the site's own shape (%d x %d)", M, want, K);
+        if (op == CP_LMHEAD && (M < 1 || M > (1 << 20))) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+        q81 = (wtype == T_Q4_1 || wtype == T_Q5_1) ? 1 : 0;
+    }
+    if (ln_in ? (!x || !ln_w || !ln_b) : (!aq_q || !aq_d || !aq_s)) BG_FAIL(-1, "%s", ln_in ? "x, ln_w or ln_b is NULL" : "aq_q, aq_d or aq_s is NULL");
+    if (!lnq && op != CP_LMHEAD && !bias) BG_FAIL(-1, "bias is NULL");
+    if ((op == CP_OPROJ || op == CP_FC2) && !resid) BG_FAIL(-1, "resid is NULL");
+    if (f32_out ? !out : (!out_q || !out_d || !out_s)) BG_FAIL(-1, "%s", f32_out ? "out is NULL" : "out_q, out_d or out_s is NULL");
+    const bool batch = seq_states != nullptr;
+    if (op == CP_QKV) {
+        if ((dev_state != nullptr) == batch) BG_FAIL(-1, "exactly one of dev_state and seq_states names the column states");
+        if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
+        if (!batch && col_mode) BG_FAIL(-1, "col_mode 1 needs seq_states");
+        if (!k_slots || !v_slots) BG_FAIL(-1, "k_slots or v_slots is NULL");
+        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+        if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
+        if (!batch && n_slots != 1) BG_FAIL(-1, "the context's own columns have one slot");
+    } else if (dev_state || batch) BG_FAIL(-1, "only QKV reads column states");
+    // ---- the route the engine takes ----
+    const ChainOp cop = op == CP_QKV ? CHAIN_QKV_Q8 : op == CP_OPROJ ? CHAIN_OPROJ : op == CP_FC1_LN ? CHAIN_FC1 : op == CP_FC1_Q8 ? CHAIN_FC1_Q8 : op == CP_FC2 ? CHAIN_FC2 : CHAIN_LMHEAD_Q8;
+    const bool mfma = route == CK_MFMA_1 || route == CK_MFMA_2;
+    if (!lnq) {
+        if (route < CK_VALU_1 || route > CK_MFMA_2) BG_FAIL(-1, "route %d is no kernel of the chain", route);
+        if (op == CP_FC1_LN) {
+            if (route != CK_VALU_1 || N != 1) BG_FAIL(-1, "FC1_LN is the 1-column kernel alone: one column, route 0");
+        } else if (mfma) {
+            const int min_cols = (op == CP_QKV && !(batch && col_mode == 0)) ? MFMA_MIN_PASS_COLS : MFMA_MIN_DECODE_COLS;
+            if (N < min_cols) BG_FAIL(-1, "%d columns: the matrix-core kernels run from %d columns on", N, min_cols);
+            if (M % 16 != 0) BG_FAIL(-1, "M = %d is no whole number of 16-row tiles: such a matrix has no image and stays on the 8-column kernel", M);
+            static const int site_of[7] = {-1, 0, 1, -1, 2, 3, 4};
+            const int tiles = bg_mfma_tiles(wtype, site_of[op], M, N);
+            if (tiles != (route == CK_MFMA_2 ? 2 : 1)) BG_FAIL(-1, "the launch takes %d row tile(s) per wave for this type, M = %d and N = %d", tiles, M, N);
+        } else {
+            const bool one = chain_one_column(cop, N, batch);
+            if (one != (route == CK_VALU_1)) BG_FAIL(-1, "%s", one ? "one column of the context's own takes the 1-column kernel here" : "the 1-column kernel serves N = 1 without column states, at out_proj, fc1 (LayerNorm fused) and fc2 only");
+        }
+    }
+    // ---- every column's cache row inside its slot, no two columns on one row ----
+    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
+    if (op == CP_QKV) {
+        std::set<std::pair<int, int>> seen;
+        for (int i = 0; i < N; i++) {
+            const int pos = batch ? hs[i].n_past : dev_state[0] + i, slot = batch ? (col_mode ? hs[i].seq_id : i) : 0;
+            if (pos < 0 || pos >= P) BG_FAIL(-1, "column %d: position %d outside [0, P)", i, pos);
+            if (slot < 0 || slot >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, slot);
+            if (!seen.insert({slot, pos}).second) BG_FAIL(-1, "column %d: a second column writes slot %d, position %d", i, slot, pos);
+        }
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    const int cols = ((N + 15) & ~15) + 1, ldo = lnq ? 0 : ((M + 127) & ~127) + 16, MQ = lnq ? 1024 : M;      // MQ: Q8 values per output column
+    const size_t bpr = (size_t)K / QK, nblk = lnq ? 0 : (size_t)M * bpr;
+    const size_t qs_b = nblk * (wtype == T_Q8_0 ? 32 : 16), sc_b = nblk * (q81 ? 4 : 2), qh_b = (wtype == T_Q5_0 || wtype == T_Q5_1) ? nblk * 4 : 0;
+    const size_t slot_f = (size_t)16 * P * 64, kv_b = op == CP_QKV ? slot_f * 4 * (size_t)n_slots : 0;
+    const size_t out_b = f32_out ? (size_t)cols * (op == CP_QKV ? 1024 : ldo) * 4 : 0, oq_b = q8_out ? (size_t)cols * MQ : 0, od_b = q8_out ? (size_t)cols * (MQ / 32) * 4 : 0;
+    size_t img_b = 0, xq = 0, xs = 0;
+    if (mfma) tile_image_place(wtype, M, K, img_b, xq, xs);
+    ByteLayout l;
+    const size_t o_qs = l.part(qs_b), o_sc = l.part(sc_b), o_qh = l.part(qh_b), o_img = l.part(img_b), o_x = l.part(ln_in ? (size_t)N * 1024 * 4 : 0), o_lw = l.part(ln_in ? 4096 : 0),
+                 o_lb = l.part(ln_in ? 4096 : 0), o_aq = l.part(ln_in ? 0 : (size_t)N * K), o_ad = l.part(ln_in ? 0 : (size_t)N * bpr * 4), o_as = l.part(ln_in ? 0 : (size_t)N * bpr * 4),
+                 o_bias = l.part(bias ? (size_t)MQ * 4 : 0), o_res = l.part(resid ? (size_t)N * M * 4 : 0), o_ds = l.part(sizeof(bgk::DevState)),
+                 o_st = l.part(batch ? sizeof(bgk::SeqState) * (size_t)N : 0), o_tab = l.part(65536 * 2), o_k = l.part(kv_b), o_v = l.part(kv_b),
+                 o_out = l.part(out_b), o_oq = l.part(oq_b), o_od = l.part(od_b), o_os = l.part(od_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));      // the outputs with their guard columns and rows
+    if (!lnq) {
+        std::vector<uint8_t> qs(qs_b), sc(sc_b), qh(qh_b);
+        repack_rows(wtype, static_cast<const uint8_t *>(w_rows), M, K, qs.data(), sc.data(), qh.data());
+        HIP_TRY(-2, hipMemcpy(d.p + o_qs, qs.data(), qs_b, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_sc, sc.data(), sc_b, hipMemcpyHostToDevice));
+        if (qh_b) HIP_TRY(-2, hipMemcpy(d.p + o_qh, qh.data(), qh_b, hipMemcpyHostToDevice));
+    }
+    if (ln_in) {
+        HIP_TRY(-2, hipMemcpy(d.p + o_x, x, (size_t)N * 1024 * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_lw, ln_w, 4096, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_lb, ln_b, 4096, hipMemcpyHostToDevice));
+    } else {
+        HIP_TRY(-2, hipMemcpy(d.p + o_aq, aq_q, (size_t)N * K, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_ad, aq_d, (size_t)N * bpr * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_as, aq_s, (size_t)N * bpr * 4, hipMemcpyHostToDevice));
+    }
+    if (bias && !lnq) HIP_TRY(-2, hipMemcpy(d.p + o_bias, bias, (size_t)MQ * 4, hipMemcpyHostToDevice));
+    if (resid && f32_out && op != CP_QKV) HIP_TRY(-2, hipMemcpy(d.p + o_res, resid, (size_t)N * M * 4, hipMemcpyHostToDevice));
+    const int32_t no_state[4] = {0, 0, 0, 0};
+    HIP_TRY(-2, hipMemcpy(d.p + o_ds, (op == CP_QKV && !batch) ? dev_state : no_state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
+    if (batch) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
+    if (op == CP_QKV) {
+        HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
+    }
+    const std::vector<uint16_t> tg = gelu_table_f16();
+    HIP_TRY(-2, hipMemcpy(d.p + o_tab, tg.data(), 65536 * 2, hipMemcpyHostToDevice));
+    ChainLaunch g{-1, 256, N, 1, 0};
+    if (lnq) {
+        HIP_TRY(-2, launch_lnq(d.at<const float>(o_x), N, d.at<const float>(o_lw), d.at<const float>(o_lb), q81, d.at<int8_t>(o_oq), d.at<float>(o_od), d.at<uint32_t>(o_os), 0));
+    } else {
+        bgk::MatvecParams p{};
+        p.W.qs = d.p + o_qs; p.W.sc = d.p + o_sc; p.W.qh = qh_b ? d.at<const uint32_t>(o_qh) : nullptr;
+        p.W.type = wtype; p.W.M = M; p.W.K = K;
+        p.eps = 1e-5f; p.D = 1024; p.dk = 64; p.dk_log2 = 6; p.P = P;
+        p.st = d.at<const bgk::DevState>(o_ds);
+        p.gelu_tab = d.at<const uint16_t>(o_tab);
+        p.inv_k = 1.0 / (double)K; p.k_pow2 = 1;
+        p.N = N;
+        if (ln_in) { p.x = d.at<const float>(o_x); p.ldx = 1024; p.ln_w = d.at<const float>(o_lw); p.ln_b = d.at<const float>(o_lb); }
+        else { p.aq_q = d.at<const int8_t>(o_aq); p.aq_d = d.at<const float>(o_ad); p.aq_s = d.at<const uint32_t>(o_as); }
+        if (bias) p.bias = d.at<const float>(o_bias);
+        if (op == CP_QKV) {
+            p.q_out = d.at<float>(o_out); p.kcache = d.at<float>(o_k); p.vcache = d.at<float>(o_v);
+            p.q_scale = 1.0f / sqrtf(64.0f);
+            if (batch) { p.seq = d.at<const bgk::SeqState>(o_st); p.col_mode = col_mode; p.kv_seq_stride = (int64_t)slot_f; }
+        } else if (f32_out) {
+            p.out = d.at<float>(o_out); p.ldo = ldo;
+            if (op != CP_LMHEAD) { p.resid = d.at<const float>(o_res); p.ldr = M; }
+        } else {
+            p.oq_q = d.at<int8_t>(o_oq); p.oq_d = d.at<float>(o_od); p.oq_s = d.at<uint32_t>(o_os);
+        }
+        bgk::DevMatrix img{};
+        if (mfma) {
+            img.qs = d.p + o_img + xq; img.sc = d.p + o_img + xs; img.qh = nullptr; img.type = wtype; img.M = M; img.K = K;
+            HIP_TRY(-2, (hipError_t)bg_mfma_retile(wtype, &p.W, sizeof(p.W), d.p + o_img + xq, d.p + o_img + xs, 0));
+        }
+        HIP_TRY(-2, launch_chain(cop, p, 0, mfma ? &img : nullptr, &g));
+        if (g.kernel != route) BG_FAIL(-2, "internal: the launch took kernel %d, not route %d", g.kernel, route);
+    }
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    if (launched) {
+        const int32_t rep[8] = {g.kernel, g.threads, g.grid_x, g.grid_y, g.lds, cols, ldo, 0};
+        std::memcpy(launched, rep, sizeof(rep));
+    }
+    if (f32_out) HIP_TRY(-2, hipMemcpy(out, d.p + o_out, out_b, hipMemcpyDeviceToHost));
+    if (q8_out) {
+        HIP_TRY(-2, hipMemcpy(out_q, d.p + o_oq, oq_b, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(out_d, d.p + o_od, od_b, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(out_s, d.p + o_os, od_b, hipMemcpyDeviceToHost));
+    }
+    if (op == CP_QKV) {
+        HIP_TRY(-2, hipMemcpy(k_slots, d.p + o_k, kv_b, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(v_slots, d.p + o_v, kv_b, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}

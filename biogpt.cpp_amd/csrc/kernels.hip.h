@@ -43,6 +43,9 @@ constexpr int QK = 32;
 enum WType : int { W_F32 = 0, W_F16 = 1, W_Q4_0 = 2, W_Q4_1 = 3, W_Q5_0 = 6, W_Q5_1 = 7, W_Q8_0 = 8 };
 enum Prologue : int { PRO_PLAIN = 0, PRO_LN = 1, PRO_Q8IN = 2 };  // Q8IN: activation already quantized by the producer kernel
 enum Epilogue : int { EPI_QKV = 0, EPI_RESID = 1, EPI_GELU = 2, EPI_LOGITS = 3, EPI_GELU_Q8 = 4 };  // GELU_Q8: fc1 writes its output as Q8 blocks
+// which kernel a launch of the many-column linear chain is, as the launch helpers of engine.hip and mfma_tu.hip report it (the one definition both units read):
+// matvec_fast_kernel<.., NC = 1> / <.., 8>; matmul_mfma_kernel<.., J = 1> / <.., 2>
+enum ChainKernel : int { CK_VALU_1 = 0, CK_VALU_8 = 1, CK_MFMA_1 = 2, CK_MFMA_2 = 3 };
 
 // Per-context mutable device state: the decode position and the token ring the kernels read
 // their inputs from (so a captured graph can advance itself without host involvement).

@@ -25,11 +25,23 @@ constexpr int LP_THREADS = 256;   // 4 waves per column; 42384 logits = 41 float
 __device__ __forceinline__ void lp_row_sum(const float *row, int n_vocab, float m, double &S) {
     __shared__ double s_sum[LP_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // sum of exp(l - m): head, then the quads, then the tail; each quad as (x + y) + (z + w)
+    // sum of exp(l - m): the quads (elements 4 q .. 4 q + 3, quad q to thread q % LP_THREADS, ascending), then the tail; each quad as (x + y) + (z + w).  Which
+    // lane adds which element decides the sum's last bits, and it must follow from the element's INDEX alone: the rows of a pass whose vocabulary is no multiple
+    // of 4 lie on all four 16-byte alignments, and score_batch owes score's bits whichever row of a pass a token is.  row_scan walks from the first 16-byte
+    // boundary on, so a row that does not lie on one is walked here, by 4-byte loads, in the order row_scan gives a row that does.
     float s = 0.0f;
-    row_scan<LP_THREADS>(
-        row, n_vocab, [&](float4 e, int) { s += (expf(e.x - m) + expf(e.y - m)) + (expf(e.z - m) + expf(e.w - m)); },
-        [&](float v, int) { s += expf(v - m); });
+    if ((((uint32_t)(uintptr_t)row) & 15u) == 0u) {
+        row_scan<LP_THREADS>(
+            row, n_vocab, [&](float4 e, int) { s += (expf(e.x - m) + expf(e.y - m)) + (expf(e.z - m) + expf(e.w - m)); },
+            [&](float v, int) { s += expf(v - m); });
+    } else {
+        const int nvec = n_vocab >> 2;
+        for (int i = tid; i < nvec; i += LP_THREADS) {
+            const float *e = row + 4 * i;
+            s += (expf(e[0] - m) + expf(e[1] - m)) + (expf(e[2] - m) + expf(e[3] - m));
+        }
+        if (4 * nvec + tid < n_vocab) s += expf(row[4 * nvec + tid] - m);
+    }
     const double ws = wave_sum_f64((double)s);
     if (lane == 0) s_sum[wv] = ws;
     __syncthreads();

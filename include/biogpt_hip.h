@@ -163,6 +163,10 @@ int biogpt_hip_resident_stats(const biogpt_hip_ctx *ctx, int64_t *out4);
  * XCD, its own K / V cache: no exchange between XCDs) while contexts stay within 256 keys.  Returns how many such launches this context has enqueued or captured (evals;
  * batched generation: one per captured context bucket + the first step) (-1: null context). */
 int64_t biogpt_hip_chunk_launches(const biogpt_hip_ctx *ctx);
+/* Launches of the many-column chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head) that went to the matrix-core kernels, counted as they are enqueued or
+ * captured; -1: ctx is NULL.  A pass below the column threshold, a context without the row-tiled image and an lm_head whose rows are no multiple of 16 stay on
+ * the 8-column kernels and do not count. */
+int64_t biogpt_hip_mfma_launches(const biogpt_hip_ctx *ctx);
 /* F32 / F16 files: single-token steps this context has enqueued (or captured into a replayed step) as ONE persistent launch for all layers (csrc/kernels_fpipe.hip.h);
  * -1: that launch is not available to this context (shape, device, BIOGPT_HIP_FPIPE=0, or abandoned after a failed launch) -- five launches per layer then */
 int64_t biogpt_hip_fpipe_launches(const biogpt_hip_ctx *ctx);
@@ -387,6 +391,22 @@ int biogpt_hip_trie_rows_bench(int device, biogpt_hip_trie *trie, int32_t mode, 
 int biogpt_hip_attn_device(int device, int32_t route, int32_t H, int32_t dk, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q,
                            const float *k_slots, const float *v_slots, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t q8, float *out,
                            int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched);
+/* One stand-alone launch of a linear stage of the many-column chain over caller-supplied inputs, through the launch code of the engine's own passes.  op: 0 LNQ
+ * (LayerNorm + Q8 of N rows of 1024; q81 picks the Q8_1 form; route -1), 1 QKV, 2 OPROJ, 3 FC1_LN (one column, LayerNorm fused), 4 FC1_Q8, 5 FC2, 6 LMHEAD.  route
+ * names the kernel the caller expects: 0 the 1-column VALU kernel, 1 the 8-column one, 2 / 3 the matrix-core kernel with one / two row tiles per wave.  A route the
+ * engine would not take for (op, type, M, N, column states), a shape that is not the site's own (q/k/v 3072 x 1024, out_proj 1024 x 1024, fc1 4096 x 1024, fc2
+ * 1024 x 4096; only lm_head's M is free) and two columns that write one (slot, position) return -1 before anything is allocated.  w_rows: M rows in the file's
+ * block format (wtype 2, 3, 6, 7, 8).  (Only op 1 carries column states: there routes 2 / 3 need 64 columns for a pass and 48 for a decode step, col_mode 0; the other
+ * ops accept them from 48 columns on, as in a decode step.)  Inputs by op: x [N][1024], ln_w, ln_b [1024] (ops 0, 3); aq_q [N][K] int8, aq_d [N][K / 32], aq_s [N][K / 32] in the
+ * device layout of a producer's Q8 blocks (all others); bias [M] (not 0, 6); resid [N][M] (2, 5); op 1: exactly one of dev_state (4 words; one slot) and
+ * seq_states ([N][8] words; col_mode 0: column i writes slot i, 1: slot seq_id) at position n_past, and one layer's k_slots / v_slots [n_slots][16][P][64],
+ * updated in place.  The outputs come back whole, as allocated and preset to 0xff bytes: cols = N rounded up to 16, plus 1; ldo = M rounded up to 128, plus 16 --
+ * out [cols][ldo] (op 1: the q rows, [cols][1024]); ops 0, 3, 4: out_q [cols][M'], out_d / out_s [cols][M' / 32] with M' = 1024 (op 0) or 4096.
+ * launched [8] (may be NULL): kernel (as route), threads, grid x, grid y, dynamic LDS bytes, cols, ldo, 0.  For tests of the kernels themselves. */
+int biogpt_hip_chain_device(int device, int32_t op, int32_t route, int32_t wtype, int32_t M, int32_t N, const void *w_rows, const float *x, const float *ln_w,
+                            const float *ln_b, int32_t q81, const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid,
+                            const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t P, int32_t n_slots, float *k_slots, float *v_slots,
+                            float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched);
 /* One decode attention launch of N columns behind a shared prefix over caller-supplied inputs (head size 64, one layer): q [N][H * 64]; k_slots / v_slots
  * [N + 1][H][P][64], slot i column i's own and slot N the prefix's; seq_states [N][8] words as the engine's column states (n_past, ..., pad[0] = shared rows,
  * pad[1] = their slot).  which 0: the existing attn_fast_kernel<4, false, true>; 1: attn_prefix_kernel<8>, eight columns per workgroup (one shared range for

@@ -1013,7 +1013,7 @@ static void mul_mat(const bo_model *mdl, const bo_tensor *W, const float *x, int
 }
 
 /* ggml_norm then (repeat(w) * cur) + repeat(b)  (biogpt.cpp:693-700) */
-static void layer_norm(const float *x, const float *w, const float *b, float *y, int n, float eps) {
+void bo_layer_norm(const float *x, const float *w, const float *b, float *y, int n, float eps) {
     double sum = 0.0;
     for (int i = 0; i < n; i++) sum += (double)x[i];
     const float mean = (float)(sum / n);
@@ -1126,7 +1126,7 @@ int bo_eval(bo_model *m, const int32_t *tokens, int N, int n_past, float *logits
         const bo_layer *ly = &m->layers[l];
         /* self-attention layer norm (biogpt.cpp:691-701) */
         for (int i = 0; i < N; i++)
-            layer_norm(inpL + (size_t)i * D, (const float *)ly->ln0_w->data, (const float *)ly->ln0_b->data, cur + (size_t)i * D, D, eps);
+            bo_layer_norm(inpL + (size_t)i * D, (const float *)ly->ln0_w->data, (const float *)ly->ln0_b->data, cur + (size_t)i * D, D, eps);
 
         /* q/k/v projections, bias, Q scale after bias (biogpt.cpp:705-718) */
         mul_mat(m, ly->q_w, cur, N, q, 0, D);
@@ -1168,7 +1168,7 @@ int bo_eval(bo_model *m, const int32_t *tokens, int N, int n_past, float *logits
 
         /* feed forward (biogpt.cpp:777-795) */
         for (int i = 0; i < N; i++)
-            layer_norm(inpFF + (size_t)i * D, (const float *)ly->ln1_w->data, (const float *)ly->ln1_b->data, tmp + (size_t)i * D, D, eps);
+            bo_layer_norm(inpFF + (size_t)i * D, (const float *)ly->ln1_w->data, (const float *)ly->ln1_b->data, tmp + (size_t)i * D, D, eps);
         mul_mat(m, ly->fc1_w, tmp, N, ff, 0, F);
         for (int i = 0; i < N; i++)
             for (int d = 0; d < F; d++) {
@@ -1190,7 +1190,7 @@ int bo_eval(bo_model *m, const int32_t *tokens, int N, int n_past, float *logits
 
     /* final layer norm + lm head (biogpt.cpp:799-803); only the rows that are returned (F8) */
     for (int i = 0; i < N; i++)
-        layer_norm(inpL + (size_t)i * D, (const float *)m->ln_w->data, (const float *)m->ln_b->data, cur + (size_t)i * D, D, eps);
+        bo_layer_norm(inpL + (size_t)i * D, (const float *)m->ln_w->data, (const float *)m->ln_b->data, cur + (size_t)i * D, D, eps);
     memcpy(m->taps + (size_t)(L + 1) * N * D, cur, sizeof(float) * (size_t)N * D);
     if (logits_all) {
         mul_mat(m, m->lm_head, cur, N, logits_all, 0, V);

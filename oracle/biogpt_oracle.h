@@ -76,6 +76,8 @@ void   bo_dequantize_row(int type, const void *src, float *dst, int64_t k);
 /* dot(W row, x) the way ggml's CPU mul_mat does it: x is converted to the type's vec_dot_type first */
 float  bo_vec_dot(int wtype, int64_t k, const void *wrow, const float *x);
 float  bo_vec_dot_q(int wtype, int64_t k, const void *wrow, const void *yblocks);   /* activation row given as Q8_0 / Q8_1 blocks */
+/* LayerNorm of one row of n values as bo_eval computes it: ggml_norm (double sums), then (w * cur) + b; y may not alias x */
+void   bo_layer_norm(const float *x, const float *w, const float *b, float *y, int n, float eps);
 int    bo_have_avx2(void);                     /* 1: this CPU runs the AVX2 + FMA forms of the SIMD-shaped dots (bo_opts.assoc bit 2) */
 
 /* ---- model file ---- */

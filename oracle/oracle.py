@@ -63,6 +63,8 @@ def lib():
     L.bo_vec_dot.restype = C.c_float
     L.bo_vec_dot_q.restype = C.c_float
     L.bo_vec_dot_q.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+    L.bo_layer_norm.restype = None
+    L.bo_layer_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float]
     L.bo_have_avx2.restype = C.c_int
     L.bo_have_avx2.argtypes = []
     L.bo_vec_dot.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
@@ -214,6 +216,20 @@ def have_avx2():
 def vec_dot_q(wtype, k, wrow_bytes, yblocks_bytes):
     """The reference's scalar vec_dot of one weight row (file-format bytes) against an activation row already quantized to Q8_0 / Q8_1 blocks."""
     return float(lib().bo_vec_dot_q(int(wtype), int(k), C.c_char_p(bytes(wrow_bytes)), C.c_char_p(bytes(yblocks_bytes))))
+
+
+def layer_norm(x, w, b, eps=1e-5):
+    """LayerNorm of one float32 row as bo_eval computes it (bo_layer_norm)."""
+    x, w, b = (np.ascontiguousarray(a, dtype=np.float32) for a in (x, w, b))
+    assert x.ndim == 1 and x.shape == w.shape == b.shape
+    y = np.zeros_like(x)
+    lib().bo_layer_norm(x.ctypes.data, w.ctypes.data, b.ctypes.data, y.ctypes.data, x.size, float(eps))
+    return y
+
+
+def gelu_table(x):
+    """The fp16 GELU table's value at f16(x), as a float (bo_gelu_table)."""
+    return float(lib().bo_gelu_table(float(x)))
 
 
 def attn_head(q, K, V, T, exp_f32=0, assoc=0):

@@ -8,7 +8,7 @@ Which attention kernel a test reaches: single tokens up to 256 keys run the atte
 layer); single tokens at 257 .. 512 keys run dec_xpipe_kernel with two workgroups per head by default and the key-range helpers of kernels_xlong.hip.h with
 BIOGPT_HIP_XPIPE_DUAL=0 (both are run here); chunks of 2 .. 8 tokens run the attention of kernels_xcols.hip.h; passes of fewer than 80 columns (the 96-token
 prompt in passes of 64 + 32, the 19-token eval) run the per-column pass attention, and only the 700-token pass (512 + 188 columns) runs attn_tile_kernel.
-Every test that names a path asserts that the path was taken."""
+Every test that names a path asserts that the path was taken (the prompt passes: biogpt_hip_mfma_launches counts the four linear stages of every layer)."""
 import numpy as np
 import pytest
 
@@ -139,6 +139,7 @@ def test_prompt_pass_on_the_matrix_cores(pkg, oracle, files, monkeypatch, name):
         t.row(g.eval_prompt(toks, 0, 8), lo, 96)
         t.done()
         _kv_rows(g, o, 96, name + " prompt pass")
+        assert g.mfma_launches() == 4 * L, "the 64-column pass left the matrix cores (or the 32-column pass reached them): %d launches there" % g.mfma_launches()
     finally:
         g.close()
 
@@ -155,6 +156,7 @@ def test_prompt_pass_beyond_the_attention_ring(pkg, oracle, files):
         t.row(g.eval_prompt(toks, 0, 8), lo, 700)
         t.done()
         _kv_rows(g, o, 700, name + " 700-token prompt pass")
+        assert g.mfma_launches() == 2 * 4 * L, "a pass left the matrix cores: %d launches there" % g.mfma_launches()
     finally:
         g.close()
 
