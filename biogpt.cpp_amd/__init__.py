@@ -373,6 +373,61 @@ def queue_plan(gen_lens, max_columns, group, limits=None):
     return {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:n]], "column": [int(v) for v in col[:n]]}
 
 
+PREFIX_BATCH_SLOTS = 512      # one biogpt_hip_score_continuations_batch call: a slot per prefix and one per continuation
+
+
+def prefix_batch_chunks(n_conts, max_slots=PREFIX_BATCH_SLOTS):
+    """How score_continuations_batch cuts a dataset into calls: n_conts[g] continuations per group -> [(first group, one past the last)], greedily and in
+    order, each call within max_slots slots (1 + n_conts[g] per group).  A group that alone needs more raises."""
+    chunks, g0, used = [], 0, 0
+    for g, n in enumerate(n_conts):
+        need = 1 + int(n)
+        if need > max_slots:
+            raise BiogptError("group %d alone needs %d slots (1 prefix + %d continuations): more than the %d of one call" % (g, need, int(n), max_slots))
+        if used + need > max_slots:
+            chunks.append((g0, g))
+            g0, used = g, 0
+        used += need
+    if used:
+        chunks.append((g0, len(n_conts)))
+    return chunks
+
+
+def attn_runs_plan(seq_states):
+    """The planner of attn_runs_kernel (biogpt_hip_attn_runs_plan) on packed column states int32 [N][8]: int32 [n_runs][4] rows (c0, n, R, S)."""
+    st = np.ascontiguousarray(seq_states, dtype=np.int32).reshape(-1, 8)
+    runs = np.zeros((max(len(st), 1), 4), dtype=np.int32)
+    n = lib().biogpt_hip_attn_runs_plan(st.ctypes.data, len(st), runs.ctypes.data)
+    if n < 0:
+        raise BiogptError(_err())
+    return runs[:n].copy()
+
+
+def attn_runs_device(H, P, t_max, n_slots, q, k_slots, v_slots, seq_states, runs=None, q8=0, device=0, reps=0):
+    """One attn_runs_kernel<8> launch on arrays held in host memory (biogpt_hip_attn_runs_device): q float32 [N][H * 64], k_slots / v_slots float32
+    [n_slots][H][P][64], seq_states int32 [N][8], runs int32 [n_runs][4] or None (the planner's).  Returns (rc, out, out_q, out_d, out_s, launched) with
+    the outputs whole: N rounded up to 16 rows plus a guard row, preset to 0xff.  reps > 0: a seventh item, the microseconds of reps further launches."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    k = np.ascontiguousarray(k_slots, dtype=np.float32)
+    v = np.ascontiguousarray(v_slots, dtype=np.float32)
+    st = np.ascontiguousarray(seq_states, dtype=np.int32).reshape(-1, 8)
+    N, D = len(st), H * 64
+    rows = (N + 15) // 16 * 16 + 1
+    out = np.zeros((rows, D), dtype=np.float32)
+    oq, od, os_ = np.zeros((rows, D), dtype=np.int8), np.zeros((rows, D // 32), dtype=np.float32), np.zeros((rows, D // 32), dtype=np.uint32)
+    launched = np.full(8, -1, dtype=np.int32)
+    rn = None if runs is None else np.ascontiguousarray(runs, dtype=np.int32).reshape(-1, 4)
+    args = (int(device), int(H), N, int(P), int(t_max), int(n_slots), q.ctypes.data, k.ctypes.data, v.ctypes.data, st.ctypes.data,
+            None if rn is None else rn.ctypes.data, 0 if rn is None else len(rn), int(q8), out.ctypes.data, oq.ctypes.data if q8 else None,
+            od.ctypes.data if q8 else None, os_.ctypes.data if q8 else None, launched.ctypes.data)
+    if reps > 0:
+        us = np.zeros(reps, dtype=np.float32)
+        rc = lib().biogpt_hip_attn_runs_bench(*args, int(reps), us.ctypes.data)
+        return rc, out, oq, od, os_, launched, us
+    rc = lib().biogpt_hip_attn_runs_device(*args)
+    return rc, out, oq, od, os_, launched
+
+
 def beam_rows(rows, n_beams, run_score, given=False, first_step=False, device=0, masked=False):
     """beam_group_rows_kernel on rows held in host memory (biogpt_hip_beam_rows_device): rows float32 [G * n_beams][n_vocab], run_score [G * n_beams].
     Returns (score float32, col int32, id int32), each [G * n_beams][2 * n_beams]; rows the kernel left alone hold (NaN, -1, -1).  masked (with given):
@@ -558,6 +613,11 @@ SYMBOLS = [
     ("biogpt_hip_score", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_score_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_score_continuations", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_score_continuations_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_double)]),
+    ("biogpt_hip_prefix_batch_stats", C.c_int, [_P, _P]),
+    ("biogpt_hip_attn_runs_plan", C.c_int, [_P, C.c_int32, _P]),
+    ("biogpt_hip_attn_runs_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 5 + [C.c_int32, C.c_int32] + [_P] * 5),
+    ("biogpt_hip_attn_runs_bench", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 5 + [C.c_int32, C.c_int32] + [_P] * 5 + [C.c_int32, _P]),
     ("biogpt_hip_generate_greedy_prefix", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_generate_sample_prefix", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
                                                     C.c_int32, _P, _P, C.POINTER(C.c_double)]),
@@ -1380,6 +1440,57 @@ class BiogptModel:
         rows = self.score_continuations(prefix, continuations)
         sums = np.asarray([lp.astype(np.float64).sum() / (len(lp) if normalize else 1) for lp, _, _ in rows], dtype=np.float64)
         return np.argsort(-sums, kind="stable"), sums
+
+    def score_continuations_batch(self, prefixes, continuations):
+        """score_continuations for a dataset: prefixes a list of id lists, continuations a list (one entry per prefix) of lists of id lists.  Returns one list
+        per group of (logprobs, argmax, logits) triples, as score_continuations(prefixes[g], continuations[g]) does.  The groups travel through common passes
+        (biogpt_hip_score_continuations_batch); a dataset that needs more than 512 slots (one per prefix, one per continuation) is cut into several calls,
+        greedily and in order (prefix_batch_chunks).  BIOGPT_HIP_RUN_ATTN=0: bit for bit the per-group calls; see include/biogpt_hip.h for the other settings."""
+        if len(prefixes) != len(continuations):
+            raise BiogptError("continuations must have one entry per prefix (%d != %d)" % (len(continuations), len(prefixes)))
+        out, secs_all, self.prefix_batch_calls = [], 0.0, 0
+        for g0, g1 in prefix_batch_chunks([len(c) for c in continuations]):
+            pres = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in prefixes[g0:g1]]
+            flat_p = np.ascontiguousarray(np.concatenate(pres)) if sum(p.size for p in pres) else np.zeros(1, np.int32)
+            plens = np.asarray([p.size for p in pres], dtype=np.int32)
+            ncs = np.asarray([len(c) for c in continuations[g0:g1]], dtype=np.int32)
+            cs = [np.asarray(c, dtype=np.int32).reshape(-1) for grp in continuations[g0:g1] for c in grp]
+            clens = np.asarray([c.size for c in cs] or [0], dtype=np.int32)
+            flat_c = np.ascontiguousarray(np.concatenate(cs)) if sum(c.size for c in cs) else np.zeros(1, np.int32)
+            n = max(int(clens.sum()), 1)
+            lp, am, lg = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+            secs = C.c_double(0.0)
+            if lib().biogpt_hip_score_continuations_batch(self._h, flat_p.ctypes.data, plens.ctypes.data, g1 - g0, flat_c.ctypes.data, clens.ctypes.data,
+                                                          ncs.ctypes.data, lp.ctypes.data, am.ctypes.data, lg.ctypes.data, C.byref(secs)) != 0:
+                raise BiogptError(_err())
+            secs_all += secs.value
+            self.prefix_batch_calls += 1
+            off, at = 0, 0
+            for nc in ncs:
+                rows = []
+                for k in clens[at:at + nc]:
+                    rows.append((lp[off:off + k].copy(), am[off:off + k].copy(), lg[off:off + k].copy()))
+                    off += int(k)
+                at += int(nc)
+                out.append(rows)
+        self.score_seconds = secs_all
+        return out
+
+    def rank_continuations_batch(self, prefixes, continuations, normalize=False):
+        """rank_continuations for a dataset: a list of (order, sums) per group -- float64 sums on the host, ties keep the order given."""
+        res = []
+        for rows in self.score_continuations_batch(prefixes, continuations):
+            sums = np.asarray([lp.astype(np.float64).sum() / (len(lp) if normalize else 1) for lp, _, _ in rows], dtype=np.float64)
+            res.append((np.argsort(-sums, kind="stable"), sums))
+        return res
+
+    def prefix_batch_stats(self):
+        """Of the last successful biogpt_hip_score_continuations_batch call on this model: prefix_columns, continuation_columns, passes, run_passes (the
+        passes whose attention ran on attn_runs_kernel)."""
+        out = np.zeros(4, dtype=np.int32)
+        if lib().biogpt_hip_prefix_batch_stats(self._h, out.ctypes.data) != 0:
+            raise BiogptError(_err())
+        return dict(prefix_columns=int(out[0]), continuation_columns=int(out[1]), passes=int(out[2]), run_passes=int(out[3]))
 
     # -- hidden states, pooled embeddings, classification heads (no reference counterpart) --
     def hidden(self, tokens, n_past=0):

@@ -32,6 +32,7 @@
 #include "host_common.h"
 #include "kernels.hip.h"
 #include "kernels_fast.hip.h"
+#include "kernels_runs.hip.h"
 #include "kernels_decode.hip.h"
 #include "kernels_fdecode.hip.h"
 #include "kernels_lmhead.hip.h"
@@ -197,7 +198,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -227,6 +228,7 @@ struct EngineOptions {
         fault_stale = get("BIOGPT_HIP_FAULT_STALE", 0);           // test switch: every k-th replayed eval starts from the PREVIOUS mailbox slot (the stale-row symptom, injected)
         proc_lock = get("BIOGPT_HIP_PROC_LOCK", 1);               // one process per device drives the pipelined launches (engine_xpipe.inc, xpipe_process_lock)
         prefix_attn = get("BIOGPT_HIP_PREFIX_ATTN", -1);          // decode steps behind a shared prefix: -1 attn_prefix_kernel where it was measured faster (PREFIX_ATTN_MIN_*), 0 never, 1 always (A/B arms)
+        run_attn = get("BIOGPT_HIP_RUN_ATTN", -1);                // the passes of biogpt_hip_score_continuations_batch (no other call looks at it): -1 attn_runs_kernel where it was measured faster (RUN_ATTN_MIN_*), 0 never, 1 in every pass of up to 1024 keys (A/B arms)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
     }
 };
@@ -289,6 +291,7 @@ struct biogpt_hip_ctx {
     int32_t *sc_tgt = nullptr;
     uint32_t *sc_out = nullptr;
     size_t sc_cap = 0;
+    int32_t pfxb_stats[4] = {0, 0, 0, 0};   // the last successful biogpt_hip_score_continuations_batch: prefix columns, continuation columns, passes, passes on attn_runs_kernel
     // hidden states / embeddings (biogpt_hip_hidden, biogpt_hip_embed_batch): one block that holds the call's output rows and what the call needs beside them
     uint8_t *emb_buf = nullptr;
     size_t emb_cap = 0;
@@ -1127,6 +1130,10 @@ struct ForwardPass {
     int head_from;
     int shared_rows = 0;    // decode_step_shared
     const bgk::SeqState *col_states = nullptr;      // Packed: the column states where they are not c->cols (packed_verify)
+    // packed_continuations of biogpt_hip_score_continuations_batch: the pass's run table on the device ([n_runs][4]: c0, n, R, S); n_runs > 0: the
+    // attention of the pass is attn_runs_kernel.  No other call sets it.
+    const int32_t *runs = nullptr;
+    int n_runs = 0;
 
     // the context's own columns
     static ForwardPass last_row(int n, int t_max) { return {n, t_max, Cols::Context, Rows::Last}; }
@@ -1202,6 +1209,7 @@ enum AttnKernel : int {
     AK_FAST_1 = 0, AK_FAST_2 = 1, AK_FAST_4 = 2, AK_FAST_SLIM = 3,      // attn_fast_kernel<1, true>, <2, false>, <4, false> at 1024 threads, <4, false> as the slim launch
     AK_FAST_SHARED = 4,                                                  // + the four above: their SHARED instantiations
     AK_PREFIX = 8, AK_SPLIT = 9, AK_GROUP = 10, AK_TILE_DMA = 11, AK_TILE = 12, AK_GENERIC = 13,
+    AK_RUNS = 16,                                                        // attn_runs_kernel<8>: no route of biogpt_hip_attn_device (its probe is biogpt_hip_attn_runs_device)
 };
 struct AttnLaunch { int kernel, threads, grid_x, grid_y; size_t lds; };
 
@@ -1247,6 +1255,36 @@ inline AttnLaunch launch_attn_prefix(const bgk::AttnParams &a, int H, int N, hip
     const AttnLaunch g{AK_PREFIX, 512, H, (N + 7) / 8, 0};
     hipLaunchKernelGGL((bgk::attn_prefix_kernel<8>), dim3(g.grid_x, g.grid_y), dim3(g.threads), 0, st, a);
     return g;
+}
+// packed columns in runs of up to eight that share their first rows (biogpt_hip_score_continuations_batch): one workgroup per (head, run)
+inline AttnLaunch launch_attn_runs(const bgk::AttnParams &a, const int32_t *runs, int n_runs, int H, hipStream_t st) {
+    const AttnLaunch g{AK_RUNS, 512, H, n_runs, 0};
+    const bgk::AttnRunsParams rp{a, runs};
+    hipLaunchKernelGGL((bgk::attn_runs_kernel<8>), dim3(g.grid_x, g.grid_y), dim3(g.threads), 0, st, rp);
+    return g;
+}
+// The planner of attn_runs_kernel: the columns of a packed pass (col_mode 1), walked greedily into runs {c0, n, R, S} -- a run is cut at 8 columns or
+// at the first column that does not fit.  A column without shared rows (pad[0] == 0) starts or joins a prefix run of its seq_id (S = seq_id, R = the
+// smallest t_vis of the run); a column with pad[0] > 0 a continuation run of its (pad[0], pad[1]) (S = pad[1], R = pad[0]).  A column that sees fewer
+// rows than pad[0] stands alone with R = t_vis.  Returns the number of runs; runs_out holds up to N.
+inline int attn_runs_plan(const bgk::SeqState *st, int N, int32_t *runs_out) {
+    int n_runs = 0;
+    for (int i = 0; i < N;) {
+        const bgk::SeqState &f = st[i];
+        const bool pre = f.pad[0] <= 0;
+        int n = 1, R = pre ? f.t_vis : std::min(f.pad[0], f.t_vis);
+        if (pre || f.t_vis >= f.pad[0]) {
+            for (; n < bgk::RUNS_MAX_COLS && i + n < N; n++) {
+                const bgk::SeqState &c = st[i + n];
+                if (pre ? !(c.pad[0] <= 0 && c.seq_id == f.seq_id) : !(c.pad[0] == f.pad[0] && c.pad[1] == f.pad[1] && c.t_vis >= c.pad[0])) break;
+                if (pre) R = std::min(R, c.t_vis);
+            }
+        }
+        int32_t *r = runs_out + 4 * (size_t)n_runs++;
+        r[0] = i; r[1] = n; r[2] = R; r[3] = pre ? f.seq_id : f.pad[1];
+        i += n;
+    }
+    return n_runs;
 }
 // a pass of many query columns: register-tiled kernel, 16 queries per workgroup share every K / V row they load (tables with attn_tile_table_ok)
 // lds_done: the kernels whose > 64 KB dynamic-LDS opt-in attribute is set on this device
@@ -1317,6 +1355,10 @@ bool enqueue_attention(PassLaunch &k, int l) {
     if (N == 1 && !batch && a.t_cap > SPLIT_ATTN_ABOVE_KEYS) {
         a.sp_scores = c->sp_scores; a.sp_max = c->sp_max; a.sp_pv = c->sp_pv;
         return launch_attn_split(a, H, st, nullptr);
+    }
+    if (k.pass.n_runs > 0) {      // biogpt_hip_score_continuations_batch decided per pass (run_attn); t_cap <= 1024 here
+        launch_attn_runs(a, k.pass.runs, k.pass.n_runs, H, st);
+        return true;
     }
     const bool slim = batch && N >= SLIM_ATTN_MIN_COLS;
     const bool grouped = k.pass.shared_prefix && k.pass.cols == ForwardPass::Cols::PerSequence && a.t_cap <= bgk::PFX_MAX_KEYS &&
@@ -3183,6 +3225,190 @@ int biogpt_hip_score_continuations(biogpt_hip_ctx *ctx, const int32_t *prefix, i
     return with_xpipe_retry(ctx, 0, [&] {
         return score_continuations_once(ctx, prefix, n_prefix, conts, cont_lens, n_conts, logprob_out, argmax_out, logit_out, seconds_out);
     });
+}
+
+// ---- several (prefix, continuations) groups in one call ----------------------------------------------------------------------------------------
+// Group g is score_continuations(prefix_g, conts_g).  Slot g holds the rows [0, n_prefix_g - 1) of prefix g; continuation f (flat index over all groups)
+// owns slot n_groups + f, re-evaluates the last token of its group's prefix and reads the prefix rows in place (SeqState::pad[0] / pad[1]).  The columns
+// travel in ONE stream of passes of up to BIOGPT_HIP_PROMPT_COLS columns: every prefix column of every group first, then every continuation column in flat
+// order -- so pure prefix passes, at most one mixed pass, then scored passes, each a ForwardPass::packed_continuations.  A continuation column may share a
+// pass with prefix columns it reads, as in the single call.  The attention of a pass is attn_fast_kernel<.., SHARED> as there, or attn_runs_kernel over the
+// runs of attn_runs_plan (BIOGPT_HIP_RUN_ATTN; the table goes up behind the column states in one copy).
+// attn_runs_kernel instead of attn_fast_kernel<.., SHARED> in a pass of this call (BIOGPT_HIP_RUN_ATTN=-1): a pass of RUN_ATTN_MIN_COLS columns or more whose longest
+// shared range (the largest R of its runs) has RUN_ATTN_MIN_SHARED rows or more, and every pass of RUN_ATTN_ANY_SHARED_COLS columns or more.
+// (2026-10-20, tools/prefix_batch_bench.py --ab: the call, 24 layers, the kernel never / always taken, runs / existing.  Passes of 512 columns: 0.63 - 0.64 x behind
+// 384-token prefixes (16 / 64 / 128 groups of three one-token candidates, 8 groups of 32 x 8, one group of 64 x 8), 0.96 x behind 64-token prefixes (64 groups; ranges of
+// at most 63 rows).  One pass of 386 columns (one example behind 384 tokens, longest range 383): 0.70 x.  One pass of 66 columns (behind 64 tokens): 1.04 x, of 18
+// columns: 1.08 x -- it loses there.  Single passes in between: 258 columns behind 256 tokens (longest range 255) 0.97 x, 396 columns of 6 groups behind 64 tokens
+// (ranges of at most 63 rows) 0.94 x; 130 columns behind 128 tokens 1.02 x and 132 columns of 2 groups behind 64 tokens 1.06 x lose.  The thresholds are the smallest
+// measured wins.  Not measured: 133 .. 257 columns; 258 .. 395 columns with ranges shorter than 255 rows; other quantizations than Q4_0.  DESIGN.md 4.7 has the tables.)
+constexpr int RUN_ATTN_MIN_COLS = 258, RUN_ATTN_MIN_SHARED = 255, RUN_ATTN_ANY_SHARED_COLS = 396;
+constexpr int PFXB_MAX_SLOTS = 512;     // each slot is a full F32 KV cache
+
+static int score_continuations_batch_once(biogpt_hip_ctx *ctx, const int32_t *prefixes, const int32_t *prefix_lens, int32_t n_groups, const int32_t *conts,
+                                          const int32_t *cont_lens, const int32_t *n_conts, float *logprob_out, int32_t *argmax_out, float *logit_out,
+                                          double *seconds_out) {
+    XpCallScope xp_scope(ctx);
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!prefixes) BG_FAIL(-1, "null argument: prefixes");
+    if (!prefix_lens) BG_FAIL(-1, "null argument: prefix_lens");
+    if (!conts) BG_FAIL(-1, "null argument: conts");
+    if (!cont_lens) BG_FAIL(-1, "null argument: cont_lens");
+    if (!n_conts) BG_FAIL(-1, "null argument: n_conts");
+    if (!logprob_out) BG_FAIL(-1, "null argument: logprob_out");
+    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (n_groups < 1) BG_FAIL(-1, "n_groups must be >= 1 (got %d)", n_groups);
+    long slots = n_groups;
+    for (int g = 0; g < n_groups; g++) {
+        if (n_conts[g] < 1) BG_FAIL(-1, "n_conts[%d] must be >= 1 (got %d)", g, n_conts[g]);
+        slots += n_conts[g];
+    }
+    if (slots > PFXB_MAX_SLOTS)
+        BG_FAIL(-1, "%ld slots exceed the %d of one call: n_groups (%d) + the sum of n_conts (%ld), one slot per prefix and one per continuation", slots, PFXB_MAX_SLOTS, n_groups, slots - n_groups);
+    const auto &hp = ctx->hp;
+    if (!check_fast_chain(ctx, "shared-prefix scoring")) return -1;
+    size_t total = 0, pre_off = 0, pre_cols = 0;
+    int cont_at = 0;
+    for (int g = 0; g < n_groups; g++) {
+        const int n_prefix = prefix_lens[g];
+        if (n_prefix < 1) BG_FAIL(-1, "prefix_lens[%d] (n_prefix of group %d) must be >= 1 (got %d)", g, g, n_prefix);
+        if (n_prefix > hp.n_positions) BG_FAIL(-1, "prefix_lens[%d] (n_prefix %d of group %d) exceeds n_positions (%d)", g, n_prefix, g, hp.n_positions);
+        for (int i = 0; i < n_prefix; i++) {
+            const int32_t t = prefixes[pre_off + (size_t)i];
+            if (t < 0 || t >= hp.n_vocab) BG_FAIL(-1, "token id %d (group %d, prefix, position %d) out of range [0, %d)", t, g, i, hp.n_vocab);
+        }
+        for (int c = 0; c < n_conts[g]; c++, cont_at++) {
+            const int len = cont_lens[cont_at];
+            if (len < 1) BG_FAIL(-1, "empty continuation (group %d, continuation %d: cont_lens[%d])", g, c, cont_at);
+            if (len > hp.n_positions - n_prefix)
+                BG_FAIL(-1, "n_prefix (%d) + cont_lens[%d] (%d) of group %d, continuation %d exceeds n_positions (%d)", n_prefix, cont_at, len, g, c, hp.n_positions);
+            for (int i = 0; i < len; i++) {
+                const int32_t t = conts[total + (size_t)i];
+                if (t < 0 || t >= hp.n_vocab) BG_FAIL(-1, "token id %d (group %d, continuation %d, position %d) out of range [0, %d)", t, g, c, i, hp.n_vocab);
+            }
+            total += (size_t)len;
+        }
+        pre_off += (size_t)n_prefix;
+        pre_cols += (size_t)(n_prefix - 1);
+    }
+    const int n_all = cont_at;
+    HIP_TRY(-2, hipSetDevice(ctx->device));
+    if (!resident_stop(ctx)) return -2; disarm_lineage(ctx);
+    // every prefix and every continuation in the per-sequence caches (bk / bv): the context's own cache, position and logits row stay as they are
+    const size_t max_cols = (size_t)std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
+    if (!ensure_seq_caches(ctx, (int)slots)) {
+        (void)hipGetLastError();
+        BG_FAIL(-2, "out of device memory: the %zu-byte K / V caches of %d prefixes and %d continuations could not be allocated",
+                (size_t)2 * 4 * hp.n_layer * hp.n_positions * hp.d_model * (size_t)slots, n_groups, n_all);
+    }
+    if ((long)std::min(max_cols, total + pre_cols) >= MFMA_MIN_PASS_COLS && !ensure_tile_images(ctx)) return -2;
+    if (!ensure_logits_rows(ctx, std::min(max_cols, total)) || !score_setup(ctx, conts, cont_lens, n_all, conts, total)) return -2;
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+
+    std::vector<bgk::SeqState> cols;
+    std::vector<int32_t> runs, up;
+    int pass_tmax = 0, n_pre = 0, n_passes = 0, n_run_passes = 0;
+    size_t flat0 = 0;
+    auto flush = [&]() -> bool {
+        if (cols.empty()) return true;
+        const int n = (int)cols.size();
+        const int t_cap = attn_decode_t_cap(hp.n_positions, pass_tmax);
+        int n_runs = 0;
+        if (t_cap <= bgk::RUNS_MAX_KEYS && ctx->opt.run_attn != 0 && (ctx->opt.run_attn == 1 || n >= RUN_ATTN_MIN_COLS)) {
+            runs.resize(4 * (size_t)n);
+            n_runs = attn_runs_plan(cols.data(), n, runs.data());
+            int longest = 0;
+            for (int r = 0; r < n_runs; r++) longest = std::max(longest, runs[4 * (size_t)r + 2]);
+            if (ctx->opt.run_attn < 0 && n < RUN_ATTN_ANY_SHARED_COLS && longest < RUN_ATTN_MIN_SHARED) n_runs = 0;      // the existing attention
+        }
+        // the column states and, behind them, the run table: one copy
+        static_assert(sizeof(bgk::SeqState) == 32, "a column state holds two table rows");
+        const size_t need = (size_t)n + ((size_t)n_runs + 1) / 2;
+        if (need > ctx->cols_cap) {
+            if (ctx->cols) (void)hipFree(ctx->cols);
+            ctx->cols = nullptr; ctx->cols_cap = 0;
+            if (hipMalloc(&ctx->cols, sizeof(bgk::SeqState) * need) != hipSuccess) {
+                (void)hipGetLastError();
+                ctx->cols = nullptr;
+                BG_FAIL(false, "out of device memory: the %zu-byte column states of a pass could not be allocated", sizeof(bgk::SeqState) * need);
+            }
+            ctx->cols_cap = need;
+        }
+        up.assign(8 * need, 0);
+        std::memcpy(up.data(), cols.data(), sizeof(bgk::SeqState) * (size_t)n);
+        if (n_runs) std::memcpy(up.data() + 8 * (size_t)n, runs.data(), 16 * (size_t)n_runs);
+        HIP_TRY(false, hipMemcpyAsync(ctx->cols, up.data(), sizeof(bgk::SeqState) * need, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(false, hipStreamSynchronize(ctx->stream));   // the host vector is reused for the next pass
+        ForwardPass fp = ForwardPass::packed_continuations(n, pass_tmax, n_pre);
+        if (n_runs) { fp.runs = reinterpret_cast<const int32_t *>(ctx->cols + n); fp.n_runs = n_runs; }
+        if (!enqueue_forward(ctx, fp) || (n_pre < n && !enqueue_logprob(ctx, n - n_pre, flat0, total))) return false;
+        flat0 += (size_t)(n - n_pre);
+        n_passes++; n_run_passes += n_runs ? 1 : 0;
+        cols.clear();
+        pass_tmax = 0; n_pre = 0;
+        return true;
+    };
+    pre_off = 0;
+    for (int g = 0; g < n_groups; g++) {
+        for (int i = 0; i + 1 < prefix_lens[g]; i++) {
+            if (cols.size() == max_cols && !flush()) return -2;
+            bgk::SeqState cst{};
+            cst.n_past = i; cst.token = prefixes[pre_off + (size_t)i]; cst.seq_id = g; cst.t_vis = i + 1;      // pad[0] = 0: every row its own
+            cols.push_back(cst);
+            n_pre++;
+            pass_tmax = std::max(pass_tmax, i + 1);
+        }
+        pre_off += (size_t)prefix_lens[g];
+    }
+    pre_off = 0;
+    size_t off = 0;
+    cont_at = 0;
+    for (int g = 0; g < n_groups; g++) {
+        const int n_prefix = prefix_lens[g];
+        for (int c = 0; c < n_conts[g]; c++, cont_at++) {
+            for (int i = 0; i < cont_lens[cont_at]; i++) {
+                if (cols.size() == max_cols && !flush()) return -2;
+                bgk::SeqState cst{};
+                cst.n_past = n_prefix - 1 + i; cst.token = i == 0 ? prefixes[pre_off + (size_t)(n_prefix - 1)] : conts[off + (size_t)(i - 1)];
+                cst.seq_id = n_groups + cont_at; cst.t_vis = n_prefix + i;
+                cst.pad[0] = n_prefix - 1; cst.pad[1] = g;      // rows [0, n_prefix - 1) lie in the group's prefix slot
+                cols.push_back(cst);
+                pass_tmax = std::max(pass_tmax, n_prefix + i);
+            }
+            off += (size_t)cont_lens[cont_at];
+        }
+        pre_off += (size_t)n_prefix;
+    }
+    if (!flush()) return -2;
+    const int rc = score_finish(ctx, total, logprob_out, argmax_out, logit_out);
+    if (rc != 0) return rc;
+    if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const int32_t stats[4] = {(int32_t)pre_cols, (int32_t)total, n_passes, n_run_passes};
+    std::memcpy(ctx->pfxb_stats, stats, sizeof(stats));
+    return 0;
+}
+
+int biogpt_hip_score_continuations_batch(biogpt_hip_ctx *ctx, const int32_t *prefixes, const int32_t *prefix_lens, int32_t n_groups, const int32_t *conts,
+                                         const int32_t *cont_lens, const int32_t *n_conts, float *logprob_out, int32_t *argmax_out, float *logit_out,
+                                         double *seconds_out) {
+    return with_xpipe_retry(ctx, 0, [&] {
+        return score_continuations_batch_once(ctx, prefixes, prefix_lens, n_groups, conts, cont_lens, n_conts, logprob_out, argmax_out, logit_out, seconds_out);
+    });
+}
+int biogpt_hip_prefix_batch_stats(const biogpt_hip_ctx *ctx, int32_t out[4]) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (!out) BG_FAIL(-1, "null argument: out");
+    std::memcpy(out, ctx->pfxb_stats, sizeof(ctx->pfxb_stats));
+    return 0;
+}
+int biogpt_hip_attn_runs_plan(const int32_t *seq_states, int32_t N, int32_t *runs_out) {
+    clear_error();
+    if (!seq_states || !runs_out) BG_FAIL(-1, "seq_states or runs_out is NULL");
+    if (N < 1 || N > 1024) BG_FAIL(-1, "N must be in [1, 1024]");
+    return attn_runs_plan(reinterpret_cast<const bgk::SeqState *>(seq_states), N, runs_out);
 }
 
 // ---- hidden states, pooled embeddings, classification heads: the same causal passes without the lm_head (kernels_embed.hip.h) ------------

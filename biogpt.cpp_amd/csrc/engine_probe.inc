@@ -383,6 +383,123 @@ int biogpt_hip_attn_prefix_bench(int device, int32_t H, int32_t N, int32_t P, in
     return attn_prefix_device(device, H, N, P, t_cap, q, k_slots, v_slots, seq_states, which, q8, out, out_q, out_d, out_s, reps, us_out);
 }
 
+// One attn_runs_kernel<8> launch over caller-supplied inputs, through the engine's own launch helper (launch_attn_runs): N packed columns (seq_states,
+// col_mode 1: slot seq_id, T = t_vis, the first pad[0] rows in slot pad[1]) in a table of P <= 1024 rows; q [N][H * 64]; k_slots / v_slots [n_slots][H][P][64];
+// t_max the pass's furthest visible key count (t_cap follows as for the engine's packed passes).  runs [n_runs][4] {c0, n, R, S}, or NULL: the planner's
+// (attn_runs_plan).  A caller's table is validated before anything is allocated: every column in exactly one run, runs of consecutive columns in order,
+// n in [1, 8], and for every member the rows [0, R) really lie in slot S and the rows [R, T) in its own slot.  Outputs, guard rows and q8 as
+// biogpt_hip_attn_device; launched [8]: kernel (16), threads, grid x, grid y, LDS bytes, t_cap, number of runs, 0.
+static int attn_runs_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots, const float *v_slots,
+                            const int32_t *seq_states, const int32_t *runs, int32_t n_runs, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s,
+                            int32_t *launched, int32_t reps, float *us_out) {
+    clear_error();
+    if (!q || !k_slots || !v_slots || !seq_states || !out) BG_FAIL(-1, "q, k_slots, v_slots, seq_states or out is NULL");
+    if (H < 1 || H > 64) BG_FAIL(-1, "H must be in [1, 64]");
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (P < 1 || P > bgk::RUNS_MAX_KEYS) BG_FAIL(-1, "P must be in [1, %d]", bgk::RUNS_MAX_KEYS);
+    if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
+    if (t_max < 1 || t_max > P) BG_FAIL(-1, "t_max must be in [1, P]: t_cap never exceeds the table");
+    if (q8 < 0 || q8 > 2 || (q8 > 0 && (!out_q || !out_d || !out_s))) BG_FAIL(-1, "q8 must be 0, 1 or 2, with out_q, out_d and out_s");
+    if (reps < 0 || reps > 10000 || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, 10000], with us_out");
+    const int t_cap = attn_decode_t_cap(P, t_max);
+    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
+    for (int i = 0; i < N; i++) {
+        const int T = hs[i].t_vis;
+        if (T < 1 || T > t_cap || T > t_max) BG_FAIL(-1, "column %d: %d visible keys outside [1, t_cap = %d] (t_max %d)", i, T, t_cap, t_max);
+        if (hs[i].seq_id < 0 || hs[i].seq_id >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, hs[i].seq_id);
+        if (hs[i].pad[0] < 0 || hs[i].pad[0] > T) BG_FAIL(-1, "column %d: %d shared rows outside [0, t_vis]", i, hs[i].pad[0]);
+        if (hs[i].pad[1] < 0 || hs[i].pad[1] >= n_slots) BG_FAIL(-1, "column %d: shared slot %d outside [0, n_slots)", i, hs[i].pad[1]);
+    }
+    std::vector<int32_t> table(4 * (size_t)N);
+    if (!runs) {
+        n_runs = attn_runs_plan(hs, N, table.data());
+    } else {
+        if (n_runs < 1 || n_runs > N) BG_FAIL(-1, "n_runs must be in [1, N]");
+        std::memcpy(table.data(), runs, 16 * (size_t)n_runs);
+    }
+    int next = 0;      // a caller's table and the planner's alike
+    for (int r = 0; r < n_runs; r++) {
+        const int c0 = table[4 * r], n = table[4 * r + 1], R = table[4 * r + 2], S = table[4 * r + 3];
+        if (n < 1 || n > bgk::RUNS_MAX_COLS) BG_FAIL(-1, "run %d: n = %d outside [1, %d]", r, n, bgk::RUNS_MAX_COLS);
+        if (c0 != next) BG_FAIL(-1, "run %d: starts at column %d, not at %d: every column lies in exactly one run, in order", r, c0, next);
+        if (c0 + n > N) BG_FAIL(-1, "run %d: columns [%d, %d) beyond N = %d", r, c0, c0 + n, N);
+        if (R < 0 || S < 0 || S >= n_slots) BG_FAIL(-1, "run %d: R = %d, S = %d outside the slots", r, R, S);
+        for (int i = c0; i < c0 + n; i++) {
+            const int ns = hs[i].pad[0], own = hs[i].seq_id, shr = hs[i].pad[1];
+            const bool first_in_S = R <= hs[i].t_vis && (std::min(R, ns) == 0 || shr == S) && (R <= ns || own == S);
+            const bool rest_own = R >= ns || shr == own || R >= hs[i].t_vis;
+            if (!first_in_S || !rest_own) BG_FAIL(-1, "run %d: the first %d rows of column %d do not lie in slot %d with the others in its own", r, R, i, S);
+        }
+        next = c0 + n;
+    }
+    if (next != N) BG_FAIL(-1, "the runs cover columns [0, %d), not all %d", next, N);
+    HIP_TRY(-2, hipSetDevice(device));
+    const int D = H * 64, rows = ((N + 15) & ~15) + 1;
+    const size_t slot = (size_t)H * P * 64, kv_b = slot * 4 * (size_t)n_slots, q_b = (size_t)N * D * 4, row_b = (size_t)rows * D * 4, blk = (size_t)rows * (D / 32);
+    ByteLayout l;
+    const size_t o_k = l.part(kv_b), o_v = l.part(kv_b), o_q = l.part(q_b), o_st = l.part(sizeof(bgk::SeqState) * (size_t)N), o_rn = l.part(16 * (size_t)n_runs),
+                 o_tab = l.part(65536 * 2), o_out = l.part(row_b), o_oq = l.part((size_t)rows * D), o_od = l.part(blk * 4), o_os = l.part(blk * 4);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    std::vector<uint16_t> te(65536);
+    for (uint32_t i = 0; i < 65536; i++) te[i] = f32_to_f16(expf(f16_to_f32((uint16_t)i)));      // the table of the model loader
+    HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_q, q, q_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_rn, table.data(), 16 * (size_t)n_runs, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_tab, te.data(), 65536 * 2, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));      // the outputs with their guard rows
+    bgk::AttnParams a{};
+    a.q = d.at<const float>(o_q); a.kcache = d.at<const float>(o_k); a.vcache = d.at<const float>(o_v); a.out = d.at<float>(o_out);
+    a.exp_tab = d.at<const uint16_t>(o_tab);
+    a.N = N; a.D = D; a.dk = 64; a.P = P; a.t_cap = t_cap;
+    a.seq = d.at<const bgk::SeqState>(o_st); a.col_mode = 1; a.kv_seq_stride = (int64_t)slot;
+    a.q81 = q8 == 2 ? 1 : 0;
+    if (q8 > 0) { a.oq_q = d.at<int8_t>(o_oq); a.oq_d = d.at<float>(o_od); a.oq_s = d.at<uint32_t>(o_os); }
+    const AttnLaunch g = launch_attn_runs(a, d.at<const int32_t>(o_rn), n_runs, H, 0);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    if (launched) {
+        const int32_t rep[8] = {g.kernel, g.threads, g.grid_x, g.grid_y, (int32_t)g.lds, t_cap, n_runs, 0};
+        std::memcpy(launched, rep, sizeof(rep));
+    }
+    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, row_b, hipMemcpyDeviceToHost));
+    if (q8 > 0) {
+        HIP_TRY(-2, hipMemcpy(out_q, d.p + o_oq, (size_t)rows * D, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(out_d, d.p + o_od, blk * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(out_s, d.p + o_os, blk * 4, hipMemcpyDeviceToHost));
+    }
+    if (reps > 0) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIP_TRY(-2, hipEventCreate(&e0));
+        HIP_TRY(-2, hipEventCreate(&e1));
+        bool ok = true;
+        for (int i = 0; i < reps && ok; i++) {
+            ok = hipEventRecord(e0, 0) == hipSuccess;
+            launch_attn_runs(a, d.at<const int32_t>(o_rn), n_runs, H, 0);
+            ok = ok && hipEventRecord(e1, 0) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
+            float ms = 0.0f;
+            ok = ok && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+            us_out[i] = ms * 1000.0f;
+        }
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        if (!ok) BG_FAIL(-2, "a timed attention launch failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    return 0;
+}
+int biogpt_hip_attn_runs_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots, const float *v_slots,
+                                const int32_t *seq_states, const int32_t *runs, int32_t n_runs, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s,
+                                int32_t *launched) {
+    return attn_runs_device(device, H, N, P, t_max, n_slots, q, k_slots, v_slots, seq_states, runs, n_runs, q8, out, out_q, out_d, out_s, launched, 0, nullptr);
+}
+int biogpt_hip_attn_runs_bench(int device, int32_t H, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots, const float *v_slots,
+                               const int32_t *seq_states, const int32_t *runs, int32_t n_runs, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s,
+                               int32_t *launched, int32_t reps, float *us_out) {
+    if (reps < 1 || reps > 10000 || !us_out) { clear_error(); BG_FAIL(-1, "reps must be in [1, 10000], with us_out"); }
+    return attn_runs_device(device, H, N, P, t_max, n_slots, q, k_slots, v_slots, seq_states, runs, n_runs, q8, out, out_q, out_d, out_s, launched, reps, us_out);
+}
+
 // logprob_rows_kernel over rows held in host memory (tests of the kernel itself): ldl = n_vocab, so an odd n_vocab puts rows 1, 2, 3 on the other
 // 16-byte alignments
 int biogpt_hip_logprob_rows_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *targets, float *lp_out, int32_t *argmax_out,

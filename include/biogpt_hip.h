@@ -419,6 +419,22 @@ int biogpt_hip_attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, i
 int biogpt_hip_attn_prefix_bench(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
                                  const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps,
                                  float *us_out /* [reps] */);
+/* The planner of attn_runs_kernel: the N packed column states of a pass (seq_states [N][8] words, col_mode 1) walked greedily into runs of up to eight
+ * consecutive columns whose first R visible rows are the same rows of one slot S.  runs_out [N][4]: c0, n, R, S.  Returns the number of runs, or -1. */
+int biogpt_hip_attn_runs_plan(const int32_t *seq_states, int32_t N, int32_t *runs_out /* [N][4]: c0, n, R, S */);
+/* One attn_runs_kernel<8> launch over caller-supplied inputs through the engine's launch helper (head size 64, one layer, P <= 1024): q [N][H * 64];
+ * k_slots / v_slots [n_slots][H][P][64]; seq_states [N][8] packed column states (slot seq_id, t_vis keys, the first pad[0] of them in slot pad[1]); t_max the
+ * furthest visible key count.  runs [n_runs][4] or NULL (the planner's table): a caller's table is validated before anything is allocated -- every column in
+ * exactly one run, n <= 8, the first R rows of every member really in S and its other rows in its own slot -- and refused with -1 otherwise.  The outputs are
+ * returned whole as biogpt_hip_attn_device returns them (N rounded up to 16 rows plus a guard row, preset to 0xff; q8 1 / 2: the Q8_0 / Q8_1 blocks too).
+ * launched [8] (may be NULL): kernel (16), threads, grid x, grid y, LDS bytes, t_cap, runs, 0.  For tests of the kernel itself. */
+int biogpt_hip_attn_runs_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots,
+                                const float *v_slots, const int32_t *seq_states, const int32_t *runs /* may be NULL */, int32_t n_runs, int32_t q8, float *out,
+                                int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched);
+/* The same, then reps in [1, 10000] further launches on the same inputs; us_out[i]: microseconds around launch i alone.  For tools/prefix_batch_bench.py. */
+int biogpt_hip_attn_runs_bench(int device, int32_t H, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots,
+                               const float *v_slots, const int32_t *seq_states, const int32_t *runs /* may be NULL */, int32_t n_runs, int32_t q8, float *out,
+                               int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched, int32_t reps, float *us_out /* [reps] */);
 /* biogpt_hip_beam_rows_device with given = 1 over rows of which any number of values may be -inf, as a trie step leaves them (entries at -inf become
  * candidates, lower id first, where fewer than 2 * n_beams finite ones are left).  For tests of the kernel itself. */
 int biogpt_hip_beam_rows_masked_device(int device, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_beams, const float *run_score,
@@ -629,6 +645,32 @@ int biogpt_hip_score_continuations(biogpt_hip_ctx *ctx, const int32_t *prefix, i
                                    const int32_t *conts /* concatenated */, const int32_t *cont_lens, int32_t n_conts,
                                    float *logprob_out, int32_t *argmax_out /* may be NULL */, float *logit_out /* may be NULL */,
                                    double *seconds_out /* may be NULL */);
+
+/* Several (prefix, continuations) groups in ONE call (a dataset of multiple-choice / yes-no-maybe / reranking examples): prefixes = the n_groups prefixes
+ * concatenated, prefix_lens[n_groups] their lengths; conts = all continuations concatenated group by group, n_conts[g] how many group g has, cont_lens
+ * [sum n_conts] their lengths.  The outputs use the flat layout of conts; group g's are biogpt_hip_score_continuations(prefix_g, conts_g).  Each prefix's
+ * rows [0, n_prefix_g - 1) are evaluated once, without an lm_head, into a K / V slot of their own; every continuation owns a slot, re-evaluates its group's
+ * last prefix token and reads the prefix rows in place.  One call holds at most 512 slots: n_groups + sum(n_conts) <= 512.  All prefix columns of all
+ * groups, then all continuation columns in flat order, travel in one stream of passes of up to BIOGPT_HIP_PROMPT_COLS columns.
+ * BIOGPT_HIP_RUN_ATTN chooses the attention kernel of these passes (no other call looks at it): 0 the per-column kernel of biogpt_hip_score_continuations,
+ * 1 attn_runs_kernel (up to eight neighbouring columns that see the same first rows load them once) in every pass of up to 1024 keys, -1 (default) the
+ * latter where it was measured faster, by the size of the pass.  What is promised:
+ *   RUN_ATTN=0  every group's numbers are those of biogpt_hip_score_continuations(prefix_g, conts_g), bit for bit;
+ *   RUN_ATTN=1  a group's numbers do not depend on the other groups, their order or the pass size, bit for bit (they are the per-column kernel's wherever
+ *               the double sums of the attention are not within a rounding of a float32 boundary);
+ *   default     a pass's kernel depends on its size, so a group's company can move an output by one float32 ulp of one attention output on such a row.
+ * Argument errors (null pointers, n_groups < 1, an n_conts[g] < 1, more than 512 slots, a prefix_lens[g] < 1, an empty continuation, a token id out of
+ * range, n_prefix_g + cont_len > n_positions, a model without the fast chain) return -1 before any HIP call and name the group and the field; a failed
+ * allocation returns -2 and names the size.  The context's own cache, position and logits row are left alone.  Returns 0 or < 0. */
+int biogpt_hip_score_continuations_batch(biogpt_hip_ctx *ctx,
+        const int32_t *prefixes /* concatenated */, const int32_t *prefix_lens, int32_t n_groups,
+        const int32_t *conts /* concatenated, group-major */, const int32_t *cont_lens /* [sum n_conts] */,
+        const int32_t *n_conts /* [n_groups] */,
+        float *logprob_out, int32_t *argmax_out /* may be NULL */, float *logit_out /* may be NULL */,
+        double *seconds_out /* may be NULL */);
+/* The last successful biogpt_hip_score_continuations_batch of the context: {prefix columns, continuation columns, passes, passes whose attention ran on
+ * attn_runs_kernel}.  Returns 0, or -1 for a null argument. */
+int biogpt_hip_prefix_batch_stats(const biogpt_hip_ctx *ctx, int32_t out[4]);
 
 /* ---- generation behind a shared prefix: one long few-shot or instruction block in front of many short inputs, or N samples of one long prompt ----
  * Sequence s is prefix ++ suffix_s (suffixes = the suffixes concatenated, suffix_lens their lengths; a suffix may be empty).  The ids -- for sampling
