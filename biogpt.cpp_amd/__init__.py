@@ -645,6 +645,8 @@ SYMBOLS = [
     ("biogpt_hip_bench_stream", C.c_int, [_P, C.c_int32, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("biogpt_hip_quantize_file", C.c_int, [C.c_char_p, C.c_char_p, C.c_int32]),
     ("biogpt_hip_quantize_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int64, C.c_int64, _P]),
+    ("biogpt_hip_ln_q8_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("biogpt_hip_q8_forms_device", C.c_int, [C.c_int, _P]),
     ("biogpt_hip_write_synthetic", C.c_int, [C.c_char_p, C.POINTER(HParams), C.c_uint64]),
     # text <-> ids (host-only)
     ("biogpt_hip_vocab_load", _P, [C.c_char_p]),
@@ -705,6 +707,39 @@ def quantize_rows_device(rows, type_id, device=0):
     if lib().biogpt_hip_quantize_rows_device(int(device), int(type_id), a.ctypes.data, nrows, k, out.ctypes.data) != 0:
         raise BiogptError(_err())
     return out
+
+
+def ln_q8_device(x, ln_w=None, ln_b=None, q81=False, want_sum=True, eps=1e-5, blocks=False, device=0):
+    """The decode launches' LayerNorm + Q8 stage alone (biogpt_hip_ln_q8_device): x [n, 1024] with ln_w / ln_b [1024] or [n, 1024]; blocks=True: the launches'
+    activation quantizer on x [n, 32].  Returns (codes int8 [n, k], d float32 [n, k / 32], s uint32 [n, k / 32])."""
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    n, k = a.shape
+    if k != (32 if blocks else 1024):
+        raise ValueError("rows of %d values" % (32 if blocks else 1024))
+    w = b = None
+    if not blocks:
+        w, b = np.ascontiguousarray(ln_w, dtype=np.float32), np.ascontiguousarray(ln_b, dtype=np.float32)
+        if w.shape != b.shape or w.shape not in ((1024,), (n, 1024)):
+            raise ValueError("ln_w and ln_b: [1024] or [n, 1024]")
+    q, d, s = np.empty((n, k), np.int8), np.empty((n, k // 32), np.float32), np.empty((n, k // 32), np.uint32)
+    if lib().biogpt_hip_ln_q8_device(int(device), 1 if blocks else 0, a.ctypes.data, n, None if blocks else w.ctypes.data, None if blocks else b.ctypes.data,
+                                     0 if blocks else int(w.ndim == 2), float(eps), int(bool(q81)), int(bool(want_sum)), q.ctypes.data, d.ctypes.data, s.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return q, d, s
+
+
+Q8_FORMS_CHECKS = ("ln_inv_std_short in range", "ln_inv_std every pattern", "q8_round |x| <= 2^22", "q8_round every other pattern", "q8_scales_short in range",
+                   "q8_scales every pattern")
+
+
+def q8_forms_device(device=0):
+    """All 2^32 float bit patterns through the short forms of the decode launches' LayerNorm + Q8 arithmetic (biogpt_hip_q8_forms_device): a dict per check of
+    Q8_FORMS_CHECKS: tested, mismatches, first (the lowest mismatching pattern, None without one)."""
+    out = np.zeros(18, np.uint64)
+    if lib().biogpt_hip_q8_forms_device(int(device), out.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return {name: {"tested": int(out[c]), "mismatches": int(out[6 + c]), "first": None if int(out[12 + c]) == 2 ** 64 - 1 else int(out[12 + c])}
+            for c, name in enumerate(Q8_FORMS_CHECKS)}
 
 
 CHAIN_OPS = {"LNQ": 0, "QKV": 1, "OPROJ": 2, "FC1_LN": 3, "FC1_Q8": 4, "FC2": 5, "LMHEAD": 6}

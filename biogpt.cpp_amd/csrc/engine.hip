@@ -34,6 +34,7 @@
 #include "kernels_fast.hip.h"
 #include "kernels_runs.hip.h"
 #include "kernels_decode.hip.h"
+#include "kernels_q8probe.hip.h"
 #include "kernels_fdecode.hip.h"
 #include "kernels_lmhead.hip.h"
 #include "kernels_sweep.hip.h"

@@ -918,6 +918,65 @@ int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, 
     return 0;
 }
 
+// The decode launches' LayerNorm + Q8 stage (mode 0: ln4_q8_1024, one workgroup of 512 threads per row of 1024) or their activation quantizer (mode 1:
+// q8_block32, n_rows blocks of 32 values) alone, on rows held in host memory.  Outputs are preset to 0xff bytes: what the stage does not write stays so.
+int biogpt_hip_ln_q8_device(int device, int32_t mode, const float *x, int32_t n_rows, const float *ln_w, const float *ln_b, int32_t wb_per_row, float eps,
+                            int32_t q81, int32_t want_sum, int8_t *q_out, float *d_out, uint32_t *s_out) {
+    clear_error();
+    if (!x || !q_out || !d_out || !s_out) BG_FAIL(-1, "null argument");
+    if (mode != 0 && mode != 1) BG_FAIL(-1, "mode must be 0 (LayerNorm + Q8 of rows of 1024) or 1 (Q8 of blocks of 32)");
+    if (n_rows < 1 || n_rows > (1 << 16)) BG_FAIL(-1, "n_rows must be in [1, %d]", 1 << 16);
+    if (mode == 0 && (!ln_w || !ln_b)) BG_FAIL(-1, "mode 0 needs ln_w and ln_b");
+    if (mode == 0 && q81 && !want_sum) BG_FAIL(-1, "the Q8_1 form always writes its block sums");
+    if (!select_device(device)) return -1;
+    const size_t k = mode == 0 ? 1024 : 32, nb = k / 32, n_wb = mode == 0 ? (wb_per_row ? (size_t)n_rows : 1) : 0;
+    ByteLayout l;      // [x | gain | bias | codes | scales | sums]
+    const size_t o_x = l.part((size_t)n_rows * k * 4), o_w = l.part(n_wb * 1024 * 4), o_b = l.part(n_wb * 1024 * 4);
+    const size_t o_q = l.part((size_t)n_rows * k), o_d = l.part((size_t)n_rows * nb * 4), o_s = l.part((size_t)n_rows * nb * 4);
+    DeviceBytes dv;
+    if (!dv.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemset(dv.p + o_q, 0xff, l.bytes() - o_q));
+    HIP_TRY(-2, hipMemcpy(dv.p + o_x, x, (size_t)n_rows * k * 4, hipMemcpyHostToDevice));
+    if (mode == 0) {
+        HIP_TRY(-2, hipMemcpy(dv.p + o_w, ln_w, n_wb * 1024 * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(dv.p + o_b, ln_b, n_wb * 1024 * 4, hipMemcpyHostToDevice));
+        const int stride = wb_per_row ? 1024 : 0;
+        auto kern = q81 ? bgk::ln_q8_probe_kernel<true, true> : (want_sum ? bgk::ln_q8_probe_kernel<false, true> : bgk::ln_q8_probe_kernel<false, false>);
+        hipLaunchKernelGGL(kern, dim3(n_rows), dim3(512), 0, 0, dv.at<const float>(o_x), dv.at<const float>(o_w), dv.at<const float>(o_b), stride, eps,
+                           dv.at<uint32_t>(o_q), dv.at<float>(o_d), dv.at<uint32_t>(o_s));
+    } else {
+        hipLaunchKernelGGL(bgk::q8_block32_probe_kernel, dim3((n_rows + 1) / 2), dim3(64), 0, 0, dv.at<const float>(o_x), (int)n_rows, (int)(q81 != 0), (int)(want_sum != 0),
+                           dv.at<int8_t>(o_q), dv.at<float>(o_d), dv.at<uint32_t>(o_s));
+    }
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(q_out, dv.p + o_q, (size_t)n_rows * k, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(d_out, dv.p + o_d, (size_t)n_rows * nb * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(s_out, dv.p + o_s, (size_t)n_rows * nb * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// q8_round, ln_inv_std and q8_scales (kernels_decode.hip.h) against the expressions they stand for, over all 2^32 float bit patterns in one launch.
+// out[18]: per check c of bgk::Q8F_CHECKS (kernels_q8probe.hip.h lists them) out[c] patterns tested, out[6 + c] mismatches, out[12 + c] the lowest
+// mismatching pattern (~0: none).
+int biogpt_hip_q8_forms_device(int device, uint64_t *out) {
+    clear_error();
+    if (!out) BG_FAIL(-1, "null argument");
+    if (!select_device(device)) return -1;
+    constexpr int N = bgk::Q8F_CHECKS;
+    unsigned long long h[3 * N];
+    for (int i = 0; i < 3 * N; i++) h[i] = i < 2 * N ? 0ull : ~0ull;
+    DeviceBytes dv;
+    if (!dv.alloc(sizeof(h))) return -2;
+    HIP_TRY(-2, hipMemcpy(dv.p, h, sizeof(h), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(bgk::q8_forms_kernel, dim3(bgk::Q8F_BLOCKS), dim3(bgk::Q8F_THREADS), 0, 0, dv.at<unsigned long long>(0));
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(h, dv.p, sizeof(h), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 3 * N; i++) out[i] = (uint64_t)h[i];
+    return 0;
+}
+
 
 // lookup_draft_kernel over texts held in host memory (tests of the kernel itself): sequence s has the text texts[..] of text_lens[s] tokens (corpus ++ prompt ++
 // its n_gen[s] generated tokens, the last one its current token at position n_past[s]).  draft_out [n_seqs][16] (-1 behind the draft), d_out [n_seqs],

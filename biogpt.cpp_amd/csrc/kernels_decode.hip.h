@@ -80,17 +80,55 @@ __device__ __forceinline__ int group32_sum(int v) {
 // MI355X (tools/microbench12.hip -> profiles/microbench12_q8_divisions_r2.txt): d' = fma(fma(-127, q, a), C, q) with q = a * C,
 // C = RN(1 / 127), matches for every finite a >= 0 (2,139,095,040 values); id' = fma(fma(-d, r, 1), r, r) with r = v_rcp_f32(d)
 // matches for 2^-100 <= a < 2^100 (it differs for a < 1.5e-36).  Outside that range the divisions themselves are used.
+//
+// The range tests are WAVE-UNIFORM (q8_scales, ln_inv_std): one integer compare of the bits (a float in [lo, hi) with 0 < lo < hi has its bits in
+// [bits(lo), bits(hi)); negatives, -0 and NaN fall outside as unsigned) and, behind the short form, a scalar branch to the general expression, taken by the whole wave when
+// any of its lanes is outside -- the general expression is right everywhere, so which lanes take it changes no result, and the short path pays no
+// exec-mask save / restore around code that normally never runs.
+__device__ __forceinline__ bool bits_in_range(float v, uint32_t lo_bits, uint32_t hi_bits) { return __float_as_uint(v) - lo_bits < hi_bits - lo_bits; }
+__device__ __forceinline__ bool wave_any(bool pred) { return __builtin_amdgcn_ballot_w64(pred) != 0ull; }
+
+__device__ __forceinline__ bool q8_scales_in_range(float amax) { return bits_in_range(amax, 0x0D800000u /* 2^-100 */, 0x71800000u /* 2^100 */); }
+__device__ __forceinline__ void q8_scales_short(float amax, float &d, float &id) {
+    const float C = 1.0f / 127.0f;
+    const float q = __fmul_rn(amax, C);
+    d = __fmaf_rn(__fmaf_rn(-127.0f, q, amax), C, q);
+    const float r = __builtin_amdgcn_rcpf(d);
+    id = __fmaf_rn(__fmaf_rn(-d, r, 1.0f), r, r);
+}
+__device__ __forceinline__ void q8_scales_general(float amax, float &d, float &id) {
+    d = amax / 127.0f;
+    id = (d != 0.0f) ? 1.0f / d : 0.0f;
+}
 __device__ __forceinline__ void q8_scales(float amax, float &d, float &id) {
-    if (amax >= 0x1p-100f && amax < 0x1p100f) {
-        const float C = 1.0f / 127.0f;
-        const float q = __fmul_rn(amax, C);
-        d = __fmaf_rn(__fmaf_rn(-127.0f, q, amax), C, q);
-        const float r = __builtin_amdgcn_rcpf(d);
-        id = __fmaf_rn(__fmaf_rn(-d, r, 1.0f), r, r);
-    } else {
-        d = amax / 127.0f;
-        id = (d != 0.0f) ? 1.0f / d : 0.0f;
-    }
+    q8_scales_short(amax, d, id);
+    if (__builtin_expect(wave_any(!q8_scales_in_range(amax)), 0)) q8_scales_general(amax, d, id);
+}
+
+// (int)roundf(x) of a Q8 quotient (half away from zero) in three instructions: the addend is the float below 0.5 (0x3EFFFFFF), the sum is rounded to
+// nearest-even and the conversion truncates.  Equal to (int)roundf(x) for every float: x + 0.5 would round 0.49999997 up to 1; with this addend a
+// sum below k + 1 never rounds up to it unless x >= k + 0.5, and from 2^23 on the sum is x itself.  Held to (int)roundf(x) over all 2^32 bit patterns
+// on the device (biogpt_hip_q8_forms_device, tests/test_gpu_ln_q8_forms.py) and over |x| < 2^8 in float32 numpy (tests/test_q8_round.py).
+__device__ __forceinline__ int q8_round(float x) { return (int)__fadd_rn(x, copysignf(0.49999997f, x)); }
+
+// LayerNorm's scale 1.0f / sqrtf(v), v = variance + eps (>= 1e-5 in every model), without the library forms' general cases: the hardware square
+// root with the +-1 ulp correction that makes it the correctly rounded one (the compiler's own sequence, less its scaling of inputs below 2^-96 and
+// its test for 0 / inf), then the reciprocal as q8_scales takes it.  Equal to the IEEE expression BIT FOR BIT for every v in [2^-20, 2^100)
+// (exhaustive on the device, as above); outside that range, and for NaN, the expression itself.
+__device__ __forceinline__ bool ln_inv_std_in_range(float v) { return bits_in_range(v, 0x35800000u /* 2^-20 */, 0x71800000u /* 2^100 */); }
+__device__ __forceinline__ float ln_inv_std_short(float v) {
+    float s = __builtin_amdgcn_sqrtf(v);
+    const float s_dn = __uint_as_float(__float_as_uint(s) - 1u), s_up = __uint_as_float(__float_as_uint(s) + 1u);
+    const float e_dn = __fmaf_rn(-s_dn, s, v), e_up = __fmaf_rn(-s_up, s, v);
+    s = (e_dn <= 0.0f) ? s_dn : s;
+    s = (e_up > 0.0f) ? s_up : s;
+    const float r = __builtin_amdgcn_rcpf(s);
+    return __fmaf_rn(__fmaf_rn(-s, r, 1.0f), r, r);
+}
+__device__ __forceinline__ float ln_inv_std(float v) {
+    float r = ln_inv_std_short(v);
+    if (__builtin_expect(wave_any(!ln_inv_std_in_range(v)), 0)) r = 1.0f / sqrtf(v);
+    return r;
 }
 
 // LayerNorm (ggml_norm + affine, double statistics) and Q8_0 / Q8_1 quantization of ONE 1024-element column inside a
@@ -141,7 +179,7 @@ __device__ __forceinline__ void ln4_q8_1024(float4 v, float4 lw, float4 lb, floa
     LN_STAMP(12);
     if (worker) {
         const float var = (float)(((s_red[4] + s_red[5]) + (s_red[6] + s_red[7])) * inv_k);
-        const float scale = 1.0f / sqrtf(__fadd_rn(var, eps));
+        const float scale = ln_inv_std(__fadd_rn(var, eps));
         a = __fadd_rn(__fmul_rn(lw.x, __fmul_rn(a, scale)), lb.x);
         b = __fadd_rn(__fmul_rn(lw.y, __fmul_rn(b, scale)), lb.y);
         c = __fadd_rn(__fmul_rn(lw.z, __fmul_rn(c, scale)), lb.z);
@@ -151,8 +189,8 @@ __device__ __forceinline__ void ln4_q8_1024(float4 v, float4 lw, float4 lb, floa
         const float amax = group8_max(fmaxf(fmaxf(fabsf(a), fabsf(b)), fmaxf(fabsf(c), fabsf(d4))));
         float d, id;
         q8_scales(amax, d, id);
-        const int q0 = (int)roundf(__fmul_rn(a, id)), q1 = (int)roundf(__fmul_rn(b, id));
-        const int q2 = (int)roundf(__fmul_rn(c, id)), q3 = (int)roundf(__fmul_rn(d4, id));
+        const int q0 = q8_round(__fmul_rn(a, id)), q1 = q8_round(__fmul_rn(b, id));
+        const int q2 = q8_round(__fmul_rn(c, id)), q3 = q8_round(__fmul_rn(d4, id));
         s_xq[tid] = (uint32_t)(q0 & 0xFF) | ((uint32_t)(q1 & 0xFF) << 8) | ((uint32_t)(q2 & 0xFF) << 16) | ((uint32_t)(q3 & 0xFF) << 24);
         if constexpr (Q81 || SUM) {
             const int isum = group8_sum(q0 + q1 + q2 + q3);
@@ -188,7 +226,7 @@ __device__ __forceinline__ void q8_block32(float v, bool q81, int8_t &q_out, flo
     const float amax = group32_max(fabsf(v));
     float d, id;
     q8_scales(amax, d, id);
-    const int q = (int)roundf(__fmul_rn(v, id));
+    const int q = q8_round(__fmul_rn(v, id));
     q_out = (int8_t)q;
     if (!q81 && !want_sum) { d_out = h2f(f2h(d)); s_out = 0u; return; }      // the consumer's units are settled signed (kernels.hip.h): no block sum
     const int isum = group32_sum(q);

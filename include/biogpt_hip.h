@@ -901,6 +901,22 @@ int biogpt_hip_quantize_file(const char *fname_in, const char *fname_out, int32_
  * memory, byte-identical to biogpt_hip_quantize_file's host encoder. */
 int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, int64_t nrows, int64_t k, uint8_t *dst);
 
+/* The LayerNorm + Q8 stage of the single-token decode launches, alone (tests of the stage itself; no model).
+ * mode 0: n_rows rows of 1024 f32 values -> ggml_norm + gain / bias (ln_w, ln_b: 1024 values, or n_rows x 1024 with wb_per_row != 0), eps as given, then
+ *   quantize_row_q8_0 (q81 = 0) or q8_1 (q81 = 1): q_out n_rows x 1024 codes, d_out n_rows x 32 block scales (q8_0: rounded through f16), s_out n_rows x 32
+ *   (q8_1: the bits of the float d * sum; q8_0 with want_sum: the integer block sums; q8_0 without: not written, left 0xffffffff).
+ * mode 1: the launches' activation quantizer on n_rows blocks of 32 values (ln_w, ln_b, eps unused): q_out n_rows x 32, d_out and s_out n_rows (q8_0 without
+ *   want_sum: s = 0).
+ * One workgroup of 512 threads per row (mode 0), thread t holding elements 4t .. 4t+3, as the pipelined launches run the stage. */
+int biogpt_hip_ln_q8_device(int device, int32_t mode, const float *x, int32_t n_rows, const float *ln_w, const float *ln_b, int32_t wb_per_row, float eps,
+                            int32_t q81, int32_t want_sum, int8_t *q_out, float *d_out, uint32_t *s_out);
+
+/* The short arithmetic forms of that stage against the expressions they stand for, over all 2^32 float bit patterns in one launch.  out[18] = tested[6],
+ * mismatches[6], lowest mismatching pattern[6] (~0: none) for the checks: 0 the short 1 / sqrtf(v) inside its guarded range, 1 the guarded function on every
+ * pattern, 2 the Q8 rounding for |x| <= 2^22, 3 for every other pattern, 4 the short d = a / 127 and id = 1 / d inside their guarded range, 5 the guarded
+ * function on every pattern. */
+int biogpt_hip_q8_forms_device(int device, uint64_t *out);
+
 /* Write a synthetic seeded BioGPT model: F32 (ftype 0) or F16 (ftype 1) file in the
  * reference's format, weights ~ N(0, 0.02^2), LayerNorm gains 1 + N(0, 0.02^2), biases N(0, 0.02^2),
  * embed_tokens row 1 zero; n_merges merge records are written (40000 keeps the reference's
