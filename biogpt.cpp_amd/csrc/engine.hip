@@ -2458,19 +2458,33 @@ static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
 
 // One pass of packed columns (pack_column_passes, pack_continuation_passes): the column states go up to ctx->cols (grown to the pass), then
 // pass(n_cols, t_max, flat0) enqueues the pass; afterwards the host vector is empty and flat0 / pass_tmax stand at the next pass.
+// tail (or null): words that go up behind the column states in the same copy, zero-padded to whole SeqStates -- at ctx->cols + n_cols while the pass runs
+// (the run table of a pass, 16 bytes per run: pack_continuation_passes).
 static bool flush_columns(biogpt_hip_ctx *ctx, std::vector<bgk::SeqState> &cols, int &pass_tmax, size_t &flat0,
-                          const std::function<bool(int, int, size_t)> &pass) {
+                          const std::function<bool(int, int, size_t)> &pass, const std::vector<int32_t> *tail = nullptr) {
     if (cols.empty()) return true;
+    const size_t n = cols.size();
+    if (tail && !tail->empty()) {
+        static_assert(sizeof(bgk::SeqState) == 32, "a column state holds two table rows");
+        cols.resize(n + (tail->size() * 4 + sizeof(bgk::SeqState) - 1) / sizeof(bgk::SeqState));      // (new states are all zero)
+        std::memcpy(static_cast<void *>(cols.data() + n), tail->data(), tail->size() * 4);
+    }
     if (cols.size() > ctx->cols_cap) {
         if (ctx->cols) (void)hipFree(ctx->cols);
         ctx->cols = nullptr; ctx->cols_cap = 0;
-        HIP_TRY(false, hipMalloc(&ctx->cols, sizeof(bgk::SeqState) * cols.size()));
+        if (!tail) {
+            HIP_TRY(false, hipMalloc(&ctx->cols, sizeof(bgk::SeqState) * cols.size()));
+        } else if (hipMalloc(&ctx->cols, sizeof(bgk::SeqState) * cols.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->cols = nullptr;
+            BG_FAIL(false, "out of device memory: the %zu-byte column states of a pass could not be allocated", sizeof(bgk::SeqState) * cols.size());
+        }
         ctx->cols_cap = cols.size();
     }
     HIP_TRY(false, hipMemcpyAsync(ctx->cols, cols.data(), sizeof(bgk::SeqState) * cols.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(false, hipStreamSynchronize(ctx->stream));   // the host vector is reused for the next pass
-    if (!pass((int)cols.size(), pass_tmax, flat0)) return false;
-    flat0 += cols.size();
+    if (!pass((int)n, pass_tmax, flat0)) return false;
+    flat0 += n;
     cols.clear();
     pass_tmax = 0;
     return true;
@@ -2483,7 +2497,7 @@ static bool flush_columns(biogpt_hip_ctx *ctx, std::vector<bgk::SeqState> &cols,
 // (flat0 = flat index of its first token).  Sequence s fills the K / V cache slot slot0 + s * slot_stride.  shared.n > 0: every sequence stands behind
 // shared.n rows that lie in slot shared.slot (a multiple of n_batch, so the chunks are those of the whole sequence): its first token has position shared.n
 // and its columns read those rows in place (SeqState::pad[0] / pad[1]; the pass is ForwardPass::packed_continuations).
-// slots (or null): sequence s fills slot slots[s] instead (biogpt_hip_generate_queue refills the columns that have finished).
+// slots (or null): sequence s fills slot slots[s] instead (run_queue_call refills the units that have finished).
 struct SharedRows { int n = 0, slot = 0; };
 static bool pack_column_passes(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int n_seqs, int n_batch,
                                const std::function<bool(int, int, size_t)> &pass, int slot_stride = 1, int slot0 = 0, SharedRows shared = SharedRows{},
@@ -3122,48 +3136,72 @@ int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32
     return with_xpipe_retry(ctx, 0, [&] { return score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out); });
 }
 
-// ---- many continuations of one prefix: the prefix once, read in place by every continuation's columns ------------------------------------
-// The prefix rows [0, n_prefix - 1) go into slot 0 of the per-sequence caches as the prompt columns of generate_greedy_batch do (t_vis = position + 1,
-// no lm_head: none of their logits are wanted).  Continuation c owns slot 1 + c; its columns are the LAST prefix token at position n_prefix - 1
-// (every continuation re-evaluates it, as the samples of generate_sample do: one target per row) and then its own tokens but the last.  A
-// column's attention reads rows [0, n_prefix - 1) from slot 0 and the rest from its own slot (attn_fast_kernel<.., SHARED>): no K / V row is
-// copied.  Prefix columns and continuation columns travel in ONE stream of passes of up to BIOGPT_HIP_PROMPT_COLS columns, the prefix first: a
-// short call is one pass, and a continuation column may share a pass with the prefix columns it reads (the q/k/v launch of a layer has written
-// every column's row before its attention launch starts, as for the columns of one sequence).  pass(n_cols, t_max, flat0, n_pre): the first n_pre
-// columns of the pass are prefix columns; the others follow the flat order of `conts`, so their flat row (from flat0) is the flat index of their TARGET.
-static bool pack_continuation_passes(biogpt_hip_ctx *ctx, const int32_t *prefix, int n_prefix, const int32_t *conts, const int32_t *cont_lens, int n_conts,
-                                     const std::function<bool(int, int, size_t, int)> &pass) {
+// ---- continuations of shared prefixes: each prefix once, read in place by the columns of its continuations -----------------------------------
+// Group g is a prefix and n_conts[g] continuations of it; biogpt_hip_score_continuations is one group, biogpt_hip_score_continuations_batch several.  The
+// prefix rows [0, n_prefix_g - 1) go into slot g of the per-sequence caches as the prompt columns of generate_greedy_batch do (t_vis = position + 1, no
+// lm_head: none of their logits are wanted).  Continuation f (flat index over all groups) owns slot n_groups + f; its columns are the LAST token of its
+// group's prefix at position n_prefix_g - 1 (every continuation re-evaluates it, as the samples of generate_sample do: one target per row) and then its
+// own tokens but the last.  A column's attention reads rows [0, n_prefix_g - 1) from slot g and the rest from its own slot (SeqState::pad[0] / pad[1];
+// attn_fast_kernel<.., SHARED>): no K / V row is copied.  The columns travel in ONE stream of passes of up to BIOGPT_HIP_PROMPT_COLS columns: every prefix
+// column of every group first, then every continuation column in the flat order of `conts` -- so pure prefix passes, at most one mixed pass, then scored
+// passes, each a ForwardPass::packed_continuations.  A short call is one pass, and a continuation column may share a pass with the prefix columns it reads
+// (the q/k/v launch of a layer has written every column's row before its attention launch starts, as for the columns of one sequence).  The continuation
+// columns of a pass have their log-probabilities taken behind it (enqueue_logprob): their flat row is the flat index of their TARGET, `total` rows in all.
+// The packer builds the column states, uploads them (flush_columns) and enqueues each pass.  The caller supplies its checked arguments and, if it wants
+// attn_runs_kernel in some passes, runs_of(cols, t_max, runs): it fills `runs` with the pass's run table (attn_runs_plan) and returns the number of runs,
+// or 0 for the existing attention; the table then goes up behind the column states in the same copy.  Without runs_of no pass has a table.
+using RunsOf = std::function<int(const std::vector<bgk::SeqState> &, int, std::vector<int32_t> &)>;
+static bool pack_continuation_passes(biogpt_hip_ctx *ctx, const int32_t *prefixes, const int32_t *prefix_lens, int n_groups, const int32_t *conts,
+                                     const int32_t *cont_lens, const int32_t *n_conts, size_t total, const RunsOf &runs_of = nullptr) {
     const size_t max_cols = (size_t)std::min(std::max(1, ctx->opt.prompt_cols), hp_cols(ctx));
     std::vector<bgk::SeqState> cols;
+    std::vector<int32_t> runs;
     int pass_tmax = 0, n_pre = 0;
     size_t flat0 = 0;
     auto flush = [&]() -> bool {
+        if (cols.empty()) return true;
+        const int pre = n_pre, n_runs = runs_of ? runs_of(cols, pass_tmax, runs) : 0;
+        runs.resize(4 * (size_t)n_runs);
         size_t at = flat0;
-        const int pre = n_pre;
-        if (!flush_columns(ctx, cols, pass_tmax, at, [&](int n_cols, int t_max, size_t f) { return pass(n_cols, t_max, f, pre); })) return false;
+        if (!flush_columns(ctx, cols, pass_tmax, at, [&](int n_cols, int t_max, size_t f) {
+                ForwardPass fp = ForwardPass::packed_continuations(n_cols, t_max, pre);
+                if (n_runs) { fp.runs = reinterpret_cast<const int32_t *>(ctx->cols + n_cols); fp.n_runs = n_runs; }
+                return enqueue_forward(ctx, fp) && (pre == n_cols || enqueue_logprob(ctx, n_cols - pre, f, total));
+            }, runs_of ? &runs : nullptr))
+            return false;
         flat0 = at - (size_t)pre;      // prefix columns have no flat row
         n_pre = 0;
         return true;
     };
-    for (int i = 0; i + 1 < n_prefix; i++) {
-        if (cols.size() == max_cols && !flush()) return false;
-        bgk::SeqState cst{};
-        cst.n_past = i; cst.token = prefix[i]; cst.seq_id = 0; cst.t_vis = i + 1;      // pad[0] = 0: every row its own
-        cols.push_back(cst);
-        n_pre++;
-        pass_tmax = std::max(pass_tmax, i + 1);
-    }
-    size_t off = 0;
-    for (int c = 0; c < n_conts; c++) {
-        for (int i = 0; i < cont_lens[c]; i++) {
+    size_t pre_off = 0;
+    for (int g = 0; g < n_groups; g++) {
+        for (int i = 0; i + 1 < prefix_lens[g]; i++) {
             if (cols.size() == max_cols && !flush()) return false;
             bgk::SeqState cst{};
-            cst.n_past = n_prefix - 1 + i; cst.token = i == 0 ? prefix[n_prefix - 1] : conts[off + (size_t)(i - 1)]; cst.seq_id = 1 + c; cst.t_vis = n_prefix + i;
-            cst.pad[0] = n_prefix - 1; cst.pad[1] = 0;      // rows [0, n_prefix - 1) lie in slot 0
+            cst.n_past = i; cst.token = prefixes[pre_off + (size_t)i]; cst.seq_id = g; cst.t_vis = i + 1;      // pad[0] = 0: every row its own
             cols.push_back(cst);
-            pass_tmax = std::max(pass_tmax, n_prefix + i);
+            n_pre++;
+            pass_tmax = std::max(pass_tmax, i + 1);
         }
-        off += (size_t)cont_lens[c];
+        pre_off += (size_t)prefix_lens[g];
+    }
+    pre_off = 0;
+    size_t off = 0;
+    for (int g = 0, f = 0; g < n_groups; g++) {
+        const int n_prefix = prefix_lens[g];
+        for (int c = 0; c < n_conts[g]; c++, f++) {
+            for (int i = 0; i < cont_lens[f]; i++) {
+                if (cols.size() == max_cols && !flush()) return false;
+                bgk::SeqState cst{};
+                cst.n_past = n_prefix - 1 + i; cst.token = i == 0 ? prefixes[pre_off + (size_t)(n_prefix - 1)] : conts[off + (size_t)(i - 1)];
+                cst.seq_id = n_groups + f; cst.t_vis = n_prefix + i;
+                cst.pad[0] = n_prefix - 1; cst.pad[1] = g;      // rows [0, n_prefix - 1) lie in the group's prefix slot
+                cols.push_back(cst);
+                pass_tmax = std::max(pass_tmax, n_prefix + i);
+            }
+            off += (size_t)cont_lens[f];
+        }
+        pre_off += (size_t)n_prefix;
     }
     return flush();
 }
@@ -3211,11 +3249,7 @@ static int score_continuations_once(biogpt_hip_ctx *ctx, const int32_t *prefix, 
     if (!ensure_logits_rows(ctx, std::min(max_cols, total)) || !score_setup(ctx, conts, cont_lens, n_conts, conts, total)) return -2;
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
     const auto t0 = std::chrono::steady_clock::now();
-    if (!pack_continuation_passes(ctx, prefix, n_prefix, conts, cont_lens, n_conts, [&](int n_cols, int t_max, size_t flat0, int n_pre) {
-            return enqueue_forward(ctx, ForwardPass::packed_continuations(n_cols, t_max, n_pre)) &&
-                   (n_pre == n_cols || enqueue_logprob(ctx, n_cols - n_pre, flat0, total));
-        }))
-        return -2;
+    if (!pack_continuation_passes(ctx, prefix, &n_prefix, 1, conts, cont_lens, &n_conts, total)) return -2;      // one group; never attn_runs_kernel
     const int rc = score_finish(ctx, total, logprob_out, argmax_out, logit_out);
     if (rc == 0 && seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return rc;
@@ -3229,12 +3263,9 @@ int biogpt_hip_score_continuations(biogpt_hip_ctx *ctx, const int32_t *prefix, i
 }
 
 // ---- several (prefix, continuations) groups in one call ----------------------------------------------------------------------------------------
-// Group g is score_continuations(prefix_g, conts_g).  Slot g holds the rows [0, n_prefix_g - 1) of prefix g; continuation f (flat index over all groups)
-// owns slot n_groups + f, re-evaluates the last token of its group's prefix and reads the prefix rows in place (SeqState::pad[0] / pad[1]).  The columns
-// travel in ONE stream of passes of up to BIOGPT_HIP_PROMPT_COLS columns: every prefix column of every group first, then every continuation column in flat
-// order -- so pure prefix passes, at most one mixed pass, then scored passes, each a ForwardPass::packed_continuations.  A continuation column may share a
-// pass with prefix columns it reads, as in the single call.  The attention of a pass is attn_fast_kernel<.., SHARED> as there, or attn_runs_kernel over the
-// runs of attn_runs_plan (BIOGPT_HIP_RUN_ATTN; the table goes up behind the column states in one copy).
+// Group g is score_continuations(prefix_g, conts_g): the columns and passes are pack_continuation_passes' for n_groups groups.  What this call adds per pass
+// is its attention: attn_fast_kernel<.., SHARED> as in the single call, or attn_runs_kernel over the runs of attn_runs_plan (BIOGPT_HIP_RUN_ATTN;
+// run_attn_table decides, the packer sends the table up behind the column states).
 // attn_runs_kernel instead of attn_fast_kernel<.., SHARED> in a pass of this call (BIOGPT_HIP_RUN_ATTN=-1): a pass of RUN_ATTN_MIN_COLS columns or more whose longest
 // shared range (the largest R of its runs) has RUN_ATTN_MIN_SHARED rows or more, and every pass of RUN_ATTN_ANY_SHARED_COLS columns or more.
 // (2026-10-20, tools/prefix_batch_bench.py --ab: the call, 24 layers, the kernel never / always taken, runs / existing.  Passes of 512 columns: 0.63 - 0.64 x behind
@@ -3245,6 +3276,20 @@ int biogpt_hip_score_continuations(biogpt_hip_ctx *ctx, const int32_t *prefix, i
 // measured wins.  Not measured: 133 .. 257 columns; 258 .. 395 columns with ranges shorter than 255 rows; other quantizations than Q4_0.  DESIGN.md 4.7 has the tables.)
 constexpr int RUN_ATTN_MIN_COLS = 258, RUN_ATTN_MIN_SHARED = 255, RUN_ATTN_ANY_SHARED_COLS = 396;
 constexpr int PFXB_MAX_SLOTS = 512;     // each slot is a full F32 KV cache
+// the run table of a pass of `cols` with t_max visible keys -> runs; the number of runs, 0: the pass keeps the existing attention
+static int run_attn_table(const biogpt_hip_ctx *ctx, const std::vector<bgk::SeqState> &cols, int t_max, std::vector<int32_t> &runs) {
+    const int n = (int)cols.size();
+    const int t_cap = attn_decode_t_cap(ctx->hp.n_positions, t_max);
+    int n_runs = 0;
+    if (t_cap <= bgk::RUNS_MAX_KEYS && ctx->opt.run_attn != 0 && (ctx->opt.run_attn == 1 || n >= RUN_ATTN_MIN_COLS)) {
+        runs.resize(4 * (size_t)n);
+        n_runs = attn_runs_plan(cols.data(), n, runs.data());
+        int longest = 0;
+        for (int r = 0; r < n_runs; r++) longest = std::max(longest, runs[4 * (size_t)r + 2]);
+        if (ctx->opt.run_attn < 0 && n < RUN_ATTN_ANY_SHARED_COLS && longest < RUN_ATTN_MIN_SHARED) n_runs = 0;      // the existing attention
+    }
+    return n_runs;
+}
 
 static int score_continuations_batch_once(biogpt_hip_ctx *ctx, const int32_t *prefixes, const int32_t *prefix_lens, int32_t n_groups, const int32_t *conts,
                                           const int32_t *cont_lens, const int32_t *n_conts, float *logprob_out, int32_t *argmax_out, float *logit_out,
@@ -3308,81 +3353,14 @@ static int score_continuations_batch_once(biogpt_hip_ctx *ctx, const int32_t *pr
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
     const auto t0 = std::chrono::steady_clock::now();
 
-    std::vector<bgk::SeqState> cols;
-    std::vector<int32_t> runs, up;
-    int pass_tmax = 0, n_pre = 0, n_passes = 0, n_run_passes = 0;
-    size_t flat0 = 0;
-    auto flush = [&]() -> bool {
-        if (cols.empty()) return true;
-        const int n = (int)cols.size();
-        const int t_cap = attn_decode_t_cap(hp.n_positions, pass_tmax);
-        int n_runs = 0;
-        if (t_cap <= bgk::RUNS_MAX_KEYS && ctx->opt.run_attn != 0 && (ctx->opt.run_attn == 1 || n >= RUN_ATTN_MIN_COLS)) {
-            runs.resize(4 * (size_t)n);
-            n_runs = attn_runs_plan(cols.data(), n, runs.data());
-            int longest = 0;
-            for (int r = 0; r < n_runs; r++) longest = std::max(longest, runs[4 * (size_t)r + 2]);
-            if (ctx->opt.run_attn < 0 && n < RUN_ATTN_ANY_SHARED_COLS && longest < RUN_ATTN_MIN_SHARED) n_runs = 0;      // the existing attention
-        }
-        // the column states and, behind them, the run table: one copy
-        static_assert(sizeof(bgk::SeqState) == 32, "a column state holds two table rows");
-        const size_t need = (size_t)n + ((size_t)n_runs + 1) / 2;
-        if (need > ctx->cols_cap) {
-            if (ctx->cols) (void)hipFree(ctx->cols);
-            ctx->cols = nullptr; ctx->cols_cap = 0;
-            if (hipMalloc(&ctx->cols, sizeof(bgk::SeqState) * need) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx->cols = nullptr;
-                BG_FAIL(false, "out of device memory: the %zu-byte column states of a pass could not be allocated", sizeof(bgk::SeqState) * need);
-            }
-            ctx->cols_cap = need;
-        }
-        up.assign(8 * need, 0);
-        std::memcpy(up.data(), cols.data(), sizeof(bgk::SeqState) * (size_t)n);
-        if (n_runs) std::memcpy(up.data() + 8 * (size_t)n, runs.data(), 16 * (size_t)n_runs);
-        HIP_TRY(false, hipMemcpyAsync(ctx->cols, up.data(), sizeof(bgk::SeqState) * need, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(false, hipStreamSynchronize(ctx->stream));   // the host vector is reused for the next pass
-        ForwardPass fp = ForwardPass::packed_continuations(n, pass_tmax, n_pre);
-        if (n_runs) { fp.runs = reinterpret_cast<const int32_t *>(ctx->cols + n); fp.n_runs = n_runs; }
-        if (!enqueue_forward(ctx, fp) || (n_pre < n && !enqueue_logprob(ctx, n - n_pre, flat0, total))) return false;
-        flat0 += (size_t)(n - n_pre);
-        n_passes++; n_run_passes += n_runs ? 1 : 0;
-        cols.clear();
-        pass_tmax = 0; n_pre = 0;
-        return true;
-    };
-    pre_off = 0;
-    for (int g = 0; g < n_groups; g++) {
-        for (int i = 0; i + 1 < prefix_lens[g]; i++) {
-            if (cols.size() == max_cols && !flush()) return -2;
-            bgk::SeqState cst{};
-            cst.n_past = i; cst.token = prefixes[pre_off + (size_t)i]; cst.seq_id = g; cst.t_vis = i + 1;      // pad[0] = 0: every row its own
-            cols.push_back(cst);
-            n_pre++;
-            pass_tmax = std::max(pass_tmax, i + 1);
-        }
-        pre_off += (size_t)prefix_lens[g];
-    }
-    pre_off = 0;
-    size_t off = 0;
-    cont_at = 0;
-    for (int g = 0; g < n_groups; g++) {
-        const int n_prefix = prefix_lens[g];
-        for (int c = 0; c < n_conts[g]; c++, cont_at++) {
-            for (int i = 0; i < cont_lens[cont_at]; i++) {
-                if (cols.size() == max_cols && !flush()) return -2;
-                bgk::SeqState cst{};
-                cst.n_past = n_prefix - 1 + i; cst.token = i == 0 ? prefixes[pre_off + (size_t)(n_prefix - 1)] : conts[off + (size_t)(i - 1)];
-                cst.seq_id = n_groups + cont_at; cst.t_vis = n_prefix + i;
-                cst.pad[0] = n_prefix - 1; cst.pad[1] = g;      // rows [0, n_prefix - 1) lie in the group's prefix slot
-                cols.push_back(cst);
-                pass_tmax = std::max(pass_tmax, n_prefix + i);
-            }
-            off += (size_t)cont_lens[cont_at];
-        }
-        pre_off += (size_t)n_prefix;
-    }
-    if (!flush()) return -2;
+    int n_passes = 0, n_run_passes = 0;
+    if (!pack_continuation_passes(ctx, prefixes, prefix_lens, n_groups, conts, cont_lens, n_conts, total,
+                                  [&](const std::vector<bgk::SeqState> &cols, int t_max, std::vector<int32_t> &runs) {
+                                      const int n_runs = run_attn_table(ctx, cols, t_max, runs);
+                                      n_passes++; n_run_passes += n_runs ? 1 : 0;
+                                      return n_runs;
+                                  }))
+        return -2;
     const int rc = score_finish(ctx, total, logprob_out, argmax_out, logit_out);
     if (rc != 0) return rc;
     if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -4464,20 +4442,26 @@ int biogpt_hip_generate_lookup(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
     });
 }
 
-// ---- generation over a queue: finished columns are refilled from a queue of requests (kernels_queue.hip.h) -----------------------------------------
-// C = min(max_columns, eligible requests) columns and K / V slots serve any number of requests: a request takes a column when one is free, generates there
-// at its own positions, under its own limit and with its own generator, and leaves the column to the next request when it finishes (EOS or limit).  The
-// schedule counts steps, never time (QueueSchedule; biogpt_hip_queue_plan is the same struct with given lengths):
-//   1. eligible requests (those that may generate a token) are admitted in index order, the first C into columns 0 .. C - 1;
-//   2. steps are enqueued in groups of min(group, the most tokens any running column may still generate);
-//   3. behind each group the header (QueueHdr: finished flags, generated lengths) travels to pinned memory and the host waits for it;
-//   4. every column found finished has its ids copied from its seq_gen row to the caller's row, in stream order, before the column is reused;
-//   5. finished columns are refilled in ascending column order with the pending requests in ascending request order: their prompts go through packed
-//      prompt passes into exactly those slots, one admit launch sets their state, they take part from the next group's first step;
-//   6. the call ends when a header shows no running column and nothing is pending.
-// The host bounds every step's keys itself: a column in use -- running, or finished and not refilled yet (it still attends at its frozen position) -- stands
+// ---- calls over a queue: finished units are refilled from a queue of requests ---------------------------------------------------------------------
+// U = min(the most units the call may use, eligible requests) units serve any number of requests.  A unit is a column with its K / V slot
+// (biogpt_hip_generate_queue, kernels_queue.hip.h) or a group slot of B columns (biogpt_hip_generate_beam_queue, kernels_beam_queue.hip.h): a request takes a
+// unit when one is free, generates there at its own positions and under its own limit, and leaves the unit to the next request when it finishes.  The
+// schedule counts steps, never time (QueueSchedule, whose "columns" are units; biogpt_hip_queue_plan is the same struct with given lengths), and
+// run_queue_call is the one procedure of both modes:
+//   1. eligible requests (those that may generate a token) are admitted in index order, the first U into units 0 .. U - 1;
+//   2. steps are enqueued in groups of min(group, the most steps any running unit may still take);
+//   3. behind each group the mode's header (finished flags, lengths) travels to pinned memory and the host waits for it;
+//   4. every unit found finished has its results copied out by the mode (collect), in stream order, before the unit is reused;
+//   5. finished units are refilled in ascending unit order with the pending requests in ascending request order: their prompts go through packed
+//      prompt passes into exactly those units' (first) slots, the admit list goes up, the mode's launches behind it (enqueue_admit) set their state, and
+//      they take part from the next group's first step;
+//   6. the call ends when a header shows no running unit and nothing is pending.
+// The host bounds every step's keys itself: a unit in use -- running, or finished and not refilled yet (it still attends at its frozen position) -- stands
 // at position len - 1 + min(steps since admission, its limit) at most.  A refilled slot keeps its old rows beyond the new prompt: no decode-step attention
-// kernel lets a column see a key at or beyond its own n_past + 1.  The steps are always the launch chain (plain_steps).
+// kernel lets a column see a key at or beyond its own n_past + 1.  The steps are always the launch chain.
+// A mode supplies (QueueCall): its units, its captured steps, the step itself, the admit record of a request and the launches behind the list, its header,
+// and what happens to a finished unit's results.  Everything else -- the shared argument checks, the clamps, the schedule, capture, the loop, the waits,
+// the timed span and the stats -- is stated once.
 extern "C++" {
 struct QueueSchedule {
     const int32_t *cap;                     // tokens request r may generate at most; 0: it never takes a column
@@ -4559,6 +4543,182 @@ int biogpt_hip_queue_plan_limits(const int32_t *gen_lens, const int32_t *limits,
     return queue_plan_of(gen_lens, limits, n_requests, max_columns, group, admit_step, column, stats);
 }
 
+// A mode checks its own arguments between the shared checks (QueueRequests), describes itself as a QueueCall and hands both to run_queue_call.  The driver
+// delivers every result as it goes, so the mode reads nothing back.
+struct QueueRequests {
+    const int32_t *prompts, *prompt_lens;       // concatenated
+    int n_requests;
+    const int32_t *n_predicts;                  // per request (or null: n_predict for every one)
+    int n_predict, max_columns, group, n_batch;
+    std::vector<size_t> off;                    // set by check_prompts: request r's prompt lies at prompts + off[r]
+    std::vector<int32_t> cap;                   // set by run_queue_call: the tokens request r may generate (main.cpp:82 per request); 0: it never takes a unit
+
+    // Tier one, what can be judged without the model (it fails the same way with no context and no device): check_count, the mode's column counts, check_sizes,
+    // the mode's other parameters, then check_prompts, which ends the tier with the context itself.
+    bool check_count() const { if (n_requests < 1) BG_FAIL(false, "n_requests must be >= 1"); return true; }
+    bool check_sizes() const {
+        if (group < 1 || group > 64) BG_FAIL(false, "group must be in [1, 64]");
+        if (n_batch < 1) BG_FAIL(false, "n_batch must be >= 1");
+        if (n_predict < 0) BG_FAIL(false, "n_predict must be >= 0");
+        for (int r = 0; n_predicts && r < n_requests; r++)
+            if (n_predicts[r] < 0 || n_predicts[r] > n_predict) BG_FAIL(false, "n_predicts[%d] (%d) must be in [0, n_predict = %d]", r, n_predicts[r], n_predict);
+        return true;
+    }
+    bool check_prompts(const biogpt_hip_ctx *ctx) {
+        off.assign((size_t)n_requests + 1, 0);
+        for (int r = 0; r < n_requests; r++) {
+            if (prompt_lens[r] < 1) BG_FAIL(false, "empty prompt (request %d)", r);
+            off[(size_t)r + 1] = off[(size_t)r] + (size_t)prompt_lens[r];
+        }
+        for (int r = 0; r < n_requests; r++)
+            for (int i = 0; i < prompt_lens[r]; i++)
+                if (prompts[off[(size_t)r] + (size_t)i] < 0) BG_FAIL(false, "token id %d (request %d, position %d) out of range", prompts[off[(size_t)r] + (size_t)i], r, i);
+        if (!ctx) BG_FAIL(false, "null context");
+        if (!ctx->ready) BG_FAIL(false, "model has no tensors loaded (empty model): cannot evaluate");
+        return true;
+    }
+    // Tier two, what needs the model's sizes: the mode's parameters, then the prompts.  Tier three, the fast chain, ends this check; what a mode still has to
+    // hold against the model comes behind it.
+    bool check_prompts_model(const biogpt_hip_ctx *ctx, const char *what) const {
+        const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
+        for (int r = 0; r < n_requests; r++) {
+            if (prompt_lens[r] > P) BG_FAIL(false, "prompt_lens[%d] (%d) exceeds n_positions (%d)", r, prompt_lens[r], P);
+            for (int i = 0; i < prompt_lens[r]; i++)
+                if (prompts[off[(size_t)r] + (size_t)i] >= V) BG_FAIL(false, "token id %d (request %d, position %d) out of range [0, %d)", prompts[off[(size_t)r] + (size_t)i], r, i, V);
+        }
+        return check_fast_chain(ctx, what);
+    }
+};
+
+struct QueueCall {
+    int max_units = 0, per_unit = 1;                // units of the schedule, at most; columns of a unit
+    const char *unit = "column", *step_name = "queue step";      // in messages
+    ColumnGraphs *graphs = nullptr;                 // the mode's captured steps, valid for (units, key_b); a step of t_max keys is exec[gset + its bucket]
+    int key_b = 0, gset = 0;
+    // what the driver writes as it goes (each may be null): the step count at which a request was admitted and its unit, the timed span, the schedule's counts
+    int32_t *out_admit_step = nullptr, *out_unit = nullptr;
+    double *seconds_out = nullptr;
+    biogpt_hip_queue_stats *stats = nullptr;
+    // prepare(units) sets these: they lie in buffers it allocates.  The admit list, on the device and pinned, with the size of a record; the header, on the
+    // device and pinned, with fin[unit] != 0 in the pinned one where the unit's request has finished.
+    void *admit_dev = nullptr, *admit_host = nullptr;
+    size_t admit_bytes = 0;
+    const void *hdr_dev = nullptr;
+    void *hdr_host = nullptr;
+    size_t hdr_bytes = 0;
+    const int32_t *fin = nullptr;
+    std::function<bool(int)> prepare;               // prepare(units): once the schedule has said how many units run -- the mode's buffers, the call's parameters and
+                                                    // a start state in which no unit runs
+    ColumnStep step;                                // step(t_max): the forward pass of all columns + the mode's selection and its report to the header
+    std::function<void(int, int, int)> admit;       // admit(unit, r, i): entry i of the pinned admit list <- request r in `unit`
+    std::function<bool(int)> enqueue_admit;         // enqueue_admit(n): the launches behind the copy of n admit records
+    std::function<int(int, int)> collect;           // collect(unit, r): enqueues the copies of what request r left in `unit` (the unit is refilled behind them); the
+                                                    // length the schedule retires it with, < 0: a failure
+    std::function<bool()> landed;                   // (or none) behind every header wait and once behind the final synchronize: copies enqueued before the wait
+                                                    // before have arrived
+};
+
+// The one order of a queued call, for requests that passed their checks.  Returns 0 once every request has been served and the stream has drained, or at once
+// where no request may generate a token (nothing was touched); -1: the columns do not fit the model; -2: a failure.
+static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc) {
+    const int P = ctx->hp.n_positions, R = rq.n_requests;
+    // every request's own clamp; the buckets the steps can need
+    rq.cap.assign((size_t)R, 0);
+    int min_len = P, max_keys = 0;
+    long total = 0;
+    for (int r = 0; r < R; r++) {
+        rq.cap[(size_t)r] = std::min(rq.n_predicts ? rq.n_predicts[r] : rq.n_predict, P - rq.prompt_lens[r]);
+        if (rq.cap[(size_t)r] <= 0) continue;
+        min_len = std::min(min_len, rq.prompt_lens[r]); max_keys = std::max(max_keys, rq.prompt_lens[r] + rq.cap[(size_t)r]);
+        total += rq.prompt_lens[r];
+    }
+    const std::vector<int32_t> &cap = rq.cap;
+    if (qc.out_admit_step) std::fill(qc.out_admit_step, qc.out_admit_step + R, -1);
+    if (qc.out_unit) std::fill(qc.out_unit, qc.out_unit + R, -1);
+    if (qc.seconds_out) *qc.seconds_out = 0.0;
+    QueueSchedule q(cap.data(), R, qc.max_units, rq.group);
+    const int U = q.C, C = U * qc.per_unit;
+    if (qc.stats) *qc.stats = q.st;
+    if (U == 0) return 0;      // nobody has room for a token: nothing was touched
+    if (C > hp_cols(ctx)) BG_FAIL(-1, "max_columns (%d) exceeds the %d activation columns of this model", C, hp_cols(ctx));
+
+    XpCallScope xp_scope(ctx);
+    XcBatchScope xc_scope{ctx};
+    if (!begin_column_call(ctx, C, C, std::min<long>(total, P))) return -2;
+    ctx->xc_batch = 0;      // the steps are always the launch chain
+    if (!qc.prepare(U)) return -2;
+    column_graphs_for(*qc.graphs, U, qc.key_b);
+    // (ColumnKeys of a call whose first replayed step sees min_len keys and whose last one max_keys: every bucket a step here can be bounded by)
+    bool use_graph;
+    if (!capture_column_steps(ctx, *qc.graphs, qc.gset, ColumnKeys{min_len - 1, 1, P}, max_keys - min_len + 2, qc.step, &use_graph)) return -2;
+
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> flat, lens, slots;
+    while (!q.done()) {
+        // ---- refill: the prompts of the admitted requests into the (first) slots of exactly their units, then the admit list and the mode's launches behind it ----
+        flat.clear(); lens.clear(); slots.clear();
+        const int n_admit = q.refill([&](int unit, int r) {
+            const int32_t *p = rq.prompts + rq.off[(size_t)r];
+            const int len = rq.prompt_lens[r];
+            qc.admit(unit, r, (int)slots.size());
+            flat.insert(flat.end(), p, p + len); lens.push_back(len); slots.push_back(unit * qc.per_unit);
+            if (qc.out_admit_step) qc.out_admit_step[r] = q.st.steps;
+            if (qc.out_unit) qc.out_unit[r] = unit;
+            q.st.prompt_columns += len;
+        });
+        if (n_admit > 0) {
+            if (!pack_column_passes(ctx, flat.data(), lens.data(), n_admit, rq.n_batch,
+                                    [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); }, 1, 0, SharedRows{},
+                                    slots.data()))
+                return -2;
+            HIP_TRY(-2, hipMemcpyAsync(qc.admit_dev, qc.admit_host, qc.admit_bytes * (size_t)n_admit, hipMemcpyHostToDevice, ctx->stream));
+            if (!qc.enqueue_admit(n_admit)) return -2;
+        }
+        // ---- one group of steps ----
+        for (int g = q.group_steps(); g > 0; g--) {
+            int t_max = 1;
+            for (int unit = 0; unit < U; unit++)
+                if (q.req[(size_t)unit] >= 0) t_max = std::max(t_max, q.position(unit, rq.prompt_lens[q.req[(size_t)unit]]) + 1);
+            t_max = std::min(t_max, P);
+            if (use_graph) {
+                hipGraphExec_t ge = qc.graphs->exec[qc.gset + graph_bucket(t_max)];
+                if (!ge) BG_FAIL(-2, "internal: no captured %s for %d keys", qc.step_name, t_max);
+                HIP_TRY(-2, hipGraphLaunch(ge, ctx->stream));
+            } else if (!qc.step(t_max)) {
+                return -2;
+            }
+            q.step();
+        }
+        q.end_group();
+        // ---- the look at the units: the header behind the group (lag 0) ----
+        HIP_TRY(-2, hipMemcpyAsync(qc.hdr_host, qc.hdr_dev, qc.hdr_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(-2, hipEventRecord(ctx->live_ev[0], ctx->stream));
+        HIP_TRY(-2, hipEventSynchronize(ctx->live_ev[0]));
+        // (the copies of the look before stand in front of this header in the stream: they have arrived)
+        if (qc.landed && !qc.landed()) return -2;
+        for (int unit = 0; unit < U; unit++) {
+            if (!q.live[(size_t)unit]) continue;
+            const int r = q.req[(size_t)unit];
+            if (!qc.fin[unit]) {
+                if (q.since[(size_t)unit] >= cap[(size_t)r])
+                    BG_FAIL(-2, "internal: request %d (%s %d) is unfinished after %d steps, its limit is %d", r, qc.unit, unit, q.since[(size_t)unit], cap[(size_t)r]);
+                continue;
+            }
+            const int len = qc.collect(unit, r);      // in stream order before the unit is reused
+            if (len < 0) return -2;
+            q.retire(unit, len);
+        }
+    }
+    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (qc.landed && !qc.landed()) return -2;
+    if (!xpipe_check(ctx)) return -2;
+    if (qc.seconds_out) *qc.seconds_out = std::chrono::duration<double>(t1 - t0).count();
+    if (qc.stats) *qc.stats = q.st;
+    return 0;
+}
+
+// ---- generation over a queue: a unit is a column; sampling with each request's own generator (kernels_queue.hip.h) ------------------------------------
 struct QueueBufs {
     bgk::SampleCtl *ctl;
     bgk::SampleSeq *seq;        // [QUEUE_COLS]
@@ -4583,155 +4743,74 @@ static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
                                const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, int32_t *out_admit_step, int32_t *out_column,
                                double *seconds_out, biogpt_hip_queue_stats *stats) {
     clear_error();
-    // (what can be judged without the model comes first: these fail the same way with no context and no device)
     if (!prompts) BG_FAIL(-1, "null argument: prompts");
     if (!prompt_lens) BG_FAIL(-1, "null argument: prompt_lens");
     if (!seeds) BG_FAIL(-1, "null argument: seeds");
     if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
     if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
-    if (n_requests < 1) BG_FAIL(-1, "n_requests must be >= 1");
+    QueueRequests rq{prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch};
+    if (!rq.check_count()) return -1;
     if (max_columns < 1 || max_columns > bgk::QUEUE_COLS) BG_FAIL(-1, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
-    if (group < 1 || group > 64) BG_FAIL(-1, "group must be in [1, 64]");
-    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
-    if (n_predict < 0) BG_FAIL(-1, "n_predict must be >= 0");
-    for (int r = 0; n_predicts && r < n_requests; r++)
-        if (n_predicts[r] < 0 || n_predicts[r] > n_predict) BG_FAIL(-1, "n_predicts[%d] (%d) must be in [0, n_predict = %d]", r, n_predicts[r], n_predict);
+    if (!rq.check_sizes()) return -1;
     if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
     if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
     if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
     if (eos_id < -1) BG_FAIL(-1, "eos_id %d out of range: must be a token id, or -1 for none", eos_id);
-    std::vector<size_t> off((size_t)n_requests + 1, 0);
-    for (int r = 0; r < n_requests; r++) {
-        if (prompt_lens[r] < 1) BG_FAIL(-1, "empty prompt (request %d)", r);
-        off[(size_t)r + 1] = off[(size_t)r] + (size_t)prompt_lens[r];
-    }
-    for (int r = 0; r < n_requests; r++)
-        for (int i = 0; i < prompt_lens[r]; i++)
-            if (prompts[off[(size_t)r] + (size_t)i] < 0) BG_FAIL(-1, "token id %d (request %d, position %d) out of range", prompts[off[(size_t)r] + (size_t)i], r, i);
-    if (!ctx) BG_FAIL(-1, "null context");
-    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (!rq.check_prompts(ctx)) return -1;
     const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
     if (top_k > V) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
     if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
-    for (int r = 0; r < n_requests; r++) {
-        if (prompt_lens[r] > P) BG_FAIL(-1, "prompt_lens[%d] (%d) exceeds n_positions (%d)", r, prompt_lens[r], P);
-        for (int i = 0; i < prompt_lens[r]; i++)
-            if (prompts[off[(size_t)r] + (size_t)i] >= V) BG_FAIL(-1, "token id %d (request %d, position %d) out of range [0, %d)", prompts[off[(size_t)r] + (size_t)i], r, i, V);
-    }
-    if (!check_fast_chain(ctx, "generation over a queue")) return -1;
-
-    // every request's own clamp (main.cpp:82 per request); the buckets the steps can need
-    std::vector<int32_t> cap((size_t)n_requests);
-    int min_len = P, max_keys = 0;
-    long total = 0;
-    for (int r = 0; r < n_requests; r++) {
-        cap[(size_t)r] = std::min(n_predicts ? n_predicts[r] : n_predict, P - prompt_lens[r]);
-        if (cap[(size_t)r] <= 0) continue;
-        min_len = std::min(min_len, prompt_lens[r]); max_keys = std::max(max_keys, prompt_lens[r] + cap[(size_t)r]);
-        total += prompt_lens[r];
-    }
+    if (!rq.check_prompts_model(ctx, "generation over a queue")) return -1;
     std::fill(out_ids, out_ids + (size_t)n_requests * (size_t)n_predict, -1);
     std::fill(out_lens, out_lens + n_requests, 0);
-    if (out_admit_step) std::fill(out_admit_step, out_admit_step + n_requests, -1);
-    if (out_column) std::fill(out_column, out_column + n_requests, -1);
-    if (seconds_out) *seconds_out = 0.0;
-    QueueSchedule q(cap.data(), n_requests, max_columns, group);
-    const int C = q.C;
-    if (stats) *stats = q.st;
-    if (C == 0) return 0;      // nobody has room for a token: nothing was touched
-    if (C > hp_cols(ctx)) BG_FAIL(-1, "max_columns (%d) exceeds the %d activation columns of this model", C, hp_cols(ctx));
 
-    XpCallScope xp_scope(ctx);
-    XcBatchScope xc_scope{ctx};
-    if (!begin_column_call(ctx, C, C, std::min<long>(total, P))) return -2;
-    ctx->xc_batch = 0;
-    if (!ctx->queue_buf) HIP_TRY(-2, hipMalloc(&ctx->queue_buf, queue_bufs_at(nullptr).bytes));
-    if (!ctx->queue_host) HIP_TRY(-2, hipHostMalloc(&ctx->queue_host, sizeof(QueueHost)));
-    const QueueBufs qb = queue_bufs_at(ctx->queue_buf);
-    QueueHost *const qh = reinterpret_cast<QueueHost *>(ctx->queue_host);
-    column_graphs_for(ctx->graphs_queue, C, 0);
-    {      // the call's parameters; nobody runs yet
+    QueueBufs qb{};
+    QueueHost *qh = nullptr;
+    int C = 0;
+    QueueCall qc;
+    qc.max_units = max_columns;
+    qc.graphs = &ctx->graphs_queue;
+    qc.out_admit_step = out_admit_step; qc.out_unit = out_column; qc.seconds_out = seconds_out; qc.stats = stats;
+    qc.prepare = [&](int units) -> bool {
+        C = units;
+        if (!ctx->queue_buf) HIP_TRY(false, hipMalloc(&ctx->queue_buf, queue_bufs_at(nullptr).bytes));
+        if (!ctx->queue_host) HIP_TRY(false, hipHostMalloc(&ctx->queue_host, sizeof(QueueHost)));
+        qb = queue_bufs_at(ctx->queue_buf);
+        qh = reinterpret_cast<QueueHost *>(ctx->queue_host);
+        qc.admit_dev = qb.admit; qc.admit_host = qh->admit; qc.admit_bytes = sizeof(bgk::QueueAdmit);
+        qc.hdr_dev = qb.hdr; qc.hdr_host = &qh->hdr; qc.hdr_bytes = sizeof(bgk::QueueHdr); qc.fin = qh->hdr.fin;
+        // the call's parameters; nobody runs yet
         const bgk::SampleCtl hc = sample_ctl_of(top_k, eos_id, 0, top_p, temp);
-        HIP_TRY(-2, hipMemcpy(qb.ctl, &hc, sizeof(hc), hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemset(qb.hdr, 0, sizeof(bgk::QueueHdr)));
-    }
-    const ColumnStep step = [&](int t_max) -> bool {
+        HIP_TRY(false, hipMemcpy(qb.ctl, &hc, sizeof(hc), hipMemcpyHostToDevice));
+        HIP_TRY(false, hipMemset(qb.hdr, 0, sizeof(bgk::QueueHdr)));
+        return true;
+    };
+    qc.step = [&](int t_max) -> bool {
         if (!enqueue_forward(ctx, ForwardPass::decode_step(C, t_max))) return false;
         hipLaunchKernelGGL(bgk::queue_rows_kernel, dim3(C), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, qb.ctl, qb.seq, ctx->seq, ctx->seq_gen, P,
                            qb.limit, qb.hdr);
         HIP_TRY(false, hipGetLastError());
         return true;
     };
-    // (ColumnKeys of a call whose first replayed step sees min_len keys and whose last one max_keys: every bucket a step here can be bounded by)
-    bool use_graph;
-    if (!capture_column_steps(ctx, ctx->graphs_queue, 0, ColumnKeys{min_len - 1, 1, P}, max_keys - min_len + 2, step, &use_graph)) return -2;
-
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<int32_t> flat, lens, slots;
-    while (!q.done()) {
-        // ---- refill: the prompts of the admitted requests into exactly their columns' slots, then one admit launch ----
-        flat.clear(); lens.clear(); slots.clear();
-        const int n_admit = q.refill([&](int col, int r) {
-            const int32_t *p = prompts + off[(size_t)r];
-            const int len = prompt_lens[r];
-            bgk::QueueAdmit &a = qh->admit[slots.size()];
-            a = bgk::QueueAdmit{};
-            a.col = col; a.last_token = p[len - 1]; a.len = len; a.limit = cap[(size_t)r]; a.seed = seeds[r];
-            flat.insert(flat.end(), p, p + len); lens.push_back(len); slots.push_back(col);
-            if (out_admit_step) out_admit_step[r] = q.st.steps;
-            if (out_column) out_column[r] = col;
-            q.st.prompt_columns += len;
-        });
-        if (n_admit > 0) {
-            if (!pack_column_passes(ctx, flat.data(), lens.data(), n_admit, n_batch,
-                                    [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); }, 1, 0, SharedRows{},
-                                    slots.data()))
-                return -2;
-            HIP_TRY(-2, hipMemcpyAsync(qb.admit, qh->admit, sizeof(bgk::QueueAdmit) * (size_t)n_admit, hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(bgk::queue_admit_kernel, dim3(n_admit), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, qb.seq, ctx->seq, qb.limit, qb.hdr);
-            HIP_TRY(-2, hipGetLastError());
-        }
-        // ---- one group of steps ----
-        for (int g = q.group_steps(); g > 0; g--) {
-            int t_max = 1;
-            for (int col = 0; col < C; col++)
-                if (q.req[(size_t)col] >= 0) t_max = std::max(t_max, q.position(col, prompt_lens[q.req[(size_t)col]]) + 1);
-            t_max = std::min(t_max, P);
-            if (use_graph) {
-                hipGraphExec_t ge = ctx->graphs_queue.exec[graph_bucket(t_max)];
-                if (!ge) BG_FAIL(-2, "internal: no captured queue step for %d keys", t_max);
-                HIP_TRY(-2, hipGraphLaunch(ge, ctx->stream));
-            } else if (!step(t_max)) {
-                return -2;
-            }
-            q.step();
-        }
-        q.end_group();
-        // ---- the look at the columns: the header behind the group (lag 0) ----
-        HIP_TRY(-2, hipMemcpyAsync(&qh->hdr, qb.hdr, sizeof(bgk::QueueHdr), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(-2, hipEventRecord(ctx->live_ev[0], ctx->stream));
-        HIP_TRY(-2, hipEventSynchronize(ctx->live_ev[0]));
-        for (int col = 0; col < C; col++) {
-            if (!q.live[(size_t)col]) continue;
-            const int r = q.req[(size_t)col];
-            if (!qh->hdr.fin[col]) {
-                if (q.since[(size_t)col] >= cap[(size_t)r])
-                    BG_FAIL(-2, "internal: request %d (column %d) is unfinished after %d steps, its limit is %d", r, col, q.since[(size_t)col], cap[(size_t)r]);
-                continue;
-            }
-            const int len = std::max(0, std::min(qh->hdr.len[col], cap[(size_t)r]));
-            if (len > 0)
-                HIP_TRY(-2, hipMemcpyAsync(out_ids + (size_t)r * (size_t)n_predict, ctx->seq_gen + (size_t)col * P, (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
-            out_lens[r] = len;
-            q.retire(col, len);
-        }
-    }
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (!xpipe_check(ctx)) return -2;
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
-    if (stats) *stats = q.st;
-    return 0;
+    qc.admit = [&](int col, int r, int i) {
+        const int len = prompt_lens[r];
+        bgk::QueueAdmit &a = qh->admit[i];
+        a = bgk::QueueAdmit{};
+        a.col = col; a.last_token = prompts[rq.off[(size_t)r] + (size_t)(len - 1)]; a.len = len; a.limit = rq.cap[(size_t)r]; a.seed = seeds[r];
+    };
+    qc.enqueue_admit = [&](int n_admit) -> bool {
+        hipLaunchKernelGGL(bgk::queue_admit_kernel, dim3(n_admit), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, qb.seq, ctx->seq, qb.limit, qb.hdr);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    qc.collect = [&](int col, int r) -> int {      // the ids straight from the column's seq_gen row to the caller's row
+        const int len = std::max(0, std::min(qh->hdr.len[col], rq.cap[(size_t)r]));
+        if (len > 0)
+            HIP_TRY(-1, hipMemcpyAsync(out_ids + (size_t)r * (size_t)n_predict, ctx->seq_gen + (size_t)col * P, (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
+        out_lens[r] = len;
+        return len;
+    };
+    return run_queue_call(ctx, rq, qc);
 }
 
 int biogpt_hip_generate_queue(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,
@@ -4744,15 +4823,15 @@ int biogpt_hip_generate_queue(biogpt_hip_ctx *ctx, const int32_t *prompts, const
     });
 }
 
-// ---- beam search over a queue: finished searches hand their B columns on (kernels_beam_queue.hip.h) ------------------------------------------------
+// ---- beam search over a queue: a unit is a group slot of B columns; finished searches hand their slot on (kernels_beam_queue.hip.h) ------------------
 // S = min(max_columns / n_beams, eligible requests) group slots of B columns and K / V slots each serve any number of requests: a request's search runs in one
 // slot -- group `slot` of biogpt_hip_generate_beam_batch's state, columns [slot * B, (slot + 1) * B) -- under its own clamp, and when it stops, by
-// transformers' stopping rules or after its own n_predict steps, its pool is copied out and the slot goes to the next request.  The schedule is
-// generate_queue's, the same QueueSchedule with "columns" = slots: admission in index order, groups of min(group, the most steps any running search may
-// still take), the report header (BeamQueueHdr) read behind each group, refill in ascending slot / request order.  A refill is a packed prompt pass into the
-// first slot of each admitted group, kv_share_slots_kernel to the group's other slots, and one admit launch.  The host bounds a step's keys as
-// generate_queue does.  A refilled slot keeps its old K / V rows beyond the new prompt and its old pool rows: no decode-step attention kernel lets a column
-// see a key at or beyond its own n_past + 1, and pool_n = 0 hides the pool.
+// transformers' stopping rules or after its own n_predict steps, its pool is copied out and the slot goes to the next request.  What the mode supplies to
+// run_queue_call: the step (the three beam kernels behind the forward pass, then beam_slot_report_kernel into the header, BeamQueueHdr); behind the admit list
+// kv_share_slots_kernel -- the prompt pass has filled the first slot of each admitted group -- and beam_slot_admit_kernel; for a finished slot the copies of its
+// BeamCtl and its B pool rows to the pinned twin, decoded into the caller's rows once a later wait has proved their arrival (landed).  A refilled slot keeps its
+// old K / V rows beyond the new prompt and its old pool rows: no decode-step attention kernel lets a column see a key at or beyond its own n_past + 1, and
+// pool_n = 0 hides the pool.
 // The searches' state block is the context's bbatch_buf, the one biogpt_hip_generate_beam_batch uses (allocated once at its largest: the captured steps of
 // both keep their pointers, and a closed call uploads its whole start state, so neither sees the other's leftovers); what the queue adds -- report header and
 // admit list -- is a block of its own.  The steps are captured per bucket into graphs_bqueue, keyed by (S, B), trie or not, and always run the launch chain.
@@ -4781,106 +4860,79 @@ static int generate_beam_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
                                     int32_t early_stopping, biogpt_hip_trie *trie, int32_t *out_ids, int32_t *out_lens, float *out_scores, int32_t *out_counts,
                                     int32_t *out_steps, int32_t *out_admit_step, int32_t *out_slot, double *seconds_out, biogpt_hip_queue_stats *stats) {
     clear_error();
-    // (what can be judged without the model comes first: these fail the same way with no context and no device)
     if (!prompts) BG_FAIL(-1, "null argument: prompts");
     if (!prompt_lens) BG_FAIL(-1, "null argument: prompt_lens");
     if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
     if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
     if (!out_scores) BG_FAIL(-1, "null argument: out_scores");
     if (!out_counts) BG_FAIL(-1, "null argument: out_counts");
-    if (n_requests < 1) BG_FAIL(-1, "n_requests must be >= 1");
+    QueueRequests rq{prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch};
+    if (!rq.check_count()) return -1;
     if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
     if (max_columns < n_beams || max_columns > BBATCH_COLS) BG_FAIL(-1, "max_columns must be in [n_beams = %d, %d]", n_beams, BBATCH_COLS);
-    if (group < 1 || group > 64) BG_FAIL(-1, "group must be in [1, 64]");
-    if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
-    if (n_predict < 0) BG_FAIL(-1, "n_predict must be >= 0");
-    for (int r = 0; n_predicts && r < n_requests; r++)
-        if (n_predicts[r] < 0 || n_predicts[r] > n_predict) BG_FAIL(-1, "n_predicts[%d] (%d) must be in [0, n_predict = %d]", r, n_predicts[r], n_predict);
+    if (!rq.check_sizes()) return -1;
     if (eos_id < -1) BG_FAIL(-1, "eos_id %d out of range: must be a token id, or -1 for none", eos_id);
     if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
     if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
     if (trie && !check_trie(trie, eos_id)) return -1;
-    std::vector<size_t> off((size_t)n_requests + 1, 0);
-    for (int r = 0; r < n_requests; r++) {
-        if (prompt_lens[r] < 1) BG_FAIL(-1, "empty prompt (request %d)", r);
-        off[(size_t)r + 1] = off[(size_t)r] + (size_t)prompt_lens[r];
-    }
-    for (int r = 0; r < n_requests; r++)
-        for (int i = 0; i < prompt_lens[r]; i++)
-            if (prompts[off[(size_t)r] + (size_t)i] < 0) BG_FAIL(-1, "token id %d (request %d, position %d) out of range", prompts[off[(size_t)r] + (size_t)i], r, i);
-    if (!ctx) BG_FAIL(-1, "null context");
-    if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
-    const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab, B = n_beams;
+    if (!rq.check_prompts(ctx)) return -1;
+    const auto &hp = ctx->hp;
+    const int P = hp.n_positions, V = hp.n_vocab, B = n_beams;
     if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
-    for (int r = 0; r < n_requests; r++) {
-        if (prompt_lens[r] > P) BG_FAIL(-1, "prompt_lens[%d] (%d) exceeds n_positions (%d)", r, prompt_lens[r], P);
-        for (int i = 0; i < prompt_lens[r]; i++)
-            if (prompts[off[(size_t)r] + (size_t)i] >= V) BG_FAIL(-1, "token id %d (request %d, position %d) out of range [0, %d)", prompts[off[(size_t)r] + (size_t)i], r, i, V);
-    }
-    if (!check_fast_chain(ctx, "beam search over a queue")) return -1;
+    if (!rq.check_prompts_model(ctx, "beam search over a queue")) return -1;
     if (V < 2 * B) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", V);
     if (trie && !check_trie_vocab(trie, V)) return -1;
-
-    // every request's own clamp (main.cpp:82 per request: what biogpt_hip_generate_beam applies to the prompt alone); the buckets the steps can need
-    std::vector<int32_t> cap((size_t)n_requests);
-    int min_len = P, max_keys = 0;
-    long total = 0;
-    for (int r = 0; r < n_requests; r++) {
-        cap[(size_t)r] = std::min(n_predicts ? n_predicts[r] : n_predict, P - prompt_lens[r]);
-        if (cap[(size_t)r] <= 0) continue;
-        min_len = std::min(min_len, prompt_lens[r]); max_keys = std::max(max_keys, prompt_lens[r] + cap[(size_t)r]);
-        total += prompt_lens[r];
-    }
     const size_t row = (size_t)n_predict, rows = (size_t)n_requests * (size_t)B;
     std::fill(out_ids, out_ids + rows * row, -1);
     std::fill(out_lens, out_lens + rows, 0);
     std::fill(out_scores, out_scores + rows, 0.0f);
     std::fill(out_counts, out_counts + n_requests, 0);
     if (out_steps) std::fill(out_steps, out_steps + n_requests, 0);
-    if (out_admit_step) std::fill(out_admit_step, out_admit_step + n_requests, -1);
-    if (out_slot) std::fill(out_slot, out_slot + n_requests, -1);
-    if (seconds_out) *seconds_out = 0.0;
-    QueueSchedule q(cap.data(), n_requests, max_columns / B, group);
-    const int S = q.C, C = S * B;
-    if (stats) *stats = q.st;
-    if (S == 0) return 0;      // nobody has room for a token: nothing was touched
-    if (C > hp_cols(ctx)) BG_FAIL(-1, "max_columns (%d) exceeds the %d activation columns of this model", C, hp_cols(ctx));
 
-    XpCallScope xp_scope(ctx);
-    XcBatchScope xc_scope{ctx};
-    if (!begin_column_call(ctx, C, C, std::min<long>(total, P))) return -2;
-    ctx->xc_batch = 0;
-    if (!ctx->bbatch_buf) {
-        size_t bytes;
-        beam_bufs_of(ctx, &bytes);
-        HIP_TRY(-2, hipMalloc(&ctx->bbatch_buf, bytes));
-    }
-    const size_t pool_words = (size_t)BBATCH_COLS * (size_t)P;
-    if (!ctx->bqueue_buf) HIP_TRY(-2, hipMalloc(&ctx->bqueue_buf, bqueue_bufs_at(nullptr).bytes));
-    if (!ctx->bqueue_host) HIP_TRY(-2, hipHostMalloc(&ctx->bqueue_host, sizeof(BeamQueueHost) + pool_words * 4));
-    const BeamBufs bufs = beam_bufs_of(ctx);
-    const BeamQueueBufs qb = bqueue_bufs_at(ctx->bqueue_buf);
-    BeamQueueHost *const qh = reinterpret_cast<BeamQueueHost *>(ctx->bqueue_host);
-    int32_t *const pool_host = reinterpret_cast<int32_t *>(ctx->bqueue_host + sizeof(BeamQueueHost));
-    column_graphs_for(ctx->graphs_bqueue, S, B);
-    const int gset = trie ? 6 : 0;
+    BeamBufs bufs{};
+    BeamQueueBufs qb{};
+    BeamQueueHost *qh = nullptr;
+    int32_t *pool_host = nullptr;
+    int S = 0, C = 0;
     const bool given = trie != nullptr;
+    const int64_t seq_stride = (int64_t)hp.n_layer * P * hp.d_model;
     bgk::BeamQueueCall call{};
-    call.n_beams = B; call.eos_id = eos_id; call.length_penalty = length_penalty; call.early_stopping = early_stopping; call.ids_stride = P; call.n_slots = S;
-    {      // nobody runs yet: every slot's search reads as stopped and reported, no forks
+    call.n_beams = B; call.eos_id = eos_id; call.length_penalty = length_penalty; call.early_stopping = early_stopping; call.ids_stride = P;
+    std::vector<std::pair<int, int>> landing;              // (slot, request): copies enqueued, not yet known to have arrived
+    QueueCall qc;
+    qc.max_units = max_columns / B; qc.per_unit = B;
+    qc.unit = "slot"; qc.step_name = "beam queue step";
+    qc.graphs = &ctx->graphs_bqueue; qc.key_b = B; qc.gset = trie ? 6 : 0;
+    qc.out_admit_step = out_admit_step; qc.out_unit = out_slot; qc.seconds_out = seconds_out; qc.stats = stats;
+    qc.prepare = [&](int units) -> bool {
+        S = units; C = S * B; call.n_slots = S;
+        if (!ctx->bbatch_buf) {
+            size_t bytes;
+            beam_bufs_of(ctx, &bytes);
+            HIP_TRY(false, hipMalloc(&ctx->bbatch_buf, bytes));
+        }
+        if (!ctx->bqueue_buf) HIP_TRY(false, hipMalloc(&ctx->bqueue_buf, bqueue_bufs_at(nullptr).bytes));
+        if (!ctx->bqueue_host) HIP_TRY(false, hipHostMalloc(&ctx->bqueue_host, sizeof(BeamQueueHost) + (size_t)BBATCH_COLS * (size_t)P * 4));
+        bufs = beam_bufs_of(ctx);
+        qb = bqueue_bufs_at(ctx->bqueue_buf);
+        qh = reinterpret_cast<BeamQueueHost *>(ctx->bqueue_host);
+        pool_host = reinterpret_cast<int32_t *>(ctx->bqueue_host + sizeof(BeamQueueHost));
+        qc.admit_dev = qb.admit; qc.admit_host = qh->admit; qc.admit_bytes = sizeof(bgk::BeamQueueAdmit);
+        qc.hdr_dev = qb.hdr; qc.hdr_host = &qh->hdr; qc.hdr_bytes = sizeof(bgk::BeamQueueHdr); qc.fin = qh->hdr.fin;
+        // nobody runs yet: every slot's search reads as stopped and reported, no forks
         HeadImage im(bufs.hdr, bufs.ctl + S);
         for (int s = 0; s < S; s++) {
             im.at(bufs.ctl)[s] = beam_ctl_of(B, 1, 0, eos_id, length_penalty, early_stopping, P);
             im.at(bufs.ctl)[s].done = 1;
         }
         for (int c = 0; c < C; c++) im.at(bufs.col_skip)[c] = 1;
-        if (!im.upload()) return -2;
+        if (!im.upload()) return false;
         qh->hdr = bgk::BeamQueueHdr{};
         for (int s = 0; s < S; s++) qh->hdr.fin[s] = 1;
-        HIP_TRY(-2, hipMemcpy(qb.hdr, &qh->hdr, sizeof(bgk::BeamQueueHdr), hipMemcpyHostToDevice));
-        if (trie && !trie_upload(ctx, trie, 1, eos_id)) return -2;
-    }
-    const ColumnStep step = [&](int t_max) -> bool {
+        HIP_TRY(false, hipMemcpy(qb.hdr, &qh->hdr, sizeof(bgk::BeamQueueHdr), hipMemcpyHostToDevice));
+        return !trie || trie_upload(ctx, trie, 1, eos_id);
+    };
+    qc.step = [&](int t_max) -> bool {
         if (!enqueue_forward(ctx, ForwardPass::decode_step(C, t_max))) return false;
         if (trie && !enqueue_trie(ctx, C, bufs.col_skip, 1)) return false;
         if (!enqueue_beam_group_select(bufs, S, B, given)) return false;
@@ -4889,96 +4941,41 @@ static int generate_beam_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
         HIP_TRY(false, hipGetLastError());
         return true;
     };
-    // (ColumnKeys of a call whose first replayed step sees min_len keys and whose last one max_keys: every bucket a step here can be bounded by)
-    bool use_graph;
-    if (!capture_column_steps(ctx, ctx->graphs_bqueue, gset, ColumnKeys{min_len - 1, 1, P}, max_keys - min_len + 2, step, &use_graph)) return -2;
-
-    const auto &hp = ctx->hp;
-    const int64_t seq_stride = (int64_t)hp.n_layer * P * hp.d_model;
-    std::vector<std::pair<int, int>> landing;              // (slot, request): copies enqueued, not yet known to have arrived
-    // the pool of a search whose copies have arrived -> request r's rows
-    auto decode = [&](int slot, int r) -> bool {
-        const size_t o = (size_t)r * (size_t)B;
-        return beam_read_pools(&qh->ctl[slot], pool_host + (size_t)slot * B * P, (size_t)P, 1, B, n_predict, out_ids + o * row, out_lens + o, out_scores + o, out_counts + r,
-                               "request", r);
+    qc.admit = [&](int slot, int r, int i) {
+        const int len = prompt_lens[r];
+        qh->admit[i] = bgk::BeamQueueAdmit{slot, prompts[rq.off[(size_t)r] + (size_t)(len - 1)], len, rq.cap[(size_t)r]};
     };
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<int32_t> flat, lens, slots;
-    while (!q.done()) {
-        // ---- refill: the prompts of the admitted requests into the first slot of their groups, shared with the groups' other slots, then one admit launch ----
-        flat.clear(); lens.clear(); slots.clear();
-        const int n_admit = q.refill([&](int slot, int r) {
-            const int32_t *p = prompts + off[(size_t)r];
-            const int len = prompt_lens[r];
-            qh->admit[slots.size()] = bgk::BeamQueueAdmit{slot, p[len - 1], len, cap[(size_t)r]};
-            flat.insert(flat.end(), p, p + len); lens.push_back(len); slots.push_back(slot * B);
-            if (out_admit_step) out_admit_step[r] = q.st.steps;
-            if (out_slot) out_slot[r] = slot;
-            q.st.prompt_columns += len;
-        });
-        if (n_admit > 0) {
-            if (!pack_column_passes(ctx, flat.data(), lens.data(), n_admit, n_batch,
-                                    [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); }, 1, 0, SharedRows{},
-                                    slots.data()))
-                return -2;
-            HIP_TRY(-2, hipMemcpyAsync(qb.admit, qh->admit, sizeof(bgk::BeamQueueAdmit) * (size_t)n_admit, hipMemcpyHostToDevice, ctx->stream));
-            if (B > 1) {
-                hipLaunchKernelGGL(bgk::kv_share_slots_kernel, dim3(hp.n_layer * hp.n_head, n_admit * (B - 1), 2), dim3(256), 0, ctx->stream, qb.admit, B, S, ctx->bk, ctx->bv,
-                                   seq_stride, P, hp.d_model / hp.n_head);
-                HIP_TRY(-2, hipGetLastError());
-            }
-            hipLaunchKernelGGL(bgk::beam_slot_admit_kernel, dim3(n_admit), dim3(bgk::BEAM_QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, call, bufs.ctl, ctx->seq, bufs.col_skip,
-                               bufs.hdr, qb.hdr);
-            HIP_TRY(-2, hipGetLastError());
+    qc.enqueue_admit = [&](int n_admit) -> bool {
+        if (B > 1) {
+            hipLaunchKernelGGL(bgk::kv_share_slots_kernel, dim3(hp.n_layer * hp.n_head, n_admit * (B - 1), 2), dim3(256), 0, ctx->stream, qb.admit, B, S, ctx->bk, ctx->bv,
+                               seq_stride, P, hp.d_model / hp.n_head);
+            HIP_TRY(false, hipGetLastError());
         }
-        // ---- one group of steps ----
-        for (int g = q.group_steps(); g > 0; g--) {
-            int t_max = 1;
-            for (int slot = 0; slot < S; slot++)
-                if (q.req[(size_t)slot] >= 0) t_max = std::max(t_max, q.position(slot, prompt_lens[q.req[(size_t)slot]]) + 1);
-            t_max = std::min(t_max, P);
-            if (use_graph) {
-                hipGraphExec_t ge = ctx->graphs_bqueue.exec[gset + graph_bucket(t_max)];
-                if (!ge) BG_FAIL(-2, "internal: no captured beam queue step for %d keys", t_max);
-                HIP_TRY(-2, hipGraphLaunch(ge, ctx->stream));
-            } else if (!step(t_max)) {
-                return -2;
-            }
-            q.step();
+        hipLaunchKernelGGL(bgk::beam_slot_admit_kernel, dim3(n_admit), dim3(bgk::BEAM_QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, call, bufs.ctl, ctx->seq, bufs.col_skip,
+                           bufs.hdr, qb.hdr);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    qc.collect = [&](int slot, int r) -> int {      // the search's state and its B pool rows (whole rows up to the last one's limit) -> the slot's pinned twin
+        const int n_steps = std::max(0, std::min(qh->hdr.steps[slot], rq.cap[(size_t)r]));
+        HIP_TRY(-1, hipMemcpyAsync(&qh->ctl[slot], bufs.ctl + slot, sizeof(bgk::BeamCtl), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(-1, hipMemcpyAsync(pool_host + (size_t)slot * B * P, bufs.pool_ids + (size_t)slot * B * P, ((size_t)(B - 1) * P + (size_t)rq.cap[(size_t)r]) * 4,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        landing.emplace_back(slot, r);
+        if (out_steps) out_steps[r] = n_steps;
+        return n_steps;
+    };
+    qc.landed = [&]() -> bool {      // the pools whose copies have arrived -> their requests' rows; the slots' twins are free again
+        for (const auto &sr : landing) {
+            const size_t o = (size_t)sr.second * (size_t)B;
+            if (!beam_read_pools(&qh->ctl[sr.first], pool_host + (size_t)sr.first * B * P, (size_t)P, 1, B, n_predict, out_ids + o * row, out_lens + o, out_scores + o,
+                                 out_counts + sr.second, "request", sr.second))
+                return false;
         }
-        q.end_group();
-        // ---- the look at the slots: the header behind the group (lag 0) ----
-        HIP_TRY(-2, hipMemcpyAsync(&qh->hdr, qb.hdr, sizeof(bgk::BeamQueueHdr), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(-2, hipEventRecord(ctx->live_ev[0], ctx->stream));
-        HIP_TRY(-2, hipEventSynchronize(ctx->live_ev[0]));
-        // (the copies of the look before stand in front of this header in the stream: they have arrived, and their slots' twins are free again)
-        for (const auto &sr : landing) if (!decode(sr.first, sr.second)) return -2;
         landing.clear();
-        for (int slot = 0; slot < S; slot++) {
-            if (!q.live[(size_t)slot]) continue;
-            const int r = q.req[(size_t)slot];
-            if (!qh->hdr.fin[slot]) {
-                if (q.since[(size_t)slot] >= cap[(size_t)r])
-                    BG_FAIL(-2, "internal: request %d (slot %d) is unfinished after %d steps, its limit is %d", r, slot, q.since[(size_t)slot], cap[(size_t)r]);
-                continue;
-            }
-            // the search's state and its B pool rows (whole rows up to the last one's limit), in stream order before the slot is reused
-            const int n_steps = std::max(0, std::min(qh->hdr.steps[slot], cap[(size_t)r]));
-            HIP_TRY(-2, hipMemcpyAsync(&qh->ctl[slot], bufs.ctl + slot, sizeof(bgk::BeamCtl), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(-2, hipMemcpyAsync(pool_host + (size_t)slot * B * P, bufs.pool_ids + (size_t)slot * B * P, ((size_t)(B - 1) * P + (size_t)cap[(size_t)r]) * 4,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-            landing.emplace_back(slot, r);
-            if (out_steps) out_steps[r] = n_steps;
-            q.retire(slot, n_steps);
-        }
-    }
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    for (const auto &sr : landing) if (!decode(sr.first, sr.second)) return -2;
-    if (!xpipe_check(ctx)) return -2;
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(t1 - t0).count();
-    if (stats) *stats = q.st;
-    return 0;
+        return true;
+    };
+    return run_queue_call(ctx, rq, qc);
 }
 
 int biogpt_hip_generate_beam_queue(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,

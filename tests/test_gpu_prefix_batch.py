@@ -155,6 +155,33 @@ def test_default_takes_the_run_kernel_in_a_full_pass(pkg, oracle, files, monkeyp
     g.close()
 
 
+def test_the_single_call_never_takes_the_run_kernel(pkg, files, monkeypatch):
+    """One group of 4 two-token continuations behind 300 tokens: one pass of 299 + 8 = 307 columns whose longest shared range has 299 rows, which the batch
+    call gives to attn_runs_kernel by default.  score_continuations builds the same columns with the same packer and must not: its bits are the same under every
+    BIOGPT_HIP_RUN_ATTN and are those of the batch call under =0; and it leaves the batch call's stats alone."""
+    monkeypatch.delenv("BIOGPT_HIP_PROMPT_COLS", raising=False)
+    rng = np.random.default_rng(21)
+    prefix = [2] + [int(v) for v in rng.integers(4, KW["n_vocab"], 299)]
+    conts = [[int(v) for v in rng.integers(4, KW["n_vocab"], 2)] for _ in range(4)]
+    single = {}
+    for switch in (None, 1, 0):
+        g = load(pkg, monkeypatch, files["q4_0"], switch)
+        single[switch] = g.score_continuations(prefix, conts)
+        if switch == 0:
+            batch_0 = g.score_continuations_batch([prefix], [conts])[0]
+        g.close()
+    assert same([single[None]], [single[1]]), "BIOGPT_HIP_RUN_ATTN=1 changes the bits of score_continuations"
+    assert same([single[None]], [single[0]]), "BIOGPT_HIP_RUN_ATTN=0 changes the bits of score_continuations"
+    assert same([single[0]], [batch_0]), "score_continuations differs from the batch call of its one group under BIOGPT_HIP_RUN_ATTN=0"
+    g = load(pkg, monkeypatch, files["q4_0"], None)
+    g.score_continuations_batch([prefix], [conts])
+    st = g.prefix_batch_stats()
+    assert st == dict(prefix_columns=299, continuation_columns=8, passes=1, run_passes=1)
+    g.score_continuations(prefix[:40], conts[:2])
+    assert g.prefix_batch_stats() == st, "a single call changed the stats of the last batch call"
+    g.close()
+
+
 # ---- 4. limits ----
 
 def test_exactly_512_slots_run_and_513_are_refused(pkg, files, monkeypatch):
