@@ -293,6 +293,30 @@ def genlp_rows(rows, n_top, mode=0, top_k=40, top_p=0.9, temp=0.9, states=None, 
     return ids, lp, tid[:, :k], tlp[:, :k]
 
 
+def queue_rows(rows, states, limits, finished, mt_states, hdr, n_top=0, stride=1, top_k=40, top_p=0.9, temp=0.9, eos_id=-1, with_lp=True, device=0):
+    """One launch of the queue's step kernel on rows held in host memory (biogpt_hip_queue_rows_device): queue_rows_lp_kernel, or with_lp=False
+    queue_rows_kernel; row r is column r.  states int32 [n][8] (n_past, token, n_gen, seq_id, t_vis, 3 more words), finished int32 [n], mt_states uint32
+    [n][625] and hdr int32 [1 + 2 n] (n_live, fin[], len[]) are contiguous arrays, changed in place as the launch leaves them; limits int32 [n].  Returns
+    (ids int32[n, stride], logprobs float32[n, stride], top_ids int32[n, stride, n_top], top_logprobs float32[n, stride, n_top]) with 0xff bytes (-1, NaN)
+    wherever the launch wrote nothing."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv, k, w = int(a.shape[0]), int(a.shape[1]), int(n_top), int(stride)
+    lim = np.ascontiguousarray(limits, dtype=np.int32).reshape(-1)
+    for name, arr, dt, shape in (("states", states, np.int32, (n, 8)), ("finished", finished, np.int32, (n,)), ("mt_states", mt_states, np.uint32, (n, 625)),
+                                 ("hdr", hdr, np.int32, (1 + 2 * n,))):
+        if not (isinstance(arr, np.ndarray) and arr.dtype == dt and arr.flags["C_CONTIGUOUS"] and arr.shape == shape):
+            raise BiogptError("%s must be a contiguous %s array of shape %s" % (name, np.dtype(dt).name, shape))
+    if lim.size != n:
+        raise BiogptError("limits must have one entry per row (%d != %d)" % (lim.size, n))
+    ids, lp = np.zeros((n, max(w, 1)), dtype=np.int32), np.zeros((n, max(w, 1)), dtype=np.float32)
+    tid, tlp = np.zeros((n, max(w, 1), max(k, 1)), dtype=np.int32), np.zeros((n, max(w, 1), max(k, 1)), dtype=np.float32)
+    if lib().biogpt_hip_queue_rows_device(int(device), 1 if with_lp else 0, a.ctypes.data, n, nv, k, w, int(top_k), float(top_p), float(temp), int(eos_id),
+                                          mt_states.ctypes.data, states.ctypes.data, lim.ctypes.data, finished.ctypes.data, hdr.ctypes.data, ids.ctypes.data,
+                                          lp.ctypes.data, tid.ctypes.data if k > 0 else None, tlp.ctypes.data if k > 0 else None) != 0:
+        raise BiogptError(_err())
+    return ids, lp, tid[:, :, :k], tlp[:, :, :k]
+
+
 def lookup_draft(texts, n_gen, n_past, n_predict, max_draft=7, max_ngram=3, finished=None, device=0):
     """lookup_draft_kernel on texts held in host memory (biogpt_hip_lookup_draft_device): texts a list of id lists (corpus + prompt + generated tokens), n_gen[s]
     how many of text s were generated, n_past[s] the position of its last token.  Returns (drafts: list of id lists, d int32[n], cols int32[n][1 + max_draft][4]:
@@ -584,6 +608,8 @@ SYMBOLS = [
     ("biogpt_hip_generate_lookup", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_generate_queue", C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32,
                                            _P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(QueueStats)]),
+    ("biogpt_hip_generate_queue_prefix", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                                  _P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(QueueStats), C.POINTER(GenLogprobs)]),
     ("biogpt_hip_queue_plan", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(QueueStats)]),
     ("biogpt_hip_queue_plan_limits", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(QueueStats)]),
     ("biogpt_hip_read_column_state", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
@@ -631,6 +657,7 @@ SYMBOLS = [
     ("biogpt_hip_generate_sample_lp", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
                                                 C.c_int32, _P, _P, C.POINTER(C.c_double), C.POINTER(GenLogprobs)]),
     ("biogpt_hip_genlp_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
+    ("biogpt_hip_queue_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32] + [_P] * 9),
     ("biogpt_hip_attn_device", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("biogpt_hip_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32] + [_P] * 7 + [C.c_int32] * 3 + [_P] * 7),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
@@ -927,6 +954,17 @@ def _logprobs_keyword(plain):
     return call
 
 
+def _queue_keywords(plain):
+    """Adds the keyword-only prefix=None and logprobs=None to generate_queue, as _logprobs_keyword adds logprobs: the method's own parameters, defaults and
+    return value stay what they are.  Neither given: the method itself.  Otherwise _generate_queue with the same arguments and the two keywords."""
+    @functools.wraps(plain)
+    def call(self, *args, prefix=None, logprobs=None, **kw):
+        if prefix is None and logprobs is None:
+            return plain(self, *args, **kw)
+        return BiogptModel._generate_queue(self, *args, prefix=prefix, logprobs=logprobs, **kw)
+    return call
+
+
 def _sampler_keyword(plain):
     """Adds the keyword-only sampler=None to generate_sample, as _logprobs_keyword adds logprobs: the method's own parameters stay what they are.  None: the
     method itself.  A sampler: _generate_sample with the same arguments and sampler=."""
@@ -1208,13 +1246,25 @@ class BiogptModel:
         return ([rows[p * got:p * got + int(ol[p])].copy() for p in range(G)],
                 [dict(passes=int(st[p, 0]), drafted=int(st[p, 1]), accepted=int(st[p, 2])) for p in range(G)], secs.value)
 
+    @_queue_keywords
     def generate_queue(self, prompts, n_predict, max_columns=64, group=4, top_k=1, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8, n_predicts=None):
         """Generation over a queue of requests (continuous batching; INTEGRATION.md, "Generation over a queue"): prompts is a list of id lists of any length,
         at most max_columns of them run at a time, and a request that finishes -- by eos_id, or after its own n_predicts[r] (None: n_predict) tokens as
         clamped to ITS prompt -- hands its column to the next one.  Request r's ids are those of generate_sample([prompts[r]], n_r, top_k, top_p, temp,
         seeds=[seeds[r]], eos_id, n_batch) alone, whatever else is in the queue; seeds=None: seed + r.  top_k=1 (the default) never draws: greedy decoding
         with an EOS.  group: steps between two looks at the columns.  Returns ([ids int32[len], ...] in request order, {"stats": {...}, "admit_step":
-        [...], "column": [...]}, seconds); a request without room for a token gets no ids and -1 in both lists."""
+        [...], "column": [...]}, seconds); a request without room for a token gets no ids and -1 in both lists.
+        prefix (keyword only): a list of ids in front of every prompt -- request r is prefix + prompts[r], a prompt may then be empty, the prefix's first
+        rows (a multiple of n_batch) are evaluated once and read in place by every column, and max_columns is at most 511 ("Generation
+        over a queue"; prefix_stats()).  The ids, admit_step, column and stats are those of the call on the concatenations, but for
+        stats["prompt_columns"], the prompt columns really evaluated.
+        logprobs (keyword only): None, or K in [0, 8] -- info["logprobs"][r] = (logprobs float32[len_r], top_ids int32[len_r, K], top_logprobs float32[len_r,
+        K]) as generate_sample(logprobs=K) of the request alone gives them, bit for bit; the ids are those of the call without it."""
+        return BiogptModel._generate_queue(self, prompts, n_predict, max_columns, group, top_k, top_p, temp, seed, seeds, eos_id, n_batch, n_predicts)
+
+    def _generate_queue(self, prompts, n_predict, max_columns=64, group=4, top_k=1, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8, n_predicts=None,
+                        prefix=None, logprobs=None):
+        """generate_queue, with prefix= and logprobs= its form behind a shared prefix and with log-probabilities (biogpt_hip_generate_queue_prefix)."""
         if len(prompts) and np.isscalar(prompts[0]):
             prompts = [prompts]
         R = len(prompts)
@@ -1237,14 +1287,28 @@ class BiogptModel:
         ol, adm, col = (np.zeros(max(R, 1), dtype=np.int32) for _ in range(3))
         st = QueueStats()
         secs = C.c_double(0.0)
-        rc = lib().biogpt_hip_generate_queue(self._h, flat.ctypes.data, lens.ctypes.data, R, None if np_arr is None or R == 0 else np_arr.ctypes.data, int(n_predict),
-                                             int(max_columns), int(group), int(n_batch), int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id),
-                                             out.ctypes.data, ol.ctypes.data, adm.ctypes.data, col.ctypes.data, C.byref(secs), C.byref(st))
+        arr = None
+        if prefix is None and logprobs is None:
+            rc = lib().biogpt_hip_generate_queue(self._h, flat.ctypes.data, lens.ctypes.data, R, None if np_arr is None or R == 0 else np_arr.ctypes.data, int(n_predict),
+                                                 int(max_columns), int(group), int(n_batch), int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id),
+                                                 out.ctypes.data, ol.ctypes.data, adm.ctypes.data, col.ctypes.data, C.byref(secs), C.byref(st))
+        else:
+            pre = None if prefix is None else _flat_ids([prefix])
+            if logprobs is not None:
+                arr = _LogprobArrays(logprobs, R, max(w, 1))
+            rc = lib().biogpt_hip_generate_queue_prefix(self._h, None if pre is None else pre.ctypes.data, 0 if prefix is None else len(prefix), flat.ctypes.data,
+                                                        lens.ctypes.data, R, None if np_arr is None or R == 0 else np_arr.ctypes.data, int(n_predict), int(max_columns),
+                                                        int(group), int(n_batch), int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id), out.ctypes.data,
+                                                        ol.ctypes.data, adm.ctypes.data, col.ctypes.data, C.byref(secs), C.byref(st),
+                                                        None if arr is None else C.byref(arr.req))
         if rc < 0:
             raise BiogptError(_err())
         rows = out.reshape(-1)      # rows are [R][n_predict as given]
         ids = [rows[r * w:r * w + int(ol[r])].copy() for r in range(R)]
-        return ids, {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:R]], "column": [int(v) for v in col[:R]]}, secs.value
+        info = {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:R]], "column": [int(v) for v in col[:R]]}
+        if arr is not None:
+            info["logprobs"] = arr.info(R, w, [int(v) for v in ol[:R]]) if w > 0 else [arr.info(1, 0, [0])[0] for _ in range(R)]
+        return ids, info, secs.value
 
     def read_column_state(self, column, pos, which=0, n_ids=0):
         """Tests of slot reuse (biogpt_hip_read_column_state): (the K (which 0) or V (1) row of position pos in every layer of column `column`'s own cache slot,

@@ -4462,6 +4462,9 @@ int biogpt_hip_generate_lookup(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
 // A mode supplies (QueueCall): its units, its captured steps, the step itself, the admit record of a request and the launches behind the list, its header,
 // and what happens to a finished unit's results.  Everything else -- the shared argument checks, the clamps, the schedule, capture, the loop, the waits,
 // the timed span and the stats -- is stated once.
+// Behind a shared prefix (QueueRequests::prefix, biogpt_hip_generate_queue_prefix) a request is prefix ++ its prompt: every length the driver reasons with is
+// the whole sequence's (whole_len), the prefix's shared rows are evaluated once into one slot behind the units', inside the timed span and before the first
+// refill, and a refill packs what follows them.
 extern "C++" {
 struct QueueSchedule {
     const int32_t *cap;                     // tokens request r may generate at most; 0: it never takes a column
@@ -4552,6 +4555,12 @@ struct QueueRequests {
     int n_predict, max_columns, group, n_batch;
     std::vector<size_t> off;                    // set by check_prompts: request r's prompt lies at prompts + off[r]
     std::vector<int32_t> cap;                   // set by run_queue_call: the tokens request r may generate (main.cpp:82 per request); 0: it never takes a unit
+    // A shared prefix (biogpt_hip_generate_queue_prefix): request r is prefix ++ prompt r, the prompts are suffixes and may be empty.  pos0: the position of
+    // every prompt's first token (the prefix's length; 0 without one).  n_shared, set by check_prompts: the prefix rows evaluated once and read in place, the
+    // largest multiple of n_batch <= pos0 - 1 (0: nothing is shared and every launch is that of the call on the concatenations).
+    const int32_t *prefix = nullptr;
+    int pos0 = 0, n_shared = 0;
+    int whole_len(int r) const { return pos0 + prompt_lens[r]; }
 
     // Tier one, what can be judged without the model (it fails the same way with no context and no device): check_count, the mode's column counts, check_sizes,
     // the mode's other parameters, then check_prompts, which ends the tier with the context itself.
@@ -4567,12 +4576,16 @@ struct QueueRequests {
     bool check_prompts(const biogpt_hip_ctx *ctx) {
         off.assign((size_t)n_requests + 1, 0);
         for (int r = 0; r < n_requests; r++) {
-            if (prompt_lens[r] < 1) BG_FAIL(false, "empty prompt (request %d)", r);
+            if (prefix && prompt_lens[r] < 0) BG_FAIL(false, "suffix_lens[%d] (%d) is negative", r, prompt_lens[r]);
+            if (!prefix && prompt_lens[r] < 1) BG_FAIL(false, "empty prompt (request %d)", r);      // (behind a prefix no sequence is empty)
             off[(size_t)r + 1] = off[(size_t)r] + (size_t)prompt_lens[r];
         }
+        for (int i = 0; i < pos0; i++)
+            if (prefix[i] < 0) BG_FAIL(false, "token id %d (prefix, position %d) out of range", prefix[i], i);
         for (int r = 0; r < n_requests; r++)
             for (int i = 0; i < prompt_lens[r]; i++)
                 if (prompts[off[(size_t)r] + (size_t)i] < 0) BG_FAIL(false, "token id %d (request %d, position %d) out of range", prompts[off[(size_t)r] + (size_t)i], r, i);
+        n_shared = prefix ? (pos0 - 1) / n_batch * n_batch : 0;
         if (!ctx) BG_FAIL(false, "null context");
         if (!ctx->ready) BG_FAIL(false, "model has no tensors loaded (empty model): cannot evaluate");
         return true;
@@ -4581,7 +4594,11 @@ struct QueueRequests {
     // hold against the model comes behind it.
     bool check_prompts_model(const biogpt_hip_ctx *ctx, const char *what) const {
         const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
+        if (pos0 > P) BG_FAIL(false, "n_prefix (%d) exceeds n_positions (%d)", pos0, P);
+        for (int i = 0; i < pos0; i++)
+            if (prefix[i] >= V) BG_FAIL(false, "token id %d (prefix, position %d) out of range [0, %d)", prefix[i], i, V);
         for (int r = 0; r < n_requests; r++) {
+            if (prefix && prompt_lens[r] > P - pos0) BG_FAIL(false, "n_prefix (%d) + suffix_lens[%d] (%d) exceeds n_positions (%d)", pos0, r, prompt_lens[r], P);
             if (prompt_lens[r] > P) BG_FAIL(false, "prompt_lens[%d] (%d) exceeds n_positions (%d)", r, prompt_lens[r], P);
             for (int i = 0; i < prompt_lens[r]; i++)
                 if (prompts[off[(size_t)r] + (size_t)i] >= V) BG_FAIL(false, "token id %d (request %d, position %d) out of range [0, %d)", prompts[off[(size_t)r] + (size_t)i], r, i, V);
@@ -4627,10 +4644,10 @@ static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc)
     int min_len = P, max_keys = 0;
     long total = 0;
     for (int r = 0; r < R; r++) {
-        rq.cap[(size_t)r] = std::min(rq.n_predicts ? rq.n_predicts[r] : rq.n_predict, P - rq.prompt_lens[r]);
+        rq.cap[(size_t)r] = std::min(rq.n_predicts ? rq.n_predicts[r] : rq.n_predict, P - rq.whole_len(r));
         if (rq.cap[(size_t)r] <= 0) continue;
-        min_len = std::min(min_len, rq.prompt_lens[r]); max_keys = std::max(max_keys, rq.prompt_lens[r] + rq.cap[(size_t)r]);
-        total += rq.prompt_lens[r];
+        min_len = std::min(min_len, rq.whole_len(r)); max_keys = std::max(max_keys, rq.whole_len(r) + rq.cap[(size_t)r]);
+        total += rq.whole_len(r);
     }
     const std::vector<int32_t> &cap = rq.cap;
     if (qc.out_admit_step) std::fill(qc.out_admit_step, qc.out_admit_step + R, -1);
@@ -4644,7 +4661,9 @@ static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc)
 
     XpCallScope xp_scope(ctx);
     XcBatchScope xc_scope{ctx};
-    if (!begin_column_call(ctx, C, C, std::min<long>(total, P))) return -2;
+    // (behind shared rows: they lie in one slot more, behind the units')
+    const SharedRows shared{rq.n_shared, rq.n_shared > 0 ? C : 0};
+    if (!begin_column_call(ctx, C + (shared.n > 0 ? 1 : 0), C, std::min<long>(total, P))) return -2;
     ctx->xc_batch = 0;      // the steps are always the launch chain
     if (!qc.prepare(U)) return -2;
     column_graphs_for(*qc.graphs, U, qc.key_b);
@@ -4654,22 +4673,32 @@ static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc)
 
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> flat, lens, slots;
+    if (shared.n > 0) {      // the shared rows, once: the prompt columns of one sequence in the slot behind the units'
+        const int32_t n = shared.n;
+        if (!pack_column_passes(ctx, rq.prefix, &n, 1, rq.n_batch, [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); },
+                                1, shared.slot))
+            return -2;
+        q.st.prompt_columns += n;
+    }
     while (!q.done()) {
         // ---- refill: the prompts of the admitted requests into the (first) slots of exactly their units, then the admit list and the mode's launches behind it ----
         flat.clear(); lens.clear(); slots.clear();
         const int n_admit = q.refill([&](int unit, int r) {
             const int32_t *p = rq.prompts + rq.off[(size_t)r];
-            const int len = rq.prompt_lens[r];
+            const int own = rq.pos0 - shared.n, len = own + rq.prompt_lens[r];      // behind a prefix: its rows that are not shared, then the suffix (never empty)
             qc.admit(unit, r, (int)slots.size());
-            flat.insert(flat.end(), p, p + len); lens.push_back(len); slots.push_back(unit * qc.per_unit);
+            if (own > 0) flat.insert(flat.end(), rq.prefix + shared.n, rq.prefix + rq.pos0);
+            flat.insert(flat.end(), p, p + rq.prompt_lens[r]); lens.push_back(len); slots.push_back(unit * qc.per_unit);
             if (qc.out_admit_step) qc.out_admit_step[r] = q.st.steps;
             if (qc.out_unit) qc.out_unit[r] = unit;
             q.st.prompt_columns += len;
         });
         if (n_admit > 0) {
             if (!pack_column_passes(ctx, flat.data(), lens.data(), n_admit, rq.n_batch,
-                                    [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); }, 1, 0, SharedRows{},
-                                    slots.data()))
+                                    [&](int n_cols, int t_max, size_t) {
+                                        return enqueue_forward(ctx, shared.n > 0 ? ForwardPass::packed_continuations(n_cols, t_max, n_cols) : ForwardPass::packed_prompts(n_cols, t_max));
+                                    },
+                                    1, 0, shared, slots.data()))
                 return -2;
             HIP_TRY(-2, hipMemcpyAsync(qc.admit_dev, qc.admit_host, qc.admit_bytes * (size_t)n_admit, hipMemcpyHostToDevice, ctx->stream));
             if (!qc.enqueue_admit(n_admit)) return -2;
@@ -4678,7 +4707,7 @@ static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc)
         for (int g = q.group_steps(); g > 0; g--) {
             int t_max = 1;
             for (int unit = 0; unit < U; unit++)
-                if (q.req[(size_t)unit] >= 0) t_max = std::max(t_max, q.position(unit, rq.prompt_lens[q.req[(size_t)unit]]) + 1);
+                if (q.req[(size_t)unit] >= 0) t_max = std::max(t_max, q.position(unit, rq.whole_len(q.req[(size_t)unit])) + 1);
             t_max = std::min(t_max, P);
             if (use_graph) {
                 hipGraphExec_t ge = qc.graphs->exec[qc.gset + graph_bucket(t_max)];
@@ -4738,18 +4767,29 @@ static QueueBufs queue_bufs_at(uint8_t *base) {
 // the pinned twin: the header as the host reads it, the admit list as the host writes it
 struct QueueHost { bgk::QueueHdr hdr; bgk::QueueAdmit admit[bgk::QUEUE_COLS]; };
 
+// prefix != null (biogpt_hip_generate_queue_prefix): request r is prefix ++ prompt r, the prompts are suffixes and may be empty; the first n_shared prefix
+// rows are evaluated once, into the slot behind the columns', and read there by the refill passes and the steps (n_shared == 0: the call on the
+// concatenations, launch for launch).  lp != null: queue_rows_lp_kernel is the selection, and a finished column's rows of the log-probability block go to its
+// request's rows of lp's arrays, in stream order before the column is reused.  Each of the four forms has its own captured steps.
 static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,
                                int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch, int32_t top_k, double top_p, double temp,
                                const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, int32_t *out_admit_step, int32_t *out_column,
-                               double *seconds_out, biogpt_hip_queue_stats *stats) {
+                               double *seconds_out, biogpt_hip_queue_stats *stats, const int32_t *prefix = nullptr, int32_t n_prefix = 0,
+                               const biogpt_hip_gen_logprobs *lp = nullptr) {
     clear_error();
-    if (!prompts) BG_FAIL(-1, "null argument: prompts");
-    if (!prompt_lens) BG_FAIL(-1, "null argument: prompt_lens");
+    if (lp && !check_gen_logprobs(lp, -1)) return -1;
+    if (!prefix && n_prefix != 0) BG_FAIL(-1, "n_prefix must be 0 without a prefix (got %d)", n_prefix);
+    if (prefix && n_prefix < 1) BG_FAIL(-1, "n_prefix must be >= 1 (got %d)", n_prefix);
+    if (!prompts) BG_FAIL(-1, prefix ? "null argument: suffixes" : "null argument: prompts");
+    if (!prompt_lens) BG_FAIL(-1, prefix ? "null argument: suffix_lens" : "null argument: prompt_lens");
     if (!seeds) BG_FAIL(-1, "null argument: seeds");
     if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
     if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
     QueueRequests rq{prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch};
+    rq.prefix = prefix; rq.pos0 = n_prefix;
     if (!rq.check_count()) return -1;
+    if (prefix && (max_columns < 1 || max_columns > bgk::QUEUE_COLS - 1))
+        BG_FAIL(-1, "max_columns must be in [1, %d] behind a prefix (got %d)", bgk::QUEUE_COLS - 1, max_columns);   // one slot holds the prefix
     if (max_columns < 1 || max_columns > bgk::QUEUE_COLS) BG_FAIL(-1, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
     if (!rq.check_sizes()) return -1;
     if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
@@ -4760,19 +4800,30 @@ static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
     const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
     if (top_k > V) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
     if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
+    if (lp && lp->n_top > V) BG_FAIL(-1, "logprobs.n_top (%d) exceeds n_vocab (%d)", lp->n_top, V);
     if (!rq.check_prompts_model(ctx, "generation over a queue")) return -1;
-    std::fill(out_ids, out_ids + (size_t)n_requests * (size_t)n_predict, -1);
+    const size_t n_out = (size_t)n_requests * (size_t)n_predict, K = lp ? (size_t)lp->n_top : 0;
+    std::fill(out_ids, out_ids + n_out, -1);
     std::fill(out_lens, out_lens + n_requests, 0);
+    if (lp) {      // entries at or past a request's length, and those of a request that never takes a column, as genlp_read leaves them
+        std::fill(lp->lp, lp->lp + n_out, 0.0f);
+        if (K > 0) { std::fill(lp->top_ids, lp->top_ids + n_out * K, -1); std::fill(lp->top_lp, lp->top_lp + n_out * K, 0.0f); }
+    }
 
     QueueBufs qb{};
     QueueHost *qh = nullptr;
+    GenLpBufs lb{};
+    // a column's entries lie lp_stride apart in the block: no request generates n_positions tokens, so the block's rows hold any n_predict
+    const int n_shared = rq.n_shared, lp_stride = std::min(n_predict, P);
     int C = 0;
+    biogpt_hip_queue_stats ran{};
     QueueCall qc;
     qc.max_units = max_columns;
-    qc.graphs = &ctx->graphs_queue;
-    qc.out_admit_step = out_admit_step; qc.out_unit = out_column; qc.seconds_out = seconds_out; qc.stats = stats;
+    qc.graphs = &ctx->graphs_queue; qc.gset = (n_shared > 0 ? 6 : 0) + (lp ? 12 : 0);      // plain, shared, lp, shared + lp: a form never replays another's step
+    qc.out_admit_step = out_admit_step; qc.out_unit = out_column; qc.seconds_out = seconds_out; qc.stats = &ran;
     qc.prepare = [&](int units) -> bool {
         C = units;
+        if (lp && (!genlp_prepare(ctx, &lb) || !genlp_upload(lb, lp->n_top, lp_stride))) return false;
         if (!ctx->queue_buf) HIP_TRY(false, hipMalloc(&ctx->queue_buf, queue_bufs_at(nullptr).bytes));
         if (!ctx->queue_host) HIP_TRY(false, hipHostMalloc(&ctx->queue_host, sizeof(QueueHost)));
         qb = queue_bufs_at(ctx->queue_buf);
@@ -4785,18 +4836,24 @@ static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
         HIP_TRY(false, hipMemset(qb.hdr, 0, sizeof(bgk::QueueHdr)));
         return true;
     };
-    qc.step = [&](int t_max) -> bool {
-        if (!enqueue_forward(ctx, ForwardPass::decode_step(C, t_max))) return false;
-        hipLaunchKernelGGL(bgk::queue_rows_kernel, dim3(C), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, qb.ctl, qb.seq, ctx->seq, ctx->seq_gen, P,
-                           qb.limit, qb.hdr);
+    qc.step = [&](int t_max) -> bool {      // (behind shared rows always in place: a queue never runs the column-per-XCD launches)
+        if (!enqueue_forward(ctx, n_shared > 0 ? ForwardPass::decode_step_shared(C, t_max, n_shared) : ForwardPass::decode_step(C, t_max))) return false;
+        if (lp)
+            hipLaunchKernelGGL(bgk::queue_rows_lp_kernel, dim3(C), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, qb.ctl, qb.seq, ctx->seq, ctx->seq_gen,
+                               P, qb.limit, qb.hdr, lb.out());
+        else
+            hipLaunchKernelGGL(bgk::queue_rows_kernel, dim3(C), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, qb.ctl, qb.seq, ctx->seq, ctx->seq_gen, P,
+                               qb.limit, qb.hdr);
         HIP_TRY(false, hipGetLastError());
         return true;
     };
-    qc.admit = [&](int col, int r, int i) {
+    qc.admit = [&](int col, int r, int i) {      // the state of the whole sequence at its last token: the suffix's, or the prefix's behind an empty one
         const int len = prompt_lens[r];
         bgk::QueueAdmit &a = qh->admit[i];
         a = bgk::QueueAdmit{};
-        a.col = col; a.last_token = prompts[rq.off[(size_t)r] + (size_t)(len - 1)]; a.len = len; a.limit = rq.cap[(size_t)r]; a.seed = seeds[r];
+        a.col = col; a.last_token = len > 0 ? prompts[rq.off[(size_t)r] + (size_t)(len - 1)] : prefix[n_prefix - 1]; a.len = rq.whole_len(r);
+        a.limit = rq.cap[(size_t)r]; a.seed = seeds[r];
+        a.n_shared = n_shared; a.shared_slot = n_shared > 0 ? C : 0;
     };
     qc.enqueue_admit = [&](int n_admit) -> bool {
         hipLaunchKernelGGL(bgk::queue_admit_kernel, dim3(n_admit), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, qb.seq, ctx->seq, qb.limit, qb.hdr);
@@ -4807,10 +4864,24 @@ static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
         const int len = std::max(0, std::min(qh->hdr.len[col], rq.cap[(size_t)r]));
         if (len > 0)
             HIP_TRY(-1, hipMemcpyAsync(out_ids + (size_t)r * (size_t)n_predict, ctx->seq_gen + (size_t)col * P, (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (lp && len > 0) {      // the column's rows of the block -> the request's rows
+            const size_t src = (size_t)col * (size_t)lp_stride, dst = (size_t)r * (size_t)n_predict;
+            HIP_TRY(-1, hipMemcpyAsync(lp->lp + dst, lb.lp + src, (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (K > 0) {
+                HIP_TRY(-1, hipMemcpyAsync(lp->top_ids + dst * K, lb.top_ids + src * K, (size_t)len * K * 4, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(-1, hipMemcpyAsync(lp->top_lp + dst * K, lb.top_lp + src * K, (size_t)len * K * 4, hipMemcpyDeviceToHost, ctx->stream));
+            }
+        }
         out_lens[r] = len;
         return len;
     };
-    return run_queue_call(ctx, rq, qc);
+    const int rc = run_queue_call(ctx, rq, qc);
+    if (stats) *stats = ran;
+    // (a call that failed, or in which no request had room for a token, leaves the stats of the last call that generated)
+    if (rc == 0 && prefix && ran.columns > 0) {
+        ctx->prefix_stats[0] = n_shared; ctx->prefix_stats[1] = ran.prompt_columns; ctx->prefix_stats[2] = 0; ctx->prefix_stats[3] = ran.columns;
+    }
+    return rc;
 }
 
 int biogpt_hip_generate_queue(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,
@@ -4820,6 +4891,18 @@ int biogpt_hip_generate_queue(biogpt_hip_ctx *ctx, const int32_t *prompts, const
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_queue_once(ctx, prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch, top_k, top_p, temp, seeds, eos_id,
                                    out_ids, out_lens, out_admit_step, out_column, seconds_out, stats);
+    });
+}
+
+// biogpt_hip_generate_queue of the requests prefix ++ suffix r behind the shared prefix rows (prefix == null: of the suffixes themselves), with the
+// log-probabilities of the generated tokens where asked
+int biogpt_hip_generate_queue_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *suffixes, const int32_t *suffix_lens, int32_t n_requests,
+                                     const int32_t *n_predicts, int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch, int32_t top_k, double top_p,
+                                     double temp, const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, int32_t *out_admit_step,
+                                     int32_t *out_column, double *seconds_out, biogpt_hip_queue_stats *stats, const biogpt_hip_gen_logprobs *logprobs) {
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_queue_once(ctx, suffixes, suffix_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch, top_k, top_p, temp, seeds, eos_id,
+                                   out_ids, out_lens, out_admit_step, out_column, seconds_out, stats, prefix, n_prefix, logprobs);
     });
 }
 

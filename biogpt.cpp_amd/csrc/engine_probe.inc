@@ -898,6 +898,81 @@ int biogpt_hip_genlp_rows_device(int device, int32_t mode, const float *rows, in
     return 0;
 }
 
+// One launch of queue_rows_lp_kernel (with_lp != 0) or queue_rows_kernel over rows held in host memory (tests of the kernels themselves): row r is column r.
+// The caller builds what a running queue would hold and gets it back as the launch left it: states [n_rows][8] (the SeqState words), finished [n_rows]
+// (SampleSeq::finished), mt_states [n_rows][625], hdr [1 + 2 * n_rows] (n_live, then fin and len of the rows); limits [n_rows] is read only.  ids_out
+// [n_rows][stride] the token histories, lp_out [n_rows][stride] and top_ids_out / top_lp_out [n_rows][stride][n_top] the rows of the log-probability
+// block (null with n_top 0): all filled with 0xff bytes before the launch, so what the kernel does not write stays so.
+int biogpt_hip_queue_rows_device(int device, int32_t with_lp, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t stride, int32_t top_k, double top_p,
+                                 double temp, int32_t eos_id, uint32_t *mt_states, int32_t *states, const int32_t *limits, int32_t *finished, int32_t *hdr,
+                                 int32_t *ids_out, float *lp_out, int32_t *top_ids_out, float *top_lp_out) {
+    clear_error();
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!mt_states) BG_FAIL(-1, "mt_states is NULL");
+    if (!states) BG_FAIL(-1, "states is NULL");
+    if (!limits) BG_FAIL(-1, "limits is NULL");
+    if (!finished) BG_FAIL(-1, "finished is NULL");
+    if (!hdr) BG_FAIL(-1, "hdr is NULL");
+    if (!ids_out) BG_FAIL(-1, "ids_out is NULL");
+    if (n_rows < 1 || n_rows > bgk::QUEUE_COLS) BG_FAIL(-1, "n_rows must be in [1, %d]", bgk::QUEUE_COLS);
+    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
+    if (stride < 1 || stride > 1024) BG_FAIL(-1, "stride must be in [1, 1024]");
+    const biogpt_hip_gen_logprobs req{n_top, lp_out, top_ids_out, top_lp_out};
+    if (!check_gen_logprobs(&req, n_vocab)) return -1;
+    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > n_vocab) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
+    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
+    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
+    if (eos_id < -1 || eos_id >= n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, n_vocab);
+    for (int r = 0; r < n_rows; r++) {
+        if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
+        if (states[(size_t)r * 8 + 2] < 0) BG_FAIL(-1, "n_gen is negative (row %d)", r);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    static_assert(sizeof(bgk::SeqState) == 32, "eight words per column state");
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, entries = (size_t)n_rows * (size_t)stride, lp_b = genlp_bufs_at(nullptr, entries, (size_t)n_top).bytes;
+    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = entries * 4;
+    std::vector<uint8_t> h(queue_bufs_at(nullptr).bytes, 0);
+    const QueueBufs hq = queue_bufs_at(h.data());
+    *hq.ctl = sample_ctl_of(top_k, eos_id, 0, top_p, temp);
+    hq.hdr->n_live = hdr[0];
+    for (int r = 0; r < n_rows; r++) {
+        std::memcpy(hq.seq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
+        hq.seq[r].finished = finished[r];
+        hq.limit[r] = limits[r];
+        hq.hdr->fin[r] = hdr[1 + r]; hq.hdr->len[r] = hdr[1 + n_rows + r];
+    }
+    ByteLayout l;      // [logits | the queue's block | column states | ids | the log-probability block]
+    const size_t o_lg = l.part(lg_b), o_q = l.part(h.size()), o_st = l.part(st_b), o_id = l.part(id_b), o_lp = l.part(lp_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    const QueueBufs qb = queue_bufs_at(d.p + o_q);
+    const GenLpBufs lb = genlp_bufs_at(d.p + o_lp, entries, (size_t)n_top);
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_q, h.data(), h.size(), hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_st, states, st_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_id, 0xff, l.bytes() - o_id));
+    if (!genlp_upload(lb, n_top, stride)) return -2;
+    if (with_lp)
+        hipLaunchKernelGGL(bgk::queue_rows_lp_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, qb.ctl, qb.seq,
+                           d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), stride, qb.limit, qb.hdr, lb.out());
+    else
+        hipLaunchKernelGGL(bgk::queue_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, qb.ctl, qb.seq,
+                           d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), stride, qb.limit, qb.hdr);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(states, d.p + o_st, st_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_q, h.size(), hipMemcpyDeviceToHost));
+    if (!genlp_read(lb, &req, n_rows, stride, nullptr)) return -2;
+    hdr[0] = hq.hdr->n_live;
+    for (int r = 0; r < n_rows; r++) {
+        std::memcpy(mt_states + (size_t)r * 625, hq.seq[r].mt, 625 * 4);
+        finished[r] = hq.seq[r].finished;
+        hdr[1 + r] = hq.hdr->fin[r]; hdr[1 + n_rows + r] = hq.hdr->len[r];
+    }
+    return 0;
+}
+
 // SURVEY 8 f1 on the device: `nrows` rows of `k` f32 values (host memory) -> the file's block format of `type`, byte-identical to
 // the host quantizer (biogpt_hip_quantize_file uses the host one: it has to work without a GPU)
 int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, int64_t nrows, int64_t k, uint8_t *dst) {

@@ -534,8 +534,8 @@ int biogpt_hip_generate_lookup(biogpt_hip_ctx *ctx, const int32_t *prompts /* co
  * prompt tokens evaluated; busy_column_steps = the sum of out_lens; column_steps = C * steps.  n_requests is limited by host memory alone: prompts stay on
  * the host until admitted.  max_columns in [1, 512], group in [1, 64], n_predicts[r] in [0, n_predict], top_k in [1, 64], temp finite and > 0, top_p finite,
  * eos_id in [-1, n_vocab), no empty prompt, prompt_lens[r] <= n_positions.  The context's own K / V cache, position and logits row are left alone.  Needs
- * the BioGPT-base fast chain (block-quantized weights); anything else fails with -1.  No rules, trie, prefix, log-probabilities or several samples per
- * request; the steps always run as the launch chain.  Returns 0, or < 0 on error (argument errors, -1, the message names the field, come before any HIP
+ * the BioGPT-base fast chain (block-quantized weights); anything else fails with -1.  No rules, trie or several samples per request (a shared prefix and
+ * log-probabilities: biogpt_hip_generate_queue_prefix); the steps always run as the launch chain.  Returns 0, or < 0 on error (argument errors, -1, the message names the field, come before any HIP
  * call). */
 typedef struct biogpt_hip_queue_stats {
     int32_t columns, steps, groups, admissions, prompt_columns;
@@ -772,6 +772,37 @@ int biogpt_hip_generate_sample_lp(biogpt_hip_ctx *ctx, const int32_t *prefix /* 
 int biogpt_hip_genlp_rows_device(int device, int32_t mode /* 0 greedy, 1 sampled */, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top,
                                  int32_t top_k, double top_p, double temp, uint32_t *mt_states, int32_t *ids_out, float *lp_out, int32_t *top_ids_out,
                                  float *top_lp_out);
+
+/* ---- generation over a queue behind a shared prefix, with log-probabilities ----
+ * biogpt_hip_generate_queue of the requests prefix ++ suffix r (suffixes concatenated, suffix_lens their lengths; behind a prefix a suffix may be empty):
+ * the first n_shared prefix rows -- the largest multiple of n_batch <= n_prefix - 1 -- are evaluated ONCE, inside the timed span, into the slot behind
+ * the columns', and the refill passes and the steps read them in place; a refill evaluates prefix[n_shared:] ++ suffix of the admitted requests alone.
+ * Request r's clamp is n_r = min(n_predicts[r], n_positions - n_prefix - suffix_lens[r]).  Its ids and length -- and with logprobs its lp / top_ids / top_lp
+ * rows -- are those of biogpt_hip_generate_sample_prefix / biogpt_hip_generate_sample_lp of the request alone (the same prefix, n_samples 1, n_r, the same
+ * sampler, seeds[r], eos_id, n_batch), bit for bit, whatever else is in the queue and whatever max_columns and group are: the ids are those of
+ * biogpt_hip_generate_queue on the concatenations, as are out_admit_step, out_column and stats but for stats.prompt_columns, the prompt columns evaluated:
+ * n_shared + the sum over admitted requests of (n_prefix - n_shared + suffix_lens[r]).  n_shared == 0 (n_prefix <= n_batch): nothing is shared, no slot
+ * is reserved and every launch is that of biogpt_hip_generate_queue on the concatenations.  prefix == NULL requires n_prefix == 0; with logprobs == NULL as
+ * well the call IS biogpt_hip_generate_queue, with logprobs the plain queue with log-probabilities.  logprobs (or NULL): the struct above with
+ * lp [n_requests][n_predict] and top_ids / top_lp [n_requests][n_predict][n_top] (n_predict the row stride as GIVEN); entries at or past a request's length,
+ * and every entry of a request that never takes a column, read 0 / -1 / 0.  max_columns in [1, 511] behind a prefix (one K / V slot holds the shared rows);
+ * n_prefix >= 1, n_prefix + suffix_lens[r] <= n_positions; everything else as biogpt_hip_generate_queue.  Afterwards biogpt_hip_prefix_stats reads
+ * {n_shared, stats.prompt_columns, 0, columns}.  No rules, trie, wide sampler or several samples per request.  Returns 0, or < 0 on error (argument errors, -1,
+ * come before any HIP call: first those of logprobs, then what needs no model, with no context and no device). */
+int biogpt_hip_generate_queue_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix /* or NULL */, int32_t n_prefix, const int32_t *suffixes /* concatenated */,
+                                     const int32_t *suffix_lens, int32_t n_requests, const int32_t *n_predicts /* or NULL */, int32_t n_predict,
+                                     int32_t max_columns, int32_t group, int32_t n_batch, int32_t top_k, double top_p, double temp, const uint32_t *seeds,
+                                     int32_t eos_id, int32_t *out_ids, int32_t *out_lens, int32_t *out_admit_step /* may be NULL */,
+                                     int32_t *out_column /* may be NULL */, double *seconds_out, biogpt_hip_queue_stats *stats /* may be NULL */,
+                                     const biogpt_hip_gen_logprobs *logprobs /* or NULL */);
+/* Test hook: one launch of the queue's step kernel alone -- queue_rows_lp_kernel, or with with_lp == 0 queue_rows_kernel -- over rows held in host memory
+ * ([n_rows][n_vocab] f32; row r is column r, n_rows <= 512).  In and out: states [n_rows][8] (n_past, token, n_gen, seq_id, t_vis, 3 more words),
+ * finished [n_rows], mt_states [n_rows][625], hdr [1 + 2 * n_rows] (n_live, fin[], len[]); limits [n_rows] is read.  ids_out [n_rows][stride],
+ * lp_out [n_rows][stride], top_ids_out / top_lp_out [n_rows][stride][n_top] (NULL with n_top 0) are preset to 0xff bytes: what the launch does not write
+ * stays so.  Argument errors return -1 before any HIP call.  Returns 0, < 0 on error. */
+int biogpt_hip_queue_rows_device(int device, int32_t with_lp, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t stride, int32_t top_k,
+                                 double top_p, double temp, int32_t eos_id, uint32_t *mt_states, int32_t *states, const int32_t *limits, int32_t *finished,
+                                 int32_t *hdr, int32_t *ids_out, float *lp_out, int32_t *top_ids_out, float *top_lp_out);
 
 /* ---- hidden states, pooled embeddings, classification heads (no counterpart in the reference) ----
  * The activations in front of the lm_head, from the causal passes of biogpt_hip_score without the lm_head and the log-softmax.
