@@ -577,6 +577,8 @@ SYMBOLS = [
     ("biogpt_hip_resident_stats", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("biogpt_hip_chunk_launches", C.c_int64, [_P]),
     ("biogpt_hip_mfma_launches", C.c_int64, [_P]),
+    ("biogpt_hip_chain_kind", C.c_int, [_P]),
+    ("biogpt_hip_wide_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_stamps", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     ("biogpt_hip_generate_launches", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
@@ -660,6 +662,8 @@ SYMBOLS = [
     ("biogpt_hip_queue_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32] + [_P] * 9),
     ("biogpt_hip_attn_device", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("biogpt_hip_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32] + [_P] * 7 + [C.c_int32] * 3 + [_P] * 7),
+    ("biogpt_hip_wide_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 4),
+    ("biogpt_hip_wide_chain_bench", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P]),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_attn_prefix_bench", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     ("biogpt_hip_hidden", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
@@ -814,6 +818,51 @@ def chain_device(op, route=None, wtype=0, M=0, N=1, w_rows=None, x=None, ln_w=No
         raise BiogptError(_err())
     res["launched"] = launched
     return res
+
+
+WIDE_EPIS = {"QKV": 0, "RESID": 1, "GELU": 2, "LOGITS": 3}
+
+
+def wide_chain_device(epi, wtype, M, K, N, w_rows, aq_q, aq_d, aq_s, bias=None, resid=None, dev_state=None, seq_states=None, col_mode=0, P=0, k_slots=None,
+                      v_slots=None, device=0):
+    """One stand-alone launch of the wide chain's linear stage (biogpt_hip_wide_chain_device; include/biogpt_hip.h has the inputs of each epilogue).  epi by name
+    (WIDE_EPIS).  Returns a dict of the outputs WHOLE as the probe allocated them, guard column and rows included and preset to 0xff bytes: "out" float32
+    [cols, ldo] ([cols, K] for QKV), "k" / "v" (copies of k_slots / v_slots after the launch, QKV), "launched" (threads, grid x, grid y, LDS bytes, cols, ldo,
+    row tiles, 0).  Raises BiogptError on a refusal."""
+    cols, ldo = ((N + 15) & ~15) + 1, ((M + 127) & ~127) + 16
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    res = {"out": np.zeros((cols, K if epi == "QKV" else ldo), np.float32)}
+    n_slots = 0
+    if epi == "QKV":
+        res["k"], res["v"] = np.array(k_slots, dtype=np.float32, order="C"), np.array(v_slots, dtype=np.float32, order="C")
+        n_slots = res["k"].shape[0]
+        assert res["k"].shape == res["v"].shape == (n_slots, K // 64, P, 64)
+    launched = np.zeros(8, np.int32)
+    o = lambda name: res[name].ctypes.data if name in res else None
+    rc = lib().biogpt_hip_wide_chain_device(int(device), WIDE_EPIS[epi], int(wtype), int(M), int(K), int(N), ptr(w_rows, np.uint8), ptr(aq_q, np.int8),
+                                            ptr(aq_d, np.float32), ptr(aq_s, np.uint32), ptr(bias, np.float32), ptr(resid, np.float32), ptr(dev_state, np.int32),
+                                            ptr(seq_states, np.int32), int(col_mode), int(P), n_slots, o("k"), o("v"), o("out"), launched.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    res["launched"] = launched
+    return res
+
+
+def wide_chain_bench(which, wtype, M, K, N, reps=9, device=0):
+    """A linear stage alone, timed (biogpt_hip_wide_chain_bench): microseconds of `reps` launches, float32 [reps].  which "wide": the wide chain's kernel at
+    any (M, K); "base": the BioGPT-base matrix-core kernel at (1024, 1024) or (1024, 4096)."""
+    us = np.zeros(int(reps), np.float32)
+    if lib().biogpt_hip_wide_chain_bench(int(device), {"wide": 0, "base": 1}[which], int(wtype), int(M), int(K), int(N), int(reps), us.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return us
 
 
 def write_synthetic(path, seed=0x42494F47, **hparams):
@@ -1681,6 +1730,18 @@ class BiogptModel:
     def mfma_launches(self):
         """Launches of the many-column chain that went to the matrix-core kernels (biogpt_hip_mfma_launches)."""
         return int(lib().biogpt_hip_mfma_launches(self._h))
+
+    def chain_kind(self):
+        """Which many-column layer chain the file has (biogpt_hip_chain_kind): 0 none, 1 the BioGPT-base chain, 2 the wide chain (any other block-quantized file
+        with head size 64, d_model a multiple of 64 and d_ff of 32)."""
+        k = int(lib().biogpt_hip_chain_kind(self._h))
+        if k < 0:
+            raise BiogptError(_err())
+        return k
+
+    def wide_launches(self):
+        """Linear-stage launches of the wide chain (biogpt_hip_wide_launches); 0 on a BioGPT-base file."""
+        return int(lib().biogpt_hip_wide_launches(self._h))
 
     def chunk_launches(self):
         """Evals of 2 .. 8 tokens that went through the column-per-XCD launch (biogpt_hip_chunk_launches)."""

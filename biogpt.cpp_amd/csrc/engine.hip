@@ -359,6 +359,7 @@ struct biogpt_hip_ctx {
     int state_n_past = 0, state_chunk = 0; // what the last upload_state put into the device state
     int64_t xc_launches = 0;               // evals that went through the chunk launch (biogpt_hip_chunk_launches)
     int64_t mfma_launches = 0;             // launches of the many-column chain that went to the matrix-core kernels (biogpt_hip_mfma_launches)
+    int64_t wide_launches = 0;             // linear-stage launches of the wide chain (kernels_mfma_wide.hip.h; biogpt_hip_wide_launches)
     int32_t gen_launch_tokens[16] = {0}; int gen_launches = 0;   // the last biogpt_hip_generate_greedy: tokens of each multi-token pipelined launch (biogpt_hip_generate_launches)
     int32_t prefix_stats[4] = {0, 0, 0, 0};   // of the last biogpt_hip_generate_*_prefix call that generated tokens: shared rows, prompt columns evaluated, path (0 in place, 1 copied), columns
     int xc_batch = 0;                      // a column generation call with 2 .. 8 columns holds the device's pipeline slot (choose_column_path): its decode steps run as column-per-XCD launches (streams mode)
@@ -579,6 +580,18 @@ hipError_t launch_chain_nc(ChainOp op, const bgk::MatvecParams &p, hipStream_t s
 // report: null, or five words (a ChainLaunch) that the launch fills in
 extern "C" int bg_mfma_launch(int wt, int op, const void *params, size_t params_bytes, const void *img, size_t img_bytes, hipStream_t st, int32_t *report);
 extern "C" int bg_mfma_retile(int wt, const void *src, size_t src_bytes, uint8_t *dq, uint8_t *ds, hipStream_t st);
+// the wide chain (kernels_mfma_wide.hip.h, mfma_wide_tu.hip): the many-column linear stage at any K % 32 == 0, and the Q8 producers in front of it
+extern "C" int bg_wide_launch(int wt, int epi, const void *params, size_t params_bytes, const void *img, size_t img_bytes, hipStream_t st);
+extern "C" int bg_wide_quantize(const float *x, int ldx, int K, int N, const float *ln_w, const float *ln_b, float eps, int q81, int8_t *oq_q, float *oq_d,
+                                uint32_t *oq_s, hipStream_t st);
+// Which many-column layer chain a file has (biogpt_hip_chain_kind).  1: BioGPT-base widths, every launch as before.  2: the wide chain -- any other block-quantized
+// file with head size 64 whose widths the kernel's tiles divide; passes over column states only, the context's own columns stay on the generic kernels.
+enum ChainKind : int { CHAIN_NONE = 0, CHAIN_BASE = 1, CHAIN_WIDE = 2 };
+inline int chain_kind_of(const biogpt_hip_hparams &hp) {
+    if (!is_quantized(ftype_to_type(hp.ftype)) || hp.n_head < 1 || hp.d_model % hp.n_head != 0 || hp.d_model / hp.n_head != 64) return CHAIN_NONE;
+    if (hp.d_model == 1024 && hp.d_ff == 4096) return CHAIN_BASE;
+    return (hp.d_model % 64 == 0 && hp.d_ff >= 32 && hp.d_ff % 32 == 0) ? CHAIN_WIDE : CHAIN_NONE;
+}
 template <int WT>
 hipError_t launch_chain_mfma(ChainOp op, const bgk::MatvecParams &p, const bgk::DevMatrix &img, hipStream_t st, ChainLaunch *rep) {
     int site = -1;
@@ -708,10 +721,11 @@ bgk::DevMatrix tile_matrix(const biogpt_hip_ctx *c, const MatSlot &m) {
 }
 // The image is addressed by whole 16-row tiles (retile_kernel, matmul_mfma_kernel): a matrix has one only when its rows are whole tiles.  Every layer matrix of the
 // chain's shapes is; an lm_head of a vocabulary that is no multiple of 16 is not, and stays on the 8-column kernel (PassLaunch::tile).
-inline bool tile_image_ok(const MatSlot &m) { return is_quantized(m.type) && m.M % 16 == 0; }
+// A wide file (chain_kind_of == CHAIN_WIDE) has no 8-column kernel to fall back to: its image holds ceil(M / 16) tiles of every matrix, the last one zero-padded.
+inline bool tile_image_ok(const MatSlot &m, bool wide = false) { return is_quantized(m.type) && (wide || m.M % 16 == 0); }
 // where a matrix's image lies: the 32-byte expanded blocks, then the f32 scales ({d, m} for Q4_1 / Q5_1), each part starting on 256 bytes; off: the running offset
 inline void tile_image_place(int32_t type, int64_t M, int64_t K, size_t &off, size_t &xq, size_t &xs) {
-    const size_t nblk = (size_t)M * (size_t)(K / QK);
+    const size_t nblk = (size_t)((M + 15) / 16 * 16) * (size_t)(K / QK);      // whole tiles (M itself for every matrix of a BioGPT-base file)
     const bool q81 = type == T_Q4_1 || type == T_Q5_1;
     xq = off; off = (off + nblk * 32 + 255) & ~(size_t)255;
     xs = off; off = (off + nblk * (q81 ? 8 : 4) + 255) & ~(size_t)255;
@@ -719,8 +733,9 @@ inline void tile_image_place(int32_t type, int64_t M, int64_t K, size_t &off, si
 bool ensure_tile_images(biogpt_hip_ctx *c) {
     if (c->tile_img || c->tile_img_failed) return true;
     size_t off = 0;
+    const bool wide = chain_kind_of(c->hp) == CHAIN_WIDE;
     auto place = [&](MatSlot &m) {
-        if (!tile_image_ok(m)) return;
+        if (!tile_image_ok(m, wide)) return;
         tile_image_place(m.type, m.M, m.K, off, m.xq, m.xs);
     };
     for (auto &L : c->plan.layers) { place(L.qkv); place(L.o); place(L.fc1); place(L.fc2); }
@@ -734,8 +749,13 @@ bool ensure_tile_images(biogpt_hip_ctx *c) {
     }
     bool retile_ok = true;
     auto one = [&](const MatSlot &m) {
-        if (!tile_image_ok(m)) return;
+        if (!tile_image_ok(m, wide)) return;
         const bgk::DevMatrix src = dev_matrix(c, m);
+        if (m.M % 16 != 0) {      // the rows the last tile has beyond the matrix: zero weights, zero scales
+            const size_t nblk = (size_t)((m.M + 15) / 16 * 16) * (size_t)(m.K / QK);
+            if (hipMemsetAsync(c->tile_img + m.xq, 0, nblk * 32, c->stream) != hipSuccess ||
+                hipMemsetAsync(c->tile_img + m.xs, 0, nblk * ((m.type == T_Q4_1 || m.type == T_Q5_1) ? 8 : 4), c->stream) != hipSuccess) retile_ok = false;
+        }
         if (bg_mfma_retile(m.type, &src, sizeof(src), c->tile_img + m.xq, c->tile_img + m.xs, c->stream) != (int)hipSuccess) retile_ok = false;
     };
     for (const auto &L : c->plan.layers) { one(L.qkv); one(L.o); one(L.fc1); one(L.fc2); }
@@ -1186,6 +1206,7 @@ struct PassLaunch {
     int N, D, F, V, H, P, dk;
     int attn_threads;               // attention workgroup size of the generic kernel
     bool chain, pchain, mfma;       // the single-token fast chain; its many-column form; on the int8 matrix cores
+    bool wchain;                    // the wide chain: a pass over column states of a block-quantized file that is not BioGPT-base (kernels_mfma_wide.hip.h)
     int q81;
     const bgk::SeqState *seq;       // column states of a pass over the per-sequence caches (null: the context's own columns)
     int col_mode;                   // 1: packed columns
@@ -1199,6 +1220,17 @@ struct PassLaunch {
         ChainLaunch rep{};
         const hipError_t e = launch_chain(op, p, st, image, &rep);
         if (e == hipSuccess && rep.kernel >= CK_MFMA_1) c->mfma_launches++;
+        return e;
+    }
+    // The wide chain's stage: the N columns' Q8 blocks into side buffer `slot` (LayerNorm first when ln_w is given), then the matrix-core kernel on the padded image.
+    // x: the f32 rows [N][W.K] the stage reads
+    hipError_t wide_stage(int epi, bgk::MatvecParams &p, const MatSlot &m, const float *x, int slot, const float *ln_w = nullptr, const float *ln_b = nullptr) {
+        hipError_t e = (hipError_t)bg_wide_quantize(x, (int)m.K, (int)m.K, p.N, ln_w, ln_b, 1e-5f, q81, c->aq_q[slot], c->aq_d[slot], c->aq_s[slot], st);
+        if (e != hipSuccess) return e;
+        p.aq_q = c->aq_q[slot]; p.aq_d = c->aq_d[slot]; p.aq_s = c->aq_s[slot];
+        img = tile_matrix(c, m);
+        e = (hipError_t)bg_wide_launch(m.type, epi, &p, sizeof(p), &img, sizeof(img), st);
+        if (e == hipSuccess) c->wide_launches++;
         return e;
     }
 };
@@ -1387,7 +1419,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.vcache = k.vroot + (size_t)l * P * D;
         if (k.seq) { p.seq = k.seq; p.col_mode = k.col_mode; p.kv_seq_stride = k.seq_stride; }
         p.q_scale = 1.0f / sqrtf((float)k.dk);
-        if (k.pchain) {
+        if (k.wchain) {
+            HIP_TRY(false, k.wide_stage(bgk::EPI_QKV, p, L.qkv, c->x, 2, p.ln_w, p.ln_b));
+        } else if (k.pchain) {
             HIP_TRY(false, launch_lnq(c, c->x, N, L.ln0_w, L.ln0_b, k.q81, st));
             p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
             HIP_TRY(false, k.chain_launch(CHAIN_QKV_Q8, p, k.tile(L.qkv)));
@@ -1402,7 +1436,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.x = c->att; p.ldx = D; p.N = N;
         p.bias = dev_vec(c, L.o_b);
         p.resid = c->x; p.ldr = D; p.out = c->x1; p.ldo = D;
-        if (k.chain) {
+        if (k.wchain) {      // (the attention kernels wrote f32 rows: no Q8 side output without the base chain)
+            HIP_TRY(false, k.wide_stage(bgk::EPI_RESID, p, L.o, c->att, 0));
+        } else if (k.chain) {
             p.aq_q = c->aq_q[0]; p.aq_d = c->aq_d[0]; p.aq_s = c->aq_s[0];
             HIP_TRY(false, k.chain_launch(CHAIN_OPROJ, p, k.tile(L.o)));
         } else {
@@ -1416,7 +1452,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.ln_w = dev_vec(c, L.ln1_w); p.ln_b = dev_vec(c, L.ln1_b);
         p.bias = dev_vec(c, L.fc1_b);
         p.out = c->h; p.ldo = F;
-        if (k.pchain) {
+        if (k.wchain) {
+            HIP_TRY(false, k.wide_stage(bgk::EPI_GELU, p, L.fc1, c->x1, 2, p.ln_w, p.ln_b));
+        } else if (k.pchain) {
             HIP_TRY(false, launch_lnq(c, c->x1, N, L.ln1_w, L.ln1_b, k.q81, st));
             p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
             p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
@@ -1434,7 +1472,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.x = c->h; p.ldx = F; p.N = N;
         p.bias = dev_vec(c, L.fc2_b);
         p.resid = c->x1; p.ldr = D; p.out = c->x; p.ldo = D;
-        if (k.chain) {
+        if (k.wchain) {
+            HIP_TRY(false, k.wide_stage(bgk::EPI_RESID, p, L.fc2, c->h, 1));
+        } else if (k.chain) {
             p.aq_q = c->aq_q[1]; p.aq_d = c->aq_d[1]; p.aq_s = c->aq_s[1];
             HIP_TRY(false, k.chain_launch(CHAIN_FC2, p, k.tile(L.fc2)));
         } else {
@@ -1463,6 +1503,12 @@ bool enqueue_final(PassLaunch &k) {
     const MatSlot &m = c->plan.lm_head;
     const MvShape s = mv_shape(m.type, m.M, m.K);
     bgk::MatvecParams p = mv_base(c, m, s);
+    if (rows == Rows::All && k.wchain) {  // the wide chain: LayerNorm+Q8 of the columns that get a row, then the lm_head on the matrix cores (its last row tile may be partial)
+        const int head_from = k.pass.head_from;
+        p.N = N - head_from; p.out = c->logits_all; p.ldo = V;
+        HIP_TRY(false, k.wide_stage(bgk::EPI_LOGITS, p, m, c->x + (size_t)head_from * D, 2, dev_vec(c, c->plan.ln_w), dev_vec(c, c->plan.ln_b)));
+        return true;
+    }
     if (rows == Rows::All && k.pchain) {  // every column needs its logits row: LayerNorm+Q8 once, then the 8-column mat-vec (matrix cores from 64 columns)
         // head_from > 0: the kernel a pass of n_rows columns alone would take.  Below 64 rows that is the 8-column VALU kernel, where score_batch of
         // the concatenation (64 columns or more) takes the matrix cores: the bit-for-bit promise of biogpt_hip_score_continuations rests on the two
@@ -1519,7 +1565,12 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     k.pchain = k.chain && (N > 1 || batch);   // several columns: LayerNorm+Q8 once per site (lnq_kernel), 8 columns per workgroup
     // enough columns to fill 16-wide MFMA tiles: the chain runs on the int8 matrix cores from the row-tiled weight image
     k.mfma = k.pchain && N >= (pass.cols == Cols::PerSequence ? MFMA_MIN_DECODE_COLS : MFMA_MIN_PASS_COLS) && c->tile_img != nullptr;
-    if (batch && !k.chain) BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)");
+    // a pass over column states of any other block-quantized file with head size 64: the wide chain (the context's own columns stay on the generic kernels)
+    k.wchain = !k.chain && batch && chain_kind_of(hp) == CHAIN_WIDE && t_max <= 1024;
+    if (batch && !k.chain && !k.wchain)
+        BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64) or the wide one (block-quantized weights, head size 64, d_model a multiple of 64, d_ff of 32)");
+    if (k.wchain && (c->tile_img == nullptr || pass.rows == Rows::Last || pass.rows == Rows::AllGeneric))
+        BG_FAIL(false, "internal: a wide fast chain pass without its row-tiled weight image, or with rows it does not serve");
     k.seq = pass.cols == Cols::Packed ? (pass.col_states ? pass.col_states : c->cols) : (batch ? c->seq : nullptr);
     k.col_mode = pass.cols == Cols::Packed ? 1 : 0;
     k.seq_stride = (int64_t)hp.n_layer * k.P * k.D;
@@ -2406,6 +2457,11 @@ int biogpt_hip_eval_inplace(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t 
 }
 int64_t biogpt_hip_chunk_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->xc_launches : -1; }
 int64_t biogpt_hip_mfma_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->mfma_launches : -1; }
+int64_t biogpt_hip_wide_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->wide_launches : -1; }
+int biogpt_hip_chain_kind(const biogpt_hip_ctx *ctx) {
+    if (!ctx) BG_FAIL(-1, "null context");
+    return chain_kind_of(ctx->hp);
+}
 int biogpt_hip_fpipe_stamps(biogpt_hip_ctx *ctx, uint64_t *out, int n) {
     if (!ctx || !out || n < 0 || ctx->fp_state != 1 || !ctx->opt.fpipe_stamps) return -1;
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
@@ -2447,8 +2503,14 @@ static bool ensure_seq_caches(biogpt_hip_ctx *ctx, int n_seqs) {
     const size_t seq_stride = (size_t)ctx->hp.n_layer * ctx->hp.n_positions * ctx->hp.d_model;
     for (void *p : {(void *)ctx->bk, (void *)ctx->bv, (void *)ctx->seq, (void *)ctx->seq_gen}) if (p) (void)hipFree(p);
     ctx->bk = ctx->bv = nullptr; ctx->seq = nullptr; ctx->seq_gen = nullptr; ctx->batch_cap = 0;
-    HIP_TRY(false, hipMalloc(&ctx->bk, seq_stride * 4 * n_seqs));
-    HIP_TRY(false, hipMalloc(&ctx->bv, seq_stride * 4 * n_seqs));
+    // every column owns a full F32 K / V cache (BioGPT-base: 201 MB; 48 layers at d_model 1600: 629 MB): a request that does not fit says how much it was
+    if (hipMalloc(&ctx->bk, seq_stride * 4 * n_seqs) != hipSuccess || hipMalloc(&ctx->bv, seq_stride * 4 * n_seqs) != hipSuccess) {
+        (void)hipGetLastError();
+        if (ctx->bk) (void)hipFree(ctx->bk);
+        ctx->bk = ctx->bv = nullptr;
+        BG_FAIL(false, "no device memory for the K / V caches of %d columns: %.1f GB (%.0f MB per column = 2 x n_layer %d x n_positions %d x d_model %d x 4 bytes)", n_seqs,
+                (double)seq_stride * 8.0 * n_seqs / 1e9, (double)seq_stride * 8.0 / 1e6, ctx->hp.n_layer, ctx->hp.n_positions, ctx->hp.d_model);
+    }
     HIP_TRY(false, hipMalloc(&ctx->seq, sizeof(bgk::SeqState) * n_seqs));
     HIP_TRY(false, hipMalloc(&ctx->seq_gen, (size_t)n_seqs * ctx->hp.n_positions * 4));
     ctx->batch_cap = n_seqs;
@@ -2614,10 +2676,17 @@ static bool check_prompts(const biogpt_hip_ctx *c, const int32_t *prompts, const
     return true;
 }
 
-static bool check_fast_chain(const biogpt_hip_ctx *c, const char *what) {
-    const auto &hp = c->hp;
-    if (!(is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.d_model / hp.n_head == 64))
-        BG_FAIL(false, "%s needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64)", what);
+// The gate of every call over column states.  wide_ok: the call is open to the wide chain (DESIGN.md 4.7 lists them); a wide file's row-tiled image is built
+// here, before any capture -- it has no kernel to fall back to, so an image that does not fit is the call's error.
+static bool check_fast_chain(biogpt_hip_ctx *c, const char *what, bool wide_ok = false) {
+    const int kind = chain_kind_of(c->hp);
+    if (kind == CHAIN_NONE)
+        BG_FAIL(false, "%s needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64) or the wide one (block-quantized weights, head size 64, d_model a multiple of 64, d_ff of 32)", what);
+    if (kind == CHAIN_BASE) return true;
+    if (!wide_ok) BG_FAIL(false, "%s needs the BioGPT-base fast chain (d_model 1024, d_ff 4096): the wide fast chain of this file (d_model %d, d_ff %d) does not serve it", what, c->hp.d_model, c->hp.d_ff);
+    HIP_TRY(false, hipSetDevice(c->device));
+    if (!ensure_tile_images(c)) return false;
+    if (c->tile_img == nullptr) BG_FAIL(false, "%s: no device memory for the row-tiled weight image the wide fast chain needs", what);
     return true;
 }
 
@@ -2629,7 +2698,10 @@ static bool begin_column_call(biogpt_hip_ctx *ctx, int n_slots, int n_seqs, long
     disarm_lineage(ctx);
     if (!ensure_seq_caches(ctx, n_slots)) return false;
     // matrix-core chain: decode steps have n_seqs columns, the prompt pass all prompt tokens; build the tiled weights before any graph capture
-    if (std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS && !ensure_tile_images(ctx)) return false;
+    // (a wide file has no other many-column kernel: always, and an image that does not fit is the call's error)
+    const bool wide = chain_kind_of(ctx->hp) == CHAIN_WIDE;
+    if ((wide || std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS) && !ensure_tile_images(ctx)) return false;
+    if (wide && ctx->tile_img == nullptr) BG_FAIL(false, "no device memory for the row-tiled weight image the wide fast chain needs");
     return ensure_logits_rows(ctx, (size_t)n_seqs);
 }
 
@@ -2920,7 +2992,8 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     if (lp && !check_gen_logprobs(lp, ctx->hp.n_vocab)) return -1;
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     if (prefix && (n_seqs < 1 || n_seqs > 511)) BG_FAIL(-1, "n_seqs must be in [1, 511] behind a prefix (got %d)", n_seqs);   // one slot holds the prefix
-    if (prefix && !check_fast_chain(ctx, "generation behind a shared prefix")) return -1;
+    // (the plain call meets the gate in enqueue_forward, as ever; the two variants are not open to the wide chain and say so by name)
+    if ((prefix || lp) && !check_fast_chain(ctx, prefix ? "generation behind a shared prefix" : "generation with log-probabilities")) return -1;
     if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");   // activation buffers hold n_positions >= 512 columns; each sequence owns a full F32 KV cache
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_seqs (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
     if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
@@ -3105,7 +3178,7 @@ static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (!seqs || !lens || !logprob_out) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");   // each sequence owns a full F32 KV cache
-    if (!check_fast_chain(ctx, "batched scoring")) return -1;
+    if (!check_fast_chain(ctx, "batched scoring", true)) return -1;
     size_t total = 0;
     for (int s = 0; s < n_seqs; s++) {
         if (lens[s] < 1) BG_FAIL(-1, "empty sequence (sequence %d)", s);
@@ -3219,7 +3292,7 @@ static int score_continuations_once(biogpt_hip_ctx *ctx, const int32_t *prefix, 
     if (n_prefix < 1) BG_FAIL(-1, "n_prefix must be >= 1 (got %d)", n_prefix);
     if (n_conts < 1 || n_conts > 511) BG_FAIL(-1, "n_conts must be in [1, 511] (got %d)", n_conts);   // slot 0 is the prefix; each continuation owns a full F32 KV cache
     const auto &hp = ctx->hp;
-    if (!check_fast_chain(ctx, "shared-prefix scoring")) return -1;
+    if (!check_fast_chain(ctx, "shared-prefix scoring", true)) return -1;
     if (n_prefix > hp.n_positions) BG_FAIL(-1, "n_prefix (%d) exceeds n_positions (%d)", n_prefix, hp.n_positions);
     for (int i = 0; i < n_prefix; i++)
         if (prefix[i] < 0 || prefix[i] >= hp.n_vocab) BG_FAIL(-1, "token id %d (prefix, position %d) out of range [0, %d)", prefix[i], i, hp.n_vocab);
@@ -3313,7 +3386,7 @@ static int score_continuations_batch_once(biogpt_hip_ctx *ctx, const int32_t *pr
     if (slots > PFXB_MAX_SLOTS)
         BG_FAIL(-1, "%ld slots exceed the %d of one call: n_groups (%d) + the sum of n_conts (%ld), one slot per prefix and one per continuation", slots, PFXB_MAX_SLOTS, n_groups, slots - n_groups);
     const auto &hp = ctx->hp;
-    if (!check_fast_chain(ctx, "shared-prefix scoring")) return -1;
+    if (!check_fast_chain(ctx, "shared-prefix scoring of many prompts")) return -1;
     size_t total = 0, pre_off = 0, pre_cols = 0;
     int cont_at = 0;
     for (int g = 0; g < n_groups; g++) {
@@ -3478,7 +3551,7 @@ static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (!ctx) BG_FAIL(-1, "null context");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     const auto &hp = ctx->hp;
-    if (!check_fast_chain(ctx, "batched embedding")) return -1;
+    if (!check_fast_chain(ctx, "batched embedding", true)) return -1;
     if (o.layer > hp.n_layer) BG_FAIL(-1, "layer (%d) must be in [-1, n_layer = %d]", o.layer, hp.n_layer);
     size_t total = 0;
     for (int s = 0; s < n_seqs; s++) {
@@ -3765,7 +3838,11 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
     if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
     if (eos_id < -1 || eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
-    if (!check_fast_chain(ctx, "sampled generation")) return -1;
+    {   // the wide chain serves the plain call; each variant it does not serve is refused by its name
+        const char *variant = wide ? "whole-vocabulary sampling" : trie ? "trie-constrained sampling" : prefix ? "sampled generation behind a shared prefix"
+                              : lp ? "sampled generation with log-probabilities" : rules_active(rules, eos_id) ? "sampled generation under rules" : nullptr;
+        if (!check_fast_chain(ctx, variant ? variant : "sampled generation", variant == nullptr)) return -1;
+    }
     if (!check_rules(rules, V, P)) return -1;
     if (trie && !check_trie_vocab(trie, V)) return -1;
     const bool ru = rules_active(rules, eos_id);
@@ -4050,7 +4127,10 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     if (eos_id < -1 || eos_id >= hp.n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, hp.n_vocab);
     if (!std::isfinite(length_penalty)) BG_FAIL(-1, "length_penalty must be finite");
     if (early_stopping != 0 && early_stopping != 1) BG_FAIL(-1, "early_stopping must be 0 or 1");
-    if (!check_fast_chain(ctx, "beam search")) return -1;
+    {
+        const char *variant = trie ? "trie-constrained beam search" : rules_active(rules, eos_id) ? "beam search under rules" : nullptr;
+        if (!check_fast_chain(ctx, variant ? variant : "beam search", variant == nullptr)) return -1;
+    }
     if (hp.n_vocab < 2 * B) BG_FAIL(-1, "a vocabulary of %d tokens holds fewer than 2 x n_beams candidates", hp.n_vocab);
     if (!check_rules(rules, hp.n_vocab, P)) return -1;
     if (rules_ban(rules, eos_id) && hp.n_vocab - rules->n_suppress - 1 - P < 2 * B)
@@ -4592,7 +4672,7 @@ struct QueueRequests {
     }
     // Tier two, what needs the model's sizes: the mode's parameters, then the prompts.  Tier three, the fast chain, ends this check; what a mode still has to
     // hold against the model comes behind it.
-    bool check_prompts_model(const biogpt_hip_ctx *ctx, const char *what) const {
+    bool check_prompts_model(biogpt_hip_ctx *ctx, const char *what, bool wide_ok = false) const {
         const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
         if (pos0 > P) BG_FAIL(false, "n_prefix (%d) exceeds n_positions (%d)", pos0, P);
         for (int i = 0; i < pos0; i++)
@@ -4603,7 +4683,7 @@ struct QueueRequests {
             for (int i = 0; i < prompt_lens[r]; i++)
                 if (prompts[off[(size_t)r] + (size_t)i] >= V) BG_FAIL(false, "token id %d (request %d, position %d) out of range [0, %d)", prompts[off[(size_t)r] + (size_t)i], r, i, V);
         }
-        return check_fast_chain(ctx, what);
+        return check_fast_chain(ctx, what, wide_ok);
     }
 };
 
@@ -4801,7 +4881,7 @@ static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
     if (top_k > V) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
     if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
     if (lp && lp->n_top > V) BG_FAIL(-1, "logprobs.n_top (%d) exceeds n_vocab (%d)", lp->n_top, V);
-    if (!rq.check_prompts_model(ctx, "generation over a queue")) return -1;
+    if (!rq.check_prompts_model(ctx, prefix ? "generation over a queue behind a shared prefix" : lp ? "generation over a queue with log-probabilities" : "generation over a queue", !prefix && !lp)) return -1;
     const size_t n_out = (size_t)n_requests * (size_t)n_predict, K = lp ? (size_t)lp->n_top : 0;
     std::fill(out_ids, out_ids + n_out, -1);
     std::fill(out_lens, out_lens + n_requests, 0);

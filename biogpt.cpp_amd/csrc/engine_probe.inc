@@ -1362,3 +1362,171 @@ int biogpt_hip_chain_device(int device, int32_t op, int32_t route, int32_t wtype
     }
     return 0;
 }
+
+// One stand-alone launch of the wide chain's linear stage (matmul_wide_kernel, kernels_mfma_wide.hip.h) over caller-supplied weights and Q8 columns, through
+// bg_wide_launch -- the entry of PassLaunch::wide_stage -- on an image laid out by tile_image_place and built as ensure_tile_images builds a wide file's (the
+// last row tile zero-padded, then bg_mfma_retile).  epi: 0 QKV (M == 3 K, 64 | K: K is d_model, heads of 64), 1 RESID, 2 GELU, 3 LOGITS; 16 | M but for LOGITS.
+// w_rows: M rows of K / 32 blocks in the file's format.  aq_q [N][K] int8, aq_d [N][K / 32] f32, aq_s [N][K / 32] words, as a producer leaves them.
+// QKV: exactly one of dev_state and seq_states (+ col_mode) names the column states; k_slots / v_slots [n_slots][K / 64][P][64] are updated in place.
+// out comes back WHOLE as allocated and preset to 0xff: cols = N rounded up to 16, plus one guard column; QKV: [cols][K] (the q rows), otherwise [cols][ldo]
+// with ldo = M rounded up to 128, plus 16 guard rows.  launched [8]: threads, grid x, grid y, static LDS bytes, cols, ldo, row tiles, 0.
+int biogpt_hip_wide_chain_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, const void *w_rows, const int8_t *aq_q, const float *aq_d,
+                                 const uint32_t *aq_s, const float *bias, const float *resid, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode,
+                                 int32_t P, int32_t n_slots, float *k_slots, float *v_slots, float *out, int32_t *launched) {
+    clear_error();
+    if (epi < bgk::EPI_QKV || epi > bgk::EPI_LOGITS) BG_FAIL(-1, "epi %d is no epilogue of the wide chain (0 QKV, 1 RESID, 2 GELU, 3 LOGITS)", epi);
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    if (epi != bgk::EPI_LOGITS && M % 16 != 0) BG_FAIL(-1, "M = %d is no whole number of 16-row tiles: only the lm_head has a partial last tile", M);
+    if (epi == bgk::EPI_QKV && (K % 64 != 0 || M != 3 * K)) BG_FAIL(-1, "q/k/v is 3 K x K with heads of 64 (got %d x %d)", M, K);
+    if (!w_rows || !aq_q || !aq_d || !aq_s || !out) BG_FAIL(-1, "w_rows, aq_q, aq_d, aq_s or out is NULL");
+    if (epi != bgk::EPI_LOGITS && !bias) BG_FAIL(-1, "bias is NULL");
+    if (epi == bgk::EPI_RESID && !resid) BG_FAIL(-1, "resid is NULL");
+    const bool qkv = epi == bgk::EPI_QKV, batch = seq_states != nullptr;
+    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
+    if (qkv) {
+        if ((dev_state != nullptr) == batch) BG_FAIL(-1, "exactly one of dev_state and seq_states names the column states");
+        if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
+        if (!batch && col_mode) BG_FAIL(-1, "col_mode 1 needs seq_states");
+        if (!k_slots || !v_slots) BG_FAIL(-1, "k_slots or v_slots is NULL");
+        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+        if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
+        if (!batch && n_slots != 1) BG_FAIL(-1, "the context's own columns have one slot");
+        std::set<std::pair<int, int>> seen;      // every column's cache row inside its slot, no two columns on one row
+        for (int i = 0; i < N; i++) {
+            const int pos = batch ? hs[i].n_past : dev_state[0] + i, slot = batch ? (col_mode ? hs[i].seq_id : i) : 0;
+            if (pos < 0 || pos >= P) BG_FAIL(-1, "column %d: position %d outside [0, P)", i, pos);
+            if (slot < 0 || slot >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, slot);
+            if (!seen.insert({slot, pos}).second) BG_FAIL(-1, "column %d: a second column writes slot %d, position %d", i, slot, pos);
+        }
+    } else if (dev_state || batch) BG_FAIL(-1, "only QKV reads column states");
+    HIP_TRY(-2, hipSetDevice(device));
+    const int q81 = (wtype == T_Q4_1 || wtype == T_Q5_1) ? 1 : 0;
+    const int cols = ((N + 15) & ~15) + 1, ldo = ((M + 127) & ~127) + 16, H = K / 64;
+    const size_t bpr = (size_t)K / QK, nblk = (size_t)M * bpr;
+    const size_t qs_b = nblk * (wtype == T_Q8_0 ? 32 : 16), sc_b = nblk * (q81 ? 4 : 2), qh_b = (wtype == T_Q5_0 || wtype == T_Q5_1) ? nblk * 4 : 0;
+    const size_t slot_f = (size_t)H * P * 64, kv_b = qkv ? slot_f * 4 * (size_t)n_slots : 0;
+    const size_t out_b = (size_t)cols * (qkv ? K : ldo) * 4;
+    size_t img_b = 0, xq = 0, xs = 0;
+    tile_image_place(wtype, M, K, img_b, xq, xs);
+    ByteLayout l;
+    const size_t o_qs = l.part(qs_b), o_sc = l.part(sc_b), o_qh = l.part(qh_b), o_img = l.part(img_b), o_aq = l.part((size_t)N * K), o_ad = l.part((size_t)N * bpr * 4),
+                 o_as = l.part((size_t)N * bpr * 4), o_bias = l.part(bias ? (size_t)M * 4 : 0), o_res = l.part(epi == bgk::EPI_RESID ? (size_t)N * M * 4 : 0),
+                 o_ds = l.part(sizeof(bgk::DevState)), o_st = l.part(batch ? sizeof(bgk::SeqState) * (size_t)N : 0), o_tab = l.part(65536 * 2), o_k = l.part(kv_b),
+                 o_v = l.part(kv_b), o_out = l.part(out_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));      // the output with its guard column and rows
+    HIP_TRY(-2, hipMemset(d.p + o_img, 0, img_b));                     // the rows the last tile has beyond the matrix
+    {
+        std::vector<uint8_t> qs(qs_b), sc(sc_b), qh(qh_b);
+        repack_rows(wtype, static_cast<const uint8_t *>(w_rows), M, K, qs.data(), sc.data(), qh.data());
+        HIP_TRY(-2, hipMemcpy(d.p + o_qs, qs.data(), qs_b, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_sc, sc.data(), sc_b, hipMemcpyHostToDevice));
+        if (qh_b) HIP_TRY(-2, hipMemcpy(d.p + o_qh, qh.data(), qh_b, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(-2, hipMemcpy(d.p + o_aq, aq_q, (size_t)N * K, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_ad, aq_d, (size_t)N * bpr * 4, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_as, aq_s, (size_t)N * bpr * 4, hipMemcpyHostToDevice));
+    if (bias) HIP_TRY(-2, hipMemcpy(d.p + o_bias, bias, (size_t)M * 4, hipMemcpyHostToDevice));
+    if (epi == bgk::EPI_RESID) HIP_TRY(-2, hipMemcpy(d.p + o_res, resid, (size_t)N * M * 4, hipMemcpyHostToDevice));
+    const int32_t no_state[4] = {0, 0, 0, 0};
+    HIP_TRY(-2, hipMemcpy(d.p + o_ds, (qkv && !batch) ? dev_state : no_state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
+    if (batch) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
+    if (qkv) {
+        HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
+    }
+    const std::vector<uint16_t> tg = gelu_table_f16();
+    HIP_TRY(-2, hipMemcpy(d.p + o_tab, tg.data(), 65536 * 2, hipMemcpyHostToDevice));
+    bgk::MatvecParams p{};
+    p.W.qs = d.p + o_qs; p.W.sc = d.p + o_sc; p.W.qh = qh_b ? d.at<const uint32_t>(o_qh) : nullptr;
+    p.W.type = wtype; p.W.M = M; p.W.K = K;
+    p.eps = 1e-5f; p.D = K; p.dk = 64; p.dk_log2 = 6; p.P = P;
+    p.st = d.at<const bgk::DevState>(o_ds);
+    p.gelu_tab = d.at<const uint16_t>(o_tab);
+    p.N = N;
+    p.aq_q = d.at<const int8_t>(o_aq); p.aq_d = d.at<const float>(o_ad); p.aq_s = d.at<const uint32_t>(o_as);
+    if (bias) p.bias = d.at<const float>(o_bias);
+    if (qkv) {
+        p.q_out = d.at<float>(o_out); p.kcache = d.at<float>(o_k); p.vcache = d.at<float>(o_v);
+        p.q_scale = 1.0f / sqrtf(64.0f);
+        if (batch) { p.seq = d.at<const bgk::SeqState>(o_st); p.col_mode = col_mode; p.kv_seq_stride = (int64_t)slot_f; }
+    } else {
+        p.out = d.at<float>(o_out); p.ldo = ldo;
+        if (epi == bgk::EPI_RESID) { p.resid = d.at<const float>(o_res); p.ldr = M; }
+    }
+    bgk::DevMatrix img{};
+    img.qs = d.p + o_img + xq; img.sc = d.p + o_img + xs; img.qh = nullptr; img.type = wtype; img.M = M; img.K = K;
+    HIP_TRY(-2, (hipError_t)bg_mfma_retile(wtype, &p.W, sizeof(p.W), d.p + o_img + xq, d.p + o_img + xs, 0));
+    HIP_TRY(-2, (hipError_t)bg_wide_launch(wtype, epi, &p, sizeof(p), &img, sizeof(img), 0));
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    if (launched) {
+        const int tiles = (M + 15) / 16;
+        const int32_t rep[8] = {256, (tiles + 3) / 4, (N + 15) / 16, 16 * (1024 + 16) + 16 * 33 * 4 * (q81 ? 2 : 1) /* WideLds::BYTES */, cols, ldo, tiles, 0};
+        std::memcpy(launched, rep, sizeof(rep));
+    }
+    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, out_b, hipMemcpyDeviceToHost));
+    if (qkv) {
+        HIP_TRY(-2, hipMemcpy(k_slots, d.p + o_k, kv_b, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(v_slots, d.p + o_v, kv_b, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// A linear stage alone, timed: reps launches on device memory of arbitrary contents (the kernels' time does not depend on the values), each between two
+// device events; one untimed launch in front.  which 0: matmul_wide_kernel with the residual epilogue at any (M, K) the wide chain takes; which 1: the
+// BioGPT-base matmul_mfma_kernel at its out_proj (K 1024) or fc2 (K 4096) site, M = 1024 -- the yardstick per block MAC.  For tools/wide_chain_bench.py.
+int biogpt_hip_wide_chain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t reps, float *us_out) {
+    clear_error();
+    if (which != 0 && which != 1) BG_FAIL(-1, "which must be 0 (the wide kernel) or 1 (the BioGPT-base kernel)");
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 16 || M > (1 << 20) || M % 16 != 0) BG_FAIL(-1, "M must be a multiple of 16 in [16, %d]", 1 << 20);
+    if (which == 1 && !((K == 1024 || K == 4096) && M == 1024)) BG_FAIL(-1, "the BioGPT-base kernel is timed at out_proj (1024 x 1024) or fc2 (1024 x 4096)");
+    if (reps < 1 || reps > 10000) BG_FAIL(-1, "reps must be in [1, 10000]");
+    if (!us_out) BG_FAIL(-1, "us_out is NULL");
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t bpr = (size_t)K / QK;
+    size_t img_b = 0, xq = 0, xs = 0;
+    tile_image_place(wtype, M, K, img_b, xq, xs);
+    ByteLayout l;
+    const size_t o_img = l.part(img_b), o_aq = l.part((size_t)N * K), o_ad = l.part((size_t)N * bpr * 4), o_as = l.part((size_t)N * bpr * 4), o_bias = l.part((size_t)M * 4),
+                 o_res = l.part((size_t)N * M * 4), o_out = l.part((size_t)N * M * 4);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemset(d.p, 0x11, l.bytes()));
+    bgk::MatvecParams p{};
+    p.W.type = wtype; p.W.M = M; p.W.K = K;
+    p.eps = 1e-5f; p.D = 1024; p.dk = 64; p.dk_log2 = 6; p.P = 1;
+    p.N = N;
+    p.aq_q = d.at<const int8_t>(o_aq); p.aq_d = d.at<const float>(o_ad); p.aq_s = d.at<const uint32_t>(o_as);
+    p.bias = d.at<const float>(o_bias); p.resid = d.at<const float>(o_res); p.ldr = M; p.out = d.at<float>(o_out); p.ldo = M;
+    bgk::DevMatrix img{};
+    img.qs = d.p + o_img + xq; img.sc = d.p + o_img + xs; img.qh = nullptr; img.type = wtype; img.M = M; img.K = K;
+    auto launch = [&]() -> hipError_t {
+        if (which == 0) return (hipError_t)bg_wide_launch(wtype, bgk::EPI_RESID, &p, sizeof(p), &img, sizeof(img), 0);
+        return launch_chain(K == 1024 ? CHAIN_OPROJ : CHAIN_FC2, p, 0, &img, nullptr);
+    };
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_TRY(-2, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); BG_FAIL(-2, "hipEventCreate failed"); }
+    hipError_t e = launch();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int i = 0; i < reps && e == hipSuccess; i++) {
+        e = hipEventRecord(e0, 0);
+        if (e == hipSuccess) e = launch();
+        if (e == hipSuccess) e = hipEventRecord(e1, 0);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.0f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        us_out[i] = ms * 1e3f;
+    }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    HIP_TRY(-2, e);
+    return 0;
+}

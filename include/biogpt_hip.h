@@ -167,6 +167,14 @@ int64_t biogpt_hip_chunk_launches(const biogpt_hip_ctx *ctx);
  * captured; -1: ctx is NULL.  A pass below the column threshold, a context without the row-tiled image and an lm_head whose rows are no multiple of 16 stay on
  * the 8-column kernels and do not count. */
 int64_t biogpt_hip_mfma_launches(const biogpt_hip_ctx *ctx);
+/* Which many-column layer chain the file has: 0 none (float weights, a head size other than 64, widths the tiles do not divide: the calls over column states
+ * refuse it), 1 the BioGPT-base chain (block-quantized, d_model 1024, d_ff 4096), 2 the wide chain -- any other block-quantized file with head size 64, d_model a
+ * multiple of 64 and d_ff of 32 (BioGPT-Large: 1600 / 6400): its passes over column states run their linear stages on the int8 matrix cores at every column
+ * count, from a row-tiled weight image whose last lm_head tile is zero-padded.  -1: ctx is NULL. */
+int biogpt_hip_chain_kind(const biogpt_hip_ctx *ctx);
+/* Linear-stage launches of the wide chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever on a
+ * BioGPT-base file.  -1: ctx is NULL. */
+int64_t biogpt_hip_wide_launches(const biogpt_hip_ctx *ctx);
 /* F32 / F16 files: single-token steps this context has enqueued (or captured into a replayed step) as ONE persistent launch for all layers (csrc/kernels_fpipe.hip.h);
  * -1: that launch is not available to this context (shape, device, BIOGPT_HIP_FPIPE=0, or abandoned after a failed launch) -- five launches per layer then */
 int64_t biogpt_hip_fpipe_launches(const biogpt_hip_ctx *ctx);
@@ -407,6 +415,21 @@ int biogpt_hip_chain_device(int device, int32_t op, int32_t route, int32_t wtype
                             const float *ln_b, int32_t q81, const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid,
                             const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t P, int32_t n_slots, float *k_slots, float *v_slots,
                             float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched);
+/* One stand-alone launch of the wide chain's linear stage over caller-supplied weights and Q8 columns, through the launch code of the engine's own passes: the
+ * row-tiled image is built as for a wide file (ceil(M / 16) tiles, the last one zero-padded).  epi: 0 QKV (M == 3 K, 64 | K: K is d_model, heads of 64), 1 RESID,
+ * 2 GELU (f32 rows through the fp16 table), 3 LOGITS; K a multiple of 32; 16 | M but for LOGITS.  w_rows: M rows of K / 32 blocks in the file's format (wtype 2, 3,
+ * 6, 7, 8); aq_q [N][K] int8, aq_d [N][K / 32], aq_s [N][K / 32] in the device layout of a producer's Q8 blocks; bias [M] (not 3); resid [N][M] (1); epi 0: exactly
+ * one of dev_state (4 words; one slot) and seq_states ([N][8] words; col_mode 0: column i writes slot i, 1: slot seq_id) at position n_past, and one layer's
+ * k_slots / v_slots [n_slots][K / 64][P][64], updated in place.  out comes back whole, as allocated and preset to 0xff bytes: cols = N rounded up to 16, plus 1;
+ * epi 0: [cols][K] (the q rows), otherwise [cols][ldo] with ldo = M rounded up to 128, plus 16.  launched [8] (may be NULL): threads, grid x, grid y, LDS bytes,
+ * cols, ldo, row tiles, 0.  For tests of the kernel itself and tools. */
+int biogpt_hip_wide_chain_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, const void *w_rows, const int8_t *aq_q, const float *aq_d,
+                                 const uint32_t *aq_s, const float *bias, const float *resid, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode,
+                                 int32_t P, int32_t n_slots, float *k_slots, float *v_slots, float *out, int32_t *launched);
+/* A linear stage alone, timed: one untimed launch, then reps in [1, 10000] launches on device memory of arbitrary contents, us_out[i]: microseconds between two
+ * device events around launch i alone.  which 0: the wide chain's kernel with the residual epilogue at M rows (16 | M) of K values (32 | K) and N <= 512 columns;
+ * which 1: the BioGPT-base matrix-core kernel at out_proj (M 1024, K 1024) or fc2 (M 1024, K 4096).  For tools/wide_chain_bench.py. */
+int biogpt_hip_wide_chain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t reps, float *us_out);
 /* One decode attention launch of N columns behind a shared prefix over caller-supplied inputs (head size 64, one layer): q [N][H * 64]; k_slots / v_slots
  * [N + 1][H][P][64], slot i column i's own and slot N the prefix's; seq_states [N][8] words as the engine's column states (n_past, ..., pad[0] = shared rows,
  * pad[1] = their slot).  which 0: the existing attn_fast_kernel<4, false, true>; 1: attn_prefix_kernel<8>, eight columns per workgroup (one shared range for
