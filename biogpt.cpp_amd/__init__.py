@@ -47,6 +47,44 @@ class GenLogprobs(C.Structure):
     _fields_ = [("n_top", C.c_int32), ("lp", C.c_void_p), ("top_ids", C.c_void_p), ("top_lp", C.c_void_p)]
 
 
+class RequestParams(C.Structure):
+    """biogpt_hip_request_params (include/biogpt_hip.h): one request's sampler, EOS id, rules and stop sequences for generate_queue(params=), made by
+    request_params() -- `keep` holds the arrays its pointers name."""
+    _fields_ = [("top_k", C.c_int32), ("eos_id", C.c_int32), ("top_p", C.c_double), ("temp", C.c_double), ("rules", GenRules),
+                ("n_stop", C.c_int32), ("stop", C.POINTER(C.c_int32)), ("stop_lens", C.POINTER(C.c_int32))]
+    keep = ()
+
+
+def request_params(top_k=1, top_p=0.9, temp=0.9, eos_id=-1, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=(), stop=()):
+    """An entry of generate_queue(params=): the request's own sampler and EOS id, its generation rules (gen_rules; at most 64 suppress_tokens here) and `stop`,
+    up to 4 stop sequences of 1 .. 8 ids each ("Generation over a queue").  The ranges are checked by the call that uses it."""
+    rules, ids = gen_rules(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)
+    if any(np.ndim(q) != 1 for q in stop):
+        raise BiogptError("stop must be a list of id lists, one per stop sequence (a single sequence: stop=[[...]]); got %r" % (stop,))
+    seqs = [np.asarray(q, dtype=np.int32).reshape(-1) for q in stop]
+    flat = np.ascontiguousarray(np.concatenate(seqs + [np.zeros(1, np.int32)]))
+    lens = np.ascontiguousarray([q.size for q in seqs] + [0], dtype=np.int32)
+    ip = C.POINTER(C.c_int32)
+    p = RequestParams(int(top_k), int(eos_id), float(top_p), float(temp), rules, len(seqs), flat.ctypes.data_as(ip) if seqs else None,
+                      lens.ctypes.data_as(ip) if seqs else None)
+    p.keep = (ids, flat, lens)
+    return p
+
+
+def _params_array(params, n):
+    """(RequestParams * n, the entries it was copied from -- they keep its pointers' arrays alive): one entry for all requests, or a list of n."""
+    entries = [params] * n if isinstance(params, RequestParams) else list(params)
+    if len(entries) != n:
+        raise BiogptError("params must have one entry per request (%d != %d)" % (len(entries), n))
+    for e in entries:
+        if not isinstance(e, RequestParams):
+            raise BiogptError("params: every entry must come from request_params() (got %r)" % (type(e).__name__,))
+    arr = (RequestParams * max(n, 1))()
+    for i, e in enumerate(entries):
+        C.memmove(C.byref(arr, i * C.sizeof(RequestParams)), C.byref(e), C.sizeof(RequestParams))
+    return arr, entries
+
+
 class Sampler(C.Structure):
     """biogpt_hip_sampler (include/biogpt_hip.h): a sampler of any width, made by sampler()."""
     _fields_ = [("top_k", C.c_int32), ("pad", C.c_int32), ("top_p", C.c_double), ("min_p", C.c_double), ("temp", C.c_double)]
@@ -313,6 +351,36 @@ def queue_rows(rows, states, limits, finished, mt_states, hdr, n_top=0, stride=1
     if lib().biogpt_hip_queue_rows_device(int(device), 1 if with_lp else 0, a.ctypes.data, n, nv, k, w, int(top_k), float(top_p), float(temp), int(eos_id),
                                           mt_states.ctypes.data, states.ctypes.data, lim.ctypes.data, finished.ctypes.data, hdr.ctypes.data, ids.ctypes.data,
                                           lp.ctypes.data, tid.ctypes.data if k > 0 else None, tlp.ctypes.data if k > 0 else None) != 0:
+        raise BiogptError(_err())
+    return ids, lp, tid[:, :, :k], tlp[:, :, :k]
+
+
+def queue_req_rows(rows, params, histories, prompt_lens, states, limits, finished, mt_states, hdr, n_top=0, stride=1, with_lp=False, device=0):
+    """One launch of queue_req_rows_kernel on rows held in host memory (biogpt_hip_queue_req_rows_device): row r is column r with the record of params[r]
+    (request_params entries) and the history histories[r], the first prompt_lens[r] tokens its prompt and the rest its generated tokens.  states int32 [n][8],
+    finished int32 [n], mt_states uint32 [n][625] and hdr int32 [1 + 3 n] (n_live, fin[], len[], reason[]) are changed in place.  Returns (ids int32
+    [n][stride], lp float32 [n][stride], top_ids int32 [n][stride][n_top], top_lp): 0xff bytes wherever the launch wrote nothing, but for the generated tokens
+    given, which stand in the first entries of their ids rows."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv = int(a.shape[0]), int(a.shape[1])
+    for name, arr, dt, shape in (("states", states, np.int32, (n, 8)), ("finished", finished, np.int32, (n,)), ("mt_states", mt_states, np.uint32, (n, 625)),
+                                 ("hdr", hdr, np.int32, (1 + 3 * n,))):
+        if not (isinstance(arr, np.ndarray) and arr.dtype == dt and arr.flags["C_CONTIGUOUS"] and arr.shape == shape):
+            raise BiogptError("%s must be a contiguous %s array of shape %r" % (name, np.dtype(dt).name, shape))
+    lim = np.ascontiguousarray(limits, dtype=np.int32).reshape(-1)
+    pl = np.ascontiguousarray(prompt_lens, dtype=np.int32).reshape(-1)
+    hl = np.ascontiguousarray([len(h) for h in histories], dtype=np.int32)
+    if lim.size != n or pl.size != n or hl.size != n:
+        raise BiogptError("limits, prompt_lens and histories must have one entry per row")
+    flat = _flat_ids(histories)
+    arr, keep = _params_array(params, n)
+    k, w = int(n_top), int(stride)
+    ids = np.zeros((n, w), dtype=np.int32)
+    lp = np.zeros((n, w), dtype=np.float32)
+    tid, tlp = np.zeros((n, w, max(k, 1)), dtype=np.int32), np.zeros((n, w, max(k, 1)), dtype=np.float32)
+    if lib().biogpt_hip_queue_req_rows_device(int(device), 1 if with_lp else 0, a.ctypes.data, n, nv, k, w, arr, flat.ctypes.data, hl.ctypes.data, pl.ctypes.data,
+                                              mt_states.ctypes.data, states.ctypes.data, lim.ctypes.data, finished.ctypes.data, hdr.ctypes.data, ids.ctypes.data,
+                                              lp.ctypes.data, tid.ctypes.data if k else None, tlp.ctypes.data if k else None) != 0:
         raise BiogptError(_err())
     return ids, lp, tid[:, :, :k], tlp[:, :, :k]
 
@@ -660,6 +728,9 @@ SYMBOLS = [
                                                 C.c_int32, _P, _P, C.POINTER(C.c_double), C.POINTER(GenLogprobs)]),
     ("biogpt_hip_genlp_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
     ("biogpt_hip_queue_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32] + [_P] * 9),
+    ("biogpt_hip_generate_queue_requests", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RequestParams), _P,
+                                                    _P, _P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(QueueStats), C.POINTER(GenLogprobs)]),
+    ("biogpt_hip_queue_req_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RequestParams)] + [_P] * 12),
     ("biogpt_hip_attn_device", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("biogpt_hip_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32] + [_P] * 7 + [C.c_int32] * 3 + [_P] * 7),
     ("biogpt_hip_wide_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 4),
@@ -1004,13 +1075,13 @@ def _logprobs_keyword(plain):
 
 
 def _queue_keywords(plain):
-    """Adds the keyword-only prefix=None and logprobs=None to generate_queue, as _logprobs_keyword adds logprobs: the method's own parameters, defaults and
-    return value stay what they are.  Neither given: the method itself.  Otherwise _generate_queue with the same arguments and the two keywords."""
+    """Adds the keyword-only prefix=None, logprobs=None and params=None to generate_queue, as _logprobs_keyword adds logprobs: the method's own parameters,
+    defaults and return value stay what they are.  None given: the method itself.  Otherwise _generate_queue with the same arguments and the keywords."""
     @functools.wraps(plain)
-    def call(self, *args, prefix=None, logprobs=None, **kw):
-        if prefix is None and logprobs is None:
+    def call(self, *args, prefix=None, logprobs=None, params=None, **kw):
+        if prefix is None and logprobs is None and params is None:
             return plain(self, *args, **kw)
-        return BiogptModel._generate_queue(self, *args, prefix=prefix, logprobs=logprobs, **kw)
+        return BiogptModel._generate_queue(self, *args, prefix=prefix, logprobs=logprobs, params=params, **kw)
     return call
 
 
@@ -1308,12 +1379,20 @@ class BiogptModel:
         over a queue"; prefix_stats()).  The ids, admit_step, column and stats are those of the call on the concatenations, but for
         stats["prompt_columns"], the prompt columns really evaluated.
         logprobs (keyword only): None, or K in [0, 8] -- info["logprobs"][r] = (logprobs float32[len_r], top_ids int32[len_r, K], top_logprobs float32[len_r,
-        K]) as generate_sample(logprobs=K) of the request alone gives them, bit for bit; the ids are those of the call without it."""
+        K]) as generate_sample(logprobs=K) of the request alone gives them, bit for bit; the ids are those of the call without it.
+        params (keyword only): one request_params() entry for all requests or a list with one per request -- every request has its own sampler, EOS id,
+        generation rules and stop sequences (biogpt_hip_generate_queue_requests), and the method's own top_k / top_p / temp / eos_id must be left at their
+        defaults.  Request r's ids are those of generate_sample of r alone with r's parameters and rules, cut just behind the first position at which one of
+        its stop sequences is complete inside the generated tokens; info["finish"][r] says why it ended: 0 its limit, 1 its EOS id, 2 + i stop sequence i,
+        -1 it never ran.  logprobs= together with a request that has a rule switched on is an error; no trie, wide sampler or several samples."""
         return BiogptModel._generate_queue(self, prompts, n_predict, max_columns, group, top_k, top_p, temp, seed, seeds, eos_id, n_batch, n_predicts)
 
     def _generate_queue(self, prompts, n_predict, max_columns=64, group=4, top_k=1, top_p=0.9, temp=0.9, seed=0, seeds=None, eos_id=-1, n_batch=8, n_predicts=None,
-                        prefix=None, logprobs=None):
-        """generate_queue, with prefix= and logprobs= its form behind a shared prefix and with log-probabilities (biogpt_hip_generate_queue_prefix)."""
+                        prefix=None, logprobs=None, params=None):
+        """generate_queue, with prefix= and logprobs= its form behind a shared prefix and with log-probabilities (biogpt_hip_generate_queue_prefix), with
+        params= the form whose requests carry their own parameters (biogpt_hip_generate_queue_requests)."""
+        if params is not None and (top_k, top_p, temp, eos_id) != (1, 0.9, 0.9, -1):
+            raise BiogptError("params= carries every request's top_k / top_p / temp / eos_id: leave the method's own at their defaults")
         if len(prompts) and np.isscalar(prompts[0]):
             prompts = [prompts]
         R = len(prompts)
@@ -1336,15 +1415,22 @@ class BiogptModel:
         ol, adm, col = (np.zeros(max(R, 1), dtype=np.int32) for _ in range(3))
         st = QueueStats()
         secs = C.c_double(0.0)
-        arr = None
-        if prefix is None and logprobs is None:
+        arr = fin = None
+        pre = None if prefix is None else _flat_ids([prefix])
+        if logprobs is not None:
+            arr = _LogprobArrays(logprobs, R, max(w, 1))
+        if params is not None:
+            pa, keep = _params_array(params, R)
+            fin = np.zeros(max(R, 1), dtype=np.int32)
+            rc = lib().biogpt_hip_generate_queue_requests(self._h, None if pre is None else pre.ctypes.data, 0 if prefix is None else len(prefix), flat.ctypes.data,
+                                                          lens.ctypes.data, R, None if np_arr is None or R == 0 else np_arr.ctypes.data, int(n_predict), int(max_columns),
+                                                          int(group), int(n_batch), pa, sd.ctypes.data, out.ctypes.data, ol.ctypes.data, fin.ctypes.data, adm.ctypes.data,
+                                                          col.ctypes.data, C.byref(secs), C.byref(st), None if arr is None else C.byref(arr.req))
+        elif prefix is None and logprobs is None:
             rc = lib().biogpt_hip_generate_queue(self._h, flat.ctypes.data, lens.ctypes.data, R, None if np_arr is None or R == 0 else np_arr.ctypes.data, int(n_predict),
                                                  int(max_columns), int(group), int(n_batch), int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id),
                                                  out.ctypes.data, ol.ctypes.data, adm.ctypes.data, col.ctypes.data, C.byref(secs), C.byref(st))
         else:
-            pre = None if prefix is None else _flat_ids([prefix])
-            if logprobs is not None:
-                arr = _LogprobArrays(logprobs, R, max(w, 1))
             rc = lib().biogpt_hip_generate_queue_prefix(self._h, None if pre is None else pre.ctypes.data, 0 if prefix is None else len(prefix), flat.ctypes.data,
                                                         lens.ctypes.data, R, None if np_arr is None or R == 0 else np_arr.ctypes.data, int(n_predict), int(max_columns),
                                                         int(group), int(n_batch), int(top_k), float(top_p), float(temp), sd.ctypes.data, int(eos_id), out.ctypes.data,
@@ -1357,6 +1443,8 @@ class BiogptModel:
         info = {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:R]], "column": [int(v) for v in col[:R]]}
         if arr is not None:
             info["logprobs"] = arr.info(R, w, [int(v) for v in ol[:R]]) if w > 0 else [arr.info(1, 0, [0])[0] for _ in range(R)]
+        if fin is not None:
+            info["finish"] = [int(v) for v in fin[:R]]
         return ids, info, secs.value
 
     def read_column_state(self, column, pos, which=0, n_ids=0):

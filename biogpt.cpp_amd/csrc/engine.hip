@@ -303,7 +303,7 @@ struct biogpt_hip_ctx {
     int launch_parity = 0;
     // column generation (greedy batch, sampling, beam search; the driver stands before generate_greedy_batch_once): the captured steps of each mode,
     // and the pinned word pair + event pair through which the host reads a mode's count of unfinished sequences / searches between groups of steps
-    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam, graphs_contrast, graphs_lookup, graphs_queue, graphs_bqueue;
+    ColumnGraphs graphs_greedy, graphs_sample, graphs_beam, graphs_contrast, graphs_lookup, graphs_queue, graphs_bqueue, graphs_queue_req;
     int32_t *live_host = nullptr;
     hipEvent_t live_ev[2] = {};
     // sampled generation (biogpt_hip_generate_sample, kernels_sample.hip.h): the call's parameters + one generator state per sequence (SampleCtl, then
@@ -333,6 +333,10 @@ struct biogpt_hip_ctx {
     // first such call -- captured steps keep their pointers -- and its pinned twin: the header the host reads behind a group, the admit list it uploads
     uint8_t *queue_buf = nullptr;
     uint8_t *queue_host = nullptr;
+    // ... whose requests carry their own parameters (biogpt_hip_generate_queue_requests): the same for that form (queue_req_bufs_at; its captured steps are
+    // graphs_queue_req), and its pinned twin
+    uint8_t *queue_req_buf = nullptr;
+    uint8_t *queue_req_host = nullptr;
     // beam search over a queue (biogpt_hip_generate_beam_queue, kernels_beam_queue.hip.h): the searches' state is bbatch_buf; this block holds what the queue adds
     // (bqueue_bufs_at: the report header and the admit list), allocated at the first such call, and its pinned twin (BeamQueueHost, then the pool rows of
     // every slot as they come back)
@@ -417,7 +421,7 @@ static void drop_graphs(ColumnGraphs &gs) {
 }
 // Captured column steps hold the pointers of seq / bk / bv / logits_all and launch shapes chosen from the options: whatever replaces one of those drops them all
 static void drop_column_graphs(biogpt_hip_ctx *c) {
-    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam, &c->graphs_contrast, &c->graphs_lookup, &c->graphs_queue, &c->graphs_bqueue}) drop_graphs(*gs);
+    for (ColumnGraphs *gs : {&c->graphs_greedy, &c->graphs_sample, &c->graphs_beam, &c->graphs_contrast, &c->graphs_lookup, &c->graphs_queue, &c->graphs_bqueue, &c->graphs_queue_req}) drop_graphs(*gs);
 }
 
 namespace {
@@ -1816,6 +1820,7 @@ void destroy(biogpt_hip_ctx *c) {
     for (auto &e : c->live_ev) if (e) (void)hipEventDestroy(e);
     if (c->live_host) (void)hipHostFree(c->live_host);
     if (c->queue_host) (void)hipHostFree(c->queue_host);
+    if (c->queue_req_host) (void)hipHostFree(c->queue_req_host);
     if (c->bqueue_host) (void)hipHostFree(c->bqueue_host);
     xpipe_release(c);
     if (c->topk_host) (void)hipHostFree(c->topk_host);
@@ -1823,7 +1828,7 @@ void destroy(biogpt_hip_ctx *c) {
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf, (void *)c->genlp_buf, (void *)c->queue_buf, (void *)c->bqueue_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf, (void *)c->genlp_buf, (void *)c->queue_buf, (void *)c->bqueue_buf, (void *)c->queue_req_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -4847,6 +4852,24 @@ static QueueBufs queue_bufs_at(uint8_t *base) {
 // the pinned twin: the header as the host reads it, the admit list as the host writes it
 struct QueueHost { bgk::QueueHdr hdr; bgk::QueueAdmit admit[bgk::QUEUE_COLS]; };
 
+// What request r left in column col, len tokens, to the caller's rows (in stream order before the column is reused): the ids straight from the column's seq_gen
+// row, and with lp the column's rows of the log-probability block (lp_stride entries apart)
+static bool queue_copy_out(biogpt_hip_ctx *ctx, int col, int r, int len, int n_predict, int32_t *out_ids, const biogpt_hip_gen_logprobs *lp, const GenLpBufs &lb,
+                           int lp_stride) {
+    if (len <= 0) return true;
+    const size_t K = lp ? (size_t)lp->n_top : 0;
+    HIP_TRY(false, hipMemcpyAsync(out_ids + (size_t)r * (size_t)n_predict, ctx->seq_gen + (size_t)col * ctx->hp.n_positions, (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (lp) {
+        const size_t src = (size_t)col * (size_t)lp_stride, dst = (size_t)r * (size_t)n_predict;
+        HIP_TRY(false, hipMemcpyAsync(lp->lp + dst, lb.lp + src, (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (K > 0) {
+            HIP_TRY(false, hipMemcpyAsync(lp->top_ids + dst * K, lb.top_ids + src * K, (size_t)len * K * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(false, hipMemcpyAsync(lp->top_lp + dst * K, lb.top_lp + src * K, (size_t)len * K * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    return true;
+}
+
 // prefix != null (biogpt_hip_generate_queue_prefix): request r is prefix ++ prompt r, the prompts are suffixes and may be empty; the first n_shared prefix
 // rows are evaluated once, into the slot behind the columns', and read there by the refill passes and the steps (n_shared == 0: the call on the
 // concatenations, launch for launch).  lp != null: queue_rows_lp_kernel is the selection, and a finished column's rows of the log-probability block go to its
@@ -4942,16 +4965,7 @@ static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
     };
     qc.collect = [&](int col, int r) -> int {      // the ids straight from the column's seq_gen row to the caller's row
         const int len = std::max(0, std::min(qh->hdr.len[col], rq.cap[(size_t)r]));
-        if (len > 0)
-            HIP_TRY(-1, hipMemcpyAsync(out_ids + (size_t)r * (size_t)n_predict, ctx->seq_gen + (size_t)col * P, (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (lp && len > 0) {      // the column's rows of the block -> the request's rows
-            const size_t src = (size_t)col * (size_t)lp_stride, dst = (size_t)r * (size_t)n_predict;
-            HIP_TRY(-1, hipMemcpyAsync(lp->lp + dst, lb.lp + src, (size_t)len * 4, hipMemcpyDeviceToHost, ctx->stream));
-            if (K > 0) {
-                HIP_TRY(-1, hipMemcpyAsync(lp->top_ids + dst * K, lb.top_ids + src * K, (size_t)len * K * 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(-1, hipMemcpyAsync(lp->top_lp + dst * K, lb.top_lp + src * K, (size_t)len * K * 4, hipMemcpyDeviceToHost, ctx->stream));
-            }
-        }
+        if (!queue_copy_out(ctx, col, r, len, n_predict, out_ids, lp, lb, lp_stride)) return -1;
         out_lens[r] = len;
         return len;
     };
@@ -4983,6 +4997,206 @@ int biogpt_hip_generate_queue_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix,
     return with_xpipe_retry(ctx, 0, [&] {
         return generate_queue_once(ctx, suffixes, suffix_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch, top_k, top_p, temp, seeds, eos_id,
                                    out_ids, out_lens, out_admit_step, out_column, seconds_out, stats, prefix, n_prefix, logprobs);
+    });
+}
+
+// ---- generation over a queue whose requests carry their own parameters (biogpt_hip_generate_queue_requests) ---------------------------------------------
+// The fifth form of the column queue: the driver, the schedule and the admit state are those of generate_queue_once; the step is the forward pass and ONE
+// launch of queue_req_rows_kernel (the closed rules call has two), which reads a column's sampler, EOS id, rules and stop sequences from the column's record.
+// An entry of the admit list is the admit record, the request's record and the request's own prompt tokens (the history its rules read), `stride` bytes apart:
+// one upload per refill, as before, and a step causes no host traffic.  Behind a prefix the prefix's tokens go up once, in prepare.  The header carries the
+// reason a column finished behind what the driver reads.  Its captured steps are graphs_queue_req, with the four sets of generate_queue_once.
+struct QueueReqBufs {
+    bgk::SampleSeq *seq;        // [QUEUE_COLS]
+    int32_t *limit;             // [QUEUE_COLS]
+    bgk::QueueReqHdr *hdr;
+    bgk::QueueReqRec *rec;      // [QUEUE_COLS]
+    int32_t *prefix;            // [n_positions]
+    int32_t *hist;              // [QUEUE_COLS][n_positions]
+    uint8_t *admit;             // QUEUE_COLS entries at their largest
+    size_t bytes;
+};
+static_assert(sizeof(biogpt_hip_request_params) == 72 && offsetof(biogpt_hip_request_params, rules) == 24 && offsetof(biogpt_hip_request_params, stop) == 56,
+              "biogpt_hip_request_params as the bindings lay it out (RequestParams, biogpt.cpp_amd/__init__.py)");
+static size_t queue_req_stride(int n_own) { return (sizeof(bgk::QueueReqAdmit) + (size_t)n_own * 4 + 15) & ~(size_t)15; }
+static QueueReqBufs queue_req_bufs_at(uint8_t *base, int P) {
+    ByteLayout l;
+    QueueReqBufs b{};
+    b.seq = l.take<bgk::SampleSeq>(base, bgk::QUEUE_COLS); b.limit = l.take<int32_t>(base, bgk::QUEUE_COLS); b.hdr = l.take<bgk::QueueReqHdr>(base, 1);
+    b.rec = l.take<bgk::QueueReqRec>(base, bgk::QUEUE_COLS); b.prefix = l.take<int32_t>(base, (size_t)P); b.hist = l.take<int32_t>(base, (size_t)bgk::QUEUE_COLS * P);
+    b.admit = l.take<uint8_t>(base, (size_t)bgk::QUEUE_COLS * queue_req_stride(P));
+    b.bytes = l.bytes();
+    return b;
+}
+
+// What can be judged of request r's parameters without the model (V < 0), and with its sizes
+static bool check_request_params(const biogpt_hip_request_params &p, int r, int V, int P) {
+    if (p.top_k < 1 || p.top_k > bgk::SAMPLE_MAX_K || (V >= 0 && p.top_k > V)) BG_FAIL(false, "params[%d].top_k must be in [1, %d] and at most n_vocab", r, bgk::SAMPLE_MAX_K);
+    if (!std::isfinite(p.temp) || !(p.temp > 0.0)) BG_FAIL(false, "params[%d].temp must be finite and > 0", r);
+    if (!std::isfinite(p.top_p)) BG_FAIL(false, "params[%d].top_p must be finite (>= 1: no cut)", r);
+    if (p.eos_id < -1) BG_FAIL(false, "params[%d].eos_id %d out of range: must be a token id, or -1 for none", r, p.eos_id);
+    if (V >= 0 && p.eos_id >= V) BG_FAIL(false, "params[%d].eos_id %d out of range: must be in [0, %d), or -1 for none", r, p.eos_id, V);
+    if (!check_rules(&p.rules, V >= 0 ? V : bgk::RULES_MAX_VOCAB, V >= 0 ? P : -1)) {
+        const std::string why = last_error();
+        BG_FAIL(false, "params[%d].rules: %s", r, why.c_str());
+    }
+    if (p.rules.n_suppress > bgk::QUEUE_REQ_SUPPRESS) BG_FAIL(false, "params[%d].rules.n_suppress (%d) must be in [0, %d] for a request of a queue", r, p.rules.n_suppress, bgk::QUEUE_REQ_SUPPRESS);
+    if (p.n_stop < 0 || p.n_stop > bgk::QUEUE_REQ_STOPS) BG_FAIL(false, "params[%d].n_stop (%d) must be in [0, %d]", r, p.n_stop, bgk::QUEUE_REQ_STOPS);
+    if (p.n_stop > 0 && !p.stop) BG_FAIL(false, "params[%d].stop is NULL with n_stop = %d", r, p.n_stop);
+    if (p.n_stop > 0 && !p.stop_lens) BG_FAIL(false, "params[%d].stop_lens is NULL with n_stop = %d", r, p.n_stop);
+    for (int i = 0, at = 0; i < p.n_stop; at += p.stop_lens[i], i++) {
+        if (p.stop_lens[i] < 1 || p.stop_lens[i] > bgk::QUEUE_REQ_STOP_LEN)
+            BG_FAIL(false, "params[%d].stop_lens[%d] (%d) must be in [1, %d]", r, i, p.stop_lens[i], bgk::QUEUE_REQ_STOP_LEN);
+        for (int j = 0; j < p.stop_lens[i]; j++) {
+            const int t = p.stop[at + j];
+            if (t < 0 || (V >= 0 && t >= V)) BG_FAIL(false, "params[%d].stop: token id %d (sequence %d, position %d) out of range%s", r, t, i, j, V >= 0 ? " for this vocabulary" : "");
+        }
+    }
+    return true;
+}
+
+static bgk::QueueReqRec request_rec_of(const biogpt_hip_request_params &p, int n_prefix, int n_own) {
+    bgk::QueueReqRec rec{};
+    rec.ctl = sample_ctl_of(p.top_k, p.eos_id, 0, p.top_p, p.temp);
+    const bgk::RulesCtl rc = rules_ctl_of(&p.rules, 0, p.eos_id);
+    rec.penalty = rc.penalty; rec.ngram = rc.ngram; rec.min_new = rc.min_new; rec.n_suppress = rc.n_suppress;
+    rec.rules_on = rules_active(&p.rules, p.eos_id) ? 1 : 0;
+    rec.n_prefix = n_prefix; rec.n_own = n_own; rec.n_stop = p.n_stop;
+    for (int i = 0; i < rc.n_suppress; i++) rec.suppress[i] = rc.suppress[i];
+    for (int i = 0, at = 0; i < p.n_stop; at += p.stop_lens[i], i++) {
+        rec.stop_len[i] = p.stop_lens[i];
+        for (int j = 0; j < p.stop_lens[i]; j++) rec.stop[i][j] = p.stop[at + j];
+    }
+    return rec;
+}
+
+static void enqueue_queue_req_rows(hipStream_t stream, int C, float *logits, int V, const QueueReqBufs &qb, bgk::SeqState *seq, int32_t *seq_gen,
+                                   int gen_stride, int hist_stride, const GenLpBufs *lb) {
+    const size_t lds = (size_t)((V + 31) / 32) * 4;
+    if (lb)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(bgk::queue_req_rows_kernel<bgk::SampleGenLp>), dim3(C), dim3(bgk::SAMPLE_THREADS), lds, stream, logits, V, V, qb.rec, qb.seq, seq,
+                           seq_gen, gen_stride, qb.limit, qb.hdr, qb.prefix, qb.hist, hist_stride, bgk::SampleGenLp{lb->out()});
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(bgk::queue_req_rows_kernel<bgk::SamplePlain>), dim3(C), dim3(bgk::SAMPLE_THREADS), lds, stream, logits, V, V, qb.rec, qb.seq, seq,
+                           seq_gen, gen_stride, qb.limit, qb.hdr, qb.prefix, qb.hist, hist_stride, bgk::SamplePlain());
+}
+
+static int generate_queue_requests_once(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests,
+                                        const int32_t *n_predicts, int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch,
+                                        const biogpt_hip_request_params *params, const uint32_t *seeds, int32_t *out_ids, int32_t *out_lens, int32_t *out_finish,
+                                        int32_t *out_admit_step, int32_t *out_column, double *seconds_out, biogpt_hip_queue_stats *stats,
+                                        const biogpt_hip_gen_logprobs *lp) {
+    clear_error();
+    if (lp && !check_gen_logprobs(lp, -1)) return -1;
+    if (!prefix && n_prefix != 0) BG_FAIL(-1, "n_prefix must be 0 without a prefix (got %d)", n_prefix);
+    if (prefix && n_prefix < 1) BG_FAIL(-1, "n_prefix must be >= 1 (got %d)", n_prefix);
+    if (!prompts) BG_FAIL(-1, prefix ? "null argument: suffixes" : "null argument: prompts");
+    if (!prompt_lens) BG_FAIL(-1, prefix ? "null argument: suffix_lens" : "null argument: prompt_lens");
+    if (!params) BG_FAIL(-1, "null argument: params");
+    if (!seeds) BG_FAIL(-1, "null argument: seeds");
+    if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
+    if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
+    QueueRequests rq{prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch};
+    rq.prefix = prefix; rq.pos0 = n_prefix;
+    if (!rq.check_count()) return -1;
+    if (prefix && (max_columns < 1 || max_columns > bgk::QUEUE_COLS - 1))
+        BG_FAIL(-1, "max_columns must be in [1, %d] behind a prefix (got %d)", bgk::QUEUE_COLS - 1, max_columns);   // one slot holds the prefix
+    if (max_columns < 1 || max_columns > bgk::QUEUE_COLS) BG_FAIL(-1, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
+    if (!rq.check_sizes()) return -1;
+    for (int r = 0; r < n_requests; r++) {
+        if (!check_request_params(params[r], r, -1, -1)) return -1;
+        if (lp && rules_active(&params[r].rules, params[r].eos_id))
+            BG_FAIL(-1, "logprobs with generation rules (params[%d].rules has a rule switched on): no closed call returns log-probabilities under rules", r);
+    }
+    if (!rq.check_prompts(ctx)) return -1;
+    const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
+    for (int r = 0; r < n_requests; r++)
+        if (!check_request_params(params[r], r, V, P)) return -1;
+    if (lp && lp->n_top > V) BG_FAIL(-1, "logprobs.n_top (%d) exceeds n_vocab (%d)", lp->n_top, V);
+    if (!rq.check_prompts_model(ctx, "generation over a queue with request parameters")) return -1;
+    const size_t n_out = (size_t)n_requests * (size_t)n_predict, K = lp ? (size_t)lp->n_top : 0;
+    std::fill(out_ids, out_ids + n_out, -1);
+    std::fill(out_lens, out_lens + n_requests, 0);
+    if (out_finish) std::fill(out_finish, out_finish + n_requests, -1);
+    if (lp) {      // entries at or past a request's length, and those of a request that never takes a column, as genlp_read leaves them
+        std::fill(lp->lp, lp->lp + n_out, 0.0f);
+        if (K > 0) { std::fill(lp->top_ids, lp->top_ids + n_out * K, -1); std::fill(lp->top_lp, lp->top_lp + n_out * K, 0.0f); }
+    }
+
+    QueueReqBufs qb{};
+    bgk::QueueReqHdr *hh = nullptr;      // pinned: the header, then the admit list
+    uint8_t *admit_host = nullptr;
+    GenLpBufs lb{};
+    const int n_shared = rq.n_shared, lp_stride = std::min(n_predict, P);
+    int most_own = 0;
+    for (int r = 0; r < n_requests; r++) most_own = std::max(most_own, prompt_lens[r]);
+    const size_t stride = queue_req_stride(most_own);      // (most_own <= n_positions: check_prompts_model)
+    int C = 0;
+    biogpt_hip_queue_stats ran{};
+    QueueCall qc;
+    qc.max_units = max_columns;
+    qc.graphs = &ctx->graphs_queue_req; qc.gset = (n_shared > 0 ? 6 : 0) + (lp ? 12 : 0);      // plain, shared, lp, shared + lp: a form never replays another's step
+    qc.out_admit_step = out_admit_step; qc.out_unit = out_column; qc.seconds_out = seconds_out; qc.stats = &ran;
+    qc.prepare = [&](int units) -> bool {
+        C = units;
+        if (lp && (!genlp_prepare(ctx, &lb) || !genlp_upload(lb, lp->n_top, lp_stride))) return false;
+        if (!ctx->queue_req_buf) HIP_TRY(false, hipMalloc(&ctx->queue_req_buf, queue_req_bufs_at(nullptr, P).bytes));
+        if (!ctx->queue_req_host) HIP_TRY(false, hipHostMalloc(&ctx->queue_req_host, sizeof(bgk::QueueReqHdr) + (size_t)bgk::QUEUE_COLS * queue_req_stride(P)));
+        qb = queue_req_bufs_at(ctx->queue_req_buf, P);
+        hh = reinterpret_cast<bgk::QueueReqHdr *>(ctx->queue_req_host);
+        admit_host = ctx->queue_req_host + sizeof(bgk::QueueReqHdr);
+        qc.admit_dev = qb.admit; qc.admit_host = admit_host; qc.admit_bytes = stride;
+        qc.hdr_dev = qb.hdr; qc.hdr_host = hh; qc.hdr_bytes = sizeof(bgk::QueueReqHdr); qc.fin = hh->q.fin;
+        // the prefix the rules read; nobody runs yet
+        if (prefix) HIP_TRY(false, hipMemcpy(qb.prefix, prefix, (size_t)n_prefix * 4, hipMemcpyHostToDevice));
+        HIP_TRY(false, hipMemset(qb.hdr, 0, sizeof(bgk::QueueReqHdr)));
+        return true;
+    };
+    qc.step = [&](int t_max) -> bool {
+        if (!enqueue_forward(ctx, n_shared > 0 ? ForwardPass::decode_step_shared(C, t_max, n_shared) : ForwardPass::decode_step(C, t_max))) return false;
+        enqueue_queue_req_rows(ctx->stream, C, ctx->logits_all, V, qb, ctx->seq, ctx->seq_gen, P, P, lp ? &lb : nullptr);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    qc.admit = [&](int col, int r, int i) {
+        const int len = prompt_lens[r];
+        bgk::QueueReqAdmit *e = reinterpret_cast<bgk::QueueReqAdmit *>(admit_host + (size_t)i * stride);
+        e->a = bgk::QueueAdmit{};
+        e->a.col = col; e->a.last_token = len > 0 ? prompts[rq.off[(size_t)r] + (size_t)(len - 1)] : prefix[n_prefix - 1]; e->a.len = rq.whole_len(r);
+        e->a.limit = rq.cap[(size_t)r]; e->a.seed = seeds[r];
+        e->a.n_shared = n_shared; e->a.shared_slot = n_shared > 0 ? C : 0;
+        e->rec = request_rec_of(params[r], n_prefix, len);
+        std::memcpy(e + 1, prompts + rq.off[(size_t)r], (size_t)len * 4);
+    };
+    qc.enqueue_admit = [&](int n_admit) -> bool {
+        hipLaunchKernelGGL(bgk::queue_req_admit_kernel, dim3(n_admit), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, (int)stride, qb.seq, ctx->seq, qb.limit, qb.hdr,
+                           qb.rec, qb.hist, P);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    qc.collect = [&](int col, int r) -> int {
+        const int len = std::max(0, std::min(hh->q.len[col], rq.cap[(size_t)r]));
+        if (!queue_copy_out(ctx, col, r, len, n_predict, out_ids, lp, lb, lp_stride)) return -1;
+        out_lens[r] = len;
+        if (out_finish) out_finish[r] = hh->reason[col];
+        return len;
+    };
+    const int rc = run_queue_call(ctx, rq, qc);
+    if (stats) *stats = ran;
+    if (rc == 0 && prefix && ran.columns > 0) {
+        ctx->prefix_stats[0] = n_shared; ctx->prefix_stats[1] = ran.prompt_columns; ctx->prefix_stats[2] = 0; ctx->prefix_stats[3] = ran.columns;
+    }
+    return rc;
+}
+
+int biogpt_hip_generate_queue_requests(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests,
+                                       const int32_t *n_predicts, int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch,
+                                       const biogpt_hip_request_params *params, const uint32_t *seeds, int32_t *out_ids, int32_t *out_lens, int32_t *out_finish,
+                                       int32_t *out_admit_step, int32_t *out_column, double *seconds_out, biogpt_hip_queue_stats *stats,
+                                       const biogpt_hip_gen_logprobs *logprobs) {
+    return with_xpipe_retry(ctx, 0, [&] {
+        return generate_queue_requests_once(ctx, prefix, n_prefix, prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch, params, seeds,
+                                            out_ids, out_lens, out_finish, out_admit_step, out_column, seconds_out, stats, logprobs);
     });
 }
 

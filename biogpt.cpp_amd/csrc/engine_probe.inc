@@ -973,6 +973,89 @@ int biogpt_hip_queue_rows_device(int device, int32_t with_lp, const float *rows,
     return 0;
 }
 
+// One launch of queue_req_rows_kernel<SampleGenLp> (with_lp != 0) or <SamplePlain> over rows held in host memory (tests of the kernel itself): row r is column r
+// with the record of params[r].  Row r's history is hist_lens[r] tokens of `hist` (the histories concatenated), the first prompt_lens[r] of them its prompt -- they
+// go to the column's hist row, there is no prefix -- and the rest its generated tokens, states[r]'s n_gen of them.  states, finished, mt_states, limits and the
+// log-probability block as for biogpt_hip_queue_rows_device; hdr [1 + 3 * n_rows]: n_live, then fin, len and reason of the rows.  ids_out [n_rows][stride] is
+// filled with 0xff bytes, then the first n_gen entries of a row with its generated tokens: what the kernel does not write stays so.
+int biogpt_hip_queue_req_rows_device(int device, int32_t with_lp, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t stride,
+                                     const biogpt_hip_request_params *params, const int32_t *hist, const int32_t *hist_lens, const int32_t *prompt_lens,
+                                     uint32_t *mt_states, int32_t *states, const int32_t *limits, int32_t *finished, int32_t *hdr, int32_t *ids_out, float *lp_out,
+                                     int32_t *top_ids_out, float *top_lp_out) {
+    clear_error();
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!params) BG_FAIL(-1, "params is NULL");
+    if (!hist) BG_FAIL(-1, "hist is NULL");
+    if (!hist_lens) BG_FAIL(-1, "hist_lens is NULL");
+    if (!prompt_lens) BG_FAIL(-1, "prompt_lens is NULL");
+    if (!mt_states) BG_FAIL(-1, "mt_states is NULL");
+    if (!states) BG_FAIL(-1, "states is NULL");
+    if (!limits) BG_FAIL(-1, "limits is NULL");
+    if (!finished) BG_FAIL(-1, "finished is NULL");
+    if (!hdr) BG_FAIL(-1, "hdr is NULL");
+    if (!ids_out) BG_FAIL(-1, "ids_out is NULL");
+    if (n_rows < 1 || n_rows > bgk::QUEUE_COLS) BG_FAIL(-1, "n_rows must be in [1, %d]", bgk::QUEUE_COLS);
+    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
+    if (stride < 1 || stride > 1024) BG_FAIL(-1, "stride must be in [1, 1024]");
+    const biogpt_hip_gen_logprobs req{n_top, lp_out, top_ids_out, top_lp_out};
+    if (!check_gen_logprobs(&req, n_vocab)) return -1;
+    int hist_stride = 1;
+    for (int r = 0; r < n_rows; r++) {
+        if (!check_request_params(params[r], r, n_vocab, -1)) return -1;
+        if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
+        const int n_gen = states[(size_t)r * 8 + 2];
+        if (n_gen < 0 || n_gen >= stride) BG_FAIL(-1, "n_gen must be in [0, stride) (row %d)", r);
+        if (prompt_lens[r] < 0 || prompt_lens[r] > 1024) BG_FAIL(-1, "prompt_lens[%d] must be in [0, 1024]", r);
+        if (hist_lens[r] != prompt_lens[r] + n_gen) BG_FAIL(-1, "hist_lens[%d] (%d) must be prompt_lens[%d] (%d) + n_gen (%d)", r, hist_lens[r], r, prompt_lens[r], n_gen);
+        hist_stride = std::max(hist_stride, prompt_lens[r]);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    static_assert(sizeof(bgk::SeqState) == 32, "eight words per column state");
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, entries = (size_t)n_rows * (size_t)stride, lp_b = genlp_bufs_at(nullptr, entries, (size_t)n_top).bytes;
+    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = entries * 4;
+    std::vector<uint8_t> h(queue_req_bufs_at(nullptr, hist_stride).bytes, 0);
+    const QueueReqBufs hq = queue_req_bufs_at(h.data(), hist_stride);
+    std::vector<int32_t> ids(entries, -1);      // (0xff bytes)
+    hq.hdr->q.n_live = hdr[0];
+    size_t at = 0;
+    for (int r = 0; r < n_rows; r++) {
+        std::memcpy(hq.seq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
+        hq.seq[r].finished = finished[r];
+        hq.limit[r] = limits[r];
+        hq.hdr->q.fin[r] = hdr[1 + r]; hq.hdr->q.len[r] = hdr[1 + n_rows + r]; hq.hdr->reason[r] = hdr[1 + 2 * n_rows + r];
+        hq.rec[r] = request_rec_of(params[r], 0, prompt_lens[r]);
+        std::memcpy(hq.hist + (size_t)r * hist_stride, hist + at, (size_t)prompt_lens[r] * 4);
+        std::memcpy(ids.data() + (size_t)r * stride, hist + at + prompt_lens[r], (size_t)(hist_lens[r] - prompt_lens[r]) * 4);
+        at += (size_t)hist_lens[r];
+    }
+    ByteLayout l;      // [logits | the queue's block | column states | ids | the log-probability block]
+    const size_t o_lg = l.part(lg_b), o_q = l.part(h.size()), o_st = l.part(st_b), o_id = l.part(id_b), o_lp = l.part(lp_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    const QueueReqBufs qb = queue_req_bufs_at(d.p + o_q, hist_stride);
+    const GenLpBufs lb = genlp_bufs_at(d.p + o_lp, entries, (size_t)n_top);
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_q, h.data(), h.size(), hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_st, states, st_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_id, 0xff, l.bytes() - o_id));
+    HIP_TRY(-2, hipMemcpy(d.p + o_id, ids.data(), id_b, hipMemcpyHostToDevice));
+    if (!genlp_upload(lb, n_top, stride)) return -2;
+    enqueue_queue_req_rows(0, n_rows, d.at<float>(o_lg), n_vocab, qb, d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), stride, hist_stride, with_lp ? &lb : nullptr);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(states, d.p + o_st, st_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_q, h.size(), hipMemcpyDeviceToHost));
+    if (!genlp_read(lb, &req, n_rows, stride, nullptr)) return -2;
+    hdr[0] = hq.hdr->q.n_live;
+    for (int r = 0; r < n_rows; r++) {
+        std::memcpy(mt_states + (size_t)r * 625, hq.seq[r].mt, 625 * 4);
+        finished[r] = hq.seq[r].finished;
+        hdr[1 + r] = hq.hdr->q.fin[r]; hdr[1 + n_rows + r] = hq.hdr->q.len[r]; hdr[1 + 2 * n_rows + r] = hq.hdr->reason[r];
+    }
+    return 0;
+}
+
 // SURVEY 8 f1 on the device: `nrows` rows of `k` f32 values (host memory) -> the file's block format of `type`, byte-identical to
 // the host quantizer (biogpt_hip_quantize_file uses the host one: it has to work without a GPU)
 int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, int64_t nrows, int64_t k, uint8_t *dst) {

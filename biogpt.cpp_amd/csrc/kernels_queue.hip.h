@@ -14,6 +14,17 @@
 //                        Behind a shared prefix the record names the shared rows and their slot (SeqState::pad[0] / pad[1], what the decode steps
 //                        behind a prefix read); the plain queue passes zeros.
 //
+//   queue_req_rows_kernel<Extra>   the step of a queue whose requests carry their own parameters (biogpt_hip_generate_queue_requests): one workgroup per
+//                        column, one launch per step.  A column's record (QueueReqRec) holds its sampler, its EOS id, its rules and its stop sequences:
+//                        the rules on the column's logits row in place (rules_apply_row, kernels_rules.hip.h -- the function rules_rows_kernel runs; skipped
+//                        where the record has none), sample_rows_step with the record's SampleCtl, then by thread 0 the stop check on the token just
+//                        appended -- the last len_i entries of the column's seq_gen row against each stop sequence, only where n_gen >= len_i, so a match
+//                        never reaches into the prompt -- and queue_report.  The reason a column finished (QueueReqHdr::reason: 0 limit, 1 EOS, 2 + i stop
+//                        sequence i) travels in the header behind QueueHdr.  The history the rules read is the call's prefix (one copy), the column's own
+//                        prompt tokens (hist, one row per column) and its seq_gen row.
+//   queue_req_admit_kernel   queue_admit_kernel's work (queue_admit_column, one function of both) and the column's record and prompt tokens, copied from the
+//                        uploaded admit list: a refilled column inherits nothing from its predecessor.
+//
 // SampleCtl / SampleSeq live in a buffer of the queue's own: the captured steps of biogpt_hip_generate_sample keep their pointers.  Both kernels write
 // plain vector stores and atomicAdd / atomicSub only.
 #pragma once
@@ -23,6 +34,7 @@
 
 #include "kernels.hip.h"
 #include "kernels_genlp.hip.h"
+#include "kernels_rules.hip.h"
 #include "kernels_sample.hip.h"
 
 namespace bgk {
@@ -77,11 +89,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void queue_rows_lp_kernel(const flo
     if (threadIdx.x == 0) queue_report(col, sq, seq, limit, hdr);
 }
 
-// grid (admitted columns), QUEUE_ADMIT_THREADS threads; list: [gridDim.x]
-__global__ __launch_bounds__(QUEUE_ADMIT_THREADS) void queue_admit_kernel(const QueueAdmit *list, SampleSeq *sq, SeqState *seq, int32_t *limit, QueueHdr *hdr) {
-    __shared__ uint32_t mt[MT_N + 1];
-    const QueueAdmit a = list[blockIdx.x];
-    if (a.col < 0 || a.col >= QUEUE_COLS) return;      // (uniform)
+// One admitted column, by the QUEUE_ADMIT_THREADS threads of a workgroup; mt: MT_N + 1 words of LDS
+__device__ __forceinline__ void queue_admit_column(const QueueAdmit &a, uint32_t *mt, SampleSeq *sq, SeqState *seq, int32_t *limit, QueueHdr *hdr) {
     if (threadIdx.x == 0) { mt_seed(a.seed, mt); mt_regenerate(mt); }
     __syncthreads();
     for (int i = threadIdx.x; i <= MT_N; i += QUEUE_ADMIT_THREADS) sq[a.col].mt[i] = mt[i];
@@ -96,6 +105,108 @@ __global__ __launch_bounds__(QUEUE_ADMIT_THREADS) void queue_admit_kernel(const 
         hdr->len[a.col] = 0;
         atomicAdd(&hdr->n_live, 1);
     }
+}
+
+// grid (admitted columns), QUEUE_ADMIT_THREADS threads; list: [gridDim.x]
+__global__ __launch_bounds__(QUEUE_ADMIT_THREADS) void queue_admit_kernel(const QueueAdmit *list, SampleSeq *sq, SeqState *seq, int32_t *limit, QueueHdr *hdr) {
+    __shared__ uint32_t mt[MT_N + 1];
+    const QueueAdmit a = list[blockIdx.x];
+    if (a.col < 0 || a.col >= QUEUE_COLS) return;      // (uniform)
+    queue_admit_column(a, mt, sq, seq, limit, hdr);
+}
+
+// ---- requests with their own parameters (biogpt_hip_generate_queue_requests) ----------------------------------------------------------------------------
+constexpr int QUEUE_REQ_SUPPRESS = 64;      // suppress ids of a request
+constexpr int QUEUE_REQ_STOPS = 4;          // stop sequences of a request
+constexpr int QUEUE_REQ_STOP_LEN = 8;       // ... of this many ids each, at most
+
+// a column's request: what the step reads instead of the call's one SampleCtl and RulesCtl
+struct QueueReqRec {
+    SampleCtl ctl;                          // the request's sampler and EOS id (n_live: a word sample_append counts down, read by nobody)
+    float penalty;                          // the rules as RulesCtl holds them: 1.0 / 0 / 0 / 0 off
+    int32_t ngram, min_new, n_suppress;
+    int32_t rules_on;                       // one of the four is on: the step runs rules_apply_row
+    int32_t n_prefix, n_own;                // the history in front of the generated tokens: n_prefix tokens of the call's prefix, then n_own of the column's hist row
+    int32_t n_stop;
+    int32_t stop_len[QUEUE_REQ_STOPS];
+    int32_t stop[QUEUE_REQ_STOPS][QUEUE_REQ_STOP_LEN];
+    int32_t suppress[QUEUE_REQ_SUPPRESS];
+};
+static_assert(sizeof(QueueReqRec) % 16 == 0, "records lie 16-byte aligned in the admit list");
+
+// the header of this form: QueueHdr as the driver reads it, then why a finished column finished (0: its limit; 1: its EOS id; 2 + i: stop sequence i)
+struct QueueReqHdr {
+    QueueHdr q;
+    int32_t reason[QUEUE_COLS];
+};
+
+// one entry of the admit list: the admit record, the request's record, then rec.n_own prompt tokens; entries lie `stride` bytes apart (a multiple of 16)
+struct QueueReqAdmit {
+    QueueAdmit a;
+    QueueReqRec rec;
+};
+
+// The step of column blockIdx.x, by the SAMPLE_THREADS threads of its workgroup.  logits: [columns][ldl], a column's row is changed in place by its rules;
+// rec: [QUEUE_COLS]; prefix_tok: the call's prefix (rec.n_prefix tokens of it are read); hist: [QUEUE_COLS][hist_stride] own prompt tokens; seen: the rules'
+// bitmap, (n_vocab + 31) / 32 words of LDS
+template <class Extra>
+__device__ __forceinline__ void queue_req_rows_step(float *logits, int ldl, int n_vocab, QueueReqRec *rec, SampleSeq *sq, SeqState *seq, int32_t *seq_gen,
+                                                    int gen_stride, const int32_t *limit, QueueReqHdr *hdr, const int32_t *prefix_tok, const int32_t *hist,
+                                                    int hist_stride, uint32_t *seen, Extra extra) {
+    const int col = blockIdx.x;
+    if (col >= QUEUE_COLS || sq[col].finished) return;      // (uniform) a finished column was reported when it finished and writes nothing
+    QueueReqRec *const me = rec + col;
+    const int32_t *gen = seq_gen + (size_t)col * gen_stride;
+    if (me->rules_on) {      // (uniform) most requests have none
+        const int n_prefix = max(0, min(me->n_prefix, hist_stride)), n_prompt = n_prefix + max(0, min(me->n_own, hist_stride - n_prefix));
+        const int32_t *own = hist + (size_t)col * hist_stride;
+        const int n_gen = max(0, min(seq[col].n_gen, gen_stride));
+        auto h = [&](int i) { return i < n_prefix ? prefix_tok[i] : i < n_prompt ? own[i - n_prefix] : gen[i - n_prompt]; };
+        rules_apply_row<SAMPLE_THREADS>(logits + (size_t)col * ldl, n_vocab, seen, h, n_prompt + n_gen, n_gen, me->penalty, me->ngram, me->min_new, me->ctl.eos_id,
+                                        max(0, min(me->n_suppress, QUEUE_REQ_SUPPRESS)), me->suppress);
+        __syncthreads();      // the selection reads the row as the rules left it
+    }
+    sample_rows_step(logits, ldl, n_vocab, &me->ctl, sq, seq, seq_gen, gen_stride, extra);
+    if (threadIdx.x == 0) {      // (it appended the token and wrote the state it reads here)
+        int reason = sq[col].finished ? 1 : 0;      // an EOS comes first
+        const int n_gen = max(0, min(seq[col].n_gen, gen_stride)), n_stop = max(0, min(me->n_stop, QUEUE_REQ_STOPS));
+        for (int i = 0; i < n_stop && reason == 0; i++) {
+            const int len = me->stop_len[i];
+            if (len < 1 || len > QUEUE_REQ_STOP_LEN || n_gen < len) continue;
+            bool same = true;
+            for (int j = 0; j < len && same; j++) same = gen[n_gen - len + j] == me->stop[i][j];
+            if (same) { sq[col].finished = 1; reason = 2 + i; }
+        }
+        queue_report(col, sq, seq, limit, &hdr->q);
+        if (sq[col].finished) hdr->reason[col] = reason;
+    }
+}
+
+// grid (columns), SAMPLE_THREADS threads, dynamic LDS: (n_vocab + 31) / 32 words.  Extra: SamplePlain, or SampleGenLp (entry n_gen of row col of its block
+// beside the id, as queue_rows_lp_kernel)
+template <class Extra>
+__global__ __launch_bounds__(SAMPLE_THREADS) void queue_req_rows_kernel(float *logits, int ldl, int n_vocab, QueueReqRec *rec, SampleSeq *sq, SeqState *seq,
+                                                                        int32_t *seq_gen, int gen_stride, const int32_t *limit, QueueReqHdr *hdr,
+                                                                        const int32_t *prefix_tok, const int32_t *hist, int hist_stride, Extra extra) {
+    extern __shared__ uint32_t queue_req_seen[];
+    queue_req_rows_step(logits, ldl, n_vocab, rec, sq, seq, seq_gen, gen_stride, limit, hdr, prefix_tok, hist, hist_stride, queue_req_seen, extra);
+}
+
+// grid (admitted columns), QUEUE_ADMIT_THREADS threads; list: gridDim.x entries (QueueReqAdmit, then the tokens), `stride` bytes apart
+__global__ __launch_bounds__(QUEUE_ADMIT_THREADS) void queue_req_admit_kernel(const uint8_t *list, int stride, SampleSeq *sq, SeqState *seq, int32_t *limit,
+                                                                              QueueReqHdr *hdr, QueueReqRec *rec, int32_t *hist, int hist_stride) {
+    __shared__ uint32_t mt[MT_N + 1];
+    const QueueReqAdmit *e = reinterpret_cast<const QueueReqAdmit *>(list + (size_t)blockIdx.x * (size_t)stride);
+    const QueueAdmit a = e->a;
+    if (a.col < 0 || a.col >= QUEUE_COLS) return;      // (uniform)
+    queue_admit_column(a, mt, sq, seq, limit, &hdr->q);
+    const int32_t *src = reinterpret_cast<const int32_t *>(&e->rec);
+    int32_t *dst = reinterpret_cast<int32_t *>(rec + a.col);
+    for (int i = threadIdx.x; i < (int)(sizeof(QueueReqRec) / 4); i += QUEUE_ADMIT_THREADS) dst[i] = src[i];
+    const int32_t *tok = reinterpret_cast<const int32_t *>(e + 1);
+    const int n_own = max(0, min(min(e->rec.n_own, hist_stride), (stride - (int)sizeof(QueueReqAdmit)) / 4));
+    for (int i = threadIdx.x; i < n_own; i += QUEUE_ADMIT_THREADS) hist[(size_t)a.col * hist_stride + i] = tok[i];
+    if (threadIdx.x == 0) hdr->reason[a.col] = 0;
 }
 
 }  // namespace bgk

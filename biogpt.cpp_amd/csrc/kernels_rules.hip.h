@@ -10,6 +10,8 @@
 //                          n-gram         every position i in [0, L - n] whose n - 1 tokens equal the last n - 1 of h bans h[i + n - 1]
 //                          min new / suppress   -inf at the EOS id while fewer than m tokens are generated / at every listed id
 //                        The penalty comes first (a barrier apart); the bans only write -inf, in any order.
+//   rules_apply_row      the penalty, the n-gram ban and the two -inf rules as a __device__ function of the row, the history accessor h(i), L, n_gen and the
+//                        rule values: rules_rows_kernel runs it with the call's values, queue_req_rows_kernel (kernels_queue.hip.h) with a column's own.
 //
 // The grid is fixed and every value is read from device memory (RulesCtl, SeqState, the histories): the launch is capturable, and a captured
 // step serves every call whose rule set switches the same kernels in.
@@ -45,6 +47,44 @@ struct RulesRow {
     int32_t n_prompt;
 };
 
+// The rules on one row, by the THREADS threads of its workgroup: h(i) is token i of the row's history of L tokens, n_gen of them generated; seen: the
+// bitmap, (n_vocab + 31) / 32 words of LDS.  rules_rows_kernel calls it with the call's values, queue_req_rows_kernel (kernels_queue.hip.h) with the
+// column's own.  Every token used as an index is range-checked.
+template <int THREADS, class Hist>
+__device__ __forceinline__ void rules_apply_row(float *row, int n_vocab, uint32_t *seen, Hist h, int L, int n_gen, float p, int n, int min_new, int eos,
+                                                int n_suppress, const int32_t *suppress) {
+    const int tid = threadIdx.x;
+    if (p != 1.0f) {
+        const int nw = (n_vocab + 31) >> 5;
+        for (int w = tid; w < nw; w += THREADS) seen[w] = 0u;
+        __syncthreads();
+        for (int i = tid; i < L; i += THREADS) {
+            const int t = h(i);
+            if (t < 0 || t >= n_vocab) continue;
+            const uint32_t bit = 1u << (t & 31);
+            if (atomicOr(&seen[t >> 5], bit) & bit) continue;      // another position of the same token came first
+            const float s = row[t];
+            row[t] = s < 0.0f ? s * p : __fdiv_rn(s, p);
+        }
+        __syncthreads();      // the bans below overwrite penalised entries
+    }
+
+    if (n > 0 && L + 1 >= n) {
+        const int t0 = L - n + 1;      // the tail h[t0 .. L - 1]: n - 1 tokens
+        for (int i = tid; i <= L - n; i += THREADS) {
+            bool same = true;
+            for (int j = 0; j < n - 1 && same; j++) same = h(i + j) == h(t0 + j);
+            const int t = h(i + n - 1);
+            if (same && t >= 0 && t < n_vocab) row[t] = -INFINITY;
+        }
+    }
+    if (tid == 0 && eos >= 0 && eos < n_vocab && n_gen < min_new) row[eos] = -INFINITY;
+    for (int i = tid; i < n_suppress; i += THREADS) {
+        const int t = suppress[i];
+        if (t >= 0 && t < n_vocab) row[t] = -INFINITY;
+    }
+}
+
 // rows: [gridDim.x][ldl], in place; seq: the rows' column states (n_gen = tokens generated); seq_gen: [row][gen_stride] generated tokens;
 // skip: nullptr, or a word per row (skip_stride words apart; 0: one word for all) that, non-zero, leaves the row alone (a finished sequence, a
 // finished search: nothing reads the row).  Dynamic LDS: (n_vocab + 31) / 32 words.
@@ -75,38 +115,7 @@ __global__ __launch_bounds__(LP_THREADS) void rules_rows_kernel(float *rows, int
         __syncthreads();
     }
 
-    const float p = ctl->penalty;
-    if (p != 1.0f) {
-        const int nw = (n_vocab + 31) >> 5;
-        for (int w = tid; w < nw; w += LP_THREADS) seen[w] = 0u;
-        __syncthreads();
-        for (int i = tid; i < L; i += LP_THREADS) {
-            const int t = h(i);
-            if (t < 0 || t >= n_vocab) continue;
-            const uint32_t bit = 1u << (t & 31);
-            if (atomicOr(&seen[t >> 5], bit) & bit) continue;      // another position of the same token came first
-            const float s = row[t];
-            row[t] = s < 0.0f ? s * p : __fdiv_rn(s, p);
-        }
-        __syncthreads();      // the bans below overwrite penalised entries
-    }
-
-    const int n = ctl->ngram;
-    if (n > 0 && L + 1 >= n) {
-        const int t0 = L - n + 1;      // the tail h[t0 .. L - 1]: n - 1 tokens
-        for (int i = tid; i <= L - n; i += LP_THREADS) {
-            bool same = true;
-            for (int j = 0; j < n - 1 && same; j++) same = h(i + j) == h(t0 + j);
-            const int t = h(i + n - 1);
-            if (same && t >= 0 && t < n_vocab) row[t] = -INFINITY;
-        }
-    }
-    const int eos = ctl->eos_id;
-    if (tid == 0 && eos >= 0 && eos < n_vocab && n_gen < ctl->min_new) row[eos] = -INFINITY;
-    for (int i = tid; i < ctl->n_suppress; i += LP_THREADS) {
-        const int t = ctl->suppress[i];
-        if (t >= 0 && t < n_vocab) row[t] = -INFINITY;
-    }
+    rules_apply_row<LP_THREADS>(row, n_vocab, seen, h, L, n_gen, ctl->penalty, ctl->ngram, ctl->min_new, ctl->eos_id, ctl->n_suppress, ctl->suppress);
 }
 
 }  // namespace bgk

@@ -558,7 +558,7 @@ int biogpt_hip_generate_lookup(biogpt_hip_ctx *ctx, const int32_t *prompts /* co
  * the host until admitted.  max_columns in [1, 512], group in [1, 64], n_predicts[r] in [0, n_predict], top_k in [1, 64], temp finite and > 0, top_p finite,
  * eos_id in [-1, n_vocab), no empty prompt, prompt_lens[r] <= n_positions.  The context's own K / V cache, position and logits row are left alone.  Needs
  * the BioGPT-base fast chain (block-quantized weights); anything else fails with -1.  No rules, trie or several samples per request (a shared prefix and
- * log-probabilities: biogpt_hip_generate_queue_prefix); the steps always run as the launch chain.  Returns 0, or < 0 on error (argument errors, -1, the message names the field, come before any HIP
+ * log-probabilities: biogpt_hip_generate_queue_prefix; rules, stop sequences and a sampler per request: biogpt_hip_generate_queue_requests); the steps always run as the launch chain.  Returns 0, or < 0 on error (argument errors, -1, the message names the field, come before any HIP
  * call). */
 typedef struct biogpt_hip_queue_stats {
     int32_t columns, steps, groups, admissions, prompt_columns;
@@ -810,7 +810,7 @@ int biogpt_hip_genlp_rows_device(int device, int32_t mode /* 0 greedy, 1 sampled
  * lp [n_requests][n_predict] and top_ids / top_lp [n_requests][n_predict][n_top] (n_predict the row stride as GIVEN); entries at or past a request's length,
  * and every entry of a request that never takes a column, read 0 / -1 / 0.  max_columns in [1, 511] behind a prefix (one K / V slot holds the shared rows);
  * n_prefix >= 1, n_prefix + suffix_lens[r] <= n_positions; everything else as biogpt_hip_generate_queue.  Afterwards biogpt_hip_prefix_stats reads
- * {n_shared, stats.prompt_columns, 0, columns}.  No rules, trie, wide sampler or several samples per request.  Returns 0, or < 0 on error (argument errors, -1,
+ * {n_shared, stats.prompt_columns, 0, columns}.  No rules (they are biogpt_hip_generate_queue_requests'), trie, wide sampler or several samples per request.  Returns 0, or < 0 on error (argument errors, -1,
  * come before any HIP call: first those of logprobs, then what needs no model, with no context and no device). */
 int biogpt_hip_generate_queue_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix /* or NULL */, int32_t n_prefix, const int32_t *suffixes /* concatenated */,
                                      const int32_t *suffix_lens, int32_t n_requests, const int32_t *n_predicts /* or NULL */, int32_t n_predict,
@@ -826,6 +826,50 @@ int biogpt_hip_generate_queue_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix 
 int biogpt_hip_queue_rows_device(int device, int32_t with_lp, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t stride, int32_t top_k,
                                  double top_p, double temp, int32_t eos_id, uint32_t *mt_states, int32_t *states, const int32_t *limits, int32_t *finished,
                                  int32_t *hdr, int32_t *ids_out, float *lp_out, int32_t *top_ids_out, float *top_lp_out);
+
+/* ---- generation over a queue whose requests carry their own parameters ----
+ * biogpt_hip_generate_queue_prefix with one biogpt_hip_request_params per request instead of one top_k / top_p / temp / eos_id for the call: every request has its
+ * own sampler, its own EOS id, its own generation rules and up to 4 stop sequences of up to 8 ids.  Request r's ids and length are those of
+ *   biogpt_hip_generate_sample_rules(its prompt alone -- behind a prefix: prefix ++ suffix r --, n_samples 1, n_r, params[r]'s top_k / top_p / temp / eos_id / rules,
+ *                                    seeds[r])
+ * truncated just behind the first position at which one of its stop sequences is complete, bit for bit, whatever else is in the queue and whatever max_columns and
+ * group are.  A stop sequence counts only where it lies entirely inside the generated tokens (a match never reaches back into the prompt); the check runs on the
+ * token just appended, behind the EOS check, so the rules and the sampler see what they see in the closed call.  An EOS ends a request as before and is included.
+ * out_finish[r] (may be NULL): 0 the request reached its limit; 1 it drew its EOS id; 2 + i stop sequence i completed (two at the same token: the lower index; a
+ * stop sequence that completes on the limit's token is reported, not the limit); -1 it never took a column.  A call whose requests all carry the same sampler,
+ * no rules and no stop sequence returns what biogpt_hip_generate_queue_prefix returns, item for item (ids, lens, admit_step, column, stats).
+ * What composes: a prefix with everything; logprobs with samplers and stop sequences (the rows are those of biogpt_hip_generate_sample_lp of the request alone up
+ * to the truncation, 0 / -1 / 0 behind it), but logprobs with a request that has a rule switched on is an argument error, as the closed calls have no such form.
+ * No trie, wide sampler or several samples per request.  A step is the forward pass and ONE selection launch (queue_req_rows_kernel: rules, draw, stop check and
+ * report; csrc/kernels_queue.hip.h).
+ * Argument errors (-1, before any HIP call, in the order of biogpt_hip_generate_queue_prefix; those of a request name params[r] and the field): top_k outside
+ * [1, 64] or above n_vocab, temp not finite or <= 0, top_p not finite, eos_id outside [-1, n_vocab), the rules as biogpt_hip_generate_sample_rules checks them,
+ * rules.n_suppress > 64, n_stop outside [0, 4], a stop length outside [1, 8], a stop id outside [0, n_vocab).  Needs the BioGPT-base fast chain; a wide file is
+ * refused (the rules were never checked at other vocabularies).  Returns 0, or < 0 on error. */
+typedef struct biogpt_hip_request_params {
+    int32_t top_k, eos_id;            /* top_k in [1, 64]; eos_id -1: none */
+    double  top_p, temp;
+    biogpt_hip_gen_rules rules;       /* as for biogpt_hip_generate_sample_rules; n_suppress <= 64 here */
+    int32_t n_stop;                   /* 0 .. 4 stop sequences */
+    const int32_t *stop;              /* concatenated ids */
+    const int32_t *stop_lens;         /* each in [1, 8] */
+} biogpt_hip_request_params;
+
+int biogpt_hip_generate_queue_requests(biogpt_hip_ctx *ctx, const int32_t *prefix /* or NULL */, int32_t n_prefix, const int32_t *prompts /* concatenated; suffixes behind a prefix */,
+                                       const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts /* or NULL */, int32_t n_predict, int32_t max_columns,
+                                       int32_t group, int32_t n_batch, const biogpt_hip_request_params *params /* [n_requests] */, const uint32_t *seeds,
+                                       int32_t *out_ids, int32_t *out_lens, int32_t *out_finish /* may be NULL */, int32_t *out_admit_step /* may be NULL */,
+                                       int32_t *out_column /* may be NULL */, double *seconds_out, biogpt_hip_queue_stats *stats /* may be NULL */,
+                                       const biogpt_hip_gen_logprobs *logprobs /* or NULL */);
+/* Test hook: one launch of queue_req_rows_kernel alone (with_lp != 0: with log-probabilities) over rows held in host memory, as biogpt_hip_queue_rows_device: row r is
+ * column r with the record of params[r].  Row r's history is hist_lens[r] tokens of hist (the histories concatenated): the first prompt_lens[r] its prompt, the
+ * rest its generated tokens, states[r]'s n_gen of them.  hdr is [1 + 3 * n_rows]: n_live, fin[], len[], reason[].  ids_out [n_rows][stride] is preset to 0xff
+ * bytes, then the first n_gen entries of row r to its generated tokens; lp_out / top_ids_out / top_lp_out are preset to 0xff bytes: what the launch does not
+ * write stays so.  Argument errors return -1 before any HIP call.  Returns 0, < 0 on error. */
+int biogpt_hip_queue_req_rows_device(int device, int32_t with_lp, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t stride,
+                                     const biogpt_hip_request_params *params /* [n_rows] */, const int32_t *hist /* concatenated */, const int32_t *hist_lens,
+                                     const int32_t *prompt_lens, uint32_t *mt_states, int32_t *states, const int32_t *limits, int32_t *finished, int32_t *hdr,
+                                     int32_t *ids_out, float *lp_out, int32_t *top_ids_out, float *top_lp_out);
 
 /* ---- hidden states, pooled embeddings, classification heads (no counterpart in the reference) ----
  * The activations in front of the lm_head, from the causal passes of biogpt_hip_score without the lm_head and the log-softmax.
