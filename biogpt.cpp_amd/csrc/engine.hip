@@ -234,15 +234,25 @@ struct EngineOptions {
     }
 };
 
-namespace {
-}  // namespace
+constexpr int GRAPH_BUCKETS = 6;      // the context buckets of a captured decode step: graph_bucket() is in [0, GRAPH_BUCKETS)
 
-// The captured steps of one mode of column generation: [12 * (form of the step: 0 plain, 1 with rules, 2 with a trie, 3 behind a shared prefix read in
-// place, 4 with log-probabilities, 5 with log-probabilities behind a shared prefix read in place) + 6 * (steps as column-per-XCD launches) + context
-// bucket], valid for the call shape (key_a, key_b) they were captured for -- sequences, or groups and beams
+// The form of a step of column generation: everything but the call's shape and the context bucket that decides which launches the step is
+struct StepForm {
+    enum Selection { Plain, Rules, Trie, Wide, N_SELECTIONS };      // the mode's selection alone, rules or a trie in front of it, the whole-vocabulary sampler
+    Selection sel = Plain;
+    bool lp = false;          // the selection also writes log-probabilities (kernels_genlp.hip.h)
+    bool shared = false;      // prefix rows are read in place (ForwardPass::decode_step_shared)
+    bool xcols = false;       // the steps are column-per-XCD launches
+};
+
+// The captured steps of one mode of column generation, valid for the call shape (key_a, key_b) they were captured for -- sequences, or groups and beams.  A step
+// is filed under its form and its context bucket; every combination of a form's fields has slots of its own, so no form replays another's step, whatever the
+// modes' argument checks let through.  slot() alone knows the layout.
 struct ColumnGraphs {
-    hipGraphExec_t exec[96] = {};
+    static constexpr int N_SLOTS = StepForm::N_SELECTIONS * 2 * 2 * 2 * GRAPH_BUCKETS;
+    hipGraphExec_t exec[N_SLOTS] = {};
     int key_a = 0, key_b = 0;
+    static int slot(const StepForm &f, int bucket) { return ((((int)f.sel * 2 + (f.lp ? 1 : 0)) * 2 + (f.shared ? 1 : 0)) * 2 + (f.xcols ? 1 : 0)) * GRAPH_BUCKETS + bucket; }
 };
 
 // ---- context ----------------------------------------------------------------------------------------
@@ -2642,9 +2652,8 @@ struct ColumnCall {
     ColumnGraphs *graphs = nullptr;     // the mode's captured steps, valid for the call shape (key_a, key_b)
     int key_a = 0, key_b = 0;
     int extra_steps = 0;                // steps beyond one per token (contrastive: 1, the prompt's last token has a step of its own)
-    int gset_extra = 0;                 // 12 with rules, 24 with a trie, 72 with the wide sampler (84 behind shared rows read in place): another form of the
-                                        // step, so other graphs
-    bool with_lp = false;               // the selection also writes log-probabilities (kernels_genlp.hip.h; never with rules or a trie): graph sets of its own
+    StepForm form;                      // the mode names what it knows, its selection and whether that writes log-probabilities; run_column_call sets shared
+                                        // and xcols
     int key_stride = 1;                 // positions a column can move on in one step, at most (prompt-lookup decoding: 1 + max_draft); > 1: the word behind
                                         // live_dev holds the furthest position of any column
     bool plain_steps = false;           // the step is no decode step of one column per sequence: never the column-per-XCD launches
@@ -2759,19 +2768,20 @@ struct ColumnKeys {
 };
 
 // Captures `step` for the context buckets of steps 2 .. n_steps (t_max = max_len + 1 .. keys.worst(n_steps - 1): the ones run_column_steps replays) into
-// graphs.exec[gset + bucket], where they are not there yet.  *use_graph: whether the steps are replayed at all.
-static bool capture_column_steps(biogpt_hip_ctx *ctx, ColumnGraphs &graphs, int gset, const ColumnKeys &keys, int n_steps, const ColumnStep &step, bool *use_graph) {
+// the slots of `form`, where they are not there yet.  *use_graph: whether the steps are replayed at all.
+static bool capture_column_steps(biogpt_hip_ctx *ctx, ColumnGraphs &graphs, const StepForm &form, const ColumnKeys &keys, int n_steps, const ColumnStep &step, bool *use_graph) {
     *use_graph = ctx->opt.no_graph == 0 && (ctx->xc_batch != 0 || plain_graph_begin(ctx));      // (a captured five-launch step is not replayed beside another context's persistent launch)
     if (*use_graph && n_steps > 1) {
         for (int b = graph_bucket(keys.first_replayed()); b <= graph_bucket(keys.worst(n_steps - 1)); b++) {
-            if (graphs.exec[gset + b]) continue;
+            hipGraphExec_t &exec = graphs.exec[ColumnGraphs::slot(form, b)];
+            if (exec) continue;
             hipGraph_t g = nullptr;
             HIP_TRY(false, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
             const bool ok = step(bucket_tmax(ctx, b));
             hipError_t e = hipStreamEndCapture(ctx->stream, &g);
             if (!ok) { if (g) (void)hipGraphDestroy(g); return false; }
             HIP_TRY(false, e);
-            HIP_TRY(false, hipGraphInstantiate(&graphs.exec[gset + b], g, nullptr, nullptr, 0));
+            HIP_TRY(false, hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
             (void)hipGraphDestroy(g);
         }
     }
@@ -2855,7 +2865,7 @@ static bool prefix_prompts(const biogpt_hip_ctx *c, ColumnCall &cc, std::vector<
 // group, and once the group BEFORE the one just enqueued reports none, nothing more is enqueued (one group stays in flight; steps after the end change nothing).
 // keys.stride > 1: the word behind live_dev (the furthest position of any column) travels with it, and a step k behind the last step e whose word has come back
 // is bounded by that position + (k - e) * stride instead of keys.worst(k): attention follows the context the columns really have.
-static bool run_column_steps(biogpt_hip_ctx *ctx, const ColumnGraphs &graphs, int gset, bool use_graph, const ColumnKeys &keys, int n_steps, const ColumnStep &step,
+static bool run_column_steps(biogpt_hip_ctx *ctx, const ColumnGraphs &graphs, const StepForm &form, bool use_graph, const ColumnKeys &keys, int n_steps, const ColumnStep &step,
                              const int32_t *live_dev) {
     if (!step(keys.worst(0))) return false;
     const bool with_pos = live_dev && keys.stride > 1;
@@ -2864,7 +2874,7 @@ static bool run_column_steps(biogpt_hip_ctx *ctx, const ColumnGraphs &graphs, in
         for (const int end = std::min(n_steps - 1, k + keys.group() - 1); k <= end; k++) {
             int t_max = keys.worst(k);
             if (seen_step >= 0) t_max = std::min<long>(t_max, std::max<long>(keys.first_replayed(), (long)seen_pos + (long)(k - seen_step) * keys.stride));
-            if (use_graph) HIP_TRY(false, hipGraphLaunch(graphs.exec[gset + graph_bucket(t_max)], ctx->stream));
+            if (use_graph) HIP_TRY(false, hipGraphLaunch(graphs.exec[ColumnGraphs::slot(form, graph_bucket(t_max))], ctx->stream));
             else if (!step(t_max)) return false;
         }
         if (!live_dev) continue;
@@ -2904,15 +2914,15 @@ static int run_column_call(biogpt_hip_ctx *ctx, ColumnCall &cc, int n_predict, d
     cc.in_place = cc.n_shared > 0 && xc == 0;
     if (!upload_column_starts(ctx, prompts, lens, cc.n_prompts, cc.per_prompt, cc.n_shared, cc.in_place ? shared : SharedRows{})) return -2;
     if (cc.upload && !cc.upload()) return -2;
-    const int gset = 6 * xc + (cc.with_lp ? (cc.in_place ? 60 : 48) : cc.in_place ? (cc.gset_extra == 72 ? 84 : 36) : cc.gset_extra);
+    cc.form.shared = cc.in_place; cc.form.xcols = xc != 0;
     const ColumnKeys keys{cc.max_len, cc.key_stride, ctx->hp.n_positions};
     bool use_graph;
-    if (!capture_column_steps(ctx, *cc.graphs, gset, keys, n_steps, cc.step, &use_graph)) return -2;
+    if (!capture_column_steps(ctx, *cc.graphs, cc.form, keys, n_steps, cc.step, &use_graph)) return -2;
 
     const auto t0 = std::chrono::steady_clock::now();
     if (!ingest_column_prompts(ctx, cc, prompts, lens, shared)) return -2;
     if (cc.after_ingest && !cc.after_ingest()) return -2;
-    if (!run_column_steps(ctx, *cc.graphs, gset, use_graph, keys, n_steps, cc.step, cc.live_dev)) return -2;
+    if (!run_column_steps(ctx, *cc.graphs, cc.form, use_graph, keys, n_steps, cc.step, cc.live_dev)) return -2;
     if (cc.before_sync && !cc.before_sync()) return -2;
     HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
     const auto t1 = std::chrono::steady_clock::now();
@@ -3010,7 +3020,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     cc.prefix = prefix; cc.n_prefix = n_prefix;
     GenLpBufs lb{};
     if (lp) {
-        cc.with_lp = true;
+        cc.form.lp = true;
         cc.prepare = [&]() -> bool { return genlp_prepare(ctx, &lb); };
         cc.upload = [&]() -> bool { return genlp_upload(lb, lp->n_top, cc.n_predict); };
     }
@@ -3798,14 +3808,42 @@ static bgk::SampleCtl sample_ctl_of(int top_k, int eos_id, int n_seqs, double to
     return hc;
 }
 
+// temp and top_p of any sampler; `who` begins the message: "", "sampler: " or "params[3]."
+static bool check_temp_top_p(double temp, double top_p, const char *who = "") {
+    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(false, "%stemp must be finite and > 0", who);
+    if (!std::isfinite(top_p)) BG_FAIL(false, "%stop_p must be finite (>= 1: no cut)", who);
+    return true;
+}
+// The values of sample_rows_kernel's sampler and an EOS id (-1: none), for rows of V entries; V < 0: the width is not known yet, and the check with it follows.
+// A message names the values with `pre` in front, a format of r: "" or "params[%d]."
+static bool check_sample_values(int top_k, double top_p, double temp, int eos_id, int V, const char *pre = "", int r = 0) {
+    char who[32];
+    std::snprintf(who, sizeof who, pre, r);
+    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || (V >= 0 && top_k > V)) BG_FAIL(false, "%stop_k must be in [1, %d] and at most n_vocab", who, bgk::SAMPLE_MAX_K);
+    if (!check_temp_top_p(temp, top_p, who)) return false;
+    if (V < 0 && eos_id < -1) BG_FAIL(false, "%seos_id %d out of range: must be a token id, or -1 for none", who, eos_id);
+    if (V >= 0 && (eos_id < -1 || eos_id >= V)) BG_FAIL(false, "%seos_id %d out of range: must be in [0, %d), or -1 for none", who, eos_id, V);
+    return true;
+}
+
+// The generators of n rows as a caller holds them, 625 words each (the state words, then the index of the next output): checked, into SampleSeq[] and back
+constexpr size_t MT_WORDS = bgk::MT_N + 1;
+static_assert(sizeof(bgk::SampleSeq::mt) == MT_WORDS * 4, "a generator as SampleSeq holds it");
+static bool check_mt_states(const uint32_t *mt, int n) {
+    for (int r = 0; r < n; r++)
+        if (mt[r * MT_WORDS + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(false, "generator index out of range (row %d)", r);
+    return true;
+}
+static void mt_states_in(bgk::SampleSeq *seq, const uint32_t *mt, int n) { for (int r = 0; r < n; r++) std::memcpy(seq[r].mt, mt + r * MT_WORDS, MT_WORDS * 4); }
+static void mt_states_out(uint32_t *mt, const bgk::SampleSeq *seq, int n) { for (int r = 0; r < n; r++) std::memcpy(mt + r * MT_WORDS, seq[r].mt, MT_WORDS * 4); }
+
 static_assert(sizeof(bgk::SampleWide) == sizeof(biogpt_hip_sampler), "the sampler goes to the device as it is");
 // the ranges of a sampler's values, for rows of V entries (V < 0: the width is not known yet)
 static bool check_sampler(const biogpt_hip_sampler *sp, int V) {
     if (!sp) BG_FAIL(false, "null sampler");
     if (sp->top_k < 0) BG_FAIL(false, "sampler: top_k must be 0 (the whole vocabulary) or in [1, n_vocab] (got %d)", sp->top_k);
     if (V >= 0 && sp->top_k > V) BG_FAIL(false, "sampler: top_k must be 0 (the whole vocabulary) or in [1, n_vocab = %d] (got %d)", V, sp->top_k);
-    if (!std::isfinite(sp->temp) || !(sp->temp > 0.0)) BG_FAIL(false, "sampler: temp must be finite and > 0");
-    if (!std::isfinite(sp->top_p)) BG_FAIL(false, "sampler: top_p must be finite (>= 1: no cut)");
+    if (!check_temp_top_p(sp->temp, sp->top_p, "sampler: ")) return false;
     if (!std::isfinite(sp->min_p) || !(sp->min_p >= 0.0 && sp->min_p < 1.0)) BG_FAIL(false, "sampler: min_p must be finite and in [0, 1) (0: off)");
     return true;
 }
@@ -3839,10 +3877,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_prompts x n_samples (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
     if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
     const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
-    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > V) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
-    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
-    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
-    if (eos_id < -1 || eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
+    if (!check_sample_values(top_k, top_p, temp, eos_id, V)) return -1;
     {   // the wide chain serves the plain call; each variant it does not serve is refused by its name
         const char *variant = wide ? "whole-vocabulary sampling" : trie ? "trie-constrained sampling" : prefix ? "sampled generation behind a shared prefix"
                               : lp ? "sampled generation with log-probabilities" : rules_active(rules, eos_id) ? "sampled generation under rules" : nullptr;
@@ -3857,9 +3892,9 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     cc.prompts = prompts; cc.prompt_lens = prompt_lens;
     cc.n_prompts = n_prompts; cc.per_prompt = n_samples; cc.n_batch = n_batch;
     cc.graphs = &ctx->graphs_sample; cc.key_a = n_seqs;
-    cc.gset_extra = wide ? 72 : trie ? 24 : ru ? 12 : 0;
+    cc.form.sel = wide ? StepForm::Wide : trie ? StepForm::Trie : ru ? StepForm::Rules : StepForm::Plain;
     cc.prefix = prefix; cc.n_prefix = n_prefix;     // (prefix != null, biogpt_hip_generate_sample_prefix: the prompts are suffixes and may be empty; no rules, no trie)
-    cc.with_lp = lp != nullptr;                     // (biogpt_hip_generate_sample_lp: sample_lp_rows_kernel is the selection; no rules, no trie)
+    cc.form.lp = lp != nullptr;                     // (biogpt_hip_generate_sample_lp: sample_lp_rows_kernel is the selection; no rules, no trie)
     cc.prepare = [&]() -> bool {
         if (lp && !genlp_prepare(ctx, &lb)) return false;
         if (n_seqs > ctx->sample_cap) {
@@ -4150,7 +4185,7 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     cc.prompts = prompts; cc.prompt_lens = prompt_lens;
     cc.n_prompts = G; cc.per_prompt = B; cc.n_batch = n_batch;
     cc.graphs = &ctx->graphs_beam; cc.key_a = G; cc.key_b = B;
-    cc.gset_extra = trie ? 24 : ru ? 12 : 0;
+    cc.form.sel = trie ? StepForm::Trie : ru ? StepForm::Rules : StepForm::Plain;
     cc.prepare = [&]() -> bool {
         if (!ctx->bbatch_buf) {
             size_t bytes;
@@ -4695,8 +4730,9 @@ struct QueueRequests {
 struct QueueCall {
     int max_units = 0, per_unit = 1;                // units of the schedule, at most; columns of a unit
     const char *unit = "column", *step_name = "queue step";      // in messages
-    ColumnGraphs *graphs = nullptr;                 // the mode's captured steps, valid for (units, key_b); a step of t_max keys is exec[gset + its bucket]
-    int key_b = 0, gset = 0;
+    ColumnGraphs *graphs = nullptr;                 // the mode's captured steps, valid for (units, key_b)
+    int key_b = 0;
+    StepForm form;                                  // the mode's selection, log-probabilities or not, shared rows or not (a queue's steps are never column-per-XCD launches)
     // what the driver writes as it goes (each may be null): the step count at which a request was admitted and its unit, the timed span, the schedule's counts
     int32_t *out_admit_step = nullptr, *out_unit = nullptr;
     double *seconds_out = nullptr;
@@ -4754,7 +4790,7 @@ static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc)
     column_graphs_for(*qc.graphs, U, qc.key_b);
     // (ColumnKeys of a call whose first replayed step sees min_len keys and whose last one max_keys: every bucket a step here can be bounded by)
     bool use_graph;
-    if (!capture_column_steps(ctx, *qc.graphs, qc.gset, ColumnKeys{min_len - 1, 1, P}, max_keys - min_len + 2, qc.step, &use_graph)) return -2;
+    if (!capture_column_steps(ctx, *qc.graphs, qc.form, ColumnKeys{min_len - 1, 1, P}, max_keys - min_len + 2, qc.step, &use_graph)) return -2;
 
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> flat, lens, slots;
@@ -4795,7 +4831,7 @@ static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc)
                 if (q.req[(size_t)unit] >= 0) t_max = std::max(t_max, q.position(unit, rq.whole_len(q.req[(size_t)unit])) + 1);
             t_max = std::min(t_max, P);
             if (use_graph) {
-                hipGraphExec_t ge = qc.graphs->exec[qc.gset + graph_bucket(t_max)];
+                hipGraphExec_t ge = qc.graphs->exec[ColumnGraphs::slot(qc.form, graph_bucket(t_max))];
                 if (!ge) BG_FAIL(-2, "internal: no captured %s for %d keys", qc.step_name, t_max);
                 HIP_TRY(-2, hipGraphLaunch(ge, ctx->stream));
             } else if (!qc.step(t_max)) {
@@ -4870,107 +4906,117 @@ static bool queue_copy_out(biogpt_hip_ctx *ctx, int col, int r, int len, int n_p
     return true;
 }
 
-// prefix != null (biogpt_hip_generate_queue_prefix): request r is prefix ++ prompt r, the prompts are suffixes and may be empty; the first n_shared prefix
+// ---- the column queue: what its two modes share ---------------------------------------------------------------------------------------------------------
+// The arguments both entry points have.  prefix != null: request r is prefix ++ prompt r, the prompts are suffixes and may be empty; the first n_shared prefix
 // rows are evaluated once, into the slot behind the columns', and read there by the refill passes and the steps (n_shared == 0: the call on the
-// concatenations, launch for launch).  lp != null: queue_rows_lp_kernel is the selection, and a finished column's rows of the log-probability block go to its
-// request's rows of lp's arrays, in stream order before the column is reused.  Each of the four forms has its own captured steps.
-static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,
-                               int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch, int32_t top_k, double top_p, double temp,
-                               const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, int32_t *out_admit_step, int32_t *out_column,
-                               double *seconds_out, biogpt_hip_queue_stats *stats, const int32_t *prefix = nullptr, int32_t n_prefix = 0,
-                               const biogpt_hip_gen_logprobs *lp = nullptr) {
+// concatenations, launch for launch).  lp != null: the selection also writes log-probabilities, and a finished column's rows of the log-probability block go to
+// its request's rows of lp's arrays, in stream order before the column is reused.
+struct ColumnQueueArgs {
+    const int32_t *prefix; int32_t n_prefix;
+    const int32_t *prompts, *prompt_lens, *n_predicts;
+    int32_t n_requests, n_predict, max_columns, group, n_batch;
+    const uint32_t *seeds;
+    int32_t *out_ids, *out_lens, *out_admit_step, *out_column;
+    double *seconds_out; biogpt_hip_queue_stats *stats; const biogpt_hip_gen_logprobs *lp;
+};
+// What differs between the modes: the closed queue (one sampler for all requests) and the queue whose requests carry their own parameters
+struct ColumnQueueMode {
+    ColumnGraphs biogpt_hip_ctx::*graphs = nullptr;
+    const char *what = nullptr;              // the mode by name, at the gate of the fast chain
+    bool wide_ok = false;                    // the wide chain serves it
+    const void *own_arg = nullptr;           // (or none, with its name) a pointer argument of the mode's own, named in a message between prompt_lens and seeds
+    const char *own_arg_name = nullptr;
+    int32_t *out_finish = nullptr;           // (or null) [n_requests]: -1 for a request that never ran, otherwise what `collected` writes
+    std::function<bool(int, int)> check;     // check(V, P): the mode's parameters without the model (V < 0), then with its sizes
+    std::function<bool(QueueCall &)> prepare;      // the mode's block on the device and its pinned twin: the QueueCall's admit list, with the size of an entry, and
+                                                   // header, and `hdr` below; the call's parameters go up and nobody runs yet
+    std::function<void()> select;            // the selection launch behind the forward pass
+    std::function<void(int, int, const bgk::QueueAdmit &, const int32_t *)> admit;      // admit(i, r, a, own): entry i of the pinned admit list <- the record a and
+                                                                                        // what the mode adds for request r, whose own tokens are `own`
+    std::function<bool(int)> enqueue_admit;  // enqueue_admit(n): the admit kernel over n entries
+    std::function<void(int, int)> collected; // (or none) collected(col, r): what the mode reads of finished column col beyond its length
+    // what generate_column_queue has settled by the time one of these runs: the columns, the model's sizes, the shared rows, with lp the block the selection writes
+    int C = 0, P = 0, V = 0, n_shared = 0;
+    GenLpBufs lb{};
+    const bgk::QueueHdr *hdr = nullptr;      // the pinned header, whose fin and len the driver reads
+};
+
+// Each of the four forms of a mode -- plain, shared rows, log-probabilities, both -- has its own captured steps (never column-per-XCD launches).
+static int generate_column_queue(biogpt_hip_ctx *ctx, const ColumnQueueArgs &a, ColumnQueueMode &m) {
     clear_error();
+    const biogpt_hip_gen_logprobs *const lp = a.lp;
+    const int32_t *const prefix = a.prefix;
+    const int32_t n_prefix = a.n_prefix, n_requests = a.n_requests, n_predict = a.n_predict, max_columns = a.max_columns;
     if (lp && !check_gen_logprobs(lp, -1)) return -1;
     if (!prefix && n_prefix != 0) BG_FAIL(-1, "n_prefix must be 0 without a prefix (got %d)", n_prefix);
     if (prefix && n_prefix < 1) BG_FAIL(-1, "n_prefix must be >= 1 (got %d)", n_prefix);
-    if (!prompts) BG_FAIL(-1, prefix ? "null argument: suffixes" : "null argument: prompts");
-    if (!prompt_lens) BG_FAIL(-1, prefix ? "null argument: suffix_lens" : "null argument: prompt_lens");
-    if (!seeds) BG_FAIL(-1, "null argument: seeds");
-    if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
-    if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
-    QueueRequests rq{prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch};
+    if (!a.prompts) BG_FAIL(-1, prefix ? "null argument: suffixes" : "null argument: prompts");
+    if (!a.prompt_lens) BG_FAIL(-1, prefix ? "null argument: suffix_lens" : "null argument: prompt_lens");
+    if (m.own_arg_name && !m.own_arg) BG_FAIL(-1, "null argument: %s", m.own_arg_name);
+    if (!a.seeds) BG_FAIL(-1, "null argument: seeds");
+    if (!a.out_ids) BG_FAIL(-1, "null argument: out_ids");
+    if (!a.out_lens) BG_FAIL(-1, "null argument: out_lens");
+    QueueRequests rq{a.prompts, a.prompt_lens, n_requests, a.n_predicts, n_predict, max_columns, a.group, a.n_batch};
     rq.prefix = prefix; rq.pos0 = n_prefix;
     if (!rq.check_count()) return -1;
     if (prefix && (max_columns < 1 || max_columns > bgk::QUEUE_COLS - 1))
         BG_FAIL(-1, "max_columns must be in [1, %d] behind a prefix (got %d)", bgk::QUEUE_COLS - 1, max_columns);   // one slot holds the prefix
     if (max_columns < 1 || max_columns > bgk::QUEUE_COLS) BG_FAIL(-1, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
     if (!rq.check_sizes()) return -1;
-    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
-    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
-    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
-    if (eos_id < -1) BG_FAIL(-1, "eos_id %d out of range: must be a token id, or -1 for none", eos_id);
+    if (!m.check(-1, -1)) return -1;
     if (!rq.check_prompts(ctx)) return -1;
-    const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
-    if (top_k > V) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
-    if (eos_id >= V) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, V);
+    const int P = m.P = ctx->hp.n_positions, V = m.V = ctx->hp.n_vocab;
+    if (!m.check(V, P)) return -1;
     if (lp && lp->n_top > V) BG_FAIL(-1, "logprobs.n_top (%d) exceeds n_vocab (%d)", lp->n_top, V);
-    if (!rq.check_prompts_model(ctx, prefix ? "generation over a queue behind a shared prefix" : lp ? "generation over a queue with log-probabilities" : "generation over a queue", !prefix && !lp)) return -1;
+    if (!rq.check_prompts_model(ctx, m.what, m.wide_ok)) return -1;
     const size_t n_out = (size_t)n_requests * (size_t)n_predict, K = lp ? (size_t)lp->n_top : 0;
-    std::fill(out_ids, out_ids + n_out, -1);
-    std::fill(out_lens, out_lens + n_requests, 0);
+    std::fill(a.out_ids, a.out_ids + n_out, -1);
+    std::fill(a.out_lens, a.out_lens + n_requests, 0);
+    if (m.out_finish) std::fill(m.out_finish, m.out_finish + n_requests, -1);
     if (lp) {      // entries at or past a request's length, and those of a request that never takes a column, as genlp_read leaves them
         std::fill(lp->lp, lp->lp + n_out, 0.0f);
         if (K > 0) { std::fill(lp->top_ids, lp->top_ids + n_out * K, -1); std::fill(lp->top_lp, lp->top_lp + n_out * K, 0.0f); }
     }
 
-    QueueBufs qb{};
-    QueueHost *qh = nullptr;
-    GenLpBufs lb{};
     // a column's entries lie lp_stride apart in the block: no request generates n_positions tokens, so the block's rows hold any n_predict
-    const int n_shared = rq.n_shared, lp_stride = std::min(n_predict, P);
-    int C = 0;
+    const int n_shared = m.n_shared = rq.n_shared, lp_stride = std::min(n_predict, P);
     biogpt_hip_queue_stats ran{};
     QueueCall qc;
     qc.max_units = max_columns;
-    qc.graphs = &ctx->graphs_queue; qc.gset = (n_shared > 0 ? 6 : 0) + (lp ? 12 : 0);      // plain, shared, lp, shared + lp: a form never replays another's step
-    qc.out_admit_step = out_admit_step; qc.out_unit = out_column; qc.seconds_out = seconds_out; qc.stats = &ran;
+    qc.graphs = &(ctx->*m.graphs); qc.form.lp = lp != nullptr; qc.form.shared = n_shared > 0;
+    qc.out_admit_step = a.out_admit_step; qc.out_unit = a.out_column; qc.seconds_out = a.seconds_out; qc.stats = &ran;
     qc.prepare = [&](int units) -> bool {
-        C = units;
-        if (lp && (!genlp_prepare(ctx, &lb) || !genlp_upload(lb, lp->n_top, lp_stride))) return false;
-        if (!ctx->queue_buf) HIP_TRY(false, hipMalloc(&ctx->queue_buf, queue_bufs_at(nullptr).bytes));
-        if (!ctx->queue_host) HIP_TRY(false, hipHostMalloc(&ctx->queue_host, sizeof(QueueHost)));
-        qb = queue_bufs_at(ctx->queue_buf);
-        qh = reinterpret_cast<QueueHost *>(ctx->queue_host);
-        qc.admit_dev = qb.admit; qc.admit_host = qh->admit; qc.admit_bytes = sizeof(bgk::QueueAdmit);
-        qc.hdr_dev = qb.hdr; qc.hdr_host = &qh->hdr; qc.hdr_bytes = sizeof(bgk::QueueHdr); qc.fin = qh->hdr.fin;
-        // the call's parameters; nobody runs yet
-        const bgk::SampleCtl hc = sample_ctl_of(top_k, eos_id, 0, top_p, temp);
-        HIP_TRY(false, hipMemcpy(qb.ctl, &hc, sizeof(hc), hipMemcpyHostToDevice));
-        HIP_TRY(false, hipMemset(qb.hdr, 0, sizeof(bgk::QueueHdr)));
+        m.C = units;
+        if (lp && (!genlp_prepare(ctx, &m.lb) || !genlp_upload(m.lb, lp->n_top, lp_stride))) return false;
+        if (!m.prepare(qc)) return false;
+        qc.fin = m.hdr->fin;
         return true;
     };
     qc.step = [&](int t_max) -> bool {      // (behind shared rows always in place: a queue never runs the column-per-XCD launches)
-        if (!enqueue_forward(ctx, n_shared > 0 ? ForwardPass::decode_step_shared(C, t_max, n_shared) : ForwardPass::decode_step(C, t_max))) return false;
-        if (lp)
-            hipLaunchKernelGGL(bgk::queue_rows_lp_kernel, dim3(C), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, qb.ctl, qb.seq, ctx->seq, ctx->seq_gen,
-                               P, qb.limit, qb.hdr, lb.out());
-        else
-            hipLaunchKernelGGL(bgk::queue_rows_kernel, dim3(C), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, V, V, qb.ctl, qb.seq, ctx->seq, ctx->seq_gen, P,
-                               qb.limit, qb.hdr);
+        if (!enqueue_forward(ctx, n_shared > 0 ? ForwardPass::decode_step_shared(m.C, t_max, n_shared) : ForwardPass::decode_step(m.C, t_max))) return false;
+        m.select();
         HIP_TRY(false, hipGetLastError());
         return true;
     };
     qc.admit = [&](int col, int r, int i) {      // the state of the whole sequence at its last token: the suffix's, or the prefix's behind an empty one
-        const int len = prompt_lens[r];
-        bgk::QueueAdmit &a = qh->admit[i];
-        a = bgk::QueueAdmit{};
-        a.col = col; a.last_token = len > 0 ? prompts[rq.off[(size_t)r] + (size_t)(len - 1)] : prefix[n_prefix - 1]; a.len = rq.whole_len(r);
-        a.limit = rq.cap[(size_t)r]; a.seed = seeds[r];
-        a.n_shared = n_shared; a.shared_slot = n_shared > 0 ? C : 0;
+        const int len = a.prompt_lens[r];
+        const int32_t *const own = a.prompts + rq.off[(size_t)r];
+        bgk::QueueAdmit rec{};
+        rec.col = col; rec.last_token = len > 0 ? own[len - 1] : prefix[n_prefix - 1]; rec.len = rq.whole_len(r);
+        rec.limit = rq.cap[(size_t)r]; rec.seed = a.seeds[r];
+        rec.n_shared = n_shared; rec.shared_slot = n_shared > 0 ? m.C : 0;
+        m.admit(i, r, rec, own);
     };
-    qc.enqueue_admit = [&](int n_admit) -> bool {
-        hipLaunchKernelGGL(bgk::queue_admit_kernel, dim3(n_admit), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, qb.seq, ctx->seq, qb.limit, qb.hdr);
-        HIP_TRY(false, hipGetLastError());
-        return true;
-    };
+    qc.enqueue_admit = m.enqueue_admit;
     qc.collect = [&](int col, int r) -> int {      // the ids straight from the column's seq_gen row to the caller's row
-        const int len = std::max(0, std::min(qh->hdr.len[col], rq.cap[(size_t)r]));
-        if (!queue_copy_out(ctx, col, r, len, n_predict, out_ids, lp, lb, lp_stride)) return -1;
-        out_lens[r] = len;
+        const int len = std::max(0, std::min(m.hdr->len[col], rq.cap[(size_t)r]));
+        if (!queue_copy_out(ctx, col, r, len, n_predict, a.out_ids, lp, m.lb, lp_stride)) return -1;
+        a.out_lens[r] = len;
+        if (m.collected) m.collected(col, r);
         return len;
     };
     const int rc = run_queue_call(ctx, rq, qc);
-    if (stats) *stats = ran;
+    if (a.stats) *a.stats = ran;
     // (a call that failed, or in which no request had room for a token, leaves the stats of the last call that generated)
     if (rc == 0 && prefix && ran.columns > 0) {
         ctx->prefix_stats[0] = n_shared; ctx->prefix_stats[1] = ran.prompt_columns; ctx->prefix_stats[2] = 0; ctx->prefix_stats[3] = ran.columns;
@@ -4978,14 +5024,52 @@ static int generate_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
     return rc;
 }
 
+// The closed queue: top_k, top_p, temp and eos_id are the call's; queue_rows_kernel is the selection, with lp queue_rows_lp_kernel.  The plain form alone is
+// open to the wide chain.
+static int generate_queue_once(biogpt_hip_ctx *ctx, const ColumnQueueArgs &a, int32_t top_k, double top_p, double temp, int32_t eos_id) {
+    QueueBufs qb{};
+    QueueHost *qh = nullptr;
+    ColumnQueueMode m;
+    m.graphs = &biogpt_hip_ctx::graphs_queue;
+    m.what = a.prefix ? "generation over a queue behind a shared prefix" : a.lp ? "generation over a queue with log-probabilities" : "generation over a queue";
+    m.wide_ok = !a.prefix && !a.lp;
+    m.check = [&](int V, int) -> bool { return check_sample_values(top_k, top_p, temp, eos_id, V); };
+    m.prepare = [&](QueueCall &qc) -> bool {
+        if (!ctx->queue_buf) HIP_TRY(false, hipMalloc(&ctx->queue_buf, queue_bufs_at(nullptr).bytes));
+        if (!ctx->queue_host) HIP_TRY(false, hipHostMalloc(&ctx->queue_host, sizeof(QueueHost)));
+        qb = queue_bufs_at(ctx->queue_buf);
+        qh = reinterpret_cast<QueueHost *>(ctx->queue_host);
+        qc.admit_dev = qb.admit; qc.admit_host = qh->admit; qc.admit_bytes = sizeof(bgk::QueueAdmit);
+        qc.hdr_dev = qb.hdr; qc.hdr_host = &qh->hdr; qc.hdr_bytes = sizeof(bgk::QueueHdr); m.hdr = &qh->hdr;
+        // the call's parameters; nobody runs yet
+        const bgk::SampleCtl hc = sample_ctl_of(top_k, eos_id, 0, top_p, temp);
+        HIP_TRY(false, hipMemcpy(qb.ctl, &hc, sizeof(hc), hipMemcpyHostToDevice));
+        HIP_TRY(false, hipMemset(qb.hdr, 0, sizeof(bgk::QueueHdr)));
+        return true;
+    };
+    m.select = [&] {
+        if (a.lp)
+            hipLaunchKernelGGL(bgk::queue_rows_lp_kernel, dim3(m.C), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, m.V, m.V, qb.ctl, qb.seq, ctx->seq, ctx->seq_gen,
+                               m.P, qb.limit, qb.hdr, m.lb.out());
+        else
+            hipLaunchKernelGGL(bgk::queue_rows_kernel, dim3(m.C), dim3(bgk::SAMPLE_THREADS), 0, ctx->stream, ctx->logits_all, m.V, m.V, qb.ctl, qb.seq, ctx->seq, ctx->seq_gen, m.P,
+                               qb.limit, qb.hdr);
+    };
+    m.admit = [&](int i, int, const bgk::QueueAdmit &rec, const int32_t *) { qh->admit[i] = rec; };
+    m.enqueue_admit = [&](int n_admit) -> bool {
+        hipLaunchKernelGGL(bgk::queue_admit_kernel, dim3(n_admit), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, qb.seq, ctx->seq, qb.limit, qb.hdr);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    return generate_column_queue(ctx, a, m);
+}
+
 int biogpt_hip_generate_queue(biogpt_hip_ctx *ctx, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests, const int32_t *n_predicts,
                               int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch, int32_t top_k, double top_p, double temp,
                               const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, int32_t *out_admit_step, int32_t *out_column,
                               double *seconds_out, biogpt_hip_queue_stats *stats) {
-    return with_xpipe_retry(ctx, 0, [&] {
-        return generate_queue_once(ctx, prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch, top_k, top_p, temp, seeds, eos_id,
-                                   out_ids, out_lens, out_admit_step, out_column, seconds_out, stats);
-    });
+    return biogpt_hip_generate_queue_prefix(ctx, nullptr, 0, prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch, top_k, top_p, temp, seeds,
+                                            eos_id, out_ids, out_lens, out_admit_step, out_column, seconds_out, stats, nullptr);
 }
 
 // biogpt_hip_generate_queue of the requests prefix ++ suffix r behind the shared prefix rows (prefix == null: of the suffixes themselves), with the
@@ -4994,18 +5078,17 @@ int biogpt_hip_generate_queue_prefix(biogpt_hip_ctx *ctx, const int32_t *prefix,
                                      const int32_t *n_predicts, int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch, int32_t top_k, double top_p,
                                      double temp, const uint32_t *seeds, int32_t eos_id, int32_t *out_ids, int32_t *out_lens, int32_t *out_admit_step,
                                      int32_t *out_column, double *seconds_out, biogpt_hip_queue_stats *stats, const biogpt_hip_gen_logprobs *logprobs) {
-    return with_xpipe_retry(ctx, 0, [&] {
-        return generate_queue_once(ctx, suffixes, suffix_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch, top_k, top_p, temp, seeds, eos_id,
-                                   out_ids, out_lens, out_admit_step, out_column, seconds_out, stats, prefix, n_prefix, logprobs);
-    });
+    const ColumnQueueArgs a{prefix, n_prefix, suffixes, suffix_lens, n_predicts, n_requests, n_predict, max_columns, group, n_batch, seeds,
+                            out_ids, out_lens, out_admit_step, out_column, seconds_out, stats, logprobs};
+    return with_xpipe_retry(ctx, 0, [&] { return generate_queue_once(ctx, a, top_k, top_p, temp, eos_id); });
 }
 
 // ---- generation over a queue whose requests carry their own parameters (biogpt_hip_generate_queue_requests) ---------------------------------------------
-// The fifth form of the column queue: the driver, the schedule and the admit state are those of generate_queue_once; the step is the forward pass and ONE
-// launch of queue_req_rows_kernel (the closed rules call has two), which reads a column's sampler, EOS id, rules and stop sequences from the column's record.
+// The second mode of the column queue (generate_column_queue): the driver, the schedule and the admit state are the closed queue's; the step is the forward
+// pass and ONE launch of queue_req_rows_kernel (the closed rules call has two), which reads a column's sampler, EOS id, rules and stop sequences from the column's record.
 // An entry of the admit list is the admit record, the request's record and the request's own prompt tokens (the history its rules read), `stride` bytes apart:
 // one upload per refill, as before, and a step causes no host traffic.  Behind a prefix the prefix's tokens go up once, in prepare.  The header carries the
-// reason a column finished behind what the driver reads.  Its captured steps are graphs_queue_req, with the four sets of generate_queue_once.
+// reason a column finished behind what the driver reads.  Its captured steps are graphs_queue_req, with the four forms of the closed queue.
 struct QueueReqBufs {
     bgk::SampleSeq *seq;        // [QUEUE_COLS]
     int32_t *limit;             // [QUEUE_COLS]
@@ -5031,11 +5114,7 @@ static QueueReqBufs queue_req_bufs_at(uint8_t *base, int P) {
 
 // What can be judged of request r's parameters without the model (V < 0), and with its sizes
 static bool check_request_params(const biogpt_hip_request_params &p, int r, int V, int P) {
-    if (p.top_k < 1 || p.top_k > bgk::SAMPLE_MAX_K || (V >= 0 && p.top_k > V)) BG_FAIL(false, "params[%d].top_k must be in [1, %d] and at most n_vocab", r, bgk::SAMPLE_MAX_K);
-    if (!std::isfinite(p.temp) || !(p.temp > 0.0)) BG_FAIL(false, "params[%d].temp must be finite and > 0", r);
-    if (!std::isfinite(p.top_p)) BG_FAIL(false, "params[%d].top_p must be finite (>= 1: no cut)", r);
-    if (p.eos_id < -1) BG_FAIL(false, "params[%d].eos_id %d out of range: must be a token id, or -1 for none", r, p.eos_id);
-    if (V >= 0 && p.eos_id >= V) BG_FAIL(false, "params[%d].eos_id %d out of range: must be in [0, %d), or -1 for none", r, p.eos_id, V);
+    if (!check_sample_values(p.top_k, p.top_p, p.temp, p.eos_id, V, "params[%d].", r)) return false;
     if (!check_rules(&p.rules, V >= 0 ? V : bgk::RULES_MAX_VOCAB, V >= 0 ? P : -1)) {
         const std::string why = last_error();
         BG_FAIL(false, "params[%d].rules: %s", r, why.c_str());
@@ -5081,112 +5160,59 @@ static void enqueue_queue_req_rows(hipStream_t stream, int C, float *logits, int
                            seq_gen, gen_stride, qb.limit, qb.hdr, qb.prefix, qb.hist, hist_stride, bgk::SamplePlain());
 }
 
-static int generate_queue_requests_once(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests,
-                                        const int32_t *n_predicts, int32_t n_predict, int32_t max_columns, int32_t group, int32_t n_batch,
-                                        const biogpt_hip_request_params *params, const uint32_t *seeds, int32_t *out_ids, int32_t *out_lens, int32_t *out_finish,
-                                        int32_t *out_admit_step, int32_t *out_column, double *seconds_out, biogpt_hip_queue_stats *stats,
-                                        const biogpt_hip_gen_logprobs *lp) {
-    clear_error();
-    if (lp && !check_gen_logprobs(lp, -1)) return -1;
-    if (!prefix && n_prefix != 0) BG_FAIL(-1, "n_prefix must be 0 without a prefix (got %d)", n_prefix);
-    if (prefix && n_prefix < 1) BG_FAIL(-1, "n_prefix must be >= 1 (got %d)", n_prefix);
-    if (!prompts) BG_FAIL(-1, prefix ? "null argument: suffixes" : "null argument: prompts");
-    if (!prompt_lens) BG_FAIL(-1, prefix ? "null argument: suffix_lens" : "null argument: prompt_lens");
-    if (!params) BG_FAIL(-1, "null argument: params");
-    if (!seeds) BG_FAIL(-1, "null argument: seeds");
-    if (!out_ids) BG_FAIL(-1, "null argument: out_ids");
-    if (!out_lens) BG_FAIL(-1, "null argument: out_lens");
-    QueueRequests rq{prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch};
-    rq.prefix = prefix; rq.pos0 = n_prefix;
-    if (!rq.check_count()) return -1;
-    if (prefix && (max_columns < 1 || max_columns > bgk::QUEUE_COLS - 1))
-        BG_FAIL(-1, "max_columns must be in [1, %d] behind a prefix (got %d)", bgk::QUEUE_COLS - 1, max_columns);   // one slot holds the prefix
-    if (max_columns < 1 || max_columns > bgk::QUEUE_COLS) BG_FAIL(-1, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
-    if (!rq.check_sizes()) return -1;
+// every request's parameters, without the model (V < 0) and with its sizes; with_lp: no request may then have a rule switched on
+static bool check_requests(const biogpt_hip_request_params *params, int n_requests, bool with_lp, int V, int P) {
     for (int r = 0; r < n_requests; r++) {
-        if (!check_request_params(params[r], r, -1, -1)) return -1;
-        if (lp && rules_active(&params[r].rules, params[r].eos_id))
-            BG_FAIL(-1, "logprobs with generation rules (params[%d].rules has a rule switched on): no closed call returns log-probabilities under rules", r);
+        if (!check_request_params(params[r], r, V, P)) return false;
+        if (V < 0 && with_lp && rules_active(&params[r].rules, params[r].eos_id))
+            BG_FAIL(false, "logprobs with generation rules (params[%d].rules has a rule switched on): no closed call returns log-probabilities under rules", r);
     }
-    if (!rq.check_prompts(ctx)) return -1;
-    const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
-    for (int r = 0; r < n_requests; r++)
-        if (!check_request_params(params[r], r, V, P)) return -1;
-    if (lp && lp->n_top > V) BG_FAIL(-1, "logprobs.n_top (%d) exceeds n_vocab (%d)", lp->n_top, V);
-    if (!rq.check_prompts_model(ctx, "generation over a queue with request parameters")) return -1;
-    const size_t n_out = (size_t)n_requests * (size_t)n_predict, K = lp ? (size_t)lp->n_top : 0;
-    std::fill(out_ids, out_ids + n_out, -1);
-    std::fill(out_lens, out_lens + n_requests, 0);
-    if (out_finish) std::fill(out_finish, out_finish + n_requests, -1);
-    if (lp) {      // entries at or past a request's length, and those of a request that never takes a column, as genlp_read leaves them
-        std::fill(lp->lp, lp->lp + n_out, 0.0f);
-        if (K > 0) { std::fill(lp->top_ids, lp->top_ids + n_out * K, -1); std::fill(lp->top_lp, lp->top_lp + n_out * K, 0.0f); }
-    }
+    return true;
+}
 
+static int generate_queue_requests_once(biogpt_hip_ctx *ctx, const ColumnQueueArgs &a, const biogpt_hip_request_params *params, int32_t *out_finish) {
     QueueReqBufs qb{};
     bgk::QueueReqHdr *hh = nullptr;      // pinned: the header, then the admit list
     uint8_t *admit_host = nullptr;
-    GenLpBufs lb{};
-    const int n_shared = rq.n_shared, lp_stride = std::min(n_predict, P);
-    int most_own = 0;
-    for (int r = 0; r < n_requests; r++) most_own = std::max(most_own, prompt_lens[r]);
-    const size_t stride = queue_req_stride(most_own);      // (most_own <= n_positions: check_prompts_model)
-    int C = 0;
-    biogpt_hip_queue_stats ran{};
-    QueueCall qc;
-    qc.max_units = max_columns;
-    qc.graphs = &ctx->graphs_queue_req; qc.gset = (n_shared > 0 ? 6 : 0) + (lp ? 12 : 0);      // plain, shared, lp, shared + lp: a form never replays another's step
-    qc.out_admit_step = out_admit_step; qc.out_unit = out_column; qc.seconds_out = seconds_out; qc.stats = &ran;
-    qc.prepare = [&](int units) -> bool {
-        C = units;
-        if (lp && (!genlp_prepare(ctx, &lb) || !genlp_upload(lb, lp->n_top, lp_stride))) return false;
+    size_t stride = 0;
+    ColumnQueueMode m;
+    m.graphs = &biogpt_hip_ctx::graphs_queue_req;
+    m.what = "generation over a queue with request parameters";
+    m.own_arg = params; m.own_arg_name = "params";
+    m.out_finish = out_finish;
+    m.check = [&](int V, int P) -> bool { return check_requests(params, a.n_requests, a.lp != nullptr, V, P); };
+    m.prepare = [&](QueueCall &qc) -> bool {
+        const int P = m.P;
+        int most_own = 0;
+        for (int r = 0; r < a.n_requests; r++) most_own = std::max(most_own, a.prompt_lens[r]);
+        stride = queue_req_stride(most_own);      // (most_own <= n_positions: check_prompts_model)
         if (!ctx->queue_req_buf) HIP_TRY(false, hipMalloc(&ctx->queue_req_buf, queue_req_bufs_at(nullptr, P).bytes));
         if (!ctx->queue_req_host) HIP_TRY(false, hipHostMalloc(&ctx->queue_req_host, sizeof(bgk::QueueReqHdr) + (size_t)bgk::QUEUE_COLS * queue_req_stride(P)));
         qb = queue_req_bufs_at(ctx->queue_req_buf, P);
         hh = reinterpret_cast<bgk::QueueReqHdr *>(ctx->queue_req_host);
         admit_host = ctx->queue_req_host + sizeof(bgk::QueueReqHdr);
         qc.admit_dev = qb.admit; qc.admit_host = admit_host; qc.admit_bytes = stride;
-        qc.hdr_dev = qb.hdr; qc.hdr_host = hh; qc.hdr_bytes = sizeof(bgk::QueueReqHdr); qc.fin = hh->q.fin;
+        qc.hdr_dev = qb.hdr; qc.hdr_host = hh; qc.hdr_bytes = sizeof(bgk::QueueReqHdr); m.hdr = &hh->q;
         // the prefix the rules read; nobody runs yet
-        if (prefix) HIP_TRY(false, hipMemcpy(qb.prefix, prefix, (size_t)n_prefix * 4, hipMemcpyHostToDevice));
+        if (a.prefix) HIP_TRY(false, hipMemcpy(qb.prefix, a.prefix, (size_t)a.n_prefix * 4, hipMemcpyHostToDevice));
         HIP_TRY(false, hipMemset(qb.hdr, 0, sizeof(bgk::QueueReqHdr)));
         return true;
     };
-    qc.step = [&](int t_max) -> bool {
-        if (!enqueue_forward(ctx, n_shared > 0 ? ForwardPass::decode_step_shared(C, t_max, n_shared) : ForwardPass::decode_step(C, t_max))) return false;
-        enqueue_queue_req_rows(ctx->stream, C, ctx->logits_all, V, qb, ctx->seq, ctx->seq_gen, P, P, lp ? &lb : nullptr);
-        HIP_TRY(false, hipGetLastError());
-        return true;
-    };
-    qc.admit = [&](int col, int r, int i) {
-        const int len = prompt_lens[r];
+    m.select = [&] { enqueue_queue_req_rows(ctx->stream, m.C, ctx->logits_all, m.V, qb, ctx->seq, ctx->seq_gen, m.P, m.P, a.lp ? &m.lb : nullptr); };
+    m.admit = [&](int i, int r, const bgk::QueueAdmit &rec, const int32_t *own) {
         bgk::QueueReqAdmit *e = reinterpret_cast<bgk::QueueReqAdmit *>(admit_host + (size_t)i * stride);
-        e->a = bgk::QueueAdmit{};
-        e->a.col = col; e->a.last_token = len > 0 ? prompts[rq.off[(size_t)r] + (size_t)(len - 1)] : prefix[n_prefix - 1]; e->a.len = rq.whole_len(r);
-        e->a.limit = rq.cap[(size_t)r]; e->a.seed = seeds[r];
-        e->a.n_shared = n_shared; e->a.shared_slot = n_shared > 0 ? C : 0;
-        e->rec = request_rec_of(params[r], n_prefix, len);
-        std::memcpy(e + 1, prompts + rq.off[(size_t)r], (size_t)len * 4);
+        e->a = rec;
+        e->rec = request_rec_of(params[r], a.n_prefix, a.prompt_lens[r]);
+        std::memcpy(e + 1, own, (size_t)a.prompt_lens[r] * 4);
     };
-    qc.enqueue_admit = [&](int n_admit) -> bool {
+    m.enqueue_admit = [&](int n_admit) -> bool {
         hipLaunchKernelGGL(bgk::queue_req_admit_kernel, dim3(n_admit), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream, qb.admit, (int)stride, qb.seq, ctx->seq, qb.limit, qb.hdr,
-                           qb.rec, qb.hist, P);
+                           qb.rec, qb.hist, m.P);
         HIP_TRY(false, hipGetLastError());
         return true;
     };
-    qc.collect = [&](int col, int r) -> int {
-        const int len = std::max(0, std::min(hh->q.len[col], rq.cap[(size_t)r]));
-        if (!queue_copy_out(ctx, col, r, len, n_predict, out_ids, lp, lb, lp_stride)) return -1;
-        out_lens[r] = len;
-        if (out_finish) out_finish[r] = hh->reason[col];
-        return len;
-    };
-    const int rc = run_queue_call(ctx, rq, qc);
-    if (stats) *stats = ran;
-    if (rc == 0 && prefix && ran.columns > 0) {
-        ctx->prefix_stats[0] = n_shared; ctx->prefix_stats[1] = ran.prompt_columns; ctx->prefix_stats[2] = 0; ctx->prefix_stats[3] = ran.columns;
-    }
-    return rc;
+    m.collected = [&](int col, int r) { if (out_finish) out_finish[r] = hh->reason[col]; };
+    return generate_column_queue(ctx, a, m);
 }
 
 int biogpt_hip_generate_queue_requests(biogpt_hip_ctx *ctx, const int32_t *prefix, int32_t n_prefix, const int32_t *prompts, const int32_t *prompt_lens, int32_t n_requests,
@@ -5194,10 +5220,9 @@ int biogpt_hip_generate_queue_requests(biogpt_hip_ctx *ctx, const int32_t *prefi
                                        const biogpt_hip_request_params *params, const uint32_t *seeds, int32_t *out_ids, int32_t *out_lens, int32_t *out_finish,
                                        int32_t *out_admit_step, int32_t *out_column, double *seconds_out, biogpt_hip_queue_stats *stats,
                                        const biogpt_hip_gen_logprobs *logprobs) {
-    return with_xpipe_retry(ctx, 0, [&] {
-        return generate_queue_requests_once(ctx, prefix, n_prefix, prompts, prompt_lens, n_requests, n_predicts, n_predict, max_columns, group, n_batch, params, seeds,
-                                            out_ids, out_lens, out_finish, out_admit_step, out_column, seconds_out, stats, logprobs);
-    });
+    const ColumnQueueArgs a{prefix, n_prefix, prompts, prompt_lens, n_predicts, n_requests, n_predict, max_columns, group, n_batch, seeds,
+                            out_ids, out_lens, out_admit_step, out_column, seconds_out, stats, logprobs};
+    return with_xpipe_retry(ctx, 0, [&] { return generate_queue_requests_once(ctx, a, params, out_finish); });
 }
 
 // ---- beam search over a queue: a unit is a group slot of B columns; finished searches hand their slot on (kernels_beam_queue.hip.h) ------------------
@@ -5279,7 +5304,7 @@ static int generate_beam_queue_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     QueueCall qc;
     qc.max_units = max_columns / B; qc.per_unit = B;
     qc.unit = "slot"; qc.step_name = "beam queue step";
-    qc.graphs = &ctx->graphs_bqueue; qc.key_b = B; qc.gset = trie ? 6 : 0;
+    qc.graphs = &ctx->graphs_bqueue; qc.key_b = B; qc.form.sel = trie ? StepForm::Trie : StepForm::Plain;
     qc.out_admit_step = out_admit_step; qc.out_unit = out_slot; qc.seconds_out = seconds_out; qc.stats = stats;
     qc.prepare = [&](int units) -> bool {
         S = units; C = S * B; call.n_slots = S;

@@ -710,8 +710,7 @@ int biogpt_hip_sample_candidates_host(const float *vals, const int32_t *ids, int
     clear_error();
     if (!vals || !ids || !mt_state625 || !id_out) BG_FAIL(-1, "null argument");
     if (k < 1 || k > (1 << 20)) BG_FAIL(-1, "k must be in [1, %d]", 1 << 20);
-    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
-    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
+    if (!check_temp_top_p(temp, top_p)) return -1;
     if (mt_state625[bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index %u out of range", mt_state625[bgk::MT_N]);
     bgk::SampleWork w;
     std::vector<double> p((size_t)k);
@@ -719,46 +718,8 @@ int biogpt_hip_sample_candidates_host(const float *vals, const int32_t *ids, int
     return 0;
 }
 
-// sample_rows_kernel over rows held in host memory (tests: ties, any row width and alignment, the selection's round form, a generator block running
-// out): row r draws from mt_states[r] (625 words, advanced in place; the words of a block regenerated on the device are those of the host's form)
-int biogpt_hip_sample_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, int32_t top_k, double top_p, double temp,
-                                  uint32_t *mt_states, int32_t *ids_out) {
-    clear_error();
-    if (!logits || !mt_states || !ids_out) BG_FAIL(-1, "null argument");
-    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
-    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > n_vocab) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
-    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
-    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
-    for (int r = 0; r < n_rows; r++)
-        if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
-    HIP_TRY(-2, hipSetDevice(device));
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sample_bufs_at(nullptr, (size_t)n_rows).bytes;
-    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = (size_t)n_rows * 4;
-    std::vector<uint8_t> h(sq_b, 0);
-    const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_rows);
-    *hb.ctl = sample_ctl_of(top_k, -1, n_rows, top_p, temp);
-    bgk::SampleSeq *const hq = hb.seq;
-    for (int r = 0; r < n_rows; r++) std::memcpy(hq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
-    ByteLayout l;      // [logits | ctl + states | column states | ids]
-    const size_t o_lg = l.part(lg_b), o_sq = l.part(sq_b), o_st = l.part(st_b), o_id = l.part(id_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    const SampleBufs sb = sample_bufs_at(d.p + o_sq, (size_t)n_rows);
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, logits, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(sb.ctl, h.data(), sq_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_st, 0, l.bytes() - o_st));
-    hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, sb.ctl, sb.seq,
-                       d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), 1);
-    HIP_TRY(-2, hipGetLastError());
-    HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(h.data(), sb.ctl, sq_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
-    for (int r = 0; r < n_rows; r++) std::memcpy(mt_states + (size_t)r * 625, hq[r].mt, 625 * 4);
-    return 0;
-}
-
-// sample_wide_rows_kernel (which 0) or sample_rows_kernel (which 1) over rows held in host memory, as biogpt_hip_sample_rows_device.  mt_out (or null): the
-// states after one launch; n_cand_out (or null): which 0 only.  reps > 0 (biogpt_hip_sample_wide_rows_bench): the launch is then repeated from the states it
+// sample_wide_rows_kernel (which 0) or sample_rows_kernel (which 1) over rows held in host memory: row r draws from mt_in[r] (625 words; the words of a block
+// regenerated on the device are those of the host's form).  mt_out (or null): the states after one launch; n_cand_out (or null): which 0 only.  reps > 0 (biogpt_hip_sample_wide_rows_bench): the launch is then repeated from the states it
 // began with, restored by a device copy in front of each, and seconds_out[i] is the time between two events around launch i alone
 static int sample_wide_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, const biogpt_hip_sampler *sampler, const uint32_t *mt_in,
                                    uint32_t *mt_out, int32_t *ids_out, int32_t *n_cand_out, int32_t which, int32_t reps, double *seconds_out) {
@@ -768,8 +729,7 @@ static int sample_wide_rows_device(int device, const float *logits, int32_t n_ro
     if (which != 0 && which != 1) BG_FAIL(-1, "which must be 0 (sample_wide_rows_kernel) or 1 (sample_rows_kernel)");
     if (which == 1 && !sampler_is_plain(*sampler)) BG_FAIL(-1, "sample_rows_kernel serves top_k in [1, %d] with min_p 0", bgk::SAMPLE_MAX_K);
     if (reps < 0 || reps > 10000 || (reps > 0 && !seconds_out)) BG_FAIL(-1, "reps must be in [0, 10000], with seconds_out");
-    for (int r = 0; r < n_rows; r++)
-        if (mt_in[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
+    if (!check_mt_states(mt_in, n_rows)) return -1;
     HIP_TRY(-2, hipSetDevice(device));
     const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sample_bufs_at(nullptr, (size_t)n_rows).bytes;
     const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = (size_t)n_rows * 4;
@@ -777,7 +737,7 @@ static int sample_wide_rows_device(int device, const float *logits, int32_t n_ro
     const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_rows);
     *hb.ctl = sample_ctl_of(which == 1 ? sampler->top_k : 1, -1, n_rows, which == 1 ? sampler->top_p : 1.0, which == 1 ? sampler->temp : 1.0);
     *hb.wide = sample_wide_of(*sampler);
-    for (int r = 0; r < n_rows; r++) std::memcpy(hb.seq[r].mt, mt_in + (size_t)r * 625, 625 * 4);
+    mt_states_in(hb.seq, mt_in, n_rows);
     ByteLayout l;      // [logits | ctl + states + sampler | column states | ids | candidate counts | ctl + states + sampler again, with reps]
     const size_t o_lg = l.part(lg_b), o_sq = l.part(sq_b), o_st = l.part(st_b), o_id = l.part(id_b), o_nc = l.part(id_b), o_keep = l.part(reps > 0 ? sq_b : 0);
     DeviceBytes d;
@@ -800,8 +760,7 @@ static int sample_wide_rows_device(int device, const float *logits, int32_t n_ro
     if (mt_out) {
         std::vector<uint8_t> back(sq_b);
         HIP_TRY(-2, hipMemcpy(back.data(), sb.ctl, sq_b, hipMemcpyDeviceToHost));
-        const SampleBufs bb = sample_bufs_at(back.data(), (size_t)n_rows);
-        for (int r = 0; r < n_rows; r++) std::memcpy(mt_out + (size_t)r * 625, bb.seq[r].mt, 625 * 4);
+        mt_states_out(mt_out, sample_bufs_at(back.data(), (size_t)n_rows).seq, n_rows);
     }
     if (ids_out) HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
     if (n_cand_out) HIP_TRY(-2, hipMemcpy(n_cand_out, d.p + o_nc, id_b, hipMemcpyDeviceToHost));
@@ -827,6 +786,18 @@ static int sample_wide_rows_device(int device, const float *logits, int32_t n_ro
         HIP_TRY(-2, err);
     }
     return 0;
+}
+// sample_rows_kernel over rows held in host memory (tests: ties, any row width and alignment, the selection's round form, a generator block running out):
+// mt_states is advanced in place
+int biogpt_hip_sample_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, int32_t top_k, double top_p, double temp,
+                                  uint32_t *mt_states, int32_t *ids_out) {
+    clear_error();
+    if (!logits || !mt_states || !ids_out) BG_FAIL(-1, "null argument");
+    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
+    if (!check_sample_values(top_k, top_p, temp, -1, n_vocab)) return -1;
+    biogpt_hip_sampler sp{};
+    sp.top_k = top_k; sp.top_p = top_p; sp.temp = temp;
+    return sample_wide_rows_device(device, logits, n_rows, n_vocab, &sp, mt_states, mt_states, ids_out, nullptr, 1, 0, nullptr);
 }
 int biogpt_hip_sample_wide_rows_device(int device, const float *logits, int32_t n_rows, int32_t n_vocab, const biogpt_hip_sampler *sampler, uint32_t *mt_states,
                                        int32_t *ids_out, int32_t *n_cand_out) {
@@ -857,11 +828,7 @@ int biogpt_hip_genlp_rows_device(int device, int32_t mode, const float *rows, in
     if (!check_gen_logprobs(&req, n_vocab)) return -1;
     if (mode == 1) {
         if (!mt_states) BG_FAIL(-1, "mt_states is NULL");
-        if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > n_vocab) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
-        if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
-        if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
-        for (int r = 0; r < n_rows; r++)
-            if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
+        if (!check_sample_values(top_k, top_p, temp, -1, n_vocab) || !check_mt_states(mt_states, n_rows)) return -1;
     }
     HIP_TRY(-2, hipSetDevice(device));
     const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sample_bufs_at(nullptr, (size_t)n_rows).bytes, lp_b = genlp_bufs_at(nullptr, (size_t)n_rows, (size_t)n_top).bytes;
@@ -869,7 +836,7 @@ int biogpt_hip_genlp_rows_device(int device, int32_t mode, const float *rows, in
     std::vector<uint8_t> h(sq_b, 0);
     const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_rows);
     *hb.ctl = sample_ctl_of(mode == 1 ? top_k : 1, -1, n_rows, top_p, temp);
-    for (int r = 0; mode == 1 && r < n_rows; r++) std::memcpy(hb.seq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
+    if (mode == 1) mt_states_in(hb.seq, mt_states, n_rows);
     ByteLayout l;      // [logits | ctl + states | column states | ids | the log-probability block]
     const size_t o_lg = l.part(lg_b), o_sq = l.part(sq_b), o_st = l.part(st_b), o_id = l.part(id_b), o_lp = l.part(lp_b);
     DeviceBytes d;
@@ -893,167 +860,162 @@ int biogpt_hip_genlp_rows_device(int device, int32_t mode, const float *rows, in
     if (!genlp_read(lb, &req, n_rows, 1, nullptr)) return -2;
     if (mode == 1) {
         HIP_TRY(-2, hipMemcpy(h.data(), sb.ctl, sq_b, hipMemcpyDeviceToHost));
-        for (int r = 0; r < n_rows; r++) std::memcpy(mt_states + (size_t)r * 625, hb.seq[r].mt, 625 * 4);
+        mt_states_out(mt_states, hb.seq, n_rows);
     }
     return 0;
 }
 
-// One launch of queue_rows_lp_kernel (with_lp != 0) or queue_rows_kernel over rows held in host memory (tests of the kernels themselves): row r is column r.
+// ---- the two queue probes: one launch of a column queue's selection over rows held in host memory (tests of the kernels themselves); row r is column r ----
 // The caller builds what a running queue would hold and gets it back as the launch left it: states [n_rows][8] (the SeqState words), finished [n_rows]
-// (SampleSeq::finished), mt_states [n_rows][625], hdr [1 + 2 * n_rows] (n_live, then fin and len of the rows); limits [n_rows] is read only.  ids_out
-// [n_rows][stride] the token histories, lp_out [n_rows][stride] and top_ids_out / top_lp_out [n_rows][stride][n_top] the rows of the log-probability
-// block (null with n_top 0): all filled with 0xff bytes before the launch, so what the kernel does not write stays so.
+// (SampleSeq::finished), mt_states [n_rows][625], hdr (n_live, then fin and len of the rows, then what a mode adds); limits [n_rows] is read only.  ids_out
+// [n_rows][stride] the token histories, lp_out [n_rows][stride] and top_ids_out / top_lp_out [n_rows][stride][n_top] the rows of the log-probability block (null
+// with n_top 0): filled with 0xff bytes before the launch, so what the kernel does not write stays so.
+struct QueueProbeArgs {
+    int device; int32_t with_lp; const float *rows; int32_t n_rows, n_vocab, n_top, stride;
+    uint32_t *mt_states; int32_t *states; const int32_t *limits; int32_t *finished, *hdr, *ids_out;
+    float *lp_out; int32_t *top_ids_out; float *top_lp_out;
+    biogpt_hip_gen_logprobs req() const { return biogpt_hip_gen_logprobs{n_top, lp_out, top_ids_out, top_lp_out}; }
+};
+// a mode's block at some base (null: its size alone): what both modes keep of a column, and the driver's header
+struct QueueProbeCols { bgk::SampleSeq *seq; int32_t *limit; bgk::QueueHdr *hdr; size_t bytes; };
+struct QueueProbeMode {
+    std::function<QueueProbeCols(uint8_t *)> cols;
+    std::function<void(uint8_t *, int32_t *)> fill;      // fill(block, ids): what the host image of the block holds beyond `cols`; the ids rows as the launch finds
+                                                         // them ([n_rows][stride], all -1 so far)
+    std::function<void(uint8_t *, float *, bgk::SeqState *, int32_t *, const GenLpBufs *)> launch;      // launch(block, rows, states, ids, lb or null), all on the device
+    std::function<void(const uint8_t *)> read;           // (or none) read(block): what the mode hands back beyond the header's fin and len
+};
+
+// the pointers and sizes both probes check, in the order of their arguments; own: a mode's own pointers, which stand between rows and mt_states
+static bool queue_probe_args(const QueueProbeArgs &a, std::initializer_list<std::pair<const void *, const char *>> own) {
+    if (!a.rows) BG_FAIL(false, "rows is NULL");
+    for (const auto &p : own)
+        if (!p.first) BG_FAIL(false, "%s is NULL", p.second);
+    if (!a.mt_states) BG_FAIL(false, "mt_states is NULL");
+    if (!a.states) BG_FAIL(false, "states is NULL");
+    if (!a.limits) BG_FAIL(false, "limits is NULL");
+    if (!a.finished) BG_FAIL(false, "finished is NULL");
+    if (!a.hdr) BG_FAIL(false, "hdr is NULL");
+    if (!a.ids_out) BG_FAIL(false, "ids_out is NULL");
+    if (a.n_rows < 1 || a.n_rows > bgk::QUEUE_COLS) BG_FAIL(false, "n_rows must be in [1, %d]", bgk::QUEUE_COLS);
+    if (a.n_vocab < 1 || a.n_vocab > (1 << 20)) BG_FAIL(false, "n_vocab must be in [1, %d]", 1 << 20);
+    if (a.stride < 1 || a.stride > 1024) BG_FAIL(false, "stride must be in [1, 1024]");
+    const biogpt_hip_gen_logprobs req = a.req();
+    return check_gen_logprobs(&req, a.n_vocab);
+}
+
+// The launch and the round trip of what both modes hold, for arguments that passed queue_probe_args and the mode's own checks.  The device block is
+// [rows | the mode's block | column states | ids | the log-probability block].
+static int queue_probe_run(const QueueProbeArgs &a, const QueueProbeMode &m) {
+    const int n_rows = a.n_rows, n_vocab = a.n_vocab, stride = a.stride, n_top = a.n_top;
+    if (!check_mt_states(a.mt_states, n_rows)) return -1;
+    HIP_TRY(-2, hipSetDevice(a.device));
+    static_assert(sizeof(bgk::SeqState) == 32, "eight words per column state");
+    const size_t lg_b = (size_t)n_rows * n_vocab * 4, entries = (size_t)n_rows * (size_t)stride, lp_b = genlp_bufs_at(nullptr, entries, (size_t)n_top).bytes;
+    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = entries * 4;
+    std::vector<uint8_t> h(m.cols(nullptr).bytes, 0);
+    const QueueProbeCols hq = m.cols(h.data());
+    std::vector<int32_t> ids(entries, -1);      // (0xff bytes)
+    hq.hdr->n_live = a.hdr[0];
+    mt_states_in(hq.seq, a.mt_states, n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        hq.seq[r].finished = a.finished[r];
+        hq.limit[r] = a.limits[r];
+        hq.hdr->fin[r] = a.hdr[1 + r]; hq.hdr->len[r] = a.hdr[1 + n_rows + r];
+    }
+    m.fill(h.data(), ids.data());
+    ByteLayout l;
+    const size_t o_lg = l.part(lg_b), o_q = l.part(h.size()), o_st = l.part(st_b), o_id = l.part(id_b), o_lp = l.part(lp_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    const GenLpBufs lb = genlp_bufs_at(d.p + o_lp, entries, (size_t)n_top);
+    const biogpt_hip_gen_logprobs req = a.req();
+    HIP_TRY(-2, hipMemcpy(d.p + o_lg, a.rows, lg_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_q, h.data(), h.size(), hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_st, a.states, st_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemset(d.p + o_id, 0xff, l.bytes() - o_id));
+    HIP_TRY(-2, hipMemcpy(d.p + o_id, ids.data(), id_b, hipMemcpyHostToDevice));
+    if (!genlp_upload(lb, n_top, stride)) return -2;
+    m.launch(d.p + o_q, d.at<float>(o_lg), d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), a.with_lp ? &lb : nullptr);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(a.ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(a.states, d.p + o_st, st_b, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_q, h.size(), hipMemcpyDeviceToHost));
+    if (!genlp_read(lb, &req, n_rows, stride, nullptr)) return -2;
+    a.hdr[0] = hq.hdr->n_live;
+    mt_states_out(a.mt_states, hq.seq, n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        a.finished[r] = hq.seq[r].finished;
+        a.hdr[1 + r] = hq.hdr->fin[r]; a.hdr[1 + n_rows + r] = hq.hdr->len[r];
+    }
+    if (m.read) m.read(h.data());
+    return 0;
+}
+
+// queue_rows_lp_kernel (with_lp != 0) or queue_rows_kernel; hdr [1 + 2 * n_rows]
 int biogpt_hip_queue_rows_device(int device, int32_t with_lp, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t stride, int32_t top_k, double top_p,
                                  double temp, int32_t eos_id, uint32_t *mt_states, int32_t *states, const int32_t *limits, int32_t *finished, int32_t *hdr,
                                  int32_t *ids_out, float *lp_out, int32_t *top_ids_out, float *top_lp_out) {
     clear_error();
-    if (!rows) BG_FAIL(-1, "rows is NULL");
-    if (!mt_states) BG_FAIL(-1, "mt_states is NULL");
-    if (!states) BG_FAIL(-1, "states is NULL");
-    if (!limits) BG_FAIL(-1, "limits is NULL");
-    if (!finished) BG_FAIL(-1, "finished is NULL");
-    if (!hdr) BG_FAIL(-1, "hdr is NULL");
-    if (!ids_out) BG_FAIL(-1, "ids_out is NULL");
-    if (n_rows < 1 || n_rows > bgk::QUEUE_COLS) BG_FAIL(-1, "n_rows must be in [1, %d]", bgk::QUEUE_COLS);
-    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
-    if (stride < 1 || stride > 1024) BG_FAIL(-1, "stride must be in [1, 1024]");
-    const biogpt_hip_gen_logprobs req{n_top, lp_out, top_ids_out, top_lp_out};
-    if (!check_gen_logprobs(&req, n_vocab)) return -1;
-    if (top_k < 1 || top_k > bgk::SAMPLE_MAX_K || top_k > n_vocab) BG_FAIL(-1, "top_k must be in [1, %d] and at most n_vocab", bgk::SAMPLE_MAX_K);
-    if (!std::isfinite(temp) || !(temp > 0.0)) BG_FAIL(-1, "temp must be finite and > 0");
-    if (!std::isfinite(top_p)) BG_FAIL(-1, "top_p must be finite (>= 1: no cut)");
-    if (eos_id < -1 || eos_id >= n_vocab) BG_FAIL(-1, "eos_id %d out of range: must be in [0, %d), or -1 for none", eos_id, n_vocab);
-    for (int r = 0; r < n_rows; r++) {
-        if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
+    const QueueProbeArgs a{device, with_lp, rows, n_rows, n_vocab, n_top, stride, mt_states, states, limits, finished, hdr, ids_out, lp_out, top_ids_out, top_lp_out};
+    if (!queue_probe_args(a, {}) || !check_sample_values(top_k, top_p, temp, eos_id, n_vocab)) return -1;
+    for (int r = 0; r < n_rows; r++)
         if (states[(size_t)r * 8 + 2] < 0) BG_FAIL(-1, "n_gen is negative (row %d)", r);
-    }
-    HIP_TRY(-2, hipSetDevice(device));
-    static_assert(sizeof(bgk::SeqState) == 32, "eight words per column state");
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, entries = (size_t)n_rows * (size_t)stride, lp_b = genlp_bufs_at(nullptr, entries, (size_t)n_top).bytes;
-    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = entries * 4;
-    std::vector<uint8_t> h(queue_bufs_at(nullptr).bytes, 0);
-    const QueueBufs hq = queue_bufs_at(h.data());
-    *hq.ctl = sample_ctl_of(top_k, eos_id, 0, top_p, temp);
-    hq.hdr->n_live = hdr[0];
-    for (int r = 0; r < n_rows; r++) {
-        std::memcpy(hq.seq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
-        hq.seq[r].finished = finished[r];
-        hq.limit[r] = limits[r];
-        hq.hdr->fin[r] = hdr[1 + r]; hq.hdr->len[r] = hdr[1 + n_rows + r];
-    }
-    ByteLayout l;      // [logits | the queue's block | column states | ids | the log-probability block]
-    const size_t o_lg = l.part(lg_b), o_q = l.part(h.size()), o_st = l.part(st_b), o_id = l.part(id_b), o_lp = l.part(lp_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    const QueueBufs qb = queue_bufs_at(d.p + o_q);
-    const GenLpBufs lb = genlp_bufs_at(d.p + o_lp, entries, (size_t)n_top);
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_q, h.data(), h.size(), hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_st, states, st_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_id, 0xff, l.bytes() - o_id));
-    if (!genlp_upload(lb, n_top, stride)) return -2;
-    if (with_lp)
-        hipLaunchKernelGGL(bgk::queue_rows_lp_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, qb.ctl, qb.seq,
-                           d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), stride, qb.limit, qb.hdr, lb.out());
-    else
-        hipLaunchKernelGGL(bgk::queue_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, qb.ctl, qb.seq,
-                           d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), stride, qb.limit, qb.hdr);
-    HIP_TRY(-2, hipGetLastError());
-    HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(states, d.p + o_st, st_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_q, h.size(), hipMemcpyDeviceToHost));
-    if (!genlp_read(lb, &req, n_rows, stride, nullptr)) return -2;
-    hdr[0] = hq.hdr->n_live;
-    for (int r = 0; r < n_rows; r++) {
-        std::memcpy(mt_states + (size_t)r * 625, hq.seq[r].mt, 625 * 4);
-        finished[r] = hq.seq[r].finished;
-        hdr[1 + r] = hq.hdr->fin[r]; hdr[1 + n_rows + r] = hq.hdr->len[r];
-    }
-    return 0;
+    QueueProbeMode m;
+    m.cols = [](uint8_t *base) { const QueueBufs b = queue_bufs_at(base); return QueueProbeCols{b.seq, b.limit, b.hdr, b.bytes}; };
+    m.fill = [&](uint8_t *block, int32_t *) { *queue_bufs_at(block).ctl = sample_ctl_of(top_k, eos_id, 0, top_p, temp); };
+    m.launch = [&](uint8_t *block, float *lg, bgk::SeqState *st, int32_t *ids, const GenLpBufs *lb) {
+        const QueueBufs qb = queue_bufs_at(block);
+        if (lb)
+            hipLaunchKernelGGL(bgk::queue_rows_lp_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, lg, n_vocab, n_vocab, qb.ctl, qb.seq, st, ids, stride, qb.limit, qb.hdr,
+                               lb->out());
+        else
+            hipLaunchKernelGGL(bgk::queue_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, lg, n_vocab, n_vocab, qb.ctl, qb.seq, st, ids, stride, qb.limit, qb.hdr);
+    };
+    return queue_probe_run(a, m);
 }
 
-// One launch of queue_req_rows_kernel<SampleGenLp> (with_lp != 0) or <SamplePlain> over rows held in host memory (tests of the kernel itself): row r is column r
-// with the record of params[r].  Row r's history is hist_lens[r] tokens of `hist` (the histories concatenated), the first prompt_lens[r] of them its prompt -- they
-// go to the column's hist row, there is no prefix -- and the rest its generated tokens, states[r]'s n_gen of them.  states, finished, mt_states, limits and the
-// log-probability block as for biogpt_hip_queue_rows_device; hdr [1 + 3 * n_rows]: n_live, then fin, len and reason of the rows.  ids_out [n_rows][stride] is
-// filled with 0xff bytes, then the first n_gen entries of a row with its generated tokens: what the kernel does not write stays so.
+// queue_req_rows_kernel<SampleGenLp> (with_lp != 0) or <SamplePlain>, row r with the record of params[r].  Row r's history is hist_lens[r] tokens of `hist` (the
+// histories concatenated), the first prompt_lens[r] of them its prompt -- they go to the column's hist row, there is no prefix -- and the rest its generated
+// tokens, states[r]'s n_gen of them, with which its row of ids_out begins.  hdr [1 + 3 * n_rows]: the reason of the rows behind fin and len.
 int biogpt_hip_queue_req_rows_device(int device, int32_t with_lp, const float *rows, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t stride,
                                      const biogpt_hip_request_params *params, const int32_t *hist, const int32_t *hist_lens, const int32_t *prompt_lens,
                                      uint32_t *mt_states, int32_t *states, const int32_t *limits, int32_t *finished, int32_t *hdr, int32_t *ids_out, float *lp_out,
                                      int32_t *top_ids_out, float *top_lp_out) {
     clear_error();
-    if (!rows) BG_FAIL(-1, "rows is NULL");
-    if (!params) BG_FAIL(-1, "params is NULL");
-    if (!hist) BG_FAIL(-1, "hist is NULL");
-    if (!hist_lens) BG_FAIL(-1, "hist_lens is NULL");
-    if (!prompt_lens) BG_FAIL(-1, "prompt_lens is NULL");
-    if (!mt_states) BG_FAIL(-1, "mt_states is NULL");
-    if (!states) BG_FAIL(-1, "states is NULL");
-    if (!limits) BG_FAIL(-1, "limits is NULL");
-    if (!finished) BG_FAIL(-1, "finished is NULL");
-    if (!hdr) BG_FAIL(-1, "hdr is NULL");
-    if (!ids_out) BG_FAIL(-1, "ids_out is NULL");
-    if (n_rows < 1 || n_rows > bgk::QUEUE_COLS) BG_FAIL(-1, "n_rows must be in [1, %d]", bgk::QUEUE_COLS);
-    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
-    if (stride < 1 || stride > 1024) BG_FAIL(-1, "stride must be in [1, 1024]");
-    const biogpt_hip_gen_logprobs req{n_top, lp_out, top_ids_out, top_lp_out};
-    if (!check_gen_logprobs(&req, n_vocab)) return -1;
+    const QueueProbeArgs a{device, with_lp, rows, n_rows, n_vocab, n_top, stride, mt_states, states, limits, finished, hdr, ids_out, lp_out, top_ids_out, top_lp_out};
+    if (!queue_probe_args(a, {{params, "params"}, {hist, "hist"}, {hist_lens, "hist_lens"}, {prompt_lens, "prompt_lens"}})) return -1;
     int hist_stride = 1;
     for (int r = 0; r < n_rows; r++) {
         if (!check_request_params(params[r], r, n_vocab, -1)) return -1;
-        if (mt_states[(size_t)r * 625 + bgk::MT_N] > (uint32_t)bgk::MT_N) BG_FAIL(-1, "generator index out of range (row %d)", r);
         const int n_gen = states[(size_t)r * 8 + 2];
         if (n_gen < 0 || n_gen >= stride) BG_FAIL(-1, "n_gen must be in [0, stride) (row %d)", r);
         if (prompt_lens[r] < 0 || prompt_lens[r] > 1024) BG_FAIL(-1, "prompt_lens[%d] must be in [0, 1024]", r);
         if (hist_lens[r] != prompt_lens[r] + n_gen) BG_FAIL(-1, "hist_lens[%d] (%d) must be prompt_lens[%d] (%d) + n_gen (%d)", r, hist_lens[r], r, prompt_lens[r], n_gen);
         hist_stride = std::max(hist_stride, prompt_lens[r]);
     }
-    HIP_TRY(-2, hipSetDevice(device));
-    static_assert(sizeof(bgk::SeqState) == 32, "eight words per column state");
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, entries = (size_t)n_rows * (size_t)stride, lp_b = genlp_bufs_at(nullptr, entries, (size_t)n_top).bytes;
-    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = entries * 4;
-    std::vector<uint8_t> h(queue_req_bufs_at(nullptr, hist_stride).bytes, 0);
-    const QueueReqBufs hq = queue_req_bufs_at(h.data(), hist_stride);
-    std::vector<int32_t> ids(entries, -1);      // (0xff bytes)
-    hq.hdr->q.n_live = hdr[0];
-    size_t at = 0;
-    for (int r = 0; r < n_rows; r++) {
-        std::memcpy(hq.seq[r].mt, mt_states + (size_t)r * 625, 625 * 4);
-        hq.seq[r].finished = finished[r];
-        hq.limit[r] = limits[r];
-        hq.hdr->q.fin[r] = hdr[1 + r]; hq.hdr->q.len[r] = hdr[1 + n_rows + r]; hq.hdr->reason[r] = hdr[1 + 2 * n_rows + r];
-        hq.rec[r] = request_rec_of(params[r], 0, prompt_lens[r]);
-        std::memcpy(hq.hist + (size_t)r * hist_stride, hist + at, (size_t)prompt_lens[r] * 4);
-        std::memcpy(ids.data() + (size_t)r * stride, hist + at + prompt_lens[r], (size_t)(hist_lens[r] - prompt_lens[r]) * 4);
-        at += (size_t)hist_lens[r];
-    }
-    ByteLayout l;      // [logits | the queue's block | column states | ids | the log-probability block]
-    const size_t o_lg = l.part(lg_b), o_q = l.part(h.size()), o_st = l.part(st_b), o_id = l.part(id_b), o_lp = l.part(lp_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    const QueueReqBufs qb = queue_req_bufs_at(d.p + o_q, hist_stride);
-    const GenLpBufs lb = genlp_bufs_at(d.p + o_lp, entries, (size_t)n_top);
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_q, h.data(), h.size(), hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_st, states, st_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_id, 0xff, l.bytes() - o_id));
-    HIP_TRY(-2, hipMemcpy(d.p + o_id, ids.data(), id_b, hipMemcpyHostToDevice));
-    if (!genlp_upload(lb, n_top, stride)) return -2;
-    enqueue_queue_req_rows(0, n_rows, d.at<float>(o_lg), n_vocab, qb, d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), stride, hist_stride, with_lp ? &lb : nullptr);
-    HIP_TRY(-2, hipGetLastError());
-    HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(states, d.p + o_st, st_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_q, h.size(), hipMemcpyDeviceToHost));
-    if (!genlp_read(lb, &req, n_rows, stride, nullptr)) return -2;
-    hdr[0] = hq.hdr->q.n_live;
-    for (int r = 0; r < n_rows; r++) {
-        std::memcpy(mt_states + (size_t)r * 625, hq.seq[r].mt, 625 * 4);
-        finished[r] = hq.seq[r].finished;
-        hdr[1 + r] = hq.hdr->q.fin[r]; hdr[1 + n_rows + r] = hq.hdr->q.len[r]; hdr[1 + 2 * n_rows + r] = hq.hdr->reason[r];
-    }
-    return 0;
+    QueueProbeMode m;
+    m.cols = [&](uint8_t *base) { const QueueReqBufs b = queue_req_bufs_at(base, hist_stride); return QueueProbeCols{b.seq, b.limit, &b.hdr->q, b.bytes}; };
+    m.fill = [&](uint8_t *block, int32_t *ids) {
+        const QueueReqBufs hq = queue_req_bufs_at(block, hist_stride);
+        size_t at = 0;
+        for (int r = 0; r < n_rows; r++) {
+            hq.hdr->reason[r] = hdr[1 + 2 * n_rows + r];
+            hq.rec[r] = request_rec_of(params[r], 0, prompt_lens[r]);
+            std::memcpy(hq.hist + (size_t)r * hist_stride, hist + at, (size_t)prompt_lens[r] * 4);
+            std::memcpy(ids + (size_t)r * stride, hist + at + prompt_lens[r], (size_t)(hist_lens[r] - prompt_lens[r]) * 4);
+            at += (size_t)hist_lens[r];
+        }
+    };
+    m.launch = [&](uint8_t *block, float *lg, bgk::SeqState *st, int32_t *ids, const GenLpBufs *lb) {
+        enqueue_queue_req_rows(0, n_rows, lg, n_vocab, queue_req_bufs_at(block, hist_stride), st, ids, stride, hist_stride, lb);
+    };
+    m.read = [&](const uint8_t *block) {
+        const QueueReqBufs hq = queue_req_bufs_at(const_cast<uint8_t *>(block), hist_stride);
+        for (int r = 0; r < n_rows; r++) hdr[1 + 2 * n_rows + r] = hq.hdr->reason[r];
+    };
+    return queue_probe_run(a, m);
 }
 
 // SURVEY 8 f1 on the device: `nrows` rows of `k` f32 values (host memory) -> the file's block format of `type`, byte-identical to

@@ -461,3 +461,39 @@ def test_model_dependent_refusals(pkg, files, q40):
     want = alone(g, prompt, 6, 21, HOT)      # still usable
     got, info = queue(pkg, g, [prompt], [6], [21], [HOT], 2, 4)
     assert got == [want[0]] and info["finish"] == [0]
+
+
+# ---- 8. the forms of the two column queues share one context ----
+
+def test_queue_forms_share_a_context(pkg, files):
+    """Plain, prefix=, logprobs= and both, of generate_queue(params=...) and of the closed generate_queue, alternating on one context with one max_columns: each
+    form has captured steps of its own, and every call returns what a fresh context returns."""
+    def conv(v):
+        if isinstance(v, np.ndarray):
+            return (v.view(np.int32) if v.dtype == np.float32 else v).tolist()
+        if isinstance(v, (list, tuple)):
+            return [conv(x) for x in v]
+        if isinstance(v, dict):
+            return {k: conv(x) for k, x in v.items()}
+        return v
+
+    prefix = prompt_of(17, 41)
+    prompts = [prompt_of(6 + 3 * r, 1000 + r) for r in range(6)]
+    suffixes = [p[1:] for p in prompts]
+    kw = dict(max_columns=3, group=4, seeds=[1100 + r for r in range(6)], n_predicts=[12, 7, 10, 12, 5, 9])
+    ruled = [pkg.request_params(**p) for p in (GREEDY, HOT, dict(HOT, repetition_penalty=1.3), dict(GREEDY, no_repeat_ngram_size=2), HOT, dict(HOT, stop=[[5, 6]]))]
+    bare = [pkg.request_params(**p) for p in (GREEDY, HOT, dict(top_k=10, top_p=0.8, temp=2.0), HOT, GREEDY, HOT)]      # (no log-probabilities under rules)
+    calls = []
+    for label, ps, more in (("plain", prompts, {}), ("prefix", suffixes, dict(prefix=prefix)), ("lp", prompts, dict(logprobs=2)),
+                            ("lp prefix", suffixes, dict(prefix=prefix, logprobs=2))):
+        calls.append(("requests " + label, lambda g, ps=ps, more=more: g.generate_queue(ps, 12, params=bare if "logprobs" in more else ruled, **more, **kw)))
+        calls.append(("closed " + label, lambda g, ps=ps, more=more: g.generate_queue(ps, 12, **HOT, **more, **kw)))
+    fresh = {}
+    for label, call in calls:
+        g = pkg.BiogptModel.load(files["q4_0"])
+        fresh[label] = conv(call(g)[:2])
+        g.close()
+    g = pkg.BiogptModel.load(files["q4_0"])
+    for at, (label, call) in enumerate(calls + calls[::-1]):
+        assert conv(call(g)[:2]) == fresh[label], (at, label, "differs from a fresh context")
+    g.close()
