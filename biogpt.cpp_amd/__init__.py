@@ -153,6 +153,105 @@ class _LogprobArrays:
         return [(lp[r, :lens[r]].copy(), ids[r, :lens[r]].copy(), top[r, :lens[r]].copy()) for r in range(n)]
 
 
+class QueueSession:
+    """BiogptModel.queue_session(): see there.  An event is a dict: id, kind ("delta" / "finished" / "cancelled"), first, ids (int32 array of the tokens
+    [first, first + len(ids))), finish (0 limit, 1 EOS, 2 + i stop sequence i; -1 otherwise), admit_step, column, and with logprobs= "logprobs":
+    (float32[n], top_ids int32[n, K], top_logprobs float32[n, K]).  The arrays are copies: they stay valid."""
+
+    def __init__(self, model, max_columns, group, n_predict, prefix, logprobs, stream, n_batch, max_len, top_k, top_p, temp, eos_id):
+        self._h = None
+        self._model = model
+        self.n_predict = int(n_predict)
+        pre = None if prefix is None else _flat_ids([prefix])
+        o = QueueOpts(int(max_columns), int(group), int(n_batch), int(n_predict), int(max_len), 0 if prefix is None else len(prefix),
+                      None if pre is None else pre.ctypes.data, -1 if logprobs is None else int(logprobs), 1 if stream else 0, int(top_k), int(eos_id), float(top_p),
+                      float(temp))
+        h = lib().biogpt_hip_queue_open(model._h, C.byref(o))
+        if not h:
+            raise BiogptError(_err())
+        self._h = h
+
+    def _handle(self):
+        if not self._h:
+            raise BiogptError("the queue session is closed")
+        return self._h
+
+    def submit(self, prompt, n_predict=None, seed=0, params=None):
+        """Copies the request (behind a prefix: its suffix, which may be empty) and returns its id: 0, 1, 2, ... in submission order."""
+        if params is not None and not isinstance(params, RequestParams):
+            raise BiogptError("params must come from request_params() (got %r)" % (type(params).__name__,))
+        h = self._handle()
+        ids = np.ascontiguousarray(list(prompt) or [0], dtype=np.int32)
+        rc = lib().biogpt_hip_queue_submit(h, ids.ctypes.data, len(prompt), self.n_predict if n_predict is None else int(n_predict), int(seed) & 0xFFFFFFFF,
+                                           None if params is None else C.byref(params))
+        if rc < 0:
+            raise BiogptError(_err())
+        return rc
+
+    def cancel(self, id):
+        h = self._handle()
+        if lib().biogpt_hip_queue_cancel(h, int(id)) != 0:
+            raise BiogptError(_err())
+
+    def poll(self, max_groups=1):
+        """At most max_groups groups of steps; the events they produced, in order."""
+        h, ev = self._handle(), C.POINTER(QueueEvent)()
+        n = lib().biogpt_hip_queue_poll(h, int(max_groups), C.byref(ev))
+        if n < 0:
+            raise BiogptError(_err())
+        out = []
+        for i in range(n):
+            e = ev[i]
+            c, k = int(e.count), int(e.n_top)
+            d = {"id": int(e.id), "kind": QUEUE_EVENT_KINDS[e.kind], "first": int(e.first), "ids": np.ctypeslib.as_array(e.ids, (c,)).copy() if c else np.zeros(0, np.int32),
+                 "finish": int(e.finish), "admit_step": int(e.admit_step), "column": int(e.column)}
+            if k >= 0:
+                d["logprobs"] = (np.ctypeslib.as_array(e.lp, (c,)).copy() if c else np.zeros(0, np.float32),
+                                 np.ctypeslib.as_array(e.top_ids, (c, k)).copy() if c and k else np.zeros((c, k), np.int32),
+                                 np.ctypeslib.as_array(e.top_lp, (c, k)).copy() if c and k else np.zeros((c, k), np.float32))
+            out.append(d)
+        return out
+
+    def stats(self):
+        """{"stats": the counts of generate_queue, accumulated, "seconds": host time inside polls, "submitted", "pending", "running"}"""
+        h, st, secs, cnt = self._handle(), QueueStats(), C.c_double(0.0), np.zeros(3, dtype=np.int32)
+        if lib().biogpt_hip_queue_session_stats(h, C.byref(st), C.byref(secs), cnt.ctypes.data) != 0:
+            raise BiogptError(_err())
+        return {"stats": st.as_dict(), "seconds": secs.value, "submitted": int(cnt[0]), "pending": int(cnt[1]), "running": int(cnt[2])}
+
+    def idle(self):
+        s = self.stats()
+        return s["pending"] == 0 and s["running"] == 0
+
+    def drain(self, max_groups=1):
+        """Polls until nothing runs and nothing waits; yields every poll's events."""
+        while True:
+            events = self.poll(max_groups)
+            if events:
+                yield events
+            if self.idle():
+                return
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, None
+            if lib().biogpt_hip_queue_close(h) != 0:
+                raise BiogptError(_err())
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class QueueStats(C.Structure):
     """biogpt_hip_queue_stats"""
     _fields_ = [("columns", C.c_int32), ("steps", C.c_int32), ("groups", C.c_int32), ("admissions", C.c_int32), ("prompt_columns", C.c_int32),
@@ -465,6 +564,89 @@ def queue_plan(gen_lens, max_columns, group, limits=None):
     return {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:n]], "column": [int(v) for v in col[:n]]}
 
 
+class QueueOpts(C.Structure):
+    """biogpt_hip_queue_opts (include/biogpt_hip.h)"""
+    _fields_ = [("max_columns", C.c_int32), ("group", C.c_int32), ("n_batch", C.c_int32), ("n_predict", C.c_int32), ("max_len", C.c_int32), ("n_prefix", C.c_int32),
+                ("prefix", C.c_void_p), ("logprobs", C.c_int32), ("stream", C.c_int32), ("top_k", C.c_int32), ("eos_id", C.c_int32), ("top_p", C.c_double),
+                ("temp", C.c_double)]
+
+
+class QueueEvent(C.Structure):
+    """biogpt_hip_queue_event (include/biogpt_hip.h)"""
+    _fields_ = [("id", C.c_int32), ("kind", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("finish", C.c_int32), ("admit_step", C.c_int32),
+                ("column", C.c_int32), ("n_top", C.c_int32), ("ids", C.POINTER(C.c_int32)), ("lp", C.POINTER(C.c_float)), ("top_ids", C.POINTER(C.c_int32)),
+                ("top_lp", C.POINTER(C.c_float))]
+
+
+QUEUE_EVENT_KINDS = ("delta", "finished", "cancelled")
+SUBMIT, POLL, CANCEL = 0, 1, 2      # the operations of a queue_plan_script script
+
+
+def queue_plan_script(ops, gen_lens, limits, max_columns, group):
+    """The schedule of a queue session (BiogptModel.queue_session) on a script, from the lengths alone (biogpt_hip_queue_plan_script: the scheduler the session
+    itself drives, no device).  ops: (SUBMIT,), (POLL, n) and (CANCEL, r) in order; the i-th SUBMIT is request i, which generates gen_lens[i] tokens under the
+    limit limits[i].  Returns {"stats": {...}, "admit_step": [...], "column": [...], "finish_group": [...], "lens": [...]}: -1 in the first two where a request
+    never took a column; finish_group the groups run when the request's finished or cancelled event came (-1: the script ends before); lens what it had then."""
+    flat = np.zeros((max(len(ops), 1), 2), dtype=np.int32)
+    for i, op in enumerate(ops):
+        flat[i, 0] = int(op[0])
+        flat[i, 1] = int(op[1]) if len(op) > 1 else 0
+    gl = np.ascontiguousarray(gen_lens, dtype=np.int32).reshape(-1)
+    lm = np.ascontiguousarray(limits, dtype=np.int32).reshape(-1)
+    n = sum(1 for op in ops if int(op[0]) == SUBMIT)
+    if gl.size != n or lm.size != n:
+        raise BiogptError("gen_lens and limits must have one entry per SUBMIT (%d, %d != %d)" % (gl.size, lm.size, n))
+    if n == 0:
+        gl = lm = np.zeros(1, np.int32)
+    adm, col, fg, ln = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(4))
+    st = QueueStats()
+    if lib().biogpt_hip_queue_plan_script(flat.ctypes.data, len(ops), gl.ctypes.data, lm.ctypes.data, int(max_columns), int(group), adm.ctypes.data, col.ctypes.data,
+                                          fg.ctypes.data, ln.ctypes.data, C.byref(st)) != 0:
+        raise BiogptError(_err())
+    return {"stats": st.as_dict(), "admit_step": [int(v) for v in adm[:n]], "column": [int(v) for v in col[:n]], "finish_group": [int(v) for v in fg[:n]],
+            "lens": [int(v) for v in ln[:n]]}
+
+
+def queue_stream_rows(n_gen, gen_rows, g, lp=None, top_ids=None, top_lp=None, guard=256, device=0):
+    """queue_stream_kernel on constructed columns (biogpt_hip_queue_stream_device): n_gen int32 [C], gen_rows int32 [C][gen_stride]; lp float32 [C][lp_stride]
+    with top_ids / top_lp [C][lp_stride][K] for the form with log-probabilities (K may be 0).  Returns (block uint8, layout bytes): the block as the launch
+    left it, preset to 0xff bytes, `guard` bytes longer than its layout."""
+    ng = np.ascontiguousarray(n_gen, dtype=np.int32).reshape(-1)
+    rows = np.ascontiguousarray(gen_rows, dtype=np.int32)
+    c, stride = int(rows.shape[0]), int(rows.shape[1])
+    k, lps = -1, 1
+    a_lp = a_ti = a_tl = None
+    if lp is not None:
+        a_lp = np.ascontiguousarray(lp, dtype=np.float32)
+        lps = int(a_lp.shape[1])
+        a_ti = np.ascontiguousarray(top_ids, dtype=np.int32)
+        a_tl = np.ascontiguousarray(top_lp, dtype=np.float32)
+        k = int(a_ti.shape[2])
+    per = c * int(g)
+    need = sum((b + 15) // 16 * 16 for b in ([c * 4, per * 4] + ([per * 4, per * k * 4, per * k * 4] if k >= 0 else [])))
+    block = np.zeros(need + int(guard), dtype=np.uint8)
+    got = lib().biogpt_hip_queue_stream_device(int(device), ng.ctypes.data, rows.ctypes.data, c, stride, int(g), k, lps, None if a_lp is None else a_lp.ctypes.data,
+                                               None if a_ti is None or k == 0 else a_ti.ctypes.data, None if a_tl is None or k == 0 else a_tl.ctypes.data,
+                                               block.ctypes.data, block.size)
+    if got < 0:
+        raise BiogptError(_err())
+    return block, int(got)
+
+
+def queue_cancel_cols(cols, finished, n_gen, hdr, device=0):
+    """queue_cancel_kernel on the list `cols` over 512 constructed columns (biogpt_hip_queue_cancel_device): finished int32 [512] and hdr int32 [1 + 1024]
+    (n_live, fin[], len[]) are changed in place, n_gen int32 [512] is read."""
+    cl = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+    ng = np.ascontiguousarray(n_gen, dtype=np.int32).reshape(-1)
+    for a, size, name in ((finished, 512, "finished"), (hdr, 1025, "hdr")):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags["C_CONTIGUOUS"] and a.size == size):
+            raise BiogptError("%s must be a contiguous int32 array of %d" % (name, size))
+    if ng.size != 512:
+        raise BiogptError("n_gen must have 512 entries")
+    if lib().biogpt_hip_queue_cancel_device(int(device), cl.ctypes.data, int(cl.size), finished.ctypes.data, ng.ctypes.data, hdr.ctypes.data) != 0:
+        raise BiogptError(_err())
+
+
 PREFIX_BATCH_SLOTS = 512      # one biogpt_hip_score_continuations_batch call: a slot per prefix and one per continuation
 
 
@@ -731,6 +913,15 @@ SYMBOLS = [
     ("biogpt_hip_generate_queue_requests", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RequestParams), _P,
                                                     _P, _P, _P, _P, _P, C.POINTER(C.c_double), C.POINTER(QueueStats), C.POINTER(GenLogprobs)]),
     ("biogpt_hip_queue_req_rows_device", C.c_int, [C.c_int, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RequestParams)] + [_P] * 12),
+    ("biogpt_hip_queue_open", _P, [_P, C.POINTER(QueueOpts)]),
+    ("biogpt_hip_queue_submit", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(RequestParams)]),
+    ("biogpt_hip_queue_cancel", C.c_int, [_P, C.c_int32]),
+    ("biogpt_hip_queue_poll", C.c_int, [_P, C.c_int32, C.POINTER(C.POINTER(QueueEvent))]),
+    ("biogpt_hip_queue_session_stats", C.c_int, [_P, C.POINTER(QueueStats), C.POINTER(C.c_double), _P]),
+    ("biogpt_hip_queue_close", C.c_int, [_P]),
+    ("biogpt_hip_queue_plan_script", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.POINTER(QueueStats)]),
+    ("biogpt_hip_queue_stream_device", C.c_int64, [C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64]),
+    ("biogpt_hip_queue_cancel_device", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, _P]),
     ("biogpt_hip_attn_device", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("biogpt_hip_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32] + [_P] * 7 + [C.c_int32] * 3 + [_P] * 7),
     ("biogpt_hip_wide_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 4),
@@ -1446,6 +1637,14 @@ class BiogptModel:
         if fin is not None:
             info["finish"] = [int(v) for v in fin[:R]]
         return ids, info, secs.value
+
+    def queue_session(self, max_columns=64, group=4, n_predict=64, prefix=None, logprobs=None, stream=False, n_batch=8, max_len=0, top_k=1, top_p=0.9, temp=0.9,
+                      eos_id=-1):
+        """A queue session ("A serving loop"; biogpt_hip_queue_open): generate_queue(params=, prefix=, logprobs=) for requests that arrive over
+        time.  A context manager with submit(prompt, n_predict=None, seed=0, params=None) -> id, poll(max_groups=1) -> [events], cancel(id), drain() and
+        stats().  n_predict is the most any request may ask for; top_k / top_p / temp / eos_id the sampler of a request submitted without params; stream=True
+        adds "delta" events for the tokens running requests append.  While it is open the model serves nothing else."""
+        return QueueSession(self, max_columns, group, n_predict, prefix, logprobs, stream, n_batch, max_len, top_k, top_p, temp, eos_id)
 
     def read_column_state(self, column, pos, which=0, n_ids=0):
         """Tests of slot reuse (biogpt_hip_read_column_state): (the K (which 0) or V (1) row of position pos in every layer of column `column`'s own cache slot,

@@ -347,6 +347,9 @@ struct biogpt_hip_ctx {
     // graphs_queue_req), and its pinned twin
     uint8_t *queue_req_buf = nullptr;
     uint8_t *queue_req_host = nullptr;
+    // a queue session (biogpt_hip_queue_open) is open on this context: it has the columns, the slots and the captured steps to itself, and every other
+    // evaluating call is refused (session_refuses) until biogpt_hip_queue_close
+    struct biogpt_hip_queue_session *session = nullptr;
     // beam search over a queue (biogpt_hip_generate_beam_queue, kernels_beam_queue.hip.h): the searches' state is bbatch_buf; this block holds what the queue adds
     // (bqueue_bufs_at: the report header and the admit list), allocated at the first such call, and its pinned twin (BeamQueueHost, then the pool rows of
     // every slot as they come back)
@@ -422,6 +425,7 @@ struct biogpt_hip_ctx {
 };
 
 static bool resident_stop(biogpt_hip_ctx *c);   // ends a resident single-token launch (defined with the eval entry points)
+static void queue_session_orphan(biogpt_hip_ctx *c);   // a context freed under its open queue session: the session keeps its handle, and nothing else
 // An entry point that enqueues work of its own (generate_*, eval_all, eval_prompt, the bench calls) makes the row of an EARLIER replayed single-token eval history: its lineage
 // watch must not fire on a later biogpt_hip_read_logits (it would re-evaluate the old token at the old position over this call's K / V rows).  ADVICE r5.
 static inline void disarm_lineage(biogpt_hip_ctx *c) { c->dev_stamp_expect = 0; c->stamp_expect = 0; }
@@ -1638,9 +1642,16 @@ bool upload_state(biogpt_hip_ctx *c, const int32_t *tokens, int n, int n_past, i
     return true;
 }
 
+// While a queue session is open its context serves nothing else: the session's columns, K / V slots and captured steps persist between its calls
+bool session_refuses(const biogpt_hip_ctx *c) {
+    if (c->session) BG_FAIL(true, "a queue session is open on this context (biogpt_hip_queue_open): it has the context to itself until biogpt_hip_queue_close");
+    return false;
+}
+
 bool check_eval_args(const biogpt_hip_ctx *c, const int32_t *tokens, int n, int n_past) {
     if (!c) BG_FAIL(false, "null context");
     if (!c->ready) BG_FAIL(false, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(c)) return false;
     if (!tokens || n < 1) BG_FAIL(false, "no tokens to evaluate");
     if (n_past < 0 || n_past + n > c->hp.n_positions)
         BG_FAIL(false, "n_past (%d) + n_tokens (%d) exceeds n_positions (%d)", n_past, n, c->hp.n_positions);
@@ -1783,6 +1794,7 @@ bool upload_weights(biogpt_hip_ctx *c, const ModelFile &mf) {
 
 void destroy(biogpt_hip_ctx *c) {
     if (!c) return;
+    queue_session_orphan(c);
     (void)hipSetDevice(c->device);
     (void)resident_stop(c);
     if ((c->opt.res_dbg & 32) && c->tstamp && c->res_seq > 8) {      // device-side stamps: token seen by XCD 0's poller [s][0], lm_head workgroup 0's completion word [s][1]
@@ -3006,6 +3018,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     if (!ctx || !prompts || !prompt_lens || !out_ids) BG_FAIL(-1, "null argument");
     if (lp && !check_gen_logprobs(lp, ctx->hp.n_vocab)) return -1;
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     if (prefix && (n_seqs < 1 || n_seqs > 511)) BG_FAIL(-1, "n_seqs must be in [1, 511] behind a prefix (got %d)", n_seqs);   // one slot holds the prefix
     // (the plain call meets the gate in enqueue_forward, as ever; the two variants are not open to the wide chain and say so by name)
     if ((prefix || lp) && !check_fast_chain(ctx, prefix ? "generation behind a shared prefix" : "generation with log-probabilities")) return -1;
@@ -3192,6 +3205,7 @@ static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (!ctx) BG_FAIL(-1, "null context");
     if (!seqs || !lens || !logprob_out) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");   // each sequence owns a full F32 KV cache
     if (!check_fast_chain(ctx, "batched scoring", true)) return -1;
     size_t total = 0;
@@ -3304,6 +3318,7 @@ static int score_continuations_once(biogpt_hip_ctx *ctx, const int32_t *prefix, 
     if (!cont_lens) BG_FAIL(-1, "null argument: cont_lens");
     if (!logprob_out) BG_FAIL(-1, "null argument: logprob_out");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     if (n_prefix < 1) BG_FAIL(-1, "n_prefix must be >= 1 (got %d)", n_prefix);
     if (n_conts < 1 || n_conts > 511) BG_FAIL(-1, "n_conts must be in [1, 511] (got %d)", n_conts);   // slot 0 is the prefix; each continuation owns a full F32 KV cache
     const auto &hp = ctx->hp;
@@ -3392,6 +3407,7 @@ static int score_continuations_batch_once(biogpt_hip_ctx *ctx, const int32_t *pr
     if (!n_conts) BG_FAIL(-1, "null argument: n_conts");
     if (!logprob_out) BG_FAIL(-1, "null argument: logprob_out");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     if (n_groups < 1) BG_FAIL(-1, "n_groups must be >= 1 (got %d)", n_groups);
     long slots = n_groups;
     for (int g = 0; g < n_groups; g++) {
@@ -3565,6 +3581,7 @@ static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (!check_embed_args(seqs, lens, n_seqs, o, out_host)) return -1;
     if (!ctx) BG_FAIL(-1, "null context");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     const auto &hp = ctx->hp;
     if (!check_fast_chain(ctx, "batched embedding", true)) return -1;
     if (o.layer > hp.n_layer) BG_FAIL(-1, "layer (%d) must be in [-1, n_layer = %d]", o.layer, hp.n_layer);
@@ -3870,6 +3887,7 @@ static int generate_sample_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     if (lp && !check_gen_logprobs(lp, ctx->hp.n_vocab)) return -1;
     if (lp && (rules || trie)) BG_FAIL(-1, "log-probabilities cannot be combined with generation rules or a trie");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     if (prefix && (n_prompts < 1 || n_samples < 1 || (int64_t)n_prompts * n_samples > 511))
         BG_FAIL(-1, "n_prompts x n_samples must be in [1, 511] behind a prefix");   // one slot holds the prefix
     if (n_prompts < 1 || n_samples < 1 || (int64_t)n_prompts * n_samples > 512) BG_FAIL(-1, "n_prompts x n_samples must be in [1, 512]");   // each sequence owns a full F32 KV cache
@@ -4156,6 +4174,7 @@ static int generate_beam_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompts,
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompts || !prompt_lens || !out_ids || !out_lens || !out_scores || !out_counts) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     if (n_prompts < 1) BG_FAIL(-1, "n_prompts must be >= 1");
     if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
     if ((int64_t)n_prompts * n_beams > BBATCH_COLS) BG_FAIL(-1, "n_prompts x n_beams must be at most %d", BBATCH_COLS);   // each column owns a full F32 KV cache
@@ -4246,6 +4265,7 @@ int biogpt_hip_generate_beam_rules(biogpt_hip_ctx *ctx, const int32_t *prompt, i
     if (!ctx) BG_FAIL(-1, "null context");
     if (!prompt || !out_ids || !out_lens || !out_scores) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     if (n_beams < 1 || n_beams > bgk::BEAM_MAX) BG_FAIL(-1, "n_beams must be in [1, %d]", bgk::BEAM_MAX);
     if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");
     if (n_prompt < 1) BG_FAIL(-1, "empty prompt");      // (in this order: a call with several bad arguments reports the first of them)
@@ -4319,6 +4339,7 @@ static int generate_contrastive_once(biogpt_hip_ctx *ctx, const int32_t *prompts
     if (eos_id < -1) BG_FAIL(-1, "eos_id %d out of range: must be a token id, or -1 for none", eos_id);
     if (!ctx) BG_FAIL(-1, "null context");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     const int G = n_prompts, K = top_k, n_seqs = G * K;
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_prompts x top_k (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
     const auto &hp = ctx->hp;
@@ -4466,6 +4487,7 @@ static int generate_lookup_once(biogpt_hip_ctx *ctx, const int32_t *prompts, con
     }
     if (!ctx) BG_FAIL(-1, "null context");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return -1;
     const int G = n_prompts, S = 1 + max_draft, n_cols = G * S;
     if (n_cols > hp_cols(ctx)) BG_FAIL(-1, "n_prompts x (1 + max_draft) (%d) exceeds the %d activation columns of this model", n_cols, hp_cols(ctx));
     const auto &hp = ctx->hp;
@@ -4587,24 +4609,33 @@ int biogpt_hip_generate_lookup(biogpt_hip_ctx *ctx, const int32_t *prompts, cons
 // refill, and a refill packs what follows them.
 extern "C++" {
 struct QueueSchedule {
-    const int32_t *cap;                     // tokens request r may generate at most; 0: it never takes a column
-    int R, C = 0, group, next = 0, pending = 0, running = 0;
+    const std::vector<int32_t> &cap;        // tokens request r may generate at most; 0: it never takes a column.  A session appends to it (submit)
+    int known = 0;                          // requests of cap the schedule has counted
+    int C = 0, group, next = 0, pending = 0, running = 0;
     std::vector<int32_t> req, since;        // per column: its request (-1: none yet), steps since its admission
     std::vector<uint8_t> live;              // per column: its request still runs
+    std::vector<uint8_t> dropped;           // per request: withdrawn while it was pending (a session's cancel)
     biogpt_hip_queue_stats st{};
-    QueueSchedule(const int32_t *cap_, int R_, int max_columns, int group_) : cap(cap_), R(R_), group(group_) {
-        for (int r = 0; r < R; r++) pending += cap[r] > 0 ? 1 : 0;
-        C = std::min(max_columns, pending);
+    // A closed call: every request of cap_ is there, and the columns shrink to the eligible requests.  A session (fixed_columns): max_columns columns from
+    // the start on, whatever has been submitted.
+    QueueSchedule(const std::vector<int32_t> &cap_, int max_columns, int group_, bool fixed_columns = false) : cap(cap_), group(group_) {
+        while (known < (int)cap.size()) submit();
+        C = fixed_columns ? max_columns : std::min(max_columns, pending);
         req.assign((size_t)C, -1); since.assign((size_t)C, 0); live.assign((size_t)C, 0);
         st.columns = C;
     }
+    // the request appended to cap becomes pending (or, without room for a token, never takes a column); its index
+    int submit() { dropped.push_back(0); pending += cap[(size_t)known] > 0 ? 1 : 0; return known++; }
     bool done() const { return running == 0 && pending == 0; }
+    bool is_pending(int r) const { return r >= next && r < known && cap[(size_t)r] > 0 && !dropped[(size_t)r]; }
+    void drop(int r) { dropped[(size_t)r] = 1; pending--; }      // a pending request is withdrawn: it never takes a column
+    int column_of(int r) const { for (int col = 0; col < C; col++) if (live[(size_t)col] && req[(size_t)col] == r) return col; return -1; }
     // free columns, ascending <- pending requests, ascending: admit(col, r) for each; the number admitted
     template <class Admit> int refill(Admit admit) {
         int n = 0;
         for (int col = 0; col < C && pending > 0; col++) {
             if (live[(size_t)col]) continue;
-            while (cap[next] <= 0) next++;
+            while (cap[(size_t)next] <= 0 || dropped[(size_t)next]) next++;
             req[(size_t)col] = next; since[(size_t)col] = 0; live[(size_t)col] = 1;
             admit(col, next);
             next++; pending--; running++; n++;
@@ -4614,14 +4645,58 @@ struct QueueSchedule {
     }
     int group_steps() const {
         int most = 0;
-        for (int col = 0; col < C; col++) if (live[(size_t)col]) most = std::max(most, cap[req[(size_t)col]] - since[(size_t)col]);
+        for (int col = 0; col < C; col++) if (live[(size_t)col]) most = std::max(most, cap[(size_t)req[(size_t)col]] - since[(size_t)col]);
         return std::min(group, most);
     }
     // the position of column col's token at its next step, at most (len: its prompt's length); -1: the column was never used
-    int position(int col, int len) const { return req[(size_t)col] < 0 ? -1 : len - 1 + std::min(since[(size_t)col], cap[req[(size_t)col]]); }
+    int position(int col, int len) const { return req[(size_t)col] < 0 ? -1 : len - 1 + std::min(since[(size_t)col], cap[(size_t)req[(size_t)col]]); }
     void step() { for (int col = 0; col < C; col++) if (req[(size_t)col] >= 0) since[(size_t)col]++; st.steps++; st.column_steps += C; }
     void end_group() { st.groups++; }
     void retire(int col, int len) { live[(size_t)col] = 0; running--; st.busy_column_steps += len; }
+};
+
+// The schedule of a queue session (biogpt_hip_queue_open): QueueSchedule with its columns fixed, fed while it runs.  A request is submitted, and may be
+// cancelled, between two polls; what that does to the schedule happens at the next poll's start (begin_poll), in front of its first refill.  The session
+// drives this struct and biogpt_hip_queue_plan_script runs it on a script with given lengths: one scheduler, with and without a device.
+struct QueueSessionSchedule {
+    enum State : uint8_t { PENDING, RUNNING, FINISHED, CANCELLED };
+    std::vector<int32_t> cap;
+    QueueSchedule q;
+    std::vector<uint8_t> state, asked;      // per request: where it stands; a cancel has been asked for
+    std::vector<int32_t> idle_new, cancels; // since the last poll: requests submitted without room for a token; cancels, in the order asked
+    QueueSessionSchedule(int max_columns, int group) : q(cap, max_columns, group, true) {}
+    int submit(int cap_r) {
+        cap.push_back(std::max(cap_r, 0));
+        state.push_back(cap_r > 0 ? PENDING : FINISHED); asked.push_back(0);
+        const int r = q.submit();
+        if (cap_r <= 0) idle_new.push_back(r);
+        return r;
+    }
+    // 0: the request will be cancelled at the next poll's start; -1: no such request; -2: it has finished or was cancelled already
+    int cancel(int r) {
+        if (r < 0 || r >= q.known) return -1;
+        if (state[(size_t)r] == FINISHED || state[(size_t)r] == CANCELLED || asked[(size_t)r]) return -2;
+        asked[(size_t)r] = 1; cancels.push_back(r);
+        return 0;
+    }
+    // A poll's start: idle(r) for a request that may not generate a token (it is finished with length 0); dropped(r) for a cancelled pending request;
+    // stopped(col, r, len) for a cancelled running one, whose column is free for this poll's first refill -- a running request has taken one step per step
+    // since its admission, so the host knows its length without a look.
+    template <class Idle, class Dropped, class Stopped> void begin_poll(Idle idle, Dropped dropped, Stopped stopped) {
+        for (int r : idle_new) idle(r);
+        idle_new.clear();
+        for (int r : cancels) {
+            if (state[(size_t)r] == PENDING) { q.drop(r); state[(size_t)r] = CANCELLED; dropped(r); }
+            else if (state[(size_t)r] == RUNNING) {
+                const int col = q.column_of(r), len = q.since[(size_t)col];
+                q.retire(col, len); state[(size_t)r] = CANCELLED;
+                stopped(col, r, len);
+            }
+        }
+        cancels.clear();
+    }
+    void admitted(int r) { state[(size_t)r] = RUNNING; }
+    void finished(int col, int r, int len) { q.retire(col, len); state[(size_t)r] = FINISHED; }
 };
 }  // extern "C++"
 
@@ -4644,7 +4719,8 @@ static int queue_plan_of(const int32_t *gen_lens, const int32_t *limits, int32_t
     }
     std::fill(admit_step, admit_step + n_requests, -1);
     std::fill(column, column + n_requests, -1);
-    QueueSchedule q(limits, n_requests, max_columns, group);
+    const std::vector<int32_t> cap(limits, limits + n_requests);
+    QueueSchedule q(cap, max_columns, group);
     while (!q.done()) {
         q.refill([&](int col, int r) { admit_step[r] = q.st.steps; column[r] = col; });
         for (int g = q.group_steps(); g > 0; g--) q.step();
@@ -4666,6 +4742,61 @@ int biogpt_hip_queue_plan_limits(const int32_t *gen_lens, const int32_t *limits,
     return queue_plan_of(gen_lens, limits, n_requests, max_columns, group, admit_step, column, stats);
 }
 
+// The session's scheduler on a script, with given lengths (biogpt_hip.h).  ops: [n_ops][2] = {kind, argument}: 0 SUBMIT (the next request: entry i of gen_lens /
+// limits for the i-th submit), 1 POLL n (at most n groups), 2 CANCEL r.
+int biogpt_hip_queue_plan_script(const int32_t *ops, int32_t n_ops, const int32_t *gen_lens, const int32_t *limits, int32_t max_columns, int32_t group, int32_t *admit_step,
+                                 int32_t *column, int32_t *finish_group, int32_t *out_lens, biogpt_hip_queue_stats *stats) {
+    clear_error();
+    if (!ops) BG_FAIL(-1, "null argument: ops");
+    if (n_ops < 0) BG_FAIL(-1, "n_ops must be >= 0");
+    if (max_columns < 1 || max_columns > bgk::QUEUE_COLS) BG_FAIL(-1, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
+    if (group < 1 || group > 64) BG_FAIL(-1, "group must be in [1, 64]");
+    int R = 0;
+    for (int i = 0; i < n_ops; i++) {
+        const int kind = ops[2 * i], arg = ops[2 * i + 1];
+        if (kind < 0 || kind > 2) BG_FAIL(-1, "ops[%d]: kind %d is none of 0 SUBMIT, 1 POLL, 2 CANCEL", i, kind);
+        if (kind == 1 && arg < 0) BG_FAIL(-1, "ops[%d]: POLL %d: the groups of a poll must be >= 0", i, arg);
+        R += kind == 0 ? 1 : 0;
+    }
+    if (R > 0) {
+        if (!gen_lens) BG_FAIL(-1, "null argument: gen_lens");
+        if (!limits) BG_FAIL(-1, "null argument: limits");
+        if (!admit_step) BG_FAIL(-1, "null argument: admit_step");
+        if (!column) BG_FAIL(-1, "null argument: column");
+        if (!finish_group) BG_FAIL(-1, "null argument: finish_group");
+    }
+    for (int r = 0; r < R; r++) {
+        if (gen_lens[r] < 0) BG_FAIL(-1, "gen_lens[%d] (%d) is negative", r, gen_lens[r]);
+        if (limits[r] < gen_lens[r]) BG_FAIL(-1, "limits[%d] (%d) is below gen_lens[%d] (%d)", r, limits[r], r, gen_lens[r]);
+        if (limits[r] > 0 && gen_lens[r] < 1) BG_FAIL(-1, "gen_lens[%d] is 0 under a limit of %d: a request that takes a column generates a token", r, limits[r]);
+        admit_step[r] = column[r] = finish_group[r] = -1;
+        if (out_lens) out_lens[r] = 0;
+    }
+    QueueSessionSchedule ss(max_columns, group);
+    QueueSchedule &q = ss.q;
+    for (int i = 0; i < n_ops; i++) {
+        const int kind = ops[2 * i], arg = ops[2 * i + 1];
+        if (kind == 0) { ss.submit(limits[q.known]); continue; }
+        if (kind == 2) { (void)ss.cancel(arg); continue; }      // (what a session refuses -- an unknown or finished request -- changes nothing)
+        ss.begin_poll([&](int r) { finish_group[r] = q.st.groups; }, [&](int r) { finish_group[r] = q.st.groups; },
+                      [&](int, int r, int len) { finish_group[r] = q.st.groups; if (out_lens) out_lens[r] = len; });
+        for (int n = 0; n < arg && !q.done(); n++) {
+            q.refill([&](int col, int r) { admit_step[r] = q.st.steps; column[r] = col; ss.admitted(r); });
+            for (int g = q.group_steps(); g > 0; g--) q.step();
+            q.end_group();
+            for (int col = 0; col < q.C; col++) {
+                const int r = q.req[(size_t)col];
+                if (!q.live[(size_t)col] || q.since[(size_t)col] < gen_lens[r]) continue;
+                ss.finished(col, r, gen_lens[r]);
+                finish_group[r] = q.st.groups;
+                if (out_lens) out_lens[r] = gen_lens[r];
+            }
+        }
+    }
+    if (stats) *stats = q.st;
+    return 0;
+}
+
 // A mode checks its own arguments between the shared checks (QueueRequests), describes itself as a QueueCall and hands both to run_queue_call.  The driver
 // delivers every result as it goes, so the mode reads nothing back.
 struct QueueRequests {
@@ -4681,6 +4812,9 @@ struct QueueRequests {
     const int32_t *prefix = nullptr;
     int pos0 = 0, n_shared = 0;
     int whole_len(int r) const { return pos0 + prompt_lens[r]; }
+    // A session keeps every request's prompt on its own (own[r]; prompts is null and off unused) and lets prompt_lens, n_requests and cap grow
+    const int32_t *const *own = nullptr;
+    const int32_t *prompt(int r) const { return own ? own[r] : prompts + off[(size_t)r]; }
 
     // Tier one, what can be judged without the model (it fails the same way with no context and no device): check_count, the mode's column counts, check_sizes,
     // the mode's other parameters, then check_prompts, which ends the tier with the context itself.
@@ -4708,6 +4842,7 @@ struct QueueRequests {
         n_shared = prefix ? (pos0 - 1) / n_batch * n_batch : 0;
         if (!ctx) BG_FAIL(false, "null context");
         if (!ctx->ready) BG_FAIL(false, "model has no tensors loaded (empty model): cannot evaluate");
+        if (session_refuses(ctx)) return false;
         return true;
     }
     // Tier two, what needs the model's sizes: the mode's parameters, then the prompts.  Tier three, the fast chain, ends this check; what a mode still has to
@@ -4754,58 +4889,61 @@ struct QueueCall {
                                                     // length the schedule retires it with, < 0: a failure
     std::function<bool()> landed;                   // (or none) behind every header wait and once behind the final synchronize: copies enqueued before the wait
                                                     // before have arrived
+    // a session's (or none): after_group(g) enqueues what the look behind a group of g steps carries beside the header, in front of the header's copy;
+    // looked() reads it, behind the wait and before any unit is collected
+    std::function<bool(int)> after_group;
+    std::function<bool()> looked;
 };
 
-// The one order of a queued call, for requests that passed their checks.  Returns 0 once every request has been served and the stream has drained, or at once
-// where no request may generate a token (nothing was touched); -1: the columns do not fit the model; -2: a failure.
-static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc) {
-    const int P = ctx->hp.n_positions, R = rq.n_requests;
-    // every request's own clamp; the buckets the steps can need
-    rq.cap.assign((size_t)R, 0);
-    int min_len = P, max_keys = 0;
-    long total = 0;
-    for (int r = 0; r < R; r++) {
-        rq.cap[(size_t)r] = std::min(rq.n_predicts ? rq.n_predicts[r] : rq.n_predict, P - rq.whole_len(r));
-        if (rq.cap[(size_t)r] <= 0) continue;
-        min_len = std::min(min_len, rq.whole_len(r)); max_keys = std::max(max_keys, rq.whole_len(r) + rq.cap[(size_t)r]);
-        total += rq.whole_len(r);
-    }
-    const std::vector<int32_t> &cap = rq.cap;
-    if (qc.out_admit_step) std::fill(qc.out_admit_step, qc.out_admit_step + R, -1);
-    if (qc.out_unit) std::fill(qc.out_unit, qc.out_unit + R, -1);
-    if (qc.seconds_out) *qc.seconds_out = 0.0;
-    QueueSchedule q(cap.data(), R, qc.max_units, rq.group);
-    const int U = q.C, C = U * qc.per_unit;
-    if (qc.stats) *qc.stats = q.st;
-    if (U == 0) return 0;      // nobody has room for a token: nothing was touched
-    if (C > hp_cols(ctx)) BG_FAIL(-1, "max_columns (%d) exceeds the %d activation columns of this model", C, hp_cols(ctx));
-
-    XpCallScope xp_scope(ctx);
-    XcBatchScope xc_scope{ctx};
-    // (behind shared rows: they lie in one slot more, behind the units')
-    const SharedRows shared{rq.n_shared, rq.n_shared > 0 ? C : 0};
-    if (!begin_column_call(ctx, C + (shared.n > 0 ? 1 : 0), C, std::min<long>(total, P))) return -2;
-    ctx->xc_batch = 0;      // the steps are always the launch chain
-    if (!qc.prepare(U)) return -2;
-    column_graphs_for(*qc.graphs, U, qc.key_b);
-    // (ColumnKeys of a call whose first replayed step sees min_len keys and whose last one max_keys: every bucket a step here can be bounded by)
-    bool use_graph;
-    if (!capture_column_steps(ctx, *qc.graphs, qc.form, ColumnKeys{min_len - 1, 1, P}, max_keys - min_len + 2, qc.step, &use_graph)) return -2;
-
-    const auto t0 = std::chrono::steady_clock::now();
+// The one order of a queued call as an object that can stop between two groups: begin (the caches, the mode's buffers, the captured steps, the shared
+// rows), turn (one refill, one group of steps, one look, the finished units collected), end (the stream drained, the pipeline's error word, the timed span).
+// A closed call is begin, turn until the schedule is done, end (run_queue_call); a session (biogpt_hip_queue_open) runs begin at open, some turns per poll
+// and end never -- its polls drain the stream themselves.  The schedule is the caller's: a session feeds it between turns.  The caller holds the call's
+// scopes (XpCallScope, XcBatchScope) around whatever it runs of this.
+struct QueueRun {
+    biogpt_hip_ctx *ctx;
+    QueueRequests &rq;
+    QueueCall &qc;
+    QueueSchedule &q;
+    int U = 0, C = 0;
+    SharedRows shared{};
+    bool use_graph = false;
+    std::chrono::steady_clock::time_point t0{};
     std::vector<int32_t> flat, lens, slots;
-    if (shared.n > 0) {      // the shared rows, once: the prompt columns of one sequence in the slot behind the units'
-        const int32_t n = shared.n;
-        if (!pack_column_passes(ctx, rq.prefix, &n, 1, rq.n_batch, [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); },
-                                1, shared.slot))
-            return -2;
-        q.st.prompt_columns += n;
+
+    // min_len / max_keys: the keys the first replayed step of any request sees at least / any step at most (the buckets to capture); total: the prompt
+    // tokens the passes may see at once.  0; -1: the columns do not fit the model; -2: a failure
+    int begin(int min_len, int max_keys, long total) {
+        const int P = ctx->hp.n_positions;
+        U = q.C; C = U * qc.per_unit;
+        if (C > hp_cols(ctx)) BG_FAIL(-1, "max_columns (%d) exceeds the %d activation columns of this model", C, hp_cols(ctx));
+        // (behind shared rows: they lie in one slot more, behind the units')
+        shared = SharedRows{rq.n_shared, rq.n_shared > 0 ? C : 0};
+        if (!begin_column_call(ctx, C + (shared.n > 0 ? 1 : 0), C, std::min<long>(total, P))) return -2;
+        ctx->xc_batch = 0;      // the steps are always the launch chain
+        if (!qc.prepare(U)) return -2;
+        column_graphs_for(*qc.graphs, U, qc.key_b);
+        // (ColumnKeys of a call whose first replayed step sees min_len keys and whose last one max_keys: every bucket a step here can be bounded by)
+        if (!capture_column_steps(ctx, *qc.graphs, qc.form, ColumnKeys{min_len - 1, 1, P}, max_keys - min_len + 2, qc.step, &use_graph)) return -2;
+        t0 = std::chrono::steady_clock::now();
+        if (shared.n > 0) {      // the shared rows, once: the prompt columns of one sequence in the slot behind the units'
+            const int32_t n = shared.n;
+            if (!pack_column_passes(ctx, rq.prefix, &n, 1, rq.n_batch, [&](int n_cols, int t_max, size_t) { return enqueue_forward(ctx, ForwardPass::packed_prompts(n_cols, t_max)); },
+                                    1, shared.slot))
+                return -2;
+            q.st.prompt_columns += n;
+        }
+        return 0;
     }
-    while (!q.done()) {
+
+    // one refill, one group, one look.  0, or -2: a failure
+    int turn() {
+        const int P = ctx->hp.n_positions;
+        const std::vector<int32_t> &cap = rq.cap;
         // ---- refill: the prompts of the admitted requests into the (first) slots of exactly their units, then the admit list and the mode's launches behind it ----
         flat.clear(); lens.clear(); slots.clear();
         const int n_admit = q.refill([&](int unit, int r) {
-            const int32_t *p = rq.prompts + rq.off[(size_t)r];
+            const int32_t *p = rq.prompt(r);
             const int own = rq.pos0 - shared.n, len = own + rq.prompt_lens[r];      // behind a prefix: its rows that are not shared, then the suffix (never empty)
             qc.admit(unit, r, (int)slots.size());
             if (own > 0) flat.insert(flat.end(), rq.prefix + shared.n, rq.prefix + rq.pos0);
@@ -4825,7 +4963,8 @@ static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc)
             if (!qc.enqueue_admit(n_admit)) return -2;
         }
         // ---- one group of steps ----
-        for (int g = q.group_steps(); g > 0; g--) {
+        const int n_steps = q.group_steps();
+        for (int g = n_steps; g > 0; g--) {
             int t_max = 1;
             for (int unit = 0; unit < U; unit++)
                 if (q.req[(size_t)unit] >= 0) t_max = std::max(t_max, q.position(unit, rq.whole_len(q.req[(size_t)unit])) + 1);
@@ -4840,12 +4979,14 @@ static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc)
             q.step();
         }
         q.end_group();
+        if (qc.after_group && !qc.after_group(n_steps)) return -2;
         // ---- the look at the units: the header behind the group (lag 0) ----
         HIP_TRY(-2, hipMemcpyAsync(qc.hdr_host, qc.hdr_dev, qc.hdr_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(-2, hipEventRecord(ctx->live_ev[0], ctx->stream));
         HIP_TRY(-2, hipEventSynchronize(ctx->live_ev[0]));
         // (the copies of the look before stand in front of this header in the stream: they have arrived)
         if (qc.landed && !qc.landed()) return -2;
+        if (qc.looked && !qc.looked()) return -2;
         for (int unit = 0; unit < U; unit++) {
             if (!q.live[(size_t)unit]) continue;
             const int r = q.req[(size_t)unit];
@@ -4854,18 +4995,54 @@ static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc)
                     BG_FAIL(-2, "internal: request %d (%s %d) is unfinished after %d steps, its limit is %d", r, qc.unit, unit, q.since[(size_t)unit], cap[(size_t)r]);
                 continue;
             }
-            const int len = qc.collect(unit, r);      // in stream order before the unit is reused
+            const int len = qc.collect(unit, r);      // in stream order before the unit is reused; a session's collect retires the unit itself
             if (len < 0) return -2;
-            q.retire(unit, len);
+            if (q.live[(size_t)unit]) q.retire(unit, len);
         }
+        return 0;
     }
-    HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
-    const auto t1 = std::chrono::steady_clock::now();
-    if (qc.landed && !qc.landed()) return -2;
-    if (!xpipe_check(ctx)) return -2;
-    if (qc.seconds_out) *qc.seconds_out = std::chrono::duration<double>(t1 - t0).count();
+
+    // the stream drained; what the caller asked for of the timed span and the counts
+    int end() {
+        HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+        const auto t1 = std::chrono::steady_clock::now();
+        if (qc.landed && !qc.landed()) return -2;
+        if (!xpipe_check(ctx)) return -2;
+        if (qc.seconds_out) *qc.seconds_out = std::chrono::duration<double>(t1 - t0).count();
+        if (qc.stats) *qc.stats = q.st;
+        return 0;
+    }
+};
+
+// A closed call, for requests that passed their checks: the run driven to its end.  Returns 0 once every request has been served and the stream has drained,
+// or at once where no request may generate a token (nothing was touched); -1: the columns do not fit the model; -2: a failure.
+static int run_queue_call(biogpt_hip_ctx *ctx, QueueRequests &rq, QueueCall &qc) {
+    const int P = ctx->hp.n_positions, R = rq.n_requests;
+    // every request's own clamp; the buckets the steps can need
+    rq.cap.assign((size_t)R, 0);
+    int min_len = P, max_keys = 0;
+    long total = 0;
+    for (int r = 0; r < R; r++) {
+        rq.cap[(size_t)r] = std::min(rq.n_predicts ? rq.n_predicts[r] : rq.n_predict, P - rq.whole_len(r));
+        if (rq.cap[(size_t)r] <= 0) continue;
+        min_len = std::min(min_len, rq.whole_len(r)); max_keys = std::max(max_keys, rq.whole_len(r) + rq.cap[(size_t)r]);
+        total += rq.whole_len(r);
+    }
+    if (qc.out_admit_step) std::fill(qc.out_admit_step, qc.out_admit_step + R, -1);
+    if (qc.out_unit) std::fill(qc.out_unit, qc.out_unit + R, -1);
+    if (qc.seconds_out) *qc.seconds_out = 0.0;
+    QueueSchedule q(rq.cap, qc.max_units, rq.group);
     if (qc.stats) *qc.stats = q.st;
-    return 0;
+    if (q.C == 0) return 0;      // nobody has room for a token: nothing was touched
+    if (q.C * qc.per_unit > hp_cols(ctx)) BG_FAIL(-1, "max_columns (%d) exceeds the %d activation columns of this model", q.C * qc.per_unit, hp_cols(ctx));
+
+    XpCallScope xp_scope(ctx);
+    XcBatchScope xc_scope{ctx};
+    QueueRun run{ctx, rq, qc, q};
+    if (const int rc = run.begin(min_len, max_keys, total)) return rc;
+    while (!q.done())
+        if (const int rc = run.turn()) return rc;
+    return run.end();
 }
 
 // ---- generation over a queue: a unit is a column; sampling with each request's own generator (kernels_queue.hip.h) ------------------------------------
@@ -5093,6 +5270,8 @@ struct QueueReqBufs {
     bgk::SampleSeq *seq;        // [QUEUE_COLS]
     int32_t *limit;             // [QUEUE_COLS]
     bgk::QueueReqHdr *hdr;
+    uint8_t *stream;            // what queue_stream_kernel writes for a streaming session, at its largest (queue_stream_at): it lies right behind the header
+                                // and travels with it in one copy
     bgk::QueueReqRec *rec;      // [QUEUE_COLS]
     int32_t *prefix;            // [n_positions]
     int32_t *hist;              // [QUEUE_COLS][n_positions]
@@ -5102,10 +5281,23 @@ struct QueueReqBufs {
 static_assert(sizeof(biogpt_hip_request_params) == 72 && offsetof(biogpt_hip_request_params, rules) == 24 && offsetof(biogpt_hip_request_params, stop) == 56,
               "biogpt_hip_request_params as the bindings lay it out (RequestParams, biogpt.cpp_amd/__init__.py)");
 static size_t queue_req_stride(int n_own) { return (sizeof(bgk::QueueReqAdmit) + (size_t)n_own * 4 + 15) & ~(size_t)15; }
+// The block of a streaming session for C columns, windows of g entries and K alternatives (K < 0: no log-probabilities), on the device or in the pinned look
+struct QueueStreamBufs { bgk::QueueStreamOut out; size_t bytes; };
+static QueueStreamBufs queue_stream_at(uint8_t *base, int C, int g, int K) {
+    ByteLayout l;
+    QueueStreamBufs b{};
+    const size_t n = (size_t)C * (size_t)g;
+    b.out.n_gen = l.take<int32_t>(base, (size_t)C); b.out.ids = l.take<int32_t>(base, n);
+    if (K >= 0) { b.out.lp = l.take<float>(base, n); b.out.top_ids = l.take<int32_t>(base, n * (size_t)K); b.out.top_lp = l.take<float>(base, n * (size_t)K); }
+    b.bytes = l.bytes();
+    return b;
+}
+static_assert(sizeof(bgk::QueueReqHdr) % 16 == 0, "the stream block begins where the header ends");
 static QueueReqBufs queue_req_bufs_at(uint8_t *base, int P) {
     ByteLayout l;
     QueueReqBufs b{};
     b.seq = l.take<bgk::SampleSeq>(base, bgk::QUEUE_COLS); b.limit = l.take<int32_t>(base, bgk::QUEUE_COLS); b.hdr = l.take<bgk::QueueReqHdr>(base, 1);
+    b.stream = l.take<uint8_t>(base, queue_stream_at(nullptr, bgk::QUEUE_COLS, 64, bgk::GENLP_MAX_TOP).bytes);
     b.rec = l.take<bgk::QueueReqRec>(base, bgk::QUEUE_COLS); b.prefix = l.take<int32_t>(base, (size_t)P); b.hist = l.take<int32_t>(base, (size_t)bgk::QUEUE_COLS * P);
     b.admit = l.take<uint8_t>(base, (size_t)bgk::QUEUE_COLS * queue_req_stride(P));
     b.bytes = l.bytes();
@@ -5223,6 +5415,374 @@ int biogpt_hip_generate_queue_requests(biogpt_hip_ctx *ctx, const int32_t *prefi
     const ColumnQueueArgs a{prefix, n_prefix, prompts, prompt_lens, n_predicts, n_requests, n_predict, max_columns, group, n_batch, seeds,
                             out_ids, out_lens, out_admit_step, out_column, seconds_out, stats, logprobs};
     return with_xpipe_retry(ctx, 0, [&] { return generate_queue_requests_once(ctx, a, params, out_finish); });
+}
+
+// ---- queue sessions: submit, poll, stream and cancel while steps run (biogpt_hip_queue_open) -------------------------------------------------------------
+// biogpt_hip_generate_queue_requests turned inside out: the run (QueueRun) is begun at open and its columns, K / V slots and captured steps persist; a poll is
+// some turns of it; the schedule (QueueSessionSchedule) is fed between polls.  The steps, the admit kernel, the records and the device block are those of the
+// closed call (graphs_queue_req, queue_req_bufs_at), so a session and closed calls of the same shape share their captured steps.  What a session adds:
+//   the look    the pinned header of its own, with the stream block behind it where streaming is on: queue_stream_kernel runs behind every group and the block
+//               travels in the header's copy.  The host keeps, per request, how many tokens it has delivered, and takes the part of the window beyond.
+//   cancel      a running request: its column goes into a small pinned list, queue_cancel_kernel finishes it in front of the poll's first refill, and what it
+//               had is copied out as for a finished one -- the host knows its length, one token per step since its admission.
+//   events      what a poll delivers lies in blocks the session owns until the next poll: one per event, so a copy in flight never sees its target move.
+// A request's prompt and record are copied at submit and dropped at its admission; a few words per request stay for the session's life.
+struct QueueSessionEvent { int32_t id, kind, first, count, finish; size_t block; };
+struct QueueSessionWaiting { std::vector<int32_t> prompt; bgk::QueueReqRec rec; };
+
+struct biogpt_hip_queue_session {
+    biogpt_hip_ctx *ctx;                    // null: the context was freed under the session
+    biogpt_hip_queue_opts o{};
+    std::vector<int32_t> prefix;
+    int K = -1;                             // alternatives per token; -1: no log-probabilities
+    int P = 0, V = 0, max_len = 0, lp_stride = 0;
+    size_t stride = 0;                      // of an entry of the admit list
+    QueueSessionSchedule ss;
+    QueueRequests rq{};
+    QueueCall qc;
+    QueueRun run;
+    // per request: what waits for its admission; then what stays
+    std::vector<std::unique_ptr<QueueSessionWaiting>> waiting;
+    std::vector<const int32_t *> own;
+    std::vector<int32_t> lens, admit_step, column, sent;
+    std::vector<uint32_t> seeds;
+    // the device block and the pinned memory
+    QueueReqBufs qb{};
+    GenLpBufs lb{};
+    uint8_t *look = nullptr;                // pinned: QueueReqHdr, then the stream block
+    QueueStreamBufs sdev{}, shost{};
+    int32_t *cancel_host = nullptr, *cancel_dev = nullptr;
+    uint8_t *admit_host = nullptr;
+    // the events of the last poll
+    std::vector<QueueSessionEvent> evs;
+    std::vector<std::vector<uint8_t>> blocks;
+    std::vector<biogpt_hip_queue_event> out;
+    double seconds = 0.0;
+    bool failed = false;                    // a poll failed: the columns' state is unknown, only close is left
+
+    biogpt_hip_queue_session(biogpt_hip_ctx *c, int max_columns, int group) : ctx(c), ss(max_columns, group), run{c, rq, qc, ss.q} {}
+    const bgk::QueueReqHdr *hdr() const { return reinterpret_cast<const bgk::QueueReqHdr *>(look); }
+    size_t block_bytes(int count) const { return (size_t)count * 4 * (K >= 0 ? 2 + 2 * (size_t)K : 1); }
+    // an event with room for `count` tokens: ids, then lp, top_ids, top_lp
+    uint8_t *event(int id, int kind, int first, int count, int finish) {
+        blocks.emplace_back(std::max<size_t>(block_bytes(count), 4));
+        evs.push_back(QueueSessionEvent{id, kind, first, count, finish, blocks.size() - 1});
+        return blocks.back().data();
+    }
+    // what column col holds of its request, len tokens, into a block (in stream order before the column is reused)
+    bool copy_out(int col, uint8_t *to, int len) {
+        if (len <= 0) return true;
+        const size_t n = (size_t)len, k = K > 0 ? (size_t)K : 0, src = (size_t)col * (size_t)lp_stride;
+        HIP_TRY(false, hipMemcpyAsync(to, ctx->seq_gen + (size_t)col * P, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (K >= 0) {
+            HIP_TRY(false, hipMemcpyAsync(to + n * 4, lb.lp + src, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (k > 0) {
+                HIP_TRY(false, hipMemcpyAsync(to + n * 8, lb.top_ids + src * k, n * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(false, hipMemcpyAsync(to + n * 8 + n * k * 4, lb.top_lp + src * k, n * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+            }
+        }
+        return true;
+    }
+};
+
+static void queue_session_orphan(biogpt_hip_ctx *c) {
+    if (!c->session) return;
+    (void)hipStreamSynchronize(c->stream);
+    c->session->ctx = nullptr;
+    c->session = nullptr;
+}
+
+static void queue_session_release(biogpt_hip_queue_session *s) {
+    if (s->ctx) {
+        (void)hipSetDevice(s->ctx->device);
+        (void)hipStreamSynchronize(s->ctx->stream);
+        s->ctx->session = nullptr;
+    }
+    if (s->look) (void)hipHostFree(s->look);
+    if (s->cancel_host) (void)hipHostFree(s->cancel_host);
+    if (s->cancel_dev) (void)hipFree(s->cancel_dev);
+    delete s;
+}
+
+biogpt_hip_queue_session *biogpt_hip_queue_open(biogpt_hip_ctx *ctx, const biogpt_hip_queue_opts *opts) {
+    clear_error();
+    if (!opts) BG_FAIL(nullptr, "null argument: opts");
+    const biogpt_hip_queue_opts &o = *opts;
+    if (o.logprobs < -1 || o.logprobs > bgk::GENLP_MAX_TOP) BG_FAIL(nullptr, "logprobs must be -1 (none) or in [0, %d] (got %d)", bgk::GENLP_MAX_TOP, o.logprobs);
+    if (!o.prefix && o.n_prefix != 0) BG_FAIL(nullptr, "n_prefix must be 0 without a prefix (got %d)", o.n_prefix);
+    if (o.prefix && o.n_prefix < 1) BG_FAIL(nullptr, "n_prefix must be >= 1 (got %d)", o.n_prefix);
+    if (o.prefix && (o.max_columns < 1 || o.max_columns > bgk::QUEUE_COLS - 1))
+        BG_FAIL(nullptr, "max_columns must be in [1, %d] behind a prefix (got %d)", bgk::QUEUE_COLS - 1, o.max_columns);   // one slot holds the prefix
+    if (o.max_columns < 1 || o.max_columns > bgk::QUEUE_COLS) BG_FAIL(nullptr, "max_columns must be in [1, %d]", bgk::QUEUE_COLS);
+    if (o.group < 1 || o.group > 64) BG_FAIL(nullptr, "group must be in [1, 64]");
+    if (o.n_batch < 1) BG_FAIL(nullptr, "n_batch must be >= 1");
+    if (o.n_predict < 0) BG_FAIL(nullptr, "n_predict must be >= 0");
+    if (o.max_len < 0) BG_FAIL(nullptr, "max_len must be >= 0 (0: n_positions)");
+    if (!check_sample_values(o.top_k, o.top_p, o.temp, o.eos_id, -1)) return nullptr;
+    for (int i = 0; i < o.n_prefix; i++)
+        if (o.prefix[i] < 0) BG_FAIL(nullptr, "token id %d (prefix, position %d) out of range", o.prefix[i], i);
+    if (!ctx) BG_FAIL(nullptr, "null context");
+    if (!ctx->ready) BG_FAIL(nullptr, "model has no tensors loaded (empty model): cannot evaluate");
+    if (session_refuses(ctx)) return nullptr;
+    const int P = ctx->hp.n_positions, V = ctx->hp.n_vocab;
+    if (!check_sample_values(o.top_k, o.top_p, o.temp, o.eos_id, V)) return nullptr;
+    if (o.logprobs > V) BG_FAIL(nullptr, "logprobs (%d) exceeds n_vocab (%d)", o.logprobs, V);
+    if (o.n_prefix > P) BG_FAIL(nullptr, "n_prefix (%d) exceeds n_positions (%d)", o.n_prefix, P);
+    for (int i = 0; i < o.n_prefix; i++)
+        if (o.prefix[i] >= V) BG_FAIL(nullptr, "token id %d (prefix, position %d) out of range [0, %d)", o.prefix[i], i, V);
+    if (o.max_len > P) BG_FAIL(nullptr, "max_len (%d) exceeds n_positions (%d)", o.max_len, P);
+    const int max_len = o.max_len > 0 ? o.max_len : P, first_len = std::max(1, (int)o.n_prefix);
+    if (max_len < first_len + 1) BG_FAIL(nullptr, "max_len (%d) leaves no room for a token behind %d", max_len, first_len);
+    if (!check_fast_chain(ctx, "a queue session")) return nullptr;
+
+    biogpt_hip_queue_session *s = new biogpt_hip_queue_session(ctx, o.max_columns, o.group);
+    s->o = o; s->o.prefix = nullptr;
+    s->prefix.assign(o.prefix, o.prefix + o.n_prefix);
+    s->K = o.logprobs; s->P = P; s->V = V; s->max_len = max_len; s->lp_stride = std::max(1, std::min((int)o.n_predict, P));
+    QueueRequests &rq = s->rq;
+    rq.prompts = nullptr; rq.prompt_lens = nullptr; rq.n_requests = 0; rq.n_predicts = nullptr;
+    rq.n_predict = o.n_predict; rq.max_columns = o.max_columns; rq.group = o.group; rq.n_batch = o.n_batch;
+    rq.prefix = s->prefix.empty() ? nullptr : s->prefix.data(); rq.pos0 = o.n_prefix;
+    rq.n_shared = rq.prefix ? (rq.pos0 - 1) / o.n_batch * o.n_batch : 0;
+    const int n_shared = rq.n_shared;
+    QueueCall &qc = s->qc;
+    qc.max_units = o.max_columns;
+    qc.graphs = &ctx->graphs_queue_req; qc.form.lp = s->K >= 0; qc.form.shared = n_shared > 0;
+    qc.prepare = [s, ctx](int units) -> bool {
+        const int P = s->P;
+        if (s->K >= 0 && (!genlp_prepare(ctx, &s->lb) || !genlp_upload(s->lb, s->K, s->lp_stride))) return false;
+        s->stride = queue_req_stride(s->max_len);
+        if (!ctx->queue_req_buf) HIP_TRY(false, hipMalloc(&ctx->queue_req_buf, queue_req_bufs_at(nullptr, P).bytes));
+        if (!ctx->queue_req_host) HIP_TRY(false, hipHostMalloc(&ctx->queue_req_host, sizeof(bgk::QueueReqHdr) + (size_t)bgk::QUEUE_COLS * queue_req_stride(P)));
+        s->qb = queue_req_bufs_at(ctx->queue_req_buf, P);
+        s->admit_host = ctx->queue_req_host + sizeof(bgk::QueueReqHdr);
+        const int g = s->o.stream ? s->o.group : 0;
+        s->sdev = queue_stream_at(s->qb.stream, units, g, s->K);
+        const size_t look_bytes = sizeof(bgk::QueueReqHdr) + (g > 0 ? s->sdev.bytes : 0);
+        HIP_TRY(false, hipHostMalloc(&s->look, look_bytes));
+        std::memset(s->look, 0, look_bytes);
+        s->shost = queue_stream_at(s->look + sizeof(bgk::QueueReqHdr), units, g, s->K);
+        HIP_TRY(false, hipHostMalloc(&s->cancel_host, sizeof(int32_t) * bgk::QUEUE_COLS));
+        HIP_TRY(false, hipMalloc(&s->cancel_dev, sizeof(int32_t) * bgk::QUEUE_COLS));
+        s->qc.admit_dev = s->qb.admit; s->qc.admit_host = s->admit_host; s->qc.admit_bytes = s->stride;
+        s->qc.hdr_dev = s->qb.hdr; s->qc.hdr_host = s->look; s->qc.hdr_bytes = look_bytes; s->qc.fin = s->hdr()->q.fin;
+        // the prefix the rules read; nobody runs yet
+        if (!s->prefix.empty()) HIP_TRY(false, hipMemcpy(s->qb.prefix, s->prefix.data(), s->prefix.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(false, hipMemset(s->qb.hdr, 0, sizeof(bgk::QueueReqHdr)));
+        return true;
+    };
+    qc.step = [s, ctx, n_shared](int t_max) -> bool {
+        if (!enqueue_forward(ctx, n_shared > 0 ? ForwardPass::decode_step_shared(s->run.U, t_max, n_shared) : ForwardPass::decode_step(s->run.U, t_max))) return false;
+        enqueue_queue_req_rows(ctx->stream, s->run.U, ctx->logits_all, s->V, s->qb, ctx->seq, ctx->seq_gen, s->P, s->P, s->K >= 0 ? &s->lb : nullptr);
+        HIP_TRY(false, hipGetLastError());
+        return true;
+    };
+    qc.admit = [s, n_shared](int col, int r, int i) {      // the state of the whole sequence at its last token: the suffix's, or the prefix's behind an empty one
+        const QueueSessionWaiting &w = *s->waiting[(size_t)r];
+        const int len = s->lens[(size_t)r];
+        bgk::QueueReqAdmit *e = reinterpret_cast<bgk::QueueReqAdmit *>(s->admit_host + (size_t)i * s->stride);
+        bgk::QueueAdmit rec{};
+        rec.col = col; rec.last_token = len > 0 ? w.prompt[(size_t)len - 1] : s->prefix.back(); rec.len = s->rq.whole_len(r);
+        rec.limit = s->rq.cap[(size_t)r]; rec.seed = s->seeds[(size_t)r];
+        rec.n_shared = n_shared; rec.shared_slot = n_shared > 0 ? s->run.U : 0;
+        e->a = rec;
+        e->rec = w.rec;
+        std::memcpy(e + 1, w.prompt.data(), (size_t)len * 4);
+        s->admit_step[(size_t)r] = s->ss.q.st.steps; s->column[(size_t)r] = col;
+        s->ss.admitted(r);
+    };
+    qc.enqueue_admit = [s, ctx](int n_admit) -> bool {
+        hipLaunchKernelGGL(bgk::queue_req_admit_kernel, dim3(n_admit), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream, s->qb.admit, (int)s->stride, s->qb.seq, ctx->seq, s->qb.limit,
+                           s->qb.hdr, s->qb.rec, s->qb.hist, s->P);
+        HIP_TRY(false, hipGetLastError());
+        // (the passes and the list's copy read the prompts of the admitted requests when they were enqueued: nothing waits for them any more)
+        for (int col = 0; col < s->run.U; col++)
+            if (s->ss.q.live[(size_t)col] && s->ss.q.since[(size_t)col] == 0) { const int r = s->ss.q.req[(size_t)col]; s->waiting[(size_t)r].reset(); s->own[(size_t)r] = nullptr; }
+        return true;
+    };
+    if (o.stream) {
+        qc.after_group = [s, ctx](int) -> bool {
+            hipLaunchKernelGGL(bgk::queue_stream_kernel, dim3(s->run.U), dim3(bgk::QUEUE_STREAM_THREADS), 0, ctx->stream, ctx->seq, ctx->seq_gen, s->P, s->run.U, (int)s->o.group,
+                               s->sdev.out, s->K >= 0 ? s->lb.lp : nullptr, s->K >= 0 ? s->lb.top_ids : nullptr, s->K >= 0 ? s->lb.top_lp : nullptr, s->lp_stride,
+                               std::max(s->K, 0));
+            HIP_TRY(false, hipGetLastError());
+            return true;
+        };
+        qc.looked = [s]() -> bool {      // per running request, the tokens behind what it has been sent
+            const QueueSchedule &q = s->ss.q;
+            const int G = s->o.group;
+            const size_t k = s->K > 0 ? (size_t)s->K : 0;
+            for (int col = 0; col < s->run.U; col++) {
+                if (!q.live[(size_t)col]) continue;
+                const int r = q.req[(size_t)col];
+                const int n = std::max(0, std::min(s->shost.out.n_gen[col], s->rq.cap[(size_t)r])), first = s->sent[(size_t)r], count = n - first, w = std::min(G, n);
+                if (count <= 0) continue;
+                const int at = first - (n - w);
+                if (at < 0) BG_FAIL(false, "internal: request %d (column %d) appended %d tokens in one group of at most %d steps", r, col, count, G);
+                uint8_t *to = s->event(r, 0, first, count, -1);
+                const size_t c4 = (size_t)count * 4, from = (size_t)col * (size_t)G + (size_t)at;
+                std::memcpy(to, s->shost.out.ids + from, c4);
+                if (s->K >= 0) {
+                    std::memcpy(to + c4, s->shost.out.lp + from, c4);
+                    std::memcpy(to + 2 * c4, s->shost.out.top_ids + from * k, c4 * k);
+                    std::memcpy(to + 2 * c4 + c4 * k, s->shost.out.top_lp + from * k, c4 * k);
+                }
+                s->sent[(size_t)r] = n;
+            }
+            return true;
+        };
+    }
+    qc.collect = [s](int col, int r) -> int {
+        const int len = std::max(0, std::min(s->hdr()->q.len[col], s->rq.cap[(size_t)r]));
+        uint8_t *to = s->event(r, 1, 0, len, s->hdr()->reason[col]);
+        if (!s->copy_out(col, to, len)) return -1;
+        s->ss.finished(col, r, len);
+        return len;
+    };
+
+    XpCallScope xp_scope(ctx);
+    XcBatchScope xc_scope{ctx};
+    const auto t0 = std::chrono::steady_clock::now();
+    if (s->run.begin(first_len, max_len, P) != 0 || hipStreamSynchronize(ctx->stream) != hipSuccess || !xpipe_check(ctx)) {
+        const std::string why = last_error();
+        queue_session_release(s);
+        BG_FAIL(nullptr, "%s", why.empty() ? "a queue session could not be opened" : why.c_str());
+    }
+    if (n_shared > 0) s->seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();      // (the shared rows belong to the timed span)
+    ctx->session = s;
+    return s;
+}
+
+static bool queue_session_usable(biogpt_hip_queue_session *s) {
+    if (!s) BG_FAIL(false, "null queue session");
+    if (!s->ctx) BG_FAIL(false, "the queue session's context has been freed: only biogpt_hip_queue_close is left");
+    if (s->failed) BG_FAIL(false, "the queue session failed in an earlier poll: only biogpt_hip_queue_close is left");
+    return true;
+}
+
+int biogpt_hip_queue_submit(biogpt_hip_queue_session *s, const int32_t *prompt, int32_t len, int32_t n_predict, uint32_t seed, const biogpt_hip_request_params *params) {
+    clear_error();
+    if (!queue_session_usable(s)) return -1;
+    const int id = s->ss.q.known, pos0 = s->rq.pos0;
+    if (len < 0) BG_FAIL(-1, "len (%d) is negative", len);
+    if (len > 0 && !prompt) BG_FAIL(-1, "null argument: prompt");
+    if (len < 1 && pos0 == 0) BG_FAIL(-1, "empty prompt (request %d)", id);      // (behind a prefix no sequence is empty)
+    if (n_predict < 0 || n_predict > s->o.n_predict) BG_FAIL(-1, "n_predict (%d) must be in [0, the session's n_predict = %d]", n_predict, s->o.n_predict);
+    biogpt_hip_request_params def{};
+    def.top_k = s->o.top_k; def.eos_id = s->o.eos_id; def.top_p = s->o.top_p; def.temp = s->o.temp; def.rules.repetition_penalty = 1.0f;
+    const biogpt_hip_request_params &p = params ? *params : def;
+    if (!check_request_params(p, id, -1, -1) || !check_request_params(p, id, s->V, s->P)) return -1;
+    if (s->K >= 0 && rules_active(&p.rules, p.eos_id))
+        BG_FAIL(-1, "logprobs with generation rules (params of request %d have a rule switched on): no closed call returns log-probabilities under rules", id);
+    if (len > s->P - pos0) BG_FAIL(-1, "n_prefix (%d) + len (%d) exceeds n_positions (%d)", pos0, len, s->P);
+    for (int i = 0; i < len; i++)
+        if (prompt[i] < 0 || prompt[i] >= s->V) BG_FAIL(-1, "token id %d (request %d, position %d) out of range [0, %d)", prompt[i], id, i, s->V);
+    const int whole = pos0 + len, cap = std::min((int)n_predict, s->P - whole);
+    if (cap > 0 && whole + cap > s->max_len)
+        BG_FAIL(-1, "request %d needs %d keys (%d tokens and %d to generate): more than the session's max_len (%d), for which its steps were captured", id, whole + cap, whole, cap, s->max_len);
+    std::unique_ptr<QueueSessionWaiting> w;
+    if (cap > 0) {
+        w.reset(new QueueSessionWaiting{std::vector<int32_t>(prompt, prompt + len), request_rec_of(p, pos0, len)});
+    }
+    s->own.push_back(w ? w->prompt.data() : nullptr);
+    s->waiting.push_back(std::move(w));
+    s->lens.push_back(len); s->admit_step.push_back(-1); s->column.push_back(-1); s->sent.push_back(0); s->seeds.push_back(seed);
+    s->rq.cap.push_back(std::max(cap, 0));      // (the driver's copy of the clamp the schedule holds)
+    const int r = s->ss.submit(cap);
+    s->rq.n_requests = s->ss.q.known; s->rq.prompt_lens = s->lens.data(); s->rq.own = s->own.data();
+    return r;
+}
+
+int biogpt_hip_queue_cancel(biogpt_hip_queue_session *s, int32_t id) {
+    clear_error();
+    if (!queue_session_usable(s)) return -1;
+    const int rc = s->ss.cancel(id);
+    if (rc == -1) BG_FAIL(-1, "no request %d in this queue session (%d submitted)", id, s->ss.q.known);
+    if (rc == -2) BG_FAIL(-1, "request %d has finished or was cancelled already", id);
+    return 0;
+}
+
+int biogpt_hip_queue_poll(biogpt_hip_queue_session *s, int32_t max_groups, const biogpt_hip_queue_event **events_out) {
+    clear_error();
+    if (!queue_session_usable(s)) return -1;
+    if (max_groups < 0) BG_FAIL(-1, "max_groups must be >= 0");
+    if (!events_out) BG_FAIL(-1, "null argument: events_out");
+    biogpt_hip_ctx *ctx = s->ctx;
+    QueueSchedule &q = s->ss.q;
+    s->evs.clear(); s->blocks.clear(); s->out.clear();
+    *events_out = nullptr;
+    s->rq.prompt_lens = s->lens.data(); s->rq.own = s->own.data();
+    bool ok = true, enqueued = false;
+    int n_stop = 0;
+    std::vector<std::pair<int, size_t>> stopped;      // the columns of the cancelled running requests, each with its event
+    s->ss.begin_poll([&](int r) { s->event(r, 1, 0, 0, -1); },
+                     [&](int r) { s->event(r, 2, 0, 0, -1); s->waiting[(size_t)r].reset(); s->own[(size_t)r] = nullptr; },
+                     [&](int col, int r, int len) {
+                         s->cancel_host[n_stop++] = col;
+                         s->event(r, 2, 0, std::min(len, s->rq.cap[(size_t)r]), -1);
+                         stopped.emplace_back(col, s->evs.size() - 1);
+                     });
+    if (!q.done() || n_stop > 0) {      // (nothing runs and nothing waits: no launch)
+        HIP_TRY(-2, hipSetDevice(ctx->device));
+        XpCallScope xp_scope(ctx);
+        XcBatchScope xc_scope{ctx};
+        const auto t0 = std::chrono::steady_clock::now();
+        s->run.use_graph = s->run.use_graph && plain_graph_begin(ctx);      // (another context may have taken the pipeline slot since: eager launches from then on)
+        if (n_stop > 0) {
+            ok = hipMemcpyAsync(s->cancel_dev, s->cancel_host, (size_t)n_stop * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+            if (ok) {
+                hipLaunchKernelGGL(bgk::queue_cancel_kernel, dim3((n_stop + bgk::QUEUE_ADMIT_THREADS - 1) / bgk::QUEUE_ADMIT_THREADS), dim3(bgk::QUEUE_ADMIT_THREADS), 0, ctx->stream,
+                                   s->cancel_dev, n_stop, s->qb.seq, ctx->seq, &s->qb.hdr->q);
+                ok = hipGetLastError() == hipSuccess;
+            }
+            for (const auto &st : stopped)
+                if (ok) ok = s->copy_out(st.first, s->blocks[s->evs[st.second].block].data(), s->evs[st.second].count);
+            if (!ok && last_error()[0] == 0) bg::set_error("biogpt_hip_queue_poll", "a cancel could not be enqueued");
+            enqueued = true;
+        }
+        for (int n = 0; ok && n < max_groups && !q.done(); n++) { ok = s->run.turn() == 0; enqueued = true; }
+        if (enqueued && hipStreamSynchronize(ctx->stream) != hipSuccess && ok) { ok = false; bg::set_error("biogpt_hip_queue_poll", "the stream could not be drained"); }
+        if (ok && enqueued && !xpipe_check(ctx)) ok = false;
+        s->seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (!ok) { s->failed = true; return -2; }
+    const size_t k = s->K > 0 ? (size_t)s->K : 0;
+    for (const QueueSessionEvent &e : s->evs) {
+        biogpt_hip_queue_event ev{};
+        const uint8_t *b = s->blocks[e.block].data();
+        const size_t c4 = (size_t)e.count * 4;
+        ev.id = e.id; ev.kind = e.kind; ev.first = e.first; ev.count = e.count; ev.finish = e.finish;
+        ev.admit_step = s->admit_step[(size_t)e.id]; ev.column = s->column[(size_t)e.id];
+        ev.n_top = s->K;
+        ev.ids = reinterpret_cast<const int32_t *>(b);
+        if (s->K >= 0) {
+            ev.lp = reinterpret_cast<const float *>(b + c4);
+            ev.top_ids = reinterpret_cast<const int32_t *>(b + 2 * c4);
+            ev.top_lp = reinterpret_cast<const float *>(b + 2 * c4 + c4 * k);
+        }
+        s->out.push_back(ev);
+    }
+    *events_out = s->out.data();
+    return (int)s->out.size();
+}
+
+int biogpt_hip_queue_session_stats(const biogpt_hip_queue_session *s, biogpt_hip_queue_stats *stats, double *seconds_out, int32_t *counts_out) {
+    clear_error();
+    if (!s) BG_FAIL(-1, "null queue session");
+    if (!stats) BG_FAIL(-1, "null argument: stats");
+    *stats = s->ss.q.st;
+    if (seconds_out) *seconds_out = s->seconds;
+    if (counts_out) { counts_out[0] = s->ss.q.known; counts_out[1] = s->ss.q.pending; counts_out[2] = s->ss.q.running; }
+    return 0;
+}
+
+int biogpt_hip_queue_close(biogpt_hip_queue_session *s) {
+    clear_error();
+    if (!s) BG_FAIL(-1, "null queue session");
+    biogpt_hip_ctx *ctx = s->ctx;
+    queue_session_release(s);      // (requests still running are dropped with their columns' state: the next call's admit kernel or upload sets its own)
+    if (ctx) (void)xpipe_check(ctx);
+    return 0;
 }
 
 // ---- beam search over a queue: a unit is a group slot of B columns; finished searches hand their slot on (kernels_beam_queue.hip.h) ------------------

@@ -1018,6 +1018,92 @@ int biogpt_hip_queue_req_rows_device(int device, int32_t with_lp, const float *r
     return queue_probe_run(a, m);
 }
 
+// ---- the two kernels of a queue session alone (kernels_queue.hip.h) ----
+// queue_stream_kernel over constructed columns: column c has generated n_gen[c] tokens (any value: the kernel clamps it to gen_stride), its seq_gen row is row c
+// of gen_rows [C][gen_stride], and with n_top >= 0 its rows of the log-probability block are lp [C][lp_stride], top_ids / top_lp [C][lp_stride][n_top].  block_out
+// [block_bytes] is what lies behind a session's header -- queue_stream_at(C, g, n_top): n_gen [C], ids [C][g], then lp [C][g] and top_ids / top_lp [C][g][n_top],
+// every part at a multiple of 16 bytes -- preset to 0xff bytes, so the padding between the parts and whatever lies behind the last one come back as they were.
+// Returns the bytes of the layout, < 0 on error.
+int64_t biogpt_hip_queue_stream_device(int device, const int32_t *n_gen, const int32_t *gen_rows, int32_t C, int32_t gen_stride, int32_t g, int32_t n_top, int32_t lp_stride,
+                                       const float *lp, const int32_t *top_ids, const float *top_lp, uint8_t *block_out, int64_t block_bytes) {
+    clear_error();
+    if (!n_gen) BG_FAIL(-1, "n_gen is NULL");
+    if (!gen_rows) BG_FAIL(-1, "gen_rows is NULL");
+    if (!block_out) BG_FAIL(-1, "block_out is NULL");
+    if (C < 1 || C > bgk::QUEUE_COLS) BG_FAIL(-1, "C must be in [1, %d]", bgk::QUEUE_COLS);
+    if (gen_stride < 1 || gen_stride > 4096) BG_FAIL(-1, "gen_stride must be in [1, 4096]");
+    if (g < 1 || g > 64) BG_FAIL(-1, "g must be in [1, 64]");
+    if (n_top < -1 || n_top > bgk::GENLP_MAX_TOP) BG_FAIL(-1, "n_top must be -1 (no log-probabilities) or in [0, %d]", bgk::GENLP_MAX_TOP);
+    if (n_top >= 0 && (lp_stride < 1 || lp_stride > gen_stride)) BG_FAIL(-1, "lp_stride must be in [1, gen_stride]");
+    if (n_top >= 0 && !lp) BG_FAIL(-1, "lp is NULL");
+    if (n_top > 0 && (!top_ids || !top_lp)) BG_FAIL(-1, "top_ids or top_lp is NULL with n_top = %d", n_top);
+    const size_t need = queue_stream_at(nullptr, C, g, n_top).bytes;
+    if (block_bytes < (int64_t)need) BG_FAIL(-1, "block_bytes (%lld) is below the %zu bytes of the layout", (long long)block_bytes, need);
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t rows = (size_t)C * (size_t)gen_stride, entries = n_top >= 0 ? (size_t)C * (size_t)lp_stride : 0, k = n_top > 0 ? (size_t)n_top : 0;
+    std::vector<bgk::SeqState> st((size_t)C);
+    for (int c = 0; c < C; c++) { st[(size_t)c] = bgk::SeqState{}; st[(size_t)c].n_gen = n_gen[c]; st[(size_t)c].seq_id = c; }
+    ByteLayout l;
+    const size_t o_st = l.part(sizeof(bgk::SeqState) * (size_t)C), o_gen = l.part(rows * 4), o_lp = l.part(entries * 4), o_ti = l.part(entries * k * 4), o_tl = l.part(entries * k * 4),
+                 o_out = l.part((size_t)block_bytes);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemcpy(d.p + o_st, st.data(), sizeof(bgk::SeqState) * (size_t)C, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_gen, gen_rows, rows * 4, hipMemcpyHostToDevice));
+    if (entries > 0) HIP_TRY(-2, hipMemcpy(d.p + o_lp, lp, entries * 4, hipMemcpyHostToDevice));
+    if (entries * k > 0) {
+        HIP_TRY(-2, hipMemcpy(d.p + o_ti, top_ids, entries * k * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_tl, top_lp, entries * k * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, (size_t)block_bytes));
+    const QueueStreamBufs sb = queue_stream_at(d.p + o_out, C, g, n_top);
+    hipLaunchKernelGGL(bgk::queue_stream_kernel, dim3(C), dim3(bgk::QUEUE_STREAM_THREADS), 0, 0, d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_gen), gen_stride, C, g, sb.out,
+                       n_top >= 0 ? d.at<float>(o_lp) : nullptr, n_top >= 0 ? d.at<int32_t>(o_ti) : nullptr, n_top >= 0 ? d.at<float>(o_tl) : nullptr, lp_stride, (int)k);
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(block_out, d.p + o_out, (size_t)block_bytes, hipMemcpyDeviceToHost));
+    return (int64_t)need;
+}
+
+// queue_cancel_kernel on the list cols [n] over QUEUE_COLS constructed columns.  In and out: finished [512] (SampleSeq::finished) and hdr [1 + 2 * 512] (n_live,
+// fin[], len[]); n_gen [512] is read.  Returns 0, < 0 on error.
+int biogpt_hip_queue_cancel_device(int device, const int32_t *cols, int32_t n, int32_t *finished, const int32_t *n_gen, int32_t *hdr) {
+    clear_error();
+    if (!cols) BG_FAIL(-1, "cols is NULL");
+    if (!finished) BG_FAIL(-1, "finished is NULL");
+    if (!n_gen) BG_FAIL(-1, "n_gen is NULL");
+    if (!hdr) BG_FAIL(-1, "hdr is NULL");
+    if (n < 1 || n > bgk::QUEUE_COLS) BG_FAIL(-1, "n must be in [1, %d]", bgk::QUEUE_COLS);
+    HIP_TRY(-2, hipSetDevice(device));
+    constexpr int Q = bgk::QUEUE_COLS;
+    std::vector<bgk::SampleSeq> sq((size_t)Q);
+    std::vector<bgk::SeqState> st((size_t)Q);
+    bgk::QueueHdr h{};
+    h.n_live = hdr[0];
+    for (int c = 0; c < Q; c++) {
+        sq[(size_t)c] = bgk::SampleSeq{}; sq[(size_t)c].finished = finished[c];
+        st[(size_t)c] = bgk::SeqState{}; st[(size_t)c].n_gen = n_gen[c];
+        h.fin[c] = hdr[1 + c]; h.len[c] = hdr[1 + Q + c];
+    }
+    ByteLayout l;
+    const size_t o_sq = l.part(sizeof(bgk::SampleSeq) * Q), o_st = l.part(sizeof(bgk::SeqState) * Q), o_h = l.part(sizeof(h)), o_c = l.part((size_t)n * 4);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemcpy(d.p + o_sq, sq.data(), sizeof(bgk::SampleSeq) * Q, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_st, st.data(), sizeof(bgk::SeqState) * Q, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_h, &h, sizeof(h), hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_c, cols, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(bgk::queue_cancel_kernel, dim3((n + bgk::QUEUE_ADMIT_THREADS - 1) / bgk::QUEUE_ADMIT_THREADS), dim3(bgk::QUEUE_ADMIT_THREADS), 0, 0, d.at<int32_t>(o_c), n,
+                       d.at<bgk::SampleSeq>(o_sq), d.at<bgk::SeqState>(o_st), d.at<bgk::QueueHdr>(o_h));
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    HIP_TRY(-2, hipMemcpy(sq.data(), d.p + o_sq, sizeof(bgk::SampleSeq) * Q, hipMemcpyDeviceToHost));
+    HIP_TRY(-2, hipMemcpy(&h, d.p + o_h, sizeof(h), hipMemcpyDeviceToHost));
+    hdr[0] = h.n_live;
+    for (int c = 0; c < Q; c++) { finished[c] = sq[(size_t)c].finished; hdr[1 + c] = h.fin[c]; hdr[1 + Q + c] = h.len[c]; }
+    return 0;
+}
+
 // SURVEY 8 f1 on the device: `nrows` rows of `k` f32 values (host memory) -> the file's block format of `type`, byte-identical to
 // the host quantizer (biogpt_hip_quantize_file uses the host one: it has to work without a GPU)
 int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, int64_t nrows, int64_t k, uint8_t *dst) {

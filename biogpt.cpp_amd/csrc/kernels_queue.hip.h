@@ -209,4 +209,59 @@ __global__ __launch_bounds__(QUEUE_ADMIT_THREADS) void queue_req_admit_kernel(co
     if (threadIdx.x == 0) hdr->reason[a.col] = 0;
 }
 
+// ---- queue sessions (biogpt_hip_queue_open): what a look carries while steps run, and a way out of a running column --------------------------------------
+// queue_stream_kernel   launched once behind a group of g steps of a streaming session.  Stateless: for column c it writes n_gen[c] (clamped to gen_stride) and
+//                       the LAST w = min(g, n_gen[c]) entries of the column's seq_gen row into row c of a compact [C][g] block that lies behind the header and
+//                       travels with it; the entries behind w read -1.  With log-probabilities the same window of the column's lp / top_ids / top_lp rows
+//                       (0 / -1 / 0 behind w, and for an entry past the rows' stride, which genlp_write never wrote).  A column appends at most g tokens in g
+//                       steps, so the window always holds what the host has not delivered yet -- the host knows how many tokens of a request it has
+//                       delivered and takes the part beyond -- and a column refilled in between needs no reset.
+// queue_cancel_kernel   one thread per entry of a small uploaded list of columns: a column that has not finished is finished in the words of queue_report
+//                       (finished = 1, fin = 1, len = n_gen, n_live one less), so the step kernels return early on it from the next group on.  An entry out
+//                       of range, or a column that has finished already, changes nothing; an entry named twice counts once (atomicExch on the flag).
+constexpr int QUEUE_STREAM_THREADS = 64;
+
+struct QueueStreamOut {
+    int32_t *n_gen;       // [C]
+    int32_t *ids;         // [C][g]
+    float *lp;            // [C][g], or null: no log-probabilities
+    int32_t *top_ids;     // [C][g][K]
+    float *top_lp;        // [C][g][K]
+};
+
+// grid (C), QUEUE_STREAM_THREADS threads.  src_*: the log-probability block the selection writes, [columns][lp_stride] and [columns][lp_stride][K]
+__global__ __launch_bounds__(QUEUE_STREAM_THREADS) void queue_stream_kernel(const SeqState *seq, const int32_t *seq_gen, int gen_stride, int C, int g, QueueStreamOut out,
+                                                                            const float *src_lp, const int32_t *src_top_ids, const float *src_top_lp, int lp_stride,
+                                                                            int K) {
+    const int col = blockIdx.x;
+    if (col >= C || col >= QUEUE_COLS || g < 1) return;      // (uniform)
+    const int n = max(0, min(seq[col].n_gen, gen_stride)), w = min(g, n);
+    if (threadIdx.x == 0) out.n_gen[col] = n;
+    const int32_t *gen = seq_gen + (size_t)col * gen_stride;
+    for (int j = threadIdx.x; j < g; j += QUEUE_STREAM_THREADS) out.ids[(size_t)col * g + j] = j < w ? gen[n - w + j] : -1;
+    if (out.lp == nullptr) return;      // (uniform)
+    for (int j = threadIdx.x; j < g; j += QUEUE_STREAM_THREADS) {
+        const int e = n - w + j;
+        const bool have = j < w && e < lp_stride;
+        const size_t at = (size_t)col * lp_stride + (have ? e : 0), to = (size_t)col * g + j;
+        out.lp[to] = have ? src_lp[at] : 0.0f;
+        for (int t = 0; t < K; t++) {
+            out.top_ids[to * K + t] = have ? src_top_ids[at * K + t] : -1;
+            out.top_lp[to * K + t] = have ? src_top_lp[at * K + t] : 0.0f;
+        }
+    }
+}
+
+// grid (ceil(n / QUEUE_ADMIT_THREADS)), QUEUE_ADMIT_THREADS threads; cols: [n]
+__global__ __launch_bounds__(QUEUE_ADMIT_THREADS) void queue_cancel_kernel(const int32_t *cols, int n, SampleSeq *sq, const SeqState *seq, QueueHdr *hdr) {
+    const int i = blockIdx.x * QUEUE_ADMIT_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int col = cols[i];
+    if (col < 0 || col >= QUEUE_COLS) return;
+    if (atomicExch(&sq[col].finished, 1) != 0) return;      // finished already: it was reported then
+    hdr->len[col] = seq[col].n_gen;
+    hdr->fin[col] = 1;
+    atomicSub(&hdr->n_live, 1);
+}
+
 }  // namespace bgk

@@ -871,6 +871,86 @@ int biogpt_hip_queue_req_rows_device(int device, int32_t with_lp, const float *r
                                      const int32_t *prompt_lens, uint32_t *mt_states, int32_t *states, const int32_t *limits, int32_t *finished, int32_t *hdr,
                                      int32_t *ids_out, float *lp_out, int32_t *top_ids_out, float *top_lp_out);
 
+/* ---- queue sessions: submit, poll, stream and cancel while steps run ----
+ * biogpt_hip_generate_queue_requests turned inside out, for a caller whose requests arrive over time: the session's columns, K / V slots and captured steps
+ * persist between calls, and the host submits a request, runs some groups of steps, reads what was produced and cancels a request, in any order.  One host
+ * thread drives a session.
+ *   Equality   Request r's ids, length, finish reason and log-probability rows are those of biogpt_hip_generate_queue_requests of r alone (so of
+ *              biogpt_hip_generate_sample* of r alone with its sampler and rules, cut behind its first complete stop sequence), bit for bit, whenever it was
+ *              submitted, whatever else is or was in the session and whatever max_columns and group are.
+ *   Schedule   Deterministic in steps, given the script of calls.  The session has max_columns columns from open on.  biogpt_hip_queue_poll(max_groups) runs
+ *              at most max_groups iterations of the closed call's loop: free columns are refilled in ascending order with the pending requests in submission
+ *              order; one group of min(group, the most steps any running request may still take) steps runs; the host takes one look at the header and
+ *              collects the finished columns.  Requests submitted between two polls are pending from the next poll's first refill on.  A poll with nothing
+ *              running and nothing pending launches nothing.  Where all R >= max_columns requests are submitted before the first poll, the results, admit
+ *              steps, columns and stats are those of biogpt_hip_generate_queue_requests with the same arguments.  biogpt_hip_queue_plan_script is the
+ *              same scheduler on a script with given lengths, without a device.
+ *   Events     A poll returns the events of its groups, in order, in memory the session owns until its next poll or its close.  kind 1 (finished): first 0,
+ *              count the request's length, ids (and with log-probabilities lp [count], top_ids / top_lp [count][n_top]) all it generated, finish 0 limit /
+ *              1 EOS / 2 + i stop sequence i.  A request that may not generate a token (n_predict 0, or no position left) is finished with count 0 at the
+ *              next poll and never takes a column; its finish, admit_step and column read -1.  kind 2 (cancelled): the same with what the request had.
+ *              kind 0 (delta), only with opts.stream: the tokens [first, first + count) a running request appended during one group; a request's deltas
+ *              are contiguous, together they are its final ids and rows, and none follows its finished event.
+ *   Cancel     A pending request is dropped at the next poll's start and never takes a column (cancelled, count 0).  A running request stops in front of
+ *              that poll's first group: its event carries the tokens it had, a prefix of what it would have produced, and its column is refilled at that
+ *              poll's first refill.  No other request's bits change.  An unknown id, or one that has finished or was cancelled, is an error (-1).
+ *   Exclusive  While a session is open every other evaluating call on its context fails with -1 before any launch, its message naming the open session.
+ *              biogpt_hip_queue_close with requests still running is legal and drops them; afterwards the context serves everything as before.
+ * opts: max_columns in [1, 512] (511 behind a prefix), group in [1, 64], n_batch >= 1, n_predict >= 0 the most any request may ask for, max_len (0:
+ * n_positions) the most keys any request may reach -- the steps are captured at open for every context bucket up to it, none inside a poll --, prefix /
+ * n_prefix (or NULL / 0) the shared prefix, logprobs -1 (none) or n_top in [0, 8], stream 0 / 1, and top_k / eos_id / top_p / temp the sampler of a request
+ * submitted without params.  biogpt_hip_queue_submit copies the prompt (the suffix behind a prefix, which may then be empty) and the parameters and returns the
+ * request's id, 0, 1, 2, ... in submission order; n_predict in [0, opts.n_predict], params (or NULL) as for biogpt_hip_generate_queue_requests, a rule under
+ * logprobs refused as there.  Argument errors return NULL / -1 before any HIP call, the message naming the field; those of opts that need no model come first,
+ * with no context and no device.  Needs the BioGPT-base fast chain (block-quantized weights).  A poll that fails (-2) leaves only the close. */
+typedef struct biogpt_hip_queue_session biogpt_hip_queue_session;
+typedef struct biogpt_hip_queue_opts {
+    int32_t max_columns, group, n_batch, n_predict;
+    int32_t max_len;                  /* 0: n_positions */
+    int32_t n_prefix;
+    const int32_t *prefix;            /* or NULL */
+    int32_t logprobs;                 /* -1: none; otherwise n_top */
+    int32_t stream;
+    int32_t top_k, eos_id;            /* the default sampler */
+    double  top_p, temp;
+} biogpt_hip_queue_opts;
+typedef struct biogpt_hip_queue_event {
+    int32_t id, kind;                 /* kind 0 delta, 1 finished, 2 cancelled */
+    int32_t first, count;
+    int32_t finish, admit_step, column, n_top;
+    const int32_t *ids;               /* [count] */
+    const float   *lp;                /* [count], or NULL without log-probabilities */
+    const int32_t *top_ids;           /* [count][n_top] */
+    const float   *top_lp;            /* [count][n_top] */
+} biogpt_hip_queue_event;
+
+biogpt_hip_queue_session *biogpt_hip_queue_open(biogpt_hip_ctx *ctx, const biogpt_hip_queue_opts *opts);
+int biogpt_hip_queue_submit(biogpt_hip_queue_session *session, const int32_t *prompt, int32_t len, int32_t n_predict, uint32_t seed,
+                            const biogpt_hip_request_params *params /* or NULL: the session's sampler */);
+int biogpt_hip_queue_cancel(biogpt_hip_queue_session *session, int32_t id);
+/* returns the number of events, *events_out the first; < 0 on error */
+int biogpt_hip_queue_poll(biogpt_hip_queue_session *session, int32_t max_groups, const biogpt_hip_queue_event **events_out);
+/* stats as biogpt_hip_generate_queue counts them, accumulated over the polls; seconds_out (may be NULL): the host time spent inside polls (and on the shared
+ * rows at open); counts_out (may be NULL) [3]: requests submitted, pending, running */
+int biogpt_hip_queue_session_stats(const biogpt_hip_queue_session *session, biogpt_hip_queue_stats *stats, double *seconds_out, int32_t *counts_out);
+int biogpt_hip_queue_close(biogpt_hip_queue_session *session);
+/* The session's scheduler alone, on the host, on a script: ops is [n_ops][2] = {kind, argument} with kind 0 SUBMIT (the i-th SUBMIT is request i: it
+ * generates gen_lens[i] tokens under the limit limits[i], as for biogpt_hip_queue_plan_limits), 1 POLL n, 2 CANCEL r (what a session refuses changes nothing).
+ * admit_step / column [requests]: as biogpt_hip_queue_plan, -1 where a request never took a column; finish_group [requests]: the groups run when the
+ * request's finished or cancelled event was produced, -1 where the script ends before; lens (may be NULL) [requests]: the tokens it had then.  Returns 0 or -1. */
+int biogpt_hip_queue_plan_script(const int32_t *ops, int32_t n_ops, const int32_t *gen_lens, const int32_t *limits, int32_t max_columns, int32_t group,
+                                 int32_t *admit_step, int32_t *column, int32_t *finish_group, int32_t *lens /* may be NULL */,
+                                 biogpt_hip_queue_stats *stats /* may be NULL */);
+/* Test hooks: the two kernels of a session alone (csrc/kernels_queue.hip.h).  queue_stream_kernel over constructed columns: column c has n_gen[c] generated
+ * tokens (any value: clamped to gen_stride), its token row is row c of gen_rows [C][gen_stride], with n_top >= 0 its log-probability rows are lp [C][lp_stride]
+ * and top_ids / top_lp [C][lp_stride][n_top].  block_out [block_bytes], preset to 0xff bytes, is what lies behind a streaming session's header: n_gen [C],
+ * ids [C][g], then lp [C][g], top_ids [C][g][n_top], top_lp [C][g][n_top], every part at a multiple of 16 bytes.  Returns the bytes of that layout, < 0 on error.
+ * queue_cancel_kernel on the list cols [n] over 512 constructed columns: finished [512] and hdr [1 + 2 * 512] (n_live, fin[], len[]) in and out, n_gen [512]
+ * read.  Returns 0, < 0 on error. */
+int64_t biogpt_hip_queue_stream_device(int device, const int32_t *n_gen, const int32_t *gen_rows, int32_t C, int32_t gen_stride, int32_t g, int32_t n_top,
+                                       int32_t lp_stride, const float *lp, const int32_t *top_ids, const float *top_lp, uint8_t *block_out, int64_t block_bytes);
+int biogpt_hip_queue_cancel_device(int device, const int32_t *cols, int32_t n, int32_t *finished, const int32_t *n_gen, int32_t *hdr);
+
 /* ---- hidden states, pooled embeddings, classification heads (no counterpart in the reference) ----
  * The activations in front of the lm_head, from the causal passes of biogpt_hip_score without the lm_head and the log-softmax.
  *
