@@ -455,6 +455,41 @@ __device__ __forceinline__ uint32_t xp_wave_sum_u32(uint32_t v) {
     return (uint32_t)((__builtin_amdgcn_readlane(s, 0) + __builtin_amdgcn_readlane(s, 16)) + (__builtin_amdgcn_readlane(s, 32) + __builtin_amdgcn_readlane(s, 48)));
 }
 
+// PV over the first n (wave-uniform) of a wave's NV key slots, in slot order: slot K's value row element vr[K] times its softmax weight (lane K of wv, or with
+// STEP != 0 lane lane0 + STEP K, taken as a wave-uniform operand) goes into a0 (K even) or a1 (K odd).  Nested scalar branches instead of a loop with an exit
+// (the compiler does not unroll a loop with a run-time exit around v_readlane, and re-rolled it indexes vr[] dynamically): whole groups of four slots first
+// -- four independent products in flight, two additions per accumulator -- then the up to three slots that are left, one branch each.
+struct XpPvAcc { double a0, a1; };
+template <int K, int NV, int STEP>
+__device__ __forceinline__ void xp_pv_key(const float (&vr)[NV], const float wv, const int lane0, XpPvAcc &a) {
+    const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wv), STEP ? lane0 + STEP * K : K));
+    const double c = (double)__fmul_rn(vr[K], w);
+    if constexpr (K & 1) a.a1 += c; else a.a0 += c;
+}
+template <int K, int KEND, int NV, int STEP>
+__device__ __forceinline__ XpPvAcc xp_pv_rest(const int n, const float (&vr)[NV], const float wv, const int lane0, XpPvAcc a) {
+    if constexpr (K < KEND) {
+        if (K < n) {
+            xp_pv_key<K, NV, STEP>(vr, wv, lane0, a);
+            return xp_pv_rest<K + 1, KEND, NV, STEP>(n, vr, wv, lane0, a);
+        }
+    }
+    return a;
+}
+template <int K, int NV, int STEP>
+__device__ __forceinline__ XpPvAcc xp_pv_old_keys(const int n, const float (&vr)[NV], const float wv, const int lane0, XpPvAcc a) {
+    static_assert(NV % 4 == 0 && K % 4 == 0, "groups of four slots");
+    if constexpr (K < NV) {
+        if (K + 4 <= n) {
+            xp_pv_key<K, NV, STEP>(vr, wv, lane0, a); xp_pv_key<K + 1, NV, STEP>(vr, wv, lane0, a);
+            xp_pv_key<K + 2, NV, STEP>(vr, wv, lane0, a); xp_pv_key<K + 3, NV, STEP>(vr, wv, lane0, a);
+            return xp_pv_old_keys<K + 4, NV, STEP>(n, vr, wv, lane0, a);
+        }
+        return xp_pv_rest<K, K + 3, NV, STEP>(n, vr, wv, lane0, a);
+    }
+    return a;
+}
+
 // The launch's work for one role: ATTN = this workgroup is one of the XCD's 16 attention heads (else it computes q/k/v rows).  The
 // role is a template parameter because the register allocator, given ONE function with a run-time role branch, spills 21-39 VGPRs
 // although each role alone fits (measured: 198-240 of 256 registers per role): two copies of the loop, no spills.
@@ -1144,29 +1179,30 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
             }
             XP_WALL(14);
             {
-                // all LDS reads first, no branches in the loop: a key past the context adds +0.0 (exact), never its stale weight
+                // PV over the keys that exist: wave w holds the value rows of keys j = HI KW + w + NW k in vr[k]; slot k goes to a0 (k even) or a1 (k odd).
+                // The softmax weight numerator * inv is formed once per key and wave (one vector multiply, the wave's slots side by side in lanes) and reaches
+                // the loop as a wave-uniform operand (v_readlane); the loop reads no LDS, runs over the old keys j < n_past only and leaves through scalar
+                // branches; the token's own key (the last one, value row in s_cur) is added behind it by the one wave that owns it.
+                // Exact against adding +0.0 for every slot past the context: the accumulators start at +0.0 and (+0.0) + (-0.0) = +0.0, so none ever holds
+                // -0.0; x + (+0.0) = x for every other x, so the dropped additions changed no bit; the additions that remain have the same operands (the same
+                // rounded products) in the same order per accumulator -- the own key's slot is the last one that is not past the context.
                 const float vcur = s_cur[128 + dd];
-                [[maybe_unused]] const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-                constexpr int CH = NV < 16 ? NV : (NV % 16 == 0 ? 16 : 8);      // softmax weights fetched at most 16 at a time (register budget)
-                double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-                for (int k0 = 0; k0 < NV; k0 += CH) {
-                    float pj[CH];
-#pragma unroll
-                    for (int k = 0; k < CH; k++) {
-                        if constexpr (SMW) pj[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ev[(k0 + k) >> 3]), wave_u + 8 * ((k0 + k) & 7)));      // key sl + 8 (k0 + k)
-                        else pj[k] = s_S[sl + NW * (k0 + k)];
-                    }
-#pragma unroll
-                    for (int k = 0; k < CH; k += 2) {
-                        const int j0 = HI * KW + sl + NW * (k0 + k), j1 = j0 + NW;
-                        const double c0 = (double)__fmul_rn(j0 == n_past ? vcur : vr[k0 + k], __fmul_rn(pj[k], inv));
-                        const double c1 = (double)__fmul_rn(j1 == n_past ? vcur : vr[k0 + k + 1], __fmul_rn(pj[k + 1], inv));
-                        a0 += (j0 < T) ? c0 : 0.0;
-                        a1 += (j1 < T) ? c1 : 0.0;
-                    }
+                const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+                float wv;
+                if constexpr (SMW) wv = __fmul_rn(ev[0], inv);      // lane j: key j (<= 64 keys)
+                else wv = __fmul_rn(s_S[wave_u + NW * min(lane, NV - 1)], inv);      // lane k < NV: slot k of this wave (the other lanes' copies are not used)
+                int own = n_past;
+                asm volatile("" : "+s"(own));      // (what follows from it is recomputed in every layer, not kept in scalar registers over the layer loop)
+                own -= HI * KW;                    // the token's own key, counted inside this workgroup's keys
+                const int n_old = __builtin_amdgcn_readfirstlane(min(max(own - wave_u + NW - 1, 0) / NW, NV));      // this wave's keys j < n_past
+                XpPvAcc acc = xp_pv_old_keys<0, NV, SMW ? NW : 0>(n_old, vr, wv, wave_u, XpPvAcc{0.0, 0.0});
+                if (own >= 0 && own < KW && (own & (NW - 1)) == wave_u) {      // the own key is this wave's: its slot n_old, the last one that is not past the context
+                    const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wv), SMW ? own : n_old));
+                    const double c = (double)__fmul_rn(vcur, w);
+                    if (n_old & 1) { acc.a1 += c; asm volatile("" : "+v"(acc.a1)); }      // (the empty asm keeps the scalar branch: one addition, no selects)
+                    else acc.a0 += c;
                 }
-                s_pv[tid] = a0 + a1;
+                s_pv[tid] = acc.a0 + acc.a1;
             }
             __syncthreads();
             XP_WALL(15);
