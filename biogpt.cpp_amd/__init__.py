@@ -829,6 +829,8 @@ SYMBOLS = [
     ("biogpt_hip_mfma_launches", C.c_int64, [_P]),
     ("biogpt_hip_chain_kind", C.c_int, [_P]),
     ("biogpt_hip_wide_launches", C.c_int64, [_P]),
+    ("biogpt_hip_float_chain", C.c_int, [_P, C.c_int]),
+    ("biogpt_hip_float_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_stamps", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     ("biogpt_hip_generate_launches", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
@@ -926,6 +928,8 @@ SYMBOLS = [
     ("biogpt_hip_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32] + [_P] * 7 + [C.c_int32] * 3 + [_P] * 7),
     ("biogpt_hip_wide_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 4),
     ("biogpt_hip_wide_chain_bench", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P]),
+    ("biogpt_hip_fchain_device", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 5),
+    ("biogpt_hip_fchain_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P]),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_attn_prefix_bench", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     ("biogpt_hip_hidden", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
@@ -1127,6 +1131,54 @@ def wide_chain_bench(which, wtype, M, K, N, reps=9, device=0):
     return us
 
 
+def fchain_device(epi, wtype, M, K, N, w_rows, x, ln_w=None, ln_b=None, bias=None, resid=None, dev_state=None, seq_states=None, col_mode=0, P=0, k_slots=None,
+                  v_slots=None, cfg=-1, device=0):
+    """One stand-alone launch of the float chain's linear stage (biogpt_hip_fchain_device; include/biogpt_hip.h has the inputs of each epilogue).  epi by name
+    (WIDE_EPIS); wtype 0: w_rows float32 [M, K], 1: float16 [M, K] (or its bits as uint16); x float32 [N, K]; ln_w / ln_b: the LayerNorm producer runs first.
+    Returns a dict of the outputs WHOLE as the probe allocated them, guard column and rows included and preset to 0xff bytes: "out" float32 [cols, ldo] ([cols, K]
+    for QKV), "ln" float32 [cols, K] (with ln_w), "k" / "v" (copies of k_slots / v_slots after the launch, QKV), "launched" (threads, grid x, grid y, LDS bytes,
+    cols, ldo, tile shape, 0).  Raises BiogptError on a refusal."""
+    cols, ldo = ((N + 15) & ~15) + 1, ((M + 127) & ~127) + 16
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    if w_rows is not None and int(wtype) == 1 and np.asarray(w_rows).dtype == np.uint16:
+        w_rows = np.asarray(w_rows).view(np.float16)
+    res = {"out": np.zeros((cols, K if epi == "QKV" else ldo), np.float32)}
+    if ln_w is not None:
+        res["ln"] = np.zeros((cols, K), np.float32)
+    n_slots = 0
+    if epi == "QKV":
+        res["k"], res["v"] = np.array(k_slots, dtype=np.float32, order="C"), np.array(v_slots, dtype=np.float32, order="C")
+        n_slots = res["k"].shape[0]
+        assert res["k"].shape == res["v"].shape == (n_slots, K // 64, P, 64)
+    launched = np.zeros(8, np.int32)
+    o = lambda name: res[name].ctypes.data if name in res else None
+    rc = lib().biogpt_hip_fchain_device(int(device), WIDE_EPIS[epi], int(wtype), int(M), int(K), int(N), int(cfg), ptr(w_rows, np.float16 if int(wtype) == 1 else np.float32),
+                                        ptr(x, np.float32), ptr(ln_w, np.float32), ptr(ln_b, np.float32), ptr(bias, np.float32), ptr(resid, np.float32),
+                                        ptr(dev_state, np.int32), ptr(seq_states, np.int32), int(col_mode), int(P), n_slots, o("k"), o("v"), o("out"), o("ln"),
+                                        launched.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    res["launched"] = launched
+    return res
+
+
+def fchain_bench(which, wtype, M, K, N, cfg=-1, reps=9, device=0):
+    """A linear stage of a float file alone, timed (biogpt_hip_fchain_bench): microseconds of `reps` launches, float32 [reps].  which "float": the float chain's
+    kernel at tile shape cfg (-1: the launch's choice); "generic": the generic mat-vec kernel a prompt pass of the context's own columns takes."""
+    us = np.zeros(int(reps), np.float32)
+    if lib().biogpt_hip_fchain_bench(int(device), {"float": 0, "generic": 1}[which], int(wtype), int(M), int(K), int(N), int(cfg), int(reps), us.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return us
+
+
 def write_synthetic(path, seed=0x42494F47, **hparams):
     """Write a seeded synthetic model file. hparams default to BioGPT-base."""
     hp = HParams(**{**BIOGPT_BASE, **hparams})
@@ -1301,10 +1353,19 @@ class BiogptModel:
 
     # -- biogpt_model_load (biogpt.h:128-132) --
     @classmethod
-    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0):
+    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False):
+        """float_chain=True: switch the float chain on behind the load (float_chain(); an F32 / F16 file with head size 64 only -- anything else raises)."""
         if arena is None:
-            return cls(lib().biogpt_hip_load(os.fsencode(fname), device, verbosity))
-        return cls(lib().biogpt_hip_load_into(os.fsencode(fname), device, verbosity, arena, arena_bytes))
+            m = cls(lib().biogpt_hip_load(os.fsencode(fname), device, verbosity))
+        else:
+            m = cls(lib().biogpt_hip_load_into(os.fsencode(fname), device, verbosity, arena, arena_bytes))
+        if float_chain:
+            try:
+                m.float_chain(True)
+            except BiogptError:
+                m.close()
+                raise
+        return m
 
     @classmethod
     def attach(cls, hparams, device, arena, arena_bytes):
@@ -2020,11 +2081,21 @@ class BiogptModel:
 
     def chain_kind(self):
         """Which many-column layer chain the file has (biogpt_hip_chain_kind): 0 none, 1 the BioGPT-base chain, 2 the wide chain (any other block-quantized file
-        with head size 64, d_model a multiple of 64 and d_ff of 32)."""
+        with head size 64, d_model a multiple of 64 and d_ff of 32), 3 the float chain (an F32 / F16 file of those widths while float_chain() is on)."""
         k = int(lib().biogpt_hip_chain_kind(self._h))
         if k < 0:
             raise BiogptError(_err())
         return k
+
+    def float_chain(self, on=True):
+        """The float chain's switch (biogpt_hip_float_chain): on, the batched calls the wide chain serves serve this F32 / F16 file, chain_kind() is 3; off (the
+        default of a load), the file has the single-sequence calls only.  Raises BiogptError with the reason where the file cannot have it."""
+        if lib().biogpt_hip_float_chain(self._h, 1 if on else 0) != 0:
+            raise BiogptError(_err())
+
+    def float_launches(self):
+        """Linear-stage launches of the float chain (biogpt_hip_float_launches); 0 while the switch is off."""
+        return int(lib().biogpt_hip_float_launches(self._h))
 
     def wide_launches(self):
         """Linear-stage launches of the wide chain (biogpt_hip_wide_launches); 0 on a BioGPT-base file."""

@@ -199,7 +199,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -230,6 +230,7 @@ struct EngineOptions {
         proc_lock = get("BIOGPT_HIP_PROC_LOCK", 1);               // one process per device drives the pipelined launches (engine_xpipe.inc, xpipe_process_lock)
         prefix_attn = get("BIOGPT_HIP_PREFIX_ATTN", -1);          // decode steps behind a shared prefix: -1 attn_prefix_kernel where it was measured faster (PREFIX_ATTN_MIN_*), 0 never, 1 always (A/B arms)
         run_attn = get("BIOGPT_HIP_RUN_ATTN", -1);                // the passes of biogpt_hip_score_continuations_batch (no other call looks at it): -1 attn_runs_kernel where it was measured faster (RUN_ATTN_MIN_*), 0 never, 1 in every pass of up to 1024 keys (A/B arms)
+        float_chain = get("BIOGPT_HIP_FLOAT_CHAIN", 0);          // 1: a new context of an F32 / F16 file the float chain serves starts with it switched on (biogpt_hip_float_chain; kernels_fchain.hip.h)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
     }
 };
@@ -377,6 +378,8 @@ struct biogpt_hip_ctx {
     int64_t xc_launches = 0;               // evals that went through the chunk launch (biogpt_hip_chunk_launches)
     int64_t mfma_launches = 0;             // launches of the many-column chain that went to the matrix-core kernels (biogpt_hip_mfma_launches)
     int64_t wide_launches = 0;             // linear-stage launches of the wide chain (kernels_mfma_wide.hip.h; biogpt_hip_wide_launches)
+    bool float_chain = false;              // the float chain is switched on (biogpt_hip_float_chain): passes over column states of this F32 / F16 file run on kernels_fchain.hip.h
+    int64_t float_launches = 0;            // linear-stage launches of the float chain (biogpt_hip_float_launches)
     int32_t gen_launch_tokens[16] = {0}; int gen_launches = 0;   // the last biogpt_hip_generate_greedy: tokens of each multi-token pipelined launch (biogpt_hip_generate_launches)
     int32_t prefix_stats[4] = {0, 0, 0, 0};   // of the last biogpt_hip_generate_*_prefix call that generated tokens: shared rows, prompt columns evaluated, path (0 in place, 1 copied), columns
     int xc_batch = 0;                      // a column generation call with 2 .. 8 columns holds the device's pipeline slot (choose_column_path): its decode steps run as column-per-XCD launches (streams mode)
@@ -604,12 +607,29 @@ extern "C" int bg_wide_quantize(const float *x, int ldx, int K, int N, const flo
                                 uint32_t *oq_s, hipStream_t st);
 // Which many-column layer chain a file has (biogpt_hip_chain_kind).  1: BioGPT-base widths, every launch as before.  2: the wide chain -- any other block-quantized
 // file with head size 64 whose widths the kernel's tiles divide; passes over column states only, the context's own columns stay on the generic kernels.
-enum ChainKind : int { CHAIN_NONE = 0, CHAIN_BASE = 1, CHAIN_WIDE = 2 };
+// 3: the float chain -- an F32 / F16 file with the wide chain's widths, and only while its context has it switched on (chain_kind; biogpt_hip_float_chain).
+enum ChainKind : int { CHAIN_NONE = 0, CHAIN_BASE = 1, CHAIN_WIDE = 2, CHAIN_FLOAT = 3 };
 inline int chain_kind_of(const biogpt_hip_hparams &hp) {
     if (!is_quantized(ftype_to_type(hp.ftype)) || hp.n_head < 1 || hp.d_model % hp.n_head != 0 || hp.d_model / hp.n_head != 64) return CHAIN_NONE;
     if (hp.d_model == 1024 && hp.d_ff == 4096) return CHAIN_BASE;
     return (hp.d_model % 64 == 0 && hp.d_ff >= 32 && hp.d_ff % 32 == 0) ? CHAIN_WIDE : CHAIN_NONE;
 }
+// the float chain (kernels_fchain.hip.h, fchain_tu.hip): the many-column linear stage on the row-major F32 / F16 weights of the arena, and the LayerNorm producer in
+// front of it.  cfg: a tile shape, -1 the launch's own choice; report: null, or five words (threads, grid x, grid y, LDS bytes, cfg)
+extern "C" int bg_fchain_launch(int wt, int epi, const void *params, size_t params_bytes, int cfg, hipStream_t st, int32_t *report);
+extern "C" int bg_fchain_ln(int wt, const float *x, int ldx, int K, int N, const float *ln_w, const float *ln_b, float eps, float *out, hipStream_t st);
+extern "C" int bg_fchain_cfg(int M, int N);
+// why a file cannot have the float chain switched on (null: it can): the wide chain's width rules, on float weights
+inline const char *float_chain_refusal(const biogpt_hip_hparams &hp) {
+    const int32_t t = ftype_to_type(hp.ftype);
+    if (t != T_F32 && t != T_F16) return "the weights are block-quantized (the float chain is for F32 / F16 files; a block-quantized file has the BioGPT-base or the wide chain)";
+    if (hp.n_head < 1 || hp.d_model % hp.n_head != 0 || hp.d_model / hp.n_head != 64) return "the head size is not 64";
+    if (hp.d_model % 64 != 0) return "d_model is no multiple of 64";
+    if (hp.d_ff < 32 || hp.d_ff % 32 != 0) return "d_ff is no multiple of 32";
+    return nullptr;
+}
+// the chain a CONTEXT's calls over column states run on: the file's, or the float chain while it is switched on
+inline int chain_kind(const biogpt_hip_ctx *c) { return c->float_chain ? CHAIN_FLOAT : chain_kind_of(c->hp); }
 template <int WT>
 hipError_t launch_chain_mfma(ChainOp op, const bgk::MatvecParams &p, const bgk::DevMatrix &img, hipStream_t st, ChainLaunch *rep) {
     int site = -1;
@@ -1225,6 +1245,7 @@ struct PassLaunch {
     int attn_threads;               // attention workgroup size of the generic kernel
     bool chain, pchain, mfma;       // the single-token fast chain; its many-column form; on the int8 matrix cores
     bool wchain;                    // the wide chain: a pass over column states of a block-quantized file that is not BioGPT-base (kernels_mfma_wide.hip.h)
+    bool fchain;                    // the float chain: a pass over column states of an F32 / F16 file whose context has it switched on (kernels_fchain.hip.h)
     int q81;
     const bgk::SeqState *seq;       // column states of a pass over the per-sequence caches (null: the context's own columns)
     int col_mode;                   // 1: packed columns
@@ -1249,6 +1270,20 @@ struct PassLaunch {
         img = tile_matrix(c, m);
         e = (hipError_t)bg_wide_launch(m.type, epi, &p, sizeof(p), &img, sizeof(img), st);
         if (e == hipSuccess) c->wide_launches++;
+        return e;
+    }
+    // The float chain's stage on the row-major weights of the arena.  x: the f32 rows [N][W.K] the stage reads; ln_w given: LayerNorm ONCE per column first
+    // (fchain_ln_kernel) into c->att, which no launch between a LayerNorm site and the stage behind it reads or writes (the attention output lives there from
+    // the attention launch to out_proj only).  The fp16 rounding of an F16 file's activation rows is the stage's own staging loop's.
+    hipError_t float_stage(int epi, bgk::MatvecParams &p, const MatSlot &m, const float *x, const float *ln_w = nullptr, const float *ln_b = nullptr) {
+        if (ln_w) {
+            const hipError_t e = (hipError_t)bg_fchain_ln(m.type, x, (int)m.K, (int)m.K, p.N, ln_w, ln_b, 1e-5f, c->att, st);
+            if (e != hipSuccess) return e;
+            x = c->att;
+        }
+        p.x = x; p.ldx = (int32_t)m.K;
+        const hipError_t e = (hipError_t)bg_fchain_launch(m.type, epi, &p, sizeof(p), -1, st, nullptr);
+        if (e == hipSuccess) c->float_launches++;
         return e;
     }
 };
@@ -1437,7 +1472,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.vcache = k.vroot + (size_t)l * P * D;
         if (k.seq) { p.seq = k.seq; p.col_mode = k.col_mode; p.kv_seq_stride = k.seq_stride; }
         p.q_scale = 1.0f / sqrtf((float)k.dk);
-        if (k.wchain) {
+        if (k.fchain) {
+            HIP_TRY(false, k.float_stage(bgk::EPI_QKV, p, L.qkv, c->x, p.ln_w, p.ln_b));
+        } else if (k.wchain) {
             HIP_TRY(false, k.wide_stage(bgk::EPI_QKV, p, L.qkv, c->x, 2, p.ln_w, p.ln_b));
         } else if (k.pchain) {
             HIP_TRY(false, launch_lnq(c, c->x, N, L.ln0_w, L.ln0_b, k.q81, st));
@@ -1454,7 +1491,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.x = c->att; p.ldx = D; p.N = N;
         p.bias = dev_vec(c, L.o_b);
         p.resid = c->x; p.ldr = D; p.out = c->x1; p.ldo = D;
-        if (k.wchain) {      // (the attention kernels wrote f32 rows: no Q8 side output without the base chain)
+        if (k.fchain) {
+            HIP_TRY(false, k.float_stage(bgk::EPI_RESID, p, L.o, c->att));
+        } else if (k.wchain) {      // (the attention kernels wrote f32 rows: no Q8 side output without the base chain)
             HIP_TRY(false, k.wide_stage(bgk::EPI_RESID, p, L.o, c->att, 0));
         } else if (k.chain) {
             p.aq_q = c->aq_q[0]; p.aq_d = c->aq_d[0]; p.aq_s = c->aq_s[0];
@@ -1470,7 +1509,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.ln_w = dev_vec(c, L.ln1_w); p.ln_b = dev_vec(c, L.ln1_b);
         p.bias = dev_vec(c, L.fc1_b);
         p.out = c->h; p.ldo = F;
-        if (k.wchain) {
+        if (k.fchain) {
+            HIP_TRY(false, k.float_stage(bgk::EPI_GELU, p, L.fc1, c->x1, p.ln_w, p.ln_b));
+        } else if (k.wchain) {
             HIP_TRY(false, k.wide_stage(bgk::EPI_GELU, p, L.fc1, c->x1, 2, p.ln_w, p.ln_b));
         } else if (k.pchain) {
             HIP_TRY(false, launch_lnq(c, c->x1, N, L.ln1_w, L.ln1_b, k.q81, st));
@@ -1490,7 +1531,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.x = c->h; p.ldx = F; p.N = N;
         p.bias = dev_vec(c, L.fc2_b);
         p.resid = c->x1; p.ldr = D; p.out = c->x; p.ldo = D;
-        if (k.wchain) {
+        if (k.fchain) {
+            HIP_TRY(false, k.float_stage(bgk::EPI_RESID, p, L.fc2, c->h));
+        } else if (k.wchain) {
             HIP_TRY(false, k.wide_stage(bgk::EPI_RESID, p, L.fc2, c->h, 1));
         } else if (k.chain) {
             p.aq_q = c->aq_q[1]; p.aq_d = c->aq_d[1]; p.aq_s = c->aq_s[1];
@@ -1521,6 +1564,12 @@ bool enqueue_final(PassLaunch &k) {
     const MatSlot &m = c->plan.lm_head;
     const MvShape s = mv_shape(m.type, m.M, m.K);
     bgk::MatvecParams p = mv_base(c, m, s);
+    if (rows == Rows::All && k.fchain) {  // the float chain: LayerNorm of the columns that get a row, once, then the lm_head stage (any n_vocab)
+        const int head_from = k.pass.head_from;
+        p.N = N - head_from; p.out = c->logits_all; p.ldo = V;
+        HIP_TRY(false, k.float_stage(bgk::EPI_LOGITS, p, m, c->x + (size_t)head_from * D, dev_vec(c, c->plan.ln_w), dev_vec(c, c->plan.ln_b)));
+        return true;
+    }
     if (rows == Rows::All && k.wchain) {  // the wide chain: LayerNorm+Q8 of the columns that get a row, then the lm_head on the matrix cores (its last row tile may be partial)
         const int head_from = k.pass.head_from;
         p.N = N - head_from; p.out = c->logits_all; p.ldo = V;
@@ -1585,7 +1634,10 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     k.mfma = k.pchain && N >= (pass.cols == Cols::PerSequence ? MFMA_MIN_DECODE_COLS : MFMA_MIN_PASS_COLS) && c->tile_img != nullptr;
     // a pass over column states of any other block-quantized file with head size 64: the wide chain (the context's own columns stay on the generic kernels)
     k.wchain = !k.chain && batch && chain_kind_of(hp) == CHAIN_WIDE && t_max <= 1024;
-    if (batch && !k.chain && !k.wchain)
+    // a pass over column states of a float file whose context has the float chain switched on (the context's own columns stay on fdec_kernel / matvec_kernel)
+    k.fchain = !k.chain && !k.wchain && batch && chain_kind(c) == CHAIN_FLOAT && t_max <= 1024;
+    if (k.fchain && (pass.rows == Rows::Last || pass.rows == Rows::AllGeneric)) BG_FAIL(false, "internal: a float fast chain pass with rows it does not serve");
+    if (batch && !k.chain && !k.wchain && !k.fchain)
         BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64) or the wide one (block-quantized weights, head size 64, d_model a multiple of 64, d_ff of 32)");
     if (k.wchain && (c->tile_img == nullptr || pass.rows == Rows::Last || pass.rows == Rows::AllGeneric))
         BG_FAIL(false, "internal: a wide fast chain pass without its row-tiled weight image, or with rows it does not serve");
@@ -1879,6 +1931,7 @@ biogpt_hip_ctx *load_impl(const char *fname, int device, int verbosity, void *ex
     std::unique_ptr<biogpt_hip_ctx, void (*)(biogpt_hip_ctx *)> c(new biogpt_hip_ctx(), destroy);
     c->opt.load();
     c->hp = mf.hp;
+    c->float_chain = c->opt.float_chain == 1 && float_chain_refusal(c->hp) == nullptr;      // (the environment's default holds where the file can have it)
     c->device = device;
     c->n_tensors = (int)mf.tensors.size();
     c->vocab = mf.vocab;
@@ -1987,6 +2040,7 @@ biogpt_hip_ctx *biogpt_hip_attach(const biogpt_hip_hparams *hp, int device, void
     std::unique_ptr<biogpt_hip_ctx, void (*)(biogpt_hip_ctx *)> c(new biogpt_hip_ctx(), destroy);
     c->opt.load();
     c->hp = *hp;
+    c->float_chain = c->opt.float_chain == 1 && float_chain_refusal(c->hp) == nullptr;
     c->device = device;
     c->pos_rows = (int64_t)hp->n_positions + 2;
     c->plan = plan_arena(*hp, c->pos_rows);
@@ -2485,9 +2539,33 @@ int biogpt_hip_eval_inplace(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t 
 int64_t biogpt_hip_chunk_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->xc_launches : -1; }
 int64_t biogpt_hip_mfma_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->mfma_launches : -1; }
 int64_t biogpt_hip_wide_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->wide_launches : -1; }
+int64_t biogpt_hip_float_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->float_launches : -1; }
 int biogpt_hip_chain_kind(const biogpt_hip_ctx *ctx) {
     if (!ctx) BG_FAIL(-1, "null context");
-    return chain_kind_of(ctx->hp);
+    return chain_kind(ctx);
+}
+// The float chain's switch.  Off (the default), a float file is what it was: no call over column states.  The captured column steps bake the route: dropped.
+int biogpt_hip_float_chain(biogpt_hip_ctx *ctx, int on) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (on != 0 && on != 1) BG_FAIL(-1, "on must be 0 or 1 (got %d)", on);
+    if (session_refuses(ctx)) return -1;
+    {
+        std::lock_guard<std::mutex> lk(g_xp_mu);
+        if (ctx->xp_in_call) BG_FAIL(-1, "the float fast chain cannot be switched while a call of this context is running");
+    }
+    if (on) {
+        if (const char *why = float_chain_refusal(ctx->hp))
+            BG_FAIL(-1, "the float fast chain cannot be switched on for this file: %s (it needs F32 / F16 weights, head size 64, d_model a multiple of 64, d_ff of 32; got ftype %d, d_model %d, d_ff %d, %d heads)", why, ctx->hp.ftype, ctx->hp.d_model, ctx->hp.d_ff, ctx->hp.n_head);
+    }
+    if (ctx->float_chain == (on == 1)) return 0;
+    if (ctx->ready) {
+        HIP_TRY(-2, hipSetDevice(ctx->device));
+        HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    }
+    drop_column_graphs(ctx);
+    ctx->float_chain = on == 1;
+    return 0;
 }
 int biogpt_hip_fpipe_stamps(biogpt_hip_ctx *ctx, uint64_t *out, int n) {
     if (!ctx || !out || n < 0 || ctx->fp_state != 1 || !ctx->opt.fpipe_stamps) return -1;
@@ -2705,7 +2783,11 @@ static bool check_prompts(const biogpt_hip_ctx *c, const int32_t *prompts, const
 // The gate of every call over column states.  wide_ok: the call is open to the wide chain (DESIGN.md 4.7 lists them); a wide file's row-tiled image is built
 // here, before any capture -- it has no kernel to fall back to, so an image that does not fit is the call's error.
 static bool check_fast_chain(biogpt_hip_ctx *c, const char *what, bool wide_ok = false) {
-    const int kind = chain_kind_of(c->hp);
+    const int kind = chain_kind(c);
+    if (kind == CHAIN_FLOAT) {      // (nothing to build: the stage reads the arena's own rows)
+        if (!wide_ok) BG_FAIL(false, "%s needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096): the float fast chain switched on for this %s file does not serve it", what, ftype_to_type(c->hp.ftype) == T_F16 ? "F16" : "F32");
+        return true;
+    }
     if (kind == CHAIN_NONE)
         BG_FAIL(false, "%s needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64) or the wide one (block-quantized weights, head size 64, d_model a multiple of 64, d_ff of 32)", what);
     if (kind == CHAIN_BASE) return true;
@@ -2726,7 +2808,9 @@ static bool begin_column_call(biogpt_hip_ctx *ctx, int n_slots, int n_seqs, long
     // matrix-core chain: decode steps have n_seqs columns, the prompt pass all prompt tokens; build the tiled weights before any graph capture
     // (a wide file has no other many-column kernel: always, and an image that does not fit is the call's error)
     const bool wide = chain_kind_of(ctx->hp) == CHAIN_WIDE;
-    if ((wide || std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS) && !ensure_tile_images(ctx)) return false;
+    // (a float file has no image at all: the float chain reads the arena's own rows)
+    const bool quant = is_quantized(ftype_to_type(ctx->hp.ftype));
+    if (quant && (wide || std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS) && !ensure_tile_images(ctx)) return false;
     if (wide && ctx->tile_img == nullptr) BG_FAIL(false, "no device memory for the row-tiled weight image the wide fast chain needs");
     return ensure_logits_rows(ctx, (size_t)n_seqs);
 }

@@ -1661,3 +1661,163 @@ int biogpt_hip_wide_chain_bench(int device, int32_t which, int32_t wtype, int32_
     HIP_TRY(-2, e);
     return 0;
 }
+
+// One stand-alone launch of the float chain's linear stage (fchain_kernel, kernels_fchain.hip.h) over caller-supplied weights and f32 columns, through
+// bg_fchain_launch (and bg_fchain_ln in front of it when ln_w is given) -- the entries of PassLaunch::float_stage.  epi: 0 QKV (M == 3 K, 64 | K: K is d_model,
+// heads of 64), 1 RESID, 2 GELU, 3 LOGITS; any M.  wtype 0: w_rows is M rows of K f32; 1: of K f16 (bits).  x [N][K] f32.  cfg: 0 .. 2 a tile shape, -1 the
+// launch's own choice.  QKV: exactly one of dev_state and seq_states (+ col_mode) names the column states; k_slots / v_slots [n_slots][K / 64][P][64] are
+// updated in place.  out comes back WHOLE as allocated and preset to 0xff: cols = N rounded up to 16, plus one guard column; QKV: [cols][K] (the q rows),
+// otherwise [cols][ldo] with ldo = M rounded up to 128, plus 16 guard rows; ln_out (may be NULL; with ln_w only) [cols][K]: the producer's rows.
+// launched [8]: threads, grid x, grid y, static LDS bytes, cols, ldo, cfg, 0.
+int biogpt_hip_fchain_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, const void *w_rows, const float *x, const float *ln_w,
+                             const float *ln_b, const float *bias, const float *resid, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t P,
+                             int32_t n_slots, float *k_slots, float *v_slots, float *out, float *ln_out, int32_t *launched) {
+    clear_error();
+    if (epi < bgk::EPI_QKV || epi > bgk::EPI_LOGITS) BG_FAIL(-1, "epi %d is no epilogue of the float chain (0 QKV, 1 RESID, 2 GELU, 3 LOGITS)", epi);
+    if (wtype != T_F32 && wtype != T_F16) BG_FAIL(-1, "type %d is no float format (0 F32, 1 F16)", wtype);
+    if (cfg < -1 || cfg > 2) BG_FAIL(-1, "cfg must be in [-1, 2]");
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    if (epi == bgk::EPI_QKV && (K % 64 != 0 || M != 3 * K)) BG_FAIL(-1, "q/k/v is 3 K x K with heads of 64 (got %d x %d)", M, K);
+    if (!w_rows || !x || !out) BG_FAIL(-1, "w_rows, x or out is NULL");
+    if ((ln_w != nullptr) != (ln_b != nullptr)) BG_FAIL(-1, "ln_w and ln_b come together");
+    if (ln_out && !ln_w) BG_FAIL(-1, "ln_out needs ln_w and ln_b");
+    if (epi != bgk::EPI_LOGITS && !bias) BG_FAIL(-1, "bias is NULL");
+    if (epi == bgk::EPI_RESID && !resid) BG_FAIL(-1, "resid is NULL");
+    const bool qkv = epi == bgk::EPI_QKV, batch = seq_states != nullptr;
+    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
+    if (qkv) {
+        if ((dev_state != nullptr) == batch) BG_FAIL(-1, "exactly one of dev_state and seq_states names the column states");
+        if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
+        if (!batch && col_mode) BG_FAIL(-1, "col_mode 1 needs seq_states");
+        if (!k_slots || !v_slots) BG_FAIL(-1, "k_slots or v_slots is NULL");
+        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+        if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
+        if (!batch && n_slots != 1) BG_FAIL(-1, "the context's own columns have one slot");
+        std::set<std::pair<int, int>> seen;      // every column's cache row inside its slot, no two columns on one row
+        for (int i = 0; i < N; i++) {
+            const int pos = batch ? hs[i].n_past : dev_state[0] + i, slot = batch ? (col_mode ? hs[i].seq_id : i) : 0;
+            if (pos < 0 || pos >= P) BG_FAIL(-1, "column %d: position %d outside [0, P)", i, pos);
+            if (slot < 0 || slot >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, slot);
+            if (!seen.insert({slot, pos}).second) BG_FAIL(-1, "column %d: a second column writes slot %d, position %d", i, slot, pos);
+        }
+    } else if (dev_state || batch) BG_FAIL(-1, "only QKV reads column states");
+    HIP_TRY(-2, hipSetDevice(device));
+    const int cols = ((N + 15) & ~15) + 1, ldo = ((M + 127) & ~127) + 16, H = K / 64;
+    const size_t w_b = (size_t)M * K * (wtype == T_F32 ? 4 : 2), x_b = (size_t)N * K * 4;
+    const size_t slot_f = (size_t)H * P * 64, kv_b = qkv ? slot_f * 4 * (size_t)n_slots : 0;
+    const size_t out_b = (size_t)cols * (qkv ? K : ldo) * 4, ln_b_ = ln_w ? (size_t)cols * K * 4 : 0;
+    ByteLayout l;
+    const size_t o_w = l.part(w_b), o_x = l.part(x_b), o_lw = l.part(ln_w ? (size_t)K * 4 : 0), o_lb = l.part(ln_w ? (size_t)K * 4 : 0), o_bias = l.part(bias ? (size_t)M * 4 : 0),
+                 o_res = l.part(epi == bgk::EPI_RESID ? (size_t)N * M * 4 : 0), o_ds = l.part(sizeof(bgk::DevState)), o_st = l.part(batch ? sizeof(bgk::SeqState) * (size_t)N : 0),
+                 o_tab = l.part(65536 * 2), o_k = l.part(kv_b), o_v = l.part(kv_b), o_ln = l.part(ln_b_), o_out = l.part(out_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemset(d.p + o_ln, 0xff, l.bytes() - o_ln));        // the producer's rows and the output, with their guard columns and rows
+    HIP_TRY(-2, hipMemcpy(d.p + o_w, w_rows, w_b, hipMemcpyHostToDevice));
+    HIP_TRY(-2, hipMemcpy(d.p + o_x, x, x_b, hipMemcpyHostToDevice));
+    if (ln_w) {
+        HIP_TRY(-2, hipMemcpy(d.p + o_lw, ln_w, (size_t)K * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_lb, ln_b, (size_t)K * 4, hipMemcpyHostToDevice));
+    }
+    if (bias) HIP_TRY(-2, hipMemcpy(d.p + o_bias, bias, (size_t)M * 4, hipMemcpyHostToDevice));
+    if (epi == bgk::EPI_RESID) HIP_TRY(-2, hipMemcpy(d.p + o_res, resid, (size_t)N * M * 4, hipMemcpyHostToDevice));
+    const int32_t no_state[4] = {0, 0, 0, 0};
+    HIP_TRY(-2, hipMemcpy(d.p + o_ds, (qkv && !batch) ? dev_state : no_state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
+    if (batch) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
+    if (qkv) {
+        HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
+    }
+    const std::vector<uint16_t> tg = gelu_table_f16();
+    HIP_TRY(-2, hipMemcpy(d.p + o_tab, tg.data(), 65536 * 2, hipMemcpyHostToDevice));
+    bgk::MatvecParams p{};
+    p.W.qs = d.p + o_w; p.W.type = wtype; p.W.M = M; p.W.K = K;
+    p.eps = 1e-5f; p.D = K; p.dk = 64; p.dk_log2 = 6; p.P = P;
+    p.st = d.at<const bgk::DevState>(o_ds);
+    p.gelu_tab = d.at<const uint16_t>(o_tab);
+    p.N = N;
+    p.x = d.at<const float>(o_x); p.ldx = K;
+    if (bias) p.bias = d.at<const float>(o_bias);
+    if (qkv) {
+        p.q_out = d.at<float>(o_out); p.kcache = d.at<float>(o_k); p.vcache = d.at<float>(o_v);
+        p.q_scale = 1.0f / sqrtf(64.0f);
+        if (batch) { p.seq = d.at<const bgk::SeqState>(o_st); p.col_mode = col_mode; p.kv_seq_stride = (int64_t)slot_f; }
+    } else {
+        p.out = d.at<float>(o_out); p.ldo = ldo;
+        if (epi == bgk::EPI_RESID) { p.resid = d.at<const float>(o_res); p.ldr = M; }
+    }
+    if (ln_w) {
+        HIP_TRY(-2, (hipError_t)bg_fchain_ln(wtype, p.x, K, K, N, d.at<const float>(o_lw), d.at<const float>(o_lb), 1e-5f, d.at<float>(o_ln), 0));
+        p.x = d.at<const float>(o_ln);
+    }
+    int32_t rep[8] = {0, 0, 0, 0, cols, ldo, 0, 0}, five[5] = {0, 0, 0, 0, 0};
+    HIP_TRY(-2, (hipError_t)bg_fchain_launch(wtype, epi, &p, sizeof(p), cfg, 0, five));
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    rep[0] = five[0]; rep[1] = five[1]; rep[2] = five[2]; rep[3] = five[3]; rep[6] = five[4];
+    if (launched) std::memcpy(launched, rep, sizeof(rep));
+    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, out_b, hipMemcpyDeviceToHost));
+    if (ln_out) HIP_TRY(-2, hipMemcpy(ln_out, d.p + o_ln, ln_b_, hipMemcpyDeviceToHost));
+    if (qkv) {
+        HIP_TRY(-2, hipMemcpy(k_slots, d.p + o_k, kv_b, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(v_slots, d.p + o_v, kv_b, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// A linear stage of a float file alone, timed: reps launches on device memory filled with 0x3c bytes (ordinary normal values), each between two device
+// events; one untimed launch in front.  which 0: fchain_kernel with the residual epilogue at tile shape cfg (-1: the launch's choice); which 1: the generic
+// matvec_kernel<PRO_PLAIN, EPI_RESID> as a prompt pass of the context's own columns launches it (launch_mv) -- the yardstick.  For tools/float_chain_bench.py.
+int biogpt_hip_fchain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, int32_t reps, float *us_out) {
+    clear_error();
+    if (which != 0 && which != 1) BG_FAIL(-1, "which must be 0 (the float chain's kernel) or 1 (the generic mat-vec kernel)");
+    if (wtype != T_F32 && wtype != T_F16) BG_FAIL(-1, "type %d is no float format (0 F32, 1 F16)", wtype);
+    if (cfg < -1 || cfg > 2) BG_FAIL(-1, "cfg must be in [-1, 2]");
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    if (reps < 1 || reps > 10000) BG_FAIL(-1, "reps must be in [1, 10000]");
+    if (!us_out) BG_FAIL(-1, "us_out is NULL");
+    HIP_TRY(-2, hipSetDevice(device));
+    ByteLayout l;
+    const size_t o_w = l.part((size_t)M * K * (wtype == T_F32 ? 4 : 2)), o_x = l.part((size_t)N * K * 4), o_bias = l.part((size_t)M * 4), o_res = l.part((size_t)N * M * 4),
+                 o_out = l.part((size_t)N * M * 4);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemset(d.p, 0x3c, l.bytes()));      // f32 0.0115, f16 1.06: ordinary products
+    EngineOptions opt{};
+    opt.load();
+    MatSlot m{};
+    m.type = wtype; m.M = M; m.K = K;
+    const MvShape s = mv_shape(wtype, M, K);
+    bgk::MatvecParams p{};
+    p.W.qs = d.p + o_w; p.W.type = wtype; p.W.M = M; p.W.K = K;
+    p.upr = s.upr; p.lpr_log2 = s.lpr_log2; p.nit = s.nit; p.rpw = s.rpw;
+    p.eps = 1e-5f; p.D = 1024; p.dk = 64; p.dk_log2 = 6; p.P = 1;
+    p.inv_k = 1.0 / (double)K; p.k_pow2 = (K & (K - 1)) == 0;
+    p.N = N; p.x = d.at<const float>(o_x); p.ldx = K;
+    p.bias = d.at<const float>(o_bias); p.resid = d.at<const float>(o_res); p.ldr = M; p.out = d.at<float>(o_out); p.ldo = M;
+    auto launch = [&]() -> hipError_t {
+        if (which == 0) return (hipError_t)bg_fchain_launch(wtype, bgk::EPI_RESID, &p, sizeof(p), cfg, 0, nullptr);
+        return launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(opt, p, s, 0);
+    };
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_TRY(-2, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); BG_FAIL(-2, "hipEventCreate failed"); }
+    hipError_t e = launch();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (int i = 0; i < reps && e == hipSuccess; i++) {
+        e = hipEventRecord(e0, 0);
+        if (e == hipSuccess) e = launch();
+        if (e == hipSuccess) e = hipEventRecord(e1, 0);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.0f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        us_out[i] = ms * 1e3f;
+    }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    HIP_TRY(-2, e);
+    return 0;
+}

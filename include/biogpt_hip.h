@@ -170,11 +170,24 @@ int64_t biogpt_hip_mfma_launches(const biogpt_hip_ctx *ctx);
 /* Which many-column layer chain the file has: 0 none (float weights, a head size other than 64, widths the tiles do not divide: the calls over column states
  * refuse it), 1 the BioGPT-base chain (block-quantized, d_model 1024, d_ff 4096), 2 the wide chain -- any other block-quantized file with head size 64, d_model a
  * multiple of 64 and d_ff of 32 (BioGPT-Large: 1600 / 6400): its passes over column states run their linear stages on the int8 matrix cores at every column
- * count, from a row-tiled weight image whose last lm_head tile is zero-padded.  -1: ctx is NULL. */
+ * count, from a row-tiled weight image whose last lm_head tile is zero-padded; 3 the float chain -- an F32 / F16 file of the wide chain's widths, and only
+ * while biogpt_hip_float_chain has switched it on for this context (a float file is 0 otherwise).  -1: ctx is NULL. */
 int biogpt_hip_chain_kind(const biogpt_hip_ctx *ctx);
 /* Linear-stage launches of the wide chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever on a
  * BioGPT-base file.  -1: ctx is NULL. */
 int64_t biogpt_hip_wide_launches(const biogpt_hip_ctx *ctx);
+/* The float chain's switch (off by default; BIOGPT_HIP_FLOAT_CHAIN=1 makes on the default of new contexts whose file can have it).  on 1: the calls over column
+ * states the wide chain serves (score_batch, embed_batch, score_continuations, generate_greedy_batch, generate_sample, generate_beam / _beam_batch, the plain
+ * generate_queue) serve this F32 / F16 file: its passes over column states run their linear stages on csrc/kernels_fchain.hip.h, which reads the file's own
+ * row-major weights (no second image) with the oracle's arithmetic (f32-rounded products, a double sum, one rounding); biogpt_hip_chain_kind returns 3.  The
+ * context's own passes (biogpt_hip_eval, score, hidden, generate_greedy, prompt chunks) are untouched, and every other call over column states refuses the
+ * context by name.  on 0: the file is what it was without the switch, call by call and message by message.  Legal only for F32 / F16 weights with head size 64,
+ * d_model a multiple of 64 and d_ff of 32, and not while a queue session is open or a call of the context is running.  Drops the captured column steps.
+ * Returns 0, or -1 with a message (biogpt_hip_last_error) that names the reason. */
+int biogpt_hip_float_chain(biogpt_hip_ctx *ctx, int on);
+/* Linear-stage launches of the float chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
+ * switch is off.  -1: ctx is NULL. */
+int64_t biogpt_hip_float_launches(const biogpt_hip_ctx *ctx);
 /* F32 / F16 files: single-token steps this context has enqueued (or captured into a replayed step) as ONE persistent launch for all layers (csrc/kernels_fpipe.hip.h);
  * -1: that launch is not available to this context (shape, device, BIOGPT_HIP_FPIPE=0, or abandoned after a failed launch) -- five launches per layer then */
 int64_t biogpt_hip_fpipe_launches(const biogpt_hip_ctx *ctx);
@@ -430,6 +443,22 @@ int biogpt_hip_wide_chain_device(int device, int32_t epi, int32_t wtype, int32_t
  * device events around launch i alone.  which 0: the wide chain's kernel with the residual epilogue at M rows (16 | M) of K values (32 | K) and N <= 512 columns;
  * which 1: the BioGPT-base matrix-core kernel at out_proj (M 1024, K 1024) or fc2 (M 1024, K 4096).  For tools/wide_chain_bench.py. */
 int biogpt_hip_wide_chain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t reps, float *us_out);
+/* One stand-alone launch of the float chain's linear stage over caller-supplied weights and f32 columns, through the launch code of the engine's own passes.
+ * epi: 0 QKV (M == 3 K, 64 | K: K is d_model, heads of 64), 1 RESID, 2 GELU (f32 rows through the fp16 table), 3 LOGITS; K a multiple of 32; any M.  wtype 0:
+ * w_rows is M rows of K f32, 1: of K f16 (bits); x [N][K] f32; ln_w / ln_b [K] (both or neither): the LayerNorm producer runs in front of the stage; cfg 0 .. 2: a
+ * tile shape (4 rows x 8 columns, 32 x 8, 64 x 16 a workgroup), -1 the launch's own choice; bias [M] (not 3); resid [N][M] (1); epi 0: exactly one of dev_state (4
+ * words; one slot) and seq_states ([N][8] words; col_mode 0: column i writes slot i, 1: slot seq_id) at position n_past, and one layer's k_slots / v_slots
+ * [n_slots][K / 64][P][64], updated in place.  out comes back whole, as allocated and preset to 0xff bytes: cols = N rounded up to 16, plus 1; epi 0: [cols][K]
+ * (the q rows), otherwise [cols][ldo] with ldo = M rounded up to 128, plus 16; ln_out (may be NULL) [cols][K]: the producer's rows, likewise.  launched [8] (may
+ * be NULL): threads, grid x, grid y, LDS bytes, cols, ldo, cfg, 0.  For tests of the kernel itself and tools. */
+int biogpt_hip_fchain_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, const void *w_rows, const float *x, const float *ln_w,
+                             const float *ln_b, const float *bias, const float *resid, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t P,
+                             int32_t n_slots, float *k_slots, float *v_slots, float *out, float *ln_out, int32_t *launched);
+/* A linear stage of a float file alone, timed: one untimed launch, then reps in [1, 10000] launches on device memory of ordinary values, us_out[i]: microseconds between
+ * two device events around launch i alone.  which 0: the float chain's kernel with the residual epilogue at M rows of K values (32 | K), N <= 512 columns and
+ * tile shape cfg (-1: the launch's choice); which 1: the generic mat-vec kernel, as a prompt pass of the context's own columns launches it.  For
+ * tools/float_chain_bench.py. */
+int biogpt_hip_fchain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, int32_t reps, float *us_out);
 /* One decode attention launch of N columns behind a shared prefix over caller-supplied inputs (head size 64, one layer): q [N][H * 64]; k_slots / v_slots
  * [N + 1][H][P][64], slot i column i's own and slot N the prefix's; seq_states [N][8] words as the engine's column states (n_past, ..., pad[0] = shared rows,
  * pad[1] = their slot).  which 0: the existing attn_fast_kernel<4, false, true>; 1: attn_prefix_kernel<8>, eight columns per workgroup (one shared range for
