@@ -930,6 +930,7 @@ SYMBOLS = [
     ("biogpt_hip_wide_chain_bench", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P]),
     ("biogpt_hip_fchain_device", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 5),
     ("biogpt_hip_fchain_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P]),
+    ("biogpt_hip_embed_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 4 + [C.c_int32] * 5 + [_P] + [C.c_int32] * 2 + [_P] * 3 + [C.c_int32] + [_P] * 3),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_attn_prefix_bench", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     ("biogpt_hip_hidden", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
@@ -1164,6 +1165,54 @@ def fchain_device(epi, wtype, M, K, N, w_rows, x, ln_w=None, ln_b=None, bias=Non
                                         ptr(x, np.float32), ptr(ln_w, np.float32), ptr(ln_b, np.float32), ptr(bias, np.float32), ptr(resid, np.float32),
                                         ptr(dev_state, np.int32), ptr(seq_states, np.int32), int(col_mode), int(P), n_slots, o("k"), o("v"), o("out"), o("ln"),
                                         launched.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    res["launched"] = launched
+    return res
+
+
+EMBED_STAGES = {"LN": 0, "POOL": 1, "HEAD": 2}
+EMBED_POOLING = {"none": 0, "last": 1, "mean": 2}
+
+
+def embed_device(stage, x, ln_w=None, ln_b=None, seq_states=None, slot_div=0, P=0, n_out_rows=None, pooling="none", normalize=False, lens=None, pass_cols=None,
+                 w=None, b=None, n_out=None, device=0):
+    """One stand-alone run of a stage of the embedding tail (biogpt_hip_embed_device; include/biogpt_hip.h has the inputs of each stage), through the launch code
+    of the engine's own calls.  stage "LN": x float32 [N, W], ln_w / ln_b [W], optionally seq_states int32 [N, 8] (n_past in word 0, seq_id in word 3) with
+    slot_div, P and n_out_rows.  "POOL": x the rows of all passes [n_rows, W], pass_cols the columns of each pass, seq_states, lens, pooling by name, normalize.
+    "HEAD": x [n_rows, W], w [n_out, W], b [n_out] or None.  Returns a dict of the outputs WHOLE as the probe allocated them, the guard row included and preset
+    to 0xff bytes: "out" float32 [rows + 1, W] ([n_rows + 1, n_out] for HEAD), "acc" float64 [n_seqs + 1, W] (mean pooling), "launched" (kernel or template,
+    threads, grid x, grid y, LDS bytes, pool_finish_kernel's grid or 0, pool_rows_kernel launches, 0).  Raises BiogptError on a refusal."""
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n_rows, W = (int(v) for v in x.shape)
+    mode = EMBED_POOLING[pooling]
+    n_seqs = 0 if lens is None else len(lens)
+    n_passes = 0 if pass_cols is None else len(pass_cols)
+    res = {}
+    if stage == "LN":
+        n_out_rows = n_rows if n_out_rows is None else int(n_out_rows)
+        res["out"] = np.zeros((max(n_out_rows, 0) + 1, W), np.float32)
+    elif stage == "POOL":
+        res["out"] = np.zeros(((n_rows if mode == 0 else n_seqs) + 1, W), np.float32)
+        if mode == 2:
+            res["acc"] = np.zeros((n_seqs + 1, W), np.float64)
+    else:
+        n_out = int(np.shape(w)[0]) if n_out is None else int(n_out)
+        res["out"] = np.zeros((n_rows + 1, max(n_out, 1)), np.float32)
+    launched = np.zeros(8, np.int32)
+    rc = lib().biogpt_hip_embed_device(int(device), EMBED_STAGES[stage], W, n_rows, x.ctypes.data, ptr(ln_w, np.float32), ptr(ln_b, np.float32), ptr(seq_states, np.int32),
+                                       int(slot_div), int(P), int(n_out_rows or 0), mode, int(normalize), ptr(lens, np.int32), n_seqs, n_passes, ptr(pass_cols, np.int32),
+                                       ptr(w, np.float32), ptr(b, np.float32), int(n_out or 0), res["out"].ctypes.data, res["acc"].ctypes.data if "acc" in res else None,
+                                       launched.ctypes.data)
     if rc != 0:
         raise BiogptError(_err())
     res["launched"] = launched

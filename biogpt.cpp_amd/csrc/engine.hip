@@ -1545,6 +1545,48 @@ bool enqueue_layer(PassLaunch &k, int l) {
     return true;
 }
 
+// ---- the launches of the embedding tail (kernels_embed.hip.h) ----
+// enqueue_final, embed_batch_once and enqueue_head launch through these, and so does the probe of the four kernels alone (biogpt_hip_embed_device,
+// engine_probe.inc): the probe's launch is the engine's.  rep: null, or what was launched (kernel: EK_*; for ln_rows_kernel the template argument).
+enum EmbedKernel : int { EK_LN_GENERIC = 0, EK_POOL_ROWS = 1, EK_POOL_FINISH = 2, EK_HEAD_ROWS = 3, EK_LN_1024 = 1024 };
+struct EmbedLaunch { int32_t kernel, threads, grid_x, grid_y, lds; };      // lds: dynamic LDS bytes
+constexpr size_t HEAD_LDS_MAX = 65536;      // the dynamic LDS a launch gets without an attribute of its own
+// head_rows_kernel keeps 8 rows of the width in LDS: the widths it can be launched at (no HIP call: an argument error of the call)
+inline bool check_head_width(int W) {
+    if ((size_t)bgk::HEAD_ROWS * (size_t)W * 4 > HEAD_LDS_MAX)
+        BG_FAIL(false, "a head over rows of width %d needs %zu bytes of LDS (%d rows x 4 bytes): more than the %zu a launch gets (width at most %zu)", W,
+                (size_t)bgk::HEAD_ROWS * (size_t)W * 4, bgk::HEAD_ROWS, HEAD_LDS_MAX, HEAD_LDS_MAX / 4 / bgk::HEAD_ROWS);
+    return true;
+}
+inline hipError_t launch_ln_rows(hipStream_t st, const float *x, int ldx, int K, int N, const float *lw, const float *lb, float *out, const bgk::SeqState *cols,
+                                 int slot_div, int P, EmbedLaunch *rep = nullptr) {
+    if (rep) *rep = EmbedLaunch{K == 1024 ? EK_LN_1024 : EK_LN_GENERIC, 256, N, 1, 0};
+    if (K == 1024) hipLaunchKernelGGL((bgk::ln_rows_kernel<1024>), dim3(N), dim3(256), 0, st, x, ldx, K, lw, lb, 1e-5f, 1.0 / 1024.0, out, cols, slot_div, P);
+    else hipLaunchKernelGGL((bgk::ln_rows_kernel<0>), dim3(N), dim3(256), 0, st, x, ldx, K, lw, lb, 1e-5f, 1.0 / (double)K, out, cols, slot_div, P);
+    return hipGetLastError();
+}
+inline hipError_t launch_pool_rows(hipStream_t st, const float *rows, int n_cols, int W, const bgk::SeqState *cols, const int32_t *lens, int mode, float *out,
+                                   double *acc, EmbedLaunch *rep = nullptr) {
+    const dim3 grid((unsigned)((W + 63) / 64), (unsigned)n_cols);
+    if (rep) *rep = EmbedLaunch{EK_POOL_ROWS, 256, (int32_t)grid.x, (int32_t)grid.y, 0};
+    hipLaunchKernelGGL(bgk::pool_rows_kernel, grid, dim3(256), 0, st, rows, n_cols, W, cols, lens, mode, out, acc);
+    return hipGetLastError();
+}
+// does a call launch pool_finish_kernel at all: when there is a mean to take or a row to normalise
+inline bool pool_needs_finish(const double *acc, int normalize) { return acc != nullptr || normalize != 0; }
+inline hipError_t launch_pool_finish(hipStream_t st, float *out, int n_rows, int W, const double *acc, const int32_t *lens, int normalize, EmbedLaunch *rep = nullptr) {
+    if (rep) *rep = EmbedLaunch{EK_POOL_FINISH, 256, n_rows, 1, 0};
+    hipLaunchKernelGGL(bgk::pool_finish_kernel, dim3((unsigned)n_rows), dim3(256), 0, st, out, W, acc, lens, normalize);
+    return hipGetLastError();
+}
+inline hipError_t launch_head_rows(hipStream_t st, const float *x, int n_rows, int W, const float *w, const float *b, int n_out, float *out, EmbedLaunch *rep = nullptr) {
+    const int grid = (n_rows + bgk::HEAD_ROWS - 1) / bgk::HEAD_ROWS;
+    const size_t lds = (size_t)bgk::HEAD_ROWS * W * 4;
+    if (rep) *rep = EmbedLaunch{EK_HEAD_ROWS, 256, grid, 1, (int32_t)lds};
+    hipLaunchKernelGGL(bgk::head_rows_kernel, dim3(grid), dim3(256), lds, st, x, n_rows, W, w, b, n_out, out);
+    return hipGetLastError();
+}
+
 // the final stage of a pass on the residual stream c->x: the rows the pass names, LayerNorm + lm_head (or the hidden rows in front of it)
 bool enqueue_final(PassLaunch &k) {
     using Rows = ForwardPass::Rows;
@@ -1556,9 +1598,7 @@ bool enqueue_final(PassLaunch &k) {
         const float *lw = dev_vec(c, c->plan.ln_w), *lb = dev_vec(c, c->plan.ln_b);
         const int div = k.pass.hid.scatter_div;
         const bgk::SeqState *sc = div > 0 ? k.seq : nullptr;
-        if (D == 1024) hipLaunchKernelGGL((bgk::ln_rows_kernel<1024>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / 1024.0, ln_out, sc, div, k.P);
-        else hipLaunchKernelGGL((bgk::ln_rows_kernel<0>), dim3(N), dim3(256), 0, st, c->x, D, D, lw, lb, 1e-5f, 1.0 / (double)D, ln_out, sc, div, k.P);
-        HIP_TRY(false, hipGetLastError());
+        HIP_TRY(false, launch_ln_rows(st, c->x, D, D, N, lw, lb, ln_out, sc, div, k.P));
     }
     if (rows == Rows::None || rows == Rows::Hidden) return true;   // prompt columns: only the KV rows matter; hidden rows: no lm_head
     const MatSlot &m = c->plan.lm_head;
@@ -3629,10 +3669,7 @@ static bool check_head_values(const biogpt_hip_embed_opts &o, int D) {
 }
 
 static bool enqueue_head(biogpt_hip_ctx *c, const float *rows, int n_rows, const float *w, const float *b, int n_out, float *out) {
-    const int D = c->hp.d_model;
-    hipLaunchKernelGGL(bgk::head_rows_kernel, dim3((n_rows + bgk::HEAD_ROWS - 1) / bgk::HEAD_ROWS), dim3(256), (size_t)bgk::HEAD_ROWS * D * 4, c->stream,
-                       rows, n_rows, D, w, b, n_out, out);
-    HIP_TRY(false, hipGetLastError());
+    HIP_TRY(false, launch_head_rows(c->stream, rows, n_rows, c->hp.d_model, w, b, n_out, out));
     return true;
 }
 
@@ -3667,6 +3704,7 @@ static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
     if (session_refuses(ctx)) return -1;
     const auto &hp = ctx->hp;
+    if (o.n_out > 0 && !check_head_width(hp.d_model)) return -1;      // (the wide and the float gates admit any d_model of 64 n_head)
     if (!check_fast_chain(ctx, "batched embedding", true)) return -1;
     if (o.layer > hp.n_layer) BG_FAIL(-1, "layer (%d) must be in [-1, n_layer = %d]", o.layer, hp.n_layer);
     size_t total = 0;
@@ -3721,16 +3759,12 @@ static int embed_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
                 if (!hs.ln_out) HIP_TRY(false, hipMemcpyAsync(d_out + flat0 * D, ctx->x, (size_t)n_cols * D * 4, hipMemcpyDeviceToDevice, st));
                 return true;
             }
-            hipLaunchKernelGGL(bgk::pool_rows_kernel, dim3((unsigned)((D + 63) / 64), n_cols), dim3(256), 0, st, rows, n_cols, (int)D, ctx->cols, d_lens, o.pooling,
-                               d_pool, d_acc);
-            HIP_TRY(false, hipGetLastError());
+            HIP_TRY(false, launch_pool_rows(st, rows, n_cols, (int)D, ctx->cols, d_lens, o.pooling, d_pool, d_acc));
             return true;
         }))
         return -2;
-    if (d_acc || o.normalize) {      // the mean of every accumulator row; the L2 normalisation of every output row
-        hipLaunchKernelGGL(bgk::pool_finish_kernel, dim3((unsigned)n_rows), dim3(256), 0, st, d_pool ? d_pool : d_out, (int)D, d_acc, d_lens, o.normalize);
-        HIP_TRY(-2, hipGetLastError());
-    }
+    if (pool_needs_finish(d_acc, o.normalize))      // the mean of every accumulator row; the L2 normalisation of every output row
+        HIP_TRY(-2, launch_pool_finish(st, d_pool ? d_pool : d_out, (int)n_rows, (int)D, d_acc, d_lens, o.normalize));
     if (d_pool && o.n_out > 0 && !enqueue_head(ctx, d_pool, n_seqs, d_w, d_b, o.n_out, d_out)) return -2;
     HIP_TRY(-2, hipMemcpyAsync(out_host, d_out, n_rows * W * 4, hipMemcpyDeviceToHost, st));
     if (!wait_stream(ctx)) return -2;

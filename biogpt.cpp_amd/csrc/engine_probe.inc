@@ -1821,3 +1821,131 @@ int biogpt_hip_fchain_bench(int device, int32_t which, int32_t wtype, int32_t M,
     HIP_TRY(-2, e);
     return 0;
 }
+
+// The four kernels of the embedding tail (kernels_embed.hip.h) alone, over caller-supplied rows, through launch_ln_rows / launch_pool_rows / launch_pool_finish /
+// launch_head_rows -- the helpers of enqueue_final, embed_batch_once and enqueue_head -- so the probe's launch is the engine's.  No model, no context.
+// stage 0 LN: x [n_rows][W], ln_w / ln_b [W]; W == 1024 takes ln_rows_kernel<1024>, any other width <0>.  seq_states (may be NULL) [n_rows][8] words with slot_div
+//   and P: row i lands at (seq_id / slot_div) * P + n_past of n_out_rows rows; without states n_out_rows == n_rows.  out [n_out_rows + 1][W].
+// stage 1 POOL: mode 0 NONE, 1 LAST, 2 MEAN; x the rows of n_passes passes one behind the other, pass_cols [n_passes] columns each (n_rows in all), seq_states
+//   [n_rows][8] words (seq_id, n_past), lens [n_seqs].  LAST / MEAN: pool_rows_kernel once per pass in stream order (MEAN: on an accumulator zeroed first), then
+//   pool_finish_kernel if there is a mean or a normalisation; out [n_seqs + 1][W], acc (MEAN) [n_seqs + 1][W] doubles.  NONE (with normalize): the rows themselves
+//   are normalised; out [n_rows + 1][W].
+// stage 2 HEAD: x [n_rows][W], w [n_out][W], b [n_out] or NULL; out [n_rows + 1][n_out].
+// Every output comes back WHOLE as allocated and preset to 0xff bytes: the last row is a guard row.  launched [8]: the kernel (ln_rows_kernel's template argument
+// 1024 / 0, 1 pool_rows_kernel, 3 head_rows_kernel), threads, grid x, grid y, dynamic LDS bytes (POOL: of the last pass's launch), the grid of pool_finish_kernel
+// (0: not launched), the number of pool_rows_kernel launches, 0.
+int biogpt_hip_embed_device(int device, int32_t stage, int32_t W, int32_t n_rows, const float *x, const float *ln_w, const float *ln_b, const int32_t *seq_states,
+                            int32_t slot_div, int32_t P, int32_t n_out_rows, int32_t mode, int32_t normalize, const int32_t *lens, int32_t n_seqs, int32_t n_passes,
+                            const int32_t *pass_cols, const float *w, const float *b, int32_t n_out, float *out, double *acc, int32_t *launched) {
+    clear_error();
+    if (stage < 0 || stage > 2) BG_FAIL(-1, "stage %d is no stage (0 LN, 1 POOL, 2 HEAD)", stage);
+    if (W < 4 || W > (1 << 16) || W % 4 != 0) BG_FAIL(-1, "W must be a multiple of 4 in [4, %d] (got %d)", 1 << 16, W);
+    if (n_rows < 1 || n_rows > (stage == 1 ? 1 << 16 : 512)) BG_FAIL(-1, "n_rows must be in [1, %d] (the columns of a pass; POOL: of all passes)", stage == 1 ? 1 << 16 : 512);
+    if (!x || !out) BG_FAIL(-1, "x or out is NULL");
+    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
+    size_t rows_out = 0, ld_out = (size_t)W;
+    if (stage == 0) {
+        if (!ln_w || !ln_b) BG_FAIL(-1, "ln_w or ln_b is NULL");
+        if (!hs) {
+            if (n_out_rows != n_rows) BG_FAIL(-1, "n_out_rows must be n_rows without seq_states");
+        } else {
+            if (slot_div < 1) BG_FAIL(-1, "slot_div must be at least 1");
+            if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+            if (n_out_rows < 1 || n_out_rows > (1 << 16)) BG_FAIL(-1, "n_out_rows must be in [1, %d]", 1 << 16);
+            std::set<long> seen;      // every row inside the output, no two columns on one row
+            for (int i = 0; i < n_rows; i++) {
+                if (hs[i].seq_id < 0) BG_FAIL(-1, "column %d: seq_id %d is negative", i, hs[i].seq_id);
+                if (hs[i].n_past < 0 || hs[i].n_past >= P) BG_FAIL(-1, "column %d: position %d outside [0, P)", i, hs[i].n_past);
+                const long r = (long)(hs[i].seq_id / slot_div) * P + hs[i].n_past;
+                if (r >= n_out_rows) BG_FAIL(-1, "column %d: row %ld outside [0, n_out_rows)", i, r);
+                if (!seen.insert(r).second) BG_FAIL(-1, "column %d: a second column writes row %ld", i, r);
+            }
+        }
+        rows_out = (size_t)n_out_rows;
+    } else if (stage == 1) {
+        if (mode < bgk::POOL_NONE || mode > bgk::POOL_MEAN) BG_FAIL(-1, "unknown mode (%d): 0 none, 1 last token, 2 mean", mode);
+        if (normalize != 0 && normalize != 1) BG_FAIL(-1, "normalize (%d) must be 0 or 1", normalize);
+        if (mode == bgk::POOL_NONE && !normalize) BG_FAIL(-1, "mode 0 without normalize launches nothing");
+        if (mode == bgk::POOL_MEAN && !acc) BG_FAIL(-1, "acc is NULL with mode 2");
+        if (mode != bgk::POOL_NONE) {
+            if (!lens || !hs || !pass_cols) BG_FAIL(-1, "lens, seq_states or pass_cols is NULL");
+            if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");
+            if (n_passes < 1 || n_passes > n_rows) BG_FAIL(-1, "n_passes must be in [1, n_rows]");
+            for (int s = 0; s < n_seqs; s++)
+                if (lens[s] < 1) BG_FAIL(-1, "lens[%d] must be at least 1", s);
+            long at = 0;
+            for (int p = 0; p < n_passes; p++) {      // the layouts pack_column_passes produces: a sequence's columns consecutive, at consecutive positions below its length, up to its last position or the pass's end
+                if (pass_cols[p] < 1 || pass_cols[p] > 512 || at + pass_cols[p] > n_rows) BG_FAIL(-1, "pass_cols[%d] = %d: a pass has 1 .. 512 columns, the passes n_rows in all", p, pass_cols[p]);
+                std::set<int> done;
+                for (long i = at; i < at + pass_cols[p]; i++) {
+                    const int s = hs[i].seq_id, pos = hs[i].n_past;
+                    if (s < 0 || s >= n_seqs) BG_FAIL(-1, "column %ld: seq_id %d outside [0, n_seqs)", i, s);
+                    if (pos < 0 || pos >= lens[s]) BG_FAIL(-1, "column %ld: position %d at or past lens[%d] = %d", i, pos, s, lens[s]);
+                    if (i > at && hs[i - 1].seq_id == s) {
+                        if (pos != hs[i - 1].n_past + 1) BG_FAIL(-1, "column %ld: positions of sequence %d not consecutive (%d after %d)", i, s, pos, hs[i - 1].n_past);
+                    } else if (!done.insert(s).second) BG_FAIL(-1, "column %ld: the columns of sequence %d are not consecutive in pass %d", i, s, p);
+                }
+                for (long i = at + 1; i < at + pass_cols[p]; i++) {      // a run ends with its sequence or with the pass (pool_rows_kernel would add the columns behind it to its sequence)
+                    const int s = hs[i - 1].seq_id;
+                    if (hs[i].seq_id != s && hs[i - 1].n_past != lens[s] - 1)
+                        BG_FAIL(-1, "column %ld: sequence %d stops at position %d, short of lens[%d] - 1 = %d, inside pass %d", i - 1, s, hs[i - 1].n_past, s, lens[s] - 1, p);
+                }
+                at += pass_cols[p];
+            }
+            if (at != n_rows) BG_FAIL(-1, "pass_cols sum to %ld, not n_rows = %d", at, n_rows);
+        }
+        rows_out = mode == bgk::POOL_NONE ? (size_t)n_rows : (size_t)n_seqs;
+    } else {
+        if (n_out < 1 || n_out > 256) BG_FAIL(-1, "n_out (%d) must be in [1, 256]", n_out);
+        if (!w) BG_FAIL(-1, "w is NULL");
+        if (!check_head_width(W)) return -1;
+        rows_out = (size_t)n_rows; ld_out = (size_t)n_out;
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    const bool pool = stage == 1 && mode != bgk::POOL_NONE, mean = pool && mode == bgk::POOL_MEAN;
+    const size_t x_b = (size_t)n_rows * W * 4, out_b = (rows_out + 1) * ld_out * 4, acc_b = mean ? (size_t)(n_seqs + 1) * W * 8 : 0;
+    ByteLayout l;
+    const size_t o_x = l.part(x_b), o_lw = l.part(stage == 0 ? (size_t)W * 4 : 0), o_lb = l.part(stage == 0 ? (size_t)W * 4 : 0),
+                 o_st = l.part(hs ? sizeof(bgk::SeqState) * (size_t)n_rows : 0), o_lens = l.part(pool ? (size_t)n_seqs * 4 : 0),
+                 o_w = l.part(stage == 2 ? (size_t)n_out * W * 4 : 0), o_b = l.part(stage == 2 && b ? (size_t)n_out * 4 : 0), o_acc = l.part(acc_b), o_out = l.part(out_b);
+    DeviceBytes d;
+    if (!d.alloc(l.bytes())) return -2;
+    HIP_TRY(-2, hipMemset(d.p + o_acc, 0xff, l.bytes() - o_acc));        // the accumulator and the output, with their guard rows
+    HIP_TRY(-2, hipMemcpy(d.p + o_x, x, x_b, hipMemcpyHostToDevice));
+    if (hs && stage != 2) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)n_rows, hipMemcpyHostToDevice));
+    EmbedLaunch k{}, fin{};
+    int32_t n_launches = 0;
+    const bgk::SeqState *d_st = d.at<const bgk::SeqState>(o_st);
+    float *d_out = d.at<float>(o_out);
+    if (stage == 0) {
+        HIP_TRY(-2, hipMemcpy(d.p + o_lw, ln_w, (size_t)W * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_lb, ln_b, (size_t)W * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, launch_ln_rows(0, d.at<const float>(o_x), W, W, n_rows, d.at<const float>(o_lw), d.at<const float>(o_lb), d_out, hs ? d_st : nullptr, hs ? slot_div : 0, P, &k));
+    } else if (stage == 1) {
+        double *d_acc = mean ? d.at<double>(o_acc) : nullptr;
+        if (pool) {
+            HIP_TRY(-2, hipMemcpy(d.p + o_lens, lens, (size_t)n_seqs * 4, hipMemcpyHostToDevice));
+            if (d_acc) HIP_TRY(-2, hipMemsetAsync(d_acc, 0, (size_t)n_seqs * W * 8, 0));
+            size_t at = 0;
+            for (int p = 0; p < n_passes; p++) {
+                HIP_TRY(-2, launch_pool_rows(0, d.at<const float>(o_x) + at * W, pass_cols[p], W, d_st + at, d.at<const int32_t>(o_lens), mode, d_out, d_acc, &k));
+                at += (size_t)pass_cols[p];
+                n_launches++;
+            }
+        } else {
+            HIP_TRY(-2, hipMemcpyAsync(d_out, d.p + o_x, x_b, hipMemcpyDeviceToDevice, 0));      // (a direct call's rows are written where they are normalised)
+        }
+        if (pool_needs_finish(d_acc, normalize))
+            HIP_TRY(-2, launch_pool_finish(0, d_out, (int)rows_out, W, d_acc, d.at<const int32_t>(o_lens), normalize, &fin));
+    } else {
+        HIP_TRY(-2, hipMemcpy(d.p + o_w, w, (size_t)n_out * W * 4, hipMemcpyHostToDevice));
+        if (b) HIP_TRY(-2, hipMemcpy(d.p + o_b, b, (size_t)n_out * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, launch_head_rows(0, d.at<const float>(o_x), n_rows, W, d.at<const float>(o_w), b ? d.at<const float>(o_b) : nullptr, n_out, d_out, &k));
+    }
+    HIP_TRY(-2, hipDeviceSynchronize());
+    const int32_t rep[8] = {k.kernel, k.threads, k.grid_x, k.grid_y, k.lds, fin.grid_x, n_launches, 0};
+    if (launched) std::memcpy(launched, rep, sizeof(rep));
+    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, out_b, hipMemcpyDeviceToHost));
+    if (mean) HIP_TRY(-2, hipMemcpy(acc, d.p + o_acc, acc_b, hipMemcpyDeviceToHost));
+    return 0;
+}

@@ -454,6 +454,21 @@ int biogpt_hip_wide_chain_bench(int device, int32_t which, int32_t wtype, int32_
 int biogpt_hip_fchain_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, const void *w_rows, const float *x, const float *ln_w,
                              const float *ln_b, const float *bias, const float *resid, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t P,
                              int32_t n_slots, float *k_slots, float *v_slots, float *out, float *ln_out, int32_t *launched);
+/* One stand-alone run of a stage of the embedding tail (ln_rows_kernel<1024> / <0>, pool_rows_kernel, pool_finish_kernel, head_rows_kernel) over caller-supplied
+ * rows, through the launch code of biogpt_hip_hidden / biogpt_hip_embed_batch.  No model, no context; W a multiple of 4.  stage 0 LN: x [n_rows][W], ln_w / ln_b
+ * [W]; W == 1024 takes the <1024> template, any other width <0>; seq_states (may be NULL) [n_rows][8] words with slot_div >= 1 and P: row i lands at row
+ * (seq_id / slot_div) * P + n_past of n_out_rows (no two on one row); without them n_out_rows == n_rows.  out [n_out_rows + 1][W].  stage 1 POOL: mode 0 none,
+ * 1 last, 2 mean; x: the rows of n_passes passes of pass_cols[p] columns one behind the other (n_rows in all), seq_states [n_rows][8] words (seq_id, n_past),
+ * lens [n_seqs]: within a pass a sequence's columns are consecutive, at consecutive positions below its length, and end at its last position or with the pass.  pool_rows_kernel runs once per pass in stream
+ * order (mean: on an accumulator zeroed first), then pool_finish_kernel when there is a mean or normalize; out [n_seqs + 1][W]; acc (mean) [n_seqs + 1][W]
+ * doubles.  Mode 0 (with normalize): the rows themselves are normalised, out [n_rows + 1][W].  stage 2 HEAD: x [n_rows][W], w [n_out][W], b [n_out] or NULL,
+ * n_out in [1, 256], 8 * W * 4 bytes within the 65536 of LDS a launch gets; out [n_rows + 1][n_out].  Outputs come back whole, as allocated and preset to 0xff
+ * bytes: the last row is a guard row.  launched [8] (may be NULL): the kernel (ln_rows_kernel's template argument 1024 / 0, 1 pool_rows_kernel, 3
+ * head_rows_kernel), threads, grid x, grid y, dynamic LDS bytes (POOL: the last pass's launch), pool_finish_kernel's grid (0: not launched), pool_rows_kernel
+ * launches, 0.  For tests of the kernels themselves. */
+int biogpt_hip_embed_device(int device, int32_t stage, int32_t W, int32_t n_rows, const float *x, const float *ln_w, const float *ln_b, const int32_t *seq_states,
+                            int32_t slot_div, int32_t P, int32_t n_out_rows, int32_t mode, int32_t normalize, const int32_t *lens, int32_t n_seqs, int32_t n_passes,
+                            const int32_t *pass_cols, const float *w, const float *b, int32_t n_out, float *out, double *acc, int32_t *launched);
 /* A linear stage of a float file alone, timed: one untimed launch, then reps in [1, 10000] launches on device memory of ordinary values, us_out[i]: microseconds between
  * two device events around launch i alone.  which 0: the float chain's kernel with the residual epilogue at M rows of K values (32 | K), N <= 512 columns and
  * tile shape cfg (-1: the launch's choice); which 1: the generic mat-vec kernel, as a prompt pass of the context's own columns launches it.  For
