@@ -931,6 +931,7 @@ SYMBOLS = [
     ("biogpt_hip_fchain_device", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 5),
     ("biogpt_hip_fchain_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P]),
     ("biogpt_hip_embed_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 4 + [C.c_int32] * 5 + [_P] + [C.c_int32] * 2 + [_P] * 3 + [C.c_int32] + [_P] * 3),
+    ("biogpt_hip_tail_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 7 + [C.c_int32] * 2 + [_P] + [C.c_int32] * 3 + [_P] * 5),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_attn_prefix_bench", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     ("biogpt_hip_hidden", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
@@ -1216,6 +1217,60 @@ def embed_device(stage, x, ln_w=None, ln_b=None, seq_states=None, slot_div=0, P=
     if rc != 0:
         raise BiogptError(_err())
     res["launched"] = launched
+    return res
+
+
+TAIL_STAGES = {"PARTIALS": 0, "FINISH": 1, "TOPK": 2, "HOST_TOPK": 3, "HOST_BLOCKS": 4, "HOST_FULL": 5}
+
+
+def tail_device(stage, wtype=0, w_rows=None, M=None, x=None, ln_w=None, ln_b=None, row=None, pmax_val=None, pmax_idx=None, nparts=None, k=0, state=(0, 0, 0, 0), n_eval=1,
+                n_positions=8, n_vocab=42384, device=0):
+    """One stand-alone run of a stage of the token tail (biogpt_hip_tail_device; include/biogpt_hip.h has the inputs of each stage), through the launch code of
+    the engine's own calls.  "PARTIALS": w_rows (M rows of 1024 weights in the file's format, wtype 0 for float32), x, ln_w, ln_b -> "row", "pmax_val", "pmax_idx"
+    WHOLE ([M + 16], unwritten entries 0xff bytes), "grid" and "rows_per_part".  "FINISH": pmax_val, pmax_idx, state, n_eval, n_positions, n_vocab -> "block" (the
+    state block whole), "token", "n_past", "n_gen", "recorded" (gen_ids[state's n_gen], or None beyond n_positions).  "TOPK" / "HOST_TOPK" / "HOST_BLOCKS" /
+    "HOST_FULL": row, k (and pmax_val [nparts]) -> "n" (k, -1, or the count found), "vals" / "ids" whole ([80]).  "launched" always.  Raises BiogptError on a refusal."""
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    st = TAIL_STAGES[stage]
+    launched = np.zeros(8, np.int32)
+    res = {"launched": launched}
+    if st == 0:
+        n = int(M if M is not None else (np.shape(w_rows)[0] if w_rows is not None else 0))
+        cap = max(n, 0) + 16
+        out_val, out_idx = np.zeros(cap, np.float32), np.zeros(1, np.int32)
+        part_val, part_idx = np.zeros(cap, np.float32), np.zeros(cap, np.int32)
+        w_ptr = ptr(w_rows, np.float32 if int(wtype) == 0 else np.uint8)
+    elif st == 1:
+        n = int(nparts if nparts is not None else (len(pmax_val) if pmax_val is not None else 0))
+        out_val, out_idx = np.zeros(1, np.float32), np.zeros(4 + 2 * max(int(n_positions), 0) + 16, np.int32)
+        part_val, part_idx = np.zeros(1, np.float32), np.zeros(1, np.int32)
+        w_ptr = None
+    else:
+        n = int(len(row) if row is not None else 0)
+        nparts = int(nparts if nparts is not None else (len(pmax_val) if pmax_val is not None else 0))
+        out_val, out_idx = np.zeros(80, np.float32), np.zeros(80, np.int32)
+        part_val, part_idx = np.zeros(1, np.float32), np.zeros(16, np.int32)
+        w_ptr = None
+    rc = lib().biogpt_hip_tail_device(int(device), st, int(wtype), n, w_ptr, ptr(x, np.float32), ptr(ln_w, np.float32), ptr(ln_b, np.float32), ptr(row, np.float32),
+                                      ptr(pmax_val, np.float32), ptr(pmax_idx, np.int32), int(nparts or 0), int(k), ptr(state, np.int32), int(n_eval), int(n_positions),
+                                      int(n_vocab), out_val.ctypes.data, out_idx.ctypes.data, part_val.ctypes.data, part_idx.ctypes.data, launched.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    if st == 0:
+        res.update(row=out_val, pmax_val=part_val, pmax_idx=part_idx, kernel=int(launched[0]), grid=int(launched[1]), rows_per_part=int(launched[2]))
+    elif st == 1:
+        g0, P = int(np.asarray(state)[1]), int(n_positions)
+        res.update(block=out_idx, n_past=int(out_idx[0]), n_gen=int(out_idx[1]), token=int(out_idx[4]), recorded=int(out_idx[4 + P + g0]) if g0 < P else None)
+    else:
+        res.update(n=int(part_idx[0]), vals=out_val, ids=out_idx, count=part_idx)
     return res
 
 

@@ -514,13 +514,18 @@ int lm_fast_steps(int M, int rps) {
     return steps;
 }
 
+// What a single-column launch of launch_mv was, as the launch itself reports it (null: not asked): 0 lm_stream_kernel, 1 matvec_fast_kernel, 2 matvec_kernel /
+// fdec_kernel; its grid; the rows one workgroup's arg-max partial covers (EPI_LOGITS)
+struct MvLaunch { int32_t kernel, grid, rows_per_part; };
+
 template <int WT, int PRO, int EPI, int K>
-hipError_t launch_fast_k(bgk::MatvecParams p, hipStream_t st, int *grid_out) {
+hipError_t launch_fast_k(bgk::MatvecParams p, hipStream_t st, int *grid_out, MvLaunch *rep = nullptr) {
     constexpr int BPR = K / 32, LPR = BPR < 64 ? BPR : 64, RPS = 64 / LPR;
     const int steps = EPI == bgk::EPI_LOGITS ? lm_fast_steps(p.W.M, RPS) : 1;
     p.rpw = RPS * steps;
     const int grid = (p.W.M + 4 * p.rpw - 1) / (4 * p.rpw);
     if (grid_out) *grid_out = grid;
+    if (rep) *rep = MvLaunch{1, grid, 4 * p.rpw};
     const size_t sm = bgk::matvec_fast_smem_bytes(K, p.rpw);
     if constexpr (EPI == bgk::EPI_LOGITS) {
         if (steps > 1) {
@@ -533,7 +538,7 @@ hipError_t launch_fast_k(bgk::MatvecParams p, hipStream_t st, int *grid_out) {
 }
 
 template <int WT, int PRO, int EPI>
-bool try_launch_fast(const EngineOptions &o, const bgk::MatvecParams &p, hipStream_t st, hipError_t &err, int *grid_out) {
+bool try_launch_fast(const EngineOptions &o, const bgk::MatvecParams &p, hipStream_t st, hipError_t &err, int *grid_out, MvLaunch *rep = nullptr) {
     if (p.N != 1) return false;
     const int K = p.W.K;
     if (EPI == bgk::EPI_QKV && p.D != K) return false;
@@ -545,13 +550,14 @@ bool try_launch_fast(const EngineOptions &o, const bgk::MatvecParams &p, hipStre
             hipLaunchKernelGGL((bgk::lm_stream_kernel<WT>), dim3((blocks + NB - 1) / NB), dim3(512), bgk::lm_stream_smem_bytes(bgk::TypeInfo<WT>::q81), st, p);
             err = hipGetLastError();
             if (grid_out) *grid_out = blocks;
+            if (rep) *rep = MvLaunch{0, blocks, 64};
             return true;
         }
     }
     if (K == 1024) {
-        err = launch_fast_k<WT, PRO, EPI, 1024>(p, st, grid_out);
+        err = launch_fast_k<WT, PRO, EPI, 1024>(p, st, grid_out, rep);
     } else if (K == 4096) {
-        if constexpr (PRO == bgk::PRO_PLAIN) err = launch_fast_k<WT, PRO, EPI, 4096>(p, st, grid_out);
+        if constexpr (PRO == bgk::PRO_PLAIN) err = launch_fast_k<WT, PRO, EPI, 4096>(p, st, grid_out, rep);
         else return false;
     } else {
         return false;
@@ -695,11 +701,12 @@ bool try_launch_fdec(const EngineOptions &o, const bgk::MatvecParams &p, hipStre
 }
 
 template <int WT, int PRO, int EPI>
-hipError_t launch_mv_typed(const EngineOptions &o, const bgk::MatvecParams &p, const MvShape &s, hipStream_t st, int *grid_out) {
+hipError_t launch_mv_typed(const EngineOptions &o, const bgk::MatvecParams &p, const MvShape &s, hipStream_t st, int *grid_out, MvLaunch *rep) {
     if (grid_out) *grid_out = s.grid;
+    if (rep) *rep = MvLaunch{2, s.grid, s.nwaves * s.rpw};
     if constexpr (bgk::TypeInfo<WT>::quant) {
         hipError_t err = hipSuccess;
-        if (try_launch_fast<WT, PRO, EPI>(o, p, st, err, grid_out)) return err;
+        if (try_launch_fast<WT, PRO, EPI>(o, p, st, err, grid_out, rep)) return err;
     } else {
         hipError_t err = hipSuccess;
         if (try_launch_fdec<WT, PRO, EPI>(o, p, st, err)) return err;
@@ -709,15 +716,15 @@ hipError_t launch_mv_typed(const EngineOptions &o, const bgk::MatvecParams &p, c
 
 // o: the options of the context whose launch this is (LM_STREAM, NO_FDEC)
 template <int PRO, int EPI>
-hipError_t launch_mv(const EngineOptions &o, const bgk::MatvecParams &p, const MvShape &s, hipStream_t st, int *grid_out = nullptr) {
+hipError_t launch_mv(const EngineOptions &o, const bgk::MatvecParams &p, const MvShape &s, hipStream_t st, int *grid_out = nullptr, MvLaunch *rep = nullptr) {
     switch (p.W.type) {
-        case T_F32: return launch_mv_typed<bgk::W_F32, PRO, EPI>(o, p, s, st, grid_out);
-        case T_F16: return launch_mv_typed<bgk::W_F16, PRO, EPI>(o, p, s, st, grid_out);
-        case T_Q4_0: return launch_mv_typed<bgk::W_Q4_0, PRO, EPI>(o, p, s, st, grid_out);
-        case T_Q4_1: return launch_mv_typed<bgk::W_Q4_1, PRO, EPI>(o, p, s, st, grid_out);
-        case T_Q5_0: return launch_mv_typed<bgk::W_Q5_0, PRO, EPI>(o, p, s, st, grid_out);
-        case T_Q5_1: return launch_mv_typed<bgk::W_Q5_1, PRO, EPI>(o, p, s, st, grid_out);
-        case T_Q8_0: return launch_mv_typed<bgk::W_Q8_0, PRO, EPI>(o, p, s, st, grid_out);
+        case T_F32: return launch_mv_typed<bgk::W_F32, PRO, EPI>(o, p, s, st, grid_out, rep);
+        case T_F16: return launch_mv_typed<bgk::W_F16, PRO, EPI>(o, p, s, st, grid_out, rep);
+        case T_Q4_0: return launch_mv_typed<bgk::W_Q4_0, PRO, EPI>(o, p, s, st, grid_out, rep);
+        case T_Q4_1: return launch_mv_typed<bgk::W_Q4_1, PRO, EPI>(o, p, s, st, grid_out, rep);
+        case T_Q5_0: return launch_mv_typed<bgk::W_Q5_0, PRO, EPI>(o, p, s, st, grid_out, rep);
+        case T_Q5_1: return launch_mv_typed<bgk::W_Q5_1, PRO, EPI>(o, p, s, st, grid_out, rep);
+        case T_Q8_0: return launch_mv_typed<bgk::W_Q8_0, PRO, EPI>(o, p, s, st, grid_out, rep);
         default: return hipErrorInvalidValue;
     }
 }
@@ -738,6 +745,29 @@ bgk::MatvecParams mv_base(const biogpt_hip_ctx *c, const MatSlot &m, const MvSha
     p.inv_k = 1.0 / (double)m.K;
     p.k_pow2 = (m.K & (m.K - 1)) == 0;
     return p;
+}
+
+// The token tail's launches as helpers over pointers: the engine's sites (enqueue_decode_fused, enqueue_xcols, enqueue_final; enqueue_argmax; eval_topk_once) and
+// the probe of the tail alone (biogpt_hip_tail_device, engine_probe.inc) launch through them, so the probe's launch is the engine's.
+// Final LayerNorm + lm_head of ONE column x [K] into out [M], with the arg-max partial of every workgroup's rows (pmax_val / pmax_idx, grid_out entries) --
+// whichever kernel launch_mv picks for the type and shape.  p: the matrix and the site's own fields (mv_base; st_adv / adv / lineage where the site has them).
+hipError_t launch_lm_head_row(const EngineOptions &o, bgk::MatvecParams p, const MvShape &s, const float *x, const float *ln_w, const float *ln_b, float *out,
+                              float *pmax_val, int32_t *pmax_idx, hipStream_t st, int *grid_out, MvLaunch *rep = nullptr) {
+    p.ln_w = ln_w; p.ln_b = ln_b;
+    p.ldx = p.W.K; p.ldo = p.W.M;
+    p.x = x; p.N = 1; p.out = out;
+    p.pmax_val = pmax_val; p.pmax_idx = pmax_idx;
+    return launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(o, p, s, st, grid_out, rep);
+}
+// argmax_kernel over nparts partials: the id into the state block (next token, gen_ids), the position moved on by n_eval
+hipError_t launch_argmax(const float *pmax_val, const int32_t *pmax_idx, int nparts, bgk::DevState *state, int n_eval, int n_positions, int n_vocab, hipStream_t st) {
+    hipLaunchKernelGGL(bgk::argmax_kernel, dim3(1), dim3(256), 0, st, pmax_val, pmax_idx, nparts, state, n_eval, n_positions, n_vocab);
+    return hipGetLastError();
+}
+// topk_kernel over a row of V logits and the nparts partial maxima its lm_head left: out_val / out_idx [64], out_n [1] (k, or -1: the caller takes topk_full_row)
+hipError_t launch_topk(const float *logits, int V, int k, const float *pmax_val, int nparts, float *out_val, int32_t *out_idx, int32_t *out_n, hipStream_t st) {
+    hipLaunchKernelGGL(bgk::topk_kernel, dim3(1), dim3(1024), 0, st, logits, V, k, pmax_val, nparts, out_val, out_idx, out_n);
+    return hipGetLastError();
 }
 
 hipError_t launch_lnq(const biogpt_hip_ctx *c, const float *x, int N, size_t ln_w, size_t ln_b, int q81, hipStream_t st) {
@@ -971,13 +1001,10 @@ bool enqueue_decode_fused(biogpt_hip_ctx *c, int t_max, int tok_src, int advance
         const MatSlot &m = c->plan.lm_head;
         const MvShape s = mv_shape(m.type, m.M, m.K);
         bgk::MatvecParams p = mv_base(c, m, s);
-        p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
-        p.ldx = D; p.ldo = V; p.x = c->x; p.N = 1; p.out = c->logits;
-        p.pmax_val = c->pmax_val; p.pmax_idx = c->pmax_idx;
         p.st_adv = c->state; p.adv = advance;
         p.lineage = c->seq_dev;
         int lm_grid = 0;
-        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, c->stream, &lm_grid)));
+        HIP_TRY(false, launch_lm_head_row(c->opt, p, s, c->x, dev_vec(c, c->plan.ln_w), dev_vec(c, c->plan.ln_b), c->logits, c->pmax_val, c->pmax_idx, c->stream, &lm_grid));
         if (lm_grid != lm_parts) BG_FAIL(false, "internal: lm_head grid %d != expected %d", lm_grid, lm_parts);
         c->lm_blocks = lm_grid;
     }
@@ -1130,14 +1157,11 @@ bool enqueue_xcols(biogpt_hip_ctx *c, int N, int t_max, bool streams = false) {
     {  // final LayerNorm + lm_head of the last column + per-workgroup arg-max partials
         const MatSlot &m = c->plan.lm_head;
         const MvShape s = mv_shape(m.type, m.M, m.K);
-        bgk::MatvecParams p = mv_base(c, m, s);
-        p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
-        p.ldx = D; p.ldo = V;
-        p.x = c->x + (size_t)(N - 1) * D; p.N = 1; p.out = c->logits;
+        const bgk::MatvecParams p = mv_base(c, m, s);
         if (s.grid > c->pmax_cap) BG_FAIL(false, "internal: arg-max partial buffer too small (%d > %d)", s.grid, c->pmax_cap);
-        p.pmax_val = c->pmax_val; p.pmax_idx = c->pmax_idx;
         int lm_grid = 0;
-        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, c->stream, &lm_grid)));
+        HIP_TRY(false, launch_lm_head_row(c->opt, p, s, c->x + (size_t)(N - 1) * D, dev_vec(c, c->plan.ln_w), dev_vec(c, c->plan.ln_b), c->logits, c->pmax_val, c->pmax_idx,
+                                          c->stream, &lm_grid));
         c->lm_blocks = lm_grid;
     }
     return true;
@@ -1629,18 +1653,17 @@ bool enqueue_final(PassLaunch &k) {
         return true;
     }
     // final LayerNorm + lm_head on the generic kernel; only the rows that are returned (F8)
-    p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
-    p.ldx = D; p.ldo = V;
     if (rows != Rows::Last) {   // eval_all; scoring of the other models
+        p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
+        p.ldx = D; p.ldo = V;
         p.x = c->x; p.N = N; p.out = c->logits_all;
-    } else {
-        p.x = c->x + (size_t)(N - 1) * D; p.N = 1; p.out = c->logits;
-        if (s.grid > c->pmax_cap) BG_FAIL(false, "internal: arg-max partial buffer too small (%d > %d)", s.grid, c->pmax_cap);
-        p.pmax_val = c->pmax_val; p.pmax_idx = c->pmax_idx;
+        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, st)));
+        return true;
     }
+    if (s.grid > c->pmax_cap) BG_FAIL(false, "internal: arg-max partial buffer too small (%d > %d)", s.grid, c->pmax_cap);
     int lm_grid = 0;
-    HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, st, &lm_grid)));
-    if (rows == Rows::Last) c->lm_blocks = lm_grid;
+    HIP_TRY(false, launch_lm_head_row(c->opt, p, s, c->x + (size_t)(N - 1) * D, dev_vec(c, c->plan.ln_w), dev_vec(c, c->plan.ln_b), c->logits, c->pmax_val, c->pmax_idx, st, &lm_grid));
+    c->lm_blocks = lm_grid;
     return true;
 }
 
@@ -1707,9 +1730,7 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
 }
 
 bool enqueue_argmax(biogpt_hip_ctx *c, int n_eval) {
-    hipLaunchKernelGGL(bgk::argmax_kernel, dim3(1), dim3(256), 0, c->stream, c->pmax_val, c->pmax_idx, c->lm_blocks,
-                       c->state, n_eval, c->hp.n_positions);
-    HIP_TRY(false, hipGetLastError());
+    HIP_TRY(false, launch_argmax(c->pmax_val, c->pmax_idx, c->lm_blocks, c->state, n_eval, c->hp.n_positions, c->hp.n_vocab, c->stream));
     return true;
 }
 
@@ -2238,6 +2259,21 @@ static int host_topk_blocks(const float *row, int n, int k, const float *bmax, i
     return sel.have;
 }
 
+// The degenerate rows of biogpt_hip_eval_topk (topk_kernel answered -1: more than TOPK_CAP logits reach its threshold, or fewer than k are comparable): a partial
+// sort of the whole row by the tail's order -- larger value first, equal values: lower id first.  NaNs compare with nothing, so they are ordered behind every
+// comparable value, among themselves by id (a strict weak order: std::partial_sort needs one) -- a row with fewer than k comparable values ends with NaN pairs.
+static void topk_full_row(const float *row, int V, int k, float *vals, int32_t *ids) {
+    std::vector<int32_t> order((size_t)V);
+    for (int i = 0; i < V; i++) order[(size_t)i] = i;
+    std::partial_sort(order.begin(), order.begin() + k, order.end(), [&](int32_t a, int32_t b) {
+        const float va = row[(size_t)a], vb = row[(size_t)b];
+        const bool na = va != va, nb = vb != vb;
+        if (na || nb) return na == nb ? a < b : nb;
+        return va > vb || (va == vb && a < b);
+    });
+    for (int i = 0; i < k; i++) { vals[i] = row[(size_t)order[(size_t)i]]; ids[i] = order[(size_t)i]; }
+}
+
 // A replayed five-launch eval carries the sequence number its FIRST node fetched, forwarded by the last layer and the lm_head as they started: any other
 // number means that the result is not this call's (profiles/two_contexts_r4.txt, profiles/stale_row_r5.txt).  Repair: the device's replay counter is put
 // right and the call is repeated on eager launches (same tokens, same position: the K / V rows are written again with the same values); refetch() then
@@ -2285,9 +2321,7 @@ static int eval_topk_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n,
     float *out_val = reinterpret_cast<float *>(ctx->topk_host);
     int32_t *out_idx = reinterpret_cast<int32_t *>(ctx->topk_host + 64 * 4);
     auto select = [&]() -> bool {
-        hipLaunchKernelGGL(bgk::topk_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->logits, ctx->hp.n_vocab, k, ctx->pmax_val, ctx->lm_blocks,
-                           out_val, out_idx, out_idx + 64);
-        HIP_TRY(false, hipGetLastError());
+        HIP_TRY(false, launch_topk(ctx->logits, ctx->hp.n_vocab, k, ctx->pmax_val, ctx->lm_blocks, out_val, out_idx, out_idx + 64, ctx->stream));
         return true;
     };
     if (!select()) return -2;
@@ -2313,10 +2347,7 @@ static int eval_topk_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n,
     const size_t V = (size_t)ctx->hp.n_vocab;
     std::vector<float> row(V);
     HIP_TRY(-2, hipMemcpy(row.data(), ctx->logits, V * 4, hipMemcpyDeviceToHost));
-    std::vector<int32_t> order(V);
-    for (size_t i = 0; i < V; i++) order[i] = (int32_t)i;
-    std::partial_sort(order.begin(), order.begin() + k, order.end(), [&](int32_t a, int32_t b) { return row[(size_t)a] > row[(size_t)b] || (row[(size_t)a] == row[(size_t)b] && a < b); });
-    for (int i = 0; i < k; i++) { vals_out[i] = row[(size_t)order[(size_t)i]]; ids_out[i] = order[(size_t)i]; }
+    topk_full_row(row.data(), (int)V, k, vals_out, ids_out);
     return k;
 }
 

@@ -1949,3 +1949,131 @@ int biogpt_hip_embed_device(int device, int32_t stage, int32_t W, int32_t n_rows
     if (mean) HIP_TRY(-2, hipMemcpy(acc, d.p + o_acc, acc_b, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// The token tail alone (the lm_head's arg-max partials, argmax_kernel, topk_kernel and the host selections of biogpt_hip_eval_topk), over caller-supplied inputs,
+// through launch_lm_head_row / launch_argmax / launch_topk -- the helpers of enqueue_decode_fused, enqueue_xcols and enqueue_final, of enqueue_argmax and of
+// eval_topk_once -- so the probe's launch is the engine's.  No model, no context.  n: M (PARTIALS), nparts (FINISH), V (the selections).
+// stage 0 PARTIALS: w_rows: n rows of 1024 weights in the file's format (wtype 0 F32, or a block format), x / ln_w / ln_b [1024].  out_val [n + 16] the logits row,
+//   part_val / part_idx [n + 16] the partials.  launched: {kernel (0 lm_stream_kernel, 1 matvec_fast_kernel, 2 matvec_kernel), grid = partials, rows per partial}.
+// stage 1 FINISH: part_in_val / part_in_idx [n] partials, n in [1, 4096]; state [4] (n_past, n_gen, causal, chunk), n_eval, n_positions in [1, 4096].  out_idx
+//   [4 + 2 n_positions + 16]: the probe's state block after the kernel -- the four words, tokens [n_positions], gen_ids [n_positions], 16 guard words; everything
+//   behind the four words preset to 0xff.  n_vocab: the clamp's bound.
+// stage 2 TOPK: row [n], part_in_val [nparts] (1 .. 4096), k in [1, min(64, n)].  out_val / out_idx [64 + 16] the pairs, part_idx [16]: word 0 out_n.
+// stage 3 HOST_TOPK, 4 HOST_BLOCKS (part_in_val: the maxima of the row's ceil(n / 64) 64-row blocks), 5 HOST_FULL (topk_full_row): the same outputs from the host
+//   selections, word 0 of part_idx the count they return; no HIP call at all.
+// Device outputs come back WHOLE as allocated and preset to 0xff bytes.  launched [8]: stage 0 as above; 1: {256, 1}; 2: {1024, 1}; host stages: zeros.
+int biogpt_hip_tail_device(int device, int32_t stage, int32_t wtype, int32_t n, const void *w_rows, const float *x, const float *ln_w, const float *ln_b, const float *row,
+                           const float *part_in_val, const int32_t *part_in_idx, int32_t nparts, int32_t k, const int32_t *state, int32_t n_eval, int32_t n_positions,
+                           int32_t n_vocab, float *out_val, int32_t *out_idx, float *part_val, int32_t *part_idx, int32_t *launched) {
+    clear_error();
+    if (stage < 0 || stage > 5) BG_FAIL(-1, "stage %d is no stage (0 PARTIALS, 1 FINISH, 2 TOPK, 3 HOST_TOPK, 4 HOST_BLOCKS, 5 HOST_FULL)", stage);
+    int32_t rep[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (stage == 0) {
+        const bool block = wtype == T_Q4_0 || wtype == T_Q4_1 || wtype == T_Q5_0 || wtype == T_Q5_1 || wtype == T_Q8_0;
+        if (!block && wtype != T_F32) BG_FAIL(-1, "type %d is neither F32 nor a block format", wtype);
+        if (n < 1 || n > (1 << 17)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 17);
+        if (!w_rows || !x || !ln_w || !ln_b) BG_FAIL(-1, "w_rows, x, ln_w or ln_b is NULL");
+        if (!out_val || !part_val || !part_idx) BG_FAIL(-1, "out_val, part_val or part_idx is NULL");
+        HIP_TRY(-2, hipSetDevice(device));
+        const int M = n, K = 1024;
+        const int q81 = (wtype == T_Q4_1 || wtype == T_Q5_1) ? 1 : 0;
+        const size_t nblk = (size_t)M * (K / QK);
+        const size_t qs_b = block ? nblk * (wtype == T_Q8_0 ? 32 : 16) : (size_t)M * K * 4, sc_b = block ? nblk * (q81 ? 4 : 2) : 0,
+                     qh_b = (wtype == T_Q5_0 || wtype == T_Q5_1) ? nblk * 4 : 0, cap_b = ((size_t)M + 16) * 4;
+        const MvShape s = mv_shape(wtype, M, K);
+        if (s.grid > M + 16) BG_FAIL(-2, "internal: %d partials for %d rows", s.grid, M);
+        ByteLayout l;
+        // (lm_stream_kernel stages a workgroup's scales 16 bytes at a time: the scale array rounded up, as in the arena)
+        const size_t o_qs = l.part(qs_b), o_sc = l.part(sc_b + 16), o_qh = l.part(qh_b), o_x = l.part(K * 4), o_lw = l.part(K * 4), o_lb = l.part(K * 4),
+                     o_out = l.part(cap_b), o_pv = l.part(cap_b), o_pi = l.part(cap_b);
+        DeviceBytes d;
+        if (!d.alloc(l.bytes())) return -2;
+        HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));
+        HIP_TRY(-2, hipMemset(d.p + o_sc, 0, sc_b + 16));
+        {
+            std::vector<uint8_t> qs(qs_b), sc(sc_b), qh(qh_b);
+            repack_rows(wtype, static_cast<const uint8_t *>(w_rows), M, K, qs.data(), sc.data(), qh.data());
+            HIP_TRY(-2, hipMemcpy(d.p + o_qs, qs.data(), qs_b, hipMemcpyHostToDevice));
+            if (sc_b) HIP_TRY(-2, hipMemcpy(d.p + o_sc, sc.data(), sc_b, hipMemcpyHostToDevice));
+            if (qh_b) HIP_TRY(-2, hipMemcpy(d.p + o_qh, qh.data(), qh_b, hipMemcpyHostToDevice));
+        }
+        HIP_TRY(-2, hipMemcpy(d.p + o_x, x, K * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_lw, ln_w, K * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_lb, ln_b, K * 4, hipMemcpyHostToDevice));
+        EngineOptions opt{};
+        opt.load();
+        bgk::MatvecParams p{};
+        p.W.qs = d.p + o_qs; p.W.sc = d.p + o_sc; p.W.qh = qh_b ? d.at<const uint32_t>(o_qh) : nullptr;
+        p.W.type = wtype; p.W.M = M; p.W.K = K;
+        p.upr = s.upr; p.lpr_log2 = s.lpr_log2; p.nit = s.nit; p.rpw = s.rpw;
+        p.eps = 1e-5f; p.D = K; p.dk = 64; p.dk_log2 = 6; p.P = 1;
+        p.inv_k = 1.0 / (double)K; p.k_pow2 = true;
+        int grid = 0;
+        MvLaunch took{-1, 0, 0};
+        HIP_TRY(-2, launch_lm_head_row(opt, p, s, d.at<const float>(o_x), d.at<const float>(o_lw), d.at<const float>(o_lb), d.at<float>(o_out), d.at<float>(o_pv),
+                                       d.at<int32_t>(o_pi), 0, &grid, &took));
+        HIP_TRY(-2, hipDeviceSynchronize());
+        rep[0] = took.kernel; rep[1] = grid; rep[2] = took.rows_per_part;      // as the launch itself reports them
+        if (launched) std::memcpy(launched, rep, sizeof(rep));
+        HIP_TRY(-2, hipMemcpy(out_val, d.p + o_out, cap_b, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(part_val, d.p + o_pv, cap_b, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(part_idx, d.p + o_pi, cap_b, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (stage == 1) {
+        if (n < 1 || n > 4096) BG_FAIL(-1, "nparts must be in [1, 4096] (the partial buffers of a context)");
+        if (!part_in_val || !part_in_idx || !state || !out_idx) BG_FAIL(-1, "part_in_val, part_in_idx, state or out_idx is NULL");
+        if (n_positions < 1 || n_positions > 4096) BG_FAIL(-1, "n_positions must be in [1, 4096]");
+        if (n_vocab < 1) BG_FAIL(-1, "n_vocab must be at least 1");
+        if (state[1] < 0) BG_FAIL(-1, "n_gen %d is negative (gen_ids[n_gen] would be written in front of the block)", state[1]);
+        HIP_TRY(-2, hipSetDevice(device));
+        const size_t st_words = 4 + 2 * (size_t)n_positions + 16;
+        ByteLayout l;
+        const size_t o_pv = l.part((size_t)n * 4), o_pi = l.part((size_t)n * 4), o_st = l.part(st_words * 4);
+        DeviceBytes d;
+        if (!d.alloc(l.bytes())) return -2;
+        HIP_TRY(-2, hipMemset(d.p + o_st, 0xff, st_words * 4));
+        HIP_TRY(-2, hipMemcpy(d.p + o_pv, part_in_val, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_pi, part_in_idx, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_st, state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
+        HIP_TRY(-2, launch_argmax(d.at<const float>(o_pv), d.at<const int32_t>(o_pi), n, d.at<bgk::DevState>(o_st), n_eval, n_positions, n_vocab, 0));
+        HIP_TRY(-2, hipDeviceSynchronize());
+        rep[0] = 256; rep[1] = 1;
+        if (launched) std::memcpy(launched, rep, sizeof(rep));
+        HIP_TRY(-2, hipMemcpy(out_idx, d.p + o_st, st_words * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    // the selections
+    if (n < 1 || n > (1 << 20)) BG_FAIL(-1, "V must be in [1, %d]", 1 << 20);
+    if (k < 1 || k > 64 || k > n) BG_FAIL(-1, "k must be in [1, min(64, V)] (biogpt_hip_eval_topk clamps it to the vocabulary)");
+    if (!row || !out_val || !out_idx || !part_idx) BG_FAIL(-1, "row, out_val, out_idx or part_idx is NULL");
+    if (stage == 2 || stage == 4) {
+        if (!part_in_val) BG_FAIL(-1, "part_in_val is NULL");
+        if (nparts < 1 || nparts > 4096) BG_FAIL(-1, "nparts must be in [1, 4096] (the partial buffers of a context)");
+        if (stage == 4 && nparts != (n + 63) / 64) BG_FAIL(-1, "HOST_BLOCKS walks the row's %d 64-row blocks (got nparts = %d)", (n + 63) / 64, nparts);
+    }
+    if (stage == 2) {
+        HIP_TRY(-2, hipSetDevice(device));
+        ByteLayout l;
+        const size_t o_row = l.part((size_t)n * 4), o_pv = l.part((size_t)nparts * 4), o_ov = l.part(80 * 4), o_oi = l.part(80 * 4), o_on = l.part(16 * 4);
+        DeviceBytes d;
+        if (!d.alloc(l.bytes())) return -2;
+        HIP_TRY(-2, hipMemset(d.p + o_ov, 0xff, l.bytes() - o_ov));
+        HIP_TRY(-2, hipMemcpy(d.p + o_row, row, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, hipMemcpy(d.p + o_pv, part_in_val, (size_t)nparts * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, launch_topk(d.at<const float>(o_row), n, k, d.at<const float>(o_pv), nparts, d.at<float>(o_ov), d.at<int32_t>(o_oi), d.at<int32_t>(o_on), 0));
+        HIP_TRY(-2, hipDeviceSynchronize());
+        rep[0] = 1024; rep[1] = 1;
+        if (launched) std::memcpy(launched, rep, sizeof(rep));
+        HIP_TRY(-2, hipMemcpy(out_val, d.p + o_ov, 80 * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(out_idx, d.p + o_oi, 80 * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(-2, hipMemcpy(part_idx, d.p + o_on, 16 * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    std::memset(out_val, 0xff, 80 * 4); std::memset(out_idx, 0xff, 80 * 4); std::memset(part_idx, 0xff, 16 * 4);
+    if (stage == 3) part_idx[0] = host_topk(row, n, k, out_val, out_idx);
+    else if (stage == 4) part_idx[0] = host_topk_blocks(row, n, k, part_in_val, nparts, out_val, out_idx);
+    else { topk_full_row(row, n, k, out_val, out_idx); part_idx[0] = k; }
+    if (launched) std::memcpy(launched, rep, sizeof(rep));
+    return 0;
+}

@@ -864,8 +864,9 @@ __global__ __launch_bounds__(256) void kv_gather_kernel(const float *cache, floa
 // ---- greedy sampler + token feedback (main.cpp:109-128 with top_k = 1) ----------------------------
 // Finishes the arg-max over the per-block partials of the lm_head kernel, appends the id to
 // gen_ids, makes it the next input token and advances n_past by n_eval (the tokens just evaluated).
+// No comparable partial (every one a NaN, or (-inf, 0x7fffffff) pairs nobody wrote over): id 0, as the fused finishers (kernels_decode.hip.h, kernels_xpipe.hip.h).
 __global__ __launch_bounds__(256) void argmax_kernel(const float *pmax_val, const int32_t *pmax_idx, int nparts,
-                                                     DevState *st, int n_eval, int n_positions) {
+                                                     DevState *st, int n_eval, int n_positions, int n_vocab) {
     __shared__ float sv[256];
     __shared__ int si[256];
     float bv = -INFINITY;
@@ -890,9 +891,11 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float *pmax_val, cons
         int32_t *tokens = state_tokens(st);
         int32_t *gen = tokens + n_positions;
         const int g = st->n_gen;
-        if (g < n_positions) gen[g] = si[0];
+        int tok = si[0];
+        if (tok < 0 || tok >= n_vocab) tok = 0;
+        if (g < n_positions) gen[g] = tok;
         st->n_gen = g + 1;
-        tokens[0] = si[0];
+        tokens[0] = tok;
         st->n_past = st->n_past + n_eval;
     }
 }

@@ -249,8 +249,7 @@ __global__ __launch_bounds__(256) void matvec_fast_kernel(const MatvecParams p) 
             s_tail[64 + f_c * 32 + wave * 8 + f_r] = h2f(p.gelu_tab[f2h(__fadd_rn(e_bias, v))]);  // rpw == 8: 32 rows / workgroup
         } else {
             p.out[(size_t)col * p.ldo + r] = v;
-            best_val = v;
-            best_idx = r;
+            if (v >= best_val) { best_val = v; best_idx = r; }      // (a NaN is never held: the reduction below could put nothing in its place)
         }
     }
     if (EPI == EPI_GELU_Q8) {

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(512) void lm_stream_kernel(const MatvecParams p) {
     const bool mine = lane < 2 * (early ? LE : LL) && my_row < M;
     if (mine) {
         my_val = sum32_in_order(part + lane * DEC_PS);
-        best_val = my_val; best_idx = my_row;
+        if (my_val >= best_val) { best_val = my_val; best_idx = my_row; }      // (a NaN is never held: nothing combined into it below could beat it, and its block's partial would hide the block from every finisher)
     }
     BG_STAMP(5);
 #pragma unroll

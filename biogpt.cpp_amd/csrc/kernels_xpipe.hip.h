@@ -1449,7 +1449,7 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
                 const float v = sum32_in_order(part + lane * DEC_PS);
                 if constexpr (RES) s_S[row - row0] = v;        // staged for the copies below (s_S: no attention runs in this workgroup now)
                 else { XPK(logits)[row] = v; if (XPK(logits_host)) XPK(logits_host)[row] = v; }
-                best_val = v; best_idx = row;
+                if (v >= best_val) { best_val = v; best_idx = row; }      // (a NaN is never held: kernels_lmhead.hip.h)
             }
         }
         if (lm_rank == 0) XP_TAIL(tk, 3);

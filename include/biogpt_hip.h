@@ -469,6 +469,26 @@ int biogpt_hip_fchain_device(int device, int32_t epi, int32_t wtype, int32_t M, 
 int biogpt_hip_embed_device(int device, int32_t stage, int32_t W, int32_t n_rows, const float *x, const float *ln_w, const float *ln_b, const int32_t *seq_states,
                             int32_t slot_div, int32_t P, int32_t n_out_rows, int32_t mode, int32_t normalize, const int32_t *lens, int32_t n_seqs, int32_t n_passes,
                             const int32_t *pass_cols, const float *w, const float *b, int32_t n_out, float *out, double *acc, int32_t *launched);
+/* One stand-alone run of a stage of the token tail -- the kernels every generated id of the single-stream path leaves through, and the host selections of
+ * biogpt_hip_eval_topk -- over caller-supplied inputs, through the launch code of the engine's own calls.  No model, no context.  The tail's order: larger value
+ * first; equal values, lower id first; a NaN is never before anything and nothing is before it.  n is M (stage 0), the number of partials (1) or V (2 .. 5).
+ * stage 0 PARTIALS: the single-token lm_head launch (final LayerNorm + one column of K = 1024, whichever kernel the type and M get) on w_rows, n <= 131072 rows in
+ * the file's format (wtype 0 F32, 2 / 3 / 6 / 7 / 8 the block formats), x / ln_w / ln_b [1024].  out_val [n + 16]: the logits row; part_val / part_idx [n + 16]:
+ * the arg-max partial of each workgroup's rows.  launched: {kernel: 0 lm_stream_kernel, 1 matvec_fast_kernel, 2 matvec_kernel; partials written; rows per partial}.
+ * stage 1 FINISH: argmax_kernel on part_in_val / part_in_idx [n], n in [1, 4096], and a state block of the probe's own: state [4] (n_past, n_gen >= 0, causal,
+ * chunk), n_eval, n_positions in [1, 4096], n_vocab >= 1.  out_idx [4 + 2 n_positions + 16]: the block after the kernel -- the four words, tokens [n_positions]
+ * (word 0: the next token), gen_ids [n_positions], 16 guard words; all but the four words preset to 0xff.  launched: {256, 1}.
+ * stage 2 TOPK: topk_kernel on row [n], n <= 1048576, part_in_val [nparts] (nparts in [1, 4096]; any values: the answer never depends on them, only whether there
+ * is one), k in [1, min(64, n)].  out_val / out_idx [80]: the pairs, part_idx [16]: word 0 is k, or -1 (more than 4096 logits reach the threshold, or fewer than k
+ * values are comparable).  launched: {1024, 1}.
+ * stage 3 HOST_TOPK, 4 HOST_BLOCKS, 5 HOST_FULL: the host selections on the same arguments and outputs, with NO HIP call (they run without a device) -- the one
+ * pass over the row; the walk over the 64-row blocks whose maximum (part_in_val [nparts], nparts == ceil(n / 64), the TRUE maxima of the row's blocks as the
+ * resident launch writes them behind the row) can hold a candidate; the partial sort of the whole row that answers when topk_kernel gives -1 (NaNs behind every
+ * comparable value, by id).  part_idx word 0: the count found (3, 4: < k only when fewer than k values are comparable) or k (5).
+ * Device outputs come back whole, as allocated and preset to 0xff bytes; the host stages preset theirs alike.  launched [8] may be NULL.  For tests of the tail itself. */
+int biogpt_hip_tail_device(int device, int32_t stage, int32_t wtype, int32_t n, const void *w_rows, const float *x, const float *ln_w, const float *ln_b, const float *row,
+                           const float *part_in_val, const int32_t *part_in_idx, int32_t nparts, int32_t k, const int32_t *state, int32_t n_eval, int32_t n_positions,
+                           int32_t n_vocab, float *out_val, int32_t *out_idx, float *part_val, int32_t *part_idx, int32_t *launched);
 /* A linear stage of a float file alone, timed: one untimed launch, then reps in [1, 10000] launches on device memory of ordinary values, us_out[i]: microseconds between
  * two device events around launch i alone.  which 0: the float chain's kernel with the residual epilogue at M rows of K values (32 | K), N <= 512 columns and
  * tile shape cfg (-1: the launch's choice); which 1: the generic mat-vec kernel, as a prompt pass of the context's own columns launches it.  For

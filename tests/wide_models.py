@@ -297,3 +297,117 @@ def compared_rows(O, name, path, n_threads=8):
             lo = o.eval(toks, n_past)
             if compared:
                 yield what, n_past, lo
+
+
+# ---- tied files (tests/test_tail_files.py, tests/test_gpu_tail_calls.py): an lm_head made of copies of a few base rows, so every logit value recurs --------------
+# Classes of rows: four "early" ones share rows 0 .. 63 (a tie inside the first partial block), n_cyc "cyclic" ones take turns from row 64 to row V - 17 (copies in
+# every later 64-row block and every 256-row workgroup: the winner's lowest copy lies in the SECOND partial), four "last" ones share rows V - 16 .. V - 1, the
+# 16-row block of the last partial.  Layout "a" has 32 cyclic classes of 1322 copies (topk_kernel answers), layout "b" 8 of 5288 -- more than topk_kernel's 4096
+# candidate slots whenever one of them wins.  The early and last base rows are longer, so that they win their share of the steps.
+TIED_SEED = {"a": 1, "b": 1}
+TIED_CYC = {"a": 32, "b": 8}
+TIED_EARLY_GAIN, TIED_LAST_GAIN = 1.3, 1.6
+TIED_K = 40
+TAIL_TYPES = QUANT + ["f32"]
+
+
+def tied_classes(layout):
+    n_cyc = TIED_CYC[layout]
+    r = np.arange(V)
+    c = 4 + (r - 64) % n_cyc
+    c[:64] = r[:64] % 4
+    c[V - 16:] = 4 + n_cyc + r[V - 16:] % 4
+    return c
+
+
+def tied(W, layout):
+    n = 4 + TIED_CYC[layout] + 4
+    base = (0.02 * np.random.default_rng(SEED + 400).standard_normal((n, D))).astype(np.float32)
+    base[:4] *= np.float32(TIED_EARLY_GAIN)
+    base[-4:] *= np.float32(TIED_LAST_GAIN)
+    W["output_projection.weight"] = base[tied_classes(layout)]
+
+
+# tail_q8: lm_head rows of the Q8_0 tied file whose first block gets another scale.  An f16 NaN gives a NaN logit at every step; +-inf gives +inf, -inf (by the
+# sign of the block's dot) or NaN (a dot of 0).  NaNs stand in the FIRST finisher lane of blocks 1 and 2 (rows 64, 128: the lowest copies of every cyclic class lie
+# behind them in block 1), in a middle lane of the in-launch kernels' and lm_stream_kernel's groups (row 64 * 3 + 34, the block's next rows behind it) and in the last
+# row; two rows of ONE class (equal codes: equal logits, tied at +-inf) carry +inf, the lower one behind the NaN of block 2; a row of the last block carries -inf.
+TAIL_NAN_ROWS = (64, 128, 64 * 3 + 34, V - 1)
+TAIL_PINF_ROWS = (128 + 2, 128 + 2 + 32 * 40)        # (r - 64) % 32 equal: one class in layout "a"
+TAIL_NINF_ROWS = (V - 14,)
+
+
+def tail_q8_edit(src, dst):
+    hp, vocab, merges, tensors = read_model(src)
+    for t in tensors:
+        if t["name"] == "output_projection.weight":
+            assert t["type"] == 8
+            blk = np.frombuffer(t["raw"], dtype=np.uint8).reshape(V, D // 32, 34).copy()
+            for rows, bits in ((TAIL_NAN_ROWS, 0x7E00), (TAIL_PINF_ROWS, 0x7C00), (TAIL_NINF_ROWS, 0xFC00)):
+                blk[list(rows), 0, 0:2] = np.array([bits], "<u2").view(np.uint8)
+            t["raw"] = blk.tobytes()
+    write_model(dst, hp, vocab, merges, tensors)
+
+
+def build_tail(pkg, d, want):
+    """Write the tied files named in `want` ("tied_a.<type>", "tied_b.<type>", type in TAIL_TYPES, or "tail_q8") into directory d; returns {name: path}."""
+    import os
+    base = os.path.join(str(d), "plain.f32.bin")
+    pkg.write_synthetic(base, **KW)
+    hp, vocab, merges, order, W = load_arrays(base)
+    out = {}
+    for layout in ("a", "b"):
+        types = [n.split(".")[1] for n in want if n.startswith("tied_%s." % layout)] + (["q8_0"] if layout == "a" and "tail_q8" in want else [])
+        if not types:
+            continue
+        T = dict(W)
+        tied(T, layout)
+        f32 = os.path.join(str(d), "tied_%s.f32.bin" % layout)
+        save_arrays(f32, hp, vocab, merges, order, T)
+        del T
+        for typ in dict.fromkeys(types):
+            if typ == "f32":
+                continue
+            path = os.path.join(str(d), "tied_%s.%s.bin" % (layout, typ))
+            pkg.quantize_file(f32, path, typ)
+            if "tied_%s.%s" % (layout, typ) in want:
+                out["tied_%s.%s" % (layout, typ)] = path
+            if layout == "a" and typ == "q8_0" and "tail_q8" in want:
+                out["tail_q8"] = os.path.join(str(d), "tail_q8.bin")
+                tail_q8_edit(path, out["tail_q8"])
+        if "tied_%s.f32" % layout in want:
+            out["tied_%s.f32" % layout] = f32
+        else:
+            os.remove(f32)
+    os.remove(base)
+    return out
+
+
+TAIL_FILES = ["tied_a." + t for t in TAIL_TYPES] + ["tied_b.q4_0", "tail_q8"]
+TAIL_STEPS, TAIL_LONG, TAIL_LONG_STEPS = 6, 264, 4
+
+
+def tail_prompt(name, which=0):
+    """The 8-token prompt of a file's short calls (which 0, 1: the two columns of the batched call); the 264-token one of the calls past 256 keys (which 2)."""
+    seed = 7000 + 10 * sorted(TAIL_FILES).index(name) + which
+    return tokens(seed, TAIL_LONG if which == 2 else 8)
+
+
+def tail_rows(o, prompt, n_steps):
+    """Greedy decoding by the tail's rule on the oracle's rows: yields (n_past of the row's last token + 1, oracle row, id by tail_ref.argmax), the id fed back."""
+    import tail_ref
+    lo = prompt_row(o, prompt)
+    n_past = len(prompt)
+    for _ in range(n_steps):
+        tok = tail_ref.argmax(lo)
+        yield n_past, lo, tok
+        lo = o.eval([tok], n_past)
+        n_past += 1
+
+
+def tail_plan(name):
+    """[(what, prompt, steps)]: the greedy sequences the GPU test compares on file `name`; every row of them is also a row of its top-k comparisons."""
+    plan = [("short", tail_prompt(name, 0), TAIL_STEPS)]
+    if name in ("tied_a.q4_0", "tail_q8"):
+        plan += [("second column", tail_prompt(name, 1), TAIL_STEPS), ("long", tail_prompt(name, 2), TAIL_LONG_STEPS)]
+    return plan
