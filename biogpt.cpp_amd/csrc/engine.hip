@@ -185,6 +185,13 @@ std::vector<uint16_t> gelu_table_f16() {
     return tg;
 }
 
+// the fp16 exp table of ggml_soft_max, built the same way: the loader's, and the attention probes' (engine_probe.inc)
+std::vector<uint16_t> exp_table_f16() {
+    std::vector<uint16_t> te(65536);
+    for (uint32_t i = 0; i < 65536; i++) te[i] = f32_to_f16(expf(f16_to_f32((uint16_t)i)));
+    return te;
+}
+
 int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 int ilog2(int v) { int l = 0; while ((1 << l) < v) l++; return l; }
 
@@ -1897,9 +1904,7 @@ bool upload_weights(biogpt_hip_ctx *c, const ModelFile &mf) {
     if (!put_matrix("output_projection.weight", pl.lm_head, 0, hp.n_vocab, D)) return false;
 
     // fp16 tables, built the way ggml_init builds them [SURVEY A.5]
-    const std::vector<uint16_t> tg = gelu_table_f16();
-    std::vector<uint16_t> te(65536);
-    for (uint32_t i = 0; i < 65536; i++) te[i] = f32_to_f16(expf(f16_to_f32((uint16_t)i)));
+    const std::vector<uint16_t> tg = gelu_table_f16(), te = exp_table_f16();
     HIP_TRY(false, hipMemcpy(c->arena + pl.gelu_tab, tg.data(), 65536 * 2, hipMemcpyHostToDevice));
     HIP_TRY(false, hipMemcpy(c->arena + pl.exp_tab, te.data(), 65536 * 2, hipMemcpyHostToDevice));
     return true;

@@ -1,6 +1,218 @@
 // Kernels reached without a model (tests of the kernels themselves, tools): rows held in host memory go to scratch device memory, the kernel runs as a call
 // launches it, the results come back.  Part of engine.hip's translation unit.  Each entry reads: checks, layout, upload, launch, read back.
 
+// ---- what the probes share --------------------------------------------------------------------------------------------------------------
+// A probe's scratch image: the parts of one device buffer, each named once, in the order they lie in (ByteLayout: every part at a multiple of 16 bytes).
+//   in(src, bytes)    the caller's rows; a null src or no bytes gives an empty part.  own(vector): a host image the probe built itself, kept until the upload
+//   fill(bytes, b)    a part of bytes b (0: zeroed)
+//   out(bytes, init)  an output: everything from the first output to the end of the buffer is preset to 0xff bytes -- guard rows, padding and whatever lies
+//                     behind -- so what a kernel does not write reads as NaN / -1; init: what the launch finds there instead
+// A part that is both (the K / V slots of a QKV stage) is an `in` that is read back.  upload() allocates, presets and copies, in that order; at() and read()
+// serve afterwards.  A size is stated where the part is named and nowhere else.
+extern "C++" {
+struct ProbePart { size_t off = 0, bytes = 0; };
+struct ProbeImage {
+    ByteLayout l;
+    DeviceBytes d;
+    struct Fill { ProbePart p; const void *src; int byte; };
+    std::vector<Fill> fills;
+    std::vector<std::shared_ptr<void>> held;
+    size_t first_out = ~(size_t)0;
+    ProbePart part(size_t bytes, const void *src, int byte) {
+        const ProbePart p{l.part(bytes), bytes};
+        if (bytes) fills.push_back(Fill{p, src, byte});
+        return p;
+    }
+    ProbePart in(const void *src, size_t bytes) { return part(src ? bytes : 0, src, 0); }
+    template <class T> ProbePart own(std::vector<T> v) {
+        auto h = std::make_shared<std::vector<T>>(std::move(v));
+        held.push_back(h);
+        return in(h->data(), h->size() * sizeof(T));
+    }
+    ProbePart fill(size_t bytes, int byte = 0) { return part(bytes, nullptr, byte); }
+    ProbePart out(size_t bytes, const void *init = nullptr) {
+        first_out = std::min(first_out, l.bytes());
+        return init ? in(init, bytes) : ProbePart{l.part(bytes), bytes};
+    }
+    bool upload() {
+        if (!d.alloc(l.bytes())) return false;
+        if (first_out < l.bytes()) HIP_TRY(false, hipMemset(d.p + first_out, 0xff, l.bytes() - first_out));
+        for (const Fill &f : fills) {
+            if (f.src) HIP_TRY(false, hipMemcpy(d.p + f.p.off, f.src, f.p.bytes, hipMemcpyHostToDevice));
+            else HIP_TRY(false, hipMemset(d.p + f.p.off, f.byte, f.p.bytes));
+        }
+        return true;
+    }
+    template <class T> T *at(ProbePart p) const { return d.at<T>(p.off); }
+    bool read(ProbePart p, void *dst) const { return read(p, dst, p.bytes); }
+    bool read(ProbePart p, void *dst, size_t bytes) const {      // (the first `bytes` of a part)
+        if (bytes) HIP_TRY(false, hipMemcpy(dst, d.p + p.off, std::min(bytes, p.bytes), hipMemcpyDeviceToHost));
+        return true;
+    }
+    // in stream order, for what a timed launch finds restored: dst = src; the first `bytes` of a part zeroed
+    hipError_t restore(ProbePart dst, ProbePart src) const { return hipMemcpyAsync(d.p + dst.off, d.p + src.off, std::min(dst.bytes, src.bytes), hipMemcpyDeviceToDevice, 0); }
+    hipError_t clear(ProbePart p, size_t bytes) const { return hipMemsetAsync(d.p + p.off, 0, std::min(bytes, p.bytes), 0); }
+};
+
+static const int32_t PROBE_NO_STATE[4] = {0, 0, 0, 0};      // the context state of a launch that reads column states, or none
+
+// a refusal under the entry's own name from a check that several entries share
+#define PROBE_FAIL(func, ret, ...) do { ::bg::set_error(func, __VA_ARGS__); return ret; } while (0)
+
+// launched [8]: the words a probe reports of its launch, zeros behind them
+static void report_launch(int32_t *launched, std::initializer_list<int32_t> words) {
+    if (!launched) return;
+    std::fill(launched, launched + 8, 0);
+    std::copy(words.begin(), words.end(), launched);
+}
+
+// The column states of a linear stage's probe (chain, wide chain, float chain), refused under the entry's name `func`.  Only QKV reads them: exactly one of
+// dev_state {n_past, ..} (the context's own columns: one slot, column i at n_past + i) and seq_states [N] SeqState words (col_mode 0: column i = slot i; 1:
+// slot seq_id), every column's cache row inside its slot, no two columns on one row.  between (or none): what the entry checks between the arguments and the
+// walk over the columns (the chain probe's route).
+static bool probe_slot_ok(const char *func, int i, int slot, int n_slots) {
+    if (slot < 0 || slot >= n_slots) PROBE_FAIL(func, false, "column %d: slot %d outside [0, n_slots)", i, slot);
+    return true;
+}
+static bool probe_one_slot(const char *func, int n_slots) {
+    if (n_slots != 1) PROBE_FAIL(func, false, "the context's own columns have one slot");
+    return true;
+}
+static bool check_probe_columns(const char *func, bool qkv, int N, const int32_t *dev_state, const int32_t *seq_states, int col_mode, int P, int n_slots,
+                                const void *k_slots, const void *v_slots, const std::function<bool()> &between = nullptr) {
+    static_assert(sizeof(bgk::SeqState) == 32 && sizeof(bgk::DevState) == 16, "eight words per column state, four of context state");
+    const bool batch = seq_states != nullptr;
+    if (!qkv) {
+        if (dev_state || batch) PROBE_FAIL(func, false, "only QKV reads column states");
+        return !between || between();
+    }
+    if ((dev_state != nullptr) == batch) PROBE_FAIL(func, false, "exactly one of dev_state and seq_states names the column states");
+    if (col_mode != 0 && col_mode != 1) PROBE_FAIL(func, false, "col_mode must be 0 or 1");
+    if (!batch && col_mode) PROBE_FAIL(func, false, "col_mode 1 needs seq_states");
+    if (!k_slots || !v_slots) PROBE_FAIL(func, false, "k_slots or v_slots is NULL");
+    if (P < 1 || P > 8192) PROBE_FAIL(func, false, "P must be in [1, 8192]");
+    if (n_slots < 1 || n_slots > 1024) PROBE_FAIL(func, false, "n_slots must be in [1, 1024]");
+    if (!batch && !probe_one_slot(func, n_slots)) return false;
+    if (between && !between()) return false;
+    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
+    std::set<std::pair<int, int>> seen;
+    for (int i = 0; i < N; i++) {
+        const int pos = batch ? hs[i].n_past : dev_state[0] + i, slot = batch ? (col_mode ? hs[i].seq_id : i) : 0;
+        if (pos < 0 || pos >= P) PROBE_FAIL(func, false, "column %d: position %d outside [0, P)", i, pos);
+        if (!probe_slot_ok(func, i, slot, n_slots)) return false;
+        if (!seen.insert({slot, pos}).second) PROBE_FAIL(func, false, "column %d: a second column writes slot %d, position %d", i, slot, pos);
+    }
+    return true;
+}
+
+// The rows of a block-format (or float) matrix in a probe's image: w_rows (M rows in the file's format; null: none) repacked by repack_rows into the parts
+// [qs | sc | qh], and with want_tile_image the row-tiled image of the matrix cores behind them, laid out by tile_image_place (image_fill: its bytes before
+// retile() -- 0 for the rows the last tile has beyond the matrix).  sc_slack: bytes of zeros behind the scales (lm_stream_kernel stages a workgroup's scales
+// 16 bytes at a time: the scale array rounded up, as in the arena).  After the upload: W() the matrix, image() its image, retile() builds the image from W().
+struct BlockRows {
+    int32_t type = 0, M = 0, K = 0;
+    ProbePart qs, sc, qh, img;
+    size_t xq = 0, xs = 0;
+    bgk::DevMatrix W(const ProbeImage &im) const {
+        bgk::DevMatrix w{};
+        w.qs = im.d.p + qs.off; w.sc = sc.bytes ? im.d.p + sc.off : nullptr; w.qh = qh.bytes ? im.at<const uint32_t>(qh) : nullptr;
+        w.type = type; w.M = M; w.K = K;
+        return w;
+    }
+    bgk::DevMatrix image(const ProbeImage &im) const {
+        bgk::DevMatrix w{};
+        w.qs = im.d.p + img.off + xq; w.sc = im.d.p + img.off + xs; w.qh = nullptr; w.type = type; w.M = M; w.K = K;
+        return w;
+    }
+    hipError_t retile(const ProbeImage &im) const {
+        const bgk::DevMatrix w = W(im);
+        return (hipError_t)bg_mfma_retile(type, &w, sizeof(w), im.d.p + img.off + xq, im.d.p + img.off + xs, 0);
+    }
+};
+static BlockRows upload_block_rows(ProbeImage &im, int32_t wtype, const void *w_rows, int M, int K, bool want_tile_image, size_t sc_slack = 0, int image_fill = 0) {
+    BlockRows r;
+    r.type = wtype; r.M = M; r.K = K;
+    if (w_rows && !is_quantized(wtype)) {
+        r.qs = im.in(w_rows, file_row_bytes(wtype, K) * (size_t)M);
+        r.sc = im.fill(sc_slack);
+    } else if (w_rows) {
+        const size_t nblk = (size_t)M * ((size_t)K / QK);
+        const bool q81 = wtype == T_Q4_1 || wtype == T_Q5_1, q5 = wtype == T_Q5_0 || wtype == T_Q5_1;
+        std::vector<uint8_t> qs(nblk * (wtype == T_Q8_0 ? 32 : 16)), sc(nblk * (q81 ? 4 : 2) + sc_slack, 0), qh(q5 ? nblk * 4 : 0);
+        repack_rows(wtype, static_cast<const uint8_t *>(w_rows), M, K, qs.data(), sc.data(), qh.data());
+        r.qs = im.own(std::move(qs)); r.sc = im.own(std::move(sc)); r.qh = im.own(std::move(qh));
+    }
+    if (want_tile_image) {
+        size_t img_b = 0;
+        tile_image_place(wtype, M, K, img_b, r.xq, r.xs);
+        r.img = im.fill(img_b, image_fill);
+    }
+    return r;
+}
+
+// The parts of a linear stage's probe behind its inputs, in the order all three lay them out -- [bias | resid | context state | column states | GELU table |
+// K slots | V slots] -- and the MatvecParams fields that follow from them: the common ones, then the QKV branch (q_out / kcache / vcache / q_scale, and with
+// column states seq / col_mode / kv_seq_stride), the RESID branch (out / ldo / resid / ldr) or the plain one (out / ldo; none without an f32 output).  The
+// caller names its output part(s) behind these and sets its input (aq_* or x / ldx).
+struct StageParts { ProbePart bias, res, ds, st, tab, k, v; };
+static StageParts stage_parts(ProbeImage &im, const float *bias, size_t bias_b, const float *resid, size_t res_b, const int32_t *dev_state, const int32_t *seq_states, int N,
+                              const float *k_slots, const float *v_slots, size_t kv_b) {
+    StageParts s;
+    s.bias = im.in(bias, bias_b); s.res = im.in(resid, res_b);
+    s.ds = im.in(dev_state ? dev_state : PROBE_NO_STATE, sizeof(bgk::DevState));
+    s.st = im.in(seq_states, sizeof(bgk::SeqState) * (size_t)N);
+    s.tab = im.own(gelu_table_f16());
+    s.k = im.in(k_slots, kv_b); s.v = im.in(v_slots, kv_b);
+    return s;
+}
+static bgk::MatvecParams stage_params(const ProbeImage &im, const bgk::DevMatrix &W, const StageParts &s, int D, int P, int N, bool qkv, int col_mode, ProbePart out, int ldo, int ldr) {
+    bgk::MatvecParams p{};
+    p.W = W;
+    p.eps = 1e-5f; p.D = D; p.dk = 64; p.dk_log2 = 6; p.P = P;
+    p.st = im.at<const bgk::DevState>(s.ds);
+    p.gelu_tab = im.at<const uint16_t>(s.tab);
+    p.N = N;
+    if (s.bias.bytes) p.bias = im.at<const float>(s.bias);
+    if (qkv) {
+        p.q_out = im.at<float>(out); p.kcache = im.at<float>(s.k); p.vcache = im.at<float>(s.v);
+        p.q_scale = 1.0f / sqrtf(64.0f);
+        if (s.st.bytes) { p.seq = im.at<const bgk::SeqState>(s.st); p.col_mode = col_mode; p.kv_seq_stride = (int64_t)(D / 64) * P * 64; }
+    } else if (out.bytes) {
+        p.out = im.at<float>(out); p.ldo = ldo;
+        if (s.res.bytes) { p.resid = im.at<const float>(s.res); p.ldr = ldr; }
+    }
+    return p;
+}
+
+// Two events and reps timed launches between them: before (or none) runs in front of the first event (the device-side restore of what the launch consumes),
+// launch between the two, store(i, ms) takes launch i's milliseconds in the caller's unit.  Returns 0, or -2 with the HIP error of the step that failed.
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair &) = delete;
+    bool create() { HIP_TRY(false, hipEventCreate(&e0)); HIP_TRY(false, hipEventCreate(&e1)); return true; }
+    ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+constexpr int PROBE_MAX_REPS = 10000;      // the timed entries take reps in [1, PROBE_MAX_REPS]; their untimed forms pass 0
+static int time_launches(int reps, const std::function<hipError_t()> &before, const std::function<hipError_t()> &launch, const std::function<void(int, float)> &store) {
+    EventPair ev;
+    if (reps < 1) return 0;
+    if (!ev.create()) return -2;
+    for (int i = 0; i < reps; i++) {
+        float ms = 0.0f;
+        hipError_t e = before ? before() : hipSuccess;
+        if (e == hipSuccess) e = hipEventRecord(ev.e0, 0);
+        if (e == hipSuccess) e = launch();
+        if (e == hipSuccess) e = hipEventRecord(ev.e1, 0);
+        if (e == hipSuccess) e = hipEventSynchronize(ev.e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev.e0, ev.e1);
+        store(i, ms);
+        if (e != hipSuccess) BG_FAIL(-2, "a timed launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+}  // extern "C++"
+
 // contrast_rank_kernel + contrast_pick over rows held in host memory (tests of the kernels themselves): k candidate rows against T context rows, no model
 int biogpt_hip_contrast_rank_device(int device, const float *cand, const float *ctx_rows, int32_t k, int32_t T, int32_t d, const float *probs, float alpha,
                                     float *pen_out, float *score_out, int32_t *winner_out) {
@@ -12,30 +224,25 @@ int biogpt_hip_contrast_rank_device(int device, const float *cand, const float *
     if (!(alpha >= 0.0f && alpha <= 1.0f)) BG_FAIL(-1, "alpha must be in [0, 1]");
     HIP_TRY(-2, hipSetDevice(device));
     const int n_slabs = (T + bgk::CT_SLAB - 1) / bgk::CT_SLAB;
-    ByteLayout l;      // [context rows | candidate rows | norms | slab maxima | probabilities | group | out]
-    const size_t o_h = l.part((size_t)T * d * 4), o_c = l.part((size_t)k * d * 4), o_n = l.part((size_t)T * 8), o_s = l.part((size_t)n_slabs * bgk::CT_MAX_K * 4);
-    const size_t o_p = l.part(bgk::CT_MAX_K * 4), o_g = l.part(sizeof(bgk::ContrastGroup)), o_o = l.part((2 * bgk::CT_MAX_K + 1) * 4);
-    DeviceBytes dv;
-    if (!dv.alloc(l.bytes())) return -2;
     bgk::ContrastGroup hg{};
     hg.len = T;
-    HIP_TRY(-2, hipMemcpy(dv.p + o_h, ctx_rows, (size_t)T * d * 4, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(dv.p + o_c, cand, (size_t)k * d * 4, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(dv.p + o_p, probs, (size_t)k * 4, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(dv.p + o_g, &hg, sizeof(hg), hipMemcpyHostToDevice));
-    const float *H = dv.at<float>(o_h);
-    double *Hn = dv.at<double>(o_n);
-    float *slab_max = dv.at<float>(o_s);
-    const bgk::ContrastGroup *grp = dv.at<bgk::ContrastGroup>(o_g);
+    ProbeImage im;      // [context rows | candidate rows | norms | slab maxima | probabilities | group | out]
+    const ProbePart o_h = im.in(ctx_rows, (size_t)T * d * 4), o_c = im.in(cand, (size_t)k * d * 4), o_n = im.fill((size_t)T * 8), o_s = im.fill((size_t)n_slabs * bgk::CT_MAX_K * 4);
+    const ProbePart o_p = im.in(probs, (size_t)k * 4), o_g = im.in(&hg, sizeof(hg)), o_o = im.out((2 * bgk::CT_MAX_K + 1) * 4);
+    if (!im.upload()) return -2;
+    const float *H = im.at<float>(o_h);
+    double *Hn = im.at<double>(o_n);
+    float *slab_max = im.at<float>(o_s);
+    const bgk::ContrastGroup *grp = im.at<bgk::ContrastGroup>(o_g);
     size_t rank_lds;
     if (!contrast_rank_lds(nullptr, k, d, &rank_lds)) return -2;
     hipLaunchKernelGGL(bgk::contrast_norms_kernel, dim3(n_slabs, 1), dim3(bgk::CT_THREADS), 0, 0, H, Hn, grp, d, T);
-    hipLaunchKernelGGL(bgk::contrast_rank_kernel, dim3(n_slabs, 1), dim3(bgk::CT_THREADS), rank_lds, 0, dv.at<const float>(o_c), H, Hn, grp, k, d, T, slab_max);
-    hipLaunchKernelGGL(bgk::contrast_pick_kernel, dim3(1), dim3(bgk::CT_THREADS), 0, 0, slab_max, grp, k, dv.at<const float>(o_p), alpha, dv.at<float>(o_o));
+    hipLaunchKernelGGL(bgk::contrast_rank_kernel, dim3(n_slabs, 1), dim3(bgk::CT_THREADS), rank_lds, 0, im.at<const float>(o_c), H, Hn, grp, k, d, T, slab_max);
+    hipLaunchKernelGGL(bgk::contrast_pick_kernel, dim3(1), dim3(bgk::CT_THREADS), 0, 0, slab_max, grp, k, im.at<const float>(o_p), alpha, im.at<float>(o_o));
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
     float out[2 * bgk::CT_MAX_K + 1];
-    HIP_TRY(-2, hipMemcpy(out, dv.p + o_o, (size_t)(2 * k + 1) * 4, hipMemcpyDeviceToHost));
+    if (!im.read(o_o, out, (size_t)(2 * k + 1) * 4)) return -2;
     std::memcpy(pen_out, out, (size_t)k * 4);
     std::memcpy(score_out, out + k, (size_t)k * 4);
     std::memcpy(winner_out, out + 2 * k, 4);
@@ -63,7 +270,6 @@ int biogpt_hip_rules_rows_device(int device, int32_t mode, const float *rows, in
         gs = std::max(gs, hist_lens[r] - prompt_lens[r]);
     }
     HIP_TRY(-2, hipSetDevice(device));
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4;
     ByteLayout sl;      // the side image: [ctl | rows | prompt words | column states | generated words]
     const size_t o_ct = sl.part(sizeof(bgk::RulesCtl)), o_rr = sl.part(sizeof(bgk::RulesRow) * (size_t)n_rows), o_tk = sl.part(n_pr * 4);
     const size_t o_st = sl.part(sizeof(bgk::SeqState) * (size_t)n_rows), o_gn = sl.part((size_t)n_rows * gs * 4);
@@ -81,19 +287,16 @@ int biogpt_hip_rules_rows_device(int device, int32_t mode, const float *rows, in
         st[r].n_gen = ng;
         at += (size_t)hist_lens[r]; po += (size_t)np;
     }
-    ByteLayout l;       // [rows | side image]
-    const size_t o_lg = l.part(lg_b), o_side = l.part(h.size());
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_side, h.data(), h.size(), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(bgk::rules_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((n_vocab + 31) / 32) * 4, 0, d.at<float>(o_lg), n_vocab, n_vocab,
-                       d.at<const bgk::RulesCtl>(o_side + o_ct), d.at<const bgk::RulesRow>(o_side + o_rr), d.at<const int32_t>(o_side + o_tk),
-                       d.at<const bgk::SeqState>(o_side + o_st), d.at<const int32_t>(o_side + o_gn), gs, nullptr, 0);
+    ProbeImage im;      // [rows | side image]
+    const ProbePart o_lg = im.in(rows, (size_t)n_rows * n_vocab * 4), o_side = im.in(h.data(), h.size());
+    if (!im.upload()) return -2;
+    const uint8_t *side = im.at<const uint8_t>(o_side);
+    hipLaunchKernelGGL(bgk::rules_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((n_vocab + 31) / 32) * 4, 0, im.at<float>(o_lg), n_vocab, n_vocab,
+                       reinterpret_cast<const bgk::RulesCtl *>(side + o_ct), reinterpret_cast<const bgk::RulesRow *>(side + o_rr), reinterpret_cast<const int32_t *>(side + o_tk),
+                       reinterpret_cast<const bgk::SeqState *>(side + o_st), reinterpret_cast<const int32_t *>(side + o_gn), gs, nullptr, 0);
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(rows_out, d.p + o_lg, lg_b, hipMemcpyDeviceToHost));
-    return 0;
+    return im.read(o_lg, rows_out) ? 0 : -2;
 }
 
 // trie_rows_kernel over rows held in host memory (tests of the kernel itself, tools): row r's generated tokens are hist_lens[r] tokens of `hist` (the
@@ -107,7 +310,7 @@ static int trie_rows_device(int device, biogpt_hip_trie *trie, int32_t mode, con
     if (!rows_out) BG_FAIL(-1, "rows_out is NULL");
     if (mode != 0 && mode != 1) BG_FAIL(-1, "mode must be 0 (logits) or 1 (log-probabilities)");
     if (n_rows < 1 || n_rows > 4096) BG_FAIL(-1, "n_rows must be in [1, 4096]");
-    if (reps < 0 || reps > 10000 || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, 10000], with us_out");
+    if (reps < 0 || reps > PROBE_MAX_REPS || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, %d], with us_out", PROBE_MAX_REPS);
     if (!check_trie(trie, eos_id)) return -1;
     if (n_vocab != trie->n_vocab) BG_FAIL(-1, "n_vocab = %d, the trie was built for %d", n_vocab, trie->n_vocab);
     size_t total = 0;
@@ -121,54 +324,34 @@ static int trie_rows_device(int device, biogpt_hip_trie *trie, int32_t mode, con
     }
     HIP_TRY(-2, hipSetDevice(device));
     const size_t lg_b = (size_t)n_rows * n_vocab * 4;
-    ByteLayout l;      // [rows | ctl | column states | generated words | the rows again, with reps]
-    const size_t o_lg = l.part(lg_b), o_ct = l.part(sizeof(bgk::TrieCtl)), o_st = l.part(sizeof(bgk::SeqState) * (size_t)n_rows), o_gn = l.part((size_t)n_rows * gs * 4);
-    const size_t side_b = l.bytes() - o_ct, o_keep = l.part(reps > 0 ? lg_b : 0);
-    std::vector<uint8_t> h(side_b, 0);      // the image of ctl .. generated words
-    bgk::TrieCtl *hc = reinterpret_cast<bgk::TrieCtl *>(h.data());
+    ByteLayout sl;      // the side image: [ctl | column states | generated words]
+    const size_t o_ct = sl.part(sizeof(bgk::TrieCtl)), o_st = sl.part(sizeof(bgk::SeqState) * (size_t)n_rows), o_gn = sl.part((size_t)n_rows * gs * 4);
+    std::vector<uint8_t> h(sl.bytes(), 0);
+    bgk::TrieCtl *hc = reinterpret_cast<bgk::TrieCtl *>(h.data() + o_ct);
     if (!trie_device(trie, device, hc)) return -2;
     hc->eos_id = eos_id; hc->mode = mode;
-    bgk::SeqState *st = reinterpret_cast<bgk::SeqState *>(h.data() + (o_st - o_ct));
-    int32_t *gn = reinterpret_cast<int32_t *>(h.data() + (o_gn - o_ct));
+    bgk::SeqState *st = reinterpret_cast<bgk::SeqState *>(h.data() + o_st);
+    int32_t *gn = reinterpret_cast<int32_t *>(h.data() + o_gn);
     size_t at = 0;
     for (int r = 0; r < n_rows; r++) {
         std::memcpy(gn + (size_t)r * gs, hist + at, (size_t)hist_lens[r] * 4);
         st[r].n_gen = hist_lens[r];
         at += (size_t)hist_lens[r];
     }
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_ct, h.data(), h.size(), hipMemcpyHostToDevice));
-    auto launch = [&] {
-        hipLaunchKernelGGL(bgk::trie_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((n_vocab + 31) / 32) * 4, 0, d.at<float>(o_lg), n_vocab, n_vocab,
-                           d.at<const bgk::TrieCtl>(o_ct), d.at<const bgk::SeqState>(o_st), d.at<const int32_t>(o_gn), gs, nullptr, 0);
+    ProbeImage im;      // [rows | side image | the rows again, with reps]
+    const ProbePart o_lg = im.in(rows, lg_b), o_side = im.in(h.data(), h.size()), o_keep = im.in(reps > 0 ? rows : nullptr, lg_b);
+    if (!im.upload()) return -2;
+    const uint8_t *side = im.at<const uint8_t>(o_side);
+    auto launch = [&]() -> hipError_t {
+        hipLaunchKernelGGL(bgk::trie_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), (size_t)((n_vocab + 31) / 32) * 4, 0, im.at<float>(o_lg), n_vocab, n_vocab,
+                           reinterpret_cast<const bgk::TrieCtl *>(side + o_ct), reinterpret_cast<const bgk::SeqState *>(side + o_st),
+                           reinterpret_cast<const int32_t *>(side + o_gn), gs, nullptr, 0);
+        return hipGetLastError();
     };
-    launch();
-    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, launch());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(rows_out, d.p + o_lg, lg_b, hipMemcpyDeviceToHost));
-    if (reps > 0) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        HIP_TRY(-2, hipMemcpy(d.p + o_keep, rows, lg_b, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipEventCreate(&e0));
-        HIP_TRY(-2, hipEventCreate(&e1));
-        hipError_t err = hipSuccess;
-        for (int i = 0; i < reps && err == hipSuccess; i++) {
-            float ms = 0.0f;
-            err = hipMemcpyAsync(d.p + o_lg, d.p + o_keep, lg_b, hipMemcpyDeviceToDevice, 0);
-            if (err == hipSuccess) err = hipEventRecord(e0, 0);
-            if (err == hipSuccess) { launch(); err = hipGetLastError(); }
-            if (err == hipSuccess) err = hipEventRecord(e1, 0);
-            if (err == hipSuccess) err = hipEventSynchronize(e1);
-            if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-            us_out[i] = ms * 1e3f;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        HIP_TRY(-2, err);
-    }
-    return 0;
+    if (!im.read(o_lg, rows_out)) return -2;
+    return time_launches(reps, [&] { return im.restore(o_lg, o_keep); }, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
 }
 int biogpt_hip_trie_rows_device(int device, biogpt_hip_trie *trie, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist,
                                 const int32_t *hist_lens, int32_t eos_id, float *rows_out) {
@@ -176,7 +359,7 @@ int biogpt_hip_trie_rows_device(int device, biogpt_hip_trie *trie, int32_t mode,
 }
 int biogpt_hip_trie_rows_bench(int device, biogpt_hip_trie *trie, int32_t mode, const float *rows, int32_t n_rows, int32_t n_vocab, const int32_t *hist,
                                const int32_t *hist_lens, int32_t eos_id, float *rows_out, int32_t reps, float *us_out) {
-    if (reps < 1) { clear_error(); BG_FAIL(-1, "reps must be in [1, 10000]"); }
+    if (reps < 1) { clear_error(); BG_FAIL(-1, "reps must be in [1, %d]", PROBE_MAX_REPS); }
     return trie_rows_device(device, trie, mode, rows, n_rows, n_vocab, hist, hist_lens, eos_id, rows_out, reps, us_out);
 }
 
@@ -189,6 +372,33 @@ int biogpt_hip_trie_rows_bench(int device, biogpt_hip_trie *trie, int32_t mode, 
 // rows = N rounded up to 16, plus one guard row, preset to 0xff -- out [rows][H * dk], out_q [rows][H * dk], out_d / out_s [rows][H * dk / 32] -- so a store
 // beyond column N shows.  launched [8]: kernel, threads, grid x, grid y, dynamic LDS bytes, t_cap, key ranges (split), 0.
 // reps > 0: the launch repeated, us_out[i] microseconds between two events around launch i alone -- a repeated stand-alone launch finds its K / V rows in cache.
+// The image of an attention probe: [K slots | V slots | q | column states | the probe's own part (extra) | exp table | out | out_q | out_d | out_s], the outputs
+// of rows = N rounded up to 16, plus one guard row; the AttnParams that follow from it (column states only where seq_states is given); the read-back.
+struct AttnProbeParts { ProbePart k, v, q, st, extra, tab, out, oq, od, os; };
+static AttnProbeParts attn_probe_parts(ProbeImage &im, int H, int dk, int N, int P, int n_slots, const float *q, const float *k_slots, const float *v_slots,
+                                       const int32_t *seq_states, const void *extra, size_t extra_b) {
+    const size_t D = (size_t)H * dk, rows = (size_t)((N + 15) & ~15) + 1, kv_b = (size_t)H * P * dk * 4 * (size_t)n_slots;
+    AttnProbeParts o;
+    o.k = im.in(k_slots, kv_b); o.v = im.in(v_slots, kv_b); o.q = im.in(q, (size_t)N * D * 4); o.st = im.in(seq_states, sizeof(bgk::SeqState) * (size_t)N);
+    o.extra = im.in(extra, extra_b);
+    o.tab = im.own(exp_table_f16());      // the table of the model loader
+    o.out = im.out(rows * D * 4); o.oq = im.out(rows * D); o.od = im.out(rows * (D / 32) * 4); o.os = im.out(rows * (D / 32) * 4);
+    return o;
+}
+static bgk::AttnParams attn_probe_params(const ProbeImage &im, const AttnProbeParts &o, int N, int D, int dk, int P, int t_cap, int col_mode, int64_t kv_seq_stride, int q8) {
+    bgk::AttnParams a{};
+    a.q = im.at<const float>(o.q); a.kcache = im.at<const float>(o.k); a.vcache = im.at<const float>(o.v); a.out = im.at<float>(o.out);
+    a.exp_tab = im.at<const uint16_t>(o.tab);
+    a.N = N; a.D = D; a.dk = dk; a.P = P; a.t_cap = t_cap;
+    if (o.st.bytes) { a.seq = im.at<const bgk::SeqState>(o.st); a.col_mode = col_mode; a.kv_seq_stride = kv_seq_stride; }
+    a.q81 = q8 == 2 ? 1 : 0;
+    if (q8 > 0) { a.oq_q = im.at<int8_t>(o.oq); a.oq_d = im.at<float>(o.od); a.oq_s = im.at<uint32_t>(o.os); }
+    return a;
+}
+static bool attn_probe_read(const ProbeImage &im, const AttnProbeParts &o, int q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s) {
+    if (!im.read(o.out, out)) return false;
+    return q8 <= 0 || (im.read(o.oq, out_q) && im.read(o.od, out_d) && im.read(o.os, out_s));
+}
 static int host_visible_keys(const int32_t *ds, int i, int N) {      // visible_keys (kernels.hip.h) on the host
     if (ds[2]) return ds[0] + i + 1;
     if (ds[3] <= 0) return ds[0] + N;
@@ -207,7 +417,7 @@ static int attn_device(int device, int32_t route, int32_t H, int32_t dk, int32_t
     if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
     if (t_max < 1 || t_max > P) BG_FAIL(-1, "t_max must be in [1, P]: t_cap never exceeds the table");
     if (q8 < 0 || q8 > 2 || (q8 > 0 && (!out_q || !out_d || !out_s))) BG_FAIL(-1, "q8 must be 0, 1 or 2, with out_q, out_d and out_s");
-    if (reps < 0 || reps > 10000 || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, 10000], with us_out");
+    if (reps < 0 || reps > PROBE_MAX_REPS || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, %d], with us_out", PROBE_MAX_REPS);
     if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
     if ((dev_state != nullptr) == (seq_states != nullptr)) BG_FAIL(-1, "exactly one of dev_state and seq_states names the column states");
     static_assert(sizeof(bgk::SeqState) == 32, "eight words per column state");
@@ -260,42 +470,23 @@ static int attn_device(int device, int32_t route, int32_t H, int32_t dk, int32_t
         if (T < 1 || T > t_cap || T > t_max) BG_FAIL(-1, "column %d: %d visible keys outside [1, t_cap = %d] (t_max %d)", i, T, t_cap, t_max);
         if (!batch) continue;
         const int slot = col_mode ? hs[i].seq_id : i;
-        if (slot < 0 || slot >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, slot);
+        if (!probe_slot_ok(__func__, i, slot, n_slots)) return -1;
         if (shared || route == AK_PREFIX) {
             if (hs[i].pad[0] < 0 || hs[i].pad[0] > (col_mode ? T : hs[i].n_past)) BG_FAIL(-1, "column %d: %d shared rows outside [0, n_past]", i, hs[i].pad[0]);
             if (hs[i].pad[1] < 0 || hs[i].pad[1] >= n_slots) BG_FAIL(-1, "column %d: shared slot %d outside [0, n_slots)", i, hs[i].pad[1]);
             if (route == AK_PREFIX && (hs[i].pad[0] != hs[0].pad[0] || hs[i].pad[1] != hs[0].pad[1])) BG_FAIL(-1, "column %d: attn_prefix_kernel needs one shared range for all columns", i);
         }
     }
-    if (!batch && n_slots != 1) BG_FAIL(-1, "the context's own columns have one slot");
+    if (!batch && !probe_one_slot(__func__, n_slots)) return -1;
     HIP_TRY(-2, hipSetDevice(device));
-    const int D = H * dk, rows = ((N + 15) & ~15) + 1;
-    const size_t slot = (size_t)H * P * dk, kv_b = slot * 4 * (size_t)n_slots, q_b = (size_t)N * D * 4, row_b = (size_t)rows * D * 4, blk = (size_t)rows * (D / 32);
-    ByteLayout l;
-    const size_t o_k = l.part(kv_b), o_v = l.part(kv_b), o_q = l.part(q_b), o_st = l.part(sizeof(bgk::SeqState) * (size_t)N), o_ds = l.part(sizeof(bgk::DevState)),
-                 o_tab = l.part(65536 * 2), o_out = l.part(row_b), o_oq = l.part((size_t)rows * D), o_od = l.part(blk * 4), o_os = l.part(blk * 4),
-                 o_sps = l.part((size_t)H * P * 4), o_spm = l.part((size_t)H * bgk::SPLIT_MAX * 4), o_spv = l.part((size_t)H * bgk::SPLIT_MAX * 64 * 8);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    std::vector<uint16_t> te(65536);
-    for (uint32_t i = 0; i < 65536; i++) te[i] = f32_to_f16(expf(f16_to_f32((uint16_t)i)));      // the table of the model loader
-    const int32_t no_state[4] = {0, 0, 0, 0};
-    HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_q, q, q_b, hipMemcpyHostToDevice));
-    if (batch) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_ds, batch ? no_state : dev_state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_tab, te.data(), 65536 * 2, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));      // the outputs with their guard rows, and the split scratch (a range past the context reads as NaN)
-    bgk::AttnParams a{};
-    a.q = d.at<const float>(o_q); a.kcache = d.at<const float>(o_k); a.vcache = d.at<const float>(o_v); a.out = d.at<float>(o_out);
-    a.st = d.at<const bgk::DevState>(o_ds);
-    a.exp_tab = d.at<const uint16_t>(o_tab);
-    a.N = N; a.D = D; a.dk = dk; a.P = P; a.t_cap = t_cap;
-    if (batch) { a.seq = d.at<const bgk::SeqState>(o_st); a.col_mode = col_mode; a.kv_seq_stride = (int64_t)slot; }
-    a.q81 = q8 == 2 ? 1 : 0;
-    if (q8 > 0) { a.oq_q = d.at<int8_t>(o_oq); a.oq_d = d.at<float>(o_od); a.oq_s = d.at<uint32_t>(o_os); }
-    if (route == AK_SPLIT) { a.sp_scores = d.at<float>(o_sps); a.sp_max = d.at<float>(o_spm); a.sp_pv = d.at<double>(o_spv); }
+    const int D = H * dk;
+    ProbeImage im;      // the outputs with their guard rows, and behind them the split scratch (a range past the context reads as NaN)
+    const AttnProbeParts o = attn_probe_parts(im, H, dk, N, P, n_slots, q, k_slots, v_slots, seq_states, batch ? PROBE_NO_STATE : dev_state, sizeof(bgk::DevState));
+    const ProbePart o_sps = im.out((size_t)H * P * 4), o_spm = im.out((size_t)H * bgk::SPLIT_MAX * 4), o_spv = im.out((size_t)H * bgk::SPLIT_MAX * 64 * 8);
+    if (!im.upload()) return -2;
+    bgk::AttnParams a = attn_probe_params(im, o, N, D, dk, P, t_cap, col_mode, (int64_t)H * P * dk, q8);
+    a.st = im.at<const bgk::DevState>(o.extra);
+    if (route == AK_SPLIT) { a.sp_scores = im.at<float>(o_sps); a.sp_max = im.at<float>(o_spm); a.sp_pv = im.at<double>(o_spv); }
     std::set<const void *> lds_done;
     AttnLaunch g{};
     auto launch = [&]() -> bool {
@@ -311,33 +502,9 @@ static int attn_device(int device, int32_t route, int32_t H, int32_t dk, int32_t
     if (!launch()) return -2;
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    if (launched) {
-        const int32_t rep[8] = {g.kernel, g.threads, g.grid_x, g.grid_y, (int32_t)g.lds, t_cap, a.n_split, 0};
-        std::memcpy(launched, rep, sizeof(rep));
-    }
-    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, row_b, hipMemcpyDeviceToHost));
-    if (q8 > 0) {
-        HIP_TRY(-2, hipMemcpy(out_q, d.p + o_oq, (size_t)rows * D, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(out_d, d.p + o_od, blk * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(out_s, d.p + o_os, blk * 4, hipMemcpyDeviceToHost));
-    }
-    if (reps > 0) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        HIP_TRY(-2, hipEventCreate(&e0));
-        HIP_TRY(-2, hipEventCreate(&e1));
-        bool ok = true;
-        for (int i = 0; i < reps && ok; i++) {
-            ok = hipEventRecord(e0, 0) == hipSuccess;
-            ok = launch() && ok;
-            ok = ok && hipEventRecord(e1, 0) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
-            float ms = 0.0f;
-            ok = ok && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-            us_out[i] = ms * 1000.0f;
-        }
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        if (!ok) BG_FAIL(-2, "a timed attention launch failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    return 0;
+    report_launch(launched, {g.kernel, g.threads, g.grid_x, g.grid_y, (int32_t)g.lds, t_cap, a.n_split});
+    if (!attn_probe_read(im, o, q8, out, out_q, out_d, out_s)) return -2;
+    return time_launches(reps, nullptr, [&] { return launch() ? hipSuccess : hipErrorLaunchFailure; }, [&](int i, float ms) { us_out[i] = ms * 1000.0f; });
 }
 int biogpt_hip_attn_device(int device, int32_t route, int32_t H, int32_t dk, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots,
                            const float *v_slots, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t q8, float *out, int8_t *out_q, float *out_d,
@@ -379,7 +546,7 @@ int biogpt_hip_attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, i
 }
 int biogpt_hip_attn_prefix_bench(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
                                  const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps, float *us_out) {
-    if (reps < 1 || reps > 10000 || !us_out) { clear_error(); BG_FAIL(-1, "reps must be in [1, 10000], with us_out"); }
+    if (reps < 1 || reps > PROBE_MAX_REPS || !us_out) { clear_error(); BG_FAIL(-1, "reps must be in [1, %d], with us_out", PROBE_MAX_REPS); }
     return attn_prefix_device(device, H, N, P, t_cap, q, k_slots, v_slots, seq_states, which, q8, out, out_q, out_d, out_s, reps, us_out);
 }
 
@@ -400,13 +567,13 @@ static int attn_runs_device(int device, int32_t H, int32_t N, int32_t P, int32_t
     if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
     if (t_max < 1 || t_max > P) BG_FAIL(-1, "t_max must be in [1, P]: t_cap never exceeds the table");
     if (q8 < 0 || q8 > 2 || (q8 > 0 && (!out_q || !out_d || !out_s))) BG_FAIL(-1, "q8 must be 0, 1 or 2, with out_q, out_d and out_s");
-    if (reps < 0 || reps > 10000 || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, 10000], with us_out");
+    if (reps < 0 || reps > PROBE_MAX_REPS || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, %d], with us_out", PROBE_MAX_REPS);
     const int t_cap = attn_decode_t_cap(P, t_max);
     const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
     for (int i = 0; i < N; i++) {
         const int T = hs[i].t_vis;
         if (T < 1 || T > t_cap || T > t_max) BG_FAIL(-1, "column %d: %d visible keys outside [1, t_cap = %d] (t_max %d)", i, T, t_cap, t_max);
-        if (hs[i].seq_id < 0 || hs[i].seq_id >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, hs[i].seq_id);
+        if (!probe_slot_ok(__func__, i, hs[i].seq_id, n_slots)) return -1;
         if (hs[i].pad[0] < 0 || hs[i].pad[0] > T) BG_FAIL(-1, "column %d: %d shared rows outside [0, t_vis]", i, hs[i].pad[0]);
         if (hs[i].pad[1] < 0 || hs[i].pad[1] >= n_slots) BG_FAIL(-1, "column %d: shared slot %d outside [0, n_slots)", i, hs[i].pad[1]);
     }
@@ -434,59 +601,19 @@ static int attn_runs_device(int device, int32_t H, int32_t N, int32_t P, int32_t
     }
     if (next != N) BG_FAIL(-1, "the runs cover columns [0, %d), not all %d", next, N);
     HIP_TRY(-2, hipSetDevice(device));
-    const int D = H * 64, rows = ((N + 15) & ~15) + 1;
-    const size_t slot = (size_t)H * P * 64, kv_b = slot * 4 * (size_t)n_slots, q_b = (size_t)N * D * 4, row_b = (size_t)rows * D * 4, blk = (size_t)rows * (D / 32);
-    ByteLayout l;
-    const size_t o_k = l.part(kv_b), o_v = l.part(kv_b), o_q = l.part(q_b), o_st = l.part(sizeof(bgk::SeqState) * (size_t)N), o_rn = l.part(16 * (size_t)n_runs),
-                 o_tab = l.part(65536 * 2), o_out = l.part(row_b), o_oq = l.part((size_t)rows * D), o_od = l.part(blk * 4), o_os = l.part(blk * 4);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    std::vector<uint16_t> te(65536);
-    for (uint32_t i = 0; i < 65536; i++) te[i] = f32_to_f16(expf(f16_to_f32((uint16_t)i)));      // the table of the model loader
-    HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_q, q, q_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_rn, table.data(), 16 * (size_t)n_runs, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_tab, te.data(), 65536 * 2, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));      // the outputs with their guard rows
-    bgk::AttnParams a{};
-    a.q = d.at<const float>(o_q); a.kcache = d.at<const float>(o_k); a.vcache = d.at<const float>(o_v); a.out = d.at<float>(o_out);
-    a.exp_tab = d.at<const uint16_t>(o_tab);
-    a.N = N; a.D = D; a.dk = 64; a.P = P; a.t_cap = t_cap;
-    a.seq = d.at<const bgk::SeqState>(o_st); a.col_mode = 1; a.kv_seq_stride = (int64_t)slot;
-    a.q81 = q8 == 2 ? 1 : 0;
-    if (q8 > 0) { a.oq_q = d.at<int8_t>(o_oq); a.oq_d = d.at<float>(o_od); a.oq_s = d.at<uint32_t>(o_os); }
-    const AttnLaunch g = launch_attn_runs(a, d.at<const int32_t>(o_rn), n_runs, H, 0);
+    const int D = H * 64;
+    ProbeImage im;
+    const AttnProbeParts o = attn_probe_parts(im, H, 64, N, P, n_slots, q, k_slots, v_slots, seq_states, table.data(), 16 * (size_t)n_runs);
+    if (!im.upload()) return -2;
+    const bgk::AttnParams a = attn_probe_params(im, o, N, D, 64, P, t_cap, 1, (int64_t)H * P * 64, q8);
+    AttnLaunch g{};
+    auto launch = [&]() -> hipError_t { g = launch_attn_runs(a, im.at<const int32_t>(o.extra), n_runs, H, 0); return hipSuccess; };
+    (void)launch();
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    if (launched) {
-        const int32_t rep[8] = {g.kernel, g.threads, g.grid_x, g.grid_y, (int32_t)g.lds, t_cap, n_runs, 0};
-        std::memcpy(launched, rep, sizeof(rep));
-    }
-    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, row_b, hipMemcpyDeviceToHost));
-    if (q8 > 0) {
-        HIP_TRY(-2, hipMemcpy(out_q, d.p + o_oq, (size_t)rows * D, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(out_d, d.p + o_od, blk * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(out_s, d.p + o_os, blk * 4, hipMemcpyDeviceToHost));
-    }
-    if (reps > 0) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        HIP_TRY(-2, hipEventCreate(&e0));
-        HIP_TRY(-2, hipEventCreate(&e1));
-        bool ok = true;
-        for (int i = 0; i < reps && ok; i++) {
-            ok = hipEventRecord(e0, 0) == hipSuccess;
-            launch_attn_runs(a, d.at<const int32_t>(o_rn), n_runs, H, 0);
-            ok = ok && hipEventRecord(e1, 0) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
-            float ms = 0.0f;
-            ok = ok && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-            us_out[i] = ms * 1000.0f;
-        }
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        if (!ok) BG_FAIL(-2, "a timed attention launch failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    return 0;
+    report_launch(launched, {g.kernel, g.threads, g.grid_x, g.grid_y, (int32_t)g.lds, t_cap, n_runs});
+    if (!attn_probe_read(im, o, q8, out, out_q, out_d, out_s)) return -2;
+    return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1000.0f; });
 }
 int biogpt_hip_attn_runs_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots, const float *v_slots,
                                 const int32_t *seq_states, const int32_t *runs, int32_t n_runs, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s,
@@ -496,7 +623,7 @@ int biogpt_hip_attn_runs_device(int device, int32_t H, int32_t N, int32_t P, int
 int biogpt_hip_attn_runs_bench(int device, int32_t H, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots, const float *v_slots,
                                const int32_t *seq_states, const int32_t *runs, int32_t n_runs, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s,
                                int32_t *launched, int32_t reps, float *us_out) {
-    if (reps < 1 || reps > 10000 || !us_out) { clear_error(); BG_FAIL(-1, "reps must be in [1, 10000], with us_out"); }
+    if (reps < 1 || reps > PROBE_MAX_REPS || !us_out) { clear_error(); BG_FAIL(-1, "reps must be in [1, %d], with us_out", PROBE_MAX_REPS); }
     return attn_runs_device(device, H, N, P, t_max, n_slots, q, k_slots, v_slots, seq_states, runs, n_runs, q8, out, out_q, out_d, out_s, launched, reps, us_out);
 }
 
@@ -513,21 +640,17 @@ int biogpt_hip_logprob_rows_device(int device, const float *rows, int32_t n_rows
     for (int r = 0; r < n_rows; r++)
         if (targets[r] < -1 || targets[r] >= n_vocab) BG_FAIL(-1, "targets[%d] = %d out of range: must be in [0, %d), or -1 for none", r, targets[r], n_vocab);
     HIP_TRY(-2, hipSetDevice(device));
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, n_b = (size_t)n_rows * 4;
-    ByteLayout l;      // [rows | targets | lp, arg-max, logit: three arrays of n_rows words, one after another]
-    const size_t o_lg = l.part(lg_b), o_tg = l.part(n_b), o_lp = l.part(3 * n_b), o_am = o_lp + n_b, o_tl = o_am + n_b;
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_tg, targets, n_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_lp, 0xff, 3 * n_b));
-    hipLaunchKernelGGL(bgk::logprob_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, d.at<const int32_t>(o_tg),
-                       d.at<float>(o_lp), d.at<int32_t>(o_am), d.at<float>(o_tl));
+    const size_t n = (size_t)n_rows;
+    ProbeImage im;      // [rows | targets | lp, arg-max, logit: three arrays of n_rows words, one after another]
+    const ProbePart o_lg = im.in(rows, n * n_vocab * 4), o_tg = im.in(targets, n * 4), o_lp = im.out(3 * n * 4);
+    if (!im.upload()) return -2;
+    hipLaunchKernelGGL(bgk::logprob_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, im.at<const float>(o_lg), n_vocab, n_vocab, im.at<const int32_t>(o_tg),
+                       im.at<float>(o_lp), im.at<int32_t>(o_lp) + n, im.at<float>(o_lp) + 2 * n);
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(lp_out, d.p + o_lp, n_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(argmax_out, d.p + o_am, n_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(logit_out, d.p + o_tl, n_b, hipMemcpyDeviceToHost));
+    std::vector<float> back(3 * n);
+    if (!im.read(o_lp, back.data())) return -2;
+    std::memcpy(lp_out, back.data(), n * 4); std::memcpy(argmax_out, back.data() + n, n * 4); std::memcpy(logit_out, back.data() + 2 * n, n * 4);
     return 0;
 }
 
@@ -566,24 +689,19 @@ static int beam_rows_device(int device, const float *rows, int32_t n_rows, int32
         c.n_beams = B; c.step = first_step ? 0 : 1; c.heur_unsat = 1;
         for (int j = 0; j < B; j++) { c.run_score[j] = run_score[g * B + j]; c.col_rank[j] = j; }
     }
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, ctl_b = sizeof(bgk::BeamCtl) * (size_t)G, cd_b = sizeof(bgk::BeamCand) * (size_t)n_rows * K;
-    ByteLayout l;      // [rows | hdr | ctl | cand]
-    const size_t o_lg = l.part(lg_b), o_hd = l.part(sizeof(bgk::BeamBatchHdr)), o_ct = l.part(ctl_b), o_cd = l.part(cd_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_hd, 0, sizeof(bgk::BeamBatchHdr)));
-    HIP_TRY(-2, hipMemcpy(d.p + o_ct, hc.data(), ctl_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_cd, 0xff, cd_b));
+    ProbeImage im;      // [rows | hdr | ctl | cand]
+    const ProbePart o_lg = im.in(rows, (size_t)n_rows * n_vocab * 4), o_hd = im.fill(sizeof(bgk::BeamBatchHdr)), o_ct = im.in(hc.data(), sizeof(bgk::BeamCtl) * (size_t)G),
+                    o_cd = im.out(sizeof(bgk::BeamCand) * (size_t)n_rows * K);
+    if (!im.upload()) return -2;
     BeamBufs b{};
     b.stream = 0;
-    b.logits = d.at<const float>(o_lg); b.n_vocab = n_vocab;
-    b.hdr = d.at<bgk::BeamBatchHdr>(o_hd); b.ctl = d.at<bgk::BeamCtl>(o_ct); b.cand = d.at<bgk::BeamCand>(o_cd);
+    b.logits = im.at<const float>(o_lg); b.n_vocab = n_vocab;
+    b.hdr = im.at<bgk::BeamBatchHdr>(o_hd); b.ctl = im.at<bgk::BeamCtl>(o_ct); b.cand = im.at<bgk::BeamCand>(o_cd);
     launch_beam_group_rows(b, G, B, given != 0);
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
     std::vector<bgk::BeamCand> out((size_t)n_rows * K);
-    HIP_TRY(-2, hipMemcpy(out.data(), d.p + o_cd, cd_b, hipMemcpyDeviceToHost));
+    if (!im.read(o_cd, out.data())) return -2;
     for (size_t i = 0; i < out.size(); i++) { cand_score[i] = out[i].score; cand_col[i] = out[i].col; cand_id[i] = out[i].id; }
     return 0;
 }
@@ -633,52 +751,45 @@ int biogpt_hip_beam_table_device(int device, const float *table, int32_t n_table
     HIP_TRY(-2, hipSetDevice(device));
     const int P = max_len + n_predict;
     constexpr int H = bgk::TABLE_HEADS, DK = bgk::TABLE_DK;
-    DeviceBytes d;
-    float *table_d = nullptr, *logits_d = nullptr;
-    const size_t tb_b = (size_t)n_table_rows * n_vocab * 4, lg_b = (size_t)n_cols * n_vocab * 4, kv_b = (size_t)n_cols * H * P * DK * 4, gen_b = (size_t)n_cols * P * 4;
+    const size_t lg_b = (size_t)n_cols * n_vocab * 4, kv_b = (size_t)n_cols * H * P * DK * 4, gen_b = (size_t)n_cols * P * 4;
     BeamBufs b{};
-    auto lay = [&](uint8_t *base) {      // [table | logits | K | V | the state block of a call | column states | histories]; no base: the size alone
+    auto state_at = [&](uint8_t *base, BeamBufs *bb) {      // the state block of a call at some base (null: its size alone)
         ByteLayout l;
-        table_d = l.take<float>(base, tb_b / 4); logits_d = l.take<float>(base, lg_b / 4);
-        b.bk = l.take<float>(base, kv_b / 4); b.bv = l.take<float>(base, kv_b / 4);
-        beam_state_parts(l, base, (size_t)n_cols, (size_t)G, (size_t)2 * B, (size_t)P, &b);
-        b.seq = l.take<bgk::SeqState>(base, (size_t)n_cols); b.seq_gen = l.take<int32_t>(base, gen_b / 4);
+        beam_state_parts(l, base, (size_t)n_cols, (size_t)G, (size_t)2 * B, (size_t)P, bb);
         return l.bytes();
     };
-    if (!d.alloc(lay(nullptr))) return -2;
-    lay(d.p);
-    b.stream = 0;
-    b.logits = logits_d; b.n_vocab = n_vocab; b.gen_stride = P;
-    b.seq_stride = (int64_t)H * P * DK; b.kv_runs = H; b.P = P; b.dk = DK;
     std::vector<bgk::BeamCtl> hc((size_t)G);
     std::vector<bgk::SeqState> hs((size_t)n_cols);
     for (int g = 0; g < G; g++) fill_column_starts(hs.data(), g, B, prompt_lens[g], start_tokens[g]);
-    std::vector<float> kv_fill(kv_b / 4, -1.0f);       // a row no step has written reads -1
-    HIP_TRY(-2, hipMemcpy(table_d, table, tb_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(logits_d, 0, lg_b));
-    HIP_TRY(-2, hipMemcpy(b.bk, kv_fill.data(), kv_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(b.bv, kv_fill.data(), kv_b, hipMemcpyHostToDevice));
-    if (!upload_beam_start(b, G, B, prompt_lens, n_predict, eos_id, length_penalty, early_stopping)) return -2;      // the initial state of a call
-    HIP_TRY(-2, hipMemset(b.cand, 0xff, sizeof(bgk::BeamCand) * (size_t)n_cols * 2 * B));
-    HIP_TRY(-2, hipMemset(b.pool_ids, 0xff, gen_b));
-    HIP_TRY(-2, hipMemcpy(b.seq, hs.data(), sizeof(bgk::SeqState) * (size_t)n_cols, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(b.seq_gen, 0xff, gen_b));
+    const std::vector<float> kv_fill(kv_b / 4, -1.0f);      // a K / V row no step has written reads -1
+    ProbeImage im;      // [table | logits | K | V | the state block of a call | column states | histories]
+    const ProbePart o_tb = im.in(table, (size_t)n_table_rows * n_vocab * 4), o_lg = im.fill(lg_b), o_k = im.in(kv_fill.data(), kv_b), o_v = im.in(kv_fill.data(), kv_b), o_state = im.out(state_at(nullptr, &b)), o_seq = im.out(sizeof(bgk::SeqState) * (size_t)n_cols, hs.data()),
+                    o_gen = im.out(gen_b);
+    if (!im.upload()) return -2;
+    state_at(im.at<uint8_t>(o_state), &b);
+    const ProbePart o_hdr{(size_t)(reinterpret_cast<uint8_t *>(b.hdr) - im.d.p), sizeof(bgk::BeamBatchHdr)};      // the header, wherever the block keeps it
+    float *table_d = im.at<float>(o_tb), *logits_d = im.at<float>(o_lg);
+    b.bk = im.at<float>(o_k); b.bv = im.at<float>(o_v); b.seq = im.at<bgk::SeqState>(o_seq); b.seq_gen = im.at<int32_t>(o_gen);
+    b.stream = 0;
+    b.logits = logits_d; b.n_vocab = n_vocab; b.gen_stride = P;
+    b.seq_stride = (int64_t)H * P * DK; b.kv_runs = H; b.P = P; b.dk = DK;
+    if (!upload_beam_start(b, G, B, prompt_lens, n_predict, eos_id, length_penalty, early_stopping)) return -2;      // the initial state of a call, onto the block's head
     bgk::BeamBatchHdr hh{};
     int n_live = G;
     for (int s = 0; s < std::min(max_steps, n_predict) && n_live > 0; s++) {
         hipLaunchKernelGGL(bgk::beam_table_feed_kernel, dim3(n_cols), dim3(256), 0, 0, b.seq, table_d, n_table_rows, n_vocab, logits_d, b.bk, b.bv, P);
         HIP_TRY(-2, hipGetLastError());
         if (!enqueue_beam_group_select(b, G, B, given != 0)) return -2;
-        HIP_TRY(-2, hipMemcpy(&hh, b.hdr, sizeof(hh), hipMemcpyDeviceToHost));      // (synchronizes)
+        if (!im.read(o_hdr, &hh)) return -2;      // (synchronizes)
         n_live = hh.n_live;
     }
-    std::vector<int32_t> ids((size_t)n_cols * P), gen((size_t)n_cols * P);
-    HIP_TRY(-2, hipMemcpy(hc.data(), b.ctl, sizeof(bgk::BeamCtl) * (size_t)G, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(hs.data(), b.seq, sizeof(bgk::SeqState) * (size_t)n_cols, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(ids.data(), b.pool_ids, ids.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(gen.data(), b.seq_gen, gen.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(kv_out, b.bk, kv_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(kv_out + kv_b / 4, b.bv, kv_b, hipMemcpyDeviceToHost));
+    std::vector<int32_t> gen((size_t)n_cols * P);
+    std::vector<uint8_t> hst(o_state.bytes);
+    BeamBufs hb{};      // the state block on the host
+    state_at(hst.data(), &hb);
+    if (!im.read(o_state, hst.data()) || !im.read(o_seq, hs.data()) || !im.read(o_gen, gen.data()) || !im.read(o_k, kv_out) || !im.read(o_v, kv_out + kv_b / 4)) return -2;
+    std::memcpy(hc.data(), hb.ctl, sizeof(bgk::BeamCtl) * (size_t)G);
+    const int32_t *ids = hb.pool_ids;
     for (int g = 0; g < G; g++) {
         grp_done[g] = hc[(size_t)g].done; grp_step[g] = hc[(size_t)g].step;
         for (int j = 0; j < B; j++) {
@@ -695,7 +806,7 @@ int biogpt_hip_beam_table_device(int device, const float *table, int32_t n_table
         std::fill(out_counts, out_counts + G, 0);
         return 0;
     }
-    if (!beam_read_pools(hc.data(), ids.data(), (size_t)P, G, B, n_predict, out_ids, out_lens, out_scores, out_counts)) return -2;
+    if (!beam_read_pools(hc.data(), ids, (size_t)P, G, B, n_predict, out_ids, out_lens, out_scores, out_counts)) return -2;
     return n_predict;
 }
 
@@ -728,64 +839,40 @@ static int sample_wide_rows_device(int device, const float *logits, int32_t n_ro
     if (n_rows < 1 || n_rows > 4096 || n_vocab < 1) BG_FAIL(-1, "n_rows must be in [1, 4096], n_vocab >= 1");
     if (which != 0 && which != 1) BG_FAIL(-1, "which must be 0 (sample_wide_rows_kernel) or 1 (sample_rows_kernel)");
     if (which == 1 && !sampler_is_plain(*sampler)) BG_FAIL(-1, "sample_rows_kernel serves top_k in [1, %d] with min_p 0", bgk::SAMPLE_MAX_K);
-    if (reps < 0 || reps > 10000 || (reps > 0 && !seconds_out)) BG_FAIL(-1, "reps must be in [0, 10000], with seconds_out");
+    if (reps < 0 || reps > PROBE_MAX_REPS || (reps > 0 && !seconds_out)) BG_FAIL(-1, "reps must be in [0, %d], with seconds_out", PROBE_MAX_REPS);
     if (!check_mt_states(mt_in, n_rows)) return -1;
     HIP_TRY(-2, hipSetDevice(device));
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sample_bufs_at(nullptr, (size_t)n_rows).bytes;
-    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = (size_t)n_rows * 4;
+    const size_t sq_b = sample_bufs_at(nullptr, (size_t)n_rows).bytes;
     std::vector<uint8_t> h(sq_b, 0);
     const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_rows);
     *hb.ctl = sample_ctl_of(which == 1 ? sampler->top_k : 1, -1, n_rows, which == 1 ? sampler->top_p : 1.0, which == 1 ? sampler->temp : 1.0);
     *hb.wide = sample_wide_of(*sampler);
     mt_states_in(hb.seq, mt_in, n_rows);
-    ByteLayout l;      // [logits | ctl + states + sampler | column states | ids | candidate counts | ctl + states + sampler again, with reps]
-    const size_t o_lg = l.part(lg_b), o_sq = l.part(sq_b), o_st = l.part(st_b), o_id = l.part(id_b), o_nc = l.part(id_b), o_keep = l.part(reps > 0 ? sq_b : 0);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    const SampleBufs sb = sample_bufs_at(d.p + o_sq, (size_t)n_rows);
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, logits, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(sb.ctl, h.data(), sq_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_st, 0, o_keep - o_st));
-    auto launch = [&] {
+    ProbeImage im;      // [logits | ctl + states + sampler | column states | ids | candidate counts | ctl + states + sampler again, with reps]
+    const ProbePart o_lg = im.in(logits, (size_t)n_rows * n_vocab * 4), o_sq = im.in(h.data(), sq_b), o_st = im.fill(sizeof(bgk::SeqState) * (size_t)n_rows),
+                    o_id = im.fill((size_t)n_rows * 4), o_nc = im.fill((size_t)n_rows * 4), o_keep = im.in(reps > 0 ? h.data() : nullptr, sq_b);
+    if (!im.upload()) return -2;
+    const SampleBufs sb = sample_bufs_at(im.at<uint8_t>(o_sq), (size_t)n_rows);
+    auto launch = [&]() -> hipError_t {
         if (which == 0)
-            hipLaunchKernelGGL(bgk::sample_wide_rows_kernel, dim3(n_rows), dim3(bgk::WIDE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, sb.wide, sb.ctl, sb.seq,
-                               d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), 1, d.at<int32_t>(o_nc));
+            hipLaunchKernelGGL(bgk::sample_wide_rows_kernel, dim3(n_rows), dim3(bgk::WIDE_THREADS), 0, 0, im.at<const float>(o_lg), n_vocab, n_vocab, sb.wide, sb.ctl, sb.seq,
+                               im.at<bgk::SeqState>(o_st), im.at<int32_t>(o_id), 1, im.at<int32_t>(o_nc));
         else
-            hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, sb.ctl, sb.seq,
-                               d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), 1);
+            hipLaunchKernelGGL(bgk::sample_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, im.at<const float>(o_lg), n_vocab, n_vocab, sb.ctl, sb.seq,
+                               im.at<bgk::SeqState>(o_st), im.at<int32_t>(o_id), 1);
+        return hipGetLastError();
     };
-    launch();
-    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, launch());
     HIP_TRY(-2, hipDeviceSynchronize());
     if (mt_out) {
         std::vector<uint8_t> back(sq_b);
-        HIP_TRY(-2, hipMemcpy(back.data(), sb.ctl, sq_b, hipMemcpyDeviceToHost));
+        if (!im.read(o_sq, back.data())) return -2;
         mt_states_out(mt_out, sample_bufs_at(back.data(), (size_t)n_rows).seq, n_rows);
     }
-    if (ids_out) HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
-    if (n_cand_out) HIP_TRY(-2, hipMemcpy(n_cand_out, d.p + o_nc, id_b, hipMemcpyDeviceToHost));
-    if (reps > 0) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        HIP_TRY(-2, hipMemcpy(d.p + o_keep, h.data(), sq_b, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipEventCreate(&e0));
-        HIP_TRY(-2, hipEventCreate(&e1));
-        hipError_t err = hipSuccess;
-        for (int i = 0; i < reps && err == hipSuccess; i++) {
-            float ms = 0.0f;
-            err = hipMemcpyAsync(sb.ctl, d.p + o_keep, sq_b, hipMemcpyDeviceToDevice, 0);
-            if (err == hipSuccess) err = hipMemsetAsync(d.p + o_st, 0, st_b, 0);
-            if (err == hipSuccess) err = hipEventRecord(e0, 0);
-            if (err == hipSuccess) { launch(); err = hipGetLastError(); }
-            if (err == hipSuccess) err = hipEventRecord(e1, 0);
-            if (err == hipSuccess) err = hipEventSynchronize(e1);
-            if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-            seconds_out[i] = (double)ms * 1e-3;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        HIP_TRY(-2, err);
-    }
-    return 0;
+    if (ids_out && !im.read(o_id, ids_out)) return -2;
+    if (n_cand_out && !im.read(o_nc, n_cand_out)) return -2;
+    auto restore = [&] { const hipError_t e = im.restore(o_sq, o_keep); return e == hipSuccess ? im.clear(o_st, o_st.bytes) : e; };
+    return time_launches(reps, restore, launch, [&](int i, float ms) { seconds_out[i] = (double)ms * 1e-3; });
 }
 // sample_rows_kernel over rows held in host memory (tests: ties, any row width and alignment, the selection's round form, a generator block running out):
 // mt_states is advanced in place
@@ -808,7 +895,7 @@ int biogpt_hip_sample_wide_rows_device(int device, const float *logits, int32_t 
 int biogpt_hip_sample_wide_rows_bench(int device, const float *logits, int32_t n_rows, int32_t n_vocab, const biogpt_hip_sampler *sampler, const uint32_t *mt_states,
                                       int32_t which, int32_t reps, double *seconds_out) {
     clear_error();
-    if (reps < 1) BG_FAIL(-1, "reps must be in [1, 10000]");
+    if (reps < 1) BG_FAIL(-1, "reps must be in [1, %d]", PROBE_MAX_REPS);
     return sample_wide_rows_device(device, logits, n_rows, n_vocab, sampler, mt_states, nullptr, nullptr, nullptr, which, reps, seconds_out);
 }
 
@@ -831,35 +918,28 @@ int biogpt_hip_genlp_rows_device(int device, int32_t mode, const float *rows, in
         if (!check_sample_values(top_k, top_p, temp, -1, n_vocab) || !check_mt_states(mt_states, n_rows)) return -1;
     }
     HIP_TRY(-2, hipSetDevice(device));
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, sq_b = sample_bufs_at(nullptr, (size_t)n_rows).bytes, lp_b = genlp_bufs_at(nullptr, (size_t)n_rows, (size_t)n_top).bytes;
-    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = (size_t)n_rows * 4;
-    std::vector<uint8_t> h(sq_b, 0);
+    std::vector<uint8_t> h(sample_bufs_at(nullptr, (size_t)n_rows).bytes, 0);
     const SampleBufs hb = sample_bufs_at(h.data(), (size_t)n_rows);
     *hb.ctl = sample_ctl_of(mode == 1 ? top_k : 1, -1, n_rows, top_p, temp);
     if (mode == 1) mt_states_in(hb.seq, mt_states, n_rows);
-    ByteLayout l;      // [logits | ctl + states | column states | ids | the log-probability block]
-    const size_t o_lg = l.part(lg_b), o_sq = l.part(sq_b), o_st = l.part(st_b), o_id = l.part(id_b), o_lp = l.part(lp_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    const SampleBufs sb = sample_bufs_at(d.p + o_sq, (size_t)n_rows);
-    const GenLpBufs lb = genlp_bufs_at(d.p + o_lp, (size_t)n_rows, (size_t)n_top);
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(sb.ctl, h.data(), sq_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_st, 0, st_b));
-    HIP_TRY(-2, hipMemset(d.p + o_id, 0xff, l.bytes() - o_id));
+    ProbeImage im;      // [logits | ctl + states | column states | ids | the log-probability block]
+    const ProbePart o_lg = im.in(rows, (size_t)n_rows * n_vocab * 4), o_sq = im.in(h.data(), h.size()), o_st = im.fill(sizeof(bgk::SeqState) * (size_t)n_rows),
+                    o_id = im.out((size_t)n_rows * 4), o_lp = im.out(genlp_bufs_at(nullptr, (size_t)n_rows, (size_t)n_top).bytes);
+    if (!im.upload()) return -2;
+    const SampleBufs sb = sample_bufs_at(im.at<uint8_t>(o_sq), (size_t)n_rows);
+    const GenLpBufs lb = genlp_bufs_at(im.at<uint8_t>(o_lp), (size_t)n_rows, (size_t)n_top);
     if (!genlp_upload(lb, n_top, 1)) return -2;
     if (mode == 0)
-        hipLaunchKernelGGL(bgk::genlp_greedy_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, d.at<bgk::SeqState>(o_st),
-                           d.at<int32_t>(o_id), 1, 1, lb.out());
+        hipLaunchKernelGGL(bgk::genlp_greedy_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, im.at<const float>(o_lg), n_vocab, n_vocab, im.at<bgk::SeqState>(o_st),
+                           im.at<int32_t>(o_id), 1, 1, lb.out());
     else
-        hipLaunchKernelGGL(bgk::sample_lp_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, d.at<const float>(o_lg), n_vocab, n_vocab, sb.ctl, sb.seq,
-                           d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), 1, lb.out());
+        hipLaunchKernelGGL(bgk::sample_lp_rows_kernel, dim3(n_rows), dim3(bgk::SAMPLE_THREADS), 0, 0, im.at<const float>(o_lg), n_vocab, n_vocab, sb.ctl, sb.seq,
+                           im.at<bgk::SeqState>(o_st), im.at<int32_t>(o_id), 1, lb.out());
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
-    if (!genlp_read(lb, &req, n_rows, 1, nullptr)) return -2;
+    if (!im.read(o_id, ids_out) || !genlp_read(lb, &req, n_rows, 1, nullptr)) return -2;
     if (mode == 1) {
-        HIP_TRY(-2, hipMemcpy(h.data(), sb.ctl, sq_b, hipMemcpyDeviceToHost));
+        if (!im.read(o_sq, h.data())) return -2;
         mt_states_out(mt_states, hb.seq, n_rows);
     }
     return 0;
@@ -911,8 +991,7 @@ static int queue_probe_run(const QueueProbeArgs &a, const QueueProbeMode &m) {
     if (!check_mt_states(a.mt_states, n_rows)) return -1;
     HIP_TRY(-2, hipSetDevice(a.device));
     static_assert(sizeof(bgk::SeqState) == 32, "eight words per column state");
-    const size_t lg_b = (size_t)n_rows * n_vocab * 4, entries = (size_t)n_rows * (size_t)stride, lp_b = genlp_bufs_at(nullptr, entries, (size_t)n_top).bytes;
-    const size_t st_b = sizeof(bgk::SeqState) * (size_t)n_rows, id_b = entries * 4;
+    const size_t entries = (size_t)n_rows * (size_t)stride;
     std::vector<uint8_t> h(m.cols(nullptr).bytes, 0);
     const QueueProbeCols hq = m.cols(h.data());
     std::vector<int32_t> ids(entries, -1);      // (0xff bytes)
@@ -924,25 +1003,17 @@ static int queue_probe_run(const QueueProbeArgs &a, const QueueProbeMode &m) {
         hq.hdr->fin[r] = a.hdr[1 + r]; hq.hdr->len[r] = a.hdr[1 + n_rows + r];
     }
     m.fill(h.data(), ids.data());
-    ByteLayout l;
-    const size_t o_lg = l.part(lg_b), o_q = l.part(h.size()), o_st = l.part(st_b), o_id = l.part(id_b), o_lp = l.part(lp_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    const GenLpBufs lb = genlp_bufs_at(d.p + o_lp, entries, (size_t)n_top);
+    ProbeImage im;
+    const ProbePart o_lg = im.in(a.rows, (size_t)n_rows * n_vocab * 4), o_q = im.in(h.data(), h.size()), o_st = im.in(a.states, sizeof(bgk::SeqState) * (size_t)n_rows),
+                    o_id = im.out(entries * 4, ids.data()), o_lp = im.out(genlp_bufs_at(nullptr, entries, (size_t)n_top).bytes);
+    if (!im.upload()) return -2;
+    const GenLpBufs lb = genlp_bufs_at(im.at<uint8_t>(o_lp), entries, (size_t)n_top);
     const biogpt_hip_gen_logprobs req = a.req();
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, a.rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_q, h.data(), h.size(), hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_st, a.states, st_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_id, 0xff, l.bytes() - o_id));
-    HIP_TRY(-2, hipMemcpy(d.p + o_id, ids.data(), id_b, hipMemcpyHostToDevice));
     if (!genlp_upload(lb, n_top, stride)) return -2;
-    m.launch(d.p + o_q, d.at<float>(o_lg), d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_id), a.with_lp ? &lb : nullptr);
+    m.launch(im.at<uint8_t>(o_q), im.at<float>(o_lg), im.at<bgk::SeqState>(o_st), im.at<int32_t>(o_id), a.with_lp ? &lb : nullptr);
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(a.ids_out, d.p + o_id, id_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(a.states, d.p + o_st, st_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_q, h.size(), hipMemcpyDeviceToHost));
-    if (!genlp_read(lb, &req, n_rows, stride, nullptr)) return -2;
+    if (!im.read(o_id, a.ids_out) || !im.read(o_st, a.states) || !im.read(o_q, h.data()) || !genlp_read(lb, &req, n_rows, stride, nullptr)) return -2;
     a.hdr[0] = hq.hdr->n_live;
     mt_states_out(a.mt_states, hq.seq, n_rows);
     for (int r = 0; r < n_rows; r++) {
@@ -1043,26 +1114,16 @@ int64_t biogpt_hip_queue_stream_device(int device, const int32_t *n_gen, const i
     const size_t rows = (size_t)C * (size_t)gen_stride, entries = n_top >= 0 ? (size_t)C * (size_t)lp_stride : 0, k = n_top > 0 ? (size_t)n_top : 0;
     std::vector<bgk::SeqState> st((size_t)C);
     for (int c = 0; c < C; c++) { st[(size_t)c] = bgk::SeqState{}; st[(size_t)c].n_gen = n_gen[c]; st[(size_t)c].seq_id = c; }
-    ByteLayout l;
-    const size_t o_st = l.part(sizeof(bgk::SeqState) * (size_t)C), o_gen = l.part(rows * 4), o_lp = l.part(entries * 4), o_ti = l.part(entries * k * 4), o_tl = l.part(entries * k * 4),
-                 o_out = l.part((size_t)block_bytes);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemcpy(d.p + o_st, st.data(), sizeof(bgk::SeqState) * (size_t)C, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_gen, gen_rows, rows * 4, hipMemcpyHostToDevice));
-    if (entries > 0) HIP_TRY(-2, hipMemcpy(d.p + o_lp, lp, entries * 4, hipMemcpyHostToDevice));
-    if (entries * k > 0) {
-        HIP_TRY(-2, hipMemcpy(d.p + o_ti, top_ids, entries * k * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_tl, top_lp, entries * k * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, (size_t)block_bytes));
-    const QueueStreamBufs sb = queue_stream_at(d.p + o_out, C, g, n_top);
-    hipLaunchKernelGGL(bgk::queue_stream_kernel, dim3(C), dim3(bgk::QUEUE_STREAM_THREADS), 0, 0, d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_gen), gen_stride, C, g, sb.out,
-                       n_top >= 0 ? d.at<float>(o_lp) : nullptr, n_top >= 0 ? d.at<int32_t>(o_ti) : nullptr, n_top >= 0 ? d.at<float>(o_tl) : nullptr, lp_stride, (int)k);
+    ProbeImage im;
+    const ProbePart o_st = im.in(st.data(), sizeof(bgk::SeqState) * (size_t)C), o_gen = im.in(gen_rows, rows * 4), o_lp = im.in(lp, entries * 4), o_ti = im.in(top_ids, entries * k * 4),
+                    o_tl = im.in(top_lp, entries * k * 4), o_out = im.out((size_t)block_bytes);
+    if (!im.upload()) return -2;
+    const QueueStreamBufs sb = queue_stream_at(im.at<uint8_t>(o_out), C, g, n_top);
+    hipLaunchKernelGGL(bgk::queue_stream_kernel, dim3(C), dim3(bgk::QUEUE_STREAM_THREADS), 0, 0, im.at<bgk::SeqState>(o_st), im.at<int32_t>(o_gen), gen_stride, C, g, sb.out,
+                       n_top >= 0 ? im.at<float>(o_lp) : nullptr, n_top >= 0 ? im.at<int32_t>(o_ti) : nullptr, n_top >= 0 ? im.at<float>(o_tl) : nullptr, lp_stride, (int)k);
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(block_out, d.p + o_out, (size_t)block_bytes, hipMemcpyDeviceToHost));
-    return (int64_t)need;
+    return im.read(o_out, block_out) ? (int64_t)need : -2;
 }
 
 // queue_cancel_kernel on the list cols [n] over QUEUE_COLS constructed columns.  In and out: finished [512] (SampleSeq::finished) and hdr [1 + 2 * 512] (n_live,
@@ -1085,20 +1146,14 @@ int biogpt_hip_queue_cancel_device(int device, const int32_t *cols, int32_t n, i
         st[(size_t)c] = bgk::SeqState{}; st[(size_t)c].n_gen = n_gen[c];
         h.fin[c] = hdr[1 + c]; h.len[c] = hdr[1 + Q + c];
     }
-    ByteLayout l;
-    const size_t o_sq = l.part(sizeof(bgk::SampleSeq) * Q), o_st = l.part(sizeof(bgk::SeqState) * Q), o_h = l.part(sizeof(h)), o_c = l.part((size_t)n * 4);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemcpy(d.p + o_sq, sq.data(), sizeof(bgk::SampleSeq) * Q, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_st, st.data(), sizeof(bgk::SeqState) * Q, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_h, &h, sizeof(h), hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_c, cols, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(bgk::queue_cancel_kernel, dim3((n + bgk::QUEUE_ADMIT_THREADS - 1) / bgk::QUEUE_ADMIT_THREADS), dim3(bgk::QUEUE_ADMIT_THREADS), 0, 0, d.at<int32_t>(o_c), n,
-                       d.at<bgk::SampleSeq>(o_sq), d.at<bgk::SeqState>(o_st), d.at<bgk::QueueHdr>(o_h));
+    ProbeImage im;
+    const ProbePart o_sq = im.in(sq.data(), sizeof(bgk::SampleSeq) * Q), o_st = im.in(st.data(), sizeof(bgk::SeqState) * Q), o_h = im.in(&h, sizeof(h)), o_c = im.in(cols, (size_t)n * 4);
+    if (!im.upload()) return -2;
+    hipLaunchKernelGGL(bgk::queue_cancel_kernel, dim3((n + bgk::QUEUE_ADMIT_THREADS - 1) / bgk::QUEUE_ADMIT_THREADS), dim3(bgk::QUEUE_ADMIT_THREADS), 0, 0, im.at<int32_t>(o_c), n,
+                       im.at<bgk::SampleSeq>(o_sq), im.at<bgk::SeqState>(o_st), im.at<bgk::QueueHdr>(o_h));
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(sq.data(), d.p + o_sq, sizeof(bgk::SampleSeq) * Q, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(&h, d.p + o_h, sizeof(h), hipMemcpyDeviceToHost));
+    if (!im.read(o_sq, sq.data()) || !im.read(o_h, &h)) return -2;
     hdr[0] = h.n_live;
     for (int c = 0; c < Q; c++) { finished[c] = sq[(size_t)c].finished; hdr[1 + c] = h.fin[c]; hdr[1 + Q + c] = h.len[c]; }
     return 0;
@@ -1112,16 +1167,13 @@ int biogpt_hip_quantize_rows_device(int device, int32_t type, const float *src, 
     if (!is_quantized(type)) BG_FAIL(-1, "type %d is not a block-quantized format", type);
     if (!select_device(device)) return -1;
     const long long nblocks = (long long)nrows * (k / QK);
-    const size_t in_bytes = (size_t)nrows * (size_t)k * 4, out_bytes = (size_t)nblocks * file_block_bytes(type);
-    DeviceBytes d_src, d_dst;
-    if (!d_src.alloc(in_bytes)) return -2;
-    if (!d_dst.alloc(out_bytes)) BG_FAIL(-2, "hipMalloc of %zu bytes failed", out_bytes);
-    HIP_TRY(-2, hipMemcpy(d_src.p, src, in_bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(bgk::quantize_blocks_kernel, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, 0, d_src.at<float>(0), d_dst.p, nblocks, (int)type,
+    ProbeImage im;
+    const ProbePart o_src = im.in(src, (size_t)nrows * (size_t)k * 4), o_dst = im.out((size_t)nblocks * file_block_bytes(type));
+    if (!im.upload()) return -2;
+    hipLaunchKernelGGL(bgk::quantize_blocks_kernel, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, 0, im.at<float>(o_src), im.at<uint8_t>(o_dst), nblocks, (int)type,
                        (int)file_block_bytes(type));
     HIP_TRY(-2, hipGetLastError());
-    HIP_TRY(-2, hipMemcpy(dst, d_dst.p, out_bytes, hipMemcpyDeviceToHost));
-    return 0;
+    return im.read(o_dst, dst) ? 0 : -2;
 }
 
 // The decode launches' LayerNorm + Q8 stage (mode 0: ln4_q8_1024, one workgroup of 512 threads per row of 1024) or their activation quantizer (mode 1:
@@ -1136,16 +1188,11 @@ int biogpt_hip_ln_q8_device(int device, int32_t mode, const float *x, int32_t n_
     if (mode == 0 && q81 && !want_sum) BG_FAIL(-1, "the Q8_1 form always writes its block sums");
     if (!select_device(device)) return -1;
     const size_t k = mode == 0 ? 1024 : 32, nb = k / 32, n_wb = mode == 0 ? (wb_per_row ? (size_t)n_rows : 1) : 0;
-    ByteLayout l;      // [x | gain | bias | codes | scales | sums]
-    const size_t o_x = l.part((size_t)n_rows * k * 4), o_w = l.part(n_wb * 1024 * 4), o_b = l.part(n_wb * 1024 * 4);
-    const size_t o_q = l.part((size_t)n_rows * k), o_d = l.part((size_t)n_rows * nb * 4), o_s = l.part((size_t)n_rows * nb * 4);
-    DeviceBytes dv;
-    if (!dv.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemset(dv.p + o_q, 0xff, l.bytes() - o_q));
-    HIP_TRY(-2, hipMemcpy(dv.p + o_x, x, (size_t)n_rows * k * 4, hipMemcpyHostToDevice));
+    ProbeImage dv;      // [x | gain | bias | codes | scales | sums]
+    const ProbePart o_x = dv.in(x, (size_t)n_rows * k * 4), o_w = dv.in(ln_w, n_wb * 1024 * 4), o_b = dv.in(ln_b, n_wb * 1024 * 4);
+    const ProbePart o_q = dv.out((size_t)n_rows * k), o_d = dv.out((size_t)n_rows * nb * 4), o_s = dv.out((size_t)n_rows * nb * 4);
+    if (!dv.upload()) return -2;
     if (mode == 0) {
-        HIP_TRY(-2, hipMemcpy(dv.p + o_w, ln_w, n_wb * 1024 * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(dv.p + o_b, ln_b, n_wb * 1024 * 4, hipMemcpyHostToDevice));
         const int stride = wb_per_row ? 1024 : 0;
         auto kern = q81 ? bgk::ln_q8_probe_kernel<true, true> : (want_sum ? bgk::ln_q8_probe_kernel<false, true> : bgk::ln_q8_probe_kernel<false, false>);
         hipLaunchKernelGGL(kern, dim3(n_rows), dim3(512), 0, 0, dv.at<const float>(o_x), dv.at<const float>(o_w), dv.at<const float>(o_b), stride, eps,
@@ -1156,10 +1203,7 @@ int biogpt_hip_ln_q8_device(int device, int32_t mode, const float *x, int32_t n_
     }
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(q_out, dv.p + o_q, (size_t)n_rows * k, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(d_out, dv.p + o_d, (size_t)n_rows * nb * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(s_out, dv.p + o_s, (size_t)n_rows * nb * 4, hipMemcpyDeviceToHost));
-    return 0;
+    return dv.read(o_q, q_out) && dv.read(o_d, d_out) && dv.read(o_s, s_out) ? 0 : -2;
 }
 
 // q8_round, ln_inv_std and q8_scales (kernels_decode.hip.h) against the expressions they stand for, over all 2^32 float bit patterns in one launch.
@@ -1172,13 +1216,13 @@ int biogpt_hip_q8_forms_device(int device, uint64_t *out) {
     constexpr int N = bgk::Q8F_CHECKS;
     unsigned long long h[3 * N];
     for (int i = 0; i < 3 * N; i++) h[i] = i < 2 * N ? 0ull : ~0ull;
-    DeviceBytes dv;
-    if (!dv.alloc(sizeof(h))) return -2;
-    HIP_TRY(-2, hipMemcpy(dv.p, h, sizeof(h), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(bgk::q8_forms_kernel, dim3(bgk::Q8F_BLOCKS), dim3(bgk::Q8F_THREADS), 0, 0, dv.at<unsigned long long>(0));
+    ProbeImage dv;
+    const ProbePart o_h = dv.in(h, sizeof(h));
+    if (!dv.upload()) return -2;
+    hipLaunchKernelGGL(bgk::q8_forms_kernel, dim3(bgk::Q8F_BLOCKS), dim3(bgk::Q8F_THREADS), 0, 0, dv.at<unsigned long long>(o_h));
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(h, dv.p, sizeof(h), hipMemcpyDeviceToHost));
+    if (!dv.read(o_h, h)) return -2;
     for (int i = 0; i < 3 * N; i++) out[i] = (uint64_t)h[i];
     return 0;
 }
@@ -1220,18 +1264,15 @@ int biogpt_hip_lookup_draft_device(int device, const int32_t *texts, const int32
         hs[(size_t)s] = bgk::SeqState{};
         hs[(size_t)s].n_past = n_past[s]; hs[(size_t)s].token = texts[at - 1]; hs[(size_t)s].n_gen = n_gen[s]; hs[(size_t)s].seq_id = s;
     }
-    ByteLayout l;      // [the step's state, with the column states as 0xff | sequence states]
-    const size_t o_lb = l.part(sz), o_st = l.part(sizeof(bgk::SeqState) * (size_t)n_seqs);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    const LookupBufs lb = lookup_bufs_at(d.p + o_lb, (size_t)n_seqs, (size_t)n_seqs * S, total);
     std::memset(hb.cols, 0xff, sizeof(bgk::SeqState) * (size_t)n_seqs * S);
-    HIP_TRY(-2, hipMemcpy(d.p + o_lb, h.data(), sz, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_st, hs.data(), sizeof(bgk::SeqState) * (size_t)n_seqs, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(bgk::lookup_draft_kernel, dim3(n_seqs), dim3(bgk::LK_DRAFT_THREADS), 0, 0, lb.ctl, lb.seq, lb.text, d.at<const bgk::SeqState>(o_st), lb.cols);
+    ProbeImage im;      // [the step's state, with the column states as 0xff | sequence states]
+    const ProbePart o_lb = im.in(h.data(), sz), o_st = im.in(hs.data(), sizeof(bgk::SeqState) * (size_t)n_seqs);
+    if (!im.upload()) return -2;
+    const LookupBufs lb = lookup_bufs_at(im.at<uint8_t>(o_lb), (size_t)n_seqs, (size_t)n_seqs * S, total);
+    hipLaunchKernelGGL(bgk::lookup_draft_kernel, dim3(n_seqs), dim3(bgk::LK_DRAFT_THREADS), 0, 0, lb.ctl, lb.seq, lb.text, im.at<const bgk::SeqState>(o_st), lb.cols);
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_lb, sz, hipMemcpyDeviceToHost));
+    if (!im.read(o_lb, h.data())) return -2;
     for (int s = 0; s < n_seqs; s++) {
         std::memcpy(draft_out + (size_t)s * (bgk::LK_MAX_DRAFT + 1), hb.seq[s].draft, sizeof(hb.seq[s].draft));
         d_out[s] = hb.seq[s].d;
@@ -1284,24 +1325,17 @@ int biogpt_hip_lookup_accept_device(int device, const float *rows, int32_t n_seq
         hs[(size_t)s] = bgk::SeqState{};
         hs[(size_t)s].n_past = n_past[s]; hs[(size_t)s].token = -1; hs[(size_t)s].n_gen = n_gen[s]; hs[(size_t)s].seq_id = s;
     }
-    const size_t lg_b = (size_t)n_seqs * S * n_vocab * 4, st_b = sizeof(bgk::SeqState) * (size_t)n_seqs, gen_b = words * 4;
-    ByteLayout l;      // [rows | the step's state | sequence states | generated ids, 0xff]
-    const size_t o_lg = l.part(lg_b), o_lb = l.part(sz), o_st = l.part(st_b), o_gen = l.part(gen_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    const LookupBufs lb = lookup_bufs_at(d.p + o_lb, (size_t)n_seqs, 0, words);
-    HIP_TRY(-2, hipMemcpy(d.p + o_lg, rows, lg_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_lb, h.data(), sz, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_st, hs.data(), st_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemset(d.p + o_gen, 0xff, gen_b));
-    hipLaunchKernelGGL(bgk::lookup_accept_kernel, dim3(n_seqs), dim3(bgk::LK_ACCEPT_THREADS), 0, 0, lb.ctl, lb.seq, lb.text, d.at<const float>(o_lg), n_vocab, n_vocab,
-                       d.at<bgk::SeqState>(o_st), d.at<int32_t>(o_gen), n_predict);
+    ProbeImage im;      // [rows | the step's state | sequence states | generated ids, 0xff]
+    const ProbePart o_lg = im.in(rows, (size_t)n_seqs * S * n_vocab * 4), o_lb = im.in(h.data(), sz), o_st = im.in(hs.data(), sizeof(bgk::SeqState) * (size_t)n_seqs),
+                    o_gen = im.out(words * 4);
+    if (!im.upload()) return -2;
+    const LookupBufs lb = lookup_bufs_at(im.at<uint8_t>(o_lb), (size_t)n_seqs, 0, words);
+    hipLaunchKernelGGL(bgk::lookup_accept_kernel, dim3(n_seqs), dim3(bgk::LK_ACCEPT_THREADS), 0, 0, lb.ctl, lb.seq, lb.text, im.at<const float>(o_lg), n_vocab, n_vocab,
+                       im.at<bgk::SeqState>(o_st), im.at<int32_t>(o_gen), n_predict);
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
     std::vector<int32_t> gen(words);
-    HIP_TRY(-2, hipMemcpy(h.data(), d.p + o_lb, sz, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(hs.data(), d.p + o_st, st_b, hipMemcpyDeviceToHost));
-    HIP_TRY(-2, hipMemcpy(gen.data(), d.p + o_gen, gen_b, hipMemcpyDeviceToHost));
+    if (!im.read(o_lb, h.data()) || !im.read(o_st, hs.data()) || !im.read(o_gen, gen.data())) return -2;
     for (int s = 0; s < n_seqs; s++) {
         int32_t *e = emit_out + (size_t)s * (bgk::LK_MAX_DRAFT + 1);
         std::fill(e, e + bgk::LK_MAX_DRAFT + 1, -1);
@@ -1359,138 +1393,59 @@ int biogpt_hip_chain_device(int device, int32_t op, int32_t route, int32_t wtype
     if ((op == CP_OPROJ || op == CP_FC2) && !resid) BG_FAIL(-1, "resid is NULL");
     if (f32_out ? !out : (!out_q || !out_d || !out_s)) BG_FAIL(-1, "%s", f32_out ? "out is NULL" : "out_q, out_d or out_s is NULL");
     const bool batch = seq_states != nullptr;
-    if (op == CP_QKV) {
-        if ((dev_state != nullptr) == batch) BG_FAIL(-1, "exactly one of dev_state and seq_states names the column states");
-        if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
-        if (!batch && col_mode) BG_FAIL(-1, "col_mode 1 needs seq_states");
-        if (!k_slots || !v_slots) BG_FAIL(-1, "k_slots or v_slots is NULL");
-        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
-        if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
-        if (!batch && n_slots != 1) BG_FAIL(-1, "the context's own columns have one slot");
-    } else if (dev_state || batch) BG_FAIL(-1, "only QKV reads column states");
-    // ---- the route the engine takes ----
+    // ---- the route the engine takes: checked between the column states' arguments and the walk over the columns ----
     const ChainOp cop = op == CP_QKV ? CHAIN_QKV_Q8 : op == CP_OPROJ ? CHAIN_OPROJ : op == CP_FC1_LN ? CHAIN_FC1 : op == CP_FC1_Q8 ? CHAIN_FC1_Q8 : op == CP_FC2 ? CHAIN_FC2 : CHAIN_LMHEAD_Q8;
     const bool mfma = route == CK_MFMA_1 || route == CK_MFMA_2;
-    if (!lnq) {
-        if (route < CK_VALU_1 || route > CK_MFMA_2) BG_FAIL(-1, "route %d is no kernel of the chain", route);
+    auto route_ok = [&]() -> bool {
+        if (lnq) return true;
+        if (route < CK_VALU_1 || route > CK_MFMA_2) PROBE_FAIL("biogpt_hip_chain_device", false, "route %d is no kernel of the chain", route);
         if (op == CP_FC1_LN) {
-            if (route != CK_VALU_1 || N != 1) BG_FAIL(-1, "FC1_LN is the 1-column kernel alone: one column, route 0");
+            if (route != CK_VALU_1 || N != 1) PROBE_FAIL("biogpt_hip_chain_device", false, "FC1_LN is the 1-column kernel alone: one column, route 0");
         } else if (mfma) {
             const int min_cols = (op == CP_QKV && !(batch && col_mode == 0)) ? MFMA_MIN_PASS_COLS : MFMA_MIN_DECODE_COLS;
-            if (N < min_cols) BG_FAIL(-1, "%d columns: the matrix-core kernels run from %d columns on", N, min_cols);
-            if (M % 16 != 0) BG_FAIL(-1, "M = %d is no whole number of 16-row tiles: such a matrix has no image and stays on the 8-column kernel", M);
+            if (N < min_cols) PROBE_FAIL("biogpt_hip_chain_device", false, "%d columns: the matrix-core kernels run from %d columns on", N, min_cols);
+            if (M % 16 != 0) PROBE_FAIL("biogpt_hip_chain_device", false, "M = %d is no whole number of 16-row tiles: such a matrix has no image and stays on the 8-column kernel", M);
             static const int site_of[7] = {-1, 0, 1, -1, 2, 3, 4};
             const int tiles = bg_mfma_tiles(wtype, site_of[op], M, N);
-            if (tiles != (route == CK_MFMA_2 ? 2 : 1)) BG_FAIL(-1, "the launch takes %d row tile(s) per wave for this type, M = %d and N = %d", tiles, M, N);
+            if (tiles != (route == CK_MFMA_2 ? 2 : 1)) PROBE_FAIL("biogpt_hip_chain_device", false, "the launch takes %d row tile(s) per wave for this type, M = %d and N = %d", tiles, M, N);
         } else {
             const bool one = chain_one_column(cop, N, batch);
-            if (one != (route == CK_VALU_1)) BG_FAIL(-1, "%s", one ? "one column of the context's own takes the 1-column kernel here" : "the 1-column kernel serves N = 1 without column states, at out_proj, fc1 (LayerNorm fused) and fc2 only");
+            if (one != (route == CK_VALU_1)) PROBE_FAIL("biogpt_hip_chain_device", false, "%s", one ? "one column of the context's own takes the 1-column kernel here" : "the 1-column kernel serves N = 1 without column states, at out_proj, fc1 (LayerNorm fused) and fc2 only");
         }
-    }
-    // ---- every column's cache row inside its slot, no two columns on one row ----
-    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
-    if (op == CP_QKV) {
-        std::set<std::pair<int, int>> seen;
-        for (int i = 0; i < N; i++) {
-            const int pos = batch ? hs[i].n_past : dev_state[0] + i, slot = batch ? (col_mode ? hs[i].seq_id : i) : 0;
-            if (pos < 0 || pos >= P) BG_FAIL(-1, "column %d: position %d outside [0, P)", i, pos);
-            if (slot < 0 || slot >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, slot);
-            if (!seen.insert({slot, pos}).second) BG_FAIL(-1, "column %d: a second column writes slot %d, position %d", i, slot, pos);
-        }
-    }
+        return true;
+    };
+    if (!check_probe_columns(__func__, op == CP_QKV, N, dev_state, seq_states, col_mode, P, n_slots, k_slots, v_slots, route_ok)) return -1;
     HIP_TRY(-2, hipSetDevice(device));
     const int cols = ((N + 15) & ~15) + 1, ldo = lnq ? 0 : ((M + 127) & ~127) + 16, MQ = lnq ? 1024 : M;      // MQ: Q8 values per output column
-    const size_t bpr = (size_t)K / QK, nblk = lnq ? 0 : (size_t)M * bpr;
-    const size_t qs_b = nblk * (wtype == T_Q8_0 ? 32 : 16), sc_b = nblk * (q81 ? 4 : 2), qh_b = (wtype == T_Q5_0 || wtype == T_Q5_1) ? nblk * 4 : 0;
-    const size_t slot_f = (size_t)16 * P * 64, kv_b = op == CP_QKV ? slot_f * 4 * (size_t)n_slots : 0;
-    const size_t out_b = f32_out ? (size_t)cols * (op == CP_QKV ? 1024 : ldo) * 4 : 0, oq_b = q8_out ? (size_t)cols * MQ : 0, od_b = q8_out ? (size_t)cols * (MQ / 32) * 4 : 0;
-    size_t img_b = 0, xq = 0, xs = 0;
-    if (mfma) tile_image_place(wtype, M, K, img_b, xq, xs);
-    ByteLayout l;
-    const size_t o_qs = l.part(qs_b), o_sc = l.part(sc_b), o_qh = l.part(qh_b), o_img = l.part(img_b), o_x = l.part(ln_in ? (size_t)N * 1024 * 4 : 0), o_lw = l.part(ln_in ? 4096 : 0),
-                 o_lb = l.part(ln_in ? 4096 : 0), o_aq = l.part(ln_in ? 0 : (size_t)N * K), o_ad = l.part(ln_in ? 0 : (size_t)N * bpr * 4), o_as = l.part(ln_in ? 0 : (size_t)N * bpr * 4),
-                 o_bias = l.part(bias ? (size_t)MQ * 4 : 0), o_res = l.part(resid ? (size_t)N * M * 4 : 0), o_ds = l.part(sizeof(bgk::DevState)),
-                 o_st = l.part(batch ? sizeof(bgk::SeqState) * (size_t)N : 0), o_tab = l.part(65536 * 2), o_k = l.part(kv_b), o_v = l.part(kv_b),
-                 o_out = l.part(out_b), o_oq = l.part(oq_b), o_od = l.part(od_b), o_os = l.part(od_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));      // the outputs with their guard columns and rows
-    if (!lnq) {
-        std::vector<uint8_t> qs(qs_b), sc(sc_b), qh(qh_b);
-        repack_rows(wtype, static_cast<const uint8_t *>(w_rows), M, K, qs.data(), sc.data(), qh.data());
-        HIP_TRY(-2, hipMemcpy(d.p + o_qs, qs.data(), qs_b, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_sc, sc.data(), sc_b, hipMemcpyHostToDevice));
-        if (qh_b) HIP_TRY(-2, hipMemcpy(d.p + o_qh, qh.data(), qh_b, hipMemcpyHostToDevice));
-    }
-    if (ln_in) {
-        HIP_TRY(-2, hipMemcpy(d.p + o_x, x, (size_t)N * 1024 * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_lw, ln_w, 4096, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_lb, ln_b, 4096, hipMemcpyHostToDevice));
-    } else {
-        HIP_TRY(-2, hipMemcpy(d.p + o_aq, aq_q, (size_t)N * K, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_ad, aq_d, (size_t)N * bpr * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_as, aq_s, (size_t)N * bpr * 4, hipMemcpyHostToDevice));
-    }
-    if (bias && !lnq) HIP_TRY(-2, hipMemcpy(d.p + o_bias, bias, (size_t)MQ * 4, hipMemcpyHostToDevice));
-    if (resid && f32_out && op != CP_QKV) HIP_TRY(-2, hipMemcpy(d.p + o_res, resid, (size_t)N * M * 4, hipMemcpyHostToDevice));
-    const int32_t no_state[4] = {0, 0, 0, 0};
-    HIP_TRY(-2, hipMemcpy(d.p + o_ds, (op == CP_QKV && !batch) ? dev_state : no_state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
-    if (batch) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
-    if (op == CP_QKV) {
-        HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
-    }
-    const std::vector<uint16_t> tg = gelu_table_f16();
-    HIP_TRY(-2, hipMemcpy(d.p + o_tab, tg.data(), 65536 * 2, hipMemcpyHostToDevice));
+    const size_t bpr = (size_t)K / QK, kv_b = op == CP_QKV ? (size_t)16 * P * 64 * 4 * (size_t)n_slots : 0;
+    const bool with_resid = f32_out && op != CP_QKV && op != CP_LMHEAD;
+    ProbeImage im;      // [weights | image | x, gain, bias of the LayerNorm or the Q8 columns | the stage's parts | out | out_q | out_d | out_s], guard columns and rows in the outputs
+    const BlockRows wr = upload_block_rows(im, wtype, lnq ? nullptr : w_rows, M, K, mfma);
+    const ProbePart o_x = im.in(ln_in ? x : nullptr, (size_t)N * 1024 * 4), o_lw = im.in(ln_in ? ln_w : nullptr, 4096), o_lb = im.in(ln_in ? ln_b : nullptr, 4096);
+    const ProbePart o_aq = im.in(ln_in ? nullptr : aq_q, (size_t)N * K), o_ad = im.in(ln_in ? nullptr : aq_d, (size_t)N * bpr * 4), o_as = im.in(ln_in ? nullptr : aq_s, (size_t)N * bpr * 4);
+    const StageParts sp = stage_parts(im, lnq ? nullptr : bias, (size_t)MQ * 4, with_resid ? resid : nullptr, (size_t)N * M * 4, dev_state, seq_states, N, k_slots, v_slots, kv_b);
+    const ProbePart o_out = im.out(f32_out ? (size_t)cols * (op == CP_QKV ? 1024 : ldo) * 4 : 0), o_oq = im.out(q8_out ? (size_t)cols * MQ : 0),
+                    o_od = im.out(q8_out ? (size_t)cols * (MQ / 32) * 4 : 0), o_os = im.out(o_od.bytes);
+    if (!im.upload()) return -2;
     ChainLaunch g{-1, 256, N, 1, 0};
     if (lnq) {
-        HIP_TRY(-2, launch_lnq(d.at<const float>(o_x), N, d.at<const float>(o_lw), d.at<const float>(o_lb), q81, d.at<int8_t>(o_oq), d.at<float>(o_od), d.at<uint32_t>(o_os), 0));
+        HIP_TRY(-2, launch_lnq(im.at<const float>(o_x), N, im.at<const float>(o_lw), im.at<const float>(o_lb), q81, im.at<int8_t>(o_oq), im.at<float>(o_od), im.at<uint32_t>(o_os), 0));
     } else {
-        bgk::MatvecParams p{};
-        p.W.qs = d.p + o_qs; p.W.sc = d.p + o_sc; p.W.qh = qh_b ? d.at<const uint32_t>(o_qh) : nullptr;
-        p.W.type = wtype; p.W.M = M; p.W.K = K;
-        p.eps = 1e-5f; p.D = 1024; p.dk = 64; p.dk_log2 = 6; p.P = P;
-        p.st = d.at<const bgk::DevState>(o_ds);
-        p.gelu_tab = d.at<const uint16_t>(o_tab);
+        bgk::MatvecParams p = stage_params(im, wr.W(im), sp, 1024, P, N, op == CP_QKV, col_mode, o_out, ldo, M);
         p.inv_k = 1.0 / (double)K; p.k_pow2 = 1;
-        p.N = N;
-        if (ln_in) { p.x = d.at<const float>(o_x); p.ldx = 1024; p.ln_w = d.at<const float>(o_lw); p.ln_b = d.at<const float>(o_lb); }
-        else { p.aq_q = d.at<const int8_t>(o_aq); p.aq_d = d.at<const float>(o_ad); p.aq_s = d.at<const uint32_t>(o_as); }
-        if (bias) p.bias = d.at<const float>(o_bias);
-        if (op == CP_QKV) {
-            p.q_out = d.at<float>(o_out); p.kcache = d.at<float>(o_k); p.vcache = d.at<float>(o_v);
-            p.q_scale = 1.0f / sqrtf(64.0f);
-            if (batch) { p.seq = d.at<const bgk::SeqState>(o_st); p.col_mode = col_mode; p.kv_seq_stride = (int64_t)slot_f; }
-        } else if (f32_out) {
-            p.out = d.at<float>(o_out); p.ldo = ldo;
-            if (op != CP_LMHEAD) { p.resid = d.at<const float>(o_res); p.ldr = M; }
-        } else {
-            p.oq_q = d.at<int8_t>(o_oq); p.oq_d = d.at<float>(o_od); p.oq_s = d.at<uint32_t>(o_os);
-        }
-        bgk::DevMatrix img{};
-        if (mfma) {
-            img.qs = d.p + o_img + xq; img.sc = d.p + o_img + xs; img.qh = nullptr; img.type = wtype; img.M = M; img.K = K;
-            HIP_TRY(-2, (hipError_t)bg_mfma_retile(wtype, &p.W, sizeof(p.W), d.p + o_img + xq, d.p + o_img + xs, 0));
-        }
+        if (ln_in) { p.x = im.at<const float>(o_x); p.ldx = 1024; p.ln_w = im.at<const float>(o_lw); p.ln_b = im.at<const float>(o_lb); }
+        else { p.aq_q = im.at<const int8_t>(o_aq); p.aq_d = im.at<const float>(o_ad); p.aq_s = im.at<const uint32_t>(o_as); }
+        if (q8_out) { p.oq_q = im.at<int8_t>(o_oq); p.oq_d = im.at<float>(o_od); p.oq_s = im.at<uint32_t>(o_os); }
+        const bgk::DevMatrix img = wr.image(im);
+        if (mfma) HIP_TRY(-2, wr.retile(im));
         HIP_TRY(-2, launch_chain(cop, p, 0, mfma ? &img : nullptr, &g));
         if (g.kernel != route) BG_FAIL(-2, "internal: the launch took kernel %d, not route %d", g.kernel, route);
     }
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    if (launched) {
-        const int32_t rep[8] = {g.kernel, g.threads, g.grid_x, g.grid_y, g.lds, cols, ldo, 0};
-        std::memcpy(launched, rep, sizeof(rep));
-    }
-    if (f32_out) HIP_TRY(-2, hipMemcpy(out, d.p + o_out, out_b, hipMemcpyDeviceToHost));
-    if (q8_out) {
-        HIP_TRY(-2, hipMemcpy(out_q, d.p + o_oq, oq_b, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(out_d, d.p + o_od, od_b, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(out_s, d.p + o_os, od_b, hipMemcpyDeviceToHost));
-    }
-    if (op == CP_QKV) {
-        HIP_TRY(-2, hipMemcpy(k_slots, d.p + o_k, kv_b, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(v_slots, d.p + o_v, kv_b, hipMemcpyDeviceToHost));
-    }
+    report_launch(launched, {g.kernel, g.threads, g.grid_x, g.grid_y, g.lds, cols, ldo});
+    if (!im.read(o_out, out) || !im.read(o_oq, out_q) || !im.read(o_od, out_d) || !im.read(o_os, out_s)) return -2;
+    if (!im.read(sp.k, k_slots) || !im.read(sp.v, v_slots)) return -2;
     return 0;
 }
 
@@ -1515,96 +1470,28 @@ int biogpt_hip_wide_chain_device(int device, int32_t epi, int32_t wtype, int32_t
     if (!w_rows || !aq_q || !aq_d || !aq_s || !out) BG_FAIL(-1, "w_rows, aq_q, aq_d, aq_s or out is NULL");
     if (epi != bgk::EPI_LOGITS && !bias) BG_FAIL(-1, "bias is NULL");
     if (epi == bgk::EPI_RESID && !resid) BG_FAIL(-1, "resid is NULL");
-    const bool qkv = epi == bgk::EPI_QKV, batch = seq_states != nullptr;
-    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
-    if (qkv) {
-        if ((dev_state != nullptr) == batch) BG_FAIL(-1, "exactly one of dev_state and seq_states names the column states");
-        if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
-        if (!batch && col_mode) BG_FAIL(-1, "col_mode 1 needs seq_states");
-        if (!k_slots || !v_slots) BG_FAIL(-1, "k_slots or v_slots is NULL");
-        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
-        if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
-        if (!batch && n_slots != 1) BG_FAIL(-1, "the context's own columns have one slot");
-        std::set<std::pair<int, int>> seen;      // every column's cache row inside its slot, no two columns on one row
-        for (int i = 0; i < N; i++) {
-            const int pos = batch ? hs[i].n_past : dev_state[0] + i, slot = batch ? (col_mode ? hs[i].seq_id : i) : 0;
-            if (pos < 0 || pos >= P) BG_FAIL(-1, "column %d: position %d outside [0, P)", i, pos);
-            if (slot < 0 || slot >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, slot);
-            if (!seen.insert({slot, pos}).second) BG_FAIL(-1, "column %d: a second column writes slot %d, position %d", i, slot, pos);
-        }
-    } else if (dev_state || batch) BG_FAIL(-1, "only QKV reads column states");
+    const bool qkv = epi == bgk::EPI_QKV;
+    if (!check_probe_columns(__func__, qkv, N, dev_state, seq_states, col_mode, P, n_slots, k_slots, v_slots)) return -1;
     HIP_TRY(-2, hipSetDevice(device));
     const int q81 = (wtype == T_Q4_1 || wtype == T_Q5_1) ? 1 : 0;
-    const int cols = ((N + 15) & ~15) + 1, ldo = ((M + 127) & ~127) + 16, H = K / 64;
-    const size_t bpr = (size_t)K / QK, nblk = (size_t)M * bpr;
-    const size_t qs_b = nblk * (wtype == T_Q8_0 ? 32 : 16), sc_b = nblk * (q81 ? 4 : 2), qh_b = (wtype == T_Q5_0 || wtype == T_Q5_1) ? nblk * 4 : 0;
-    const size_t slot_f = (size_t)H * P * 64, kv_b = qkv ? slot_f * 4 * (size_t)n_slots : 0;
-    const size_t out_b = (size_t)cols * (qkv ? K : ldo) * 4;
-    size_t img_b = 0, xq = 0, xs = 0;
-    tile_image_place(wtype, M, K, img_b, xq, xs);
-    ByteLayout l;
-    const size_t o_qs = l.part(qs_b), o_sc = l.part(sc_b), o_qh = l.part(qh_b), o_img = l.part(img_b), o_aq = l.part((size_t)N * K), o_ad = l.part((size_t)N * bpr * 4),
-                 o_as = l.part((size_t)N * bpr * 4), o_bias = l.part(bias ? (size_t)M * 4 : 0), o_res = l.part(epi == bgk::EPI_RESID ? (size_t)N * M * 4 : 0),
-                 o_ds = l.part(sizeof(bgk::DevState)), o_st = l.part(batch ? sizeof(bgk::SeqState) * (size_t)N : 0), o_tab = l.part(65536 * 2), o_k = l.part(kv_b),
-                 o_v = l.part(kv_b), o_out = l.part(out_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));      // the output with its guard column and rows
-    HIP_TRY(-2, hipMemset(d.p + o_img, 0, img_b));                     // the rows the last tile has beyond the matrix
-    {
-        std::vector<uint8_t> qs(qs_b), sc(sc_b), qh(qh_b);
-        repack_rows(wtype, static_cast<const uint8_t *>(w_rows), M, K, qs.data(), sc.data(), qh.data());
-        HIP_TRY(-2, hipMemcpy(d.p + o_qs, qs.data(), qs_b, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_sc, sc.data(), sc_b, hipMemcpyHostToDevice));
-        if (qh_b) HIP_TRY(-2, hipMemcpy(d.p + o_qh, qh.data(), qh_b, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(-2, hipMemcpy(d.p + o_aq, aq_q, (size_t)N * K, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_ad, aq_d, (size_t)N * bpr * 4, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_as, aq_s, (size_t)N * bpr * 4, hipMemcpyHostToDevice));
-    if (bias) HIP_TRY(-2, hipMemcpy(d.p + o_bias, bias, (size_t)M * 4, hipMemcpyHostToDevice));
-    if (epi == bgk::EPI_RESID) HIP_TRY(-2, hipMemcpy(d.p + o_res, resid, (size_t)N * M * 4, hipMemcpyHostToDevice));
-    const int32_t no_state[4] = {0, 0, 0, 0};
-    HIP_TRY(-2, hipMemcpy(d.p + o_ds, (qkv && !batch) ? dev_state : no_state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
-    if (batch) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
-    if (qkv) {
-        HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
-    }
-    const std::vector<uint16_t> tg = gelu_table_f16();
-    HIP_TRY(-2, hipMemcpy(d.p + o_tab, tg.data(), 65536 * 2, hipMemcpyHostToDevice));
-    bgk::MatvecParams p{};
-    p.W.qs = d.p + o_qs; p.W.sc = d.p + o_sc; p.W.qh = qh_b ? d.at<const uint32_t>(o_qh) : nullptr;
-    p.W.type = wtype; p.W.M = M; p.W.K = K;
-    p.eps = 1e-5f; p.D = K; p.dk = 64; p.dk_log2 = 6; p.P = P;
-    p.st = d.at<const bgk::DevState>(o_ds);
-    p.gelu_tab = d.at<const uint16_t>(o_tab);
-    p.N = N;
-    p.aq_q = d.at<const int8_t>(o_aq); p.aq_d = d.at<const float>(o_ad); p.aq_s = d.at<const uint32_t>(o_as);
-    if (bias) p.bias = d.at<const float>(o_bias);
-    if (qkv) {
-        p.q_out = d.at<float>(o_out); p.kcache = d.at<float>(o_k); p.vcache = d.at<float>(o_v);
-        p.q_scale = 1.0f / sqrtf(64.0f);
-        if (batch) { p.seq = d.at<const bgk::SeqState>(o_st); p.col_mode = col_mode; p.kv_seq_stride = (int64_t)slot_f; }
-    } else {
-        p.out = d.at<float>(o_out); p.ldo = ldo;
-        if (epi == bgk::EPI_RESID) { p.resid = d.at<const float>(o_res); p.ldr = M; }
-    }
-    bgk::DevMatrix img{};
-    img.qs = d.p + o_img + xq; img.sc = d.p + o_img + xs; img.qh = nullptr; img.type = wtype; img.M = M; img.K = K;
-    HIP_TRY(-2, (hipError_t)bg_mfma_retile(wtype, &p.W, sizeof(p.W), d.p + o_img + xq, d.p + o_img + xs, 0));
+    const int cols = ((N + 15) & ~15) + 1, ldo = ((M + 127) & ~127) + 16;
+    const size_t bpr = (size_t)K / QK, kv_b = qkv ? (size_t)(K / 64) * P * 64 * 4 * (size_t)n_slots : 0;
+    ProbeImage im;      // [weights | image | the Q8 columns | the stage's parts | out], guard column and rows in the output
+    const BlockRows wr = upload_block_rows(im, wtype, w_rows, M, K, true);
+    const ProbePart o_aq = im.in(aq_q, (size_t)N * K), o_ad = im.in(aq_d, (size_t)N * bpr * 4), o_as = im.in(aq_s, (size_t)N * bpr * 4);
+    const StageParts sp = stage_parts(im, bias, (size_t)M * 4, epi == bgk::EPI_RESID ? resid : nullptr, (size_t)N * M * 4, dev_state, seq_states, N, k_slots, v_slots, kv_b);
+    const ProbePart o_out = im.out((size_t)cols * (qkv ? K : ldo) * 4);
+    if (!im.upload()) return -2;
+    bgk::MatvecParams p = stage_params(im, wr.W(im), sp, K, P, N, qkv, col_mode, o_out, ldo, M);
+    p.aq_q = im.at<const int8_t>(o_aq); p.aq_d = im.at<const float>(o_ad); p.aq_s = im.at<const uint32_t>(o_as);
+    const bgk::DevMatrix img = wr.image(im);
+    HIP_TRY(-2, wr.retile(im));
     HIP_TRY(-2, (hipError_t)bg_wide_launch(wtype, epi, &p, sizeof(p), &img, sizeof(img), 0));
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    if (launched) {
-        const int tiles = (M + 15) / 16;
-        const int32_t rep[8] = {256, (tiles + 3) / 4, (N + 15) / 16, 16 * (1024 + 16) + 16 * 33 * 4 * (q81 ? 2 : 1) /* WideLds::BYTES */, cols, ldo, tiles, 0};
-        std::memcpy(launched, rep, sizeof(rep));
-    }
-    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, out_b, hipMemcpyDeviceToHost));
-    if (qkv) {
-        HIP_TRY(-2, hipMemcpy(k_slots, d.p + o_k, kv_b, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(v_slots, d.p + o_v, kv_b, hipMemcpyDeviceToHost));
-    }
+    const int tiles = (M + 15) / 16;
+    report_launch(launched, {256, (tiles + 3) / 4, (N + 15) / 16, 16 * (1024 + 16) + 16 * 33 * 4 * (q81 ? 2 : 1) /* WideLds::BYTES */, cols, ldo, tiles});
+    if (!im.read(o_out, out) || !im.read(sp.k, k_slots) || !im.read(sp.v, v_slots)) return -2;
     return 0;
 }
 
@@ -1619,47 +1506,29 @@ int biogpt_hip_wide_chain_bench(int device, int32_t which, int32_t wtype, int32_
     if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
     if (M < 16 || M > (1 << 20) || M % 16 != 0) BG_FAIL(-1, "M must be a multiple of 16 in [16, %d]", 1 << 20);
     if (which == 1 && !((K == 1024 || K == 4096) && M == 1024)) BG_FAIL(-1, "the BioGPT-base kernel is timed at out_proj (1024 x 1024) or fc2 (1024 x 4096)");
-    if (reps < 1 || reps > 10000) BG_FAIL(-1, "reps must be in [1, 10000]");
+    if (reps < 1 || reps > PROBE_MAX_REPS) BG_FAIL(-1, "reps must be in [1, %d]", PROBE_MAX_REPS);
     if (!us_out) BG_FAIL(-1, "us_out is NULL");
     HIP_TRY(-2, hipSetDevice(device));
     const size_t bpr = (size_t)K / QK;
-    size_t img_b = 0, xq = 0, xs = 0;
-    tile_image_place(wtype, M, K, img_b, xq, xs);
-    ByteLayout l;
-    const size_t o_img = l.part(img_b), o_aq = l.part((size_t)N * K), o_ad = l.part((size_t)N * bpr * 4), o_as = l.part((size_t)N * bpr * 4), o_bias = l.part((size_t)M * 4),
-                 o_res = l.part((size_t)N * M * 4), o_out = l.part((size_t)N * M * 4);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemset(d.p, 0x11, l.bytes()));
+    ProbeImage im;      // every part of 0x11 bytes
+    const BlockRows wr = upload_block_rows(im, wtype, nullptr, M, K, true, 0, 0x11);
+    const ProbePart o_aq = im.fill((size_t)N * K, 0x11), o_ad = im.fill((size_t)N * bpr * 4, 0x11), o_as = im.fill((size_t)N * bpr * 4, 0x11), o_bias = im.fill((size_t)M * 4, 0x11),
+                    o_res = im.fill((size_t)N * M * 4, 0x11), o_out = im.fill((size_t)N * M * 4, 0x11);
+    if (!im.upload()) return -2;
     bgk::MatvecParams p{};
     p.W.type = wtype; p.W.M = M; p.W.K = K;
     p.eps = 1e-5f; p.D = 1024; p.dk = 64; p.dk_log2 = 6; p.P = 1;
     p.N = N;
-    p.aq_q = d.at<const int8_t>(o_aq); p.aq_d = d.at<const float>(o_ad); p.aq_s = d.at<const uint32_t>(o_as);
-    p.bias = d.at<const float>(o_bias); p.resid = d.at<const float>(o_res); p.ldr = M; p.out = d.at<float>(o_out); p.ldo = M;
-    bgk::DevMatrix img{};
-    img.qs = d.p + o_img + xq; img.sc = d.p + o_img + xs; img.qh = nullptr; img.type = wtype; img.M = M; img.K = K;
+    p.aq_q = im.at<const int8_t>(o_aq); p.aq_d = im.at<const float>(o_ad); p.aq_s = im.at<const uint32_t>(o_as);
+    p.bias = im.at<const float>(o_bias); p.resid = im.at<const float>(o_res); p.ldr = M; p.out = im.at<float>(o_out); p.ldo = M;
+    const bgk::DevMatrix img = wr.image(im);
     auto launch = [&]() -> hipError_t {
         if (which == 0) return (hipError_t)bg_wide_launch(wtype, bgk::EPI_RESID, &p, sizeof(p), &img, sizeof(img), 0);
         return launch_chain(K == 1024 ? CHAIN_OPROJ : CHAIN_FC2, p, 0, &img, nullptr);
     };
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(-2, hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); BG_FAIL(-2, "hipEventCreate failed"); }
-    hipError_t e = launch();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    for (int i = 0; i < reps && e == hipSuccess; i++) {
-        e = hipEventRecord(e0, 0);
-        if (e == hipSuccess) e = launch();
-        if (e == hipSuccess) e = hipEventRecord(e1, 0);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.0f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        us_out[i] = ms * 1e3f;
-    }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIP_TRY(-2, e);
-    return 0;
+    HIP_TRY(-2, launch());      // one untimed launch in front
+    HIP_TRY(-2, hipDeviceSynchronize());
+    return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
 }
 
 // One stand-alone launch of the float chain's linear stage (fchain_kernel, kernels_fchain.hip.h) over caller-supplied weights and f32 columns, through
@@ -1685,85 +1554,29 @@ int biogpt_hip_fchain_device(int device, int32_t epi, int32_t wtype, int32_t M, 
     if (ln_out && !ln_w) BG_FAIL(-1, "ln_out needs ln_w and ln_b");
     if (epi != bgk::EPI_LOGITS && !bias) BG_FAIL(-1, "bias is NULL");
     if (epi == bgk::EPI_RESID && !resid) BG_FAIL(-1, "resid is NULL");
-    const bool qkv = epi == bgk::EPI_QKV, batch = seq_states != nullptr;
-    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
-    if (qkv) {
-        if ((dev_state != nullptr) == batch) BG_FAIL(-1, "exactly one of dev_state and seq_states names the column states");
-        if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
-        if (!batch && col_mode) BG_FAIL(-1, "col_mode 1 needs seq_states");
-        if (!k_slots || !v_slots) BG_FAIL(-1, "k_slots or v_slots is NULL");
-        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
-        if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
-        if (!batch && n_slots != 1) BG_FAIL(-1, "the context's own columns have one slot");
-        std::set<std::pair<int, int>> seen;      // every column's cache row inside its slot, no two columns on one row
-        for (int i = 0; i < N; i++) {
-            const int pos = batch ? hs[i].n_past : dev_state[0] + i, slot = batch ? (col_mode ? hs[i].seq_id : i) : 0;
-            if (pos < 0 || pos >= P) BG_FAIL(-1, "column %d: position %d outside [0, P)", i, pos);
-            if (slot < 0 || slot >= n_slots) BG_FAIL(-1, "column %d: slot %d outside [0, n_slots)", i, slot);
-            if (!seen.insert({slot, pos}).second) BG_FAIL(-1, "column %d: a second column writes slot %d, position %d", i, slot, pos);
-        }
-    } else if (dev_state || batch) BG_FAIL(-1, "only QKV reads column states");
+    const bool qkv = epi == bgk::EPI_QKV;
+    if (!check_probe_columns(__func__, qkv, N, dev_state, seq_states, col_mode, P, n_slots, k_slots, v_slots)) return -1;
     HIP_TRY(-2, hipSetDevice(device));
-    const int cols = ((N + 15) & ~15) + 1, ldo = ((M + 127) & ~127) + 16, H = K / 64;
-    const size_t w_b = (size_t)M * K * (wtype == T_F32 ? 4 : 2), x_b = (size_t)N * K * 4;
-    const size_t slot_f = (size_t)H * P * 64, kv_b = qkv ? slot_f * 4 * (size_t)n_slots : 0;
-    const size_t out_b = (size_t)cols * (qkv ? K : ldo) * 4, ln_b_ = ln_w ? (size_t)cols * K * 4 : 0;
-    ByteLayout l;
-    const size_t o_w = l.part(w_b), o_x = l.part(x_b), o_lw = l.part(ln_w ? (size_t)K * 4 : 0), o_lb = l.part(ln_w ? (size_t)K * 4 : 0), o_bias = l.part(bias ? (size_t)M * 4 : 0),
-                 o_res = l.part(epi == bgk::EPI_RESID ? (size_t)N * M * 4 : 0), o_ds = l.part(sizeof(bgk::DevState)), o_st = l.part(batch ? sizeof(bgk::SeqState) * (size_t)N : 0),
-                 o_tab = l.part(65536 * 2), o_k = l.part(kv_b), o_v = l.part(kv_b), o_ln = l.part(ln_b_), o_out = l.part(out_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemset(d.p + o_ln, 0xff, l.bytes() - o_ln));        // the producer's rows and the output, with their guard columns and rows
-    HIP_TRY(-2, hipMemcpy(d.p + o_w, w_rows, w_b, hipMemcpyHostToDevice));
-    HIP_TRY(-2, hipMemcpy(d.p + o_x, x, x_b, hipMemcpyHostToDevice));
+    const int cols = ((N + 15) & ~15) + 1, ldo = ((M + 127) & ~127) + 16;
+    const size_t kv_b = qkv ? (size_t)(K / 64) * P * 64 * 4 * (size_t)n_slots : 0;
+    ProbeImage im;      // [weights | x | gain | bias of the LayerNorm | the stage's parts | the producer's rows | out], guard columns and rows in both outputs
+    const BlockRows wr = upload_block_rows(im, wtype, w_rows, M, K, false);
+    const ProbePart o_x = im.in(x, (size_t)N * K * 4), o_lw = im.in(ln_w, (size_t)K * 4), o_lb = im.in(ln_b, (size_t)K * 4);
+    const StageParts sp = stage_parts(im, bias, (size_t)M * 4, epi == bgk::EPI_RESID ? resid : nullptr, (size_t)N * M * 4, dev_state, seq_states, N, k_slots, v_slots, kv_b);
+    const ProbePart o_ln = im.out(ln_w ? (size_t)cols * K * 4 : 0), o_out = im.out((size_t)cols * (qkv ? K : ldo) * 4);
+    if (!im.upload()) return -2;
+    bgk::MatvecParams p = stage_params(im, wr.W(im), sp, K, P, N, qkv, col_mode, o_out, ldo, M);
+    p.x = im.at<const float>(o_x); p.ldx = K;
     if (ln_w) {
-        HIP_TRY(-2, hipMemcpy(d.p + o_lw, ln_w, (size_t)K * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_lb, ln_b, (size_t)K * 4, hipMemcpyHostToDevice));
+        HIP_TRY(-2, (hipError_t)bg_fchain_ln(wtype, p.x, K, K, N, im.at<const float>(o_lw), im.at<const float>(o_lb), 1e-5f, im.at<float>(o_ln), 0));
+        p.x = im.at<const float>(o_ln);
     }
-    if (bias) HIP_TRY(-2, hipMemcpy(d.p + o_bias, bias, (size_t)M * 4, hipMemcpyHostToDevice));
-    if (epi == bgk::EPI_RESID) HIP_TRY(-2, hipMemcpy(d.p + o_res, resid, (size_t)N * M * 4, hipMemcpyHostToDevice));
-    const int32_t no_state[4] = {0, 0, 0, 0};
-    HIP_TRY(-2, hipMemcpy(d.p + o_ds, (qkv && !batch) ? dev_state : no_state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
-    if (batch) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)N, hipMemcpyHostToDevice));
-    if (qkv) {
-        HIP_TRY(-2, hipMemcpy(d.p + o_k, k_slots, kv_b, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_v, v_slots, kv_b, hipMemcpyHostToDevice));
-    }
-    const std::vector<uint16_t> tg = gelu_table_f16();
-    HIP_TRY(-2, hipMemcpy(d.p + o_tab, tg.data(), 65536 * 2, hipMemcpyHostToDevice));
-    bgk::MatvecParams p{};
-    p.W.qs = d.p + o_w; p.W.type = wtype; p.W.M = M; p.W.K = K;
-    p.eps = 1e-5f; p.D = K; p.dk = 64; p.dk_log2 = 6; p.P = P;
-    p.st = d.at<const bgk::DevState>(o_ds);
-    p.gelu_tab = d.at<const uint16_t>(o_tab);
-    p.N = N;
-    p.x = d.at<const float>(o_x); p.ldx = K;
-    if (bias) p.bias = d.at<const float>(o_bias);
-    if (qkv) {
-        p.q_out = d.at<float>(o_out); p.kcache = d.at<float>(o_k); p.vcache = d.at<float>(o_v);
-        p.q_scale = 1.0f / sqrtf(64.0f);
-        if (batch) { p.seq = d.at<const bgk::SeqState>(o_st); p.col_mode = col_mode; p.kv_seq_stride = (int64_t)slot_f; }
-    } else {
-        p.out = d.at<float>(o_out); p.ldo = ldo;
-        if (epi == bgk::EPI_RESID) { p.resid = d.at<const float>(o_res); p.ldr = M; }
-    }
-    if (ln_w) {
-        HIP_TRY(-2, (hipError_t)bg_fchain_ln(wtype, p.x, K, K, N, d.at<const float>(o_lw), d.at<const float>(o_lb), 1e-5f, d.at<float>(o_ln), 0));
-        p.x = d.at<const float>(o_ln);
-    }
-    int32_t rep[8] = {0, 0, 0, 0, cols, ldo, 0, 0}, five[5] = {0, 0, 0, 0, 0};
+    int32_t five[5] = {0, 0, 0, 0, 0};
     HIP_TRY(-2, (hipError_t)bg_fchain_launch(wtype, epi, &p, sizeof(p), cfg, 0, five));
     HIP_TRY(-2, hipGetLastError());
     HIP_TRY(-2, hipDeviceSynchronize());
-    rep[0] = five[0]; rep[1] = five[1]; rep[2] = five[2]; rep[3] = five[3]; rep[6] = five[4];
-    if (launched) std::memcpy(launched, rep, sizeof(rep));
-    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, out_b, hipMemcpyDeviceToHost));
-    if (ln_out) HIP_TRY(-2, hipMemcpy(ln_out, d.p + o_ln, ln_b_, hipMemcpyDeviceToHost));
-    if (qkv) {
-        HIP_TRY(-2, hipMemcpy(k_slots, d.p + o_k, kv_b, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(v_slots, d.p + o_v, kv_b, hipMemcpyDeviceToHost));
-    }
+    report_launch(launched, {five[0], five[1], five[2], five[3], cols, ldo, five[4]});
+    if (!im.read(o_out, out) || (ln_out && !im.read(o_ln, ln_out)) || !im.read(sp.k, k_slots) || !im.read(sp.v, v_slots)) return -2;
     return 0;
 }
 
@@ -1778,48 +1591,32 @@ int biogpt_hip_fchain_bench(int device, int32_t which, int32_t wtype, int32_t M,
     if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
     if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
     if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
-    if (reps < 1 || reps > 10000) BG_FAIL(-1, "reps must be in [1, 10000]");
+    if (reps < 1 || reps > PROBE_MAX_REPS) BG_FAIL(-1, "reps must be in [1, %d]", PROBE_MAX_REPS);
     if (!us_out) BG_FAIL(-1, "us_out is NULL");
     HIP_TRY(-2, hipSetDevice(device));
-    ByteLayout l;
-    const size_t o_w = l.part((size_t)M * K * (wtype == T_F32 ? 4 : 2)), o_x = l.part((size_t)N * K * 4), o_bias = l.part((size_t)M * 4), o_res = l.part((size_t)N * M * 4),
-                 o_out = l.part((size_t)N * M * 4);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemset(d.p, 0x3c, l.bytes()));      // f32 0.0115, f16 1.06: ordinary products
+    ProbeImage im;      // every part of 0x3c bytes (f32 0.0115, f16 1.06: ordinary products)
+    const ProbePart o_w = im.fill((size_t)M * K * (wtype == T_F32 ? 4 : 2), 0x3c), o_x = im.fill((size_t)N * K * 4, 0x3c), o_bias = im.fill((size_t)M * 4, 0x3c),
+                    o_res = im.fill((size_t)N * M * 4, 0x3c), o_out = im.fill((size_t)N * M * 4, 0x3c);
+    if (!im.upload()) return -2;
     EngineOptions opt{};
     opt.load();
     MatSlot m{};
     m.type = wtype; m.M = M; m.K = K;
     const MvShape s = mv_shape(wtype, M, K);
     bgk::MatvecParams p{};
-    p.W.qs = d.p + o_w; p.W.type = wtype; p.W.M = M; p.W.K = K;
+    p.W.qs = im.at<uint8_t>(o_w); p.W.type = wtype; p.W.M = M; p.W.K = K;
     p.upr = s.upr; p.lpr_log2 = s.lpr_log2; p.nit = s.nit; p.rpw = s.rpw;
     p.eps = 1e-5f; p.D = 1024; p.dk = 64; p.dk_log2 = 6; p.P = 1;
     p.inv_k = 1.0 / (double)K; p.k_pow2 = (K & (K - 1)) == 0;
-    p.N = N; p.x = d.at<const float>(o_x); p.ldx = K;
-    p.bias = d.at<const float>(o_bias); p.resid = d.at<const float>(o_res); p.ldr = M; p.out = d.at<float>(o_out); p.ldo = M;
+    p.N = N; p.x = im.at<const float>(o_x); p.ldx = K;
+    p.bias = im.at<const float>(o_bias); p.resid = im.at<const float>(o_res); p.ldr = M; p.out = im.at<float>(o_out); p.ldo = M;
     auto launch = [&]() -> hipError_t {
         if (which == 0) return (hipError_t)bg_fchain_launch(wtype, bgk::EPI_RESID, &p, sizeof(p), cfg, 0, nullptr);
         return launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(opt, p, s, 0);
     };
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(-2, hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); BG_FAIL(-2, "hipEventCreate failed"); }
-    hipError_t e = launch();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    for (int i = 0; i < reps && e == hipSuccess; i++) {
-        e = hipEventRecord(e0, 0);
-        if (e == hipSuccess) e = launch();
-        if (e == hipSuccess) e = hipEventRecord(e1, 0);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.0f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        us_out[i] = ms * 1e3f;
-    }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIP_TRY(-2, e);
-    return 0;
+    HIP_TRY(-2, launch());      // one untimed launch in front
+    HIP_TRY(-2, hipDeviceSynchronize());
+    return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
 }
 
 // The four kernels of the embedding tail (kernels_embed.hip.h) alone, over caller-supplied rows, through launch_ln_rows / launch_pool_rows / launch_pool_finish /
@@ -1903,51 +1700,39 @@ int biogpt_hip_embed_device(int device, int32_t stage, int32_t W, int32_t n_rows
     }
     HIP_TRY(-2, hipSetDevice(device));
     const bool pool = stage == 1 && mode != bgk::POOL_NONE, mean = pool && mode == bgk::POOL_MEAN;
-    const size_t x_b = (size_t)n_rows * W * 4, out_b = (rows_out + 1) * ld_out * 4, acc_b = mean ? (size_t)(n_seqs + 1) * W * 8 : 0;
-    ByteLayout l;
-    const size_t o_x = l.part(x_b), o_lw = l.part(stage == 0 ? (size_t)W * 4 : 0), o_lb = l.part(stage == 0 ? (size_t)W * 4 : 0),
-                 o_st = l.part(hs ? sizeof(bgk::SeqState) * (size_t)n_rows : 0), o_lens = l.part(pool ? (size_t)n_seqs * 4 : 0),
-                 o_w = l.part(stage == 2 ? (size_t)n_out * W * 4 : 0), o_b = l.part(stage == 2 && b ? (size_t)n_out * 4 : 0), o_acc = l.part(acc_b), o_out = l.part(out_b);
-    DeviceBytes d;
-    if (!d.alloc(l.bytes())) return -2;
-    HIP_TRY(-2, hipMemset(d.p + o_acc, 0xff, l.bytes() - o_acc));        // the accumulator and the output, with their guard rows
-    HIP_TRY(-2, hipMemcpy(d.p + o_x, x, x_b, hipMemcpyHostToDevice));
-    if (hs && stage != 2) HIP_TRY(-2, hipMemcpy(d.p + o_st, seq_states, sizeof(bgk::SeqState) * (size_t)n_rows, hipMemcpyHostToDevice));
+    ProbeImage im;      // [x | gain | bias | column states | lens | head matrix | head bias | accumulator | out]: the last two with their guard rows
+    const ProbePart o_x = im.in(x, (size_t)n_rows * W * 4), o_lw = im.in(stage == 0 ? ln_w : nullptr, (size_t)W * 4), o_lb = im.in(stage == 0 ? ln_b : nullptr, (size_t)W * 4),
+                    o_st = im.in(stage != 2 ? seq_states : nullptr, sizeof(bgk::SeqState) * (size_t)n_rows), o_lens = im.in(pool ? lens : nullptr, (size_t)n_seqs * 4),
+                    o_w = im.in(stage == 2 ? w : nullptr, (size_t)n_out * W * 4), o_b = im.in(stage == 2 ? b : nullptr, (size_t)n_out * 4),
+                    o_acc = im.out(mean ? (size_t)(n_seqs + 1) * W * 8 : 0), o_out = im.out((rows_out + 1) * ld_out * 4);
+    if (!im.upload()) return -2;
     EmbedLaunch k{}, fin{};
     int32_t n_launches = 0;
-    const bgk::SeqState *d_st = d.at<const bgk::SeqState>(o_st);
-    float *d_out = d.at<float>(o_out);
+    const bgk::SeqState *d_st = im.at<const bgk::SeqState>(o_st);
+    float *d_out = im.at<float>(o_out);
     if (stage == 0) {
-        HIP_TRY(-2, hipMemcpy(d.p + o_lw, ln_w, (size_t)W * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_lb, ln_b, (size_t)W * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, launch_ln_rows(0, d.at<const float>(o_x), W, W, n_rows, d.at<const float>(o_lw), d.at<const float>(o_lb), d_out, hs ? d_st : nullptr, hs ? slot_div : 0, P, &k));
+        HIP_TRY(-2, launch_ln_rows(0, im.at<const float>(o_x), W, W, n_rows, im.at<const float>(o_lw), im.at<const float>(o_lb), d_out, hs ? d_st : nullptr, hs ? slot_div : 0, P, &k));
     } else if (stage == 1) {
-        double *d_acc = mean ? d.at<double>(o_acc) : nullptr;
+        double *d_acc = mean ? im.at<double>(o_acc) : nullptr;
         if (pool) {
-            HIP_TRY(-2, hipMemcpy(d.p + o_lens, lens, (size_t)n_seqs * 4, hipMemcpyHostToDevice));
-            if (d_acc) HIP_TRY(-2, hipMemsetAsync(d_acc, 0, (size_t)n_seqs * W * 8, 0));
+            if (d_acc) HIP_TRY(-2, im.clear(o_acc, (size_t)n_seqs * W * 8));
             size_t at = 0;
             for (int p = 0; p < n_passes; p++) {
-                HIP_TRY(-2, launch_pool_rows(0, d.at<const float>(o_x) + at * W, pass_cols[p], W, d_st + at, d.at<const int32_t>(o_lens), mode, d_out, d_acc, &k));
+                HIP_TRY(-2, launch_pool_rows(0, im.at<const float>(o_x) + at * W, pass_cols[p], W, d_st + at, im.at<const int32_t>(o_lens), mode, d_out, d_acc, &k));
                 at += (size_t)pass_cols[p];
                 n_launches++;
             }
         } else {
-            HIP_TRY(-2, hipMemcpyAsync(d_out, d.p + o_x, x_b, hipMemcpyDeviceToDevice, 0));      // (a direct call's rows are written where they are normalised)
+            HIP_TRY(-2, im.restore(o_out, o_x));      // (a direct call's rows are written where they are normalised)
         }
         if (pool_needs_finish(d_acc, normalize))
-            HIP_TRY(-2, launch_pool_finish(0, d_out, (int)rows_out, W, d_acc, d.at<const int32_t>(o_lens), normalize, &fin));
+            HIP_TRY(-2, launch_pool_finish(0, d_out, (int)rows_out, W, d_acc, im.at<const int32_t>(o_lens), normalize, &fin));
     } else {
-        HIP_TRY(-2, hipMemcpy(d.p + o_w, w, (size_t)n_out * W * 4, hipMemcpyHostToDevice));
-        if (b) HIP_TRY(-2, hipMemcpy(d.p + o_b, b, (size_t)n_out * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, launch_head_rows(0, d.at<const float>(o_x), n_rows, W, d.at<const float>(o_w), b ? d.at<const float>(o_b) : nullptr, n_out, d_out, &k));
+        HIP_TRY(-2, launch_head_rows(0, im.at<const float>(o_x), n_rows, W, im.at<const float>(o_w), b ? im.at<const float>(o_b) : nullptr, n_out, d_out, &k));
     }
     HIP_TRY(-2, hipDeviceSynchronize());
-    const int32_t rep[8] = {k.kernel, k.threads, k.grid_x, k.grid_y, k.lds, fin.grid_x, n_launches, 0};
-    if (launched) std::memcpy(launched, rep, sizeof(rep));
-    HIP_TRY(-2, hipMemcpy(out, d.p + o_out, out_b, hipMemcpyDeviceToHost));
-    if (mean) HIP_TRY(-2, hipMemcpy(acc, d.p + o_acc, acc_b, hipMemcpyDeviceToHost));
-    return 0;
+    report_launch(launched, {k.kernel, k.threads, k.grid_x, k.grid_y, k.lds, fin.grid_x, n_launches});
+    return im.read(o_out, out) && (!mean || im.read(o_acc, acc)) ? 0 : -2;
 }
 
 // The token tail alone (the lm_head's arg-max partials, argmax_kernel, topk_kernel and the host selections of biogpt_hip_eval_topk), over caller-supplied inputs,
@@ -1967,7 +1752,6 @@ int biogpt_hip_tail_device(int device, int32_t stage, int32_t wtype, int32_t n, 
                            int32_t n_vocab, float *out_val, int32_t *out_idx, float *part_val, int32_t *part_idx, int32_t *launched) {
     clear_error();
     if (stage < 0 || stage > 5) BG_FAIL(-1, "stage %d is no stage (0 PARTIALS, 1 FINISH, 2 TOPK, 3 HOST_TOPK, 4 HOST_BLOCKS, 5 HOST_FULL)", stage);
-    int32_t rep[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (stage == 0) {
         const bool block = wtype == T_Q4_0 || wtype == T_Q4_1 || wtype == T_Q5_0 || wtype == T_Q5_1 || wtype == T_Q8_0;
         if (!block && wtype != T_F32) BG_FAIL(-1, "type %d is neither F32 nor a block format", wtype);
@@ -1976,49 +1760,27 @@ int biogpt_hip_tail_device(int device, int32_t stage, int32_t wtype, int32_t n, 
         if (!out_val || !part_val || !part_idx) BG_FAIL(-1, "out_val, part_val or part_idx is NULL");
         HIP_TRY(-2, hipSetDevice(device));
         const int M = n, K = 1024;
-        const int q81 = (wtype == T_Q4_1 || wtype == T_Q5_1) ? 1 : 0;
-        const size_t nblk = (size_t)M * (K / QK);
-        const size_t qs_b = block ? nblk * (wtype == T_Q8_0 ? 32 : 16) : (size_t)M * K * 4, sc_b = block ? nblk * (q81 ? 4 : 2) : 0,
-                     qh_b = (wtype == T_Q5_0 || wtype == T_Q5_1) ? nblk * 4 : 0, cap_b = ((size_t)M + 16) * 4;
+        const size_t cap_b = ((size_t)M + 16) * 4;
         const MvShape s = mv_shape(wtype, M, K);
         if (s.grid > M + 16) BG_FAIL(-2, "internal: %d partials for %d rows", s.grid, M);
-        ByteLayout l;
-        // (lm_stream_kernel stages a workgroup's scales 16 bytes at a time: the scale array rounded up, as in the arena)
-        const size_t o_qs = l.part(qs_b), o_sc = l.part(sc_b + 16), o_qh = l.part(qh_b), o_x = l.part(K * 4), o_lw = l.part(K * 4), o_lb = l.part(K * 4),
-                     o_out = l.part(cap_b), o_pv = l.part(cap_b), o_pi = l.part(cap_b);
-        DeviceBytes d;
-        if (!d.alloc(l.bytes())) return -2;
-        HIP_TRY(-2, hipMemset(d.p + o_out, 0xff, l.bytes() - o_out));
-        HIP_TRY(-2, hipMemset(d.p + o_sc, 0, sc_b + 16));
-        {
-            std::vector<uint8_t> qs(qs_b), sc(sc_b), qh(qh_b);
-            repack_rows(wtype, static_cast<const uint8_t *>(w_rows), M, K, qs.data(), sc.data(), qh.data());
-            HIP_TRY(-2, hipMemcpy(d.p + o_qs, qs.data(), qs_b, hipMemcpyHostToDevice));
-            if (sc_b) HIP_TRY(-2, hipMemcpy(d.p + o_sc, sc.data(), sc_b, hipMemcpyHostToDevice));
-            if (qh_b) HIP_TRY(-2, hipMemcpy(d.p + o_qh, qh.data(), qh_b, hipMemcpyHostToDevice));
-        }
-        HIP_TRY(-2, hipMemcpy(d.p + o_x, x, K * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_lw, ln_w, K * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_lb, ln_b, K * 4, hipMemcpyHostToDevice));
+        ProbeImage im;
+        const BlockRows wr = upload_block_rows(im, wtype, w_rows, M, K, false, 16);
+        const ProbePart o_x = im.in(x, K * 4), o_lw = im.in(ln_w, K * 4), o_lb = im.in(ln_b, K * 4), o_out = im.out(cap_b), o_pv = im.out(cap_b), o_pi = im.out(cap_b);
+        if (!im.upload()) return -2;
         EngineOptions opt{};
         opt.load();
         bgk::MatvecParams p{};
-        p.W.qs = d.p + o_qs; p.W.sc = d.p + o_sc; p.W.qh = qh_b ? d.at<const uint32_t>(o_qh) : nullptr;
-        p.W.type = wtype; p.W.M = M; p.W.K = K;
+        p.W = wr.W(im);
         p.upr = s.upr; p.lpr_log2 = s.lpr_log2; p.nit = s.nit; p.rpw = s.rpw;
         p.eps = 1e-5f; p.D = K; p.dk = 64; p.dk_log2 = 6; p.P = 1;
         p.inv_k = 1.0 / (double)K; p.k_pow2 = true;
         int grid = 0;
         MvLaunch took{-1, 0, 0};
-        HIP_TRY(-2, launch_lm_head_row(opt, p, s, d.at<const float>(o_x), d.at<const float>(o_lw), d.at<const float>(o_lb), d.at<float>(o_out), d.at<float>(o_pv),
-                                       d.at<int32_t>(o_pi), 0, &grid, &took));
+        HIP_TRY(-2, launch_lm_head_row(opt, p, s, im.at<const float>(o_x), im.at<const float>(o_lw), im.at<const float>(o_lb), im.at<float>(o_out), im.at<float>(o_pv),
+                                       im.at<int32_t>(o_pi), 0, &grid, &took));
         HIP_TRY(-2, hipDeviceSynchronize());
-        rep[0] = took.kernel; rep[1] = grid; rep[2] = took.rows_per_part;      // as the launch itself reports them
-        if (launched) std::memcpy(launched, rep, sizeof(rep));
-        HIP_TRY(-2, hipMemcpy(out_val, d.p + o_out, cap_b, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(part_val, d.p + o_pv, cap_b, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(part_idx, d.p + o_pi, cap_b, hipMemcpyDeviceToHost));
-        return 0;
+        report_launch(launched, {took.kernel, grid, took.rows_per_part});      // as the launch itself reports them
+        return im.read(o_out, out_val) && im.read(o_pv, part_val) && im.read(o_pi, part_idx) ? 0 : -2;
     }
     if (stage == 1) {
         if (n < 1 || n > 4096) BG_FAIL(-1, "nparts must be in [1, 4096] (the partial buffers of a context)");
@@ -2028,20 +1790,15 @@ int biogpt_hip_tail_device(int device, int32_t stage, int32_t wtype, int32_t n, 
         if (state[1] < 0) BG_FAIL(-1, "n_gen %d is negative (gen_ids[n_gen] would be written in front of the block)", state[1]);
         HIP_TRY(-2, hipSetDevice(device));
         const size_t st_words = 4 + 2 * (size_t)n_positions + 16;
-        ByteLayout l;
-        const size_t o_pv = l.part((size_t)n * 4), o_pi = l.part((size_t)n * 4), o_st = l.part(st_words * 4);
-        DeviceBytes d;
-        if (!d.alloc(l.bytes())) return -2;
-        HIP_TRY(-2, hipMemset(d.p + o_st, 0xff, st_words * 4));
-        HIP_TRY(-2, hipMemcpy(d.p + o_pv, part_in_val, (size_t)n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_pi, part_in_idx, (size_t)n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_st, state, sizeof(bgk::DevState), hipMemcpyHostToDevice));
-        HIP_TRY(-2, launch_argmax(d.at<const float>(o_pv), d.at<const int32_t>(o_pi), n, d.at<bgk::DevState>(o_st), n_eval, n_positions, n_vocab, 0));
+        std::vector<int32_t> st(st_words, -1);      // (0xff bytes behind the four words)
+        std::memcpy(st.data(), state, sizeof(bgk::DevState));
+        ProbeImage im;
+        const ProbePart o_pv = im.in(part_in_val, (size_t)n * 4), o_pi = im.in(part_in_idx, (size_t)n * 4), o_st = im.out(st_words * 4, st.data());
+        if (!im.upload()) return -2;
+        HIP_TRY(-2, launch_argmax(im.at<const float>(o_pv), im.at<const int32_t>(o_pi), n, im.at<bgk::DevState>(o_st), n_eval, n_positions, n_vocab, 0));
         HIP_TRY(-2, hipDeviceSynchronize());
-        rep[0] = 256; rep[1] = 1;
-        if (launched) std::memcpy(launched, rep, sizeof(rep));
-        HIP_TRY(-2, hipMemcpy(out_idx, d.p + o_st, st_words * 4, hipMemcpyDeviceToHost));
-        return 0;
+        report_launch(launched, {256, 1});
+        return im.read(o_st, out_idx) ? 0 : -2;
     }
     // the selections
     if (n < 1 || n > (1 << 20)) BG_FAIL(-1, "V must be in [1, %d]", 1 << 20);
@@ -2054,26 +1811,18 @@ int biogpt_hip_tail_device(int device, int32_t stage, int32_t wtype, int32_t n, 
     }
     if (stage == 2) {
         HIP_TRY(-2, hipSetDevice(device));
-        ByteLayout l;
-        const size_t o_row = l.part((size_t)n * 4), o_pv = l.part((size_t)nparts * 4), o_ov = l.part(80 * 4), o_oi = l.part(80 * 4), o_on = l.part(16 * 4);
-        DeviceBytes d;
-        if (!d.alloc(l.bytes())) return -2;
-        HIP_TRY(-2, hipMemset(d.p + o_ov, 0xff, l.bytes() - o_ov));
-        HIP_TRY(-2, hipMemcpy(d.p + o_row, row, (size_t)n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, hipMemcpy(d.p + o_pv, part_in_val, (size_t)nparts * 4, hipMemcpyHostToDevice));
-        HIP_TRY(-2, launch_topk(d.at<const float>(o_row), n, k, d.at<const float>(o_pv), nparts, d.at<float>(o_ov), d.at<int32_t>(o_oi), d.at<int32_t>(o_on), 0));
+        ProbeImage im;
+        const ProbePart o_row = im.in(row, (size_t)n * 4), o_pv = im.in(part_in_val, (size_t)nparts * 4), o_ov = im.out(80 * 4), o_oi = im.out(80 * 4), o_on = im.out(16 * 4);
+        if (!im.upload()) return -2;
+        HIP_TRY(-2, launch_topk(im.at<const float>(o_row), n, k, im.at<const float>(o_pv), nparts, im.at<float>(o_ov), im.at<int32_t>(o_oi), im.at<int32_t>(o_on), 0));
         HIP_TRY(-2, hipDeviceSynchronize());
-        rep[0] = 1024; rep[1] = 1;
-        if (launched) std::memcpy(launched, rep, sizeof(rep));
-        HIP_TRY(-2, hipMemcpy(out_val, d.p + o_ov, 80 * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(out_idx, d.p + o_oi, 80 * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(-2, hipMemcpy(part_idx, d.p + o_on, 16 * 4, hipMemcpyDeviceToHost));
-        return 0;
+        report_launch(launched, {1024, 1});
+        return im.read(o_ov, out_val) && im.read(o_oi, out_idx) && im.read(o_on, part_idx) ? 0 : -2;
     }
     std::memset(out_val, 0xff, 80 * 4); std::memset(out_idx, 0xff, 80 * 4); std::memset(part_idx, 0xff, 16 * 4);
     if (stage == 3) part_idx[0] = host_topk(row, n, k, out_val, out_idx);
     else if (stage == 4) part_idx[0] = host_topk_blocks(row, n, k, part_in_val, nparts, out_val, out_idx);
     else { topk_full_row(row, n, k, out_val, out_idx); part_idx[0] = k; }
-    if (launched) std::memcpy(launched, rep, sizeof(rep));
+    report_launch(launched, {});
     return 0;
 }

@@ -142,3 +142,56 @@ def test_expected_geometry_of_the_cases():
     assert C.expected_launch("OPROJ", "VALU_1", R.Q5_0, 1024, 1024, 1)[:4] == (0, 256, 128, 1)
     assert C.expected_launch("FC2", "VALU_8", R.Q5_0, 1024, 4096, 8)[:4] == (1, 256, 256, 1)
     assert C.expected_launch("FC1_LN", "VALU_1", R.Q5_0, 4096, 1024, 1)[:4] == (0, 256, 128, 1)
+
+
+def _qkv_probes(pkg, N, **states):
+    """One QKV launch of each linear-stage probe on the same column states (zero weights: nothing reads them before a refusal)."""
+    n_slots = states.pop("n_slots", 1)
+    P = states["P"]
+    z = lambda *s: np.zeros(s, np.float32)
+    big = dict(k_slots=z(n_slots, 16, P, 64), v_slots=z(n_slots, 16, P, 64), **states)
+    small = dict(k_slots=z(n_slots, 1, P, 64), v_slots=z(n_slots, 1, P, 64), **states)
+    aq = lambda K: dict(aq_q=np.zeros((N, K), np.int8), aq_d=z(N, K // 32), aq_s=np.zeros((N, K // 32), np.uint32))
+    return (
+        lambda: pkg.chain_device(op="QKV", route="VALU_8", wtype=R.Q4_0, M=3072, N=N, w_rows=np.zeros(3072 * 32 * R.BLOCK_BYTES[R.Q4_0], np.uint8), bias=z(3072), **aq(1024), **big),
+        lambda: pkg.wide_chain_device("QKV", R.Q4_0, 192, 64, N, np.zeros(192 * 2 * R.BLOCK_BYTES[R.Q4_0], np.uint8), bias=z(192), **aq(64), **small),
+        lambda: pkg.fchain_device("QKV", 0, 192, 64, N, z(192, 64), z(N, 64), bias=z(192), **small),
+    )
+
+
+def _packed(N=8, P=4):
+    st = np.zeros((N, 8), np.int32)
+    st[:, 0] = np.arange(N) % P        # n_past
+    st[:, 3] = np.arange(N) // P       # seq_id
+    return st
+
+
+def _with(st, row, word, val):
+    st = st.copy()
+    st[row, word] = val
+    return st
+
+
+COLUMN_REFUSALS = {
+    "neither": ("exactly one of dev_state and seq_states names the column states", dict(dev_state=None, seq_states=None, P=8)),
+    "both": ("exactly one of dev_state and seq_states names the column states", dict(dev_state=np.zeros(4, np.int32), seq_states=_packed(), col_mode=1, P=4, n_slots=2)),
+    "col_mode 2": ("col_mode must be 0 or 1", dict(seq_states=_packed(), col_mode=2, P=4, n_slots=2)),
+    "slot": ("column 7: slot 2 outside [0, n_slots)", dict(seq_states=_with(_packed(), 7, 3, 2), col_mode=1, P=4, n_slots=2)),
+    "position": ("column 6: position 4 outside [0, P)", dict(seq_states=_with(_packed(), 6, 0, 4), col_mode=1, P=4, n_slots=2)),
+    "one row": ("column 5: a second column writes slot 1, position 0", dict(seq_states=_with(_packed(), 5, 0, 0), col_mode=1, P=4, n_slots=2)),
+}
+
+
+@pytest.mark.parametrize("case", sorted(COLUMN_REFUSALS))
+def test_the_three_linear_stage_probes_refuse_column_states_alike(pkg, case):
+    """The chain, wide-chain and float-chain probes check a QKV launch's column states by one rule: the same refusal, word for word, from all three, each
+    under its own entry's name."""
+    text, states = COLUMN_REFUSALS[case]
+    said = []
+    for call in _qkv_probes(pkg, 8, **states):
+        with pytest.raises(pkg.BiogptError) as e:
+            call()
+        said.append(str(e.value).split(": ", 1))
+    assert [s[0] for s in said] == ["biogpt_hip_chain_device", "biogpt_hip_wide_chain_device", "biogpt_hip_fchain_device"], said
+    assert said[0][1] == said[1][1] == said[2][1], said
+    assert text in said[0][1], (text, said[0][1])
