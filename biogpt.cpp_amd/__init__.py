@@ -831,6 +831,8 @@ SYMBOLS = [
     ("biogpt_hip_wide_launches", C.c_int64, [_P]),
     ("biogpt_hip_float_chain", C.c_int, [_P, C.c_int]),
     ("biogpt_hip_float_launches", C.c_int64, [_P]),
+    ("biogpt_hip_assoc", C.c_int, [_P, C.c_int]),
+    ("biogpt_hip_get_assoc", C.c_int, [_P]),
     ("biogpt_hip_fpipe_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_stamps", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     ("biogpt_hip_generate_launches", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
@@ -930,6 +932,8 @@ SYMBOLS = [
     ("biogpt_hip_wide_chain_bench", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P]),
     ("biogpt_hip_fchain_device", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 5),
     ("biogpt_hip_fchain_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P]),
+    ("biogpt_hip_assoc_device", C.c_int, [C.c_int] + [C.c_int32] * 9 + [_P] * 17),
+    ("biogpt_hip_assoc_bench", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P]),
     ("biogpt_hip_embed_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 4 + [C.c_int32] * 5 + [_P] + [C.c_int32] * 2 + [_P] * 3 + [C.c_int32] + [_P] * 3),
     ("biogpt_hip_tail_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 7 + [C.c_int32] * 2 + [_P] + [C.c_int32] * 3 + [_P] * 5),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
@@ -1170,6 +1174,66 @@ def fchain_device(epi, wtype, M, K, N, w_rows, x, ln_w=None, ln_b=None, bias=Non
         raise BiogptError(_err())
     res["launched"] = launched
     return res
+
+
+ASSOC_STAGES = {"Q8": 0, "MATVEC": 1, "ATTN": 2}
+ASSOC_MODES = {"scalar": 0, "simd": 1}
+ASSOC_MAX_PARTS = 1025      # arg-max partials a MATVEC / LOGITS probe returns: the launch's grid limit, plus a guard
+
+
+def assoc_device(stage, wtype=2, M=0, K=0, N=None, w_rows=None, x=None, ln_w=None, ln_b=None, epi=None, bias=None, resid=None, dev_state=None, P=0, k_slots=None,
+                 v_slots=None, q=None, H=0, partials=False, device=0):
+    """One stand-alone launch of a kernel of the SIMD association (biogpt_hip_assoc_device; include/biogpt_hip.h has the inputs of each stage).  stage "Q8": x
+    float32 [N, K] (ln_w / ln_b: the LayerNorm in front) -> "q" int8 [N + 1, K], "d" float32 and "s" uint32 [N + 1, K / 32].  "MATVEC": w_rows (uint8 bytes of M
+    rows in the file's format), x [N, K], epi by name (WIDE_EPIS; the LayerNorm prologue goes with ln_w / ln_b), bias, resid, for QKV dev_state, P and k_slots /
+    v_slots [K / 64, P, 64] -> "out" float32 [N + 1, M + 16] ([N + 1, K] for QKV), "k" / "v", with partials=True "pmax_val" / "pmax_idx" [ASSOC_MAX_PARTS].
+    "ATTN": q [N, H * 64], k_slots / v_slots [H, P, 64], dev_state -> "out" [N + 1, H * 64].  Outputs come back WHOLE, guard rows included and preset to 0xff
+    bytes; "launched" as the header lists it.  Raises BiogptError on a refusal."""
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    st = ASSOC_STAGES[stage] if isinstance(stage, str) else int(stage)
+    if N is None:
+        N = int(np.shape(q if st == 2 else x)[0])
+    M, K, N, H, P = int(M), int(K), int(N), int(H), int(P)
+    res = {}
+    if st == 0:
+        res["q"], res["d"], res["s"] = np.zeros((N + 1, max(K, 0)), np.int8), np.zeros((N + 1, max(K, 0) // 32), np.float32), np.zeros((N + 1, max(K, 0) // 32), np.uint32)
+    elif st == 1:
+        res["out"] = np.zeros((N + 1, K if epi == "QKV" else M + 16), np.float32)
+        if epi == "QKV":
+            res["k"], res["v"] = np.array(k_slots, dtype=np.float32, order="C"), np.array(v_slots, dtype=np.float32, order="C")
+        if partials:
+            res["pmax_val"], res["pmax_idx"] = np.zeros(ASSOC_MAX_PARTS, np.float32), np.zeros(ASSOC_MAX_PARTS, np.int32)
+    else:
+        res["out"] = np.zeros((N + 1, max(H, 0) * 64), np.float32)
+    launched = np.zeros(8, np.int32)
+    o = lambda name: res[name].ctypes.data if name in res else None
+    kv = (o("k"), o("v")) if st == 1 else (ptr(k_slots, np.float32), ptr(v_slots, np.float32))
+    rc = lib().biogpt_hip_assoc_device(int(device), st, int(wtype), 0 if ln_w is None else 1, WIDE_EPIS[epi] if isinstance(epi, str) else int(epi or 0), M, K, N, H, P,
+                                       ptr(w_rows, np.uint8), ptr(x, np.float32), ptr(ln_w, np.float32), ptr(ln_b, np.float32), ptr(bias, np.float32),
+                                       ptr(resid, np.float32), ptr(dev_state, np.int32), ptr(q, np.float32), kv[0], kv[1], o("out"), o("q"), o("d"), o("s"),
+                                       o("pmax_val"), o("pmax_idx"), launched.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    res["launched"] = launched
+    return res
+
+
+def assoc_bench(which, wtype, M, K, N, reps=9, device=0):
+    """A kernel of the SIMD association alone, timed (biogpt_hip_assoc_bench): microseconds of `reps` launches, float32 [reps].  which "simd": the SIMD mat-vec
+    with the residual epilogue at (M, K, N); "scalar": the scalar association's mat-vec of the five-launch route at the same shape; "attn": the SIMD attention
+    with M heads, N causal query columns, K keys for the last."""
+    us = np.zeros(int(reps), np.float32)
+    if lib().biogpt_hip_assoc_bench(int(device), {"simd": 0, "scalar": 1, "attn": 2}[which], int(wtype), int(M), int(K), int(N), int(reps), us.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return us
 
 
 EMBED_STAGES = {"LN": 0, "POOL": 1, "HEAD": 2}
@@ -1457,18 +1521,21 @@ class BiogptModel:
 
     # -- biogpt_model_load (biogpt.h:128-132) --
     @classmethod
-    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False):
-        """float_chain=True: switch the float chain on behind the load (float_chain(); an F32 / F16 file with head size 64 only -- anything else raises)."""
+    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None):
+        """float_chain=True: switch the float chain on behind the load (float_chain(); an F32 / F16 file with head size 64 only -- anything else raises).
+        assoc="scalar" | "simd": set the association behind the load (set_assoc(); None: the default, scalar unless BIOGPT_HIP_ASSOC=1)."""
         if arena is None:
             m = cls(lib().biogpt_hip_load(os.fsencode(fname), device, verbosity))
         else:
             m = cls(lib().biogpt_hip_load_into(os.fsencode(fname), device, verbosity, arena, arena_bytes))
-        if float_chain:
-            try:
+        try:
+            if float_chain:
                 m.float_chain(True)
-            except BiogptError:
-                m.close()
-                raise
+            if assoc is not None:
+                m.set_assoc(assoc)
+        except BiogptError:
+            m.close()
+            raise
         return m
 
     @classmethod
@@ -2196,6 +2263,23 @@ class BiogptModel:
         default of a load), the file has the single-sequence calls only.  Raises BiogptError with the reason where the file cannot have it."""
         if lib().biogpt_hip_float_chain(self._h, 1 if on else 0) != 0:
             raise BiogptError(_err())
+
+    def set_assoc(self, mode):
+        """The association's switch (biogpt_hip_assoc): "scalar" (ggml's scalar summation order, the default) or "simd" (the order of an AVX2 build of the
+        reference: the oracle's assoc = 3).  In "simd" the context serves the single-sequence calls on five launches per layer and refuses the calls over
+        column states.  Raises BiogptError with the reason where the file cannot have the mode (an F32 / F16 file, a head size other than 64)."""
+        if mode not in ASSOC_MODES:
+            raise ValueError("assoc must be 'scalar' or 'simd' (got %r)" % (mode,))
+        if lib().biogpt_hip_assoc(self._h, ASSOC_MODES[mode]) != 0:
+            raise BiogptError(_err())
+
+    @property
+    def assoc(self):
+        """The context's association: "scalar" or "simd" (biogpt_hip_get_assoc)."""
+        k = int(lib().biogpt_hip_get_assoc(self._h))
+        if k < 0:
+            raise BiogptError(_err())
+        return "simd" if k == 1 else "scalar"
 
     def float_launches(self):
         """Linear-stage launches of the float chain (biogpt_hip_float_launches); 0 while the switch is off."""

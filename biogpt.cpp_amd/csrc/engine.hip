@@ -32,6 +32,7 @@
 #include "host_common.h"
 #include "kernels.hip.h"
 #include "kernels_fast.hip.h"
+#include "kernels_assoc.hip.h"
 #include "kernels_runs.hip.h"
 #include "kernels_decode.hip.h"
 #include "kernels_q8probe.hip.h"
@@ -206,7 +207,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -238,6 +239,7 @@ struct EngineOptions {
         prefix_attn = get("BIOGPT_HIP_PREFIX_ATTN", -1);          // decode steps behind a shared prefix: -1 attn_prefix_kernel where it was measured faster (PREFIX_ATTN_MIN_*), 0 never, 1 always (A/B arms)
         run_attn = get("BIOGPT_HIP_RUN_ATTN", -1);                // the passes of biogpt_hip_score_continuations_batch (no other call looks at it): -1 attn_runs_kernel where it was measured faster (RUN_ATTN_MIN_*), 0 never, 1 in every pass of up to 1024 keys (A/B arms)
         float_chain = get("BIOGPT_HIP_FLOAT_CHAIN", 0);          // 1: a new context of an F32 / F16 file the float chain serves starts with it switched on (biogpt_hip_float_chain; kernels_fchain.hip.h)
+        assoc = get("BIOGPT_HIP_ASSOC", 0);                        // 1: a new context of a file the SIMD association serves starts in it (biogpt_hip_assoc; kernels_assoc.hip.h)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
     }
 };
@@ -387,6 +389,7 @@ struct biogpt_hip_ctx {
     int64_t wide_launches = 0;             // linear-stage launches of the wide chain (kernels_mfma_wide.hip.h; biogpt_hip_wide_launches)
     bool float_chain = false;              // the float chain is switched on (biogpt_hip_float_chain): passes over column states of this F32 / F16 file run on kernels_fchain.hip.h
     int64_t float_launches = 0;            // linear-stage launches of the float chain (biogpt_hip_float_launches)
+    int assoc = 0;                         // 1: the SIMD association (biogpt_hip_assoc): every pass on the five-launch layer with the kernels of kernels_assoc.hip.h; no call over column states
     int32_t gen_launch_tokens[16] = {0}; int gen_launches = 0;   // the last biogpt_hip_generate_greedy: tokens of each multi-token pipelined launch (biogpt_hip_generate_launches)
     int32_t prefix_stats[4] = {0, 0, 0, 0};   // of the last biogpt_hip_generate_*_prefix call that generated tokens: shared rows, prompt columns evaluated, path (0 in place, 1 copied), columns
     int xc_batch = 0;                      // a column generation call with 2 .. 8 columns holds the device's pipeline slot (choose_column_path): its decode steps run as column-per-XCD launches (streams mode)
@@ -641,8 +644,18 @@ inline const char *float_chain_refusal(const biogpt_hip_hparams &hp) {
     if (hp.d_ff < 32 || hp.d_ff % 32 != 0) return "d_ff is no multiple of 32";
     return nullptr;
 }
-// the chain a CONTEXT's calls over column states run on: the file's, or the float chain while it is switched on
-inline int chain_kind(const biogpt_hip_ctx *c) { return c->float_chain ? CHAIN_FLOAT : chain_kind_of(c->hp); }
+// why a file cannot have the SIMD association (null: it can): the oracle restates the AVX2 dot of the five block formats only (biogpt_hip_assoc)
+inline const char *assoc_refusal(const biogpt_hip_hparams &hp) {
+    const int32_t t = ftype_to_type(hp.ftype);
+    if (t == T_F32) return "an F32 file (the oracle's AVX2 F32 dot is not built into the mat-vec yet)";
+    if (t == T_F16) return "an F16 file (the oracle does not restate an AVX2 F16 dot: there is nothing to hold one to)";
+    if (!is_quantized(t)) return "no block-quantized file";
+    if (hp.n_head < 1 || hp.d_model % hp.n_head != 0 || hp.d_model / hp.n_head != 64) return "a head size other than 64";
+    if (hp.d_model % 32 != 0 || hp.d_ff < 32 || hp.d_ff % 32 != 0) return "d_model or d_ff no multiple of 32";
+    return nullptr;
+}
+// the chain a CONTEXT's calls over column states run on: the file's, or the float chain while it is switched on; none in the SIMD association
+inline int chain_kind(const biogpt_hip_ctx *c) { return c->assoc ? CHAIN_NONE : c->float_chain ? CHAIN_FLOAT : chain_kind_of(c->hp); }
 template <int WT>
 hipError_t launch_chain_mfma(ChainOp op, const bgk::MatvecParams &p, const bgk::DevMatrix &img, hipStream_t st, ChainLaunch *rep) {
     int site = -1;
@@ -736,6 +749,54 @@ hipError_t launch_mv(const EngineOptions &o, const bgk::MatvecParams &p, const M
     }
 }
 
+// ---- the SIMD association (kernels_assoc.hip.h): the launches of a context in mode 1, and of the probe of its kernels (biogpt_hip_assoc_device) ----
+// What a launch of matvec_simd_kernel was: its geometry, the columns per workgroup and the rows one workgroup (and its arg-max partial) covers
+struct SimdLaunch { int32_t threads, grid_x, grid_y, lds, nc, rows; };
+// Four threads per row and one serial chain per thread: small matrices take small workgroups so that the chip sees enough of them (a workgroup repeats the
+// prologue, which is short beside K / 32 dependent fma per row); then row steps until the grid is at most MATVEC_MAX_GRID workgroups (the arg-max
+// partial buffer holds that many).  Columns per workgroup: 1, 4 or 8, what the LDS holds of them.
+inline SimdLaunch simd_mv_geometry(int64_t M, int K, int N) {
+    int threads = 256;
+    while (threads > 64 && (M + threads / 4 - 1) / (threads / 4) < MATVEC_MIN_GRID) threads >>= 1;
+    int steps = 1;
+    while ((M + (int64_t)(threads / 4) * steps - 1) / ((int64_t)(threads / 4) * steps) > MATVEC_MAX_GRID) steps++;
+    const int rows = threads / 4 * steps;
+    int nc = N == 1 ? 1 : (N <= 4 ? 4 : 8);
+    while (nc > 1 && bgk::matvec_simd_smem_bytes(K, nc) > 64 * 1024) nc = nc == 8 ? 4 : 1;
+    return SimdLaunch{threads, (int32_t)((M + rows - 1) / rows), (N + nc - 1) / nc, (int32_t)bgk::matvec_simd_smem_bytes(K, nc), nc, rows};
+}
+template <int WT, int PRO, int EPI>
+hipError_t launch_mv_simd_typed(bgk::MatvecParams p, hipStream_t st, int *grid_out, SimdLaunch *rep) {
+    const SimdLaunch g = simd_mv_geometry(p.W.M, p.W.K, p.N);
+    if (g.lds > 64 * 1024) return hipErrorInvalidValue;      // one column of K > 60 000 values: not a shape of any BioGPT
+    p.rpw = g.rows;
+    if (grid_out) *grid_out = g.grid_x;
+    if (rep) *rep = g;
+    const dim3 grid(g.grid_x, g.grid_y), block(g.threads);
+    if (g.nc == 1) hipLaunchKernelGGL((bgk::matvec_simd_kernel<WT, PRO, EPI, 1>), grid, block, g.lds, st, p);
+    else if (g.nc == 4) hipLaunchKernelGGL((bgk::matvec_simd_kernel<WT, PRO, EPI, 4>), grid, block, g.lds, st, p);
+    else hipLaunchKernelGGL((bgk::matvec_simd_kernel<WT, PRO, EPI, 8>), grid, block, g.lds, st, p);
+    return hipGetLastError();
+}
+template <int PRO, int EPI>
+hipError_t launch_mv_simd(const bgk::MatvecParams &p, hipStream_t st, int *grid_out = nullptr, SimdLaunch *rep = nullptr) {
+    switch (p.W.type) {
+        case T_Q4_0: return launch_mv_simd_typed<bgk::W_Q4_0, PRO, EPI>(p, st, grid_out, rep);
+        case T_Q4_1: return launch_mv_simd_typed<bgk::W_Q4_1, PRO, EPI>(p, st, grid_out, rep);
+        case T_Q5_0: return launch_mv_simd_typed<bgk::W_Q5_0, PRO, EPI>(p, st, grid_out, rep);
+        case T_Q5_1: return launch_mv_simd_typed<bgk::W_Q5_1, PRO, EPI>(p, st, grid_out, rep);
+        case T_Q8_0: return launch_mv_simd_typed<bgk::W_Q8_0, PRO, EPI>(p, st, grid_out, rep);
+        default: return hipErrorInvalidValue;
+    }
+}
+// the Q8 rows alone (the probe's stage 0)
+inline hipError_t launch_q8_simd_rows(const bgk::Q8SimdParams &q, hipStream_t st, SimdLaunch *rep = nullptr) {
+    const size_t lds = bgk::matvec_simd_smem_bytes(q.K, 1);
+    if (rep) *rep = SimdLaunch{256, q.N, 1, (int32_t)lds, 1, 0};
+    hipLaunchKernelGGL(bgk::q8_simd_rows_kernel, dim3(q.N), dim3(256), lds, st, q);
+    return hipGetLastError();
+}
+
 bgk::MatvecParams mv_base(const biogpt_hip_ctx *c, const MatSlot &m, const MvShape &s) {
     bgk::MatvecParams p{};
     p.W = dev_matrix(c, m);
@@ -759,11 +820,17 @@ bgk::MatvecParams mv_base(const biogpt_hip_ctx *c, const MatSlot &m, const MvSha
 // Final LayerNorm + lm_head of ONE column x [K] into out [M], with the arg-max partial of every workgroup's rows (pmax_val / pmax_idx, grid_out entries) --
 // whichever kernel launch_mv picks for the type and shape.  p: the matrix and the site's own fields (mv_base; st_adv / adv / lineage where the site has them).
 hipError_t launch_lm_head_row(const EngineOptions &o, bgk::MatvecParams p, const MvShape &s, const float *x, const float *ln_w, const float *ln_b, float *out,
-                              float *pmax_val, int32_t *pmax_idx, hipStream_t st, int *grid_out, MvLaunch *rep = nullptr) {
+                              float *pmax_val, int32_t *pmax_idx, hipStream_t st, int *grid_out, MvLaunch *rep = nullptr, bool simd = false) {
     p.ln_w = ln_w; p.ln_b = ln_b;
     p.ldx = p.W.K; p.ldo = p.W.M;
     p.x = x; p.N = 1; p.out = out;
     p.pmax_val = pmax_val; p.pmax_idx = pmax_idx;
+    if (simd) {      // a context in the SIMD association (kernels_assoc.hip.h); kernel 3 of a report
+        SimdLaunch g{};
+        const hipError_t e = launch_mv_simd<bgk::PRO_LN, bgk::EPI_LOGITS>(p, st, grid_out, &g);
+        if (rep) *rep = MvLaunch{3, g.grid_x, g.rows};
+        return e;
+    }
     return launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(o, p, s, st, grid_out, rep);
 }
 // argmax_kernel over nparts partials: the id into the state block (next token, gen_ids), the position moved on by n_eval
@@ -854,7 +921,7 @@ bool ensure_tile_images(biogpt_hip_ctx *c) {
 bool fused_decode_ok(const biogpt_hip_ctx *c, int t_max) {
     const auto &hp = c->hp;
     return is_quantized(ftype_to_type(hp.ftype)) && hp.d_model == 1024 && hp.d_ff == 4096 && hp.n_head == 16 && t_max <= 1024 &&
-           hp.n_positions >= 64 && !c->opt.no_fused_decode;
+           hp.n_positions >= 64 && !c->opt.no_fused_decode && c->assoc == 0;      // (the SIMD association has the five launches per layer only)
 }
 
 // only: -1 = the five kernels of the layer in order; 0..4 = just that kernel (biogpt_hip_bench_matvec)
@@ -1277,6 +1344,7 @@ struct PassLaunch {
     bool chain, pchain, mfma;       // the single-token fast chain; its many-column form; on the int8 matrix cores
     bool wchain;                    // the wide chain: a pass over column states of a block-quantized file that is not BioGPT-base (kernels_mfma_wide.hip.h)
     bool fchain;                    // the float chain: a pass over column states of an F32 / F16 file whose context has it switched on (kernels_fchain.hip.h)
+    bool simd;                      // the context is in the SIMD association: the generic sites launch the kernels of kernels_assoc.hip.h
     int q81;
     const bgk::SeqState *seq;       // column states of a pass over the per-sequence caches (null: the context's own columns)
     int col_mode;                   // 1: packed columns
@@ -1285,6 +1353,11 @@ struct PassLaunch {
     bgk::DevMatrix img;
     // a matrix whose rows are no whole 16-row tiles (an lm_head of a vocabulary that is no multiple of 16) has no image: it stays on the 8-column kernel
     const bgk::DevMatrix *tile(const MatSlot &m) { if (!mfma || !tile_image_ok(m)) return nullptr; img = tile_matrix(c, m); return &img; }
+    // a generic site's launch: whichever kernel launch_mv picks for the type and shape, or the SIMD association's mat-vec
+    template <int PRO, int EPI>
+    hipError_t mv(const bgk::MatvecParams &p, const MvShape &s) {
+        return simd ? launch_mv_simd<PRO, EPI>(p, st) : launch_mv<PRO, EPI>(c->opt, p, s, st);
+    }
     // one launch of the chain; counts the ones that went to the matrix cores
     hipError_t chain_launch(ChainOp op, const bgk::MatvecParams &p, const bgk::DevMatrix *image = nullptr) {
         ChainLaunch rep{};
@@ -1327,6 +1400,7 @@ enum AttnKernel : int {
     AK_FAST_SHARED = 4,                                                  // + the four above: their SHARED instantiations
     AK_PREFIX = 8, AK_SPLIT = 9, AK_GROUP = 10, AK_TILE_DMA = 11, AK_TILE = 12, AK_GENERIC = 13,
     AK_RUNS = 16,                                                        // attn_runs_kernel<8>: no route of biogpt_hip_attn_device (its probe is biogpt_hip_attn_runs_device)
+    AK_SIMD = 17,                                                        // attn_simd_kernel: the SIMD association's (its probe is biogpt_hip_assoc_device)
 };
 struct AttnLaunch { int kernel, threads, grid_x, grid_y; size_t lds; };
 
@@ -1441,6 +1515,12 @@ inline AttnLaunch launch_attn_generic(const bgk::AttnParams &a, int H, int N, in
     hipLaunchKernelGGL(bgk::attn_kernel, dim3(g.grid_x, g.grid_y), dim3(g.threads), g.lds, st, a);
     return g;
 }
+// the SIMD association's attention (kernels_assoc.hip.h): head size 64, up to SIMD_ATTN_MAXT keys; lds: its static LDS
+inline AttnLaunch launch_attn_simd(const bgk::AttnParams &a, int H, int N, hipStream_t st) {
+    const AttnLaunch g{AK_SIMD, 256, H, N, 64 * 4 + bgk::SIMD_ATTN_MAXT * 4 + 32 * 64 * 4 + 16 * 8};
+    hipLaunchKernelGGL(bgk::attn_simd_kernel, dim3(g.grid_x, g.grid_y), dim3(g.threads), 0, st, a);
+    return g;
+}
 
 // the attention launch(es) of layer l
 bool enqueue_attention(PassLaunch &k, int l) {
@@ -1457,6 +1537,10 @@ bool enqueue_attention(PassLaunch &k, int l) {
     a.dbg = c->opt.dbg; a.tstamp = c->tstamp;
     a.q81 = k.q81;
     if (k.chain) { a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; }
+    if (k.simd) {      // (head size 64 and t_max <= SIMD_ATTN_MAXT: enqueue_forward)
+        launch_attn_simd(a, H, N, st);
+        return true;
+    }
     if (!(dk == 64 && t_max <= 1024)) {
         launch_attn_generic(a, H, N, k.attn_threads, st);
         return true;
@@ -1512,7 +1596,7 @@ bool enqueue_layer(PassLaunch &k, int l) {
             p.aq_q = c->aq_q[2]; p.aq_d = c->aq_d[2]; p.aq_s = c->aq_s[2];
             HIP_TRY(false, k.chain_launch(CHAIN_QKV_Q8, p, k.tile(L.qkv)));
         } else {
-            HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_QKV>(c->opt, p, s, st)));
+            HIP_TRY(false, (k.mv<bgk::PRO_LN, bgk::EPI_QKV>(p, s)));
         }
     }
     if (!enqueue_attention(k, l)) return false;
@@ -1530,7 +1614,7 @@ bool enqueue_layer(PassLaunch &k, int l) {
             p.aq_q = c->aq_q[0]; p.aq_d = c->aq_d[0]; p.aq_s = c->aq_s[0];
             HIP_TRY(false, k.chain_launch(CHAIN_OPROJ, p, k.tile(L.o)));
         } else {
-            HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
+            HIP_TRY(false, (k.mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(p, s)));
         }
     }
     {  // LN1 + fc1 + bias + GELU
@@ -1553,7 +1637,7 @@ bool enqueue_layer(PassLaunch &k, int l) {
             p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
             HIP_TRY(false, k.chain_launch(CHAIN_FC1, p));
         } else {
-            HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_GELU>(c->opt, p, s, st)));
+            HIP_TRY(false, (k.mv<bgk::PRO_LN, bgk::EPI_GELU>(p, s)));
         }
     }
     {  // fc2 + bias + residual
@@ -1570,7 +1654,7 @@ bool enqueue_layer(PassLaunch &k, int l) {
             p.aq_q = c->aq_q[1]; p.aq_d = c->aq_d[1]; p.aq_s = c->aq_s[1];
             HIP_TRY(false, k.chain_launch(CHAIN_FC2, p, k.tile(L.fc2)));
         } else {
-            HIP_TRY(false, (launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(c->opt, p, s, st)));
+            HIP_TRY(false, (k.mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(p, s)));
         }
     }
     return true;
@@ -1664,12 +1748,13 @@ bool enqueue_final(PassLaunch &k) {
         p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
         p.ldx = D; p.ldo = V;
         p.x = c->x; p.N = N; p.out = c->logits_all;
-        HIP_TRY(false, (launch_mv<bgk::PRO_LN, bgk::EPI_LOGITS>(c->opt, p, s, st)));
+        HIP_TRY(false, (k.mv<bgk::PRO_LN, bgk::EPI_LOGITS>(p, s)));
         return true;
     }
-    if (s.grid > c->pmax_cap) BG_FAIL(false, "internal: arg-max partial buffer too small (%d > %d)", s.grid, c->pmax_cap);
+    if (s.grid > c->pmax_cap) BG_FAIL(false, "internal: arg-max partial buffer too small (%d > %d)", s.grid, c->pmax_cap);      // (the SIMD launch: at most MATVEC_MAX_GRID <= pmax_cap partials)
     int lm_grid = 0;
-    HIP_TRY(false, launch_lm_head_row(c->opt, p, s, c->x + (size_t)(N - 1) * D, dev_vec(c, c->plan.ln_w), dev_vec(c, c->plan.ln_b), c->logits, c->pmax_val, c->pmax_idx, st, &lm_grid));
+    HIP_TRY(false, launch_lm_head_row(c->opt, p, s, c->x + (size_t)(N - 1) * D, dev_vec(c, c->plan.ln_w), dev_vec(c, c->plan.ln_b), c->logits, c->pmax_val, c->pmax_idx, st, &lm_grid,
+                                      nullptr, k.simd));
     c->lm_blocks = lm_grid;
     return true;
 }
@@ -1698,7 +1783,12 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
 
     // single-token fast chain: BioGPT-base shapes, block-quantized weights -> producer-side Q8 hand-offs
     const int32_t wt = ftype_to_type(hp.ftype);
-    k.chain = is_quantized(wt) && k.D == 1024 && k.F == 4096 && k.dk == 64 && t_max <= 1024;
+    // the SIMD association: the context's own columns on the five launches per layer, no chain; the calls over column states were refused at their entry
+    k.simd = c->assoc != 0;
+    if (k.simd && batch) BG_FAIL(false, "internal: a pass over column states reached a context in the SIMD association");
+    if (k.simd && (k.dk != 64 || t_max > bgk::SIMD_ATTN_MAXT))
+        BG_FAIL(false, "the SIMD association serves head size 64 and contexts of up to %d tokens (got head size %d, %d tokens)", bgk::SIMD_ATTN_MAXT, k.dk, t_max);
+    k.chain = !k.simd && is_quantized(wt) && k.D == 1024 && k.F == 4096 && k.dk == 64 && t_max <= 1024;
     k.pchain = k.chain && (N > 1 || batch);   // several columns: LayerNorm+Q8 once per site (lnq_kernel), 8 columns per workgroup
     // enough columns to fill 16-wide MFMA tiles: the chain runs on the int8 matrix cores from the row-tiled weight image
     k.mfma = k.pchain && N >= (pass.cols == Cols::PerSequence ? MFMA_MIN_DECODE_COLS : MFMA_MIN_PASS_COLS) && c->tile_img != nullptr;
@@ -1998,6 +2088,7 @@ biogpt_hip_ctx *load_impl(const char *fname, int device, int verbosity, void *ex
     c->opt.load();
     c->hp = mf.hp;
     c->float_chain = c->opt.float_chain == 1 && float_chain_refusal(c->hp) == nullptr;      // (the environment's default holds where the file can have it)
+    c->assoc = (c->opt.assoc == 1 && assoc_refusal(c->hp) == nullptr) ? 1 : 0;      // (likewise BIOGPT_HIP_ASSOC)
     c->device = device;
     c->n_tensors = (int)mf.tensors.size();
     c->vocab = mf.vocab;
@@ -2107,6 +2198,7 @@ biogpt_hip_ctx *biogpt_hip_attach(const biogpt_hip_hparams *hp, int device, void
     c->opt.load();
     c->hp = *hp;
     c->float_chain = c->opt.float_chain == 1 && float_chain_refusal(c->hp) == nullptr;
+    c->assoc = (c->opt.assoc == 1 && assoc_refusal(c->hp) == nullptr) ? 1 : 0;
     c->device = device;
     c->pos_rows = (int64_t)hp->n_positions + 2;
     c->plan = plan_arena(*hp, c->pos_rows);
@@ -2161,7 +2253,7 @@ int biogpt_hip_refresh_options(biogpt_hip_ctx *ctx) {
 
 int biogpt_hip_xpipe_state(const biogpt_hip_ctx *ctx) {
     if (!ctx) return -2;
-    if (ctx->xp_state != 1 || !ctx->opt.xpipe) return ctx->xp_state == 1 ? 0 : ctx->xp_state;
+    if (ctx->xp_state != 1 || !ctx->opt.xpipe || ctx->assoc) return ctx->xp_state == 1 ? 0 : ctx->xp_state;      // (the SIMD association takes no pipelined launch)
     std::lock_guard<std::mutex> lk(g_xp_mu);
     const biogpt_hip_ctx *owner = (ctx->device >= 0 && ctx->device < 64) ? g_xp_owner[ctx->device] : nullptr;
     return (owner == nullptr || owner == ctx) ? 1 : 0;
@@ -2643,6 +2735,38 @@ int biogpt_hip_float_chain(biogpt_hip_ctx *ctx, int on) {
     ctx->float_chain = on == 1;
     return 0;
 }
+// The association's switch.  Mode 0, the scalar association, is the context as it ever was; mode 1 is the SIMD association (kernels_assoc.hip.h): the five
+// launches per layer on its kernels and nothing else.  Every captured graph bakes a route -- the column steps, the single-token steps and evals: dropped.
+int biogpt_hip_assoc(biogpt_hip_ctx *ctx, int mode) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (mode != 0 && mode != 1) BG_FAIL(-1, "mode must be 0 (the scalar association) or 1 (the SIMD association) (got %d)", mode);
+    if (session_refuses(ctx)) return -1;
+    {
+        std::lock_guard<std::mutex> lk(g_xp_mu);
+        if (ctx->xp_in_call) BG_FAIL(-1, "the association cannot be switched while a call of this context is running");
+    }
+    if (mode == 1) {
+        if (const char *why = assoc_refusal(ctx->hp))
+            BG_FAIL(-1, "the SIMD association cannot be switched on for this file: it is %s (it needs Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 weights, head size 64, d_model and d_ff multiples of 32; got ftype %d, d_model %d, d_ff %d, %d heads)", why, ctx->hp.ftype, ctx->hp.d_model, ctx->hp.d_ff, ctx->hp.n_head);
+    }
+    if (ctx->assoc == mode) return 0;
+    if (ctx->ready) {
+        HIP_TRY(-2, hipSetDevice(ctx->device));
+        if (!resident_stop(ctx)) return -2;      // (a resident launch is a scalar-association launch; it synchronises the stream)
+        HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+        disarm_lineage(ctx);
+    }
+    for (auto &pl : ctx->graph_step) for (auto &row : pl) for (auto &g : row) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    for (auto &pl : ctx->graph_eval) for (auto &f : pl) for (auto &row : f) for (auto &g : row) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    drop_column_graphs(ctx);
+    ctx->assoc = mode;
+    return 0;
+}
+int biogpt_hip_get_assoc(const biogpt_hip_ctx *ctx) {
+    if (!ctx) BG_FAIL(-1, "null context");
+    return ctx->assoc;
+}
 int biogpt_hip_fpipe_stamps(biogpt_hip_ctx *ctx, uint64_t *out, int n) {
     if (!ctx || !out || n < 0 || ctx->fp_state != 1 || !ctx->opt.fpipe_stamps) return -1;
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
@@ -2858,7 +2982,13 @@ static bool check_prompts(const biogpt_hip_ctx *c, const int32_t *prompts, const
 
 // The gate of every call over column states.  wide_ok: the call is open to the wide chain (DESIGN.md 4.7 lists them); a wide file's row-tiled image is built
 // here, before any capture -- it has no kernel to fall back to, so an image that does not fit is the call's error.
+// A context in the SIMD association serves the single-sequence calls: every call over column states is refused by its name, before any launch
+static bool assoc_refuses(const biogpt_hip_ctx *c, const char *what) {
+    if (c->assoc) BG_FAIL(true, "%s runs over column states, which the SIMD association does not serve (biogpt_hip_assoc(ctx, 0) switches the context back to the scalar association)", what);
+    return false;
+}
 static bool check_fast_chain(biogpt_hip_ctx *c, const char *what, bool wide_ok = false) {
+    if (assoc_refuses(c, what)) return false;
     const int kind = chain_kind(c);
     if (kind == CHAIN_FLOAT) {      // (nothing to build: the stage reads the arena's own rows)
         if (!wide_ok) BG_FAIL(false, "%s needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096): the float fast chain switched on for this %s file does not serve it", what, ftype_to_type(c->hp.ftype) == T_F16 ? "F16" : "F32");
@@ -3182,6 +3312,7 @@ static int generate_greedy_batch_once(biogpt_hip_ctx *ctx, const int32_t *prompt
     if (prefix && (n_seqs < 1 || n_seqs > 511)) BG_FAIL(-1, "n_seqs must be in [1, 511] behind a prefix (got %d)", n_seqs);   // one slot holds the prefix
     // (the plain call meets the gate in enqueue_forward, as ever; the two variants are not open to the wide chain and say so by name)
     if ((prefix || lp) && !check_fast_chain(ctx, prefix ? "generation behind a shared prefix" : "generation with log-probabilities")) return -1;
+    if (assoc_refuses(ctx, "batched greedy generation")) return -1;
     if (n_seqs < 1 || n_seqs > 512) BG_FAIL(-1, "n_seqs must be in [1, 512]");   // activation buffers hold n_positions >= 512 columns; each sequence owns a full F32 KV cache
     if (n_seqs > hp_cols(ctx)) BG_FAIL(-1, "n_seqs (%d) exceeds the %d activation columns of this model", n_seqs, hp_cols(ctx));
     if (n_batch < 1) BG_FAIL(-1, "n_batch must be >= 1");

@@ -1826,3 +1826,175 @@ int biogpt_hip_tail_device(int device, int32_t stage, int32_t wtype, int32_t n, 
     report_launch(launched, {});
     return 0;
 }
+
+// ---- the kernels of the SIMD association alone (kernels_assoc.hip.h), through the launch functions of a context in mode 1 ----
+// stage 0 Q8: x [N][K] -> the rows as the mat-vec's prologue leaves them in LDS (behind the LayerNorm when ln_w / ln_b are given): out_q [N + 1][K] codes,
+//   out_d [N + 1][K / 32] the scale the dot reads (through f16 for the Q8_0 form), out_s [N + 1][K / 32] words (Q8_0: the integer sum; Q8_1: bits of d * sum).
+//   wtype names the weight format whose activation form it is (Q4_1 / Q5_1: Q8_1).
+// stage 1 MATVEC: one launch of matvec_simd_kernel<wtype, pro, epi>: pro 0 PLAIN, 1 LN (ln_w, ln_b); epi 0 QKV (M == 3 K, 64 | K; dev_state, P and
+//   k_slots / v_slots [1][K / 64][P][64], updated in place; out = the q rows [N + 1][K]), 1 RESID (bias, resid [N][M]), 2 GELU (bias), 3 LOGITS (N == 1: the
+//   arg-max partial of every workgroup into pmax_val / pmax_idx [1025]; either NULL: none).  w_rows: M rows of K / 32 blocks in the file's format.
+//   out but for QKV: [N + 1][M + 16].  N is what one workgroup row takes: 1 .. 8.
+// stage 2 ATTN: attn_simd_kernel over q [N][H * 64], k_slots / v_slots [H][P][64] and dev_state {n_past, n_gen, causal, chunk}, from which column i's visible
+//   keys follow as in every attention kernel (at most 1024, at most P); out [N + 1][H * 64].
+// The outputs come back WHOLE as allocated and preset to 0xff bytes: what the launch does not write reads as NaN / -1.  launched [8]: stage 0 / 1: threads,
+// grid x, grid y, dynamic LDS bytes, columns per workgroup, rows per workgroup; stage 2: AK_SIMD, threads, grid x, grid y, static LDS bytes.
+int biogpt_hip_assoc_device(int device, int32_t stage, int32_t wtype, int32_t pro, int32_t epi, int32_t M, int32_t K, int32_t N, int32_t H, int32_t P, const void *w_rows,
+                            const float *x, const float *ln_w, const float *ln_b, const float *bias, const float *resid, const int32_t *dev_state, const float *q,
+                            float *k_slots, float *v_slots, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, float *pmax_val, int32_t *pmax_idx,
+                            int32_t *launched) {
+    clear_error();
+    if (stage < 0 || stage > 2) BG_FAIL(-1, "stage %d is no stage (0 Q8, 1 MATVEC, 2 ATTN)", stage);
+    if (stage == 2) {
+        if (H < 1 || H > 64) BG_FAIL(-1, "H must be in [1, 64]");
+        if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+        if (!q || !k_slots || !v_slots || !dev_state || !out) BG_FAIL(-1, "q, k_slots, v_slots, dev_state or out is NULL");
+        if (dev_state[0] < 0) BG_FAIL(-1, "n_past %d is negative", dev_state[0]);
+        for (int i = 0; i < N; i++) {
+            const int T = host_visible_keys(dev_state, i, N);
+            if (T < 1 || T > bgk::SIMD_ATTN_MAXT) BG_FAIL(-1, "column %d sees T = %d keys: the kernel holds 1 .. %d", i, T, bgk::SIMD_ATTN_MAXT);
+            if (T > P) BG_FAIL(-1, "column %d sees %d keys of a table of P = %d rows", i, T, P);
+        }
+        HIP_TRY(-2, hipSetDevice(device));
+        const size_t D = (size_t)H * 64, kv_b = (size_t)H * P * 64 * 4;
+        ProbeImage im;      // [K | V | q | context state | exp table | out], one guard row
+        const ProbePart o_k = im.in(k_slots, kv_b), o_v = im.in(v_slots, kv_b), o_q = im.in(q, (size_t)N * D * 4), o_ds = im.in(dev_state, sizeof(bgk::DevState));
+        const ProbePart o_tab = im.own(exp_table_f16()), o_out = im.out((size_t)(N + 1) * D * 4);
+        if (!im.upload()) return -2;
+        bgk::AttnParams a{};
+        a.q = im.at<const float>(o_q); a.kcache = im.at<const float>(o_k); a.vcache = im.at<const float>(o_v); a.out = im.at<float>(o_out);
+        a.st = im.at<const bgk::DevState>(o_ds); a.exp_tab = im.at<const uint16_t>(o_tab);
+        a.N = N; a.D = (int32_t)D; a.dk = 64; a.P = P;
+        const AttnLaunch g = launch_attn_simd(a, H, N, 0);
+        HIP_TRY(-2, hipGetLastError());
+        HIP_TRY(-2, hipDeviceSynchronize());
+        report_launch(launched, {g.kernel, g.threads, g.grid_x, g.grid_y, (int32_t)g.lds});
+        return im.read(o_out, out) ? 0 : -2;
+    }
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (N < 1 || N > bgk::SIMD_MAX_COLS) BG_FAIL(-1, "N must be in [1, %d]: the columns of one workgroup row", bgk::SIMD_MAX_COLS);
+    if (!x) BG_FAIL(-1, "x is NULL");
+    if ((ln_w != nullptr) != (ln_b != nullptr)) BG_FAIL(-1, "ln_w and ln_b come together");
+    const int q81 = (wtype == T_Q4_1 || wtype == T_Q5_1) ? 1 : 0;
+    if (stage == 0) {
+        if (!out_q || !out_d || !out_s) BG_FAIL(-1, "out_q, out_d or out_s is NULL");
+        HIP_TRY(-2, hipSetDevice(device));
+        const size_t bpr = (size_t)K / QK;
+        ProbeImage im;      // [x | gain | bias of the LayerNorm | codes | d | s], one guard row each
+        const ProbePart o_x = im.in(x, (size_t)N * K * 4), o_lw = im.in(ln_w, (size_t)K * 4), o_lb = im.in(ln_b, (size_t)K * 4);
+        const ProbePart o_q = im.out((size_t)(N + 1) * K), o_d = im.out((size_t)(N + 1) * bpr * 4), o_s = im.out((size_t)(N + 1) * bpr * 4);
+        if (!im.upload()) return -2;
+        bgk::Q8SimdParams qp{};
+        qp.x = im.at<const float>(o_x); qp.K = K; qp.N = N; qp.q81 = q81; qp.eps = 1e-5f;
+        if (ln_w) { qp.ln_w = im.at<const float>(o_lw); qp.ln_b = im.at<const float>(o_lb); }
+        qp.oq = im.at<int8_t>(o_q); qp.od = im.at<float>(o_d); qp.os = im.at<uint32_t>(o_s);
+        SimdLaunch g{};
+        HIP_TRY(-2, launch_q8_simd_rows(qp, 0, &g));
+        HIP_TRY(-2, hipDeviceSynchronize());
+        report_launch(launched, {g.threads, g.grid_x, g.grid_y, g.lds, g.nc, g.rows});
+        return im.read(o_q, out_q) && im.read(o_d, out_d) && im.read(o_s, out_s) ? 0 : -2;
+    }
+    // stage 1
+    if (pro != bgk::PRO_PLAIN && pro != bgk::PRO_LN) BG_FAIL(-1, "pro %d is no prologue of the SIMD mat-vec (0 PLAIN, 1 LN)", pro);
+    if (epi < bgk::EPI_QKV || epi > bgk::EPI_LOGITS) BG_FAIL(-1, "epi %d is no epilogue of the SIMD mat-vec (0 QKV, 1 RESID, 2 GELU, 3 LOGITS)", epi);
+    const bool forms_ok = (pro == bgk::PRO_LN && epi != bgk::EPI_RESID) || (pro == bgk::PRO_PLAIN && epi == bgk::EPI_RESID);
+    if (!forms_ok) BG_FAIL(-1, "pro %d with epi %d is no site of the layer (LN -> QKV, PLAIN -> RESID, LN -> GELU, LN -> LOGITS)", pro, epi);
+    if ((pro == bgk::PRO_LN) != (ln_w != nullptr)) BG_FAIL(-1, "ln_w and ln_b go with pro 1 (LN) and only with it");
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    if (epi == bgk::EPI_QKV && (K % 64 != 0 || M != 3 * K)) BG_FAIL(-1, "q/k/v is 3 K x K with heads of 64 (got %d x %d)", M, K);
+    if (!w_rows || !out) BG_FAIL(-1, "w_rows or out is NULL");
+    if (epi != bgk::EPI_LOGITS && !bias) BG_FAIL(-1, "bias is NULL");
+    if (epi == bgk::EPI_RESID && !resid) BG_FAIL(-1, "resid is NULL");
+    if ((pmax_val != nullptr) != (pmax_idx != nullptr)) BG_FAIL(-1, "pmax_val and pmax_idx come together");
+    if (pmax_val && (epi != bgk::EPI_LOGITS || N != 1)) BG_FAIL(-1, "the arg-max partials are the LOGITS epilogue's, of one column");
+    const bool qkv = epi == bgk::EPI_QKV;
+    if (!check_probe_columns(__func__, qkv, N, dev_state, nullptr, 0, P, 1, k_slots, v_slots)) return -1;
+    if (bgk::matvec_simd_smem_bytes(K, 1) > 64 * 1024) BG_FAIL(-1, "a column of K = %d values exceeds the kernel's LDS", K);
+    HIP_TRY(-2, hipSetDevice(device));
+    const int cols = N + 1, ldo = M + 16;
+    const size_t kv_b = qkv ? (size_t)(K / 64) * P * 64 * 4 : 0, part_b = (size_t)(MATVEC_MAX_GRID + 1) * 4;
+    ProbeImage im;      // [weights | x | gain | bias of the LayerNorm | the stage's parts | out | partials], guard column and rows in the output
+    const BlockRows wr = upload_block_rows(im, wtype, w_rows, M, K, false);
+    const ProbePart o_x = im.in(x, (size_t)N * K * 4), o_lw = im.in(ln_w, (size_t)K * 4), o_lb = im.in(ln_b, (size_t)K * 4);
+    const StageParts sp = stage_parts(im, bias, (size_t)M * 4, epi == bgk::EPI_RESID ? resid : nullptr, (size_t)N * M * 4, dev_state, nullptr, N, k_slots, v_slots, kv_b);
+    const ProbePart o_out = im.out((size_t)cols * (qkv ? K : ldo) * 4), o_pv = im.out(pmax_val ? part_b : 0), o_pi = im.out(pmax_val ? part_b : 0);
+    if (!im.upload()) return -2;
+    bgk::MatvecParams p = stage_params(im, wr.W(im), sp, K, P, N, qkv, 0, o_out, ldo, M);
+    p.x = im.at<const float>(o_x); p.ldx = K;
+    if (ln_w) { p.ln_w = im.at<const float>(o_lw); p.ln_b = im.at<const float>(o_lb); }
+    if (pmax_val) { p.pmax_val = im.at<float>(o_pv); p.pmax_idx = im.at<int32_t>(o_pi); }
+    SimdLaunch g{};
+    hipError_t e = hipErrorInvalidValue;
+    if (epi == bgk::EPI_QKV) e = launch_mv_simd<bgk::PRO_LN, bgk::EPI_QKV>(p, 0, nullptr, &g);
+    else if (epi == bgk::EPI_RESID) e = launch_mv_simd<bgk::PRO_PLAIN, bgk::EPI_RESID>(p, 0, nullptr, &g);
+    else if (epi == bgk::EPI_GELU) e = launch_mv_simd<bgk::PRO_LN, bgk::EPI_GELU>(p, 0, nullptr, &g);
+    else e = launch_mv_simd<bgk::PRO_LN, bgk::EPI_LOGITS>(p, 0, nullptr, &g);
+    HIP_TRY(-2, e);
+    HIP_TRY(-2, hipDeviceSynchronize());
+    report_launch(launched, {g.threads, g.grid_x, g.grid_y, g.lds, g.nc, g.rows});
+    if (!im.read(o_out, out) || !im.read(sp.k, k_slots) || !im.read(sp.v, v_slots)) return -2;
+    if (pmax_val && (!im.read(o_pv, pmax_val) || !im.read(o_pi, pmax_idx))) return -2;
+    return 0;
+}
+
+// A kernel of the SIMD association alone, timed: one untimed launch, then reps launches on device memory of 0x11 bytes (the kernels' time does not depend on the
+// values), each between two device events.  which 0: matvec_simd_kernel<PLAIN, RESID> at M rows of K values and N columns (any N: the launch's own grid);
+// which 1: the mat-vec a context in the scalar association launches at the same shape on its five-launch route (launch_mv<PLAIN, RESID>) -- the yardstick;
+// which 2: attn_simd_kernel with M heads, K visible keys (1 .. 1024) and N query columns.  For tools/assoc_bench.py.
+int biogpt_hip_assoc_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t reps, float *us_out) {
+    clear_error();
+    if (which < 0 || which > 2) BG_FAIL(-1, "which must be 0 (the SIMD mat-vec), 1 (the scalar association's mat-vec) or 2 (the SIMD attention)");
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (reps < 1 || reps > PROBE_MAX_REPS) BG_FAIL(-1, "reps must be in [1, %d]", PROBE_MAX_REPS);
+    if (!us_out) BG_FAIL(-1, "us_out is NULL");
+    if (which == 2) {
+        if (M < 1 || M > 64) BG_FAIL(-1, "M (heads) must be in [1, 64]");
+        if (K < N || K > bgk::SIMD_ATTN_MAXT) BG_FAIL(-1, "K (visible keys of the last column) must be in [N, %d]", bgk::SIMD_ATTN_MAXT);
+        HIP_TRY(-2, hipSetDevice(device));
+        const size_t D = (size_t)M * 64, kv_b = (size_t)M * K * 64 * 4;
+        const int32_t ds[4] = {K - N, 0, 1, 0};      // causal: column N - 1 sees K keys, the others fewer
+        ProbeImage im;
+        const ProbePart o_k = im.fill(kv_b, 0x11), o_v = im.fill(kv_b, 0x11), o_q = im.fill((size_t)N * D * 4, 0x11), o_ds = im.in(ds, sizeof(ds));
+        const ProbePart o_tab = im.own(exp_table_f16()), o_out = im.fill((size_t)N * D * 4, 0x11);
+        if (!im.upload()) return -2;
+        bgk::AttnParams a{};
+        a.q = im.at<const float>(o_q); a.kcache = im.at<const float>(o_k); a.vcache = im.at<const float>(o_v); a.out = im.at<float>(o_out);
+        a.st = im.at<const bgk::DevState>(o_ds); a.exp_tab = im.at<const uint16_t>(o_tab);
+        a.N = N; a.D = (int32_t)D; a.dk = 64; a.P = K;
+        auto launch = [&]() -> hipError_t { launch_attn_simd(a, M, N, 0); return hipGetLastError(); };
+        HIP_TRY(-2, launch());
+        HIP_TRY(-2, hipDeviceSynchronize());
+        return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+    }
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    if (bgk::matvec_simd_smem_bytes(K, 1) > 64 * 1024) BG_FAIL(-1, "a column of K = %d values exceeds the kernel's LDS", K);
+    HIP_TRY(-2, hipSetDevice(device));
+    ProbeImage im;      // every part of 0x11 bytes: [qs | sc | qh | x | bias | resid | out]
+    const size_t nblk = (size_t)M * (K / QK);
+    const bool q81 = wtype == T_Q4_1 || wtype == T_Q5_1, q5 = wtype == T_Q5_0 || wtype == T_Q5_1;
+    const ProbePart o_qs = im.fill(nblk * (wtype == T_Q8_0 ? 32 : 16), 0x11), o_sc = im.fill(nblk * (q81 ? 4 : 2) + 16, 0x11), o_qh = im.fill(q5 ? nblk * 4 : 0, 0x11);
+    const ProbePart o_x = im.fill((size_t)N * K * 4, 0x11), o_bias = im.fill((size_t)M * 4, 0x11), o_res = im.fill((size_t)N * M * 4, 0x11), o_out = im.fill((size_t)N * M * 4, 0x11);
+    if (!im.upload()) return -2;
+    const MvShape s = mv_shape(wtype, M, K);
+    bgk::MatvecParams p{};
+    p.W.qs = im.d.p + o_qs.off; p.W.sc = im.d.p + o_sc.off; p.W.qh = q5 ? im.at<const uint32_t>(o_qh) : nullptr;
+    p.W.type = wtype; p.W.M = M; p.W.K = K;
+    p.upr = s.upr; p.lpr_log2 = s.lpr_log2; p.nit = s.nit; p.rpw = s.rpw;
+    p.eps = 1e-5f; p.D = 1024; p.dk = 64; p.dk_log2 = 6; p.P = 1;
+    p.inv_k = 1.0 / (double)K; p.k_pow2 = (K & (K - 1)) == 0;
+    p.N = N; p.x = im.at<const float>(o_x); p.ldx = K;
+    p.bias = im.at<const float>(o_bias); p.resid = im.at<const float>(o_res); p.ldr = M; p.out = im.at<float>(o_out); p.ldo = M;
+    EngineOptions opt{};
+    opt.load();
+    auto launch = [&]() -> hipError_t {
+        if (which == 0) return launch_mv_simd<bgk::PRO_PLAIN, bgk::EPI_RESID>(p, 0);
+        return launch_mv<bgk::PRO_PLAIN, bgk::EPI_RESID>(opt, p, s, 0);
+    };
+    HIP_TRY(-2, launch());      // one untimed launch in front
+    HIP_TRY(-2, hipDeviceSynchronize());
+    return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+}

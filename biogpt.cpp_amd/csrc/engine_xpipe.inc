@@ -252,7 +252,7 @@ void xpipe_prepare(biogpt_hip_ctx *c) {
 
 // may a step of context bucket t_max go through the pipeline at all (model, device, options, bucket) ?
 bool xpipe_bucket_ok(const biogpt_hip_ctx *c, int t_max) {
-    return c->opt.xpipe && c->xp_state == 1 && (t_max <= 256 || (t_max <= 1024 && c->xp_gran_l != nullptr)) && c->device >= 0 && c->device < 64;
+    return c->opt.xpipe && c->xp_state == 1 && c->assoc == 0 && (t_max <= 256 || (t_max <= 1024 && c->xp_gran_l != nullptr)) && c->device >= 0 && c->device < 64;
 }
 // ... and does this context hold the device's pipeline slot ?  Taken here if it is free -- or if its holder is outside every API call that took it and
 // has nothing in flight (a resident launch that left after its idle time keeps the slot until its context is called again: such a holder is relieved here;

@@ -185,6 +185,20 @@ int64_t biogpt_hip_wide_launches(const biogpt_hip_ctx *ctx);
  * d_model a multiple of 64 and d_ff of 32, and not while a queue session is open or a call of the context is running.  Drops the captured column steps.
  * Returns 0, or -1 with a message (biogpt_hip_last_error) that names the reason. */
 int biogpt_hip_float_chain(biogpt_hip_ctx *ctx, int on);
+/* The association's switch: in which order the context sums.  mode 0 (the default) is ggml's SCALAR association, the context as it ever was.  mode 1 is the
+ * SIMD association -- the logits, K / V rows and greedy ids of an AVX2 build of the reference, what the oracle computes with bo_opts.assoc = 3: activation
+ * rows quantized with id = 127 / amax and nearest-even rounding, block dots in eight fma lanes, attention dots in 4 x 8 f32 fma lanes
+ * (csrc/kernels_assoc.hip.h).  A context in mode 1 runs every pass as five launches per layer on those kernels: no fused, pipelined, chunk or resident launch,
+ * no chain (biogpt_hip_chain_kind returns 0).  It serves the single-sequence calls -- biogpt_hip_eval and its _inplace / _device / _all / _topk / _prompt forms,
+ * score, hidden, generate_greedy, biogpt_eval of the compat layer -- with contexts of up to 1024 tokens, and refuses every call over column states (the batched,
+ * queue, beam, prefix, lookup, contrastive, trie and rules calls, embed_batch, score_batch) before any launch, with a message that names the call and the
+ * association.  Mode 0 after mode 1 is bit for bit the context it was.  Legal for Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 files with head size 64, d_model and d_ff
+ * multiples of 32 (an F32 / F16 file is refused with a message that names the file type), and not while a queue session is open or a call of the context is
+ * running.  Synchronises the stream, ends a resident launch, drops every captured graph.  BIOGPT_HIP_ASSOC=1 makes mode 1 the default of new contexts whose
+ * file can have it.  Returns 0, -1 with a message (biogpt_hip_last_error), -2 on a HIP error. */
+int biogpt_hip_assoc(biogpt_hip_ctx *ctx, int mode);
+/* The context's association: 0 scalar, 1 SIMD.  -1: ctx is NULL. */
+int biogpt_hip_get_assoc(const biogpt_hip_ctx *ctx);
 /* Linear-stage launches of the float chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
  * switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_float_launches(const biogpt_hip_ctx *ctx);
@@ -454,6 +468,28 @@ int biogpt_hip_wide_chain_bench(int device, int32_t which, int32_t wtype, int32_
 int biogpt_hip_fchain_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, const void *w_rows, const float *x, const float *ln_w,
                              const float *ln_b, const float *bias, const float *resid, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t P,
                              int32_t n_slots, float *k_slots, float *v_slots, float *out, float *ln_out, int32_t *launched);
+/* One stand-alone launch of a kernel of the SIMD association (csrc/kernels_assoc.hip.h) over caller-supplied inputs, through the launch functions of a context
+ * in mode 1 (biogpt_hip_assoc).  No model, no context.  wtype: a block format (2 / 3 / 6 / 7 / 8); K a multiple of 32.
+ * stage 0 Q8: x [N][K], N in [1, 8]; ln_w / ln_b [K] (both or neither): the LayerNorm in front.  out_q [N + 1][K] the codes, out_d [N + 1][K / 32] the scale
+ *   the dot reads (through f16 for Q4_0 / Q5_0 / Q8_0 weights; f32 for Q4_1 / Q5_1), out_s [N + 1][K / 32] words: the integer sum, or the bits of d * sum.
+ * stage 1 MATVEC: matvec_simd_kernel on w_rows (M rows of K / 32 blocks in the file's format) and x [N][K], N in [1, 8]; (pro, epi) one of (1 LN, 0 QKV),
+ *   (0 PLAIN, 1 RESID), (1, 2 GELU), (1, 3 LOGITS); ln_w / ln_b with pro 1; bias [M] (not 3); resid [N][M] (1).  epi 0: M == 3 K, 64 | K, dev_state (4 words)
+ *   and one layer's k_slots / v_slots [K / 64][P][64], updated in place; out [N + 1][K] the q rows.  Otherwise out [N + 1][M + 16].  epi 3 with N == 1:
+ *   pmax_val / pmax_idx [1025] (both or neither) the arg-max partial of every workgroup's rows.
+ * stage 2 ATTN: attn_simd_kernel on q [N][H * 64], N in [1, 512], k_slots / v_slots [H][P][64] and dev_state {n_past, n_gen, causal, chunk}: column i sees
+ *   the keys every attention kernel would show it, 1 .. 1024 and at most P.  out [N + 1][H * 64].
+ * Outputs come back whole, as allocated and preset to 0xff bytes.  launched [8] (may be NULL): stage 0 / 1: threads, grid x, grid y, dynamic LDS bytes,
+ * columns per workgroup, rows per workgroup; stage 2: 17, threads, grid x, grid y, static LDS bytes.  Every refusal comes before any HIP call.  For tests of
+ * the kernels themselves and tools/assoc_bench.py. */
+int biogpt_hip_assoc_device(int device, int32_t stage, int32_t wtype, int32_t pro, int32_t epi, int32_t M, int32_t K, int32_t N, int32_t H, int32_t P, const void *w_rows,
+                            const float *x, const float *ln_w, const float *ln_b, const float *bias, const float *resid, const int32_t *dev_state, const float *q,
+                            float *k_slots, float *v_slots, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, float *pmax_val, int32_t *pmax_idx,
+                            int32_t *launched);
+/* A kernel of the SIMD association alone, timed: one untimed launch, then reps in [1, 10000] launches on device memory of arbitrary contents, us_out[i]:
+ * microseconds between two device events around launch i alone.  which 0: matvec_simd_kernel with the residual epilogue at M rows of K values (32 | K) and
+ * N <= 512 columns; which 1: the mat-vec a context in the scalar association launches at the same shape on its five-launch route -- the yardstick; which 2:
+ * attn_simd_kernel with M heads, N query columns under the causal mask, the last of which sees K keys (N <= K <= 1024).  For tools/assoc_bench.py. */
+int biogpt_hip_assoc_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t reps, float *us_out);
 /* One stand-alone run of a stage of the embedding tail (ln_rows_kernel<1024> / <0>, pool_rows_kernel, pool_finish_kernel, head_rows_kernel) over caller-supplied
  * rows, through the launch code of biogpt_hip_hidden / biogpt_hip_embed_batch.  No model, no context; W a multiple of 4.  stage 0 LN: x [n_rows][W], ln_w / ln_b
  * [W]; W == 1024 takes the <1024> template, any other width <0>; seq_states (may be NULL) [n_rows][8] words with slot_div >= 1 and P: row i lands at row
