@@ -833,6 +833,9 @@ SYMBOLS = [
     ("biogpt_hip_float_launches", C.c_int64, [_P]),
     ("biogpt_hip_assoc", C.c_int, [_P, C.c_int]),
     ("biogpt_hip_get_assoc", C.c_int, [_P]),
+    ("biogpt_hip_assoc_chain", C.c_int, [_P, C.c_int]),
+    ("biogpt_hip_get_assoc_chain", C.c_int, [_P]),
+    ("biogpt_hip_simd_chain_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_stamps", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     ("biogpt_hip_generate_launches", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
@@ -934,6 +937,8 @@ SYMBOLS = [
     ("biogpt_hip_fchain_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P]),
     ("biogpt_hip_assoc_device", C.c_int, [C.c_int] + [C.c_int32] * 9 + [_P] * 17),
     ("biogpt_hip_assoc_bench", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P]),
+    ("biogpt_hip_schain_device", C.c_int, [C.c_int] + [C.c_int32] * 12 + [_P] * 16),
+    ("biogpt_hip_schain_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P]),
     ("biogpt_hip_embed_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 4 + [C.c_int32] * 5 + [_P] + [C.c_int32] * 2 + [_P] * 3 + [C.c_int32] + [_P] * 3),
     ("biogpt_hip_tail_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 7 + [C.c_int32] * 2 + [_P] + [C.c_int32] * 3 + [_P] * 5),
     ("biogpt_hip_attn_prefix_device", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
@@ -1236,6 +1241,68 @@ def assoc_bench(which, wtype, M, K, N, reps=9, device=0):
     return us
 
 
+SCHAIN_STAGES = {"Q8": 0, "STAGE": 1, "ATTN": 2}
+
+
+def schain_device(stage, wtype=2, M=0, K=0, N=None, w_rows=None, x=None, ln_w=None, ln_b=None, epi=None, bias=None, resid=None, dev_state=None, seq_states=None,
+                  col_mode=0, shared=0, P=0, k_slots=None, v_slots=None, q=None, H=0, cfg=-1, device=0):
+    """One stand-alone run of a kernel of the SIMD chain (biogpt_hip_schain_device; include/biogpt_hip.h has the inputs of each stage).  stage "Q8": x float32
+    [N, K] (ln_w / ln_b: the LayerNorm in front) -> "q" int8 [N + 1, K], "d" float32 and "s" uint32 [N + 1, K / 32].  "STAGE": the producer, then the linear
+    stage at tile shape cfg (-1: the launch's choice): w_rows (uint8 bytes of M rows in the file's format), x [N, K], epi by name (WIDE_EPIS), bias, resid, for QKV
+    dev_state or seq_states [N, 8] (+ col_mode), P and k_slots / v_slots [n_slots, K / 64, P, 64] -> "out" float32 [cols, ldo] ([cols, K] for QKV), "k" / "v".
+    "ATTN": q [N, H * 64], k_slots / v_slots [n_slots, H, P, 64], seq_states [N, 8], col_mode, shared -> "out" [N + 1, H * 64].  Outputs come back WHOLE, guard
+    rows and columns included and preset to 0xff bytes; "launched" as the header lists it.  Raises BiogptError on a refusal."""
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    st = SCHAIN_STAGES[stage] if isinstance(stage, str) else int(stage)
+    if N is None:
+        N = int(np.shape(q if st == 2 else x)[0])
+    M, K, N, H, P = int(M), int(K), int(N), int(H), int(P)
+    res, n_slots = {}, 0
+    if st == 0:
+        res["q"], res["d"], res["s"] = np.zeros((N + 1, max(K, 0)), np.int8), np.zeros((N + 1, max(K, 0) // 32), np.float32), np.zeros((N + 1, max(K, 0) // 32), np.uint32)
+    elif st == 1:
+        cols, ldo = ((max(N, 0) + 31) & ~31) + 1, ((max(M, 0) + 63) & ~63) + 16
+        res["out"] = np.zeros((cols, max(K, 0) if epi == "QKV" else ldo), np.float32)
+        if epi == "QKV" and k_slots is not None and v_slots is not None:
+            res["k"], res["v"] = np.array(k_slots, dtype=np.float32, order="C"), np.array(v_slots, dtype=np.float32, order="C")
+            n_slots = res["k"].shape[0]
+            assert res["k"].shape == res["v"].shape == (n_slots, K // 64, P, 64)
+    else:
+        res["out"] = np.zeros((max(N, 0) + 1, max(H, 0) * 64), np.float32)
+        if k_slots is not None:
+            n_slots = int(np.shape(k_slots)[0])
+    launched = np.zeros(8, np.int32)
+    o = lambda name: res[name].ctypes.data if name in res else None
+    kv = (o("k"), o("v")) if st == 1 else (ptr(k_slots, np.float32), ptr(v_slots, np.float32))
+    rc = lib().biogpt_hip_schain_device(int(device), st, int(wtype), WIDE_EPIS[epi] if isinstance(epi, str) else int(epi or 0), M, K, N, int(cfg), H, P, n_slots,
+                                        int(col_mode), int(shared), ptr(w_rows, np.uint8), ptr(x, np.float32), ptr(ln_w, np.float32), ptr(ln_b, np.float32),
+                                        ptr(bias, np.float32), ptr(resid, np.float32), ptr(dev_state, np.int32), ptr(seq_states, np.int32), ptr(q, np.float32),
+                                        kv[0], kv[1], o("out"), o("q"), o("d"), o("s"), launched.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    res["launched"] = launched
+    return res
+
+
+def schain_bench(which, wtype, M, K, N, cfg=-1, reps=9, device=0):
+    """A linear stage of the SIMD association alone, timed (biogpt_hip_schain_bench): microseconds of `reps` launches, float32 [reps].  which "stage": the SIMD
+    chain's stage with the residual epilogue at tile shape cfg (-1: the launch's choice); "q8": its producer; "matvec": the SIMD mat-vec of a context's own pass at
+    N columns; "wide": the scalar association's matrix-core stage (for scale)."""
+    us = np.zeros(int(reps), np.float32)
+    if lib().biogpt_hip_schain_bench(int(device), {"stage": 0, "q8": 1, "matvec": 2, "wide": 3}[which], int(wtype), int(M), int(K), int(N), int(cfg), int(reps),
+                                     us.ctypes.data) != 0:
+        raise BiogptError(_err())
+    return us
+
+
 EMBED_STAGES = {"LN": 0, "POOL": 1, "HEAD": 2}
 EMBED_POOLING = {"none": 0, "last": 1, "mean": 2}
 
@@ -1521,9 +1588,10 @@ class BiogptModel:
 
     # -- biogpt_model_load (biogpt.h:128-132) --
     @classmethod
-    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None):
+    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None, assoc_chain=None):
         """float_chain=True: switch the float chain on behind the load (float_chain(); an F32 / F16 file with head size 64 only -- anything else raises).
-        assoc="scalar" | "simd": set the association behind the load (set_assoc(); None: the default, scalar unless BIOGPT_HIP_ASSOC=1)."""
+        assoc="scalar" | "simd": set the association behind the load (set_assoc(); None: the default, scalar unless BIOGPT_HIP_ASSOC=1).
+        assoc_chain=True | False: set the SIMD chain's switch behind the load (set_assoc_chain(); None: the default, off unless BIOGPT_HIP_ASSOC_CHAIN=1)."""
         if arena is None:
             m = cls(lib().biogpt_hip_load(os.fsencode(fname), device, verbosity))
         else:
@@ -1533,6 +1601,8 @@ class BiogptModel:
                 m.float_chain(True)
             if assoc is not None:
                 m.set_assoc(assoc)
+            if assoc_chain is not None:
+                m.set_assoc_chain(assoc_chain)
         except BiogptError:
             m.close()
             raise
@@ -2252,7 +2322,8 @@ class BiogptModel:
 
     def chain_kind(self):
         """Which many-column layer chain the file has (biogpt_hip_chain_kind): 0 none, 1 the BioGPT-base chain, 2 the wide chain (any other block-quantized file
-        with head size 64, d_model a multiple of 64 and d_ff of 32), 3 the float chain (an F32 / F16 file of those widths while float_chain() is on)."""
+        with head size 64, d_model a multiple of 64 and d_ff of 32), 3 the float chain (an F32 / F16 file of those widths while float_chain() is on), 4 the SIMD chain (a context in
+        the "simd" association while assoc_chain is on; such a context is 0 otherwise)."""
         k = int(lib().biogpt_hip_chain_kind(self._h))
         if k < 0:
             raise BiogptError(_err())
@@ -2280,6 +2351,25 @@ class BiogptModel:
         if k < 0:
             raise BiogptError(_err())
         return "simd" if k == 1 else "scalar"
+
+    def set_assoc_chain(self, on=True):
+        """The SIMD chain's switch (biogpt_hip_assoc_chain): on, a context in the "simd" association serves the batched calls the wide chain serves (score_batch,
+        embed_batch, score_continuations, generate_greedy_batch, generate_sample, generate_beam(_batch), the plain generate_queue) in that association, and
+        chain_kind() is 4; in the "scalar" association the switch changes nothing.  Raises BiogptError with the reason where the file cannot have it."""
+        if lib().biogpt_hip_assoc_chain(self._h, 1 if on else 0) != 0:
+            raise BiogptError(_err())
+
+    @property
+    def assoc_chain(self):
+        """Whether the SIMD chain's switch is on (biogpt_hip_get_assoc_chain)."""
+        k = int(lib().biogpt_hip_get_assoc_chain(self._h))
+        if k < 0:
+            raise BiogptError(_err())
+        return k == 1
+
+    def simd_chain_launches(self):
+        """Linear-stage launches of the SIMD chain (biogpt_hip_simd_chain_launches); 0 while the switch is off."""
+        return int(lib().biogpt_hip_simd_chain_launches(self._h))
 
     def float_launches(self):
         """Linear-stage launches of the float chain (biogpt_hip_float_launches); 0 while the switch is off."""

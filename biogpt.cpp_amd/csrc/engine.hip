@@ -207,7 +207,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -239,6 +239,7 @@ struct EngineOptions {
         prefix_attn = get("BIOGPT_HIP_PREFIX_ATTN", -1);          // decode steps behind a shared prefix: -1 attn_prefix_kernel where it was measured faster (PREFIX_ATTN_MIN_*), 0 never, 1 always (A/B arms)
         run_attn = get("BIOGPT_HIP_RUN_ATTN", -1);                // the passes of biogpt_hip_score_continuations_batch (no other call looks at it): -1 attn_runs_kernel where it was measured faster (RUN_ATTN_MIN_*), 0 never, 1 in every pass of up to 1024 keys (A/B arms)
         float_chain = get("BIOGPT_HIP_FLOAT_CHAIN", 0);          // 1: a new context of an F32 / F16 file the float chain serves starts with it switched on (biogpt_hip_float_chain; kernels_fchain.hip.h)
+        assoc_chain = get("BIOGPT_HIP_ASSOC_CHAIN", 0);            // 1: a new context of a file the SIMD association serves starts with the SIMD chain switched on (biogpt_hip_assoc_chain; kernels_schain.hip.h)
         assoc = get("BIOGPT_HIP_ASSOC", 0);                        // 1: a new context of a file the SIMD association serves starts in it (biogpt_hip_assoc; kernels_assoc.hip.h)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
     }
@@ -390,6 +391,8 @@ struct biogpt_hip_ctx {
     bool float_chain = false;              // the float chain is switched on (biogpt_hip_float_chain): passes over column states of this F32 / F16 file run on kernels_fchain.hip.h
     int64_t float_launches = 0;            // linear-stage launches of the float chain (biogpt_hip_float_launches)
     int assoc = 0;                         // 1: the SIMD association (biogpt_hip_assoc): every pass on the five-launch layer with the kernels of kernels_assoc.hip.h; no call over column states
+    bool assoc_chain = false;              // the SIMD chain is switched on (biogpt_hip_assoc_chain): while assoc == 1, passes over column states run on kernels_schain.hip.h; nothing while assoc == 0
+    int64_t simd_chain_launches = 0;       // linear-stage launches of the SIMD chain (biogpt_hip_simd_chain_launches)
     int32_t gen_launch_tokens[16] = {0}; int gen_launches = 0;   // the last biogpt_hip_generate_greedy: tokens of each multi-token pipelined launch (biogpt_hip_generate_launches)
     int32_t prefix_stats[4] = {0, 0, 0, 0};   // of the last biogpt_hip_generate_*_prefix call that generated tokens: shared rows, prompt columns evaluated, path (0 in place, 1 copied), columns
     int xc_batch = 0;                      // a column generation call with 2 .. 8 columns holds the device's pipeline slot (choose_column_path): its decode steps run as column-per-XCD launches (streams mode)
@@ -624,7 +627,8 @@ extern "C" int bg_wide_quantize(const float *x, int ldx, int K, int N, const flo
 // Which many-column layer chain a file has (biogpt_hip_chain_kind).  1: BioGPT-base widths, every launch as before.  2: the wide chain -- any other block-quantized
 // file with head size 64 whose widths the kernel's tiles divide; passes over column states only, the context's own columns stay on the generic kernels.
 // 3: the float chain -- an F32 / F16 file with the wide chain's widths, and only while its context has it switched on (chain_kind; biogpt_hip_float_chain).
-enum ChainKind : int { CHAIN_NONE = 0, CHAIN_BASE = 1, CHAIN_WIDE = 2, CHAIN_FLOAT = 3 };
+// 4: the SIMD chain -- a context in the SIMD association (biogpt_hip_assoc, mode 1) while it has the chain switched on (biogpt_hip_assoc_chain).
+enum ChainKind : int { CHAIN_NONE = 0, CHAIN_BASE = 1, CHAIN_WIDE = 2, CHAIN_FLOAT = 3, CHAIN_SIMD = 4 };
 inline int chain_kind_of(const biogpt_hip_hparams &hp) {
     if (!is_quantized(ftype_to_type(hp.ftype)) || hp.n_head < 1 || hp.d_model % hp.n_head != 0 || hp.d_model / hp.n_head != 64) return CHAIN_NONE;
     if (hp.d_model == 1024 && hp.d_ff == 4096) return CHAIN_BASE;
@@ -654,8 +658,16 @@ inline const char *assoc_refusal(const biogpt_hip_hparams &hp) {
     if (hp.d_model % 32 != 0 || hp.d_ff < 32 || hp.d_ff % 32 != 0) return "d_model or d_ff no multiple of 32";
     return nullptr;
 }
-// the chain a CONTEXT's calls over column states run on: the file's, or the float chain while it is switched on; none in the SIMD association
-inline int chain_kind(const biogpt_hip_ctx *c) { return c->assoc ? CHAIN_NONE : c->float_chain ? CHAIN_FLOAT : chain_kind_of(c->hp); }
+// the SIMD chain (kernels_schain.hip.h, schain_tu.hip): the Q8 producer, the many-column linear stage and the attention over column states of a context in the
+// SIMD association.  cfg: a tile shape, -1 the launch's own choice; report: null, or five words (threads, grid x, grid y, LDS bytes, cfg) / four for the other two
+extern "C" int bg_schain_launch(int wt, int epi, const void *params, size_t params_bytes, int cfg, hipStream_t st, int32_t *report);
+extern "C" int bg_schain_q8(int q81, const float *x, int ldx, int K, int N, const float *ln_w, const float *ln_b, float eps, int8_t *oq, float *od, uint32_t *os,
+                            hipStream_t st, int32_t *report);
+extern "C" int bg_schain_attn(const void *params, size_t params_bytes, int shared, int H, int N, hipStream_t st, int32_t *report);
+extern "C" int bg_schain_cfg(int M, int N);
+// the chain a CONTEXT's calls over column states run on: the file's, or the float chain while it is switched on; in the SIMD association the SIMD chain while
+// that is switched on, else none
+inline int chain_kind(const biogpt_hip_ctx *c) { return c->assoc ? (c->assoc_chain ? CHAIN_SIMD : CHAIN_NONE) : c->float_chain ? CHAIN_FLOAT : chain_kind_of(c->hp); }
 template <int WT>
 hipError_t launch_chain_mfma(ChainOp op, const bgk::MatvecParams &p, const bgk::DevMatrix &img, hipStream_t st, ChainLaunch *rep) {
     int site = -1;
@@ -1345,6 +1357,7 @@ struct PassLaunch {
     bool wchain;                    // the wide chain: a pass over column states of a block-quantized file that is not BioGPT-base (kernels_mfma_wide.hip.h)
     bool fchain;                    // the float chain: a pass over column states of an F32 / F16 file whose context has it switched on (kernels_fchain.hip.h)
     bool simd;                      // the context is in the SIMD association: the generic sites launch the kernels of kernels_assoc.hip.h
+    bool schain;                    // the SIMD chain: a pass over column states of a context in the SIMD association that has it switched on (kernels_schain.hip.h)
     int q81;
     const bgk::SeqState *seq;       // column states of a pass over the per-sequence caches (null: the context's own columns)
     int col_mode;                   // 1: packed columns
@@ -1388,6 +1401,16 @@ struct PassLaunch {
         p.x = x; p.ldx = (int32_t)m.K;
         const hipError_t e = (hipError_t)bg_fchain_launch(m.type, epi, &p, sizeof(p), -1, st, nullptr);
         if (e == hipSuccess) c->float_launches++;
+        return e;
+    }
+    // The SIMD chain's stage: the N columns' Q8 blocks in the SIMD association's form into side buffer `slot` by ONE producer launch (LayerNorm first when ln_w
+    // is given), then schain_kernel on the arena's own block rows.  x: the f32 rows [N][W.K] the stage reads
+    hipError_t simd_stage(int epi, bgk::MatvecParams &p, const MatSlot &m, const float *x, int slot, const float *ln_w = nullptr, const float *ln_b = nullptr) {
+        hipError_t e = (hipError_t)bg_schain_q8(q81, x, (int)m.K, (int)m.K, p.N, ln_w, ln_b, 1e-5f, c->aq_q[slot], c->aq_d[slot], c->aq_s[slot], st, nullptr);
+        if (e != hipSuccess) return e;
+        p.aq_q = c->aq_q[slot]; p.aq_d = c->aq_d[slot]; p.aq_s = c->aq_s[slot];
+        e = (hipError_t)bg_schain_launch(m.type, epi, &p, sizeof(p), -1, st, nullptr);
+        if (e == hipSuccess) c->simd_chain_launches++;
         return e;
     }
 };
@@ -1541,6 +1564,10 @@ bool enqueue_attention(PassLaunch &k, int l) {
         launch_attn_simd(a, H, N, st);
         return true;
     }
+    if (k.schain) {    // (likewise; the columns' slots, counts and shared rows are the column states')
+        HIP_TRY(false, (hipError_t)bg_schain_attn(&a, sizeof(a), k.pass.shared_prefix ? 1 : 0, H, N, st, nullptr));
+        return true;
+    }
     if (!(dk == 64 && t_max <= 1024)) {
         launch_attn_generic(a, H, N, k.attn_threads, st);
         return true;
@@ -1587,7 +1614,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.vcache = k.vroot + (size_t)l * P * D;
         if (k.seq) { p.seq = k.seq; p.col_mode = k.col_mode; p.kv_seq_stride = k.seq_stride; }
         p.q_scale = 1.0f / sqrtf((float)k.dk);
-        if (k.fchain) {
+        if (k.schain) {
+            HIP_TRY(false, k.simd_stage(bgk::EPI_QKV, p, L.qkv, c->x, 2, p.ln_w, p.ln_b));
+        } else if (k.fchain) {
             HIP_TRY(false, k.float_stage(bgk::EPI_QKV, p, L.qkv, c->x, p.ln_w, p.ln_b));
         } else if (k.wchain) {
             HIP_TRY(false, k.wide_stage(bgk::EPI_QKV, p, L.qkv, c->x, 2, p.ln_w, p.ln_b));
@@ -1606,7 +1635,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.x = c->att; p.ldx = D; p.N = N;
         p.bias = dev_vec(c, L.o_b);
         p.resid = c->x; p.ldr = D; p.out = c->x1; p.ldo = D;
-        if (k.fchain) {
+        if (k.schain) {
+            HIP_TRY(false, k.simd_stage(bgk::EPI_RESID, p, L.o, c->att, 0));
+        } else if (k.fchain) {
             HIP_TRY(false, k.float_stage(bgk::EPI_RESID, p, L.o, c->att));
         } else if (k.wchain) {      // (the attention kernels wrote f32 rows: no Q8 side output without the base chain)
             HIP_TRY(false, k.wide_stage(bgk::EPI_RESID, p, L.o, c->att, 0));
@@ -1624,7 +1655,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.ln_w = dev_vec(c, L.ln1_w); p.ln_b = dev_vec(c, L.ln1_b);
         p.bias = dev_vec(c, L.fc1_b);
         p.out = c->h; p.ldo = F;
-        if (k.fchain) {
+        if (k.schain) {
+            HIP_TRY(false, k.simd_stage(bgk::EPI_GELU, p, L.fc1, c->x1, 2, p.ln_w, p.ln_b));
+        } else if (k.fchain) {
             HIP_TRY(false, k.float_stage(bgk::EPI_GELU, p, L.fc1, c->x1, p.ln_w, p.ln_b));
         } else if (k.wchain) {
             HIP_TRY(false, k.wide_stage(bgk::EPI_GELU, p, L.fc1, c->x1, 2, p.ln_w, p.ln_b));
@@ -1646,7 +1679,9 @@ bool enqueue_layer(PassLaunch &k, int l) {
         p.x = c->h; p.ldx = F; p.N = N;
         p.bias = dev_vec(c, L.fc2_b);
         p.resid = c->x1; p.ldr = D; p.out = c->x; p.ldo = D;
-        if (k.fchain) {
+        if (k.schain) {
+            HIP_TRY(false, k.simd_stage(bgk::EPI_RESID, p, L.fc2, c->h, 1));
+        } else if (k.fchain) {
             HIP_TRY(false, k.float_stage(bgk::EPI_RESID, p, L.fc2, c->h));
         } else if (k.wchain) {
             HIP_TRY(false, k.wide_stage(bgk::EPI_RESID, p, L.fc2, c->h, 1));
@@ -1719,6 +1754,12 @@ bool enqueue_final(PassLaunch &k) {
     const MatSlot &m = c->plan.lm_head;
     const MvShape s = mv_shape(m.type, m.M, m.K);
     bgk::MatvecParams p = mv_base(c, m, s);
+    if (rows == Rows::All && k.schain) {  // the SIMD chain: LayerNorm + Q8 of the columns that get a row, once, then the lm_head stage (any n_vocab)
+        const int head_from = k.pass.head_from;
+        p.N = N - head_from; p.out = c->logits_all; p.ldo = V;
+        HIP_TRY(false, k.simd_stage(bgk::EPI_LOGITS, p, m, c->x + (size_t)head_from * D, 2, dev_vec(c, c->plan.ln_w), dev_vec(c, c->plan.ln_b)));
+        return true;
+    }
     if (rows == Rows::All && k.fchain) {  // the float chain: LayerNorm of the columns that get a row, once, then the lm_head stage (any n_vocab)
         const int head_from = k.pass.head_from;
         p.N = N - head_from; p.out = c->logits_all; p.ldo = V;
@@ -1784,20 +1825,23 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     // single-token fast chain: BioGPT-base shapes, block-quantized weights -> producer-side Q8 hand-offs
     const int32_t wt = ftype_to_type(hp.ftype);
     // the SIMD association: the context's own columns on the five launches per layer, no chain; the calls over column states were refused at their entry
-    k.simd = c->assoc != 0;
+    // (with the SIMD chain switched on, the passes over column states run on kernels_schain.hip.h: the same association on many columns)
+    k.schain = c->assoc != 0 && batch && chain_kind(c) == CHAIN_SIMD;
+    k.simd = c->assoc != 0 && !k.schain;
     if (k.simd && batch) BG_FAIL(false, "internal: a pass over column states reached a context in the SIMD association");
-    if (k.simd && (k.dk != 64 || t_max > bgk::SIMD_ATTN_MAXT))
+    if (k.schain && (pass.rows == Rows::Last || pass.rows == Rows::AllGeneric)) BG_FAIL(false, "internal: a SIMD chain pass with rows it does not serve");
+    if (c->assoc != 0 && (k.dk != 64 || t_max > bgk::SIMD_ATTN_MAXT))
         BG_FAIL(false, "the SIMD association serves head size 64 and contexts of up to %d tokens (got head size %d, %d tokens)", bgk::SIMD_ATTN_MAXT, k.dk, t_max);
-    k.chain = !k.simd && is_quantized(wt) && k.D == 1024 && k.F == 4096 && k.dk == 64 && t_max <= 1024;
+    k.chain = c->assoc == 0 && is_quantized(wt) && k.D == 1024 && k.F == 4096 && k.dk == 64 && t_max <= 1024;
     k.pchain = k.chain && (N > 1 || batch);   // several columns: LayerNorm+Q8 once per site (lnq_kernel), 8 columns per workgroup
     // enough columns to fill 16-wide MFMA tiles: the chain runs on the int8 matrix cores from the row-tiled weight image
     k.mfma = k.pchain && N >= (pass.cols == Cols::PerSequence ? MFMA_MIN_DECODE_COLS : MFMA_MIN_PASS_COLS) && c->tile_img != nullptr;
     // a pass over column states of any other block-quantized file with head size 64: the wide chain (the context's own columns stay on the generic kernels)
-    k.wchain = !k.chain && batch && chain_kind_of(hp) == CHAIN_WIDE && t_max <= 1024;
+    k.wchain = !k.chain && !k.schain && batch && chain_kind_of(hp) == CHAIN_WIDE && t_max <= 1024;
     // a pass over column states of a float file whose context has the float chain switched on (the context's own columns stay on fdec_kernel / matvec_kernel)
     k.fchain = !k.chain && !k.wchain && batch && chain_kind(c) == CHAIN_FLOAT && t_max <= 1024;
     if (k.fchain && (pass.rows == Rows::Last || pass.rows == Rows::AllGeneric)) BG_FAIL(false, "internal: a float fast chain pass with rows it does not serve");
-    if (batch && !k.chain && !k.wchain && !k.fchain)
+    if (batch && !k.chain && !k.wchain && !k.fchain && !k.schain)
         BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64) or the wide one (block-quantized weights, head size 64, d_model a multiple of 64, d_ff of 32)");
     if (k.wchain && (c->tile_img == nullptr || pass.rows == Rows::Last || pass.rows == Rows::AllGeneric))
         BG_FAIL(false, "internal: a wide fast chain pass without its row-tiled weight image, or with rows it does not serve");
@@ -2089,6 +2133,7 @@ biogpt_hip_ctx *load_impl(const char *fname, int device, int verbosity, void *ex
     c->hp = mf.hp;
     c->float_chain = c->opt.float_chain == 1 && float_chain_refusal(c->hp) == nullptr;      // (the environment's default holds where the file can have it)
     c->assoc = (c->opt.assoc == 1 && assoc_refusal(c->hp) == nullptr) ? 1 : 0;      // (likewise BIOGPT_HIP_ASSOC)
+    c->assoc_chain = c->opt.assoc_chain == 1 && assoc_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_ASSOC_CHAIN)
     c->device = device;
     c->n_tensors = (int)mf.tensors.size();
     c->vocab = mf.vocab;
@@ -2199,6 +2244,7 @@ biogpt_hip_ctx *biogpt_hip_attach(const biogpt_hip_hparams *hp, int device, void
     c->hp = *hp;
     c->float_chain = c->opt.float_chain == 1 && float_chain_refusal(c->hp) == nullptr;
     c->assoc = (c->opt.assoc == 1 && assoc_refusal(c->hp) == nullptr) ? 1 : 0;
+    c->assoc_chain = c->opt.assoc_chain == 1 && assoc_refusal(c->hp) == nullptr;
     c->device = device;
     c->pos_rows = (int64_t)hp->n_positions + 2;
     c->plan = plan_arena(*hp, c->pos_rows);
@@ -2767,6 +2813,36 @@ int biogpt_hip_get_assoc(const biogpt_hip_ctx *ctx) {
     if (!ctx) BG_FAIL(-1, "null context");
     return ctx->assoc;
 }
+// The SIMD chain's switch: a property of the context that takes effect only while it is in the SIMD association.  Off (the default), a context in mode 1 is what
+// it was: no call over column states.  In mode 0 the switch is inert -- no launch, no check and no message looks at it.  The captured column steps bake the
+// route: dropped.
+int biogpt_hip_assoc_chain(biogpt_hip_ctx *ctx, int on) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (on != 0 && on != 1) BG_FAIL(-1, "on must be 0 or 1 (got %d)", on);
+    if (session_refuses(ctx)) return -1;
+    {
+        std::lock_guard<std::mutex> lk(g_xp_mu);
+        if (ctx->xp_in_call) BG_FAIL(-1, "the SIMD chain cannot be switched while a call of this context is running");
+    }
+    if (on) {
+        if (const char *why = assoc_refusal(ctx->hp))
+            BG_FAIL(-1, "the SIMD chain cannot be switched on for this file: it is %s (like the SIMD association it needs Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 weights, head size 64, d_model and d_ff multiples of 32; got ftype %d, d_model %d, d_ff %d, %d heads)", why, ctx->hp.ftype, ctx->hp.d_model, ctx->hp.d_ff, ctx->hp.n_head);
+    }
+    if (ctx->assoc_chain == (on == 1)) return 0;
+    if (ctx->ready) {
+        HIP_TRY(-2, hipSetDevice(ctx->device));
+        HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    }
+    drop_column_graphs(ctx);
+    ctx->assoc_chain = on == 1;
+    return 0;
+}
+int biogpt_hip_get_assoc_chain(const biogpt_hip_ctx *ctx) {
+    if (!ctx) BG_FAIL(-1, "null context");
+    return ctx->assoc_chain ? 1 : 0;
+}
+int64_t biogpt_hip_simd_chain_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->simd_chain_launches : -1; }
 int biogpt_hip_fpipe_stamps(biogpt_hip_ctx *ctx, uint64_t *out, int n) {
     if (!ctx || !out || n < 0 || ctx->fp_state != 1 || !ctx->opt.fpipe_stamps) return -1;
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
@@ -2984,12 +3060,16 @@ static bool check_prompts(const biogpt_hip_ctx *c, const int32_t *prompts, const
 // here, before any capture -- it has no kernel to fall back to, so an image that does not fit is the call's error.
 // A context in the SIMD association serves the single-sequence calls: every call over column states is refused by its name, before any launch
 static bool assoc_refuses(const biogpt_hip_ctx *c, const char *what) {
-    if (c->assoc) BG_FAIL(true, "%s runs over column states, which the SIMD association does not serve (biogpt_hip_assoc(ctx, 0) switches the context back to the scalar association)", what);
+    if (c->assoc && !c->assoc_chain) BG_FAIL(true, "%s runs over column states, which the SIMD association does not serve (biogpt_hip_assoc(ctx, 0) switches the context back to the scalar association)", what);
     return false;
 }
 static bool check_fast_chain(biogpt_hip_ctx *c, const char *what, bool wide_ok = false) {
     if (assoc_refuses(c, what)) return false;
     const int kind = chain_kind(c);
+    if (kind == CHAIN_SIMD) {       // (nothing to build either)
+        if (!wide_ok) BG_FAIL(false, "%s needs the BioGPT-base fast chain in the scalar association: the SIMD chain switched on for this context (biogpt_hip_assoc_chain) does not serve it (biogpt_hip_assoc(ctx, 0) switches the context back to the scalar association)", what);
+        return true;
+    }
     if (kind == CHAIN_FLOAT) {      // (nothing to build: the stage reads the arena's own rows)
         if (!wide_ok) BG_FAIL(false, "%s needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096): the float fast chain switched on for this %s file does not serve it", what, ftype_to_type(c->hp.ftype) == T_F16 ? "F16" : "F32");
         return true;
@@ -3013,9 +3093,9 @@ static bool begin_column_call(biogpt_hip_ctx *ctx, int n_slots, int n_seqs, long
     if (!ensure_seq_caches(ctx, n_slots)) return false;
     // matrix-core chain: decode steps have n_seqs columns, the prompt pass all prompt tokens; build the tiled weights before any graph capture
     // (a wide file has no other many-column kernel: always, and an image that does not fit is the call's error)
-    const bool wide = chain_kind_of(ctx->hp) == CHAIN_WIDE;
-    // (a float file has no image at all: the float chain reads the arena's own rows)
-    const bool quant = is_quantized(ftype_to_type(ctx->hp.ftype));
+    // (a float file has no image at all: the float chain reads the arena's own rows; so does the SIMD chain)
+    const bool wide = chain_kind_of(ctx->hp) == CHAIN_WIDE && chain_kind(ctx) != CHAIN_SIMD;
+    const bool quant = is_quantized(ftype_to_type(ctx->hp.ftype)) && chain_kind(ctx) != CHAIN_SIMD;
     if (quant && (wide || std::max<long>(n_seqs, total) >= MFMA_MIN_DECODE_COLS) && !ensure_tile_images(ctx)) return false;
     if (wide && ctx->tile_img == nullptr) BG_FAIL(false, "no device memory for the row-tiled weight image the wide fast chain needs");
     return ensure_logits_rows(ctx, (size_t)n_seqs);
@@ -3053,7 +3133,7 @@ static bool upload_column_starts(biogpt_hip_ctx *ctx, const int32_t *prompts, co
 // 2 .. 8 columns: the steps as column-per-XCD launches while this call holds the device's pipeline slot.  Decided ONCE per call, before any capture: a
 // graph is replayed only in the state it was captured for.  Returns the choice (0 | 1), which is also ctx->xc_batch until the call's XcBatchScope ends.
 static int choose_column_path(biogpt_hip_ctx *ctx, int n_seqs, int max_len) {
-    ctx->xc_batch = (n_seqs >= 2 && n_seqs <= 8 && max_len + 1 <= 256 && xcols_prepare(ctx, n_seqs, std::min(256, max_len + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
+    ctx->xc_batch = (chain_kind(ctx) != CHAIN_SIMD && n_seqs >= 2 && n_seqs <= 8 && max_len + 1 <= 256 && xcols_prepare(ctx, n_seqs, std::min(256, max_len + 1)) && xpipe_usable(ctx, 256)) ? 1 : 0;
     return ctx->xc_batch;
 }
 

@@ -1998,3 +1998,155 @@ int biogpt_hip_assoc_bench(int device, int32_t which, int32_t wtype, int32_t M, 
     HIP_TRY(-2, hipDeviceSynchronize());
     return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
 }
+
+// ---- the kernels of the SIMD chain alone (kernels_schain.hip.h), through the launch functions PassLaunch::simd_stage and enqueue_attention use ----
+// stage 0 Q8: the producer (bg_schain_q8) over x [N][K], behind the LayerNorm when ln_w / ln_b are given: out_q [N + 1][K] codes, out_d [N + 1][K / 32] the
+//   scale the dot reads (through f16 for the Q8_0 form), out_s [N + 1][K / 32] words.  wtype names the weight format whose activation form it is.
+// stage 1 STAGE: the producer, then one launch of schain_kernel<wtype, epi> (bg_schain_launch) at tile shape cfg (0 .. 2; -1: the launch's own choice) -- a
+//   linear stage as a pass enqueues it.  epi 0 QKV (M == 3 K, 64 | K; exactly one of dev_state and seq_states (+ col_mode) names the column states; k_slots /
+//   v_slots [n_slots][K / 64][P][64], updated in place; out = the q rows [cols][K]), 1 RESID (bias, resid [N][M]), 2 GELU (bias), 3 LOGITS; any M.  out but for
+//   QKV: [cols][ldo]; cols = N rounded up to 32, plus one guard column; ldo = M rounded up to 64, plus 16 guard rows.
+// stage 2 ATTN: attn_simd_cols_kernel (bg_schain_attn) over q [N][H * 64], k_slots / v_slots [n_slots][H][P][64] and seq_states [N]: column i reads slot i
+//   (col_mode 0, n_past + 1 keys) or slot seq_id (col_mode 1, t_vis keys); shared 1: its rows j < pad[0] come from slot pad[1].  out [N + 1][H * 64].
+// The outputs come back WHOLE as allocated and preset to 0xff bytes.  launched [8]: stage 0 / 2: threads, grid x, grid y, LDS bytes; stage 1: threads, grid x,
+// grid y, static LDS bytes, cols, ldo, cfg, columns of a tile.  Every refusal comes before any HIP call.
+int biogpt_hip_schain_device(int device, int32_t stage, int32_t wtype, int32_t epi, int32_t M, int32_t K, int32_t N, int32_t cfg, int32_t H, int32_t P, int32_t n_slots,
+                             int32_t col_mode, int32_t shared, const void *w_rows, const float *x, const float *ln_w, const float *ln_b, const float *bias,
+                             const float *resid, const int32_t *dev_state, const int32_t *seq_states, const float *q, float *k_slots, float *v_slots, float *out,
+                             int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched) {
+    clear_error();
+    if (stage < 0 || stage > 2) BG_FAIL(-1, "stage %d is no stage (0 Q8, 1 STAGE, 2 ATTN)", stage);
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (stage == 2) {
+        if (H < 1 || H > 64) BG_FAIL(-1, "H must be in [1, 64]");
+        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+        if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
+        if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
+        if (shared != 0 && shared != 1) BG_FAIL(-1, "shared must be 0 or 1");
+        if (!q || !k_slots || !v_slots || !seq_states || !out) BG_FAIL(-1, "q, k_slots, v_slots, seq_states or out is NULL");
+        const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
+        for (int i = 0; i < N; i++) {
+            const int T = col_mode ? hs[i].t_vis : hs[i].n_past + 1;
+            if (T < 1 || T > bgk::SIMD_ATTN_MAXT) BG_FAIL(-1, "column %d sees T = %d keys: the kernel holds 1 .. %d", i, T, bgk::SIMD_ATTN_MAXT);
+            if (T > P) BG_FAIL(-1, "column %d sees %d keys of a table of P = %d rows", i, T, P);
+            if (!probe_slot_ok(__func__, i, col_mode ? hs[i].seq_id : i, n_slots)) return -1;
+            if (shared && (hs[i].pad[0] < 0 || hs[i].pad[0] > P)) BG_FAIL(-1, "column %d: %d shared rows outside [0, P]", i, hs[i].pad[0]);
+            if (shared && (hs[i].pad[1] < 0 || hs[i].pad[1] >= n_slots)) BG_FAIL(-1, "column %d: shared slot %d outside [0, n_slots)", i, hs[i].pad[1]);
+        }
+        HIP_TRY(-2, hipSetDevice(device));
+        const size_t D = (size_t)H * 64, kv_b = (size_t)n_slots * H * P * 64 * 4;
+        ProbeImage im;      // [K | V | q | column states | exp table | out], one guard row
+        const ProbePart o_k = im.in(k_slots, kv_b), o_v = im.in(v_slots, kv_b), o_q = im.in(q, (size_t)N * D * 4), o_st = im.in(seq_states, sizeof(bgk::SeqState) * (size_t)N);
+        const ProbePart o_ds = im.in(PROBE_NO_STATE, sizeof(bgk::DevState)), o_tab = im.own(exp_table_f16()), o_out = im.out((size_t)(N + 1) * D * 4);
+        if (!im.upload()) return -2;
+        bgk::AttnParams a{};
+        a.q = im.at<const float>(o_q); a.kcache = im.at<const float>(o_k); a.vcache = im.at<const float>(o_v); a.out = im.at<float>(o_out);
+        a.st = im.at<const bgk::DevState>(o_ds); a.exp_tab = im.at<const uint16_t>(o_tab);
+        a.seq = im.at<const bgk::SeqState>(o_st); a.col_mode = col_mode; a.kv_seq_stride = (int64_t)H * P * 64;
+        a.N = N; a.D = (int32_t)D; a.dk = 64; a.P = P;
+        int32_t four[4] = {0, 0, 0, 0};
+        HIP_TRY(-2, (hipError_t)bg_schain_attn(&a, sizeof(a), shared, H, N, 0, four));
+        HIP_TRY(-2, hipDeviceSynchronize());
+        report_launch(launched, {four[0], four[1], four[2], four[3]});
+        return im.read(o_out, out) ? 0 : -2;
+    }
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (!x) BG_FAIL(-1, "x is NULL");
+    if ((ln_w != nullptr) != (ln_b != nullptr)) BG_FAIL(-1, "ln_w and ln_b come together");
+    const int q81 = (wtype == T_Q4_1 || wtype == T_Q5_1) ? 1 : 0;
+    const size_t bpr = (size_t)K / QK;
+    if (stage == 0) {
+        if (!out_q || !out_d || !out_s) BG_FAIL(-1, "out_q, out_d or out_s is NULL");
+        HIP_TRY(-2, hipSetDevice(device));
+        ProbeImage im;      // [x | gain | bias of the LayerNorm | codes | d | s], one guard row each
+        const ProbePart o_x = im.in(x, (size_t)N * K * 4), o_lw = im.in(ln_w, (size_t)K * 4), o_lb = im.in(ln_b, (size_t)K * 4);
+        const ProbePart o_q = im.out((size_t)(N + 1) * K), o_d = im.out((size_t)(N + 1) * bpr * 4), o_s = im.out((size_t)(N + 1) * bpr * 4);
+        if (!im.upload()) return -2;
+        int32_t four[4] = {0, 0, 0, 0};
+        HIP_TRY(-2, (hipError_t)bg_schain_q8(q81, im.at<const float>(o_x), K, K, N, ln_w ? im.at<const float>(o_lw) : nullptr, ln_w ? im.at<const float>(o_lb) : nullptr, 1e-5f,
+                                             im.at<int8_t>(o_q), im.at<float>(o_d), im.at<uint32_t>(o_s), 0, four));
+        HIP_TRY(-2, hipDeviceSynchronize());
+        report_launch(launched, {four[0], four[1], four[2], four[3]});
+        return im.read(o_q, out_q) && im.read(o_d, out_d) && im.read(o_s, out_s) ? 0 : -2;
+    }
+    // stage 1
+    if (epi < bgk::EPI_QKV || epi > bgk::EPI_LOGITS) BG_FAIL(-1, "epi %d is no epilogue of the SIMD chain (0 QKV, 1 RESID, 2 GELU, 3 LOGITS)", epi);
+    if (cfg < -1 || cfg > 2) BG_FAIL(-1, "cfg must be in [-1, 2]");
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    if (epi == bgk::EPI_QKV && (K % 64 != 0 || M != 3 * K)) BG_FAIL(-1, "q/k/v is 3 K x K with heads of 64 (got %d x %d)", M, K);
+    if (!w_rows || !out) BG_FAIL(-1, "w_rows or out is NULL");
+    if (epi != bgk::EPI_LOGITS && !bias) BG_FAIL(-1, "bias is NULL");
+    if (epi == bgk::EPI_RESID && !resid) BG_FAIL(-1, "resid is NULL");
+    const bool qkv = epi == bgk::EPI_QKV;
+    if (!check_probe_columns(__func__, qkv, N, dev_state, seq_states, col_mode, P, n_slots, k_slots, v_slots)) return -1;
+    HIP_TRY(-2, hipSetDevice(device));
+    const int cols = ((N + 31) & ~31) + 1, ldo = ((M + 63) & ~63) + 16;
+    const size_t kv_b = qkv ? (size_t)(K / 64) * P * 64 * 4 * (size_t)n_slots : 0;
+    ProbeImage im;      // [weights | x | gain | bias of the LayerNorm | the stage's parts | the producer's rows | out], guard column and rows in the output
+    const BlockRows wr = upload_block_rows(im, wtype, w_rows, M, K, false);
+    const ProbePart o_x = im.in(x, (size_t)N * K * 4), o_lw = im.in(ln_w, (size_t)K * 4), o_lb = im.in(ln_b, (size_t)K * 4);
+    const StageParts sp = stage_parts(im, bias, (size_t)M * 4, epi == bgk::EPI_RESID ? resid : nullptr, (size_t)N * M * 4, dev_state, seq_states, N, k_slots, v_slots, kv_b);
+    const ProbePart o_q = im.fill((size_t)N * K), o_d = im.fill((size_t)N * bpr * 4), o_s = im.fill((size_t)N * bpr * 4);
+    const ProbePart o_out = im.out((size_t)cols * (qkv ? K : ldo) * 4);
+    if (!im.upload()) return -2;
+    bgk::MatvecParams p = stage_params(im, wr.W(im), sp, K, P, N, qkv, col_mode, o_out, ldo, M);
+    HIP_TRY(-2, (hipError_t)bg_schain_q8(q81, im.at<const float>(o_x), K, K, N, ln_w ? im.at<const float>(o_lw) : nullptr, ln_w ? im.at<const float>(o_lb) : nullptr, 1e-5f,
+                                         im.at<int8_t>(o_q), im.at<float>(o_d), im.at<uint32_t>(o_s), 0, nullptr));
+    p.aq_q = im.at<const int8_t>(o_q); p.aq_d = im.at<const float>(o_d); p.aq_s = im.at<const uint32_t>(o_s);
+    int32_t five[5] = {0, 0, 0, 0, 0};
+    HIP_TRY(-2, (hipError_t)bg_schain_launch(wtype, epi, &p, sizeof(p), cfg, 0, five));
+    HIP_TRY(-2, hipDeviceSynchronize());
+    report_launch(launched, {five[0], five[1], five[2], five[3], cols, ldo, five[4], 4 << (five[4] == 0 ? 0 : five[4] + 1)});
+    if (!im.read(o_out, out) || !im.read(sp.k, k_slots) || !im.read(sp.v, v_slots)) return -2;
+    return 0;
+}
+
+// A linear stage of the SIMD association alone, timed: one untimed launch, then reps launches on device memory of 0x11 bytes (the kernels' time does not depend
+// on the values), each between two device events.  which 0: schain_kernel with the residual epilogue at tile shape cfg (-1: the launch's choice) on rows a
+// producer launch made in front of the timing; which 1: the producer alone; which 2: matvec_simd_kernel<PLAIN, RESID> as a context's own pass in mode 1
+// launches it at N columns (its own grid) -- the yardstick at N = 8; which 3: the wide chain's matrix-core stage of the scalar association, for scale only.
+// For tools/simd_chain_bench.py.
+int biogpt_hip_schain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, int32_t reps, float *us_out) {
+    clear_error();
+    if (which < 0 || which > 3) BG_FAIL(-1, "which must be 0 (the SIMD chain's stage), 1 (its producer), 2 (the SIMD mat-vec) or 3 (the wide chain's stage)");
+    if (which == 3) return biogpt_hip_wide_chain_bench(device, 0, wtype, M, K, N, reps, us_out);
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    if (cfg < -1 || cfg > 2) BG_FAIL(-1, "cfg must be in [-1, 2]");
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    if (reps < 1 || reps > PROBE_MAX_REPS) BG_FAIL(-1, "reps must be in [1, %d]", PROBE_MAX_REPS);
+    if (!us_out) BG_FAIL(-1, "us_out is NULL");
+    if (which == 2 && bgk::matvec_simd_smem_bytes(K, 1) > 64 * 1024) BG_FAIL(-1, "a column of K = %d values exceeds the SIMD mat-vec's LDS", K);
+    HIP_TRY(-2, hipSetDevice(device));
+    ProbeImage im;      // every part of 0x11 bytes: [qs | sc | qh | x | bias | resid | codes | d | s | out]
+    const size_t nblk = (size_t)M * (K / QK), bpr = (size_t)K / QK;
+    const bool q81 = wtype == T_Q4_1 || wtype == T_Q5_1, q5 = wtype == T_Q5_0 || wtype == T_Q5_1;
+    const ProbePart o_qs = im.fill(nblk * (wtype == T_Q8_0 ? 32 : 16), 0x11), o_sc = im.fill(nblk * (q81 ? 4 : 2) + 16, 0x11), o_qh = im.fill(q5 ? nblk * 4 : 0, 0x11);
+    const ProbePart o_x = im.fill((size_t)N * K * 4, 0x11), o_bias = im.fill((size_t)M * 4, 0x11), o_res = im.fill((size_t)N * M * 4, 0x11);
+    const ProbePart o_q = im.fill((size_t)N * K, 0x11), o_d = im.fill((size_t)N * bpr * 4, 0x11), o_s = im.fill((size_t)N * bpr * 4, 0x11), o_out = im.fill((size_t)N * M * 4, 0x11);
+    if (!im.upload()) return -2;
+    const MvShape s = mv_shape(wtype, M, K);
+    bgk::MatvecParams p{};
+    p.W.qs = im.d.p + o_qs.off; p.W.sc = im.d.p + o_sc.off; p.W.qh = q5 ? im.at<const uint32_t>(o_qh) : nullptr;
+    p.W.type = wtype; p.W.M = M; p.W.K = K;
+    p.upr = s.upr; p.lpr_log2 = s.lpr_log2; p.nit = s.nit; p.rpw = s.rpw;
+    p.eps = 1e-5f; p.D = 1024; p.dk = 64; p.dk_log2 = 6; p.P = 1;
+    p.inv_k = 1.0 / (double)K; p.k_pow2 = (K & (K - 1)) == 0;
+    p.N = N; p.x = im.at<const float>(o_x); p.ldx = K;
+    p.bias = im.at<const float>(o_bias); p.resid = im.at<const float>(o_res); p.ldr = M; p.out = im.at<float>(o_out); p.ldo = M;
+    p.aq_q = im.at<const int8_t>(o_q); p.aq_d = im.at<const float>(o_d); p.aq_s = im.at<const uint32_t>(o_s);
+    auto produce = [&]() -> hipError_t {
+        return (hipError_t)bg_schain_q8(q81 ? 1 : 0, p.x, K, K, N, nullptr, nullptr, 1e-5f, im.at<int8_t>(o_q), im.at<float>(o_d), im.at<uint32_t>(o_s), 0, nullptr);
+    };
+    auto launch = [&]() -> hipError_t {
+        if (which == 0) return (hipError_t)bg_schain_launch(wtype, bgk::EPI_RESID, &p, sizeof(p), cfg, 0, nullptr);
+        if (which == 1) return produce();
+        return launch_mv_simd<bgk::PRO_PLAIN, bgk::EPI_RESID>(p, 0);
+    };
+    HIP_TRY(-2, produce());
+    HIP_TRY(-2, launch());      // one untimed launch in front
+    HIP_TRY(-2, hipDeviceSynchronize());
+    return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+}

@@ -171,7 +171,8 @@ int64_t biogpt_hip_mfma_launches(const biogpt_hip_ctx *ctx);
  * refuse it), 1 the BioGPT-base chain (block-quantized, d_model 1024, d_ff 4096), 2 the wide chain -- any other block-quantized file with head size 64, d_model a
  * multiple of 64 and d_ff of 32 (BioGPT-Large: 1600 / 6400): its passes over column states run their linear stages on the int8 matrix cores at every column
  * count, from a row-tiled weight image whose last lm_head tile is zero-padded; 3 the float chain -- an F32 / F16 file of the wide chain's widths, and only
- * while biogpt_hip_float_chain has switched it on for this context (a float file is 0 otherwise).  -1: ctx is NULL. */
+ * while biogpt_hip_float_chain has switched it on for this context (a float file is 0 otherwise); 4 the SIMD chain -- a context in the SIMD association
+ * (biogpt_hip_assoc, mode 1) while biogpt_hip_assoc_chain has switched it on (a context in mode 1 is 0 otherwise).  -1: ctx is NULL. */
 int biogpt_hip_chain_kind(const biogpt_hip_ctx *ctx);
 /* Linear-stage launches of the wide chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever on a
  * BioGPT-base file.  -1: ctx is NULL. */
@@ -199,6 +200,24 @@ int biogpt_hip_float_chain(biogpt_hip_ctx *ctx, int on);
 int biogpt_hip_assoc(biogpt_hip_ctx *ctx, int mode);
 /* The context's association: 0 scalar, 1 SIMD.  -1: ctx is NULL. */
 int biogpt_hip_get_assoc(const biogpt_hip_ctx *ctx);
+/* The SIMD chain's switch (off by default; BIOGPT_HIP_ASSOC_CHAIN=1 makes on the default of new contexts whose file can have it).  It is a property of the
+ * context that takes effect only while the context is in the SIMD association: in mode 0 a context with the switch set is bit for bit and launch for launch a
+ * mode-0 context.  on 1, in mode 1: the calls over column states the wide and float chains serve (score_batch, embed_batch, score_continuations,
+ * generate_greedy_batch, generate_sample, generate_beam / _beam_batch, the plain generate_queue) serve this context in the SIMD association -- every sequence's
+ * logits, K / V rows and ids are those of the single-sequence calls of mode 1, i.e. of an AVX2 build of the reference.  Its passes over column states run on
+ * csrc/kernels_schain.hip.h: one Q8 producer launch per linear stage, a many-column stage in which a thread owns whole (row, column) pairs, and the SIMD
+ * attention over column states, with contexts of up to 1024 keys; biogpt_hip_chain_kind returns 4; a biogpt_hip_generate_greedy_batch of 2 .. 8 sequences takes no
+ * column-per-XCD launch.  The context's own passes are untouched, and every other call over column states (prefix generation, log-probabilities, rules, trie,
+ * contrastive, lookup, the wide sampler, score_continuations_batch, queue prefix / requests / sessions, the beam queue) refuses the context before any launch,
+ * with a message that names the call and the SIMD chain.  on 0: a context in mode 1 is what it was without the switch, call by call and message by message.
+ * Legal wherever biogpt_hip_assoc(ctx, 1) is (an F32 / F16 file is refused by file type), and not while a queue session is open or a call of the context is
+ * running.  Drops the captured column steps.  Returns 0, -1 with a message (biogpt_hip_last_error), -2 on a HIP error. */
+int biogpt_hip_assoc_chain(biogpt_hip_ctx *ctx, int on);
+/* The SIMD chain's switch: 0 off, 1 on (whatever the association).  -1: ctx is NULL. */
+int biogpt_hip_get_assoc_chain(const biogpt_hip_ctx *ctx);
+/* Linear-stage launches of the SIMD chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
+ * switch is off.  -1: ctx is NULL. */
+int64_t biogpt_hip_simd_chain_launches(const biogpt_hip_ctx *ctx);
 /* Linear-stage launches of the float chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
  * switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_float_launches(const biogpt_hip_ctx *ctx);
@@ -490,6 +509,27 @@ int biogpt_hip_assoc_device(int device, int32_t stage, int32_t wtype, int32_t pr
  * N <= 512 columns; which 1: the mat-vec a context in the scalar association launches at the same shape on its five-launch route -- the yardstick; which 2:
  * attn_simd_kernel with M heads, N query columns under the causal mask, the last of which sees K keys (N <= K <= 1024).  For tools/assoc_bench.py. */
 int biogpt_hip_assoc_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t reps, float *us_out);
+/* The kernels of the SIMD chain alone (csrc/kernels_schain.hip.h), through the launch functions a pass over column states of a context on the SIMD chain uses.  No
+ * model, no context.  wtype: a block format (2 / 3 / 6 / 7 / 8); K a multiple of 32; N in [1, 512].
+ *   stage 0 Q8: the producer over x [N][K], behind the LayerNorm when ln_w / ln_b are given: out_q [N + 1][K] codes, out_d [N + 1][K / 32] the scale the dot
+ *     reads, out_s [N + 1][K / 32] words (Q8_0 form: the integer sum; Q8_1 form, for Q4_1 / Q5_1: bits of d * sum).
+ *   stage 1 STAGE: the producer, then the many-column linear stage at tile shape cfg (0: 64 rows x 4 columns, 1: x 16, 2: x 32; -1: the launch's own choice).
+ *     epi 0 QKV (M == 3 K, 64 | K; exactly one of dev_state {n_past, ..} and seq_states [N][8] (+ col_mode) names the column states; k_slots / v_slots
+ *     [n_slots][K / 64][P][64] are updated in place; out = the q rows [cols][K]), 1 RESID (bias, resid [N][M]), 2 GELU (bias), 3 LOGITS; any M.  out but for QKV:
+ *     [cols][ldo]; cols = N rounded up to 32, plus one guard column; ldo = M rounded up to 64, plus 16 guard rows.
+ *   stage 2 ATTN: the SIMD attention over column states: q [N][H * 64], k_slots / v_slots [n_slots][H][P][64], seq_states [N][8]: column i reads slot i and
+ *     n_past + 1 keys (col_mode 0) or slot seq_id and t_vis keys (col_mode 1), at most 1024 and at most P; shared 1: its rows j < pad[0] come from slot pad[1].
+ *     out [N + 1][H * 64].
+ * The outputs come back WHOLE as allocated and preset to 0xff bytes.  launched [8]: stage 0 / 2: threads, grid x, grid y, LDS bytes; stage 1: threads, grid x,
+ * grid y, static LDS bytes, cols, ldo, cfg, columns of a tile.  Returns 0, -1 on a bad argument (before any HIP call), -2 on a HIP error. */
+int biogpt_hip_schain_device(int device, int32_t stage, int32_t wtype, int32_t epi, int32_t M, int32_t K, int32_t N, int32_t cfg, int32_t H, int32_t P, int32_t n_slots,
+                             int32_t col_mode, int32_t shared, const void *w_rows, const float *x, const float *ln_w, const float *ln_b, const float *bias,
+                             const float *resid, const int32_t *dev_state, const int32_t *seq_states, const float *q, float *k_slots, float *v_slots, float *out,
+                             int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched);
+/* A linear stage of the SIMD association alone, timed (microseconds of reps launches, each between two device events; one untimed launch in front).  which 0:
+ * the SIMD chain's stage with the residual epilogue at tile shape cfg (-1: the launch's choice); 1: its Q8 producer; 2: the SIMD mat-vec a context's own pass in
+ * mode 1 launches at N columns; 3: the wide chain's matrix-core stage of the scalar association (M a multiple of 16), for scale.  tools/simd_chain_bench.py. */
+int biogpt_hip_schain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, int32_t reps, float *us_out);
 /* One stand-alone run of a stage of the embedding tail (ln_rows_kernel<1024> / <0>, pool_rows_kernel, pool_finish_kernel, head_rows_kernel) over caller-supplied
  * rows, through the launch code of biogpt_hip_hidden / biogpt_hip_embed_batch.  No model, no context; W a multiple of 4.  stage 0 LN: x [n_rows][W], ln_w / ln_b
  * [W]; W == 1024 takes the <1024> template, any other width <0>; seq_states (may be NULL) [n_rows][8] words with slot_div >= 1 and P: row i lands at row
