@@ -836,6 +836,10 @@ SYMBOLS = [
     ("biogpt_hip_assoc_chain", C.c_int, [_P, C.c_int]),
     ("biogpt_hip_get_assoc_chain", C.c_int, [_P]),
     ("biogpt_hip_simd_chain_launches", C.c_int64, [_P]),
+    ("biogpt_hip_wide_decode", C.c_int, [_P, C.c_int]),
+    ("biogpt_hip_get_wide_decode", C.c_int, [_P]),
+    ("biogpt_hip_wide_decode_launches", C.c_int64, [_P]),
+    ("biogpt_hip_wide_decode_key_borders", C.c_int, [_P, C.c_int]),
     ("biogpt_hip_fpipe_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_stamps", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     ("biogpt_hip_generate_launches", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
@@ -938,6 +942,7 @@ SYMBOLS = [
     ("biogpt_hip_assoc_device", C.c_int, [C.c_int] + [C.c_int32] * 9 + [_P] * 17),
     ("biogpt_hip_assoc_bench", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P]),
     ("biogpt_hip_schain_device", C.c_int, [C.c_int] + [C.c_int32] * 12 + [_P] * 16),
+    ("biogpt_hip_wdecode_device", C.c_int, [C.c_int] + [C.c_int32] * 8 + [_P] * 18),
     ("biogpt_hip_schain_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P]),
     ("biogpt_hip_embed_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 4 + [C.c_int32] * 5 + [_P] + [C.c_int32] * 2 + [_P] * 3 + [C.c_int32] + [_P] * 3),
     ("biogpt_hip_tail_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 7 + [C.c_int32] * 2 + [_P] + [C.c_int32] * 3 + [_P] * 5),
@@ -1292,6 +1297,65 @@ def schain_device(stage, wtype=2, M=0, K=0, N=None, w_rows=None, x=None, ln_w=No
     return res
 
 
+WDECODE_STAGES = {"QKV": 0, "ATTN": 1, "OPROJ": 2, "FC1": 3, "FC2": 4}
+
+
+def wide_decode_key_borders():
+    """The key counts at which the wide decode layer's attention launch changes form (biogpt_hip_wide_decode_key_borders); beyond the last one the layer keeps the
+    generic route's attention launch."""
+    b = np.zeros(8, np.int32)
+    n = int(lib().biogpt_hip_wide_decode_key_borders(b.ctypes.data, 8))
+    return [int(v) for v in b[:n]]
+
+
+def wdecode_device(stage, wtype=2, M=0, K=0, w_rows=None, x=None, ln_w=None, ln_b=None, aq=None, bias=None, resid=None, q=None, k_cache=None, v_cache=None, H=0,
+                   P=0, n_past=0, reps=0, device=0):
+    """One stand-alone run of a kernel of the wide decode layer (biogpt_hip_wdecode_device; include/biogpt_hip.h has the inputs of each stage), one token.  stage
+    "QKV": w_rows, x / ln_w / ln_b [K], bias [3 K], k_cache / v_cache [K / 64, P, 64], n_past -> "out" [K + 16] (the q row), "k", "v".  "ATTN": q [H * 64],
+    k_cache / v_cache [H, P, 64], n_past -> "out" [H * 64 + 16], "q" int8 [H * 64 + 32], "d" / "s" [2 H + 1].  "OPROJ" / "FC2": aq = (codes int8 [K], d float32
+    [K / 32], s uint32 [K / 32]), bias, resid [M] -> "out" [M + 16].  "FC1": x / ln_w / ln_b [K], bias [M] -> "q" [M + 32], "d" / "s" [M / 32 + 1].  Outputs come
+    back WHOLE, guard words included and preset to 0xff bytes; "launched" as the header lists it; reps > 0: "us", the microseconds of reps timed launches.
+    Raises BiogptError on a refusal."""
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    st = WDECODE_STAGES[stage] if isinstance(stage, str) else int(stage)
+    M, K, H, P = int(M), int(K), int(H), int(P)
+    res = {}
+    if st == 0:
+        res["out"] = np.zeros(max(K, 0) + 16, np.float32)
+        if k_cache is not None and v_cache is not None:
+            res["k"], res["v"] = np.array(k_cache, dtype=np.float32, order="C"), np.array(v_cache, dtype=np.float32, order="C")
+    elif st == 1:
+        D = max(H, 0) * 64
+        res["out"], res["q"] = np.zeros(D + 16, np.float32), np.zeros(D + 32, np.int8)
+        res["d"], res["s"] = np.zeros(2 * max(H, 0) + 1, np.float32), np.zeros(2 * max(H, 0) + 1, np.uint32)
+    elif st == 3:
+        res["q"], res["d"], res["s"] = np.zeros(max(M, 0) + 32, np.int8), np.zeros(max(M, 0) // 32 + 1, np.float32), np.zeros(max(M, 0) // 32 + 1, np.uint32)
+    else:
+        res["out"] = np.zeros(max(M, 0) + 16, np.float32)
+    launched, us = np.zeros(8, np.int32), np.zeros(max(int(reps), 1), np.float32)
+    o = lambda name: res[name].ctypes.data if name in res else None
+    kv = (o("k"), o("v")) if st == 0 else (ptr(k_cache, np.float32), ptr(v_cache, np.float32))
+    aq = aq or (None, None, None)
+    rc = lib().biogpt_hip_wdecode_device(int(device), st, int(wtype), M, K, H, P, int(n_past), int(reps), ptr(w_rows, np.uint8), ptr(x, np.float32),
+                                         ptr(ln_w, np.float32), ptr(ln_b, np.float32), ptr(aq[0], np.int8), ptr(aq[1], np.float32), ptr(aq[2], np.uint32),
+                                         ptr(bias, np.float32), ptr(resid, np.float32), ptr(q, np.float32), kv[0], kv[1], o("out"), o("q"), o("d"), o("s"),
+                                         launched.ctypes.data, us.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    res["launched"] = launched
+    if reps > 0:
+        res["us"] = us
+    return res
+
+
 def schain_bench(which, wtype, M, K, N, cfg=-1, reps=9, device=0):
     """A linear stage of the SIMD association alone, timed (biogpt_hip_schain_bench): microseconds of `reps` launches, float32 [reps].  which "stage": the SIMD
     chain's stage with the residual epilogue at tile shape cfg (-1: the launch's choice); "q8": its producer; "matvec": the SIMD mat-vec of a context's own pass at
@@ -1588,10 +1652,11 @@ class BiogptModel:
 
     # -- biogpt_model_load (biogpt.h:128-132) --
     @classmethod
-    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None, assoc_chain=None):
+    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None, assoc_chain=None, wide_decode=None):
         """float_chain=True: switch the float chain on behind the load (float_chain(); an F32 / F16 file with head size 64 only -- anything else raises).
         assoc="scalar" | "simd": set the association behind the load (set_assoc(); None: the default, scalar unless BIOGPT_HIP_ASSOC=1).
-        assoc_chain=True | False: set the SIMD chain's switch behind the load (set_assoc_chain(); None: the default, off unless BIOGPT_HIP_ASSOC_CHAIN=1)."""
+        assoc_chain=True | False: set the SIMD chain's switch behind the load (set_assoc_chain(); None: the default, off unless BIOGPT_HIP_ASSOC_CHAIN=1).
+        wide_decode=True | False: set the wide decode layer's switch behind the load (set_wide_decode(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_DECODE=0)."""
         if arena is None:
             m = cls(lib().biogpt_hip_load(os.fsencode(fname), device, verbosity))
         else:
@@ -1603,6 +1668,8 @@ class BiogptModel:
                 m.set_assoc(assoc)
             if assoc_chain is not None:
                 m.set_assoc_chain(assoc_chain)
+            if wide_decode is not None:
+                m.set_wide_decode(wide_decode)
         except BiogptError:
             m.close()
             raise
@@ -2370,6 +2437,28 @@ class BiogptModel:
     def simd_chain_launches(self):
         """Linear-stage launches of the SIMD chain (biogpt_hip_simd_chain_launches); 0 while the switch is off."""
         return int(lib().biogpt_hip_simd_chain_launches(self._h))
+
+    def set_wide_decode(self, on=True):
+        """The wide decode layer's switch (biogpt_hip_wide_decode): on, single-token evals and the steps of generate_greedy of a block-quantized file that is not
+        BioGPT-base (head size 64, d_model a multiple of 64, d_ff of 32) run on csrc/kernels_wdecode.hip.h -- the same bits as off.  Returns True where the file is
+        served, False where it is not (nothing changed; biogpt_hip_last_error then reads "not served: ...").  Raises BiogptError on a bad call."""
+        rc = lib().biogpt_hip_wide_decode(self._h, 1 if on else 0)
+        if rc < 0:
+            raise BiogptError(_err())
+        return rc == 0
+
+    @property
+    def wide_decode(self):
+        """Whether the wide decode layer's switch is on (biogpt_hip_get_wide_decode)."""
+        k = int(lib().biogpt_hip_get_wide_decode(self._h))
+        if k < 0:
+            raise BiogptError(_err())
+        return k == 1
+
+    def wide_decode_launches(self):
+        """Layer-stage launches of the wide decode layer enqueued or captured (biogpt_hip_wide_decode_launches): five per layer and token; a captured step counts
+        when it is captured, not per replay; 0 while the switch is off."""
+        return int(lib().biogpt_hip_wide_decode_launches(self._h))
 
     def float_launches(self):
         """Linear-stage launches of the float chain (biogpt_hip_float_launches); 0 while the switch is off."""

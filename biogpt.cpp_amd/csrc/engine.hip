@@ -35,6 +35,7 @@
 #include "kernels_assoc.hip.h"
 #include "kernels_runs.hip.h"
 #include "kernels_decode.hip.h"
+#include "kernels_wdecode.hip.h"   // parameter block and layouts only: the kernels are instantiated in wdecode_tu.hip
 #include "kernels_q8probe.hip.h"
 #include "kernels_fdecode.hip.h"
 #include "kernels_lmhead.hip.h"
@@ -207,7 +208,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain, wide_decode;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -240,6 +241,7 @@ struct EngineOptions {
         run_attn = get("BIOGPT_HIP_RUN_ATTN", -1);                // the passes of biogpt_hip_score_continuations_batch (no other call looks at it): -1 attn_runs_kernel where it was measured faster (RUN_ATTN_MIN_*), 0 never, 1 in every pass of up to 1024 keys (A/B arms)
         float_chain = get("BIOGPT_HIP_FLOAT_CHAIN", 0);          // 1: a new context of an F32 / F16 file the float chain serves starts with it switched on (biogpt_hip_float_chain; kernels_fchain.hip.h)
         assoc_chain = get("BIOGPT_HIP_ASSOC_CHAIN", 0);            // 1: a new context of a file the SIMD association serves starts with the SIMD chain switched on (biogpt_hip_assoc_chain; kernels_schain.hip.h)
+        wide_decode = get("BIOGPT_HIP_WIDE_DECODE", 1);          // 1 (the default: measured faster at every key count): a new context of a file the wide decode layer serves starts with it switched on; 0: off (biogpt_hip_wide_decode; kernels_wdecode.hip.h)
         assoc = get("BIOGPT_HIP_ASSOC", 0);                        // 1: a new context of a file the SIMD association serves starts in it (biogpt_hip_assoc; kernels_assoc.hip.h)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
     }
@@ -390,6 +392,8 @@ struct biogpt_hip_ctx {
     int64_t wide_launches = 0;             // linear-stage launches of the wide chain (kernels_mfma_wide.hip.h; biogpt_hip_wide_launches)
     bool float_chain = false;              // the float chain is switched on (biogpt_hip_float_chain): passes over column states of this F32 / F16 file run on kernels_fchain.hip.h
     int64_t float_launches = 0;            // linear-stage launches of the float chain (biogpt_hip_float_launches)
+    bool wide_decode = false;              // the wide decode layer is switched on (biogpt_hip_wide_decode): one token of the context's own column runs on kernels_wdecode.hip.h
+    int64_t wdec_launches = 0;             // layer-stage launches of the wide decode layer enqueued or captured (biogpt_hip_wide_decode_launches)
     int assoc = 0;                         // 1: the SIMD association (biogpt_hip_assoc): every pass on the five-launch layer with the kernels of kernels_assoc.hip.h; no call over column states
     bool assoc_chain = false;              // the SIMD chain is switched on (biogpt_hip_assoc_chain): while assoc == 1, passes over column states run on kernels_schain.hip.h; nothing while assoc == 0
     int64_t simd_chain_launches = 0;       // linear-stage launches of the SIMD chain (biogpt_hip_simd_chain_launches)
@@ -633,6 +637,25 @@ inline int chain_kind_of(const biogpt_hip_hparams &hp) {
     if (!is_quantized(ftype_to_type(hp.ftype)) || hp.n_head < 1 || hp.d_model % hp.n_head != 0 || hp.d_model / hp.n_head != 64) return CHAIN_NONE;
     if (hp.d_model == 1024 && hp.d_ff == 4096) return CHAIN_BASE;
     return (hp.d_model % 64 == 0 && hp.d_ff >= 32 && hp.d_ff % 32 == 0) ? CHAIN_WIDE : CHAIN_NONE;
+}
+// the wide decode layer (kernels_wdecode.hip.h, wdecode_tu.hip): one token of the context's own column of a wide file, five launches per layer.  stage: WS_*;
+// report: null, or four words (linear stages: threads, grid, LDS bytes, most rows of a workgroup; attention: threads, grid, lanes per key, 0)
+enum WdecStage : int { WS_QKV = 0, WS_ATTN = 1, WS_OPROJ = 2, WS_FC1 = 3, WS_FC2 = 4 };
+extern "C" int bg_wdec_geometry(int stage, int M, int K, int32_t *four);
+extern "C" int bg_wdec_launch(int wt, int stage, const void *params, size_t params_bytes, hipStream_t st, int32_t *report);
+extern "C" int bg_wdec_attn_max_keys(void);
+extern "C" int bg_wdec_attn_borders(int32_t *out, int cap);
+extern "C" int bg_wdec_attn(const void *params, size_t params_bytes, int H, hipStream_t st, int32_t *report);
+// why a file cannot have the wide decode layer (null: it can): a wide file whose four matrices the kernels hold
+inline const char *wide_decode_refusal(const biogpt_hip_hparams &hp) {
+    if (!is_quantized(ftype_to_type(hp.ftype))) return "the weights are not block-quantized";
+    const int kind = chain_kind_of(hp);
+    if (kind == CHAIN_BASE) return "it has BioGPT-base shapes, which have their own five-launch decode layer";
+    if (kind != CHAIN_WIDE) return "the head size is not 64, or d_model is no multiple of 64, or d_ff of 32";
+    const int D = hp.d_model, F = hp.d_ff;
+    if (bg_wdec_geometry(WS_QKV, 3 * D, D, nullptr) || bg_wdec_geometry(WS_OPROJ, D, D, nullptr) || bg_wdec_geometry(WS_FC1, F, D, nullptr) || bg_wdec_geometry(WS_FC2, D, F, nullptr))
+        return "a row of it exceeds what a workgroup of the layer holds";
+    return nullptr;
 }
 // the float chain (kernels_fchain.hip.h, fchain_tu.hip): the many-column linear stage on the row-major F32 / F16 weights of the arena, and the LayerNorm producer in
 // front of it.  cfg: a tile shape, -1 the launch's own choice; report: null, or five words (threads, grid x, grid y, LDS bytes, cfg)
@@ -1263,6 +1286,7 @@ bool enqueue_xcols(biogpt_hip_ctx *c, int N, int t_max, bool streams = false) {
 // call was not measured: the thresholds are the smallest measured wins.  Repeated stand-alone launches (--kernel, K / V in cache) flatter the kernel: there it
 // already wins at 64 columns with 8 own rows.  DESIGN.md 4.7 has the tables.)
 constexpr int PREFIX_ATTN_MIN_COLS = 128, PREFIX_ATTN_MIN_SHARED = 376;
+constexpr int FAST_ATTN_MAX_KEYS = 1024;      // enqueue_attention: the most keys of the head-size-64 attention kernels (they write out_proj's Q8 blocks when asked); beyond, attn_kernel
 constexpr int MFMA_MIN_DECODE_COLS = 48, MFMA_MIN_PASS_COLS = 64, GROUPED_ATTN_MIN_COLS = 80, SLIM_ATTN_MIN_COLS = 48, SPLIT_ATTN_ABOVE_KEYS = 256;
 
 // ---- a forward pass, by name --------------------------------------------------------------------------------------------------------------
@@ -1356,6 +1380,7 @@ struct PassLaunch {
     bool chain, pchain, mfma;       // the single-token fast chain; its many-column form; on the int8 matrix cores
     bool wchain;                    // the wide chain: a pass over column states of a block-quantized file that is not BioGPT-base (kernels_mfma_wide.hip.h)
     bool fchain;                    // the float chain: a pass over column states of an F32 / F16 file whose context has it switched on (kernels_fchain.hip.h)
+    bool wdec;                      // the wide decode layer: one token of the context's own column of a wide file whose context has it switched on (kernels_wdecode.hip.h)
     bool simd;                      // the context is in the SIMD association: the generic sites launch the kernels of kernels_assoc.hip.h
     bool schain;                    // the SIMD chain: a pass over column states of a context in the SIMD association that has it switched on (kernels_schain.hip.h)
     int q81;
@@ -1559,7 +1584,7 @@ bool enqueue_attention(PassLaunch &k, int l) {
     a.N = N; a.D = D; a.dk = dk; a.P = P;
     a.dbg = c->opt.dbg; a.tstamp = c->tstamp;
     a.q81 = k.q81;
-    if (k.chain) { a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; }
+    if (k.chain || k.wdec) { a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; }      // (the wide decode layer beyond its own attention's keys: out_proj reads these blocks)
     if (k.simd) {      // (head size 64 and t_max <= SIMD_ATTN_MAXT: enqueue_forward)
         launch_attn_simd(a, H, N, st);
         return true;
@@ -1568,7 +1593,7 @@ bool enqueue_attention(PassLaunch &k, int l) {
         HIP_TRY(false, (hipError_t)bg_schain_attn(&a, sizeof(a), k.pass.shared_prefix ? 1 : 0, H, N, st, nullptr));
         return true;
     }
-    if (!(dk == 64 && t_max <= 1024)) {
+    if (!(dk == 64 && t_max <= FAST_ATTN_MAX_KEYS)) {
         launch_attn_generic(a, H, N, k.attn_threads, st);
         return true;
     }
@@ -1597,9 +1622,69 @@ bool enqueue_attention(PassLaunch &k, int l) {
     return true;
 }
 
+// Layer l of the wide decode layer (N == 1, the context's own column): q/k/v, attention, out_proj, fc1, fc2 on kernels_wdecode.hip.h.  The attention is
+// dec_attn_kernel while the launch's load bound is within bg_wdec_attn_max_keys(); beyond, the generic route's attention launch (enqueue_attention), which
+// writes the same Q8 blocks beside its f32 row.  Activations travel as in the base layer: aq[0] attention -> out_proj, aq[1] fc1 -> fc2.
+inline bool wdec_own_attention(int P, int t_max) { return attn_decode_t_cap(P, t_max) <= bg_wdec_attn_max_keys(); }
+bool enqueue_wdec_layer(PassLaunch &k, int l) {
+    biogpt_hip_ctx *c = k.c;
+    const int D = k.D, P = k.P;
+    hipStream_t st = k.st;
+    const LayerSlots &L = c->plan.layers[(size_t)l];
+    auto stage = [&](int which, const MatSlot &m, bgk::WdecParams &p) -> bool {
+        p.W = dev_matrix(c, m);
+        HIP_TRY(false, (hipError_t)bg_wdec_launch(m.type, which, &p, sizeof(p), st, nullptr));
+        c->wdec_launches++;
+        return true;
+    };
+    {
+        bgk::WdecParams p{};
+        p.x = c->x; p.ln_w = dev_vec(c, L.ln0_w); p.ln_b = dev_vec(c, L.ln0_b); p.eps = 1e-5f;
+        p.bias = dev_vec(c, L.qkv_b);
+        p.q_out = c->q; p.kcache = k.kroot + (size_t)l * P * D; p.vcache = k.vroot + (size_t)l * P * D;
+        p.D = D; p.P = P; p.q_scale = 1.0f / sqrtf((float)k.dk); p.st = c->state;
+        if (!stage(WS_QKV, L.qkv, p)) return false;
+    }
+    if (wdec_own_attention(P, k.pass.t_max)) {
+        bgk::DecAttnParams a{};
+        a.q = c->q; a.kcache = k.kroot + (size_t)l * P * D; a.vcache = k.vroot + (size_t)l * P * D;
+        a.st = c->state; a.P = P; a.t_cap = attn_decode_t_cap(P, k.pass.t_max);
+        a.exp_tab = reinterpret_cast<const uint16_t *>(c->arena + c->plan.exp_tab);
+        a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; a.att_out = c->att; a.q81 = k.q81;
+        HIP_TRY(false, (hipError_t)bg_wdec_attn(&a, sizeof(a), k.H, st, nullptr));
+    } else {
+        if (!enqueue_attention(k, l)) return false;
+        // (beyond FAST_ATTN_MAX_KEYS that launch is attn_kernel, which writes the f32 row alone: its Q8 blocks by q8_rows_kernel)
+        if (k.pass.t_max > FAST_ATTN_MAX_KEYS) HIP_TRY(false, (hipError_t)bg_wide_quantize(c->att, D, D, 1, nullptr, nullptr, 1e-5f, k.q81, c->aq_q[0], c->aq_d[0], c->aq_s[0], st));
+    }
+    c->wdec_launches++;
+    {
+        bgk::WdecParams p{};
+        p.aq_q = c->aq_q[0]; p.aq_d = c->aq_d[0]; p.aq_s = c->aq_s[0];
+        p.bias = dev_vec(c, L.o_b); p.resid = c->x; p.out = c->x1;
+        if (!stage(WS_OPROJ, L.o, p)) return false;
+    }
+    {
+        bgk::WdecParams p{};
+        p.x = c->x1; p.ln_w = dev_vec(c, L.ln1_w); p.ln_b = dev_vec(c, L.ln1_b); p.eps = 1e-5f;
+        p.bias = dev_vec(c, L.fc1_b);
+        p.gelu_tab = reinterpret_cast<const uint16_t *>(c->arena + c->plan.gelu_tab);
+        p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
+        if (!stage(WS_FC1, L.fc1, p)) return false;
+    }
+    {
+        bgk::WdecParams p{};
+        p.aq_q = c->aq_q[1]; p.aq_d = c->aq_d[1]; p.aq_s = c->aq_s[1];
+        p.bias = dev_vec(c, L.fc2_b); p.resid = c->x1; p.out = c->x;
+        if (!stage(WS_FC2, L.fc2, p)) return false;
+    }
+    return true;
+}
+
 // layer l on the chain of launches: q/k/v, attention, out_proj, fc1, fc2
 bool enqueue_layer(PassLaunch &k, int l) {
     biogpt_hip_ctx *c = k.c;
+    if (k.wdec) return enqueue_wdec_layer(k, l);
     const int N = k.N, D = k.D, F = k.F, P = k.P;
     hipStream_t st = k.st;
     const LayerSlots &L = c->plan.layers[(size_t)l];
@@ -1841,6 +1926,8 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     // a pass over column states of a float file whose context has the float chain switched on (the context's own columns stay on fdec_kernel / matvec_kernel)
     k.fchain = !k.chain && !k.wchain && batch && chain_kind(c) == CHAIN_FLOAT && t_max <= 1024;
     if (k.fchain && (pass.rows == Rows::Last || pass.rows == Rows::AllGeneric)) BG_FAIL(false, "internal: a float fast chain pass with rows it does not serve");
+    // one token of the context's own column of a wide file: the wide decode layer, where the context has it switched on
+    k.wdec = c->wide_decode && N == 1 && last_own && c->assoc == 0 && !k.chain && chain_kind_of(hp) == CHAIN_WIDE && t_max <= hp.n_positions;
     if (batch && !k.chain && !k.wchain && !k.fchain && !k.schain)
         BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64) or the wide one (block-quantized weights, head size 64, d_model a multiple of 64, d_ff of 32)");
     if (k.wchain && (c->tile_img == nullptr || pass.rows == Rows::Last || pass.rows == Rows::AllGeneric))
@@ -2134,6 +2221,7 @@ biogpt_hip_ctx *load_impl(const char *fname, int device, int verbosity, void *ex
     c->float_chain = c->opt.float_chain == 1 && float_chain_refusal(c->hp) == nullptr;      // (the environment's default holds where the file can have it)
     c->assoc = (c->opt.assoc == 1 && assoc_refusal(c->hp) == nullptr) ? 1 : 0;      // (likewise BIOGPT_HIP_ASSOC)
     c->assoc_chain = c->opt.assoc_chain == 1 && assoc_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_ASSOC_CHAIN)
+    c->wide_decode = c->opt.wide_decode == 1 && wide_decode_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_DECODE)
     c->device = device;
     c->n_tensors = (int)mf.tensors.size();
     c->vocab = mf.vocab;
@@ -2245,6 +2333,7 @@ biogpt_hip_ctx *biogpt_hip_attach(const biogpt_hip_hparams *hp, int device, void
     c->float_chain = c->opt.float_chain == 1 && float_chain_refusal(c->hp) == nullptr;
     c->assoc = (c->opt.assoc == 1 && assoc_refusal(c->hp) == nullptr) ? 1 : 0;
     c->assoc_chain = c->opt.assoc_chain == 1 && assoc_refusal(c->hp) == nullptr;
+    c->wide_decode = c->opt.wide_decode == 1 && wide_decode_refusal(c->hp) == nullptr;
     c->device = device;
     c->pos_rows = (int64_t)hp->n_positions + 2;
     c->plan = plan_arena(*hp, c->pos_rows);
@@ -2843,6 +2932,44 @@ int biogpt_hip_get_assoc_chain(const biogpt_hip_ctx *ctx) {
     return ctx->assoc_chain ? 1 : 0;
 }
 int64_t biogpt_hip_simd_chain_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->simd_chain_launches : -1; }
+// The wide decode layer's switch.  On a file the layer does not serve it changes nothing and says so (1); a context in the SIMD association keeps the switch
+// and its own launches (the gate in enqueue_forward looks at the association).  The captured single-token steps bake the route: dropped.
+int biogpt_hip_wide_decode(biogpt_hip_ctx *ctx, int on) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (on != 0 && on != 1) BG_FAIL(-1, "on must be 0 or 1 (got %d)", on);
+    if (session_refuses(ctx)) return -1;
+    {
+        std::lock_guard<std::mutex> lk(g_xp_mu);
+        if (ctx->xp_in_call) BG_FAIL(-1, "the wide decode layer cannot be switched while a call of this context is running");
+    }
+    if (const char *why = wide_decode_refusal(ctx->hp)) {
+        bg::set_error(__func__, "not served: the wide decode layer is for block-quantized files with head size 64, d_model a multiple of 64 and d_ff of 32 that are not BioGPT-base: %s (got ftype %d, d_model %d, d_ff %d, %d heads)", why, ctx->hp.ftype, ctx->hp.d_model, ctx->hp.d_ff, ctx->hp.n_head);
+        return 1;
+    }
+    if (ctx->wide_decode == (on == 1)) return 0;
+    if (ctx->ready) {
+        HIP_TRY(-2, hipSetDevice(ctx->device));
+        HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    }
+    for (auto &pl : ctx->graph_step) for (auto &row : pl) for (auto &g : row) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    ctx->wide_decode = on == 1;
+    return 0;
+}
+int biogpt_hip_get_wide_decode(const biogpt_hip_ctx *ctx) {
+    if (!ctx) BG_FAIL(-1, "null context");
+    return ctx->wide_decode ? 1 : 0;
+}
+int64_t biogpt_hip_wide_decode_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->wdec_launches : -1; }
+// the key counts at which the layer's attention launch changes form: dec_attn_kernel at 16 / 8 / 4 lanes per key up to the first three, beyond them the generic
+// route's launch, which writes the Q8 blocks itself up to the last and leaves them to q8_rows_kernel beyond it.  Returns how many there are; out (or null) takes the first cap.
+int biogpt_hip_wide_decode_key_borders(int32_t *out, int cap) {
+    int32_t b[8];
+    int n = bg_wdec_attn_borders(b, 7);      // the layer's own attention launch (wdecode_tu.hip)
+    b[n++] = FAST_ATTN_MAX_KEYS;             // enqueue_attention: beyond, attn_kernel, and the Q8 blocks by a launch of their own
+    for (int i = 0; i < n && i < cap && out; i++) out[i] = b[i];
+    return n;
+}
 int biogpt_hip_fpipe_stamps(biogpt_hip_ctx *ctx, uint64_t *out, int n) {
     if (!ctx || !out || n < 0 || ctx->fp_state != 1 || !ctx->opt.fpipe_stamps) return -1;
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;

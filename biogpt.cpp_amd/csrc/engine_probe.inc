@@ -2150,3 +2150,92 @@ int biogpt_hip_schain_bench(int device, int32_t which, int32_t wtype, int32_t M,
     HIP_TRY(-2, hipDeviceSynchronize());
     return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
 }
+
+// ---- the kernels of the wide decode layer alone (kernels_wdecode.hip.h), through the launch functions enqueue_wdec_layer uses ----
+// One token, so one column.  stage 0 QKV: x [K], ln_w / ln_b [K], bias [M], M == 3 K, 64 | K; k_cache / v_cache [K / 64][P][64] are updated in place at row
+//   n_past; out = the scaled q row, [K + 16].  stage 1 ATTN: q [H * 64], k_cache / v_cache [H][P][64], n_past + 1 keys (at most bg_wdec_attn_max_keys() and P);
+//   out [H * 64 + 16], out_q [H * 64 + 32], out_d / out_s [2 H + 1].  stage 2 OPROJ / 4 FC2: aq_q [K], aq_d / aq_s [K / 32], bias / resid [M]; out [M + 16].
+//   stage 3 FC1: x, ln_w / ln_b [K], bias [M], 32 | M; out_q [M + 32], out_d / out_s [M / 32 + 1].
+// The outputs come back WHOLE as allocated and preset to 0xff bytes.  launched [8]: linear stages: threads, grid, LDS bytes, most rows of a workgroup; ATTN:
+// threads, grid, lanes per key.  reps > 0: after the checked launch, reps timed launches (microseconds into us_out [reps]).  Every refusal comes before any HIP call.
+int biogpt_hip_wdecode_device(int device, int32_t stage, int32_t wtype, int32_t M, int32_t K, int32_t H, int32_t P, int32_t n_past, int32_t reps, const void *w_rows,
+                              const float *x, const float *ln_w, const float *ln_b, const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias,
+                              const float *resid, const float *q, float *k_cache, float *v_cache, float *out, int8_t *out_q, float *out_d, uint32_t *out_s,
+                              int32_t *launched, float *us_out) {
+    clear_error();
+    if (stage < WS_QKV || stage > WS_FC2) BG_FAIL(-1, "stage %d is no stage (0 QKV, 1 ATTN, 2 OPROJ, 3 FC1, 4 FC2)", stage);
+    if (reps < 0 || reps > PROBE_MAX_REPS) BG_FAIL(-1, "reps must be in [0, %d]", PROBE_MAX_REPS);
+    if (reps > 0 && !us_out) BG_FAIL(-1, "us_out is NULL");
+    const bool q81 = wtype == T_Q4_1 || wtype == T_Q5_1;
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    const int32_t state[4] = {n_past, 0, 0, 0};
+    int32_t four[4] = {0, 0, 0, 0};
+    if (stage == WS_ATTN) {
+        if (H < 1 || H > 64) BG_FAIL(-1, "H must be in [1, 64]");
+        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+        if (n_past < 0 || n_past + 1 > P || !wdec_own_attention(P, n_past + 1)) BG_FAIL(-1, "n_past + 1 = %d keys: the kernel holds 1 .. %d, within P = %d", n_past + 1, bg_wdec_attn_max_keys(), P);
+        if (!q || !k_cache || !v_cache || !out || !out_q || !out_d || !out_s) BG_FAIL(-1, "q, k_cache, v_cache, out, out_q, out_d or out_s is NULL");
+        HIP_TRY(-2, hipSetDevice(device));
+        const size_t D = (size_t)H * 64, kv_b = D * P * 4;
+        ProbeImage im;      // [K | V | q | state | exp table | out | codes | d | s]
+        const ProbePart o_k = im.in(k_cache, kv_b), o_v = im.in(v_cache, kv_b), o_q = im.in(q, D * 4), o_ds = im.in(state, sizeof(state)), o_tab = im.own(exp_table_f16());
+        const ProbePart o_out = im.out((D + 16) * 4), o_oq = im.out(D + 32), o_od = im.out((2 * (size_t)H + 1) * 4), o_os = im.out((2 * (size_t)H + 1) * 4);
+        if (!im.upload()) return -2;
+        bgk::DecAttnParams a{};
+        a.q = im.at<const float>(o_q); a.kcache = im.at<const float>(o_k); a.vcache = im.at<const float>(o_v); a.st = im.at<const bgk::DevState>(o_ds);
+        a.P = P; a.t_cap = attn_decode_t_cap(P, n_past + 1); a.exp_tab = im.at<const uint16_t>(o_tab);
+        a.oq_q = im.at<int8_t>(o_oq); a.oq_d = im.at<float>(o_od); a.oq_s = im.at<uint32_t>(o_os); a.att_out = im.at<float>(o_out); a.q81 = q81 ? 1 : 0;
+        auto launch = [&]() -> hipError_t { return (hipError_t)bg_wdec_attn(&a, sizeof(a), H, 0, four); };
+        HIP_TRY(-2, launch());
+        HIP_TRY(-2, hipDeviceSynchronize());
+        report_launch(launched, {four[0], four[1], four[2], four[3]});
+        if (!im.read(o_out, out) || !im.read(o_oq, out_q) || !im.read(o_od, out_d) || !im.read(o_os, out_s)) return -2;
+        return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+    }
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    if (bg_wdec_geometry(stage, M, K, nullptr)) BG_FAIL(-1, "the wide decode layer does not hold a %d x %d matrix at stage %d (fc1: 32 | M; a row within a workgroup's LDS and threads)", M, K, stage);
+    if (!w_rows || !bias) BG_FAIL(-1, "w_rows or bias is NULL");
+    const bool ln = stage == WS_QKV || stage == WS_FC1, res = stage == WS_OPROJ || stage == WS_FC2;
+    if (ln && (!x || !ln_w || !ln_b)) BG_FAIL(-1, "x, ln_w or ln_b is NULL");
+    if (!ln && (!aq_q || !aq_d || !aq_s)) BG_FAIL(-1, "aq_q, aq_d or aq_s is NULL");
+    if (res && !resid) BG_FAIL(-1, "resid is NULL");
+    if (stage != WS_FC1 && !out) BG_FAIL(-1, "out is NULL");
+    if (stage == WS_FC1 && (!out_q || !out_d || !out_s)) BG_FAIL(-1, "out_q, out_d or out_s is NULL");
+    if (stage == WS_QKV) {
+        if (K % 64 != 0 || M != 3 * K) BG_FAIL(-1, "q/k/v is 3 K x K with heads of 64 (got %d x %d)", M, K);
+        if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+        if (n_past < 0 || n_past >= P) BG_FAIL(-1, "position %d outside [0, P)", n_past);
+        if (!k_cache || !v_cache) BG_FAIL(-1, "k_cache or v_cache is NULL");
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t bpr = (size_t)K / QK, kv_b = stage == WS_QKV ? (size_t)K * P * 4 : 0;
+    ProbeImage im;      // [weights | x | gain | bias of the LayerNorm | codes | d | s | bias | resid | state | GELU table | K | V | out | codes | d | s]
+    const BlockRows wr = upload_block_rows(im, wtype, w_rows, M, K, false);
+    const ProbePart o_x = im.in(ln ? x : nullptr, (size_t)K * 4), o_lw = im.in(ln ? ln_w : nullptr, (size_t)K * 4), o_lb = im.in(ln ? ln_b : nullptr, (size_t)K * 4);
+    const ProbePart o_aq = im.in(ln ? nullptr : aq_q, (size_t)K), o_ad = im.in(ln ? nullptr : aq_d, bpr * 4), o_as = im.in(ln ? nullptr : aq_s, bpr * 4);
+    const ProbePart o_bias = im.in(bias, (size_t)M * 4), o_res = im.in(res ? resid : nullptr, (size_t)M * 4), o_ds = im.in(state, sizeof(state)), o_tab = im.own(gelu_table_f16());
+    const ProbePart o_k = im.in(k_cache, kv_b), o_v = im.in(v_cache, kv_b);
+    const size_t out_n = stage == WS_QKV ? (size_t)K + 16 : (size_t)M + 16, nb = (size_t)M / 32 + 1;
+    const ProbePart o_out = im.out(stage == WS_FC1 ? 0 : out_n * 4);
+    const ProbePart o_oq = im.out(stage == WS_FC1 ? (size_t)M + 32 : 0), o_od = im.out(stage == WS_FC1 ? nb * 4 : 0), o_os = im.out(stage == WS_FC1 ? nb * 4 : 0);
+    if (!im.upload()) return -2;
+    bgk::WdecParams p{};
+    p.W = wr.W(im);
+    p.eps = 1e-5f; p.bias = im.at<const float>(o_bias);
+    if (ln) { p.x = im.at<const float>(o_x); p.ln_w = im.at<const float>(o_lw); p.ln_b = im.at<const float>(o_lb); }
+    else { p.aq_q = im.at<const int8_t>(o_aq); p.aq_d = im.at<const float>(o_ad); p.aq_s = im.at<const uint32_t>(o_as); }
+    if (res) { p.resid = im.at<const float>(o_res); p.out = im.at<float>(o_out); }
+    if (stage == WS_QKV) {
+        p.q_out = im.at<float>(o_out); p.kcache = im.at<float>(o_k); p.vcache = im.at<float>(o_v);
+        p.D = K; p.P = P; p.q_scale = 1.0f / sqrtf(64.0f); p.st = im.at<const bgk::DevState>(o_ds);
+    }
+    if (stage == WS_FC1) { p.gelu_tab = im.at<const uint16_t>(o_tab); p.oq_q = im.at<int8_t>(o_oq); p.oq_d = im.at<float>(o_od); p.oq_s = im.at<uint32_t>(o_os); }
+    auto launch = [&]() -> hipError_t { return (hipError_t)bg_wdec_launch(wtype, stage, &p, sizeof(p), 0, four); };
+    HIP_TRY(-2, launch());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    report_launch(launched, {four[0], four[1], four[2], four[3]});
+    if (stage == WS_FC1) { if (!im.read(o_oq, out_q) || !im.read(o_od, out_d) || !im.read(o_os, out_s)) return -2; }
+    else if (!im.read(o_out, out) || !im.read(o_k, k_cache) || !im.read(o_v, v_cache)) return -2;
+    return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+}

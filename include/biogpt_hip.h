@@ -218,6 +218,27 @@ int biogpt_hip_get_assoc_chain(const biogpt_hip_ctx *ctx);
 /* Linear-stage launches of the SIMD chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
  * switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_simd_chain_launches(const biogpt_hip_ctx *ctx);
+/* The wide decode layer's switch, per context (initial value: BIOGPT_HIP_WIDE_DECODE=0/1, default 1 on the files it serves).  It serves block-quantized files that are not BioGPT-base
+ * with head size 64, d_model a multiple of 64 and d_ff of 32 (BioGPT-Large: 1600 / 6400 / 25 heads), in all five formats.  on 1: one token of the context's own
+ * column with the last row wanted -- a single-token biogpt_hip_eval / eval_device / eval_topk / the compat layer's biogpt_eval, and every step of
+ * biogpt_hip_generate_greedy, captured steps included -- runs its layers on csrc/kernels_wdecode.hip.h: five launches per layer (q/k/v behind one LayerNorm per
+ * workgroup, attention, out_proj, fc1 with its Q8 hand-off, fc2), at any context up to n_positions.  Logits, K / V rows and ids are bit for bit those of the
+ * generic route, and the cache layout is shared with it, so chunk evals and single tokens mix freely.  Evals of 2 or more tokens, every pass over column states,
+ * BioGPT-base files, float files and a context while it is in the SIMD association keep the launches they have.  The switch is a property of the context: on a
+ * context in the SIMD association the call succeeds (0) and is remembered, its launches stay the association's, and it takes effect when biogpt_hip_assoc(ctx, 0)
+ * returns the context to the scalar association (as biogpt_hip_assoc_chain is inert in mode 0).  Not while a queue session is open or a call of
+ * the context is running.  Drops the captured single-token steps.  Returns 0; 1 when the file is not one the layer serves: nothing changed, and
+ * biogpt_hip_last_error says why ("not served: ..."); -1 with a message on a bad argument; -2 on a HIP error. */
+int biogpt_hip_wide_decode(biogpt_hip_ctx *ctx, int on);
+/* The wide decode layer's switch: 0 off, 1 on.  -1: ctx is NULL. */
+int biogpt_hip_get_wide_decode(const biogpt_hip_ctx *ctx);
+/* Layer-stage launches of the wide decode layer enqueued or captured (five per layer and token: q/k/v, attention, out_proj, fc1, fc2; a captured step counts
+ * once, when it is captured, not per replay); 0 for ever while the switch is off.  -1: ctx is NULL. */
+int64_t biogpt_hip_wide_decode_launches(const biogpt_hip_ctx *ctx);
+/* The key counts at which the wide decode layer's attention launch changes form: up to the first / second / third, dec_attn_kernel at 16 / 8 / 4 lanes per key;
+ * beyond the third the generic route's attention launch, which writes out_proj's Q8 blocks itself up to the fourth (1024) and leaves them to a q8_rows_kernel
+ * launch beyond it.  Returns how many there are; out (may be NULL) takes the first cap of them. */
+int biogpt_hip_wide_decode_key_borders(int32_t *out, int cap);
 /* Linear-stage launches of the float chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
  * switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_float_launches(const biogpt_hip_ctx *ctx);
@@ -530,6 +551,20 @@ int biogpt_hip_schain_device(int device, int32_t stage, int32_t wtype, int32_t e
  * the SIMD chain's stage with the residual epilogue at tile shape cfg (-1: the launch's choice); 1: its Q8 producer; 2: the SIMD mat-vec a context's own pass in
  * mode 1 launches at N columns; 3: the wide chain's matrix-core stage of the scalar association (M a multiple of 16), for scale.  tools/simd_chain_bench.py. */
 int biogpt_hip_schain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, int32_t reps, float *us_out);
+/* One stand-alone run of a kernel of the wide decode layer (csrc/kernels_wdecode.hip.h) over caller-supplied rows, through the layer's own launch functions.  No
+ * model, no context; one token, so one column; wtype one of the five block formats, w_rows [M] rows of K values in the file's format.
+ *   stage 0 QKV: x, ln_w, ln_b [K], bias [M], M == 3 K, 64 | K; k_cache / v_cache [K / 64][P][64] are updated in place at row n_past; out [K + 16]: the scaled q row.
+ *   stage 1 ATTN: q [H * 64], k_cache / v_cache [H][P][64], n_past + 1 keys (at most the third border of biogpt_hip_wide_decode_key_borders, 256, and P);
+ *     out [H * 64 + 16], out_q [H * 64 + 32], out_d / out_s [2 H + 1]: the f32 row and its Q8 blocks (the form of wtype's activations).
+ *   stage 2 OPROJ, 4 FC2: aq_q [K], aq_d / aq_s [K / 32] (the producer's blocks), bias, resid [M]; out [M + 16].
+ *   stage 3 FC1: x, ln_w, ln_b [K], bias [M], 32 | M; out_q [M + 32], out_d / out_s [M / 32 + 1]: the GELU outputs as fc2's Q8 blocks.
+ * Outputs come back whole, as allocated and preset to 0xff bytes: what lies behind the row is guard.  launched [8] (may be NULL): linear stages: threads, grid,
+ * dynamic LDS bytes, most rows of a workgroup; ATTN: threads, grid, lanes per key.  reps > 0: behind the checked launch, reps launches timed each between two
+ * device events, microseconds into us_out [reps] (tools/wide_decode_bench.py).  Returns 0, -1 on a bad argument (before any HIP call), -2 on a HIP error. */
+int biogpt_hip_wdecode_device(int device, int32_t stage, int32_t wtype, int32_t M, int32_t K, int32_t H, int32_t P, int32_t n_past, int32_t reps, const void *w_rows,
+                              const float *x, const float *ln_w, const float *ln_b, const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias,
+                              const float *resid, const float *q, float *k_cache, float *v_cache, float *out, int8_t *out_q, float *out_d, uint32_t *out_s,
+                              int32_t *launched, float *us_out);
 /* One stand-alone run of a stage of the embedding tail (ln_rows_kernel<1024> / <0>, pool_rows_kernel, pool_finish_kernel, head_rows_kernel) over caller-supplied
  * rows, through the launch code of biogpt_hip_hidden / biogpt_hip_embed_batch.  No model, no context; W a multiple of 4.  stage 0 LN: x [n_rows][W], ln_w / ln_b
  * [W]; W == 1024 takes the <1024> template, any other width <0>; seq_states (may be NULL) [n_rows][8] words with slot_div >= 1 and P: row i lands at row
