@@ -448,44 +448,50 @@ __device__ __forceinline__ void xp_settle(Unit<WT> &u) {
     }
 }
 
-// sum of one unsigned value per lane over the wave, uniform result (4 DPP adds, 4 v_readlane, scalar adds)
+// sum of one unsigned value per lane over the wave, uniform result (4 DPP adds, 4 v_readlane, scalar adds); unsigned arithmetic: sums up to 2^32 - 1
 __device__ __forceinline__ uint32_t xp_wave_sum_u32(uint32_t v) {
-    int s = (int)v;
-    s += dpp_i<DPP_QUAD_XOR1>(s); s += dpp_i<DPP_QUAD_XOR2>(s); s += dpp_i<DPP_ROW_HALF_MIRROR>(s); s += dpp_i<DPP_ROW_MIRROR>(s);
-    return (uint32_t)((__builtin_amdgcn_readlane(s, 0) + __builtin_amdgcn_readlane(s, 16)) + (__builtin_amdgcn_readlane(s, 32) + __builtin_amdgcn_readlane(s, 48)));
+    uint32_t s = v;
+    s += (uint32_t)dpp_i<DPP_QUAD_XOR1>((int)s); s += (uint32_t)dpp_i<DPP_QUAD_XOR2>((int)s);
+    s += (uint32_t)dpp_i<DPP_ROW_HALF_MIRROR>((int)s); s += (uint32_t)dpp_i<DPP_ROW_MIRROR>((int)s);
+    return ((uint32_t)__builtin_amdgcn_readlane((int)s, 0) + (uint32_t)__builtin_amdgcn_readlane((int)s, 16)) +
+           ((uint32_t)__builtin_amdgcn_readlane((int)s, 32) + (uint32_t)__builtin_amdgcn_readlane((int)s, 48));
 }
 
-// PV over the first n (wave-uniform) of a wave's NV key slots, in slot order: slot K's value row element vr[K] times its softmax weight (lane K of wv, or with
-// STEP != 0 lane lane0 + STEP K, taken as a wave-uniform operand) goes into a0 (K even) or a1 (K odd).  Nested scalar branches instead of a loop with an exit
+// PV over the first n (wave-uniform) of a wave's NV key slots, in slot order: slot K's value row element vr[K] times its softmax weight goes into a0 (K even) or
+// a1 (K odd).  The weight is taken as a wave-uniform operand (v_readlane): with STEP == 0 from lane K of wv[0]; with STEP != 0 (the one-exchange softmax: lane j
+// of wv[c] holds key j + 64 c, and slot K of the wave is key lane0 + STEP K) from lane lane0 + STEP (K mod 64 / STEP) of wv[K STEP / 64] -- register and lane
+// offset are compile-time choices.  Nested scalar branches instead of a loop with an exit
 // (the compiler does not unroll a loop with a run-time exit around v_readlane, and re-rolled it indexes vr[] dynamically): whole groups of four slots first
 // -- four independent products in flight, two additions per accumulator -- then the up to three slots that are left, one branch each.
 struct XpPvAcc { double a0, a1; };
-template <int K, int NV, int STEP>
-__device__ __forceinline__ void xp_pv_key(const float (&vr)[NV], const float wv, const int lane0, XpPvAcc &a) {
-    const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wv), STEP ? lane0 + STEP * K : K));
+template <int K, int NV, int STEP, int NC>
+__device__ __forceinline__ void xp_pv_key(const float (&vr)[NV], const float (&wv)[NC], const int lane0, XpPvAcc &a) {
+    constexpr int C = STEP ? K * STEP / 64 : 0, KL = STEP ? K % (64 / STEP) : K;
+    static_assert(C < NC, "the slot's key lies in one of the wave's weight registers");
+    const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wv[C]), STEP ? lane0 + STEP * KL : KL));
     const double c = (double)__fmul_rn(vr[K], w);
     if constexpr (K & 1) a.a1 += c; else a.a0 += c;
 }
-template <int K, int KEND, int NV, int STEP>
-__device__ __forceinline__ XpPvAcc xp_pv_rest(const int n, const float (&vr)[NV], const float wv, const int lane0, XpPvAcc a) {
+template <int K, int KEND, int NV, int STEP, int NC>
+__device__ __forceinline__ XpPvAcc xp_pv_rest(const int n, const float (&vr)[NV], const float (&wv)[NC], const int lane0, XpPvAcc a) {
     if constexpr (K < KEND) {
         if (K < n) {
-            xp_pv_key<K, NV, STEP>(vr, wv, lane0, a);
-            return xp_pv_rest<K + 1, KEND, NV, STEP>(n, vr, wv, lane0, a);
+            xp_pv_key<K, NV, STEP, NC>(vr, wv, lane0, a);
+            return xp_pv_rest<K + 1, KEND, NV, STEP, NC>(n, vr, wv, lane0, a);
         }
     }
     return a;
 }
-template <int K, int NV, int STEP>
-__device__ __forceinline__ XpPvAcc xp_pv_old_keys(const int n, const float (&vr)[NV], const float wv, const int lane0, XpPvAcc a) {
+template <int K, int NV, int STEP, int NC>
+__device__ __forceinline__ XpPvAcc xp_pv_old_keys(const int n, const float (&vr)[NV], const float (&wv)[NC], const int lane0, XpPvAcc a) {
     static_assert(NV % 4 == 0 && K % 4 == 0, "groups of four slots");
     if constexpr (K < NV) {
         if (K + 4 <= n) {
-            xp_pv_key<K, NV, STEP>(vr, wv, lane0, a); xp_pv_key<K + 1, NV, STEP>(vr, wv, lane0, a);
-            xp_pv_key<K + 2, NV, STEP>(vr, wv, lane0, a); xp_pv_key<K + 3, NV, STEP>(vr, wv, lane0, a);
-            return xp_pv_old_keys<K + 4, NV, STEP>(n, vr, wv, lane0, a);
+            xp_pv_key<K, NV, STEP, NC>(vr, wv, lane0, a); xp_pv_key<K + 1, NV, STEP, NC>(vr, wv, lane0, a);
+            xp_pv_key<K + 2, NV, STEP, NC>(vr, wv, lane0, a); xp_pv_key<K + 3, NV, STEP, NC>(vr, wv, lane0, a);
+            return xp_pv_old_keys<K + 4, NV, STEP, NC>(n, vr, wv, lane0, a);
         }
-        return xp_pv_rest<K, K + 3, NV, STEP>(n, vr, wv, lane0, a);
+        return xp_pv_rest<K, K + 3, NV, STEP, NC>(n, vr, wv, lane0, a);
     }
     return a;
 }
@@ -1071,15 +1077,21 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
                 if (jg < T && !(LATE_KV && jg == n_past)) sc = key_score(kr);
             }
             static_assert(NW == 8, "key j = wave + 8 k sits in lane (wave + 8 k) & 63 of slot k >> 3");
-            constexpr bool SMW = KCAP <= 64;      // (measured: -1.5 us per token with 64 keys, +-0 with 128, +1 / +9 us with 192 / 256 -- 2-4 look-ups per lane and 16-32 v_readlane per wave)
+            // (measured against two exchanges: -1.5 us per token with 64 keys; with 128 keys -- two numerator registers per lane, PV weights by register and lane
+            // -- 1.5 - 2.5 us per token less inside multi-token launches in three builds against two, while the stage lines of a single-token launch move by no
+            // more than 0.03 us ("scores + max" + 0.03, "exp + sum" - 0.02 .. - 0.05); with 192 keys -- three registers, the own key's score formed by every wave
+            // behind the barrier -- + 4 us per token, + 0.25 us per layer: profiles/softmax_exchange_ab.txt)
+            constexpr bool SMW = KCAP <= 128;
             constexpr int KC = (KCAP + 63) / 64;
             [[maybe_unused]] float ev[KC];
             float inv;
             if constexpr (SMW) {
                 // One exchange instead of two: the scores go to LDS, and behind ONE barrier every wave works the softmax out for itself -- the maximum, the
-                // table look-ups and the sum of all keys (<= 4 per lane), identically in the 8 waves -- so that the PV lanes take their weights from the wave's
-                // own registers (v_readlane).  The sum of the numerators is formed in integers: they are fp16 values <= 1.0 (exp of a non-positive argument),
-                // i.e. multiples of 2^-24, <= 256 of them: sums of the low and high 16 bits of value * 2^24, exact -- as the reference's double sum is.
+                // table look-ups and the sum of all keys (KC per lane: lane j holds keys j + 64 c), identically in the 8 waves -- so that the PV lanes take
+                // their weights from the wave's own registers (v_readlane).  The sum of the numerators is formed in integers: they are fp16 values <= 1.0
+                // (exp of a non-positive argument), i.e. multiples of 2^-24, so value * 2^24 is an integer <= 2^24, and fewer than 256 of them sum below
+                // 2^32: one unsigned sum, exact -- as the reference's double sum is in any order -- and inv_sum_f32 sees the same double.
+                static_assert(KCAP < 256, "numerators * 2^24 of every key sum below 2^32");
                 if (ksub == 0) s_S[kidx] = sc;      // every key slot of the variant: -inf beyond the context (and, LATE_KV, for the token's own key)
                 __syncthreads();                    // the scores -- and (LATE_KV) the token's k / v rows in s_cur
                 float scl[KC];
@@ -1099,7 +1111,7 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
                 for (int c = 1; c < KC; c++) mx = fmaxf(mx, scl[c]);
                 mx = wave_max_f32(mx);
                 XP_WALL(13);
-                uint32_t ulo = 0u, uhi = 0u;
+                uint32_t usum = 0u;
 #pragma unroll
                 for (int c = 0; c < KC; c++) {
                     float val = 0.0f;
@@ -1114,12 +1126,9 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
                         val = h2f(e16);
                     }
                     ev[c] = val;
-                    const uint32_t u = (uint32_t)__fmul_rn(val, 16777216.0f);
-                    ulo += u & 0xFFFFu; uhi += u >> 16;
+                    usum += (uint32_t)__fmul_rn(val, 16777216.0f);
                 }
-                ulo = xp_wave_sum_u32(ulo); uhi = xp_wave_sum_u32(uhi);
-                const double sum = ((double)uhi * 65536.0 + (double)ulo) * 0x1p-24;
-                inv = inv_sum_f32(sum);
+                inv = inv_sum_f32((double)xp_wave_sum_u32(usum) * 0x1p-24);
             } else {
                 if constexpr (LATE_KV) {
                     __syncthreads();      // the token's k / v rows are in s_cur
@@ -1169,6 +1178,8 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
                     if (ksub == 0) s_S[kidx] = val;
                     sum = (double)val;
                 }
+                // (an integer sum here too -- low and high 16 bits of value * 2^24 through LDS as 8 pairs -- was measured: the stage's "exp + sum" line
+                // 0.02 - 0.04 us shorter at 160 keys, no shorter at 230, the multi-token launches 1 - 3 us per token SLOWER in each of three builds)
                 sum = wave_sum_f64(sum);
                 if (lane == 0) s_redd[wave] = sum;
                 __syncthreads();
@@ -1188,16 +1199,22 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
                 // rounded products) in the same order per accumulator -- the own key's slot is the last one that is not past the context.
                 const float vcur = s_cur[128 + dd];
                 const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-                float wv;
-                if constexpr (SMW) wv = __fmul_rn(ev[0], inv);      // lane j: key j (<= 64 keys)
-                else wv = __fmul_rn(s_S[wave_u + NW * min(lane, NV - 1)], inv);      // lane k < NV: slot k of this wave (the other lanes' copies are not used)
+                constexpr int NC = SMW ? KC : 1;
+                float wv[NC];
+                if constexpr (SMW) {
+#pragma unroll
+                    for (int c = 0; c < KC; c++) wv[c] = __fmul_rn(ev[c], inv);      // lane j of wv[c]: key j + 64 c
+                } else wv[0] = __fmul_rn(s_S[wave_u + NW * min(lane, NV - 1)], inv);      // lane k < NV: slot k of this wave (the other lanes' copies are not used)
                 int own = n_past;
                 asm volatile("" : "+s"(own));      // (what follows from it is recomputed in every layer, not kept in scalar registers over the layer loop)
                 own -= HI * KW;                    // the token's own key, counted inside this workgroup's keys
                 const int n_old = __builtin_amdgcn_readfirstlane(min(max(own - wave_u + NW - 1, 0) / NW, NV));      // this wave's keys j < n_past
-                XpPvAcc acc = xp_pv_old_keys<0, NV, SMW ? NW : 0>(n_old, vr, wv, wave_u, XpPvAcc{0.0, 0.0});
+                XpPvAcc acc = xp_pv_old_keys<0, NV, SMW ? NW : 0, NC>(n_old, vr, wv, wave_u, XpPvAcc{0.0, 0.0});
                 if (own >= 0 && own < KW && (own & (NW - 1)) == wave_u) {      // the own key is this wave's: its slot n_old, the last one that is not past the context
-                    const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wv), SMW ? own : n_old));
+                    float wo = wv[0];      // (one-exchange softmax: key own sits in lane own mod 64 of wv[own / 64] -- a wave-uniform choice)
+#pragma unroll
+                    for (int c = 1; c < NC; c++) if (own >= 64 * c) wo = wv[c];
+                    const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wo), SMW ? (own & 63) : n_old));
                     const double c = (double)__fmul_rn(vcur, w);
                     if (n_old & 1) { acc.a1 += c; asm volatile("" : "+v"(acc.a1)); }      // (the empty asm keeps the scalar branch: one addition, no selects)
                     else acc.a0 += c;
@@ -1207,9 +1224,17 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
             __syncthreads();
             XP_WALL(15);
             if (tid < DK) {
-                double t0 = 0.0, t1 = 0.0;
+                // The eight slice sums are read together (the empty asm: left alone the compiler issues the reads one or two at a time, each between the
+                // additions of the one before -- three LDS round trips in a row) and added in the order t0 = s0 + s2 + s4 + s6, t1 = s1 + s3 + s5 + s7, t0 + t1.
+                // The sums start from s0 and s1, not from +0.0: no slice sum is -0.0 (the sum of two accumulators that never hold -0.0, above), and
+                // (+0.0) + x = x for every other x.
+                double sl[NW];
 #pragma unroll
-                for (int s2 = 0; s2 < NW; s2 += 2) { t0 += s_pv[s2 * DK + tid]; t1 += s_pv[(s2 + 1) * DK + tid]; }
+                for (int s2 = 0; s2 < NW; s2++) sl[s2] = s_pv[s2 * DK + tid];
+                asm volatile("" : "+v"(sl[0]), "+v"(sl[1]), "+v"(sl[2]), "+v"(sl[3]), "+v"(sl[4]), "+v"(sl[5]), "+v"(sl[6]), "+v"(sl[7]));
+                double t0 = sl[0], t1 = sl[1];
+#pragma unroll
+                for (int s2 = 2; s2 < NW; s2 += 2) { t0 += sl[s2]; t1 += sl[s2 + 1]; }
                 double tot = t0 + t1;
                 [[maybe_unused]] xp_u64 *const gpv = DUAL ? p.gran_l + (size_t)L * XL_G_LAYER + XL_G_PV + head * 16 * 128 : nullptr;
                 if constexpr (DUAL && HI == 1) {      // the upper keys' partial sums go to the head's first workgroup
@@ -1224,6 +1249,8 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
                     int8_t q8; float d8; uint32_t s8;
                     q8_block32(o, TI::q81, q8, d8, s8, TI::q81);
                     const uint32_t packed = xp_pack4(q8);
+                    // (quants, scale and block sum in ONE store instruction -- lanes 0, 4, .. the quants, lanes 1 and 2 of a block its scale and sum -- costs the
+                    // resident 192-key kernel 8 more spilled scalar registers, profiles/softmax_exchange_ab.txt: two stores, or three, as before)
                     const int blk = head * 2 + (tid >> 5);
                     if ((tid & 3) == 0) xp_put_local(G + XP_G_ATT + head * 16 + (tid >> 2), etag, packed);
                     if ((tid & 31) == 0) { xp_put_local(G + XP_G_ATT + 256 + blk, etag, __float_as_uint(d8)); if (TI::q81) xp_put_local(G + XP_G_ATT + 288 + blk, etag, s8); }
