@@ -2239,3 +2239,61 @@ int biogpt_hip_wdecode_device(int device, int32_t stage, int32_t wtype, int32_t 
     else if (!im.read(o_out, out) || !im.read(o_k, k_cache) || !im.read(o_v, v_cache)) return -2;
     return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
 }
+
+// ---- a linear stage of the wide chunk layer alone (kernels_wchunk.hip.h), through the launch function enqueue_wchunk_layer uses ----
+// N columns, 2 <= N <= 8.  Every stage reads a producer's blocks aq_q [N][K], aq_d / aq_s [N][K / 32], and bias [M].  stage 0 QKV: M == 3 K, 64 | K, dev_state
+//   {n_past, ..}: column c at position n_past + c of the one slot k_slots / v_slots [K / 64][P][64], updated in place; out [N + 1][K].  stage 2 OPROJ / 4 FC2:
+//   resid [N][M]; out [N + 1][M].  stage 3 FC1: 32 | M; out_q [N + 1][M], out_d / out_s [N + 1][M / 32].
+// The outputs come back WHOLE as allocated and preset to 0xff bytes: row N is guard.  launched [8]: threads, grid, LDS bytes, most rows of a workgroup.  N and
+// the shape are refused by name before any HIP call; an LDS request beyond the device's behind hipSetDevice, before any launch.
+int biogpt_hip_wchunk_device(int device, int32_t stage, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t P, int32_t reps, const void *w_rows, const int8_t *aq_q,
+                             const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid, const int32_t *dev_state, float *k_slots, float *v_slots,
+                             float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched, float *us_out) {
+    clear_error();
+    if (stage != WS_QKV && stage != WS_OPROJ && stage != WS_FC1 && stage != WS_FC2) BG_FAIL(-1, "stage %d is no linear stage (0 QKV, 2 OPROJ, 3 FC1, 4 FC2)", stage);
+    if (reps < 0 || reps > PROBE_MAX_REPS) BG_FAIL(-1, "reps must be in [0, %d]", PROBE_MAX_REPS);
+    if (reps > 0 && !us_out) BG_FAIL(-1, "us_out is NULL");
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    if (N < bgk::WCHUNK_MIN_COLS || N > bgk::WCHUNK_MAX_COLS) BG_FAIL(-1, "N = %d columns: the wide chunk layer holds %d .. %d", N, bgk::WCHUNK_MIN_COLS, bgk::WCHUNK_MAX_COLS);
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    if (bg_wchunk_geometry(stage, M, K, N, 0, nullptr)) BG_FAIL(-1, "the wide chunk layer does not hold a %d x %d matrix at stage %d and %d columns (fc1: 32 | M; a finisher thread per row and column)", M, K, stage, N);
+    if (!w_rows || !bias || !aq_q || !aq_d || !aq_s) BG_FAIL(-1, "w_rows, bias, aq_q, aq_d or aq_s is NULL");
+    const bool qkv = stage == WS_QKV, fc1 = stage == WS_FC1, res = stage == WS_OPROJ || stage == WS_FC2;
+    if (res && !resid) BG_FAIL(-1, "resid is NULL");
+    if (!fc1 && !out) BG_FAIL(-1, "out is NULL");
+    if (fc1 && (!out_q || !out_d || !out_s)) BG_FAIL(-1, "out_q, out_d or out_s is NULL");
+    if (qkv && (K % 64 != 0 || M != 3 * K)) BG_FAIL(-1, "q/k/v is 3 K x K with heads of 64 (got %d x %d)", M, K);
+    if (!check_probe_columns(__func__, qkv, N, dev_state, nullptr, 0, P, 1, k_slots, v_slots)) return -1;
+    HIP_TRY(-2, hipSetDevice(device));
+    int32_t four[4] = {0, 0, 0, 0};
+    if (bg_wchunk_geometry(stage, M, K, N, -1, four)) BG_FAIL(-1, "the wide chunk layer's %d x %d stage %d asks for more LDS at %d columns than a workgroup of this device gets", M, K, stage, N);
+    const size_t bpr = (size_t)K / QK, kv_b = qkv ? (size_t)K * P * 4 : 0, ldo = qkv ? (size_t)K : (size_t)M;
+    ProbeImage im;      // [weights | codes | d | s | bias | resid | state | GELU table | K | V | out | codes | d | s], one guard row behind every output
+    const BlockRows wr = upload_block_rows(im, wtype, w_rows, M, K, false);
+    const ProbePart o_aq = im.in(aq_q, (size_t)N * K), o_ad = im.in(aq_d, (size_t)N * bpr * 4), o_as = im.in(aq_s, (size_t)N * bpr * 4);
+    const ProbePart o_bias = im.in(bias, (size_t)M * 4), o_res = im.in(res ? resid : nullptr, (size_t)N * M * 4);
+    const ProbePart o_ds = im.in(dev_state ? dev_state : PROBE_NO_STATE, sizeof(bgk::DevState)), o_tab = im.own(gelu_table_f16());
+    const ProbePart o_k = im.in(qkv ? k_slots : nullptr, kv_b), o_v = im.in(qkv ? v_slots : nullptr, kv_b);
+    const size_t rows = (size_t)N + 1;
+    const ProbePart o_out = im.out(fc1 ? 0 : rows * ldo * 4);
+    const ProbePart o_oq = im.out(fc1 ? rows * M : 0), o_od = im.out(fc1 ? rows * (M / 32) * 4 : 0), o_os = im.out(fc1 ? rows * (M / 32) * 4 : 0);
+    if (!im.upload()) return -2;
+    bgk::WchunkParams p{};
+    p.W = wr.W(im); p.N = N;
+    p.aq_q = im.at<const int8_t>(o_aq); p.aq_d = im.at<const float>(o_ad); p.aq_s = im.at<const uint32_t>(o_as);
+    p.bias = im.at<const float>(o_bias);
+    if (res) { p.resid = im.at<const float>(o_res); p.out = im.at<float>(o_out); }
+    if (qkv) {
+        p.q_out = im.at<float>(o_out); p.kcache = im.at<float>(o_k); p.vcache = im.at<float>(o_v);
+        p.D = K; p.P = P; p.q_scale = 1.0f / sqrtf(64.0f); p.st = im.at<const bgk::DevState>(o_ds);
+    }
+    if (fc1) { p.gelu_tab = im.at<const uint16_t>(o_tab); p.oq_q = im.at<int8_t>(o_oq); p.oq_d = im.at<float>(o_od); p.oq_s = im.at<uint32_t>(o_os); }
+    auto launch = [&]() -> hipError_t { return (hipError_t)bg_wchunk_launch(wtype, stage, &p, sizeof(p), 0, four); };
+    HIP_TRY(-2, launch());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    report_launch(launched, {four[0], four[1], four[2], four[3]});
+    if (fc1) { if (!im.read(o_oq, out_q) || !im.read(o_od, out_d) || !im.read(o_os, out_s)) return -2; }
+    else if (!im.read(o_out, out) || !im.read(o_k, k_slots) || !im.read(o_v, v_slots)) return -2;
+    return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+}

@@ -239,6 +239,20 @@ int64_t biogpt_hip_wide_decode_launches(const biogpt_hip_ctx *ctx);
  * beyond the third the generic route's attention launch, which writes out_proj's Q8 blocks itself up to the fourth (1024) and leaves them to a q8_rows_kernel
  * launch beyond it.  Returns how many there are; out (may be NULL) takes the first cap of them. */
 int biogpt_hip_wide_decode_key_borders(int32_t *out, int cap);
+/* The wide chunk layer's switch, per context (initial value: BIOGPT_HIP_WIDE_CHUNK=0/1, default 1 on the files it serves).  It serves the files of the wide decode layer.  on 1: an eval of
+ * 2 .. 8 tokens of the context's own columns with the last row wanted, up to 1024 keys -- biogpt_hip_eval / eval_device / eval_topk / the compat layer's
+ * biogpt_eval (the reference's prompt loop of n_batch = 8) and the prompt chunks of biogpt_hip_generate_greedy -- runs its layers on csrc/kernels_wchunk.hip.h:
+ * seven launches per layer (LayerNorm + Q8 of the columns, q/k/v, attention, out_proj, LayerNorm + Q8, fc1 with its Q8 hand-off, fc2).  Logits, K / V rows and
+ * ids are bit for bit those of the generic route, and the cache layout is shared with it.  Single tokens, evals of more than 8 tokens or beyond 1024 keys, passes
+ * that want every row, every pass over column states, BioGPT-base files, float files, a context while it is in the SIMD association, and a device whose
+ * workgroups cannot have the LDS the stage asks for keep the launches they have.  Legality and return values are those of biogpt_hip_wide_decode: not while a
+ * queue session is open or a call of the context is running; 1 with "not served: ..." in biogpt_hip_last_error on a file the layer does not serve. */
+int biogpt_hip_wide_chunk(biogpt_hip_ctx *ctx, int on);
+/* The wide chunk layer's switch: 0 off, 1 on.  -1: ctx is NULL. */
+int biogpt_hip_get_wide_chunk(const biogpt_hip_ctx *ctx);
+/* Launches of the wide chunk layer enqueued (seven per layer and eval: two LayerNorm + Q8 producers, q/k/v, attention, out_proj, fc1, fc2); 0 for ever while the
+ * switch is off.  -1: ctx is NULL. */
+int64_t biogpt_hip_wide_chunk_launches(const biogpt_hip_ctx *ctx);
 /* Linear-stage launches of the float chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
  * switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_float_launches(const biogpt_hip_ctx *ctx);
@@ -565,6 +579,20 @@ int biogpt_hip_wdecode_device(int device, int32_t stage, int32_t wtype, int32_t 
                               const float *x, const float *ln_w, const float *ln_b, const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias,
                               const float *resid, const float *q, float *k_cache, float *v_cache, float *out, int8_t *out_q, float *out_d, uint32_t *out_s,
                               int32_t *launched, float *us_out);
+/* One stand-alone run of a linear stage of the wide chunk layer (csrc/kernels_wchunk.hip.h) over caller-supplied rows, through the layer's own launch function.
+ * No model, no context; N columns, 2 <= N <= 8; wtype one of the five block formats, w_rows [M] rows of K values in the file's format.  Every stage reads a
+ * producer's blocks: aq_q [N][K], aq_d / aq_s [N][K / 32], and bias [M].
+ *   stage 0 QKV: M == 3 K, 64 | K; dev_state [4] words {n_past, 0, 0, 0}: column c is position n_past + c of the one slot k_slots / v_slots [K / 64][P][64],
+ *     updated in place; out [N + 1][K]: the scaled q rows.
+ *   stage 2 OPROJ, 4 FC2: resid [N][M]; out [N + 1][M].
+ *   stage 3 FC1: 32 | M; out_q [N + 1][M], out_d / out_s [N + 1][M / 32]: the GELU outputs as fc2's Q8 blocks.
+ * Outputs come back whole, as allocated and preset to 0xff bytes: row N is guard.  launched [8] (may be NULL): threads, grid, dynamic LDS bytes, most rows of a
+ * workgroup.  reps > 0: behind the checked launch, reps launches timed each between two device events, microseconds into us_out [reps]
+ * (tools/wide_chunk_bench.py).  Returns 0; -1 on a bad argument -- N outside [2, 8] and a shape the layer's geometry does not hold before any HIP call, an LDS
+ * request beyond what the device gives a workgroup behind hipSetDevice and before any launch; -2 on a HIP error. */
+int biogpt_hip_wchunk_device(int device, int32_t stage, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t P, int32_t reps, const void *w_rows, const int8_t *aq_q,
+                             const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid, const int32_t *dev_state, float *k_slots, float *v_slots,
+                             float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched, float *us_out);
 /* One stand-alone run of a stage of the embedding tail (ln_rows_kernel<1024> / <0>, pool_rows_kernel, pool_finish_kernel, head_rows_kernel) over caller-supplied
  * rows, through the launch code of biogpt_hip_hidden / biogpt_hip_embed_batch.  No model, no context; W a multiple of 4.  stage 0 LN: x [n_rows][W], ln_w / ln_b
  * [W]; W == 1024 takes the <1024> template, any other width <0>; seq_states (may be NULL) [n_rows][8] words with slot_div >= 1 and P: row i lands at row
