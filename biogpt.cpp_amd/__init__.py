@@ -843,6 +843,9 @@ SYMBOLS = [
     ("biogpt_hip_wide_chunk", C.c_int, [_P, C.c_int]),
     ("biogpt_hip_get_wide_chunk", C.c_int, [_P]),
     ("biogpt_hip_wide_chunk_launches", C.c_int64, [_P]),
+    ("biogpt_hip_wide_pass", C.c_int, [_P, C.c_int]),
+    ("biogpt_hip_get_wide_pass", C.c_int, [_P]),
+    ("biogpt_hip_wide_pass_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_stamps", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     ("biogpt_hip_generate_launches", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
@@ -947,6 +950,7 @@ SYMBOLS = [
     ("biogpt_hip_schain_device", C.c_int, [C.c_int] + [C.c_int32] * 12 + [_P] * 16),
     ("biogpt_hip_wdecode_device", C.c_int, [C.c_int] + [C.c_int32] * 8 + [_P] * 18),
     ("biogpt_hip_wchunk_device", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 15),
+    ("biogpt_hip_wpass_device", C.c_int, [C.c_int] + [C.c_int32] * 9 + [_P] * 15),
     ("biogpt_hip_schain_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P]),
     ("biogpt_hip_embed_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 4 + [C.c_int32] * 5 + [_P] + [C.c_int32] * 2 + [_P] * 3 + [C.c_int32] + [_P] * 3),
     ("biogpt_hip_tail_device", C.c_int, [C.c_int] + [C.c_int32] * 3 + [_P] * 7 + [C.c_int32] * 2 + [_P] + [C.c_int32] * 3 + [_P] * 5),
@@ -1399,6 +1403,50 @@ def wchunk_device(stage, wtype, M, K, N, w_rows=None, aq=None, bias=None, resid=
     return res
 
 
+WPASS_SITES = {"QKV": 0, "RESID": 1, "LOGITS": 3, "FC1": 4}
+
+
+def wpass_device(site, wtype, M, K, N, w_rows=None, aq=None, bias=None, resid=None, k_cache=None, v_cache=None, P=0, n_past=0, reps=0, which=0, cfg=-1, device=0):
+    """One stand-alone run of a linear stage of the wide pass layer on N >= 9 columns (biogpt_hip_wpass_device).  Every site reads a producer's blocks: aq =
+    (codes int8 [N, K], d float32 [N, K / 32], s uint32 [N, K / 32]), and bias [M] but at "LOGITS".  site "QKV": k_cache / v_cache [K / 64, P, 64], n_past (column c
+    is position n_past + c) -> "out" [N + 1, K] (the q rows), "k", "v".  "RESID" (out_proj, fc2): resid [N, M] -> "out" [N + 1, M].  "FC1": -> "q" int8 [N + 1, M],
+    "d" / "s" [N + 1, M / 32].  "LOGITS": -> "out" [N + 1, M].  Outputs come back WHOLE, the guard row N included and preset to 0xff bytes; "launched": column
+    tiles per wave, waves per workgroup, grid x, grid y, LDS bytes, the compute units the rule counted; cfg -1: the launch shape by the engine's rule, 11 / 14 / 21 / 24:
+    column tiles per wave and waves per workgroup forced (10 CT + WPB); reps > 0: "us", the microseconds of reps timed launches (which=1: of the wide chain's kernel
+    at the same site).  Raises BiogptError on a refusal."""
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    st = WPASS_SITES[site] if isinstance(site, str) else int(site)
+    M, K, N, P = int(M), int(K), int(N), int(P)
+    rows, res = max(N, 0) + 1, {}
+    if st == 4:
+        res["q"], res["d"], res["s"] = np.zeros((rows, max(M, 0)), np.int8), np.zeros((rows, max(M, 0) // 32), np.float32), np.zeros((rows, max(M, 0) // 32), np.uint32)
+    else:
+        res["out"] = np.zeros((rows, max(K if st == 0 else M, 0)), np.float32)
+    if st == 0 and k_cache is not None and v_cache is not None:
+        res["k"], res["v"] = np.array(k_cache, dtype=np.float32, order="C"), np.array(v_cache, dtype=np.float32, order="C")
+    state = np.array([n_past, 0, 0, 0], np.int32) if st == 0 else None
+    launched, us = np.zeros(8, np.int32), np.zeros(max(int(reps), 1), np.float32)
+    o = lambda name: res[name].ctypes.data if name in res else None
+    aq = aq or (None, None, None)
+    rc = lib().biogpt_hip_wpass_device(int(device), st, int(wtype), M, K, N, P, int(reps), int(which), int(cfg), ptr(w_rows, np.uint8), ptr(aq[0], np.int8), ptr(aq[1], np.float32),
+                                       ptr(aq[2], np.uint32), ptr(bias, np.float32), ptr(resid, np.float32), ptr(state, np.int32), o("k"), o("v"), o("out"), o("q"),
+                                       o("d"), o("s"), launched.ctypes.data, us.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    res["launched"] = launched
+    if reps > 0:
+        res["us"] = us
+    return res
+
+
 def schain_bench(which, wtype, M, K, N, cfg=-1, reps=9, device=0):
     """A linear stage of the SIMD association alone, timed (biogpt_hip_schain_bench): microseconds of `reps` launches, float32 [reps].  which "stage": the SIMD
     chain's stage with the residual epilogue at tile shape cfg (-1: the launch's choice); "q8": its producer; "matvec": the SIMD mat-vec of a context's own pass at
@@ -1695,12 +1743,13 @@ class BiogptModel:
 
     # -- biogpt_model_load (biogpt.h:128-132) --
     @classmethod
-    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None, assoc_chain=None, wide_decode=None, wide_chunk=None):
+    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None, assoc_chain=None, wide_decode=None, wide_chunk=None, wide_pass=None):
         """float_chain=True: switch the float chain on behind the load (float_chain(); an F32 / F16 file with head size 64 only -- anything else raises).
         assoc="scalar" | "simd": set the association behind the load (set_assoc(); None: the default, scalar unless BIOGPT_HIP_ASSOC=1).
         assoc_chain=True | False: set the SIMD chain's switch behind the load (set_assoc_chain(); None: the default, off unless BIOGPT_HIP_ASSOC_CHAIN=1).
         wide_decode=True | False: set the wide decode layer's switch behind the load (set_wide_decode(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_DECODE=0).
-        wide_chunk=True | False: set the wide chunk layer's switch behind the load (set_wide_chunk(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_CHUNK=0)."""
+        wide_chunk=True | False: set the wide chunk layer's switch behind the load (set_wide_chunk(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_CHUNK=0).
+        wide_pass=True | False: set the wide pass layer's switch behind the load (set_wide_pass(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_PASS=0)."""
         if arena is None:
             m = cls(lib().biogpt_hip_load(os.fsencode(fname), device, verbosity))
         else:
@@ -1716,6 +1765,8 @@ class BiogptModel:
                 m.set_wide_decode(wide_decode)
             if wide_chunk is not None:
                 m.set_wide_chunk(wide_chunk)
+            if wide_pass is not None:
+                m.set_wide_pass(wide_pass)
         except BiogptError:
             m.close()
             raise
@@ -2526,6 +2577,29 @@ class BiogptModel:
     def wide_chunk_launches(self):
         """Launches of the wide chunk layer enqueued (biogpt_hip_wide_chunk_launches): seven per layer and eval of 2 .. 8 tokens; 0 while the switch is off."""
         return int(lib().biogpt_hip_wide_chunk_launches(self._h))
+
+    def set_wide_pass(self, on=True):
+        """The wide pass layer's switch (biogpt_hip_wide_pass): on, passes of 9 or more tokens of the context's own columns (eval, eval_all, eval_topk, eval_prompt,
+        the prompt pass of generate_greedy, score, hidden) of a block-quantized file that is not BioGPT-base run on csrc/kernels_wpass.hip.h up to 1024 keys -- the
+        same bits as off.  Returns True where the file is served, False where it is not (nothing changed; biogpt_hip_last_error then reads "not served: ...").
+        Raises BiogptError on a bad call."""
+        rc = lib().biogpt_hip_wide_pass(self._h, 1 if on else 0)
+        if rc < 0:
+            raise BiogptError(_err())
+        return rc == 0
+
+    @property
+    def wide_pass(self):
+        """Whether the wide pass layer's switch is on (biogpt_hip_get_wide_pass)."""
+        k = int(lib().biogpt_hip_get_wide_pass(self._h))
+        if k < 0:
+            raise BiogptError(_err())
+        return k == 1
+
+    def wide_pass_launches(self):
+        """Launches of the wide pass layer enqueued (biogpt_hip_wide_pass_launches): seven per layer and pass of 9 or more tokens, two more per pass that wants
+        every row; 0 while the switch is off."""
+        return int(lib().biogpt_hip_wide_pass_launches(self._h))
 
     def float_launches(self):
         """Linear-stage launches of the float chain (biogpt_hip_float_launches); 0 while the switch is off."""

@@ -37,6 +37,7 @@
 #include "kernels_decode.hip.h"
 #include "kernels_wdecode.hip.h"   // parameter block and layouts only: the kernels are instantiated in wdecode_tu.hip
 #include "kernels_wchunk.hip.h"    // likewise: wchunk_tu.hip
+#include "kernels_wpass.hip.h"     // likewise: wpass_tu.hip
 #include "kernels_q8probe.hip.h"
 #include "kernels_fdecode.hip.h"
 #include "kernels_lmhead.hip.h"
@@ -209,7 +210,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain, wide_decode, wide_chunk;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain, wide_decode, wide_chunk, wide_pass;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -244,6 +245,7 @@ struct EngineOptions {
         assoc_chain = get("BIOGPT_HIP_ASSOC_CHAIN", 0);            // 1: a new context of a file the SIMD association serves starts with the SIMD chain switched on (biogpt_hip_assoc_chain; kernels_schain.hip.h)
         wide_decode = get("BIOGPT_HIP_WIDE_DECODE", 1);          // 1 (the default: measured faster at every key count): a new context of a file the wide decode layer serves starts with it switched on; 0: off (biogpt_hip_wide_decode; kernels_wdecode.hip.h)
         wide_chunk = get("BIOGPT_HIP_WIDE_CHUNK", 1);            // 1 (the default: measured faster at every chunk size and key count): a new context of a file the wide chunk layer serves starts with it switched on; 0: off (biogpt_hip_wide_chunk; kernels_wchunk.hip.h)
+        wide_pass = get("BIOGPT_HIP_WIDE_PASS", 1);              // 1 (the default: DESIGN 4.4): a new context of a file the wide pass layer serves starts with it switched on; 0: off (biogpt_hip_wide_pass; kernels_wpass.hip.h)
         assoc = get("BIOGPT_HIP_ASSOC", 0);                        // 1: a new context of a file the SIMD association serves starts in it (biogpt_hip_assoc; kernels_assoc.hip.h)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
     }
@@ -399,6 +401,9 @@ struct biogpt_hip_ctx {
     bool wide_chunk = false;               // the wide chunk layer is switched on (biogpt_hip_wide_chunk): evals of 2 .. 8 tokens of the context's own columns run on kernels_wchunk.hip.h
     int wchunk_max_cols = -1;              // the most columns at which the layer's geometry holds all four matrices of the file on the context's device (0: none; -1: not asked yet, enqueue_forward asks)
     int64_t wchunk_launches = 0;           // stage and producer launches of the wide chunk layer enqueued (biogpt_hip_wide_chunk_launches)
+    bool wide_pass = false;                // the wide pass layer is switched on (biogpt_hip_wide_pass): passes of 9 or more of the context's own columns run on kernels_wpass.hip.h
+    int wpass_max_cols = -1;               // the most columns of such a pass: n_positions where the layer's geometry holds the file's five matrices within the device's LDS, else 0 (-1: not asked yet, enqueue_forward asks)
+    int64_t wpass_launches = 0;            // launches of the wide pass layer enqueued (biogpt_hip_wide_pass_launches)
     int assoc = 0;                         // 1: the SIMD association (biogpt_hip_assoc): every pass on the five-launch layer with the kernels of kernels_assoc.hip.h; no call over column states
     bool assoc_chain = false;              // the SIMD chain is switched on (biogpt_hip_assoc_chain): while assoc == 1, passes over column states run on kernels_schain.hip.h; nothing while assoc == 0
     int64_t simd_chain_launches = 0;       // linear-stage launches of the SIMD chain (biogpt_hip_simd_chain_launches)
@@ -687,6 +692,31 @@ inline int wchunk_cols_on_device(const biogpt_hip_hparams &hp) {
     for (int n = bgk::WCHUNK_MAX_COLS; n >= bgk::WCHUNK_MIN_COLS; n--)
         if (wchunk_holds_file(hp, n, -1)) return n;
     return 0;
+}
+// the wide pass layer (kernels_wpass.hip.h, wpass_tu.hip): 9 or more of the context's own columns of a wide file, the linear stages of seven launches per layer on
+// the row-tiled image.  epi: EPI_QKV, EPI_RESID, EPI_GELU_Q8 (fc1), EPI_LOGITS.  lds_limit as bg_wchunk_geometry's; cfg -1: the launch shape by the rule
+extern "C" int bg_wpass_geometry(int epi, int M, int K, int N, int q81, int64_t lds_limit, int cfg, int32_t *six);
+extern "C" int bg_wpass_launch(int wt, int epi, const void *params, size_t params_bytes, int cfg, hipStream_t st, int32_t *report);
+inline bool wpass_holds_file(const biogpt_hip_hparams &hp, int N, int64_t lds_limit) {
+    const int D = hp.d_model, F = hp.d_ff, t = ftype_to_type(hp.ftype), q81 = (t == T_Q4_1 || t == T_Q5_1) ? 1 : 0;
+    return !bg_wpass_geometry(bgk::EPI_QKV, 3 * D, D, N, q81, lds_limit, -1, nullptr) && !bg_wpass_geometry(bgk::EPI_RESID, D, D, N, q81, lds_limit, -1, nullptr) &&
+           !bg_wpass_geometry(bgk::EPI_GELU_Q8, F, D, N, q81, lds_limit, -1, nullptr) && !bg_wpass_geometry(bgk::EPI_RESID, D, F, N, q81, lds_limit, -1, nullptr) &&
+           !bg_wpass_geometry(bgk::EPI_LOGITS, hp.n_vocab, D, N, q81, lds_limit, -1, nullptr);
+}
+// why a file cannot have the wide pass layer (null: it can): the wide chain's files (what the current device's LDS allows is wpass_cols_on_device)
+inline const char *wide_pass_refusal(const biogpt_hip_hparams &hp) {
+    if (!is_quantized(ftype_to_type(hp.ftype))) return "the weights are not block-quantized";
+    const int kind = chain_kind_of(hp);
+    if (kind == CHAIN_BASE) return "it has BioGPT-base shapes, which have their own pass launches";
+    if (kind != CHAIN_WIDE) return "the head size is not 64, or d_model is no multiple of 64, or d_ff of 32";
+    if (!wpass_holds_file(hp, bgk::WPASS_MIN_COLS, 0)) return "the layer's kernels do not hold its matrices";
+    return nullptr;
+}
+// the most columns of a pass of the layer on the CURRENT device (0: none): the LDS a workgroup asks for follows from the column tiles per wave and the row
+// length, not from N, so the limit is n_positions or nothing
+inline int wpass_cols_on_device(const biogpt_hip_hparams &hp) {
+    if (wide_pass_refusal(hp)) return 0;
+    return (wpass_holds_file(hp, bgk::WPASS_MIN_COLS, -1) && wpass_holds_file(hp, std::max(hp.n_positions, bgk::WPASS_MIN_COLS), -1)) ? hp.n_positions : 0;
 }
 // the float chain (kernels_fchain.hip.h, fchain_tu.hip): the many-column linear stage on the row-major F32 / F16 weights of the arena, and the LayerNorm producer in
 // front of it.  cfg: a tile shape, -1 the launch's own choice; report: null, or five words (threads, grid x, grid y, LDS bytes, cfg)
@@ -1413,6 +1443,7 @@ struct PassLaunch {
     bool fchain;                    // the float chain: a pass over column states of an F32 / F16 file whose context has it switched on (kernels_fchain.hip.h)
     bool wdec;                      // the wide decode layer: one token of the context's own column of a wide file whose context has it switched on (kernels_wdecode.hip.h)
     bool wchunk;                    // the wide chunk layer: 2 .. 8 tokens of the context's own columns of a wide file whose context has it switched on (kernels_wchunk.hip.h)
+    bool wpass;                     // the wide pass layer: 9 or more of the context's own columns of a wide file whose context has it switched on (kernels_wpass.hip.h)
     bool simd;                      // the context is in the SIMD association: the generic sites launch the kernels of kernels_assoc.hip.h
     bool schain;                    // the SIMD chain: a pass over column states of a context in the SIMD association that has it switched on (kernels_schain.hip.h)
     int q81;
@@ -1616,7 +1647,7 @@ bool enqueue_attention(PassLaunch &k, int l) {
     a.N = N; a.D = D; a.dk = dk; a.P = P;
     a.dbg = c->opt.dbg; a.tstamp = c->tstamp;
     a.q81 = k.q81;
-    if (k.chain || k.wdec || k.wchunk) { a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; }      // (the wide decode layer beyond its own attention's keys: out_proj reads these blocks)
+    if (k.chain || k.wdec || k.wchunk || k.wpass) { a.oq_q = c->aq_q[0]; a.oq_d = c->aq_d[0]; a.oq_s = c->aq_s[0]; }      // (the wide decode layer beyond its own attention's keys: out_proj reads these blocks)
     if (k.simd) {      // (head size 64 and t_max <= SIMD_ATTN_MAXT: enqueue_forward)
         launch_attn_simd(a, H, N, st);
         return true;
@@ -1764,11 +1795,67 @@ bool enqueue_wchunk_layer(PassLaunch &k, int l) {
     return true;
 }
 
+// One stage of the wide pass layer on the row-tiled image of matrix m: the N columns' Q8 blocks of side buffer `slot` in, the site's epilogue out.
+bool enqueue_wpass_stage(PassLaunch &k, int epi, const MatSlot &m, int slot, int N, bgk::WpassParams &p) {
+    biogpt_hip_ctx *c = k.c;
+    const bgk::DevMatrix img = tile_matrix(c, m);
+    p.img_q = img.qs; p.img_s = img.sc; p.M = img.M; p.K = img.K; p.N = N;
+    p.aq_q = c->aq_q[slot]; p.aq_d = c->aq_d[slot]; p.aq_s = c->aq_s[slot];
+    HIP_TRY(false, (hipError_t)bg_wpass_launch(m.type, epi, &p, sizeof(p), -1, k.st, nullptr));
+    c->wpass_launches++;
+    return true;
+}
+
+// Layer l of the wide pass layer (N >= 9, the context's own columns, up to FAST_ATTN_MAX_KEYS keys): seven launches.  LayerNorm + Q8 of the N columns is a
+// producer launch (lnq_wide_kernel), every linear stage reads a producer's blocks: aq[2] LayerNorm -> q/k/v and fc1, aq[0] attention -> out_proj, aq[1] fc1
+// -> fc2 (written by the fc1 stage's own waves: no f32 h row).  The attention is the generic route's launch with its Q8 side output switched on.
+bool enqueue_wpass_layer(PassLaunch &k, int l) {
+    biogpt_hip_ctx *c = k.c;
+    const int N = k.N, D = k.D, P = k.P;
+    hipStream_t st = k.st;
+    const LayerSlots &L = c->plan.layers[(size_t)l];
+    auto produce = [&](const float *x, size_t lw, size_t lb) -> bool {
+        HIP_TRY(false, (hipError_t)bg_wide_quantize(x, D, D, N, dev_vec(c, lw), dev_vec(c, lb), 1e-5f, k.q81, c->aq_q[2], c->aq_d[2], c->aq_s[2], st));
+        c->wpass_launches++;
+        return true;
+    };
+    if (!produce(c->x, L.ln0_w, L.ln0_b)) return false;
+    {
+        bgk::WpassParams p{};
+        p.bias = dev_vec(c, L.qkv_b);
+        p.q_out = c->q; p.kcache = k.kroot + (size_t)l * P * D; p.vcache = k.vroot + (size_t)l * P * D;
+        p.D = D; p.P = P; p.q_scale = 1.0f / sqrtf((float)k.dk); p.st = c->state;
+        if (!enqueue_wpass_stage(k, bgk::EPI_QKV, L.qkv, 2, N, p)) return false;
+    }
+    if (!enqueue_attention(k, l)) return false;
+    c->wpass_launches++;
+    {
+        bgk::WpassParams p{};
+        p.bias = dev_vec(c, L.o_b); p.resid = c->x; p.ldr = D; p.out = c->x1; p.ldo = D;
+        if (!enqueue_wpass_stage(k, bgk::EPI_RESID, L.o, 0, N, p)) return false;
+    }
+    if (!produce(c->x1, L.ln1_w, L.ln1_b)) return false;
+    {
+        bgk::WpassParams p{};
+        p.bias = dev_vec(c, L.fc1_b);
+        p.gelu_tab = reinterpret_cast<const uint16_t *>(c->arena + c->plan.gelu_tab);
+        p.oq_q = c->aq_q[1]; p.oq_d = c->aq_d[1]; p.oq_s = c->aq_s[1];
+        if (!enqueue_wpass_stage(k, bgk::EPI_GELU_Q8, L.fc1, 2, N, p)) return false;
+    }
+    {
+        bgk::WpassParams p{};
+        p.bias = dev_vec(c, L.fc2_b); p.resid = c->x1; p.ldr = D; p.out = c->x; p.ldo = D;
+        if (!enqueue_wpass_stage(k, bgk::EPI_RESID, L.fc2, 1, N, p)) return false;
+    }
+    return true;
+}
+
 // layer l on the chain of launches: q/k/v, attention, out_proj, fc1, fc2
 bool enqueue_layer(PassLaunch &k, int l) {
     biogpt_hip_ctx *c = k.c;
     if (k.wdec) return enqueue_wdec_layer(k, l);
     if (k.wchunk) return enqueue_wchunk_layer(k, l);
+    if (k.wpass) return enqueue_wpass_layer(k, l);
     const int N = k.N, D = k.D, F = k.F, P = k.P;
     hipStream_t st = k.st;
     const LayerSlots &L = c->plan.layers[(size_t)l];
@@ -1953,6 +2040,16 @@ bool enqueue_final(PassLaunch &k) {
         HIP_TRY(false, k.chain_launch(CHAIN_LMHEAD_Q8, p, (head_from > 0 && n_rows < MFMA_MIN_PASS_COLS) ? nullptr : k.tile(c->plan.lm_head)));
         return true;
     }
+    if (rows != Rows::Last && k.wpass) {  // the wide pass layer: LayerNorm + Q8 of the columns that get a row, then the lm_head on the image (its last row tile is partial)
+        const int head_from = k.pass.head_from, n_rows = N - head_from;
+        if (n_rows < bgk::WPASS_MIN_COLS) BG_FAIL(false, "internal: a wide pass layer pass with %d rows behind head_from %d", n_rows, head_from);      // (the context's own columns: head_from is 0)
+        HIP_TRY(false, (hipError_t)bg_wide_quantize(c->x + (size_t)head_from * D, D, D, n_rows, dev_vec(c, c->plan.ln_w), dev_vec(c, c->plan.ln_b), 1e-5f, k.q81,
+                                                    c->aq_q[2], c->aq_d[2], c->aq_s[2], st));
+        c->wpass_launches++;
+        bgk::WpassParams wp{};
+        wp.out = c->logits_all; wp.ldo = V;
+        return enqueue_wpass_stage(k, bgk::EPI_LOGITS, m, 2, n_rows, wp);
+    }
     // final LayerNorm + lm_head on the generic kernel; only the rows that are returned (F8)
     if (rows != Rows::Last) {   // eval_all; scoring of the other models
         p.ln_w = dev_vec(c, c->plan.ln_w); p.ln_b = dev_vec(c, c->plan.ln_b);
@@ -2017,6 +2114,11 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     if (c->wide_chunk && c->wchunk_max_cols < 0) c->wchunk_max_cols = wchunk_cols_on_device(hp);
     k.wchunk = c->wide_chunk && N >= bgk::WCHUNK_MIN_COLS && N <= c->wchunk_max_cols && last_own && c->assoc == 0 && !k.chain && chain_kind_of(hp) == CHAIN_WIDE &&
                t_max <= FAST_ATTN_MAX_KEYS;
+    // 9 or more of the context's own columns of a wide file, whatever rows the pass wants: the wide pass layer, where the context has it switched on, the
+    // device's LDS holds its workgroups and the row-tiled image is there (built here by the first such pass; without memory for it the generic route stays)
+    k.wpass = c->wide_pass && !batch && N >= bgk::WPASS_MIN_COLS && c->assoc == 0 && !k.chain && chain_kind_of(hp) == CHAIN_WIDE && t_max <= FAST_ATTN_MAX_KEYS;
+    if (k.wpass && c->wpass_max_cols < 0) c->wpass_max_cols = wpass_cols_on_device(hp);
+    k.wpass = k.wpass && N <= c->wpass_max_cols && ensure_tile_images(c) && c->tile_img != nullptr;
     if (batch && !k.chain && !k.wchain && !k.fchain && !k.schain)
         BG_FAIL(false, "batched decode needs the BioGPT-base fast chain (block-quantized weights, d_model 1024, d_ff 4096, head size 64) or the wide one (block-quantized weights, head size 64, d_model a multiple of 64, d_ff of 32)");
     if (k.wchain && (c->tile_img == nullptr || pass.rows == Rows::Last || pass.rows == Rows::AllGeneric))
@@ -2312,6 +2414,7 @@ biogpt_hip_ctx *load_impl(const char *fname, int device, int verbosity, void *ex
     c->assoc_chain = c->opt.assoc_chain == 1 && assoc_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_ASSOC_CHAIN)
     c->wide_decode = c->opt.wide_decode == 1 && wide_decode_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_DECODE)
     c->wide_chunk = c->opt.wide_chunk == 1 && wide_chunk_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_CHUNK)
+    c->wide_pass = c->opt.wide_pass == 1 && wide_pass_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_PASS)
     c->device = device;
     c->n_tensors = (int)mf.tensors.size();
     c->vocab = mf.vocab;
@@ -2425,6 +2528,7 @@ biogpt_hip_ctx *biogpt_hip_attach(const biogpt_hip_hparams *hp, int device, void
     c->assoc_chain = c->opt.assoc_chain == 1 && assoc_refusal(c->hp) == nullptr;
     c->wide_decode = c->opt.wide_decode == 1 && wide_decode_refusal(c->hp) == nullptr;
     c->wide_chunk = c->opt.wide_chunk == 1 && wide_chunk_refusal(c->hp) == nullptr;
+    c->wide_pass = c->opt.wide_pass == 1 && wide_pass_refusal(c->hp) == nullptr;
     c->device = device;
     c->pos_rows = (int64_t)hp->n_positions + 2;
     c->plan = plan_arena(*hp, c->pos_rows);
@@ -3079,6 +3183,33 @@ int biogpt_hip_get_wide_chunk(const biogpt_hip_ctx *ctx) {
     return ctx->wide_chunk ? 1 : 0;
 }
 int64_t biogpt_hip_wide_chunk_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->wchunk_launches : -1; }
+// The wide pass layer's switch: the rules of biogpt_hip_wide_decode.  No captured graph holds a pass of 9 or more columns, so none is dropped.
+int biogpt_hip_wide_pass(biogpt_hip_ctx *ctx, int on) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (on != 0 && on != 1) BG_FAIL(-1, "on must be 0 or 1 (got %d)", on);
+    if (session_refuses(ctx)) return -1;
+    {
+        std::lock_guard<std::mutex> lk(g_xp_mu);
+        if (ctx->xp_in_call) BG_FAIL(-1, "the wide pass layer cannot be switched while a call of this context is running");
+    }
+    if (const char *why = wide_pass_refusal(ctx->hp)) {
+        bg::set_error(__func__, "not served: the wide pass layer is for block-quantized files with head size 64, d_model a multiple of 64 and d_ff of 32 that are not BioGPT-base: %s (got ftype %d, d_model %d, d_ff %d, %d heads)", why, ctx->hp.ftype, ctx->hp.d_model, ctx->hp.d_ff, ctx->hp.n_head);
+        return 1;
+    }
+    if (ctx->wide_pass == (on == 1)) return 0;
+    if (ctx->ready) {
+        HIP_TRY(-2, hipSetDevice(ctx->device));
+        HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->wide_pass = on == 1;
+    return 0;
+}
+int biogpt_hip_get_wide_pass(const biogpt_hip_ctx *ctx) {
+    if (!ctx) BG_FAIL(-1, "null context");
+    return ctx->wide_pass ? 1 : 0;
+}
+int64_t biogpt_hip_wide_pass_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->wpass_launches : -1; }
 // the key counts at which the layer's attention launch changes form: dec_attn_kernel at 16 / 8 / 4 lanes per key up to the first three, beyond them the generic
 // route's launch, which writes the Q8 blocks itself up to the last and leaves them to q8_rows_kernel beyond it.  Returns how many there are; out (or null) takes the first cap.
 int biogpt_hip_wide_decode_key_borders(int32_t *out, int cap) {

@@ -2297,3 +2297,79 @@ int biogpt_hip_wchunk_device(int device, int32_t stage, int32_t wtype, int32_t M
     else if (!im.read(o_out, out) || !im.read(o_k, k_slots) || !im.read(o_v, v_slots)) return -2;
     return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
 }
+
+// ---- a linear stage of the wide pass layer alone (kernels_wpass.hip.h), through the launch function enqueue_wpass_stage uses ----
+// N >= 9 columns.  Every stage reads a producer's blocks aq_q [N][K], aq_d / aq_s [N][K / 32], and bias [M] but at the logits site; the image is laid out by
+// tile_image_place and built as ensure_tile_images builds a wide file's.  epi 0 QKV: M == 3 K, 64 | K, dev_state {n_past, ..}: column c at position n_past + c
+//   of the one slot k_slots / v_slots [K / 64][P][64], updated in place; out [N + 1][K].  epi 1 RESID: resid [N][M]; out [N + 1][M].  epi 4 FC1: 32 | M; out_q
+//   [N + 1][M], out_d / out_s [N + 1][M / 32].  epi 3 LOGITS: any M; out [N + 1][M].
+// The outputs come back WHOLE as allocated and preset to 0xff bytes: row N is guard.  launched [8]: column tiles per wave, waves per workgroup, grid x, grid y,
+// LDS bytes, the compute units the rule counted.  cfg -1: the launch shape by the engine's rule; 11, 14, 21, 24: CT and WPB forced (10 CT + WPB).  which 1 (reps > 0 only): the timed launches are matmul_wide_kernel's at the same site, image and columns (fc1: its GELU epilogue into f32 rows).
+int biogpt_hip_wpass_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t P, int32_t reps, int32_t which, int32_t cfg, const void *w_rows,
+                            const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid, const int32_t *dev_state, float *k_slots,
+                            float *v_slots, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched, float *us_out) {
+    clear_error();
+    if (epi != bgk::EPI_QKV && epi != bgk::EPI_RESID && epi != bgk::EPI_GELU_Q8 && epi != bgk::EPI_LOGITS) BG_FAIL(-1, "epi %d is no site of the wide pass layer (0 QKV, 1 RESID, 4 FC1, 3 LOGITS)", epi);
+    if (reps < 0 || reps > PROBE_MAX_REPS) BG_FAIL(-1, "reps must be in [0, %d]", PROBE_MAX_REPS);
+    if (reps > 0 && !us_out) BG_FAIL(-1, "us_out is NULL");
+    if (cfg != -1 && cfg != 11 && cfg != 14 && cfg != 21 && cfg != 24) BG_FAIL(-1, "cfg %d is no launch shape (-1 the rule, or 10 CT + WPB: 11, 14, 21, 24)", cfg);
+    if (which != 0 && !(which == 1 && reps > 0)) BG_FAIL(-1, "which must be 0, or 1 with reps > 0 (the wide chain's kernel, timed)");
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    if (N < bgk::WPASS_MIN_COLS || N > 4096) BG_FAIL(-1, "N = %d columns: the wide pass layer holds %d .. 4096 here", N, bgk::WPASS_MIN_COLS);
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    const bool qkv = epi == bgk::EPI_QKV, fc1 = epi == bgk::EPI_GELU_Q8, res = epi == bgk::EPI_RESID, lgt = epi == bgk::EPI_LOGITS;
+    const int q81 = (wtype == T_Q4_1 || wtype == T_Q5_1) ? 1 : 0;
+    if (bg_wpass_geometry(epi, M, K, N, q81, 0, cfg, nullptr)) BG_FAIL(-1, "the wide pass layer does not hold a %d x %d matrix at site %d (16 | M at the layer sites, 32 | M at fc1, q/k/v 3 K x K with 64 | K)", M, K, epi);
+    if (!w_rows || !aq_q || !aq_d || !aq_s || (!lgt && !bias)) BG_FAIL(-1, "w_rows, bias, aq_q, aq_d or aq_s is NULL");
+    if (res && !resid) BG_FAIL(-1, "resid is NULL");
+    if (!fc1 && !out) BG_FAIL(-1, "out is NULL");
+    if (fc1 && (!out_q || !out_d || !out_s)) BG_FAIL(-1, "out_q, out_d or out_s is NULL");
+    if (!check_probe_columns(__func__, qkv, N, dev_state, nullptr, 0, P, 1, k_slots, v_slots)) return -1;
+    HIP_TRY(-2, hipSetDevice(device));
+    int32_t five[6] = {0, 0, 0, 0, 0, 0};
+    if (bg_wpass_geometry(epi, M, K, N, q81, -1, cfg, five)) BG_FAIL(-1, "the wide pass layer's %d x %d site %d asks for more LDS than a workgroup of this device gets", M, K, epi);
+    const size_t bpr = (size_t)K / QK, kv_b = qkv ? (size_t)K * P * 4 : 0, ldo = qkv ? (size_t)K : (size_t)M;
+    ProbeImage im;      // [weights | image | codes | d | s | bias | resid | state | GELU table | K | V | out | codes | d | s | f32 rows of the wide chain's fc1], one guard row behind every output
+    const BlockRows wr = upload_block_rows(im, wtype, w_rows, M, K, true);
+    const ProbePart o_aq = im.in(aq_q, (size_t)N * K), o_ad = im.in(aq_d, (size_t)N * bpr * 4), o_as = im.in(aq_s, (size_t)N * bpr * 4);
+    const ProbePart o_bias = im.in(lgt ? nullptr : bias, (size_t)M * 4), o_res = im.in(res ? resid : nullptr, (size_t)N * M * 4);
+    const ProbePart o_ds = im.in(dev_state ? dev_state : PROBE_NO_STATE, sizeof(bgk::DevState)), o_tab = im.own(gelu_table_f16());
+    const ProbePart o_k = im.in(qkv ? k_slots : nullptr, kv_b), o_v = im.in(qkv ? v_slots : nullptr, kv_b);
+    const size_t rows = (size_t)N + 1;
+    const ProbePart o_out = im.out(fc1 ? 0 : rows * ldo * 4);
+    const ProbePart o_oq = im.out(fc1 ? rows * M : 0), o_od = im.out(fc1 ? rows * (M / 32) * 4 : 0), o_os = im.out(fc1 ? rows * (M / 32) * 4 : 0);
+    const ProbePart o_h = im.out(fc1 && which == 1 ? rows * M * 4 : 0);
+    if (!im.upload()) return -2;
+    HIP_TRY(-2, wr.retile(im));
+    const bgk::DevMatrix img = wr.image(im);
+    bgk::WpassParams p{};
+    p.img_q = img.qs; p.img_s = img.sc; p.M = M; p.K = K; p.N = N;
+    p.aq_q = im.at<const int8_t>(o_aq); p.aq_d = im.at<const float>(o_ad); p.aq_s = im.at<const uint32_t>(o_as);
+    if (!lgt) p.bias = im.at<const float>(o_bias);
+    if (res) { p.resid = im.at<const float>(o_res); p.ldr = M; }
+    if (res || lgt) { p.out = im.at<float>(o_out); p.ldo = M; }
+    if (qkv) {
+        p.q_out = im.at<float>(o_out); p.kcache = im.at<float>(o_k); p.vcache = im.at<float>(o_v);
+        p.D = K; p.P = P; p.q_scale = 1.0f / sqrtf(64.0f); p.st = im.at<const bgk::DevState>(o_ds);
+    }
+    if (fc1) { p.gelu_tab = im.at<const uint16_t>(o_tab); p.oq_q = im.at<int8_t>(o_oq); p.oq_d = im.at<float>(o_od); p.oq_s = im.at<uint32_t>(o_os); }
+    auto launch = [&]() -> hipError_t { return (hipError_t)bg_wpass_launch(wtype, epi, &p, sizeof(p), cfg, 0, five); };
+    HIP_TRY(-2, launch());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    report_launch(launched, {five[0], five[1], five[2], five[3], five[4], five[5]});
+    if (fc1) { if (!im.read(o_oq, out_q) || !im.read(o_od, out_d) || !im.read(o_os, out_s)) return -2; }
+    else if (!im.read(o_out, out) || !im.read(o_k, k_slots) || !im.read(o_v, v_slots)) return -2;
+    if (which == 0) return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+    bgk::MatvecParams mp{};      // the wide chain's kernel at the same site (what PassLaunch::wide_stage launches behind its producer)
+    mp.W.type = wtype; mp.W.M = M; mp.W.K = K; mp.N = N; mp.eps = 1e-5f;
+    mp.aq_q = p.aq_q; mp.aq_d = p.aq_d; mp.aq_s = p.aq_s; mp.bias = p.bias;
+    mp.resid = p.resid; mp.ldr = M; mp.out = fc1 ? im.at<float>(o_h) : p.out; mp.ldo = M;
+    mp.q_out = p.q_out; mp.kcache = p.kcache; mp.vcache = p.vcache; mp.D = K; mp.dk = 64; mp.dk_log2 = 6; mp.P = P; mp.q_scale = p.q_scale; mp.st = p.st;
+    mp.gelu_tab = im.at<const uint16_t>(o_tab);
+    const int wide_epi = fc1 ? (int)bgk::EPI_GELU : epi;
+    auto launch_wide = [&]() -> hipError_t { return (hipError_t)bg_wide_launch(wtype, wide_epi, &mp, sizeof(mp), &img, sizeof(img), 0); };
+    HIP_TRY(-2, launch_wide());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    return time_launches(reps, nullptr, launch_wide, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+}

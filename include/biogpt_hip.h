@@ -253,6 +253,22 @@ int biogpt_hip_get_wide_chunk(const biogpt_hip_ctx *ctx);
 /* Launches of the wide chunk layer enqueued (seven per layer and eval: two LayerNorm + Q8 producers, q/k/v, attention, out_proj, fc1, fc2); 0 for ever while the
  * switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_wide_chunk_launches(const biogpt_hip_ctx *ctx);
+/* The wide pass layer's switch, per context (initial value: BIOGPT_HIP_WIDE_PASS=0/1, default 1 on the files it serves).  It serves the files of the wide decode layer.
+ * on 1: a pass of 9 or more tokens of the context's own columns, up to 1024 keys -- biogpt_hip_eval / eval_all / eval_topk / eval_prompt on a prompt, the prompt
+ * pass of biogpt_hip_generate_greedy, biogpt_hip_score and biogpt_hip_hidden -- runs its layers on csrc/kernels_wpass.hip.h: seven launches per layer (LayerNorm +
+ * Q8 of the columns, q/k/v, attention with its Q8 side output, out_proj, LayerNorm + Q8, fc1 with its Q8 hand-off, fc2), and a pass that wants a logits row of
+ * every column its final stage too (LayerNorm + Q8 of the rows, the lm_head).  The first such pass builds the row-tiled weight image (36 / 40 bytes per 32
+ * weights beside the file's own bytes); without device memory for it the passes keep the generic route.  Logits, K / V rows, log-probabilities and ids are bit for
+ * bit those of the generic route, and the cache layout is shared with it.  Evals of up to 8 tokens, passes beyond 1024 keys, every pass over column states,
+ * BioGPT-base files, float files, a context while it is in the SIMD association, and a device whose workgroups cannot have the LDS a stage asks for keep the
+ * launches they have.  Legality and return values are those of biogpt_hip_wide_decode: not while a queue session is open or a call of the context is running; 1
+ * with "not served: ..." in biogpt_hip_last_error on a file the layer does not serve. */
+int biogpt_hip_wide_pass(biogpt_hip_ctx *ctx, int on);
+/* The wide pass layer's switch: 0 off, 1 on.  -1: ctx is NULL. */
+int biogpt_hip_get_wide_pass(const biogpt_hip_ctx *ctx);
+/* Launches of the wide pass layer enqueued: seven per layer and pass (two LayerNorm + Q8 producers, q/k/v, attention, out_proj, fc1, fc2), and two per pass that
+ * wants every row (LayerNorm + Q8 of the rows, the lm_head); 0 for ever while the switch is off.  -1: ctx is NULL. */
+int64_t biogpt_hip_wide_pass_launches(const biogpt_hip_ctx *ctx);
 /* Linear-stage launches of the float chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
  * switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_float_launches(const biogpt_hip_ctx *ctx);
@@ -593,6 +609,24 @@ int biogpt_hip_wdecode_device(int device, int32_t stage, int32_t wtype, int32_t 
 int biogpt_hip_wchunk_device(int device, int32_t stage, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t P, int32_t reps, const void *w_rows, const int8_t *aq_q,
                              const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid, const int32_t *dev_state, float *k_slots, float *v_slots,
                              float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched, float *us_out);
+/* One stand-alone run of a linear stage of the wide pass layer (csrc/kernels_wpass.hip.h) over caller-supplied rows and Q8 columns, through the layer's own
+ * launch function, on an image built as a context builds a wide file's (the last row tile zero-padded).  No model, no context; N >= 9 columns; wtype one of the
+ * five block formats, w_rows [M] rows of K values in the file's format; aq_q [N][K], aq_d / aq_s [N][K / 32]; bias [M] but at the logits site.
+ *   epi 0 QKV: M == 3 K, 64 | K; dev_state [4] words {n_past, 0, 0, 0}: column c is position n_past + c of the one slot k_slots / v_slots [K / 64][P][64], updated
+ *     in place; out [N + 1][K]: the scaled q rows.
+ *   epi 1 RESID (out_proj, fc2): 16 | M; resid [N][M]; out [N + 1][M].
+ *   epi 4 FC1: 32 | M; out_q [N + 1][M], out_d / out_s [N + 1][M / 32]: the GELU outputs as fc2's Q8 blocks.
+ *   epi 3 LOGITS: any M; out [N + 1][M].
+ * Outputs come back whole, as allocated and preset to 0xff bytes: row N is guard.  launched [8] (may be NULL): column tiles per wave, waves per workgroup, grid x,
+ * grid y, dynamic LDS bytes, the compute units the launch rule counted.  cfg -1: the launch shape by the engine's rule; 11, 14, 21, 24: column
+ * tiles per wave and waves per workgroup forced (10 CT + WPB), so that every instantiation can be held to a reference at a small shape.  reps > 0: behind the checked launch, reps launches timed each between two device events, microseconds into us_out [reps]; which
+ * 1 times matmul_wide_kernel (its RESID, GELU or LOGITS epilogue; no QKV) on the same image and columns instead (tools/wide_pass_bench.py).  Returns 0; -1 on a
+ * bad argument -- N below 9 and a shape the kernels do not hold before any HIP call, an LDS request beyond what the device gives a workgroup behind hipSetDevice
+ * and before any launch; -2 on a HIP error. */
+int biogpt_hip_wpass_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t P, int32_t reps, int32_t which, int32_t cfg,
+                            const void *w_rows,
+                            const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid, const int32_t *dev_state, float *k_slots,
+                            float *v_slots, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched, float *us_out);
 /* One stand-alone run of a stage of the embedding tail (ln_rows_kernel<1024> / <0>, pool_rows_kernel, pool_finish_kernel, head_rows_kernel) over caller-supplied
  * rows, through the launch code of biogpt_hip_hidden / biogpt_hip_embed_batch.  No model, no context; W a multiple of 4.  stage 0 LN: x [n_rows][W], ln_w / ln_b
  * [W]; W == 1024 takes the <1024> template, any other width <0>; seq_states (may be NULL) [n_rows][8] words with slot_div >= 1 and P: row i lands at row
