@@ -702,6 +702,32 @@ def attn_runs_device(H, P, t_max, n_slots, q, k_slots, v_slots, seq_states, runs
     return rc, out, oq, od, os_, launched
 
 
+def attn_long_device(form, H, N, P, t_max, q, k_slot, v_slot, dev_state, q8=0, device=0, reps=0):
+    """One launch of a long-context attention kernel on arrays held in host memory (biogpt_hip_attn_long_device): form 0 attn_long_col_kernel (N <= 8), 1
+    attn_long_tile_kernel (N >= 9); q float32 [N][H * 64], k_slot / v_slot float32 [H][P][64], dev_state int32 [4] {n_past, n_gen, causal, chunk}; t_max in
+    1025 .. 2048.  Returns (rc, out, out_q, out_d, out_s, launched) with the outputs whole: N rounded up to 16 rows plus a guard row, preset to 0xff; launched
+    [8]: form, threads, grid x, grid y, LDS bytes, t_cap.  reps > 0: a seventh item, the microseconds of reps further launches (launched stays -1)."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    k = np.ascontiguousarray(k_slot, dtype=np.float32)
+    v = np.ascontiguousarray(v_slot, dtype=np.float32)
+    st = None if dev_state is None else np.ascontiguousarray(dev_state, dtype=np.int32).reshape(4)
+    N, D = int(N), int(H) * 64
+    if min(N, D, int(P)) >= 1 and (q.size < N * D or k.size < D * int(P) or v.size < D * int(P)):
+        raise BiogptError("attn_long_device: q holds fewer than N rows, or a slot fewer than H * P")
+    rows = (max(N, 0) + 15) // 16 * 16 + 1
+    out = np.zeros((rows, max(D, 0)), dtype=np.float32)
+    oq, od, os_ = np.zeros((rows, max(D, 0)), dtype=np.int8), np.zeros((rows, max(D, 0) // 32), dtype=np.float32), np.zeros((rows, max(D, 0) // 32), dtype=np.uint32)
+    launched = np.full(8, -1, dtype=np.int32)
+    args = (int(device), int(form), int(H), N, int(P), int(t_max), q.ctypes.data, k.ctypes.data, v.ctypes.data, None if st is None else st.ctypes.data, int(q8),
+            out.ctypes.data, oq.ctypes.data if q8 else None, od.ctypes.data if q8 else None, os_.ctypes.data if q8 else None)
+    if reps > 0:
+        us = np.zeros(reps, dtype=np.float32)
+        rc = lib().biogpt_hip_attn_long_bench(*args, int(reps), us.ctypes.data)
+        return rc, out, oq, od, os_, launched, us
+    rc = lib().biogpt_hip_attn_long_device(*args, launched.ctypes.data)
+    return rc, out, oq, od, os_, launched
+
+
 def beam_rows(rows, n_beams, run_score, given=False, first_step=False, device=0, masked=False):
     """beam_group_rows_kernel on rows held in host memory (biogpt_hip_beam_rows_device): rows float32 [G * n_beams][n_vocab], run_score [G * n_beams].
     Returns (score float32, col int32, id int32), each [G * n_beams][2 * n_beams]; rows the kernel left alone hold (NaN, -1, -1).  masked (with given):
@@ -846,6 +872,9 @@ SYMBOLS = [
     ("biogpt_hip_wide_pass", C.c_int, [_P, C.c_int]),
     ("biogpt_hip_get_wide_pass", C.c_int, [_P]),
     ("biogpt_hip_wide_pass_launches", C.c_int64, [_P]),
+    ("biogpt_hip_long_context", C.c_int, [_P, C.c_int]),
+    ("biogpt_hip_get_long_context", C.c_int, [_P]),
+    ("biogpt_hip_long_attn_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_stamps", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     ("biogpt_hip_generate_launches", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
@@ -940,6 +969,9 @@ SYMBOLS = [
     ("biogpt_hip_queue_stream_device", C.c_int64, [C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64]),
     ("biogpt_hip_queue_cancel_device", C.c_int, [C.c_int, _P, C.c_int32, _P, _P, _P]),
     ("biogpt_hip_attn_device", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    ("biogpt_hip_attn_device_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P] * 5 + [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
+    ("biogpt_hip_attn_long_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32, _P, _P, _P, _P, _P]),
+    ("biogpt_hip_attn_long_bench", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     ("biogpt_hip_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32] + [_P] * 7 + [C.c_int32] * 3 + [_P] * 7),
     ("biogpt_hip_wide_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 4),
     ("biogpt_hip_wide_chain_bench", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P]),
@@ -1743,13 +1775,14 @@ class BiogptModel:
 
     # -- biogpt_model_load (biogpt.h:128-132) --
     @classmethod
-    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None, assoc_chain=None, wide_decode=None, wide_chunk=None, wide_pass=None):
+    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None, assoc_chain=None, wide_decode=None, wide_chunk=None, wide_pass=None, long_context=None):
         """float_chain=True: switch the float chain on behind the load (float_chain(); an F32 / F16 file with head size 64 only -- anything else raises).
         assoc="scalar" | "simd": set the association behind the load (set_assoc(); None: the default, scalar unless BIOGPT_HIP_ASSOC=1).
         assoc_chain=True | False: set the SIMD chain's switch behind the load (set_assoc_chain(); None: the default, off unless BIOGPT_HIP_ASSOC_CHAIN=1).
         wide_decode=True | False: set the wide decode layer's switch behind the load (set_wide_decode(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_DECODE=0).
         wide_chunk=True | False: set the wide chunk layer's switch behind the load (set_wide_chunk(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_CHUNK=0).
-        wide_pass=True | False: set the wide pass layer's switch behind the load (set_wide_pass(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_PASS=0)."""
+        wide_pass=True | False: set the wide pass layer's switch behind the load (set_wide_pass(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_PASS=0).
+        long_context=True | False: set the long-context attention's switch behind the load (set_long_context(); None: the default, off unless BIOGPT_HIP_LONG_CONTEXT=1)."""
         if arena is None:
             m = cls(lib().biogpt_hip_load(os.fsencode(fname), device, verbosity))
         else:
@@ -1767,6 +1800,8 @@ class BiogptModel:
                 m.set_wide_chunk(wide_chunk)
             if wide_pass is not None:
                 m.set_wide_pass(wide_pass)
+            if long_context is not None:
+                m.set_long_context(long_context)
         except BiogptError:
             m.close()
             raise
@@ -2600,6 +2635,28 @@ class BiogptModel:
         """Launches of the wide pass layer enqueued (biogpt_hip_wide_pass_launches): seven per layer and pass of 9 or more tokens, two more per pass that wants
         every row; 0 while the switch is off."""
         return int(lib().biogpt_hip_wide_pass_launches(self._h))
+
+    def set_long_context(self, on=True):
+        """The long-context attention's switch (biogpt_hip_long_context): on, evals of the context's own columns of a block-quantized file that is not BioGPT-base
+        whose furthest visible key lies in 1025 .. min(n_positions, 2048) attend on csrc/kernels_attn_long.hip.h, and the wide decode, chunk and pass layers serve
+        them -- the same bits as off.  Returns True where the file is served, False where it is not (nothing changed; biogpt_hip_last_error then reads
+        "not served: ...").  Raises BiogptError on a bad call."""
+        rc = lib().biogpt_hip_long_context(self._h, 1 if on else 0)
+        if rc < 0:
+            raise BiogptError(_err())
+        return rc == 0
+
+    @property
+    def long_context(self):
+        """Whether the long-context attention's switch is on (biogpt_hip_get_long_context)."""
+        k = int(lib().biogpt_hip_get_long_context(self._h))
+        if k < 0:
+            raise BiogptError(_err())
+        return k == 1
+
+    def long_attn_launches(self):
+        """Launches of the long-context attention kernels enqueued (biogpt_hip_long_attn_launches): one per layer and eval beyond 1024 keys; 0 while the switch is off."""
+        return int(lib().biogpt_hip_long_attn_launches(self._h))
 
     def float_launches(self):
         """Linear-stage launches of the float chain (biogpt_hip_float_launches); 0 while the switch is off."""

@@ -210,7 +210,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain, wide_decode, wide_chunk, wide_pass;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain, wide_decode, wide_chunk, wide_pass, long_context;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -246,6 +246,7 @@ struct EngineOptions {
         wide_decode = get("BIOGPT_HIP_WIDE_DECODE", 1);          // 1 (the default: measured faster at every key count): a new context of a file the wide decode layer serves starts with it switched on; 0: off (biogpt_hip_wide_decode; kernels_wdecode.hip.h)
         wide_chunk = get("BIOGPT_HIP_WIDE_CHUNK", 1);            // 1 (the default: measured faster at every chunk size and key count): a new context of a file the wide chunk layer serves starts with it switched on; 0: off (biogpt_hip_wide_chunk; kernels_wchunk.hip.h)
         wide_pass = get("BIOGPT_HIP_WIDE_PASS", 1);              // 1 (the default: DESIGN 4.4): a new context of a file the wide pass layer serves starts with it switched on; 0: off (biogpt_hip_wide_pass; kernels_wpass.hip.h)
+        long_context = get("BIOGPT_HIP_LONG_CONTEXT", 0);        // 0 (the default): off; 1: a new context of a wide file starts with the long-context attention switched on (biogpt_hip_long_context; kernels_attn_long.hip.h)
         assoc = get("BIOGPT_HIP_ASSOC", 0);                        // 1: a new context of a file the SIMD association serves starts in it (biogpt_hip_assoc; kernels_assoc.hip.h)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
     }
@@ -403,6 +404,8 @@ struct biogpt_hip_ctx {
     int64_t wchunk_launches = 0;           // stage and producer launches of the wide chunk layer enqueued (biogpt_hip_wide_chunk_launches)
     bool wide_pass = false;                // the wide pass layer is switched on (biogpt_hip_wide_pass): passes of 9 or more of the context's own columns run on kernels_wpass.hip.h
     int wpass_max_cols = -1;               // the most columns of such a pass: n_positions where the layer's geometry holds the file's five matrices within the device's LDS, else 0 (-1: not asked yet, enqueue_forward asks)
+    bool long_context = false;             // the long-context attention is switched on (biogpt_hip_long_context): the context's own columns of a wide file at 1025 .. 2048 keys attend on kernels_attn_long.hip.h
+    int64_t long_attn_launches = 0;        // launches of attn_long_col_kernel / attn_long_tile_kernel enqueued (biogpt_hip_long_attn_launches)
     int64_t wpass_launches = 0;            // launches of the wide pass layer enqueued (biogpt_hip_wide_pass_launches)
     int assoc = 0;                         // 1: the SIMD association (biogpt_hip_assoc): every pass on the five-launch layer with the kernels of kernels_assoc.hip.h; no call over column states
     bool assoc_chain = false;              // the SIMD chain is switched on (biogpt_hip_assoc_chain): while assoc == 1, passes over column states run on kernels_schain.hip.h; nothing while assoc == 0
@@ -717,6 +720,21 @@ inline const char *wide_pass_refusal(const biogpt_hip_hparams &hp) {
 inline int wpass_cols_on_device(const biogpt_hip_hparams &hp) {
     if (wide_pass_refusal(hp)) return 0;
     return (wpass_holds_file(hp, bgk::WPASS_MIN_COLS, -1) && wpass_holds_file(hp, std::max(hp.n_positions, bgk::WPASS_MIN_COLS), -1)) ? hp.n_positions : 0;
+}
+// the long-context attention (kernels_attn_long.hip.h, attn_long_tu.hip): head size 64, the context's own columns, 1025 .. LONG_ATTN_MAX_KEYS keys.  form 0: one
+// column per workgroup (attn_long_col_kernel), 1: sixteen (attn_long_tile_kernel, whose score block needs the device's opt-in LDS: bg_attn_long_tile_fits).
+// six: form, threads, grid x, grid y, LDS bytes, t_cap
+constexpr int LONG_ATTN_MAX_KEYS = 2048;
+extern "C" int bg_attn_long_geometry(int form, int H, int N, int t_cap, int32_t *six);
+extern "C" int bg_attn_long_tile_fits(int t_cap);
+extern "C" int bg_attn_long_launch(int form, const void *params, size_t params_bytes, int H, int N, hipStream_t st, int32_t *report);
+// why a file cannot have the long-context attention (null: it can): the files of the wide decode / chunk / pass layers, with a table beyond 1024 rows or not
+inline const char *long_context_refusal(const biogpt_hip_hparams &hp) {
+    if (!is_quantized(ftype_to_type(hp.ftype))) return "the weights are not block-quantized";
+    const int kind = chain_kind_of(hp);
+    if (kind == CHAIN_BASE) return "it has BioGPT-base shapes";
+    if (kind != CHAIN_WIDE) return "the head size is not 64, or d_model is no multiple of 64, or d_ff of 32";
+    return nullptr;
 }
 // the float chain (kernels_fchain.hip.h, fchain_tu.hip): the many-column linear stage on the row-major F32 / F16 weights of the arena, and the LayerNorm producer in
 // front of it.  cfg: a tile shape, -1 the launch's own choice; report: null, or five words (threads, grid x, grid y, LDS bytes, cfg)
@@ -1443,6 +1461,7 @@ struct PassLaunch {
     bool fchain;                    // the float chain: a pass over column states of an F32 / F16 file whose context has it switched on (kernels_fchain.hip.h)
     bool wdec;                      // the wide decode layer: one token of the context's own column of a wide file whose context has it switched on (kernels_wdecode.hip.h)
     bool wchunk;                    // the wide chunk layer: 2 .. 8 tokens of the context's own columns of a wide file whose context has it switched on (kernels_wchunk.hip.h)
+    bool long_attn;                 // the attention launch of this pass is one of kernels_attn_long.hip.h (1025 .. 2048 keys of a wide file, biogpt_hip_long_context on)
     bool wpass;                     // the wide pass layer: 9 or more of the context's own columns of a wide file whose context has it switched on (kernels_wpass.hip.h)
     bool simd;                      // the context is in the SIMD association: the generic sites launch the kernels of kernels_assoc.hip.h
     bool schain;                    // the SIMD chain: a pass over column states of a context in the SIMD association that has it switched on (kernels_schain.hip.h)
@@ -1656,6 +1675,13 @@ bool enqueue_attention(PassLaunch &k, int l) {
         HIP_TRY(false, (hipError_t)bg_schain_attn(&a, sizeof(a), k.pass.shared_prefix ? 1 : 0, H, N, st, nullptr));
         return true;
     }
+    if (k.long_attn) {      // (head size 64, the context's own columns, 1024 < t_max <= min(P, LONG_ATTN_MAX_KEYS), the tile form within the device's LDS: enqueue_forward)
+        const bool tile = N >= GROUPED_ATTN_MIN_COLS;
+        a.t_cap = tile ? attn_pass_t_cap(P, t_max) : attn_decode_t_cap(P, t_max);
+        HIP_TRY(false, (hipError_t)bg_attn_long_launch(tile ? 1 : 0, &a, sizeof(a), H, N, st, nullptr));
+        c->long_attn_launches++;
+        return true;
+    }
     if (!(dk == 64 && t_max <= FAST_ATTN_MAX_KEYS)) {
         launch_attn_generic(a, H, N, k.attn_threads, st);
         return true;
@@ -1718,7 +1744,8 @@ bool enqueue_wdec_layer(PassLaunch &k, int l) {
     } else {
         if (!enqueue_attention(k, l)) return false;
         // (beyond FAST_ATTN_MAX_KEYS that launch is attn_kernel, which writes the f32 row alone: its Q8 blocks by q8_rows_kernel)
-        if (k.pass.t_max > FAST_ATTN_MAX_KEYS) HIP_TRY(false, (hipError_t)bg_wide_quantize(c->att, D, D, 1, nullptr, nullptr, 1e-5f, k.q81, c->aq_q[0], c->aq_d[0], c->aq_s[0], st));
+        // (the long-context kernels write them themselves)
+        if (k.pass.t_max > FAST_ATTN_MAX_KEYS && !k.long_attn) HIP_TRY(false, (hipError_t)bg_wide_quantize(c->att, D, D, 1, nullptr, nullptr, 1e-5f, k.q81, c->aq_q[0], c->aq_d[0], c->aq_s[0], st));
     }
     c->wdec_launches++;
     {
@@ -2111,12 +2138,16 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     k.wdec = c->wide_decode && N == 1 && last_own && c->assoc == 0 && !k.chain && chain_kind_of(hp) == CHAIN_WIDE && t_max <= hp.n_positions;
     // 2 .. 8 tokens of the context's own columns of a wide file: the wide chunk layer, where the context has it switched on and its geometry holds the file's
     // four matrices at N columns within this device's LDS (the attention launch writes out_proj's Q8 blocks up to FAST_ATTN_MAX_KEYS)
+    // beyond FAST_ATTN_MAX_KEYS with the long-context attention switched on: the attention launch of kernels_attn_long.hip.h, which writes out_proj's Q8 blocks as the
+    // shorter contexts' kernels do, so the chunk and pass layers below reach as far (a pass whose tile workgroup the device's LDS cannot hold keeps today's route)
+    k.long_attn = c->long_context && !batch && c->assoc == 0 && !k.chain && k.dk == 64 && chain_kind_of(hp) == CHAIN_WIDE && t_max > FAST_ATTN_MAX_KEYS &&
+                  t_max <= std::min(hp.n_positions, LONG_ATTN_MAX_KEYS) && (N < GROUPED_ATTN_MIN_COLS || bg_attn_long_tile_fits(attn_pass_t_cap(k.P, t_max)) == 1);
     if (c->wide_chunk && c->wchunk_max_cols < 0) c->wchunk_max_cols = wchunk_cols_on_device(hp);
     k.wchunk = c->wide_chunk && N >= bgk::WCHUNK_MIN_COLS && N <= c->wchunk_max_cols && last_own && c->assoc == 0 && !k.chain && chain_kind_of(hp) == CHAIN_WIDE &&
-               t_max <= FAST_ATTN_MAX_KEYS;
+               (t_max <= FAST_ATTN_MAX_KEYS || k.long_attn);
     // 9 or more of the context's own columns of a wide file, whatever rows the pass wants: the wide pass layer, where the context has it switched on, the
     // device's LDS holds its workgroups and the row-tiled image is there (built here by the first such pass; without memory for it the generic route stays)
-    k.wpass = c->wide_pass && !batch && N >= bgk::WPASS_MIN_COLS && c->assoc == 0 && !k.chain && chain_kind_of(hp) == CHAIN_WIDE && t_max <= FAST_ATTN_MAX_KEYS;
+    k.wpass = c->wide_pass && !batch && N >= bgk::WPASS_MIN_COLS && c->assoc == 0 && !k.chain && chain_kind_of(hp) == CHAIN_WIDE && (t_max <= FAST_ATTN_MAX_KEYS || k.long_attn);
     if (k.wpass && c->wpass_max_cols < 0) c->wpass_max_cols = wpass_cols_on_device(hp);
     k.wpass = k.wpass && N <= c->wpass_max_cols && ensure_tile_images(c) && c->tile_img != nullptr;
     if (batch && !k.chain && !k.wchain && !k.fchain && !k.schain)
@@ -2415,6 +2446,7 @@ biogpt_hip_ctx *load_impl(const char *fname, int device, int verbosity, void *ex
     c->wide_decode = c->opt.wide_decode == 1 && wide_decode_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_DECODE)
     c->wide_chunk = c->opt.wide_chunk == 1 && wide_chunk_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_CHUNK)
     c->wide_pass = c->opt.wide_pass == 1 && wide_pass_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_PASS)
+    c->long_context = c->opt.long_context == 1 && long_context_refusal(c->hp) == nullptr;      // (BIOGPT_HIP_LONG_CONTEXT: off unless asked for)
     c->device = device;
     c->n_tensors = (int)mf.tensors.size();
     c->vocab = mf.vocab;
@@ -2529,6 +2561,7 @@ biogpt_hip_ctx *biogpt_hip_attach(const biogpt_hip_hparams *hp, int device, void
     c->wide_decode = c->opt.wide_decode == 1 && wide_decode_refusal(c->hp) == nullptr;
     c->wide_chunk = c->opt.wide_chunk == 1 && wide_chunk_refusal(c->hp) == nullptr;
     c->wide_pass = c->opt.wide_pass == 1 && wide_pass_refusal(c->hp) == nullptr;
+    c->long_context = c->opt.long_context == 1 && long_context_refusal(c->hp) == nullptr;
     c->device = device;
     c->pos_rows = (int64_t)hp->n_positions + 2;
     c->plan = plan_arena(*hp, c->pos_rows);
@@ -3210,6 +3243,35 @@ int biogpt_hip_get_wide_pass(const biogpt_hip_ctx *ctx) {
     return ctx->wide_pass ? 1 : 0;
 }
 int64_t biogpt_hip_wide_pass_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->wpass_launches : -1; }
+// The long-context attention's switch: the rules of biogpt_hip_wide_decode (a captured single-token step holds the attention launch of its key bucket, so
+// the captured steps are dropped).  Off (the default) is the engine without it: beyond 1024 keys the generic route.
+int biogpt_hip_long_context(biogpt_hip_ctx *ctx, int on) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (on != 0 && on != 1) BG_FAIL(-1, "on must be 0 or 1 (got %d)", on);
+    if (session_refuses(ctx)) return -1;
+    {
+        std::lock_guard<std::mutex> lk(g_xp_mu);
+        if (ctx->xp_in_call) BG_FAIL(-1, "the long-context attention cannot be switched while a call of this context is running");
+    }
+    if (const char *why = long_context_refusal(ctx->hp)) {
+        bg::set_error(__func__, "not served: the long-context attention is for block-quantized files with head size 64, d_model a multiple of 64 and d_ff of 32 that are not BioGPT-base: %s (got ftype %d, d_model %d, d_ff %d, %d heads)", why, ctx->hp.ftype, ctx->hp.d_model, ctx->hp.d_ff, ctx->hp.n_head);
+        return 1;
+    }
+    if (ctx->long_context == (on == 1)) return 0;
+    if (ctx->ready) {
+        HIP_TRY(-2, hipSetDevice(ctx->device));
+        HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    }
+    for (auto &pl : ctx->graph_step) for (auto &row : pl) for (auto &g : row) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    ctx->long_context = on == 1;
+    return 0;
+}
+int biogpt_hip_get_long_context(const biogpt_hip_ctx *ctx) {
+    if (!ctx) BG_FAIL(-1, "null context");
+    return ctx->long_context ? 1 : 0;
+}
+int64_t biogpt_hip_long_attn_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->long_attn_launches : -1; }
 // the key counts at which the layer's attention launch changes form: dec_attn_kernel at 16 / 8 / 4 lanes per key up to the first three, beyond them the generic
 // route's launch, which writes the Q8 blocks itself up to the last and leaves them to q8_rows_kernel beyond it.  Returns how many there are; out (or null) takes the first cap.
 int biogpt_hip_wide_decode_key_borders(int32_t *out, int cap) {

@@ -513,6 +513,68 @@ int biogpt_hip_attn_device(int device, int32_t route, int32_t H, int32_t dk, int
     return attn_device(device, route, H, dk, N, P, t_max, n_slots, q, k_slots, v_slots, dev_state, seq_states, col_mode, q8, out, out_q, out_d, out_s, launched, 0, nullptr);
 }
 
+// One stand-alone launch of a long-context attention kernel (kernels_attn_long.hip.h) over caller-supplied inputs, through bg_attn_long_launch as enqueue_attention
+// launches it: biogpt_hip_attn_device restricted to a device state, head size 64 and 1025 .. 2048 keys.  form 0: attn_long_col_kernel (the engine launches it below
+// GROUPED_ATTN_MIN_COLS columns; the probe up to 8, a chunk's), 1: attn_long_tile_kernel (the engine from GROUPED_ATTN_MIN_COLS columns on; the probe from 9, so
+// that tiles of few columns can be examined alone).  q [N][H * 64]; k_slot / v_slot [H][P][64]; dev_state {n_past, n_gen, causal, chunk}; q8 and the outputs as
+// biogpt_hip_attn_device's (rows = N rounded up to 16, plus one guard row, preset to 0xff).  launched [8]: form, threads, grid x, grid y, LDS bytes, t_cap, 0, 0.
+static int attn_long_device(int device, int32_t form, int32_t H, int32_t N, int32_t P, int32_t t_max, const float *q, const float *k_slot, const float *v_slot,
+                            const int32_t *dev_state, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched, int32_t reps, float *us_out) {
+    if (!q || !k_slot || !v_slot || !dev_state || !out) BG_FAIL(-1, "q, k_slot, v_slot, dev_state or out is NULL");
+    if (form != 0 && form != 1) BG_FAIL(-1, "form must be 0 (attn_long_col_kernel) or 1 (attn_long_tile_kernel)");
+    if (H < 1 || H > 64) BG_FAIL(-1, "H must be in [1, 64]");
+    if (N < 1 || N > 512) BG_FAIL(-1, "N must be in [1, 512]");
+    if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+    if (t_max <= FAST_ATTN_MAX_KEYS || t_max > LONG_ATTN_MAX_KEYS) BG_FAIL(-1, "t_max must be in [%d, %d]: up to %d keys a pass takes the kernels of biogpt_hip_attn_device", FAST_ATTN_MAX_KEYS + 1, LONG_ATTN_MAX_KEYS, FAST_ATTN_MAX_KEYS);
+    if (t_max > P) BG_FAIL(-1, "t_max must be at most P: t_cap never exceeds the table");
+    if (form == 1 && N < bgk::WPASS_MIN_COLS) BG_FAIL(-1, "the tile form serves passes of %d or more columns (the engine launches it from %d on)", bgk::WPASS_MIN_COLS, GROUPED_ATTN_MIN_COLS);
+    if (form == 0 && N > bgk::WCHUNK_MAX_COLS) BG_FAIL(-1, "the column form serves up to %d columns here: the single token and a chunk's", bgk::WCHUNK_MAX_COLS);
+    if (q8 < 0 || q8 > 2 || (q8 > 0 && (!out_q || !out_d || !out_s))) BG_FAIL(-1, "q8 must be 0, 1 or 2, with out_q, out_d and out_s");
+    if (reps < 0 || reps > PROBE_MAX_REPS || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, %d], with us_out", PROBE_MAX_REPS);
+    const int t_cap = form == 1 ? attn_pass_t_cap(P, t_max) : attn_decode_t_cap(P, t_max);
+    if (dev_state[0] < 0) BG_FAIL(-1, "n_past %d is negative", dev_state[0]);
+    for (int i = 0; i < N; i++) {
+        const int T = host_visible_keys(dev_state, i, N);
+        if (T < 1 || T > t_cap || T > t_max) BG_FAIL(-1, "column %d: %d visible keys outside [1, t_cap = %d] (t_max %d)", i, T, t_cap, t_max);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    if (form == 1 && bg_attn_long_tile_fits(t_cap) != 1) BG_FAIL(-1, "the device's LDS does not hold the tile form's workgroup at %d keys", t_cap);
+    const int D = H * 64;
+    ProbeImage im;
+    const AttnProbeParts o = attn_probe_parts(im, H, 64, N, P, 1, q, k_slot, v_slot, nullptr, dev_state, sizeof(bgk::DevState));
+    if (!im.upload()) return -2;
+    bgk::AttnParams a = attn_probe_params(im, o, N, D, 64, P, t_cap, 0, 0, q8);
+    a.st = im.at<const bgk::DevState>(o.extra);
+    int32_t six[6] = {0, 0, 0, 0, 0, 0};
+    auto launch = [&]() -> hipError_t { return (hipError_t)bg_attn_long_launch(form, &a, sizeof(a), H, N, 0, six); };
+    HIP_TRY(-2, launch());
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    report_launch(launched, {six[0], six[1], six[2], six[3], six[4], six[5], 0});
+    if (!attn_probe_read(im, o, q8, out, out_q, out_d, out_s)) return -2;
+    return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1000.0f; });
+}
+int biogpt_hip_attn_long_device(int device, int32_t form, int32_t H, int32_t N, int32_t P, int32_t t_max, const float *q, const float *k_slot, const float *v_slot,
+                                const int32_t *dev_state, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched) {
+    clear_error();
+    return attn_long_device(device, form, H, N, P, t_max, q, k_slot, v_slot, dev_state, q8, out, out_q, out_d, out_s, launched, 0, nullptr);
+}
+// the same with the launch repeated: us_out[i] microseconds between two events around launch i alone (tools/long_context_bench.py)
+int biogpt_hip_attn_long_bench(int device, int32_t form, int32_t H, int32_t N, int32_t P, int32_t t_max, const float *q, const float *k_slot, const float *v_slot,
+                               const int32_t *dev_state, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps, float *us_out) {
+    clear_error();
+    if (reps < 1 || reps > PROBE_MAX_REPS || !us_out) BG_FAIL(-1, "reps must be in [1, %d], with us_out", PROBE_MAX_REPS);
+    return attn_long_device(device, form, H, N, P, t_max, q, k_slot, v_slot, dev_state, q8, out, out_q, out_d, out_s, nullptr, reps, us_out);
+}
+
+int biogpt_hip_attn_device_bench(int device, int32_t route, int32_t H, int32_t dk, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots,
+                                 const float *v_slots, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t q8, float *out, int8_t *out_q,
+                                 float *out_d, uint32_t *out_s, int32_t reps, float *us_out) {
+    clear_error();
+    if (reps < 1 || reps > PROBE_MAX_REPS || !us_out) BG_FAIL(-1, "reps must be in [1, %d], with us_out", PROBE_MAX_REPS);
+    return attn_device(device, route, H, dk, N, P, t_max, n_slots, q, k_slots, v_slots, dev_state, seq_states, col_mode, q8, out, out_q, out_d, out_s, nullptr, reps, us_out);
+}
+
 // One decode attention launch of N columns behind a shared prefix (head size 64): k_slots / v_slots [N + 1][H][P][64], slot i column i's own, slot N the prefix's.
 // which 0: attn_fast_kernel<4, false, true> as a slim launch; 1: attn_prefix_kernel<8>.  A caller of attn_device with the outputs cut to their N rows.
 static int attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,

@@ -269,6 +269,19 @@ int biogpt_hip_get_wide_pass(const biogpt_hip_ctx *ctx);
 /* Launches of the wide pass layer enqueued: seven per layer and pass (two LayerNorm + Q8 producers, q/k/v, attention, out_proj, fc1, fc2), and two per pass that
  * wants every row (LayerNorm + Q8 of the rows, the lm_head); 0 for ever while the switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_wide_pass_launches(const biogpt_hip_ctx *ctx);
+/* The long-context attention's switch, per context (initial value: BIOGPT_HIP_LONG_CONTEXT=0/1, default 0).  It serves the files of the wide decode layer.
+ * on 1: an eval of the context's own columns whose furthest visible key lies in 1025 .. min(n_positions, 2048) attends on csrc/kernels_attn_long.hip.h -- one
+ * workgroup per (head, column) below 80 columns, sixteen columns per workgroup from 80 on -- which writes out_proj's Q8 blocks beside the f32 rows, so the wide
+ * decode, chunk and pass layers (where they are switched on) serve these evals as they serve shorter contexts.  Logits, K / V rows and ids are bit for bit those
+ * of off.  Off, evals up to 1024 keys, every pass over column states (the batched calls stay refused beyond 1024 keys), BioGPT-base files, float files and a
+ * context in the SIMD association are untouched; a pass of 80 or more columns on a device whose opt-in LDS cannot hold 16 x t_cap scores keeps the generic
+ * route.  Legality and return values are those of biogpt_hip_wide_decode (the captured single-token steps are dropped). */
+int biogpt_hip_long_context(biogpt_hip_ctx *ctx, int on);
+/* The long-context attention's switch: 0 off, 1 on.  -1: ctx is NULL. */
+int biogpt_hip_get_long_context(const biogpt_hip_ctx *ctx);
+/* Launches of attn_long_col_kernel / attn_long_tile_kernel enqueued or captured: one per layer and eval beyond 1024 keys; 0 for ever while the switch is off.
+ * -1: ctx is NULL. */
+int64_t biogpt_hip_long_attn_launches(const biogpt_hip_ctx *ctx);
 /* Linear-stage launches of the float chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
  * switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_float_launches(const biogpt_hip_ctx *ctx);
@@ -667,6 +680,20 @@ int biogpt_hip_tail_device(int device, int32_t stage, int32_t wtype, int32_t n, 
  * tile shape cfg (-1: the launch's choice); which 1: the generic mat-vec kernel, as a prompt pass of the context's own columns launches it.  For
  * tools/float_chain_bench.py. */
 int biogpt_hip_fchain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t cfg, int32_t reps, float *us_out);
+/* One stand-alone launch of a long-context attention kernel (csrc/kernels_attn_long.hip.h) through the engine's own launch helper: biogpt_hip_attn_device for a
+ * device state, head size 64 and t_max in 1025 .. 2048.  form 0: attn_long_col_kernel, N <= 8; 1: attn_long_tile_kernel, N >= 9.  q [N][H * 64]; k_slot / v_slot
+ * [H][P][64]; dev_state {n_past, n_gen, causal, chunk}; q8 0 / 1 / 2 and the outputs as biogpt_hip_attn_device's (rows = N rounded up to 16, plus one guard row,
+ * preset to 0xff).  launched [8]: form, threads, grid x, grid y, LDS bytes, t_cap, 0, 0.  Returns 0; -1 on an argument the engine never launches these kernels
+ * with (refused before the device is touched; biogpt_hip_last_error names it); -2 on a HIP error. */
+int biogpt_hip_attn_long_device(int device, int32_t form, int32_t H, int32_t N, int32_t P, int32_t t_max, const float *q, const float *k_slot, const float *v_slot,
+                                const int32_t *dev_state, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched);
+/* The same, then the launch reps times: us_out[i] microseconds between two events around launch i alone (tools/long_context_bench.py). */
+int biogpt_hip_attn_long_bench(int device, int32_t form, int32_t H, int32_t N, int32_t P, int32_t t_max, const float *q, const float *k_slot, const float *v_slot,
+                               const int32_t *dev_state, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps, float *us_out);
+/* biogpt_hip_attn_device, then the launch reps times, timed as above (tools/long_context_bench.py: the kernels the long-context ones are held against). */
+int biogpt_hip_attn_device_bench(int device, int32_t route, int32_t H, int32_t dk, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q,
+                                 const float *k_slots, const float *v_slots, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t q8,
+                                 float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps, float *us_out);
 /* One decode attention launch of N columns behind a shared prefix over caller-supplied inputs (head size 64, one layer): q [N][H * 64]; k_slots / v_slots
  * [N + 1][H][P][64], slot i column i's own and slot N the prefix's; seq_states [N][8] words as the engine's column states (n_past, ..., pad[0] = shared rows,
  * pad[1] = their slot).  which 0: the existing attn_fast_kernel<4, false, true>; 1: attn_prefix_kernel<8>, eight columns per workgroup (one shared range for
