@@ -728,6 +728,52 @@ def attn_long_device(form, H, N, P, t_max, q, k_slot, v_slot, dev_state, q8=0, d
     return rc, out, oq, od, os_, launched
 
 
+def long_runs_plan(seq_states):
+    """The planner of attn_long_runs_kernel (biogpt_hip_long_runs_plan) on packed column states int32 [N][8]: int32 [n_runs][2] rows (c0, n) -- runs of up to 16
+    neighbouring columns with equal (seq_id, pad[0], pad[1])."""
+    st = np.ascontiguousarray(seq_states, dtype=np.int32).reshape(-1, 8)
+    runs = np.zeros((max(len(st), 1), 2), dtype=np.int32)
+    n = lib().biogpt_hip_long_runs_plan(st.ctypes.data, len(st), runs.ctypes.data)
+    if n < 0:
+        raise BiogptError(_err())
+    return runs[:n].copy()
+
+
+def column_bucket(n_positions, T, own=False):
+    """The context bucket of a captured step at T keys in a table of n_positions rows (biogpt_hip_column_bucket): own: the context's own single-token steps;
+    otherwise the column steps of the batched calls, which have the buckets (512, 1024] and (1024, n_positions] in a table beyond 1024 rows."""
+    b = lib().biogpt_hip_column_bucket(int(n_positions), int(T), 1 if own else 0)
+    if b < 0:
+        raise BiogptError(_err())
+    return b
+
+
+def attn_long_cols_device(form, H, P, t_max, n_slots, q, k_slots, v_slots, seq_states, col_mode=1, shared=False, runs=None, q8=0, device=0, reps=0):
+    """One launch of an attention kernel over column states at 1025 .. 2048 keys on arrays held in host memory (biogpt_hip_attn_long_cols_device): form 0
+    attn_long_seq_kernel (one workgroup per column; shared: the first pad[0] rows in slot pad[1]), 1 attn_long_runs_kernel over runs int32 [n_runs][2] or None
+    (the planner's).  q float32 [N][H * 64], k_slots / v_slots float32 [n_slots][H][P][64], seq_states int32 [N][8].  Returns (rc, out, out_q, out_d, out_s,
+    launched) with the outputs whole: N rounded up to 16 rows plus a guard row, preset to 0xff; launched [8]: form, threads, grid x, grid y, LDS bytes, t_cap,
+    runs.  reps > 0: a seventh item, the microseconds of reps further launches."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    k = np.ascontiguousarray(k_slots, dtype=np.float32)
+    v = np.ascontiguousarray(v_slots, dtype=np.float32)
+    st = None if seq_states is None else np.ascontiguousarray(seq_states, dtype=np.int32).reshape(-1, 8)
+    N, D = 0 if st is None else len(st), int(H) * 64
+    if st is not None and min(D, int(P), int(n_slots)) >= 1 and (q.size < N * D or k.size < int(n_slots) * D * int(P) or v.size < int(n_slots) * D * int(P)):
+        raise BiogptError("attn_long_cols_device: q holds fewer than N rows, or the slots fewer than n_slots * H * P")
+    rows = (N + 15) // 16 * 16 + 1
+    out = np.zeros((rows, max(D, 0)), dtype=np.float32)
+    oq, od, os_ = np.zeros((rows, max(D, 0)), dtype=np.int8), np.zeros((rows, max(D, 0) // 32), dtype=np.float32), np.zeros((rows, max(D, 0) // 32), dtype=np.uint32)
+    launched = np.full(8, -1, dtype=np.int32)
+    rn = None if runs is None else np.ascontiguousarray(runs, dtype=np.int32).reshape(-1, 2)
+    us = np.zeros(max(int(reps), 1), dtype=np.float32)
+    rc = lib().biogpt_hip_attn_long_cols_device(int(device), int(form), int(H), N, int(P), int(n_slots), int(t_max), q.ctypes.data, k.ctypes.data, v.ctypes.data,
+                                                None if st is None else st.ctypes.data, int(col_mode), 1 if shared else 0, None if rn is None else rn.ctypes.data,
+                                                0 if rn is None else len(rn), int(q8), out.ctypes.data, oq.ctypes.data if q8 else None, od.ctypes.data if q8 else None,
+                                                os_.ctypes.data if q8 else None, launched.ctypes.data, int(reps), us.ctypes.data if reps > 0 else None)
+    return (rc, out, oq, od, os_, launched, us) if reps > 0 else (rc, out, oq, od, os_, launched)
+
+
 def beam_rows(rows, n_beams, run_score, given=False, first_step=False, device=0, masked=False):
     """beam_group_rows_kernel on rows held in host memory (biogpt_hip_beam_rows_device): rows float32 [G * n_beams][n_vocab], run_score [G * n_beams].
     Returns (score float32, col int32, id int32), each [G * n_beams][2 * n_beams]; rows the kernel left alone hold (NaN, -1, -1).  masked (with given):
@@ -875,6 +921,10 @@ SYMBOLS = [
     ("biogpt_hip_long_context", C.c_int, [_P, C.c_int]),
     ("biogpt_hip_get_long_context", C.c_int, [_P]),
     ("biogpt_hip_long_attn_launches", C.c_int64, [_P]),
+    ("biogpt_hip_long_cols_launches", C.c_int64, [_P]),
+    ("biogpt_hip_long_runs_plan", C.c_int, [_P, C.c_int32, _P]),
+    ("biogpt_hip_column_bucket", C.c_int, [C.c_int32] * 3),
+    ("biogpt_hip_attn_long_cols_device", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P] * 4 + [C.c_int32] * 2 + [_P, C.c_int32, C.c_int32] + [_P] * 5 + [C.c_int32, _P]),
     ("biogpt_hip_fpipe_launches", C.c_int64, [_P]),
     ("biogpt_hip_fpipe_stamps", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     ("biogpt_hip_generate_launches", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
@@ -2653,6 +2703,10 @@ class BiogptModel:
         if k < 0:
             raise BiogptError(_err())
         return k == 1
+
+    def long_cols_launches(self):
+        """Launches of the long attention kernels over column states enqueued (biogpt_hip_long_cols_launches): one per layer and batched pass beyond 1024 keys."""
+        return int(lib().biogpt_hip_long_cols_launches(self._h))
 
     def long_attn_launches(self):
         """Launches of the long-context attention kernels enqueued (biogpt_hip_long_attn_launches): one per layer and eval beyond 1024 keys; 0 while the switch is off."""

@@ -210,7 +210,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain, wide_decode, wide_chunk, wide_pass, long_context;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain, wide_decode, wide_chunk, wide_pass, long_context, long_runs;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -247,12 +247,14 @@ struct EngineOptions {
         wide_chunk = get("BIOGPT_HIP_WIDE_CHUNK", 1);            // 1 (the default: measured faster at every chunk size and key count): a new context of a file the wide chunk layer serves starts with it switched on; 0: off (biogpt_hip_wide_chunk; kernels_wchunk.hip.h)
         wide_pass = get("BIOGPT_HIP_WIDE_PASS", 1);              // 1 (the default: DESIGN 4.4): a new context of a file the wide pass layer serves starts with it switched on; 0: off (biogpt_hip_wide_pass; kernels_wpass.hip.h)
         long_context = get("BIOGPT_HIP_LONG_CONTEXT", 0);        // 0 (the default): off; 1: a new context of a wide file starts with the long-context attention switched on (biogpt_hip_long_context; kernels_attn_long.hip.h)
+        long_runs = get("BIOGPT_HIP_LONG_RUNS", -1);              // packed passes of a wide file over column states beyond 1024 keys: -1 attn_long_runs_kernel by the form rule (LONG_RUNS_MIN_AVG_COLS), 0 never (attn_long_seq_kernel), 1 wherever the device's LDS holds it (A/B arms)
         assoc = get("BIOGPT_HIP_ASSOC", 0);                        // 1: a new context of a file the SIMD association serves starts in it (biogpt_hip_assoc; kernels_assoc.hip.h)
         xpipe_as_res = get("BIOGPT_HIP_XPIPE_AS_RES", 0);          // measurement only: ordinary pipelined launches through the RES instantiations (tests/test_gpu_resident.py)
     }
 };
 
 constexpr int GRAPH_BUCKETS = 6;      // the context buckets of a captured decode step: graph_bucket() is in [0, GRAPH_BUCKETS)
+constexpr int COLUMN_BUCKETS = 7;     // those of a captured column step: column_bucket() is in [0, COLUMN_BUCKETS)
 
 // The form of a step of column generation: everything but the call's shape and the context bucket that decides which launches the step is
 struct StepForm {
@@ -267,10 +269,10 @@ struct StepForm {
 // is filed under its form and its context bucket; every combination of a form's fields has slots of its own, so no form replays another's step, whatever the
 // modes' argument checks let through.  slot() alone knows the layout.
 struct ColumnGraphs {
-    static constexpr int N_SLOTS = StepForm::N_SELECTIONS * 2 * 2 * 2 * GRAPH_BUCKETS;
+    static constexpr int N_SLOTS = StepForm::N_SELECTIONS * 2 * 2 * 2 * COLUMN_BUCKETS;
     hipGraphExec_t exec[N_SLOTS] = {};
     int key_a = 0, key_b = 0;
-    static int slot(const StepForm &f, int bucket) { return ((((int)f.sel * 2 + (f.lp ? 1 : 0)) * 2 + (f.shared ? 1 : 0)) * 2 + (f.xcols ? 1 : 0)) * GRAPH_BUCKETS + bucket; }
+    static int slot(const StepForm &f, int bucket) { return ((((int)f.sel * 2 + (f.lp ? 1 : 0)) * 2 + (f.shared ? 1 : 0)) * 2 + (f.xcols ? 1 : 0)) * COLUMN_BUCKETS + bucket; }
 };
 
 // ---- context ----------------------------------------------------------------------------------------
@@ -405,6 +407,9 @@ struct biogpt_hip_ctx {
     bool wide_pass = false;                // the wide pass layer is switched on (biogpt_hip_wide_pass): passes of 9 or more of the context's own columns run on kernels_wpass.hip.h
     int wpass_max_cols = -1;               // the most columns of such a pass: n_positions where the layer's geometry holds the file's five matrices within the device's LDS, else 0 (-1: not asked yet, enqueue_forward asks)
     bool long_context = false;             // the long-context attention is switched on (biogpt_hip_long_context): the context's own columns of a wide file at 1025 .. 2048 keys attend on kernels_attn_long.hip.h
+    int64_t long_cols_launches = 0;        // launches of attn_long_seq_kernel / attn_long_runs_kernel enqueued (biogpt_hip_long_cols_launches): passes over column states beyond 1024 keys
+    const int32_t *long_runs = nullptr;    // the run plan of the packed pass being enqueued, behind its column states on the device (flush_columns); n_long_runs == 0: none
+    int n_long_runs = 0;
     int64_t long_attn_launches = 0;        // launches of attn_long_col_kernel / attn_long_tile_kernel enqueued (biogpt_hip_long_attn_launches)
     int64_t wpass_launches = 0;            // launches of the wide pass layer enqueued (biogpt_hip_wide_pass_launches)
     int assoc = 0;                         // 1: the SIMD association (biogpt_hip_assoc): every pass on the five-launch layer with the kernels of kernels_assoc.hip.h; no call over column states
@@ -728,6 +733,34 @@ constexpr int LONG_ATTN_MAX_KEYS = 2048;
 extern "C" int bg_attn_long_geometry(int form, int H, int N, int t_cap, int32_t *six);
 extern "C" int bg_attn_long_tile_fits(int t_cap);
 extern "C" int bg_attn_long_launch(int form, const void *params, size_t params_bytes, int H, int N, hipStream_t st, int32_t *report);
+// the same reach over column states (kernels_attn_long_cols.hip.h, attn_long_cols_tu.hip).  form 0: one column per workgroup (attn_long_seq_kernel<shared>), 1: a
+// run of up to LONG_RUN_COLS packed columns per workgroup (attn_long_runs_kernel; runs: n_runs {c0, n} pairs on the device; the workgroup is as large as the tile
+// kernel's: bg_attn_long_runs_fits).  six: form, threads, grid x, grid y, LDS bytes, t_cap
+constexpr int LONG_RUN_COLS = 16;
+extern "C" int bg_attn_long_runs_fits(int t_cap);
+extern "C" int bg_attn_long_cols_launch(int form, const void *params, size_t params_bytes, int shared, const int32_t *runs, int n_runs, int H, int N, hipStream_t st,
+                                        int32_t *report);
+// The planner of attn_long_runs_kernel: the columns of a packed pass walked greedily into runs {c0, n} -- a run is cut at LONG_RUN_COLS columns or at the first
+// column whose (seq_id, pad[0], pad[1]) differ: the chunks of one prompt, the tokens of one continuation.  Returns the number of runs; runs_out holds up to 2 * N words.
+inline int long_runs_plan(const bgk::SeqState *st, int N, int32_t *runs_out) {
+    int n_runs = 0;
+    for (int i = 0; i < N;) {
+        int n = 1;
+        while (n < LONG_RUN_COLS && i + n < N && st[i + n].seq_id == st[i].seq_id && st[i + n].pad[0] == st[i].pad[0] && st[i + n].pad[1] == st[i].pad[1]) n++;
+        runs_out[2 * (size_t)n_runs] = i; runs_out[2 * (size_t)n_runs + 1] = n;
+        n_runs++;
+        i += n;
+    }
+    return n_runs;
+}
+// Which form a packed pass of n columns in n_runs runs takes (opt: BIOGPT_HIP_LONG_RUNS).  The rule is the own columns' carried over, NOT a measurement: the tile
+// kernel takes over from GROUPED_ATTN_MIN_COLS columns (there every workgroup has 16 queries), so the run form needs as many columns and runs that are at least
+// half full on average (LONG_RUNS_MIN_AVG_COLS); and the device's opt-in LDS has to hold the workgroup.
+constexpr int LONG_RUNS_MIN_AVG_COLS = 8;
+inline bool long_runs_form(int opt, int n, int n_runs, int t_cap, int min_cols) {
+    if (opt == 0 || n_runs < 1 || bg_attn_long_runs_fits(t_cap) != 1) return false;
+    return opt == 1 || (n >= min_cols && n >= LONG_RUNS_MIN_AVG_COLS * n_runs);
+}
 // why a file cannot have the long-context attention (null: it can): the files of the wide decode / chunk / pass layers, with a table beyond 1024 rows or not
 inline const char *long_context_refusal(const biogpt_hip_hparams &hp) {
     if (!is_quantized(ftype_to_type(hp.ftype))) return "the weights are not block-quantized";
@@ -1462,6 +1495,7 @@ struct PassLaunch {
     bool wdec;                      // the wide decode layer: one token of the context's own column of a wide file whose context has it switched on (kernels_wdecode.hip.h)
     bool wchunk;                    // the wide chunk layer: 2 .. 8 tokens of the context's own columns of a wide file whose context has it switched on (kernels_wchunk.hip.h)
     bool long_attn;                 // the attention launch of this pass is one of kernels_attn_long.hip.h (1025 .. 2048 keys of a wide file, biogpt_hip_long_context on)
+    bool long_cols;                 // the wide chain beyond FAST_ATTN_MAX_KEYS: the attention launch is one of kernels_attn_long_cols.hip.h (column states, up to min(P, 2048) keys)
     bool wpass;                     // the wide pass layer: 9 or more of the context's own columns of a wide file whose context has it switched on (kernels_wpass.hip.h)
     bool simd;                      // the context is in the SIMD association: the generic sites launch the kernels of kernels_assoc.hip.h
     bool schain;                    // the SIMD chain: a pass over column states of a context in the SIMD association that has it switched on (kernels_schain.hip.h)
@@ -1680,6 +1714,13 @@ bool enqueue_attention(PassLaunch &k, int l) {
         a.t_cap = tile ? attn_pass_t_cap(P, t_max) : attn_decode_t_cap(P, t_max);
         HIP_TRY(false, (hipError_t)bg_attn_long_launch(tile ? 1 : 0, &a, sizeof(a), H, N, st, nullptr));
         c->long_attn_launches++;
+        return true;
+    }
+    if (k.long_cols) {      // (the wide chain, 1024 < t_max <= min(P, LONG_ATTN_MAX_KEYS): enqueue_forward).  The run form for the packed pass whose plan flush_columns left
+        const bool runs = k.col_mode == 1 && k.seq == c->cols && c->n_long_runs > 0;
+        a.t_cap = runs ? attn_pass_t_cap(P, t_max) : attn_decode_t_cap(P, t_max);
+        HIP_TRY(false, (hipError_t)bg_attn_long_cols_launch(runs ? 1 : 0, &a, sizeof(a), k.pass.shared_prefix ? 1 : 0, c->long_runs, c->n_long_runs, H, N, st, nullptr));
+        c->long_cols_launches++;
         return true;
     }
     if (!(dk == 64 && t_max <= FAST_ATTN_MAX_KEYS)) {
@@ -2130,7 +2171,9 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     // enough columns to fill 16-wide MFMA tiles: the chain runs on the int8 matrix cores from the row-tiled weight image
     k.mfma = k.pchain && N >= (pass.cols == Cols::PerSequence ? MFMA_MIN_DECODE_COLS : MFMA_MIN_PASS_COLS) && c->tile_img != nullptr;
     // a pass over column states of any other block-quantized file with head size 64: the wide chain (the context's own columns stay on the generic kernels)
-    k.wchain = !k.chain && !k.schain && batch && chain_kind_of(hp) == CHAIN_WIDE && t_max <= 1024;
+    // (beyond FAST_ATTN_MAX_KEYS, up to the reach of kernels_attn_long_cols.hip.h, it attends on those kernels: long_cols)
+    k.wchain = !k.chain && !k.schain && batch && chain_kind_of(hp) == CHAIN_WIDE && t_max <= std::max(FAST_ATTN_MAX_KEYS, std::min(hp.n_positions, LONG_ATTN_MAX_KEYS));
+    k.long_cols = k.wchain && t_max > FAST_ATTN_MAX_KEYS;
     // a pass over column states of a float file whose context has the float chain switched on (the context's own columns stay on fdec_kernel / matvec_kernel)
     k.fchain = !k.chain && !k.wchain && batch && chain_kind(c) == CHAIN_FLOAT && t_max <= 1024;
     if (k.fchain && (pass.rows == Rows::Last || pass.rows == Rows::AllGeneric)) BG_FAIL(false, "internal: a float fast chain pass with rows it does not serve");
@@ -2505,6 +2548,15 @@ int graph_bucket(int T) { return T <= 256 ? (T - 1) / 64 : (T <= 512 ? 4 : 5); }
 int bucket_tmax(const biogpt_hip_ctx *c, int b) {
     const int t = b < 4 ? 64 * (b + 1) : (b == 4 ? 512 : c->hp.n_positions);
     return std::min(t, c->hp.n_positions);
+}
+// The buckets of the captured COLUMN steps (ColumnGraphs): graph_bucket's for a table of up to 1024 rows.  A longer table has a bucket (512, 1024] in front of its
+// last one (1024, P]: steps at 513 .. 1024 keys are captured with t_max = 1024 and keep the kernels every chain has there -- captured at t_max = P they would be
+// refused by the base, float and SIMD chains, and the wide chain would attend on its long kernels where it need not.
+int column_bucket(int P, int T) { return (P <= 1024 || T <= 1024) ? graph_bucket(T) : 6; }
+int column_bucket_tmax(const biogpt_hip_ctx *c, int b) {
+    const int P = c->hp.n_positions;
+    if (P <= 1024 || b < 5) return bucket_tmax(c, b);
+    return b == 5 ? 1024 : P;
 }
 
 // pl: 1 = the step as the XCD-pipelined launch (the caller holds the device's pipeline slot), 0 = the five-launch layer
@@ -3272,6 +3324,18 @@ int biogpt_hip_get_long_context(const biogpt_hip_ctx *ctx) {
     return ctx->long_context ? 1 : 0;
 }
 int64_t biogpt_hip_long_attn_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->long_attn_launches : -1; }
+int64_t biogpt_hip_long_cols_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->long_cols_launches : -1; }
+int biogpt_hip_long_runs_plan(const int32_t *seq_states, int32_t N, int32_t *runs_out) {
+    clear_error();
+    if (!seq_states || !runs_out) BG_FAIL(-1, "seq_states or runs_out is NULL");
+    if (N < 1 || N > LONG_ATTN_MAX_KEYS) BG_FAIL(-1, "N must be in [1, %d]", LONG_ATTN_MAX_KEYS);
+    return long_runs_plan(reinterpret_cast<const bgk::SeqState *>(seq_states), N, runs_out);
+}
+int biogpt_hip_column_bucket(int32_t n_positions, int32_t T, int32_t own) {
+    clear_error();
+    if (n_positions < 1 || T < 1 || T > n_positions) BG_FAIL(-1, "T must be in [1, n_positions]");
+    return own ? graph_bucket(T) : column_bucket(n_positions, T);
+}
 // the key counts at which the layer's attention launch changes form: dec_attn_kernel at 16 / 8 / 4 lanes per key up to the first three, beyond them the generic
 // route's launch, which writes the Q8 blocks itself up to the last and leaves them to q8_rows_kernel beyond it.  Returns how many there are; out (or null) takes the first cap.
 int biogpt_hip_wide_decode_key_borders(int32_t *out, int cap) {
@@ -3345,6 +3409,17 @@ static bool flush_columns(biogpt_hip_ctx *ctx, std::vector<bgk::SeqState> &cols,
                           const std::function<bool(int, int, size_t)> &pass, const std::vector<int32_t> *tail = nullptr) {
     if (cols.empty()) return true;
     const size_t n = cols.size();
+    // a pass of a wide file beyond FAST_ATTN_MAX_KEYS that carries no other table: its run plan (long_runs_plan) goes up as the tail where the form rule takes the
+    // run form, and enqueue_attention finds it through ctx->long_runs while the pass is enqueued
+    std::vector<int32_t> long_plan;
+    int n_long_runs = 0;
+    if (pass_tmax > FAST_ATTN_MAX_KEYS && (!tail || tail->empty()) && ctx->opt.long_runs != 0 && chain_kind_of(ctx->hp) == CHAIN_WIDE) {
+        long_plan.resize(2 * n);
+        n_long_runs = long_runs_plan(cols.data(), (int)n, long_plan.data());
+        if (!long_runs_form(ctx->opt.long_runs, (int)n, n_long_runs, attn_pass_t_cap(ctx->hp.n_positions, pass_tmax), GROUPED_ATTN_MIN_COLS)) n_long_runs = 0;
+        long_plan.resize(2 * (size_t)n_long_runs);
+        if (n_long_runs) tail = &long_plan;
+    }
     if (tail && !tail->empty()) {
         static_assert(sizeof(bgk::SeqState) == 32, "a column state holds two table rows");
         cols.resize(n + (tail->size() * 4 + sizeof(bgk::SeqState) - 1) / sizeof(bgk::SeqState));      // (new states are all zero)
@@ -3364,7 +3439,11 @@ static bool flush_columns(biogpt_hip_ctx *ctx, std::vector<bgk::SeqState> &cols,
     }
     HIP_TRY(false, hipMemcpyAsync(ctx->cols, cols.data(), sizeof(bgk::SeqState) * cols.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(false, hipStreamSynchronize(ctx->stream));   // the host vector is reused for the next pass
-    if (!pass((int)n, pass_tmax, flat0)) return false;
+    ctx->long_runs = n_long_runs ? reinterpret_cast<const int32_t *>(ctx->cols + n) : nullptr;
+    ctx->n_long_runs = n_long_runs;
+    const bool ok = pass((int)n, pass_tmax, flat0);
+    ctx->long_runs = nullptr; ctx->n_long_runs = 0;
+    if (!ok) return false;
     flat0 += n;
     cols.clear();
     pass_tmax = 0;
@@ -3592,12 +3671,12 @@ struct ColumnKeys {
 static bool capture_column_steps(biogpt_hip_ctx *ctx, ColumnGraphs &graphs, const StepForm &form, const ColumnKeys &keys, int n_steps, const ColumnStep &step, bool *use_graph) {
     *use_graph = ctx->opt.no_graph == 0 && (ctx->xc_batch != 0 || plain_graph_begin(ctx));      // (a captured five-launch step is not replayed beside another context's persistent launch)
     if (*use_graph && n_steps > 1) {
-        for (int b = graph_bucket(keys.first_replayed()); b <= graph_bucket(keys.worst(n_steps - 1)); b++) {
+        for (int b = column_bucket(keys.P, keys.first_replayed()); b <= column_bucket(keys.P, keys.worst(n_steps - 1)); b++) {
             hipGraphExec_t &exec = graphs.exec[ColumnGraphs::slot(form, b)];
             if (exec) continue;
             hipGraph_t g = nullptr;
             HIP_TRY(false, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-            const bool ok = step(bucket_tmax(ctx, b));
+            const bool ok = step(column_bucket_tmax(ctx, b));
             hipError_t e = hipStreamEndCapture(ctx->stream, &g);
             if (!ok) { if (g) (void)hipGraphDestroy(g); return false; }
             HIP_TRY(false, e);
@@ -3694,7 +3773,7 @@ static bool run_column_steps(biogpt_hip_ctx *ctx, const ColumnGraphs &graphs, co
         for (const int end = std::min(n_steps - 1, k + keys.group() - 1); k <= end; k++) {
             int t_max = keys.worst(k);
             if (seen_step >= 0) t_max = std::min<long>(t_max, std::max<long>(keys.first_replayed(), (long)seen_pos + (long)(k - seen_step) * keys.stride));
-            if (use_graph) HIP_TRY(false, hipGraphLaunch(graphs.exec[ColumnGraphs::slot(form, graph_bucket(t_max))], ctx->stream));
+            if (use_graph) HIP_TRY(false, hipGraphLaunch(graphs.exec[ColumnGraphs::slot(form, column_bucket(keys.P, t_max))], ctx->stream));
             else if (!step(t_max)) return false;
         }
         if (!live_dev) continue;
@@ -5773,7 +5852,7 @@ struct QueueRun {
                 if (q.req[(size_t)unit] >= 0) t_max = std::max(t_max, q.position(unit, rq.whole_len(q.req[(size_t)unit])) + 1);
             t_max = std::min(t_max, P);
             if (use_graph) {
-                hipGraphExec_t ge = qc.graphs->exec[ColumnGraphs::slot(qc.form, graph_bucket(t_max))];
+                hipGraphExec_t ge = qc.graphs->exec[ColumnGraphs::slot(qc.form, column_bucket(P, t_max))];
                 if (!ge) BG_FAIL(-2, "internal: no captured %s for %d keys", qc.step_name, t_max);
                 HIP_TRY(-2, hipGraphLaunch(ge, ctx->stream));
             } else if (!qc.step(t_max)) {

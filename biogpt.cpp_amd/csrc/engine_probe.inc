@@ -567,6 +567,78 @@ int biogpt_hip_attn_long_bench(int device, int32_t form, int32_t H, int32_t N, i
     return attn_long_device(device, form, H, N, P, t_max, q, k_slot, v_slot, dev_state, q8, out, out_q, out_d, out_s, nullptr, reps, us_out);
 }
 
+// One stand-alone launch of an attention kernel over column states at 1025 .. 2048 keys (kernels_attn_long_cols.hip.h), through bg_attn_long_cols_launch as
+// enqueue_attention launches it.  form 0: attn_long_seq_kernel<shared>; 1: attn_long_runs_kernel over `runs` (null: long_runs_plan's).  Everything the engine
+// never launches is refused before the device is touched; a caller's plan is held to what the planner guarantees.
+int biogpt_hip_attn_long_cols_device(int device, int32_t form, int32_t H, int32_t N, int32_t P, int32_t n_slots, int32_t t_max, const float *q, const float *k_slots,
+                                     const float *v_slots, const int32_t *seq_states, int32_t col_mode, int32_t shared, const int32_t *runs, int32_t n_runs, int32_t q8,
+                                     float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched, int32_t reps, float *us_out) {
+    clear_error();
+    if (!q || !k_slots || !v_slots || !seq_states || !out) BG_FAIL(-1, "q, k_slots, v_slots, seq_states or out is NULL");
+    if (form != 0 && form != 1) BG_FAIL(-1, "form must be 0 (attn_long_seq_kernel) or 1 (attn_long_runs_kernel)");
+    if (H < 1 || H > 64) BG_FAIL(-1, "H must be in [1, 64]");
+    if (N < 1 || N > LONG_ATTN_MAX_KEYS) BG_FAIL(-1, "N must be in [1, %d]", LONG_ATTN_MAX_KEYS);
+    if (P < 1 || P > 8192) BG_FAIL(-1, "P must be in [1, 8192]");
+    if (n_slots < 1 || n_slots > 1024) BG_FAIL(-1, "n_slots must be in [1, 1024]");
+    if (t_max <= FAST_ATTN_MAX_KEYS || t_max > LONG_ATTN_MAX_KEYS) BG_FAIL(-1, "t_max must be in [%d, %d]: up to %d keys a pass takes the kernels of biogpt_hip_attn_device", FAST_ATTN_MAX_KEYS + 1, LONG_ATTN_MAX_KEYS, FAST_ATTN_MAX_KEYS);
+    if (t_max > P) BG_FAIL(-1, "t_max must be at most P: t_cap never exceeds the table");
+    if (col_mode != 0 && col_mode != 1) BG_FAIL(-1, "col_mode must be 0 or 1");
+    if (form == 1 && col_mode != 1) BG_FAIL(-1, "the run form serves packed columns only (col_mode 1)");
+    if (q8 < 0 || q8 > 2 || (q8 > 0 && (!out_q || !out_d || !out_s))) BG_FAIL(-1, "q8 must be 0, 1 or 2, with out_q, out_d and out_s");
+    if (reps < 0 || reps > PROBE_MAX_REPS || (reps > 0 && !us_out)) BG_FAIL(-1, "reps must be in [0, %d], with us_out", PROBE_MAX_REPS);
+    const int t_cap = form == 1 ? attn_pass_t_cap(P, t_max) : attn_decode_t_cap(P, t_max);
+    const bgk::SeqState *hs = reinterpret_cast<const bgk::SeqState *>(seq_states);
+    for (int i = 0; i < N; i++) {
+        const int T = col_mode ? hs[i].t_vis : hs[i].n_past + 1;
+        if (T < 1 || T > t_cap || T > t_max) BG_FAIL(-1, "column %d: %d visible keys outside [1, t_cap = %d] (t_max %d)", i, T, t_cap, t_max);
+        if (!probe_slot_ok(__func__, i, col_mode ? hs[i].seq_id : i, n_slots)) return -1;
+        if (form == 1 || shared) {
+            if (hs[i].pad[0] < 0 || hs[i].pad[0] > T) BG_FAIL(-1, "column %d: %d shared rows outside [0, its visible keys]", i, hs[i].pad[0]);
+            if (hs[i].pad[1] < 0 || hs[i].pad[1] >= n_slots) BG_FAIL(-1, "column %d: shared slot %d outside [0, n_slots)", i, hs[i].pad[1]);
+        }
+    }
+    std::vector<int32_t> plan;
+    if (form == 1) {
+        plan.resize(2 * (size_t)N);
+        if (!runs) {
+            n_runs = long_runs_plan(hs, N, plan.data());
+        } else {
+            if (n_runs < 1 || n_runs > N) BG_FAIL(-1, "n_runs must be in [1, N]");
+            std::memcpy(plan.data(), runs, 8 * (size_t)n_runs);
+        }
+        int next = 0;
+        for (int r = 0; r < n_runs; r++) {
+            const int c0 = plan[2 * r], n = plan[2 * r + 1];
+            if (n < 1 || n > LONG_RUN_COLS) BG_FAIL(-1, "run %d: n = %d outside [1, %d]", r, n, LONG_RUN_COLS);
+            if (c0 != next || c0 + n > N) BG_FAIL(-1, "run %d: columns [%d, %d), expected to start at %d within N = %d: every column lies in exactly one run, in order", r, c0, c0 + n, next, N);
+            for (int i = c0 + 1; i < c0 + n; i++)
+                if (hs[i].seq_id != hs[c0].seq_id || hs[i].pad[0] != hs[c0].pad[0] || hs[i].pad[1] != hs[c0].pad[1])
+                    BG_FAIL(-1, "run %d: column %d has another slot or other shared rows than column %d", r, i, c0);
+            next = c0 + n;
+        }
+        if (next != N) BG_FAIL(-1, "the runs cover columns [0, %d), not all %d", next, N);
+        plan.resize(2 * (size_t)n_runs);
+    }
+    HIP_TRY(-2, hipSetDevice(device));
+    if (form == 1 && bg_attn_long_runs_fits(t_cap) != 1) BG_FAIL(-1, "the device's LDS does not hold the run form's workgroup at %d keys", t_cap);
+    const int D = H * 64;
+    ProbeImage im;
+    const AttnProbeParts o = attn_probe_parts(im, H, 64, N, P, n_slots, q, k_slots, v_slots, seq_states, form == 1 ? plan.data() : PROBE_NO_STATE,
+                                               form == 1 ? plan.size() * 4 : sizeof(PROBE_NO_STATE));
+    if (!im.upload()) return -2;
+    const bgk::AttnParams a = attn_probe_params(im, o, N, D, 64, P, t_cap, col_mode, (int64_t)H * P * 64, q8);
+    int32_t six[6] = {0, 0, 0, 0, 0, 0};
+    auto launch = [&]() -> hipError_t {
+        return (hipError_t)bg_attn_long_cols_launch(form, &a, sizeof(a), shared ? 1 : 0, form == 1 ? im.at<const int32_t>(o.extra) : nullptr, form == 1 ? n_runs : 0, H, N, 0, six);
+    };
+    HIP_TRY(-2, launch());
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    report_launch(launched, {six[0], six[1], six[2], six[3], six[4], six[5], form == 1 ? n_runs : 0});
+    if (!attn_probe_read(im, o, q8, out, out_q, out_d, out_s)) return -2;
+    return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1000.0f; });
+}
+
 int biogpt_hip_attn_device_bench(int device, int32_t route, int32_t H, int32_t dk, int32_t N, int32_t P, int32_t t_max, int32_t n_slots, const float *q, const float *k_slots,
                                  const float *v_slots, const int32_t *dev_state, const int32_t *seq_states, int32_t col_mode, int32_t q8, float *out, int8_t *out_q,
                                  float *out_d, uint32_t *out_s, int32_t reps, float *us_out) {

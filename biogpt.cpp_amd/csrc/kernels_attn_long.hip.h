@@ -68,6 +68,7 @@ __device__ __forceinline__ float long_inv_sum(double s) {
     return (float)r;
 }
 
+#ifndef BGK_ATTN_LONG_NO_KERNELS      // (kernels_attn_long_cols.hip.h reads the constants and helpers above in a unit of its own)
 __global__ __launch_bounds__(1024) void attn_long_tile_kernel(const AttnParams p) {
     constexpr int DK = 64, NW = 16, G = LONG_TILE_COLS, MXP = LONG_TILE_MXP, NT = LONG_ATTN_THREADS, KT = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -383,5 +384,6 @@ __global__ __launch_bounds__(1024) void attn_long_col_kernel(const AttnParams p)
         store_head_output(p, i, h, tid, (float)(t0 + t1), p.oq_q != nullptr);
     }
 }
+#endif
 
 }  // namespace bgk

@@ -273,7 +273,7 @@ int64_t biogpt_hip_wide_pass_launches(const biogpt_hip_ctx *ctx);
  * on 1: an eval of the context's own columns whose furthest visible key lies in 1025 .. min(n_positions, 2048) attends on csrc/kernels_attn_long.hip.h -- one
  * workgroup per (head, column) below 80 columns, sixteen columns per workgroup from 80 on -- which writes out_proj's Q8 blocks beside the f32 rows, so the wide
  * decode, chunk and pass layers (where they are switched on) serve these evals as they serve shorter contexts.  Logits, K / V rows and ids are bit for bit those
- * of off.  Off, evals up to 1024 keys, every pass over column states (the batched calls stay refused beyond 1024 keys), BioGPT-base files, float files and a
+ * of off.  Off, evals up to 1024 keys, every pass over column states (the batched calls attend on csrc/kernels_attn_long_cols.hip.h there, with no switch), BioGPT-base files, float files and a
  * context in the SIMD association are untouched; a pass of 80 or more columns on a device whose opt-in LDS cannot hold 16 x t_cap scores keeps the generic
  * route.  Legality and return values are those of biogpt_hip_wide_decode (the captured single-token steps are dropped). */
 int biogpt_hip_long_context(biogpt_hip_ctx *ctx, int on);
@@ -282,6 +282,13 @@ int biogpt_hip_get_long_context(const biogpt_hip_ctx *ctx);
 /* Launches of attn_long_col_kernel / attn_long_tile_kernel enqueued or captured: one per layer and eval beyond 1024 keys; 0 for ever while the switch is off.
  * -1: ctx is NULL. */
 int64_t biogpt_hip_long_attn_launches(const biogpt_hip_ctx *ctx);
+/* Launches of attn_long_seq_kernel / attn_long_runs_kernel (csrc/kernels_attn_long_cols.hip.h) enqueued or captured: one per layer and pass over column
+ * states of a wide file whose furthest visible key lies in 1025 .. min(n_positions, 2048) -- the batched calls there (score_batch, embed_batch,
+ * score_continuations, the column-generation calls, the queue).  No switch: these passes were refused before.  A packed pass takes the run form (runs of up to 16
+ * neighbouring columns of one slot per workgroup) when it has 80 columns or more, its runs average 8 columns or more and the device's opt-in LDS holds the
+ * workgroup, otherwise one workgroup per column, as every decode step (BIOGPT_HIP_LONG_RUNS: -1 this rule, 0 never the run form, 1 wherever it fits).
+ * biogpt_hip_long_attn_launches does not count them.  -1: ctx is NULL. */
+int64_t biogpt_hip_long_cols_launches(const biogpt_hip_ctx *ctx);
 /* Linear-stage launches of the float chain (q/k/v, out_proj, fc1, fc2, the all-rows lm_head), counted as they are enqueued or captured; 0 for ever while the
  * switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_float_launches(const biogpt_hip_ctx *ctx);
@@ -706,6 +713,24 @@ int biogpt_hip_attn_prefix_device(int device, int32_t H, int32_t N, int32_t P, i
 int biogpt_hip_attn_prefix_bench(int device, int32_t H, int32_t N, int32_t P, int32_t t_cap, const float *q, const float *k_slots, const float *v_slots,
                                  const int32_t *seq_states, int32_t which, int32_t q8, float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t reps,
                                  float *us_out /* [reps] */);
+/* The planner of attn_long_runs_kernel, no device: the N <= 2048 packed column states of a pass (seq_states [N][8] words) walked greedily into runs of up to 16
+ * neighbouring columns with equal (seq_id, pad[0], pad[1]).  runs_out [N][2]: c0, n.  Returns the number of runs, or -1. */
+int biogpt_hip_long_runs_plan(const int32_t *seq_states, int32_t N, int32_t *runs_out);
+/* The context bucket a captured step at T keys is filed under in a table of n_positions rows, no device.  own 1: the context's own single-token steps (64 / 128 /
+ * 192 / 256 / 512 / n_positions keys); 0: the column steps, which are the same for n_positions <= 1024 and have the buckets (512, 1024] and (1024, n_positions]
+ * beyond.  -1: T outside [1, n_positions]. */
+int biogpt_hip_column_bucket(int32_t n_positions, int32_t T, int32_t own);
+/* One stand-alone launch of an attention kernel of csrc/kernels_attn_long_cols.hip.h through the helper the engine's passes use: head size 64, t_max in 1025 ..
+ * 2048, N <= 2048 column states.  form 0: attn_long_seq_kernel<shared != 0>, one workgroup per column (col_mode 0: slot i, n_past + 1 keys; 1: slot seq_id, t_vis
+ * keys; shared: the first pad[0] rows in slot pad[1]); form 1: attn_long_runs_kernel (col_mode 1 only; the shared rows are read from the states whatever `shared`
+ * says) over runs [n_runs][2] {c0, n}, or NULL for the planner's.  A caller's plan is validated: every column in exactly one run, in order, n in [1, 16], one
+ * (seq_id, pad[0], pad[1]) per run.  q [N][H * 64]; k_slots / v_slots [n_slots][H][P][64]; q8 and the outputs as biogpt_hip_attn_device's (rows = N rounded up to
+ * 16, plus one guard row, preset to 0xff).  launched [8]: form, threads, grid x, grid y, LDS bytes, t_cap, runs, 0.  reps > 0: the launch reps more times, us_out[i]
+ * microseconds between two events around launch i alone (tools/long_batch_bench.py).  Returns 0; -1 on an argument the engine never launches these kernels with
+ * (refused before the device is touched); -2 on a HIP error. */
+int biogpt_hip_attn_long_cols_device(int device, int32_t form, int32_t H, int32_t N, int32_t P, int32_t n_slots, int32_t t_max, const float *q, const float *k_slots,
+                                     const float *v_slots, const int32_t *seq_states, int32_t col_mode, int32_t shared, const int32_t *runs, int32_t n_runs, int32_t q8,
+                                     float *out, int8_t *out_q, float *out_d, uint32_t *out_s, int32_t *launched, int32_t reps, float *us_out);
 /* The planner of attn_runs_kernel: the N packed column states of a pass (seq_states [N][8] words, col_mode 1) walked greedily into runs of up to eight
  * consecutive columns whose first R visible rows are the same rows of one slot S.  runs_out [N][4]: c0, n, R, S.  Returns the number of runs, or -1. */
 int biogpt_hip_attn_runs_plan(const int32_t *seq_states, int32_t N, int32_t *runs_out /* [N][4]: c0, n, R, S */);
