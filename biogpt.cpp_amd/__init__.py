@@ -915,6 +915,9 @@ SYMBOLS = [
     ("biogpt_hip_wide_chunk", C.c_int, [_P, C.c_int]),
     ("biogpt_hip_get_wide_chunk", C.c_int, [_P]),
     ("biogpt_hip_wide_chunk_launches", C.c_int64, [_P]),
+    ("biogpt_hip_wide_cols", C.c_int, [_P, C.c_int]),
+    ("biogpt_hip_get_wide_cols", C.c_int, [_P]),
+    ("biogpt_hip_wide_cols_launches", C.c_int64, [_P]),
     ("biogpt_hip_wide_pass", C.c_int, [_P, C.c_int]),
     ("biogpt_hip_get_wide_pass", C.c_int, [_P]),
     ("biogpt_hip_wide_pass_launches", C.c_int64, [_P]),
@@ -1025,6 +1028,7 @@ SYMBOLS = [
     ("biogpt_hip_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 4 + [C.c_int32] + [_P] * 7 + [C.c_int32] * 3 + [_P] * 7),
     ("biogpt_hip_wide_chain_device", C.c_int, [C.c_int] + [C.c_int32] * 5 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 4),
     ("biogpt_hip_wide_chain_bench", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P]),
+    ("biogpt_hip_wcols_device", C.c_int, [C.c_int] + [C.c_int32] * 8 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 5),
     ("biogpt_hip_fchain_device", C.c_int, [C.c_int] + [C.c_int32] * 6 + [_P] * 8 + [C.c_int32] * 3 + [_P] * 5),
     ("biogpt_hip_fchain_bench", C.c_int, [C.c_int] + [C.c_int32] * 7 + [_P]),
     ("biogpt_hip_assoc_device", C.c_int, [C.c_int] + [C.c_int32] * 9 + [_P] * 17),
@@ -1222,6 +1226,42 @@ def wide_chain_device(epi, wtype, M, K, N, w_rows, aq_q, aq_d, aq_s, bias=None, 
     rc = lib().biogpt_hip_wide_chain_device(int(device), WIDE_EPIS[epi], int(wtype), int(M), int(K), int(N), ptr(w_rows, np.uint8), ptr(aq_q, np.int8),
                                             ptr(aq_d, np.float32), ptr(aq_s, np.uint32), ptr(bias, np.float32), ptr(resid, np.float32), ptr(dev_state, np.int32),
                                             ptr(seq_states, np.int32), int(col_mode), int(P), n_slots, o("k"), o("v"), o("out"), launched.ctypes.data)
+    if rc != 0:
+        raise BiogptError(_err())
+    res["launched"] = launched
+    return res
+
+
+def wcols_device(epi, wtype, M, K, N, w_rows=None, aq_q=None, aq_d=None, aq_s=None, bias=None, resid=None, dev_state=None, seq_states=None, col_mode=0, P=0,
+                 k_slots=None, v_slots=None, nw=0, reps=0, which="cols", device=0):
+    """One stand-alone launch of the wide column layer's linear stage on N <= 16 columns (biogpt_hip_wcols_device): wide_chain_device's arguments and outputs.
+    nw: 0 the launch rule's waves, 4 or 8 forced.  "launched": waves, threads, grid, LDS bytes, rounds, cols, ldo, 0.  Without w_rows only the geometry is
+    reported (no GPU).  reps > 0 adds "us": microseconds of that many timed launches, of the layer's kernel (which "cols") or of matmul_wide_kernel at the same
+    site ("wide").  Raises BiogptError on a refusal."""
+    cols, ldo = ((N + 15) & ~15) + 1, ((M + 127) & ~127) + 16
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    res = {} if w_rows is None else {"out": np.zeros((cols, K if epi == "QKV" else ldo), np.float32)}
+    n_slots = 0
+    if epi == "QKV" and w_rows is not None:
+        res["k"], res["v"] = np.array(k_slots, dtype=np.float32, order="C"), np.array(v_slots, dtype=np.float32, order="C")
+        n_slots = res["k"].shape[0]
+        assert res["k"].shape == res["v"].shape == (n_slots, K // 64, P, 64)
+    if reps:
+        res["us"] = np.zeros(int(reps), np.float32)
+    launched = np.zeros(8, np.int32)
+    o = lambda name: res[name].ctypes.data if name in res else None
+    rc = lib().biogpt_hip_wcols_device(int(device), WIDE_EPIS[epi], int(wtype), int(M), int(K), int(N), int(nw), int(reps), {"cols": 0, "wide": 1}[which],
+                                       ptr(w_rows, np.uint8), ptr(aq_q, np.int8), ptr(aq_d, np.float32), ptr(aq_s, np.uint32), ptr(bias, np.float32),
+                                       ptr(resid, np.float32), ptr(dev_state, np.int32), ptr(seq_states, np.int32), int(col_mode), int(P), n_slots, o("k"), o("v"),
+                                       o("out"), launched.ctypes.data, o("us"))
     if rc != 0:
         raise BiogptError(_err())
     res["launched"] = launched
@@ -1825,14 +1865,15 @@ class BiogptModel:
 
     # -- biogpt_model_load (biogpt.h:128-132) --
     @classmethod
-    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None, assoc_chain=None, wide_decode=None, wide_chunk=None, wide_pass=None, long_context=None):
+    def load(cls, fname, device=0, verbosity=0, arena=None, arena_bytes=0, float_chain=False, assoc=None, assoc_chain=None, wide_decode=None, wide_chunk=None, wide_pass=None, long_context=None, wide_cols=None):
         """float_chain=True: switch the float chain on behind the load (float_chain(); an F32 / F16 file with head size 64 only -- anything else raises).
         assoc="scalar" | "simd": set the association behind the load (set_assoc(); None: the default, scalar unless BIOGPT_HIP_ASSOC=1).
         assoc_chain=True | False: set the SIMD chain's switch behind the load (set_assoc_chain(); None: the default, off unless BIOGPT_HIP_ASSOC_CHAIN=1).
         wide_decode=True | False: set the wide decode layer's switch behind the load (set_wide_decode(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_DECODE=0).
         wide_chunk=True | False: set the wide chunk layer's switch behind the load (set_wide_chunk(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_CHUNK=0).
         wide_pass=True | False: set the wide pass layer's switch behind the load (set_wide_pass(); None: the default, on for the files it serves unless BIOGPT_HIP_WIDE_PASS=0).
-        long_context=True | False: set the long-context attention's switch behind the load (set_long_context(); None: the default, off unless BIOGPT_HIP_LONG_CONTEXT=1)."""
+        long_context=True | False: set the long-context attention's switch behind the load (set_long_context(); None: the default, off unless BIOGPT_HIP_LONG_CONTEXT=1).
+        wide_cols=True | False: set the wide column layer's switch behind the load (set_wide_cols(); None: the default, off unless BIOGPT_HIP_WIDE_COLS=1)."""
         if arena is None:
             m = cls(lib().biogpt_hip_load(os.fsencode(fname), device, verbosity))
         else:
@@ -1852,6 +1893,8 @@ class BiogptModel:
                 m.set_wide_pass(wide_pass)
             if long_context is not None:
                 m.set_long_context(long_context)
+            if wide_cols is not None:
+                m.set_wide_cols(wide_cols)
         except BiogptError:
             m.close()
             raise
@@ -2685,6 +2728,28 @@ class BiogptModel:
         """Launches of the wide pass layer enqueued (biogpt_hip_wide_pass_launches): seven per layer and pass of 9 or more tokens, two more per pass that wants
         every row; 0 while the switch is off."""
         return int(lib().biogpt_hip_wide_pass_launches(self._h))
+
+    def set_wide_cols(self, on=True):
+        """The wide column layer's switch (biogpt_hip_wide_cols): on, passes over column states of at most 16 columns (the decode steps of generate_greedy_batch,
+        generate_sample, generate_beam / generate_beam_batch and generate_queue at 1 .. 16 sequences) of a block-quantized file that is not BioGPT-base launch
+        their linear stages on csrc/kernels_wcols.hip.h -- the same bits as off.  Returns True where the file is served, False where it is not (nothing changed;
+        biogpt_hip_last_error then reads "not served: ...").  Raises BiogptError on a bad call."""
+        rc = lib().biogpt_hip_wide_cols(self._h, 1 if on else 0)
+        if rc < 0:
+            raise BiogptError(_err())
+        return rc == 0
+
+    @property
+    def wide_cols(self):
+        """Whether the wide column layer's switch is on (biogpt_hip_get_wide_cols)."""
+        k = int(lib().biogpt_hip_get_wide_cols(self._h))
+        if k < 0:
+            raise BiogptError(_err())
+        return k == 1
+
+    def wide_cols_launches(self):
+        """Linear-stage launches of the wide column layer enqueued or captured (biogpt_hip_wide_cols_launches); 0 while the switch is off."""
+        return int(lib().biogpt_hip_wide_cols_launches(self._h))
 
     def set_long_context(self, on=True):
         """The long-context attention's switch (biogpt_hip_long_context): on, evals of the context's own columns of a block-quantized file that is not BioGPT-base

@@ -210,7 +210,7 @@ int env_int(const char *name, int dflt) {
 // biogpt_hip_refresh_options): no getenv on any launch path.
 struct EngineOptions {
     int dbg, prompt_cols, no_graph, causal, no_fused_decode, xpipe, xpipe_fault, xpipe_multi, xpipe_dual, xpipe_as_res, proc_lock, graph_contended, fault_stale, xcols,
-        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain, wide_decode, wide_chunk, wide_pass, long_context, long_runs;
+        resident, resident_us, res_dbg, res_spec, no_fdec, lm_stream, hop_place, verbose, topk_blocks, fpipe, fpipe_stamps, fpipe_lead, fpipe_fault, prefix_attn, run_attn, float_chain, assoc, assoc_chain, wide_decode, wide_chunk, wide_pass, wide_cols, long_context, long_runs;
     void load() {
         auto get = [](const char *name, int dflt) { return env_int(name, dflt); };
         no_fdec = get("BIOGPT_HIP_NO_FDEC", 0);             // 1: float-weight decode mat-vecs on the generic kernel (A/B arm of kernels_fdecode.hip.h)
@@ -246,6 +246,7 @@ struct EngineOptions {
         wide_decode = get("BIOGPT_HIP_WIDE_DECODE", 1);          // 1 (the default: measured faster at every key count): a new context of a file the wide decode layer serves starts with it switched on; 0: off (biogpt_hip_wide_decode; kernels_wdecode.hip.h)
         wide_chunk = get("BIOGPT_HIP_WIDE_CHUNK", 1);            // 1 (the default: measured faster at every chunk size and key count): a new context of a file the wide chunk layer serves starts with it switched on; 0: off (biogpt_hip_wide_chunk; kernels_wchunk.hip.h)
         wide_pass = get("BIOGPT_HIP_WIDE_PASS", 1);              // 1 (the default: DESIGN 4.4): a new context of a file the wide pass layer serves starts with it switched on; 0: off (biogpt_hip_wide_pass; kernels_wpass.hip.h)
+        wide_cols = get("BIOGPT_HIP_WIDE_COLS", 0);              // 0 (the default; DESIGN 4.4 has the measurements and why it ships off): off; 1: a new context of a wide file starts with the wide column layer switched on (biogpt_hip_wide_cols; kernels_wcols.hip.h)
         long_context = get("BIOGPT_HIP_LONG_CONTEXT", 0);        // 0 (the default): off; 1: a new context of a wide file starts with the long-context attention switched on (biogpt_hip_long_context; kernels_attn_long.hip.h)
         long_runs = get("BIOGPT_HIP_LONG_RUNS", -1);              // packed passes of a wide file over column states beyond 1024 keys: -1 attn_long_runs_kernel by the form rule (LONG_RUNS_MIN_AVG_COLS), 0 never (attn_long_seq_kernel), 1 wherever the device's LDS holds it (A/B arms)
         assoc = get("BIOGPT_HIP_ASSOC", 0);                        // 1: a new context of a file the SIMD association serves starts in it (biogpt_hip_assoc; kernels_assoc.hip.h)
@@ -406,6 +407,9 @@ struct biogpt_hip_ctx {
     int64_t wchunk_launches = 0;           // stage and producer launches of the wide chunk layer enqueued (biogpt_hip_wide_chunk_launches)
     bool wide_pass = false;                // the wide pass layer is switched on (biogpt_hip_wide_pass): passes of 9 or more of the context's own columns run on kernels_wpass.hip.h
     int wpass_max_cols = -1;               // the most columns of such a pass: n_positions where the layer's geometry holds the file's five matrices within the device's LDS, else 0 (-1: not asked yet, enqueue_forward asks)
+    bool wide_cols = false;                // the wide column layer is switched on (biogpt_hip_wide_cols): the linear stages of passes of 1 .. 16 column states run on kernels_wcols.hip.h
+    int wcols_ok = -1;                     // 1: the layer's geometry holds the file's five matrices on the context's device; 0: not; -1: not asked yet (enqueue_forward asks)
+    int64_t wcols_launches = 0;            // linear-stage launches of the wide column layer enqueued or captured (biogpt_hip_wide_cols_launches)
     bool long_context = false;             // the long-context attention is switched on (biogpt_hip_long_context): the context's own columns of a wide file at 1025 .. 2048 keys attend on kernels_attn_long.hip.h
     int64_t long_cols_launches = 0;        // launches of attn_long_seq_kernel / attn_long_runs_kernel enqueued (biogpt_hip_long_cols_launches): passes over column states beyond 1024 keys
     const int32_t *long_runs = nullptr;    // the run plan of the packed pass being enqueued, behind its column states on the device (flush_columns); n_long_runs == 0: none
@@ -700,6 +704,26 @@ inline int wchunk_cols_on_device(const biogpt_hip_hparams &hp) {
     for (int n = bgk::WCHUNK_MAX_COLS; n >= bgk::WCHUNK_MIN_COLS; n--)
         if (wchunk_holds_file(hp, n, -1)) return n;
     return 0;
+}
+// the wide column layer (kernels_wcols.hip.h, wcols_tu.hip): the wide chain's linear stage for passes of 1 .. 16 column states.  epi: EPI_QKV, EPI_RESID, EPI_GELU,
+// EPI_LOGITS; nw: 0 the rule, 4 or 8 waves forced; lds_limit as bg_wchunk_geometry's; five / report: waves, threads, grid, LDS bytes, rounds
+extern "C" int bg_wcols_geometry(int epi, int M, int K, int N, int nw, int64_t lds_limit, int32_t *five);
+extern "C" int bg_wcols_launch(int wt, int epi, const void *params, size_t params_bytes, const void *img, size_t img_bytes, int nw, hipStream_t st, int32_t *report);
+constexpr int WCOLS_MAX_COLS = 16;      // (bgk::WCOLS_MAX_COLS of the layer's unit: the pass's single column tile)
+inline bool wcols_holds_file(const biogpt_hip_hparams &hp, int64_t lds_limit) {
+    const int D = hp.d_model, F = hp.d_ff, N = WCOLS_MAX_COLS;
+    return !bg_wcols_geometry(bgk::EPI_QKV, 3 * D, D, N, 0, lds_limit, nullptr) && !bg_wcols_geometry(bgk::EPI_RESID, D, D, N, 0, lds_limit, nullptr) &&
+           !bg_wcols_geometry(bgk::EPI_GELU, F, D, N, 0, lds_limit, nullptr) && !bg_wcols_geometry(bgk::EPI_RESID, D, F, N, 0, lds_limit, nullptr) &&
+           !bg_wcols_geometry(bgk::EPI_LOGITS, hp.n_vocab, D, N, 0, lds_limit, nullptr);
+}
+// why a file cannot have the wide column layer (null: it can): the wide chain's files (what the current device's LDS allows is asked by enqueue_forward)
+inline const char *wide_cols_refusal(const biogpt_hip_hparams &hp) {
+    if (!is_quantized(ftype_to_type(hp.ftype))) return "the weights are not block-quantized";
+    const int kind = chain_kind_of(hp);
+    if (kind == CHAIN_BASE) return "it has BioGPT-base shapes, which have their own many-column chain";
+    if (kind != CHAIN_WIDE) return "the head size is not 64, or d_model is no multiple of 64, or d_ff of 32";
+    if (!wcols_holds_file(hp, 0)) return "one of its matrices is no shape of the layer's kernels";
+    return nullptr;
 }
 // the wide pass layer (kernels_wpass.hip.h, wpass_tu.hip): 9 or more of the context's own columns of a wide file, the linear stages of seven launches per layer on
 // the row-tiled image.  epi: EPI_QKV, EPI_RESID, EPI_GELU_Q8 (fc1), EPI_LOGITS.  lds_limit as bg_wchunk_geometry's; cfg -1: the launch shape by the rule
@@ -1491,6 +1515,7 @@ struct PassLaunch {
     int attn_threads;               // attention workgroup size of the generic kernel
     bool chain, pchain, mfma;       // the single-token fast chain; its many-column form; on the int8 matrix cores
     bool wchain;                    // the wide chain: a pass over column states of a block-quantized file that is not BioGPT-base (kernels_mfma_wide.hip.h)
+    bool wcols;                     // the wide column layer: a wide chain pass of at most 16 columns whose context has it switched on -- its linear stages launch kernels_wcols.hip.h
     bool fchain;                    // the float chain: a pass over column states of an F32 / F16 file whose context has it switched on (kernels_fchain.hip.h)
     bool wdec;                      // the wide decode layer: one token of the context's own column of a wide file whose context has it switched on (kernels_wdecode.hip.h)
     bool wchunk;                    // the wide chunk layer: 2 .. 8 tokens of the context's own columns of a wide file whose context has it switched on (kernels_wchunk.hip.h)
@@ -1526,6 +1551,11 @@ struct PassLaunch {
         if (e != hipSuccess) return e;
         p.aq_q = c->aq_q[slot]; p.aq_d = c->aq_d[slot]; p.aq_s = c->aq_s[slot];
         img = tile_matrix(c, m);
+        if (wcols && p.N <= WCOLS_MAX_COLS) {      // (p.N: the lm_head's columns behind head_from are no more than the pass's)
+            e = (hipError_t)bg_wcols_launch(m.type, epi, &p, sizeof(p), &img, sizeof(img), 0, st, nullptr);
+            if (e == hipSuccess) c->wcols_launches++;
+            return e;
+        }
         e = (hipError_t)bg_wide_launch(m.type, epi, &p, sizeof(p), &img, sizeof(img), st);
         if (e == hipSuccess) c->wide_launches++;
         return e;
@@ -2174,6 +2204,10 @@ bool enqueue_forward(biogpt_hip_ctx *c, const ForwardPass &pass) {
     // (beyond FAST_ATTN_MAX_KEYS, up to the reach of kernels_attn_long_cols.hip.h, it attends on those kernels: long_cols)
     k.wchain = !k.chain && !k.schain && batch && chain_kind_of(hp) == CHAIN_WIDE && t_max <= std::max(FAST_ATTN_MAX_KEYS, std::min(hp.n_positions, LONG_ATTN_MAX_KEYS));
     k.long_cols = k.wchain && t_max > FAST_ATTN_MAX_KEYS;
+    // a wide chain pass of at most 16 columns in all, where the context has the wide column layer switched on and its geometry holds the file's five matrices on
+    // this device: the linear stages on kernels_wcols.hip.h; the producers, the attention and every row kernel stay the chain's
+    if (k.wchain && c->wide_cols && N <= WCOLS_MAX_COLS && c->wcols_ok < 0) c->wcols_ok = wcols_holds_file(hp, -1) ? 1 : 0;
+    k.wcols = k.wchain && c->wide_cols && N <= WCOLS_MAX_COLS && c->wcols_ok == 1;
     // a pass over column states of a float file whose context has the float chain switched on (the context's own columns stay on fdec_kernel / matvec_kernel)
     k.fchain = !k.chain && !k.wchain && batch && chain_kind(c) == CHAIN_FLOAT && t_max <= 1024;
     if (k.fchain && (pass.rows == Rows::Last || pass.rows == Rows::AllGeneric)) BG_FAIL(false, "internal: a float fast chain pass with rows it does not serve");
@@ -2489,6 +2523,7 @@ biogpt_hip_ctx *load_impl(const char *fname, int device, int verbosity, void *ex
     c->wide_decode = c->opt.wide_decode == 1 && wide_decode_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_DECODE)
     c->wide_chunk = c->opt.wide_chunk == 1 && wide_chunk_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_CHUNK)
     c->wide_pass = c->opt.wide_pass == 1 && wide_pass_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_PASS)
+    c->wide_cols = c->opt.wide_cols == 1 && wide_cols_refusal(c->hp) == nullptr;      // (and BIOGPT_HIP_WIDE_COLS)
     c->long_context = c->opt.long_context == 1 && long_context_refusal(c->hp) == nullptr;      // (BIOGPT_HIP_LONG_CONTEXT: off unless asked for)
     c->device = device;
     c->n_tensors = (int)mf.tensors.size();
@@ -2613,6 +2648,7 @@ biogpt_hip_ctx *biogpt_hip_attach(const biogpt_hip_hparams *hp, int device, void
     c->wide_decode = c->opt.wide_decode == 1 && wide_decode_refusal(c->hp) == nullptr;
     c->wide_chunk = c->opt.wide_chunk == 1 && wide_chunk_refusal(c->hp) == nullptr;
     c->wide_pass = c->opt.wide_pass == 1 && wide_pass_refusal(c->hp) == nullptr;
+    c->wide_cols = c->opt.wide_cols == 1 && wide_cols_refusal(c->hp) == nullptr;
     c->long_context = c->opt.long_context == 1 && long_context_refusal(c->hp) == nullptr;
     c->device = device;
     c->pos_rows = (int64_t)hp->n_positions + 2;
@@ -3295,6 +3331,35 @@ int biogpt_hip_get_wide_pass(const biogpt_hip_ctx *ctx) {
     return ctx->wide_pass ? 1 : 0;
 }
 int64_t biogpt_hip_wide_pass_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->wpass_launches : -1; }
+// The wide column layer's switch: the rules of biogpt_hip_wide_decode.  A captured column step holds the linear-stage launches chosen before its capture, so the
+// captured column steps of every mode are dropped.  Off (the default) is the engine without it, launch for launch.
+int biogpt_hip_wide_cols(biogpt_hip_ctx *ctx, int on) {
+    clear_error();
+    if (!ctx) BG_FAIL(-1, "null context");
+    if (on != 0 && on != 1) BG_FAIL(-1, "on must be 0 or 1 (got %d)", on);
+    if (session_refuses(ctx)) return -1;
+    {
+        std::lock_guard<std::mutex> lk(g_xp_mu);
+        if (ctx->xp_in_call) BG_FAIL(-1, "the wide column layer cannot be switched while a call of this context is running");
+    }
+    if (const char *why = wide_cols_refusal(ctx->hp)) {
+        bg::set_error(__func__, "not served: the wide column layer is for block-quantized files with head size 64, d_model a multiple of 64 and d_ff of 32 that are not BioGPT-base: %s (got ftype %d, d_model %d, d_ff %d, %d heads)", why, ctx->hp.ftype, ctx->hp.d_model, ctx->hp.d_ff, ctx->hp.n_head);
+        return 1;
+    }
+    if (ctx->wide_cols == (on == 1)) return 0;
+    if (ctx->ready) {
+        HIP_TRY(-2, hipSetDevice(ctx->device));
+        HIP_TRY(-2, hipStreamSynchronize(ctx->stream));
+    }
+    drop_column_graphs(ctx);
+    ctx->wide_cols = on == 1;
+    return 0;
+}
+int biogpt_hip_get_wide_cols(const biogpt_hip_ctx *ctx) {
+    if (!ctx) BG_FAIL(-1, "null context");
+    return ctx->wide_cols ? 1 : 0;
+}
+int64_t biogpt_hip_wide_cols_launches(const biogpt_hip_ctx *ctx) { return ctx ? ctx->wcols_launches : -1; }
 // The long-context attention's switch: the rules of biogpt_hip_wide_decode (a captured single-token step holds the attention launch of its key bucket, so
 // the captured steps are dropped).  Off (the default) is the engine without it: beyond 1024 keys the generic route.
 int biogpt_hip_long_context(biogpt_hip_ctx *ctx, int on) {

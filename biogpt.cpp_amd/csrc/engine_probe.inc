@@ -1665,6 +1665,64 @@ int biogpt_hip_wide_chain_bench(int device, int32_t which, int32_t wtype, int32_
     return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
 }
 
+// One stand-alone launch of the wide column layer's linear stage (wcols_kernel, kernels_wcols.hip.h) through bg_wcols_launch -- the entry PassLaunch::wide_stage
+// takes for a pass of at most 16 columns -- on biogpt_hip_wide_chain_device's arguments, image, checks and output layout (out WHOLE, preset to 0xff: cols = 17,
+// QKV [cols][K], otherwise [cols][ldo] with ldo = M rounded up to 128, plus 16 guard rows).  1 <= N <= 16.  nw: 0 the launch rule's waves, 4 or 8 forced.
+// launched [8]: waves, threads, grid, LDS bytes, rounds, cols, ldo, 0.  reps > 0: that many timed launches behind the checked one, microseconds into us_out;
+// which 1 (reps > 0 only): the timed launches are matmul_wide_kernel's at the same site, image and columns.  For tools/wide_cols_bench.py.
+int biogpt_hip_wcols_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t nw, int32_t reps, int32_t which, const void *w_rows,
+                            const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid, const int32_t *dev_state,
+                            const int32_t *seq_states, int32_t col_mode, int32_t P, int32_t n_slots, float *k_slots, float *v_slots, float *out, int32_t *launched,
+                            float *us_out) {
+    clear_error();
+    if (epi < bgk::EPI_QKV || epi > bgk::EPI_LOGITS) BG_FAIL(-1, "epi %d is no epilogue of the wide chain (0 QKV, 1 RESID, 2 GELU, 3 LOGITS)", epi);
+    if (wtype != T_Q4_0 && wtype != T_Q4_1 && wtype != T_Q5_0 && wtype != T_Q5_1 && wtype != T_Q8_0) BG_FAIL(-1, "type %d is no block format", wtype);
+    if (reps < 0 || reps > PROBE_MAX_REPS) BG_FAIL(-1, "reps must be in [0, %d]", PROBE_MAX_REPS);
+    if (reps > 0 && !us_out) BG_FAIL(-1, "us_out is NULL");
+    if (which != 0 && !(which == 1 && reps > 0)) BG_FAIL(-1, "which must be 0, or 1 with reps > 0 (the wide chain's kernel, timed)");
+    if (nw != 0 && nw != 4 && nw != 8) BG_FAIL(-1, "nw must be 0 (the rule), 4 or 8 waves (got %d)", nw);
+    if (N < 1 || N > WCOLS_MAX_COLS) BG_FAIL(-1, "N = %d columns: the wide column layer holds 1 .. %d", N, WCOLS_MAX_COLS);
+    if (K < QK || K > (1 << 16) || K % QK != 0) BG_FAIL(-1, "K must be a multiple of %d in [%d, %d]", QK, QK, 1 << 16);
+    if (M < 1 || M > (1 << 20)) BG_FAIL(-1, "M must be in [1, %d]", 1 << 20);
+    int32_t five[5] = {0, 0, 0, 0, 0};
+    if (bg_wcols_geometry(epi, M, K, N, nw, 0, five))
+        BG_FAIL(-1, "the wide column layer does not hold a %d x %d matrix at site %d (16 | M but at the logits site, q/k/v 3 K x K with 64 | K)", M, K, epi);
+    const int cols = ((N + 15) & ~15) + 1, ldo = ((M + 127) & ~127) + 16;
+    if (!w_rows && !aq_q && !aq_d && !aq_s && !out) {      // the geometry alone: no HIP call
+        report_launch(launched, {five[0], five[1], five[2], five[3], five[4], cols, ldo});
+        return 0;
+    }
+    if (!w_rows || !aq_q || !aq_d || !aq_s || !out) BG_FAIL(-1, "w_rows, aq_q, aq_d, aq_s or out is NULL");
+    if (epi != bgk::EPI_LOGITS && !bias) BG_FAIL(-1, "bias is NULL");
+    if (epi == bgk::EPI_RESID && !resid) BG_FAIL(-1, "resid is NULL");
+    const bool qkv = epi == bgk::EPI_QKV;
+    if (!check_probe_columns(__func__, qkv, N, dev_state, seq_states, col_mode, P, n_slots, k_slots, v_slots)) return -1;
+    HIP_TRY(-2, hipSetDevice(device));
+    if (bg_wcols_geometry(epi, M, K, N, nw, -1, five)) BG_FAIL(-1, "the wide column layer's %d x %d site %d asks for more LDS than a workgroup of this device gets", M, K, epi);
+    const size_t bpr = (size_t)K / QK, kv_b = qkv ? (size_t)(K / 64) * P * 64 * 4 * (size_t)n_slots : 0;
+    ProbeImage im;      // [weights | image | the Q8 columns | the stage's parts | out], guard column and rows in the output
+    const BlockRows wr = upload_block_rows(im, wtype, w_rows, M, K, true);
+    const ProbePart o_aq = im.in(aq_q, (size_t)N * K), o_ad = im.in(aq_d, (size_t)N * bpr * 4), o_as = im.in(aq_s, (size_t)N * bpr * 4);
+    const StageParts sp = stage_parts(im, bias, (size_t)M * 4, epi == bgk::EPI_RESID ? resid : nullptr, (size_t)N * M * 4, dev_state, seq_states, N, k_slots, v_slots, kv_b);
+    const ProbePart o_out = im.out((size_t)cols * (qkv ? K : ldo) * 4);
+    if (!im.upload()) return -2;
+    bgk::MatvecParams p = stage_params(im, wr.W(im), sp, K, P, N, qkv, col_mode, o_out, ldo, M);
+    p.aq_q = im.at<const int8_t>(o_aq); p.aq_d = im.at<const float>(o_ad); p.aq_s = im.at<const uint32_t>(o_as);
+    const bgk::DevMatrix img = wr.image(im);
+    HIP_TRY(-2, wr.retile(im));
+    auto launch = [&]() -> hipError_t { return (hipError_t)bg_wcols_launch(wtype, epi, &p, sizeof(p), &img, sizeof(img), nw, 0, five); };
+    HIP_TRY(-2, launch());
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    report_launch(launched, {five[0], five[1], five[2], five[3], five[4], cols, ldo});
+    if (!im.read(o_out, out) || !im.read(sp.k, k_slots) || !im.read(sp.v, v_slots)) return -2;
+    if (which == 0) return time_launches(reps, nullptr, launch, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+    auto launch_wide = [&]() -> hipError_t { return (hipError_t)bg_wide_launch(wtype, epi, &p, sizeof(p), &img, sizeof(img), 0); };
+    HIP_TRY(-2, launch_wide());      // (the same values into the same places)
+    HIP_TRY(-2, hipDeviceSynchronize());
+    return time_launches(reps, nullptr, launch_wide, [&](int i, float ms) { us_out[i] = ms * 1e3f; });
+}
+
 // One stand-alone launch of the float chain's linear stage (fchain_kernel, kernels_fchain.hip.h) over caller-supplied weights and f32 columns, through
 // bg_fchain_launch (and bg_fchain_ln in front of it when ln_w is given) -- the entries of PassLaunch::float_stage.  epi: 0 QKV (M == 3 K, 64 | K: K is d_model,
 // heads of 64), 1 RESID, 2 GELU, 3 LOGITS; any M.  wtype 0: w_rows is M rows of K f32; 1: of K f16 (bits).  x [N][K] f32.  cfg: 0 .. 2 a tile shape, -1 the

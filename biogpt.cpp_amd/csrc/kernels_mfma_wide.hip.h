@@ -35,6 +35,48 @@ struct WideLds {
     static constexpr int BYTES = OFF_S + (Q81 ? 16 * SP * 4 : 0);
 };
 
+// The epilogue of one lane's outputs -- rows orow .. orow + 3 of column col < N, block sums in acc -- at the wide chain's four sites: the one copy, called by
+// matmul_wide_kernel below and by wcols_kernel (kernels_wcols.hip.h).
+template <int EPI>
+__device__ __forceinline__ void wide_epilogue(const MatvecParams &p, const float (&acc)[4], int col, int orow) {
+    static_assert(EPI == EPI_QKV || EPI == EPI_RESID || EPI == EPI_GELU || EPI == EPI_LOGITS, "the wide chain's four sites");
+    const int K = p.W.K, M = p.W.M;
+    if (EPI == EPI_LOGITS) {                                 // n_vocab need not be a multiple of 4: row by row, rows >= M are never stored
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+            if (orow + r < M) p.out[(size_t)col * p.ldo + orow + r] = acc[r];
+        return;
+    }
+    if (orow >= M) return;                                   // (16 | M at the three layer sites)
+    const float4 eb = *reinterpret_cast<const float4 *>(p.bias + orow);
+    if (EPI == EPI_QKV) {
+        const int e_npast = p.seq ? p.seq[col].n_past : p.st->n_past + col;
+        const int e_seq = (p.seq && p.col_mode) ? p.seq[col].seq_id : col;
+        float4 v;
+        v.x = __fadd_rn(eb.x, acc[0]); v.y = __fadd_rn(eb.y, acc[1]); v.z = __fadd_rn(eb.z, acc[2]); v.w = __fadd_rn(eb.w, acc[3]);
+        const int which = orow / K, rr = orow - which * K;   // d_model == K for the q/k/v projection
+        if (which == 0) {
+            v.x = __fmul_rn(v.x, p.q_scale); v.y = __fmul_rn(v.y, p.q_scale); v.z = __fmul_rn(v.z, p.q_scale); v.w = __fmul_rn(v.w, p.q_scale);
+            *reinterpret_cast<float4 *>(p.q_out + (size_t)col * K + rr) = v;
+        } else {
+            float *cache = ((which == 1) ? p.kcache : p.vcache) + (p.seq ? (size_t)e_seq * p.kv_seq_stride : 0);
+            const int hh = rr >> p.dk_log2, dd = rr & (p.dk - 1);                                       // head-major cache: [H][P][dk]; 4 | dk
+            *reinterpret_cast<float4 *>(cache + (((size_t)hh * p.P + e_npast) << p.dk_log2) + dd) = v;
+        }
+    } else if (EPI == EPI_RESID) {
+        const float4 er = *reinterpret_cast<const float4 *>(p.resid + (size_t)col * p.ldr + orow);
+        float4 v;
+        v.x = __fadd_rn(__fadd_rn(acc[0], eb.x), er.x); v.y = __fadd_rn(__fadd_rn(acc[1], eb.y), er.y);
+        v.z = __fadd_rn(__fadd_rn(acc[2], eb.z), er.z); v.w = __fadd_rn(__fadd_rn(acc[3], eb.w), er.w);
+        *reinterpret_cast<float4 *>(p.out + (size_t)col * p.ldo + orow) = v;
+    } else {                                                 // EPI_GELU
+        float4 v;
+        v.x = h2f(p.gelu_tab[f2h(__fadd_rn(eb.x, acc[0]))]); v.y = h2f(p.gelu_tab[f2h(__fadd_rn(eb.y, acc[1]))]);
+        v.z = h2f(p.gelu_tab[f2h(__fadd_rn(eb.z, acc[2]))]); v.w = h2f(p.gelu_tab[f2h(__fadd_rn(eb.w, acc[3]))]);
+        *reinterpret_cast<float4 *>(p.out + (size_t)col * p.ldo + orow) = v;
+    }
+}
+
 // EPI: EPI_QKV (column states: seq / col_mode / kv_seq_stride, head-major cache), EPI_RESID, EPI_GELU (f32 rows through the fp16 GELU table), EPI_LOGITS
 template <int WT, int EPI>
 __global__ __launch_bounds__(256) void matmul_wide_kernel(const MatvecParams p, const DevMatrix img) {
@@ -112,40 +154,7 @@ __global__ __launch_bounds__(256) void matmul_wide_kernel(const MatvecParams p, 
 
     const int col = col0 + li, orow = tile * 16 + 4 * g;     // this lane's outputs: rows orow .. orow + 3 of column col
     if (!tile_ok || col >= p.N) return;
-    if (EPI == EPI_LOGITS) {                                 // n_vocab need not be a multiple of 4: row by row, rows >= M are never stored
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            if (orow + r < M) p.out[(size_t)col * p.ldo + orow + r] = acc[r];
-        return;
-    }
-    if (orow >= M) return;                                   // (16 | M at the three layer sites)
-    const float4 eb = *reinterpret_cast<const float4 *>(p.bias + orow);
-    if (EPI == EPI_QKV) {
-        const int e_npast = p.seq ? p.seq[col].n_past : p.st->n_past + col;
-        const int e_seq = (p.seq && p.col_mode) ? p.seq[col].seq_id : col;
-        float4 v;
-        v.x = __fadd_rn(eb.x, acc[0]); v.y = __fadd_rn(eb.y, acc[1]); v.z = __fadd_rn(eb.z, acc[2]); v.w = __fadd_rn(eb.w, acc[3]);
-        const int which = orow / K, rr = orow - which * K;   // d_model == K for the q/k/v projection
-        if (which == 0) {
-            v.x = __fmul_rn(v.x, p.q_scale); v.y = __fmul_rn(v.y, p.q_scale); v.z = __fmul_rn(v.z, p.q_scale); v.w = __fmul_rn(v.w, p.q_scale);
-            *reinterpret_cast<float4 *>(p.q_out + (size_t)col * K + rr) = v;
-        } else {
-            float *cache = ((which == 1) ? p.kcache : p.vcache) + (p.seq ? (size_t)e_seq * p.kv_seq_stride : 0);
-            const int hh = rr >> p.dk_log2, dd = rr & (p.dk - 1);                                       // head-major cache: [H][P][dk]; 4 | dk
-            *reinterpret_cast<float4 *>(cache + (((size_t)hh * p.P + e_npast) << p.dk_log2) + dd) = v;
-        }
-    } else if (EPI == EPI_RESID) {
-        const float4 er = *reinterpret_cast<const float4 *>(p.resid + (size_t)col * p.ldr + orow);
-        float4 v;
-        v.x = __fadd_rn(__fadd_rn(acc[0], eb.x), er.x); v.y = __fadd_rn(__fadd_rn(acc[1], eb.y), er.y);
-        v.z = __fadd_rn(__fadd_rn(acc[2], eb.z), er.z); v.w = __fadd_rn(__fadd_rn(acc[3], eb.w), er.w);
-        *reinterpret_cast<float4 *>(p.out + (size_t)col * p.ldo + orow) = v;
-    } else {                                                 // EPI_GELU
-        float4 v;
-        v.x = h2f(p.gelu_tab[f2h(__fadd_rn(eb.x, acc[0]))]); v.y = h2f(p.gelu_tab[f2h(__fadd_rn(eb.y, acc[1]))]);
-        v.z = h2f(p.gelu_tab[f2h(__fadd_rn(eb.z, acc[2]))]); v.w = h2f(p.gelu_tab[f2h(__fadd_rn(eb.w, acc[3]))]);
-        *reinterpret_cast<float4 *>(p.out + (size_t)col * p.ldo + orow) = v;
-    }
+    wide_epilogue<EPI>(p, acc, col, orow);
 }
 
 // quantize_row_q8_0 / _q8_1 of one 4-element chunk whose 32-element block is 8 consecutive lanes (matvec_kernel's prologue): Q8_0 keeps the

@@ -269,6 +269,21 @@ int biogpt_hip_get_wide_pass(const biogpt_hip_ctx *ctx);
 /* Launches of the wide pass layer enqueued: seven per layer and pass (two LayerNorm + Q8 producers, q/k/v, attention, out_proj, fc1, fc2), and two per pass that
  * wants every row (LayerNorm + Q8 of the rows, the lm_head); 0 for ever while the switch is off.  -1: ctx is NULL. */
 int64_t biogpt_hip_wide_pass_launches(const biogpt_hip_ctx *ctx);
+/* The wide column layer's switch, per context (initial value: BIOGPT_HIP_WIDE_COLS=0/1, default 0).  It serves the files of the wide chain
+ * (biogpt_hip_chain_kind 2).  on 1: a pass over column states of at most 16 columns in all -- the decode steps of biogpt_hip_generate_greedy_batch,
+ * generate_sample, generate_beam / generate_beam_batch and generate_queue at 1 .. 16 sequences, and a packed prompt pass that small -- launches its linear
+ * stages (q/k/v, out_proj, fc1, fc2, the lm_head) on csrc/kernels_wcols.hip.h: a workgroup per 16-row tile, the K axis split over 4 or 8 waves, the block terms
+ * summed in block order through LDS.  The Q8 producers, the attention launches, the samplers and every row kernel are the wide chain's; ids, logits, scores and
+ * K / V rows are bit for bit those of off.  Passes of 17 or more columns, the context's own columns, BioGPT-base files, float files and a context in the SIMD
+ * association keep the launches they have; off is the engine without the layer, launch for launch.  Legality and return values are those of
+ * biogpt_hip_wide_decode (the captured column steps of every mode are dropped): not while a queue session is open or a call of the context is running; 1 with
+ * "not served: ..." in biogpt_hip_last_error on a file the layer does not serve. */
+int biogpt_hip_wide_cols(biogpt_hip_ctx *ctx, int on);
+/* The wide column layer's switch: 0 off, 1 on.  -1: ctx is NULL. */
+int biogpt_hip_get_wide_cols(const biogpt_hip_ctx *ctx);
+/* Linear-stage launches of the wide column layer enqueued or captured (four per layer and pass, one more for the lm_head; the fc1 stage writes f32 GELU rows and
+ * the wide chain's Q8 producer behind it is not counted); 0 for ever while the switch is off.  -1: ctx is NULL. */
+int64_t biogpt_hip_wide_cols_launches(const biogpt_hip_ctx *ctx);
 /* The long-context attention's switch, per context (initial value: BIOGPT_HIP_LONG_CONTEXT=0/1, default 0).  It serves the files of the wide decode layer.
  * on 1: an eval of the context's own columns whose furthest visible key lies in 1025 .. min(n_positions, 2048) attends on csrc/kernels_attn_long.hip.h -- one
  * workgroup per (head, column) below 80 columns, sixteen columns per workgroup from 80 on -- which writes out_proj's Q8 blocks beside the f32 rows, so the wide
@@ -547,6 +562,16 @@ int biogpt_hip_wide_chain_device(int device, int32_t epi, int32_t wtype, int32_t
  * device events around launch i alone.  which 0: the wide chain's kernel with the residual epilogue at M rows (16 | M) of K values (32 | K) and N <= 512 columns;
  * which 1: the BioGPT-base matrix-core kernel at out_proj (M 1024, K 1024) or fc2 (M 1024, K 4096).  For tools/wide_chain_bench.py. */
 int biogpt_hip_wide_chain_bench(int device, int32_t which, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t reps, float *us_out);
+/* One stand-alone launch of the wide column layer's linear stage (wcols_kernel, csrc/kernels_wcols.hip.h) through the engine's own launch entry, on the arguments,
+ * the image, the checks and the output layout of biogpt_hip_wide_chain_device; 1 <= N <= 16.  nw: 0 the launch rule's waves (8 where a row has more than 32
+ * blocks, else 4), 4 or 8 forced.  launched [8]: waves, threads, grid, LDS bytes, rounds, cols, ldo, 0.  With w_rows, aq_q, aq_d, aq_s and out all NULL only the
+ * geometry is reported (no HIP call).  reps > 0: that many timed launches behind the checked one, microseconds into us_out [reps]; which 1 (reps > 0 only): the
+ * timed launches are matmul_wide_kernel's at the same site (tools/wide_cols_bench.py).  Returns 0; -1 on a bad argument or a shape the layer's geometry does not
+ * hold, before any HIP call; -2 on a HIP error. */
+int biogpt_hip_wcols_device(int device, int32_t epi, int32_t wtype, int32_t M, int32_t K, int32_t N, int32_t nw, int32_t reps, int32_t which, const void *w_rows,
+                            const int8_t *aq_q, const float *aq_d, const uint32_t *aq_s, const float *bias, const float *resid, const int32_t *dev_state,
+                            const int32_t *seq_states, int32_t col_mode, int32_t P, int32_t n_slots, float *k_slots, float *v_slots, float *out, int32_t *launched,
+                            float *us_out);
 /* One stand-alone launch of the float chain's linear stage over caller-supplied weights and f32 columns, through the launch code of the engine's own passes.
  * epi: 0 QKV (M == 3 K, 64 | K: K is d_model, heads of 64), 1 RESID, 2 GELU (f32 rows through the fp16 table), 3 LOGITS; K a multiple of 32; any M.  wtype 0:
  * w_rows is M rows of K f32, 1: of K f16 (bits); x [N][K] f32; ln_w / ln_b [K] (both or neither): the LayerNorm producer runs in front of the stage; cfg 0 .. 2: a
