@@ -124,7 +124,6 @@ __device__ __forceinline__ void xl_run(const XpParams &p, unsigned char *smem, c
     float *const s_hd = reinterpret_cast<float *>(smem + XP_S_HD);
     uint32_t *const s_hs = reinterpret_cast<uint32_t *>(smem + XP_S_HS);
     float *const s_part = reinterpret_cast<float *>(smem + XP_S_PART);
-    float *const s_g = reinterpret_cast<float *>(smem + XP_S_G);
     float *const s_ln = reinterpret_cast<float *>(smem + XP_S_LN);
     float *const s_bias = reinterpret_cast<float *>(smem + XP_S_BIAS);
     float *const s_cur = reinterpret_cast<float *>(smem + XP_S_CUR);
@@ -715,15 +714,15 @@ __device__ __forceinline__ void xl_run(const XpParams &p, unsigned char *smem, c
                         ax[0] = a.x; ax[1] = a.y; ax[2] = a.z; ax[3] = a.w; ax[4] = b.x; ax[5] = b.y; ax[6] = b.z; ax[7] = b.w;
                         const float axd = s_xd[sub];
                         const uint32_t axs = s_xs[sub];
-                        float *const part = s_part + wave * 2 * FS * DEC_PS;
+                        // (as stage D of kernels_xpipe.hip.h: row jr's block terms at s_part + jr * DEC_PS, thread t < 128 sums row t behind the barrier)
 #pragma unroll
-                        for (int s = 0; s < FS; s++) part[(s * 2 + rsub) * DEC_PS + sub] = xp_dot<WT, true>(w1[s], ax, axd, __uint_as_float(axs), (int)axs);
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                        if (lane < 2 * FS) {
-                            const int jr = (lane >> 1) * 2 * NW + wave * 2 + (lane & 1);
-                            const float v = __fadd_rn(s_bias[224 + jr], sum32_in_order(part + lane * DEC_PS));
+                        for (int s = 0; s < FS; s++) s_part[(s * 2 * NW + wave * 2 + rsub) * DEC_PS + sub] = xp_dot<WT, true>(w1[s], ax, axd, __uint_as_float(axs), (int)axs);
+                    }
+                    __syncthreads();
+                    if (tid < 128) {
+                        float g;
+                        {
+                            const float v = __fadd_rn(s_bias[224 + tid], sum32_in_order(s_part + tid * DEC_PS));
                             const uint32_t ix = f2h(v), neg = ix - 0x8000u;               // ggml_gelu: fp16 table
                             uint16_t g16;
                             if (ix < (uint32_t)p.gelu_p) g16 = s_gelu[ix];
@@ -731,14 +730,11 @@ __device__ __forceinline__ void xl_run(const XpParams &p, unsigned char *smem, c
                             else if (neg < (uint32_t)p.gelu_n) g16 = s_gelu[p.gelu_p + neg];
                             else if (neg < 0x7C00u && p.gelu_n > 0) g16 = (uint16_t)p.gelu_z;
                             else g16 = p.gelu_tab[ix];                                     // -inf, NaN (or no slice in LDS)
-                            s_g[jr] = h2f(g16);
+                            g = h2f(g16);
                         }
-                    }
-                    __syncthreads();
-                    XL_WALL2(11);
-                    if (tid < 128) {
+                        XL_WALL2(11);
                         int8_t q8; float d8; uint32_t s8;
-                        q8_block32(s_g[tid], TI::q81, q8, d8, s8, TI::q81);
+                        q8_block32(g, TI::q81, q8, d8, s8, TI::q81);
                         const uint32_t packed = xp_pack4(q8);
                         const int blk = slot * 4 + (tid >> 5);
                         if ((tid & 3) == 0) xp_put_local(G + XP_G_H + slot * 32 + (tid >> 2), epoch, packed);

@@ -141,9 +141,13 @@ struct XpParams {
 // the token's tail (round 4, tools/tail_timeline.py): bank tk % 8 of 16 stamps at wall[4096 ..]: 0 the last layer's output published (token tk), 1 .. 4 lm_head
 // workgroup 0: that output seen / LayerNorm done / rows done / partials published, 5 .. 6 XCD 0's workgroup 0: token tk sampled / its embedding done
 #define XP_TAIL(tok, k) do { if (p.wall && tid == 0) p.wall[4096 + ((tok) & 7) * 16 + (k)] = wall_clock64(); } while (0)
+// inside a stage (tools/row_sum_split.py): [n_layer][8] stamps at wall[2048 ..]: "block terms in LDS, the in-order sums start" of 0 q/k/v (own rows of the head),
+// 1 fc1, 2 fc2
+#define XP_WALLX(k) do { if (p.wall && tid == 0 && (slot & 15) == 0) p.wall[2048 + L * 8 + (k)] = wall_clock64(); } while (0)
 #else
 #define XP_WALL(k) do {} while (0)
 #define XP_TAIL(tok, k) do {} while (0)
+#define XP_WALLX(k) do {} while (0)
 #endif
 
 // Parameters that are read once per token (the sampler's and the lm_head pass's buffers, everything of the resident form) are NOT held in scalar registers over the launch:
@@ -926,6 +930,7 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                XP_WALLX(0);
                 if (lane < 2 * QS) {
                     const int jj = (lane >> 1) * 2 * NW + wave * 2 + (lane & 1);
                     float v = __fadd_rn(s_bias[jj], sum32_in_order(part + lane * DEC_PS));
@@ -1308,34 +1313,52 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
             ax[0] = a.x; ax[1] = a.y; ax[2] = a.z; ax[3] = a.w; ax[4] = b.x; ax[5] = b.y; ax[6] = b.z; ax[7] = b.w;
             const float axd = s_xd[sub];
             const uint32_t axs = s_xs[sub];
-            float *const part = s_part + wave * 2 * FS * DEC_PS;
-#pragma unroll
-            for (int s = 0; s < FS; s++) part[(s * 2 + rsub) * DEC_PS + sub] = xp_dot<WT, EXPAND>(w1[s], ax, axd, __uint_as_float(axs), (int)axs);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (lane < 2 * FS) {
-                const int jr = (lane >> 1) * 2 * NW + wave * 2 + (lane & 1);
-                const float v = __fadd_rn(s_bias[224 + jr], sum32_in_order(part + lane * DEC_PS));
-                const uint32_t ix = f2h(v), neg = ix - 0x8000u;               // ggml_gelu: fp16 table
+            // the GELU of a finished fc1 row: ggml_gelu's fp16 table, its busy slice in LDS
+            const auto gelu_of = [&](const float v) __attribute__((always_inline)) -> float {
+                const uint32_t ix = f2h(v), neg = ix - 0x8000u;
                 uint16_t g16;
                 if (ix < (uint32_t)p.gelu_p) g16 = s_gelu[ix];
                 else if (ix <= 0x7C00u) g16 = (p.gelu_p > 0) ? (uint16_t)ix : p.gelu_tab[ix];
                 else if (neg < (uint32_t)p.gelu_n) g16 = s_gelu[p.gelu_p + neg];
                 else if (neg < 0x7C00u && p.gelu_n > 0) g16 = (uint16_t)p.gelu_z;
                 else g16 = p.gelu_tab[ix];                                     // -inf, NaN (or no slice in LDS)
-                s_g[jr] = h2f(g16);
+                return h2f(g16);
+            };
+            if constexpr (!RES) {
+                // the block terms of row jr at s_part + jr * DEC_PS: behind the barrier thread t < 128 sums row t in order and keeps the GELU value in its register
+                // for the Q8 step -- the 32 dependent additions are issued by two full waves instead of by 16 lanes of every wave, and the values make no round
+                // trip through LDS (profiles/row_sums_one_wave_ab.txt: the stage 0.08 - 0.19 us shorter)
+#pragma unroll
+                for (int s = 0; s < FS; s++) s_part[(s * 2 * NW + wave * 2 + rsub) * DEC_PS + sub] = xp_dot<WT, EXPAND>(w1[s], ax, axd, __uint_as_float(axs), (int)axs);
+            } else {
+                // the resident kernels keep the sums in front of the barrier, on 2 * FS lanes of every wave: the form above costs the resident 256-key kernel 7 more
+                // spilled scalar registers (the budget is 4)
+                float *const part = s_part + wave * 2 * FS * DEC_PS;
+#pragma unroll
+                for (int s = 0; s < FS; s++) part[(s * 2 + rsub) * DEC_PS + sub] = xp_dot<WT, EXPAND>(w1[s], ax, axd, __uint_as_float(axs), (int)axs);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                XP_WALLX(1);
+                if (lane < 2 * FS) {
+                    const int jr = (lane >> 1) * 2 * NW + wave * 2 + (lane & 1);
+                    s_g[jr] = gelu_of(__fadd_rn(s_bias[224 + jr], sum32_in_order(part + lane * DEC_PS)));
+                }
             }
-        }
-        __syncthreads();
-        XP_WALL(11);
-        if (tid < 128) {
-            int8_t q8; float d8; uint32_t s8;
-            q8_block32(s_g[tid], TI::q81, q8, d8, s8, TI::q81);
-            const uint32_t packed = xp_pack4(q8);
-            const int blk = slot * 4 + (tid >> 5);
-            if ((tid & 3) == 0) xp_put_local(G + XP_G_H + slot * 32 + (tid >> 2), etag, packed);
-            if ((tid & 31) == 0) { xp_put_local(G + XP_G_H + 1024 + blk, etag, __float_as_uint(d8)); if (TI::q81) xp_put_local(G + XP_G_H + 1152 + blk, etag, s8); }
+            __syncthreads();
+            if (!RES) XP_WALLX(1);
+            if (tid < 128) {
+                float g;
+                if constexpr (RES) g = s_g[tid];
+                else g = gelu_of(__fadd_rn(s_bias[224 + tid], sum32_in_order(s_part + tid * DEC_PS)));
+                XP_WALL(11);
+                int8_t q8; float d8; uint32_t s8;
+                q8_block32(g, TI::q81, q8, d8, s8, TI::q81);
+                const uint32_t packed = xp_pack4(q8);
+                const int blk = slot * 4 + (tid >> 5);
+                if ((tid & 3) == 0) xp_put_local(G + XP_G_H + slot * 32 + (tid >> 2), etag, packed);
+                if ((tid & 31) == 0) { xp_put_local(G + XP_G_H + 1024 + blk, etag, __float_as_uint(d8)); if (TI::q81) xp_put_local(G + XP_G_H + 1152 + blk, etag, s8); }
+            }
         }
         XP_WALL(4);
         // ================= stage E: fc2 + bias + residual (biogpt.cpp:790-795) =================
@@ -1387,6 +1410,7 @@ __device__ __forceinline__ void xp_run(const XpParams &p, unsigned char *smem, c
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            XP_WALLX(2);
             if (lane < F2R) {
                 const float4 *p4 = reinterpret_cast<const float4 *>(part + lane * DEC_PS2);
                 float sumf = 0.0f;
