@@ -413,6 +413,54 @@ def logprob_rows(rows, targets, device=0):
     return lp, am, lg
 
 
+class ScoreStats(C.Structure):
+    """struct biogpt_hip_score_stats"""
+    _fields_ = [("n_top", C.c_int32), ("rank", C.c_void_p), ("entropy", C.c_void_p), ("top_ids", C.c_void_p), ("top_lp", C.c_void_p)]
+
+
+class ScoreCmp(C.Structure):
+    """biogpt_hip_score_cmp"""
+    _fields_ = [("kl_pq", C.c_void_p), ("kl_qp", C.c_void_p), ("lp_p", C.c_void_p), ("lp_q", C.c_void_p), ("argmax_p", C.c_void_p), ("argmax_q", C.c_void_p)]
+
+
+def score_stats_device(rows, targets, n_top=0, rows_q=None, start=0, device=0):
+    """score_stats_rows_kernel (rows_q None) or score_compare_rows_kernel alone on rows held in host memory (biogpt_hip_score_stats_device): rows
+    float32 [n][n_vocab] (the row stride is n_vocab: an odd one puts consecutive rows on the four alignments), row 0 starting `start` floats behind
+    a 16-byte boundary; targets [n] (-1: none).  Returns a dict of arrays of n + 1 entries each (the last: the guard entry, 0xff bytes) -- stats: lp, argmax, logit,
+    rank, entropy, top_ids [n + 1][n_top], top_lp; compare: kl, kl_rev, lp, lp_other, argmax, argmax_other."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    n, nv = a.shape
+    b = None if rows_q is None else np.ascontiguousarray(rows_q, dtype=np.float32)
+    if b is not None and b.shape != a.shape:
+        raise BiogptError("score_stats_device: rows_q must have the shape of rows")
+    t = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+    if t.size != n:
+        raise BiogptError("score_stats_device: one target per row (%d != %d)" % (t.size, n))
+    K, g = int(n_top), n + 1
+    out = np.zeros(g * (6 if b is not None else 5 + 2 * K), dtype=np.uint32)
+    if lib().biogpt_hip_score_stats_device(int(device), a.ctypes.data, None if b is None else b.ctypes.data, n, nv, nv, int(start), t.ctypes.data, K,
+                                           out.ctypes.data) != 0:
+        raise BiogptError(_err())
+    part = lambda k, dt, w=1: out[k * g:(k + w) * g].view(dt)
+    if b is not None:
+        names = ("kl", "kl_rev", "lp", "lp_other")
+        res = {nm: part(k, np.float32) for k, nm in enumerate(names)}
+        res["argmax"], res["argmax_other"] = part(4, np.int32), part(5, np.int32)
+        return res
+    return {"lp": part(0, np.float32), "argmax": part(1, np.int32), "logit": part(2, np.float32), "rank": part(3, np.int32), "entropy": part(4, np.float32),
+            "top_ids": part(5, np.int32, K).reshape(g, K), "top_lp": part(5 + K, np.float32, K).reshape(g, K)}
+
+
+def _score_stats_arrays(n, top, rank, entropy):
+    """The request of a stats call over n rows and the arrays it fills: (ScoreStats, {rank, entropy, top_ids, top_lp})."""
+    K = 0 if top is None else int(top)
+    rows = max(int(n), 1)
+    res = {"rank": np.zeros(rows, np.int32)[:n] if rank else None, "entropy": np.zeros(rows, np.float32)[:n] if entropy else None,
+           "top_ids": np.zeros((rows, max(K, 0)), np.int32)[:n], "top_lp": np.zeros((rows, max(K, 0)), np.float32)[:n]}
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    return ScoreStats(K, ptr(res["rank"]), ptr(res["entropy"]), ptr(res["top_ids"]), ptr(res["top_lp"])), res
+
+
 def genlp_rows(rows, n_top, mode=0, top_k=40, top_p=0.9, temp=0.9, states=None, device=0):
     """The selection kernels of generation with log-probabilities on rows held in host memory (biogpt_hip_genlp_rows_device): mode 0
     genlp_greedy_rows_kernel, mode 1 sample_lp_rows_kernel drawing from states (uint32 [n][625], advanced in place).  Returns (ids int32[n],
@@ -989,6 +1037,10 @@ SYMBOLS = [
     ("biogpt_hip_sample_rows_device", C.c_int, [C.c_int, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P]),
     ("biogpt_hip_score", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("biogpt_hip_score_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    ("biogpt_hip_score_stats", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.POINTER(ScoreStats)]),
+    ("biogpt_hip_score_batch_stats", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, C.POINTER(ScoreStats)]),
+    ("biogpt_hip_score_compare", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(ScoreCmp)]),
+    ("biogpt_hip_score_stats_device", C.c_int, [C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     ("biogpt_hip_score_continuations", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_score_continuations_batch", C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     ("biogpt_hip_prefix_batch_stats", C.c_int, [_P, _P]),
@@ -2398,10 +2450,13 @@ class BiogptModel:
         return [rows[r * got:r * got + int(ol[r])].copy() for r in range(n)], secs.value
 
     # -- sequence scoring (no reference counterpart): teacher-forced causal log-probabilities --
-    def score(self, tokens, n_past=0, targets=None):
+    def score(self, tokens, n_past=0, targets=None, top=None, rank=False, entropy=False):
         """Row i sees tokens[0..i] (after n_past cached positions).  Returns (logprobs float32[n], argmax int32[n], target_logits float32[n]):
         log P(targets[i] | ...) (natural log; targets=None: the next token, the last row unscored), each row's arg-max, and the target's
-        logit.  Rows with a negative target get 0 in logprobs and target_logits."""
+        logit.  Rows with a negative target get 0 in logprobs and target_logits.
+        With top=K (0 .. 8), rank=True or entropy=True (biogpt_hip_score_stats) the result is a dict: lp, argmax, logit as above, and rank int32[n]
+        (entries before the target in its row; -1: no target), entropy float32[n] (nats), top_ids int32[n, K], top_lp float32[n, K] (the row's best K,
+        (-1, 0) where it has fewer); rank / entropy are None where not asked for."""
         toks = np.ascontiguousarray(tokens, dtype=np.int32)
         tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32)
         if tg is not None and tg.size != toks.size:
@@ -2409,14 +2464,39 @@ class BiogptModel:
         lp = np.zeros(toks.size, dtype=np.float32)
         am = np.zeros(toks.size, dtype=np.int32)
         lg = np.zeros(toks.size, dtype=np.float32)
-        if lib().biogpt_hip_score(self._h, toks.ctypes.data, toks.size, int(n_past), None if tg is None else tg.ctypes.data,
-                                  lp.ctypes.data, am.ctypes.data, lg.ctypes.data) != 0:
+        if top is None and not rank and not entropy:
+            if lib().biogpt_hip_score(self._h, toks.ctypes.data, toks.size, int(n_past), None if tg is None else tg.ctypes.data,
+                                      lp.ctypes.data, am.ctypes.data, lg.ctypes.data) != 0:
+                raise BiogptError(_err())
+            return lp, am, lg
+        st, res = _score_stats_arrays(toks.size, top, rank, entropy)
+        if lib().biogpt_hip_score_stats(self._h, toks.ctypes.data, toks.size, int(n_past), None if tg is None else tg.ctypes.data,
+                                        lp.ctypes.data, am.ctypes.data, lg.ctypes.data, C.byref(st)) != 0:
             raise BiogptError(_err())
-        return lp, am, lg
+        res.update(lp=lp, argmax=am, logit=lg)
+        return res
 
-    def score_batch(self, seqs, targets=None):
+    def compare(self, other, tokens, n_past=0, targets=None):
+        """This file (the yardstick, P) against another loaded file (Q) on the same text (biogpt_hip_score_compare): the scoring pass of score() on
+        each, the rows compared on the device.  Returns a dict of arrays [n]: kl = KL(P || Q) and kl_rev = KL(Q || P) per position (nats), lp /
+        lp_other the target's log-probability under each file (score()'s bits), argmax / argmax_other.  Both models are left as score() leaves them."""
+        toks = np.ascontiguousarray(tokens, dtype=np.int32)
+        tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32)
+        if tg is not None and tg.size != toks.size:
+            raise BiogptError("targets must have one entry per token (%d != %d)" % (tg.size, toks.size))
+        n = max(int(toks.size), 1)
+        res = {"kl": np.zeros(n, np.float32), "kl_rev": np.zeros(n, np.float32), "lp": np.zeros(n, np.float32), "lp_other": np.zeros(n, np.float32),
+               "argmax": np.zeros(n, np.int32), "argmax_other": np.zeros(n, np.int32)}
+        out = ScoreCmp(*[a.ctypes.data for a in res.values()])
+        if lib().biogpt_hip_score_compare(self._h, getattr(other, "_h", None), toks.ctypes.data, toks.size, int(n_past),
+                                          None if tg is None else tg.ctypes.data, C.byref(out)) != 0:
+            raise BiogptError(_err())
+        return {k: v[:toks.size] for k, v in res.items()}
+
+    def score_batch(self, seqs, targets=None, top=None, rank=False, entropy=False):
         """score() of several independent sequences (each from position 0, in its own K / V cache) in common passes.  targets: None, or one
-        entry per sequence -- None (next-token scoring) or that sequence's targets.  Returns a list of (logprobs, argmax, target_logits)."""
+        entry per sequence -- None (next-token scoring) or that sequence's targets.  Returns a list of (logprobs, argmax, target_logits); with
+        top / rank / entropy (biogpt_hip_score_batch_stats) a list of score()'s dicts."""
         lens = np.asarray([len(s) for s in seqs], dtype=np.int32)
         flat = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs]) if len(seqs) else np.zeros(0, np.int32))
         tg = None
@@ -2433,12 +2513,24 @@ class BiogptModel:
             tg = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, np.int32))
         n = max(int(flat.size), 1)
         lp, am, lg = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.float32)
-        if lib().biogpt_hip_score_batch(self._h, flat.ctypes.data, lens.ctypes.data, len(seqs), None if tg is None else tg.ctypes.data,
-                                        lp.ctypes.data, am.ctypes.data, lg.ctypes.data) != 0:
+        plain = top is None and not rank and not entropy
+        if plain:
+            rc = lib().biogpt_hip_score_batch(self._h, flat.ctypes.data, lens.ctypes.data, len(seqs), None if tg is None else tg.ctypes.data,
+                                              lp.ctypes.data, am.ctypes.data, lg.ctypes.data)
+        else:
+            st, res = _score_stats_arrays(n, top, rank, entropy)
+            rc = lib().biogpt_hip_score_batch_stats(self._h, flat.ctypes.data, lens.ctypes.data, len(seqs), None if tg is None else tg.ctypes.data,
+                                                    lp.ctypes.data, am.ctypes.data, lg.ctypes.data, C.byref(st))
+        if rc != 0:
             raise BiogptError(_err())
         out, off = [], 0
         for k in lens:
-            out.append((lp[off:off + k].copy(), am[off:off + k].copy(), lg[off:off + k].copy()))
+            if plain:
+                out.append((lp[off:off + k].copy(), am[off:off + k].copy(), lg[off:off + k].copy()))
+            else:
+                d = {name: None if a is None else a[off:off + k].copy() for name, a in res.items()}
+                d.update(lp=lp[off:off + k].copy(), argmax=am[off:off + k].copy(), logit=lg[off:off + k].copy())
+                out.append(d)
             off += int(k)
         return out
 

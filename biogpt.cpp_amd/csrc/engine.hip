@@ -52,6 +52,7 @@
 #include "kernels_sample.hip.h"
 #include "kernels_wide_sample.hip.h"
 #include "kernels_genlp.hip.h"
+#include "kernels_score_stats.hip.h"
 #include "kernels_rules.hip.h"
 #include "kernels_trie.hip.h"
 #include "kernels_contrast.hip.h"
@@ -323,6 +324,9 @@ struct biogpt_hip_ctx {
     int32_t *sc_tgt = nullptr;
     uint32_t *sc_out = nullptr;
     size_t sc_cap = 0;
+    // what biogpt_hip_score*_stats / biogpt_hip_score_compare add to them (kernels_score_stats.hip.h): ss_cap words, laid out per call
+    uint32_t *ss_out = nullptr;
+    size_t ss_cap = 0;
     int32_t pfxb_stats[4] = {0, 0, 0, 0};   // the last successful biogpt_hip_score_continuations_batch: prefix columns, continuation columns, passes, passes on attn_runs_kernel
     // hidden states / embeddings (biogpt_hip_hidden, biogpt_hip_embed_batch): one block that holds the call's output rows and what the call needs beside them
     uint8_t *emb_buf = nullptr;
@@ -2488,7 +2492,7 @@ void destroy(biogpt_hip_ctx *c) {
     if (c->mbox_ctr) (void)hipFree(c->mbox_ctr);
     if (c->seq_dev) (void)hipFree(c->seq_dev);
     plain_graph_end(c);
-    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf, (void *)c->genlp_buf, (void *)c->queue_buf, (void *)c->bqueue_buf, (void *)c->queue_req_buf}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->bk, (void *)c->bv, (void *)c->seq, (void *)c->seq_gen, (void *)c->cols, (void *)c->sc_tgt, (void *)c->sc_out, (void *)c->ss_out, (void *)c->emb_buf, (void *)c->sample_ctl, (void *)c->rules_buf, (void *)c->trie_ctl, (void *)c->bbatch_buf, (void *)c->contrast_buf, (void *)c->contrast_h, (void *)c->lookup_buf, (void *)c->genlp_buf, (void *)c->queue_buf, (void *)c->bqueue_buf, (void *)c->queue_req_buf}) if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -4099,11 +4103,59 @@ static bool enqueue_logprob(biogpt_hip_ctx *c, int m, size_t flat0, size_t total
     return true;
 }
 
-// one copy of the outputs back, then into the caller's arrays (argmax_out / logit_out may be NULL)
-static int score_finish(biogpt_hip_ctx *c, size_t total, float *logprob_out, int32_t *argmax_out, float *logit_out) {
-    std::vector<uint32_t> h(3 * total);
+// ---- what the stats calls add (kernels_score_stats.hip.h): ss_out laid out [rank | entropy | top_ids [total][n_top] | top_lp [total][n_top]] for this call ----
+using ScoreStats = struct biogpt_hip_score_stats;
+static bool check_score_stats(const ScoreStats *st) {
+    if (!st) BG_FAIL(false, "null argument: stats");
+    if (st->n_top < 0 || st->n_top > bgk::GENLP_MAX_TOP) BG_FAIL(false, "stats.n_top must be in [0, %d] (got %d)", bgk::GENLP_MAX_TOP, st->n_top);
+    if (st->n_top > 0 && !st->top_ids) BG_FAIL(false, "null argument: stats.top_ids (n_top = %d)", st->n_top);
+    if (st->n_top > 0 && !st->top_lp) BG_FAIL(false, "null argument: stats.top_lp (n_top = %d)", st->n_top);
+    return true;
+}
+static bool ensure_stats_words(biogpt_hip_ctx *c, size_t words) {
+    if (words <= c->ss_cap) return true;
+    if (c->ss_out) (void)hipFree(c->ss_out);
+    c->ss_out = nullptr; c->ss_cap = 0;
+    HIP_TRY(false, hipMalloc(&c->ss_out, words * 4));
+    c->ss_cap = words;
+    return true;
+}
+static size_t score_stats_words(size_t total, const ScoreStats *st) { return total * (2 + 2 * (size_t)st->n_top); }
+
+// enqueue_logprob with score_stats_rows_kernel: the same rows, the same three outputs, and the stats of flat rows [flat0, flat0 + m)
+static bool enqueue_score_stats(biogpt_hip_ctx *c, int m, size_t flat0, size_t total, const ScoreStats *st) {
+    const int V = c->hp.n_vocab;
+    float *const lp = reinterpret_cast<float *>(c->sc_out) + flat0;
+    int32_t *const am = reinterpret_cast<int32_t *>(c->sc_out + total) + flat0;
+    float *const lg = reinterpret_cast<float *>(c->sc_out + 2 * total) + flat0;
+    const size_t K = (size_t)st->n_top;
+    bgk::ScoreStatsOut o{};
+    o.n_top = st->n_top;
+    o.rank = st->rank ? reinterpret_cast<int32_t *>(c->ss_out) + flat0 : nullptr;
+    o.entropy = st->entropy ? reinterpret_cast<float *>(c->ss_out + total) + flat0 : nullptr;
+    o.top_ids = reinterpret_cast<int32_t *>(c->ss_out + 2 * total) + flat0 * K;
+    o.top_lp = reinterpret_cast<float *>(c->ss_out + (2 + K) * total) + flat0 * K;
+    hipLaunchKernelGGL(bgk::score_stats_rows_kernel, dim3(m), dim3(bgk::LP_THREADS), 0, c->stream, c->logits_all, V, V, c->sc_tgt + flat0, lp, am, lg, o);
+    HIP_TRY(false, hipGetLastError());
+    return true;
+}
+// the row launch behind a scoring pass: the plain kernel, or the stats kernel where the call asked for stats
+static bool enqueue_score_rows(biogpt_hip_ctx *c, int m, size_t flat0, size_t total, const ScoreStats *st) {
+    return st ? enqueue_score_stats(c, m, flat0, total, st) : enqueue_logprob(c, m, flat0, total);
+}
+
+// one copy of the outputs back, then into the caller's arrays (argmax_out / logit_out may be NULL); with st, the stats block behind it
+static int score_finish(biogpt_hip_ctx *c, size_t total, float *logprob_out, int32_t *argmax_out, float *logit_out, const ScoreStats *st = nullptr) {
+    std::vector<uint32_t> h(3 * total), hs(st ? score_stats_words(total, st) : 0);
     HIP_TRY(-2, hipMemcpyAsync(h.data(), c->sc_out, 3 * total * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!hs.empty()) HIP_TRY(-2, hipMemcpyAsync(hs.data(), c->ss_out, hs.size() * 4, hipMemcpyDeviceToHost, c->stream));
     if (!wait_stream(c)) return -2;
+    if (st) {
+        const size_t K = (size_t)st->n_top;
+        if (st->rank) std::memcpy(st->rank, hs.data(), total * 4);
+        if (st->entropy) std::memcpy(st->entropy, hs.data() + total, total * 4);
+        if (K) { std::memcpy(st->top_ids, hs.data() + 2 * total, total * K * 4); std::memcpy(st->top_lp, hs.data() + (2 + K) * total, total * K * 4); }
+    }
     std::memcpy(logprob_out, h.data(), total * 4);
     if (argmax_out) std::memcpy(argmax_out, h.data() + total, total * 4);
     if (logit_out) std::memcpy(logit_out, h.data() + 2 * total, total * 4);
@@ -4129,9 +4181,10 @@ bool causal_passes(biogpt_hip_ctx *ctx, const int32_t *tokens, int n, int n_past
 }
 
 static int score_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int32_t n_past, const int32_t *targets,
-                      float *logprob_out, int32_t *argmax_out, float *logit_out) {
+                      float *logprob_out, int32_t *argmax_out, float *logit_out, const ScoreStats *st = nullptr, bool with_stats = false) {
     XpCallScope xp_scope(ctx);
     clear_error();
+    if (with_stats && !check_score_stats(st)) return -1;
     if (!check_eval_args(ctx, tokens, n, n_past)) return -1;
     if (!logprob_out) BG_FAIL(-1, "null logprob buffer");
     if (!check_targets(ctx, targets, n, 0)) return -1;
@@ -4140,21 +4193,23 @@ static int score_once(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n, int
     const int max_cols = causal_pass_cols(ctx, n);
     if (!max_cols) return -2;
     if (!ensure_logits_rows(ctx, (size_t)std::min(max_cols, (int)n)) || !score_setup(ctx, tokens, &n, 1, targets, (size_t)n)) return -2;
+    if (st && !ensure_stats_words(ctx, score_stats_words((size_t)n, st))) return -2;
     const size_t V = (size_t)ctx->hp.n_vocab;
     const bool ok = causal_passes(ctx, tokens, n, n_past, max_cols, [&](int at, int m) -> bool {
-        if (!enqueue_forward(ctx, ForwardPass::scored(m, n_past + at + m)) || !enqueue_logprob(ctx, m, (size_t)at, (size_t)n)) return false;
+        if (!enqueue_forward(ctx, ForwardPass::scored(m, n_past + at + m)) || !enqueue_score_rows(ctx, m, (size_t)at, (size_t)n, st)) return false;
         if (at + m == n)   // the last row is what biogpt_hip_read_logits / biogpt_hip_logits_device return afterwards
             HIP_TRY(false, hipMemcpyAsync(ctx->logits, ctx->logits_all + (size_t)(m - 1) * V, V * 4, hipMemcpyDeviceToDevice, ctx->stream));
         return true;
     });
     if (!ok) return -2;
-    return score_finish(ctx, (size_t)n, logprob_out, argmax_out, logit_out);
+    return score_finish(ctx, (size_t)n, logprob_out, argmax_out, logit_out, st);
 }
 
 static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
-                            float *logprob_out, int32_t *argmax_out, float *logit_out) {
+                            float *logprob_out, int32_t *argmax_out, float *logit_out, const ScoreStats *st = nullptr, bool with_stats = false) {
     XpCallScope xp_scope(ctx);
     clear_error();
+    if (with_stats && !check_score_stats(st)) return -1;
     if (!ctx) BG_FAIL(-1, "null context");
     if (!seqs || !lens || !logprob_out) BG_FAIL(-1, "null argument");
     if (!ctx->ready) BG_FAIL(-1, "model has no tensors loaded (empty model): cannot evaluate");
@@ -4175,11 +4230,12 @@ static int score_batch_once(biogpt_hip_ctx *ctx, const int32_t *seqs, const int3
     if (!ensure_seq_caches(ctx, n_seqs)) return -2;
     if ((long)std::min(max_cols, total) >= MFMA_MIN_PASS_COLS && !ensure_tile_images(ctx)) return -2;
     if (!ensure_logits_rows(ctx, std::min(max_cols, total)) || !score_setup(ctx, seqs, lens, n_seqs, targets, total)) return -2;
+    if (st && !ensure_stats_words(ctx, score_stats_words(total, st))) return -2;
     if (!pack_column_passes(ctx, seqs, lens, n_seqs, 1, [&](int n_cols, int t_max, size_t flat0) {
-            return enqueue_forward(ctx, ForwardPass::packed_scored(n_cols, t_max)) && enqueue_logprob(ctx, n_cols, flat0, total);
+            return enqueue_forward(ctx, ForwardPass::packed_scored(n_cols, t_max)) && enqueue_score_rows(ctx, n_cols, flat0, total, st);
         }))
         return -2;
-    return score_finish(ctx, total, logprob_out, argmax_out, logit_out);
+    return score_finish(ctx, total, logprob_out, argmax_out, logit_out, st);
 }
 
 int biogpt_hip_score(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, const int32_t *targets,
@@ -4189,6 +4245,97 @@ int biogpt_hip_score(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_token
 int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
                            float *logprob_out, int32_t *argmax_out, float *logit_out) {
     return with_xpipe_retry(ctx, 0, [&] { return score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out); });
+}
+
+int biogpt_hip_score_stats(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, const int32_t *targets,
+                           float *logprob_out, int32_t *argmax_out, float *logit_out, const struct biogpt_hip_score_stats *stats) {
+    return with_xpipe_retry(ctx, n_past, [&] { return score_once(ctx, tokens, n_tokens, n_past, targets, logprob_out, argmax_out, logit_out, stats, true); });
+}
+int biogpt_hip_score_batch_stats(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
+                                 float *logprob_out, int32_t *argmax_out, float *logit_out, const struct biogpt_hip_score_stats *stats) {
+    return with_xpipe_retry(ctx, 0, [&] { return score_batch_once(ctx, seqs, lens, n_seqs, targets, logprob_out, argmax_out, logit_out, stats, true); });
+}
+
+// ---- two files on the same text: biogpt_hip_score's passes on each context in turn, score_compare_rows_kernel over the two contexts' rows ------------
+// Per pass: ctx_p's columns on ctx_p's stream; ctx_q's stream waits for them, runs its own pass and the compare kernel over both logits_all; ctx_p's next
+// pass waits for that kernel (it reads ctx_p's rows).  So the two contexts' launches never run beside each other: whichever holds the device's pipeline
+// slot keeps it for the call, the other takes the launches it takes beside a holder.  Outputs: ctx_q's ss_out, [kl_pq | kl_qp | lp_p | lp_q | argmax_p |
+// argmax_q], n words each; the targets: ctx_q's sc_tgt.
+struct CmpEvents {
+    hipEvent_t p = nullptr, q = nullptr;
+    bool make() {
+        HIP_TRY(false, hipEventCreateWithFlags(&p, hipEventDisableTiming));
+        HIP_TRY(false, hipEventCreateWithFlags(&q, hipEventDisableTiming));
+        return true;
+    }
+    ~CmpEvents() {
+        if (p) (void)hipEventDestroy(p);
+        if (q) (void)hipEventDestroy(q);
+    }
+};
+static int score_compare_once(biogpt_hip_ctx *cp, biogpt_hip_ctx *cq, const int32_t *tokens, int32_t n, int32_t n_past, const int32_t *targets,
+                              const biogpt_hip_score_cmp *out) {
+    XpCallScope scope_p(cp), scope_q(cq);
+    clear_error();
+    if (cp->device != cq->device) BG_FAIL(-1, "ctx_p is on device %d and ctx_q on device %d: the compare kernel reads both contexts' rows", cp->device, cq->device);
+    if (cp->hp.n_vocab != cq->hp.n_vocab) BG_FAIL(-1, "n_vocab differs: %d (ctx_p) and %d (ctx_q)", cp->hp.n_vocab, cq->hp.n_vocab);
+    for (biogpt_hip_ctx *c : {cp, cq}) {
+        if (!check_eval_args(c, tokens, n, n_past)) return -1;      // (an open queue session among them)
+        if (!check_targets(c, targets, n, 0)) return -1;
+    }
+    HIP_TRY(-2, hipSetDevice(cq->device));
+    int max_cols = n;
+    for (biogpt_hip_ctx *c : {cp, cq}) {
+        if (!resident_stop(c)) return -2;
+        disarm_lineage(c);
+        const int mc = causal_pass_cols(c, n);
+        if (!mc) return -2;
+        max_cols = std::min(max_cols, mc);
+    }
+    for (biogpt_hip_ctx *c : {cp, cq})
+        if (!ensure_logits_rows(c, (size_t)max_cols)) return -2;
+    const size_t N = (size_t)n, V = (size_t)cq->hp.n_vocab;
+    if (!score_setup(cq, tokens, &n, 1, targets, N) || !ensure_stats_words(cq, 6 * N)) return -2;
+    CmpEvents ev;
+    if (!ev.make()) return -2;
+    for (int at = 0; at < n;) {
+        const int m = std::min(max_cols, n - at);
+        for (biogpt_hip_ctx *c : {cp, cq}) {
+            if (c == cp && at > 0) HIP_TRY(-2, hipStreamWaitEvent(cp->stream, ev.q, 0));
+            if (c == cq) HIP_TRY(-2, hipStreamWaitEvent(cq->stream, ev.p, 0));
+            if (!upload_state(c, tokens + at, m, n_past + at, m > 1 ? 1 : 0) || !enqueue_forward(c, ForwardPass::scored(m, n_past + at + m))) return -2;
+            if (at + m == n)   // the last row is what biogpt_hip_read_logits / biogpt_hip_logits_device return afterwards
+                HIP_TRY(-2, hipMemcpyAsync(c->logits, c->logits_all + (size_t)(m - 1) * V, V * 4, hipMemcpyDeviceToDevice, c->stream));
+            if (c == cp) HIP_TRY(-2, hipEventRecord(ev.p, cp->stream));
+        }
+        bgk::ScoreCmpOut o{};
+        float *const f = reinterpret_cast<float *>(cq->ss_out) + at;
+        o.kl_pq = f; o.kl_qp = f + N; o.lp_p = f + 2 * N; o.lp_q = f + 3 * N;
+        o.argmax_p = reinterpret_cast<int32_t *>(f + 4 * N); o.argmax_q = reinterpret_cast<int32_t *>(f + 5 * N);
+        hipLaunchKernelGGL(bgk::score_compare_rows_kernel, dim3(m), dim3(bgk::LP_THREADS), 0, cq->stream, cp->logits_all, (int)V, cq->logits_all, (int)V, (int)V,
+                           cq->sc_tgt + at, o);
+        HIP_TRY(-2, hipGetLastError());
+        HIP_TRY(-2, hipEventRecord(ev.q, cq->stream));
+        at += m;
+    }
+    std::vector<uint32_t> h(6 * N);
+    HIP_TRY(-2, hipMemcpyAsync(h.data(), cq->ss_out, 6 * N * 4, hipMemcpyDeviceToHost, cq->stream));
+    if (!wait_stream(cq) || !wait_stream(cp)) return -2;      // (ctx_p's stream ran dry before ctx_q's last pass began)
+    void *const dst[6] = {out->kl_pq, out->kl_qp, out->lp_p, out->lp_q, out->argmax_p, out->argmax_q};
+    for (int k = 0; k < 6; k++)
+        if (dst[k]) std::memcpy(dst[k], h.data() + (size_t)k * N, N * 4);
+    return 0;
+}
+int biogpt_hip_score_compare(biogpt_hip_ctx *ctx_p, biogpt_hip_ctx *ctx_q, const int32_t *tokens, int32_t n_tokens, int32_t n_past, const int32_t *targets,
+                             const biogpt_hip_score_cmp *out) {
+    clear_error();      // (what needs no look into a context comes first)
+    if (!out) BG_FAIL(-1, "null argument: out");
+    if (!out->kl_pq) BG_FAIL(-1, "null argument: out.kl_pq");
+    if (!ctx_p || !ctx_q) BG_FAIL(-1, "null context: %s", !ctx_p ? "ctx_p" : "ctx_q");
+    if (ctx_p == ctx_q) BG_FAIL(-1, "ctx_p and ctx_q are the same context: a file is compared with a second load of itself");
+    return with_xpipe_retry(ctx_p, n_past, [&] {
+        return with_xpipe_retry(ctx_q, n_past, [&] { return score_compare_once(ctx_p, ctx_q, tokens, n_tokens, n_past, targets, out); });
+    });
 }
 
 // ---- continuations of shared prefixes: each prefix once, read in place by the columns of its continuations -----------------------------------

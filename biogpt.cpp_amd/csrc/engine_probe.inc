@@ -788,6 +788,54 @@ int biogpt_hip_logprob_rows_device(int device, const float *rows, int32_t n_rows
     return 0;
 }
 
+// score_stats_rows_kernel (rows_q null) or score_compare_rows_kernel over rows held in host memory (tests of the kernels themselves): row r starts
+// start + r * ld floats behind a 16-byte boundary.  The outputs are arrays of n_rows + 1 entries one after another -- the last entry of each is never
+// written -- and come back whole.
+int biogpt_hip_score_stats_device(int device, const float *rows, const float *rows_q, int32_t n_rows, int32_t ld, int32_t n_vocab, int32_t start,
+                                  const int32_t *targets, int32_t n_top, uint32_t *out) {
+    clear_error();
+    if (!rows) BG_FAIL(-1, "rows is NULL");
+    if (!targets) BG_FAIL(-1, "targets is NULL");
+    if (!out) BG_FAIL(-1, "out is NULL");
+    if (n_rows < 1 || n_rows > 4096) BG_FAIL(-1, "n_rows must be in [1, 4096]");
+    if (n_vocab < 1 || n_vocab > (1 << 20)) BG_FAIL(-1, "n_vocab must be in [1, %d]", 1 << 20);
+    if (ld < n_vocab || ld > (1 << 20)) BG_FAIL(-1, "ld must be in [n_vocab, %d]", 1 << 20);
+    if (start < 0 || start > 3) BG_FAIL(-1, "start must be in [0, 3]");
+    if (n_top < 0 || n_top > bgk::GENLP_MAX_TOP || (rows_q && n_top)) BG_FAIL(-1, "n_top must be in [0, %d], and 0 with rows_q", bgk::GENLP_MAX_TOP);
+    for (int r = 0; r < n_rows; r++)
+        if (targets[r] < -1 || targets[r] >= n_vocab) BG_FAIL(-1, "targets[%d] = %d out of range: must be in [0, %d), or -1 for none", r, targets[r], n_vocab);
+    HIP_TRY(-2, hipSetDevice(device));
+    const size_t n = (size_t)n_rows, g = n + 1, K = (size_t)n_top, n_in = (size_t)start + n * (size_t)ld;
+    auto shifted = [&](const float *src) {
+        std::vector<float> v(n_in, 0.0f);
+        std::memcpy(v.data() + start, src, n * (size_t)ld * 4);
+        return v;
+    };
+    ProbeImage im;      // [rows | the second file's rows | targets | the outputs, n_rows + 1 entries each]
+    const ProbePart o_p = im.own(shifted(rows)), o_q = rows_q ? im.own(shifted(rows_q)) : ProbePart{}, o_tg = im.in(targets, n * 4);
+    const size_t words = g * (rows_q ? 6 : 5 + 2 * K);
+    const ProbePart o_out = im.out(words * 4);
+    if (!im.upload()) return -2;
+    uint32_t *const w = im.at<uint32_t>(o_out);
+    if (rows_q) {
+        bgk::ScoreCmpOut o{};
+        o.kl_pq = reinterpret_cast<float *>(w); o.kl_qp = reinterpret_cast<float *>(w + g); o.lp_p = reinterpret_cast<float *>(w + 2 * g);
+        o.lp_q = reinterpret_cast<float *>(w + 3 * g); o.argmax_p = reinterpret_cast<int32_t *>(w + 4 * g); o.argmax_q = reinterpret_cast<int32_t *>(w + 5 * g);
+        hipLaunchKernelGGL(bgk::score_compare_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, im.at<const float>(o_p) + start, ld,
+                           im.at<const float>(o_q) + start, ld, n_vocab, im.at<const int32_t>(o_tg), o);
+    } else {
+        bgk::ScoreStatsOut o{};
+        o.n_top = n_top;
+        o.rank = reinterpret_cast<int32_t *>(w + 3 * g); o.entropy = reinterpret_cast<float *>(w + 4 * g);
+        o.top_ids = reinterpret_cast<int32_t *>(w + 5 * g); o.top_lp = reinterpret_cast<float *>(w + (5 + K) * g);
+        hipLaunchKernelGGL(bgk::score_stats_rows_kernel, dim3(n_rows), dim3(bgk::LP_THREADS), 0, 0, im.at<const float>(o_p) + start, ld, n_vocab,
+                           im.at<const int32_t>(o_tg), reinterpret_cast<float *>(w), reinterpret_cast<int32_t *>(w + g), reinterpret_cast<float *>(w + 2 * g), o);
+    }
+    HIP_TRY(-2, hipGetLastError());
+    HIP_TRY(-2, hipDeviceSynchronize());
+    return im.read(o_out, out) ? 0 : -2;
+}
+
 // what the beam entries below check of a row read as log-probabilities: the row kernel's precondition (the rules' argument check in a call)
 static bool beam_given_rows_ok(const float *rows, size_t n_rows, int n_vocab, int K, const char *what) {
     for (size_t r = 0; r < n_rows; r++) {

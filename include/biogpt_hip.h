@@ -967,6 +967,60 @@ int biogpt_hip_score(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_token
 int biogpt_hip_score_batch(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
                            float *logprob_out, int32_t *argmax_out, float *logit_out);
 
+/* The distribution at every scored position.  biogpt_hip_score_stats / biogpt_hip_score_batch_stats are biogpt_hip_score / biogpt_hip_score_batch -- the
+ * same passes on whatever chain the context has, the same three outputs bit for bit, the same K / V rows, device row and return value -- with
+ * score_stats_rows_kernel (csrc/kernels_score_stats.hip.h) behind each pass in place of the plain row kernel.  Per row, in the flat layout of the outputs:
+ *   top_ids / top_lp [rows][n_top]  the row's first n_top entries, value descending, equal values lower id first, a NaN never; each with
+ *                                   (l[id] - m) - log(S) as biogpt_hip_generate_greedy_batch_lp writes it (the same bits for the same row); an entry the
+ *                                   row does not have is (-1, 0).  n_top in [0, 8]; both arrays are read with n_top > 0 only
+ *   rank [rows]                     how many entries come before the target in that order (0: the target is the arg-max); -1 for a row without a
+ *                                   target or whose target logit is NaN.  May be NULL
+ *   entropy [rows]                  H = log(S) - N / S in nats, S = sum_v exp(l[v] - m), N = sum_v exp(l[v] - m) (l[v] - m), every term and sum in double,
+ *                                   rounded once; entries at -inf contribute 0, a row with a NaN or +inf gives NaN.  May be NULL
+ * Argument errors (-1, before any launch): those of the plain call, a NULL stats, n_top outside [0, 8], top_ids or top_lp NULL with n_top > 0.
+ * (The struct shares its name with the call, so it is named by its tag: `struct biogpt_hip_score_stats`.) */
+struct biogpt_hip_score_stats {
+    int32_t n_top;
+    int32_t *rank;
+    float *entropy;
+    int32_t *top_ids;
+    float *top_lp;
+};
+int biogpt_hip_score_stats(biogpt_hip_ctx *ctx, const int32_t *tokens, int32_t n_tokens, int32_t n_past, const int32_t *targets,
+                           float *logprob_out, int32_t *argmax_out, float *logit_out, const struct biogpt_hip_score_stats *stats);
+int biogpt_hip_score_batch_stats(biogpt_hip_ctx *ctx, const int32_t *seqs, const int32_t *lens, int32_t n_seqs, const int32_t *targets,
+                                 float *logprob_out, int32_t *argmax_out, float *logit_out, const struct biogpt_hip_score_stats *stats);
+
+/* How far apart two loaded files are as distributions on the same text: the scoring pass of biogpt_hip_score(tokens, n_past, targets) on ctx_p (the
+ * yardstick) and then on ctx_q, each on its own stream (ctx_q's waits for ctx_p's pass), and score_compare_rows_kernel on ctx_q's stream over the two
+ * contexts' logits rows -- no row leaves the device.  Per row i, with P / Q the two softmax distributions (n_tokens entries each; all but kl_pq may be NULL):
+ *   kl_pq = KL(P || Q) = A / S_p - log S_p + log S_q,  A = sum_v e_p,v ((p_v - m_p) - (q_v - m_q)),  e_p,v = exp(p_v - m_p): terms and sums in double, rounded
+ *           once (nats); kl_qp = KL(Q || P) likewise.  A term of weight 0 is skipped, a positive weight against -inf in the other row gives +inf, a NaN
+ *           in either row gives NaN.  Two rows with the same bits give exactly 0
+ *   lp_p, lp_q            the target's log-probability under each file: the bits biogpt_hip_score gives that file
+ *   argmax_p, argmax_q    each row's arg-max
+ * Passes of at most BIOGPT_HIP_PROMPT_COLS columns (the smaller of the two contexts' pass widths).  Each context is left as biogpt_hip_score leaves it.
+ * Refused with -1 before any launch: a NULL out or out->kl_pq, a NULL context, ctx_p == ctx_q, contexts on different devices, different n_vocab, an open
+ * queue session on either, and biogpt_hip_score's own argument errors on either. */
+typedef struct biogpt_hip_score_cmp {
+    float *kl_pq;
+    float *kl_qp;
+    float *lp_p;
+    float *lp_q;
+    int32_t *argmax_p;
+    int32_t *argmax_q;
+} biogpt_hip_score_cmp;
+int biogpt_hip_score_compare(biogpt_hip_ctx *ctx_p, biogpt_hip_ctx *ctx_q, const int32_t *tokens, int32_t n_tokens, int32_t n_past, const int32_t *targets,
+                             const biogpt_hip_score_cmp *out);
+
+/* score_stats_rows_kernel (rows_q NULL) or score_compare_rows_kernel (rows_q: the second file's rows) alone, over n_rows <= 4096 rows of n_vocab floats
+ * held in host memory with row stride ld >= n_vocab; on the device row 0 starts `start` in [0, 3] floats behind a 16-byte boundary, so with ld every
+ * alignment can be asked for.  targets[r] in [-1, n_vocab); n_top in [0, 8] (stats only).  out comes back WHOLE as allocated and preset to 0xff bytes, arrays
+ * of n_rows + 1 entries (the last: guard) one after another -- stats: lp, argmax, logit, rank, entropy, top_ids [n_rows + 1][n_top], top_lp likewise,
+ * (n_rows + 1) x (5 + 2 n_top) words; compare: kl_pq, kl_qp, lp_p, lp_q, argmax_p, argmax_q, (n_rows + 1) x 6 words.  For tests of the kernels themselves. */
+int biogpt_hip_score_stats_device(int device, const float *rows, const float *rows_q, int32_t n_rows, int32_t ld, int32_t n_vocab, int32_t start,
+                                  const int32_t *targets, int32_t n_top, uint32_t *out);
+
 /* Many continuations of ONE prefix (multiple choice, label ranking, reranking hypotheses of one prompt): conts = the n_conts continuations
  * concatenated, cont_lens[n_conts] their lengths; the outputs use the flat layout of conts.  For continuation c and i in [0, cont_lens[c]):
  * logprob_out = log P(cont_c[i] | prefix, cont_c[0..i)), logit_out = that token's logit, argmax_out = the row's arg-max -- rows
